@@ -11,6 +11,11 @@ quoted on; configs[1] — 500x4, single tangent — is latency-bound and is repo
 N>1 GPUs: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`; tangent
 columns shard across ranks (32 per GPU, weak scaling), every rank runs the primal redundantly, one
 RCCL all-gather per step assembles the P x (32·N) aggregate-tangent block on every rank.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (with --dump-outputs DIR it first
+writes the last timed step's outputs, DIR/agg.npy and DIR/dagg.npy). Everything else it can measure — the roofline
+from extra untimed steps, the output check against the CPU oracle, the CPU baseline, the other BASELINE configs in
+`extra` and, on N > 1 GPUs, the device-group run — comes with --full.
 """
 from __future__ import annotations
 
@@ -319,15 +324,32 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="ks_2000x11_T300_N32", choices=sorted(WORKLOADS))
     ap.add_argument("--tangents", type=int, default=None, help="override the per-GPU tangent batch width")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline (live per-sweep times of extra untimed steps), the output check against "
+                         "the CPU oracle, the CPU baseline, every side measurement (`extra`) and, with N > 1 GPUs, the device-group run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the output check and the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out `extra` (and the device-group run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (agg.npy: the aggregate path, dagg.npy: its tangent columns, float64)")
     ap.add_argument("--split", action="store_true", help="hank_primal + hank_jvp as two calls instead of the dual pass hank_primal_jvp")
     ap.add_argument("--mode", default="ranks", choices=("ranks", "devicegroup"),
                     help="ranks: one process per GPU + one RCCL all-gather per step (the driver's contract); "
                          "devicegroup: ONE process, one context per GPU (hank_create_on), no collective")
     ap.add_argument("--stand-in", action="store_true",
                     help="CPU test of the launcher and of the distributed plumbing: gloo, a stand-in step, no GPU, no product code")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(out_dir, agg, dagg):
+    """what a caller of the timed path receives from one step: the aggregate path (P,) and its tangent columns (P, columns),
+    float64 (P x 32 doubles per GPU: far below any size cap)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "agg.npy", np.ascontiguousarray(agg, dtype=np.float64))
+    np.save(d / "dagg.npy", np.ascontiguousarray(dagg, dtype=np.float64))
 
 
 def _free_port():
@@ -487,6 +509,8 @@ def devicegroup_main(args):
     el = time.perf_counter() - t0
     for hb in blocks:
         hb.check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bufs[0][2].cpu().numpy(), d_all.cpu().numpy().reshape((P, len(blocks) * N), order="F"))
     out = {"metric": "sequence-space JVPs/sec (household block: BackwardIteration+ForwardIteration+aggregation, Krusell-Smith T=300)",
            "value": args.gpus * N * args.steps / el, "unit": "JVPs/s", "n_gpus": len(blocks), "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
@@ -505,6 +529,9 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse_args(argv)
     launcher_env = "RANK" in os.environ and "WORLD_SIZE" in os.environ
+    if args.dump_outputs and not os.path.isabs(args.dump_outputs):
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv = argv + ["--dump-outputs", args.dump_outputs]     # the ranks below run from the repository root
     if args.mode == "ranks" and args.gpus > 1 and not launcher_env:
         raise SystemExit(self_launch(args, argv))        # before anything here touches a GPU
     if args.stand_in:
@@ -600,11 +627,16 @@ def main(argv=None):
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, as the caller holds them: the aggregate path and the tangent columns (every rank's,
+        # after the all-gather)
+        dagg = (d_all if use_dist else d_dagg).cpu().numpy().reshape((P, world * N), order="F")
+        dump_outputs(args.dump_outputs, d_agg.cpu().numpy(), dagg)
 
-    # live per-sweep device times over a few extra (untimed) steps, for the roofline object
+    # live per-sweep device times over a few extra (untimed) steps, for the roofline object (--full)
     reps = 5
     acc = {k: 0.0 for k in sweeps}
-    for _ in range(reps):
+    for _ in range(reps if args.full else 0):
         step()
         tmi = hb.last_timings()
         for k in acc:
@@ -615,55 +647,56 @@ def main(argv=None):
     if rank == 0:
         total_jvps = world * N * args.steps
         ms_per_step = 1e3 * el / args.steps
-        # dominant kernel: the per-period tangent kernels (k_tan_back / k_tan_fwd). One launch moves
-        # the policy partials of ONE period for N directions: G*8*N algorithmic bytes
-        # (B_alg = 2*P*G*8*(1+N) per batch = G*8 bytes per (sweep, period, direction)).
-        persistent = split_keys and launches.get("tangent_forward", P) < P
-        wide = hb.info()["last_tangent_family_name"] == "on-chip-wide"
-        if wide:
-            # the on-chip wide sweeps (csrc/hank_wide.h): one workgroup per direction, ONE launch per sweep; a launch moves the policy
-            # partials of every period and direction once (written by k_wide_back, read by k_wide_fwd): P*G*8*N bytes. The Float64
-            # sweeps run before them as XCD-local persistent sweeps and are part of ms_per_step.
-            dom = max(("tangent_backward", "tangent_forward"), key=lambda k: acc[k])
-            kname = {"tangent_backward": "k_wide_back", "tangent_forward": "k_wide_fwd"}[dom]
-            bytes_per_launch = P * G * 8 * N
-        elif persistent and not args.split and acc.get("tangent_backward", 0.0) < 0.05:
-            # the persistent Dual pass: ONE launch per sweep, value and partials together in both (k_xdual_back writes the policy
-            # and the policy partials of every period, k_xfwd<D, true> reads them): P*G*8*(1+N) algorithmic bytes per launch
-            dom = max(("primal_backward", "tangent_forward"), key=lambda k: acc[k])
-            kname = {"primal_backward": "k_xdual_back", "tangent_forward": "k_xfwd"}[dom]
-            bytes_per_launch = P * G * 8 * (1 + N)
-        elif persistent:
-            # XCD-local persistent sweeps at a recorded primal: ONE launch carries a whole sweep (P periods). The kernels that
-            # move the algorithmic bytes are the tangent sweeps (the policy-partials sequence: written once by k_xtan_back, read
-            # once by k_xfwd): P*G*8*N_pass per launch; a batch wider than 32 runs as ceil(N/32) passes. The Float64
-            # sweeps move P*G*8 bytes each and are latency-bound: reported beside, not hidden.
-            dom = max(("tangent_backward", "tangent_forward"), key=lambda k: acc[k])
-            kname = {"tangent_backward": "k_xtan_back", "tangent_forward": "k_xfwd"}[dom]
-            bytes_per_launch = P * G * 8 * N / launches[dom]
-        elif split_keys:
-            dom = max(("tangent_backward", "tangent_forward"), key=lambda k: acc[k])
-            kname = {"tangent_backward": "k_tan_back", "tangent_forward": "k_tan_fwd"}[dom]
-            bytes_per_launch = G * 8 * N
-        else:   # a dual-sweep launch advances the primal and the N tangents by one period: G*8*(1+N)
-            dom = max(("dual_backward", "dual_forward"), key=lambda k: acc[k])
-            kname = {"dual_backward": "k_fused_back", "dual_forward": "k_fused_fwd"}[dom]
-            bytes_per_launch = G * 8 * (1 + N)
-        avg_launch_s = 1e-3 * acc[dom] / launches[dom]
-        achieved = bytes_per_launch / avg_launch_s / 1e9
-        # HBM bytes per launch of that kernel from the committed rocprofv3 PMC passes (FETCH_SIZE and
-        # WRITE_SIZE in separate runs, profiles/r01b_pmc_*): a profile artefact, not measured live
-        pmc, traffic, traffic_stale = None, None, None
-        pmc_file = ROOT / "profiles" / "pmc_latest.json"
-        if pmc_file.exists() and N == WORKLOADS[args.workload]["N"]:
-            try:
-                rec = json.loads(pmc_file.read_text()).get(args.workload, {})
-                pmc = rec.get(kname)
-                traffic = pmc["hbm_bytes"] if pmc else None
-                # the counters belong to the kernel sources they were collected on: a different hash = re-profile
-                traffic_stale = (rec.get("kernel_source_sha16") != kernel_source_sha16()) if pmc else None
-            except Exception:
-                pmc, traffic, traffic_stale = None, None, None
+        if args.full:
+            # dominant kernel: the per-period tangent kernels (k_tan_back / k_tan_fwd). One launch moves
+            # the policy partials of ONE period for N directions: G*8*N algorithmic bytes
+            # (B_alg = 2*P*G*8*(1+N) per batch = G*8 bytes per (sweep, period, direction)).
+            persistent = split_keys and launches.get("tangent_forward", P) < P
+            wide = hb.info()["last_tangent_family_name"] == "on-chip-wide"
+            if wide:
+                # the on-chip wide sweeps (csrc/hank_wide.h): one workgroup per direction, ONE launch per sweep; a launch moves the policy
+                # partials of every period and direction once (written by k_wide_back, read by k_wide_fwd): P*G*8*N bytes. The Float64
+                # sweeps run before them as XCD-local persistent sweeps and are part of ms_per_step.
+                dom = max(("tangent_backward", "tangent_forward"), key=lambda k: acc[k])
+                kname = {"tangent_backward": "k_wide_back", "tangent_forward": "k_wide_fwd"}[dom]
+                bytes_per_launch = P * G * 8 * N
+            elif persistent and not args.split and acc.get("tangent_backward", 0.0) < 0.05:
+                # the persistent Dual pass: ONE launch per sweep, value and partials together in both (k_xdual_back writes the policy
+                # and the policy partials of every period, k_xfwd<D, true> reads them): P*G*8*(1+N) algorithmic bytes per launch
+                dom = max(("primal_backward", "tangent_forward"), key=lambda k: acc[k])
+                kname = {"primal_backward": "k_xdual_back", "tangent_forward": "k_xfwd"}[dom]
+                bytes_per_launch = P * G * 8 * (1 + N)
+            elif persistent:
+                # XCD-local persistent sweeps at a recorded primal: ONE launch carries a whole sweep (P periods). The kernels that
+                # move the algorithmic bytes are the tangent sweeps (the policy-partials sequence: written once by k_xtan_back, read
+                # once by k_xfwd): P*G*8*N_pass per launch; a batch wider than 32 runs as ceil(N/32) passes. The Float64
+                # sweeps move P*G*8 bytes each and are latency-bound: reported beside, not hidden.
+                dom = max(("tangent_backward", "tangent_forward"), key=lambda k: acc[k])
+                kname = {"tangent_backward": "k_xtan_back", "tangent_forward": "k_xfwd"}[dom]
+                bytes_per_launch = P * G * 8 * N / launches[dom]
+            elif split_keys:
+                dom = max(("tangent_backward", "tangent_forward"), key=lambda k: acc[k])
+                kname = {"tangent_backward": "k_tan_back", "tangent_forward": "k_tan_fwd"}[dom]
+                bytes_per_launch = G * 8 * N
+            else:   # a dual-sweep launch advances the primal and the N tangents by one period: G*8*(1+N)
+                dom = max(("dual_backward", "dual_forward"), key=lambda k: acc[k])
+                kname = {"dual_backward": "k_fused_back", "dual_forward": "k_fused_fwd"}[dom]
+                bytes_per_launch = G * 8 * (1 + N)
+            avg_launch_s = 1e-3 * acc[dom] / launches[dom]
+            achieved = bytes_per_launch / avg_launch_s / 1e9
+            # HBM bytes per launch of that kernel from the committed rocprofv3 PMC passes (FETCH_SIZE and
+            # WRITE_SIZE in separate runs, profiles/r01b_pmc_*): a profile artefact, not measured live
+            pmc, traffic, traffic_stale = None, None, None
+            pmc_file = ROOT / "profiles" / "pmc_latest.json"
+            if pmc_file.exists() and N == WORKLOADS[args.workload]["N"]:
+                try:
+                    rec = json.loads(pmc_file.read_text()).get(args.workload, {})
+                    pmc = rec.get(kname)
+                    traffic = pmc["hbm_bytes"] if pmc else None
+                    # the counters belong to the kernel sources they were collected on: a different hash = re-profile
+                    traffic_stale = (rec.get("kernel_source_sha16") != kernel_source_sha16()) if pmc else None
+                except Exception:
+                    pmc, traffic, traffic_stale = None, None, None
         b_alg_batch = 2 * P * G * 8 * (1 + N)
         out = {
             "metric": "sequence-space JVPs/sec (household block: BackwardIteration+ForwardIteration+aggregation, Krusell-Smith T=300)",
@@ -674,29 +707,34 @@ def main(argv=None):
                        "step": ("1 primal sweep + 1 batched JVP of N tangents (hank_primal + hank_jvp)" if args.split else
                                 "1 dual-sweep pass: primal + N tangents (hank_primal_jvp)") + (" + RCCL all-gather" if use_dist else ""),
                        "parallelism": f"tangent-sharded x{world}"},
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_stale": traffic_stale, "traffic_detail": pmc,
-                         "bytes_per_launch": bytes_per_launch, "avg_launch_us": 1e6 * avg_launch_s,
-                         "model_ceiling": model_ceiling(G, N, n_e),
-                         "schedule": "on-chip-wide" if wide else ("xcd-persistent" if persistent else "launch-per-period"),
-                         # measured per-wave issue and wait shares of that kernel (a separate rocprofv3 --pmc pass, same hash rule as traffic)
-                         "counters": (pmc or {}).get("counters"),
-                         "note": "avg launch = HIP-event time of the sweep's kernels on the library's stream / launches"},
+        }
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_stale": traffic_stale, "traffic_detail": pmc,
+                               "bytes_per_launch": bytes_per_launch, "avg_launch_us": 1e6 * avg_launch_s,
+                               "model_ceiling": model_ceiling(G, N, n_e),
+                               "schedule": "on-chip-wide" if wide else ("xcd-persistent" if persistent else "launch-per-period"),
+                               # measured per-wave issue and wait shares of that kernel (a separate counter pass, same hash rule as traffic)
+                               "counters": (pmc or {}).get("counters"),
+                               "note": "avg launch = HIP-event time of the sweep's kernels on the library's stream / launches"}
+        out.update({
             # hank_stats of the timed context: schedule in use (2 = auto, 1 = persistent forced, 0 = launches), fallbacks from the
             # persistent sweeps to the launches (the run FAILS if one happens inside the timed region), primal sweeps the memo skipped
             "hank_stats": {k: st_timed[k] for k in ("schedule", "fallbacks", "primal_memo_hits", "primal_sweeps", "sweep_launches")},
             "tangent_family": hb.info()["last_tangent_family_name"],
             "whole_batch": {"B_alg_bytes": b_alg_batch, "achieved_GBs": b_alg_batch / (1e-3 * ms_per_step) / 1e9,
                             "frac_of_hbm_peak": b_alg_batch / (1e-3 * ms_per_step) / 1e9 / HBM_PEAK_GBS},
-            "sweeps_ms": {k: round(acc[k], 4) for k in acc}, "launches": launches,
-        }
-        if not args.no_cpu_baseline and world == 1:
+            "launches": launches,
+        })
+        if args.full:
+            out["sweeps_ms"] = {k: round(acc[k], 4) for k in acc}
+        if args.full and not args.no_cpu_baseline and world == 1:
             step(); fence()          # the benched call once more, its outputs against the CPU oracle
             out["output_check"] = check_timed_output(m, ss, x, dx_flat.reshape((2, P, N), order="F"), d_agg.cpu().numpy(),
                                                      d_dagg.cpu().numpy().reshape((P, N), order="F"))
             out["cpu_baseline"] = cpu_baseline(m, ss, x, Z)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
             try:
                 out["extra"] = extra_measurements(hb, d_x, P, N, dev, stream.cuda_stream)
             except Exception as e:      # noqa: BLE001 - the headline line must survive a failure of the side measurements
@@ -711,7 +749,7 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not args.no_extra:
+        if world > 1 and args.full and not args.no_extra:
             # the same partition with ONE process driving one context per GPU (no collective), measured in a fresh child once
             # the ranks are done with the GPUs (idle behind the barrier above): a failure there must not cost the headline line
             import subprocess

@@ -9,6 +9,7 @@ Duals are numpy arrays with a trailing axis of length 1+N: [..., 0] = value, [..
 from __future__ import annotations
 
 import ctypes as C
+import os
 import subprocess
 from pathlib import Path
 
@@ -28,11 +29,20 @@ class orc_model(C.Structure):
                 ("beta", C.c_double), ("gamma", C.c_double), ("borrow_cons", C.c_double)]
 
 
+def _reference_present() -> bool:
+    """the reference's C++ sources are readable here (a user who may not enter their parent directory has none)."""
+    ref = Path("/root/reference/ForwardDiff.jl/benchmarks/cpp")
+    try:
+        return ref.is_dir() and os.access(ref, os.R_OK | os.X_OK)
+    except OSError:
+        return False
+
+
 def build(force: bool = False) -> None:
     """compile the oracle (and oracle/_ref when /root/reference is present) with make."""
     if force or not _LIB.exists() or _LIB.stat().st_mtime < (_DIR / "hank_oracle.c").stat().st_mtime:
         subprocess.run(["make", "-C", str(_DIR), "libhank_oracle.so"], check=True, capture_output=True)
-    if Path("/root/reference/ForwardDiff.jl/benchmarks/cpp").is_dir() and (force or not _REF.exists()):
+    if _reference_present() and (force or not _REF.exists()):
         subprocess.run(["make", "-C", str(_DIR), "ref"], check=True, capture_output=True)
 
 

@@ -1,10 +1,11 @@
 # dev: the headline bench on several builds of the library (A/B of dev knobs): bash scripts/dev_libs.sh dev/libA.so dev/libB.so ...
-R=${GRAFT_REPO_ROOT:-$(pwd)}; mkdir -p $R/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd); O=$(mktemp -d)
 for L in "$@"; do
-  HANK_HIP_LIB=$R/$L timeout -k 10 200 python $R/bench.py --no-extra --no-cpu-baseline > $R/gpurun_out/ab.json 2> $R/gpurun_out/ab.err || { echo "$L: failed"; tail -3 $R/gpurun_out/ab.err; continue; }
+  HANK_HIP_LIB=$R/$L timeout -k 10 200 python $R/bench.py --full --no-extra --no-cpu-baseline > $O/ab.json 2> $O/ab.err || { echo "$L: failed"; tail -3 $O/ab.err; continue; }
   python - "$L" <<PY
 import json, sys
-d = json.loads(open("$R/gpurun_out/ab.json").read().strip().splitlines()[-1])
+d = json.loads(open("$O/ab.json").read().strip().splitlines()[-1])
 print(sys.argv[1], round(d["value"]), d["sweeps_ms"], flush=True)
 PY
 done
+rm -rf "$O"

@@ -1,6 +1,6 @@
 # counters of the wide batch (N = 256; HANK_SCHEDULE=launch for the launch path): bash scripts/dev_pmc_wide.sh <tag>
 TAG=${1:-r05n256}; R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/prof_$TAG; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-ARGS="--tangents 256 --steps 3 --warmup 1 --no-cpu-baseline --no-extra"
+ARGS="--tangents 256 --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 $R/bench.py $ARGS > $O/kt.log 2>&1
 cp "$(find $O/kt -name '*kernel_stats.csv' | head -1)" $O/${TAG}_kernel_stats.csv; rm -rf $O/kt
 n=0

@@ -4,6 +4,10 @@ freeze the restated semantics (regression anchor for the oracle, parity target f
 they are not reference outputs ("parity unpinned" in that sense).
 
     python tests/golden/make_golden.py
+
+`python tests/golden/make_golden.py ref` writes ref_cppdual_ops.npz instead: the outputs of the reference's own C++
+dual classes (oracle/_ref, built by `make -C oracle ref` where the reference sources are present) on the inputs
+tests/test_oracle_dual_vs_ref.py draws, so that test runs without the reference.
 """
 import sys
 from pathlib import Path
@@ -47,5 +51,45 @@ def main():
     print("golden written")
 
 
+def ref_cppdual():
+    """reference C++ dual ops on the inputs of tests/test_oracle_dual_vs_ref.py (same seeds, same draw order)."""
+    import ctypes as C
+    from oracle import oracle
+    lib = oracle.ref_lib()
+    assert lib is not None, "oracle/_ref not built"
+    dp = C.POINTER(C.c_double)
+    arrays = {}
+    for N, fname in ((1, "ref_dual1_op"), (3, "ref_dual3_op")):
+        f = getattr(lib, fname)
+        rng = np.random.default_rng(7)
+        xs, ys, outs = [], [], []
+        for _ in range(200):
+            x, y = rng.standard_normal(1 + N), rng.standard_normal(1 + N)
+            o = np.empty((5, 1 + N))
+            for rop in range(5):
+                r = np.empty(1 + N)
+                f(rop, x.ctypes.data_as(dp), y.ctypes.data_as(dp), r.ctypes.data_as(dp))
+                o[rop] = r
+            xs.append(x); ys.append(y); outs.append(o)
+        arrays[f"binop_n{N}_x"], arrays[f"binop_n{N}_y"], arrays[f"binop_n{N}_out"] = np.array(xs), np.array(ys), np.array(outs)
+    rng = np.random.default_rng(3)
+    xs, outs = [], []
+    for _ in range(100):
+        x = np.array([rng.uniform(0.1, 5.0), rng.standard_normal()])
+        r = np.empty(2)
+        lib.ref_dual1_op(5, x.ctypes.data_as(dp), x.ctypes.data_as(dp), r.ctypes.data_as(dp))
+        xs.append(x); outs.append(r)
+    arrays["sqrt_n1_x"], arrays["sqrt_n1_out"] = np.array(xs), np.array(outs)
+    x = np.arange(10, dtype=np.float64)
+    g = np.empty(10)
+    lib.ref_rosenbrock_grad1(x.ctypes.data_as(dp), 10, g.ctypes.data_as(dp))
+    arrays["rosenbrock_grad1_x"], arrays["rosenbrock_grad1"] = x, g
+    np.savez_compressed(Path(__file__).resolve().parent / "ref_cppdual_ops.npz", **arrays)
+    print("ref_cppdual_ops.npz written")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref"]:
+        ref_cppdual()
+    else:
+        main()

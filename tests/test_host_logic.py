@@ -8,7 +8,11 @@ REF_YAML = Path("/root/reference/KrusellSmith.yaml")
 
 
 def test_reference_yaml_is_accepted_unchanged(hank):
-    if not REF_YAML.exists():
+    try:
+        present = REF_YAML.is_file()
+    except OSError:                     # e.g. a user who may not enter the reference's parent directory
+        present = False
+    if not present:
         pytest.skip("reference checkout not present on this machine")
     m = hank.build_model_from_yaml(str(REF_YAML))
     cs = m.compspec

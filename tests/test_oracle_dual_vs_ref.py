@@ -1,17 +1,20 @@
 """Pins the oracle's dual arithmetic against the REFERENCE's own C++ dual classes
 (ForwardDiff.jl/benchmarks/cpp, compiled from /root/reference into oracle/_ref by oracle/Makefile)
-and against the rosenbrock known answers the reference asserts (benchmarks.cpp:39-61)."""
+and against the rosenbrock known answers the reference asserts (benchmarks.cpp:39-61).
+The reference's outputs on these inputs are stored in tests/golden/ref_cppdual_ops.npz
+(tests/golden/make_golden.py ref), so the pins hold without the reference; where oracle/_ref
+was built, the live library must reproduce the stored outputs as well."""
 import ctypes as C
+from pathlib import Path
 
 import numpy as np
 import pytest
 
+GOLDEN = Path(__file__).resolve().parent / "golden" / "ref_cppdual_ops.npz"
 
-def _ref(oracle_mod):
-    lib = oracle_mod.ref_lib()
-    if lib is None:
-        pytest.skip("oracle/_ref not built (reference sources absent at build time)")
-    return lib
+
+def _golden():
+    return np.load(GOLDEN)
 
 
 # (ref op code, oracle op code): add, sub, mul, real*dual, real-dual
@@ -20,15 +23,20 @@ OPS = [(0, 0), (1, 1), (2, 2), (3, 4), (4, 5)]
 
 @pytest.mark.parametrize("N,fname", [(1, "ref_dual1_op"), (3, "ref_dual3_op")])
 def test_binary_rules_match_reference_cpp(oracle_mod, N, fname):
-    lib = _ref(oracle_mod)
-    f = getattr(lib, fname)
+    g = _golden()
+    lib = oracle_mod.ref_lib()
+    f = getattr(lib, fname) if lib is not None else None
     rng = np.random.default_rng(7)
     dp = C.POINTER(C.c_double)
-    for _ in range(200):
+    for i in range(200):
         x, y = rng.standard_normal(1 + N), rng.standard_normal(1 + N)
+        assert np.array_equal(x, g[f"binop_n{N}_x"][i]) and np.array_equal(y, g[f"binop_n{N}_y"][i])
         for rop, oop in OPS:
-            out = np.empty(1 + N)
-            f(rop, x.ctypes.data_as(dp), y.ctypes.data_as(dp), out.ctypes.data_as(dp))
+            out = g[f"binop_n{N}_out"][i, rop]
+            if f is not None:
+                live = np.empty(1 + N)
+                f(rop, x.ctypes.data_as(dp), y.ctypes.data_as(dp), live.ctypes.data_as(dp))
+                assert np.array_equal(live, out), (rop, x, y, live, out)
             if oop == 4:      # oracle Dual*Real with the roles swapped: (y as dual) * x.value
                 mine = oracle_mod.dual_binop(4, y, x, N)
             else:
@@ -38,13 +46,18 @@ def test_binary_rules_match_reference_cpp(oracle_mod, N, fname):
 
 def test_pow_rule_matches_reference_sqrt_exp(oracle_mod):
     """reference sqrt(Dual) = (sqrt v, eps/(2 sqrt v)); oracle Dual^0.5 must agree to rounding."""
-    lib = _ref(oracle_mod)
+    g = _golden()
+    lib = oracle_mod.ref_lib()
     dp = C.POINTER(C.c_double)
     rng = np.random.default_rng(3)
-    for _ in range(100):
+    for i in range(100):
         x = np.array([rng.uniform(0.1, 5.0), rng.standard_normal()])
-        out = np.empty(2)
-        lib.ref_dual1_op(5, x.ctypes.data_as(dp), x.ctypes.data_as(dp), out.ctypes.data_as(dp))
+        assert np.array_equal(x, g["sqrt_n1_x"][i])
+        out = g["sqrt_n1_out"][i]
+        if lib is not None:
+            live = np.empty(2)
+            lib.ref_dual1_op(5, x.ctypes.data_as(dp), x.ctypes.data_as(dp), live.ctypes.data_as(dp))
+            assert np.array_equal(live, out), (x, live, out)
         mine = oracle_mod.dual_binop(7, x, np.array([0.5, 0.0]), 1)
         np.testing.assert_allclose(mine, out, rtol=4e-16, atol=0)
 
@@ -54,6 +67,7 @@ def test_rosenbrock_known_answers(oracle_mod):
     (a) by the reference's own template through oracle/_ref and (b) with the oracle's dual ops."""
     expect10 = np.array([-2., -200., 1002., 5804., 16606., 35808., 65810., 109012., 167814., -11000.])
     x = np.arange(10, dtype=np.float64)
+    assert np.array_equal(_golden()["rosenbrock_grad1"], expect10)
     lib = oracle_mod.ref_lib()
     if lib is not None:
         out = np.empty(10)
