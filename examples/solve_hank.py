@@ -21,13 +21,16 @@ sys.path.insert(0, str(ROOT))
 
 
 def build(n_a=1000, n_e=7, T=500, spec="one_asset_hank.yaml"):
-    """spec: one_asset_hank.yaml (asset-market clearing, one heterogeneous variable) or one_asset_hank_goods.yaml (goods-market
-    clearing: savings AND consumption aggregated by the device sweeps)."""
+    """spec: one_asset_hank.yaml (asset-market clearing, one heterogeneous variable), one_asset_hank_goods.yaml (goods-market
+    clearing: savings AND consumption aggregated by the device sweeps) or one_asset_hank_wages.yaml (sticky wages: the wage
+    Phillips curve reads UCE, a heterogeneous output that is not affine in the policy)."""
     import hank_amd as h
     from hank_amd import OneAssetHANK as oa
     ov = {"T": T, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": n_e}}}
     m = h.build_model_from_yaml(str(ROOT / "examples" / spec), overrides=ov)
     m.params.B = oa.calibrate_bond_supply(m)
+    if hasattr(m.params, "vφ"):
+        m.params.vφ = oa.calibrate_disutility(m)
     ss, _ = h.get_SteadyStates(m)
     return m, ss
 
@@ -72,7 +75,8 @@ if __name__ == "__main__":
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--inner", default="fixed_point", choices=["fixed_point", "krylov"])
     ap.add_argument("--jacobian", default="toeplitz", choices=["toeplitz", "columns"])
-    ap.add_argument("--spec", default="one_asset_hank.yaml", choices=["one_asset_hank.yaml", "one_asset_hank_goods.yaml"])
+    ap.add_argument("--spec", default="one_asset_hank.yaml", choices=["one_asset_hank.yaml", "one_asset_hank_goods.yaml",
+                                                                 "one_asset_hank_wages.yaml"])
     a = ap.parse_args()
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))

@@ -164,8 +164,12 @@ int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out);
  * affine combination of them; the budget residual c = (1+r_t) a + w_t z_e + tr_t - a' (the c_grid of KrusellSmith.jl:79) is the
  * one built in:
  *   hank_get_het_outputs(ctx, n_het, dxhh, N, agg_out, dagg_out): output 0 = the policy variable of the endogenous dimension
- *   (KD / A: what hank_primal and hank_jvp return), output 1 = consumption; n_het in {1, 2} says how many the model's
- *   `heterogeneous:` section lists. agg_out (P, n_het) column-major of the last primal sweep; dagg_out (P, n_het, N)
+ *   (KD / A: what hank_primal and hank_jvp return), output 1 = consumption, output 2 = Value = (1+r_t) c^-gamma (the
+ *   value_current of KrusellSmith.jl:80), output 3 (one-asset HANK only) = UCE = z_e c^-gamma; n_het (1..3 Krusell-Smith,
+ *   1..4 one-asset HANK) says how many the model's `heterogeneous:` section reaches, and may not exceed the count declared
+ *   with hank_set_het_outputs (HANK_ERR_NOT_READY). Outputs 2 and 3 are not affine in the policy: they are reduced from the
+ *   same post-transition D_t and the distribution tangent of the last tangent sweep's policy partials (csrc/hank_hetx.h),
+ *   in buffers the context keeps (P·G·(2·(n_het-2) + N) doubles and less, grown to the widest request, freed by hank_destroy). agg_out (P, n_het) column-major of the last primal sweep; dagg_out (P, n_het, N)
  *   column-major of the last tangent sweep — whichever kernel family ran it — whose input `dxhh` (n_hh, P, N) is passed
  *   again (the partials of r_t, w_t, tr_t enter consumption directly). dagg_out NULL or N = 0: values only.
  *   hank_get_grid_aggregates: the raw second reduction, agg2_out[P] = sum a D_t and dagg2_out (P, N) = sum a dD_t, for a host
@@ -173,6 +177,12 @@ int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out);
  * The _dev forms take device pointers and are ordered on the context's stream.                                              */
 int hank_get_het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double *agg_out, double *dagg_out);
 int hank_get_het_outputs_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, int32_t N, double *d_agg_out, double *d_dagg_out);
+/* hank_set_het_outputs: how many of the family's heterogeneous outputs the caller will ask hank_get_het_outputs for
+ * (BackwardIteration.jl:99-112 keeps one sequence per key listed under `heterogeneous:`, ForwardIteration.jl:303-307 dots each
+ * with the same D_t). 1..3 for Krusell-Smith (KD, C, Value), 1..4 for the one-asset HANK (A, C, Value, UCE); default 2. The
+ * sweeps are the same for every count; a change of the count drops the primal memo of hank_primal_jvp (a host shim that
+ * serves several callers on one context only ever raises it: BackwardIteration.py ensure_het_outputs).                     */
+int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het);
 int hank_get_grid_aggregates(hank_ctx *ctx, double *agg2_out, int32_t N, double *dagg2_out);
 int hank_get_grid_aggregates_dev(hank_ctx *ctx, double *d_agg2_out, int32_t N, double *d_dagg2_out);
 /* The distribution path D_1..D_P of the last hank_primal -> out[P*G] (ForwardIteration.jl:297-300). */

@@ -61,6 +61,21 @@ def policy_variable(model: SequenceModel) -> str:
     return next(d.policy_var for d in model.heterogeneity.values() if d.dim_type == "endogenous")
 
 
+def het_output_count(model, het_keys) -> int:
+    """how many of the family's outputs the device must serve for these heterogeneous variables: 1 + the largest output index
+    (hank_set_het_outputs; output j of hank_get_het_outputs is value_fn.outputs[j])."""
+    outs = tuple(model.value_fn.outputs)
+    return 1 + max((outs.index(k) for k in het_keys if k in outs), default=0)
+
+
+def ensure_het_outputs(hb, n: int) -> None:
+    """declare at least n outputs on the model's shared context. The count is only ever raised: every caller may read fewer than
+    declared, and a change of the declaration drops the primal memo of hank_primal_jvp (callers alternating on one model would
+    otherwise invalidate each other's memo)."""
+    if n > getattr(hb, "_n_het_declared", 2):
+        hb.set_het_outputs(n)
+
+
 class PolicySequences(dict):
     """BackwardIteration's return value: {het_var: list of P (n_a x n_e) matrices}; the matrices are
     fetched from HBM lazily. Carries the tag ForwardIteration uses to stay on the fused path.
@@ -84,6 +99,9 @@ class PolicySequences(dict):
         """the ONE fused device sweep of this BackwardIteration (+ ForwardIteration) pair."""
         hb, pend = self._hb, self._pending
         hb.set_boundary(pend["value"], D0)
+        n_out = het_output_count(self._model, self._het_keys) if self._model is not None else 1
+        if len(self._het_keys) > 1:
+            ensure_het_outputs(hb, n_out)
         if pend["dxhh"] is not None:      # a Dual pass carries value and partials together, like the reference's JVP
             agg, dagg = hb.primal_jvp(pend["xhh"], pend["dxhh"])
         else:
@@ -91,7 +109,7 @@ class PolicySequences(dict):
         hb._generation = getattr(hb, "_generation", 0) + 1
         hb._last = {"agg": agg, "dagg": dagg, "D0": D0, "xhh": pend["xhh"], "dxhh": pend["dxhh"], "value": pend["value"]}
         if len(self._het_keys) > 1:        # every heterogeneous variable's aggregate, reduced by the same sweeps
-            hb._last["het"] = hb.het_outputs(len(self._model.value_fn.outputs), pend["dxhh"])
+            hb._last["het"] = hb.het_outputs(n_out, pend["dxhh"])
         self._D_used, self._generation, self._pending = D0, hb._generation, None
 
     def _fetch(self):

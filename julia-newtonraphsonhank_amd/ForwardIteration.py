@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .BackwardIteration import PolicySequences, household_block
+from .BackwardIteration import PolicySequences, ensure_het_outputs, het_output_count, household_block
 from .dual import Dual
 from .GeneralStructures import SequenceModel, vars_of_type
 
@@ -78,7 +78,8 @@ def ForwardIteration(policy_seqs, model: SequenceModel, ss_initial):
             dagg = hb.jvp(last["dxhh"]) if last["dxhh"] is not None else None
             last.update(agg=agg, dagg=dagg, D0=D0)
             if "het" in last:
-                last["het"] = hb.het_outputs(len(outs), last["dxhh"])
+                ensure_het_outputs(hb, het_output_count(model, het_keys))
+                last["het"] = hb.het_outputs(het_output_count(model, het_keys), last["dxhh"])
         agg, dagg = last["agg"], last["dagg"]
         if len(het_keys) == 1:
             return {pol_key: Dual(agg, dagg) if dagg is not None else agg}

@@ -33,17 +33,21 @@ class _KSValueFunction:
     name = "ValueFunction"
     value_fn_id = HANK_VF_KRUSELL_SMITH
     household_inputs = ("r", "w")   # rows of xVals the household block reads
-    outputs = ("KD", "C")           # one policy per heterogeneous variable a model may list: the reference's KD, and consumption (the
-                                    # c_grid of KrusellSmith.jl:79 as a second policy: hank_get_het_outputs; not returned by the reference's plugin)
+    outputs = ("KD", "C", "Value")  # one policy per heterogeneous variable a model may list: the reference's KD and Value
+                                    # (KrusellSmith.jl:80-82), and consumption (the c_grid of KrusellSmith.jl:79 as a second policy);
+                                    # device output index = position here (hank_get_het_outputs)
     endogenous_dim, exogenous_dim = "wealth", "productivity"
 
     def derived_policy(self, key: str, policy, xVals: dict, model):
         """a heterogeneous variable other than the policy variable from the savings policy (n_a, n_e), Float64 or `Dual`."""
-        if key != "C":
+        if key not in ("C", "Value"):
             raise KeyError(key)
         grid = model.heterogeneity["wealth"].grid
         z = model.heterogeneity["productivity"].grid
-        return (1.0 + xVals["r"]) * grid[:, None] + xVals["w"] * z[None, :] - policy
+        c = (1.0 + xVals["r"]) * grid[:, None] + xVals["w"] * z[None, :] - policy
+        if key == "C":
+            return c
+        return (1.0 + xVals["r"]) * c ** (-model.params.γ)       # value_current, KrusellSmith.jl:80
 
     def host_steady_state_step(self, value_next: np.ndarray, xVals: dict, model) -> dict:
         """one Float64 EGM step for the host steady-state VFI (same algebra as KrusellSmith.jl:59-80)."""

@@ -13,7 +13,7 @@ import numpy as np
 import scipy.sparse.linalg as spla
 
 from .Aggregation import Residuals
-from .BackwardIteration import BackwardIteration, household_block, household_inputs
+from .BackwardIteration import BackwardIteration, ensure_het_outputs, household_block, household_inputs
 from .dual import Dual
 from .ForwardIteration import ForwardIteration
 from .GeneralStructures import JVP, SequenceModel, assemble_full_xMat, vars_of_type
@@ -48,7 +48,7 @@ class LinearizedFunction:
         self.het = het
         outs = tuple(mod.value_fn.outputs)
         self._out_idx = [outs.index(k) for k in het]        # device output of each heterogeneous variable (hank_get_het_outputs)
-        self._n_out = len(outs) if len(het) > 1 else 1
+        self._n_out = 1 + max(self._out_idx)              # outputs the device serves: up to the last one listed (hank_set_het_outputs)
         self._record_primal()
         self._xMat = assemble_full_xMat(self.x, {k: self.aggs[:, j] for k, j in zip(het, self._out_idx)}, exog_paths, mod, ss_initial, ss_ending)
         self.Fx = Residuals(self._xMat, mod)
@@ -107,6 +107,8 @@ class LinearizedFunction:
         hb = self.hb
         hb.set_boundary(self.ss_ending.value, self.ss_initial.D)
         self.agg = hb.primal(self._xhh)
+        if self._n_out > 2:
+            ensure_het_outputs(hb, self._n_out)
         self.aggs = self.agg[:, None] if self._n_out == 1 else hb.het_outputs(self._n_out)[0]      # (P, outputs)
         hb._generation = getattr(hb, "_generation", 0) + 1
         hb._last = None          # an older PolicySequences must not take ForwardIteration's fused shortcut
@@ -140,6 +142,8 @@ class LinearizedFunction:
                 sub = padded
             dagg[:, nz] = self.hb.jvp(sub)[:, :len(nz)]
             if self._n_out > 1:
+                if self._n_out > 2:
+                    ensure_het_outputs(self.hb, self._n_out)
                 daggs[:, :, nz] = self.hb.het_outputs(self._n_out, sub)[1][:, :, :len(nz)]
         if self.exact_residual_layer:           # the reference's way: re-evaluate the equations under the Dual every time
             agg = {k: Dual(self.aggs[:, j], np.ascontiguousarray(daggs[:, j, :])) for k, j in zip(self.het, self._out_idx)}

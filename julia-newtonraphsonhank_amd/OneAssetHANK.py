@@ -37,17 +37,21 @@ class _HANKValueFunction:
     name = "HANKValueFunction"
     value_fn_id = HANK_VF_ONE_ASSET_HANK
     household_inputs = ("r", "om", "Tr")   # rows of xVals the household block reads
-    outputs = ("A", "C")                    # device output index = position here (hank_get_het_outputs)
+    outputs = ("A", "C", "Value", "UCE")    # device output index = position here (hank_get_het_outputs); UCE = z_e c^-γ (wage Phillips curve)
     endogenous_dim, exogenous_dim = "wealth", "productivity"
 
     def derived_policy(self, key: str, policy, xVals: dict, model):
         """a heterogeneous variable other than the policy variable, from the savings policy (n_a, n_e) — Float64 or `Dual` —
         and the period's inputs: consumption, the budget residual."""
-        if key != "C":
+        if key not in ("C", "Value", "UCE"):
             raise KeyError(key)
         grid = model.heterogeneity["wealth"].grid
         z = model.heterogeneity["productivity"].grid
-        return (1.0 + xVals["r"]) * grid[:, None] + (xVals["om"] * z[None, :] + xVals["Tr"]) - policy
+        c = (1.0 + xVals["r"]) * grid[:, None] + (xVals["om"] * z[None, :] + xVals["Tr"]) - policy
+        if key == "C":
+            return c
+        uc = c ** (-model.params.γ)
+        return (1.0 + xVals["r"]) * uc if key == "Value" else z[None, :] * uc
 
     def host_steady_state_step(self, value_next: np.ndarray, xVals: dict, model) -> dict:
         """one Float64 EGM step for the host steady-state VFI (the KS step with the transfer in cash on hand)."""
@@ -117,3 +121,16 @@ def calibrate_bond_supply(model, tol: float = 1e-10):
         b0, b1, f0 = b1, b1 - f1 * (b1 - b0) / (f1 - f0), f1
         f1 = excess(b1)
     return b1
+
+
+def calibrate_disutility(model):
+    """the disutility of hours vφ that makes Y = 1 a steady state of the sticky-wage variant (examples/one_asset_hank_wages.yaml):
+    at zero wage inflation the wage Phillips curve reads vφ Y^(1+1/ν) = (1-τ) w Y UCE / μw, so with Y = 1, w = 1/μ and the
+    household block solved once at the known prices (r = rstar, the bond supply B already calibrated),
+    vφ = (1-τ) w UCE_ss / μw, UCE_ss = Σ z_e c^-γ D."""
+    p = model.params
+    w = 1.0 / p.μ
+    xv = {"r": p.rstar, "om": (1.0 - p.τ) * w, "Tr": 1.0 - w + p.τ * w - p.rstar * p.B}
+    _, _, pol, D = household_asset_demand(model, xv["r"], xv["om"], xv["Tr"])
+    uce = float(HANKValueFunction.derived_policy("UCE", pol, xv, model).reshape(-1, order="F") @ D)
+    return (1.0 - p.τ) * w * uce / p.μw

@@ -111,6 +111,10 @@ class SSAssembler:
                 if tol < self.vfi_tol:
                     break
                 res = vf.host_steady_state_step(value, xv, model)
+            pol = res[self.endog_dim.policy_var]
+            for k in vars_of_type(model, "heterogeneous"):
+                if k not in res:          # (keys the host step does not return, UCE: from the policy, as on the device branch)
+                    res[k] = vf.derived_policy(k, pol, xv, model)
         if self.vfi_on_device and self.endog_dim.n * self.n_exog > 4000:
             # chains this large take the power method on the host too (invariant_dist): the same iteration, run with the
             # forward step kernel of the hot path, warm-started from the last iterate
@@ -186,12 +190,15 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
     if asm.vfi_on_device:
         from .BackwardIteration import household_block
         _, pol = household_block(model).backward_step(ss_value, [vars_[k] for k in model.value_fn.household_inputs])
-        res = {asm.endog_dim.policy_var: pol}
+        res = {asm.endog_dim.policy_var: pol, "Value": ss_value}       # (the converged value IS the Value key)
         for k in vars_of_type(model, "heterogeneous"):
             if k not in res:
                 res[k] = model.value_fn.derived_policy(k, pol, vars_, model)
     else:
         res = model.value_fn.host_steady_state_step(ss_value, vars_, model)
+        for k in vars_of_type(model, "heterogeneous"):
+            if k not in res:
+                res[k] = model.value_fn.derived_policy(k, res[asm.endog_dim.policy_var], vars_, model)
     het_keys = vars_of_type(model, "heterogeneous")
     policies = {k: res[k] for k in het_keys}
     Λ_endog = make_endogenous_transition(policies[asm.endog_dim.policy_var], asm.endog_dim, asm.n_exog)

@@ -7,6 +7,7 @@
 #include "hank_xsweep.h"
 #include "hank_jacobian.h"
 #include "hank_wide.h"
+#include "hank_hetx.h"
 #include "../../include/hank_hip.h"
 
 #include <cstdarg>
@@ -155,6 +156,9 @@ struct hank_ctx {
     bool xdual_back = true;                           // dev knob HANK_XDUAL_BACK=0 (read at hank_create): a persistent Dual pass runs k_xprimal_back + k_xtan_back instead of k_xdual_back
     bool memo_valid = false;
     std::vector<double> memo_xhh;
+    int n_het = 2;                                    // heterogeneous outputs the caller declared (hank_set_het_outputs; a change drops the memo)
+    char *hx_slab = nullptr;                          // the extra outputs' buffers (hx_outputs), grown to the largest request, freed with the context
+    size_t hx_bytes = 0;
     bool stationary = false;                          // the recorded primal is the constant steady-state path with the steady state as both boundaries (hank_fake_news)
     std::vector<double> h_ss_value, h_ss_D;           // the boundary as the host handed it in (stationarity check)
     hipEvent_t ev_stream = nullptr;
@@ -1222,7 +1226,7 @@ int hank_destroy(hank_ctx *ctx) {
     for (WTan &t : ctx->wtans) w_free_tan(t);
     ctx->wtans.clear();
     ctx->wcur = nullptr;
-    (void)hipFree(ctx->rec_slab); (void)hipFree(ctx->d_ibw);
+    (void)hipFree(ctx->rec_slab); (void)hipFree(ctx->d_ibw); (void)hipFree(ctx->hx_slab);
     (void)hipFree(ctx->d_a); (void)hipFree(ctx->d_z); (void)hipFree(ctx->d_Pi); (void)hipFree(ctx->d_ss_value);
     (void)hipFree(ctx->d_xhh); (void)hipFree(ctx->d_agg); (void)hipFree(ctx->d_agg_rm); (void)hipFree(ctx->d_zd); (void)hipFree(ctx->d_aggpart); (void)hipFree(ctx->d_err);
     for (int k = 0; k < 16; k++)
@@ -2001,29 +2005,97 @@ static int granular_backward(hank_ctx *ctx, const double *value_next, const doub
 // agg (P, 2) and dagg (P, 2 N) as the sweeps leave them -> out_agg (P, n_het), out_dagg (P, n_het, N) column-major.
 __global__ void k_het_outputs(int P, int n_hh, int n_het, int N, const double *__restrict__ xhh, const double *__restrict__ dxhh,
                               const double *__restrict__ agg, const double *__restrict__ dagg, const double *__restrict__ zd,
+                              const double *__restrict__ hxS, const double *__restrict__ hxT,
                               double *__restrict__ out_agg, double *__restrict__ out_dagg) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)P * (N + 1)) return;
     const int t = (int)(idx % P), n = (int)(idx / P) - 1;
+    const int NX = n_het > 2 ? n_het - 2 : 0;      // outputs 2, 3 (Value, UCE): hank_hetx.h
     const double r = xhh[n_hh * t], w = xhh[n_hh * t + 1], tr = n_hh > 2 ? xhh[n_hh * t + 2] : 0.0;
     const double KD = agg[t], AD = agg[P + t], ZD = zd[t], MD = zd[P + t];
     if (n < 0) {
         if (!out_agg) return;
         out_agg[t] = KD;
         if (n_het > 1) out_agg[P + t] = ((1.0 + r) * AD + w * ZD + tr * MD) - KD;
+        for (int jx = 0; jx < NX; jx++) out_agg[(size_t)(2 + jx) * P + t] = hxS[((size_t)t * NX + jx) * HX_NS];
         return;
     }
     if (!out_dagg) return;
     const double dKD = dagg[(size_t)n * P + t], dAD = dagg[((size_t)N + n) * P + t];
     const double *dx = dxhh + ((size_t)n * P + t) * n_hh;
+    const double dtr = n_hh > 2 ? dx[2] : 0.0;
     out_dagg[((size_t)n * n_het) * P + t] = dKD;
-    if (n_het > 1) out_dagg[((size_t)n * n_het + 1) * P + t] = (dx[0] * AD + dx[1] * ZD + (n_hh > 2 ? dx[2] : 0.0) * MD + (1.0 + r) * dAD) - dKD;
+    if (n_het > 1) out_dagg[((size_t)n * n_het + 1) * P + t] = (dx[0] * AD + dx[1] * ZD + dtr * MD + (1.0 + r) * dAD) - dKD;
+    for (int jx = 0; jx < NX; jx++) {
+        const double *S = hxS + ((size_t)t * NX + jx) * HX_NS;      // Y, Sa, Sz, S1, Sr
+        out_dagg[((size_t)n * n_het + 2 + jx) * P + t] = hxT[((size_t)n * P + t) * NX + jx] + dx[0] * (S[1] + S[4]) + dx[1] * S[2] + dtr * S[3];
+    }
+}
+
+// the policy partials of the last tangent sweep, whichever family ran it, as [n][t][pt] (the (G, P, N) export layout)
+static int export_dpol_dev(hank_ctx *ctx, int N, double *out) {
+    const size_t total = (size_t)ctx->c.P * ctx->c.G * N;
+    if (ctx->last_tan == 2) {
+        hipLaunchKernelGGL(k_wide_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->wcur->dpol, ctx->c.G, ctx->c.P, N, out);
+    } else if (ctx->last_tan == 1) {
+        for (const XPass &ps : ctx->xcur->passes) {
+            const size_t cnt = (size_t)ctx->c.P * ctx->c.G * ps.N;
+            hipLaunchKernelGGL(k_xexport_dpol, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, ctx->xcur->dpol + ps.dpol_off, ctx->c.G,
+                               ctx->c.P, ps.groups, ps.D, ps.n0, ps.N, out);
+        }
+    } else {
+        hipLaunchKernelGGL(k_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->tw->dpol, ctx->c.G, ctx->c.P, N, out);
+    }
+    HIPC(ctx, hipGetLastError());
+    return HANK_OK;
+}
+
+// outputs 2 .. n_het-1: the direction-independent sums (S), and — for N > 0 — the in-period sums of every direction (T) from one
+// forward tangent recurrence over the exported policy partials (hank_hetx.h). The buffers live in the context (hx_slab: one
+// allocation, grown when a wider batch asks, reused in stream order), so the _dev form stays asynchronous.
+static int hx_outputs(hank_ctx *ctx, int NX, int N, double **S_out, double **T_out) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P, G = c.G;
+    const int nbr = (c.n_a + HX_ROWS - 1) / HX_ROWS;
+    const size_t sz[8] = {NX * P * G, NX * P * G, P * NX * HX_NS, P * G * N, G * N, G * N, (size_t)N * P * nbr * NX, (size_t)N * P * NX};
+    size_t need = 0;
+    for (size_t k : sz) need += (sizeof(double) * k + 255) / 256 * 256;
+    if (need > ctx->hx_bytes) {
+        if (ctx->hx_slab) { HIPC(ctx, hipStreamSynchronize(ctx->stream)); HIPC(ctx, hipFree(ctx->hx_slab)); ctx->hx_slab = nullptr; ctx->hx_bytes = 0; }
+        HIPC(ctx, hipMalloc(&ctx->hx_slab, need));
+        ctx->hx_bytes = need;
+    }
+    double *buf[8];
+    size_t off = 0;
+    for (int k = 0; k < 8; k++) { buf[k] = reinterpret_cast<double *>(ctx->hx_slab + off); off += (sizeof(double) * sz[k] + 255) / 256 * 256; }
+    double *f = buf[0], *fc = buf[1], *S = buf[2];
+    hipLaunchKernelGGL(k_hx_record, dim3((unsigned)P, (unsigned)NX), dim3(256), 0, ctx->stream, c, ctx->R, ctx->d_xhh, NX, f, fc, S);
+    HIPC(ctx, hipGetLastError());
+    *S_out = S;
+    *T_out = nullptr;
+    if (N == 0) return HANK_OK;
+    double *dpc = buf[3], *mid = buf[4], *dD = buf[5], *parts = buf[6], *T = buf[7];
+    int rc = export_dpol_dev(ctx, N, dpc);
+    if (rc) return rc;
+    const dim3 gmid((unsigned)((G + HX_ROWS - 1) / HX_ROWS), (unsigned)N), gmix((unsigned)nbr, (unsigned)N);
+    for (size_t t = 0; t < P; t++) {
+        hipLaunchKernelGGL(k_hx_mid, gmid, dim3(HX_ROWS), 0, ctx->stream, c, ctx->R, (int)t, dpc, dD, mid);
+        hipLaunchKernelGGL(k_hx_mix, gmix, dim3(HX_ROWS), 0, ctx->stream, c, ctx->R, (int)t, NX, dpc, mid, f, fc, dD, parts);
+    }
+    const size_t cnt = (size_t)N * P * NX;
+    hipLaunchKernelGGL(k_hx_reduce, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, parts, nbr, NX, cnt, T);
+    HIPC(ctx, hipGetLastError());
+    *T_out = T;
+    return HANK_OK;
 }
 
 static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double *agg_out, double *dagg_out, bool dev) {
     if (!ctx) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
-    if (n_het < 1 || n_het > 2 || N < 0 || (!agg_out && !dagg_out)) return fail(ctx, HANK_ERR_BAD_ARG, "n_het must be 1 or 2 (the policy variable, consumption), N >= 0");
+    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
+    if (n_het < 1 || n_het > max_het || N < 0 || (!agg_out && !dagg_out))
+        return fail(ctx, HANK_ERR_BAD_ARG, "n_het must be 1..%d (the policy variable, consumption, Value%s), N >= 0", max_het, max_het > 3 ? ", UCE" : "");
+    if (n_het > ctx->n_het) return fail(ctx, HANK_ERR_NOT_READY, "%d outputs asked for, %d declared: call hank_set_het_outputs first", n_het, ctx->n_het);
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
     const size_t P = ctx->c.P, nh = ctx->c.n_hh;
     const bool tan = dagg_out && N > 0;
@@ -2050,8 +2122,13 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
         if (agg_out) HIPC(ctx, sc.alloc(&d_a, P * n_het));
     }
     const int Nk = tan ? N : 0;
+    double *hxS = nullptr, *hxT = nullptr;
+    if (n_het > 2) {
+        int rc = hx_outputs(ctx, n_het - 2, Nk, &hxS, &hxT);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * (Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, Nk, ctx->d_xhh,
-                       d_dx, ctx->d_agg, src, ctx->d_zd, d_a, tan ? d_da : nullptr);
+                       d_dx, ctx->d_agg, src, ctx->d_zd, hxS, hxT, d_a, tan ? d_da : nullptr);
     HIPC(ctx, hipGetLastError());
     if (!dev) {
         if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, d_a, sizeof(double) * P * n_het, hipMemcpyDeviceToHost, ctx->stream));
@@ -2066,6 +2143,15 @@ int hank_get_het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32
 }
 int hank_get_het_outputs_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, int32_t N, double *d_agg_out, double *d_dagg_out) {
     return het_outputs(ctx, n_het, d_dxhh, N, d_agg_out, d_dagg_out, true);
+}
+int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
+    if (n_het < 1 || n_het > max_het) return fail(ctx, HANK_ERR_BAD_ARG, "n_het must be 1..%d for this value-function family", max_het);
+    if (n_het != ctx->n_het) ctx->memo_valid = false;      // the next hank_primal_jvp records its primal afresh
+    ctx->n_het = n_het;
+    return HANK_OK;
 }
 }
 

@@ -26,7 +26,7 @@ ABI_SYMBOLS = (
     "hank_create", "hank_create_on", "hank_gather_columns", "hank_destroy", "hank_last_error", "hank_n_hh", "hank_set_stream", "hank_sync",
     "hank_set_boundary", "hank_primal", "hank_jvp", "hank_primal_dev", "hank_jvp_dev", "hank_check",
     "hank_primal_jvp", "hank_primal_jvp_dev",
-    "hank_get_policy_seq", "hank_get_dpolicy_seq", "hank_get_dist_seq", "hank_get_het_outputs", "hank_get_het_outputs_dev",
+    "hank_get_policy_seq", "hank_get_dpolicy_seq", "hank_get_dist_seq", "hank_get_het_outputs", "hank_get_het_outputs_dev", "hank_set_het_outputs",
     "hank_get_grid_aggregates", "hank_get_grid_aggregates_dev", "hank_backward_step",
     "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_device_available",
 )
@@ -100,6 +100,7 @@ def load_library() -> C.CDLL:
     lib.hank_get_dist_seq.argtypes = [vp, dp]
     lib.hank_get_het_outputs.argtypes = [vp, i32, dp, i32, dp, dp]
     lib.hank_get_het_outputs_dev.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.hank_set_het_outputs.argtypes = [vp, i32]
     lib.hank_get_grid_aggregates.argtypes = [vp, dp, i32, dp]
     lib.hank_get_grid_aggregates_dev.argtypes = [vp, vp, i32, vp]
     lib.hank_backward_step.argtypes = [vp, dp, dp, dp, dp]
@@ -319,7 +320,8 @@ class HouseholdBlock:
 
     def het_outputs(self, n_het: int = 2, dxhh=None):
         """every heterogeneous variable's aggregate of the last sweeps (hank_get_het_outputs; ForwardIteration.jl:303-307):
-        output 0 the policy variable (KD / A), output 1 consumption. -> agg (P, n_het), and dagg (P, n_het, N) when `dxhh`
+        output 0 the policy variable (KD / A), output 1 consumption, output 2 Value, output 3 UCE (one-asset HANK), up to the
+        count declared with `set_het_outputs`. -> agg (P, n_het), and dagg (P, n_het, N) when `dxhh`
         (n_hh, P, N) — the input of the last tangent sweep — is given (else None)."""
         agg = np.empty((self.P, n_het), order="F")
         if dxhh is None:
@@ -332,6 +334,11 @@ class HouseholdBlock:
         dagg = np.empty((self.P, n_het, N), order="F")
         self._chk(self._lib.hank_get_het_outputs(self._ctx, int(n_het), _p(dxhh), N, _p(agg), _p(dagg)))
         return agg, dagg
+
+    def set_het_outputs(self, n_het: int):
+        """declare how many heterogeneous outputs het_outputs will be asked for (hank_set_het_outputs; default 2)."""
+        self._chk(self._lib.hank_set_het_outputs(self._ctx, int(n_het)))
+        self._n_het_declared = int(n_het)
 
     def het_outputs_dev(self, n_het: int, d_dxhh: int, N: int, d_agg: int, d_dagg: int):
         """device-pointer form (asynchronous on the context's stream)."""

@@ -33,9 +33,16 @@ end
 
 # native kernel families by value-function name: id (include/hank_hip.h), the household inputs it reads, and the heterogeneous
 # variables it returns (output 1 = the policy variable of the endogenous dimension, output 2 = consumption, the c_grid of
-# KrusellSmith.jl:79 returned as a second policy: hank_get_het_outputs)
-const _FAMILIES = Dict(:ValueFunction => (0, (:r, :w), (:KD, :C)),                # KrusellSmith.jl:43-83, :53-54
-                       :HANKValueFunction => (1, (:r, :om, :Tr), (:A, :C)))      # one-asset HANK (not in the reference)
+# KrusellSmith.jl:79 returned as a second policy, output 3 = Value = (1+r) c^-γ, KrusellSmith.jl:80, output 4 = UCE = z_e c^-γ:
+# hank_get_het_outputs)
+const _FAMILIES = Dict(:ValueFunction => (0, (:r, :w), (:KD, :C, :Value)),                  # KrusellSmith.jl:43-83, :53-54
+                       :HANKValueFunction => (1, (:r, :om, :Tr), (:A, :C, :Value, :UCE)))  # one-asset HANK (not in the reference)
+
+# declare how many of the family's outputs the next hank_get_het_outputs reads (BackwardIteration.jl:99-112 keeps one sequence per
+# key listed under `heterogeneous:`); the outputs up to the last listed key
+_n_het(ctx::HankCtx, het_keys) = maximum(k -> findfirst(==(Symbol(k)), ctx.outputs), het_keys)
+hank_set_het_outputs(ctx::HankCtx, n_het::Integer) =
+    _check(ctx.ptr, ccall((:hank_set_het_outputs, LIBHANK), Cint, (Ptr{Cvoid}, Int32), ctx.ptr, Int32(n_het)))
 
 # one device context per (SequenceModel, HIP device); device -1 = the current one. Keyed on the model ITSELF (an IdDict keeps it
 # alive: an objectid can be recycled by a later model and hand it a context built for other grids) and guarded by a lock:
@@ -105,6 +112,7 @@ end
 function _run_block!(s::DevicePolicySeqs, D0::Vector{Float64})
     ctx = s.ctx
     _check(ctx.ptr, ccall((:hank_set_boundary, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, s.value, D0))
+    length(s.het_keys) > 1 && hank_set_het_outputs(ctx, max(_n_het(ctx, s.het_keys), 2))
     agg = Vector{Float64}(undef, ctx.P)
     dagg = nothing
     if s.dxhh === nothing
@@ -116,7 +124,7 @@ function _run_block!(s::DevicePolicySeqs, D0::Vector{Float64})
     end
     s.D0, s.agg, s.dagg = D0, agg, dagg
     if length(s.het_keys) > 1     # every heterogeneous variable's aggregate, reduced by the same sweeps (ForwardIteration.jl:303-307)
-        n_het = length(ctx.outputs)
+        n_het = _n_het(ctx, s.het_keys)
         s.aggs = Matrix{Float64}(undef, ctx.P, n_het)
         s.daggs = s.dxhh === nothing ? nothing : Array{Float64}(undef, ctx.P, n_het, s.N)
         _check(ctx.ptr, ccall((:hank_get_het_outputs, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
