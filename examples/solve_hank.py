@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """One-asset HANK (examples/one_asset_hank.yaml; NOT in the reference) through the same
-sequence as examples/solve_transition.py: YAML -> calibrate the bond supply -> steady state (host) -> J̅ (batched
-unit-tangent JVPs on the GPU, household family HANK_VF_ONE_ASSET_HANK) -> NewtonRaphsonHANK -> the perfect-foresight
+sequence as examples/solve_transition.py: YAML -> calibrate the bond supply -> steady state -> J̅ (its Toeplitz structure:
+one set of backward tangent sweeps on the GPU for every heterogeneous variable, hank_fake_news / hank_fake_news_het, household
+family HANK_VF_ONE_ASSET_HANK; --jacobian columns: batched unit-tangent JVPs) -> NewtonRaphsonHANK -> the perfect-foresight
 response to a monetary-policy shock.
 
     python examples/solve_hank.py [--n-a 1000 --n-e 7 --T 500 --shock 0.0025]

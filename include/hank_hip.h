@@ -248,6 +248,21 @@ int hank_stationary_dist(hank_ctx *ctx, const double *policy, double *D_io, doub
  * J_k[t, 0] = F[t, 0, k] for t > 0 (0-based; hank_amd.SteadyStateJacobian.household_jacobian does the recursion). */
 int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out);
 
+/* hank_fake_news_het: the same Toeplitz form for the first n_het heterogeneous outputs of hank_get_het_outputs (0 the policy
+ * variable KD / A, 1 consumption, 2 Value, 3 UCE for the one-asset HANK): n_het is 1..3 for Krusell-Smith, 1..4 for the
+ * one-asset HANK, else HANK_ERR_BAD_ARG. Every output is Y^o_t = sum f_o D_t with the same post-transition D_t
+ * (ForwardIteration.jl:303-307), so the policy responses Y_j and the lottery impulses iota_j are shared; per output only the
+ * expectation vectors E^o_0 = f_o,ss, E^o_{u+1} = T' E^o_u and the direct term differ:
+ *   F_out  (P, P, n_hh, n_het) column-major: F[u, j, k, o] = E^o_u . iota_{j,k}
+ *   Dv_out (P, n_hh, n_het):     Dv[j, k, o] = sum D_ss (d f_o / d a') Y_{j,k} + [j == 0] d_{o,k}, d_{o,k} the same-period
+ *          effect of input k on output o at the steady state (0 for o = 0; sum D (a, z_e, 1) for consumption; the Sa + Sr, Sz,
+ *          S1 of hank_get_het_outputs for Value and UCE)
+ * Output 0 equals hank_fake_news's F and Dv bit for bit; each output's J follows from the same recursion. The multi-output
+ * J̅ has no counterpart in the reference (its slicing assumes one heterogeneous variable, SteadyStateJacobian.jl:295-303).
+ * Same precondition and HANK_ERR_NOT_READY cases as hank_fake_news; independent of hank_set_het_outputs, which it leaves
+ * unchanged. */
+int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------------------
  * Device time, in milliseconds, of the sweeps of the most recent hank_primal[_dev]/hank_jvp[_dev],
  * from HIP events recorded on the context's stream around each sweep:

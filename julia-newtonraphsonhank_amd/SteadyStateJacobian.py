@@ -70,7 +70,9 @@ def getSteadyStateJacobian(ss, model: SequenceModel, chunk: int = 512, drop_tol:
 
     method="toeplitz" (default): the reference's own structure — direct blocks of the equations (:124-145) plus the
     household block's Jacobian from its Toeplitz recursion (:187-256, :293-323, :358-387), obtained on the device from
-    n_hh backward tangent sweeps seeded at the last period (`hank_fake_news`) instead of n unit tangents.
+    n_hh backward tangent sweeps seeded at the last period (`hank_fake_news`) instead of n unit tangents; a model with more
+    than one heterogeneous variable (or one that is not the policy variable) gets every variable's Jacobian from the same
+    sweeps (`hank_fake_news_het`: the reference's slicing assumes one heterogeneous variable, :295-303, the maths does not).
     method="columns": n unit-tangent JVPs of the full pipeline (`chunk` per call; only those that move the household
     inputs reach the GPU, in device batches padded to `device_batch`), sharded over the ranks of `group` — exact at ANY
     primal path, and the check of the other branch (they agree to ~1e-10 at a converged steady state)."""
@@ -85,15 +87,17 @@ def getSteadyStateJacobian(ss, model: SequenceModel, chunk: int = 512, drop_tol:
     x_ss = np.tile(np.array([ss.vars[k] for k in endog_keys]), P)
     exog_ss = {k: np.full(P, float(ss.vars[k])) for k in exog_keys}
     lin = LinearizedFunction(x_ss, exog_ss, model, ss, ss)
-    if method == "toeplitz" and len(lin.het) > 1:
-        # hank_fake_news carries the expectation vectors of the policy variable's aggregate only: a model with a second
-        # heterogeneous variable takes the unit-tangent columns (exact at any path; n JVPs in device batches)
-        method = "columns"
     if method == "toeplitz":
         from .GeneralStructures import var_names
         keys = var_names(model)
         n_eq, n_endog = len(model.equations), cs.n_endog
-        Jhh = household_jacobian(*lin.hb.fake_news())                  # (n_hh, P, P)
+        # one household Jacobian (n_hh, P, P) per heterogeneous variable, from its device output (LinearizedFunction's rule:
+        # value_fn.outputs.index(key)); all of them from ONE set of tangent sweeps (hank_fake_news_het)
+        if lin._n_out == 1:
+            Jhh = {lin.het[0]: household_jacobian(*lin.hb.fake_news())}
+        else:
+            F, Dv = lin.hb.fake_news_het(lin._n_out)
+            Jhh = {h: household_jacobian(F[..., o], Dv[..., o]) for h, o in zip(lin.het, lin._out_idx)}
         B = direct_blocks(model, ss)
         J4 = np.zeros((P, n_eq, P, n_endog))                           # [t, eq, s, j]  ->  row eq + n_eq t, column j + n_endog s
         tt = np.arange(P)
@@ -113,7 +117,7 @@ def getSteadyStateJacobian(ss, model: SequenceModel, chunk: int = 512, drop_tol:
                     if name not in endog_keys:
                         continue                                       # an exogenous household input: no column of J̅
                     M = np.zeros((P, P))
-                    M[tt[ok]] = Jhh[kk][tt[ok] + o]
+                    M[tt[ok]] = Jhh[h][kk][tt[ok] + o]
                     jcol = endog_keys.index(name)
                     for q in np.flatnonzero(colh):                      # (the few equations the aggregate enters)
                         J4[:, q, :, jcol] += colh[q] * M

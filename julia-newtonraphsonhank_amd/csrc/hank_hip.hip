@@ -136,7 +136,7 @@ struct hank_ctx {
     int last_tan = 0;              // which implementation ran the last tangent sweep (0 launches, 1 persistent): hank_get_dpolicy_seq
     int xjvp_max = 64;             // auto: batches up to this width take the persistent tangent sweeps (measured crossover)
     XWork xw;
-    struct { double *dpT = nullptr, *iota = nullptr, *E = nullptr, *Cp = nullptr, *F = nullptr, *Dv = nullptr; int N = 0; } fn;   // hank_fake_news workspace
+    struct { double *dpT = nullptr, *iota = nullptr, *E = nullptr, *Cp = nullptr, *F = nullptr, *Dv = nullptr, *W = nullptr, *dsum = nullptr; int N = 0, n_het = 0; } fn;   // hank_fake_news[_het] workspace (E, Cp, F, Dv, W, dsum sized for n_het outputs)
     XTan *xcur = nullptr;          // tangent buffers of the last xcd-schedule JVP
     // on-chip wide sweeps: 0 = never, 1 = auto (batches of at least wide_min directions), 2 = every batch (HANK_SCHEDULE=wide: tests)
     int wide_mode = 0, wide_min = 80, num_cus = 256, wide_r = 2;     // wide_r: rows per thread of the wide kernels (2: 1024-thread workgroups, 4 waves per SIMD — since the L2 warming of round 5 the faster geometry for both sweeps, 5.16 / 6.80 ms against 5.30 / 7.10 at N=256; dev knob HANK_WIDE_R=2|4 at hank_create)
@@ -166,6 +166,7 @@ struct hank_ctx {
 };
 
 static int fail(hank_ctx *ctx, int code, const char *fmt, ...);
+static void free_fn(hank_ctx *ctx);
 static void w_invalidate(hank_ctx *ctx) { for (WTan &t : ctx->wtans) t.valid = false; }
 static void w_new_primal(hank_ctx *ctx) { ctx->wprep_valid = false; }      // (the record is about to be rewritten)
 static void w_free_tan(WTan &w) {
@@ -1216,7 +1217,7 @@ int hank_destroy(hank_ctx *ctx) {
     ctx->tws.clear();
     ctx->tw = nullptr;
     x_free(ctx);
-    (void)hipFree(ctx->fn.dpT); (void)hipFree(ctx->fn.iota); (void)hipFree(ctx->fn.E); (void)hipFree(ctx->fn.Cp); (void)hipFree(ctx->fn.F); (void)hipFree(ctx->fn.Dv);
+    free_fn(ctx);
     if (ctx->ev_stream) (void)hipEventDestroy(ctx->ev_stream);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_side) (void)hipEventDestroy(ctx->ev_side);
@@ -1673,18 +1674,49 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
     return HANK_OK;
 }
 
+static void free_fn(hank_ctx *ctx) {
+    (void)hipFree(ctx->fn.dpT); (void)hipFree(ctx->fn.iota); (void)hipFree(ctx->fn.E); (void)hipFree(ctx->fn.Cp); (void)hipFree(ctx->fn.F); (void)hipFree(ctx->fn.Dv);
+    (void)hipFree(ctx->fn.W); (void)hipFree(ctx->fn.dsum);
+    ctx->fn = {};
+}
+
+// the fake-news workspace for n_het outputs: allocated at the first call, grown (all of it, after the stream drains) when a
+// call asks for more outputs than it holds
+static int ensure_fn(hank_ctx *ctx, int n_het) {
+    if (ctx->fn.n_het >= n_het) return HANK_OK;
+    const size_t P = ctx->c.P, G = ctx->c.G, NP = P * ctx->c.n_hh, S = 16, nh = n_het;
+    if (ctx->fn.dpT) HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    free_fn(ctx);
+    auto alloc = [&]() -> int {
+        HIPC(ctx, dmalloc(&ctx->fn.dpT, G * NP)); HIPC(ctx, dmalloc(&ctx->fn.iota, G * NP));
+        HIPC(ctx, dmalloc(&ctx->fn.E, nh * P * G)); HIPC(ctx, dmalloc(&ctx->fn.Cp, S * nh * P * NP));
+        HIPC(ctx, dmalloc(&ctx->fn.F, nh * P * NP)); HIPC(ctx, dmalloc(&ctx->fn.Dv, nh * NP));
+        HIPC(ctx, dmalloc(&ctx->fn.W, nh * G)); HIPC(ctx, dmalloc(&ctx->fn.dsum, nh * ctx->c.n_hh));
+        return HANK_OK;
+    };
+    const int rc = alloc();
+    if (rc) {
+        free_fn(ctx);
+        (void)hipGetLastError();
+        return rc;
+    }
+    ctx->fn.n_het = n_het;
+    return HANK_OK;
+}
+
 // The household block's sequence-space Jacobian at a stationary primal from its Toeplitz structure (hank_jacobian.h):
-// F (P, P, n_hh) and Dv (P, n_hh), column-major. Requires hank_primal at the constant steady-state path with the steady
-// state as both boundaries (what getSteadyStateJacobian builds, SteadyStateJacobian.jl:53-57).
-int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out) {
-    ENTER(ctx);
-    if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
-    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_fake_news");
+// F (P, P, n_hh[, n_het]) and Dv (P, n_hh[, n_het]), column-major. Requires hank_primal at the constant steady-state path
+// with the steady state as both boundaries (what getSteadyStateJacobian builds, SteadyStateJacobian.jl:53-57).
+// n_het == 0: hank_fake_news (the policy variable's aggregate: E_0 = pol_ss, Dv weights D_ss); n_het >= 1: hank_fake_news_het
+// (outputs 0 .. n_het-1 of hank_get_het_outputs; output 0 is the same arithmetic as n_het == 0, bit for bit).
+static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
+    const char *name = n_het ? "hank_fake_news_het" : "hank_fake_news";
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before %s", name);
     if (!ctx->stationary)
-        return fail(ctx, HANK_ERR_NOT_READY, "hank_fake_news needs the recorded primal to be hank_primal at a CONSTANT path (the steady state; SteadyStateJacobian.jl:53-57): "
-                    "the last primal was recorded at a path that varies over time, or through a device-pointer entry");
+        return fail(ctx, HANK_ERR_NOT_READY, "%s needs the recorded primal to be hank_primal at a CONSTANT path (the steady state; SteadyStateJacobian.jl:53-57): "
+                    "the last primal was recorded at a path that varies over time, or through a device-pointer entry", name);
     const Consts &c = ctx->c;
-    const int P = c.P, G = c.G, N = c.n_hh, NP = P * N, S = 16;
+    const int P = c.P, G = c.G, N = c.n_hh, NP = P * N, S = 16, nh = n_het ? n_het : 1;
     hipStream_t s = ctx->stream;
     {   // ... and to be stationary: the policy of the first period equals the policy of the last (a constant path that is not the
         // steady state of the boundary drifts; 1e-6 of the policy's scale is far above a converged value iteration's 1e-11)
@@ -1696,8 +1728,8 @@ int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out) {
         double scale = 0.0, diff = 0.0;
         for (int k = 0; k < G; k++) { scale = std::max(scale, fabs(p1[k])); diff = std::max(diff, fabs(p0[k] - p1[k])); }
         if (!(diff <= 1e-6 * std::max(scale, 1e-300)))
-            return fail(ctx, HANK_ERR_NOT_READY, "hank_fake_news: the recorded primal is not stationary (policy of period 1 and of period %d differ by %.3g): "
-                        "it needs hank_primal at the steady state with the steady state as both boundaries", P, diff);
+            return fail(ctx, HANK_ERR_NOT_READY, "%s: the recorded primal is not stationary (policy of period 1 and of period %d differ by %.3g): "
+                        "it needs hank_primal at the steady state with the steady state as both boundaries", name, P, diff);
     }
     { const int src = ensure_seg(ctx); if (src) return src; }
     // 1. n_hh backward tangent sweeps (one batch) seeded at the last period: every lag of the policy response
@@ -1706,21 +1738,8 @@ int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out) {
     TanWork &w = *ctx->tw;
     rc = ensure_graphs(ctx, w, 0);
     if (rc) return rc;
-    if (!ctx->fn.dpT) {
-        auto alloc = [&]() -> int {
-            HIPC(ctx, dmalloc(&ctx->fn.dpT, (size_t)G * NP)); HIPC(ctx, dmalloc(&ctx->fn.iota, (size_t)G * NP));
-            HIPC(ctx, dmalloc(&ctx->fn.E, (size_t)P * G)); HIPC(ctx, dmalloc(&ctx->fn.Cp, (size_t)S * P * NP));
-            HIPC(ctx, dmalloc(&ctx->fn.F, (size_t)P * NP)); HIPC(ctx, dmalloc(&ctx->fn.Dv, (size_t)NP));
-            return HANK_OK;
-        };
-        rc = alloc();
-        if (rc) {
-            (void)hipFree(ctx->fn.dpT); (void)hipFree(ctx->fn.iota); (void)hipFree(ctx->fn.E); (void)hipFree(ctx->fn.Cp); (void)hipFree(ctx->fn.F); (void)hipFree(ctx->fn.Dv);
-            ctx->fn = {};
-            (void)hipGetLastError();
-            return rc;
-        }
-    }
+    rc = ensure_fn(ctx, nh);
+    if (rc) return rc;
     HIPC(ctx, join_side(ctx));      // D_1 and the {w, ig D} records come from the primal's forward sweep
     hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
     HIPC(ctx, hipGraphLaunch(w.g_back, s));
@@ -1729,32 +1748,62 @@ int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out) {
     // 2. the lottery impulse of every lag and input at once
     hipLaunchKernelGGL(k_fn_transpose, dim3((unsigned)((G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256), 0, s, w.dpol, P, G, N, ctx->fn.dpT);
     hipLaunchKernelGGL(k_fn_impulse, dim3((unsigned)c.n_a, (unsigned)((NP + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.dpT, NP, ctx->fn.iota);
-    // 3. the expectation vectors E_u = (T')^u pol_ss
-    HIPC(ctx, hipMemcpyAsync(ctx->fn.E, ctx->R.pol, sizeof(double) * G, hipMemcpyDeviceToDevice, s));
-    for (int u = 0; u + 1 < P; u++)
-        hipLaunchKernelGGL(k_fn_expect, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.E + (size_t)u * G, ctx->fn.E + (size_t)(u + 1) * G);
-    // 4. F = E iota, Dv = D_ss' dpT
-    const int kchunk = ((G + S - 1) / S + 15) / 16 * 16;
-    hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), (unsigned)((P + 63) / 64), (unsigned)S), dim3(256), 0, s, ctx->fn.E, ctx->fn.iota, ctx->fn.Cp, P, NP, G, kchunk);
-    hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)((P * NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, P * NP, S, ctx->fn.F);
-    hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), 1, (unsigned)S), dim3(256), 0, s, ctx->R.Dseq + G, ctx->fn.dpT, ctx->fn.Cp, 1, NP, G, kchunk);
-    hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, NP, S, ctx->fn.Dv);
+    // 3. the expectation vectors E^o_u = (T')^u f_o,ss of every output (rows o*P + u of E) and the direct term's weights
+    const size_t PG = (size_t)P * G;
+    const double *Wd = ctx->R.Dseq + G;
+    if (n_het) {
+        hipLaunchKernelGGL(k_fn_het_record, dim3((unsigned)nh), dim3(256), 0, s, c, ctx->R, ctx->d_xhh, PG, ctx->fn.E, ctx->fn.W, ctx->fn.dsum);
+        for (int u = 0; u + 1 < P; u++)
+            hipLaunchKernelGGL(k_fn_expect_het, dim3((unsigned)((G + 255) / 256), (unsigned)nh), dim3(256), 0, s, c, ctx->R, ctx->fn.E, PG, u);
+        Wd = ctx->fn.W;
+    } else {
+        HIPC(ctx, hipMemcpyAsync(ctx->fn.E, ctx->R.pol, sizeof(double) * G, hipMemcpyDeviceToDevice, s));
+        for (int u = 0; u + 1 < P; u++)
+            hipLaunchKernelGGL(k_fn_expect, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.E + (size_t)u * G, ctx->fn.E + (size_t)(u + 1) * G);
+    }
+    // 4. F = E iota, Dv = W dpT (the K split depends on G only: every output's elements are summed in the same order)
+    const int kchunk = ((G + S - 1) / S + 15) / 16 * 16, MP = nh * P;
+    hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), (unsigned)((MP + 63) / 64), (unsigned)S), dim3(256), 0, s, ctx->fn.E, ctx->fn.iota, ctx->fn.Cp, MP, NP, G, kchunk);
+    hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)(((size_t)MP * NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, MP * NP, S, ctx->fn.F);
+    hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), (unsigned)((nh + 63) / 64), (unsigned)S), dim3(256), 0, s, Wd, ctx->fn.dpT, ctx->fn.Cp, nh, NP, G, kchunk);
+    hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)((nh * NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, nh * NP, S, ctx->fn.Dv);
     HIPC(ctx, hipGetLastError());
-    std::vector<double> hF((size_t)P * NP), hD((size_t)NP);
+    std::vector<double> hF((size_t)MP * NP), hD((size_t)nh * NP), hd((size_t)nh * N, 0.0);
     HIPC(ctx, hipMemcpyAsync(hF.data(), ctx->fn.F, sizeof(double) * hF.size(), hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipMemcpyAsync(hD.data(), ctx->fn.Dv, sizeof(double) * hD.size(), hipMemcpyDeviceToHost, s));
+    if (n_het) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
     rc = fetch_device_error(ctx);
     if (rc) return rc;
-    // column n' = t*N + k of the device arrays is lag j = P-1-t of input k
-    for (int k = 0; k < N; k++)
-        for (int t = 0; t < P; t++) {
-            const int j = P - 1 - t;
-            Dv_out[j + (size_t)P * k] = hD[(size_t)t * N + k];
-            for (int u = 0; u < P; u++) F_out[u + (size_t)P * (j + (size_t)P * k)] = hF[(size_t)u * NP + (size_t)t * N + k];
-        }
+    // column n' = t*N + k of the device arrays is lag j = P-1-t of input k; the same-period effect d_{o,k} lands at lag 0
+    for (int o = 0; o < nh; o++)
+        for (int k = 0; k < N; k++)
+            for (int t = 0; t < P; t++) {
+                const int j = P - 1 - t;
+                const size_t ko = (size_t)k + (size_t)N * o;
+                const double dv = hD[(size_t)o * NP + (size_t)t * N + k];
+                Dv_out[j + (size_t)P * ko] = (o > 0 && j == 0) ? dv + hd[ko] : dv;
+                for (int u = 0; u < P; u++) F_out[u + (size_t)P * (j + (size_t)P * ko)] = hF[((size_t)o * P + u) * NP + (size_t)t * N + k];
+            }
     ctx->errmsg[0] = 0;
     return HANK_OK;
+}
+
+int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out) {
+    ENTER(ctx);
+    if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
+    return fake_news(ctx, 0, F_out, Dv_out);
+}
+
+// every heterogeneous output at once (hank_jacobian.h): F (P, P, n_hh, n_het), Dv (P, n_hh, n_het). Independent of the
+// hank_set_het_outputs declaration, which it leaves as it is.
+int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out) {
+    ENTER(ctx);
+    if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
+    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
+    if (n_het < 1 || n_het > max_het)
+        return fail(ctx, HANK_ERR_BAD_ARG, "n_het must be 1..%d (the policy variable, consumption, Value%s)", max_het, max_het > 3 ? ", UCE" : "");
+    return fake_news(ctx, n_het, F_out, Dv_out);
 }
 
 #ifdef HANK_XSTAMP

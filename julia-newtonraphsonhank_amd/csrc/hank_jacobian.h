@@ -12,6 +12,7 @@
 // J[t, s] = J[t-1, s-1] + F[t, s] (:363-371). 598 unit tangents become 2.
 #pragma once
 #include "hank_kernels.h"
+#include "hank_hetx.h"
 
 namespace hank {
 
@@ -57,9 +58,7 @@ __global__ void __launch_bounds__(256) k_fn_impulse(Consts c, Record R, const do
 }
 
 // E_next[j, e] = (1 - w_j) U[lo_j, e] + w_j U[lo_j + 1, e],  U[r, e] = sum_e2 Pi[e, e2] E[r, e2]   (the transposed forward step)
-__global__ void k_fn_expect(Consts c, Record R, const double *__restrict__ E, double *__restrict__ En) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= c.G) return;
+__device__ inline double fn_expect_at(const Consts &c, const Record &R, const double *__restrict__ E, int idx) {
     const int ne = c.n_e, na = c.n_a, e = idx / na;
     const int lo = R.lo[idx];
     const double w = R.lw[idx];
@@ -69,7 +68,71 @@ __global__ void k_fn_expect(Consts c, Record R, const double *__restrict__ E, do
         u0 += p * E[(size_t)e2 * na + lo];
         u1 += p * E[(size_t)e2 * na + lo + 1];
     }
-    En[idx] = (1.0 - w) * u0 + w * u1;
+    return (1.0 - w) * u0 + w * u1;
+}
+__global__ void k_fn_expect(Consts c, Record R, const double *__restrict__ E, double *__restrict__ En) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= c.G) return;
+    En[idx] = fn_expect_at(c, R, E, idx);
+}
+
+// ---- every heterogeneous output (hank_fake_news_het) ------------------------------------------------------------------------
+// Output o is Y^o_t = sum f_o D_t with the same post-transition D_t for every o (ForwardIteration.jl:303-307), so the policy
+// responses Y_j and the impulses iota_j above serve all outputs; only the expectation vectors and the direct term differ:
+//     E^o_0 = f_o,ss,  E^o_{u+1} = T' E^o_u,  F^o[u, j] = E^o_u . iota_j
+//     Dv^o[j, k] = sum D_ss (df_o/da') Y_{j,k} + [j == 0] d_{o,k}
+// with f_0 = a' (df/da' = 1, d = 0), f_1 = c = (1+r) a + w z_e + tr - a' (-1; d = (sum D a, sum D z_e, sum D)), and f_2 = Value,
+// f_3 = UCE (-f_c; d = (Sa + Sr, Sz, S1), the coefficients of hank_hetx.h at the steady state).
+
+// one block per output o < n_het, at the stationary record (period 0): E0 [o][pt] = f_o (row o of E, `ostride` apart),
+// W [o][pt] = D_ss df_o/da', dsum [o][k] = d_{o,k}. Fixed-order block reductions: the same record gives the same bits.
+__global__ void __launch_bounds__(256) k_fn_het_record(Consts c, Record R, const double *__restrict__ xhh, size_t ostride,
+                                                       double *__restrict__ E0, double *__restrict__ W, double *__restrict__ dsum) {
+    __shared__ double red[16];
+    const int o = blockIdx.x, G = c.G;
+    const double r = xhh[0], w = xhh[1], tr = c.n_hh > 2 ? xhh[2] : 0.0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};      // o = 1: D a, D z, D; o >= 2: Sa, Sz, S1, Sr
+    for (int pt = threadIdx.x; pt < G; pt += blockDim.x) {
+        const double pol = R.pol[pt], D = R.Dseq[G + pt];
+        double f, wt;
+        if (o == 0) {
+            f = pol;
+            wt = D;
+        } else {
+            const int e = pt / c.n_a, ia = pt - e * c.n_a;
+            const double a = c.a[ia], z = c.z[e];
+            const double cons = (1.0 + r) * a + w * z + tr - pol;
+            if (o == 1) {
+                f = cons;
+                wt = -D;
+                acc[0] += D * a; acc[1] += D * z; acc[2] += D;
+            } else {
+                double fc, fr;
+                hx_f(o, c.gamma, r, z, cons, f, fc, fr);
+                wt = -fc * D;
+                acc[0] += fc * D * a; acc[1] += fc * D * z; acc[2] += fc * D; acc[3] += fr * D;
+            }
+        }
+        E0[(size_t)o * ostride + pt] = f;
+        W[(size_t)o * G + pt] = wt;
+    }
+    double tot[4];
+    for (int k = 0; k < 4; k++) tot[k] = block_sum(acc[k], red, blockDim.x);
+    if (threadIdx.x == 0) {
+        double *d = dsum + (size_t)o * c.n_hh;
+        d[0] = tot[0] + tot[3];
+        d[1] = tot[1];
+        if (c.n_hh > 2) d[2] = tot[2];
+    }
+}
+
+// E^o_{u+1} = T' E^o_u for every output in one launch: grid (ceil(G / 256), n_het), output o's vectors `ostride` apart.
+// The arithmetic is k_fn_expect's (fn_expect_at), so output 0 keeps its bits.
+__global__ void k_fn_expect_het(Consts c, Record R, double *__restrict__ E, size_t ostride, int u) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= c.G) return;
+    double *Eu = E + (size_t)blockIdx.y * ostride + (size_t)u * c.G;
+    Eu[c.G + idx] = fn_expect_at(c, R, Eu, idx);
 }
 
 // Cp[z][M][N] = A[M][K-slice z] * B[K-slice z][N]: a plain fp64 product (row-major operands), 64 x 64 tiles, 4 x 4 per thread,

@@ -28,7 +28,7 @@ ABI_SYMBOLS = (
     "hank_primal_jvp", "hank_primal_jvp_dev",
     "hank_get_policy_seq", "hank_get_dpolicy_seq", "hank_get_dist_seq", "hank_get_het_outputs", "hank_get_het_outputs_dev", "hank_set_het_outputs",
     "hank_get_grid_aggregates", "hank_get_grid_aggregates_dev", "hank_backward_step",
-    "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_device_available",
+    "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
 )
 
 
@@ -113,6 +113,7 @@ def load_library() -> C.CDLL:
     lib.hank_vfi.argtypes = [vp, dp, C.c_double, i32, dp, dp, C.POINTER(i32), dp]
     lib.hank_stationary_dist.argtypes = [vp, dp, dp, C.c_double, i32, i32, C.POINTER(i32)]
     lib.hank_fake_news.argtypes = [vp, dp, dp]
+    lib.hank_fake_news_het.argtypes = [vp, i32, dp, dp]
     lib.hank_device_available.argtypes = []
     for name in ABI_SYMBOLS:
         if name != "hank_last_error":
@@ -358,6 +359,16 @@ class HouseholdBlock:
         F = np.empty((self.P, self.P, self.n_hh), order="F")
         Dv = np.empty((self.P, self.n_hh), order="F")
         self._chk(self._lib.hank_fake_news(self._ctx, _p(F), _p(Dv)))
+        return F, Dv
+
+    def fake_news_het(self, n_het: int):
+        """the same Toeplitz form for heterogeneous outputs 0 .. n_het-1 of `het_outputs` (hank_fake_news_het):
+        -> F (P, P, n_hh, n_het), Dv (P, n_hh, n_het); output 0 equals `fake_news()` bit for bit, and
+        `household_jacobian(F[..., o], Dv[..., o])` is d agg^o_t / d xhh_{k,s}."""
+        nb = max(int(n_het), 1)                  # (the library refuses an n_het outside 1..3 / 1..4)
+        F = np.empty((self.P, self.P, self.n_hh, nb), order="F")
+        Dv = np.empty((self.P, self.n_hh, nb), order="F")
+        self._chk(self._lib.hank_fake_news_het(self._ctx, int(n_het), _p(F), _p(Dv)))
         return F, Dv
 
     def vfi(self, value0, xhh_t, tol: float, max_iter: int = 10_000):

@@ -249,6 +249,9 @@ end
 # fake-news matrix F[u, j, k] and the direct term Dv[j, k] of the household block at the steady state; the Toeplitz
 # recursion (:363-371) stays here. Returns J[t, s, k] = d agg_t / d xhh_{k,s} (xhh rows in the order of `ctx.hh_rows`);
 # the caller places it behind the equations' direct blocks (:124-145) exactly where `helper` goes today.
+# A model that lists more than one heterogeneous variable (or one that is not the policy variable) takes hank_fake_news_het:
+# every output is dotted with the same D_t (ForwardIteration.jl:303-307), so one set of sweeps serves all of them; the result
+# is then a Dict of such J per heterogeneous key (the reference's slicing, :295-303, assumes one variable).
 function household_jacobian_toeplitz(model::SequenceModel, ss; device = nothing)
     ctx = hank_context(model; device = device)
     P = ctx.P; n_hh = length(ctx.hh_rows)
@@ -257,8 +260,23 @@ function household_jacobian_toeplitz(model::SequenceModel, ss; device = nothing)
                           Matrix{Float64}(ss.value), Vector{Float64}(ss.D)))
     agg = Vector{Float64}(undef, P)
     _check(ctx.ptr, ccall((:hank_primal, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, xhh, agg))
-    F = Array{Float64}(undef, P, P, n_hh); Dv = Matrix{Float64}(undef, P, n_hh)
-    _check(ctx.ptr, ccall((:hank_fake_news, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, F, Dv))
+    het_keys = Tuple(Symbol.(vars_of_type(model, :heterogeneous)))
+    if length(het_keys) == 1 && het_keys[1] == ctx.outputs[1]
+        F = Array{Float64}(undef, P, P, n_hh); Dv = Matrix{Float64}(undef, P, n_hh)
+        _check(ctx.ptr, ccall((:hank_fake_news, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, F, Dv))
+        return _toeplitz_recursion(F, Dv)
+    end
+    n_het = _n_het(ctx, het_keys)
+    Fh = Array{Float64}(undef, P, P, n_hh, n_het); Dvh = Array{Float64}(undef, P, n_hh, n_het)
+    _check(ctx.ptr, ccall((:hank_fake_news_het, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}),
+                          ctx.ptr, Int32(n_het), Fh, Dvh))
+    return Dict(k => _toeplitz_recursion(Fh[:, :, :, o], Dvh[:, :, o]) for (k, o) in
+                ((k, findfirst(==(k), ctx.outputs)) for k in het_keys))
+end
+
+# J[t, s] = J[t-1, s-1] + F[t, s], J[1, s] = Dv[s] + F[1, s] (:363-371), per household input k
+function _toeplitz_recursion(F::Array{Float64,3}, Dv::Matrix{Float64})
+    P, _, n_hh = size(F)
     J = similar(F)
     for k in 1:n_hh
         J[1, :, k] = Dv[:, k] .+ F[1, :, k]
