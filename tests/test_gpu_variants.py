@@ -1,0 +1,476 @@
+"""The sweep variants the other GPU tests never launch, against the CPU oracle (oracle/hank_oracle.c) at rel 1e-10 + abs 1e-12:
+
+1. a parity matrix over the CRRA curvature and the record layout. gamma picks code paths, not only values: pow_crra's branches
+   (X half x^(-1/gamma), Y half x^(-gamma): rcp at gamma = 1, rcp(x^2) and rsqrt at gamma = 0.5, pow elsewhere), and the record
+   diet (on for gamma in {1, 2}: the tangent sweeps rebuild kc and v; off otherwise, or with HANK_RECORD_DIET=0: they read them,
+   and the wide backward sweep is another template). Every schedule (launch, xcd, wide, auto), both entry points;
+2. the rest of the pipeline at gamma != 2: the device VFI, the Toeplitz Jacobian, the extra heterogeneous outputs;
+3. the shape edges of the persistent and wide families: the 1024-thread persistent family (n_e >= 12), a last 63-row slab full
+   or holding one row, the largest grid the XCD schedule takes and the first it refuses, every instantiated n_e of the wide
+   family in both geometries and both record layouts, and n_a = WIDE_CS.
+
+The boundary (V_T, D_0) of each curvature is the host steady state of a fresh model (never a model ks_setup cached: its params
+are shared by the session). The shape tests take a cheaper boundary, a host VFI iterate and a uniform D_0: parity needs a valid
+boundary, not a stationary one."""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, ks_paths
+
+pytestmark = pytest.mark.gpu
+
+FAMILY = {"launch": "launch-per-period", "xcd": "xcd-persistent", "wide": "on-chip-wide"}
+
+# case: (gamma, HANK_RECORD_DIET or None, the record diet the context must report)
+CASES = {
+    "gamma1": (1.0, None, 1),             # pow_crra: rcp | rcp; diet on, its gamma = 1 arm
+    "gamma0.5": (0.5, None, 0),           # rcp(x^2) | rsqrt: the fast paths swap halves; diet off
+    "gamma1.5": (1.5, None, 0),           # pow | pow
+    "gamma3": (3.0, None, 0),
+    "gamma2-nodiet": (2.0, "0", 0),       # rsqrt | rcp(x^2), kc and v read from the record
+    "gamma1-nodiet": (1.0, "0", 0),
+}
+# the one-asset HANK calibration (the bond supply that clears the asset market) has no steady state at gamma = 0.5 (its Newton
+# step is singular); no other gamma takes the rcp(x^2) | rsqrt pair, so Krusell-Smith alone covers it
+MATRIX = [(fam, case) for fam in ("ks", "hank") for case in CASES if not (fam == "hank" and case == "gamma0.5")]
+
+
+def _close(a, b, rel=1e-10, ab=1e-12, what=""):
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    err = np.max(np.abs(a - b))
+    assert err <= ab + rel * np.abs(b).max(), f"{what}: max err {err:.3e} vs scale {np.abs(b).max():.3e}"
+
+
+def _block(hank, m, schedule, **env):
+    """a context of model m created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
+    env = {"HANK_SCHEDULE": schedule, **env}
+    old = {k: os.environ.get(k) for k in env}
+    for k, v in env.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = str(v)
+    try:
+        wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
+        return hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
+                                   m.value_fn.value_fn_id)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _hank_x(ss, P):
+    t = np.arange(P)
+    return np.stack([ss.vars["r"] + 0.002 * 0.8 ** t, ss.vars["om"] * (1 + 0.01 * 0.7 ** t), ss.vars["Tr"] * (1 - 0.02 * 0.9 ** t)])
+
+
+_ECON = {}
+
+
+def _economy(family, gamma):
+    """(model, steady state, household inputs (n_hh, P), oracle) of Krusell-Smith 130x3 or one-asset HANK 80x3, T = 40, at gamma:
+    a fresh model, its gamma set, its steady state solved on the host (cached per family and gamma)."""
+    key = (family, gamma)
+    if key not in _ECON:
+        import hank_amd as h
+        from oracle.oracle import Oracle
+        spec, n_a = ("krusell_smith.yaml", 130) if family == "ks" else ("one_asset_hank.yaml", 80)
+        m = h.build_model_from_yaml(str(ROOT / "examples" / spec), overrides={"T": 40, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": 3}}})
+        m.params.γ = gamma
+        if family == "hank":
+            from hank_amd import OneAssetHANK as oa
+            m.params.B = oa.calibrate_bond_supply(m)
+        ss, _ = h.get_SteadyStates(m, vfi="host")
+        assert m.params.γ == gamma
+        P = m.compspec.T - 1
+        xhh = ks_paths(m, ss, "x1", 0.05)[0][2:4] if family == "ks" else _hank_x(ss, P)
+        wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
+        _ECON[key] = (m, ss, np.ascontiguousarray(xhh), Oracle(wd.grid, pdm.grid, pdm.transition, gamma=gamma, beta=m.params.β,
+                                                               borrow_cons=m.params.borrow_cons))
+    return _ECON[key]
+
+
+def _oracle(orc, value, D, xhh, y):
+    """the oracle's household block at xhh (n_hh, P) with the partials y (n_hh, P, N), 32 partials per pass ->
+    agg (P,), dagg (P, N), policy (P, n_a, n_e), dpolicy (P, n_a, n_e, N)."""
+    from oracle.oracle import SUPPORTED_N, pad_N
+    n_hh, P, N = y.shape
+    dagg, dpol = [], []
+    for c0 in range(0, N, SUPPORTED_N[-1]):
+        c1 = min(N, c0 + SUPPORTED_N[-1])
+        Nc = pad_N(c1 - c0)
+        xd = np.zeros((n_hh, P, 1 + Nc))
+        xd[..., 0] = xhh
+        xd[..., 1:1 + c1 - c0] = y[:, :, c0:c1]
+        st, oa, op = orc.household_block(xd[0], xd[1], value, D, Nc, xd[2] if n_hh > 2 else None)
+        assert st == 0
+        agg, pol = oa[:, 0], op[..., 0]
+        dagg.append(oa[:, 1:1 + c1 - c0]); dpol.append(op[..., 1:1 + c1 - c0])
+    return agg, np.concatenate(dagg, axis=1), pol, np.concatenate(dpol, axis=-1)
+
+
+def _sweeps(hb, xhh, y, Ns):
+    """both entry points at every batch width: the Dual pass (hank_primal_jvp) and the Float64 sweeps followed by the tangent
+    sweeps (hank_primal, hank_jvp), each from a record of another x (no memo hit: every sweep runs). A second hank_jvp at the same
+    record returns the same bits. -> {(entry, N): (family, agg, dagg, policy (P, n_a, n_e), dpolicy (P, n_a, n_e, N), D)}."""
+    out = {}
+    for N in Ns:
+        yN = np.ascontiguousarray(y[:, :, :N])
+        hb.primal(xhh * 1.01)
+        agg, dagg = hb.primal_jvp(xhh, yN)
+        fam = hb.info()["last_tangent_family_name"]
+        out["dual", N] = (fam, agg, dagg, hb.policy_seq().transpose(2, 0, 1), hb.dpolicy_seq(N).transpose(2, 0, 1, 3), hb.dist_seq())
+        hb.primal(xhh * 1.01)
+        agg = hb.primal(xhh)
+        dagg = hb.jvp(yN)
+        fam = hb.info()["last_tangent_family_name"]
+        out["tan", N] = (fam, agg, dagg, hb.policy_seq().transpose(2, 0, 1), hb.dpolicy_seq(N).transpose(2, 0, 1, 3), hb.dist_seq())
+        assert np.array_equal(hb.jvp(yN), dagg), ("a second hank_jvp at the same record", N)
+    return out
+
+
+def _expected_family(sched, entry, N):
+    if sched is not None:
+        return FAMILY[sched]
+    if N >= 80:
+        return FAMILY["wide"]                   # a full round of the on-chip wide sweeps
+    if entry == "dual":
+        return FAMILY["xcd" if N <= 32 else "launch"]     # one-pass Dual batches run on the persistent Dual pass
+    return FAMILY["xcd"]                        # tangent batches up to xjvp_max = 64
+
+
+NS = (1, 5, 12, 40)          # with 8 groups: D = 1, 1, 2, and two passes (32 at D = 4, then 8)
+NWIDE = 96                   # the default schedule sends it to the on-chip wide sweeps
+
+
+@pytest.mark.parametrize("family,case", MATRIX)
+def test_parity_over_curvature_and_record_layout(hank, family, case):
+    gamma, diet_env, diet = CASES[case]
+    m, ss, xhh, orc = _economy(family, gamma)
+    n_hh, P = xhh.shape
+    y = np.random.default_rng(17).standard_normal((n_hh, P, NWIDE))
+    oagg, odagg, opol, odpol = _oracle(orc, ss.value, ss.D, xhh, y[:, :, :max(NS)])
+    res = {}
+    for sched in ("launch", "xcd", "wide", None):
+        hb = _block(hank, m, sched, HANK_RECORD_DIET=diet_env)
+        hb.set_boundary(ss.value, ss.D)
+        info = hb.info()
+        assert info["record_diet"] == diet, (sched, info)
+        assert info["wide_mode"] == {"wide": 2, None: 1}.get(sched, 0), (sched, info)
+        Ns = NS + ((NWIDE,) if sched in (None, "launch") else ())
+        res[sched] = _sweeps(hb, xhh, y, Ns)
+        st = hb.stats()
+        assert st["schedule"] == {"launch": 0, "xcd": 1}.get(sched, 2) and st["fallbacks"] == 0, (sched, st)
+        hb.close()
+        for (entry, N), (fam, agg, dagg, pol, dpol, D) in res[sched].items():
+            what = f"{family} {case} {sched} {entry} N={N}"
+            assert fam == _expected_family(sched, entry, N), (what, fam)
+            k = min(N, max(NS))
+            _close(agg, oagg, what=what + " agg"); _close(dagg[:, :k], odagg[:, :k], what=what + " dagg")
+            _close(pol, opol, what=what + " policy"); _close(dpol[..., :k], odpol[..., :k], what=what + " dpolicy")
+            np.testing.assert_allclose(D.sum(axis=(0, 1)), 1.0, rtol=0, atol=1e-12)
+    # the three families against each other; the persistent sweeps and the launches hold the same policy bits whether a kernel
+    # reads kc and v from the record or rebuilds them (the wide family rebuilds A and B by a reciprocal: to rounding)
+    for sched in ("xcd", "wide", None):
+        for (entry, N), (fam, agg, dagg, pol, dpol, D) in res[sched].items():
+            _, agg0, dagg0, pol0, dpol0, D0 = res["launch"][entry, N]
+            what = f"{family} {case} {sched} vs launch {entry} N={N}"
+            _close(agg, agg0, 1e-12, what=what + " agg"); _close(dagg, dagg0, 1e-12, what=what + " dagg")
+            _close(dpol, dpol0, 1e-12, what=what + " dpolicy"); _close(D, D0, 1e-12, what=what + " D")
+            assert np.array_equal(pol, pol0), what + " policy"
+            if fam != FAMILY["wide"]:
+                assert np.array_equal(dpol, dpol0), what + " dpolicy bits"
+    if diet_env == "0":
+        # the same curvature with the diet on: kc and v rebuilt through the cancellation in cm (~1e-13)
+        for sched in ("launch", "xcd", "wide", None):
+            hb = _block(hank, m, sched)
+            hb.set_boundary(ss.value, ss.D)
+            assert hb.info()["record_diet"] == 1
+            Ns = NS + ((NWIDE,) if sched is None else ())
+            on = _sweeps(hb, xhh, y, Ns)
+            assert hb.stats()["fallbacks"] == 0
+            hb.close()
+            for key, (fam, agg, dagg, pol, dpol, D) in on.items():
+                what = f"{family} {case} {sched} diet on vs off {key}"
+                assert fam == res[sched][key][0], what
+                assert np.array_equal(pol, res[sched][key][3]), what + " policy"
+                _close(dagg, res[sched][key][2], 1e-12, what=what + " dagg")
+                _close(dpol, res[sched][key][4], 1e-12, what=what + " dpolicy")
+
+
+# ---- 2. the rest of the pipeline at gamma != 2 -------------------------------------------------------------------------------
+def _oracle_vfi(orc, shape, r, w, tol, cap=20_000):
+    """the reference's inner fixed point (SteadyState.jl:132-141) on the oracle's ValueFunction, from ones until
+    max|new - old| < tol (tests/test_gpu_steady_state.py) -> (value, policy, steps)."""
+    value = np.ones(shape)
+    for k in range(1, cap + 1):
+        st, V, KD = orc.value_function(value, r, w, 1)
+        assert st == 0
+        vn, pol = V[..., 0], KD[..., 0]
+        nrm = float(np.max(np.abs(vn - value)))
+        value = vn
+        if nrm < tol:
+            return value, pol, k
+    raise AssertionError("oracle VFI did not converge")
+
+
+@pytest.mark.parametrize("gamma", [1.0, 0.5, 3.0])
+def test_device_vfi_at_other_curvatures(hank, gamma):
+    """hank_vfi (k_xvfi under xcd, k_egm_step under launch) on the other pow_crra branches: the oracle iteration's step count
+    within one, value and policy to 1e-10."""
+    m, ss, _, orc = _economy("ks", gamma)
+    n_a, n_e = ss.value.shape
+    r, w, tol = ss.vars["r"], ss.vars["w"], 1e-11
+    v_o, p_o, steps_o = _oracle_vfi(orc, (n_a, n_e), r, w, tol)
+    for sched in ("launch", "xcd"):
+        hb = _block(hank, m, sched)
+        v, pol, it, nrm = hb.vfi(np.ones((n_a, n_e)), [r, w], tol)
+        assert abs(it - steps_o) <= 1 and nrm < tol, (sched, it, steps_o)
+        assert np.max(np.abs(v - v_o)) < 1e-10 * np.abs(v_o).max(), sched
+        assert np.max(np.abs(pol - p_o)) < 1e-10 * max(1.0, np.abs(p_o).max()), sched
+        assert hb.stats()["fallbacks"] == 0 and hb.stats()["schedule"] == (0 if sched == "launch" else 1)
+        hb.close()
+
+
+@pytest.mark.parametrize("gamma,diet", [(1.0, 1), (1.5, 0)])
+def test_toeplitz_jacobian_at_other_curvatures(hank, gamma, diet):
+    """hank_fake_news against the unit-tangent J̅ (method="columns": 156 columns, the on-chip wide sweeps) at 1e-8 of the largest
+    entry, the bar of tests/test_gpu_jacobian.py."""
+    from hank_amd.BackwardIteration import household_block
+    m, ss, _, _ = _economy("ks", gamma)
+    Jt = hank.getSteadyStateJacobian(ss, m, method="toeplitz").toarray()
+    Jc = hank.getSteadyStateJacobian(ss, m, method="columns").toarray()
+    hb = household_block(m)
+    assert hb.info()["record_diet"] == diet and hb.stats()["fallbacks"] == 0
+    assert np.max(np.abs(Jc)) > 0.5
+    assert np.max(np.abs(Jt - Jc)) < 1e-8 * np.max(np.abs(Jc))
+
+
+def _oracle_outputs(orc, gamma, ss, x, y, n_het):
+    """x (n_hh, P), y (n_hh, P, N) -> agg (n_het, P), dagg (n_het, P, N) of (savings, consumption, Value[, UCE]) under the oracle's
+    dual arithmetic (tests/test_gpu_het_nonaffine.py)."""
+    from oracle.oracle import _dp, _fn, pad_N
+    import ctypes as C
+    n_hh, P, N = y.shape
+    Nc = pad_N(N)
+    xd = np.zeros((n_hh, P, 1 + Nc))
+    xd[..., 0] = x
+    xd[..., 1:1 + N] = y
+    xt = xd[2] if n_hh > 2 else None
+    st, pol = orc.backward_iteration(xd[0], xd[1], ss.value, Nc, xt)
+    assert st == 0
+    V = np.empty((P, orc.n_a, orc.n_e, 1 + Nc))
+    Vn = np.asarray(ss.value, dtype=np.float64)
+    for t in range(P - 1, -1, -1):
+        st, Vt, KD = orc.value_function(Vn, xd[0, t], xd[1, t], Nc, None if xt is None else xt[t])
+        assert st == 0
+        _close(KD, pol[t], 1e-12)
+        V[t], Vn = Vt, Vt
+    ps = np.ascontiguousarray(pol.transpose(0, 2, 1, 3))
+    cons = np.empty_like(ps)
+    _fn("orc_consumption_policy", Nc)(C.byref(orc.m), P, _dp(np.ascontiguousarray(xd[0])), _dp(np.ascontiguousarray(xd[1])),
+                                      None if xt is None else _dp(np.ascontiguousarray(xt)), _dp(ps), _dp(cons))
+    seqs = [ps, cons, np.ascontiguousarray(V.transpose(0, 2, 1, 3))]
+    if n_het > 3:
+        c0 = cons[..., 0]
+        u = np.empty_like(cons)
+        u[..., 0] = c0 ** (-gamma)
+        u[..., 1:] = (-gamma * c0 ** (-gamma - 1.0))[..., None] * cons[..., 1:]
+        seqs.append(orc.z[None, :, None, None] * u)
+    seqs = np.ascontiguousarray(np.stack(seqs))
+    D0 = np.ascontiguousarray(np.asarray(ss.D, dtype=np.float64).reshape((orc.n_a, orc.n_e), order="F").T)
+    agg = np.empty((n_het, P, 1 + Nc))
+    _fn("orc_forward_iteration_het", Nc)(C.byref(orc.m), P, n_het, _dp(seqs), _dp(D0), _dp(agg))
+    return agg[..., 0], agg[..., 1:1 + N]
+
+
+@pytest.mark.parametrize("family,n_het", [("ks", 3), ("hank", 4)])
+def test_nonaffine_outputs_at_gamma_1_5(hank, family, n_het):
+    """Value (Krusell-Smith) and UCE (one-asset HANK) at gamma = 1.5 (pow branches, diet off): hank_get_het_outputs after a
+    Dual pass, and hank_fake_news_het's columns against the oracle's unit tangents at the steady state (1e-8, the bar of
+    tests/test_gpu_fake_news_het.py)."""
+    from hank_amd.BackwardIteration import household_inputs
+    from hank_amd.GeneralStructures import vars_of_type
+    from hank_amd.SteadyStateJacobian import household_jacobian
+    gamma = 1.5
+    m, ss, xhh, orc = _economy(family, gamma)
+    n_hh, P = xhh.shape
+    y = np.random.default_rng(23).standard_normal((n_hh, P, 5))
+    hb = _block(hank, m, None)
+    hb.set_boundary(ss.value, ss.D)
+    assert hb.info()["record_diet"] == 0
+    hb.set_het_outputs(n_het)
+    hb.primal_jvp(xhh, y)
+    agg, dagg = hb.het_outputs(n_het, y)
+    oagg, odagg = _oracle_outputs(orc, gamma, ss, xhh, y, n_het)
+    for j in range(n_het):
+        _close(agg[:, j], oagg[j], what=f"output {j}")
+        _close(dagg[:, j, :], odagg[j], what=f"output {j} partials")
+    # the Toeplitz form at the stationary primal
+    x_ss = np.tile(np.array([ss.vars[k] for k in vars_of_type(m, "endogenous")]), P)
+    exog = {k: np.full(P, float(ss.vars[k])) for k in vars_of_type(m, "exogenous")}
+    xss = np.asarray(household_inputs(x_ss, exog, m)[0])
+    hb.primal(xss)
+    F, Dv = hb.fake_news_het(n_het)
+    assert hb.stats()["fallbacks"] == 0
+    hb.close()
+    cols = sorted(set([0, 1, P // 2, P - 2, P - 1]))
+    yu = np.zeros((n_hh, P, n_hh * len(cols)))
+    for q, s_ in enumerate(cols):
+        for k in range(n_hh):
+            yu[k, s_, q * n_hh + k] = 1.0
+    _, odu = _oracle_outputs(orc, gamma, ss, xss, yu, n_het)
+    for o in range(n_het):
+        J = household_jacobian(F[..., o], Dv[..., o])
+        scale = np.max(np.abs(odu[o]))
+        assert scale > 1e-6, o
+        for q, s_ in enumerate(cols):
+            for k in range(n_hh):
+                err = np.max(np.abs(J[k][:, s_] - odu[o][:, q * n_hh + k]))
+                assert err < 1e-8 * scale, f"output {o}, input {k}, column {s_}: {err:.3e} vs scale {scale:.3e}"
+
+
+# ---- 3. shape edges of the persistent and wide families ----------------------------------------------------------------------
+_SHAPE = {}
+
+
+def _shape(n_a, n_e, T):
+    """Krusell-Smith of the given shape at gamma = 2 with a cheap valid boundary: V_T the 200th host VFI iterate from ones at the
+    130x3 steady state's prices, D_0 uniform; the x1 path of those prices (cached per shape)."""
+    key = (n_a, n_e, T)
+    if key not in _SHAPE:
+        import hank_amd as h
+        from oracle.oracle import Oracle
+        m = h.build_model_from_yaml(str(ROOT / "examples" / "krusell_smith.yaml"),
+                                    overrides={"T": T, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": n_e}}})
+        assert m.params.γ == 2.0
+        _, ss0, _, _ = _economy("ks", 2.0)
+        xv = {"r": ss0.vars["r"], "w": ss0.vars["w"]}
+        V = np.ones((n_a, n_e))
+        for _ in range(200):
+            V = m.value_fn.host_steady_state_step(V, xv, m)["Value"]
+        D = np.full(n_a * n_e, 1.0 / (n_a * n_e))
+        P = T - 1
+        t = np.arange(1, P + 1)
+        xhh = np.stack([xv["r"] + 0.004 * 0.8 ** t, xv["w"] * (1.0 + 0.01 * 0.8 ** t)])
+        wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
+        _SHAPE[key] = (m, V, D, xhh, Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons))
+    return _SHAPE[key]
+
+
+def _forced_against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
+    """each (schedule, env) of `runs`, both entry points at every N of Ns, against the oracle and a launch-schedule context."""
+    m, V, D, xhh, orc = shape
+    n_hh, P = xhh.shape
+    y = np.random.default_rng(seed).standard_normal((n_hh, P, max(Ns)))
+    oagg, odagg, opol, odpol = _oracle(orc, V, D, xhh, y)
+    refs = {}
+    for sched, env in runs:
+        diet = env.get("HANK_RECORD_DIET")
+        if diet not in refs:                # the launches with the same record layout (diet on and off differ by rounding)
+            hl = _block(hank, m, "launch", HANK_RECORD_DIET=diet)
+            hl.set_boundary(V, D)
+            refs[diet] = _sweeps(hl, xhh, y, Ns)
+            hl.close()
+        ref = refs[diet]
+        hb = _block(hank, m, sched, **env)
+        hb.set_boundary(V, D)
+        got = _sweeps(hb, xhh, y, Ns)
+        st, info = hb.stats(), hb.info()
+        assert st["fallbacks"] == 0 and (st["schedule"] == 1 if sched == "xcd" else info["wide_mode"] == 2), (sched, env, st, info)
+        assert info["record_diet"] == (0 if env.get("HANK_RECORD_DIET") == 0 else 1), (sched, env, info)
+        hb.close()
+        for (entry, N), (fam, agg, dagg, pol, dpol, Dq) in got.items():
+            what = f"{m.heterogeneity['wealth'].n}x{m.heterogeneity['productivity'].n} {sched} {env} {entry} N={N}"
+            assert fam == FAMILY[sched], (what, fam)
+            _close(agg, oagg, what=what + " agg"); _close(dagg, odagg[:, :N], what=what + " dagg")
+            _close(pol, opol, what=what + " policy"); _close(dpol, odpol[..., :N], what=what + " dpolicy")
+            np.testing.assert_allclose(Dq.sum(axis=(0, 1)), 1.0, rtol=0, atol=1e-12)
+            _, agg0, dagg0, pol0, dpol0, _ = ref[entry, N]
+            _close(agg, agg0, 1e-12, what=what + " agg vs launch"); _close(dagg, dagg0, 1e-12, what=what + " dagg vs launch")
+            assert np.array_equal(pol, pol0), what + " policy vs launch"
+            if sched == "xcd":
+                assert np.array_equal(dpol, dpol0), what + " dpolicy bits vs launch"
+            else:
+                _close(dpol, dpol0, 1e-12, what=what + " dpolicy vs launch")
+
+
+@pytest.mark.parametrize("n_e", [11, 12, 16])
+def test_xcd_sweeps_across_the_1024_thread_boundary(hank, n_e):
+    """64 (n_e + 1) threads: n_e = 11 is the last 768-thread grid, 12 the first 1024-thread one (dmax = 2). N = 12 is D = 2 in
+    one pass, N = 40 one pass at 768 threads and three (16 + 16 + 8) at 1024; with the diet on and off."""
+    _forced_against_oracle_and_launches(hank, _shape(40, n_e, 10), [("xcd", {}), ("xcd", {"HANK_RECORD_DIET": 0})], (12, 40))
+
+
+@pytest.mark.parametrize("n_a", [63, 64, 126, 127])
+def test_last_slab_full_or_holding_one_row(hank, n_a):
+    """the persistent sweeps work in 63-row slabs, one per CU of an XCD: a last slab exactly full (63, 126) or holding one row
+    (64, 127); and the wide family at the same grids (rows in pairs or quads per thread)."""
+    _forced_against_oracle_and_launches(hank, _shape(n_a, 3, 12), [("xcd", {}), ("xcd", {"HANK_RECORD_DIET": 0}), ("wide", {}),
+                                                                   ("wide", {"HANK_WIDE_R": 4})], (5, 40))
+
+
+def test_xcd_capacity(hank):
+    """the largest grid the XCD schedule takes, one 63-row slab per CU of an XCD, runs forced `xcd`; one more row: a forced `xcd`
+    fails at hank_create with its reason, and the default schedule is the launches."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count // 8
+    n_a = 63 * cus
+    _forced_against_oracle_and_launches(hank, _shape(n_a, 2, 5), [("xcd", {})], (4,))
+    g = np.linspace(0.0, 200.0, n_a + 1)
+    Pi = np.array([[0.9, 0.1], [0.1, 0.9]])
+    old = os.environ.get("HANK_SCHEDULE")
+    try:
+        os.environ["HANK_SCHEDULE"] = "xcd"
+        with pytest.raises(hank.HankHIPError, match=f"HANK_SCHEDULE=xcd: n_a={n_a + 1} needs {cus + 1} workgroups per XCD"):
+            hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
+        os.environ.pop("HANK_SCHEDULE")
+        hb = hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
+        assert hb.stats()["schedule"] == 0
+        hb.close()
+    finally:
+        if old is None:
+            os.environ.pop("HANK_SCHEDULE", None)
+        else:
+            os.environ["HANK_SCHEDULE"] = old
+
+
+@pytest.mark.parametrize("n_e", [2, 3, 4, 5, 7, 11])
+def test_every_instantiated_wide_ne(hank, n_e):
+    """k_wide_back / k_wide_fwd of every n_e of HANK_WIDE_NE_LIST, in both geometries (2 rows per thread, 1024-thread workgroups;
+    4 rows, 512) and both record layouts (the diet-off backward sweep is another template)."""
+    runs = [("wide", {"HANK_WIDE_R": r, "HANK_RECORD_DIET": d}) for r in (2, 4) for d in (None, 0)]
+    _forced_against_oracle_and_launches(hank, _shape(40, n_e, 10), runs, (5,))
+
+
+@pytest.mark.parametrize("n_a", [2047, 2048])
+def test_wide_capacity(hank, n_a):
+    """WIDE_CS = 2048 rows: at 2047 and 2048 every row slot of a workgroup is live (both geometries, both layouts)."""
+    runs = [("wide", {"HANK_WIDE_R": r, "HANK_RECORD_DIET": d}) for r in (2, 4) for d in (None, 0)]
+    _forced_against_oracle_and_launches(hank, _shape(n_a, 2, 5), runs, (3,))
+
+
+def test_wide_refuses_one_row_more_than_it_holds(hank):
+    """n_a = 2049: auto reports the wide sweeps unsupported, a forced `wide` fails at hank_create with its reason."""
+    g = np.linspace(0.0, 200.0, 2049)
+    Pi = np.array([[0.9, 0.1], [0.1, 0.9]])
+    old = os.environ.get("HANK_SCHEDULE")
+    try:
+        os.environ.pop("HANK_SCHEDULE", None)
+        hb = hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
+        assert hb.info()["wide_supported"] == 0 and hb.info()["wide_mode"] == 0
+        hb.close()
+        os.environ["HANK_SCHEDULE"] = "wide"
+        with pytest.raises(hank.HankHIPError, match="n_a <= 2048"):
+            hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
+    finally:
+        if old is None:
+            os.environ.pop("HANK_SCHEDULE", None)
+        else:
+            os.environ["HANK_SCHEDULE"] = old
