@@ -152,7 +152,8 @@ int hank_primal_jvp_dev(hank_ctx *ctx, const double *d_xhh, const double *d_dxhh
 
 /* BackwardIteration's return value (BackwardIteration.jl:115): the policy sequence of the last
  * hank_primal, P matrices of n_a x n_e -> out[P*G]; and its partials for the last hank_jvp,
- * out[(G, P, N)] column-major (seqs_data[j][t] as Matrix{Dual}). */
+ * out[(G, P, N)] column-major (seqs_data[j][t] as Matrix{Dual}). A new primal or a new boundary
+ * makes the partials HANK_ERR_NOT_READY until the next hank_jvp, under every schedule. */
 int hank_get_policy_seq(hank_ctx *ctx, double *out);
 int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out);
 /* More than one heterogeneous variable. BackwardIteration keeps one policy sequence per heterogeneous variable

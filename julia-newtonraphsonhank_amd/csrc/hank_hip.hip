@@ -52,7 +52,6 @@ struct TanWork {
     int nbx = 0, nbxf = 0;
     hipGraphExec_t g_back = nullptr, g_fwd = nullptr;
     hipGraphExec_t g_fback = nullptr, g_ffwd = nullptr;   // dual-sweep graphs (primal + tangents in one chain)
-    bool valid = false;  // dpol holds the partials of the current primal
     int VB = 1, VF = 1, RGB = 1, RGF = 1;   // lane widths and row groups the graphs are captured with
     unsigned nbf = 0;
 };
@@ -70,7 +69,6 @@ struct XTan {                       // one per batch width N (kept in a small LR
     double *daggpart = nullptr;     // [P][Sact*n_e][XG*XD_MAX] (reused by every pass)
     double *dagg_pass = nullptr;    // [P][XG*XD_MAX]
     double *dagg_cm = nullptr;      // (P, N) column-major
-    bool valid = false;             // dpol holds the partials of the current primal
 };
 struct XWork {
     bool ready = false;
@@ -100,7 +98,17 @@ struct WTan {
     double *dxhh = nullptr;         // (n_hh, P, N) the caller's input tangents (staging for the host-pointer entries)
     double *dpol = nullptr;         // [P][N][G]
     double *dagg_cm = nullptr;      // (P, N) column-major
-    bool valid = false;             // dpol holds the partials of the current primal
+};
+
+// The current tangent batch: at most ONE is current, and it belongs to the recorded primal. Written by batch_ran ("family F has
+// just run a batch on workspace W") and batch_none ("nothing is current") only; the readers ask batch_current.
+struct TanBatch {
+    int family = 0;                 // which family ran the last tangent sweep (0 launches, 1 persistent, 2 wide): kept for hank_info when nothing is current
+    bool current = false;
+    int N = 0;
+    const void *ws = nullptr;       // the cache entry that holds it (its eviction makes nothing current)
+    const double *dagg_cm = nullptr, *dpol = nullptr;     // the family's (P, 2 N) tangents of the aggregates and its policy partials
+    const std::vector<XPass> *passes = nullptr;           // persistent family: how dpol is laid out
 };
 
 struct hank_ctx {
@@ -128,16 +136,14 @@ struct hank_ctx {
     bool ev_valid[6] = {false, false, false, false, false, false};
     int launches[6] = {0, 0, 0, 0, 0, 0};
     std::list<TanWork> tws;        // per batch width, most recently used first (a small cache: Jacobian assembly and Newton alternate widths)
-    TanWork *tw = nullptr;         // the current one
     // 0 = one launch per period for everything; 1 = XCD-local persistent sweeps for everything; 2 = auto (default where
     // the persistent sweeps are supported): each entry point takes the faster of the two for its shape — see sched_*
     int schedule = 2;
     bool forced_xcd = false;       // HANK_SCHEDULE=xcd at hank_create: no silent fallback to the launches
-    int last_tan = 0;              // which implementation ran the last tangent sweep (0 launches, 1 persistent): hank_get_dpolicy_seq
+    TanBatch batch;                // the current tangent batch (hank_get_dpolicy_seq, hank_get_grid_aggregates, hank_get_het_outputs, hank_info)
     int xjvp_max = 64;             // auto: batches up to this width take the persistent tangent sweeps (measured crossover)
     XWork xw;
     struct { double *dpT = nullptr, *iota = nullptr, *E = nullptr, *Cp = nullptr, *F = nullptr, *Dv = nullptr, *W = nullptr, *dsum = nullptr; int N = 0, n_het = 0; } fn;   // hank_fake_news[_het] workspace (E, Cp, F, Dv, W, dsum sized for n_het outputs)
-    XTan *xcur = nullptr;          // tangent buffers of the last xcd-schedule JVP
     // on-chip wide sweeps: 0 = never, 1 = auto (batches of at least wide_min directions), 2 = every batch (HANK_SCHEDULE=wide: tests)
     int wide_mode = 0, wide_min = 80, num_cus = 256, wide_r = 2;     // wide_r: rows per thread of the wide kernels (2: 1024-thread workgroups, 4 waves per SIMD — since the L2 warming of round 5 the faster geometry for both sweeps, 5.16 / 6.80 ms against 5.30 / 7.10 at N=256; dev knob HANK_WIDE_R=2|4 at hank_create)
     size_t lds_max = 65536;
@@ -147,7 +153,6 @@ struct hank_ctx {
     bool seg_valid = true;          // the record's per-target segment records match its lottery (k_lottery writes them except in the persistent Dual pass)
     bool wprep_valid = false;
     std::list<WTan> wtans;         // most recently used first
-    WTan *wcur = nullptr;
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
     long long stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // see hank_stats
     // primal memo of the host-pointer hank_primal_jvp (NewtonRaphson.jl:91-95 calls JVP(fullFunction, x, y) ~21 times at one x):
@@ -167,8 +172,28 @@ struct hank_ctx {
 
 static int fail(hank_ctx *ctx, int code, const char *fmt, ...);
 static void free_fn(hank_ctx *ctx);
-static void w_invalidate(hank_ctx *ctx) { for (WTan &t : ctx->wtans) t.valid = false; }
-static void w_new_primal(hank_ctx *ctx) { ctx->wprep_valid = false; }      // (the record is about to be rewritten)
+static void batch_none(hank_ctx *ctx) { ctx->batch.current = false; ctx->batch.ws = nullptr; }
+static void batch_ran(hank_ctx *ctx, int family, const void *ws, int N, const double *dagg_cm, const double *dpol, const std::vector<XPass> *passes = nullptr) {
+    ctx->batch = TanBatch{family, true, N, ws, dagg_cm, dpol, passes};
+}
+// every reader's question: is a batch of N directions current?
+static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
+    if (!ctx->batch.current || ctx->batch.N != N) return fail(ctx, HANK_ERR_NOT_READY, "no tangent sweep with N=%d is current", N);
+    *out = &ctx->batch;
+    return HANK_OK;
+}
+// the record was rewritten (or is about to be, by work already enqueued): what was derived from the old one goes, and so does the
+// batch. seg_written: the per-target segment records were written with it (k_lottery writes them except in the persistent Dual pass)
+static void record_rewritten(hank_ctx *ctx, bool seg_written) {
+    ctx->primal_done = true; ctx->seg_valid = seg_written;
+    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false;
+    batch_none(ctx);
+}
+// the record is gone (a new boundary, a persistent sweep that did not run): the next tangent sweep needs a primal first
+static void record_gone(hank_ctx *ctx) {
+    record_rewritten(ctx, false);
+    ctx->primal_done = false;
+}
 static void w_free_tan(WTan &w) {
     (void)hipFree(w.dxhh); (void)hipFree(w.dpol); (void)hipFree(w.dagg_cm);
     w = WTan();
@@ -399,24 +424,38 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     return rc;
 }
 
-static int ensure_tanwork(hank_ctx *ctx, int N) {
-    for (auto it = ctx->tws.begin(); it != ctx->tws.end(); ++it)
-        if (it->N == N) { ctx->tws.splice(ctx->tws.begin(), ctx->tws, it); ctx->tw = &ctx->tws.front(); return HANK_OK; }
+// The workspaces of one family for a batch of N directions, from a small most-recently-used cache (Jacobian assembly at N = 256
+// and the Newton inner loop at N = 1 alternate: neither re-allocates). On a miss `build` sizes and allocates the new entry
+// (its N is set); `release` frees an entry's device memory.
+template <typename W, typename Build>
+static int tan_cache_get(hank_ctx *ctx, std::list<W> &cache, int N, void (*release)(W &), Build build, W **out) {
+    for (auto it = cache.begin(); it != cache.end(); ++it)
+        if (it->N == N) { cache.splice(cache.begin(), cache, it); *out = &cache.front(); return HANK_OK; }
     const char *ce = getenv("HANK_TAN_CACHE");
     const size_t keep = ce ? (size_t)atoi(ce) : 3;
-    while (ctx->tws.size() >= (keep ? keep : 1)) {     // evict the least recently used — the async entries may still have its graphs in flight
+    while (cache.size() >= (keep ? keep : 1)) {        // evict the least recently used — the async entries may still have its graphs or buffers in flight
         HIPC(ctx, join_side(ctx));
         HIPC(ctx, hipStreamSynchronize(ctx->stream));
-        free_tanwork(ctx->tws.back());
-        ctx->tws.pop_back();
+        if (ctx->batch.ws == &cache.back()) batch_none(ctx);
+        release(cache.back());
+        cache.pop_back();
     }
-    ctx->tws.emplace_front();
-    ctx->tw = &ctx->tws.front();
-    TanWork &w = *ctx->tw;
+    cache.emplace_front();
+    W &w = cache.front();
+    w.N = N;
     ctx->stats[1]++;
+    // a failed allocation must not leave a half-built entry in the cache: a retry with this N would find it, return
+    // HANK_OK and launch on null pointers
+    const int rc = build(w);
+    if (rc) { release(w); cache.pop_front(); (void)hipGetLastError(); return rc; }
+    *out = &w;
+    return HANK_OK;
+}
+
+static int build_tanwork(hank_ctx *ctx, TanWork &w) {
     const Consts &c = ctx->c;
     const size_t P = c.P, G = c.G;
-    w.N = N;
+    const int N = w.N;
     // an even batch can run two directions per lane (16-byte accesses): the [..][N] layout is the same, so
     // each sweep picks its own lane width
     const int VB = tan_lane_width(N, 0), VF = tan_lane_width(N, 1);
@@ -439,26 +478,22 @@ static int ensure_tanwork(hank_ctx *ctx, int N) {
     const int RGB = tan_rg(w.g.N, 0), RGF = tan_rg(w.gf.N, 1, w.gf.ss);
     const unsigned nbf = (w.nbxf + RGF - 1) / RGF + KV;   // forward blocks: regular + mass-point
     w.VB = VB; w.VF = VF; w.RGB = RGB; w.RGF = RGF; w.nbf = nbf;
-    // a failed allocation must not leave a half-built entry in the cache: a retry with this N would find it, return
-    // HANK_OK and launch on null pointers
-    auto alloc = [&]() -> int {
-        HIPC(ctx, dmalloc(&w.dxhh, (size_t)c.n_hh * P * N));
-        HIPC(ctx, dmalloc(&w.dxr, P * N));
-        HIPC(ctx, dmalloc(&w.dxw, P * N));
-        HIPC(ctx, dmalloc(&w.dxt, P * N));
-        for (int k = 0; k < 2; k++) {
-            HIPC(ctx, dmalloc(&w.ds[k], G * N));
-            HIPC(ctx, dmalloc(&w.dD[k], GV * N));
-        }
-        HIPC(ctx, dmalloc(&w.dpol, P * G * N));
-        HIPC(ctx, dmalloc(&w.aggpart, 2 * P * (size_t)nbf * N));      // both aggregates: [P][blocks][2 N]
-        HIPC(ctx, dmalloc(&w.dagg, 2 * P * N));
-        HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * N));                    // (P, 2 N) column-major: the policy-weighted aggregate's N columns, then the grid-weighted one's
-        return HANK_OK;
-    };
-    const int rc = alloc();
-    if (rc) { free_tanwork(w); ctx->tws.pop_front(); ctx->tw = ctx->tws.empty() ? nullptr : &ctx->tws.front(); (void)hipGetLastError(); return rc; }
+    HIPC(ctx, dmalloc(&w.dxhh, (size_t)c.n_hh * P * N));
+    HIPC(ctx, dmalloc(&w.dxr, P * N));
+    HIPC(ctx, dmalloc(&w.dxw, P * N));
+    HIPC(ctx, dmalloc(&w.dxt, P * N));
+    for (int k = 0; k < 2; k++) {
+        HIPC(ctx, dmalloc(&w.ds[k], G * N));
+        HIPC(ctx, dmalloc(&w.dD[k], GV * N));
+    }
+    HIPC(ctx, dmalloc(&w.dpol, P * G * N));
+    HIPC(ctx, dmalloc(&w.aggpart, 2 * P * (size_t)nbf * N));      // both aggregates: [P][blocks][2 N]
+    HIPC(ctx, dmalloc(&w.dagg, 2 * P * N));
+    HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * N));                    // (P, 2 N) column-major: the policy-weighted aggregate's N columns, then the grid-weighted one's
     return HANK_OK;
+}
+static int ensure_tanwork(hank_ctx *ctx, int N, TanWork **out) {
+    return tan_cache_get(ctx, ctx->tws, N, free_tanwork, [ctx](TanWork &w) { return build_tanwork(ctx, w); }, out);
 }
 
 // the graph pair of one schedule, captured the first time that schedule runs at this batch width
@@ -556,7 +591,6 @@ static void x_free(hank_ctx *ctx) {
     XWork &X = ctx->xw;
     for (XTan &w : X.tans) x_free_tan(w);
     X.tans.clear();
-    ctx->xcur = nullptr;
     (void)hipFree(X.sync); (void)hipFree(X.st_s); (void)hipFree(X.st_ds); (void)hipFree(X.st_D); (void)hipFree(X.st_dD);
     (void)hipFree(X.Dvirt); (void)hipFree(X.aggpart); (void)hipFree(X.rho); (void)hipFree(X.srcB); (void)hipFree(X.srcF); (void)hipFree(X.unitsF); (void)hipFree(X.unit_overflow);
     X = XWork();
@@ -609,26 +643,12 @@ static int x_setup(hank_ctx *ctx) {
     return HANK_OK;
 }
 
-// tangent buffers for a batch of N directions, from a small most-recently-used cache (Jacobian assembly at N = 256
-// and the Newton inner loop at N = 1 alternate: neither re-allocates)
-static int x_ensure_tan(hank_ctx *ctx, int N, XTan **out) {
+// the passes of a batch of w.N directions and their buffers
+static int x_build_tan(hank_ctx *ctx, XTan &w) {
     XWork &X = ctx->xw;
-    for (auto it = X.tans.begin(); it != X.tans.end(); ++it)
-        if (it->N == N) { X.tans.splice(X.tans.begin(), X.tans, it); *out = &X.tans.front(); return HANK_OK; }
-    if (N > 8 * X.dmax * XPASS_MAX) return fail(ctx, HANK_ERR_BAD_ARG, "N=%d exceeds %d directions per call", N, 8 * X.dmax * XPASS_MAX);
-    const char *ce = getenv("HANK_TAN_CACHE");
-    const size_t keep = ce ? (size_t)atoi(ce) : 3;
-    while (X.tans.size() >= (keep ? keep : 1)) {       // evict the least recently used — after the stream has drained
-        HIPC(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->xcur == &X.tans.back()) ctx->xcur = nullptr;
-        x_free_tan(X.tans.back());
-        X.tans.pop_back();
-    }
-    X.tans.emplace_front();
-    XTan &w = X.tans.front();
     const Consts &c = ctx->c;
     const size_t P = c.P, G = c.G;
-    w.N = N;
+    const int N = w.N;
     size_t off = 0;
     for (int n0 = 0; n0 < N; n0 += XG * X.dmax) {
         XPass ps;
@@ -639,28 +659,21 @@ static int x_ensure_tan(hank_ctx *ctx, int N, XTan **out) {
         off += P * ps.groups * G * ps.D;
         w.passes.push_back(ps);
     }
-    if ((int)w.passes.size() > XPASS_MAX) {
-        const int np_ = (int)w.passes.size();
-        X.tans.pop_front();
-        return fail(ctx, HANK_ERR_BAD_ARG, "N=%d needs %d passes, at most %d per call", N, np_, XPASS_MAX);
-    }
-    ctx->stats[1]++;
-    // (a failed allocation leaves no half-built entry behind: the next call with this N must not find it in the cache)
-    auto alloc = [&]() -> int {
-        HIPC(ctx, dmalloc(&w.dxhh, (size_t)c.n_hh * P * N));
-        HIPC(ctx, dmalloc(&w.dxr, P * N)); HIPC(ctx, dmalloc(&w.dxw, P * N)); HIPC(ctx, dmalloc(&w.dxt, P * N));
-        HIPC(ctx, dmalloc(&w.dpol, off));
-        const size_t W = (size_t)XG * X.dmax, nb = (size_t)X.Sact;
-        HIPC(ctx, dmalloc(&w.daggpart, 2 * P * nb * W));              // both aggregates: [P][members][2 W]
-        HIPC(ctx, hipMemsetAsync(w.daggpart, 0, sizeof(double) * 2 * P * nb * W, ctx->stream));
-        HIPC(ctx, dmalloc(&w.dagg_pass, 2 * P * W));
-        HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * N));                    // (P, 2 N) column-major
-        return HANK_OK;
-    };
-    const int rc = alloc();
-    if (rc) { x_free_tan(w); X.tans.pop_front(); (void)hipGetLastError(); return rc; }
-    *out = &w;
+    if ((int)w.passes.size() > XPASS_MAX) return fail(ctx, HANK_ERR_BAD_ARG, "N=%d needs %d passes, at most %d per call", N, (int)w.passes.size(), XPASS_MAX);
+    HIPC(ctx, dmalloc(&w.dxhh, (size_t)c.n_hh * P * N));
+    HIPC(ctx, dmalloc(&w.dxr, P * N)); HIPC(ctx, dmalloc(&w.dxw, P * N)); HIPC(ctx, dmalloc(&w.dxt, P * N));
+    HIPC(ctx, dmalloc(&w.dpol, off));
+    const size_t W = (size_t)XG * X.dmax, nb = (size_t)X.Sact;
+    HIPC(ctx, dmalloc(&w.daggpart, 2 * P * nb * W));              // both aggregates: [P][members][2 W]
+    HIPC(ctx, hipMemsetAsync(w.daggpart, 0, sizeof(double) * 2 * P * nb * W, ctx->stream));
+    HIPC(ctx, dmalloc(&w.dagg_pass, 2 * P * W));
+    HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * N));                    // (P, 2 N) column-major
     return HANK_OK;
+}
+static int x_ensure_tan(hank_ctx *ctx, int N, XTan **out) {
+    const int nmax = 8 * ctx->xw.dmax * XPASS_MAX;      // (a cached width has passed this check)
+    if (N > nmax) return fail(ctx, HANK_ERR_BAD_ARG, "N=%d exceeds %d directions per call", N, nmax);
+    return tan_cache_get(ctx, ctx->xw.tans, N, x_free_tan, [ctx](XTan &w) { return x_build_tan(ctx, w); }, out);
 }
 
 
@@ -732,6 +745,13 @@ static int x_sync_reset(hank_ctx *ctx, XSync *base, int count, int where) {     
     return HANK_OK;
 }
 
+// workgroup of the persistent kernels: 64 threads per productivity state + one wave that only runs the group barrier's poll,
+// where the block has room (dev knob HANK_XSYNCWAVE=0: wave 0 polls)
+static dim3 x_block(const XWork &X, const Consts &c) {
+    const bool fits = 64 * (c.n_e + 1) <= X.maxt && X.syncwave;
+    return dim3(fits ? 64 * (c.n_e + 1) : 64 * c.n_e);
+}
+
 // the Float64 recurrences at the context's current x (d_xhh) and boundary: two persistent launches on ONE XCD's
 // workgroups (the policy sequence, the distribution path and the linearisation record the tangent sweeps read)
 // skip_fwd: the distribution sweep travels with the tangents' forward sweep instead (k_xfwd<D, true>, x_run_tangent(.., val))
@@ -751,9 +771,7 @@ static int x_run_primal(hank_ctx *ctx, bool skip_fwd = false, XTan *dual = nullp
         hipLaunchKernelGGL(k_xrho, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, ctx->d_xhh, c.n_hh, (int)P, X.rho);
         if (dual) hipLaunchKernelGGL(k_tan_in, dim3((unsigned)((P * dual->N + 255) / 256)), dim3(256), 0, s, dual->dxhh, c.n_hh, (int)P, dual->N, dual->dxr, dual->dxw, dual->dxt);
     }
-    // + one wave that only runs the group barrier's poll, where the block has room (dev knob HANK_XSYNCWAVE=0: wave 0 polls)
-    const bool fits = 64 * (c.n_e + 1) <= X.maxt && X.syncwave;
-    const dim3 grd(X.grid), blk(fits ? 64 * (c.n_e + 1) : 64 * c.n_e), blkf = blk;
+    const dim3 grd(X.grid), blk = x_block(X, c), blkf = blk;
     XBackArgs ab{};
     ab.c = c; ab.ss_value = ctx->d_ss_value; ab.xhh = ctx->d_xhh; ab.rho = X.rho; ab.sy = X.sync; ab.st_s = X.st_s;
     ab.err = ctx->d_err; ab.R = ctx->R;
@@ -770,8 +788,7 @@ static int x_run_primal(hank_ctx *ctx, bool skip_fwd = false, XTan *dual = nullp
     HIPC(ctx, hipEventRecord(ctx->ev[1], s));
     // (the Dual pass's forward half reads the lottery through its work units: the per-target segment records are built when somebody asks)
     hipLaunchKernelGGL(k_lottery, dim3((unsigned)(P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, (int)P * c.n_e, ctx->d_err, dual ? 0 : 1, 1);
-    ctx->seg_valid = !dual;
-    X.rng_valid = false;
+    record_rewritten(ctx, !dual);
     x_ensure_rng(ctx);
     HIPC(ctx, hipEventRecord(ctx->ev[6], s));
     if (!skip_fwd) {
@@ -794,11 +811,6 @@ static int x_run_primal(hank_ctx *ctx, bool skip_fwd = false, XTan *dual = nullp
     ctx->launches[0] = ctx->launches[1] = 1;
     ctx->ev_valid[0] = true; ctx->ev_valid[1] = !skip_fwd;
     ctx->ev_valid[2] = ctx->ev_valid[3] = ctx->ev_valid[4] = ctx->ev_valid[5] = false;
-    ctx->primal_done = true; w_new_primal(ctx);
-    X.src_valid = false;
-    for (XTan &t : X.tans) t.valid = false;
-    w_invalidate(ctx);
-    ctx->xcur = nullptr;
     return HANK_OK;
 }
 
@@ -828,9 +840,7 @@ static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_bac
     x_ensure_rng(ctx);
     const bool neigh = X.neigh;
     const dim3 grd(X.grid);
-    // + one wave that only runs the group barrier's poll, where the block has room (dev knob HANK_XSYNCWAVE=0: wave 0 polls)
-    const bool fits = 64 * (c.n_e + 1) <= X.maxt && X.syncwave;
-    const dim3 blk(fits ? 64 * (c.n_e + 1) : 64 * c.n_e), blkF = blk;
+    const dim3 blk = x_block(X, c), blkF = blk;
     XTanBackArgs ab{};
     ab.c = c; ab.R = ctx->R; ab.rho = X.rho; ab.xhh = ctx->d_xhh; ab.dxr = w->dxr; ab.dxw = w->dxw; ab.dxt = w->dxt; ab.Ntot = N; ab.st_ds = X.st_ds;
     ab.src = neigh ? X.srcB : nullptr;
@@ -881,11 +891,7 @@ static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_bac
     ctx->launches[2] = ctx->launches[3] = np;
     ctx->ev_valid[2] = ctx->ev_valid[3] = true;
     ctx->ev_valid[4] = ctx->ev_valid[5] = false;
-    for (XTan &t : X.tans) t.valid = false;
-    w->valid = true;
-    ctx->xcur = w;
-    ctx->last_tan = 1;
-    for (TanWork &t : ctx->tws) t.valid = false; w_invalidate(ctx);
+    batch_ran(ctx, 1, w, N, w->dagg_cm, w->dpol, &w->passes);
     return HANK_OK;
 }
 
@@ -897,17 +903,14 @@ static int x_status(hank_ctx *ctx) {
     HIPC(ctx, hipMemcpy(&uo, X.unit_overflow, sizeof(int), hipMemcpyDeviceToHost));
     if (uo) {
         HIPC(ctx, hipMemsetAsync(X.unit_overflow, 0, sizeof(int), ctx->stream));
-        ctx->primal_done = false;
-        X.rng_valid = false;
-        for (XTan &t : X.tans) t.valid = false;
+        record_gone(ctx);
         return fail(ctx, HANK_ERR_SWEEP, "persistent forward sweep: a member's walk over its sources needs more than %d work units (a savings policy this flat is served by the per-period launches)", XUCAP);
     }
     std::vector<XSync> h(2 * (size_t)X.last_passes);
     HIPC(ctx, hipMemcpy(h.data(), X.sync, sizeof(XSync) * h.size(), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < h.size(); k++)
         if (h[k].status[0] != 0) {
-            ctx->primal_done = false;
-            for (XTan &t : X.tans) t.valid = false;
+            record_gone(ctx);
             char waited[64] = "";
             if (h[k].status[0] == XERR_TIMEOUT) snprintf(waited, sizeof(waited), " after %.1f ms", h[k].status[2] / 1000.0);
             return fail(ctx, HANK_ERR_SWEEP, "persistent %s sweep %zu (0 = primal, then one per tangent pass): %s%s on XCD %u (workgroups per XCD: %u %u %u %u %u %u %u %u)",
@@ -982,38 +985,16 @@ static int w_launch(hank_ctx *ctx, bool fwd, int N, const WideArgs &a) {
     return fail(ctx, HANK_ERR_BAD_ARG, "on-chip wide sweeps: n_e=%d is not instantiated", ctx->c.n_e);
 }
 
+// (the staging buffer of the host-pointer entries is allocated when one of them first uses the width)
 static int w_ensure_tan(hank_ctx *ctx, int N, bool staging, WTan **out) {
-    for (auto it = ctx->wtans.begin(); it != ctx->wtans.end(); ++it)
-        if (it->N == N) {
-            ctx->wtans.splice(ctx->wtans.begin(), ctx->wtans, it);
-            WTan &w = ctx->wtans.front();
-            if (staging && !w.dxhh) HIPC(ctx, dmalloc(&w.dxhh, (size_t)ctx->c.n_hh * ctx->c.P * N));
-            *out = &w;
-            return HANK_OK;
-        }
-    const char *ce = getenv("HANK_TAN_CACHE");
-    const size_t keep = ce ? (size_t)atoi(ce) : 3;
-    while (ctx->wtans.size() >= (keep ? keep : 1)) {       // evict the least recently used — after the stream has drained
-        HIPC(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->wcur == &ctx->wtans.back()) ctx->wcur = nullptr;
-        w_free_tan(ctx->wtans.back());
-        ctx->wtans.pop_back();
-    }
-    ctx->wtans.emplace_front();
-    WTan &w = ctx->wtans.front();
-    const Consts &c = ctx->c;
-    const size_t P = c.P, G = c.G;
-    w.N = N;
-    ctx->stats[1]++;
-    auto alloc = [&]() -> int {
-        if (staging) HIPC(ctx, dmalloc(&w.dxhh, (size_t)c.n_hh * P * N));
+    const size_t P = ctx->c.P, G = ctx->c.G;
+    const int rc = tan_cache_get(ctx, ctx->wtans, N, w_free_tan, [=](WTan &w) -> int {
         HIPC(ctx, dmalloc(&w.dpol, P * (size_t)N * G + 2));       // (+ 2: the last 16-byte load of an odd-sized grid reads 8 bytes past its row)
         HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * (size_t)N));            // (P, 2 N) column-major: both aggregates
         return HANK_OK;
-    };
-    const int rc = alloc();
-    if (rc) { w_free_tan(w); ctx->wtans.pop_front(); (void)hipGetLastError(); return rc; }
-    *out = &w;
+    }, out);
+    if (rc) return rc;
+    if (staging && !(*out)->dxhh) HIPC(ctx, dmalloc(&(*out)->dxhh, (size_t)ctx->c.n_hh * P * N));
     return HANK_OK;
 }
 
@@ -1052,12 +1033,7 @@ static int w_run_tangent(hank_ctx *ctx, WTan *w, const double *d_dxhh) {
     ctx->launches[2] = ctx->launches[3] = 1;
     ctx->ev_valid[2] = ctx->ev_valid[3] = true;
     ctx->ev_valid[4] = ctx->ev_valid[5] = false;
-    for (TanWork &t : ctx->tws) t.valid = false;
-    for (XTan &t : ctx->xw.tans) t.valid = false;
-    w_invalidate(ctx);
-    w->valid = true;
-    ctx->wcur = w;
-    ctx->last_tan = 2;
+    batch_ran(ctx, 2, w, w->N, w->dagg_cm, w->dpol);
     ctx->stats[0] += 2;
     return HANK_OK;
 }
@@ -1071,6 +1047,25 @@ static int w_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, d
     rc = w_run_tangent(ctx, w, staging ? w->dxhh : dxhh);
     if (rc) return rc;
     if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
+    return HANK_OK;
+}
+
+// the policy partials of the current tangent batch, whichever family ran it, as [n][t][pt] (the (G, P, N) export layout)
+static int export_dpol_dev(hank_ctx *ctx, const TanBatch &b, double *out) {
+    const int G = ctx->c.G, P = ctx->c.P;
+    const size_t total = (size_t)P * G * b.N;
+    const dim3 grd((unsigned)((total + 255) / 256)), blk(256);
+    if (b.family == 2) {
+        hipLaunchKernelGGL(k_wide_export_dpol, grd, blk, 0, ctx->stream, b.dpol, G, P, b.N, out);
+    } else if (b.family == 1) {
+        for (const XPass &ps : *b.passes) {
+            const size_t cnt = (size_t)P * G * ps.N;
+            hipLaunchKernelGGL(k_xexport_dpol, dim3((unsigned)((cnt + 255) / 256)), blk, 0, ctx->stream, b.dpol + ps.dpol_off, G, P, ps.groups, ps.D, ps.n0, ps.N, out);
+        }
+    } else {
+        hipLaunchKernelGGL(k_export_dpol, grd, blk, 0, ctx->stream, b.dpol, G, P, b.N, out);
+    }
+    HIPC(ctx, hipGetLastError());
     return HANK_OK;
 }
 
@@ -1215,7 +1210,6 @@ int hank_destroy(hank_ctx *ctx) {
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     for (TanWork &t : ctx->tws) free_tanwork(t);
     ctx->tws.clear();
-    ctx->tw = nullptr;
     x_free(ctx);
     free_fn(ctx);
     if (ctx->ev_stream) (void)hipEventDestroy(ctx->ev_stream);
@@ -1226,7 +1220,6 @@ int hank_destroy(hank_ctx *ctx) {
     if (ctx->g_pfwd) (void)hipGraphExecDestroy(ctx->g_pfwd);
     for (WTan &t : ctx->wtans) w_free_tan(t);
     ctx->wtans.clear();
-    ctx->wcur = nullptr;
     (void)hipFree(ctx->rec_slab); (void)hipFree(ctx->d_ibw); (void)hipFree(ctx->hx_slab);
     (void)hipFree(ctx->d_a); (void)hipFree(ctx->d_z); (void)hipFree(ctx->d_Pi); (void)hipFree(ctx->d_ss_value);
     (void)hipFree(ctx->d_xhh); (void)hipFree(ctx->d_agg); (void)hipFree(ctx->d_agg_rm); (void)hipFree(ctx->d_zd); (void)hipFree(ctx->d_aggpart); (void)hipFree(ctx->d_err);
@@ -1288,12 +1281,11 @@ int hank_set_boundary(hank_ctx *ctx, const double *ss_end_value, const double *s
     }
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     ctx->boundary_set = true;
-    ctx->primal_done = false;
+    record_gone(ctx);
     ctx->memo_valid = false;
     ctx->stationary = false;
     ctx->h_ss_value.assign(ss_end_value, ss_end_value + G);
     ctx->h_ss_D.assign(ss_init_D, ss_init_D + G);
-    for (TanWork &t : ctx->tws) t.valid = false; w_invalidate(ctx);
     ctx->errmsg[0] = 0;
     return HANK_OK;
 }
@@ -1328,9 +1320,7 @@ static int run_primal(hank_ctx *ctx, double *d_agg_out) {
     ctx->side_pending = true;
     ctx->ev_valid[0] = ctx->ev_valid[1] = true;
     ctx->ev_valid[4] = ctx->ev_valid[5] = false;
-    ctx->primal_done = true; ctx->seg_valid = true; w_new_primal(ctx);
-    ctx->xw.src_valid = false; ctx->xw.rng_valid = false;
-    for (TanWork &t : ctx->tws) t.valid = false; w_invalidate(ctx);
+    record_rewritten(ctx, true);
     return HANK_OK;
 }
 
@@ -1408,7 +1398,7 @@ static bool use_x_fused(const hank_ctx *ctx, int N) {
 
 // a sweep could not form its groups (or timed out): this context continues on the per-period launches
 static int to_launch_schedule(hank_ctx *ctx) {
-    ctx->primal_done = false;
+    record_gone(ctx);
     if (!ctx->g_pback) {                    // (a context that has only run persistent sweeps has never captured them)
         const int rc = build_primal_graphs(ctx);
         if (rc != HANK_OK) return rc;       // the schedule is left as it was: the next call reports the sweep's failure again, not a null graph
@@ -1419,16 +1409,33 @@ static int to_launch_schedule(hank_ctx *ctx) {
 }
 static bool x_fallback_allowed(const hank_ctx *ctx) { return !ctx->forced_xcd; }      // a schedule forced at hank_create fails loudly instead
 
+// after a host-pointer entry has enqueued its work: drain it and take the device's verdict. A persistent sweep that could not
+// run moves the context to the per-period launches (unless its schedule was forced) and sets *rerun: the caller runs its work
+// again, which the launches now serve. (The device-pointer entries never re-run work: hank_check reports and moves the context.)
+static int settle(hank_ctx *ctx, bool *rerun) {
+    *rerun = false;
+    int rc = fetch_device_error(ctx);
+    if (rc == HANK_ERR_SWEEP && x_fallback_allowed(ctx)) {
+        rc = to_launch_schedule(ctx);
+        *rerun = rc == HANK_OK;
+    }
+    return rc;
+}
+
+// hank_primal[_dev]: x from the caller (kind: where it lives) and the Float64 sweeps of the context's schedule
+static int enqueue_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double *d_agg_out) {
+    if (use_x_primal(ctx)) return x_primal(ctx, xhh, kind, d_agg_out);
+    HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * ctx->c.P, kind, ctx->stream));
+    return run_primal(ctx, d_agg_out);
+}
+
 int hank_primal_dev(hank_ctx *ctx, const double *d_xhh, double *d_agg_out) {
     ENTER(ctx);
     if (!ctx || !d_xhh) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
     note_primal_x(ctx, nullptr);
     ctx->stats[7]++;
-    if (use_x_primal(ctx)) return x_primal(ctx, d_xhh, hipMemcpyDeviceToDevice, d_agg_out);
-    const size_t P = ctx->c.P;
-    HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, d_xhh, sizeof(double) * ctx->c.n_hh * P, hipMemcpyDeviceToDevice, ctx->stream));
-    return run_primal(ctx, d_agg_out);
+    return enqueue_primal(ctx, d_xhh, hipMemcpyDeviceToDevice, d_agg_out);
 }
 
 int hank_check(hank_ctx *ctx) {
@@ -1456,24 +1463,16 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
     for (size_t t = 0; t < P; t++)
         if (!(1.0 + xhh[ctx->c.n_hh * t] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive (period %zu)", t + 1);
     note_primal_x(ctx, nullptr);
-    int rc = HANK_OK;
-    bool done = false;
-    if (use_x_primal(ctx)) {
-        rc = x_primal(ctx, xhh, hipMemcpyHostToDevice, nullptr);
+    int rc = enqueue_primal(ctx, xhh, hipMemcpyHostToDevice, nullptr);
+    if (rc) return rc;
+    bool rerun = false;
+    rc = settle(ctx, &rerun);
+    if (rerun) {
+        rc = enqueue_primal(ctx, xhh, hipMemcpyHostToDevice, nullptr);
         if (rc) return rc;
         rc = fetch_device_error(ctx);
-        if (rc == HANK_ERR_SWEEP && x_fallback_allowed(ctx)) rc = to_launch_schedule(ctx);
-        else if (rc) return rc;
-        else done = true;
-        if (rc) return rc;
     }
-    if (!done) {
-        HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * P, hipMemcpyHostToDevice, ctx->stream));
-        rc = run_primal(ctx, nullptr);
-        if (rc) return rc;
-        rc = fetch_device_error(ctx);
-        if (rc) return rc;
-    }
+    if (rc) return rc;
     if (agg_out) {
         HIPC(ctx, hipMemcpyAsync(agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
         HIPC(ctx, hipStreamSynchronize(ctx->stream));
@@ -1484,8 +1483,7 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
     return HANK_OK;
 }
 
-static int run_jvp(hank_ctx *ctx) {
-    TanWork &w = *ctx->tw;
+static int run_jvp(hank_ctx *ctx, TanWork &w) {
     int grc = ensure_graphs(ctx, w, 0);
     if (grc) return grc;
     ctx->launches[2] = ctx->c.P + 2; ctx->launches[3] = ctx->c.P + 3;
@@ -1498,10 +1496,23 @@ static int run_jvp(hank_ctx *ctx) {
     HIPC(ctx, hipGraphLaunch(w.g_fwd, ctx->stream));
     HIPC(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
     ctx->ev_valid[2] = ctx->ev_valid[3] = true;
-    for (TanWork &t : ctx->tws) t.valid = false; w_invalidate(ctx);
-    w.valid = true;
-    ctx->last_tan = 0;
-    for (XTan &t : ctx->xw.tans) t.valid = false;
+    batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
+    return HANK_OK;
+}
+
+// hank_jvp[_dev]: N directions from the caller (kind: where they live) through the tangent sweeps of the family that serves
+// this width at the recorded primal; batch_ran has named the family and its buffers when this returns HANK_OK
+static int enqueue_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, double *d_dagg_out) {
+    if (use_wide(ctx, N)) return w_jvp(ctx, dxhh, kind, N, d_dagg_out);
+    if (use_x_jvp(ctx, N)) return x_dual(ctx, nullptr, dxhh, kind, N, nullptr, d_dagg_out);
+    TanWork *w = nullptr;
+    int rc = ensure_tanwork(ctx, N, &w);
+    if (rc) return rc;
+    const size_t P = ctx->c.P;
+    HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
+    rc = run_jvp(ctx, *w);
+    if (rc) return rc;
+    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
     return HANK_OK;
 }
 
@@ -1509,16 +1520,7 @@ int hank_jvp_dev(hank_ctx *ctx, const double *d_dxhh, int32_t N, double *d_dagg_
     ENTER(ctx);
     if (!ctx || !d_dxhh || N < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument (N=%d)", N);
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp");
-    if (use_wide(ctx, N)) return w_jvp(ctx, d_dxhh, hipMemcpyDeviceToDevice, N, d_dagg_out);
-    if (use_x_jvp(ctx, N)) return x_dual(ctx, nullptr, d_dxhh, hipMemcpyDeviceToDevice, N, nullptr, d_dagg_out);
-    int rc = ensure_tanwork(ctx, N);
-    if (rc) return rc;
-    const size_t P = ctx->c.P;
-    HIPC(ctx, hipMemcpyAsync(ctx->tw->dxhh, d_dxhh, sizeof(double) * ctx->c.n_hh * P * N, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = run_jvp(ctx);
-    if (rc) return rc;
-    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, ctx->tw->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
-    return HANK_OK;
+    return enqueue_jvp(ctx, d_dxhh, hipMemcpyDeviceToDevice, N, d_dagg_out);
 }
 
 int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
@@ -1526,50 +1528,30 @@ int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
     if (!ctx || !dxhh || !dagg_out || N < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument (N=%d)", N);
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp");
     const size_t P = ctx->c.P;
-    int rc = HANK_OK;
-    if (use_wide(ctx, N)) {      // a wide batch at the recorded primal: the on-chip sweeps (no cross-workgroup waits: nothing to fall back from)
-        rc = w_jvp(ctx, dxhh, hipMemcpyHostToDevice, N, nullptr);
-        if (rc) return rc;
-        rc = fetch_device_error(ctx);
-        if (rc) return rc;
-        HIPC(ctx, hipMemcpyAsync(dagg_out, ctx->wcur->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
-        HIPC(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->errmsg[0] = 0;
-        return HANK_OK;
-    }
-    if (use_x_jvp(ctx, N)) {
-        rc = x_dual(ctx, nullptr, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr);
-        if (rc) return rc;
-        rc = fetch_device_error(ctx);
-        const bool fell_back = rc == HANK_ERR_SWEEP && x_fallback_allowed(ctx);
-        if (fell_back) {
-            rc = to_launch_schedule(ctx);
-            if (rc) return rc;
+    int rc = enqueue_jvp(ctx, dxhh, hipMemcpyHostToDevice, N, nullptr);
+    if (rc) return rc;
+    // the launches' tangent sweeps raise no device error; the on-chip wide sweeps do, but have no cross-workgroup waits:
+    // nothing to fall back from
+    if (ctx->batch.family == 2) rc = fetch_device_error(ctx);
+    else if (ctx->batch.family == 1) {
+        bool rerun = false;
+        rc = settle(ctx, &rerun);
+        if (rerun) {
             rc = run_primal(ctx, nullptr);       // re-record the primal at the current x with the launches
             if (rc) return rc;
             rc = fetch_device_error(ctx);
-        }
-        if (rc) return rc;
-        if (!fell_back) {
-            HIPC(ctx, hipMemcpyAsync(dagg_out, ctx->xcur->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
-            HIPC(ctx, hipStreamSynchronize(ctx->stream));
-            ctx->errmsg[0] = 0;
-            return HANK_OK;
+            if (rc) return rc;
+            rc = enqueue_jvp(ctx, dxhh, hipMemcpyHostToDevice, N, nullptr);
         }
     }
-    rc = ensure_tanwork(ctx, N);
     if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(ctx->tw->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, hipMemcpyHostToDevice, ctx->stream));
-    rc = run_jvp(ctx);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(dagg_out, ctx->tw->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(dagg_out, ctx->batch.dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     ctx->errmsg[0] = 0;
     return HANK_OK;
 }
 
-static int run_fused(hank_ctx *ctx) {
-    TanWork &w = *ctx->tw;
+static int run_fused(hank_ctx *ctx, TanWork &w) {
     int grc = ensure_graphs(ctx, w, 1);
     if (grc) return grc;
     ctx->launches[4] = ctx->launches[5] = ctx->c.P + 5;
@@ -1581,12 +1563,26 @@ static int run_fused(hank_ctx *ctx) {
     HIPC(ctx, hipEventRecord(ctx->ev[10], ctx->stream));
     ctx->ev_valid[4] = ctx->ev_valid[5] = true;
     ctx->ev_valid[0] = ctx->ev_valid[1] = ctx->ev_valid[2] = ctx->ev_valid[3] = false;
-    ctx->primal_done = true; ctx->seg_valid = true; w_new_primal(ctx);
-    ctx->xw.src_valid = false; ctx->xw.rng_valid = false;
-    for (TanWork &t : ctx->tws) t.valid = false; w_invalidate(ctx);
-    w.valid = true;
-    ctx->last_tan = 0;
-    for (XTan &t : ctx->xw.tans) t.valid = false;
+    record_rewritten(ctx, true);
+    batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
+    return HANK_OK;
+}
+
+// hank_primal_jvp[_dev] below the wide batches (those are hank_primal + hank_jvp of the same form): x and N directions from the
+// caller (kind: where they live) through one Dual pass, on the persistent sweeps or the dual-sweep launches
+static int enqueue_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, hipMemcpyKind kind, int N, double *d_agg_out, double *d_dagg_out) {
+    if (use_x_fused(ctx, N)) return x_dual(ctx, xhh, dxhh, kind, N, d_agg_out, d_dagg_out);
+    TanWork *w = nullptr;
+    int rc = ensure_tanwork(ctx, N, &w);
+    if (rc) return rc;
+    const size_t P = ctx->c.P;
+    HIPC(ctx, join_side(ctx));
+    HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * P, kind, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
+    rc = run_fused(ctx, *w);
+    if (rc) return rc;
+    if (d_agg_out) HIPC(ctx, hipMemcpyAsync(d_agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
     return HANK_OK;
 }
 
@@ -1601,18 +1597,7 @@ int hank_primal_jvp_dev(hank_ctx *ctx, const double *d_xhh, const double *d_dxhh
     }
     note_primal_x(ctx, nullptr);      // (this entry never skips work: bench.py times it)
     ctx->stats[7]++;
-    if (use_x_fused(ctx, N)) return x_dual(ctx, d_xhh, d_dxhh, hipMemcpyDeviceToDevice, N, d_agg_out, d_dagg_out);
-    int rc = ensure_tanwork(ctx, N);
-    if (rc) return rc;
-    const size_t P = ctx->c.P;
-    HIPC(ctx, join_side(ctx));
-    HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, d_xhh, sizeof(double) * ctx->c.n_hh * P, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPC(ctx, hipMemcpyAsync(ctx->tw->dxhh, d_dxhh, sizeof(double) * ctx->c.n_hh * P * N, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = run_fused(ctx);
-    if (rc) return rc;
-    if (d_agg_out) HIPC(ctx, hipMemcpyAsync(d_agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, ctx->tw->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
-    return HANK_OK;
+    return enqueue_primal_jvp(ctx, d_xhh, d_dxhh, hipMemcpyDeviceToDevice, N, d_agg_out, d_dagg_out);
 }
 
 int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_t N, double *agg_out, double *dagg_out) {
@@ -1643,30 +1628,18 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
         return rc ? rc : hank_jvp(ctx, dxhh, N, dagg_out);
     }
     note_primal_x(ctx, nullptr);
-    const double *d_dagg = nullptr;
-    if (use_x_fused(ctx, N)) {
-        rc = x_dual(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr);
+    rc = enqueue_primal_jvp(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr);
+    if (rc) return rc;
+    bool rerun = false;
+    rc = settle(ctx, &rerun);
+    if (rerun) {
+        rc = enqueue_primal_jvp(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr);
         if (rc) return rc;
         rc = fetch_device_error(ctx);
-        if (rc == HANK_ERR_SWEEP && x_fallback_allowed(ctx)) rc = to_launch_schedule(ctx);
-        else if (rc) return rc;
-        else d_dagg = ctx->xcur->dagg_cm;
-        if (rc) return rc;
     }
-    if (!d_dagg) {
-        rc = ensure_tanwork(ctx, N);
-        if (rc) return rc;
-        HIPC(ctx, join_side(ctx));
-        HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * P, hipMemcpyHostToDevice, ctx->stream));
-        HIPC(ctx, hipMemcpyAsync(ctx->tw->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, hipMemcpyHostToDevice, ctx->stream));
-        rc = run_fused(ctx);
-        if (rc) return rc;
-        rc = fetch_device_error(ctx);
-        if (rc) { ctx->tw->valid = false; return rc; }
-        d_dagg = ctx->tw->dagg_cm;
-    }
+    if (rc) { batch_none(ctx); return rc; }      // (the partials of a primal that failed are nobody's)
     if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipMemcpyAsync(dagg_out, d_dagg, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(dagg_out, ctx->batch.dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     note_primal_x(ctx, xhh);
     ctx->stats[7]++;
@@ -1733,9 +1706,10 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
     }
     { const int src = ensure_seg(ctx); if (src) return src; }
     // 1. n_hh backward tangent sweeps (one batch) seeded at the last period: every lag of the policy response
-    int rc = ensure_tanwork(ctx, N);
+    TanWork *wp = nullptr;
+    int rc = ensure_tanwork(ctx, N, &wp);
     if (rc) return rc;
-    TanWork &w = *ctx->tw;
+    TanWork &w = *wp;
     rc = ensure_graphs(ctx, w, 0);
     if (rc) return rc;
     rc = ensure_fn(ctx, nh);
@@ -1743,8 +1717,7 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
     HIPC(ctx, join_side(ctx));      // D_1 and the {w, ig D} records come from the primal's forward sweep
     hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
     HIPC(ctx, hipGraphLaunch(w.g_back, s));
-    for (TanWork &t : ctx->tws) t.valid = false; w_invalidate(ctx);      // (w.dpol no longer belongs to a caller's batch)
-    for (XTan &t : ctx->xw.tans) t.valid = false;
+    batch_none(ctx);      // (w.dpol no longer belongs to a caller's batch)
     // 2. the lottery impulse of every lag and input at once
     hipLaunchKernelGGL(k_fn_transpose, dim3((unsigned)((G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256), 0, s, w.dpol, P, G, N, ctx->fn.dpT);
     hipLaunchKernelGGL(k_fn_impulse, dim3((unsigned)c.n_a, (unsigned)((NP + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.dpT, NP, ctx->fn.iota);
@@ -1861,7 +1834,7 @@ int hank_gather_columns(hank_ctx *const *ctxs, int32_t n, const double *const *d
 
 int hank_info(hank_ctx *ctx, int64_t out[8]) {
     if (!ctx || !out) return HANK_ERR_BAD_ARG;
-    out[0] = ctx->last_tan; out[1] = ctx->wide_mode; out[2] = ctx->wide_min; out[3] = w_supported(ctx) ? 1 : 0;
+    out[0] = ctx->batch.family; out[1] = ctx->wide_mode; out[2] = ctx->wide_min; out[3] = w_supported(ctx) ? 1 : 0;
     out[4] = ctx->xjvp_max; out[5] = ctx->c.diet; out[6] = (int64_t)ctx->rec_bytes; out[7] = 0;
     return HANK_OK;
 }
@@ -1918,12 +1891,10 @@ static int grid_aggregates(hank_ctx *ctx, double *agg2_out, int32_t N, double *d
         HIPC(ctx, hipMemcpyAsync(agg2_out, ctx->d_agg + P, sizeof(double) * P, kind, ctx->stream));
     }
     if (dagg2_out && N > 0) {
-        const double *src = nullptr;
-        if (ctx->last_tan == 2) { if (ctx->wcur && ctx->wcur->valid && ctx->wcur->N == N) src = ctx->wcur->dagg_cm; }
-        else if (ctx->last_tan == 1) { if (ctx->xcur && ctx->xcur->valid && ctx->xcur->N == N) src = ctx->xcur->dagg_cm; }
-        else if (ctx->tw && ctx->tw->valid && ctx->tw->N == N) src = ctx->tw->dagg_cm;
-        if (!src) return fail(ctx, HANK_ERR_NOT_READY, "no tangent sweep with N=%d is current", N);
-        HIPC(ctx, hipMemcpyAsync(dagg2_out, src + P * (size_t)N, sizeof(double) * P * N, kind, ctx->stream));
+        const TanBatch *b = nullptr;
+        const int rc = batch_current(ctx, N, &b);
+        if (rc) return rc;
+        HIPC(ctx, hipMemcpyAsync(dagg2_out, b->dagg_cm + P * (size_t)N, sizeof(double) * P * N, kind, ctx->stream));
     }
     if (!dev) HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return HANK_OK;
@@ -1934,43 +1905,17 @@ int hank_get_grid_aggregates_dev(hank_ctx *ctx, double *d_agg2_out, int32_t N, d
 int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out) {
     if (!ctx || !out) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
+    const TanBatch *b = nullptr;
+    int rc = batch_current(ctx, N, &b);
+    if (rc) return rc;
     const size_t total = (size_t)ctx->c.P * ctx->c.G * N;
     double *tmp = nullptr;
-    if (ctx->last_tan == 2) {
-        WTan *w = ctx->wcur;
-        if (!w || !w->valid || w->N != N) return fail(ctx, HANK_ERR_NOT_READY, "no tangent sweep with N=%d is current", N);
-        HIPC(ctx, dmalloc(&tmp, total));
-        hipLaunchKernelGGL(k_wide_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, w->dpol, ctx->c.G, ctx->c.P, N, tmp);
-        hipError_t e1 = hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-        HIPC(ctx, e1);
-        HIPC(ctx, e2);
-        return HANK_OK;
-    }
-    if (ctx->last_tan == 1) {
-        XTan *x = ctx->xcur;
-        if (!x || !x->valid || x->N != N) return fail(ctx, HANK_ERR_NOT_READY, "no tangent sweep with N=%d is current", N);
-        HIPC(ctx, dmalloc(&tmp, total));
-        for (const XPass &ps : x->passes) {
-            const size_t cnt = (size_t)ctx->c.P * ctx->c.G * ps.N;
-            hipLaunchKernelGGL(k_xexport_dpol, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, x->dpol + ps.dpol_off, ctx->c.G, ctx->c.P,
-                               ps.groups, ps.D, ps.n0, ps.N, tmp);
-        }
-        hipError_t e1 = hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-        HIPC(ctx, e1);
-        HIPC(ctx, e2);
-        return HANK_OK;
-    }
-    if (!ctx->tw || !ctx->tw->valid || ctx->tw->N != N) return fail(ctx, HANK_ERR_NOT_READY, "no tangent sweep with N=%d is current", N);
-    TanWork &w = *ctx->tw;
     HIPC(ctx, dmalloc(&tmp, total));
-    hipLaunchKernelGGL(k_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, w.dpol, ctx->c.G, ctx->c.P, N, tmp);
+    rc = export_dpol_dev(ctx, *b, tmp);
     hipError_t e1 = hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream);
     hipError_t e2 = hipStreamSynchronize(ctx->stream);
     (void)hipFree(tmp);
+    if (rc) return rc;
     HIPC(ctx, e1);
     HIPC(ctx, e2);
     return HANK_OK;
@@ -2081,29 +2026,12 @@ __global__ void k_het_outputs(int P, int n_hh, int n_het, int N, const double *_
     }
 }
 
-// the policy partials of the last tangent sweep, whichever family ran it, as [n][t][pt] (the (G, P, N) export layout)
-static int export_dpol_dev(hank_ctx *ctx, int N, double *out) {
-    const size_t total = (size_t)ctx->c.P * ctx->c.G * N;
-    if (ctx->last_tan == 2) {
-        hipLaunchKernelGGL(k_wide_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->wcur->dpol, ctx->c.G, ctx->c.P, N, out);
-    } else if (ctx->last_tan == 1) {
-        for (const XPass &ps : ctx->xcur->passes) {
-            const size_t cnt = (size_t)ctx->c.P * ctx->c.G * ps.N;
-            hipLaunchKernelGGL(k_xexport_dpol, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, ctx->xcur->dpol + ps.dpol_off, ctx->c.G,
-                               ctx->c.P, ps.groups, ps.D, ps.n0, ps.N, out);
-        }
-    } else {
-        hipLaunchKernelGGL(k_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->tw->dpol, ctx->c.G, ctx->c.P, N, out);
-    }
-    HIPC(ctx, hipGetLastError());
-    return HANK_OK;
-}
-
 // outputs 2 .. n_het-1: the direction-independent sums (S), and — for N > 0 — the in-period sums of every direction (T) from one
 // forward tangent recurrence over the exported policy partials (hank_hetx.h). The buffers live in the context (hx_slab: one
 // allocation, grown when a wider batch asks, reused in stream order), so the _dev form stays asynchronous.
-static int hx_outputs(hank_ctx *ctx, int NX, int N, double **S_out, double **T_out) {
+static int hx_outputs(hank_ctx *ctx, int NX, const TanBatch *b, double **S_out, double **T_out) {      // b: the current batch, or nullptr (no tangents asked for)
     const Consts &c = ctx->c;
+    const int N = b ? b->N : 0;
     const size_t P = c.P, G = c.G;
     const int nbr = (c.n_a + HX_ROWS - 1) / HX_ROWS;
     const size_t sz[8] = {NX * P * G, NX * P * G, P * NX * HX_NS, P * G * N, G * N, G * N, (size_t)N * P * nbr * NX, (size_t)N * P * NX};
@@ -2124,7 +2052,7 @@ static int hx_outputs(hank_ctx *ctx, int NX, int N, double **S_out, double **T_o
     *T_out = nullptr;
     if (N == 0) return HANK_OK;
     double *dpc = buf[3], *mid = buf[4], *dD = buf[5], *parts = buf[6], *T = buf[7];
-    int rc = export_dpol_dev(ctx, N, dpc);
+    int rc = export_dpol_dev(ctx, *b, dpc);
     if (rc) return rc;
     const dim3 gmid((unsigned)((G + HX_ROWS - 1) / HX_ROWS), (unsigned)N), gmix((unsigned)nbr, (unsigned)N);
     for (size_t t = 0; t < P; t++) {
@@ -2149,12 +2077,10 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
     const size_t P = ctx->c.P, nh = ctx->c.n_hh;
     const bool tan = dagg_out && N > 0;
     if (tan && !dxhh) return fail(ctx, HANK_ERR_BAD_ARG, "the tangent outputs need the dxhh of the last tangent sweep");
-    const double *src = nullptr;
+    const TanBatch *b = nullptr;
     if (tan) {
-        if (ctx->last_tan == 2) { if (ctx->wcur && ctx->wcur->valid && ctx->wcur->N == N) src = ctx->wcur->dagg_cm; }
-        else if (ctx->last_tan == 1) { if (ctx->xcur && ctx->xcur->valid && ctx->xcur->N == N) src = ctx->xcur->dagg_cm; }
-        else if (ctx->tw && ctx->tw->valid && ctx->tw->N == N) src = ctx->tw->dagg_cm;
-        if (!src) return fail(ctx, HANK_ERR_NOT_READY, "no tangent sweep with N=%d is current", N);
+        const int rc = batch_current(ctx, N, &b);
+        if (rc) return rc;
     }
     HIPC(ctx, join_side(ctx));
     Scratch sc;
@@ -2173,11 +2099,11 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
     const int Nk = tan ? N : 0;
     double *hxS = nullptr, *hxT = nullptr;
     if (n_het > 2) {
-        int rc = hx_outputs(ctx, n_het - 2, Nk, &hxS, &hxT);
+        int rc = hx_outputs(ctx, n_het - 2, b, &hxS, &hxT);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * (Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, Nk, ctx->d_xhh,
-                       d_dx, ctx->d_agg, src, ctx->d_zd, hxS, hxT, d_a, tan ? d_da : nullptr);
+                       d_dx, ctx->d_agg, b ? b->dagg_cm : nullptr, ctx->d_zd, hxS, hxT, d_a, tan ? d_da : nullptr);
     HIPC(ctx, hipGetLastError());
     if (!dev) {
         if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, d_a, sizeof(double) * P * n_het, hipMemcpyDeviceToHost, ctx->stream));
@@ -2216,6 +2142,13 @@ int hank_backward_step_dual(hank_ctx *ctx, const double *value_next, const doubl
 }
 }  // extern "C"
 
+// the device's error word after a synchronisation, cleared when set (reported once: the next call starts clean)
+static int take_device_error(hank_ctx *ctx, int e[4]) {
+    HIPC(ctx, hipMemcpy(e, ctx->d_err, 4 * sizeof(int), hipMemcpyDeviceToHost));
+    if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, 4 * sizeof(int), ctx->stream));
+    return HANK_OK;
+}
+
 // ---- steady state: the inner fixed point of get_xVals on the device (SteadyState.jl:132-141) ------------------
 extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t max_iter, double *value_io, double *policy_out,
                         int32_t *iters_out, double *supnorm_out) {
@@ -2253,8 +2186,7 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
         XVfiArgs va{};
         va.c = c; va.V0 = V[0]; va.r = r; va.w = w; va.tr = tr; va.tol = tol; va.max_iter = max_iter; va.sy = X.sync; va.st_s = X.st_s;
         va.err = ctx->d_err; va.Vout = V[1]; va.pol = pol; va.iters = state; va.supnorm = norm;
-        const bool fits = 64 * (c.n_e + 1) <= X.maxt && X.syncwave;
-        const dim3 xblk(fits ? 64 * (c.n_e + 1) : 64 * c.n_e);
+        const dim3 xblk = x_block(X, c);
         const size_t lds = sizeof(double) * ((size_t)c.n_e * 64 + (size_t)c.n_e * c.n_e + c.n_a + 16) + 64;
         if (X.maxt == 768) hipLaunchKernelGGL((k_xvfi<768>), dim3(X.grid), xblk, lds, s, va);
         else hipLaunchKernelGGL((k_xvfi<1024>), dim3(X.grid), xblk, lds, s, va);
@@ -2269,8 +2201,7 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
         X.last_passes = 0;       // (this sync block has been checked here)
         if (hsy.status[0] == 0) {
             int e[4];
-            HIPC(ctx, hipMemcpy(e, ctx->d_err, sizeof(e), hipMemcpyDeviceToHost));
-            if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, sizeof(e), ctx->stream));
+            { const int erc = take_device_error(ctx, e); if (erc) return erc; }
             if (e[0] == ERR_KNOTS)
                 return fail(ctx, HANK_ERR_KNOTS, "knot-vectors must be unique and sorted in increasing order (steady-state value iteration, step %d, "
                             "productivity state %d, wealth index %d)", xs[0], e[2] + 1, e[3] + 1);
@@ -2310,8 +2241,7 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
         HIPC(ctx, hipMemcpyAsync(hstate, state, sizeof(hstate), hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));
         int e[4];
-        HIPC(ctx, hipMemcpy(e, ctx->d_err, sizeof(e), hipMemcpyDeviceToHost));
-        if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, sizeof(e), ctx->stream));
+        { const int erc = take_device_error(ctx, e); if (erc) return erc; }
         if (e[0] == ERR_KNOTS)
             return fail(ctx, HANK_ERR_KNOTS, "knot-vectors must be unique and sorted in increasing order (steady-state value iteration, step %d, "
                         "productivity state %d, wealth index %d)", hstate[1] + 1, e[2] + 1, e[3] + 1);
@@ -2375,8 +2305,7 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         XStatArgs sa{};
         sa.c = c; sa.R = R; sa.D0 = D[0]; sa.tol = tol; sa.max_iter = max_iter; sa.check_every = check_every; sa.sy = X.sync;
         sa.st_D = X.st_D; sa.Dout = D[1]; sa.iters = state;
-        const bool fits = 64 * (c.n_e + 1) <= X.maxt && X.syncwave;
-        const dim3 xblk(fits ? 64 * (c.n_e + 1) : 64 * c.n_e);
+        const dim3 xblk = x_block(X, c);
         const size_t lds = sizeof(double) * ((size_t)c.n_e * 64 + 16) + 64;
         if (X.maxt == 768) hipLaunchKernelGGL((k_xstat<768>), dim3(X.grid), xblk, lds, s, sa);
         else hipLaunchKernelGGL((k_xstat<1024>), dim3(X.grid), xblk, lds, s, sa);
@@ -2391,8 +2320,7 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         X.last_passes = 0;
         if (hsy.status[0] == 0) {
             int e[4];
-            HIPC(ctx, hipMemcpy(e, ctx->d_err, sizeof(e), hipMemcpyDeviceToHost));
-            if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, sizeof(e), ctx->stream));
+            { const int erc = take_device_error(ctx, e); if (erc) return erc; }
             if (e[0] == ERR_NONMONO) return fail(ctx, HANK_ERR_NONMONOTONE, "savings policy is not monotone in wealth (productivity state %d, wealth index %d)", e[2] + 1, e[3] + 1);
             HIPC(ctx, hipMemcpyAsync(D_io, D[1], sizeof(double) * G, hipMemcpyDeviceToHost, s));
             HIPC(ctx, hipStreamSynchronize(s));
@@ -2420,8 +2348,7 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         HIPC(ctx, hipStreamSynchronize(s));
     }
     int e[4];
-    HIPC(ctx, hipMemcpy(e, ctx->d_err, sizeof(e), hipMemcpyDeviceToHost));
-    if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, sizeof(e), ctx->stream));
+    { const int erc = take_device_error(ctx, e); if (erc) return erc; }
     if (e[0] == ERR_NONMONO) return fail(ctx, HANK_ERR_NONMONOTONE, "savings policy is not monotone in wealth (productivity state %d, wealth index %d)", e[2] + 1, e[3] + 1);
     // once converged the iteration kernels stop touching the buffers: Dchk holds the last checked iterate
     HIPC(ctx, hipMemcpyAsync(D_io, Dchk, sizeof(double) * G, hipMemcpyDeviceToHost, s));

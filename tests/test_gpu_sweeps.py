@@ -186,6 +186,40 @@ def test_alternating_batch_widths_reuse_workspaces(hank):
         hb.dpolicy_seq(256)          # the last sweep carried 32 directions, not 256
 
 
+def test_a_new_primal_or_boundary_leaves_no_tangent_batch_current(hank):
+    """the partials a reader hands out belong to the last hank_jvp of the last hank_primal (include/hank_hip.h): a new primal or a
+    new boundary makes them HANK_ERR_NOT_READY whichever family ran the batch and whichever records the new primal — on the
+    default schedule too, where the launches' batch once outlived a persistent primal and the persistent one a new boundary."""
+    m, ss, _ = ks_setup(50, 2, 100)
+    P = 99
+    x, _ = ks_paths(m, ss, "x1", 0.05)
+    rng = np.random.default_rng(11)
+    y70, y3 = rng.standard_normal((2, P, 70)), rng.standard_normal((2, P, 3))
+
+    def refused(call):
+        with pytest.raises(hank.HankHIPError) as ei:
+            call()
+        assert ei.value.code == hank.hip.HANK_ERR_NOT_READY, ei.value
+
+    hb = hank.household_block(m)
+    hb.set_boundary(ss.value, ss.D)
+    hb.primal(x[2:4])
+    hb.jvp(y70)                          # 64 < 70 < 80: the per-period launches
+    assert hb.info()["last_tangent_family_name"] == "launch-per-period" and hb.stats()["schedule"] == 2
+    assert hb.dpolicy_seq(70).shape == (50, 2, P, 70) and hb.grid_aggregates(70)[1].shape == (P, 70)
+    hb.primal(x[2:4] * 1.01)             # the persistent sweeps record another primal
+    refused(lambda: hb.dpolicy_seq(70))
+    refused(lambda: hb.grid_aggregates(70))
+
+    hb.jvp(y3)
+    assert hb.info()["last_tangent_family_name"] == "xcd-persistent"
+    assert hb.dpolicy_seq(3).shape == (50, 2, P, 3)
+    hb.set_boundary(ss.value * 1.01, ss.D)
+    refused(lambda: hb.dpolicy_seq(3))
+    refused(lambda: hb.grid_aggregates(3))
+    assert hb.stats()["fallbacks"] == 0
+
+
 def test_schedules_agree(hank):
     """the XCD-local persistent sweeps and the per-period launches are two implementations of the same arithmetic (the
     default schedule picks per entry point and batch width): policies and their partials bit for bit, aggregates to
