@@ -54,6 +54,32 @@ def solve(n_a=500, n_e=4, T=300, shock=0.01, eps=1e-9, verbose=False, cold=False
             "inner": inner, "jacobian": jacobian}, x
 
 
+def gradient(n_a=500, n_e=4, T=300, shock=0.01, chunk=256):
+    """The gradient of the merit function ½‖F(x)‖² at the Newton starting point (the steady state repeated, where F ≠ 0 under
+    the shock): ∇ = J(x)ᵀ F(x). Reverse mode: ONE hank_vjp at M = 1 (`LinearizedFunction.vjp`). Forward mode: the n unit
+    tangents, of which n_hh·P move the household inputs and reach the device (hank_jvp in batches of `chunk`). Prints both
+    times and their agreement."""
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    from conftest import ks_setup
+    m, ss, _ = ks_setup(n_a, n_e, T)
+    P = T - 1
+    Z = 1.0 + shock * 0.8 ** np.arange(1, P + 1)
+    x0 = np.tile(np.array([ss.vars[k] for k in ("Y", "KS", "r", "w")]), P)
+    lin = h.LinearizedFunction(x0, {"Z": Z}, m, ss, ss)
+    n = x0.size
+    lin.vjp(lin.Fx); lin.jvp(np.eye(n)[:, :chunk])                      # warm-up: workspaces, graphs, the residual layer's linearisation
+    t0 = time.perf_counter()
+    g_rev = lin.vjp(lin.Fx)
+    t_rev = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    g_fwd = np.concatenate([lin.Fx @ lin.jvp(np.eye(n)[:, c0:c0 + chunk]) for c0 in range(0, n, chunk)])
+    t_fwd = time.perf_counter() - t0
+    return {"grid": f"{n_a}x{n_e}", "T": T, "unknowns": n, "merit": 0.5 * float(lin.Fx @ lin.Fx), "gradient_norm": float(np.linalg.norm(g_rev)),
+            "reverse_s": round(t_rev, 5), "reverse_vjps": 1, "forward_s": round(t_fwd, 5), "forward_jvp_columns": lin.hb.n_hh * P,
+            "max_abs_difference_over_max": float(np.max(np.abs(g_rev - g_fwd)) / np.max(np.abs(g_fwd)))}
+
+
 def solve_permanent(n_a=200, n_e=3, T=150, Z_end=1.03, eps=1e-9, verbose=False):
     """The two-steady-state scenario of the reference YAML (`ending:` block, KrusellSmith.yaml:109-116): TFP moves
     to Z_end for good in period 1. The path starts from the initial steady state (KS_0, D_0 = ss_initial), the terminal
@@ -92,6 +118,7 @@ if __name__ == "__main__":
     ap.add_argument("--cold", action="store_true", help="solve the steady state from the YAML guesses (no fixture)")
     ap.add_argument("--inner", default="fixed_point", choices=["fixed_point", "krylov"], help="y-iteration: the reference's damped fixed point or GMRES on J(x) preconditioned by the steady-state Jacobian")
     ap.add_argument("--jacobian", default="toeplitz", choices=["toeplitz", "columns"])
+    ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one hank_vjp against n_hh·P JVP columns")
     a = ap.parse_args()
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -101,7 +128,9 @@ if __name__ == "__main__":
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", torch.cuda.current_device()))
-    if a.permanent is not None:
+    if a.gradient:
+        out = gradient(a.n_a, a.n_e, a.T, a.shock)
+    elif a.permanent is not None:
         out = solve_permanent(a.n_a, a.n_e, a.T, a.permanent, verbose=a.verbose)[0]
     else:
         out, x = solve(a.n_a, a.n_e, a.T, a.shock, verbose=a.verbose, cold=a.cold, inner=a.inner, jacobian=a.jacobian)

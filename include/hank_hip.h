@@ -264,6 +264,29 @@ int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out);
  * unchanged. */
 int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out);
 
+/* ---- the transposed household block: xhh_bar = J(x)' agg_bar -------------------------------------
+ * hank_vjp == the reverse rules of the same composition at the recorded primal: the pullback of ForwardIteration
+ * (ForwardIteration.jl:339-420, built on the reverse rule of transition_step, :131-192) followed by the transpose of the
+ * partials of BackwardIteration (BackwardIteration.jl:46-116; the reference differentiates it forward only, so this half has
+ * no counterpart there). It is the exact transpose of what hank_jvp / hank_get_het_outputs compute, for M cotangent columns
+ * at once: one launch per period and sweep (csrc/hank_adjoint.h), no atomics — the same record and cotangents give the same
+ * bits.
+ *   agg_bar (P, n_het, M) column-major: cotangents of the aggregates of output 0 (the policy variable, KD / A) and, with
+ *   n_het = 2, of output 1 (consumption) — the shape of hank_get_het_outputs's dagg_out. Outputs 2 and 3 (Value, UCE) are
+ *   not affine in the policy: n_het > 2 is refused with HANK_ERR_BAD_ARG.
+ *   xhh_bar (n_hh, P, M) column-major: cotangents of the household inputs — the shape of dxhh.
+ * Needs a valid record (HANK_ERR_NOT_READY before the first primal, after a new boundary, after a persistent sweep that did
+ * not run), written by any kernel family; touches neither the record, nor the current tangent batch (hank_get_dpolicy_seq,
+ * hank_get_het_outputs keep serving it), nor the primal memo. The _dev form takes device pointers, is asynchronous on the
+ * context's stream and never waits on the host; the host form copies in, runs, copies out and synchronises. */
+int hank_vjp(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar);
+int hank_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar);
+/* The cotangent of the policy sequence of the last hank_vjp, out[(G, P, M)] column-major like hank_get_dpolicy_seq: the
+ * reference's `Δpolicy_seqs` (ForwardIteration.jl:412-416) for the policy variable when n_het = 1. With n_het = 2 it is the
+ * TOTAL cotangent of the savings policy: consumption's dependence on it (-agg_bar[t, 1, m] D_t) is folded in. A new primal or
+ * a new boundary makes it HANK_ERR_NOT_READY until the next hank_vjp (never the cotangents of an older primal). */
+int hank_get_policy_cotangent_seq(hank_ctx *ctx, int32_t M, double *out);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------------------
  * Device time, in milliseconds, of the sweeps of the most recent hank_primal[_dev]/hank_jvp[_dev],
  * from HIP events recorded on the context's stream around each sweep:
@@ -271,6 +294,10 @@ int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_o
  *   out[4] dual-sweep backward, out[5] dual-sweep forward (hank_primal_jvp); -1 where not applicable.
  * launches[k] = kernel launches inside sweep k. Valid after hank_sync. */
 int hank_last_timings(hank_ctx *ctx, double out_ms[6], int32_t launches[6]);
+/* The same for the two sweeps of the most recent hank_vjp[_dev]: out[0] Sweep A (the reverse of the distribution sweep,
+ * ForwardIteration.jl:339-420), out[1] Sweep B (the reverse of the EGM sweep, with the reduction of xhh_bar); -1 before the
+ * first hank_vjp. Valid after hank_sync. */
+int hank_last_vjp_timings(hank_ctx *ctx, double out_ms[2], int32_t launches[2]);
 
 /* Counters of this context (tests and scripts): out[0] sweep kernels launched by the persistent schedule, out[1] tangent
  * workspaces allocated (a change of batch width N re-uses a cached workspace: a small most-recently-used cache, 3 deep),

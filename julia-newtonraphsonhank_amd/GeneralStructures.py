@@ -254,6 +254,20 @@ def JVP(func: Callable, primal, tangent):
     return res.p[:, 0].copy() if single else res.p.copy()
 
 
+def VJP(func, primal, cotangent):
+    """J(primal)ᵀ·cotangent, next to `JVP` (the reference gets these from Zygote pullbacks, SteadyStateJacobian.jl:249-253;
+    its hand-written reverse rules are ForwardIteration.jl:131-192, :339-420). `func` is a function whose linearisation
+    knows its transpose: a `NewtonRaphson.LinearizedFunction` (its record must be `primal`'s), or a callable with a
+    `linearize(primal)` method that returns one. `cotangent`: (m,) or (m, M) -> (n,) or (n, M)."""
+    lin = func.linearize(primal) if hasattr(func, "linearize") else func
+    if not hasattr(lin, "vjp"):
+        raise TypeError("VJP: func has no reverse rule (pass a LinearizedFunction, or a callable with .linearize(primal))")
+    x = getattr(lin, "x", None)
+    if x is not None and not np.array_equal(np.asarray(x), np.asarray(primal, dtype=np.float64)):
+        raise ValueError("VJP: the linearisation was recorded at another primal")
+    return lin.vjp(np.asarray(cotangent, dtype=np.float64))
+
+
 def RayleighQuotient(M, z):
     z = np.asarray(z, dtype=np.float64)
     return float(z @ (M @ z)) / float(z @ z)

@@ -29,6 +29,8 @@ def make_fullFunction(exog_paths, mod: SequenceModel, ss_initial, ss_ending):
         padded_xMat = assemble_full_xMat(x_Vec, agg_seqs, exog_paths, mod, ss_initial, ss_ending)
         return Residuals(padded_xMat, mod)
 
+    # what `VJP(fullFunction, x, ȳ)` differentiates: the linearisation at x, which knows its transpose
+    fullFunction.linearize = lambda x: LinearizedFunction(x, exog_paths, mod, ss_initial, ss_ending)
     return fullFunction
 
 
@@ -154,6 +156,48 @@ class LinearizedFunction:
         Y = y[:, None] if single else y
         out = self._Rx @ Y + self._Ragg @ np.concatenate([daggs[:, j, :] for j in self._out_idx], axis=0)     # rows: het variable, period
         return out[:, 0].copy() if single else out
+
+
+    def vjp(self, ȳ):
+        """J(x)ᵀ·ȳ for one cotangent (n,) or a batch (n, M): the transpose of `jvp`, layer by layer — `_Raggᵀ` (the residual
+        layer's dependence on the aggregates) → ONE hank_vjp (the reverse rules of ForwardIteration.jl:339-420 and of the
+        backward loop) → the transpose of `household_inputs` (a selection of rows of x) — plus `_Rxᵀ`. Cotangent columns that
+        put no weight on any aggregate are not sent to the GPU."""
+        if self._n_out > 2:
+            raise NotImplementedError(
+                f"LinearizedFunction.vjp: the heterogeneous variables {self.het} reach {self.mod.value_fn.outputs[self._n_out - 1]!r} "
+                "(device output >= 2), which is not affine in the policy: hank_vjp carries cotangents on the policy variable and on consumption only")
+        ȳ = np.asarray(ȳ, dtype=np.float64)
+        single = ȳ.ndim == 1
+        Yb = ȳ[:, None] if single else ȳ
+        if self._Rx is None:
+            self._linearise_residuals()
+        cs = self.mod.compspec
+        P, M = cs.T - 1, Yb.shape[1]
+        out = np.asarray(self._Rx.T @ Yb)
+        ab = np.asarray(self._Ragg.T @ Yb).reshape(len(self.het), P, M)          # rows: het variable, period
+        agg_bar = np.zeros((P, self._n_out, M))
+        for j, o in enumerate(self._out_idx):
+            agg_bar[:, o, :] += ab[j]
+        nz = np.flatnonzero(np.any(agg_bar != 0.0, axis=(0, 1)))
+        if len(nz):
+            if getattr(self.hb, "_generation", None) != self._generation:
+                self._record_primal()           # (the same generation check as jvp: the context holds another x's record)
+            xb = self.hb.vjp(agg_bar[:, :, nz], self._n_out)                     # (n_hh, P, len(nz))
+            endog_keys = vars_of_type(self.mod, "endogenous")
+            for k, name in enumerate(self.mod.value_fn.household_inputs):
+                if name in endog_keys:          # exogenous inputs carry no cotangent back to x; x is (n_endog, P) column-major
+                    out[np.ix_(endog_keys.index(name) + cs.n_endog * np.arange(P), nz)] += xb[k]
+        return out[:, 0].copy() if single else out
+
+    def as_linear_operator(self):
+        """J(x) as a scipy.sparse.linalg.LinearOperator with both products: matvec / matmat = `jvp`, rmatvec / rmatmat = `vjp`
+        (LSQR / LSMR, BiCG, QMR and every other user of the transpose)."""
+        n = len(self.x)
+        col = lambda f: (lambda v: f(np.asarray(v, dtype=np.float64).reshape(-1)))
+        mat = lambda f: (lambda V: f(np.asarray(V, dtype=np.float64)))
+        return spla.LinearOperator((len(self.Fx), n), matvec=col(self.jvp), matmat=mat(self.jvp), rmatvec=col(self.vjp), rmatmat=mat(self.vjp),
+                                   dtype=np.float64)
 
 
 def _gmres(J, b, x0):

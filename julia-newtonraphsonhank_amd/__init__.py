@@ -6,7 +6,7 @@ block implemented as hand-written HIP kernels for gfx950 behind a C ABI (include
 """
 from .dual import Dual
 from .GeneralStructures import (ComputationalSpec, HeterogeneityDimension, SequenceModel, SteadyStateSpec,
-                                Variable, JVP, RayleighQuotient, assemble_full_xMat, double_exponential,
+                                Variable, JVP, VJP, RayleighQuotient, assemble_full_xMat, double_exponential,
                                 generate_exog_paths, get_RouwenhorstDiscretization, invariant_dist,
                                 make_DoubleExponentialGrid, n_total, rouwenhorst_discretization, shift_lag,
                                 shift_lead, var_names, vars_of_type)

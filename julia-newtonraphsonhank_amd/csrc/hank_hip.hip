@@ -8,6 +8,7 @@
 #include "hank_jacobian.h"
 #include "hank_wide.h"
 #include "hank_hetx.h"
+#include "hank_adjoint.h"
 #include "../../include/hank_hip.h"
 
 #include <cstdarg>
@@ -100,6 +101,28 @@ struct WTan {
     double *dagg_cm = nullptr;      // (P, N) column-major
 };
 
+// ---- transposed sweeps (hank_adjoint.h): hank_vjp's workspace per batch width M (its own: no TanWork's dpol is reused, so the
+// current tangent batch stays current and its readers keep serving it) ----
+struct CotWork {
+    int N = 0;                      // the batch width M (the cache's key)
+    int V = 1;                      // cotangent columns per lane
+    AdjGeom g{};
+    double *ybar = nullptr;         // (P, n_het <= 2, M) the caller's cotangents (staging for both entries)
+    double *yb0 = nullptr, *yb1 = nullptr;      // [P][M] cotangents of the policy variable's aggregate and of consumption's
+    double *st[2] = {nullptr, nullptr};         // [G][M] ping-pong state: lam in Sweep A, then mu in Sweep B
+    double *pbar = nullptr;         // [P][G][M] the policy cotangent sequence: written once by Sweep A, read once by Sweep B
+    double *partS = nullptr, *partM = nullptr;  // [P][nb][3][M] per-block partial sums of the inputs' cotangents
+    double *xbar = nullptr;         // (n_hh, P, M) column-major
+    hipGraphExec_t g_A = nullptr, g_B = nullptr;
+};
+// The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
+struct CotBatch {
+    bool current = false;
+    int M = 0;
+    const void *ws = nullptr;
+    const double *pbar = nullptr;
+};
+
 // The current tangent batch: at most ONE is current, and it belongs to the recorded primal. Written by batch_ran ("family F has
 // just run a batch on workspace W") and batch_none ("nothing is current") only; the readers ask batch_current.
 struct TanBatch {
@@ -153,6 +176,11 @@ struct hank_ctx {
     bool seg_valid = true;          // the record's per-target segment records match its lottery (k_lottery writes them except in the persistent Dual pass)
     bool wprep_valid = false;
     std::list<WTan> wtans;         // most recently used first
+    std::list<CotWork> cws;        // hank_vjp's workspaces, most recently used first
+    CotBatch cot;                  // the current cotangent batch (hank_get_policy_cotangent_seq)
+    int *d_adj_sb = nullptr;       // [P][n_e][n_a + 1] Sweep B's bracket segment starts (k_adj_seg), valid for the recorded primal or not
+    bool adj_seg_valid = false;
+    bool vjp_ev_valid = false;     // ev[11..13] bracket the sweeps of the last hank_vjp
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
     long long stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // see hank_stats
     // primal memo of the host-pointer hank_primal_jvp (NewtonRaphson.jl:91-95 calls JVP(fullFunction, x, y) ~21 times at one x):
@@ -173,6 +201,8 @@ struct hank_ctx {
 static int fail(hank_ctx *ctx, int code, const char *fmt, ...);
 static void free_fn(hank_ctx *ctx);
 static void batch_none(hank_ctx *ctx) { ctx->batch.current = false; ctx->batch.ws = nullptr; }
+static void cot_none(hank_ctx *ctx) { ctx->cot = CotBatch(); }
+static void cot_ran(hank_ctx *ctx, const void *ws, int M, const double *pbar) { ctx->cot = CotBatch{true, M, ws, pbar}; }
 static void batch_ran(hank_ctx *ctx, int family, const void *ws, int N, const double *dagg_cm, const double *dpol, const std::vector<XPass> *passes = nullptr) {
     ctx->batch = TanBatch{family, true, N, ws, dagg_cm, dpol, passes};
 }
@@ -186,13 +216,21 @@ static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
 // batch. seg_written: the per-target segment records were written with it (k_lottery writes them except in the persistent Dual pass)
 static void record_rewritten(hank_ctx *ctx, bool seg_written) {
     ctx->primal_done = true; ctx->seg_valid = seg_written;
-    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false;
+    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false;
     batch_none(ctx);
+    cot_none(ctx);
 }
 // the record is gone (a new boundary, a persistent sweep that did not run): the next tangent sweep needs a primal first
 static void record_gone(hank_ctx *ctx) {
     record_rewritten(ctx, false);
     ctx->primal_done = false;
+}
+static void free_cotwork(CotWork &w) {
+    if (w.g_A) (void)hipGraphExecDestroy(w.g_A);
+    if (w.g_B) (void)hipGraphExecDestroy(w.g_B);
+    (void)hipFree(w.ybar); (void)hipFree(w.yb0); (void)hipFree(w.yb1); (void)hipFree(w.st[0]); (void)hipFree(w.st[1]);
+    (void)hipFree(w.pbar); (void)hipFree(w.partS); (void)hipFree(w.partM); (void)hipFree(w.xbar);
+    w = CotWork();
 }
 static void w_free_tan(WTan &w) {
     (void)hipFree(w.dxhh); (void)hipFree(w.dpol); (void)hipFree(w.dagg_cm);
@@ -437,6 +475,7 @@ static int tan_cache_get(hank_ctx *ctx, std::list<W> &cache, int N, void (*relea
         HIPC(ctx, join_side(ctx));
         HIPC(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->batch.ws == &cache.back()) batch_none(ctx);
+        if (ctx->cot.ws == &cache.back()) cot_none(ctx);
         release(cache.back());
         cache.pop_back();
     }
@@ -1220,6 +1259,9 @@ int hank_destroy(hank_ctx *ctx) {
     if (ctx->g_pfwd) (void)hipGraphExecDestroy(ctx->g_pfwd);
     for (WTan &t : ctx->wtans) w_free_tan(t);
     ctx->wtans.clear();
+    for (CotWork &t : ctx->cws) free_cotwork(t);
+    ctx->cws.clear();
+    (void)hipFree(ctx->d_adj_sb);
     (void)hipFree(ctx->rec_slab); (void)hipFree(ctx->d_ibw); (void)hipFree(ctx->hx_slab);
     (void)hipFree(ctx->d_a); (void)hipFree(ctx->d_z); (void)hipFree(ctx->d_Pi); (void)hipFree(ctx->d_ss_value);
     (void)hipFree(ctx->d_xhh); (void)hipFree(ctx->d_agg); (void)hipFree(ctx->d_agg_rm); (void)hipFree(ctx->d_zd); (void)hipFree(ctx->d_aggpart); (void)hipFree(ctx->d_err);
@@ -1921,6 +1963,177 @@ int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out) {
     return HANK_OK;
 }
 
+}  // extern "C"
+
+// ================================ transposed sweeps: hank_vjp (hank_adjoint.h) ==========================
+// Lane geometry per batch width M: two adjacent cotangent columns per lane for an even M (16-byte state / pbar accesses); at
+// most 16 lanes span the columns (wider batches take more blocks in y), so a wave instruction moves RB = 64 / NC >= 4 rows;
+// a block owns R = max(RB, 8) rows: its LDS tile (n_e x (R + 2) x NC lanes) stays below 48 KiB up to n_e = 16.
+static int build_cotwork(hank_ctx *ctx, CotWork &w) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P, G = c.G, M = (size_t)w.N;
+    w.V = (w.N % 2 == 0) ? 2 : 1;
+    AdjGeom &g = w.g;
+    g.MV = w.N / w.V;
+    g.NC = 1; g.lgNC = 0;
+    while (g.NC < g.MV && g.NC < 16) { g.NC <<= 1; g.lgNC++; }
+    const int RB = 64 / g.NC;
+    g.R = std::max(RB, 8);
+    g.nb = (c.n_a + g.R - 1) / g.R;
+    HIPC(ctx, dmalloc(&w.ybar, 2 * P * M));
+    HIPC(ctx, dmalloc(&w.yb0, P * M));
+    HIPC(ctx, dmalloc(&w.yb1, P * M));
+    for (int k = 0; k < 2; k++) HIPC(ctx, dmalloc(&w.st[k], G * M));
+    HIPC(ctx, dmalloc(&w.pbar, P * G * M));
+    HIPC(ctx, dmalloc(&w.partS, P * (size_t)g.nb * 3 * M));
+    HIPC(ctx, dmalloc(&w.partM, P * (size_t)g.nb * 3 * M));
+    HIPC(ctx, dmalloc(&w.xbar, (size_t)c.n_hh * P * M));
+    return HANK_OK;
+}
+static size_t adj_lds_dist(const Consts &c, const AdjGeom &g, int V) { return sizeof(double) * ((size_t)c.n_e * (g.R + 2) * g.NC * V + (size_t)c.n_e * c.n_e); }
+static size_t adj_lds_egm(const Consts &c, const AdjGeom &g, int V) {
+    return sizeof(double) * ((size_t)c.n_e * g.R * g.NC * V + (((size_t)c.n_e * c.n_e + 1) & ~(size_t)1) + (size_t)c.n_e * 6 * g.NC * V);
+}
+
+// the two graphs of a width, captured the first time hank_vjp runs at it: Sweep A (P launches, t = P-1 .. 0) and Sweep B
+// (P launches, t = 0 .. P-1, then the fixed-order reduction of the inputs' cotangents)
+template <typename VT>
+static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
+    const Consts &c = ctx->c;
+    const int P = c.P;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(64 * c.n_e), grd((unsigned)w.g.nb, (unsigned)((w.g.MV + w.g.NC - 1) / w.g.NC));
+    const size_t ldsA = adj_lds_dist(c, w.g, w.V), ldsB = adj_lds_egm(c, w.g, w.V);
+    VT *st[2] = {reinterpret_cast<VT *>(w.st[0]), reinterpret_cast<VT *>(w.st[1])};
+    VT *pbar = reinterpret_cast<VT *>(w.pbar);
+    const VT *yb0 = reinterpret_cast<const VT *>(w.yb0), *yb1 = reinterpret_cast<const VT *>(w.yb1);
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int cur = 0;
+    for (int t = P - 1; t >= 0; t--) {
+        hipLaunchKernelGGL((k_adj_dist<VT>), grd, blk, ldsA, s, c, ctx->R, ctx->d_xhh, w.g, t, t == P - 1 ? 1 : 0, yb0, yb1, st[cur], st[cur ^ 1], pbar);
+        cur ^= 1;
+    }
+    int rc = end_capture(ctx, &w.g_A);
+    if (rc) return rc;
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    cur = 0;
+    for (int t = 0; t < P; t++) {
+        hipLaunchKernelGGL((k_adj_egm<VT>), grd, blk, ldsB, s, c, ctx->R, w.g, t, t == 0 ? 1 : 0, t == P - 1 ? 1 : 0, ctx->d_adj_sb, st[cur], st[cur ^ 1], pbar,
+                           reinterpret_cast<VT *>(w.partS), reinterpret_cast<VT *>(w.partM));
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(k_adj_out, dim3((unsigned)((P * w.N + 255) / 256)), dim3(256), 0, s, P, c.n_hh, w.N, w.g.nb, ctx->d_xhh, w.partS, w.partM, w.yb1,
+                       ctx->d_agg + P, ctx->d_zd, w.xbar);
+    return end_capture(ctx, &w.g_B);
+}
+
+// Sweep B's segment starts belong to the record (like seg_valid): built before the first hank_vjp at a record, by whichever family wrote it
+static int ensure_adj_seg(hank_ctx *ctx) {
+    const Consts &c = ctx->c;
+    if (ctx->adj_seg_valid) return HANK_OK;
+    hipLaunchKernelGGL(k_adj_seg, dim3((unsigned)(c.P * c.n_e)), dim3(256), sizeof(int) * ((size_t)c.n_a + 1), ctx->stream, c, ctx->R, c.P * c.n_e, ctx->d_adj_sb);
+    HIPC(ctx, hipGetLastError());
+    ctx->adj_seg_valid = true;
+    return HANK_OK;
+}
+
+// hank_vjp[_dev]: M cotangent columns from the caller (kind: where they live) through the transposed sweeps at the recorded
+// primal, whichever family recorded it. Touches neither the record nor the tangent batch nor the primal memo.
+static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P;
+    CotWork *w = nullptr;
+    int rc = tan_cache_get(ctx, ctx->cws, M, free_cotwork, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
+    if (rc) return rc;
+    if (adj_lds_dist(c, w->g, w->V) > ctx->lds_max || adj_lds_egm(c, w->g, w->V) > ctx->lds_max)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_e=%d needs more LDS per workgroup than the device has", c.n_e);
+    if (!w->g_A) {
+        if (!ctx->d_adj_sb) HIPC(ctx, dmalloc(&ctx->d_adj_sb, P * c.n_e * ((size_t)c.n_a + 1)));      // (the graphs hold its address)
+        rc = w->V == 2 ? capture_cot_graphs<double2>(ctx, *w) : capture_cot_graphs<double>(ctx, *w);
+        if (rc) return rc;
+    }
+    hipStream_t s = ctx->stream;
+    HIPC(ctx, hipMemcpyAsync(w->ybar, agg_bar, sizeof(double) * P * n_het * M, kind, s));
+    HIPC(ctx, join_side(ctx));      // D_t, the lottery and the grid aggregates come from the primal's forward sweep
+    rc = ensure_adj_seg(ctx);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_adj_in, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->yb0, w->yb1);
+    HIPC(ctx, hipEventRecord(ctx->ev[11], s));
+    HIPC(ctx, hipGraphLaunch(w->g_A, s));
+    HIPC(ctx, hipEventRecord(ctx->ev[12], s));
+    HIPC(ctx, hipGraphLaunch(w->g_B, s));
+    HIPC(ctx, hipEventRecord(ctx->ev[13], s));
+    ctx->vjp_ev_valid = true;
+    cot_ran(ctx, w, M, w->pbar);
+    if (d_xhh_bar) HIPC(ctx, hipMemcpyAsync(d_xhh_bar, w->xbar, sizeof(double) * c.n_hh * P * M, hipMemcpyDeviceToDevice, s));
+    *out = w;
+    return HANK_OK;
+}
+static int vjp_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out) {
+    if (!ctx || !in || !out || M < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: bad argument (M=%d)", M);
+    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
+    if (n_het > 2 && n_het <= max_het)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_het=%d reaches Value / UCE, which are not affine in the policy: their cotangents are not implemented (n_het must be 1 or 2)", n_het);
+    if (n_het < 1 || n_het > 2) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_het must be 1 (the policy variable) or 2 (and consumption), got %d", n_het);
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp");
+    return HANK_OK;
+}
+
+extern "C" {
+int hank_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) {
+    ENTER(ctx);
+    int rc = vjp_args(ctx, n_het, d_agg_bar, M, d_xhh_bar);
+    if (rc) return rc;
+    CotWork *w = nullptr;
+    return enqueue_vjp(ctx, n_het, d_agg_bar, hipMemcpyDeviceToDevice, M, d_xhh_bar, &w);
+}
+
+int hank_vjp(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) {
+    ENTER(ctx);
+    int rc = vjp_args(ctx, n_het, agg_bar, M, xhh_bar);
+    if (rc) return rc;
+    CotWork *w = nullptr;
+    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w);
+    if (rc) return rc;
+    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
+int hank_get_policy_cotangent_seq(hank_ctx *ctx, int32_t M, double *out) {
+    if (!ctx || !out) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    if (!ctx->cot.current || ctx->cot.M != M) return fail(ctx, HANK_ERR_NOT_READY, "no hank_vjp with M=%d is current", M);
+    const size_t G = ctx->c.G, P = ctx->c.P, total = P * G * (size_t)M;
+    double *tmp = nullptr;
+    HIPC(ctx, dmalloc(&tmp, total));
+    hipLaunchKernelGGL(k_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cot.pbar, (int)G, (int)P, M, tmp);
+    hipError_t e0 = hipGetLastError();
+    hipError_t e1 = hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(tmp);
+    HIPC(ctx, e0);
+    HIPC(ctx, e1);
+    HIPC(ctx, e2);
+    return HANK_OK;
+}
+
+int hank_last_vjp_timings(hank_ctx *ctx, double out_ms[2], int32_t launches[2]) {
+    if (!ctx || !out_ms) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 2; k++) {
+        out_ms[k] = -1.0;
+        if (ctx->vjp_ev_valid) {
+            float ms = 0.f;
+            HIPC(ctx, hipEventElapsedTime(&ms, ctx->ev[11 + k], ctx->ev[12 + k]));
+            out_ms[k] = ms;
+        }
+        if (launches) launches[k] = ctx->c.P + k;
+    }
+    return HANK_OK;
+}
 }  // extern "C"
 
 // ---- granular steps ---------------------------------------------------------------------------

@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "hank_get_policy_seq", "hank_get_dpolicy_seq", "hank_get_dist_seq", "hank_get_het_outputs", "hank_get_het_outputs_dev", "hank_set_het_outputs",
     "hank_get_grid_aggregates", "hank_get_grid_aggregates_dev", "hank_backward_step",
     "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
+    "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings",
 )
 
 
@@ -115,6 +116,10 @@ def load_library() -> C.CDLL:
     lib.hank_fake_news.argtypes = [vp, dp, dp]
     lib.hank_fake_news_het.argtypes = [vp, i32, dp, dp]
     lib.hank_device_available.argtypes = []
+    lib.hank_vjp.argtypes = [vp, i32, dp, i32, dp]
+    lib.hank_vjp_dev.argtypes = [vp, i32, vp, i32, vp]
+    lib.hank_get_policy_cotangent_seq.argtypes = [vp, i32, dp]
+    lib.hank_last_vjp_timings.argtypes = [vp, dp, C.POINTER(i32)]
     for name in ABI_SYMBOLS:
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
@@ -277,6 +282,40 @@ class HouseholdBlock:
 
     def jvp_dev(self, d_dxhh_ptr: int, N: int, d_dagg_ptr: int = 0):
         self._chk(self._lib.hank_jvp_dev(self._ctx, C.c_void_p(d_dxhh_ptr), int(N), C.c_void_p(d_dagg_ptr)))
+
+    # -- the transposed block ---------------------------------------------------------------
+    def vjp(self, agg_bar, n_het: int = 1) -> np.ndarray:
+        """J(x)' agg_bar at the recorded primal (hank_vjp; the reverse rules of ForwardIteration.jl:339-420 and of the
+        backward loop). agg_bar: (P,) or (P, M) for n_het = 1, (P, n_het, M) in general — cotangents of the aggregates of
+        the policy variable and (n_het = 2) of consumption. -> xhh_bar (n_hh, P, M)."""
+        yb = np.asarray(agg_bar, dtype=np.float64)
+        if yb.ndim == 1:
+            yb = yb[:, None]
+        if yb.ndim == 2:
+            if int(n_het) != 1:
+                raise ValueError("agg_bar must be (P, n_het, M) when n_het > 1")
+            yb = yb[:, None, :]
+        M = yb.shape[2]
+        yb = _f(yb, (self.P, int(n_het), M) if int(n_het) in (1, 2) else None)      # (the library refuses any other n_het)
+        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
+        self._chk(self._lib.hank_vjp(self._ctx, int(n_het), _p(yb), M, _p(out)))
+        return out
+
+    def vjp_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int):
+        """device-pointer form (asynchronous on the context's stream)."""
+        self._chk(self._lib.hank_vjp_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr)))
+
+    def policy_cotangent_seq(self, M: int) -> np.ndarray:
+        """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp (hank_get_policy_cotangent_seq)."""
+        out = np.empty((self.n_a, self.n_e, self.P, max(int(M), 1)), order="F")
+        self._chk(self._lib.hank_get_policy_cotangent_seq(self._ctx, int(M), _p(out)))
+        return out
+
+    def last_vjp_timings(self):
+        ms = (C.c_double * 2)()
+        ln = (C.c_int32 * 2)()
+        self._chk(self._lib.hank_last_vjp_timings(self._ctx, ms, ln))
+        return {k: {"ms": ms[i], "launches": ln[i]} for i, k in enumerate(("sweep_a", "sweep_b"))}
 
     def last_timings(self):
         ms = (C.c_double * 6)()

@@ -287,3 +287,46 @@ function _toeplitz_recursion(F::Array{Float64,3}, Dv::Matrix{Float64})
     end
     return J
 end
+
+# ---- the transposed household block (hank_vjp) -----------------------------------------------------------------------------
+# xhh_bar = J(x)' agg_bar at the primal the context has on record (the last hank_primal / hank_primal_jvp): the pullback of
+# ForwardIteration (ForwardIteration.jl:339-420, on the reverse rule of transition_step, :131-192) followed by the transpose of
+# the partials of BackwardIteration, for M cotangent columns at once. agg_bar is (P, n_het, M): cotangents of the aggregates of
+# ctx.outputs[1] (the policy variable) and, with n_het = 2, of ctx.outputs[2] (consumption); xhh_bar is (n_hh, P, M), rows in
+# the order of ctx.hh_rows. Returns xhh_bar.
+function hank_vjp!(xhh_bar::Array{Float64,3}, ctx::HankCtx, agg_bar::Array{Float64,3})
+    P, n_het, M = size(agg_bar)
+    @assert P == ctx.P && size(xhh_bar) == (length(ctx.hh_rows), P, M)
+    _check(ctx.ptr, ccall((:hank_vjp, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}),
+                          ctx.ptr, Int32(n_het), agg_bar, Int32(M), xhh_bar))
+    return xhh_bar
+end
+
+# the cotangent of the policy sequence of the last hank_vjp!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
+# (ForwardIteration.jl:412-416) for the policy variable when n_het = 1
+function hank_policy_cotangent_seq(ctx::HankCtx, M::Integer)
+    out = Array{Float64}(undef, ctx.n_a, ctx.n_e, ctx.P, M)
+    _check(ctx.ptr, ccall((:hank_get_policy_cotangent_seq, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), ctx.ptr, Int32(M), out))
+    return out
+end
+
+# A ChainRules-shaped pullback of the device household block, for callers that differentiate a scalar of the path in reverse
+# mode: `agg, pb = ForwardIteration_pullback(seqs, model, ss_initial)`; `pb(Δagg)` takes the cotangents of the aggregates as a
+# NamedTuple keyed like `agg` (the shape of the reference's ForwardIteration_pullback argument, ForwardIteration.jl:387) and
+# returns the cotangent of the household inputs as an (n_hh, P) matrix (rows: ctx.hh_rows) — the device sweeps BackwardIteration
+# and ForwardIteration together, so the pullback covers both. Heterogeneous keys beyond consumption are refused by the library.
+function ForwardIteration_pullback(seqs::DevicePolicySeqs, model::SequenceModel, ss_initial)
+    agg = ForwardIteration(seqs, model, ss_initial)             # records the primal the pullback is taken at
+    ctx = hank_context(model)
+    het_keys = Tuple(Symbol.(vars_of_type(model, :heterogeneous)))
+    n_het = _n_het(ctx, het_keys)
+    function pullback(Δagg)
+        agg_bar = zeros(Float64, ctx.P, n_het, 1)
+        for k in het_keys
+            agg_bar[:, findfirst(==(k), ctx.outputs), 1] .= Δagg[k]
+        end
+        xhh_bar = Array{Float64}(undef, length(ctx.hh_rows), ctx.P, 1)
+        return hank_vjp!(xhh_bar, ctx, agg_bar)[:, :, 1]
+    end
+    return agg, pullback
+end
