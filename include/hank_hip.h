@@ -313,7 +313,9 @@ int hank_stats(hank_ctx *ctx, int64_t out[8]);
  * direction, the loop-carried state in registers), out[1] the wide sweeps' mode (0 off, 1 auto: batches of at least out[2]
  * directions, 2 every batch: HANK_SCHEDULE=wide), out[2] that threshold (HANK_WIDE_MIN at hank_create), out[3] 1 when the grid fits
  * the wide sweeps, out[4] the widest batch the persistent tangent sweeps take at a recorded primal, out[5] 1 when the tangent sweeps
- * rebuild kc and v instead of reading them (record diet), out[6] bytes of the linearisation record, out[7] reserved. */
+ * rebuild kc and v instead of reading them (record diet), out[6] bytes of the linearisation record, out[7] times the per-source
+ * records {w, ig D} were built on demand (a persistent Dual pass does not write them: the first tangent sweep or hank_fake_news
+ * at its record builds them, once per record). */
 int hank_info(hank_ctx *ctx, int64_t out[8]);
 
 #ifdef __cplusplus

@@ -77,6 +77,7 @@ struct XWork {
     XSync *sync = nullptr;          // [2 * XPASS_MAX]: backward and forward sweep of every pass
     double *st_s = nullptr, *st_ds = nullptr, *st_D = nullptr, *st_dD = nullptr;
     double *Dvirt = nullptr, *aggpart = nullptr, *rho = nullptr;
+    double *D0own = nullptr;        // [P][n_e] row 0 of every D_t as member 0 held it, before the virtual rows' mass was added (k_xlwg_build)
     int *srcB = nullptr, *srcF = nullptr;     // [P][Sact] source-member ranges of the tangent sweeps at the recorded primal
     int2 *unitsF = nullptr;                   // [P][Sact][XUCAP] the forward sweeps' work units (k_xunits_fwd)
     int *unit_overflow = nullptr;             // set by k_xunits_fwd when a member has more units than XUCAP
@@ -174,6 +175,8 @@ struct hank_ctx {
     size_t rec_bytes = 0;
     int *d_ibw = nullptr;          // the wide backward sweep's bracket record (k_wide_prep), valid for the recorded primal or not
     bool seg_valid = true;          // the record's per-target segment records match its lottery (k_lottery writes them except in the persistent Dual pass)
+    bool lwg_valid = true;          // the record's per-source records {w, ig D} match it (every forward sweep of a primal writes them except the persistent Dual pass's)
+    long long lwg_builds = 0;       // times k_xlwg_build ran (hank_info)
     bool wprep_valid = false;
     std::list<WTan> wtans;         // most recently used first
     std::list<CotWork> cws;        // hank_vjp's workspaces, most recently used first
@@ -213,16 +216,17 @@ static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
     return HANK_OK;
 }
 // the record was rewritten (or is about to be, by work already enqueued): what was derived from the old one goes, and so does the
-// batch. seg_written: the per-target segment records were written with it (k_lottery writes them except in the persistent Dual pass)
-static void record_rewritten(hank_ctx *ctx, bool seg_written) {
-    ctx->primal_done = true; ctx->seg_valid = seg_written;
+// batch. seg_written: the per-target segment records were written with it (k_lottery writes them except in the persistent Dual pass);
+// lwg_written: so were the per-source records {w, ig D} (the forward sweep writes them except the persistent Dual pass's)
+static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written) {
+    ctx->primal_done = true; ctx->seg_valid = seg_written; ctx->lwg_valid = lwg_written;
     ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false;
     batch_none(ctx);
     cot_none(ctx);
 }
 // the record is gone (a new boundary, a persistent sweep that did not run): the next tangent sweep needs a primal first
 static void record_gone(hank_ctx *ctx) {
-    record_rewritten(ctx, false);
+    record_rewritten(ctx, false, false);
     ctx->primal_done = false;
 }
 static void free_cotwork(CotWork &w) {
@@ -631,7 +635,7 @@ static void x_free(hank_ctx *ctx) {
     for (XTan &w : X.tans) x_free_tan(w);
     X.tans.clear();
     (void)hipFree(X.sync); (void)hipFree(X.st_s); (void)hipFree(X.st_ds); (void)hipFree(X.st_D); (void)hipFree(X.st_dD);
-    (void)hipFree(X.Dvirt); (void)hipFree(X.aggpart); (void)hipFree(X.rho); (void)hipFree(X.srcB); (void)hipFree(X.srcF); (void)hipFree(X.unitsF); (void)hipFree(X.unit_overflow);
+    (void)hipFree(X.Dvirt); (void)hipFree(X.D0own); (void)hipFree(X.aggpart); (void)hipFree(X.rho); (void)hipFree(X.srcB); (void)hipFree(X.srcF); (void)hipFree(X.unitsF); (void)hipFree(X.unit_overflow);
     X = XWork();
 }
 
@@ -655,6 +659,7 @@ static int x_setup(hank_ctx *ctx) {
     HIPC(ctx, dmalloc(&X.st_D, 2 * XG * std::max(GV, GM)));
     HIPC(ctx, dmalloc(&X.st_dD, 2 * XG * GM * (X.dmax + 2)));      // D partials + the value, padded to pairs
     HIPC(ctx, dmalloc(&X.Dvirt, P * c.n_e * 64));
+    HIPC(ctx, dmalloc(&X.D0own, P * c.n_e));
     HIPC(ctx, dmalloc(&X.aggpart, 2 * P * (size_t)X.Sact));       // [P][members][2]
     HIPC(ctx, dmalloc(&X.rho, P));
     HIPC(ctx, dmalloc(&X.srcB, P * X.Sact));
@@ -758,6 +763,17 @@ static int ensure_seg(hank_ctx *ctx) {       // before a reader of R.seg (launch
     ctx->seg_valid = true;
     return HANK_OK;
 }
+// before a reader of R.lwg (every forward tangent sweep at a recorded primal — persistent, launch family, wide — and
+// hank_fake_news): a persistent Dual pass leaves the record to be made from what it wrote (lw, ig, D_t, the virtual rows' mass)
+static int ensure_lwg(hank_ctx *ctx) {
+    if (ctx->lwg_valid) return HANK_OK;
+    const XWork &X = ctx->xw;
+    hipLaunchKernelGGL(k_xlwg_build, dim3((unsigned)(ctx->c.P * ctx->c.n_e)), dim3(256), 0, ctx->stream, ctx->c, ctx->R, X.Dvirt, X.D0own, X.Sact);
+    HIPC(ctx, hipGetLastError());
+    ctx->lwg_valid = true;
+    ctx->lwg_builds++;
+    return HANK_OK;
+}
 static int x_serialize_begin(hank_ctx *ctx) {
     const int d = ctx->device & 63;
     if (t_xdepth[d]++ == 0) g_xsection[d].lock();
@@ -827,7 +843,7 @@ static int x_run_primal(hank_ctx *ctx, bool skip_fwd = false, XTan *dual = nullp
     HIPC(ctx, hipEventRecord(ctx->ev[1], s));
     // (the Dual pass's forward half reads the lottery through its work units: the per-target segment records are built when somebody asks)
     hipLaunchKernelGGL(k_lottery, dim3((unsigned)(P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, (int)P * c.n_e, ctx->d_err, dual ? 0 : 1, 1);
-    record_rewritten(ctx, !dual);
+    record_rewritten(ctx, !dual, !skip_fwd && HANK_XPRIMAL_LWG_IN_SWEEP);     // (skip_fwd: the Dual pass's forward half follows, and it writes no per-source records)
     x_ensure_rng(ctx);
     HIPC(ctx, hipEventRecord(ctx->ev[6], s));
     if (!skip_fwd) {
@@ -840,7 +856,7 @@ static int x_run_primal(hank_ctx *ctx, bool skip_fwd = false, XTan *dual = nullp
     if (!skip_fwd) {
         hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, X.aggpart, X.Sact, 2, ctx->d_agg_rm);
             hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
-        hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact);
+        hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact, X.D0own);
     }
     HIPC(ctx, hipGetLastError());
     rc = x_serialize_end(ctx);
@@ -902,20 +918,21 @@ static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_bac
         fa.sy = X.sync + 2 + 2 * p + 1; fa.groups = ps.groups; fa.dpol = w->dpol + ps.dpol_off;
         const bool v = val && p == 0;
         if (v) { fa.D0 = ctx->d_ss_D; fa.Dvirt = X.Dvirt; fa.aggpart = X.aggpart; }
+        else { rc = ensure_lwg(ctx); if (rc) return rc; }      // (behind k_xfix_D where the first pass carried the value)
         x_launch_fwd(X, ps.D, v, grd, blkF, x_lds_fwd(c, ps.D + (v ? 1 : 0)), s, fa);
         const int W = XG * ps.D;
         if (v && np == 1 && xo) {               // the one-pass Dual pass: everything behind the sweep in ONE launch (k_xdual_epilogue)
             HIPC(ctx, hipEventRecord(ctx->ev[5], s));
             const int per = 2 * W + 2 + c.n_e;
             hipLaunchKernelGGL(k_xdual_epilogue, dim3((unsigned)((P * per + 255) / 256)), dim3(256), 0, s, c, X.aggpart, w->daggpart, X.Sact, W, ps.n0, ps.N, N,
-                               ctx->d_agg_rm, ctx->d_agg, w->dagg_pass, w->dagg_cm, ctx->R.Dseq, X.Dvirt, xo->agg, xo->dagg);
+                               ctx->d_agg_rm, ctx->d_agg, w->dagg_pass, w->dagg_cm, ctx->R.Dseq, X.Dvirt, X.D0own, xo->agg, xo->dagg);
             xo->done = true;
             break;
         }
         if (v) {
             hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, X.aggpart, X.Sact, 2, ctx->d_agg_rm);
             hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
-            hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact);
+            hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact, X.D0own);
         }
         if (p == np - 1) HIPC(ctx, hipEventRecord(ctx->ev[5], s));
         hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * W + 63) / 64), dim3(256), 0, s, w->daggpart, nb, 2 * W, w->dagg_pass);
@@ -1062,6 +1079,8 @@ static int w_run_tangent(hank_ctx *ctx, WTan *w, const double *d_dxhh) {
     if (rc) return rc;
     HIPC(ctx, hipEventRecord(ctx->ev[4], s));
     HIPC(ctx, join_side(ctx));              // the forward sweep reads D_t and the {w, ig D} record of the primal's forward sweep
+    rc = ensure_lwg(ctx);
+    if (rc) return rc;
     HIPC(ctx, hipEventRecord(ctx->ev[7], s));
     rc = w_launch(ctx, true, w->N, a);
     if (rc) return rc;
@@ -1362,7 +1381,7 @@ static int run_primal(hank_ctx *ctx, double *d_agg_out) {
     ctx->side_pending = true;
     ctx->ev_valid[0] = ctx->ev_valid[1] = true;
     ctx->ev_valid[4] = ctx->ev_valid[5] = false;
-    record_rewritten(ctx, true);
+    record_rewritten(ctx, true, true);
     return HANK_OK;
 }
 
@@ -1534,6 +1553,7 @@ static int run_jvp(hank_ctx *ctx, TanWork &w) {
     HIPC(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     HIPC(ctx, join_side(ctx));      // the tangent forward sweep needs D_t
     { const int src = ensure_seg(ctx); if (src) return src; }
+    { const int src = ensure_lwg(ctx); if (src) return src; }
     HIPC(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     HIPC(ctx, hipGraphLaunch(w.g_fwd, ctx->stream));
     HIPC(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
@@ -1605,7 +1625,7 @@ static int run_fused(hank_ctx *ctx, TanWork &w) {
     HIPC(ctx, hipEventRecord(ctx->ev[10], ctx->stream));
     ctx->ev_valid[4] = ctx->ev_valid[5] = true;
     ctx->ev_valid[0] = ctx->ev_valid[1] = ctx->ev_valid[2] = ctx->ev_valid[3] = false;
-    record_rewritten(ctx, true);
+    record_rewritten(ctx, true, true);
     batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
     return HANK_OK;
 }
@@ -1747,6 +1767,7 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
                         "it needs hank_primal at the steady state with the steady state as both boundaries", name, P, diff);
     }
     { const int src = ensure_seg(ctx); if (src) return src; }
+    { const int src = ensure_lwg(ctx); if (src) return src; }
     // 1. n_hh backward tangent sweeps (one batch) seeded at the last period: every lag of the policy response
     TanWork *wp = nullptr;
     int rc = ensure_tanwork(ctx, N, &wp);
@@ -1877,7 +1898,7 @@ int hank_gather_columns(hank_ctx *const *ctxs, int32_t n, const double *const *d
 int hank_info(hank_ctx *ctx, int64_t out[8]) {
     if (!ctx || !out) return HANK_ERR_BAD_ARG;
     out[0] = ctx->batch.family; out[1] = ctx->wide_mode; out[2] = ctx->wide_min; out[3] = w_supported(ctx) ? 1 : 0;
-    out[4] = ctx->xjvp_max; out[5] = ctx->c.diet; out[6] = (int64_t)ctx->rec_bytes; out[7] = 0;
+    out[4] = ctx->xjvp_max; out[5] = ctx->c.diet; out[6] = (int64_t)ctx->rec_bytes; out[7] = ctx->lwg_builds;
     return HANK_OK;
 }
 

@@ -1154,7 +1154,9 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
 //   k_xfwd<0, true>  the Float64 distribution sweep: group 0 only, writes D_1..D_P, {w, ig D} and the aggregate
 //   k_xfwd<D, false> D partials per group at a recorded primal
 //   k_xfwd<D, true>  value AND D partials per group (the forward half of the Dual pass, hank_primal_jvp): every group carries
-//                    D_t itself — one more slot of the same linear step, no pow, no search — and group 0 writes the record
+//                    D_t itself — one more slot of the same linear step, no pow, no search — and group 0 writes D_t. The
+//                    per-source record {w, ig D} is NOT written here: nothing of a Dual pass reads it, and it is a pure function
+//                    of what the pass leaves behind (k_xlwg_build, before the first tangent sweep at this record)
 // A member's period in the target-stationary form of rounds 2-3 was a gather loop per target row: 2-8 sources on one row,
 // three at a time, each trip a dependent L2 round trip, every source row fetched by both of its targets, and the workgroup
 // waited for its slowest wave. Here the SOURCES are walked: 64 source rows per instruction, each source's two lottery parts
@@ -1168,10 +1170,13 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
 // The mass kept on the members' virtual rows travels as extra lanes of the unit that walks source row 0 of an open column
 // (same lottery record, the members' virtual rows as state rows): no special sums. The mass point itself needs no load at
 // all: a member's clamped rows and its virtual row are its own rows of the previous period — its own registers.
+#ifndef HANK_XPRIMAL_LWG_IN_SWEEP
+#define HANK_XPRIMAL_LWG_IN_SWEEP 1     // dev knob, 0: the Float64 sweep (k_xfwd<0, true>) leaves the per-source record to k_xlwg_build too
+#endif
 constexpr int XUCAP = 64;       // work units per member and period (k_xunits_fwd reports an overflow; the host then uses the launches)
 struct XSweepFwdArgs {
     Consts c;
-    Record R;                   // pol, lo, lw, ig (k_lottery); !VAL: lwg, Dseq of the recorded primal; VAL: group 0 writes lwg, Dseq
+    Record R;                   // pol, lo, lw, ig (k_lottery); !VAL: lwg, Dseq of the recorded primal; VAL: group 0 writes Dseq (and, D = 0, lwg)
     XSync *sy;
     double *st;                 // [2][XG][n_e*members*64][SP] the ping-pong state
     const double *D0;           // VAL: [G] initial distribution (ForwardIteration.jl:293)
@@ -1219,10 +1224,12 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     const int Sact = (na + XRW - 1) / XRW;
     if (g.S < Sact) { if (threadIdx.x == 0) xfail(A.sy, XERR_PLACEMENT, x); return; }
     if (cW >= Sact) return;
-    // every group carries the same D_t: group 0 writes D_t, the virtual rows' mass and the aggregate, group 1 (where there is one)
-    // the per-source record {w, ig D_{t-1}} — whose row 0 needs every member's virtual row, i.e. member 0 waits for everybody
-    // (spreading the three outputs of group 0 further — one each to groups 0, 2, 3 — was slower: 2.73 against 2.63 ms at N = 32)
-    const bool recD = VAL && x == 0, recL = VAL && x == 1 % A.groups;
+    // every group carries the same D_t: group 0 writes D_t, the virtual rows' mass and the aggregate. The Float64 sweep (D = 0,
+    // one group) also writes the per-source record {w, ig D_{t-1}} — whose row 0 needs every member's virtual row, i.e. member 0
+    // waits for everybody; the Dual pass (D >= 1) leaves that record to k_xlwg_build: its two own-row loads were dead in seven
+    // groups of eight, and the all-member wait of its row 0 sat in the period's latency chain
+    constexpr bool RECL = VAL && D == 0 && HANK_XPRIMAL_LWG_IN_SWEEP;
+    const bool recD = VAL && x == 0, recL = RECL && x == 1 % A.groups;       // (one group: group 0)
     for (int k = threadIdx.x; k < ne * ne; k += blockDim.x) Pish[k] = c.Pi[k];
     for (int k = threadIdx.x; k < P * ne; k += blockDim.x) closh[k] = R.clo[k];
     for (int k = threadIdx.x; k < P; k += blockDim.x) {
@@ -1268,20 +1275,21 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     double polr = 0.0, Dr = 0.0, lwr = 0.0, igr = 0.0, dpr[DD];
 #pragma unroll
     for (int k = 0; k < DD; k++) dpr[k] = 0.0;
-    // dev timing build (wrong numbers): HANK_X_TIMING_L2 confines what a period READS of the record and of the policy partials to
-    // two periods — every such load an L2 / Infinity-Cache hit: what the HBM latency of the sweep's input streams costs
+    // dev timing build (wrong numbers): -DHANK_X_TIMING_L2=<mask> confines what a period READS of an input stream to two periods —
+    // every such load an L2 / Infinity-Cache hit: what the HBM latency of that stream costs the sweep. Bits: 1 the units' lottery
+    // record, 2 the units' policy partials, 4 the own-row batch, 8 the unit descriptors (7 = every record and partial load)
 #ifdef HANK_X_TIMING_L2
-#define XTPER(t) ((t) & 1)
+#define XTPER(bit, t) ((((HANK_X_TIMING_L2) >> (bit)) & 1) ? ((t) & 1) : (t))
 #else
-#define XTPER(t) (t)
+#define XTPER(bit, t) (t)
 #endif
     auto prefetch = [&](int t_) {
-        const int t = XTPER(t_);
+        const int t = XTPER(2, t_);
         const size_t ro = (size_t)t * G + (size_t)e * na + (own ? r : 0);       // (a virtual row carries row 0's policy and partials)
         polr = R.pol[ro];
         if constexpr (D > 0) xload_row_plain<DD>(A.dpol + ((size_t)t * A.groups + x) * (size_t)G * D + ((size_t)e * na + (own ? r : 0)) * D, dpr);
-        if constexpr (VAL) { lwr = R.lw[ro]; igr = R.ig[ro]; }
-        else { if constexpr (D > 0) Dr = R.Dseq[ro + G]; }      // D_t[r] (row 0 includes what the primal kept on its virtual rows)
+        if constexpr (RECL) { lwr = R.lw[ro]; igr = R.ig[ro]; }
+        else if constexpr (!VAL && D > 0) Dr = R.Dseq[ro + G];      // D_t[r] (row 0 includes what the primal kept on its virtual rows)
     };
     // ---- the two work units of this wave, register sets 0 and 1: per lane a source's lottery record {lo, w, ig D_{t-1} | ig},
     // its policy partials and (at a recorded primal) D_t of its row; then its state row
@@ -1291,14 +1299,15 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     bool qon[2], qvl[2];
     const int2 *const ubase = A.units + (size_t)cW * XUCAP;
     auto unit_desc = [&](int t, int u) -> int2 {        // unit u of this member in period t (u wave-uniform): broadcast load -> scalar registers
-        const int2 q = ubase[(size_t)t * Sact * XUCAP + u];
+        const int2 q = ubase[(size_t)XTPER(3, t) * Sact * XUCAP + u];
         return make_int2(__builtin_amdgcn_readfirstlane(q.x), __builtin_amdgcn_readfirstlane(q.y));
     };
     // (branch-free: every lane loads — a lane beyond the unit's sources the unit's last row, an empty unit row 0 of column 0 — and
     // qon / qvl say what counts)
     auto load_rec = [&](auto U, int t_, int2 d, int i0) {
         constexpr int u = decltype(U)::value;
-        const int t = XTPER(t_);
+        const int t = XTPER(0, t_), tp = XTPER(1, t_);
+        (void)tp;
         const int ue = d.x & 15, ja = (d.x >> 4) & 0xfff, cnt = (d.x >> 16) & 0xfff, nv = (d.y >> 16) & 0xff;
         const int i = i0 + lane;
         const bool real = i < cnt;
@@ -1309,7 +1318,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         qlo[u] = R.lo[cb + j];
         if constexpr (VAL) { qw[u] = R.lw[cb + j]; if constexpr (D > 0) qg[u] = R.ig[cb + j]; }       // (ig only weights the policy partials)
         else { const double2 wg = R.lwg[cb + j]; qw[u] = wg.x; qg[u] = wg.y; if constexpr (D > 0) qdn[u] = R.Dseq[cb + G + j]; }
-        if constexpr (D > 0) xload_row_plain<DD>(A.dpol + (((size_t)t * A.groups + x) * G + (size_t)ue * na + j) * D, qdp[u]);
+        if constexpr (D > 0) xload_row_plain<DD>(A.dpol + (((size_t)tp * A.groups + x) * G + (size_t)ue * na + j) * D, qdp[u]);
     };
     auto load_state = [&](auto U, size_t hb, int2 d, int i0) {
         constexpr int u = decltype(U)::value;
@@ -1326,12 +1335,12 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     bool udv[2] = {false, false};                       // ... and whether this wave has such a unit at all
     udn[0] = udn[1] = make_int2(0, 0);
     auto request_units = [&](int t) {                   // this wave's two units of period t (branch-free: an index that exists is loaded anyway)
-        const int tc = min(t, P - 1);
-        int nu = (srcsh[tc] >> 18) & 0xff;
+        const int tc = min(t, P - 1), tu = XTPER(3, tc);
+        int nu = (srcsh[tu] >> 18) & 0xff;              // (tu == tc but in the timing build: the count belongs to the descriptors)
         nu = t < P ? nu : 0;
         udv[0] = wv < nu; udv[1] = wv + ne < nu;
-        udn[0] = ubase[(size_t)tc * Sact * XUCAP + (udv[0] ? wv : 0)];
-        udn[1] = ubase[(size_t)tc * Sact * XUCAP + (udv[1] ? wv + ne : 0)];
+        udn[0] = ubase[(size_t)tu * Sact * XUCAP + (udv[0] ? wv : 0)];
+        udn[1] = ubase[(size_t)tu * Sact * XUCAP + (udv[1] ? wv + ne : 0)];
     };
     auto take_units = [&]() {
         ud[0] = udv[0] ? make_int2(__builtin_amdgcn_readfirstlane(udn[0].x), __builtin_amdgcn_readfirstlane(udn[0].y)) : make_int2(0, 0);
@@ -1344,13 +1353,13 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     //    waves x 17 loads through one CU's vector-memory path took 2.4 us, every member's flag waited for the slowest wave's last
     //    load to be accepted, and the mixing (2 us of LDS and arithmetic that needs no memory path) sat in front of it, idle on
     //    that path. Issued here they are accepted while the waves mix, and have landed when the period's stores are drained;
-    //  * the OWN-ROW batch (policy, policy partials, lottery weights of this lane's row: their registers are in use until the
+    //  * the OWN-ROW batch (policy, policy partials, and — D = 0 — lottery weights of this lane's row: their registers are in use until the
     //    aggregate) stays behind the period's last store as a batch of exactly XFWD_NLD instructions, every one unconditional, and
     //    the drain waits with vmcnt(XFWD_NLD): everything older — the stores, and the unit batch — has completed, the own-row batch
     //    stays in flight through the publish, the next poll and the next state loads (tests/test_isa_hazards.py counts the
     //    instructions between the two markers in the ISA against the immediate).
     constexpr int DPI = D == 0 ? 0 : (D <= 2 ? 1 : D / 2);                 // load instructions per row of policy partials
-    constexpr int XFWD_NLD = 1 + DPI + (VAL ? 2 : (D > 0 ? 1 : 0));
+    constexpr int XFWD_NLD = 1 + DPI + (RECL ? 2 : ((!VAL && D > 0) ? 1 : 0));    // policy, its partials; lw and ig (the record's writer), or D_t (at a recorded primal)
     auto next_units_loads = [&](int t) {                // t: the period being processed (ud holds the NEXT period's units by now)
         const int t1 = min(t + 1, P - 1);
         load_rec(I0, t1, ud[0], 0);
@@ -1420,7 +1429,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         double v0 = 0.0;                                // the record's row 0: the mass on every member's virtual row of this column
         if (!syncw) {
             const bool need0 = recL && r0 == 0 && vnz && clo == 0;      // (wave-uniform)
-            if constexpr (VAL) {
+            if constexpr (RECL) {
                 if (need0 && lane < Sact) v0 = rows.load_one(hb + gx + ((size_t)e * Sact + lane) * 64 + 63, IV);
             }
             load_state(I0, hb, ud[0], 0);
@@ -1509,7 +1518,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #undef lds_add
 #endif
             // (rare) a unit wider than a wave — more than 64 sources on ONE target row — and units beyond the member's 2 n_e slots
+#ifdef HANK_X_TIMING_L2
+            const int nu = (srcsh[XTPER(3, t)] >> 18) & 0xff;      // (the count belongs to the descriptors)
+#else
             const int nu = (sw >> 18) & 0xff;
+#endif
             for (int u2 = wv; u2 < nu; u2 += ne) {
                 const int2 d = u2 < 2 * ne ? ud[u2 >= ne ? 1 : 0] : unit_desc(t, u2);
                 const int tot = ((d.x >> 16) & 0xfff) + ((d.y >> 16) & 0xff);
@@ -1519,7 +1532,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
                     process(I0, d);
                 }
             }
-            if constexpr (VAL) { if (need0) v0 = xwave_sum(v0); }
+            if constexpr (RECL) { if (need0) v0 = xwave_sum(v0); }
             take_units();                               // the next period's descriptors (requested a period ago; this wave's loads have all landed here)
             XSTAMP(1, son, t, 2);
             // the mass point: sources clamped at the first grid point (:54-58) go to row 0 with weight one and no weight
@@ -1556,13 +1569,16 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             double at[NAP];
 #pragma unroll
             for (int k = 0; k < NAP; k++) at[k] = 0.0;
-            if constexpr (VAL) {
+            if constexpr (RECL) {
                 if (recL && own) {
-                    // what the tangent sweeps read per SOURCE: {w, ig * D_{t-1}} (k_lottery's w and ig)
+                    // what the tangent sweeps read per SOURCE: {w, ig * D_{t-1}} (k_lottery's w and ig); k_xlwg_build repeats this
+                    // arithmetic operand by operand
                     double Dfull = mxp[IV];
                     if (r == 0 && clo == 0) Dfull += v0;
                     R.lwg[base + r] = make_double2(lwr, igr * Dfull);
                 }
+            }
+            if constexpr (VAL) {
                 if (recD) {
                     if (own) R.Dseq[(size_t)(t + 1) * G + pt] = mx[IV];
                     else if (virt) A.Dvirt[((size_t)t * ne + e) * 64 + cW] = mx[IV];
@@ -1730,14 +1746,43 @@ __global__ void k_xrho(const double *xhh, int n_hh, int P, double *rho) {
     if (t < P) rho[t] = 1.0 / (1.0 + xhh[n_hh * t]);
 }
 
-// row 0 of every column of D_1..D_P: add the virtual mass the forward sweep kept apart (member order fixed)
-__global__ void k_xfix_D(Consts c, double *Dseq, const double *Dvirt, int Sact) {
+// row 0 of every column of D_1..D_P: add the virtual mass the forward sweep kept apart (member order fixed). D0own keeps what
+// member 0 itself held on that row (k_xlwg_build's operand)
+__global__ void k_xfix_D(Consts c, double *Dseq, const double *Dvirt, int Sact, double *D0own) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= c.P * c.n_e) return;
     const int t = idx / c.n_e, e = idx - t * c.n_e;
     double s = Dseq[(size_t)(t + 1) * c.G + (size_t)e * c.n_a];
+    D0own[idx] = s;
     for (int m = 0; m < Sact; m++) s += Dvirt[(size_t)idx * 64 + m];
     Dseq[(size_t)(t + 1) * c.G + (size_t)e * c.n_a] = s;
+}
+
+// The per-source record {w, ig D_{t-1}} of every period, for the tangent sweeps at a primal that a Dual pass recorded (its forward
+// half does not write it: see k_xfwd). One block per (period, column); 24 bytes read and 16 written per point. Operand by
+// operand what the Float64 sweep's writer does (k_xfwd<0, true>), so that the record has the same bits whoever made it: a row's
+// D_{t-1} as its member stored it, and for row 0 of an open column while the virtual rows hold mass (some column was clamped the
+// period before) member 0's own part PLUS the butterfly sum of the members' virtual rows in lane order (xwave_sum) — not the
+// completed row 0 of Dseq, which k_xfix_D sums member by member.
+__global__ void __launch_bounds__(256) k_xlwg_build(Consts c, Record R, const double *__restrict__ Dvirt, const double *__restrict__ D0own, int Sact) {
+    const int col = blockIdx.x, ne = c.n_e, n = c.n_a;
+    if (col >= c.P * ne) return;
+    const int t = col / ne, e = col - t * ne, lane = threadIdx.x & 63;
+    const size_t base = (size_t)col * n;                // == t * G + e * n_a
+    bool vnz = false;
+    if (t > 0)
+        for (int k = 0; k < ne; k++) vnz = vnz || R.clo[(size_t)(t - 1) * ne + k] > 0;
+    const int clo = min(max(R.clo[col], 0), n);
+    double v0 = 0.0;
+    if (threadIdx.x < 64 && vnz && clo == 0) {          // (block-uniform but for the wave: wave 0 owns row 0)
+        if (lane < Sact) v0 = Dvirt[((size_t)(t - 1) * ne + e) * 64 + lane];
+        v0 = xwave_sum(v0);
+    }
+    for (int r = threadIdx.x; r < n; r += blockDim.x) {
+        double Dfull = (r == 0 && t > 0) ? D0own[(size_t)(t - 1) * ne + e] : R.Dseq[base + r];
+        if (r == 0 && clo == 0) Dfull += v0;
+        R.lwg[base + r] = make_double2(R.lw[base + r], R.ig[base + r] * Dfull);
+    }
 }
 
 // dagg of one pass [P][XG*D] -> columns [n0, n0+N) of the caller's (P, Ntot) column-major block
@@ -1794,10 +1839,10 @@ __device__ __forceinline__ double xreduce_parts_at(const double *__restrict__ pa
 }
 // k_xdual_epilogue: both aggregates of the value and of the pass's partials summed over the members (k_reduce_parts' order), laid
 // out as the entry points return them (k_tan_out, k_xout) — into the context's buffers AND the caller's —, and row 0 of every D_t
-// completed with the virtual rows' mass (k_xfix_D). One thread per (period, output).
+// completed with the virtual rows' mass (k_xfix_D, which also keeps member 0's own part). One thread per (period, output).
 __global__ void k_xdual_epilogue(Consts c, const double *__restrict__ aggpart, const double *__restrict__ daggpart, int Sact, int W, int n0, int N, int Ntot,
                                  double *__restrict__ agg_rm, double *__restrict__ agg_cm, double *__restrict__ dagg_pass, double *__restrict__ dagg_cm,
-                                 double *__restrict__ Dseq, const double *__restrict__ Dvirt, double *__restrict__ out_agg, double *__restrict__ out_dagg) {
+                                 double *__restrict__ Dseq, const double *__restrict__ Dvirt, double *__restrict__ D0own, double *__restrict__ out_agg, double *__restrict__ out_dagg) {
     const int P = c.P, per = 2 * W + 2 + c.n_e;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= P * per) return;
@@ -1820,6 +1865,7 @@ __global__ void k_xdual_epilogue(Consts c, const double *__restrict__ aggpart, c
         const int e = j - 2 * W - 2;
         const size_t q = (size_t)t * c.n_e + e, o = (size_t)(t + 1) * c.G + (size_t)e * c.n_a;
         double sD = Dseq[o];
+        D0own[q] = sD;
         for (int m = 0; m < Sact; m++) sD += Dvirt[q * 64 + m];
         Dseq[o] = sD;
     }

@@ -336,7 +336,7 @@ class HouseholdBlock:
         """which kernel family served the last tangent sweep and how the context chooses (include/hank_hip.h: hank_info)."""
         out = (C.c_int64 * 8)()
         self._chk(self._lib.hank_info(self._ctx, out))
-        names = ("last_tangent_family", "wide_mode", "wide_min", "wide_supported", "xjvp_max", "record_diet", "record_bytes", "reserved")
+        names = ("last_tangent_family", "wide_mode", "wide_min", "wide_supported", "xjvp_max", "record_diet", "record_bytes", "lwg_builds")
         d = {k: int(out[i]) for i, k in enumerate(names)}
         d["last_tangent_family_name"] = ("launch-per-period", "xcd-persistent", "on-chip-wide")[d["last_tangent_family"]]
         return d
