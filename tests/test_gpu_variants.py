@@ -17,21 +17,12 @@ import os
 import numpy as np
 import pytest
 
-from conftest import ROOT, ks_paths
+from vjp_cases import CASES, block as _block, economy as _economy, shape as _shape
 
 pytestmark = pytest.mark.gpu
 
 FAMILY = {"launch": "launch-per-period", "xcd": "xcd-persistent", "wide": "on-chip-wide"}
 
-# case: (gamma, HANK_RECORD_DIET or None, the record diet the context must report)
-CASES = {
-    "gamma1": (1.0, None, 1),             # pow_crra: rcp | rcp; diet on, its gamma = 1 arm
-    "gamma0.5": (0.5, None, 0),           # rcp(x^2) | rsqrt: the fast paths swap halves; diet off
-    "gamma1.5": (1.5, None, 0),           # pow | pow
-    "gamma3": (3.0, None, 0),
-    "gamma2-nodiet": (2.0, "0", 0),       # rsqrt | rcp(x^2), kc and v read from the record
-    "gamma1-nodiet": (1.0, "0", 0),
-}
 # the one-asset HANK calibration (the bond supply that clears the asset market) has no steady state at gamma = 0.5 (its Newton
 # step is singular); no other gamma takes the rcp(x^2) | rsqrt pair, so Krusell-Smith alone covers it
 MATRIX = [(fam, case) for fam in ("ks", "hank") for case in CASES if not (fam == "hank" and case == "gamma0.5")]
@@ -42,58 +33,6 @@ def _close(a, b, rel=1e-10, ab=1e-12, what=""):
     assert a.shape == b.shape, (what, a.shape, b.shape)
     err = np.max(np.abs(a - b))
     assert err <= ab + rel * np.abs(b).max(), f"{what}: max err {err:.3e} vs scale {np.abs(b).max():.3e}"
-
-
-def _block(hank, m, schedule, **env):
-    """a context of model m created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
-    env = {"HANK_SCHEDULE": schedule, **env}
-    old = {k: os.environ.get(k) for k in env}
-    for k, v in env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        return hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                                   m.value_fn.value_fn_id)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _hank_x(ss, P):
-    t = np.arange(P)
-    return np.stack([ss.vars["r"] + 0.002 * 0.8 ** t, ss.vars["om"] * (1 + 0.01 * 0.7 ** t), ss.vars["Tr"] * (1 - 0.02 * 0.9 ** t)])
-
-
-_ECON = {}
-
-
-def _economy(family, gamma):
-    """(model, steady state, household inputs (n_hh, P), oracle) of Krusell-Smith 130x3 or one-asset HANK 80x3, T = 40, at gamma:
-    a fresh model, its gamma set, its steady state solved on the host (cached per family and gamma)."""
-    key = (family, gamma)
-    if key not in _ECON:
-        import hank_amd as h
-        from oracle.oracle import Oracle
-        spec, n_a = ("krusell_smith.yaml", 130) if family == "ks" else ("one_asset_hank.yaml", 80)
-        m = h.build_model_from_yaml(str(ROOT / "examples" / spec), overrides={"T": 40, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": 3}}})
-        m.params.γ = gamma
-        if family == "hank":
-            from hank_amd import OneAssetHANK as oa
-            m.params.B = oa.calibrate_bond_supply(m)
-        ss, _ = h.get_SteadyStates(m, vfi="host")
-        assert m.params.γ == gamma
-        P = m.compspec.T - 1
-        xhh = ks_paths(m, ss, "x1", 0.05)[0][2:4] if family == "ks" else _hank_x(ss, P)
-        wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        _ECON[key] = (m, ss, np.ascontiguousarray(xhh), Oracle(wd.grid, pdm.grid, pdm.transition, gamma=gamma, beta=m.params.β,
-                                                               borrow_cons=m.params.borrow_cons))
-    return _ECON[key]
 
 
 def _oracle(orc, value, D, xhh, y):
@@ -337,33 +276,6 @@ def test_nonaffine_outputs_at_gamma_1_5(hank, family, n_het):
 
 
 # ---- 3. shape edges of the persistent and wide families ----------------------------------------------------------------------
-_SHAPE = {}
-
-
-def _shape(n_a, n_e, T):
-    """Krusell-Smith of the given shape at gamma = 2 with a cheap valid boundary: V_T the 200th host VFI iterate from ones at the
-    130x3 steady state's prices, D_0 uniform; the x1 path of those prices (cached per shape)."""
-    key = (n_a, n_e, T)
-    if key not in _SHAPE:
-        import hank_amd as h
-        from oracle.oracle import Oracle
-        m = h.build_model_from_yaml(str(ROOT / "examples" / "krusell_smith.yaml"),
-                                    overrides={"T": T, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": n_e}}})
-        assert m.params.γ == 2.0
-        _, ss0, _, _ = _economy("ks", 2.0)
-        xv = {"r": ss0.vars["r"], "w": ss0.vars["w"]}
-        V = np.ones((n_a, n_e))
-        for _ in range(200):
-            V = m.value_fn.host_steady_state_step(V, xv, m)["Value"]
-        D = np.full(n_a * n_e, 1.0 / (n_a * n_e))
-        P = T - 1
-        t = np.arange(1, P + 1)
-        xhh = np.stack([xv["r"] + 0.004 * 0.8 ** t, xv["w"] * (1.0 + 0.01 * 0.8 ** t)])
-        wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        _SHAPE[key] = (m, V, D, xhh, Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons))
-    return _SHAPE[key]
-
-
 def _forced_against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
     """each (schedule, env) of `runs`, both entry points at every N of Ns, against the oracle and a launch-schedule context."""
     m, V, D, xhh, orc = shape

@@ -5,7 +5,6 @@ restatement of the reference's ForwardIteration_pullback (ForwardIteration.jl:39
 transition_step, :164-189) and by the pairing with the policy partials; (3) at the benched size by projection on 32 oracle JVP
 columns; (4) the context's state rules; (5) the host layers. Tolerance: the suite's rel 1e-10 + abs 1e-12 on the largest entry
 of the compared array unless stated."""
-import os
 import sys
 from pathlib import Path
 
@@ -13,27 +12,11 @@ import numpy as np
 import pytest
 
 from conftest import ks_paths, ks_setup
+from vjp_cases import block as _block, forward_iteration_pullback as _forward_iteration_pullback, jt as _jt, oracle_jacobian
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-
-
-def _block(hank, m, schedule):
-    old = os.environ.get("HANK_SCHEDULE")
-    if schedule:
-        os.environ["HANK_SCHEDULE"] = schedule
-    else:
-        os.environ.pop("HANK_SCHEDULE", None)
-    try:
-        wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        return hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                                   m.value_fn.value_fn_id)
-    finally:
-        if old is None:
-            os.environ.pop("HANK_SCHEDULE", None)
-        else:
-            os.environ["HANK_SCHEDULE"] = old
 
 
 def _close(a, b, rel=1e-10, ab=1e-12):
@@ -44,22 +27,7 @@ def _close(a, b, rel=1e-10, ab=1e-12):
 
 
 def _oracle_jacobian(orc, ss, x):
-    """J (2, P, n_hh, P): d (savings, consumption aggregate)_t / d input k at period s, from unit tangents through the CPU
-    oracle's two-variable household block, 32 columns per pass."""
-    n_hh, P = x.shape
-    J = np.zeros((2, P, n_hh, P))
-    cols = [(k, s) for s in range(P) for k in range(n_hh)]
-    for c0 in range(0, len(cols), 32):
-        chunk = cols[c0:c0 + 32]
-        xd = np.zeros((n_hh, P, 33))
-        xd[..., 0] = x
-        for j, (k, s) in enumerate(chunk):
-            xd[k, s, 1 + j] = 1.0
-        st, agg, _, _ = orc.household_block_het(xd[0], xd[1], ss.value, ss.D, 32, xt=xd[2] if n_hh > 2 else None)
-        assert st == 0
-        for j, (k, s) in enumerate(chunk):
-            J[:, :, k, s] = agg[:, :, 1 + j]
-    return J
+    return oracle_jacobian(orc, ss.value, ss.D, x)
 
 
 _JCACHE = {}
@@ -101,11 +69,6 @@ def _hank_case():
     return _JCACHE["hank"]
 
 
-def _jt(J, yb):
-    """J (n_het, P, n_hh, P), yb (P, n_het, M) -> (n_hh, P, M)"""
-    return np.einsum("otks,tom->ksm", J, yb)
-
-
 # ---- 1. against the oracle's Jacobian, transposed -------------------------------------------------------------------------
 @pytest.mark.parametrize("M", [1, 5, 32, 33])
 @pytest.mark.parametrize("n_het", [1, 2])
@@ -145,28 +108,6 @@ def test_vjp_is_the_oracle_jacobian_transposed_one_asset_hank_80x3(hank, oracle_
 
 
 # ---- 2. Sweep A alone against the reference's rule ------------------------------------------------------------------------
-def _forward_iteration_pullback(grid, Pi, pol, D0, Dseq, yb):
-    """ForwardIteration_pullback (ForwardIteration.jl:394-410) with transition_pullback (:164-189) for the policy variable:
-    pol, Dseq (n_a, n_e, P), yb (P,) -> Δpolicy (n_a, n_e, P)."""
-    n_a, n_e, P = pol.shape
-    cols = np.arange(n_e)[None, :]
-    dD = np.zeros((n_a, n_e))
-    out = np.zeros((n_a, n_e, P))
-    for t in range(P - 1, -1, -1):
-        Dt, Dprev = Dseq[:, :, t], (Dseq[:, :, t - 1] if t > 0 else D0)
-        dD = dD + yb[t] * pol[:, :, t]                          # :399
-        out[:, :, t] += yb[t] * Dt                              # :400
-        u = dD @ Pi.T                                           # Λ_exog' ΔD (:166): u[r, e] = sum_e2 Pi[e, e2] ΔD[r, e2]
-        m0 = np.searchsorted(grid, pol[:, :, t], side="left")   # searchsortedfirst, 0-based (:146)
-        interior = (m0 > 0) & (m0 < n_a)
-        hi, lo = np.clip(m0, 1, n_a - 1), np.clip(m0, 1, n_a - 1) - 1
-        gap = grid[hi] - grid[lo]
-        out[:, :, t] += np.where(interior, Dprev * (u[hi, cols] - u[lo, cols]) / gap, 0.0)      # :176-182
-        w = (pol[:, :, t] - grid[lo]) / gap
-        dD = np.where(m0 == 0, u[0, cols], np.where(m0 >= n_a, u[n_a - 1, cols], (1 - w) * u[lo, cols] + w * u[hi, cols]))   # Λ_endog' u (:169)
-    return out
-
-
 @pytest.mark.parametrize("schedule", ["launch", "xcd"])
 def test_policy_cotangent_is_the_reference_pullback_and_pairs_with_the_policy_partials(hank, oracle_mod, schedule):
     m, ss, x, J = _ks_case()
@@ -199,20 +140,14 @@ def test_policy_cotangent_is_the_reference_pullback_and_pairs_with_the_policy_pa
 
 # ---- 3. full size, oracle-pinned by projection ----------------------------------------------------------------------------
 def test_full_size_2000x11_T300_M32_by_projection_on_oracle_columns(hank, oracle_mod):
-    from concurrent.futures import ThreadPoolExecutor
-    from test_gpu_fullsize import _oracle_cols
-    m, ss, orc = ks_setup(2000, 11, 300)
+    from vjp_cases import fullsize_oracle_columns
+    m, ss, xhh, y, Jy2 = fullsize_oracle_columns()              # (computed once; tests/test_gpu_vjp_variants.py reads both aggregates)
     hb = hank.household_block(m)
     hb.set_boundary(ss.value, ss.D)
-    x, _ = ks_paths(m, ss, "x1", 0.01)
     P, M = 299, 32
-    y = np.random.default_rng(0).standard_normal((2, P, 32))
-    chunks = [list(range(c0, c0 + 8)) for c0 in range(0, 32, 8)]
-    with ThreadPoolExecutor(max_workers=4) as ex:
-        outs = list(ex.map(lambda cols: _oracle_cols(orc, x[2:4], y, cols, ss), chunks))
-    Jy = np.concatenate([o[:, 1:] for o in outs], axis=1)       # (P, 32): (J y_n)_oracle
+    Jy = Jy2[0]                                                 # (P, 32): (J y_n)_oracle of the policy variable's aggregate
     yb = np.random.default_rng(1).standard_normal((P, 1, M))
-    hb.primal(x[2:4])
+    hb.primal(xhh)
     xbar = hb.vjp(yb, 1)                                        # (2, P, M)
     lhs = np.einsum("tm,tn->mn", yb[:, 0, :], Jy)
     rhs = np.einsum("ktm,ktn->mn", xbar, y)

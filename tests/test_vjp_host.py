@@ -2,7 +2,8 @@
 section 3d) are the exact transpose of the tangent recurrences of DESIGN.md section 1 — both maps stated in numpy here and
 compared on random linearisation records (two outputs, three inputs, a clamped prefix); (2) the host layers above the device
 (`LinearizedFunction.vjp`, `as_linear_operator`, `VJP`, `DeviceGroup.vjp`) with a stand-in block that multiplies by the CPU
-oracle's Jacobian of the household block at 30x3, T = 25."""
+oracle's Jacobian of the household block at 30x3, T = 25; (3) the raw-grid economies of tests/vjp_cases.py hold, on the oracle's policy, the
+data-dependent edges tests/test_gpu_vjp_variants.py runs hank_vjp through: proven present without a GPU."""
 import numpy as np
 import pytest
 
@@ -250,3 +251,19 @@ def test_device_group_shards_cotangent_columns_like_tangent_columns(stub_setup):
         assert grp.vjp(yb[:, :, :2], 1).shape == (2, stub.P, 2)                  # fewer columns than devices
     finally:
         grp.close()
+
+
+# ---- (3) the edge economies' preconditions ----------------------------------------------------------------------------------
+def test_edge_economies_hold_their_edges_on_the_oracles_policy(oracle_mod):
+    """each economy of vjp_cases.EDGE_GRIDS, on the CPU oracle's policy: a clamped prefix of 8 rows or more that is no multiple of
+    the row-block count nb = ceil(n_a / R) at any tested width (and, over the economies, on both sides of nb); 8 or more sources
+    clamped at the top; runs of rows in one bracket of length >= 5, odd and even. Prints what it measured (run with -s)."""
+    import vjp_cases as vc
+    sides = {"clo_lt_nb": False, "clo_gt_nb": False}
+    for name in vc.EDGE_GRIDS:
+        ec = vc.raw_economy(name)
+        assert np.all(np.diff(ec["grid"]) > 0)
+        got = vc.check_edges(name, ec["grid"], vc.oracle_policy(ec["orc"], ec["V"], ec["x"]))
+        sides = {k: sides[k] or got[k] for k in sides}
+    assert sides == {"clo_lt_nb": True, "clo_gt_nb": True}, sides
+    assert [vc.adj_rows_per_block(M) for M in (1, 2, 3, 4, 5, 6, 8, 9, 16, 18, 32, 33)] == [64, 64, 16, 32, 8, 16, 16, 8, 8, 8, 8, 8]
