@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <list>
 #include <mutex>
 #include <new>
@@ -56,7 +57,6 @@ struct TanWork {
     int VB = 1, VF = 1, RGB = 1, RGF = 1;   // lane widths and row groups the graphs are captured with
     unsigned nbf = 0;
 };
-
 
 // ---- XCD-local persistent sweeps (hank_xsweep.h): per-context workspace and per-batch-width tangent buffers ----
 constexpr int XD_MAX = 4;           // directions per group and pass (D = 8 spills registers: wider batches run as passes)
@@ -135,6 +135,40 @@ struct TanBatch {
     const std::vector<XPass> *passes = nullptr;           // persistent family: how dpol is laid out
 };
 
+// The timed sweeps of hank_last_timings (the first six, in its slot order) and hank_last_vjp_timings (the last two). A span is a
+// begin event, an end event, a valid flag and the launch count of the run that ended it; the run functions reach them through these
+// operations only. Recording a span's begin makes it invalid until its end is recorded. What each run function leaves behind
+// (V valid, I invalid, . untouched) — the families do NOT agree, see DESIGN.md section 2a:
+//                        PRIMAL_BACK PRIMAL_FWD TAN_BACK TAN_FWD DUAL_BACK DUAL_FWD VJP_A VJP_B
+//   run_primal                V          V         .        .        I        I       .     .
+//   x_run_primal              V          V*        I        I        I        I       .     .      (* I with skip_fwd: a Dual pass)
+//   x_run_tangent             .          .         V        V        I        I       .     .
+//   w_run_tangent             .          .         V        V        I        I       .     .
+//   run_jvp                   .          .         V        V        .        .       .     .
+//   run_fused                 I          I         I        I        V        V       .     .
+//   enqueue_vjp               .          .         .        .        .        .       V     V
+enum Span { PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD, VJP_A, VJP_B, N_SPANS };
+struct Spans {
+    struct One { hipEvent_t ev0 = nullptr, ev1 = nullptr, from = nullptr; bool valid = false; int launches = 0; } s[N_SPANS];      // from: the event the span began with (ev0, or the end of the span before it)
+    hipError_t create() { hipError_t e = hipSuccess; for (One &o : s) { if (e == hipSuccess) e = hipEventCreate(&o.ev0); if (e == hipSuccess) e = hipEventCreate(&o.ev1); } return e; }
+    void destroy() { for (One &o : s) { if (o.ev0) (void)hipEventDestroy(o.ev0); if (o.ev1) (void)hipEventDestroy(o.ev1); } }
+    hipError_t begin(Span k, hipStream_t st) { s[k].valid = false; s[k].from = s[k].ev0; return hipEventRecord(s[k].ev0, st); }
+    hipError_t end(Span k, hipStream_t st, int launches) { const hipError_t e = hipEventRecord(s[k].ev1, st); s[k].launches = launches; s[k].valid = e == hipSuccess; return e; }
+    // ONE event ends span k and begins span next
+    hipError_t end_begin(Span k, int launches, Span next, hipStream_t st) { s[next].valid = false; s[next].from = s[k].ev1; return end(k, st, launches); }
+    void invalidate(std::initializer_list<Span> ks) { for (Span k : ks) s[k].valid = false; }
+    // after a synchronisation: -1 ms for an invalid span; the launch count of the last run that ended it either way
+    hipError_t read(Span k, double *ms, int32_t *launches) const {
+        float f = -1.f;
+        const hipError_t e = s[k].valid ? hipEventElapsedTime(&f, s[k].from, s[k].ev1) : hipSuccess;
+        *ms = e == hipSuccess ? f : -1.0;
+        if (launches) *launches = s[k].launches;
+        return e;
+    }
+};
+// the slots of hank_stats, named as hip.py names them (SCHEDULE is filled from the context's schedule when it is read)
+enum Stat { SWEEP_LAUNCHES, TANGENT_WORKSPACES_ALLOCATED, GRAPHS_CAPTURED, SCHEDULE, FALLBACKS, VFI_ITERATIONS, PRIMAL_MEMO_HITS, PRIMAL_SWEEPS, N_STATS };
+
 struct hank_ctx {
     int device = 0;
     Consts c{};
@@ -156,9 +190,7 @@ struct hank_ctx {
     hipEvent_t ev_fork = nullptr, ev_side = nullptr;
     bool side_pending = false;
     hipGraphExec_t g_pback = nullptr, g_pfwd = nullptr;
-    hipEvent_t ev[16] = {};
-    bool ev_valid[6] = {false, false, false, false, false, false};
-    int launches[6] = {0, 0, 0, 0, 0, 0};
+    Spans spans;                   // the timed sweeps (hank_last_timings, hank_last_vjp_timings)
     std::list<TanWork> tws;        // per batch width, most recently used first (a small cache: Jacobian assembly and Newton alternate widths)
     // 0 = one launch per period for everything; 1 = XCD-local persistent sweeps for everything; 2 = auto (default where
     // the persistent sweeps are supported): each entry point takes the faster of the two for its shape — see sched_*
@@ -183,9 +215,8 @@ struct hank_ctx {
     CotBatch cot;                  // the current cotangent batch (hank_get_policy_cotangent_seq)
     int *d_adj_sb = nullptr;       // [P][n_e][n_a + 1] Sweep B's bracket segment starts (k_adj_seg), valid for the recorded primal or not
     bool adj_seg_valid = false;
-    bool vjp_ev_valid = false;     // ev[11..13] bracket the sweeps of the last hank_vjp
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
-    long long stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // see hank_stats
+    long long stats[N_STATS] = {};   // see Stat and hank_stats
     // primal memo of the host-pointer hank_primal_jvp (NewtonRaphson.jl:91-95 calls JVP(fullFunction, x, y) ~21 times at one x):
     // the x whose linearisation is on record, as the host handed it in
     bool memo_on = true;                              // HANK_PRIMAL_MEMO=0 (read at hank_create) switches it off
@@ -296,6 +327,17 @@ static hipError_t dmalloc(T **p, size_t count) {
     return hipMalloc((void **)p, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
 }
 
+// the copy-outs of the sweeps' results on stream s: column `col` of d_agg (P, 2), and the N columns of aggregate `col` of a family's
+// dagg_cm (P, 2 N) — both column-major; a null destination asks for nothing
+static hipError_t copy_agg(hank_ctx *ctx, double *dst, hipMemcpyKind kind, hipStream_t s, int col = 0) {
+    const size_t P = ctx->c.P;
+    return dst ? hipMemcpyAsync(dst, ctx->d_agg + P * col, sizeof(double) * P, kind, s) : hipSuccess;
+}
+static hipError_t copy_dagg(hank_ctx *ctx, double *dst, const double *dagg_cm, int N, hipMemcpyKind kind, int col = 0) {
+    const size_t PN = (size_t)ctx->c.P * N;
+    return dst ? hipMemcpyAsync(dst, dagg_cm + PN * col, sizeof(double) * PN, kind, ctx->stream) : hipSuccess;
+}
+
 static size_t primal_lds(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * RBP + (size_t)c.n_e * c.n_e + 16); }
 
 static void free_tanwork(TanWork &w) {
@@ -316,7 +358,7 @@ static int end_capture(hank_ctx *ctx, hipGraphExec_t *out) {
     HIPC(ctx, hipGraphInstantiate(out, graph, nullptr, nullptr, 0));
     HIPC(ctx, hipGraphDestroy(graph));
     HIPC(ctx, hipGetLastError());
-    ctx->stats[2]++;
+    ctx->stats[GRAPHS_CAPTURED]++;
     return HANK_OK;
 }
 
@@ -342,10 +384,7 @@ static int build_primal_graphs(hank_ctx *ctx) {
         hipLaunchKernelGGL(k_dist_step, grd, blk, lds, s, c, ctx->R, t, ctx->d_aggpart);
     hipLaunchKernelGGL(k_reduce_parts, dim3(P, 1), dim3(256), 0, s, ctx->d_aggpart, ctx->nbp, 2, ctx->d_agg_rm);
     hipLaunchKernelGGL(k_tan_out, dim3((2 * P + 255) / 256), dim3(256), 0, s, ctx->d_agg_rm, P, 2, ctx->d_agg);
-    rc = end_capture(ctx, &ctx->g_pfwd);
-    ctx->launches[0] = P + 2;
-    ctx->launches[1] = P + 1;
-    return rc;
+    return end_capture(ctx, &ctx->g_pfwd);
 }
 
 // Captures the four tangent graphs for lane type VT (double: one direction per lane; double2: two).
@@ -415,11 +454,7 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     }
     hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)nbf, 2 * N, w.dagg);
     hipLaunchKernelGGL(k_tan_out, dim3((2 * PN + 255) / 256), dim3(256), 0, s, w.dagg, (int)P, 2 * N, w.dagg_cm);
-    rc = end_capture(ctx, &w.g_fwd);
-    if (rc) return rc;
-    ctx->launches[2] = (int)P + 2;
-    ctx->launches[3] = (int)P + 3;
-    return HANK_OK;
+    return end_capture(ctx, &w.g_fwd);
     }
 
     // ---- dual-sweep graphs: the primal recurrence and the tangent recurrence advance in the SAME
@@ -460,10 +495,7 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
     hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)nbf, 2 * N, w.dagg);
     hipLaunchKernelGGL(k_tan_out, dim3((2 * PN + 255) / 256), dim3(256), 0, s, w.dagg, (int)P, 2 * N, w.dagg_cm);
-    rc = end_capture(ctx, &w.g_ffwd);
-    ctx->launches[4] = (int)P + 5;
-    ctx->launches[5] = (int)P + 5;
-    return rc;
+    return end_capture(ctx, &w.g_ffwd);
 }
 
 // The workspaces of one family for a batch of N directions, from a small most-recently-used cache (Jacobian assembly at N = 256
@@ -486,7 +518,7 @@ static int tan_cache_get(hank_ctx *ctx, std::list<W> &cache, int N, void (*relea
     cache.emplace_front();
     W &w = cache.front();
     w.N = N;
-    ctx->stats[1]++;
+    ctx->stats[TANGENT_WORKSPACES_ALLOCATED]++;
     // a failed allocation must not leave a half-built entry in the cache: a retry with this N would find it, return
     // HANK_OK and launch on null pointers
     const int rc = build(w);
@@ -599,29 +631,13 @@ static void x_section_release(int dev) {
     if (t_xdepth[dev] > 0) { t_xdepth[dev] = 0; g_xsection[dev].unlock(); }
 }
 
-// dynamic LDS of the persistent kernels (the expressions the kernels carve up): it grows with the horizon P
-static size_t x_lds_primal_back(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * 64 + (size_t)c.n_e * c.n_e + c.n_a + 4 * (size_t)c.P) + 64; }
-static size_t x_lds_tan_back(const Consts &c, int D) {
-    const int SLt = D == 4 ? 6 : D;      // XTileT<D>::SL
-    return sizeof(double) * ((size_t)SLt * c.n_e * 64 + c.P + 1 + 3 * (size_t)c.P + 1 + 3 * (size_t)c.P * D) + sizeof(int) * (size_t)c.P + 64;
-}
-// k_xdual_back<D>: tile of D + 1 slots, the grid, the household inputs and this group's input tangents of every period
-static size_t x_lds_dual_back(const Consts &c, int D) {
-    const int NSL = D + 1, SLt = NSL <= 2 ? NSL : (NSL <= 6 ? 6 : 10);
-    return sizeof(double) * ((size_t)SLt * c.n_e * 64 + c.n_a + 1 + 4 * (size_t)c.P + 3 * (size_t)c.P * D) + 64;
-}
-// k_xfwd with NSL live slots (the D partials + the value): tile, Pi, {source range, clamped prefix} and source members of every period
-static size_t x_lds_fwd(const Consts &c, int NSL) {
-    const int SLt = NSL <= 2 ? NSL : (NSL <= 6 ? 6 : 10);      // XSlots<NSL>::SL
-    const int NAP = 2 * NSL;                                   // the two aggregates' terms per lane (k_xfwd: aggsh)
-    return sizeof(double) * ((size_t)SLt * c.n_e * 64 + (size_t)c.n_e * c.n_e + 1 + (size_t)c.n_e * 64 * NAP) + sizeof(int) * ((size_t)c.P * c.n_e + c.P) + 64;
-}
 // the grid fits the XCD-local schedule: a 63-row slab per CU of an XCD, and the Float64 sweeps' LDS (which holds the
 // per-period inputs of the WHOLE horizon) fits a workgroup
+static size_t x_lds_float64(const Consts &c) { return std::max(x_lds_primal_back(c), x_lds_fwd(c, 0, true)); }
 static bool x_supported(const hank_ctx *ctx, int cus, size_t lds_max) {
     const Consts &c = ctx->c;
     const int Sact = (c.n_a + XRW - 1) / XRW;
-    return cus >= XG && Sact <= cus / XG && c.n_e <= 16 && std::max(x_lds_primal_back(c), x_lds_fwd(c, 1)) <= lds_max;
+    return cus >= XG && Sact <= cus / XG && c.n_e <= 16 && x_lds_float64(c) <= lds_max;
 }
 
 static void x_free_tan(XTan &w) {
@@ -657,7 +673,7 @@ static int x_setup(hank_ctx *ctx) {
     HIPC(ctx, dmalloc(&X.st_ds, 2 * XG * G * X.dmax));
     const size_t GM = (size_t)c.n_e * X.Sact * 64;       // member-major state of the forward sweeps: [n_e][members][64]
     HIPC(ctx, dmalloc(&X.st_D, 2 * XG * std::max(GV, GM)));
-    HIPC(ctx, dmalloc(&X.st_dD, 2 * XG * GM * (X.dmax + 2)));      // D partials + the value, padded to pairs
+    HIPC(ctx, dmalloc(&X.st_dD, 2 * XG * GM * xslots(X.dmax + 1).SP));      // D partials + the value, padded to pairs
     HIPC(ctx, dmalloc(&X.Dvirt, P * c.n_e * 64));
     HIPC(ctx, dmalloc(&X.D0own, P * c.n_e));
     HIPC(ctx, dmalloc(&X.aggpart, 2 * P * (size_t)X.Sact));       // [P][members][2]
@@ -720,33 +736,48 @@ static int x_ensure_tan(hank_ctx *ctx, int N, XTan **out) {
     return tan_cache_get(ctx, ctx->xw.tans, N, x_free_tan, [ctx](XTan &w) { return x_build_tan(ctx, w); }, out);
 }
 
-
-template <int MAXT>
-static void x_launch_tan_back(int D, dim3 grd, dim3 blk, size_t lds, hipStream_t s, const XTanBackArgs &ab) {
-    if (D == 1) hipLaunchKernelGGL((k_xtan_back<1, MAXT>), grd, blk, lds, s, ab);
-    else if (D == 2) hipLaunchKernelGGL((k_xtan_back<2, MAXT>), grd, blk, lds, s, ab);
-    else if (D == 4) { if constexpr (MAXT == 768) hipLaunchKernelGGL((k_xtan_back<4, MAXT>), grd, blk, lds, s, ab); }
+// workgroup of the persistent kernels: 64 threads per productivity state + one wave that only runs the group barrier's poll,
+// where the block has room (dev knob HANK_XSYNCWAVE=0: wave 0 polls)
+static dim3 x_block(const XWork &X, const Consts &c) {
+    const bool fits = 64 * (c.n_e + 1) <= X.maxt && X.syncwave;
+    return dim3(fits ? 64 * (c.n_e + 1) : 64 * c.n_e);
 }
 
-static void x_launch_dual_back(int D, dim3 grd, dim3 blk, size_t lds, hipStream_t s, const XDualBackArgs &ab) {
-    if (D == 1) hipLaunchKernelGGL((k_xdual_back<1, 768>), grd, blk, lds, s, ab);
-    else if (D == 2) hipLaunchKernelGGL((k_xdual_back<2, 768>), grd, blk, lds, s, ab);
-    else hipLaunchKernelGGL((k_xdual_back<4, 768>), grd, blk, lds, s, ab);
+// One launcher per persistent kernel: the whole chip (a workgroup per CU), the instance for X.maxt (and D, val), and the dynamic LDS
+// of THAT instance from the size function under the kernel. k_xdual_back and every D = 4 instance exist for 768 threads only.
+// (x_launch_vfi and x_launch_stat stand with their caller, x_fixed_point. The kernels are emitted into the code object in the order
+// these launchers name them: moving one moves its kernels, and a disassembly diff against the previous build is no longer empty.)
+template <typename F>
+static void x_by_maxt(const XWork &X, F launch) { if (X.maxt == 768) launch(std::integral_constant<int, 768>()); else launch(std::integral_constant<int, 1024>()); }
+#define XL(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(X.grid), x_block(X, c), lds, s, a)
+static bool x_has_dual_back(const XWork &X) { return X.maxt == 768; }
+static void x_launch_dual_back(const XWork &X, const Consts &c, int D, hipStream_t s, const XDualBackArgs &a) {
+    const size_t lds = x_lds_dual_back(c, D);
+    if (!x_has_dual_back(X)) return;
+    if (D == 1) XL(k_xdual_back<1, 768>);
+    else if (D == 2) XL(k_xdual_back<2, 768>);
+    else XL(k_xdual_back<4, 768>);
 }
-
 // k_xfwd<D, VAL>: D = 0 (the Float64 sweep alone, VAL), 1, 2, 4
-template <int MAXT>
-static void x_launch_fwd(int D, bool val, dim3 grd, dim3 blk, size_t lds, hipStream_t s, const XSweepFwdArgs &a) {
-#define XF(DV, VV) hipLaunchKernelGGL((k_xfwd<DV, VV, MAXT>), grd, blk, lds, s, a)
-    if (D == 0) XF(0, true);
-    else if (D == 1) { if (val) XF(1, true); else XF(1, false); }
-    else if (D == 2) { if (val) XF(2, true); else XF(2, false); }
-    else if (D == 4) { if constexpr (MAXT == 768) { if (val) XF(4, true); else XF(4, false); } }
-#undef XF
+static void x_launch_fwd(const XWork &X, const Consts &c, int D, bool val, hipStream_t s, const XSweepFwdArgs &a) {
+    const size_t lds = x_lds_fwd(c, D, val || D == 0);
+    x_by_maxt(X, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        if (D == 0) XL(k_xfwd<0, true, MT>);
+        else if (D == 1) { if (val) XL(k_xfwd<1, true, MT>); else XL(k_xfwd<1, false, MT>); }
+        else if (D == 2) { if (val) XL(k_xfwd<2, true, MT>); else XL(k_xfwd<2, false, MT>); }
+        else if (D == 4) { if constexpr (MT == 768) { if (val) XL(k_xfwd<4, true, MT>); else XL(k_xfwd<4, false, MT>); } }
+    });
 }
-static void x_launch_fwd(const XWork &X, int D, bool val, dim3 grd, dim3 blk, size_t lds, hipStream_t s, const XSweepFwdArgs &a) {
-    if (X.maxt == 768) x_launch_fwd<768>(D, val, grd, blk, lds, s, a);
-    else x_launch_fwd<1024>(D, val, grd, blk, lds, s, a);
+static void x_launch_primal_back(const XWork &X, const Consts &c, hipStream_t s, const XBackArgs &a) { const size_t lds = x_lds_primal_back(c); x_by_maxt(X, [&](auto mt) { XL(k_xprimal_back<decltype(mt)::value>); }); }
+static void x_launch_tan_back(const XWork &X, const Consts &c, int D, hipStream_t s, const XTanBackArgs &a) {
+    const size_t lds = x_lds_tan_back(c, D);
+    x_by_maxt(X, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        if (D == 1) XL(k_xtan_back<1, MT>);
+        else if (D == 2) XL(k_xtan_back<2, MT>);
+        else if (D == 4) { if constexpr (MT == 768) XL(k_xtan_back<4, MT>); }
+    });
 }
 // the forward sweeps' geometry at the recorded lottery (once per primal)
 static void x_ensure_rng(hank_ctx *ctx) {
@@ -800,11 +831,15 @@ static int x_sync_reset(hank_ctx *ctx, XSync *base, int count, int where) {     
     return HANK_OK;
 }
 
-// workgroup of the persistent kernels: 64 threads per productivity state + one wave that only runs the group barrier's poll,
-// where the block has room (dev knob HANK_XSYNCWAVE=0: wave 0 polls)
-static dim3 x_block(const XWork &X, const Consts &c) {
-    const bool fits = 64 * (c.n_e + 1) <= X.maxt && X.syncwave;
-    return dim3(fits ? 64 * (c.n_e + 1) : 64 * c.n_e);
+// behind a forward sweep that carried the value: both aggregates summed over the members, and the virtual rows' mass folded into D_t
+static void x_value_epilogue(hank_ctx *ctx) {
+    const XWork &X = ctx->xw;
+    const Consts &c = ctx->c;
+    const size_t P = c.P;
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, X.aggpart, X.Sact, 2, ctx->d_agg_rm);
+    hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
+    hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact, X.D0own);
 }
 
 // the Float64 recurrences at the context's current x (d_xhh) and boundary: two persistent launches on ONE XCD's
@@ -826,46 +861,38 @@ static int x_run_primal(hank_ctx *ctx, bool skip_fwd = false, XTan *dual = nullp
         hipLaunchKernelGGL(k_xrho, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, ctx->d_xhh, c.n_hh, (int)P, X.rho);
         if (dual) hipLaunchKernelGGL(k_tan_in, dim3((unsigned)((P * dual->N + 255) / 256)), dim3(256), 0, s, dual->dxhh, c.n_hh, (int)P, dual->N, dual->dxr, dual->dxw, dual->dxt);
     }
-    const dim3 grd(X.grid), blk = x_block(X, c), blkf = blk;
     XBackArgs ab{};
     ab.c = c; ab.ss_value = ctx->d_ss_value; ab.xhh = ctx->d_xhh; ab.rho = X.rho; ab.sy = X.sync; ab.st_s = X.st_s;
     ab.err = ctx->d_err; ab.R = ctx->R;
-    const size_t ldsb = x_lds_primal_back(c);
-    HIPC(ctx, hipEventRecord(ctx->ev[0], s));
+    HIPC(ctx, ctx->spans.begin(PRIMAL_BACK, s));
     if (dual) {
         const XPass &ps = dual->passes[0];
         XDualBackArgs db{};
         db.p = ab; db.dxr = dual->dxr; db.dxw = dual->dxw; db.dxt = dual->dxt; db.Ntot = dual->N; db.n0 = ps.n0; db.N = ps.N;
         db.st_ds = X.st_ds; db.dpol = dual->dpol + ps.dpol_off; db.groups = ps.groups;
-        x_launch_dual_back(ps.D, grd, blk, x_lds_dual_back(c, ps.D), s, db);
-    } else if (X.maxt == 768) hipLaunchKernelGGL((k_xprimal_back<768>), grd, blk, ldsb, s, ab);
-    else hipLaunchKernelGGL((k_xprimal_back<1024>), grd, blk, ldsb, s, ab);
-    HIPC(ctx, hipEventRecord(ctx->ev[1], s));
+        x_launch_dual_back(X, c, ps.D, s, db);
+    } else x_launch_primal_back(X, c, s, ab);
+    HIPC(ctx, ctx->spans.end(PRIMAL_BACK, s, 1));
     // (the Dual pass's forward half reads the lottery through its work units: the per-target segment records are built when somebody asks)
     hipLaunchKernelGGL(k_lottery, dim3((unsigned)(P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, (int)P * c.n_e, ctx->d_err, dual ? 0 : 1, 1);
     record_rewritten(ctx, !dual, !skip_fwd && HANK_XPRIMAL_LWG_IN_SWEEP);     // (skip_fwd: the Dual pass's forward half follows, and it writes no per-source records)
     x_ensure_rng(ctx);
-    HIPC(ctx, hipEventRecord(ctx->ev[6], s));
+    HIPC(ctx, ctx->spans.begin(PRIMAL_FWD, s));
     if (!skip_fwd) {
         XSweepFwdArgs fa{};
         fa.c = c; fa.R = ctx->R; fa.sy = X.sync + 1; fa.st = X.st_D; fa.D0 = ctx->d_ss_D; fa.groups = 1; fa.Dvirt = X.Dvirt; fa.aggpart = X.aggpart;
         fa.src = X.srcF; fa.units = X.unitsF; fa.overflow = X.unit_overflow; fa.all_members = X.neigh ? 0 : 1;
-        x_launch_fwd(X, 0, true, grd, blkf, x_lds_fwd(c, 1), s, fa);
+        x_launch_fwd(X, c, 0, true, s, fa);
     }
-    HIPC(ctx, hipEventRecord(ctx->ev[2], s));
-    if (!skip_fwd) {
-        hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, X.aggpart, X.Sact, 2, ctx->d_agg_rm);
-            hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
-        hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact, X.D0own);
-    }
+    HIPC(ctx, ctx->spans.end(PRIMAL_FWD, s, 1));
+    if (!skip_fwd) x_value_epilogue(ctx);
     HIPC(ctx, hipGetLastError());
     rc = x_serialize_end(ctx);
     if (rc) return rc;
-    ctx->stats[0] += skip_fwd ? 1 : 2;
+    ctx->stats[SWEEP_LAUNCHES] += skip_fwd ? 1 : 2;
     X.last_passes = 1;
-    ctx->launches[0] = ctx->launches[1] = 1;
-    ctx->ev_valid[0] = true; ctx->ev_valid[1] = !skip_fwd;
-    ctx->ev_valid[2] = ctx->ev_valid[3] = ctx->ev_valid[4] = ctx->ev_valid[5] = false;
+    ctx->spans.invalidate({TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD});
+    if (skip_fwd) ctx->spans.invalidate({PRIMAL_FWD});      // (its two events bracket nothing)
     return HANK_OK;
 }
 
@@ -894,24 +921,20 @@ static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_bac
     }
     x_ensure_rng(ctx);
     const bool neigh = X.neigh;
-    const dim3 grd(X.grid);
-    const dim3 blk = x_block(X, c), blkF = blk;
     XTanBackArgs ab{};
     ab.c = c; ab.R = ctx->R; ab.rho = X.rho; ab.xhh = ctx->d_xhh; ab.dxr = w->dxr; ab.dxw = w->dxw; ab.dxt = w->dxt; ab.Ntot = N; ab.st_ds = X.st_ds;
     ab.src = neigh ? X.srcB : nullptr;
     ab.stall = X.fault == 3 ? 1 : 0;
     XSweepFwdArgs fa{};
     fa.c = c; fa.R = ctx->R; fa.st = X.st_dD; fa.daggpart = w->daggpart; fa.src = X.srcF; fa.units = X.unitsF; fa.overflow = X.unit_overflow; fa.all_members = neigh ? 0 : 1;
-    HIPC(ctx, hipEventRecord(ctx->ev[3], s));
+    HIPC(ctx, ctx->spans.begin(TAN_BACK, s));
     for (int p = 0; p < np && !skip_back; p++) {
         const XPass &ps = w->passes[p];
         ab.n0 = ps.n0; ab.N = ps.N; ab.groups = ps.groups; ab.sy = X.sync + 2 + 2 * p; ab.dpol = w->dpol + ps.dpol_off;
-        const size_t lds = x_lds_tan_back(c, ps.D);
-        if (X.maxt == 768) x_launch_tan_back<768>(ps.D, grd, blk, lds, s, ab);
-        else x_launch_tan_back<1024>(ps.D, grd, blk, lds, s, ab);
+        x_launch_tan_back(X, c, ps.D, s, ab);
     }
-    HIPC(ctx, hipEventRecord(ctx->ev[4], s));
-    HIPC(ctx, hipEventRecord(ctx->ev[7], s));
+    HIPC(ctx, ctx->spans.end(TAN_BACK, s, np));
+    HIPC(ctx, ctx->spans.begin(TAN_FWD, s));
     const int nb = X.Sact;                  // (one row of partials per member: the sync wave sums a member's columns)
     for (int p = 0; p < np; p++) {
         const XPass &ps = w->passes[p];
@@ -919,22 +942,18 @@ static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_bac
         const bool v = val && p == 0;
         if (v) { fa.D0 = ctx->d_ss_D; fa.Dvirt = X.Dvirt; fa.aggpart = X.aggpart; }
         else { rc = ensure_lwg(ctx); if (rc) return rc; }      // (behind k_xfix_D where the first pass carried the value)
-        x_launch_fwd(X, ps.D, v, grd, blkF, x_lds_fwd(c, ps.D + (v ? 1 : 0)), s, fa);
+        x_launch_fwd(X, c, ps.D, v, s, fa);
         const int W = XG * ps.D;
         if (v && np == 1 && xo) {               // the one-pass Dual pass: everything behind the sweep in ONE launch (k_xdual_epilogue)
-            HIPC(ctx, hipEventRecord(ctx->ev[5], s));
+            HIPC(ctx, ctx->spans.end(TAN_FWD, s, np));
             const int per = 2 * W + 2 + c.n_e;
             hipLaunchKernelGGL(k_xdual_epilogue, dim3((unsigned)((P * per + 255) / 256)), dim3(256), 0, s, c, X.aggpart, w->daggpart, X.Sact, W, ps.n0, ps.N, N,
                                ctx->d_agg_rm, ctx->d_agg, w->dagg_pass, w->dagg_cm, ctx->R.Dseq, X.Dvirt, X.D0own, xo->agg, xo->dagg);
             xo->done = true;
             break;
         }
-        if (v) {
-            hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, X.aggpart, X.Sact, 2, ctx->d_agg_rm);
-            hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
-            hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact, X.D0own);
-        }
-        if (p == np - 1) HIPC(ctx, hipEventRecord(ctx->ev[5], s));
+        if (v) x_value_epilogue(ctx);
+        if (p == np - 1) HIPC(ctx, ctx->spans.end(TAN_FWD, s, np));
         hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * W + 63) / 64), dim3(256), 0, s, w->daggpart, nb, 2 * W, w->dagg_pass);
         hipLaunchKernelGGL(k_xout, dim3((unsigned)((P * ps.N + 255) / 256)), dim3(256), 0, s, w->dagg_pass, (int)P, 2 * W, 0, ps.n0, ps.N, w->dagg_cm);
         hipLaunchKernelGGL(k_xout, dim3((unsigned)((P * ps.N + 255) / 256)), dim3(256), 0, s, w->dagg_pass, (int)P, 2 * W, W, ps.n0, ps.N, w->dagg_cm + P * (size_t)N);
@@ -942,11 +961,9 @@ static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_bac
     HIPC(ctx, hipGetLastError());
     rc = x_serialize_end(ctx);
     if (rc) return rc;
-    ctx->stats[0] += skip_back ? np : 2 * np;
+    ctx->stats[SWEEP_LAUNCHES] += skip_back ? np : 2 * np;
     X.last_passes = 1 + np;
-    ctx->launches[2] = ctx->launches[3] = np;
-    ctx->ev_valid[2] = ctx->ev_valid[3] = true;
-    ctx->ev_valid[4] = ctx->ev_valid[5] = false;
+    ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
     batch_ran(ctx, 1, w, N, w->dagg_cm, w->dpol, &w->passes);
     return HANK_OK;
 }
@@ -1074,25 +1091,23 @@ static int w_run_tangent(hank_ctx *ctx, WTan *w, const double *d_dxhh) {
         hipLaunchKernelGGL(k_wide_prep, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, s, R.ib, R.A, R.B, npt, ctx->d_ibw);
         ctx->wprep_valid = true;
     }
-    HIPC(ctx, hipEventRecord(ctx->ev[3], s));
+    HIPC(ctx, ctx->spans.begin(TAN_BACK, s));
     rc = w_launch(ctx, false, w->N, a);
     if (rc) return rc;
-    HIPC(ctx, hipEventRecord(ctx->ev[4], s));
+    HIPC(ctx, ctx->spans.end(TAN_BACK, s, 1));
     HIPC(ctx, join_side(ctx));              // the forward sweep reads D_t and the {w, ig D} record of the primal's forward sweep
     rc = ensure_lwg(ctx);
     if (rc) return rc;
-    HIPC(ctx, hipEventRecord(ctx->ev[7], s));
+    HIPC(ctx, ctx->spans.begin(TAN_FWD, s));
     rc = w_launch(ctx, true, w->N, a);
     if (rc) return rc;
-    HIPC(ctx, hipEventRecord(ctx->ev[5], s));
+    HIPC(ctx, ctx->spans.end(TAN_FWD, s, 1));
     HIPC(ctx, hipGetLastError());
     rc = x_serialize_end(ctx);
     if (rc) return rc;
-    ctx->launches[2] = ctx->launches[3] = 1;
-    ctx->ev_valid[2] = ctx->ev_valid[3] = true;
-    ctx->ev_valid[4] = ctx->ev_valid[5] = false;
+    ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
     batch_ran(ctx, 2, w, w->N, w->dagg_cm, w->dpol);
-    ctx->stats[0] += 2;
+    ctx->stats[SWEEP_LAUNCHES] += 2;
     return HANK_OK;
 }
 static int w_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, double *d_dagg_out) {
@@ -1100,11 +1115,10 @@ static int w_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, d
     const bool staging = kind != hipMemcpyDeviceToDevice;
     int rc = w_ensure_tan(ctx, N, staging, &w);
     if (rc) return rc;
-    const size_t P = ctx->c.P;
-    if (staging) HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
+    if (staging) HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * ctx->c.P * N, kind, ctx->stream));
     rc = w_run_tangent(ctx, w, staging ? w->dxhh : dxhh);
     if (rc) return rc;
-    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
     return HANK_OK;
 }
 
@@ -1185,7 +1199,7 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     HIPC(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
     HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     HIPC(ctx, hipEventCreate(&ctx->ev_side));
-    for (int k = 0; k < 16; k++) HIPC(ctx, hipEventCreate(&ctx->ev[k]));
+    HIPC(ctx, ctx->spans.create());
     HIPC(ctx, dmalloc(&ctx->d_a, c.n_a));
     HIPC(ctx, dmalloc(&ctx->d_z, c.n_e));
     HIPC(ctx, dmalloc(&ctx->d_Pi, (size_t)c.n_e * c.n_e));
@@ -1235,7 +1249,7 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     if (se && strcmp(se, "xcd") == 0) {
         if (ctx->schedule == 0)
             return fail(ctx, HANK_ERR_BAD_ARG, "HANK_SCHEDULE=xcd: n_a=%d needs %d workgroups per XCD (the device has %d) and %zu bytes of LDS per workgroup (it has %zu)", c.n_a,
-                        (c.n_a + XRW - 1) / XRW, prop.multiProcessorCount / XG, std::max(x_lds_primal_back(c), x_lds_fwd(c, 1)), (size_t)prop.sharedMemPerBlock);
+                        (c.n_a + XRW - 1) / XRW, prop.multiProcessorCount / XG, x_lds_float64(c), (size_t)prop.sharedMemPerBlock);
         ctx->schedule = 1;
         ctx->forced_xcd = true;
     }
@@ -1284,8 +1298,7 @@ int hank_destroy(hank_ctx *ctx) {
     (void)hipFree(ctx->rec_slab); (void)hipFree(ctx->d_ibw); (void)hipFree(ctx->hx_slab);
     (void)hipFree(ctx->d_a); (void)hipFree(ctx->d_z); (void)hipFree(ctx->d_Pi); (void)hipFree(ctx->d_ss_value);
     (void)hipFree(ctx->d_xhh); (void)hipFree(ctx->d_agg); (void)hipFree(ctx->d_agg_rm); (void)hipFree(ctx->d_zd); (void)hipFree(ctx->d_aggpart); (void)hipFree(ctx->d_err);
-    for (int k = 0; k < 16; k++)
-        if (ctx->ev[k]) (void)hipEventDestroy(ctx->ev[k]);
+    ctx->spans.destroy();
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return HANK_OK;
@@ -1365,22 +1378,20 @@ static void note_primal_x(hank_ctx *ctx, const double *xhh) {
 
 static int run_primal(hank_ctx *ctx, double *d_agg_out) {
     HIPC(ctx, join_side(ctx));     // a previous forward sweep still reads the record this one overwrites
-    HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    HIPC(ctx, ctx->spans.begin(PRIMAL_BACK, ctx->stream));
     HIPC(ctx, hipGraphLaunch(ctx->g_pback, ctx->stream));
-    HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    HIPC(ctx, ctx->spans.end(PRIMAL_BACK, ctx->stream, ctx->c.P + 2));
     // fork: the distribution sweep goes to the side stream; the main stream is free for the tangent
     // backward sweep and joins (join_side) before anything that needs D_t or the aggregates
     HIPC(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     HIPC(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-    HIPC(ctx, hipEventRecord(ctx->ev[6], ctx->side_stream));
+    HIPC(ctx, ctx->spans.begin(PRIMAL_FWD, ctx->side_stream));
     HIPC(ctx, hipGraphLaunch(ctx->g_pfwd, ctx->side_stream));
-    HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->side_stream));
-    if (d_agg_out)
-        HIPC(ctx, hipMemcpyAsync(d_agg_out, ctx->d_agg, sizeof(double) * ctx->c.P, hipMemcpyDeviceToDevice, ctx->side_stream));
+    HIPC(ctx, ctx->spans.end(PRIMAL_FWD, ctx->side_stream, ctx->c.P + 1));
+    HIPC(ctx, copy_agg(ctx, d_agg_out, hipMemcpyDeviceToDevice, ctx->side_stream));
     HIPC(ctx, hipEventRecord(ctx->ev_side, ctx->side_stream));
     ctx->side_pending = true;
-    ctx->ev_valid[0] = ctx->ev_valid[1] = true;
-    ctx->ev_valid[4] = ctx->ev_valid[5] = false;
+    ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
     record_rewritten(ctx, true, true);
     return HANK_OK;
 }
@@ -1392,7 +1403,7 @@ static int x_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double
     HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * ctx->c.P, kind, ctx->stream));
     rc = x_run_primal(ctx);
     if (rc) return rc;
-    if (d_agg_out) HIPC(ctx, hipMemcpyAsync(d_agg_out, ctx->d_agg, sizeof(double) * ctx->c.P, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPC(ctx, copy_agg(ctx, d_agg_out, hipMemcpyDeviceToDevice, ctx->stream));
     return HANK_OK;
 }
 // value and N partials; xhh == nullptr keeps the recorded primal (hank_jvp): the partials are linear recurrences at
@@ -1429,8 +1440,8 @@ static int x_dual(hank_ctx *ctx, const double *xhh, const double *dxhh, hipMemcp
     rc = x_run_tangent(ctx, w, xhh != nullptr, fused_back, &xo);
     if (rc) return rc;
     if (!xo.done) {
-        if (d_agg_out) HIPC(ctx, hipMemcpyAsync(d_agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-        if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPC(ctx, copy_agg(ctx, d_agg_out, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
     }
     return HANK_OK;
 }
@@ -1441,7 +1452,7 @@ static bool x_tan_fits(const hank_ctx *ctx, int N) {
     const XWork &X = ctx->xw;
     int D = 1;
     while (XG * D < N && D < X.dmax) D *= 2;
-    return std::max(x_lds_tan_back(ctx->c, D), x_lds_fwd(ctx->c, D + 1)) <= (size_t)X.lds_max;
+    return std::max(x_lds_tan_back(ctx->c, D), x_lds_fwd(ctx->c, D, true)) <= (size_t)X.lds_max;
 }
 static bool use_x_jvp(const hank_ctx *ctx, int N) { return (ctx->schedule == 1 || (ctx->schedule == 2 && N <= ctx->xjvp_max)) && x_tan_fits(ctx, N); }
 // hank_primal_jvp on the persistent sweeps. Forced schedule: always. auto: a batch of ONE pass (N <= 8 groups x 4) runs value and
@@ -1449,7 +1460,7 @@ static bool use_x_jvp(const hank_ctx *ctx, int N) { return (ctx->schedule == 1 |
 // T=300, N=32; 3.3 against 4.2 at N=1); wider batches would be two backward sweeps at the same record: the launches keep them
 static bool x_dual_back_fits(const hank_ctx *ctx, int D) {
     const XWork &X = ctx->xw;
-    return ctx->xdual_back && X.maxt == 768 && 64 * (ctx->c.n_e + 1) <= X.maxt && x_lds_dual_back(ctx->c, D) <= (size_t)X.lds_max;
+    return ctx->xdual_back && x_has_dual_back(X) && 64 * (ctx->c.n_e + 1) <= X.maxt && x_lds_dual_back(ctx->c, D) <= (size_t)X.lds_max;
 }
 static bool use_x_fused(const hank_ctx *ctx, int N) {
     if (ctx->schedule < 1 || !x_tan_fits(ctx, N)) return false;
@@ -1465,7 +1476,7 @@ static int to_launch_schedule(hank_ctx *ctx) {
         if (rc != HANK_OK) return rc;       // the schedule is left as it was: the next call reports the sweep's failure again, not a null graph
     }
     ctx->schedule = 0;
-    ctx->stats[4]++;
+    ctx->stats[FALLBACKS]++;
     return HANK_OK;
 }
 static bool x_fallback_allowed(const hank_ctx *ctx) { return !ctx->forced_xcd; }      // a schedule forced at hank_create fails loudly instead
@@ -1483,6 +1494,23 @@ static int settle(hank_ctx *ctx, bool *rerun) {
     return rc;
 }
 
+static int check_rates(hank_ctx *ctx, const double *xhh) {      // the host-pointer entries see x before the device does
+    for (int t = 0; t < ctx->c.P; t++)
+        if (!(1.0 + xhh[ctx->c.n_hh * t] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive (period %zu)", (size_t)t + 1);
+    return HANK_OK;
+}
+}  // extern "C" (a template)
+// a host-pointer entry: enqueue, settle, and when the context has moved to the launches enqueue again and take their verdict
+template <typename Enqueue>
+static int run_settled(hank_ctx *ctx, Enqueue enqueue) {
+    bool rerun = false;
+    int rc = enqueue();
+    if (!rc) rc = settle(ctx, &rerun);
+    if (rerun) rc = enqueue();
+    return rerun && !rc ? fetch_device_error(ctx) : rc;
+}
+extern "C" {
+
 // hank_primal[_dev]: x from the caller (kind: where it lives) and the Float64 sweeps of the context's schedule
 static int enqueue_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double *d_agg_out) {
     if (use_x_primal(ctx)) return x_primal(ctx, xhh, kind, d_agg_out);
@@ -1495,7 +1523,7 @@ int hank_primal_dev(hank_ctx *ctx, const double *d_xhh, double *d_agg_out) {
     if (!ctx || !d_xhh) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
     note_primal_x(ctx, nullptr);
-    ctx->stats[7]++;
+    ctx->stats[PRIMAL_SWEEPS]++;
     return enqueue_primal(ctx, d_xhh, hipMemcpyDeviceToDevice, d_agg_out);
 }
 
@@ -1520,26 +1548,16 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
     ENTER(ctx);
     if (!ctx || !xhh) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
-    const size_t P = ctx->c.P;
-    for (size_t t = 0; t < P; t++)
-        if (!(1.0 + xhh[ctx->c.n_hh * t] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive (period %zu)", t + 1);
+    { const int rrc = check_rates(ctx, xhh); if (rrc) return rrc; }
     note_primal_x(ctx, nullptr);
-    int rc = enqueue_primal(ctx, xhh, hipMemcpyHostToDevice, nullptr);
-    if (rc) return rc;
-    bool rerun = false;
-    rc = settle(ctx, &rerun);
-    if (rerun) {
-        rc = enqueue_primal(ctx, xhh, hipMemcpyHostToDevice, nullptr);
-        if (rc) return rc;
-        rc = fetch_device_error(ctx);
-    }
+    const int rc = run_settled(ctx, [&] { return enqueue_primal(ctx, xhh, hipMemcpyHostToDevice, nullptr); });
     if (rc) return rc;
     if (agg_out) {
-        HIPC(ctx, hipMemcpyAsync(agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(ctx, copy_agg(ctx, agg_out, hipMemcpyDeviceToHost, ctx->stream));
         HIPC(ctx, hipStreamSynchronize(ctx->stream));
     }
     note_primal_x(ctx, xhh);
-    ctx->stats[7]++;
+    ctx->stats[PRIMAL_SWEEPS]++;
     ctx->errmsg[0] = 0;
     return HANK_OK;
 }
@@ -1547,17 +1565,15 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
 static int run_jvp(hank_ctx *ctx, TanWork &w) {
     int grc = ensure_graphs(ctx, w, 0);
     if (grc) return grc;
-    ctx->launches[2] = ctx->c.P + 2; ctx->launches[3] = ctx->c.P + 3;
-    HIPC(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    HIPC(ctx, ctx->spans.begin(TAN_BACK, ctx->stream));
     HIPC(ctx, hipGraphLaunch(w.g_back, ctx->stream));
-    HIPC(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, ctx->c.P + 2));
     HIPC(ctx, join_side(ctx));      // the tangent forward sweep needs D_t
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
-    HIPC(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    HIPC(ctx, ctx->spans.begin(TAN_FWD, ctx->stream));
     HIPC(ctx, hipGraphLaunch(w.g_fwd, ctx->stream));
-    HIPC(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid[2] = ctx->ev_valid[3] = true;
+    HIPC(ctx, ctx->spans.end(TAN_FWD, ctx->stream, ctx->c.P + 3));
     batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
     return HANK_OK;
 }
@@ -1574,7 +1590,7 @@ static int enqueue_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, in
     HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
     rc = run_jvp(ctx, *w);
     if (rc) return rc;
-    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
     return HANK_OK;
 }
 
@@ -1589,7 +1605,6 @@ int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
     ENTER(ctx);
     if (!ctx || !dxhh || !dagg_out || N < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument (N=%d)", N);
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp");
-    const size_t P = ctx->c.P;
     int rc = enqueue_jvp(ctx, dxhh, hipMemcpyHostToDevice, N, nullptr);
     if (rc) return rc;
     // the launches' tangent sweeps raise no device error; the on-chip wide sweeps do, but have no cross-workgroup waits:
@@ -1607,7 +1622,7 @@ int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
         }
     }
     if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(dagg_out, ctx->batch.dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, copy_dagg(ctx, dagg_out, ctx->batch.dagg_cm, N, hipMemcpyDeviceToHost));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     ctx->errmsg[0] = 0;
     return HANK_OK;
@@ -1616,15 +1631,13 @@ int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
 static int run_fused(hank_ctx *ctx, TanWork &w) {
     int grc = ensure_graphs(ctx, w, 1);
     if (grc) return grc;
-    ctx->launches[4] = ctx->launches[5] = ctx->c.P + 5;
     HIPC(ctx, join_side(ctx));
-    HIPC(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
+    HIPC(ctx, ctx->spans.begin(DUAL_BACK, ctx->stream));
     HIPC(ctx, hipGraphLaunch(w.g_fback, ctx->stream));
-    HIPC(ctx, hipEventRecord(ctx->ev[9], ctx->stream));
+    HIPC(ctx, ctx->spans.end_begin(DUAL_BACK, ctx->c.P + 5, DUAL_FWD, ctx->stream));
     HIPC(ctx, hipGraphLaunch(w.g_ffwd, ctx->stream));
-    HIPC(ctx, hipEventRecord(ctx->ev[10], ctx->stream));
-    ctx->ev_valid[4] = ctx->ev_valid[5] = true;
-    ctx->ev_valid[0] = ctx->ev_valid[1] = ctx->ev_valid[2] = ctx->ev_valid[3] = false;
+    HIPC(ctx, ctx->spans.end(DUAL_FWD, ctx->stream, ctx->c.P + 5));
+    ctx->spans.invalidate({PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD});
     record_rewritten(ctx, true, true);
     batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
     return HANK_OK;
@@ -1643,8 +1656,8 @@ static int enqueue_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dx
     HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
     rc = run_fused(ctx, *w);
     if (rc) return rc;
-    if (d_agg_out) HIPC(ctx, hipMemcpyAsync(d_agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToDevice, ctx->stream));
-    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPC(ctx, copy_agg(ctx, d_agg_out, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
     return HANK_OK;
 }
 
@@ -1658,7 +1671,7 @@ int hank_primal_jvp_dev(hank_ctx *ctx, const double *d_xhh, const double *d_dxhh
         return rc ? rc : hank_jvp_dev(ctx, d_dxhh, N, d_dagg_out);
     }
     note_primal_x(ctx, nullptr);      // (this entry never skips work: bench.py times it)
-    ctx->stats[7]++;
+    ctx->stats[PRIMAL_SWEEPS]++;
     return enqueue_primal_jvp(ctx, d_xhh, d_dxhh, hipMemcpyDeviceToDevice, N, d_agg_out, d_dagg_out);
 }
 
@@ -1667,20 +1680,19 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
     if (!ctx || !xhh || !dxhh || !dagg_out || N < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument (N=%d)", N);
     if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
     const size_t P = ctx->c.P;
-    for (size_t t = 0; t < P; t++)
-        if (!(1.0 + xhh[ctx->c.n_hh * t] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive (period %zu)", t + 1);
-    int rc = HANK_OK;
+    int rc = check_rates(ctx, xhh);
+    if (rc) return rc;
     // The reference calls JVP(fullFunction, x, y) about 21 times per Newton step at ONE x (NewtonRaphson.jl:91-95) and its Dual
     // pass recomputes the primal every time (GeneralStructures.jl:546-547). The linearisation of the x on record is still
     // valid when the same x comes in again: only the tangent sweeps run (what hank_jvp does), the value is the recorded one.
     if (ctx->memo_on && ctx->primal_done && ctx->memo_valid && ctx->memo_xhh.size() == (size_t)ctx->c.n_hh * P &&
         memcmp(ctx->memo_xhh.data(), xhh, sizeof(double) * ctx->c.n_hh * P) == 0) {
-        ctx->stats[6]++;
+        ctx->stats[PRIMAL_MEMO_HITS]++;
         rc = hank_jvp(ctx, dxhh, N, dagg_out);
         if (rc) return rc;
         if (agg_out) {
             HIPC(ctx, join_side(ctx));
-            HIPC(ctx, hipMemcpyAsync(agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
+            HIPC(ctx, copy_agg(ctx, agg_out, hipMemcpyDeviceToHost, ctx->stream));
             HIPC(ctx, hipStreamSynchronize(ctx->stream));
         }
         return HANK_OK;
@@ -1690,21 +1702,14 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
         return rc ? rc : hank_jvp(ctx, dxhh, N, dagg_out);
     }
     note_primal_x(ctx, nullptr);
-    rc = enqueue_primal_jvp(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr);
-    if (rc) return rc;
-    bool rerun = false;
-    rc = settle(ctx, &rerun);
-    if (rerun) {
-        rc = enqueue_primal_jvp(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr);
-        if (rc) return rc;
-        rc = fetch_device_error(ctx);
-    }
-    if (rc) { batch_none(ctx); return rc; }      // (the partials of a primal that failed are nobody's)
-    if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, ctx->d_agg, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipMemcpyAsync(dagg_out, ctx->batch.dagg_cm, sizeof(double) * P * N, hipMemcpyDeviceToHost, ctx->stream));
+    bool enqueued = false;
+    rc = run_settled(ctx, [&] { const int e = enqueue_primal_jvp(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr); enqueued = e == HANK_OK; return e; });
+    if (rc) { if (enqueued) batch_none(ctx); return rc; }      // (the device's verdict: the partials of a primal that failed are nobody's)
+    HIPC(ctx, copy_agg(ctx, agg_out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, copy_dagg(ctx, dagg_out, ctx->batch.dagg_cm, N, hipMemcpyDeviceToHost));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     note_primal_x(ctx, xhh);
-    ctx->stats[7]++;
+    ctx->stats[PRIMAL_SWEEPS]++;
     ctx->errmsg[0] = 0;
     return HANK_OK;
 }
@@ -1859,8 +1864,7 @@ int hank_debug_stamps(hank_ctx *ctx, unsigned long long *out) {
 
 int hank_stats(hank_ctx *ctx, int64_t out[8]) {
     if (!ctx || !out) return HANK_ERR_BAD_ARG;
-    ctx->stats[3] = ctx->schedule;
-    for (int k = 0; k < 8; k++) out[k] = ctx->stats[k];
+    for (int k = 0; k < N_STATS; k++) out[k] = k == SCHEDULE ? ctx->schedule : ctx->stats[k];
     return HANK_OK;
 }
 
@@ -1902,21 +1906,12 @@ int hank_info(hank_ctx *ctx, int64_t out[8]) {
     return HANK_OK;
 }
 
-int hank_last_timings(hank_ctx *ctx, double out_ms[6], int32_t launches[6]) {
+int hank_last_timings(hank_ctx *ctx, double *out_ms, int32_t *launches) {      // (six slots each: PRIMAL_BACK .. DUAL_FWD)
     if (!ctx || !out_ms) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
     HIPC(ctx, join_side(ctx));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    int a[6] = {0, 6, 3, 7, 8, 9}, b[6] = {1, 2, 4, 5, 9, 10};
-    for (int k = 0; k < 6; k++) {
-        out_ms[k] = -1.0;
-        if (ctx->ev_valid[k]) {
-            float ms = 0.f;
-            HIPC(ctx, hipEventElapsedTime(&ms, ctx->ev[a[k]], ctx->ev[b[k]]));
-            out_ms[k] = ms;
-        }
-        if (launches) launches[k] = ctx->launches[k];
-    }
+    for (int k = PRIMAL_BACK; k <= DUAL_FWD; k++) HIPC(ctx, ctx->spans.read((Span)k, &out_ms[k], launches ? &launches[k] : nullptr));
     return HANK_OK;
 }
 
@@ -1946,18 +1941,17 @@ int hank_get_dist_seq(hank_ctx *ctx, double *out) {
 static int grid_aggregates(hank_ctx *ctx, double *agg2_out, int32_t N, double *dagg2_out, bool dev) {
     if (!ctx || (!agg2_out && !dagg2_out) || N < 0) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
-    const size_t P = ctx->c.P;
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (agg2_out) {
         if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
         HIPC(ctx, join_side(ctx));
-        HIPC(ctx, hipMemcpyAsync(agg2_out, ctx->d_agg + P, sizeof(double) * P, kind, ctx->stream));
+        HIPC(ctx, copy_agg(ctx, agg2_out, kind, ctx->stream, 1));
     }
     if (dagg2_out && N > 0) {
         const TanBatch *b = nullptr;
         const int rc = batch_current(ctx, N, &b);
         if (rc) return rc;
-        HIPC(ctx, hipMemcpyAsync(dagg2_out, b->dagg_cm + P * (size_t)N, sizeof(double) * P * N, kind, ctx->stream));
+        HIPC(ctx, copy_dagg(ctx, dagg2_out, b->dagg_cm, N, kind, 1));
     }
     if (!dev) HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return HANK_OK;
@@ -2079,12 +2073,11 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     rc = ensure_adj_seg(ctx);
     if (rc) return rc;
     hipLaunchKernelGGL(k_adj_in, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->yb0, w->yb1);
-    HIPC(ctx, hipEventRecord(ctx->ev[11], s));
+    HIPC(ctx, ctx->spans.begin(VJP_A, s));
     HIPC(ctx, hipGraphLaunch(w->g_A, s));
-    HIPC(ctx, hipEventRecord(ctx->ev[12], s));
+    HIPC(ctx, ctx->spans.end_begin(VJP_A, (int)P, VJP_B, s));
     HIPC(ctx, hipGraphLaunch(w->g_B, s));
-    HIPC(ctx, hipEventRecord(ctx->ev[13], s));
-    ctx->vjp_ev_valid = true;
+    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1));
     cot_ran(ctx, w, M, w->pbar);
     if (d_xhh_bar) HIPC(ctx, hipMemcpyAsync(d_xhh_bar, w->xbar, sizeof(double) * c.n_hh * P * M, hipMemcpyDeviceToDevice, s));
     *out = w;
@@ -2140,19 +2133,11 @@ int hank_get_policy_cotangent_seq(hank_ctx *ctx, int32_t M, double *out) {
     return HANK_OK;
 }
 
-int hank_last_vjp_timings(hank_ctx *ctx, double out_ms[2], int32_t launches[2]) {
+int hank_last_vjp_timings(hank_ctx *ctx, double *out_ms, int32_t *launches) {      // (two slots each: VJP_A, VJP_B)
     if (!ctx || !out_ms) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2; k++) {
-        out_ms[k] = -1.0;
-        if (ctx->vjp_ev_valid) {
-            float ms = 0.f;
-            HIPC(ctx, hipEventElapsedTime(&ms, ctx->ev[11 + k], ctx->ev[12 + k]));
-            out_ms[k] = ms;
-        }
-        if (launches) launches[k] = ctx->c.P + k;
-    }
+    for (int k = 0; k < 2; k++) HIPC(ctx, ctx->spans.read((Span)(VJP_A + k), &out_ms[k], launches ? &launches[k] : nullptr));
     return HANK_OK;
 }
 }  // extern "C"
@@ -2383,6 +2368,59 @@ static int take_device_error(hank_ctx *ctx, int e[4]) {
     return HANK_OK;
 }
 
+// the device's verdict on steps of the value iteration / of the power method (step: the caller's count of the step that raised it)
+static int vfi_device_error(hank_ctx *ctx, int step) {
+    int e[4];
+    const int rc = take_device_error(ctx, e);
+    if (rc) return rc;
+    if (e[0] == ERR_KNOTS)
+        return fail(ctx, HANK_ERR_KNOTS, "knot-vectors must be unique and sorted in increasing order (steady-state value iteration, step %d, "
+                    "productivity state %d, wealth index %d)", step, e[2] + 1, e[3] + 1);
+    if (e[0] == ERR_DOMAIN)
+        return fail(ctx, HANK_ERR_DOMAIN, "DomainError: negative base under a non-integer power (steady-state value iteration, step %d)", step);
+    return HANK_OK;
+}
+static int stat_device_error(hank_ctx *ctx) {
+    int e[4];
+    const int rc = take_device_error(ctx, e);
+    if (rc) return rc;
+    if (e[0] == ERR_NONMONO) return fail(ctx, HANK_ERR_NONMONOTONE, "savings policy is not monotone in wealth (productivity state %d, wealth index %d)", e[2] + 1, e[3] + 1);
+    return HANK_OK;
+}
+
+static void x_launch_vfi(const XWork &X, const Consts &c, hipStream_t s, const XVfiArgs &a) { const size_t lds = x_lds_vfi(c); x_by_maxt(X, [&](auto mt) { XL(k_xvfi<decltype(mt)::value>); }); }
+static void x_launch_stat(const XWork &X, const Consts &c, hipStream_t s, const XStatArgs &a) { const size_t lds = x_lds_stat(c); x_by_maxt(X, [&](auto mt) { XL(k_xstat<decltype(mt)::value>); }); }
+#undef XL
+// A steady-state fixed point as ONE persistent launch on the group of XCD 0 (`launch` enqueues it on sync block 0), through to the
+// fallback decision. HANK_OK with *ran: the group formed and xs holds the kernel's {steps, converged} (d_state); HANK_OK without: it
+// did not (or a wait timed out), the context has moved to the launches and d_state is zeroed for them. A forced schedule fails loudly.
+template <typename Launch>
+static int x_fixed_point(hank_ctx *ctx, const char *what, int *d_state, int xs[2], bool *ran, Launch launch) {
+    hipStream_t s = ctx->stream;
+    int rc = x_setup(ctx);
+    XWork &X = ctx->xw;
+    if (!rc) rc = x_serialize_begin(ctx);
+    if (!rc) rc = x_sync_reset(ctx, X.sync, 1, 4);
+    if (rc) return rc;
+    launch(X);
+    HIPC(ctx, hipGetLastError());
+    rc = x_serialize_end(ctx);
+    if (rc) return rc;
+    XSync hsy;
+    HIPC(ctx, hipMemcpyAsync(xs, d_state, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipMemcpyAsync(&hsy, X.sync, sizeof(XSync), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));
+    X.last_passes = 0;       // (this sync block has been checked here)
+    *ran = hsy.status[0] == 0;
+    if (*ran) return HANK_OK;
+    if (!x_fallback_allowed(ctx))
+        return fail(ctx, HANK_ERR_SWEEP, "persistent %s: %s on XCD %u", what, hsy.status[0] == XERR_PLACEMENT ? "the group is short of members" : "a wait timed out", hsy.status[1]);
+    rc = to_launch_schedule(ctx);
+    if (rc) return rc;
+    HIPC(ctx, hipMemsetAsync(d_state, 0, 2 * sizeof(int), s));
+    return HANK_OK;
+}
+
 // ---- steady state: the inner fixed point of get_xVals on the device (SteadyState.jl:132-141) ------------------
 extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t max_iter, double *value_io, double *policy_out,
                         int32_t *iters_out, double *supnorm_out) {
@@ -2408,57 +2446,35 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
     const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
     const double r = xhh_t[0], w = xhh_t[1], tr = c.n_hh > 2 ? xhh_t[2] : 0.0;
     int hstate[2] = {0, 0};
+    auto finish = [&](const double *Vfin, int iters) -> int {
+        double hn = 0.0;
+        HIPC(ctx, hipMemcpyAsync(value_io, Vfin, sizeof(double) * G, hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipMemcpyAsync(policy_out, pol, sizeof(double) * G, hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipMemcpyAsync(&hn, norm, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipStreamSynchronize(s));
+        if (iters_out) *iters_out = iters;
+        if (supnorm_out) *supnorm_out = hn;
+        ctx->stats[VFI_ITERATIONS] += iters;
+        ctx->errmsg[0] = 0;
+        return HANK_OK;
+    };
     const char *xve = getenv("HANK_XVFI");            // dev knob: 0 = per-step launches
     if (use_x_primal(ctx) && !(xve && atoi(xve) == 0)) {
         // the whole iteration as ONE persistent launch on the group of XCD 0 (k_xvfi): the vote on convergence rides on the group barrier
-        int rc = x_setup(ctx);
-        if (rc) return rc;
-        XWork &X = ctx->xw;
-        rc = x_serialize_begin(ctx);
-        if (rc) return rc;
-        { const int rc_ = x_sync_reset(ctx, X.sync, 1, 4); if (rc_) return rc_; }
-        XVfiArgs va{};
-        va.c = c; va.V0 = V[0]; va.r = r; va.w = w; va.tr = tr; va.tol = tol; va.max_iter = max_iter; va.sy = X.sync; va.st_s = X.st_s;
-        va.err = ctx->d_err; va.Vout = V[1]; va.pol = pol; va.iters = state; va.supnorm = norm;
-        const dim3 xblk = x_block(X, c);
-        const size_t lds = sizeof(double) * ((size_t)c.n_e * 64 + (size_t)c.n_e * c.n_e + c.n_a + 16) + 64;
-        if (X.maxt == 768) hipLaunchKernelGGL((k_xvfi<768>), dim3(X.grid), xblk, lds, s, va);
-        else hipLaunchKernelGGL((k_xvfi<1024>), dim3(X.grid), xblk, lds, s, va);
-        HIPC(ctx, hipGetLastError());
-        rc = x_serialize_end(ctx);
-        if (rc) return rc;
         int xs[2] = {0, 0};      // {steps, converged}
-        XSync hsy;
-        HIPC(ctx, hipMemcpyAsync(xs, state, sizeof(xs), hipMemcpyDeviceToHost, s));
-        HIPC(ctx, hipMemcpyAsync(&hsy, X.sync, sizeof(XSync), hipMemcpyDeviceToHost, s));
-        HIPC(ctx, hipStreamSynchronize(s));
-        X.last_passes = 0;       // (this sync block has been checked here)
-        if (hsy.status[0] == 0) {
-            int e[4];
-            { const int erc = take_device_error(ctx, e); if (erc) return erc; }
-            if (e[0] == ERR_KNOTS)
-                return fail(ctx, HANK_ERR_KNOTS, "knot-vectors must be unique and sorted in increasing order (steady-state value iteration, step %d, "
-                            "productivity state %d, wealth index %d)", xs[0], e[2] + 1, e[3] + 1);
-            if (e[0] == ERR_DOMAIN)
-                return fail(ctx, HANK_ERR_DOMAIN, "DomainError: negative base under a non-integer power (steady-state value iteration, step %d)", xs[0]);
-            double hn = 0.0;
-            HIPC(ctx, hipMemcpyAsync(value_io, V[1], sizeof(double) * G, hipMemcpyDeviceToHost, s));
-            HIPC(ctx, hipMemcpyAsync(policy_out, pol, sizeof(double) * G, hipMemcpyDeviceToHost, s));
-            HIPC(ctx, hipMemcpyAsync(&hn, norm, sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPC(ctx, hipStreamSynchronize(s));
-            if (iters_out) *iters_out = xs[0];
-            if (supnorm_out) *supnorm_out = hn;
-            ctx->stats[5] += xs[0];
-            ctx->errmsg[0] = 0;
-            return HANK_OK;
-        }
-        // the group did not form or a wait timed out: this context continues on the launches (a forced schedule fails loudly)
-        if (!x_fallback_allowed(ctx))
-            return fail(ctx, HANK_ERR_SWEEP, "persistent value iteration: %s on XCD %u", hsy.status[0] == XERR_PLACEMENT ? "the group is short of members" : "a wait timed out", hsy.status[1]);
-        rc = to_launch_schedule(ctx);
+        bool ran = false;
+        int rc = x_fixed_point(ctx, "value iteration", state, xs, &ran, [&](const XWork &X) {
+            XVfiArgs va{};
+            va.c = c; va.V0 = V[0]; va.r = r; va.w = w; va.tr = tr; va.tol = tol; va.max_iter = max_iter; va.sy = X.sync; va.st_s = X.st_s;
+            va.err = ctx->d_err; va.Vout = V[1]; va.pol = pol; va.iters = state; va.supnorm = norm;
+            x_launch_vfi(X, c, s, va);
+        });
         if (rc) return rc;
-        HIPC(ctx, hipMemsetAsync(state, 0, 2 * sizeof(int), s));
-        hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);
+        if (ran) {
+            rc = vfi_device_error(ctx, xs[0]);
+            return rc ? rc : finish(V[1], xs[0]);
+        }
+        hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);      // the context continues on the launches
     }
     int done = 0;                      // steps enqueued
     const int chunk = 64;              // the stop flag travels to the host once per chunk; converged steps freeze the state
@@ -2474,25 +2490,9 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
         HIPC(ctx, hipGetLastError());
         HIPC(ctx, hipMemcpyAsync(hstate, state, sizeof(hstate), hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));
-        int e[4];
-        { const int erc = take_device_error(ctx, e); if (erc) return erc; }
-        if (e[0] == ERR_KNOTS)
-            return fail(ctx, HANK_ERR_KNOTS, "knot-vectors must be unique and sorted in increasing order (steady-state value iteration, step %d, "
-                        "productivity state %d, wealth index %d)", hstate[1] + 1, e[2] + 1, e[3] + 1);
-        if (e[0] == ERR_DOMAIN)
-            return fail(ctx, HANK_ERR_DOMAIN, "DomainError: negative base under a non-integer power (steady-state value iteration, step %d)", hstate[1] + 1);
+        { const int erc = vfi_device_error(ctx, hstate[1] + 1); if (erc) return erc; }
     }
-    const int fin = hstate[1] & 1;     // step k reads V[(k-1)&1] and writes V[k&1]
-    double hn = 0.0;
-    HIPC(ctx, hipMemcpyAsync(value_io, V[fin], sizeof(double) * G, hipMemcpyDeviceToHost, s));
-    HIPC(ctx, hipMemcpyAsync(policy_out, pol, sizeof(double) * G, hipMemcpyDeviceToHost, s));
-    HIPC(ctx, hipMemcpyAsync(&hn, norm, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPC(ctx, hipStreamSynchronize(s));
-    if (iters_out) *iters_out = hstate[1];
-    if (supnorm_out) *supnorm_out = hn;
-    ctx->stats[5] += hstate[1];
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
+    return finish(V[hstate[1] & 1], hstate[1]);     // step k reads V[(k-1)&1] and writes V[k&1]
 }
 
 // ---- steady state: the stationary distribution by the power method on the device --------------------------------
@@ -2530,43 +2530,24 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
     const char *xse = getenv("HANK_XSTAT");           // dev knob: 0 = one launch per iteration
     if (use_x_primal(ctx) && !(xse && atoi(xse) == 0)) {
         // the whole power method as ONE persistent launch on the group of XCD 0 (k_xstat)
-        int rc = x_setup(ctx);
-        if (rc) return rc;
-        XWork &X = ctx->xw;
-        rc = x_serialize_begin(ctx);
-        if (rc) return rc;
-        { const int rc_ = x_sync_reset(ctx, X.sync, 1, 4); if (rc_) return rc_; }
-        XStatArgs sa{};
-        sa.c = c; sa.R = R; sa.D0 = D[0]; sa.tol = tol; sa.max_iter = max_iter; sa.check_every = check_every; sa.sy = X.sync;
-        sa.st_D = X.st_D; sa.Dout = D[1]; sa.iters = state;
-        const dim3 xblk = x_block(X, c);
-        const size_t lds = sizeof(double) * ((size_t)c.n_e * 64 + 16) + 64;
-        if (X.maxt == 768) hipLaunchKernelGGL((k_xstat<768>), dim3(X.grid), xblk, lds, s, sa);
-        else hipLaunchKernelGGL((k_xstat<1024>), dim3(X.grid), xblk, lds, s, sa);
-        HIPC(ctx, hipGetLastError());
-        rc = x_serialize_end(ctx);
-        if (rc) return rc;
         int xs[2] = {0, 0};
-        XSync hsy;
-        HIPC(ctx, hipMemcpyAsync(xs, state, sizeof(xs), hipMemcpyDeviceToHost, s));
-        HIPC(ctx, hipMemcpyAsync(&hsy, X.sync, sizeof(XSync), hipMemcpyDeviceToHost, s));
-        HIPC(ctx, hipStreamSynchronize(s));
-        X.last_passes = 0;
-        if (hsy.status[0] == 0) {
-            int e[4];
-            { const int erc = take_device_error(ctx, e); if (erc) return erc; }
-            if (e[0] == ERR_NONMONO) return fail(ctx, HANK_ERR_NONMONOTONE, "savings policy is not monotone in wealth (productivity state %d, wealth index %d)", e[2] + 1, e[3] + 1);
+        bool ran = false;
+        int rc = x_fixed_point(ctx, "power method", state, xs, &ran, [&](const XWork &X) {
+            XStatArgs sa{};
+            sa.c = c; sa.R = R; sa.D0 = D[0]; sa.tol = tol; sa.max_iter = max_iter; sa.check_every = check_every; sa.sy = X.sync;
+            sa.st_D = X.st_D; sa.Dout = D[1]; sa.iters = state;
+            x_launch_stat(X, c, s, sa);
+        });
+        if (rc) return rc;
+        if (ran) {
+            rc = stat_device_error(ctx);
+            if (rc) return rc;
             HIPC(ctx, hipMemcpyAsync(D_io, D[1], sizeof(double) * G, hipMemcpyDeviceToHost, s));
             HIPC(ctx, hipStreamSynchronize(s));
             if (iters_out) *iters_out = xs[0];
             ctx->errmsg[0] = 0;
             return HANK_OK;
         }
-        if (!x_fallback_allowed(ctx))
-            return fail(ctx, HANK_ERR_SWEEP, "persistent power method: %s on XCD %u", hsy.status[0] == XERR_PLACEMENT ? "the group is short of members" : "a wait timed out", hsy.status[1]);
-        rc = to_launch_schedule(ctx);
-        if (rc) return rc;
-        HIPC(ctx, hipMemsetAsync(state, 0, 2 * sizeof(int), s));
     }
     while (!hstate[0] && done < max_iter) {
         // a chunk = several checks; every check compares the iterate with the one check_every steps earlier
@@ -2581,9 +2562,7 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         HIPC(ctx, hipMemcpyAsync(hstate, state, sizeof(hstate), hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));
     }
-    int e[4];
-    { const int erc = take_device_error(ctx, e); if (erc) return erc; }
-    if (e[0] == ERR_NONMONO) return fail(ctx, HANK_ERR_NONMONOTONE, "savings policy is not monotone in wealth (productivity state %d, wealth index %d)", e[2] + 1, e[3] + 1);
+    { const int erc = stat_device_error(ctx); if (erc) return erc; }
     // once converged the iteration kernels stop touching the buffers: Dchk holds the last checked iterate
     HIPC(ctx, hipMemcpyAsync(D_io, Dchk, sizeof(double) * G, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));

@@ -64,6 +64,7 @@ struct XSync {                    // zeroed by a memset node before EVERY launch
     unsigned status[32];          // [0]: XERR_* (sticky), [1]: the XCD that raised it, [2]: microseconds the wait that timed out had lasted
     unsigned pad[32];
 };
+constexpr size_t XCTL_BYTES = 64;      // ctl[] at the end of every persistent kernel's LDS carve: the group placement and a vote's outcome
 
 typedef unsigned int xv4u __attribute__((ext_vector_type(4)));
 
@@ -407,7 +408,7 @@ struct XBackArgs {
 
 template <int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xprimal_back(XBackArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double xl[];
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_primal_back (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
     double *Vsh = xl;                                   // [ne][64]
@@ -483,6 +484,8 @@ __global__ void __launch_bounds__(MAXT) k_xprimal_back(XBackArgs A) {
         }
     }
 }
+// dynamic LDS of k_xprimal_back: the carve at its top (Vsh, Pish, ash, xsh, ctl) — it grows with the horizon P
+static inline size_t x_lds_primal_back(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * 64 + (size_t)c.n_e * c.n_e + c.n_a + 4 * (size_t)c.P) + XCTL_BYTES; }
 
 // ---- the steady state's inner fixed point as ONE launch (hank_vfi; SteadyState.jl:132-141) ----------------------------
 // value <- value_fn(value, xVals).Value until max|value' - value| < tol, on the group of XCD 0 exactly like k_xprimal_back
@@ -506,7 +509,7 @@ struct XVfiArgs {
 
 template <int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double xl[];
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_vfi (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const int ne = c.n_e, na = c.n_a, G = c.G;
     double *Vsh = xl;                                   // [ne][64]
@@ -616,6 +619,8 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
     if (own) { A.Vout[pt] = V; A.pol[pt] = pol; }
     if (cW == 0 && threadIdx.x == 0) { A.iters[0] = steps; A.iters[1] = conv; *A.supnorm = gmax; }
 }
+// dynamic LDS of k_xvfi: the carve at its top (Vsh, Pish, ash, redsh, ctl)
+static inline size_t x_lds_vfi(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * 64 + (size_t)c.n_e * c.n_e + c.n_a + 16) + XCTL_BYTES; }
 
 // ================================ tangent-only sweeps at a recorded primal ===================================
 // The dual sweeps above cost what the Float64 recurrence costs — and every group repeats it (bracket search, two
@@ -626,6 +631,7 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
 // slots of the tangent tile: D, padded where a lane stride of 8*D bytes would bank-conflict the 16-byte reads (D = 4: 32 B
 // -> lanes i and i+8 collide, 31 % of the LDS cycles in profiles/r02a; 48 B is conflict-free)
 template <int D> struct XTileT { static constexpr int SL = D == 4 ? 6 : (D == 8 ? 10 : D); };
+static inline int xtile_sl(int D) { return D == 1 ? XTileT<1>::SL : (D == 2 ? XTileT<2>::SL : XTileT<4>::SL); }      // the trait at a run-time D in {1, 2, 4} (the host's size functions)
 
 // ---- the stationary distribution as ONE launch (hank_stationary_dist) ------------------------------------------------
 // D <- Lambda(policy) D on the group of XCD 0 exactly like k_xprimal_fwd with ONE period's lottery record (k_lottery on the
@@ -647,7 +653,7 @@ struct XStatArgs {
 
 template <int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xstat(XStatArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double xl[];
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_stat (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const Record &R = A.R;
     const int ne = c.n_e, na = c.n_a, G = c.G;
@@ -791,6 +797,8 @@ __global__ void __launch_bounds__(MAXT) k_xstat(XStatArgs A) {
     }
     if (cW == 0 && threadIdx.x == 0) { A.iters[0] = it; A.iters[1] = conv; }
 }
+// dynamic LDS of k_xstat: the carve at its top (tile, redsh, ctl)
+static inline size_t x_lds_stat(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * 64 + 16) + XCTL_BYTES; }
 
 struct XTanBackArgs {
     Consts c;
@@ -810,7 +818,7 @@ struct XTanBackArgs {
 template <int D, int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xtan_back(XTanBackArgs A) {
     constexpr int SL = XTileT<D>::SL;
-    extern __shared__ __attribute__((aligned(16))) double xl[];
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_tan_back (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const Record &R = A.R;
     const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
@@ -956,12 +964,17 @@ __global__ void __launch_bounds__(MAXT) k_xtan_back(XTanBackArgs A) {
         }
     }
 }
+// dynamic LDS of k_xtan_back<D>: the carve at its top (tile, rhosh and pxsh padded to pairs, dxsh, srcsh, ctl) — the group's input tangents of every period
+static inline size_t x_lds_tan_back(const Consts &c, int D) { return sizeof(double) * ((size_t)xtile_sl(D) * c.n_e * 64 + c.P + 1 + 3 * (size_t)c.P + 1 + 3 * (size_t)c.P * D) + sizeof(int) * (size_t)c.P + XCTL_BYTES; }
 
 // slots of a sweep that carries NSL numbers per grid point (the D partials and, in a Dual pass, the value)
 template <int NSL> struct XSlots {
     static constexpr int SP = NSL == 1 ? 1 : ((NSL + 1) / 2) * 2;        // slots of a state row (planes of 16-byte pairs)
     static constexpr int SL = NSL <= 2 ? NSL : (NSL <= 6 ? 6 : 10);      // slots of a tile entry (see XTileT)
 };
+struct XSlotsRt { int SP, SL; };                                          // the traits at a run-time NSL in {1, ..., 5} (the host's size functions and buffers)
+template <int NSL> constexpr XSlotsRt xslots_of() { return {XSlots<NSL>::SP, XSlots<NSL>::SL}; }
+static inline XSlotsRt xslots(int NSL) { return NSL == 1 ? xslots_of<1>() : NSL == 2 ? xslots_of<2>() : NSL == 3 ? xslots_of<3>() : NSL == 4 ? xslots_of<4>() : xslots_of<5>(); }
 
 // ---- the backward half of a Dual pass (hank_primal_jvp) as ONE launch: value AND D partials in every group -----------
 // Every group repeats the Float64 EGM step (bit for bit the same in all of them: same expressions, same order) and carries
@@ -983,7 +996,7 @@ struct XDualBackArgs {
 template <int D, int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     constexpr int NSL = D + 1, SL = XSlots<NSL>::SL, IV = D;
-    extern __shared__ __attribute__((aligned(16))) double xl[];
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_dual_back (under this kernel) is the host's sum of the same pieces
     const XBackArgs &A = B.p;
     const Consts &c = A.c;
     const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
@@ -1148,6 +1161,8 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     }
     XSTAMP1(0, son, 11);
 }
+// dynamic LDS of k_xdual_back<D>: the carve at its top (tile of D + 1 live slots, ash padded to a pair, xsh, dxsh, ctl)
+static inline size_t x_lds_dual_back(const Consts &c, int D) { return sizeof(double) * ((size_t)xslots(D + 1).SL * c.n_e * 64 + c.n_a + 1 + 4 * (size_t)c.P + 3 * (size_t)c.P * D) + XCTL_BYTES; }
 
 // ================================ forward sweeps, source-stationary (round 4) ========================================
 // ONE kernel for the three forward recurrences (ForwardIteration.jl:297-308 and its partials):
@@ -1199,7 +1214,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     constexpr int IV = D;                               // the value's slot
     constexpr int DD = D > 0 ? D : 1;
     constexpr bool PIREG = NSL < 4;                     // the mixing's coefficients in registers
-    extern __shared__ __attribute__((aligned(16))) double xl[];
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_fwd (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const Record &R = A.R;
     const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
@@ -1616,6 +1631,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         XSTAMP(1, son, t, 6);
     }
     if (sync_duty) reduce_agg(P - 1);                   // (every wave wrote its terms before the last barrier)
+}
+// dynamic LDS of k_xfwd<D, VAL>: the carve at its top (tile, Pish padded to a pair, aggsh, closh, srcsh, ctl), with the kernel's own NSL and NAP
+static inline size_t x_lds_fwd(const Consts &c, int D, bool val) {
+    const int NSL = D + (val ? 1 : 0), NAP = 2 * NSL;
+    return sizeof(double) * ((size_t)xslots(NSL).SL * c.n_e * 64 + (size_t)c.n_e * c.n_e + 1 + (size_t)c.n_e * 64 * NAP) + sizeof(int) * ((size_t)c.P * c.n_e + c.P) + XCTL_BYTES;
 }
 
 // the forward sweeps' work units from the lottery record (see k_xfwd), one block per (period, member): thread e cuts column
