@@ -23,6 +23,38 @@
 
 using namespace hank;
 
+// Who owns device memory and graph handles: ONE move-only owner type. An Owner holds a handle or nothing, releases it in its
+// destructor and before it takes another, and converts to the handle where one is read (kernel arguments, copies, launches).
+// DevBuf<T> is the owner of one device allocation, GraphExec the owner of one instantiated graph; every other pointer to device
+// memory in this file is a view into one of them.
+struct FreeDevice { void operator()(void *p) const { (void)hipFree(p); } };
+struct FreeGraphExec { void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); } };
+template <typename H, typename Release>
+struct Owner {
+    Owner() = default;
+    Owner(const Owner &) = delete;
+    Owner &operator=(const Owner &) = delete;
+    Owner(Owner &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Owner &operator=(Owner &&o) noexcept { if (this != &o) { reset(o.h); o.h = nullptr; } return *this; }
+    ~Owner() { reset(); }
+    void reset(H next = nullptr) { if (h) Release()(h); h = next; }
+    H get() const { return h; }
+    operator H() const { return h; }
+protected:
+    H h = nullptr;
+};
+using GraphExec = Owner<hipGraphExec_t, FreeGraphExec>;
+template <typename T>
+struct DevBuf : Owner<T *, FreeDevice> {
+    // count elements (8 bytes for none: every buffer has an address); what the buffer held before is released first
+    hipError_t alloc(size_t count) {
+        this->reset();
+        return hipMalloc((void **)&this->h, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
+    }
+};
+// a slab is carved into 256-byte aligned pieces: the offset of the next piece of `bytes`
+static size_t carve(size_t &off, size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+
 // Lane geometry of the tangent kernels, chosen per batch width N (measured, MI355X, 2000x11, T=300):
 //  - lane width: an even batch runs TWO adjacent directions per lane (double2): every state / dpol access is
 //    16 bytes, half the vector-memory instructions per byte (N=32: 4650 -> 5380 JVPs/s; N=256: 8130 -> 10940);
@@ -43,17 +75,17 @@ static inline int tan_lane_width(int N, int forward) {
 struct TanWork {
     int N = 0;
     TanGeom g{}, gf{};   // lane geometry of the backward / forward tangent kernels
-    double *dxhh = nullptr;   // (2,P,N) staging for the host-pointer entry
-    double *dxr = nullptr, *dxw = nullptr, *dxt = nullptr;   // [P][N] tangents of r, w (, lump-sum transfer)
-    double *ds[2] = {nullptr, nullptr};
-    double *dD[2] = {nullptr, nullptr};
-    double *dpol = nullptr;
-    double *aggpart = nullptr;
-    double *dagg = nullptr;     // [P][N]
-    double *dagg_cm = nullptr;  // (P,N) column-major
+    DevBuf<double> dxhh;      // (2,P,N) staging for the host-pointer entry
+    DevBuf<double> dxr, dxw, dxt;   // [P][N] tangents of r, w (, lump-sum transfer)
+    DevBuf<double> ds[2];
+    DevBuf<double> dD[2];
+    DevBuf<double> dpol;
+    DevBuf<double> aggpart;
+    DevBuf<double> dagg;      // [P][N]
+    DevBuf<double> dagg_cm;   // (P,N) column-major
     int nbx = 0, nbxf = 0;
-    hipGraphExec_t g_back = nullptr, g_fwd = nullptr;
-    hipGraphExec_t g_fback = nullptr, g_ffwd = nullptr;   // dual-sweep graphs (primal + tangents in one chain)
+    GraphExec g_back, g_fwd;
+    GraphExec g_fback, g_ffwd;   // dual-sweep graphs (primal + tangents in one chain)
     int VB = 1, VF = 1, RGB = 1, RGF = 1;   // lane widths and row groups the graphs are captured with
     unsigned nbf = 0;
 };
@@ -65,22 +97,22 @@ struct XPass { int n0, N, D, groups; size_t dpol_off; };
 struct XTan {                       // one per batch width N (kept in a small LRU: Jacobian assembly and Newton alternate widths)
     int N = 0;
     std::vector<XPass> passes;
-    double *dxhh = nullptr, *dxr = nullptr, *dxw = nullptr, *dxt = nullptr;   // staging + [P][N] input tangents
-    double *dpol = nullptr;         // per pass [P][groups][G][D]
-    double *daggpart = nullptr;     // [P][Sact*n_e][XG*XD_MAX] (reused by every pass)
-    double *dagg_pass = nullptr;    // [P][XG*XD_MAX]
-    double *dagg_cm = nullptr;      // (P, N) column-major
+    DevBuf<double> dxhh, dxr, dxw, dxt;   // staging + [P][N] input tangents
+    DevBuf<double> dpol;            // per pass [P][groups][G][D]
+    DevBuf<double> daggpart;        // [P][Sact*n_e][XG*XD_MAX] (reused by every pass)
+    DevBuf<double> dagg_pass;       // [P][XG*XD_MAX]
+    DevBuf<double> dagg_cm;         // (P, N) column-major
 };
 struct XWork {
     bool ready = false;
     int grid = 0, Sact = 0, maxt = 768, dmax = XD_MAX;
-    XSync *sync = nullptr;          // [2 * XPASS_MAX]: backward and forward sweep of every pass
-    double *st_s = nullptr, *st_ds = nullptr, *st_D = nullptr, *st_dD = nullptr;
-    double *Dvirt = nullptr, *aggpart = nullptr, *rho = nullptr;
-    double *D0own = nullptr;        // [P][n_e] row 0 of every D_t as member 0 held it, before the virtual rows' mass was added (k_xlwg_build)
-    int *srcB = nullptr, *srcF = nullptr;     // [P][Sact] source-member ranges of the tangent sweeps at the recorded primal
-    int2 *unitsF = nullptr;                   // [P][Sact][XUCAP] the forward sweeps' work units (k_xunits_fwd)
-    int *unit_overflow = nullptr;             // set by k_xunits_fwd when a member has more units than XUCAP
+    DevBuf<XSync> sync;             // [2 * XPASS_MAX]: backward and forward sweep of every pass
+    DevBuf<double> st_s, st_ds, st_D, st_dD;
+    DevBuf<double> Dvirt, aggpart, rho;
+    DevBuf<double> D0own;           // [P][n_e] row 0 of every D_t as member 0 held it, before the virtual rows' mass was added (k_xlwg_build)
+    DevBuf<int> srcB, srcF;                   // [P][Sact] source-member ranges of the tangent sweeps at the recorded primal
+    DevBuf<int2> unitsF;                      // [P][Sact][XUCAP] the forward sweeps' work units (k_xunits_fwd)
+    DevBuf<int> unit_overflow;                // set by k_xunits_fwd when a member has more units than XUCAP
     int ucap = 64;                            // dev knob HANK_XUCAP (read once, at hank_create): a smaller budget, to exercise the overflow path
     bool rng_valid = false;                   // srcF / unitsF belong to the recorded lottery
     bool neigh = true;                        // dev knob HANK_XNEIGH=0 (read once, at hank_create): every period waits for every member
@@ -97,9 +129,9 @@ struct XWork {
 // ---- on-chip wide sweeps (hank_wide.h): tangent buffers per batch width ----
 struct WTan {
     int N = 0;
-    double *dxhh = nullptr;         // (n_hh, P, N) the caller's input tangents (staging for the host-pointer entries)
-    double *dpol = nullptr;         // [P][N][G]
-    double *dagg_cm = nullptr;      // (P, N) column-major
+    DevBuf<double> dxhh;            // (n_hh, P, N) the caller's input tangents (staging for the host-pointer entries)
+    DevBuf<double> dpol;            // [P][N][G]
+    DevBuf<double> dagg_cm;         // (P, N) column-major
 };
 
 // ---- transposed sweeps (hank_adjoint.h): hank_vjp's workspace per batch width M (its own: no TanWork's dpol is reused, so the
@@ -108,20 +140,20 @@ struct CotWork {
     int N = 0;                      // the batch width M (the cache's key)
     int V = 1;                      // cotangent columns per lane
     AdjGeom g{};
-    double *ybar = nullptr;         // (P, n_het <= 2, M) the caller's cotangents (staging for both entries)
-    double *yb0 = nullptr, *yb1 = nullptr;      // [P][M] cotangents of the policy variable's aggregate and of consumption's
-    double *st[2] = {nullptr, nullptr};         // [G][M] ping-pong state: lam in Sweep A, then mu in Sweep B
-    double *pbar = nullptr;         // [P][G][M] the policy cotangent sequence: written once by Sweep A, read once by Sweep B
-    double *partS = nullptr, *partM = nullptr;  // [P][nb][3][M] per-block partial sums of the inputs' cotangents
-    double *xbar = nullptr;         // (n_hh, P, M) column-major
-    hipGraphExec_t g_A = nullptr, g_B = nullptr;
+    DevBuf<double> ybar;            // (P, n_het <= 2, M) the caller's cotangents (staging for both entries)
+    DevBuf<double> yb0, yb1;                    // [P][M] cotangents of the policy variable's aggregate and of consumption's
+    DevBuf<double> st[2];                       // [G][M] ping-pong state: lam in Sweep A, then mu in Sweep B
+    DevBuf<double> pbar;            // [P][G][M] the policy cotangent sequence: written once by Sweep A, read once by Sweep B
+    DevBuf<double> partS, partM;                // [P][nb][3][M] per-block partial sums of the inputs' cotangents
+    DevBuf<double> xbar;            // (n_hh, P, M) column-major
+    GraphExec g_A, g_B;
 };
 // The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
 struct CotBatch {
     bool current = false;
     int M = 0;
-    const void *ws = nullptr;
-    const double *pbar = nullptr;
+    const void *ws = nullptr;       // view
+    const double *pbar = nullptr;   // view
 };
 
 // The current tangent batch: at most ONE is current, and it belongs to the recorded primal. Written by batch_ran ("family F has
@@ -130,8 +162,8 @@ struct TanBatch {
     int family = 0;                 // which family ran the last tangent sweep (0 launches, 1 persistent, 2 wide): kept for hank_info when nothing is current
     bool current = false;
     int N = 0;
-    const void *ws = nullptr;       // the cache entry that holds it (its eviction makes nothing current)
-    const double *dagg_cm = nullptr, *dpol = nullptr;     // the family's (P, 2 N) tangents of the aggregates and its policy partials
+    const void *ws = nullptr;       // view: the cache entry that holds it (its eviction makes nothing current)
+    const double *dagg_cm = nullptr, *dpol = nullptr;     // views: the family's (P, 2 N) tangents of the aggregates and its policy partials
     const std::vector<XPass> *passes = nullptr;           // persistent family: how dpol is laid out
 };
 
@@ -171,15 +203,16 @@ enum Stat { SWEEP_LAUNCHES, TANGENT_WORKSPACES_ALLOCATED, GRAPHS_CAPTURED, SCHED
 
 struct hank_ctx {
     int device = 0;
-    Consts c{};
-    Record R{};
+    Consts c{};                    // (c.a, c.z, c.Pi: views of d_a, d_z, d_Pi)
+    Record R{};                    // views: every member points into rec_slab
     int T = 0;
-    double *d_a = nullptr, *d_z = nullptr, *d_Pi = nullptr;
-    double *d_ss_value = nullptr, *d_ss_D = nullptr;  // d_ss_D aliases Dseq[0]
-    double *d_xhh = nullptr, *d_agg = nullptr, *d_aggpart = nullptr;     // d_agg: (P, 2) column-major — the policy-weighted aggregate, then the grid-weighted one
-    double *d_agg_rm = nullptr;     // [P][2] as the reduction leaves it
-    double *d_zd = nullptr;         // [2][P]: sum_e z_e m_t(e) and sum_e m_t(e), m_t = Pi' m_{t-1} the productivity marginal of D_t (hank_get_het_outputs)
-    int *d_err = nullptr;
+    DevBuf<double> d_a, d_z, d_Pi;
+    DevBuf<double> d_ss_value;
+    double *d_ss_D = nullptr;      // view: aliases R.Dseq[0]
+    DevBuf<double> d_xhh, d_agg, d_aggpart;     // d_agg: (P, 2) column-major — the policy-weighted aggregate, then the grid-weighted one
+    DevBuf<double> d_agg_rm;        // [P][2] as the reduction leaves it
+    DevBuf<double> d_zd;            // [2][P]: sum_e z_e m_t(e) and sum_e m_t(e), m_t = Pi' m_{t-1} the productivity marginal of D_t (hank_get_het_outputs)
+    DevBuf<int> d_err;
     int nbp = 0;  // row blocks of the primal kernels
     bool boundary_set = false, primal_done = false;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -189,7 +222,7 @@ struct hank_ctx {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_side = nullptr;
     bool side_pending = false;
-    hipGraphExec_t g_pback = nullptr, g_pfwd = nullptr;
+    GraphExec g_pback, g_pfwd;
     Spans spans;                   // the timed sweeps (hank_last_timings, hank_last_vjp_timings)
     std::list<TanWork> tws;        // per batch width, most recently used first (a small cache: Jacobian assembly and Newton alternate widths)
     // 0 = one launch per period for everything; 1 = XCD-local persistent sweeps for everything; 2 = auto (default where
@@ -199,13 +232,13 @@ struct hank_ctx {
     TanBatch batch;                // the current tangent batch (hank_get_dpolicy_seq, hank_get_grid_aggregates, hank_get_het_outputs, hank_info)
     int xjvp_max = 64;             // auto: batches up to this width take the persistent tangent sweeps (measured crossover)
     XWork xw;
-    struct { double *dpT = nullptr, *iota = nullptr, *E = nullptr, *Cp = nullptr, *F = nullptr, *Dv = nullptr, *W = nullptr, *dsum = nullptr; int N = 0, n_het = 0; } fn;   // hank_fake_news[_het] workspace (E, Cp, F, Dv, W, dsum sized for n_het outputs)
+    struct { DevBuf<double> dpT, iota, E, Cp, F, Dv, W, dsum; int N = 0, n_het = 0; } fn;   // hank_fake_news[_het] workspace (E, Cp, F, Dv, W, dsum sized for n_het outputs)
     // on-chip wide sweeps: 0 = never, 1 = auto (batches of at least wide_min directions), 2 = every batch (HANK_SCHEDULE=wide: tests)
     int wide_mode = 0, wide_min = 80, num_cus = 256, wide_r = 2;     // wide_r: rows per thread of the wide kernels (2: 1024-thread workgroups, 4 waves per SIMD — since the L2 warming of round 5 the faster geometry for both sweeps, 5.16 / 6.80 ms against 5.30 / 7.10 at N=256; dev knob HANK_WIDE_R=2|4 at hank_create)
     size_t lds_max = 65536;
-    char *rec_slab = nullptr;      // the record's ONE allocation
+    DevBuf<char> rec_slab;         // the record's ONE allocation
     size_t rec_bytes = 0;
-    int *d_ibw = nullptr;          // the wide backward sweep's bracket record (k_wide_prep), valid for the recorded primal or not
+    DevBuf<int> d_ibw;             // the wide backward sweep's bracket record (k_wide_prep), valid for the recorded primal or not
     bool seg_valid = true;          // the record's per-target segment records match its lottery (k_lottery writes them except in the persistent Dual pass)
     bool lwg_valid = true;          // the record's per-source records {w, ig D} match it (every forward sweep of a primal writes them except the persistent Dual pass's)
     long long lwg_builds = 0;       // times k_xlwg_build ran (hank_info)
@@ -213,7 +246,7 @@ struct hank_ctx {
     std::list<WTan> wtans;         // most recently used first
     std::list<CotWork> cws;        // hank_vjp's workspaces, most recently used first
     CotBatch cot;                  // the current cotangent batch (hank_get_policy_cotangent_seq)
-    int *d_adj_sb = nullptr;       // [P][n_e][n_a + 1] Sweep B's bracket segment starts (k_adj_seg), valid for the recorded primal or not
+    DevBuf<int> d_adj_sb;          // [P][n_e][n_a + 1] Sweep B's bracket segment starts (k_adj_seg), valid for the recorded primal or not
     bool adj_seg_valid = false;
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
     long long stats[N_STATS] = {};   // see Stat and hank_stats
@@ -224,7 +257,7 @@ struct hank_ctx {
     bool memo_valid = false;
     std::vector<double> memo_xhh;
     int n_het = 2;                                    // heterogeneous outputs the caller declared (hank_set_het_outputs; a change drops the memo)
-    char *hx_slab = nullptr;                          // the extra outputs' buffers (hx_outputs), grown to the largest request, freed with the context
+    DevBuf<char> hx_slab;                             // the extra outputs' buffers (hx_outputs), grown to the largest request, freed with the context
     size_t hx_bytes = 0;
     bool stationary = false;                          // the recorded primal is the constant steady-state path with the steady state as both boundaries (hank_fake_news)
     std::vector<double> h_ss_value, h_ss_D;           // the boundary as the host handed it in (stationarity check)
@@ -233,7 +266,6 @@ struct hank_ctx {
 };
 
 static int fail(hank_ctx *ctx, int code, const char *fmt, ...);
-static void free_fn(hank_ctx *ctx);
 static void batch_none(hank_ctx *ctx) { ctx->batch.current = false; ctx->batch.ws = nullptr; }
 static void cot_none(hank_ctx *ctx) { ctx->cot = CotBatch(); }
 static void cot_ran(hank_ctx *ctx, const void *ws, int M, const double *pbar) { ctx->cot = CotBatch{true, M, ws, pbar}; }
@@ -259,17 +291,6 @@ static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written) 
 static void record_gone(hank_ctx *ctx) {
     record_rewritten(ctx, false, false);
     ctx->primal_done = false;
-}
-static void free_cotwork(CotWork &w) {
-    if (w.g_A) (void)hipGraphExecDestroy(w.g_A);
-    if (w.g_B) (void)hipGraphExecDestroy(w.g_B);
-    (void)hipFree(w.ybar); (void)hipFree(w.yb0); (void)hipFree(w.yb1); (void)hipFree(w.st[0]); (void)hipFree(w.st[1]);
-    (void)hipFree(w.pbar); (void)hipFree(w.partS); (void)hipFree(w.partM); (void)hipFree(w.xbar);
-    w = CotWork();
-}
-static void w_free_tan(WTan &w) {
-    (void)hipFree(w.dxhh); (void)hipFree(w.dpol); (void)hipFree(w.dagg_cm);
-    w = WTan();
 }
 static hipError_t join_side(hank_ctx *ctx) {
     if (!ctx->side_pending) return hipSuccess;
@@ -322,11 +343,6 @@ DeviceGuard::DeviceGuard(const hank_ctx *ctx) {
     DeviceGuard dev_guard_(ctx);                                                                                         \
     if (!dev_guard_.ok) return fail(ctx, HANK_ERR_NO_DEVICE, "HIP device %d of this context could not be made current", (ctx) ? (ctx)->device : -1)
 
-template <typename T>
-static hipError_t dmalloc(T **p, size_t count) {
-    return hipMalloc((void **)p, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
-}
-
 // the copy-outs of the sweeps' results on stream s: column `col` of d_agg (P, 2), and the N columns of aggregate `col` of a family's
 // dagg_cm (P, 2 N) — both column-major; a null destination asks for nothing
 static hipError_t copy_agg(hank_ctx *ctx, double *dst, hipMemcpyKind kind, hipStream_t s, int col = 0) {
@@ -340,22 +356,13 @@ static hipError_t copy_dagg(hank_ctx *ctx, double *dst, const double *dagg_cm, i
 
 static size_t primal_lds(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * RBP + (size_t)c.n_e * c.n_e + 16); }
 
-static void free_tanwork(TanWork &w) {
-    if (w.g_back) (void)hipGraphExecDestroy(w.g_back);
-    if (w.g_fwd) (void)hipGraphExecDestroy(w.g_fwd);
-    if (w.g_fback) (void)hipGraphExecDestroy(w.g_fback);
-    if (w.g_ffwd) (void)hipGraphExecDestroy(w.g_ffwd);
-    (void)hipFree(w.dxhh); (void)hipFree(w.dxr); (void)hipFree(w.dxw); (void)hipFree(w.dxt);
-    (void)hipFree(w.ds[0]); (void)hipFree(w.ds[1]); (void)hipFree(w.dD[0]); (void)hipFree(w.dD[1]);
-    (void)hipFree(w.dpol); (void)hipFree(w.aggpart); (void)hipFree(w.dagg); (void)hipFree(w.dagg_cm);
-    w = TanWork();
-}
-
 // ---- graph construction -----------------------------------------------------------------------
-static int end_capture(hank_ctx *ctx, hipGraphExec_t *out) {
+static int end_capture(hank_ctx *ctx, GraphExec *out) {
     hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
     HIPC(ctx, hipStreamEndCapture(ctx->own_stream, &graph));
-    HIPC(ctx, hipGraphInstantiate(out, graph, nullptr, nullptr, 0));
+    HIPC(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    out->reset(exec);
     HIPC(ctx, hipGraphDestroy(graph));
     HIPC(ctx, hipGetLastError());
     ctx->stats[GRAPHS_CAPTURED]++;
@@ -423,11 +430,11 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     const dim3 blk(64 * c.n_e);
     const unsigned ny = (w.g.N + w.g.NC - 1) / w.g.NC, nyf = (w.gf.N + w.gf.NC - 1) / w.gf.NC;
     const int PN = (int)(P * N);
-    const VT *dxr = reinterpret_cast<const VT *>(w.dxr), *dxw = reinterpret_cast<const VT *>(w.dxw), *dxt = reinterpret_cast<const VT *>(w.dxt);
-    VT *ds[2] = {reinterpret_cast<VT *>(w.ds[0]), reinterpret_cast<VT *>(w.ds[1])};
-    VF *dD[2] = {reinterpret_cast<VF *>(w.dD[0]), reinterpret_cast<VF *>(w.dD[1])};
-    VT *dpol = reinterpret_cast<VT *>(w.dpol);
-    VF *dpolf = reinterpret_cast<VF *>(w.dpol), *aggpart = reinterpret_cast<VF *>(w.aggpart);
+    const VT *dxr = reinterpret_cast<const VT *>(w.dxr.get()), *dxw = reinterpret_cast<const VT *>(w.dxw.get()), *dxt = reinterpret_cast<const VT *>(w.dxt.get());
+    VT *ds[2] = {reinterpret_cast<VT *>(w.ds[0].get()), reinterpret_cast<VT *>(w.ds[1].get())};
+    VF *dD[2] = {reinterpret_cast<VF *>(w.dD[0].get()), reinterpret_cast<VF *>(w.dD[1].get())};
+    VT *dpol = reinterpret_cast<VT *>(w.dpol.get());
+    VF *dpolf = reinterpret_cast<VF *>(w.dpol.get()), *aggpart = reinterpret_cast<VF *>(w.aggpart.get());
     const unsigned nbt = (w.nbx + RGB - 1) / RGB;
     int rc = HANK_OK, cur = 0;
     if (which == 0) {
@@ -500,9 +507,9 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
 
 // The workspaces of one family for a batch of N directions, from a small most-recently-used cache (Jacobian assembly at N = 256
 // and the Newton inner loop at N = 1 alternate: neither re-allocates). On a miss `build` sizes and allocates the new entry
-// (its N is set); `release` frees an entry's device memory.
+// (its N is set); an entry's members own its device memory and graphs, so dropping the entry releases them.
 template <typename W, typename Build>
-static int tan_cache_get(hank_ctx *ctx, std::list<W> &cache, int N, void (*release)(W &), Build build, W **out) {
+static int tan_cache_get(hank_ctx *ctx, std::list<W> &cache, int N, Build build, W **out) {
     for (auto it = cache.begin(); it != cache.end(); ++it)
         if (it->N == N) { cache.splice(cache.begin(), cache, it); *out = &cache.front(); return HANK_OK; }
     const char *ce = getenv("HANK_TAN_CACHE");
@@ -512,7 +519,6 @@ static int tan_cache_get(hank_ctx *ctx, std::list<W> &cache, int N, void (*relea
         HIPC(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->batch.ws == &cache.back()) batch_none(ctx);
         if (ctx->cot.ws == &cache.back()) cot_none(ctx);
-        release(cache.back());
         cache.pop_back();
     }
     cache.emplace_front();
@@ -522,7 +528,7 @@ static int tan_cache_get(hank_ctx *ctx, std::list<W> &cache, int N, void (*relea
     // a failed allocation must not leave a half-built entry in the cache: a retry with this N would find it, return
     // HANK_OK and launch on null pointers
     const int rc = build(w);
-    if (rc) { release(w); cache.pop_front(); (void)hipGetLastError(); return rc; }
+    if (rc) { cache.pop_front(); (void)hipGetLastError(); return rc; }
     *out = &w;
     return HANK_OK;
 }
@@ -553,27 +559,27 @@ static int build_tanwork(hank_ctx *ctx, TanWork &w) {
     const int RGB = tan_rg(w.g.N, 0), RGF = tan_rg(w.gf.N, 1, w.gf.ss);
     const unsigned nbf = (w.nbxf + RGF - 1) / RGF + KV;   // forward blocks: regular + mass-point
     w.VB = VB; w.VF = VF; w.RGB = RGB; w.RGF = RGF; w.nbf = nbf;
-    HIPC(ctx, dmalloc(&w.dxhh, (size_t)c.n_hh * P * N));
-    HIPC(ctx, dmalloc(&w.dxr, P * N));
-    HIPC(ctx, dmalloc(&w.dxw, P * N));
-    HIPC(ctx, dmalloc(&w.dxt, P * N));
+    HIPC(ctx, w.dxhh.alloc((size_t)c.n_hh * P * N));
+    HIPC(ctx, w.dxr.alloc(P * N));
+    HIPC(ctx, w.dxw.alloc(P * N));
+    HIPC(ctx, w.dxt.alloc(P * N));
     for (int k = 0; k < 2; k++) {
-        HIPC(ctx, dmalloc(&w.ds[k], G * N));
-        HIPC(ctx, dmalloc(&w.dD[k], GV * N));
+        HIPC(ctx, w.ds[k].alloc(G * N));
+        HIPC(ctx, w.dD[k].alloc(GV * N));
     }
-    HIPC(ctx, dmalloc(&w.dpol, P * G * N));
-    HIPC(ctx, dmalloc(&w.aggpart, 2 * P * (size_t)nbf * N));      // both aggregates: [P][blocks][2 N]
-    HIPC(ctx, dmalloc(&w.dagg, 2 * P * N));
-    HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * N));                    // (P, 2 N) column-major: the policy-weighted aggregate's N columns, then the grid-weighted one's
+    HIPC(ctx, w.dpol.alloc(P * G * N));
+    HIPC(ctx, w.aggpart.alloc(2 * P * (size_t)nbf * N));      // both aggregates: [P][blocks][2 N]
+    HIPC(ctx, w.dagg.alloc(2 * P * N));
+    HIPC(ctx, w.dagg_cm.alloc(2 * P * N));                    // (P, 2 N) column-major: the policy-weighted aggregate's N columns, then the grid-weighted one's
     return HANK_OK;
 }
 static int ensure_tanwork(hank_ctx *ctx, int N, TanWork **out) {
-    return tan_cache_get(ctx, ctx->tws, N, free_tanwork, [ctx](TanWork &w) { return build_tanwork(ctx, w); }, out);
+    return tan_cache_get(ctx, ctx->tws, N, [ctx](TanWork &w) { return build_tanwork(ctx, w); }, out);
 }
 
 // the graph pair of one schedule, captured the first time that schedule runs at this batch width
 static int ensure_graphs(hank_ctx *ctx, TanWork &w, int which) {
-    if (which == 0 ? w.g_back != nullptr : w.g_fback != nullptr) return HANK_OK;
+    if (which == 0 ? w.g_back.get() != nullptr : w.g_fback.get() != nullptr) return HANK_OK;
     if (w.VB == 2) return w.VF == 2 ? capture_tangent_graphs<double2, double2>(ctx, w, which) : capture_tangent_graphs<double2, double>(ctx, w, which);
     return w.VF == 2 ? capture_tangent_graphs<double, double2>(ctx, w, which) : capture_tangent_graphs<double, double>(ctx, w, which);
 }
@@ -610,7 +616,7 @@ static int fetch_device_error(hank_ctx *ctx) {
                     "savings policy is not monotone in wealth (period %d, productivity state %d, "
                     "wealth index %d)", e[1] + 1, e[2] + 1, e[3] + 1);
     default:
-        return fail(ctx, HANK_ERR_BAD_ARG, "unknown device error %d (%d,%d,%d) d_err=%p", e[0], e[1], e[2], e[3], (void*)ctx->d_err);
+        return fail(ctx, HANK_ERR_BAD_ARG, "unknown device error %d (%d,%d,%d) d_err=%p", e[0], e[1], e[2], e[3], (void *)ctx->d_err.get());
     }
 }
 
@@ -640,21 +646,6 @@ static bool x_supported(const hank_ctx *ctx, int cus, size_t lds_max) {
     return cus >= XG && Sact <= cus / XG && c.n_e <= 16 && x_lds_float64(c) <= lds_max;
 }
 
-static void x_free_tan(XTan &w) {
-    (void)hipFree(w.dxhh); (void)hipFree(w.dxr); (void)hipFree(w.dxw); (void)hipFree(w.dxt);
-    (void)hipFree(w.dpol); (void)hipFree(w.daggpart); (void)hipFree(w.dagg_pass); (void)hipFree(w.dagg_cm);
-    w = XTan();
-}
-
-static void x_free(hank_ctx *ctx) {
-    XWork &X = ctx->xw;
-    for (XTan &w : X.tans) x_free_tan(w);
-    X.tans.clear();
-    (void)hipFree(X.sync); (void)hipFree(X.st_s); (void)hipFree(X.st_ds); (void)hipFree(X.st_D); (void)hipFree(X.st_dD);
-    (void)hipFree(X.Dvirt); (void)hipFree(X.D0own); (void)hipFree(X.aggpart); (void)hipFree(X.rho); (void)hipFree(X.srcB); (void)hipFree(X.srcF); (void)hipFree(X.unitsF); (void)hipFree(X.unit_overflow);
-    X = XWork();
-}
-
 static int x_setup(hank_ctx *ctx) {
     XWork &X = ctx->xw;
     if (X.ready) return HANK_OK;
@@ -667,21 +658,21 @@ static int x_setup(hank_ctx *ctx) {
     X.maxt = 64 * (c.n_e + 1) <= 768 ? 768 : 1024;
     X.dmax = X.maxt == 768 ? XD_MAX : 2;
     const size_t G = c.G, GV = G + 64 * (size_t)c.n_e, P = c.P;
-    HIPC(ctx, dmalloc(&X.sync, (size_t)2 + 2 * XPASS_MAX));
+    HIPC(ctx, X.sync.alloc((size_t)2 + 2 * XPASS_MAX));
     HIPC(ctx, hipMemsetAsync(X.sync, 0, sizeof(XSync) * ((size_t)2 + 2 * XPASS_MAX), ctx->stream));      // x_status reads blocks 0, 1 also when the launches recorded the primal
-    HIPC(ctx, dmalloc(&X.st_s, 2 * XG * G));
-    HIPC(ctx, dmalloc(&X.st_ds, 2 * XG * G * X.dmax));
+    HIPC(ctx, X.st_s.alloc(2 * XG * G));
+    HIPC(ctx, X.st_ds.alloc(2 * XG * G * X.dmax));
     const size_t GM = (size_t)c.n_e * X.Sact * 64;       // member-major state of the forward sweeps: [n_e][members][64]
-    HIPC(ctx, dmalloc(&X.st_D, 2 * XG * std::max(GV, GM)));
-    HIPC(ctx, dmalloc(&X.st_dD, 2 * XG * GM * xslots(X.dmax + 1).SP));      // D partials + the value, padded to pairs
-    HIPC(ctx, dmalloc(&X.Dvirt, P * c.n_e * 64));
-    HIPC(ctx, dmalloc(&X.D0own, P * c.n_e));
-    HIPC(ctx, dmalloc(&X.aggpart, 2 * P * (size_t)X.Sact));       // [P][members][2]
-    HIPC(ctx, dmalloc(&X.rho, P));
-    HIPC(ctx, dmalloc(&X.srcB, P * X.Sact));
-    HIPC(ctx, dmalloc(&X.srcF, P * X.Sact));
-    HIPC(ctx, dmalloc(&X.unitsF, P * X.Sact * XUCAP));
-    HIPC(ctx, dmalloc(&X.unit_overflow, 1));
+    HIPC(ctx, X.st_D.alloc(2 * XG * std::max(GV, GM)));
+    HIPC(ctx, X.st_dD.alloc(2 * XG * GM * xslots(X.dmax + 1).SP));      // D partials + the value, padded to pairs
+    HIPC(ctx, X.Dvirt.alloc(P * c.n_e * 64));
+    HIPC(ctx, X.D0own.alloc(P * c.n_e));
+    HIPC(ctx, X.aggpart.alloc(2 * P * (size_t)X.Sact));       // [P][members][2]
+    HIPC(ctx, X.rho.alloc(P));
+    HIPC(ctx, X.srcB.alloc(P * X.Sact));
+    HIPC(ctx, X.srcF.alloc(P * X.Sact));
+    HIPC(ctx, X.unitsF.alloc(P * X.Sact * XUCAP));
+    HIPC(ctx, X.unit_overflow.alloc(1));
     HIPC(ctx, hipMemsetAsync(X.unit_overflow, 0, sizeof(int), ctx->stream));
     if (const char *ng = getenv("HANK_XNEIGH")) X.neigh = atoi(ng) != 0;
     if (const char *uc = getenv("HANK_XUCAP")) X.ucap = std::min(XUCAP, std::max(1, atoi(uc)));
@@ -720,20 +711,20 @@ static int x_build_tan(hank_ctx *ctx, XTan &w) {
         w.passes.push_back(ps);
     }
     if ((int)w.passes.size() > XPASS_MAX) return fail(ctx, HANK_ERR_BAD_ARG, "N=%d needs %d passes, at most %d per call", N, (int)w.passes.size(), XPASS_MAX);
-    HIPC(ctx, dmalloc(&w.dxhh, (size_t)c.n_hh * P * N));
-    HIPC(ctx, dmalloc(&w.dxr, P * N)); HIPC(ctx, dmalloc(&w.dxw, P * N)); HIPC(ctx, dmalloc(&w.dxt, P * N));
-    HIPC(ctx, dmalloc(&w.dpol, off));
+    HIPC(ctx, w.dxhh.alloc((size_t)c.n_hh * P * N));
+    HIPC(ctx, w.dxr.alloc(P * N)); HIPC(ctx, w.dxw.alloc(P * N)); HIPC(ctx, w.dxt.alloc(P * N));
+    HIPC(ctx, w.dpol.alloc(off));
     const size_t W = (size_t)XG * X.dmax, nb = (size_t)X.Sact;
-    HIPC(ctx, dmalloc(&w.daggpart, 2 * P * nb * W));              // both aggregates: [P][members][2 W]
+    HIPC(ctx, w.daggpart.alloc(2 * P * nb * W));              // both aggregates: [P][members][2 W]
     HIPC(ctx, hipMemsetAsync(w.daggpart, 0, sizeof(double) * 2 * P * nb * W, ctx->stream));
-    HIPC(ctx, dmalloc(&w.dagg_pass, 2 * P * W));
-    HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * N));                    // (P, 2 N) column-major
+    HIPC(ctx, w.dagg_pass.alloc(2 * P * W));
+    HIPC(ctx, w.dagg_cm.alloc(2 * P * N));                    // (P, 2 N) column-major
     return HANK_OK;
 }
 static int x_ensure_tan(hank_ctx *ctx, int N, XTan **out) {
     const int nmax = 8 * ctx->xw.dmax * XPASS_MAX;      // (a cached width has passed this check)
     if (N > nmax) return fail(ctx, HANK_ERR_BAD_ARG, "N=%d exceeds %d directions per call", N, nmax);
-    return tan_cache_get(ctx, ctx->xw.tans, N, x_free_tan, [ctx](XTan &w) { return x_build_tan(ctx, w); }, out);
+    return tan_cache_get(ctx, ctx->xw.tans, N, [ctx](XTan &w) { return x_build_tan(ctx, w); }, out);
 }
 
 // workgroup of the persistent kernels: 64 threads per productivity state + one wave that only runs the group barrier's poll,
@@ -923,7 +914,7 @@ static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_bac
     const bool neigh = X.neigh;
     XTanBackArgs ab{};
     ab.c = c; ab.R = ctx->R; ab.rho = X.rho; ab.xhh = ctx->d_xhh; ab.dxr = w->dxr; ab.dxw = w->dxw; ab.dxt = w->dxt; ab.Ntot = N; ab.st_ds = X.st_ds;
-    ab.src = neigh ? X.srcB : nullptr;
+    ab.src = neigh ? X.srcB.get() : nullptr;
     ab.stall = X.fault == 3 ? 1 : 0;
     XSweepFwdArgs fa{};
     fa.c = c; fa.R = ctx->R; fa.st = X.st_dD; fa.daggpart = w->daggpart; fa.src = X.srcF; fa.units = X.unitsF; fa.overflow = X.unit_overflow; fa.all_members = neigh ? 0 : 1;
@@ -1061,13 +1052,13 @@ static int w_launch(hank_ctx *ctx, bool fwd, int N, const WideArgs &a) {
 // (the staging buffer of the host-pointer entries is allocated when one of them first uses the width)
 static int w_ensure_tan(hank_ctx *ctx, int N, bool staging, WTan **out) {
     const size_t P = ctx->c.P, G = ctx->c.G;
-    const int rc = tan_cache_get(ctx, ctx->wtans, N, w_free_tan, [=](WTan &w) -> int {
-        HIPC(ctx, dmalloc(&w.dpol, P * (size_t)N * G + 2));       // (+ 2: the last 16-byte load of an odd-sized grid reads 8 bytes past its row)
-        HIPC(ctx, dmalloc(&w.dagg_cm, 2 * P * (size_t)N));            // (P, 2 N) column-major: both aggregates
+    const int rc = tan_cache_get(ctx, ctx->wtans, N, [=](WTan &w) -> int {
+        HIPC(ctx, w.dpol.alloc(P * (size_t)N * G + 2));       // (+ 2: the last 16-byte load of an odd-sized grid reads 8 bytes past its row)
+        HIPC(ctx, w.dagg_cm.alloc(2 * P * (size_t)N));            // (P, 2 N) column-major: both aggregates
         return HANK_OK;
     }, out);
     if (rc) return rc;
-    if (staging && !(*out)->dxhh) HIPC(ctx, dmalloc(&(*out)->dxhh, (size_t)ctx->c.n_hh * P * N));
+    if (staging && !(*out)->dxhh) HIPC(ctx, (*out)->dxhh.alloc((size_t)ctx->c.n_hh * P * N));
     return HANK_OK;
 }
 
@@ -1077,7 +1068,7 @@ static int w_run_tangent(hank_ctx *ctx, WTan *w, const double *d_dxhh) {
     hipStream_t s = ctx->stream;
     int rc = x_serialize_begin(ctx);        // (a persistent sweep of another context must not find the chip half full of these workgroups)
     if (rc) return rc;
-    if (!ctx->d_ibw) HIPC(ctx, dmalloc(&ctx->d_ibw, (size_t)c.P * c.G + 4));      // (before the kernel arguments are filled in)
+    if (!ctx->d_ibw) HIPC(ctx, ctx->d_ibw.alloc((size_t)c.P * c.G + 4));      // (before the kernel arguments are filled in)
     WideArgs a{};
     a.c = c; a.R = ctx->R; a.xhh = ctx->d_xhh; a.dxhh = d_dxhh; a.Ntot = w->N; a.n0 = 0; a.dpol = w->dpol; a.dagg = w->dagg_cm;
     a.rec = ctx->rec_slab;
@@ -1116,7 +1107,7 @@ static int w_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, d
     int rc = w_ensure_tan(ctx, N, staging, &w);
     if (rc) return rc;
     if (staging) HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * ctx->c.P * N, kind, ctx->stream));
-    rc = w_run_tangent(ctx, w, staging ? w->dxhh : dxhh);
+    rc = w_run_tangent(ctx, w, staging ? w->dxhh.get() : dxhh);
     if (rc) return rc;
     HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
     return HANK_OK;
@@ -1200,13 +1191,13 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     HIPC(ctx, hipEventCreate(&ctx->ev_side));
     HIPC(ctx, ctx->spans.create());
-    HIPC(ctx, dmalloc(&ctx->d_a, c.n_a));
-    HIPC(ctx, dmalloc(&ctx->d_z, c.n_e));
-    HIPC(ctx, dmalloc(&ctx->d_Pi, (size_t)c.n_e * c.n_e));
+    HIPC(ctx, ctx->d_a.alloc(c.n_a));
+    HIPC(ctx, ctx->d_z.alloc(c.n_e));
+    HIPC(ctx, ctx->d_Pi.alloc((size_t)c.n_e * c.n_e));
     HIPC(ctx, hipMemcpy(ctx->d_a, m->a_grid, sizeof(double) * c.n_a, hipMemcpyHostToDevice));
     HIPC(ctx, hipMemcpy(ctx->d_z, m->z_grid, sizeof(double) * c.n_e, hipMemcpyHostToDevice));
     HIPC(ctx, hipMemcpy(ctx->d_Pi, m->Pi, sizeof(double) * c.n_e * c.n_e, hipMemcpyHostToDevice));
-    c.a = ctx->d_a; c.z = ctx->d_z; c.Pi = ctx->d_Pi;
+    c.a = ctx->d_a; c.z = ctx->d_z; c.Pi = ctx->d_Pi;      // views
     ctx->h_Pi.assign(m->Pi, m->Pi + (size_t)c.n_e * c.n_e);
     ctx->h_z.assign(m->z_grid, m->z_grid + c.n_e);
     ctx->lds_max = prop.sharedMemPerBlock;
@@ -1214,13 +1205,13 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     Record &R = ctx->R;
     {   // the record is ONE allocation: the on-chip wide sweeps reach every array through one buffer descriptor (hank_wide.h)
         size_t off = 0;
-        auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
         const size_t d8 = P * G * sizeof(double);
-        const size_t o_s = carve(d8), o_kc = carve(d8), o_A = carve(d8), o_B = carve(d8), o_u = carve(d8), o_v = carve(d8), o_pol = carve(d8),
-                     o_lw = carve(d8), o_ig = carve(d8), o_D = carve((P + 1) * G * sizeof(double)), o_ib = carve(P * G * sizeof(int)),
-                     o_lo = carve(P * G * sizeof(int)), o_st = carve(P * (size_t)c.n_e * (c.n_a + 1) * sizeof(int)),
-                     o_clo = carve(P * (size_t)c.n_e * sizeof(int)), o_lwg = carve(P * G * sizeof(double2)), o_seg = carve(P * G * sizeof(int4));
-        HIPC(ctx, hipMalloc((void **)&ctx->rec_slab, off));
+        const size_t o_s = carve(off, d8), o_kc = carve(off, d8), o_A = carve(off, d8), o_B = carve(off, d8), o_u = carve(off, d8), o_v = carve(off, d8),
+                     o_pol = carve(off, d8), o_lw = carve(off, d8), o_ig = carve(off, d8), o_D = carve(off, (P + 1) * G * sizeof(double)),
+                     o_ib = carve(off, P * G * sizeof(int)), o_lo = carve(off, P * G * sizeof(int)),
+                     o_st = carve(off, P * (size_t)c.n_e * (c.n_a + 1) * sizeof(int)), o_clo = carve(off, P * (size_t)c.n_e * sizeof(int)),
+                     o_lwg = carve(off, P * G * sizeof(double2)), o_seg = carve(off, P * G * sizeof(int4));
+        HIPC(ctx, ctx->rec_slab.alloc(off));
         ctx->rec_bytes = off;
         char *b = ctx->rec_slab;
         R.s = (double *)(b + o_s); R.kc = (double *)(b + o_kc); R.A = (double *)(b + o_A); R.B = (double *)(b + o_B);
@@ -1228,15 +1219,15 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
         R.ig = (double *)(b + o_ig); R.Dseq = (double *)(b + o_D); R.ib = (int *)(b + o_ib); R.lo = (int *)(b + o_lo);
         R.start = (int *)(b + o_st); R.clo = (int *)(b + o_clo); R.lwg = (double2 *)(b + o_lwg); R.seg = (int4 *)(b + o_seg);
     }
-    HIPC(ctx, dmalloc(&ctx->d_ss_value, G));
-    ctx->d_ss_D = R.Dseq;
+    HIPC(ctx, ctx->d_ss_value.alloc(G));
+    ctx->d_ss_D = R.Dseq;      // view
     ctx->nbp = (c.n_a + RBP - 1) / RBP;
-    HIPC(ctx, dmalloc(&ctx->d_xhh, (size_t)c.n_hh * P));
-    HIPC(ctx, dmalloc(&ctx->d_agg, 2 * P));
-    HIPC(ctx, dmalloc(&ctx->d_agg_rm, 2 * P));
-    HIPC(ctx, dmalloc(&ctx->d_zd, 2 * P));
-    HIPC(ctx, dmalloc(&ctx->d_aggpart, 2 * P * (size_t)ctx->nbp));
-    HIPC(ctx, dmalloc(&ctx->d_err, 4));
+    HIPC(ctx, ctx->d_xhh.alloc((size_t)c.n_hh * P));
+    HIPC(ctx, ctx->d_agg.alloc(2 * P));
+    HIPC(ctx, ctx->d_agg_rm.alloc(2 * P));
+    HIPC(ctx, ctx->d_zd.alloc(2 * P));
+    HIPC(ctx, ctx->d_aggpart.alloc(2 * P * (size_t)ctx->nbp));
+    HIPC(ctx, ctx->d_err.alloc(4));
     HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, 4 * sizeof(int), ctx->stream));
     HIPC(ctx, hipEventCreateWithFlags(&ctx->ev_stream, hipEventDisableTiming));
     // schedule (measured on MI355X): "auto" wherever the grid fits one 63-row slab per CU of an XCD —
@@ -1280,27 +1271,14 @@ int hank_destroy(hank_ctx *ctx) {
     ENTER(ctx);
     if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-    for (TanWork &t : ctx->tws) free_tanwork(t);
-    ctx->tws.clear();
-    x_free(ctx);
-    free_fn(ctx);
     if (ctx->ev_stream) (void)hipEventDestroy(ctx->ev_stream);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_side) (void)hipEventDestroy(ctx->ev_side);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
-    if (ctx->g_pback) (void)hipGraphExecDestroy(ctx->g_pback);
-    if (ctx->g_pfwd) (void)hipGraphExecDestroy(ctx->g_pfwd);
-    for (WTan &t : ctx->wtans) w_free_tan(t);
-    ctx->wtans.clear();
-    for (CotWork &t : ctx->cws) free_cotwork(t);
-    ctx->cws.clear();
-    (void)hipFree(ctx->d_adj_sb);
-    (void)hipFree(ctx->rec_slab); (void)hipFree(ctx->d_ibw); (void)hipFree(ctx->hx_slab);
-    (void)hipFree(ctx->d_a); (void)hipFree(ctx->d_z); (void)hipFree(ctx->d_Pi); (void)hipFree(ctx->d_ss_value);
-    (void)hipFree(ctx->d_xhh); (void)hipFree(ctx->d_agg); (void)hipFree(ctx->d_agg_rm); (void)hipFree(ctx->d_zd); (void)hipFree(ctx->d_aggpart); (void)hipFree(ctx->d_err);
     ctx->spans.destroy();
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    const hipStream_t own = ctx->own_stream;
+    delete ctx;      // both streams are idle: the members release their device memory and graphs, in any order
+    if (own) (void)hipStreamDestroy(own);      // (the own stream outlives them)
     return HANK_OK;
 }
 
@@ -1427,7 +1405,7 @@ static int x_dual(hank_ctx *ctx, const double *xhh, const double *dxhh, hipMemcp
         rc = x_serialize_begin(ctx);        // (the sync blocks about to be zeroed may belong to a sweep still in flight on another stream)
         if (rc) return rc;
         hipLaunchKernelGGL(k_xdual_prologue, dim3(64), dim3(256), 0, ctx->stream, xhh, ctx->d_xhh, dxhh, w->dxhh, ctx->c.n_hh, (int)P, N, X.rho, w->dxr, w->dxw, w->dxt,
-                           reinterpret_cast<xv4u *>(X.sync), sizeof(XSync) * 4 / sizeof(xv4u), ctx->d_err);
+                           reinterpret_cast<xv4u *>(X.sync.get()), sizeof(XSync) * 4 / sizeof(xv4u), ctx->d_err);
         xo.pro_done = true;
     } else {
         HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
@@ -1714,29 +1692,23 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
     return HANK_OK;
 }
 
-static void free_fn(hank_ctx *ctx) {
-    (void)hipFree(ctx->fn.dpT); (void)hipFree(ctx->fn.iota); (void)hipFree(ctx->fn.E); (void)hipFree(ctx->fn.Cp); (void)hipFree(ctx->fn.F); (void)hipFree(ctx->fn.Dv);
-    (void)hipFree(ctx->fn.W); (void)hipFree(ctx->fn.dsum);
-    ctx->fn = {};
-}
-
 // the fake-news workspace for n_het outputs: allocated at the first call, grown (all of it, after the stream drains) when a
 // call asks for more outputs than it holds
 static int ensure_fn(hank_ctx *ctx, int n_het) {
     if (ctx->fn.n_het >= n_het) return HANK_OK;
     const size_t P = ctx->c.P, G = ctx->c.G, NP = P * ctx->c.n_hh, S = 16, nh = n_het;
     if (ctx->fn.dpT) HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    free_fn(ctx);
+    ctx->fn = {};
     auto alloc = [&]() -> int {
-        HIPC(ctx, dmalloc(&ctx->fn.dpT, G * NP)); HIPC(ctx, dmalloc(&ctx->fn.iota, G * NP));
-        HIPC(ctx, dmalloc(&ctx->fn.E, nh * P * G)); HIPC(ctx, dmalloc(&ctx->fn.Cp, S * nh * P * NP));
-        HIPC(ctx, dmalloc(&ctx->fn.F, nh * P * NP)); HIPC(ctx, dmalloc(&ctx->fn.Dv, nh * NP));
-        HIPC(ctx, dmalloc(&ctx->fn.W, nh * G)); HIPC(ctx, dmalloc(&ctx->fn.dsum, nh * ctx->c.n_hh));
+        HIPC(ctx, ctx->fn.dpT.alloc(G * NP)); HIPC(ctx, ctx->fn.iota.alloc(G * NP));
+        HIPC(ctx, ctx->fn.E.alloc(nh * P * G)); HIPC(ctx, ctx->fn.Cp.alloc(S * nh * P * NP));
+        HIPC(ctx, ctx->fn.F.alloc(nh * P * NP)); HIPC(ctx, ctx->fn.Dv.alloc(nh * NP));
+        HIPC(ctx, ctx->fn.W.alloc(nh * G)); HIPC(ctx, ctx->fn.dsum.alloc(nh * ctx->c.n_hh));
         return HANK_OK;
     };
     const int rc = alloc();
     if (rc) {
-        free_fn(ctx);
+        ctx->fn = {};
         (void)hipGetLastError();
         return rc;
     }
@@ -1966,15 +1938,12 @@ int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out) {
     int rc = batch_current(ctx, N, &b);
     if (rc) return rc;
     const size_t total = (size_t)ctx->c.P * ctx->c.G * N;
-    double *tmp = nullptr;
-    HIPC(ctx, dmalloc(&tmp, total));
+    DevBuf<double> tmp;      // (released on every way out: hipFree waits for the work that uses it)
+    HIPC(ctx, tmp.alloc(total));
     rc = export_dpol_dev(ctx, *b, tmp);
-    hipError_t e1 = hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp);
     if (rc) return rc;
-    HIPC(ctx, e1);
-    HIPC(ctx, e2);
+    HIPC(ctx, hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return HANK_OK;
 }
 
@@ -1995,14 +1964,14 @@ static int build_cotwork(hank_ctx *ctx, CotWork &w) {
     const int RB = 64 / g.NC;
     g.R = std::max(RB, 8);
     g.nb = (c.n_a + g.R - 1) / g.R;
-    HIPC(ctx, dmalloc(&w.ybar, 2 * P * M));
-    HIPC(ctx, dmalloc(&w.yb0, P * M));
-    HIPC(ctx, dmalloc(&w.yb1, P * M));
-    for (int k = 0; k < 2; k++) HIPC(ctx, dmalloc(&w.st[k], G * M));
-    HIPC(ctx, dmalloc(&w.pbar, P * G * M));
-    HIPC(ctx, dmalloc(&w.partS, P * (size_t)g.nb * 3 * M));
-    HIPC(ctx, dmalloc(&w.partM, P * (size_t)g.nb * 3 * M));
-    HIPC(ctx, dmalloc(&w.xbar, (size_t)c.n_hh * P * M));
+    HIPC(ctx, w.ybar.alloc(2 * P * M));
+    HIPC(ctx, w.yb0.alloc(P * M));
+    HIPC(ctx, w.yb1.alloc(P * M));
+    for (int k = 0; k < 2; k++) HIPC(ctx, w.st[k].alloc(G * M));
+    HIPC(ctx, w.pbar.alloc(P * G * M));
+    HIPC(ctx, w.partS.alloc(P * (size_t)g.nb * 3 * M));
+    HIPC(ctx, w.partM.alloc(P * (size_t)g.nb * 3 * M));
+    HIPC(ctx, w.xbar.alloc((size_t)c.n_hh * P * M));
     return HANK_OK;
 }
 static size_t adj_lds_dist(const Consts &c, const AdjGeom &g, int V) { return sizeof(double) * ((size_t)c.n_e * (g.R + 2) * g.NC * V + (size_t)c.n_e * c.n_e); }
@@ -2019,9 +1988,9 @@ static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
     hipStream_t s = ctx->own_stream;
     const dim3 blk(64 * c.n_e), grd((unsigned)w.g.nb, (unsigned)((w.g.MV + w.g.NC - 1) / w.g.NC));
     const size_t ldsA = adj_lds_dist(c, w.g, w.V), ldsB = adj_lds_egm(c, w.g, w.V);
-    VT *st[2] = {reinterpret_cast<VT *>(w.st[0]), reinterpret_cast<VT *>(w.st[1])};
-    VT *pbar = reinterpret_cast<VT *>(w.pbar);
-    const VT *yb0 = reinterpret_cast<const VT *>(w.yb0), *yb1 = reinterpret_cast<const VT *>(w.yb1);
+    VT *st[2] = {reinterpret_cast<VT *>(w.st[0].get()), reinterpret_cast<VT *>(w.st[1].get())};
+    VT *pbar = reinterpret_cast<VT *>(w.pbar.get());
+    const VT *yb0 = reinterpret_cast<const VT *>(w.yb0.get()), *yb1 = reinterpret_cast<const VT *>(w.yb1.get());
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     int cur = 0;
     for (int t = P - 1; t >= 0; t--) {
@@ -2034,7 +2003,7 @@ static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
     cur = 0;
     for (int t = 0; t < P; t++) {
         hipLaunchKernelGGL((k_adj_egm<VT>), grd, blk, ldsB, s, c, ctx->R, w.g, t, t == 0 ? 1 : 0, t == P - 1 ? 1 : 0, ctx->d_adj_sb, st[cur], st[cur ^ 1], pbar,
-                           reinterpret_cast<VT *>(w.partS), reinterpret_cast<VT *>(w.partM));
+                           reinterpret_cast<VT *>(w.partS.get()), reinterpret_cast<VT *>(w.partM.get()));
         cur ^= 1;
     }
     hipLaunchKernelGGL(k_adj_out, dim3((unsigned)((P * w.N + 255) / 256)), dim3(256), 0, s, P, c.n_hh, w.N, w.g.nb, ctx->d_xhh, w.partS, w.partM, w.yb1,
@@ -2058,12 +2027,12 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     const Consts &c = ctx->c;
     const size_t P = c.P;
     CotWork *w = nullptr;
-    int rc = tan_cache_get(ctx, ctx->cws, M, free_cotwork, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
+    int rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
     if (rc) return rc;
     if (adj_lds_dist(c, w->g, w->V) > ctx->lds_max || adj_lds_egm(c, w->g, w->V) > ctx->lds_max)
         return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_e=%d needs more LDS per workgroup than the device has", c.n_e);
     if (!w->g_A) {
-        if (!ctx->d_adj_sb) HIPC(ctx, dmalloc(&ctx->d_adj_sb, P * c.n_e * ((size_t)c.n_a + 1)));      // (the graphs hold its address)
+        if (!ctx->d_adj_sb) HIPC(ctx, ctx->d_adj_sb.alloc(P * c.n_e * ((size_t)c.n_a + 1)));      // (the graphs hold its address)
         rc = w->V == 2 ? capture_cot_graphs<double2>(ctx, *w) : capture_cot_graphs<double>(ctx, *w);
         if (rc) return rc;
     }
@@ -2120,16 +2089,12 @@ int hank_get_policy_cotangent_seq(hank_ctx *ctx, int32_t M, double *out) {
     ENTER(ctx);
     if (!ctx->cot.current || ctx->cot.M != M) return fail(ctx, HANK_ERR_NOT_READY, "no hank_vjp with M=%d is current", M);
     const size_t G = ctx->c.G, P = ctx->c.P, total = P * G * (size_t)M;
-    double *tmp = nullptr;
-    HIPC(ctx, dmalloc(&tmp, total));
-    hipLaunchKernelGGL(k_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cot.pbar, (int)G, (int)P, M, tmp);
-    hipError_t e0 = hipGetLastError();
-    hipError_t e1 = hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp);
-    HIPC(ctx, e0);
-    HIPC(ctx, e1);
-    HIPC(ctx, e2);
+    DevBuf<double> tmp;
+    HIPC(ctx, tmp.alloc(total));
+    hipLaunchKernelGGL(k_export_dpol, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cot.pbar, (int)G, (int)P, M, tmp.get());
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, hipMemcpyAsync(out, tmp, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return HANK_OK;
 }
 
@@ -2143,12 +2108,12 @@ int hank_last_vjp_timings(hank_ctx *ctx, double *out_ms, int32_t *launches) {   
 }  // extern "C"
 
 // ---- granular steps ---------------------------------------------------------------------------
-struct Scratch {  // frees its device buffers on scope exit
-    std::vector<void *> p;
-    ~Scratch() { for (void *q : p) (void)hipFree(q); }
+struct Scratch {  // a call's device buffers, of any element type: released on scope exit
+    std::vector<DevBuf<char>> p;
     template <typename T> hipError_t alloc(T **out, size_t n) {
-        hipError_t e = dmalloc(out, n);
-        if (e == hipSuccess) p.push_back(*out);
+        p.emplace_back();
+        const hipError_t e = p.back().alloc(n * sizeof(T));
+        *out = reinterpret_cast<T *>(p.back().get());
         return e;
     }
 };
@@ -2254,16 +2219,16 @@ static int hx_outputs(hank_ctx *ctx, int NX, const TanBatch *b, double **S_out, 
     const size_t P = c.P, G = c.G;
     const int nbr = (c.n_a + HX_ROWS - 1) / HX_ROWS;
     const size_t sz[8] = {NX * P * G, NX * P * G, P * NX * HX_NS, P * G * N, G * N, G * N, (size_t)N * P * nbr * NX, (size_t)N * P * NX};
-    size_t need = 0;
-    for (size_t k : sz) need += (sizeof(double) * k + 255) / 256 * 256;
+    size_t need = 0, off = 0;
+    for (size_t k : sz) carve(need, sizeof(double) * k);
     if (need > ctx->hx_bytes) {
-        if (ctx->hx_slab) { HIPC(ctx, hipStreamSynchronize(ctx->stream)); HIPC(ctx, hipFree(ctx->hx_slab)); ctx->hx_slab = nullptr; ctx->hx_bytes = 0; }
-        HIPC(ctx, hipMalloc(&ctx->hx_slab, need));
+        if (ctx->hx_slab) HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (the old slab is released by alloc)
+        ctx->hx_bytes = 0;
+        HIPC(ctx, ctx->hx_slab.alloc(need));
         ctx->hx_bytes = need;
     }
-    double *buf[8];
-    size_t off = 0;
-    for (int k = 0; k < 8; k++) { buf[k] = reinterpret_cast<double *>(ctx->hx_slab + off); off += (sizeof(double) * sz[k] + 255) / 256 * 256; }
+    double *buf[8];      // views
+    for (int k = 0; k < 8; k++) buf[k] = reinterpret_cast<double *>(ctx->hx_slab + carve(off, sizeof(double) * sz[k]));
     double *f = buf[0], *fc = buf[1], *S = buf[2];
     hipLaunchKernelGGL(k_hx_record, dim3((unsigned)P, (unsigned)NX), dim3(256), 0, ctx->stream, c, ctx->R, ctx->d_xhh, NX, f, fc, S);
     HIPC(ctx, hipGetLastError());
