@@ -82,6 +82,16 @@ def pad_N(N: int) -> int:
     raise ValueError(f"N={N} exceeds the oracle's largest compiled chunk {SUPPORTED_N[-1]}")
 
 
+def _ok(st: int) -> None:
+    if st != ORC_OK:
+        raise RuntimeError(f"oracle status {st}")
+
+
+def _cat(parts, axis):
+    """the passes' partials side by side (a single pass as it is: no copy of a full-size policy sequence)."""
+    return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=axis)
+
+
 class Oracle:
     """CPU restatement of the household block + KS residuals for one model."""
 
@@ -149,6 +159,22 @@ class Oracle:
             st = f(C.byref(self.m), P, _dp(xr), _dp(xw), _dp(xt), _dp(vT), _dp(pol))
         return st, pol.transpose(0, 2, 1, 3).copy()
 
+    def _consumption(self, xr, xw, xt, ps, N: int) -> np.ndarray:
+        """the c_grid of KrusellSmith.jl:79 as a policy, for the policy sequence ps in memory order [t][e][a][1+N]."""
+        cons = np.empty_like(ps)
+        xr, xw = np.ascontiguousarray(xr, dtype=np.float64), np.ascontiguousarray(xw, dtype=np.float64)
+        xt = None if xt is None else np.ascontiguousarray(xt, dtype=np.float64)
+        _fn("orc_consumption_policy", N)(C.byref(self.m), ps.shape[0], _dp(xr), _dp(xw), None if xt is None else _dp(xt), _dp(ps), _dp(cons))
+        return cons
+
+    def _aggregate(self, seqs, ss_init_D, N: int) -> np.ndarray:
+        """each sequence of seqs ([t][e][a][1+N]) dotted with the same D_t (ForwardIteration.jl:303-307) -> (len(seqs), P, 1+N)."""
+        seqs = np.ascontiguousarray(np.stack(seqs))
+        D0 = np.ascontiguousarray(np.asarray(ss_init_D, dtype=np.float64).reshape((self.n_a, self.n_e), order="F").T)
+        agg = np.empty(seqs.shape[:2] + (1 + N,))
+        _fn("orc_forward_iteration_het", N)(C.byref(self.m), seqs.shape[1], seqs.shape[0], _dp(seqs), _dp(D0), _dp(agg))
+        return agg
+
     def transition_step(self, policy, D_prev, N: int):
         """transition_step (ForwardIteration.jl:95-99). policy/D_prev: (n_a,n_e[,1+N])."""
         p = self._mat_to_mem(policy, N)
@@ -183,17 +209,87 @@ class Oracle:
         (BackwardIteration.jl:99-112), ForwardIteration aggregates each with the same D_t (ForwardIteration.jl:303-307).
         -> (status, agg (2, P, 1+N), policy_seq, cons_seq)."""
         st, pol = self.backward_iteration(xr, xw, ss_end_value, N, xt)
-        P = pol.shape[0]
         ps = np.ascontiguousarray(pol.transpose(0, 2, 1, 3))
-        cons = np.empty_like(ps)
-        xr = np.ascontiguousarray(xr, dtype=np.float64); xw = np.ascontiguousarray(xw, dtype=np.float64)
-        xt_ = None if xt is None else np.ascontiguousarray(xt, dtype=np.float64)
-        _fn("orc_consumption_policy", N)(C.byref(self.m), P, _dp(xr), _dp(xw), None if xt_ is None else _dp(xt_), _dp(ps), _dp(cons))
-        seqs = np.ascontiguousarray(np.stack([ps, cons]))
-        D0 = np.ascontiguousarray(np.asarray(ss_init_D, dtype=np.float64).reshape((self.n_a, self.n_e), order="F").T)
-        agg = np.empty((2, P, 1 + N))
-        _fn("orc_forward_iteration_het", N)(C.byref(self.m), P, 2, _dp(seqs), _dp(D0), _dp(agg))
-        return st, agg, pol, cons.transpose(0, 2, 1, 3).copy()
+        cons = self._consumption(xr, xw, xt, ps, N)
+        return st, self._aggregate([ps, cons], ss_init_D, N), pol, cons.transpose(0, 2, 1, 3).copy()
+
+    # ---- the references of the GPU suite: seeded, checked, partials split from the value ----
+    @staticmethod
+    def _seeded(xhh, y):
+        """xhh (n_hh, P) with the partials y (n_hh, P, N), or None for the value alone -> per pass (n, Nc, xd): n partials in a
+        dual xd (n_hh, P, 1 + Nc) of the compiled width Nc = pad_N(n); at most SUPPORTED_N[-1] partials per pass."""
+        xhh = np.asarray(xhh, dtype=np.float64)
+        N = 0 if y is None else y.shape[2]
+        for c0 in range(0, max(N, 1), SUPPORTED_N[-1]):
+            n = min(N, c0 + SUPPORTED_N[-1]) - c0
+            xd = np.zeros(xhh.shape + (1 + pad_N(n),))
+            xd[..., 0] = xhh
+            if n:
+                xd[..., 1:1 + n] = y[:, :, c0:c0 + n]
+            yield n, xd.shape[2] - 1, xd
+
+    def block(self, xhh, y, value, D):
+        """household_block at xhh (n_hh, P) with the partials y (n_hh, P, N), or y=None for the value alone; row 2 of xhh / y is
+        the transfer path when n_hh > 2. -> agg (P,), dagg (P, N), policy (P, n_a, n_e), dpolicy (P, n_a, n_e, N)."""
+        dagg, dpol = [], []
+        for n, Nc, xd in self._seeded(xhh, y):
+            st, oa, op = self.household_block(xd[0], xd[1], value, D, Nc, xd[2] if len(xd) > 2 else None)
+            _ok(st)
+            agg, pol = oa[:, 0], op[..., 0]
+            dagg.append(oa[:, 1:1 + n]); dpol.append(op[..., 1:1 + n])
+        return agg, _cat(dagg, 1), pol, _cat(dpol, -1)
+
+    def block_het(self, xhh, y, value, D):
+        """`block` through household_block_het -> agg (2, P), dagg (2, P, N) of (savings, consumption)."""
+        dagg = []
+        for n, Nc, xd in self._seeded(xhh, y):
+            st, oa, _, _ = self.household_block_het(xd[0], xd[1], value, D, Nc, xd[2] if len(xd) > 2 else None)
+            _ok(st)
+            agg = oa[..., 0]
+            dagg.append(oa[..., 1:1 + n])
+        return agg, _cat(dagg, 2)
+
+    def het_outputs(self, xhh, y, value, D, n_het, gamma):
+        """agg (n_het, P), dagg (n_het, P, N) of (savings, consumption, Value[, UCE]) under the dual arithmetic, one pass. The
+        reference dots every key of the value function's NamedTuple with the same post-transition D_t (BackwardIteration.jl:99-112,
+        ForwardIteration.jl:303-307): Value is the reference's ValueFunction itself, once per period backward
+        (BackwardIteration.jl:90-113); UCE = z_e c^-γ of the one-asset HANK family, c^-γ and its partials by the chain rule."""
+        (n, Nc, xd), = self._seeded(xhh, y)
+        P, xt = xd.shape[1], xd[2] if len(xd) > 2 else None
+        st, pol = self.backward_iteration(xd[0], xd[1], value, Nc, xt)
+        _ok(st)
+        V = np.empty((P, self.n_a, self.n_e, 1 + Nc))
+        Vn = np.asarray(value, dtype=np.float64)
+        for t in range(P - 1, -1, -1):
+            st, Vt, KD = self.value_function(Vn, xd[0, t], xd[1, t], Nc, None if xt is None else xt[t])
+            _ok(st)
+            err = np.max(np.abs(KD - pol[t]))
+            assert err <= 1e-12 + 1e-12 * np.abs(pol[t]).max(), f"period {t}: the policies of value_function and backward_iteration differ by {err:.3e}"
+            V[t], Vn = Vt, Vt
+        ps = np.ascontiguousarray(pol.transpose(0, 2, 1, 3))                       # [t][e][a][1+N]
+        cons = self._consumption(xd[0], xd[1], xt, ps, Nc)
+        seqs = [ps, cons, np.ascontiguousarray(V.transpose(0, 2, 1, 3))]
+        if n_het > 3:
+            c0 = cons[..., 0]
+            u = np.empty_like(cons)
+            u[..., 0] = c0 ** (-gamma)
+            u[..., 1:] = (-gamma * c0 ** (-gamma - 1.0))[..., None] * cons[..., 1:]
+            seqs.append(self.z[None, :, None, None] * u)
+        agg = self._aggregate(seqs[:n_het], D, Nc)
+        return agg[..., 0], agg[..., 1:1 + n]
+
+    def vfi(self, shape, r, w, tol, cap=20_000):
+        """the reference's inner fixed point (SteadyState.jl:132-141) on ValueFunction: value <- value_fn(value).Value from ones
+        until max|new - old| < tol -> (value, policy, steps, per-step sup-norms)."""
+        value, norms = np.ones(shape), []
+        for k in range(1, cap + 1):
+            st, V, KD = self.value_function(value, r, w, 1)
+            _ok(st)
+            norms.append(float(np.max(np.abs(V[..., 0] - value))))
+            value = V[..., 0]
+            if norms[-1] < tol:
+                return value, KD[..., 0], k, norms
+        raise RuntimeError(f"oracle VFI did not converge in {cap} steps")
 
     def ks_full_function(self, x, Z, alpha, delta, KS_ss_start, ss_end_value, ss_init_D, N: int):
         """fullFunction of y_Iteration for KrusellSmith.yaml (NewtonRaphson.jl:77-83).
@@ -229,8 +325,7 @@ class Oracle:
         xd[..., 0] = np.asarray(x, dtype=np.float64).reshape(4, P, order="F") if np.asarray(x).ndim == 1 else x
         xd[..., 1:1 + Nreq] = y
         st, F, _ = self.ks_full_function(xd, Z, alpha, delta, KS_ss_start, ss_end_value, ss_init_D, N)
-        if st != ORC_OK:
-            raise RuntimeError(f"oracle status {st}")
+        _ok(st)
         Fv = F[..., 0].reshape(-1, order="F")
         J = F[..., 1:1 + Nreq].reshape(4 * P, Nreq, order="F")
         return Fv, J

@@ -15,7 +15,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
 import hank_amd as h  # noqa: E402
-import vjp_cases as vc  # noqa: E402
+import cases as vc  # noqa: E402
 from conftest import ks_setup  # noqa: E402
 from test_gpu_lifetime import SCHEDULES, _inputs, _use_everything  # noqa: E402
 

@@ -1,11 +1,14 @@
-"""Case builders shared by the GPU variant suites (tests/test_gpu_variants.py, tests/test_gpu_vjp.py,
-tests/test_gpu_vjp_variants.py) and by the CPU test of the edge economies' preconditions (tests/test_vjp_host.py). Nothing here
-needs a GPU except `block`, which creates a device context.
+"""The one case module of the suite: what the GPU modules (tests/test_gpu_*.py) and the CPU tests of their preconditions
+(tests/test_vjp_host.py, tests/test_cases_host.py) share. Nothing here needs a GPU except `raw_block` / `block`, which create a
+device context.
 
+0. the owners: `close` (the suite's only tolerance function), `raw_block` / `block` (a context under HANK_* variables, every
+   variable restored), `model_args` / `oracle_of` (a model's constructor arguments), `hank_economy` / `hank_x` (the one-asset HANK
+   economy and its input path). The oracle's references are methods of oracle.oracle.Oracle: block, block_het, het_outputs, vfi;
 1. the references of hank_vjp: the CPU oracle's Jacobian from unit tangents (`oracle_jacobian`, transposed by `jt`) and the numpy
    restatement of the reference's ForwardIteration_pullback for Sweep A alone (`forward_iteration_pullback`);
 2. the economies of the variant suite: `economy` (a curvature, its own host steady state), `shape` (a grid shape with a cheap
-   valid boundary), `CASES` (curvature x record layout), `block` (a context under HANK_* variables);
+   valid boundary), `CASES` (curvature x record layout);
 3. raw-grid economies (`raw_economy`, `EDGE_GRIDS`) whose oracle policy holds the data-dependent edges the calibrated grids never
    show — a deep clamped prefix, many sources clamped at the top, long runs of rows in one bracket — and `edge_stats`, which
    measures those edges on a policy."""
@@ -17,7 +20,8 @@ from conftest import ROOT, ks_paths, ks_setup
 
 
 def close(a, b, rel=1e-10, ab=1e-12, what=""):
-    """the suite's tolerance: rel 1e-10 + abs 1e-12 on the largest entry of the reference; prints the figure before it asserts."""
+    """the suite's tolerance: rel 1e-10 + abs 1e-12 on the largest entry of the reference b, no floor on that scale; equal shapes
+    (nothing broadcasts); prints the figure before it asserts. A NaN on either side fails it."""
     a, b = np.asarray(a), np.asarray(b)
     assert a.shape == b.shape, (what, a.shape, b.shape)
     err, scale = np.max(np.abs(a - b)), np.abs(b).max()
@@ -25,24 +29,81 @@ def close(a, b, rel=1e-10, ab=1e-12, what=""):
     assert err <= ab + rel * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
 
 
+def raw_block(hank, args, schedule, **env):
+    """hank.HouseholdBlock(*args) created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
+    env = {"HANK_SCHEDULE": schedule, **env}
+    old = {k: os.environ.get(k) for k in env}
+    for k, v in env.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = str(v)
+    try:
+        return hank.HouseholdBlock(*args)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def raw_args(grid, z, Pi, m, T):
+    """the raw HouseholdBlock constructor's arguments for model m's preferences on (grid, z, Pi)."""
+    return (grid, z, Pi, m.params.β, m.params.γ, m.params.borrow_cons, T, m.value_fn.value_fn_id)
+
+
+def model_args(m):
+    """the eight constructor arguments of hank.HouseholdBlock for model m."""
+    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
+    return raw_args(wd.grid, pd_.grid, pd_.transition, m, m.compspec.T)
+
+
+def oracle_of(m):
+    """the CPU oracle of model m's household block."""
+    from oracle.oracle import Oracle
+    return Oracle(*model_args(m)[:6])
+
+
+def block(hank, m, schedule, **env):
+    """a context of model m created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
+    return raw_block(hank, model_args(m), schedule, **env)
+
+
+_HANK = {}
+
+
+def hank_economy(n_a, n_e, T, spec="one_asset_hank.yaml"):
+    """(model, steady state) of examples.solve_hank.build, cached per size and model file."""
+    key = (n_a, n_e, T, spec)
+    if key not in _HANK:
+        from examples.solve_hank import build
+        _HANK[key] = build(n_a, n_e, T, spec)
+    return _HANK[key]
+
+
+def hank_x(ss, P):
+    """the household inputs (r, om, Tr) (3, P) of the one-asset HANK tests: geometric deviations from the steady state."""
+    t = np.arange(P)
+    return np.stack([ss.vars["r"] + 0.002 * 0.8 ** t, ss.vars["om"] * (1 + 0.01 * 0.7 ** t), ss.vars["Tr"] * (1 - 0.02 * 0.9 ** t)])
+
+
 # ---- 1. references --------------------------------------------------------------------------------------------------------
+def unit_tangents(n_hh, P):
+    """y (n_hh, P, n_hh P): a unit shock to input k at period s in column k + n_hh s (the layout of dxhh)."""
+    y = np.zeros((n_hh, P, n_hh * P))
+    for s in range(P):
+        for k in range(n_hh):
+            y[k, s, k + n_hh * s] = 1.0
+    return y
+
+
 def oracle_jacobian(orc, value, D, x):
     """J (2, P, n_hh, P): d (savings, consumption aggregate)_t / d input k at period s, from unit tangents through the CPU
-    oracle's two-variable household block, 32 columns per pass."""
+    oracle's two-variable household block."""
     n_hh, P = x.shape
-    J = np.zeros((2, P, n_hh, P))
-    cols = [(k, s) for s in range(P) for k in range(n_hh)]
-    for c0 in range(0, len(cols), 32):
-        chunk = cols[c0:c0 + 32]
-        xd = np.zeros((n_hh, P, 33))
-        xd[..., 0] = x
-        for j, (k, s) in enumerate(chunk):
-            xd[k, s, 1 + j] = 1.0
-        st, agg, _, _ = orc.household_block_het(xd[0], xd[1], value, D, 32, xt=xd[2] if n_hh > 2 else None)
-        assert st == 0
-        for j, (k, s) in enumerate(chunk):
-            J[:, :, k, s] = agg[:, :, 1 + j]
-    return J
+    _, dagg = orc.block_het(x, unit_tangents(n_hh, P), value, D)
+    return np.ascontiguousarray(dagg.reshape(2, P, P, n_hh).transpose(0, 1, 3, 2))
 
 
 def jt(J, yb):
@@ -84,37 +145,6 @@ CASES = {
 }
 
 
-def raw_block(hank, args, schedule, **env):
-    """hank.HouseholdBlock(*args) created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
-    env = {"HANK_SCHEDULE": schedule, **env}
-    old = {k: os.environ.get(k) for k in env}
-    for k, v in env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        return hank.HouseholdBlock(*args)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def block(hank, m, schedule, **env):
-    """a context of model m created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    return raw_block(hank, (wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                            m.value_fn.value_fn_id), schedule, **env)
-
-
-def hank_x(ss, P):
-    t = np.arange(P)
-    return np.stack([ss.vars["r"] + 0.002 * 0.8 ** t, ss.vars["om"] * (1 + 0.01 * 0.7 ** t), ss.vars["Tr"] * (1 - 0.02 * 0.9 ** t)])
-
-
 _ECON = {}
 
 
@@ -124,7 +154,6 @@ def economy(family, gamma):
     key = (family, gamma)
     if key not in _ECON:
         import hank_amd as h
-        from oracle.oracle import Oracle
         spec, n_a = ("krusell_smith.yaml", 130) if family == "ks" else ("one_asset_hank.yaml", 80)
         m = h.build_model_from_yaml(str(ROOT / "examples" / spec), overrides={"T": 40, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": 3}}})
         m.params.γ = gamma
@@ -135,9 +164,7 @@ def economy(family, gamma):
         assert m.params.γ == gamma
         P = m.compspec.T - 1
         xhh = ks_paths(m, ss, "x1", 0.05)[0][2:4] if family == "ks" else hank_x(ss, P)
-        wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        _ECON[key] = (m, ss, np.ascontiguousarray(xhh), Oracle(wd.grid, pdm.grid, pdm.transition, gamma=gamma, beta=m.params.β,
-                                                               borrow_cons=m.params.borrow_cons))
+        _ECON[key] = (m, ss, np.ascontiguousarray(xhh), oracle_of(m))
     return _ECON[key]
 
 
@@ -150,7 +177,6 @@ def shape(n_a, n_e, T):
     key = (n_a, n_e, T)
     if key not in _SHAPE:
         import hank_amd as h
-        from oracle.oracle import Oracle
         m = h.build_model_from_yaml(str(ROOT / "examples" / "krusell_smith.yaml"),
                                     overrides={"T": T, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": n_e}}})
         assert m.params.γ == 2.0
@@ -163,8 +189,7 @@ def shape(n_a, n_e, T):
         P = T - 1
         t = np.arange(1, P + 1)
         xhh = np.stack([xv["r"] + 0.004 * 0.8 ** t, xv["w"] * (1.0 + 0.01 * 0.8 ** t)])
-        wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        _SHAPE[key] = (m, V, D, xhh, Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons))
+        _SHAPE[key] = (m, V, D, xhh, oracle_of(m))
     return _SHAPE[key]
 
 
@@ -202,15 +227,8 @@ def fullsize_oracle_columns():
         P = xhh.shape[1]
         y = np.random.default_rng(0).standard_normal((2, P, 32))
 
-        def cols(c0):
-            xd = np.zeros((2, P, 9))
-            xd[..., 0] = xhh
-            xd[..., 1:] = y[:, :, c0:c0 + 8]
-            st, agg, _, _ = orc.household_block_het(xd[0], xd[1], ss.value, ss.D, 8)
-            assert st == 0
-            return agg[:, :, 1:]
         with ThreadPoolExecutor(max_workers=4) as ex:
-            Jy = np.concatenate(list(ex.map(cols, range(0, 32, 8))), axis=2)
+            Jy = np.concatenate(list(ex.map(lambda c0: orc.block_het(xhh, y[:, :, c0:c0 + 8], ss.value, ss.D)[1], range(0, 32, 8))), axis=2)
         _FULL["case"] = (m, ss, xhh, y, Jy)
     return _FULL["case"]
 
@@ -227,11 +245,6 @@ EDGE_NEEDS = {"dense-bottom": ("clo", "runs"), "short-top": ("top",), "both": ("
 EDGE_WIDTHS = (1, 4, 32, 33)          # hank_vjp's batch widths on these economies: R = 64, 32, 8, 8 rows per block
 EDGE_P = 9
 _RAW = {}
-
-
-def raw_args(grid, z, Pi, m, T):
-    """the raw HouseholdBlock constructor's arguments for model m's preferences on (grid, z, Pi)."""
-    return (grid, z, Pi, m.params.β, m.params.γ, m.params.borrow_cons, T, m.value_fn.value_fn_id)
 
 
 def raw_economy(name):
@@ -251,16 +264,6 @@ def raw_economy(name):
         _RAW[name] = dict(args=raw_args(grid, pdm.grid, pdm.transition, m, EDGE_P + 1), grid=grid, Pi=np.asarray(pdm.transition), V=V, D=D,
                           x=x, orc=orc)
     return _RAW[name]
-
-
-def oracle_policy(orc, V, x):
-    """the oracle's policy sequence (P, n_a, n_e) at the inputs x (2, P)."""
-    P = x.shape[1]
-    xd = np.zeros((2, P, 2))
-    xd[..., 0] = x
-    st, pol = orc.backward_iteration(xd[0], xd[1], V, 1)
-    assert st == 0
-    return pol[..., 0]
 
 
 def edge_stats(grid, pol):

@@ -24,7 +24,7 @@ def _draws(N, seed):
         yield v1, rng.uniform(0.1, 2.0, N) * rng.choice([-1.0, 1.0], N), v2, rng.uniform(0.1, 2.0, N) * rng.choice([-1.0, 1.0], N), pr
 
 
-def _close(a, b):
+def _isapprox(a, b):
     np.testing.assert_allclose(a, b, rtol=1e-13, atol=1e-15)
 
 
@@ -33,14 +33,14 @@ def test_oracle_division_and_power_meet_the_references_identities(oracle_mod, N)
     B = oracle_mod.dual_binop
     for v1, p1, v2, p2, pr in _draws(N, 10 + N):
         x, y = np.r_[v1, p1], np.r_[v2, p2]
-        _close(B(3, x, y, N), np.r_[v1 / v2, p1 * (1.0 / v2) + p2 * (-(v1 / (v2 * v2)))])       # :431
-        _close(B(3, x, np.r_[pr, np.zeros(N)], N), np.r_[v1 / pr, p1 / pr])                      # :432 (a Real is a Dual with zero partials)
-        _close(B(6, np.r_[pr, np.zeros(N)], x, N), np.r_[pr / v1, (-(pr) / v1 ** 2) * p1])       # :433
+        _isapprox(B(3, x, y, N), np.r_[v1 / v2, p1 * (1.0 / v2) + p2 * (-(v1 / (v2 * v2)))])       # :431
+        _isapprox(B(3, x, np.r_[pr, np.zeros(N)], N), np.r_[v1 / pr, p1 / pr])                      # :432 (a Real is a Dual with zero partials)
+        _isapprox(B(6, np.r_[pr, np.zeros(N)], x, N), np.r_[pr / v1, (-(pr) / v1 ** 2) * p1])       # :433
         b = abs(v1)                                                                              # :443 needs log(FDNUM): positive base
         lv = np.r_[np.log(b), p1 / b]                                                            # log(FDNUM)
         ev = np.exp(pr * lv[0])
-        _close(B(7, np.r_[b, p1], np.r_[pr, np.zeros(N)], N), np.r_[ev, ev * pr * lv[1:]])       # exp(PRIMAL * log(FDNUM))
-    _close(B(7, np.r_[-2.0, 1.0, np.zeros(N - 1)], np.r_[2.0, np.zeros(N)], N)[:2], [4.0, -4.0])  # :451
+        _isapprox(B(7, np.r_[b, p1], np.r_[pr, np.zeros(N)], N), np.r_[ev, ev * pr * lv[1:]])       # exp(PRIMAL * log(FDNUM))
+    _isapprox(B(7, np.r_[-2.0, 1.0, np.zeros(N - 1)], np.r_[2.0, np.zeros(N)], N)[:2], [4.0, -4.0])  # :451
 
 
 @pytest.mark.parametrize("N", [1, 3])
@@ -49,17 +49,17 @@ def test_host_dual_division_and_power_meet_the_references_identities(hank, N):
     for v1, p1, v2, p2, pr in _draws(N, 20 + N):
         x, y = Dual(np.array(v1), p1), Dual(np.array(v2), p2)
         q = x / y
-        _close(q.v, v1 / v2); _close(q.p, p1 * (1.0 / v2) + p2 * (-(v1 / (v2 * v2))))
+        _isapprox(q.v, v1 / v2); _isapprox(q.p, p1 * (1.0 / v2) + p2 * (-(v1 / (v2 * v2))))
         q = x / pr
-        _close(q.v, v1 / pr); _close(q.p, p1 / pr)
+        _isapprox(q.v, v1 / pr); _isapprox(q.p, p1 / pr)
         q = pr / x
-        _close(q.v, pr / v1); _close(q.p, (-(pr) / v1 ** 2) * p1)
+        _isapprox(q.v, pr / v1); _isapprox(q.p, (-(pr) / v1 ** 2) * p1)
         b = abs(v1)
         q = Dual(np.array(b), p1) ** pr
         ev = np.exp(pr * np.log(b))
-        _close(q.v, ev); _close(q.p, ev * pr * p1 / b)
+        _isapprox(q.v, ev); _isapprox(q.p, ev * pr * p1 / b)
     q = Dual(np.array(-2.0), np.r_[1.0, np.zeros(N - 1)]) ** 2.0
-    _close(q.v, 4.0); assert q.p[0] == -4.0
+    _isapprox(q.v, 4.0); assert q.p[0] == -4.0
 
 
 @pytest.mark.gpu

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from cases import block, model_args, raw_block
 from conftest import ks_paths, ks_setup
 
 pytestmark = pytest.mark.gpu
@@ -38,8 +39,7 @@ def test_create_on_a_named_device_and_device_group(hank):
     P = 19
     x, _ = ks_paths(m, ss, "x1", 0.05)
     y = np.random.default_rng(4).standard_normal((2, P, 7))
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    args = (wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+    args = model_args(m)
     hb0 = hank.HouseholdBlock(*args)
     hb1 = hank.HouseholdBlock(*args, device=0)
     with pytest.raises(hank.HankHIPError, match="device"):
@@ -77,15 +77,8 @@ def test_a_failed_workspace_allocation_is_not_cached(hank):
     x, _ = ks_paths(m, ss, "x1", 0.01)
     import torch
     dev = torch.device("cuda", 0)
-    for sched in ("launch", "auto"):
-        import os
-        if sched == "launch":
-            os.environ["HANK_SCHEDULE"] = "launch"
-        try:
-            wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-            hb = hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
-        finally:
-            os.environ.pop("HANK_SCHEDULE", None)
+    for sched in ("launch", None):
+        hb = block(hank, m, sched)
         hb.set_boundary(ss.value, ss.D)
         agg = hb.primal(x[2:4])
         N = 8192                    # dpol: 299 * 22000 * 8192 * 8 B = 431 GB > 288 GB
@@ -106,9 +99,9 @@ def test_a_long_horizon_goes_to_the_launches(hank):
     the per-period launches (which take any T) instead of failing at the launch. T = 6000 at 130x3: the Float64 sweeps need
     8*(3*64 + 9 + 130 + 4*5999) + 64 = 194 KB > 160 KB."""
     m, ss, _ = ks_setup(130, 3, 20)
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
     T = 6000
-    hb = hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, T)
+    args = (*model_args(m)[:6], T)
+    hb = hank.HouseholdBlock(*args)
     assert hb.stats()["schedule"] == 0
     hb.set_boundary(ss.value, ss.D)
     P = T - 1
@@ -119,9 +112,4 @@ def test_a_long_horizon_goes_to_the_launches(hank):
     assert np.isfinite(hb.jvp(y)).all()
     hb.close()
     with pytest.raises(hank.HankHIPError, match="LDS"):
-        import os
-        os.environ["HANK_SCHEDULE"] = "xcd"
-        try:
-            hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, T)
-        finally:
-            os.environ.pop("HANK_SCHEDULE", None)
+        raw_block(hank, args, "xcd")

@@ -8,71 +8,19 @@ entry, the bar of test_gpu_jacobian.py."""
 import numpy as np
 import pytest
 
+from cases import hank_economy, model_args, oracle_of
 from conftest import ROOT, ks_setup
 
 pytestmark = pytest.mark.gpu
 
-_CACHE = {}
-
-
-def _close(a, b, rel=1e-10, ab=1e-12):
-    a, b = np.asarray(a), np.asarray(b)
-    err = np.max(np.abs(a - b))
-    assert err <= ab + rel * np.abs(b).max(), f"max err {err:.3e} vs scale {np.abs(b).max():.3e}"
-
-
-def _oracle_outputs(orc, gamma, ss, x, y, n_het):
-    """x (n_hh, P), y (n_hh, P, N) -> agg (n_het, P), dagg (n_het, P, N) of (savings, consumption, Value[, UCE]) under the
-    oracle's dual arithmetic: Value from the reference's ValueFunction once per period backward, UCE = z_e c^-γ by the chain
-    rule, each aggregated by orc_forward_iteration_het (the restatement of test_gpu_het_nonaffine._oracle_outputs)."""
-    from oracle.oracle import _dp, _fn, pad_N
-    import ctypes as C
-    n_hh, P, N = y.shape
-    Nc = pad_N(N)
-    xd = np.zeros((n_hh, P, 1 + Nc))
-    xd[..., 0] = x
-    xd[..., 1:1 + N] = y
-    xt = xd[2] if n_hh > 2 else None
-    st, pol = orc.backward_iteration(xd[0], xd[1], ss.value, Nc, xt)
-    assert st == 0
-    V = np.empty((P, orc.n_a, orc.n_e, 1 + Nc))
-    Vn = np.asarray(ss.value, dtype=np.float64)
-    for t in range(P - 1, -1, -1):
-        st, Vt, KD = orc.value_function(Vn, xd[0, t], xd[1, t], Nc, None if xt is None else xt[t])
-        assert st == 0
-        _close(KD, pol[t], 1e-12)
-        V[t], Vn = Vt, Vt
-    ps = np.ascontiguousarray(pol.transpose(0, 2, 1, 3))                       # [t][e][a][1+N]
-    cons = np.empty_like(ps)
-    _fn("orc_consumption_policy", Nc)(C.byref(orc.m), P, _dp(np.ascontiguousarray(xd[0])), _dp(np.ascontiguousarray(xd[1])),
-                                      None if xt is None else _dp(np.ascontiguousarray(xt)), _dp(ps), _dp(cons))
-    seqs = [ps, cons, np.ascontiguousarray(V.transpose(0, 2, 1, 3))]
-    if n_het > 3:
-        c0 = cons[..., 0]
-        u = np.empty_like(cons)
-        u[..., 0] = c0 ** (-gamma)
-        u[..., 1:] = (-gamma * c0 ** (-gamma - 1.0))[..., None] * cons[..., 1:]
-        seqs.append(orc.z[None, :, None, None] * u)
-    seqs = np.ascontiguousarray(np.stack(seqs))
-    D0 = np.ascontiguousarray(np.asarray(ss.D, dtype=np.float64).reshape((orc.n_a, orc.n_e), order="F").T)
-    agg = np.empty((n_het, P, 1 + Nc))
-    _fn("orc_forward_iteration_het", Nc)(C.byref(orc.m), P, n_het, _dp(seqs), _dp(D0), _dp(agg))
-    return agg[..., 0], agg[..., 1:1 + N]
-
-
-def _hank_model(n_a, n_e, T, spec="one_asset_hank_goods.yaml"):
-    key = (spec, n_a, n_e, T)
-    if key not in _CACHE:
-        from examples.solve_hank import build
-        _CACHE[key] = build(n_a, n_e, T, spec)
-    return _CACHE[key]
+GOODS = "one_asset_hank_goods.yaml"
 
 
 def _setup(family, n_a, n_e, T):
     """model, steady state, the constant steady-state household inputs (n_hh, P) and the family's output count."""
     from hank_amd.BackwardIteration import household_inputs
     from hank_amd.GeneralStructures import vars_of_type
-    m, ss = ks_setup(n_a, n_e, T)[:2] if family == "ks" else _hank_model(n_a, n_e, T)
+    m, ss = ks_setup(n_a, n_e, T)[:2] if family == "ks" else hank_economy(n_a, n_e, T, GOODS)
     P = m.compspec.T - 1
     x_ss = np.tile(np.array([ss.vars[k] for k in vars_of_type(m, "endogenous")]), P)
     exog = {k: np.full(P, float(ss.vars[k])) for k in vars_of_type(m, "exogenous")}
@@ -80,10 +28,8 @@ def _setup(family, n_a, n_e, T):
     return m, ss, xhh, len(m.value_fn.outputs)
 
 
-def _block(hank, m, ss, xhh):
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    hb = hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                             m.value_fn.value_fn_id)
+def _at_the_steady_state(hank, m, ss, xhh):
+    hb = hank.HouseholdBlock(*model_args(m))
     hb.set_boundary(ss.value, ss.D)
     hb.primal(xhh)
     return hb
@@ -117,7 +63,7 @@ def _check_columns(F, Dv, cols, dagg, what):
 def test_output_0_is_fake_news_bit_for_bit(hank, family, n_a, n_e, T):
     m, ss, xhh, n_max = _setup(family, n_a, n_e, T)
     P, n_hh = m.compspec.T - 1, xhh.shape[0]
-    hb = _block(hank, m, ss, xhh)
+    hb = _at_the_steady_state(hank, m, ss, xhh)
     F0, Dv0 = hb.fake_news()
     last = None
     for n in range(1, n_max + 1):
@@ -144,7 +90,7 @@ def test_every_output_against_unit_tangents(hank, family, n_a, n_e, T):
     """household_jacobian of each output against hb.jvp + hb.het_outputs of unit tangents at the same stationary primal."""
     m, ss, xhh, n_max = _setup(family, n_a, n_e, T)
     P, n_hh = m.compspec.T - 1, xhh.shape[0]
-    hb = _block(hank, m, ss, xhh)
+    hb = _at_the_steady_state(hank, m, ss, xhh)
     F, Dv = hb.fake_news_het(n_max)
     cols, y = _unit_tangents(n_hh, P)
     hb.set_het_outputs(n_max)
@@ -158,16 +104,13 @@ def test_every_output_against_unit_tangents(hank, family, n_a, n_e, T):
 @pytest.mark.parametrize("family,n_a,n_e,T", [("ks", 130, 3, 20), ("hank", 80, 3, 40)])
 def test_every_output_against_the_oracle(hank, family, n_a, n_e, T):
     """the same columns against the CPU oracle's unit-tangent outputs (savings, consumption, Value[, UCE])."""
-    from oracle.oracle import Oracle
     m, ss, xhh, n_max = _setup(family, n_a, n_e, T)
     P, n_hh = m.compspec.T - 1, xhh.shape[0]
-    hb = _block(hank, m, ss, xhh)
+    hb = _at_the_steady_state(hank, m, ss, xhh)
     F, Dv = hb.fake_news_het(n_max)
     hb.close()
     cols, y = _unit_tangents(n_hh, P)
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    orc = Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
-    _, odagg = _oracle_outputs(orc, m.params.γ, ss, xhh, y, n_max)
+    _, odagg = oracle_of(m).het_outputs(xhh, y, ss.value, ss.D, n_max, m.params.γ)
     _check_columns(F, Dv, cols, odagg, f"oracle {family} {n_a}x{n_e} T={T}")
 
 
@@ -190,9 +133,9 @@ def test_toeplitz_jacobian_of_multi_output_models_equals_the_columns(hank, model
     toeplitz call."""
     import hank_amd.parallel as par
     if model == "goods":
-        m, ss = _hank_model(80, 3, 40)
+        m, ss = hank_economy(80, 3, 40, GOODS)
     elif model == "wages":
-        m, ss = _hank_model(200, 5, 80, "one_asset_hank_wages.yaml")
+        m, ss = hank_economy(200, 5, 80, "one_asset_hank_wages.yaml")
     else:
         m, ss = _ks_value_model(hank, tmp_path, 130, 3, 40)
     assert len(hank.vars_of_type(m, "heterogeneous")) > 1
@@ -212,7 +155,7 @@ def test_toeplitz_jacobian_of_multi_output_models_equals_the_columns(hank, model
 
 
 def test_newton_on_the_wage_model_does_not_depend_on_the_jacobian_branch(hank):
-    m, ss = _hank_model(200, 5, 80, "one_asset_hank_wages.yaml")
+    m, ss = hank_economy(200, 5, 80, "one_asset_hank_wages.yaml")
     P = m.compspec.T - 1
     ei = {"ei": 0.0025 * 0.6 ** np.arange(P)}
     x0 = np.tile(np.array([ss.vars[k] for k in hank.vars_of_type(m, "endogenous")]), P)
@@ -227,9 +170,7 @@ def test_newton_on_the_wage_model_does_not_depend_on_the_jacobian_branch(hank):
 def test_fake_news_het_refuses_what_fake_news_refuses(hank, family, n_a, n_e, T):
     m, ss, xhh, n_max = _setup(family, n_a, n_e, T)
     P = m.compspec.T - 1
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    hb = hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                             m.value_fn.value_fn_id)
+    hb = hank.HouseholdBlock(*model_args(m))
     hb.set_boundary(ss.value, ss.D)
     for n in (0, n_max + 1):                 # outside 1..3 (Krusell-Smith) / 1..4 (one-asset HANK)
         with pytest.raises(hank.HankHIPError):

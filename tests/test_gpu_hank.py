@@ -2,60 +2,34 @@
 inputs r, om, Tr). NOT in the reference: parity is unpinned by construction — the GPU path is
 checked against the oracle's restatement of the same family, against central differences, and by solving the
 perfect-foresight response to a monetary shock. Tolerance as for the KS family: rel 1e-10 + abs 1e-12."""
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
+from cases import close, hank_economy, hank_x, oracle_of
+
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-
-
-def close(a, b, rel=1e-10, abs_=1e-12):
-    a, b = np.asarray(a), np.asarray(b)
-    scale = max(np.max(np.abs(b)), 1e-300)
-    err = np.max(np.abs(a - b))
-    assert err <= abs_ + rel * scale, f"max err {err:.3e} vs scale {scale:.3e}"
 
 
 @pytest.fixture(scope="module")
 def hank_model():
-    from examples.solve_hank import build
-    return build(80, 3, 40)
-
-
-def _paths(m, ss, P, seed=0):
-    rng = np.random.default_rng(seed)
-    t = np.arange(P)
-    x = np.stack([ss.vars["r"] + 0.002 * 0.8 ** t, ss.vars["om"] * (1 + 0.01 * 0.7 ** t), ss.vars["Tr"] * (1 - 0.02 * 0.9 ** t)])
-    return x, rng
+    return hank_economy(80, 3, 40)
 
 
 @pytest.mark.parametrize("N", [1, 4, 32])
 def test_household_block_matches_oracle(hank, hank_model, N):
-    from oracle.oracle import Oracle, pad_N
     m, ss = hank_model
     P = m.compspec.T - 1
-    x, rng = _paths(m, ss, P)
-    y = rng.standard_normal((3, P, N))
+    x = hank_x(ss, P)
+    y = np.random.default_rng(0).standard_normal((3, P, N))
     hb = hank.household_block(m)
     assert hb.n_hh == 3
     hb.set_boundary(ss.value, ss.D)
     agg, dagg = hb.primal_jvp(x, y)
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    orc = Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
-    Nc = pad_N(N)
-    xd = np.zeros((3, P, 1 + Nc))
-    xd[..., 0] = x
-    xd[..., 1:1 + N] = y
-    st, oagg, opol = orc.household_block(xd[0], xd[1], ss.value, ss.D, Nc, xt=xd[2])
-    assert st == 0
-    close(agg, oagg[:, 0])
-    close(dagg, oagg[:, 1:1 + N])
-    close(hb.policy_seq().transpose(2, 0, 1), opol[..., 0])
-    close(hb.dpolicy_seq(N).transpose(2, 0, 1, 3), opol[..., 1:1 + N])
+    oagg, odagg, opol, odpol = oracle_of(m).block(x, y, ss.value, ss.D)
+    close(agg, oagg)
+    close(dagg, odagg)
+    close(hb.policy_seq().transpose(2, 0, 1), opol)
+    close(hb.dpolicy_seq(N).transpose(2, 0, 1, 3), odpol)
     # hank_primal, then hank_jvp: the same numbers (to the rounding of the aggregate sums: the default schedule runs these
     # two as XCD-local persistent sweeps and hank_primal_jvp as per-period launches)
     close(hb.primal(x), agg, rel=1e-13)
@@ -65,23 +39,21 @@ def test_household_block_matches_oracle(hank, hank_model, N):
 def test_transfer_tangent_against_central_differences(hank, hank_model):
     m, ss = hank_model
     P = m.compspec.T - 1
-    x, rng = _paths(m, ss, P, 1)
+    x = hank_x(ss, P)
     y = np.zeros((3, P, 1))
-    y[2, :, 0] = rng.standard_normal(P)          # a pure transfer direction
+    y[2, :, 0] = np.random.default_rng(1).standard_normal(P)          # a pure transfer direction
     hb = hank.household_block(m)
     hb.set_boundary(ss.value, ss.D)
     _, dagg = hb.primal_jvp(x, y)
     h_ = 1e-6
     fd = (hb.primal(x + h_ * y[..., 0]) - hb.primal(x - h_ * y[..., 0])) / (2 * h_)
-    close(dagg[:, 0], fd, rel=2e-6, abs_=1e-8)
+    close(dagg[:, 0], fd, rel=2e-6, ab=1e-8)
 
 
 def test_granular_step_with_transfer(hank, hank_model):
-    from oracle.oracle import Oracle
     m, ss = hank_model
     hb = hank.household_block(m)
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    orc = Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
+    orc = oracle_of(m)
     rng = np.random.default_rng(2)
     N = 3
     xt = np.array([ss.vars["r"], ss.vars["om"], ss.vars["Tr"]])

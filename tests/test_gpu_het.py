@@ -5,50 +5,13 @@ hank_get_het_outputs assembles (savings, consumption) from them. The reference s
 construction): the checks are the CPU oracle's two-variable household block (orc_consumption_policy +
 orc_forward_iteration_het: each variable's OWN policy dotted with D_t under the dual arithmetic), at rel 1e-10 + abs 1e-12 like
 every sweep test, the distribution path itself, and the Newton solve of the goods-market-clearing model."""
-import os
-
 import numpy as np
 import pytest
 
+from cases import block as _block, close as _close, hank_economy, hank_x, oracle_of
 from conftest import ks_paths, ks_setup
 
 pytestmark = pytest.mark.gpu
-
-
-def _block(hank, m, schedule):
-    old = os.environ.get("HANK_SCHEDULE")
-    if schedule:
-        os.environ["HANK_SCHEDULE"] = schedule
-    else:
-        os.environ.pop("HANK_SCHEDULE", None)
-    try:
-        wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        return hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                                   m.value_fn.value_fn_id)
-    finally:
-        if old is None:
-            os.environ.pop("HANK_SCHEDULE", None)
-        else:
-            os.environ["HANK_SCHEDULE"] = old
-
-
-def _close(a, b, rel=1e-10, ab=1e-12):
-    a, b = np.asarray(a), np.asarray(b)
-    err = np.max(np.abs(a - b))
-    assert err <= ab + rel * np.abs(b).max(), f"max err {err:.3e} vs scale {np.abs(b).max():.3e}"
-
-
-def _oracle_two(orc, ss, x, y):
-    """x (n_hh, P), y (n_hh, P, N) -> agg (2, P), dagg (2, P, N) of (savings, consumption)."""
-    from oracle.oracle import pad_N
-    n_hh, P, N = y.shape
-    Nc = pad_N(N)
-    xd = np.zeros((n_hh, P, 1 + Nc))
-    xd[..., 0] = x
-    xd[..., 1:1 + N] = y
-    st, agg, _, _ = orc.household_block_het(xd[0], xd[1], ss.value, ss.D, Nc, xt=xd[2] if n_hh > 2 else None)
-    assert st == 0
-    return agg[..., 0], agg[..., 1:1 + N]
 
 
 def _check(hb, x, y, oagg, odagg, family):
@@ -85,7 +48,7 @@ def test_two_outputs_krusell_smith_130x3(hank, schedule, family, N):
     x, _ = ks_paths(m, ss, "x1", 0.05)
     y = np.random.default_rng(3).standard_normal((2, P, N))
     k = min(N, 32)
-    oagg, odagg = _oracle_two(orc, ss, x[2:4], y[:, :, :k])
+    oagg, odagg = orc.block_het(x[2:4], y[:, :, :k], ss.value, ss.D)
     hb = _block(hank, m, schedule)
     hb.set_boundary(ss.value, ss.D)
     if N <= 32:
@@ -102,19 +65,13 @@ def test_two_outputs_krusell_smith_130x3(hank, schedule, family, N):
 @pytest.mark.parametrize("schedule,family", [("launch", "launch-per-period"), ("xcd", "xcd-persistent"), ("wide", "on-chip-wide")])
 def test_two_outputs_one_asset_hank_1000x7_T500(hank, schedule, family):
     """BASELINE.json configs[4]'s shape: the HANK family (three household inputs: the transfer enters consumption directly)."""
-    from examples.solve_hank import build
-    from oracle.oracle import Oracle
-    m, ss = _hank_1000x7()
+    m, ss = hank_economy(1000, 7, 500, "one_asset_hank_goods.yaml")
     P = m.compspec.T - 1
-    t = np.arange(P)
-    x = np.stack([ss.vars["r"] + 0.002 * 0.8 ** t, ss.vars["om"] * (1 + 0.01 * 0.7 ** t), ss.vars["Tr"] * (1 - 0.02 * 0.9 ** t)])
+    x = hank_x(ss, P)
     y = np.random.default_rng(5).standard_normal((3, P, 2))
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    orc = Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
-    key = "oracle"
-    if key not in _CACHE:
-        _CACHE[key] = _oracle_two(orc, ss, x, y)
-    oagg, odagg = _CACHE[key]
+    if "oracle" not in _CACHE:
+        _CACHE["oracle"] = oracle_of(m).block_het(x, y, ss.value, ss.D)
+    oagg, odagg = _CACHE["oracle"]
     hb = _block(hank, m, schedule)
     hb.set_boundary(ss.value, ss.D)
     _check(hb, x, y, oagg, odagg, family)
@@ -122,13 +79,6 @@ def test_two_outputs_one_asset_hank_1000x7_T500(hank, schedule, family):
 
 
 _CACHE = {}
-
-
-def _hank_1000x7():
-    if "model" not in _CACHE:
-        from examples.solve_hank import build
-        _CACHE["model"] = build(1000, 7, 500, "one_asset_hank_goods.yaml")
-    return _CACHE["model"]
 
 
 def test_device_pointer_form_equals_the_host_form(hank):

@@ -4,78 +4,15 @@ NamedTuple with the same post-transition D_t (BackwardIteration.jl:99-112, Forwa
 the reference's semantics with nothing added: Value from orc_value_function (the dual ValueFunction, once per period backward),
 UCE from orc_consumption_policy and dual algebra for c^-γ, each aggregated by orc_forward_iteration_het. Tolerance rel 1e-10 +
 abs 1e-12 like every sweep test."""
-import os
-
 import numpy as np
 import pytest
 
+from cases import block as _block, close as _close, hank_economy, hank_x as _hank_x, oracle_of
 from conftest import ROOT, ks_paths, ks_setup
 
 pytestmark = pytest.mark.gpu
 
-
-def _block(hank, m, schedule):
-    old = os.environ.get("HANK_SCHEDULE")
-    if schedule:
-        os.environ["HANK_SCHEDULE"] = schedule
-    else:
-        os.environ.pop("HANK_SCHEDULE", None)
-    try:
-        wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        return hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                                   m.value_fn.value_fn_id)
-    finally:
-        if old is None:
-            os.environ.pop("HANK_SCHEDULE", None)
-        else:
-            os.environ["HANK_SCHEDULE"] = old
-
-
-def _close(a, b, rel=1e-10, ab=1e-12):
-    a, b = np.asarray(a), np.asarray(b)
-    err = np.max(np.abs(a - b))
-    assert err <= ab + rel * np.abs(b).max(), f"max err {err:.3e} vs scale {np.abs(b).max():.3e}"
-
-
-def _oracle_outputs(orc, gamma, ss, x, y, n_het):
-    """x (n_hh, P), y (n_hh, P, N) -> agg (n_het, P), dagg (n_het, P, N) of (savings, consumption, Value[, UCE]) under the
-    oracle's dual arithmetic."""
-    from oracle.oracle import _dp, _fn, pad_N
-    import ctypes as C
-    n_hh, P, N = y.shape
-    Nc = pad_N(N)
-    xd = np.zeros((n_hh, P, 1 + Nc))
-    xd[..., 0] = x
-    xd[..., 1:1 + N] = y
-    xt = xd[2] if n_hh > 2 else None
-    st, pol = orc.backward_iteration(xd[0], xd[1], ss.value, Nc, xt)
-    assert st == 0
-    # Value: the reference's ValueFunction itself, once per period backward (BackwardIteration.jl:90-113)
-    V = np.empty((P, orc.n_a, orc.n_e, 1 + Nc))
-    Vn = np.asarray(ss.value, dtype=np.float64)
-    for t in range(P - 1, -1, -1):
-        st, Vt, KD = orc.value_function(Vn, xd[0, t], xd[1, t], Nc, None if xt is None else xt[t])
-        assert st == 0
-        _close(KD, pol[t], 1e-12)
-        V[t], Vn = Vt, Vt
-    ps = np.ascontiguousarray(pol.transpose(0, 2, 1, 3))                       # [t][e][a][1+N]
-    cons = np.empty_like(ps)
-    _fn("orc_consumption_policy", Nc)(C.byref(orc.m), P, _dp(np.ascontiguousarray(xd[0])), _dp(np.ascontiguousarray(xd[1])),
-                                      None if xt is None else _dp(np.ascontiguousarray(xt)), _dp(ps), _dp(cons))
-    seqs = [ps, cons, np.ascontiguousarray(V.transpose(0, 2, 1, 3))]
-    if n_het > 3:           # UCE = z_e c^-γ: c^-γ and its partials by the chain rule
-        c0 = cons[..., 0]
-        u = np.empty_like(cons)
-        u[..., 0] = c0 ** (-gamma)
-        u[..., 1:] = (-gamma * c0 ** (-gamma - 1.0))[..., None] * cons[..., 1:]
-        seqs.append(orc.z[None, :, None, None] * u)
-    seqs = np.ascontiguousarray(np.stack(seqs))
-    D0 = np.ascontiguousarray(np.asarray(ss.D, dtype=np.float64).reshape((orc.n_a, orc.n_e), order="F").T)
-    agg = np.empty((n_het, P, 1 + Nc))
-    _fn("orc_forward_iteration_het", Nc)(C.byref(orc.m), P, n_het, _dp(seqs), _dp(D0), _dp(agg))
-    return agg[..., 0], agg[..., 1:1 + N]
-
-
+GOODS = "one_asset_hank_goods.yaml"
 _CACHE = {}
 
 
@@ -89,7 +26,7 @@ def test_value_krusell_smith_130x3(hank, schedule, family, N):
     k = min(N, 32)
     key = ("ks130", N)
     if key not in _CACHE:
-        _CACHE[key] = _oracle_outputs(orc, m.params.γ, ss, x[2:4], y[:, :, :k], 3)
+        _CACHE[key] = orc.het_outputs(x[2:4], y[:, :, :k], ss.value, ss.D, 3, m.params.γ)
     oagg, odagg = _CACHE[key]
     hb = _block(hank, m, schedule)
     hb.set_boundary(ss.value, ss.D)
@@ -118,29 +55,13 @@ def test_value_krusell_smith_130x3(hank, schedule, family, N):
     hb.close()
 
 
-def _hank_model(n_a, n_e, T):
-    key = ("hank", n_a, n_e, T)
-    if key not in _CACHE:
-        from examples.solve_hank import build
-        _CACHE[key] = build(n_a, n_e, T, "one_asset_hank_goods.yaml")
-    return _CACHE[key]
-
-
-def _hank_x(ss, P):
-    t = np.arange(P)
-    return np.stack([ss.vars["r"] + 0.002 * 0.8 ** t, ss.vars["om"] * (1 + 0.01 * 0.7 ** t), ss.vars["Tr"] * (1 - 0.02 * 0.9 ** t)])
-
-
 @pytest.mark.parametrize("n_a,n_e,T", [(130, 3, 60), (1000, 7, 500)])
 def test_value_and_uce_one_asset_hank(hank, n_a, n_e, T):
-    from oracle.oracle import Oracle
-    m, ss = _hank_model(n_a, n_e, T)
+    m, ss = hank_economy(n_a, n_e, T, GOODS)
     P = m.compspec.T - 1
     x = _hank_x(ss, P)
     y = np.random.default_rng(5).standard_normal((3, P, 4))
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    orc = Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
-    oagg, odagg = _oracle_outputs(orc, m.params.γ, ss, x, y, 4)
+    oagg, odagg = oracle_of(m).het_outputs(x, y, ss.value, ss.D, 4, m.params.γ)
     hb = _block(hank, m, None)
     hb.set_boundary(ss.value, ss.D)
     hb.set_het_outputs(4)
@@ -179,7 +100,7 @@ def test_value_full_size_dual_pass(hank):
     hb.primal_jvp(x[2:4], y)
     a3, d3 = hb.het_outputs(3, y)
     assert np.array_equal(a3[:, :2], a2) and np.array_equal(d3[:, :2, :], d2)
-    oagg, odagg = _oracle_outputs(orc, m.params.γ, ss, x[2:4], y[:, :, :4], 3)
+    oagg, odagg = orc.het_outputs(x[2:4], y[:, :, :4], ss.value, ss.D, 3, m.params.γ)
     _close(a3[:, 2], oagg[2])
     _close(d3[:, 2, :4], odagg[2])
     hb.close()
@@ -257,7 +178,7 @@ def test_reference_shaped_api_with_value(hank, tmp_path):
     from hank_amd.BackwardIteration import household_inputs
     _, dxhh = household_inputs(xd, {"Z": Z}, m)
     dxhh = np.asarray(dxhh)
-    oagg, odagg = _oracle_outputs(orc, m.params.γ, ss, x[2:4], dxhh, 3)
+    oagg, odagg = orc.het_outputs(x[2:4], dxhh, ss.value, ss.D, 3, m.params.γ)
     seqs = hank.BackwardIteration(xd, {"Z": Z}, m, ss)
     fused = hank.ForwardIteration(seqs, m, ss)
     _close(fused["Value"].v, oagg[2]); _close(fused["Value"].p, odagg[2])
@@ -269,10 +190,10 @@ def test_reference_shaped_api_with_value(hank, tmp_path):
     _close(fv["Value"], oagg[2])
 
 
-def test_fallback_mid_run_still_serves_the_extra_outputs(hank, monkeypatch):
+def test_fallback_mid_run_still_serves_the_extra_outputs(hank):
     """a context whose persistent sweeps fail (the HANK_XFAULT dev knob pre-sets their status word) continues on the per-period
     launches (hank_check's recovery path); outputs 2 and 3 of the call that fell back equal a launch-family context's."""
-    m, ss = _hank_model(130, 3, 60)
+    m, ss = hank_economy(130, 3, 60, GOODS)
     P = m.compspec.T - 1
     x = _hank_x(ss, P)
     y = np.random.default_rng(6).standard_normal((3, P, 5))
@@ -282,9 +203,7 @@ def test_fallback_mid_run_still_serves_the_extra_outputs(hank, monkeypatch):
     ref.primal_jvp(x, y)
     a_ref, d_ref = ref.het_outputs(4, y)
     ref.close()
-    monkeypatch.setenv("HANK_XFAULT", "placement")
-    hb = _block(hank, m, None)
-    monkeypatch.delenv("HANK_XFAULT", raising=False)
+    hb = _block(hank, m, None, HANK_XFAULT="placement")
     hb.set_boundary(ss.value, ss.D)
     hb.set_het_outputs(4)
     hb.primal_jvp(x, y)
@@ -300,7 +219,6 @@ def test_sticky_wage_hank_solves(hank, inner):
     fallback; the converged path's UCE is the oracle's recomputation at the converged x; a contractionary monetary shock lowers
     output and wage inflation on impact (sanity, not parity)."""
     from examples.solve_hank import solve
-    from oracle.oracle import Oracle
     from hank_amd.BackwardIteration import household_block, household_inputs
     out, x, m, ss = solve(200, 5, 80, shock=0.0025, spec="one_asset_hank_wages.yaml", inner=inner)
     assert out["residual_norm"] < 1e-8, out
@@ -312,7 +230,5 @@ def test_sticky_wage_hank_solves(hank, inner):
     lin = hank.LinearizedFunction(x, ei, m, ss, ss)
     uce = lin.aggs[:, lin._out_idx[lin.het.index("UCE")]]
     xhh, _ = household_inputs(x, ei, m)
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    orc = Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
-    oagg, _ = _oracle_outputs(orc, m.params.γ, ss, np.asarray(xhh), np.zeros((3, P, 1)), 4)
+    oagg, _ = oracle_of(m).het_outputs(np.asarray(xhh), np.zeros((3, P, 1)), ss.value, ss.D, 4, m.params.γ)
     _close(uce, oagg[3])

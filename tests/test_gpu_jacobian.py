@@ -5,17 +5,13 @@ against the oracle's unit-tangent household block, the assembled J̅ against the
 seven columns (test_SteadyState.jl:194-231). Tolerance: 1e-8 of the largest entry (observed 5e-10 .. 1.3e-9) — the Toeplitz
 form assumes the recorded steady state is exactly stationary (VFI tolerance 1e-11), the oracle differentiates the path as it
 is."""
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
+from cases import model_args
 from conftest import ks_setup
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
 
 
 @pytest.mark.parametrize("n_a,n_e,T", [(50, 2, 100), (500, 4, 300), (130, 3, 20)])
@@ -58,8 +54,7 @@ def test_toeplitz_jacobian_one_asset_hank(hank):
 
 def test_fake_news_needs_a_recorded_primal(hank):
     m, ss, _ = ks_setup(50, 2, 100)
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    hb = hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+    hb = hank.HouseholdBlock(*model_args(m))
     hb.set_boundary(ss.value, ss.D)
     with pytest.raises(hank.HankHIPError):
         hb.fake_news()
@@ -102,7 +97,6 @@ def test_krylov_inner_loop_reaches_the_same_path_with_fewer_jvps(hank):
 def test_toeplitz_household_jacobian_against_the_oracle(hank, n_a, n_e, T):
     """household_jacobian(*hb.fake_news()) columns [0, 1, P//2, P-2, P-1] for every household input against the ORACLE's household
     block under unit tangents (SteadyStateJacobian.jl:300-305, :363-371): 1e-8 of the largest entry."""
-    from oracle.oracle import pad_N
     from hank_amd.SteadyStateJacobian import household_jacobian
     from hank_amd.BackwardIteration import household_block
     m, ss, orc = ks_setup(n_a, n_e, T)
@@ -113,20 +107,16 @@ def test_toeplitz_household_jacobian_against_the_oracle(hank, n_a, n_e, T):
     hb.primal(x)
     Jhh = household_jacobian(*hb.fake_news())
     cols = sorted(set([0, 1, P // 2, P - 2, P - 1]))
-    N = 2 * len(cols)
-    Nc = pad_N(N)
-    xr = np.zeros((P, 1 + Nc)); xw = np.zeros((P, 1 + Nc))
-    xr[:, 0], xw[:, 0] = x[0], x[1]
+    y = np.zeros((2, P, 2 * len(cols)))
     for q, s_ in enumerate(cols):
-        xr[s_, 1 + 2 * q] = 1.0                # d / d r_s
-        xw[s_, 1 + 2 * q + 1] = 1.0            # d / d w_s
-    st, oagg, _ = orc.household_block(xr, xw, ss.value, ss.D, Nc)
-    assert st == 0
-    scale = np.max(np.abs(oagg[:, 1:1 + N]))
+        y[0, s_, 2 * q] = 1.0                  # d / d r_s
+        y[1, s_, 2 * q + 1] = 1.0              # d / d w_s
+    odagg = orc.block(x, y, ss.value, ss.D)[1]
+    scale = np.max(np.abs(odagg))
     assert scale > 1e-3
     for q, s_ in enumerate(cols):
-        assert np.max(np.abs(Jhh[0][:, s_] - oagg[:, 1 + 2 * q])) < 1e-8 * scale, ("r", s_)
-        assert np.max(np.abs(Jhh[1][:, s_] - oagg[:, 1 + 2 * q + 1])) < 1e-8 * scale, ("w", s_)
+        assert np.max(np.abs(Jhh[0][:, s_] - odagg[:, 2 * q])) < 1e-8 * scale, ("r", s_)
+        assert np.max(np.abs(Jhh[1][:, s_] - odagg[:, 2 * q + 1])) < 1e-8 * scale, ("w", s_)
 
 
 def test_toeplitz_jacobian_on_the_reference_seven_columns_against_the_oracle(hank):

@@ -1,12 +1,12 @@
 """Lifetime of a context's device memory and graphs (csrc/hank_hip.hip): contexts created, used through every
 entry that allocates, and destroyed, again and again; workspaces evicted from a cache that holds one; a context after a hank_create
 that failed. What is pinned is behaviour — the same bits every time, the readers' answers after an eviction — on Krusell-Smith
-65x3, T = 12 (vjp_cases.shape: two members per group of the persistent sweeps, the second with two rows; n_e = 3 is instantiated
+65x3, T = 12 (cases.shape: two members per group of the persistent sweeps, the second with two rows; n_e = 3 is instantiated
 for the wide sweeps), under every schedule: the default, launch, xcd and wide. A schedule that hank_create refuses fails the test."""
 import numpy as np
 import pytest
 
-import vjp_cases as vc
+import cases as vc
 
 pytestmark = pytest.mark.gpu
 
@@ -98,22 +98,15 @@ def test_a_failed_create_leaves_the_process_usable(hank):
     """hank_create returns its context on failure too (for hank_last_error) and the caller destroys it: a wealth grid that does
     not increase is refused, and a context of the right grid, created next, matches the oracle (rel 1e-10 + abs 1e-12 of the
     output scale, tests/test_gpu_sweeps.py's bound for hank_primal)."""
-    from oracle.oracle import pad_N
     m, V, D, xhh, orc, _, _ = _inputs()
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    bad = np.array(wd.grid, copy=True)
+    bad = np.array(m.heterogeneity["wealth"].grid, copy=True)
     bad[7] = bad[6]
     with pytest.raises(hank.HankHIPError, match="strictly increasing"):
-        hank.HouseholdBlock(bad, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+        hank.HouseholdBlock(bad, *vc.model_args(m)[1:])
     hb = vc.block(hank, m, None)
     try:
         hb.set_boundary(V, D)
         agg = hb.primal(xhh)
     finally:
         hb.close()
-    P, Nc = xhh.shape[1], pad_N(1)
-    xd = np.zeros((2, P, 1 + Nc))
-    xd[..., 0] = xhh
-    st, oagg, _ = orc.household_block(xd[0], xd[1], V, D, Nc)
-    assert st == 0
-    vc.close(agg, oagg[:, 0], what="hank_primal after a failed hank_create")
+    vc.close(agg, orc.block(xhh, None, V, D)[0], what="hank_primal after a failed hank_create")

@@ -15,22 +15,13 @@ HANK_PRIMAL_MEMO=0 at hank_create: every hank_primal_jvp really runs its Dual pa
 import numpy as np
 import pytest
 
+from cases import block
 from conftest import ks_paths, ks_setup
 
 pytestmark = pytest.mark.gpu
 
 SMALL = (130, 3, 40)
 FULL = (2000, 11, 300)
-
-
-def make_block(hank, m, monkeypatch):
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    monkeypatch.setenv("HANK_PRIMAL_MEMO", "0")
-    try:
-        return hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T,
-                                   m.value_fn.value_fn_id)
-    finally:
-        monkeypatch.delenv("HANK_PRIMAL_MEMO", raising=False)
 
 
 def assert_row0_path_is_exercised(hb, m):
@@ -51,7 +42,7 @@ def dual_pass(hb, x, y32):
 
 
 @pytest.mark.parametrize("n_a,n_e,T", [SMALL, FULL])
-def test_record_built_behind_a_dual_pass_has_the_bits_of_hank_primals(hank, monkeypatch, n_a, n_e, T):
+def test_record_built_behind_a_dual_pass_has_the_bits_of_hank_primals(hank, n_a, n_e, T):
     """the same fixed tangent batches through the persistent (N = 32), launch (N = 72) and — at 2000x11 — wide (N = 256) families:
     record by Dual pass + builder against record by hank_primal"""
     m, ss, _ = ks_setup(n_a, n_e, T)
@@ -62,7 +53,7 @@ def test_record_built_behind_a_dual_pass_has_the_bits_of_hank_primals(hank, monk
     batches = {"xcd-persistent": rng.standard_normal((2, P, 32)), "launch-per-period": rng.standard_normal((2, P, 72))}
     if (n_a, n_e, T) == FULL:
         batches["on-chip-wide"] = rng.standard_normal((2, P, 256))
-    hb = make_block(hank, m, monkeypatch)
+    hb = block(hank, m, None, HANK_PRIMAL_MEMO=0)
     hb.set_boundary(ss.value, ss.D)
     assert hb.info()["lwg_builds"] == 0
     for fam, y in batches.items():
@@ -85,12 +76,12 @@ def test_record_built_behind_a_dual_pass_has_the_bits_of_hank_primals(hank, monk
 
 
 @pytest.mark.parametrize("n_a,n_e,T", [SMALL, FULL])
-def test_fake_news_after_a_dual_pass_equals_the_one_after_hank_primal(hank, monkeypatch, n_a, n_e, T):
+def test_fake_news_after_a_dual_pass_equals_the_one_after_hank_primal(hank, n_a, n_e, T):
     m, ss, _ = ks_setup(n_a, n_e, T)
     P = T - 1
     x = np.tile(np.array([[ss.vars["r"]], [ss.vars["w"]]]), (1, P))
     y32 = np.random.default_rng(3).standard_normal((2, P, 32))
-    hb = make_block(hank, m, monkeypatch)
+    hb = block(hank, m, None, HANK_PRIMAL_MEMO=0)
     hb.set_boundary(ss.value, ss.D)
     hb.primal(x)
     assert_row0_path_is_exercised(hb, m)
@@ -111,13 +102,13 @@ def test_fake_news_after_a_dual_pass_equals_the_one_after_hank_primal(hank, monk
 
 
 @pytest.mark.parametrize("n_a,n_e,T", [SMALL, FULL])
-def test_every_dual_pass_invalidates_the_record_and_one_build_serves_every_later_reader(hank, monkeypatch, n_a, n_e, T):
+def test_every_dual_pass_invalidates_the_record_and_one_build_serves_every_later_reader(hank, n_a, n_e, T):
     m, ss, _ = ks_setup(n_a, n_e, T)
     P = T - 1
     x, _ = ks_paths(m, ss, "x1", 0.01)
     rng = np.random.default_rng(29)
     y32, y = rng.standard_normal((2, P, 32)), rng.standard_normal((2, P, 32))
-    hb = make_block(hank, m, monkeypatch)
+    hb = block(hank, m, None, HANK_PRIMAL_MEMO=0)
     hb.set_boundary(ss.value, ss.D)
     hb.primal(x[2:4])
     assert_row0_path_is_exercised(hb, m)

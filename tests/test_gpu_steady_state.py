@@ -6,6 +6,7 @@ import time
 import numpy as np
 import pytest
 
+from cases import block
 from conftest import ROOT, ks_setup
 
 pytestmark = pytest.mark.gpu
@@ -73,7 +74,7 @@ def test_device_stationary_distribution_matches_the_host(hank):
     assert steps > 25
 
 
-def test_persistent_and_launched_value_iteration_agree(hank, monkeypatch):
+def test_persistent_and_launched_value_iteration_agree(hank):
     """hank_vfi as ONE persistent launch (k_xvfi: the vote on convergence rides on the group barrier) against the
     per-step launches: the same number of steps, the same value and policy (same expressions; both stop on the Float64
     comparison max|Δvalue| < tol), at a small grid and at the headline grid."""
@@ -82,9 +83,7 @@ def test_persistent_and_launched_value_iteration_agree(hank, monkeypatch):
         xv = dict(ss.vars)
         out = {}
         for sched in ("launch", "xcd"):
-            monkeypatch.setenv("HANK_SCHEDULE", sched)
-            hb = hank.HouseholdBlock(m.heterogeneity["wealth"].grid, m.heterogeneity["productivity"].grid,
-                                     m.heterogeneity["productivity"].transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+            hb = block(hank, m, sched)
             out[sched] = hb.vfi(np.ones((n_a, n_e)), [xv["r"], xv["w"]], 1e-11)
             assert hb.stats()["fallbacks"] == 0
             hb.close()
@@ -93,21 +92,17 @@ def test_persistent_and_launched_value_iteration_agree(hank, monkeypatch):
         assert np.max(np.abs(v1 - v0)) <= 1e-13 * np.abs(v0).max()
         assert np.max(np.abs(p1 - p0)) <= 1e-13 * np.abs(p0).max()
         # not converged within the cap: both report the cap and the last iterate
-        monkeypatch.setenv("HANK_SCHEDULE", "xcd")
-        hb = hank.HouseholdBlock(m.heterogeneity["wealth"].grid, m.heterogeneity["productivity"].grid,
-                                 m.heterogeneity["productivity"].transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+        hb = block(hank, m, "xcd")
         v2, p2, it2, n2 = hb.vfi(np.ones((n_a, n_e)), [xv["r"], xv["w"]], 1e-11, 7)
         assert it2 == 7 and n2 > 1e-11
         hb.close()
 
 
-def test_persistent_value_iteration_reports_the_reference_errors(hank, monkeypatch):
+def test_persistent_value_iteration_reports_the_reference_errors(hank):
     """a wage so negative that consumption turns negative: the DomainError of the reference's power, raised by the
     persistent loop in the step it happens (it leaves the loop through the vote), not after max_iter steps."""
-    monkeypatch.setenv("HANK_SCHEDULE", "xcd")
     m, ss, _ = ks_setup(50, 2, 100)
-    hb = hank.HouseholdBlock(m.heterogeneity["wealth"].grid, m.heterogeneity["productivity"].grid,
-                             m.heterogeneity["productivity"].transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+    hb = block(hank, m, "xcd")
     with pytest.raises((hank.DomainError, hank.KnotsNotSortedError)):
         hb.vfi(np.ones((50, 2)), [0.01, -50.0], 1e-11)
     # the context is usable afterwards
@@ -117,7 +112,7 @@ def test_persistent_value_iteration_reports_the_reference_errors(hank, monkeypat
     hb.close()
 
 
-def test_persistent_and_launched_power_method_agree(hank, monkeypatch):
+def test_persistent_and_launched_power_method_agree(hank):
     """hank_stationary_dist as ONE persistent launch (k_xstat) against one launch per iteration: the same fixed point of the
     reference's transition matrix to 1e-14, from a uniform start and from a warm start; the cap on the iterations is
     honoured."""
@@ -130,8 +125,7 @@ def test_persistent_and_launched_power_method_agree(hank, monkeypatch):
         Λ = (Λ_exog @ hank.make_endogenous_transition(pol, wd, pdm.n)).tocsc()
         out = {}
         for sched in ("launch", "xcd"):
-            monkeypatch.setenv("HANK_SCHEDULE", sched)
-            hb = hank.HouseholdBlock(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+            hb = block(hank, m, sched)
             D, steps = hb.stationary_dist(pol)
             assert np.max(np.abs(Λ @ D - D)) < 1e-14 and abs(D.sum() - 1.0) < 1e-13 and D.min() >= 0.0
             Dw, steps_w = hb.stationary_dist(pol, D0=D)          # warm start at the fixed point: the first check passes (the
@@ -146,7 +140,7 @@ def test_persistent_and_launched_power_method_agree(hank, monkeypatch):
         assert np.max(np.abs(out["xcd"][0] - ss.D)) < 1e-10
 
 
-def test_power_method_stops_only_when_every_member_has_converged(hank, monkeypatch):
+def test_power_method_stops_only_when_every_member_has_converged(hank):
     """far from the solution (r = 4 %: every household saves, the mass ends on the top grid point) the bottom of the grid
     settles hundreds of iterations before the top. The persistent launch must keep going until EVERY member's rows pass the
     rule — the first version of its vote looked at member 0 only and stopped at 500 of 800 iterations with |ΛD − D| = 6e-9,
@@ -157,8 +151,7 @@ def test_power_method_stops_only_when_every_member_has_converged(hank, monkeypat
     Λ_exog = sp.kron(sp.csc_matrix(pdm.transition.T), sp.identity(wd.n, format="csc"), format="csc")
     out = {}
     for sched in ("launch", "xcd"):
-        monkeypatch.setenv("HANK_SCHEDULE", sched)
-        hb = hank.HouseholdBlock(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+        hb = block(hank, m, sched)
         v, pol, it, nrm = hb.vfi(np.ones((2000, 11)), [0.04, 1.0], 1e-11)
         Λ = (Λ_exog @ hank.make_endogenous_transition(pol, wd, pdm.n)).tocsc()
         D, steps = hb.stationary_dist(pol)
@@ -170,33 +163,15 @@ def test_power_method_stops_only_when_every_member_has_converged(hank, monkeypat
     assert np.max(np.abs(out["xcd"][0] - out["launch"][0])) < 1e-13
 
 
-def _oracle_vfi(orc, shape, r, w, tol, cap=20_000):
-    """the reference's inner fixed point (SteadyState.jl:132-141) on the CPU oracle's ValueFunction: value <- value_fn(value).Value
-    from ones until max|new - old| < tol; returns (value, policy, steps, per-step sup-norms)."""
-    value = np.ones(shape)
-    norms = []
-    for k in range(1, cap + 1):
-        st, V, KD = orc.value_function(value, r, w, 1)
-        assert st == 0
-        vn, pol = V[..., 0], KD[..., 0]
-        norms.append(float(np.max(np.abs(vn - value))))
-        value = vn
-        if norms[-1] < tol:
-            return value, pol, k, norms
-    raise AssertionError("oracle VFI did not converge")
-
-
 @pytest.mark.parametrize("n_a,n_e,T", [(50, 2, 100), (37, 3, 9)])
-def test_device_vfi_matches_the_oracle_iteration(hank, monkeypatch, n_a, n_e, T):
+def test_device_vfi_matches_the_oracle_iteration(hank, n_a, n_e, T):
     """hank_vfi (both schedules) against oracle/ — the C restatement of KrusellSmith.jl:43-83 iterated with the reference's
     stopping rule: the same number of steps, value and policy to rel 1e-10 (SURVEY.md 8c tolerance)."""
     m, ss, orc = ks_setup(n_a, n_e, T)
     r, w, tol = ss.vars["r"], ss.vars["w"], 1e-11
-    v_o, p_o, steps_o, _ = _oracle_vfi(orc, (n_a, n_e), r, w, tol)
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
+    v_o, p_o, steps_o, _ = orc.vfi((n_a, n_e), r, w, tol)
     for sched in ("launch", "xcd"):
-        monkeypatch.setenv("HANK_SCHEDULE", sched)
-        hb = hank.HouseholdBlock(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+        hb = block(hank, m, sched)
         v, pol, it, nrm = hb.vfi(np.ones((n_a, n_e)), [r, w], tol)
         assert abs(it - steps_o) <= 1 and nrm < tol, (sched, it, steps_o)      # (a sup-norm within rounding of tol may tip one step)
         assert np.max(np.abs(v - v_o)) < 1e-10 * np.abs(v_o).max()
@@ -204,15 +179,14 @@ def test_device_vfi_matches_the_oracle_iteration(hank, monkeypatch, n_a, n_e, T)
         hb.close()
 
 
-def test_value_iteration_stops_only_when_every_member_has_converged(hank, monkeypatch):
+def test_value_iteration_stops_only_when_every_member_has_converged(hank):
     """the twin of the power-method case above for k_xvfi's vote: at r = 1.5 %, w = 1 the marginal value of the rich keeps
     moving long after the bottom of the grid has settled — member 0's 63 rows pass max|Δ| < tol at step 662, the top member at
     818 (on the oracle). A vote that looked at member 0 only would stop 156 steps early. The persistent loop, the launched
     loop and the oracle iteration must all stop in the step in which the LAST rows pass, and agree on value and policy."""
     m, ss, orc = ks_setup(500, 4, 300)
-    wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
     r, w, tol = 0.015, 1.0, 1e-10
-    v_o, p_o, steps_o, norms = _oracle_vfi(orc, (500, 4), r, w, tol)
+    v_o, p_o, steps_o, norms = orc.vfi((500, 4), r, w, tol)
     # the members really do converge at different times: the first 63 rows pass the rule long before the whole grid does
     value = np.ones((500, 4)); first = None
     for k in range(1, steps_o + 1):
@@ -223,8 +197,7 @@ def test_value_iteration_stops_only_when_every_member_has_converged(hank, monkey
     assert first is not None and first < steps_o - 100, (first, steps_o)
     out = {}
     for sched in ("launch", "xcd"):
-        monkeypatch.setenv("HANK_SCHEDULE", sched)
-        hb = hank.HouseholdBlock(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
+        hb = block(hank, m, sched)
         out[sched] = hb.vfi(np.ones((500, 4)), [r, w], tol)
         assert hb.stats()["fallbacks"] == 0
         hb.close()

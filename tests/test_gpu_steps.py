@@ -8,15 +8,10 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from cases import close
+
 pytestmark = pytest.mark.gpu
 G = Path(__file__).resolve().parent / "golden"
-
-
-def close(a, b, rel=1e-10, abs_=1e-12):
-    a, b = np.asarray(a), np.asarray(b)
-    scale = max(np.max(np.abs(b)), 1e-300)
-    err = np.max(np.abs(a - b))
-    assert err <= abs_ + rel * scale, f"max err {err:.3e} vs scale {scale:.3e}"
 
 
 @pytest.mark.parametrize("N", [1, 3, 8])

@@ -6,17 +6,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from cases import block as _forced, close
 from conftest import ks_paths, ks_setup
 
 pytestmark = pytest.mark.gpu
 G = Path(__file__).resolve().parent / "golden"
-
-
-def close(a, b, rel=1e-10, abs_=1e-12):
-    a, b = np.asarray(a), np.asarray(b)
-    scale = max(np.max(np.abs(b)), 1e-300)
-    err = np.max(np.abs(a - b))
-    assert err <= abs_ + rel * scale, f"max err {err:.3e} vs scale {scale:.3e}"
 
 
 def run_case(hank, n_a, n_e, T, N, kind, shock, check_policies=True):
@@ -29,24 +23,11 @@ def run_case(hank, n_a, n_e, T, N, kind, shock, check_policies=True):
     hb.set_boundary(ss.value, ss.D)
     agg = hb.primal(x[2:4])
     dagg = hb.jvp(y[2:4])
-    from oracle.oracle import pad_N, SUPPORTED_N
-    oagg_cols, opol_cols = [], []
-    for c0 in range(0, N, SUPPORTED_N[-1]):            # the oracle carries at most 32 partials per pass
-        c1 = min(N, c0 + SUPPORTED_N[-1])
-        Nc = pad_N(c1 - c0)
-        xr = np.zeros((P, 1 + Nc)); xw = np.zeros((P, 1 + Nc))
-        xr[:, 0], xw[:, 0] = x[2], x[3]
-        xr[:, 1:1 + c1 - c0], xw[:, 1:1 + c1 - c0] = y[2][:, c0:c1], y[3][:, c0:c1]
-        st, oa, op = orc.household_block(xr, xw, ss.value, ss.D, Nc)
-        assert st == 0
-        oagg0, opol0 = oa[:, 0], op[..., 0]
-        oagg_cols.append(oa[:, 1:1 + c1 - c0]); opol_cols.append(op[..., 1:1 + c1 - c0])
-    oagg = np.concatenate([oagg0[:, None]] + oagg_cols, axis=1)
-    opol = np.concatenate([opol0[..., None]] + opol_cols, axis=-1)
-    close(agg, oagg[:, 0]); close(dagg, oagg[:, 1:])
+    oagg, odagg, opol, odpol = orc.block(x[2:4], y[2:4], ss.value, ss.D)
+    close(agg, oagg); close(dagg, odagg)
     if check_policies:
-        close(hb.policy_seq().transpose(2, 0, 1), opol[..., 0])
-        close(hb.dpolicy_seq(N).transpose(2, 0, 1, 3), opol[..., 1:])
+        close(hb.policy_seq().transpose(2, 0, 1), opol)
+        close(hb.dpolicy_seq(N).transpose(2, 0, 1, 3), odpol)
         D = hb.dist_seq()
         np.testing.assert_allclose(D.sum(axis=(0, 1)), 1.0, atol=1e-12)
     return m, ss, orc, x, Z, y
@@ -125,17 +106,6 @@ def test_knots_error_from_the_sweep(hank):
     hb.primal(x[2:4])                          # context recovers
 
 
-def _forced(hank, m, sched):
-    """a context of model m with one implementation forced for every entry point (HANK_SCHEDULE)."""
-    import os
-    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-    os.environ["HANK_SCHEDULE"] = sched
-    try:
-        return hank.HouseholdBlock(wd.grid, pd_.grid, pd_.transition, m.params.β, m.params.γ, m.params.borrow_cons, m.compspec.T)
-    finally:
-        os.environ.pop("HANK_SCHEDULE")
-
-
 def test_dual_sweep_equals_primal_then_jvp(hank):
     """hank_primal_jvp (value and partials in one pass) == hank_primal followed by hank_jvp, and it leaves the same record
     behind: bit for bit with the per-period launches; to rounding of the aggregate sums with the XCD-local persistent sweeps
@@ -149,14 +119,14 @@ def test_dual_sweep_equals_primal_then_jvp(hank):
         y = np.random.default_rng(5).standard_normal((2, P, N))
         for sched in ("launch", "xcd", None):
             hb = _forced(hank, m, sched) if sched else hank.household_block(m)
-            same = np.array_equal if sched == "launch" else (lambda a, b: np.max(np.abs(a - b)) <= 1e-13 * max(np.max(np.abs(b)), 1e-300))
+            same = np.testing.assert_array_equal if sched == "launch" else (lambda a, b: close(a, b, 1e-13, ab=0.0))
             hb.set_boundary(ss.value, ss.D)
             agg0 = hb.primal(x[2:4]); dagg0 = hb.jvp(y); pol0 = hb.policy_seq(); dpol0 = hb.dpolicy_seq(N)
             hb.primal(x[2:4] * 1.01)                       # scramble the record
             agg1, dagg1 = hb.primal_jvp(x[2:4], y)
-            assert same(agg0, agg1) and same(dagg0, dagg1)
+            same(agg0, agg1); same(dagg0, dagg1)
             assert np.array_equal(pol0, hb.policy_seq()) and np.array_equal(dpol0, hb.dpolicy_seq(N))
-            assert same(hb.jvp(y), dagg0)                  # the record it leaves serves later JVPs
+            same(hb.jvp(y), dagg0)                         # the record it leaves serves later JVPs
             if sched:
                 hb.close()
 

@@ -12,12 +12,10 @@
 The boundary (V_T, D_0) of each curvature is the host steady state of a fresh model (never a model ks_setup cached: its params
 are shared by the session). The shape tests take a cheaper boundary, a host VFI iterate and a uniform D_0: parity needs a valid
 boundary, not a stationary one."""
-import os
-
 import numpy as np
 import pytest
 
-from vjp_cases import CASES, block as _block, economy as _economy, shape as _shape
+from cases import CASES, block as _block, close as _close, economy as _economy, raw_block, shape as _shape
 
 pytestmark = pytest.mark.gpu
 
@@ -26,32 +24,6 @@ FAMILY = {"launch": "launch-per-period", "xcd": "xcd-persistent", "wide": "on-ch
 # the one-asset HANK calibration (the bond supply that clears the asset market) has no steady state at gamma = 0.5 (its Newton
 # step is singular); no other gamma takes the rcp(x^2) | rsqrt pair, so Krusell-Smith alone covers it
 MATRIX = [(fam, case) for fam in ("ks", "hank") for case in CASES if not (fam == "hank" and case == "gamma0.5")]
-
-
-def _close(a, b, rel=1e-10, ab=1e-12, what=""):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    err = np.max(np.abs(a - b))
-    assert err <= ab + rel * np.abs(b).max(), f"{what}: max err {err:.3e} vs scale {np.abs(b).max():.3e}"
-
-
-def _oracle(orc, value, D, xhh, y):
-    """the oracle's household block at xhh (n_hh, P) with the partials y (n_hh, P, N), 32 partials per pass ->
-    agg (P,), dagg (P, N), policy (P, n_a, n_e), dpolicy (P, n_a, n_e, N)."""
-    from oracle.oracle import SUPPORTED_N, pad_N
-    n_hh, P, N = y.shape
-    dagg, dpol = [], []
-    for c0 in range(0, N, SUPPORTED_N[-1]):
-        c1 = min(N, c0 + SUPPORTED_N[-1])
-        Nc = pad_N(c1 - c0)
-        xd = np.zeros((n_hh, P, 1 + Nc))
-        xd[..., 0] = xhh
-        xd[..., 1:1 + c1 - c0] = y[:, :, c0:c1]
-        st, oa, op = orc.household_block(xd[0], xd[1], value, D, Nc, xd[2] if n_hh > 2 else None)
-        assert st == 0
-        agg, pol = oa[:, 0], op[..., 0]
-        dagg.append(oa[:, 1:1 + c1 - c0]); dpol.append(op[..., 1:1 + c1 - c0])
-    return agg, np.concatenate(dagg, axis=1), pol, np.concatenate(dpol, axis=-1)
 
 
 def _sweeps(hb, xhh, y, Ns):
@@ -94,7 +66,7 @@ def test_parity_over_curvature_and_record_layout(hank, family, case):
     m, ss, xhh, orc = _economy(family, gamma)
     n_hh, P = xhh.shape
     y = np.random.default_rng(17).standard_normal((n_hh, P, NWIDE))
-    oagg, odagg, opol, odpol = _oracle(orc, ss.value, ss.D, xhh, y[:, :, :max(NS)])
+    oagg, odagg, opol, odpol = orc.block(xhh, y[:, :, :max(NS)], ss.value, ss.D)
     res = {}
     for sched in ("launch", "xcd", "wide", None):
         hb = _block(hank, m, sched, HANK_RECORD_DIET=diet_env)
@@ -144,21 +116,6 @@ def test_parity_over_curvature_and_record_layout(hank, family, case):
 
 
 # ---- 2. the rest of the pipeline at gamma != 2 -------------------------------------------------------------------------------
-def _oracle_vfi(orc, shape, r, w, tol, cap=20_000):
-    """the reference's inner fixed point (SteadyState.jl:132-141) on the oracle's ValueFunction, from ones until
-    max|new - old| < tol (tests/test_gpu_steady_state.py) -> (value, policy, steps)."""
-    value = np.ones(shape)
-    for k in range(1, cap + 1):
-        st, V, KD = orc.value_function(value, r, w, 1)
-        assert st == 0
-        vn, pol = V[..., 0], KD[..., 0]
-        nrm = float(np.max(np.abs(vn - value)))
-        value = vn
-        if nrm < tol:
-            return value, pol, k
-    raise AssertionError("oracle VFI did not converge")
-
-
 @pytest.mark.parametrize("gamma", [1.0, 0.5, 3.0])
 def test_device_vfi_at_other_curvatures(hank, gamma):
     """hank_vfi (k_xvfi under xcd, k_egm_step under launch) on the other pow_crra branches: the oracle iteration's step count
@@ -166,7 +123,7 @@ def test_device_vfi_at_other_curvatures(hank, gamma):
     m, ss, _, orc = _economy("ks", gamma)
     n_a, n_e = ss.value.shape
     r, w, tol = ss.vars["r"], ss.vars["w"], 1e-11
-    v_o, p_o, steps_o = _oracle_vfi(orc, (n_a, n_e), r, w, tol)
+    v_o, p_o, steps_o, _ = orc.vfi((n_a, n_e), r, w, tol)
     for sched in ("launch", "xcd"):
         hb = _block(hank, m, sched)
         v, pol, it, nrm = hb.vfi(np.ones((n_a, n_e)), [r, w], tol)
@@ -191,44 +148,6 @@ def test_toeplitz_jacobian_at_other_curvatures(hank, gamma, diet):
     assert np.max(np.abs(Jt - Jc)) < 1e-8 * np.max(np.abs(Jc))
 
 
-def _oracle_outputs(orc, gamma, ss, x, y, n_het):
-    """x (n_hh, P), y (n_hh, P, N) -> agg (n_het, P), dagg (n_het, P, N) of (savings, consumption, Value[, UCE]) under the oracle's
-    dual arithmetic (tests/test_gpu_het_nonaffine.py)."""
-    from oracle.oracle import _dp, _fn, pad_N
-    import ctypes as C
-    n_hh, P, N = y.shape
-    Nc = pad_N(N)
-    xd = np.zeros((n_hh, P, 1 + Nc))
-    xd[..., 0] = x
-    xd[..., 1:1 + N] = y
-    xt = xd[2] if n_hh > 2 else None
-    st, pol = orc.backward_iteration(xd[0], xd[1], ss.value, Nc, xt)
-    assert st == 0
-    V = np.empty((P, orc.n_a, orc.n_e, 1 + Nc))
-    Vn = np.asarray(ss.value, dtype=np.float64)
-    for t in range(P - 1, -1, -1):
-        st, Vt, KD = orc.value_function(Vn, xd[0, t], xd[1, t], Nc, None if xt is None else xt[t])
-        assert st == 0
-        _close(KD, pol[t], 1e-12)
-        V[t], Vn = Vt, Vt
-    ps = np.ascontiguousarray(pol.transpose(0, 2, 1, 3))
-    cons = np.empty_like(ps)
-    _fn("orc_consumption_policy", Nc)(C.byref(orc.m), P, _dp(np.ascontiguousarray(xd[0])), _dp(np.ascontiguousarray(xd[1])),
-                                      None if xt is None else _dp(np.ascontiguousarray(xt)), _dp(ps), _dp(cons))
-    seqs = [ps, cons, np.ascontiguousarray(V.transpose(0, 2, 1, 3))]
-    if n_het > 3:
-        c0 = cons[..., 0]
-        u = np.empty_like(cons)
-        u[..., 0] = c0 ** (-gamma)
-        u[..., 1:] = (-gamma * c0 ** (-gamma - 1.0))[..., None] * cons[..., 1:]
-        seqs.append(orc.z[None, :, None, None] * u)
-    seqs = np.ascontiguousarray(np.stack(seqs))
-    D0 = np.ascontiguousarray(np.asarray(ss.D, dtype=np.float64).reshape((orc.n_a, orc.n_e), order="F").T)
-    agg = np.empty((n_het, P, 1 + Nc))
-    _fn("orc_forward_iteration_het", Nc)(C.byref(orc.m), P, n_het, _dp(seqs), _dp(D0), _dp(agg))
-    return agg[..., 0], agg[..., 1:1 + N]
-
-
 @pytest.mark.parametrize("family,n_het", [("ks", 3), ("hank", 4)])
 def test_nonaffine_outputs_at_gamma_1_5(hank, family, n_het):
     """Value (Krusell-Smith) and UCE (one-asset HANK) at gamma = 1.5 (pow branches, diet off): hank_get_het_outputs after a
@@ -247,7 +166,7 @@ def test_nonaffine_outputs_at_gamma_1_5(hank, family, n_het):
     hb.set_het_outputs(n_het)
     hb.primal_jvp(xhh, y)
     agg, dagg = hb.het_outputs(n_het, y)
-    oagg, odagg = _oracle_outputs(orc, gamma, ss, xhh, y, n_het)
+    oagg, odagg = orc.het_outputs(xhh, y, ss.value, ss.D, n_het, gamma)
     for j in range(n_het):
         _close(agg[:, j], oagg[j], what=f"output {j}")
         _close(dagg[:, j, :], odagg[j], what=f"output {j} partials")
@@ -264,7 +183,7 @@ def test_nonaffine_outputs_at_gamma_1_5(hank, family, n_het):
     for q, s_ in enumerate(cols):
         for k in range(n_hh):
             yu[k, s_, q * n_hh + k] = 1.0
-    _, odu = _oracle_outputs(orc, gamma, ss, xss, yu, n_het)
+    _, odu = orc.het_outputs(xss, yu, ss.value, ss.D, n_het, gamma)
     for o in range(n_het):
         J = household_jacobian(F[..., o], Dv[..., o])
         scale = np.max(np.abs(odu[o]))
@@ -276,12 +195,12 @@ def test_nonaffine_outputs_at_gamma_1_5(hank, family, n_het):
 
 
 # ---- 3. shape edges of the persistent and wide families ----------------------------------------------------------------------
-def _forced_against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
+def _against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
     """each (schedule, env) of `runs`, both entry points at every N of Ns, against the oracle and a launch-schedule context."""
     m, V, D, xhh, orc = shape
     n_hh, P = xhh.shape
     y = np.random.default_rng(seed).standard_normal((n_hh, P, max(Ns)))
-    oagg, odagg, opol, odpol = _oracle(orc, V, D, xhh, y)
+    oagg, odagg, opol, odpol = orc.block(xhh, y, V, D)
     refs = {}
     for sched, env in runs:
         diet = env.get("HANK_RECORD_DIET")
@@ -317,14 +236,14 @@ def _forced_against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
 def test_xcd_sweeps_across_the_1024_thread_boundary(hank, n_e):
     """64 (n_e + 1) threads: n_e = 11 is the last 768-thread grid, 12 the first 1024-thread one (dmax = 2). N = 12 is D = 2 in
     one pass, N = 40 one pass at 768 threads and three (16 + 16 + 8) at 1024; with the diet on and off."""
-    _forced_against_oracle_and_launches(hank, _shape(40, n_e, 10), [("xcd", {}), ("xcd", {"HANK_RECORD_DIET": 0})], (12, 40))
+    _against_oracle_and_launches(hank, _shape(40, n_e, 10), [("xcd", {}), ("xcd", {"HANK_RECORD_DIET": 0})], (12, 40))
 
 
 @pytest.mark.parametrize("n_a", [63, 64, 126, 127])
 def test_last_slab_full_or_holding_one_row(hank, n_a):
     """the persistent sweeps work in 63-row slabs, one per CU of an XCD: a last slab exactly full (63, 126) or holding one row
     (64, 127); and the wide family at the same grids (rows in pairs or quads per thread)."""
-    _forced_against_oracle_and_launches(hank, _shape(n_a, 3, 12), [("xcd", {}), ("xcd", {"HANK_RECORD_DIET": 0}), ("wide", {}),
+    _against_oracle_and_launches(hank, _shape(n_a, 3, 12), [("xcd", {}), ("xcd", {"HANK_RECORD_DIET": 0}), ("wide", {}),
                                                                    ("wide", {"HANK_WIDE_R": 4})], (5, 40))
 
 
@@ -334,23 +253,13 @@ def test_xcd_capacity(hank):
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count // 8
     n_a = 63 * cus
-    _forced_against_oracle_and_launches(hank, _shape(n_a, 2, 5), [("xcd", {})], (4,))
-    g = np.linspace(0.0, 200.0, n_a + 1)
-    Pi = np.array([[0.9, 0.1], [0.1, 0.9]])
-    old = os.environ.get("HANK_SCHEDULE")
-    try:
-        os.environ["HANK_SCHEDULE"] = "xcd"
-        with pytest.raises(hank.HankHIPError, match=f"HANK_SCHEDULE=xcd: n_a={n_a + 1} needs {cus + 1} workgroups per XCD"):
-            hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
-        os.environ.pop("HANK_SCHEDULE")
-        hb = hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
-        assert hb.stats()["schedule"] == 0
-        hb.close()
-    finally:
-        if old is None:
-            os.environ.pop("HANK_SCHEDULE", None)
-        else:
-            os.environ["HANK_SCHEDULE"] = old
+    _against_oracle_and_launches(hank, _shape(n_a, 2, 5), [("xcd", {})], (4,))
+    args = (np.linspace(0.0, 200.0, n_a + 1), np.array([0.5, 1.5]), np.array([[0.9, 0.1], [0.1, 0.9]]), 0.98, 2.0, 0.0, 5)
+    with pytest.raises(hank.HankHIPError, match=f"HANK_SCHEDULE=xcd: n_a={n_a + 1} needs {cus + 1} workgroups per XCD"):
+        raw_block(hank, args, "xcd")
+    hb = raw_block(hank, args, None)
+    assert hb.stats()["schedule"] == 0
+    hb.close()
 
 
 @pytest.mark.parametrize("n_e", [2, 3, 4, 5, 7, 11])
@@ -358,31 +267,21 @@ def test_every_instantiated_wide_ne(hank, n_e):
     """k_wide_back / k_wide_fwd of every n_e of HANK_WIDE_NE_LIST, in both geometries (2 rows per thread, 1024-thread workgroups;
     4 rows, 512) and both record layouts (the diet-off backward sweep is another template)."""
     runs = [("wide", {"HANK_WIDE_R": r, "HANK_RECORD_DIET": d}) for r in (2, 4) for d in (None, 0)]
-    _forced_against_oracle_and_launches(hank, _shape(40, n_e, 10), runs, (5,))
+    _against_oracle_and_launches(hank, _shape(40, n_e, 10), runs, (5,))
 
 
 @pytest.mark.parametrize("n_a", [2047, 2048])
 def test_wide_capacity(hank, n_a):
     """WIDE_CS = 2048 rows: at 2047 and 2048 every row slot of a workgroup is live (both geometries, both layouts)."""
     runs = [("wide", {"HANK_WIDE_R": r, "HANK_RECORD_DIET": d}) for r in (2, 4) for d in (None, 0)]
-    _forced_against_oracle_and_launches(hank, _shape(n_a, 2, 5), runs, (3,))
+    _against_oracle_and_launches(hank, _shape(n_a, 2, 5), runs, (3,))
 
 
 def test_wide_refuses_one_row_more_than_it_holds(hank):
     """n_a = 2049: auto reports the wide sweeps unsupported, a forced `wide` fails at hank_create with its reason."""
-    g = np.linspace(0.0, 200.0, 2049)
-    Pi = np.array([[0.9, 0.1], [0.1, 0.9]])
-    old = os.environ.get("HANK_SCHEDULE")
-    try:
-        os.environ.pop("HANK_SCHEDULE", None)
-        hb = hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
-        assert hb.info()["wide_supported"] == 0 and hb.info()["wide_mode"] == 0
-        hb.close()
-        os.environ["HANK_SCHEDULE"] = "wide"
-        with pytest.raises(hank.HankHIPError, match="n_a <= 2048"):
-            hank.HouseholdBlock(g, np.array([0.5, 1.5]), Pi, 0.98, 2.0, 0.0, 5)
-    finally:
-        if old is None:
-            os.environ.pop("HANK_SCHEDULE", None)
-        else:
-            os.environ["HANK_SCHEDULE"] = old
+    args = (np.linspace(0.0, 200.0, 2049), np.array([0.5, 1.5]), np.array([[0.9, 0.1], [0.1, 0.9]]), 0.98, 2.0, 0.0, 5)
+    hb = raw_block(hank, args, None)
+    assert hb.info()["wide_supported"] == 0 and hb.info()["wide_mode"] == 0
+    hb.close()
+    with pytest.raises(hank.HankHIPError, match="n_a <= 2048"):
+        raw_block(hank, args, "wide")

@@ -5,30 +5,14 @@ restatement of the reference's ForwardIteration_pullback (ForwardIteration.jl:39
 transition_step, :164-189) and by the pairing with the policy partials; (3) at the benched size by projection on 32 oracle JVP
 columns; (4) the context's state rules; (5) the host layers. Tolerance: the suite's rel 1e-10 + abs 1e-12 on the largest entry
 of the compared array unless stated."""
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
+import cases
+from cases import block as _block, close as _close, forward_iteration_pullback as _forward_iteration_pullback, jt as _jt, oracle_jacobian
 from conftest import ks_paths, ks_setup
-from vjp_cases import block as _block, forward_iteration_pullback as _forward_iteration_pullback, jt as _jt, oracle_jacobian
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-
-
-def _close(a, b, rel=1e-10, ab=1e-12):
-    a, b = np.asarray(a), np.asarray(b)
-    err = np.max(np.abs(a - b))
-    print(f"max err {err:.3e} vs scale {np.abs(b).max():.3e} (bound {ab + rel * np.abs(b).max():.3e})")
-    assert err <= ab + rel * np.abs(b).max(), f"max err {err:.3e} vs scale {np.abs(b).max():.3e}"
-
-
-def _oracle_jacobian(orc, ss, x):
-    return oracle_jacobian(orc, ss.value, ss.D, x)
-
 
 _JCACHE = {}
 
@@ -37,35 +21,20 @@ def _ks_case():
     if "ks" not in _JCACHE:
         m, ss, orc = ks_setup(130, 3, 40)
         x, _ = ks_paths(m, ss, "x1", 0.05)
-        _JCACHE["ks"] = (m, ss, x[2:4], _oracle_jacobian(orc, ss, x[2:4]))
+        _JCACHE["ks"] = (m, ss, x[2:4], oracle_jacobian(orc, ss.value, ss.D, x[2:4]))
     return _JCACHE["ks"]
 
 
 def _hank_case():
     if "hank" not in _JCACHE:
-        from examples.solve_hank import build
-        from oracle.oracle import Oracle
-        from test_gpu_hank import _paths
-        m, ss = build(80, 3, 40)
-        x, _ = _paths(m, ss, m.compspec.T - 1)
-        wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        orc = Oracle(wd.grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
-        J2 = _oracle_jacobian(orc, ss, x)
+        m, ss = cases.hank_economy(80, 3, 40)
+        x = cases.hank_x(ss, m.compspec.T - 1)
+        orc = cases.oracle_of(m)
+        J2 = oracle_jacobian(orc, ss.value, ss.D, x)
         # n_het = 1 from Oracle.household_block (the one-variable block): its own unit-tangent Jacobian
         n_hh, P = x.shape
-        J1 = np.zeros((P, n_hh, P))
-        cols = [(k, s) for s in range(P) for k in range(n_hh)]
-        for c0 in range(0, len(cols), 32):
-            chunk = cols[c0:c0 + 32]
-            xd = np.zeros((n_hh, P, 33))
-            xd[..., 0] = x
-            for j, (k, s) in enumerate(chunk):
-                xd[k, s, 1 + j] = 1.0
-            st, agg, _ = orc.household_block(xd[0], xd[1], ss.value, ss.D, 32, xt=xd[2])
-            assert st == 0
-            for j, (k, s) in enumerate(chunk):
-                J1[:, k, s] = agg[:, 1 + j]
-        _JCACHE["hank"] = (m, ss, x, J2, J1)
+        dagg = orc.block(x, cases.unit_tangents(n_hh, P), ss.value, ss.D)[1]
+        _JCACHE["hank"] = (m, ss, x, J2, np.ascontiguousarray(dagg.reshape(P, P, n_hh).transpose(0, 2, 1)))
     return _JCACHE["hank"]
 
 
@@ -140,8 +109,7 @@ def test_policy_cotangent_is_the_reference_pullback_and_pairs_with_the_policy_pa
 
 # ---- 3. full size, oracle-pinned by projection ----------------------------------------------------------------------------
 def test_full_size_2000x11_T300_M32_by_projection_on_oracle_columns(hank, oracle_mod):
-    from vjp_cases import fullsize_oracle_columns
-    m, ss, xhh, y, Jy2 = fullsize_oracle_columns()              # (computed once; tests/test_gpu_vjp_variants.py reads both aggregates)
+    m, ss, xhh, y, Jy2 = cases.fullsize_oracle_columns()              # (computed once; tests/test_gpu_vjp_variants.py reads both aggregates)
     hb = hank.household_block(m)
     hb.set_boundary(ss.value, ss.D)
     P, M = 299, 32

@@ -16,14 +16,14 @@ E. raw-grid economies whose policy holds a deep clamped prefix (the 1/nb share-o
    VJP alone is a kernel finding and a miss of both an ill-conditioned grid;
 F. the benched size with both aggregates and an odd width (VT = double), by projection on oracle columns.
 
-Tolerance: the suite's rel 1e-10 + abs 1e-12 on the largest entry of the reference (vjp_cases.close), 1e-10 of the summed
+Tolerance: the suite's rel 1e-10 + abs 1e-12 on the largest entry of the reference (cases.close), 1e-10 of the summed
 magnitudes for the projection, 1e-12 of the summed magnitudes for the pairing, 1e-13 of the largest entry for one column in
 different batches, 1e-12 for the same record written by another family or with the other layout."""
 import numpy as np
 import pytest
 
-import vjp_cases as vc
-from vjp_cases import close, jt
+import cases as vc
+from cases import close, jt
 
 pytestmark = pytest.mark.gpu
 

@@ -5,7 +5,7 @@
 import numpy as np
 import pytest
 
-from conftest import ks_paths
+from conftest import ks_paths, ks_setup
 
 
 def test_ss_residual_and_full_pipeline_at_ss(ks_small):
@@ -98,3 +98,76 @@ def test_oracle_reports_julia_errors(ks_small):
     o2 = Oracle(wd.grid, pd_.grid, pd_.transition, m.params.β, 2.5, m.params.borrow_cons)
     st, _, _ = o2.value_function(-np.abs(ss.value), [ss.vars["r"]], [ss.vars["w"]], 1)
     assert st in (3, 4)
+
+
+# ---- the references of the GPU suite (Oracle.block, block_het, het_outputs) against the functions they wrap ----
+def _seeded_by_hand(x, y):
+    """the two passes of N = 33 as Oracle.block makes them: 32 partials, then one (N = 1 is a compiled width)."""
+    from oracle.oracle import pad_N
+    for c0, c1 in ((0, 32), (32, y.shape[2])):
+        Nc = pad_N(c1 - c0)
+        xd = np.zeros(x.shape + (1 + Nc,))
+        xd[..., 0] = x
+        xd[..., 1:1 + c1 - c0] = y[:, :, c0:c1]
+        yield c1 - c0, Nc, xd
+
+
+@pytest.fixture(scope="module")
+def ks_30x3():
+    m, ss, orc = ks_setup(30, 3, 25)
+    return m, ss, orc, np.ascontiguousarray(ks_paths(m, ss, "x1", 0.05)[0][2:4])
+
+
+def test_block_is_household_block_on_the_seeded_passes(ks_30x3):
+    """N = 33: one full pass of 32 partials and one of a single partial; bit for bit what household_block returns on the same
+    two duals, and with y=None the value column of those passes."""
+    m, ss, orc, x = ks_30x3
+    y = np.random.default_rng(4).standard_normal((2, 24, 33))
+    agg, dagg, pol, dpol = orc.block(x, y, ss.value, ss.D)
+    assert agg.shape == (24,) and dagg.shape == (24, 33) and pol.shape == (24, 30, 3) and dpol.shape == (24, 30, 3, 33)
+    c0 = 0
+    for n, Nc, xd in _seeded_by_hand(x, y):
+        st, oa, op = orc.household_block(xd[0], xd[1], ss.value, ss.D, Nc)
+        assert st == 0
+        assert np.array_equal(agg, oa[:, 0]) and np.array_equal(pol, op[..., 0])
+        assert np.array_equal(dagg[:, c0:c0 + n], oa[:, 1:1 + n]) and np.array_equal(dpol[..., c0:c0 + n], op[..., 1:1 + n])
+        c0 += n
+    a0, d0, p0, dp0 = orc.block(x, None, ss.value, ss.D)
+    assert np.array_equal(a0, agg) and np.array_equal(p0, pol) and d0.shape == (24, 0) and dp0.shape == (24, 30, 3, 0)
+    with pytest.raises(RuntimeError, match="oracle status 3"):          # a non-zero status raises
+        bad = np.array(ss.value, copy=True)
+        bad[10, :] *= 1e-4
+        orc.block(x, None, bad, ss.D)
+
+
+def test_block_het_is_household_block_het_on_the_seeded_pass(ks_30x3):
+    from oracle.oracle import pad_N
+    m, ss, orc, x = ks_30x3
+    N = 3
+    y = np.random.default_rng(5).standard_normal((2, 24, N))
+    xd = np.zeros((2, 24, 1 + pad_N(N)))
+    xd[..., 0] = x
+    xd[..., 1:] = y
+    st, oa, _, _ = orc.household_block_het(xd[0], xd[1], ss.value, ss.D, pad_N(N))
+    assert st == 0
+    agg, dagg = orc.block_het(x, y, ss.value, ss.D)
+    assert agg.shape == (2, 24) and dagg.shape == (2, 24, N)
+    assert np.array_equal(agg, oa[..., 0]) and np.array_equal(dagg, oa[..., 1:])
+    assert np.array_equal(orc.block_het(x, None, ss.value, ss.D)[0], agg)
+
+
+def test_het_outputs_rows_and_the_value_rows_central_difference(ks_30x3):
+    """n_het = 3: rows 0 and 1 are block_het's bit for bit; row 2 (Value) agrees with a central difference of its own value
+    along the first direction, h = 1e-6: measured 2.7e-10 of the largest partial on the CPU oracle (truncation O(h^2) against
+    rounding eps/h, smallest at this h), bound 3e-9, a decade above."""
+    m, ss, orc, x = ks_30x3
+    y = np.random.default_rng(5).standard_normal((2, 24, 3))
+    agg, dagg = orc.het_outputs(x, y, ss.value, ss.D, 3, m.params.γ)
+    assert agg.shape == (3, 24) and dagg.shape == (3, 24, 3)
+    a2, d2 = orc.block_het(x, y, ss.value, ss.D)
+    assert np.array_equal(agg[:2], a2) and np.array_equal(dagg[:2], d2)
+    h, d = 1e-6, y[:, :, 0]
+    up, dn = (orc.het_outputs(x + s * h * d, None, ss.value, ss.D, 3, m.params.γ)[0][2] for s in (1.0, -1.0))
+    err = np.max(np.abs((up - dn) / (2 * h) - dagg[2][:, 0])) / np.max(np.abs(dagg[2][:, 0]))
+    print(f"Value row: central difference vs partial, relative to the largest partial: {err:.3e}")
+    assert err <= 3e-9

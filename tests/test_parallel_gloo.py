@@ -13,9 +13,8 @@ ROOT = Path(__file__).resolve().parent.parent
 
 
 def _worker(rank, world, port, N, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     try:
         from conftest import ks_paths, ks_setup
         from hank_amd.parallel import shard_bounds, sharded_jvp
@@ -40,9 +39,8 @@ def _worker(rank, world, port, N, ret):
 
 
 def _worker_cols(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, str(ROOT))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     try:
         from hank_amd.parallel import assemble_columns
         n = 13

@@ -2,11 +2,12 @@
 section 3d) are the exact transpose of the tangent recurrences of DESIGN.md section 1 — both maps stated in numpy here and
 compared on random linearisation records (two outputs, three inputs, a clamped prefix); (2) the host layers above the device
 (`LinearizedFunction.vjp`, `as_linear_operator`, `VJP`, `DeviceGroup.vjp`) with a stand-in block that multiplies by the CPU
-oracle's Jacobian of the household block at 30x3, T = 25; (3) the raw-grid economies of tests/vjp_cases.py hold, on the oracle's policy, the
+oracle's Jacobian of the household block at 30x3, T = 25; (3) the raw-grid economies of tests/cases.py hold, on the oracle's policy, the
 data-dependent edges tests/test_gpu_vjp_variants.py runs hank_vjp through: proven present without a GPU."""
 import numpy as np
 import pytest
 
+import cases as vc
 from conftest import ks_paths, ks_setup
 
 
@@ -128,23 +129,6 @@ def test_policy_cotangent_pairs_with_the_policy_partials():
 
 
 # ---- (2) the host layers with a stand-in block ------------------------------------------------------------------------------
-def _oracle_J(orc, ss, x_hh):
-    """J (P, n_hh P) of the policy variable's aggregate from unit tangents through the CPU oracle, 32 columns per pass;
-    column k + n_hh s = input k at period s (the layout of dxhh)."""
-    n_hh, P = x_hh.shape
-    J = np.zeros((P, n_hh * P))
-    for c0 in range(0, n_hh * P, 32):
-        c1 = min(n_hh * P, c0 + 32)
-        xd = np.zeros((n_hh, P, 33))
-        xd[..., 0] = x_hh
-        for c in range(c0, c1):
-            xd[c % n_hh, c // n_hh, 1 + c - c0] = 1.0
-        st, agg, _ = orc.household_block(xd[0], xd[1], ss.value, ss.D, 32)
-        assert st == 0
-        J[:, c0:c1] = agg[:, 1:1 + c1 - c0]
-    return J, agg[:, 0].copy()
-
-
 class _StubBlock:
     """stands in for the device context: jvp / vjp multiply by the oracle's J."""
     device = None
@@ -184,7 +168,9 @@ class _StubBlock:
 def stub_setup(hank, oracle_mod):
     m, ss, orc = ks_setup(30, 3, 25)
     x, Z = ks_paths(m, ss, "x1", 0.05)
-    J, agg = _oracle_J(orc, ss, x[2:4])
+    # J (P, n_hh P) of the policy variable's aggregate from unit tangents through the CPU oracle: column k + n_hh s = input k at
+    # period s (the layout of dxhh)
+    agg, J, _, _ = orc.block(x[2:4], vc.unit_tangents(2, m.compspec.T - 1), ss.value, ss.D)
     old = m._hip_block
     stub = _StubBlock(J, agg, 2, m.compspec.T - 1)
     m._hip_block = stub
@@ -255,15 +241,14 @@ def test_device_group_shards_cotangent_columns_like_tangent_columns(stub_setup):
 
 # ---- (3) the edge economies' preconditions ----------------------------------------------------------------------------------
 def test_edge_economies_hold_their_edges_on_the_oracles_policy(oracle_mod):
-    """each economy of vjp_cases.EDGE_GRIDS, on the CPU oracle's policy: a clamped prefix of 8 rows or more that is no multiple of
+    """each economy of cases.EDGE_GRIDS, on the CPU oracle's policy: a clamped prefix of 8 rows or more that is no multiple of
     the row-block count nb = ceil(n_a / R) at any tested width (and, over the economies, on both sides of nb); 8 or more sources
     clamped at the top; runs of rows in one bracket of length >= 5, odd and even. Prints what it measured (run with -s)."""
-    import vjp_cases as vc
     sides = {"clo_lt_nb": False, "clo_gt_nb": False}
     for name in vc.EDGE_GRIDS:
         ec = vc.raw_economy(name)
         assert np.all(np.diff(ec["grid"]) > 0)
-        got = vc.check_edges(name, ec["grid"], vc.oracle_policy(ec["orc"], ec["V"], ec["x"]))
+        got = vc.check_edges(name, ec["grid"], ec["orc"].block(ec["x"], None, ec["V"], ec["D"])[2])
         sides = {k: sides[k] or got[k] for k in sides}
     assert sides == {"clo_lt_nb": True, "clo_gt_nb": True}, sides
     assert [vc.adj_rows_per_block(M) for M in (1, 2, 3, 4, 5, 6, 8, 9, 16, 18, 32, 33)] == [64, 64, 16, 32, 8, 16, 16, 8, 8, 8, 8, 8]
