@@ -67,6 +67,33 @@ def solve(n_a=1000, n_e=7, T=500, shock=0.0025, rho=0.6, eps=1e-9, verbose=False
     return out, x, m, ss
 
 
+def gradient(n_a=1000, n_e=7, T=500, shock=0.0025, rho=0.6, spec="one_asset_hank_wages.yaml", chunk=256):
+    """The gradient of the merit function ½‖F(x)‖² at the Newton starting point (the steady state repeated, where F ≠ 0 under
+    the shock): ∇ = J(x)ᵀ F(x). Reverse mode: ONE transposed product at M = 1 (`LinearizedFunction.vjp_het`: hank_vjp_het on the
+    sticky-wage model, whose wage Phillips curve reads UCE; hank_vjp on the models with at most two device outputs). Forward
+    mode: the n unit tangents, of which n_hh·P move the household inputs and reach the device (hank_jvp and the outputs'
+    tangents, in batches of `chunk`). Prints both times and their agreement."""
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    m, ss = build(n_a, n_e, T, spec)
+    P = T - 1
+    keys = h.vars_of_type(m, "endogenous")
+    x0 = np.tile(np.array([ss.vars[k] for k in keys]), P)
+    lin = h.LinearizedFunction(x0, {"ei": shock * rho ** np.arange(P)}, m, ss, ss)
+    n = x0.size
+    lin.vjp_het(lin.Fx); lin.jvp(np.eye(n)[:, :chunk])                  # warm-up: workspaces, graphs, the residual layer's linearisation
+    t0 = time.perf_counter()
+    g_rev = lin.vjp_het(lin.Fx)
+    t_rev = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    g_fwd = np.concatenate([lin.Fx @ lin.jvp(np.eye(n)[:, c0:c0 + chunk]) for c0 in range(0, n, chunk)])
+    t_fwd = time.perf_counter() - t0
+    return {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "unknowns": n, "device_outputs": lin._n_out,
+            "merit": 0.5 * float(lin.Fx @ lin.Fx), "gradient_norm": float(np.linalg.norm(g_rev)),
+            "reverse_s": round(t_rev, 5), "reverse_vjps": 1, "forward_s": round(t_fwd, 5), "forward_jvp_columns": lin.hb.n_hh * P,
+            "max_abs_difference_over_max": float(np.max(np.abs(g_rev - g_fwd)) / np.max(np.abs(g_fwd)))}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-a", type=int, default=1000)
@@ -78,7 +105,11 @@ if __name__ == "__main__":
     ap.add_argument("--jacobian", default="toeplitz", choices=["toeplitz", "columns"])
     ap.add_argument("--spec", default="one_asset_hank.yaml", choices=["one_asset_hank.yaml", "one_asset_hank_goods.yaml",
                                                                  "one_asset_hank_wages.yaml"])
+    ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one transposed product against n_hh·P JVP columns")
     a = ap.parse_args()
+    if a.gradient:
+        print(json.dumps(gradient(a.n_a, a.n_e, a.T, a.shock, spec=a.spec)))
+        sys.exit(0)
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world > 1:

@@ -273,7 +273,7 @@ int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_o
  * bits.
  *   agg_bar (P, n_het, M) column-major: cotangents of the aggregates of output 0 (the policy variable, KD / A) and, with
  *   n_het = 2, of output 1 (consumption) — the shape of hank_get_het_outputs's dagg_out. Outputs 2 and 3 (Value, UCE) are
- *   not affine in the policy: n_het > 2 is refused with HANK_ERR_BAD_ARG.
+ *   not affine in the policy: n_het > 2 is refused here with HANK_ERR_BAD_ARG — hank_vjp_het below carries their cotangents.
  *   xhh_bar (n_hh, P, M) column-major: cotangents of the household inputs — the shape of dxhh.
  * Needs a valid record (HANK_ERR_NOT_READY before the first primal, after a new boundary, after a persistent sweep that did
  * not run), written by any kernel family; touches neither the record, nor the current tangent batch (hank_get_dpolicy_seq,
@@ -281,7 +281,18 @@ int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_o
  * context's stream and never waits on the host; the host form copies in, runs, copies out and synchronises. */
 int hank_vjp(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar);
 int hank_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar);
-/* The cotangent of the policy sequence of the last hank_vjp, out[(G, P, M)] column-major like hank_get_dpolicy_seq: the
+/* The same product with cotangents on EVERY heterogeneous output: agg_bar (P, n_het, M) with n_het up to the family's count (3 for
+ * Krusell-Smith: Value; 4 for the one-asset HANK: Value, UCE — the outputs of hank_get_het_outputs, which the reference dots with
+ * the same D_t, ForwardIteration.jl:303-307). Y^o_t = sum f_o,t D_t is not affine in the policy for o >= 2; its cotangent enters
+ * the reverse of the distribution sweep as a weight f_o,t on the distribution, a direct term -f_c,o,t D_t on the policy, and
+ * (Sa + Sr, Sz, S1)_o,t on the inputs, from f, f_c and the sums hank_get_het_outputs uses, recorded once per primal.
+ *   n_het above the family's count: HANK_ERR_BAD_ARG; above what hank_set_het_outputs declared: HANK_ERR_NOT_READY (the rule of
+ *   hank_get_het_outputs); n_het <= 2: hank_vjp's own path, the same bits.
+ * Everything else as hank_vjp: the record it needs, what it leaves alone, the workspace per batch width (shared with hank_vjp),
+ * hank_get_policy_cotangent_seq and hank_last_vjp_timings, the _dev form. */
+int hank_vjp_het(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar);
+int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar);
+/* The cotangent of the policy sequence of the last hank_vjp[_het], out[(G, P, M)] column-major like hank_get_dpolicy_seq: the
  * reference's `Δpolicy_seqs` (ForwardIteration.jl:412-416) for the policy variable when n_het = 1. With n_het = 2 it is the
  * TOTAL cotangent of the savings policy: consumption's dependence on it (-agg_bar[t, 1, m] D_t) is folded in. A new primal or
  * a new boundary makes it HANK_ERR_NOT_READY until the next hank_vjp (never the cotangents of an older primal). */

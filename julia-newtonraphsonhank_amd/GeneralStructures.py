@@ -265,7 +265,8 @@ def VJP(func, primal, cotangent):
     x = getattr(lin, "x", None)
     if x is not None and not np.array_equal(np.asarray(x), np.asarray(primal, dtype=np.float64)):
         raise ValueError("VJP: the linearisation was recorded at another primal")
-    return lin.vjp(np.asarray(cotangent, dtype=np.float64))
+    het = getattr(lin, "_n_out", 0) > 2 and hasattr(lin, "vjp_het")      # Value / UCE among the heterogeneous variables
+    return (lin.vjp_het if het else lin.vjp)(np.asarray(cotangent, dtype=np.float64))
 
 
 def RayleighQuotient(M, z):

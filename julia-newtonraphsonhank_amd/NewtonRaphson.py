@@ -166,7 +166,17 @@ class LinearizedFunction:
         if self._n_out > 2:
             raise NotImplementedError(
                 f"LinearizedFunction.vjp: the heterogeneous variables {self.het} reach {self.mod.value_fn.outputs[self._n_out - 1]!r} "
-                "(device output >= 2), which is not affine in the policy: hank_vjp carries cotangents on the policy variable and on consumption only")
+                "(device output >= 2), which is not affine in the policy: hank_vjp carries cotangents on the policy variable and on consumption only "
+                "(vjp_het carries them all)")
+        return self._vjp(ȳ, False)
+
+    def vjp_het(self, ȳ):
+        """`vjp` for every model: the same layers, with ONE hank_vjp_het in the middle when the heterogeneous variables reach
+        Value or UCE (device outputs >= 2, not affine in the policy). With at most two device outputs it goes through hank_vjp:
+        the same bits as `vjp`."""
+        return self._vjp(ȳ, self._n_out > 2)
+
+    def _vjp(self, ȳ, het: bool):
         ȳ = np.asarray(ȳ, dtype=np.float64)
         single = ȳ.ndim == 1
         Yb = ȳ[:, None] if single else ȳ
@@ -183,7 +193,11 @@ class LinearizedFunction:
         if len(nz):
             if getattr(self.hb, "_generation", None) != self._generation:
                 self._record_primal()           # (the same generation check as jvp: the context holds another x's record)
-            xb = self.hb.vjp(agg_bar[:, :, nz], self._n_out)                     # (n_hh, P, len(nz))
+            if het:
+                ensure_het_outputs(self.hb, self._n_out)
+                xb = self.hb.vjp_het(agg_bar[:, :, nz], self._n_out)
+            else:
+                xb = self.hb.vjp(agg_bar[:, :, nz], self._n_out)                 # (n_hh, P, len(nz))
             endog_keys = vars_of_type(self.mod, "endogenous")
             for k, name in enumerate(self.mod.value_fn.household_inputs):
                 if name in endog_keys:          # exogenous inputs carry no cotangent back to x; x is (n_endog, P) column-major
@@ -192,11 +206,13 @@ class LinearizedFunction:
 
     def as_linear_operator(self):
         """J(x) as a scipy.sparse.linalg.LinearOperator with both products: matvec / matmat = `jvp`, rmatvec / rmatmat = `vjp`
-        (LSQR / LSMR, BiCG, QMR and every other user of the transpose)."""
+        (`vjp_het` for a model whose heterogeneous variables reach Value or UCE) — LSQR / LSMR, BiCG, QMR and every other user of
+        the transpose."""
         n = len(self.x)
+        vjp = self.vjp_het if self._n_out > 2 else self.vjp
         col = lambda f: (lambda v: f(np.asarray(v, dtype=np.float64).reshape(-1)))
         mat = lambda f: (lambda V: f(np.asarray(V, dtype=np.float64)))
-        return spla.LinearOperator((len(self.Fx), n), matvec=col(self.jvp), matmat=mat(self.jvp), rmatvec=col(self.vjp), rmatmat=mat(self.vjp),
+        return spla.LinearOperator((len(self.Fx), n), matvec=col(self.jvp), matmat=mat(self.jvp), rmatvec=col(vjp), rmatmat=mat(vjp),
                                    dtype=np.float64)
 
 

@@ -20,7 +20,15 @@
 // [e][a][M] and pbar [P][G][M], cotangent index fastest; VT = double2 (two adjacent columns per lane, every state / pbar access
 // 16 bytes) for an even M, double otherwise. Block = one wave per productivity column, lanes = (column pair fastest, row).
 // No atomics: every sum has a fixed order, so the same record and cotangents give the same bits.
+//
+// Outputs 2, 3 (Value, UCE: hank_hetx.h) are not affine in the policy: Y^o_t = sum f_o,t D_t. Their cotangents (hank_vjp_het)
+// enter Sweep A in two places, NX = 1 or 2 of them at a time, from the record k_hx_record writes once per primal:
+//       lam        += sum_o ybx_o,t f_o,t                          (next to yb0 pol + yb1 c, before the Pi mix)
+//       pbar_t[j,e] -= sum_o ybx_o,t f_c,o,t[j,e] D_t[j,e]         (next to (yb0 - yb1) D_t)
+// and the household inputs' cotangents directly (k_adj_hx_out, after Sweep B): xbar_r += ybx_o,t (Sa + Sr), xbar_w += ybx_o,t Sz,
+// xbar_tr += ybx_o,t S1. Sweep B is the same: pbar carries everything it reads.
 #pragma once
+#include "hank_hetx.h"
 #include "hank_kernels.h"
 
 namespace hank {
@@ -38,6 +46,14 @@ __global__ void k_adj_in(const double *__restrict__ agg_bar, int P, int n_het, i
     const double *y = agg_bar + (size_t)t + (size_t)P * n_het * m;
     yb0[idx] = y[0];
     yb1[idx] = n_het > 1 ? y[P] : 0.0;
+}
+
+// agg_bar (P, n_het, M) column-major, outputs 2 .. n_het-1 -> ybx[P][NX][M], NX = n_het - 2
+__global__ void k_adj_in_hx(const double *__restrict__ agg_bar, int P, int n_het, int M, double *__restrict__ ybx) {
+    const int NX = n_het - 2, idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= P * NX * M) return;
+    const int t = idx / (NX * M), jx = (idx - t * NX * M) / M, m = idx - (t * NX + jx) * M;
+    ybx[idx] = agg_bar[(size_t)t + (size_t)P * ((2 + jx) + (size_t)n_het * m)];
 }
 
 // Segment starts of the interpolation brackets, once per record: sb[col][i] = first row a of column col = (t, e) with
@@ -84,11 +100,16 @@ __device__ __forceinline__ VT adj_rows_sum(VT v, int NC) {
 // [start[r0], start[r1]) that the recorded lottery sends to its rows — the transpose of the source-stationary forward kernel —
 // plus its share of the clamped prefix [0, clo) (sources that all read U[0] and whose policy cotangent has no lottery part:
 // shared out evenly over the row blocks). Every source row is written by exactly one block.
+// NX extra outputs (hx: nothing for NX = 0): a lane also reads f_o at its target rows, f_c,o at its source rows and ybx_o,t.
 // dynamic LDS: VT tile[n_e][R + 2][NC] (slot R + 1 = row 0), double Pish[n_e * n_e]
+template <typename VT, int NX>
+struct AdjHx { const double *f, *fc; const VT *ybx; };      // f, f_c [jx][P][G] and their stride P G (k_hx_record); ybx [P][NX][MV]
 template <typename VT>
+struct AdjHx<VT, 0> {};
+template <typename VT, int NX>
 __global__ void __launch_bounds__(1024)
 k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t, int first, const VT *__restrict__ yb0,
-           const VT *__restrict__ yb1, const VT *__restrict__ lamIn, VT *__restrict__ lamOut, VT *__restrict__ pbar) {
+           const VT *__restrict__ yb1, const VT *__restrict__ lamIn, VT *__restrict__ lamOut, VT *__restrict__ pbar, AdjHx<VT, NX> hx) {
     extern __shared__ __attribute__((aligned(16))) double adj_sh[];
     const int NS = g.R + 2, n = c.n_a, ne = c.n_e;
     VT *tile = reinterpret_cast<VT *>(adj_sh);
@@ -103,6 +124,15 @@ k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t,
     VT y0, y1;
     vzero(y0); vzero(y1);
     if (mok) { y0 = yb0[(size_t)t * MV + m]; y1 = yb1[(size_t)t * MV + m]; }
+    [[maybe_unused]] VT yx[NX > 0 ? NX : 1];
+    [[maybe_unused]] const size_t PG = (size_t)c.P * c.G;
+    if constexpr (NX > 0) {
+#pragma unroll
+        for (int o = 0; o < NX; o++) {
+            vzero(yx[o]);
+            if (mok) yx[o] = hx.ybx[((size_t)t * NX + o) * MV + m];
+        }
+    }
     const double r = xhh[c.n_hh * t], w = xhh[c.n_hh * t + 1], tr = hh_tr(c, xhh, t), ze = c.z[e];
     const size_t colb = (size_t)t * c.G + (size_t)e * n;      // (t, e) column of the record
     // 1. lam + yb0 pol + yb1 c of the block's rows, own column
@@ -117,6 +147,10 @@ k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t,
                 const double pol = R.pol[colb + row], cons = ((1.0 + r) * c.a[row] + (w * ze + tr)) - pol;
                 if (!first) v = lamIn[((size_t)e * n + row) * MV + m];
                 v = vadd(v, vadd(vmul(pol, y0), vmul(cons, y1)));
+                if constexpr (NX > 0) {
+#pragma unroll
+                    for (int o = 0; o < NX; o++) v = vadd(v, vmul(hx.f[o * PG + colb + row], yx[o]));
+                }
             }
             tile[((size_t)e * NS + slot) * g.NC + nl] = v;
         }
@@ -151,7 +185,12 @@ k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t,
         const double wj = R.lw[colb + j], gD = R.ig[colb + j] * Dprev[j], Dn = Dnext[j];
         const VT u0 = Ue[(size_t)sl * g.NC], u1 = Ue[(size_t)(sl + 1) * g.NC];
         st_mode<HANK_ST_STATE>(&lo_out[(size_t)j * MV], vadd(vmul(1.0 - wj, u0), vmul(wj, u1)));
-        st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], vadd(vmul(Dn, yd), vmul(gD, vsub(u1, u0))));
+        VT ye = yd;      // the policy's direct weight in the outputs, per unit of D_t: yb0 - yb1 - sum_o f_c,o ybx_o
+        if constexpr (NX > 0) {
+#pragma unroll
+            for (int o = 0; o < NX; o++) ye = vsub(ye, vmul(hx.fc[o * PG + colb + j], yx[o]));
+        }
+        st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], vadd(vmul(Dn, ye), vmul(gD, vsub(u1, u0))));
     }
     // 4. the block's share of the clamped prefix
     const int clo = min(max(R.clo[(size_t)t * ne + e], 0), n);
@@ -159,7 +198,12 @@ k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t,
     const VT U0 = Ue[(size_t)(g.R + 1) * g.NC];
     for (int j = c0 + rl; j < c1; j += RB) {
         st_mode<HANK_ST_STATE>(&lo_out[(size_t)j * MV], U0);
-        st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], vmul(Dnext[j], yd));
+        VT ye = yd;
+        if constexpr (NX > 0) {
+#pragma unroll
+            for (int o = 0; o < NX; o++) ye = vsub(ye, vmul(hx.fc[o * PG + colb + j], yx[o]));
+        }
+        st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], vmul(Dnext[j], ye));
     }
 }
 
@@ -281,6 +325,23 @@ __global__ void k_adj_out(int P, int n_hh, int M, int nb, const double *__restri
     out[0] = (mu[0] - rho * s[0]) + y1 * agg2[t];
     out[1] = (mu[1] - rho * s[1]) + y1 * zd[t];
     if (n_hh > 2) out[2] = (mu[2] - rho * s[2]) + y1 * zd[P + t];
+}
+
+// The extra outputs' direct dependence on the inputs, added to xhh_bar after k_adj_out, in output order:
+// ybx_o,t (Sa + Sr, Sz, S1) of k_hx_record's sums S [t][SX][HX_NS] (SX: the outputs the record holds). One thread per (t, column).
+__global__ void k_adj_hx_out(int P, int n_hh, int M, int NX, int SX, const double *__restrict__ ybx, const double *__restrict__ S,
+                             double *__restrict__ xhh_bar) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= P * M) return;
+    const int t = idx / M, m = idx - t * M;
+    double *out = xhh_bar + (size_t)n_hh * ((size_t)t + (size_t)P * m);
+    for (int o = 0; o < NX; o++) {
+        const double y = ybx[((size_t)t * NX + o) * M + m];
+        const double *s = S + ((size_t)t * SX + o) * HX_NS;      // Y, Sa, Sz, S1, Sr
+        out[0] += y * (s[1] + s[4]);
+        out[1] += y * s[2];
+        if (n_hh > 2) out[2] += y * s[3];
+    }
 }
 
 }  // namespace hank

@@ -140,13 +140,15 @@ struct CotWork {
     int N = 0;                      // the batch width M (the cache's key)
     int V = 1;                      // cotangent columns per lane
     AdjGeom g{};
-    DevBuf<double> ybar;            // (P, n_het <= 2, M) the caller's cotangents (staging for both entries)
+    DevBuf<double> ybar;            // (P, n_het, M) the caller's cotangents (staging for every entry; sized for the family's outputs)
     DevBuf<double> yb0, yb1;                    // [P][M] cotangents of the policy variable's aggregate and of consumption's
+    DevBuf<double> ybx;             // [P][NX][M] cotangents of outputs 2 .. (hank_vjp_het), sized for the family's largest NX
     DevBuf<double> st[2];                       // [G][M] ping-pong state: lam in Sweep A, then mu in Sweep B
     DevBuf<double> pbar;            // [P][G][M] the policy cotangent sequence: written once by Sweep A, read once by Sweep B
     DevBuf<double> partS, partM;                // [P][nb][3][M] per-block partial sums of the inputs' cotangents
     DevBuf<double> xbar;            // (n_hh, P, M) column-major
     GraphExec g_A, g_B;
+    GraphExec g_AX[2];              // Sweep A with NX = 1, 2 extra outputs (hank_vjp_het), captured on first use; Sweep B is g_B
 };
 // The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
 struct CotBatch {
@@ -248,6 +250,8 @@ struct hank_ctx {
     CotBatch cot;                  // the current cotangent batch (hank_get_policy_cotangent_seq)
     DevBuf<int> d_adj_sb;          // [P][n_e][n_a + 1] Sweep B's bracket segment starts (k_adj_seg), valid for the recorded primal or not
     bool adj_seg_valid = false;
+    DevBuf<double> d_adj_hxf, d_adj_hxfc, d_adj_hxS;     // [NX][P][G] f and f_c, [P][NX][HX_NS] sums of outputs 2 .. at the family's largest NX (k_hx_record), valid for the recorded primal or not
+    bool adj_hx_valid = false;
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
     long long stats[N_STATS] = {};   // see Stat and hank_stats
     // primal memo of the host-pointer hank_primal_jvp (NewtonRaphson.jl:91-95 calls JVP(fullFunction, x, y) ~21 times at one x):
@@ -283,7 +287,7 @@ static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
 // lwg_written: so were the per-source records {w, ig D} (the forward sweep writes them except the persistent Dual pass's)
 static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written) {
     ctx->primal_done = true; ctx->seg_valid = seg_written; ctx->lwg_valid = lwg_written;
-    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false;
+    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->adj_hx_valid = false;
     batch_none(ctx);
     cot_none(ctx);
 }
@@ -1964,9 +1968,11 @@ static int build_cotwork(hank_ctx *ctx, CotWork &w) {
     const int RB = 64 / g.NC;
     g.R = std::max(RB, 8);
     g.nb = (c.n_a + g.R - 1) / g.R;
-    HIPC(ctx, w.ybar.alloc(2 * P * M));
+    const size_t max_het = c.n_hh > 2 ? 4 : 3;
+    HIPC(ctx, w.ybar.alloc(max_het * P * M));
     HIPC(ctx, w.yb0.alloc(P * M));
     HIPC(ctx, w.yb1.alloc(P * M));
+    HIPC(ctx, w.ybx.alloc((max_het - 2) * P * M));      // (the NX > 0 graphs hold its address)
     for (int k = 0; k < 2; k++) HIPC(ctx, w.st[k].alloc(G * M));
     HIPC(ctx, w.pbar.alloc(P * G * M));
     HIPC(ctx, w.partS.alloc(P * (size_t)g.nb * 3 * M));
@@ -1979,28 +1985,46 @@ static size_t adj_lds_egm(const Consts &c, const AdjGeom &g, int V) {
     return sizeof(double) * ((size_t)c.n_e * g.R * g.NC * V + (((size_t)c.n_e * c.n_e + 1) & ~(size_t)1) + (size_t)c.n_e * 6 * g.NC * V);
 }
 
-// the two graphs of a width, captured the first time hank_vjp runs at it: Sweep A (P launches, t = P-1 .. 0) and Sweep B
-// (P launches, t = 0 .. P-1, then the fixed-order reduction of the inputs' cotangents)
-template <typename VT>
-static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
+// Sweep A's graph of a width with NX extra outputs (P launches, t = P-1 .. 0): hx = the record and cotangents of those outputs
+template <typename VT, int NX>
+static int capture_cot_graph_a(hank_ctx *ctx, CotWork &w, AdjHx<VT, NX> hx, GraphExec *out) {
     const Consts &c = ctx->c;
     const int P = c.P;
     hipStream_t s = ctx->own_stream;
     const dim3 blk(64 * c.n_e), grd((unsigned)w.g.nb, (unsigned)((w.g.MV + w.g.NC - 1) / w.g.NC));
-    const size_t ldsA = adj_lds_dist(c, w.g, w.V), ldsB = adj_lds_egm(c, w.g, w.V);
+    const size_t ldsA = adj_lds_dist(c, w.g, w.V);
     VT *st[2] = {reinterpret_cast<VT *>(w.st[0].get()), reinterpret_cast<VT *>(w.st[1].get())};
     VT *pbar = reinterpret_cast<VT *>(w.pbar.get());
     const VT *yb0 = reinterpret_cast<const VT *>(w.yb0.get()), *yb1 = reinterpret_cast<const VT *>(w.yb1.get());
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     int cur = 0;
     for (int t = P - 1; t >= 0; t--) {
-        hipLaunchKernelGGL((k_adj_dist<VT>), grd, blk, ldsA, s, c, ctx->R, ctx->d_xhh, w.g, t, t == P - 1 ? 1 : 0, yb0, yb1, st[cur], st[cur ^ 1], pbar);
+        hipLaunchKernelGGL((k_adj_dist<VT, NX>), grd, blk, ldsA, s, c, ctx->R, ctx->d_xhh, w.g, t, t == P - 1 ? 1 : 0, yb0, yb1, st[cur], st[cur ^ 1], pbar, hx);
         cur ^= 1;
     }
-    int rc = end_capture(ctx, &w.g_A);
+    return end_capture(ctx, out);
+}
+template <typename VT, int NX>
+static int capture_cot_graph_ax(hank_ctx *ctx, CotWork &w) {
+    const AdjHx<VT, NX> hx{ctx->d_adj_hxf.get(), ctx->d_adj_hxfc.get(), reinterpret_cast<const VT *>(w.ybx.get())};
+    return capture_cot_graph_a<VT, NX>(ctx, w, hx, &w.g_AX[NX - 1]);
+}
+
+// the two graphs of a width, captured the first time hank_vjp runs at it: Sweep A (NX = 0) and Sweep B (P launches,
+// t = 0 .. P-1, then the fixed-order reduction of the inputs' cotangents)
+template <typename VT>
+static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
+    const Consts &c = ctx->c;
+    const int P = c.P;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(64 * c.n_e), grd((unsigned)w.g.nb, (unsigned)((w.g.MV + w.g.NC - 1) / w.g.NC));
+    const size_t ldsB = adj_lds_egm(c, w.g, w.V);
+    VT *st[2] = {reinterpret_cast<VT *>(w.st[0].get()), reinterpret_cast<VT *>(w.st[1].get())};
+    VT *pbar = reinterpret_cast<VT *>(w.pbar.get());
+    int rc = capture_cot_graph_a<VT, 0>(ctx, w, AdjHx<VT, 0>{}, &w.g_A);
     if (rc) return rc;
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    cur = 0;
+    int cur = 0;
     for (int t = 0; t < P; t++) {
         hipLaunchKernelGGL((k_adj_egm<VT>), grd, blk, ldsB, s, c, ctx->R, w.g, t, t == 0 ? 1 : 0, t == P - 1 ? 1 : 0, ctx->d_adj_sb, st[cur], st[cur ^ 1], pbar,
                            reinterpret_cast<VT *>(w.partS.get()), reinterpret_cast<VT *>(w.partM.get()));
@@ -2021,11 +2045,27 @@ static int ensure_adj_seg(hank_ctx *ctx) {
     return HANK_OK;
 }
 
-// hank_vjp[_dev]: M cotangent columns from the caller (kind: where they live) through the transposed sweeps at the recorded
-// primal, whichever family recorded it. Touches neither the record nor the tangent batch nor the primal memo.
+// f, f_c and the direction-independent sums of outputs 2 .. (k_hx_record) belong to the record in the same way: built before the
+// first hank_vjp_het at a record, at the family's largest NX (the layout the NX > 0 graphs and k_adj_hx_out read)
+static int adj_hx_count(const hank_ctx *ctx) { return ctx->c.n_hh > 2 ? 2 : 1; }
+static int ensure_adj_hx(hank_ctx *ctx) {
+    const Consts &c = ctx->c;
+    if (ctx->adj_hx_valid) return HANK_OK;
+    const int SX = adj_hx_count(ctx);
+    hipLaunchKernelGGL(k_hx_record, dim3((unsigned)c.P, (unsigned)SX), dim3(256), 0, ctx->stream, c, ctx->R, ctx->d_xhh, SX, ctx->d_adj_hxf.get(),
+                       ctx->d_adj_hxfc.get(), ctx->d_adj_hxS.get());
+    HIPC(ctx, hipGetLastError());
+    ctx->adj_hx_valid = true;
+    return HANK_OK;
+}
+
+// hank_vjp[_dev], hank_vjp_het[_dev]: M cotangent columns from the caller (kind: where they live) through the transposed sweeps
+// at the recorded primal, whichever family recorded it. Touches neither the record nor the tangent batch nor the primal memo.
+// n_het > 2: Sweep A's graph with NX = n_het - 2 extra outputs, and their direct terms after Sweep B.
 static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
+    const int NX = n_het > 2 ? n_het - 2 : 0;
     CotWork *w = nullptr;
     int rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
     if (rc) return rc;
@@ -2036,17 +2076,39 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
         rc = w->V == 2 ? capture_cot_graphs<double2>(ctx, *w) : capture_cot_graphs<double>(ctx, *w);
         if (rc) return rc;
     }
+    if (NX > 0 && !w->g_AX[NX - 1]) {
+        if (!ctx->d_adj_hxf) {      // (the graphs hold their addresses)
+            const size_t SX = adj_hx_count(ctx);
+            HIPC(ctx, ctx->d_adj_hxf.alloc(SX * P * c.G));
+            HIPC(ctx, ctx->d_adj_hxfc.alloc(SX * P * c.G));
+            HIPC(ctx, ctx->d_adj_hxS.alloc(P * SX * HX_NS));
+            ctx->adj_hx_valid = false;
+        }
+        if (NX == 1) rc = w->V == 2 ? capture_cot_graph_ax<double2, 1>(ctx, *w) : capture_cot_graph_ax<double, 1>(ctx, *w);
+        else rc = w->V == 2 ? capture_cot_graph_ax<double2, 2>(ctx, *w) : capture_cot_graph_ax<double, 2>(ctx, *w);
+        if (rc) return rc;
+    }
     hipStream_t s = ctx->stream;
     HIPC(ctx, hipMemcpyAsync(w->ybar, agg_bar, sizeof(double) * P * n_het * M, kind, s));
     HIPC(ctx, join_side(ctx));      // D_t, the lottery and the grid aggregates come from the primal's forward sweep
     rc = ensure_adj_seg(ctx);
     if (rc) return rc;
+    if (NX > 0) {
+        rc = ensure_adj_hx(ctx);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(k_adj_in, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->yb0, w->yb1);
+    if (NX > 0) hipLaunchKernelGGL(k_adj_in_hx, dim3((unsigned)((P * NX * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->ybx.get());
     HIPC(ctx, ctx->spans.begin(VJP_A, s));
-    HIPC(ctx, hipGraphLaunch(w->g_A, s));
+    HIPC(ctx, hipGraphLaunch(NX > 0 ? w->g_AX[NX - 1] : w->g_A, s));
     HIPC(ctx, ctx->spans.end_begin(VJP_A, (int)P, VJP_B, s));
     HIPC(ctx, hipGraphLaunch(w->g_B, s));
     HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1));
+    if (NX > 0) {
+        hipLaunchKernelGGL(k_adj_hx_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, NX, adj_hx_count(ctx), w->ybx.get(),
+                           ctx->d_adj_hxS.get(), w->xbar.get());
+        HIPC(ctx, hipGetLastError());
+    }
     cot_ran(ctx, w, M, w->pbar);
     if (d_xhh_bar) HIPC(ctx, hipMemcpyAsync(d_xhh_bar, w->xbar, sizeof(double) * c.n_hh * P * M, hipMemcpyDeviceToDevice, s));
     *out = w;
@@ -2062,7 +2124,39 @@ static int vjp_args(hank_ctx *ctx, int n_het, const void *in, int M, const void 
     return HANK_OK;
 }
 
+// hank_vjp_het's rules: the family's count, then the declared count (the rule of hank_get_het_outputs), then the record
+static int vjp_het_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out) {
+    if (!ctx || !in || !out || M < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_het: bad argument (M=%d)", M);
+    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
+    if (n_het < 1 || n_het > max_het)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_het: n_het must be 1..%d (the policy variable, consumption, Value%s), got %d", max_het, max_het > 3 ? ", UCE" : "", n_het);
+    if (n_het > ctx->n_het) return fail(ctx, HANK_ERR_NOT_READY, "hank_vjp_het: %d outputs asked for, %d declared: call hank_set_het_outputs first", n_het, ctx->n_het);
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp_het");
+    return HANK_OK;
+}
+
 extern "C" {
+int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) {
+    ENTER(ctx);
+    int rc = vjp_het_args(ctx, n_het, d_agg_bar, M, d_xhh_bar);
+    if (rc) return rc;
+    CotWork *w = nullptr;
+    return enqueue_vjp(ctx, n_het, d_agg_bar, hipMemcpyDeviceToDevice, M, d_xhh_bar, &w);
+}
+
+int hank_vjp_het(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) {
+    ENTER(ctx);
+    int rc = vjp_het_args(ctx, n_het, agg_bar, M, xhh_bar);
+    if (rc) return rc;
+    CotWork *w = nullptr;
+    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w);
+    if (rc) return rc;
+    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
 int hank_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) {
     ENTER(ctx);
     int rc = vjp_args(ctx, n_het, d_agg_bar, M, d_xhh_bar);

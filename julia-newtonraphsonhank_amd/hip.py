@@ -29,7 +29,7 @@ ABI_SYMBOLS = (
     "hank_get_policy_seq", "hank_get_dpolicy_seq", "hank_get_dist_seq", "hank_get_het_outputs", "hank_get_het_outputs_dev", "hank_set_het_outputs",
     "hank_get_grid_aggregates", "hank_get_grid_aggregates_dev", "hank_backward_step",
     "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
-    "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings",
+    "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings", "hank_vjp_het", "hank_vjp_het_dev",
 )
 
 
@@ -118,6 +118,8 @@ def load_library() -> C.CDLL:
     lib.hank_device_available.argtypes = []
     lib.hank_vjp.argtypes = [vp, i32, dp, i32, dp]
     lib.hank_vjp_dev.argtypes = [vp, i32, vp, i32, vp]
+    lib.hank_vjp_het.argtypes = [vp, i32, dp, i32, dp]
+    lib.hank_vjp_het_dev.argtypes = [vp, i32, vp, i32, vp]
     lib.hank_get_policy_cotangent_seq.argtypes = [vp, i32, dp]
     lib.hank_last_vjp_timings.argtypes = [vp, dp, C.POINTER(i32)]
     for name in ABI_SYMBOLS:
@@ -305,8 +307,25 @@ class HouseholdBlock:
         """device-pointer form (asynchronous on the context's stream)."""
         self._chk(self._lib.hank_vjp_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr)))
 
+    def vjp_het(self, agg_bar, n_het: int) -> np.ndarray:
+        """`vjp` with cotangents on every heterogeneous output (hank_vjp_het): agg_bar (P, n_het, M), n_het up to the count
+        declared with `set_het_outputs` — outputs 2, 3 are Value and UCE, which are not affine in the policy.
+        -> xhh_bar (n_hh, P, M). n_het <= 2 runs `vjp`'s path: the same bits."""
+        yb = np.asarray(agg_bar, dtype=np.float64)
+        if yb.ndim != 3:
+            raise ValueError("agg_bar must be (P, n_het, M)")
+        M = yb.shape[2]
+        yb = _f(yb, (self.P, int(n_het), M) if 1 <= int(n_het) <= 4 else None)      # (the library refuses any other n_het)
+        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
+        self._chk(self._lib.hank_vjp_het(self._ctx, int(n_het), _p(yb), M, _p(out)))
+        return out
+
+    def vjp_het_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int):
+        """device-pointer form (asynchronous on the context's stream)."""
+        self._chk(self._lib.hank_vjp_het_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr)))
+
     def policy_cotangent_seq(self, M: int) -> np.ndarray:
-        """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp (hank_get_policy_cotangent_seq)."""
+        """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp / vjp_het (hank_get_policy_cotangent_seq)."""
         out = np.empty((self.n_a, self.n_e, self.P, max(int(M), 1)), order="F")
         self._chk(self._lib.hank_get_policy_cotangent_seq(self._ctx, int(M), _p(out)))
         return out

@@ -127,6 +127,16 @@ class DeviceGroup:
         parts = self._each(lambda b, lo, hi: b.vjp(yb[:, :, lo:hi], n_het) if hi > lo else np.empty((b0.n_hh, b0.P, 0)), bounds)
         return np.concatenate(parts, axis=2)
 
+    def vjp_het(self, agg_bar, n_het: int):
+        """`vjp` with cotangents on every heterogeneous output (HouseholdBlock.vjp_het), sharded the same way."""
+        import numpy as np
+        yb = np.asarray(agg_bar, dtype=np.float64)
+        M, W = yb.shape[2], len(self.blocks)
+        bounds = [shard_bounds(M, W, g) for g in range(W)]
+        b0 = self.blocks[0]
+        parts = self._each(lambda b, lo, hi: b.vjp_het(yb[:, :, lo:hi], n_het) if hi > lo else np.empty((b0.n_hh, b0.P, 0)), bounds)
+        return np.concatenate(parts, axis=2)
+
     def jvp_dev(self, d_y_blocks, N_k):
         """the same partition with everything on the devices: GPU g's tangent columns are already in its memory (`d_y_blocks[g]`: a
         torch tensor of (n_hh, P, N_k[g]) column-major values on that device), every context runs its sweeps asynchronously, and

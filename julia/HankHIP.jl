@@ -302,7 +302,17 @@ function hank_vjp!(xhh_bar::Array{Float64,3}, ctx::HankCtx, agg_bar::Array{Float
     return xhh_bar
 end
 
-# the cotangent of the policy sequence of the last hank_vjp!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
+# hank_vjp! with cotangents on every heterogeneous output (hank_vjp_het): n_het up to length(ctx.outputs) — ctx.outputs[3], [4] are
+# Value and UCE, which are not affine in the policy — and at most what hank_set_het_outputs declared. n_het <= 2: hank_vjp!'s bits.
+function hank_vjp_het!(xhh_bar::Array{Float64,3}, ctx::HankCtx, agg_bar::Array{Float64,3})
+    P, n_het, M = size(agg_bar)
+    @assert P == ctx.P && size(xhh_bar) == (length(ctx.hh_rows), P, M)
+    _check(ctx.ptr, ccall((:hank_vjp_het, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}),
+                          ctx.ptr, Int32(n_het), agg_bar, Int32(M), xhh_bar))
+    return xhh_bar
+end
+
+# the cotangent of the policy sequence of the last hank_vjp! / hank_vjp_het!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
 # (ForwardIteration.jl:412-416) for the policy variable when n_het = 1
 function hank_policy_cotangent_seq(ctx::HankCtx, M::Integer)
     out = Array{Float64}(undef, ctx.n_a, ctx.n_e, ctx.P, M)
@@ -314,7 +324,7 @@ end
 # mode: `agg, pb = ForwardIteration_pullback(seqs, model, ss_initial)`; `pb(Δagg)` takes the cotangents of the aggregates as a
 # NamedTuple keyed like `agg` (the shape of the reference's ForwardIteration_pullback argument, ForwardIteration.jl:387) and
 # returns the cotangent of the household inputs as an (n_hh, P) matrix (rows: ctx.hh_rows) — the device sweeps BackwardIteration
-# and ForwardIteration together, so the pullback covers both. Heterogeneous keys beyond consumption are refused by the library.
+# and ForwardIteration together, so the pullback covers both. Heterogeneous keys beyond consumption (Value, UCE) take hank_vjp_het!.
 function ForwardIteration_pullback(seqs::DevicePolicySeqs, model::SequenceModel, ss_initial)
     agg = ForwardIteration(seqs, model, ss_initial)             # records the primal the pullback is taken at
     ctx = hank_context(model)
@@ -326,7 +336,7 @@ function ForwardIteration_pullback(seqs::DevicePolicySeqs, model::SequenceModel,
             agg_bar[:, findfirst(==(k), ctx.outputs), 1] .= Δagg[k]
         end
         xhh_bar = Array{Float64}(undef, length(ctx.hh_rows), ctx.P, 1)
-        return hank_vjp!(xhh_bar, ctx, agg_bar)[:, :, 1]
+        return (n_het > 2 ? hank_vjp_het! : hank_vjp!)(xhh_bar, ctx, agg_bar)[:, :, 1]
     end
     return agg, pullback
 end
