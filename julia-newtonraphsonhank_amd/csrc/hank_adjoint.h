@@ -22,7 +22,8 @@
 // No atomics: every sum has a fixed order, so the same record and cotangents give the same bits.
 //
 // Outputs 2, 3 (Value, UCE: hank_hetx.h) are not affine in the policy: Y^o_t = sum f_o,t D_t. Their cotangents (hank_vjp_het)
-// enter Sweep A in two places, NX = 1 or 2 of them at a time, from the record k_hx_record writes once per primal:
+// enter Sweep A in two places, NX = 1 or 2 of them at a time, from the record k_hx_record writes once per primal (the context's
+// HxRecord, the one hank_get_het_outputs reads: ensure_hx_record, hank_hip.hip):
 //       lam        += sum_o ybx_o,t f_o,t                          (next to yb0 pol + yb1 c, before the Pi mix)
 //       pbar_t[j,e] -= sum_o ybx_o,t f_c,o,t[j,e] D_t[j,e]         (next to (yb0 - yb1) D_t)
 // and the household inputs' cotangents directly (k_adj_hx_out, after Sweep B): xbar_r += ybx_o,t (Sa + Sr), xbar_w += ybx_o,t Sz,

@@ -5,7 +5,8 @@
 //     Y_t  = sum f_t D_t
 //     dY_t = sum f_t dD_t - sum f_c,t D_t da'_t  +  dr_t (Sa_t + Sr_t) + dw_t Sz_t + dtr_t S1_t
 //     Sa_t = sum D_t f_c a, Sz_t = sum D_t f_c z_e, S1_t = sum D_t f_c, Sr_t = sum D_t df/dr|_c   (f_c = df/dc = -gamma f / c)
-// The last four do not depend on the direction (k_hx_record, one block per period and output). The first two need the
+// The last four do not depend on the direction (k_hx_record, one block per period and output: once per primal record, for the
+// tangent side here and the transposed sweeps of hank_adjoint.h alike — ensure_hx_record, hank_hip.hip). The first two need the
 // distribution tangent dD_t of every direction: k_hx_mid / k_hx_mix re-run the forward tangent recurrence (ForwardIteration.jl:
 // 37-99 under the Dual) from the policy partials the last tangent sweep left (any family, exported to one layout) and the
 // lottery record of the primal, as a deterministic gather over the source segments of each target row (no atomics: the same
@@ -26,7 +27,8 @@ __device__ inline void hx_f(int j, double gamma, double r, double z, double cons
     fc = -gamma * f / cons;
 }
 
-// grid (P, NX): f and f_c of every point (rec [jx][t][pt], 2 arrays) and the direction-independent sums (S [t][jx][HX_NS])
+// grid (P, NX): f and f_c of every point (rec [jx][t][pt], 2 arrays) and the direction-independent sums (S [t][jx][HX_NS]). Its one
+// caller passes the family's count of extra outputs; the readers index S with that count as the stride, whatever they ask for.
 __global__ void __launch_bounds__(256) k_hx_record(Consts c, Record R, const double *__restrict__ xhh, int NX,
                                                    double *__restrict__ fr_out, double *__restrict__ fc_out, double *__restrict__ S) {
     __shared__ double red[16];

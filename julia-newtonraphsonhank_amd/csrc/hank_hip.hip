@@ -158,6 +158,12 @@ struct CotBatch {
     const double *pbar = nullptr;   // view
 };
 
+// f, f_c and the direction-independent sums of the outputs that are not affine in the policy (2 Value, 3 UCE: k_hx_record), always
+// at the family's count SX (hx_count): f, fc [SX][P][G], S [P][SX][HX_NS]. They belong to the recorded primal: ensure_hx_record
+// builds them for whoever asks first (hx_outputs, enqueue_vjp) and record_rewritten drops them. Allocated at first use and never
+// again: the NX > 0 Sweep A graphs hold the addresses.
+struct HxRecord { DevBuf<double> f, fc, S; bool valid = false; };
+
 // The current tangent batch: at most ONE is current, and it belongs to the recorded primal. Written by batch_ran ("family F has
 // just run a batch on workspace W") and batch_none ("nothing is current") only; the readers ask batch_current.
 struct TanBatch {
@@ -250,8 +256,7 @@ struct hank_ctx {
     CotBatch cot;                  // the current cotangent batch (hank_get_policy_cotangent_seq)
     DevBuf<int> d_adj_sb;          // [P][n_e][n_a + 1] Sweep B's bracket segment starts (k_adj_seg), valid for the recorded primal or not
     bool adj_seg_valid = false;
-    DevBuf<double> d_adj_hxf, d_adj_hxfc, d_adj_hxS;     // [NX][P][G] f and f_c, [P][NX][HX_NS] sums of outputs 2 .. at the family's largest NX (k_hx_record), valid for the recorded primal or not
-    bool adj_hx_valid = false;
+    HxRecord hx;                   // the extra outputs' share of the record (ensure_hx_record), valid for the recorded primal or not
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
     long long stats[N_STATS] = {};   // see Stat and hank_stats
     // primal memo of the host-pointer hank_primal_jvp (NewtonRaphson.jl:91-95 calls JVP(fullFunction, x, y) ~21 times at one x):
@@ -261,7 +266,7 @@ struct hank_ctx {
     bool memo_valid = false;
     std::vector<double> memo_xhh;
     int n_het = 2;                                    // heterogeneous outputs the caller declared (hank_set_het_outputs; a change drops the memo)
-    DevBuf<char> hx_slab;                             // the extra outputs' buffers (hx_outputs), grown to the largest request, freed with the context
+    DevBuf<char> hx_slab;                             // the extra outputs' direction-dependent buffers (hx_outputs), grown to the largest request, freed with the context
     size_t hx_bytes = 0;
     bool stationary = false;                          // the recorded primal is the constant steady-state path with the steady state as both boundaries (hank_fake_news)
     std::vector<double> h_ss_value, h_ss_D;           // the boundary as the host handed it in (stationarity check)
@@ -270,6 +275,10 @@ struct hank_ctx {
 };
 
 static int fail(hank_ctx *ctx, int code, const char *fmt, ...);
+// heterogeneous outputs of the context's value-function family: the policy variable, consumption, Value, and UCE where there are
+// transfers; the last hx_count of them are not affine in the policy (hank_hetx.h)
+static int het_max(const hank_ctx *ctx) { return ctx->c.n_hh > 2 ? 4 : 3; }
+static int hx_count(const hank_ctx *ctx) { return het_max(ctx) - 2; }
 static void batch_none(hank_ctx *ctx) { ctx->batch.current = false; ctx->batch.ws = nullptr; }
 static void cot_none(hank_ctx *ctx) { ctx->cot = CotBatch(); }
 static void cot_ran(hank_ctx *ctx, const void *ws, int M, const double *pbar) { ctx->cot = CotBatch{true, M, ws, pbar}; }
@@ -287,7 +296,7 @@ static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
 // lwg_written: so were the per-source records {w, ig D} (the forward sweep writes them except the persistent Dual pass's)
 static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written) {
     ctx->primal_done = true; ctx->seg_valid = seg_written; ctx->lwg_valid = lwg_written;
-    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->adj_hx_valid = false;
+    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->hx.valid = false;
     batch_none(ctx);
     cot_none(ctx);
 }
@@ -310,6 +319,18 @@ static int fail(hank_ctx *ctx, int code, const char *fmt, ...) {
         va_end(ap);
     }
     return code;
+}
+
+// every entry that takes a count of heterogeneous outputs: above the family's count is a bad argument; above the declared count
+// (where the entry serves declared outputs only) the caller has to declare them first. rest_ok: the entry's other arguments, refused
+// in the same check as the count
+static int het_count_ok(hank_ctx *ctx, const char *who, int n_het, bool declared, bool rest_ok = true) {
+    const int max_het = het_max(ctx);
+    if (n_het < 1 || n_het > max_het || !rest_ok)
+        return fail(ctx, HANK_ERR_BAD_ARG, "%s: bad argument: n_het must be 1..%d (the policy variable, consumption, Value%s), got %d", who, max_het, max_het > 3 ? ", UCE" : "", n_het);
+    if (declared && n_het > ctx->n_het)
+        return fail(ctx, HANK_ERR_NOT_READY, "%s: %d outputs asked for, %d declared: call hank_set_het_outputs first", who, n_het, ctx->n_het);
+    return HANK_OK;
 }
 
 static int hip_status(hipError_t e) {
@@ -1817,10 +1838,8 @@ int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out) {
 int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out) {
     ENTER(ctx);
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
-    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
-    if (n_het < 1 || n_het > max_het)
-        return fail(ctx, HANK_ERR_BAD_ARG, "n_het must be 1..%d (the policy variable, consumption, Value%s)", max_het, max_het > 3 ? ", UCE" : "");
-    return fake_news(ctx, n_het, F_out, Dv_out);
+    const int rc = het_count_ok(ctx, "hank_fake_news_het", n_het, false);
+    return rc ? rc : fake_news(ctx, n_het, F_out, Dv_out);
 }
 
 #ifdef HANK_XSTAMP
@@ -1968,11 +1987,10 @@ static int build_cotwork(hank_ctx *ctx, CotWork &w) {
     const int RB = 64 / g.NC;
     g.R = std::max(RB, 8);
     g.nb = (c.n_a + g.R - 1) / g.R;
-    const size_t max_het = c.n_hh > 2 ? 4 : 3;
-    HIPC(ctx, w.ybar.alloc(max_het * P * M));
+    HIPC(ctx, w.ybar.alloc(het_max(ctx) * P * M));
     HIPC(ctx, w.yb0.alloc(P * M));
     HIPC(ctx, w.yb1.alloc(P * M));
-    HIPC(ctx, w.ybx.alloc((max_het - 2) * P * M));      // (the NX > 0 graphs hold its address)
+    HIPC(ctx, w.ybx.alloc(hx_count(ctx) * P * M));      // (the NX > 0 graphs hold its address)
     for (int k = 0; k < 2; k++) HIPC(ctx, w.st[k].alloc(G * M));
     HIPC(ctx, w.pbar.alloc(P * G * M));
     HIPC(ctx, w.partS.alloc(P * (size_t)g.nb * 3 * M));
@@ -2006,7 +2024,7 @@ static int capture_cot_graph_a(hank_ctx *ctx, CotWork &w, AdjHx<VT, NX> hx, Grap
 }
 template <typename VT, int NX>
 static int capture_cot_graph_ax(hank_ctx *ctx, CotWork &w) {
-    const AdjHx<VT, NX> hx{ctx->d_adj_hxf.get(), ctx->d_adj_hxfc.get(), reinterpret_cast<const VT *>(w.ybx.get())};
+    const AdjHx<VT, NX> hx{ctx->hx.f.get(), ctx->hx.fc.get(), reinterpret_cast<const VT *>(w.ybx.get())};
     return capture_cot_graph_a<VT, NX>(ctx, w, hx, &w.g_AX[NX - 1]);
 }
 
@@ -2045,17 +2063,21 @@ static int ensure_adj_seg(hank_ctx *ctx) {
     return HANK_OK;
 }
 
-// f, f_c and the direction-independent sums of outputs 2 .. (k_hx_record) belong to the record in the same way: built before the
-// first hank_vjp_het at a record, at the family's largest NX (the layout the NX > 0 graphs and k_adj_hx_out read)
-static int adj_hx_count(const hank_ctx *ctx) { return ctx->c.n_hh > 2 ? 2 : 1; }
-static int ensure_adj_hx(hank_ctx *ctx) {
+// the extra outputs' share belongs to the record in the same way: built before the first reader at a record (hx_outputs,
+// enqueue_vjp: after join_side, the sums read D_t), whichever product asks first. The only launch of k_hx_record.
+static int ensure_hx_record(hank_ctx *ctx) {
     const Consts &c = ctx->c;
-    if (ctx->adj_hx_valid) return HANK_OK;
-    const int SX = adj_hx_count(ctx);
-    hipLaunchKernelGGL(k_hx_record, dim3((unsigned)c.P, (unsigned)SX), dim3(256), 0, ctx->stream, c, ctx->R, ctx->d_xhh, SX, ctx->d_adj_hxf.get(),
-                       ctx->d_adj_hxfc.get(), ctx->d_adj_hxS.get());
+    HxRecord &h = ctx->hx;
+    if (h.valid) return HANK_OK;
+    const size_t P = c.P, SX = hx_count(ctx);
+    if (!h.S) {
+        HIPC(ctx, h.f.alloc(SX * P * c.G));
+        HIPC(ctx, h.fc.alloc(SX * P * c.G));
+        HIPC(ctx, h.S.alloc(P * SX * HX_NS));
+    }
+    hipLaunchKernelGGL(k_hx_record, dim3((unsigned)P, (unsigned)SX), dim3(256), 0, ctx->stream, c, ctx->R, ctx->d_xhh, (int)SX, h.f.get(), h.fc.get(), h.S.get());
     HIPC(ctx, hipGetLastError());
-    ctx->adj_hx_valid = true;
+    h.valid = true;
     return HANK_OK;
 }
 
@@ -2076,26 +2098,19 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
         rc = w->V == 2 ? capture_cot_graphs<double2>(ctx, *w) : capture_cot_graphs<double>(ctx, *w);
         if (rc) return rc;
     }
-    if (NX > 0 && !w->g_AX[NX - 1]) {
-        if (!ctx->d_adj_hxf) {      // (the graphs hold their addresses)
-            const size_t SX = adj_hx_count(ctx);
-            HIPC(ctx, ctx->d_adj_hxf.alloc(SX * P * c.G));
-            HIPC(ctx, ctx->d_adj_hxfc.alloc(SX * P * c.G));
-            HIPC(ctx, ctx->d_adj_hxS.alloc(P * SX * HX_NS));
-            ctx->adj_hx_valid = false;
-        }
-        if (NX == 1) rc = w->V == 2 ? capture_cot_graph_ax<double2, 1>(ctx, *w) : capture_cot_graph_ax<double, 1>(ctx, *w);
-        else rc = w->V == 2 ? capture_cot_graph_ax<double2, 2>(ctx, *w) : capture_cot_graph_ax<double, 2>(ctx, *w);
-        if (rc) return rc;
-    }
     hipStream_t s = ctx->stream;
     HIPC(ctx, hipMemcpyAsync(w->ybar, agg_bar, sizeof(double) * P * n_het * M, kind, s));
     HIPC(ctx, join_side(ctx));      // D_t, the lottery and the grid aggregates come from the primal's forward sweep
     rc = ensure_adj_seg(ctx);
     if (rc) return rc;
     if (NX > 0) {
-        rc = ensure_adj_hx(ctx);
+        rc = ensure_hx_record(ctx);      // (before the capture: the graph holds the record's addresses)
         if (rc) return rc;
+        if (!w->g_AX[NX - 1]) {
+            if (NX == 1) rc = w->V == 2 ? capture_cot_graph_ax<double2, 1>(ctx, *w) : capture_cot_graph_ax<double, 1>(ctx, *w);
+            else rc = w->V == 2 ? capture_cot_graph_ax<double2, 2>(ctx, *w) : capture_cot_graph_ax<double, 2>(ctx, *w);
+            if (rc) return rc;
+        }
     }
     hipLaunchKernelGGL(k_adj_in, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->yb0, w->yb1);
     if (NX > 0) hipLaunchKernelGGL(k_adj_in_hx, dim3((unsigned)((P * NX * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->ybx.get());
@@ -2105,8 +2120,8 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     HIPC(ctx, hipGraphLaunch(w->g_B, s));
     HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1));
     if (NX > 0) {
-        hipLaunchKernelGGL(k_adj_hx_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, NX, adj_hx_count(ctx), w->ybx.get(),
-                           ctx->d_adj_hxS.get(), w->xbar.get());
+        hipLaunchKernelGGL(k_adj_hx_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, NX, hx_count(ctx), w->ybx.get(),
+                           ctx->hx.S.get(), w->xbar.get());
         HIPC(ctx, hipGetLastError());
     }
     cot_ran(ctx, w, M, w->pbar);
@@ -2116,8 +2131,7 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
 }
 static int vjp_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out) {
     if (!ctx || !in || !out || M < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: bad argument (M=%d)", M);
-    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
-    if (n_het > 2 && n_het <= max_het)
+    if (n_het > 2 && n_het <= het_max(ctx))
         return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_het=%d reaches Value / UCE, which are not affine in the policy: their cotangents are not implemented (n_het must be 1 or 2)", n_het);
     if (n_het < 1 || n_het > 2) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_het must be 1 (the policy variable) or 2 (and consumption), got %d", n_het);
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp");
@@ -2127,56 +2141,31 @@ static int vjp_args(hank_ctx *ctx, int n_het, const void *in, int M, const void 
 // hank_vjp_het's rules: the family's count, then the declared count (the rule of hank_get_het_outputs), then the record
 static int vjp_het_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out) {
     if (!ctx || !in || !out || M < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_het: bad argument (M=%d)", M);
-    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
-    if (n_het < 1 || n_het > max_het)
-        return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_het: n_het must be 1..%d (the policy variable, consumption, Value%s), got %d", max_het, max_het > 3 ? ", UCE" : "", n_het);
-    if (n_het > ctx->n_het) return fail(ctx, HANK_ERR_NOT_READY, "hank_vjp_het: %d outputs asked for, %d declared: call hank_set_het_outputs first", n_het, ctx->n_het);
+    const int rc = het_count_ok(ctx, "hank_vjp_het", n_het, true);
+    if (rc) return rc;
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp_het");
     return HANK_OK;
 }
 
+// the four entries' one body: args is the entry's rule; the _dev form leaves the copy to enqueue_vjp and stays asynchronous
+static int vjp(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, const void *), int n_het, const double *agg_bar, int M, double *xhh_bar, bool dev) {
+    ENTER(ctx);
+    int rc = args(ctx, n_het, agg_bar, M, xhh_bar);
+    if (rc) return rc;
+    CotWork *w = nullptr;
+    rc = enqueue_vjp(ctx, n_het, agg_bar, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, M, dev ? xhh_bar : nullptr, &w);
+    if (rc || dev) return rc;
+    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
 extern "C" {
-int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) {
-    ENTER(ctx);
-    int rc = vjp_het_args(ctx, n_het, d_agg_bar, M, d_xhh_bar);
-    if (rc) return rc;
-    CotWork *w = nullptr;
-    return enqueue_vjp(ctx, n_het, d_agg_bar, hipMemcpyDeviceToDevice, M, d_xhh_bar, &w);
-}
-
-int hank_vjp_het(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) {
-    ENTER(ctx);
-    int rc = vjp_het_args(ctx, n_het, agg_bar, M, xhh_bar);
-    if (rc) return rc;
-    CotWork *w = nullptr;
-    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
-}
-
-int hank_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) {
-    ENTER(ctx);
-    int rc = vjp_args(ctx, n_het, d_agg_bar, M, d_xhh_bar);
-    if (rc) return rc;
-    CotWork *w = nullptr;
-    return enqueue_vjp(ctx, n_het, d_agg_bar, hipMemcpyDeviceToDevice, M, d_xhh_bar, &w);
-}
-
-int hank_vjp(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) {
-    ENTER(ctx);
-    int rc = vjp_args(ctx, n_het, agg_bar, M, xhh_bar);
-    if (rc) return rc;
-    CotWork *w = nullptr;
-    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
-}
+int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) { return vjp(ctx, vjp_het_args, n_het, d_agg_bar, M, d_xhh_bar, true); }
+int hank_vjp_het(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) { return vjp(ctx, vjp_het_args, n_het, agg_bar, M, xhh_bar, false); }
+int hank_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) { return vjp(ctx, vjp_args, n_het, d_agg_bar, M, d_xhh_bar, true); }
+int hank_vjp(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) { return vjp(ctx, vjp_args, n_het, agg_bar, M, xhh_bar, false); }
 
 int hank_get_policy_cotangent_seq(hank_ctx *ctx, int32_t M, double *out) {
     if (!ctx || !out) return HANK_ERR_BAD_ARG;
@@ -2274,8 +2263,9 @@ static int granular_backward(hank_ctx *ctx, const double *value_next, const doub
 // - a' (KrusellSmith.jl:80): its aggregate is affine in what the sweeps already reduce,
 //     C_t  = (1+r_t) AD_t + w_t ZD_t + tr_t MD_t - KD_t,      AD_t = sum a D_t (the grid-weighted aggregate), ZD_t = sum z_e D_t, MD_t = sum D_t
 //     dC_t = dr_t AD_t + dw_t ZD_t + dtr_t MD_t + (1+r_t) dAD_t - dKD_t      (ZD_t, MD_t carry no partials: see hank_set_boundary)
-// agg (P, 2) and dagg (P, 2 N) as the sweeps leave them -> out_agg (P, n_het), out_dagg (P, n_het, N) column-major.
-__global__ void k_het_outputs(int P, int n_hh, int n_het, int N, const double *__restrict__ xhh, const double *__restrict__ dxhh,
+// agg (P, 2) and dagg (P, 2 N) as the sweeps leave them -> out_agg (P, n_het), out_dagg (P, n_het, N) column-major. hxS: the
+// record's sums [t][SX][HX_NS] (SX: the outputs the record holds); hxT: the call's in-period sums [n][t][NX].
+__global__ void k_het_outputs(int P, int n_hh, int n_het, int SX, int N, const double *__restrict__ xhh, const double *__restrict__ dxhh,
                               const double *__restrict__ agg, const double *__restrict__ dagg, const double *__restrict__ zd,
                               const double *__restrict__ hxS, const double *__restrict__ hxT,
                               double *__restrict__ out_agg, double *__restrict__ out_dagg) {
@@ -2289,7 +2279,7 @@ __global__ void k_het_outputs(int P, int n_hh, int n_het, int N, const double *_
         if (!out_agg) return;
         out_agg[t] = KD;
         if (n_het > 1) out_agg[P + t] = ((1.0 + r) * AD + w * ZD + tr * MD) - KD;
-        for (int jx = 0; jx < NX; jx++) out_agg[(size_t)(2 + jx) * P + t] = hxS[((size_t)t * NX + jx) * HX_NS];
+        for (int jx = 0; jx < NX; jx++) out_agg[(size_t)(2 + jx) * P + t] = hxS[((size_t)t * SX + jx) * HX_NS];
         return;
     }
     if (!out_dagg) return;
@@ -2299,20 +2289,25 @@ __global__ void k_het_outputs(int P, int n_hh, int n_het, int N, const double *_
     out_dagg[((size_t)n * n_het) * P + t] = dKD;
     if (n_het > 1) out_dagg[((size_t)n * n_het + 1) * P + t] = (dx[0] * AD + dx[1] * ZD + dtr * MD + (1.0 + r) * dAD) - dKD;
     for (int jx = 0; jx < NX; jx++) {
-        const double *S = hxS + ((size_t)t * NX + jx) * HX_NS;      // Y, Sa, Sz, S1, Sr
+        const double *S = hxS + ((size_t)t * SX + jx) * HX_NS;      // Y, Sa, Sz, S1, Sr
         out_dagg[((size_t)n * n_het + 2 + jx) * P + t] = hxT[((size_t)n * P + t) * NX + jx] + dx[0] * (S[1] + S[4]) + dx[1] * S[2] + dtr * S[3];
     }
 }
 
-// outputs 2 .. n_het-1: the direction-independent sums (S), and — for N > 0 — the in-period sums of every direction (T) from one
-// forward tangent recurrence over the exported policy partials (hank_hetx.h). The buffers live in the context (hx_slab: one
-// allocation, grown when a wider batch asks, reused in stream order), so the _dev form stays asynchronous.
-static int hx_outputs(hank_ctx *ctx, int NX, const TanBatch *b, double **S_out, double **T_out) {      // b: the current batch, or nullptr (no tangents asked for)
+// outputs 2 .. n_het-1: for N > 0 the in-period sums of every direction (T) from one forward tangent recurrence over the exported
+// policy partials (hank_hetx.h) and the record's f, f_c (ensure_hx_record, which also holds the direction-independent sums). The
+// direction-dependent buffers live in the context (hx_slab: one allocation, grown when a wider batch asks, reused in stream
+// order), so the _dev form stays asynchronous.
+static int hx_outputs(hank_ctx *ctx, int NX, const TanBatch *b, double **T_out) {      // b: the current batch, or nullptr (no tangents asked for)
     const Consts &c = ctx->c;
     const int N = b ? b->N : 0;
     const size_t P = c.P, G = c.G;
     const int nbr = (c.n_a + HX_ROWS - 1) / HX_ROWS;
-    const size_t sz[8] = {NX * P * G, NX * P * G, P * NX * HX_NS, P * G * N, G * N, G * N, (size_t)N * P * nbr * NX, (size_t)N * P * NX};
+    int rc = ensure_hx_record(ctx);
+    if (rc) return rc;
+    *T_out = nullptr;
+    if (N == 0) return HANK_OK;
+    const size_t sz[5] = {P * G * N, G * N, G * N, (size_t)N * P * nbr * NX, (size_t)N * P * NX};
     size_t need = 0, off = 0;
     for (size_t k : sz) carve(need, sizeof(double) * k);
     if (need > ctx->hx_bytes) {
@@ -2321,21 +2316,15 @@ static int hx_outputs(hank_ctx *ctx, int NX, const TanBatch *b, double **S_out, 
         HIPC(ctx, ctx->hx_slab.alloc(need));
         ctx->hx_bytes = need;
     }
-    double *buf[8];      // views
-    for (int k = 0; k < 8; k++) buf[k] = reinterpret_cast<double *>(ctx->hx_slab + carve(off, sizeof(double) * sz[k]));
-    double *f = buf[0], *fc = buf[1], *S = buf[2];
-    hipLaunchKernelGGL(k_hx_record, dim3((unsigned)P, (unsigned)NX), dim3(256), 0, ctx->stream, c, ctx->R, ctx->d_xhh, NX, f, fc, S);
-    HIPC(ctx, hipGetLastError());
-    *S_out = S;
-    *T_out = nullptr;
-    if (N == 0) return HANK_OK;
-    double *dpc = buf[3], *mid = buf[4], *dD = buf[5], *parts = buf[6], *T = buf[7];
-    int rc = export_dpol_dev(ctx, *b, dpc);
+    double *buf[5];      // views
+    for (int k = 0; k < 5; k++) buf[k] = reinterpret_cast<double *>(ctx->hx_slab + carve(off, sizeof(double) * sz[k]));
+    double *dpc = buf[0], *mid = buf[1], *dD = buf[2], *parts = buf[3], *T = buf[4];
+    rc = export_dpol_dev(ctx, *b, dpc);
     if (rc) return rc;
     const dim3 gmid((unsigned)((G + HX_ROWS - 1) / HX_ROWS), (unsigned)N), gmix((unsigned)nbr, (unsigned)N);
     for (size_t t = 0; t < P; t++) {
         hipLaunchKernelGGL(k_hx_mid, gmid, dim3(HX_ROWS), 0, ctx->stream, c, ctx->R, (int)t, dpc, dD, mid);
-        hipLaunchKernelGGL(k_hx_mix, gmix, dim3(HX_ROWS), 0, ctx->stream, c, ctx->R, (int)t, NX, dpc, mid, f, fc, dD, parts);
+        hipLaunchKernelGGL(k_hx_mix, gmix, dim3(HX_ROWS), 0, ctx->stream, c, ctx->R, (int)t, NX, dpc, mid, ctx->hx.f.get(), ctx->hx.fc.get(), dD, parts);
     }
     const size_t cnt = (size_t)N * P * NX;
     hipLaunchKernelGGL(k_hx_reduce, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, parts, nbr, NX, cnt, T);
@@ -2347,17 +2336,15 @@ static int hx_outputs(hank_ctx *ctx, int NX, const TanBatch *b, double **S_out, 
 static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double *agg_out, double *dagg_out, bool dev) {
     if (!ctx) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
-    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
-    if (n_het < 1 || n_het > max_het || N < 0 || (!agg_out && !dagg_out))
-        return fail(ctx, HANK_ERR_BAD_ARG, "n_het must be 1..%d (the policy variable, consumption, Value%s), N >= 0", max_het, max_het > 3 ? ", UCE" : "");
-    if (n_het > ctx->n_het) return fail(ctx, HANK_ERR_NOT_READY, "%d outputs asked for, %d declared: call hank_set_het_outputs first", n_het, ctx->n_het);
+    int rc = het_count_ok(ctx, "hank_get_het_outputs", n_het, true, N >= 0 && (agg_out || dagg_out));      // (N >= 0, an output array)
+    if (rc) return rc;
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
     const size_t P = ctx->c.P, nh = ctx->c.n_hh;
     const bool tan = dagg_out && N > 0;
     if (tan && !dxhh) return fail(ctx, HANK_ERR_BAD_ARG, "the tangent outputs need the dxhh of the last tangent sweep");
     const TanBatch *b = nullptr;
     if (tan) {
-        const int rc = batch_current(ctx, N, &b);
+        rc = batch_current(ctx, N, &b);
         if (rc) return rc;
     }
     HIPC(ctx, join_side(ctx));
@@ -2375,13 +2362,13 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
         if (agg_out) HIPC(ctx, sc.alloc(&d_a, P * n_het));
     }
     const int Nk = tan ? N : 0;
-    double *hxS = nullptr, *hxT = nullptr;
+    double *hxT = nullptr;
     if (n_het > 2) {
-        int rc = hx_outputs(ctx, n_het - 2, b, &hxS, &hxT);
+        rc = hx_outputs(ctx, n_het - 2, b, &hxT);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * (Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, Nk, ctx->d_xhh,
-                       d_dx, ctx->d_agg, b ? b->dagg_cm : nullptr, ctx->d_zd, hxS, hxT, d_a, tan ? d_da : nullptr);
+    hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * (Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, hx_count(ctx), Nk, ctx->d_xhh,
+                       d_dx, ctx->d_agg, b ? b->dagg_cm : nullptr, ctx->d_zd, ctx->hx.S.get(), hxT, d_a, tan ? d_da : nullptr);
     HIPC(ctx, hipGetLastError());
     if (!dev) {
         if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, d_a, sizeof(double) * P * n_het, hipMemcpyDeviceToHost, ctx->stream));
@@ -2400,8 +2387,8 @@ int hank_get_het_outputs_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh,
 int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het) {
     if (!ctx) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
-    const int max_het = ctx->c.n_hh > 2 ? 4 : 3;
-    if (n_het < 1 || n_het > max_het) return fail(ctx, HANK_ERR_BAD_ARG, "n_het must be 1..%d for this value-function family", max_het);
+    const int rc = het_count_ok(ctx, "hank_set_het_outputs", n_het, false);
+    if (rc) return rc;
     if (n_het != ctx->n_het) ctx->memo_valid = false;      // the next hank_primal_jvp records its primal afresh
     ctx->n_het = n_het;
     return HANK_OK;

@@ -5,7 +5,8 @@
 1. tests/test_gpu_lifetime.py's churn: three cycles over the four schedules of create, every entry, close, close;
 2. its eviction sequence under HANK_TAN_CACHE=1, every schedule: hank_jvp at N = 2, 3 and hank_vjp at M = 2, 3, four times each;
 3. at a steady state (Krusell-Smith 50x2, T = 20; the default schedule and the launches): hank_fake_news, hank_fake_news_het (the
-   workspace grows), the non-affine outputs (hx_slab, grown once), hank_vfi, hank_stationary_dist and the four granular steps."""
+   workspace grows), the non-affine outputs (the record's f, f_c and S, allocated once per context; hx_slab's
+   direction-dependent buffers, grown once), hank_vfi, hank_stationary_dist and the four granular steps."""
 import os
 import sys
 from pathlib import Path

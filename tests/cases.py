@@ -5,7 +5,8 @@ device context.
 0. the owners: `close` (the suite's only tolerance function), `raw_block` / `block` (a context under HANK_* variables, every
    variable restored), `model_args` / `oracle_of` (a model's constructor arguments), `hank_economy` / `hank_x` (the one-asset HANK
    economy and its input path). The oracle's references are methods of oracle.oracle.Oracle: block, block_het, het_outputs, vfi;
-1. the references of hank_vjp: the CPU oracle's Jacobian from unit tangents (`oracle_jacobian`, transposed by `jt`) and the numpy
+1. the references of hank_vjp[_het]: the CPU oracle's Jacobian from unit tangents (`oracle_jacobian`, `oracle_jacobian_het` /
+   `jacobian_het` for every heterogeneous output, transposed by `jt`) and the numpy
    restatement of the reference's ForwardIteration_pullback for Sweep A alone (`forward_iteration_pullback`);
 2. the economies of the variant suite: `economy` (a curvature, its own host steady state), `shape` (a grid shape with a cheap
    valid boundary), `CASES` (curvature x record layout);
@@ -104,6 +105,25 @@ def oracle_jacobian(orc, value, D, x):
     n_hh, P = x.shape
     _, dagg = orc.block_het(x, unit_tangents(n_hh, P), value, D)
     return np.ascontiguousarray(dagg.reshape(2, P, P, n_hh).transpose(0, 1, 3, 2))
+
+
+def oracle_jacobian_het(orc, value, D, x, n_het, gamma):
+    """J (n_het, P, n_hh, P): d output o at t / d input k at s, from unit tangents through Oracle.het_outputs, 32 columns per pass"""
+    n_hh, P = x.shape
+    y = unit_tangents(n_hh, P)
+    dagg = np.concatenate([orc.het_outputs(x, y[:, :, c0:c0 + 32], value, D, n_het, gamma)[1] for c0 in range(0, n_hh * P, 32)], axis=2)
+    return np.ascontiguousarray(dagg.reshape(n_het, P, P, n_hh).transpose(0, 1, 3, 2))
+
+
+_JHET = {}
+
+
+def jacobian_het(key, orc, V, D, x, n_het, gamma):
+    """`oracle_jacobian_het` of a case, once per session and key; every output's block must be non-trivial"""
+    if key not in _JHET:
+        _JHET[key] = oracle_jacobian_het(orc, V, D, x, n_het, gamma)
+        assert all(np.abs(_JHET[key][o]).max() > 1e-3 for o in range(n_het)), key
+    return _JHET[key]
 
 
 def jt(J, yb):

@@ -11,29 +11,12 @@ import numpy as np
 import pytest
 
 import cases
-from cases import block as _block, close as _close, jt as _jt
+from cases import block as _block, close as _close, jacobian_het as _jac, jt as _jt
 from conftest import ks_paths, ks_setup
 
 pytestmark = pytest.mark.gpu
 
 WIDTHS = (1, 5, 32, 33)
-_J = {}
-
-
-def oracle_jacobian_het(orc, value, D, x, n_het, gamma):
-    """J (n_het, P, n_hh, P): d output o at t / d input k at s, from unit tangents through Oracle.het_outputs, 32 columns per pass"""
-    n_hh, P = x.shape
-    y = cases.unit_tangents(n_hh, P)
-    dagg = np.concatenate([orc.het_outputs(x, y[:, :, c0:c0 + 32], value, D, n_het, gamma)[1] for c0 in range(0, n_hh * P, 32)], axis=2)
-    return np.ascontiguousarray(dagg.reshape(n_het, P, P, n_hh).transpose(0, 1, 3, 2))
-
-
-def _jac(key, orc, V, D, x, n_het, gamma):
-    """the oracle's Jacobian of a case, once per session"""
-    if key not in _J:
-        _J[key] = oracle_jacobian_het(orc, V, D, x, n_het, gamma)
-        assert all(np.abs(_J[key][o]).max() > 1e-3 for o in range(n_het)), key
-    return _J[key]
 
 
 def _ks_case():

@@ -191,14 +191,6 @@ class _StubBlock3:
         return (self.Jm.T @ np.asarray(agg_bar).transpose(1, 0, 2).reshape(3 * self.P, M)).reshape(self.n_hh, self.P, M)
 
 
-def oracle_jacobian_het(orc, value, D, x, n_het, gamma):
-    """J (n_het, P, n_hh, P) from unit tangents through Oracle.het_outputs, at most 32 columns per call (it takes one pass)."""
-    n_hh, P = x.shape
-    y = vc.unit_tangents(n_hh, P)
-    dagg = np.concatenate([orc.het_outputs(x, y[:, :, c0:c0 + 32], value, D, n_het, gamma)[1] for c0 in range(0, n_hh * P, 32)], axis=2)
-    return np.ascontiguousarray(dagg.reshape(n_het, P, P, n_hh).transpose(0, 1, 3, 2))
-
-
 @pytest.fixture(scope="module")
 def stub3_setup(hank, oracle_mod, tmp_path_factory):
     """Krusell-Smith 30x3, T = 25 with heterogeneous: [KD, Value] and a market-clearing equation that reads both (a toy model:
@@ -214,7 +206,7 @@ def stub3_setup(hank, oracle_mod, tmp_path_factory):
     m = hank.build_model_from_yaml(str(spec), overrides={"T": 25, "dimensions": {"wealth": {"n": 30}, "productivity": {"n": 3}}})
     assert hank.vars_of_type(m, "heterogeneous") == ("KD", "Value")
     P = m.compspec.T - 1
-    J = oracle_jacobian_het(orc, ss0.value, ss0.D, x[2:4], 3, m.params.γ)
+    J = vc.oracle_jacobian_het(orc, ss0.value, ss0.D, x[2:4], 3, m.params.γ)
     agg = orc.het_outputs(x[2:4], None, ss0.value, ss0.D, 3, m.params.γ)[0].T                 # (P, 3)
     ss = SimpleNamespace(value=ss0.value, D=ss0.D, vars={**{k: 1.0 for k in m.variables}, **dict(ss0.vars)})
     stub = _StubBlock3(J, np.ascontiguousarray(agg), 2, P)
@@ -225,7 +217,7 @@ def stub3_setup(hank, oracle_mod, tmp_path_factory):
 def test_oracle_jacobian_of_the_first_two_outputs_is_the_two_output_one(hank, oracle_mod):
     m, ss, orc = ks_setup(30, 3, 25)
     x, _ = ks_paths(m, ss, "x1", 0.05)
-    J3 = oracle_jacobian_het(orc, ss.value, ss.D, x[2:4], 3, m.params.γ)
+    J3 = vc.oracle_jacobian_het(orc, ss.value, ss.D, x[2:4], 3, m.params.γ)
     assert np.array_equal(J3[:2], vc.oracle_jacobian(orc, ss.value, ss.D, x[2:4])) and np.abs(J3[2]).max() > 1e-3
 
 
