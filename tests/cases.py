@@ -1,6 +1,6 @@
 """The one case module of the suite: what the GPU modules (tests/test_gpu_*.py) and the CPU tests of their preconditions
 (tests/test_vjp_host.py, tests/test_cases_host.py) share. Nothing here needs a GPU except `raw_block` / `block`, which create a
-device context.
+device context, and section 4, which runs sweeps on one.
 
 0. the owners: `close` (the suite's only tolerance function), `raw_block` / `block` (a context under HANK_* variables, every
    variable restored), `model_args` / `oracle_of` (a model's constructor arguments), `hank_economy` / `hank_x` (the one-asset HANK
@@ -12,7 +12,12 @@ device context.
    valid boundary), `CASES` (curvature x record layout);
 3. raw-grid economies (`raw_economy`, `EDGE_GRIDS`) whose oracle policy holds the data-dependent edges the calibrated grids never
    show — a deep clamped prefix, many sources clamped at the top, long runs of rows in one bracket — and `edge_stats`, which
-   measures those edges on a policy."""
+   measures those edges on a policy. They serve the forward families too (tests/test_gpu_fwd_edges.py), next to three more
+   (`FWD_EDGE_ECONOMIES`: a grid and an offset on the path of r) whose edges only the forward kernels have code for: a prefix over
+   several 63-row members and past row 128, every column or a whole column clamped, a clamp that vanishes after a clamped period
+   and returns, more than 64 sources on one target row — measured by `forward_edges`, which restates k_xunits_fwd's cut;
+4. the forward sweeps' comparison (`sweeps`, `against_oracle_and_launches`, `expected_family`): both entry points at every
+   batch width against the oracle and a launch-schedule context, for a model or for raw constructor arguments."""
 import os
 
 import numpy as np
@@ -264,22 +269,42 @@ EDGE_GRIDS = {
 EDGE_NEEDS = {"dense-bottom": ("clo", "runs"), "short-top": ("top",), "both": ("clo", "top", "runs")}
 EDGE_WIDTHS = (1, 4, 32, 33)          # hank_vjp's batch widths on these economies: R = 64, 32, 8, 8 rows per block
 EDGE_P = 9
+# the forward families' economies: (grid, an additive offset on the r row of the nine-period x1 path, or None). Measured with the
+# oracle's policy (clo per column over the nine periods) and asserted by tests/test_cases_host.py:
+#   deep-prefix  column 0: 140 167 182 192 198 203 207 210 177, columns 1, 2: 0 — members 0..3 of the persistent family, wave 1 of
+#                the wide family's 2-row geometry; sources clamped at the top of column 2: 10 9 9 8 8 8 7 7 76
+#   swing        column 0: 36 128 0 0 0 0 0 39 41, column 1: 0 117 0 .., column 2: 0 62 0 ..: period 1 has every column clamped,
+#                periods 2-6 no clamp at all (2 after a clamped period, 3-6 after unclamped ones), the clamp returns in period 7;
+#                121-122 sources at the top of every column in period 7
+#   collapse     column 0: 155 589 646 0 0 0 0 167 177, column 1: 0 644 700 0 .., column 2: 0 700 700 0 ..: whole columns
+#                clamped, all mass on row 0 and the aggregate exactly 0 in periods 1 and 2
+_SWING = (0.0, 0.0, -0.6, -0.6, 0.0, 0.0, 1.5, 1.5, 0.0)
+FWD_EDGE_ECONOMIES = {
+    "deep-prefix": (lambda: 1.0 * np.linspace(0.0, 1.0, 700) ** 4, None),
+    "swing": (EDGE_GRIDS["dense-bottom"], _SWING),
+    "collapse": (lambda: 1.0 * np.linspace(0.0, 1.0, 700) ** 4, _SWING),
+}
+FWD_ECONOMIES = tuple(EDGE_GRIDS) + tuple(FWD_EDGE_ECONOMIES)         # what tests/test_gpu_fwd_edges.py runs
 _RAW = {}
 
 
 def raw_economy(name):
-    """-> dict(args: HouseholdBlock's, grid, Pi, V (n_a, 3), D (n_a * 3,), x (2, 9), orc): EDGE_GRIDS[name] under the
-    Krusell-Smith 130x3 calibration; V_T that economy's steady-state value interpolated onto the grid, D_0 uniform, the inputs the
-    first 9 periods of its x1 path (shock 0.05)."""
+    """-> dict(args: HouseholdBlock's, grid, Pi, V (n_a, 3), D (n_a * 3,), x (2, 9), orc): EDGE_GRIDS[name], or the grid and the
+    path modifier of FWD_EDGE_ECONOMIES[name], under the Krusell-Smith 130x3 calibration; V_T that economy's steady-state value
+    interpolated onto the grid, D_0 uniform, the inputs the first 9 periods of its x1 path (shock 0.05), the modifier added to
+    its r row."""
     if name not in _RAW:
         from oracle.oracle import Oracle
         m, ss, _ = ks_setup(130, 3, 40)
         wd, pdm = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
-        grid = np.ascontiguousarray(EDGE_GRIDS[name]())
+        make_grid, r_offset = FWD_EDGE_ECONOMIES[name] if name in FWD_EDGE_ECONOMIES else (EDGE_GRIDS[name], None)
+        grid = np.ascontiguousarray(make_grid())
         n_a, n_e = grid.size, pdm.grid.size
         V = np.stack([np.interp(grid, wd.grid, np.asarray(ss.value)[:, e]) for e in range(n_e)], axis=1)
         D = np.full(n_a * n_e, 1.0 / (n_a * n_e))
         x = np.ascontiguousarray(ks_paths(m, ss, "x1", 0.05)[0][2:4, :EDGE_P])
+        if r_offset is not None:
+            x[0] += np.asarray(r_offset)
         orc = Oracle(grid, pdm.grid, pdm.transition, m.params.β, m.params.γ, m.params.borrow_cons)
         _RAW[name] = dict(args=raw_args(grid, pdm.grid, pdm.transition, m, EDGE_P + 1), grid=grid, Pi=np.asarray(pdm.transition), V=V, D=D,
                           x=x, orc=orc)
@@ -305,6 +330,55 @@ def edge_stats(grid, pol):
                 for ln in np.diff(np.concatenate([[0], edges, [b.size]])):
                     runs[int(ln)] = runs.get(int(ln), 0) + 1
     return clo, top, dict(sorted(runs.items()))
+
+
+XRW, XUCAP = 63, 64          # csrc/hank_xsweep.h: rows per member of the persistent family, work units per member and period
+
+
+def forward_edges(grid, pol):
+    """what the forward kernels care about on a policy sequence pol (P, n_a, n_e), with k_lottery's `start` and k_xunits_fwd's
+    greedy cut (csrc/hank_kernels.h, csrc/hank_xsweep.h) restated in numpy. -> dict of
+    clo (P, n_e); members (P, n_e) = ceil(clo / 63), the members that hold clamped rows of a column; past128 (P, n_e), the prefix
+    passes row 128 (wave 1 of the wide family's 2-row geometry); all_clamped (P,); reopened (P,): no column clamped after a period
+    that had one (all virtual mass re-enters through row 0's lottery); quiet (P,): no column clamped after a period without one;
+    sources (P, n_e): the most sources on one target row (target r receives the upper parts of [start[r-1], start[r]) and the lower
+    parts of [start[r], start[r+1])); units (P, members): work units per member and period, every column's together;
+    column_units: the most units of one column of a member; longest: the longest unit in lanes, its virtual lanes included."""
+    P, n_a, n_e = pol.shape
+    S = -(-n_a // XRW)
+    m0 = np.searchsorted(grid, pol, side="left")            # searchsortedfirst: grid[m0 - 1] < pol <= grid[m0]
+    clo = (m0 == 0).sum(axis=1)
+    lo = np.where(m0 == 0, -1, np.where(m0 >= n_a, n_a - 2, m0 - 1))       # k_lottery's bracket; clamped-low sources sort first
+    assert np.all(np.diff(lo, axis=1) >= 0), "the policy is not monotone in wealth"
+    start = np.empty((P, n_e, n_a + 1), dtype=np.int64)     # start[r] = max(clo, #sources with lo < r): the first source with lo >= r
+    for t in range(P):
+        for e in range(n_e):
+            start[t, e] = np.searchsorted(lo[t, :, e], np.arange(n_a + 1), side="left")
+    assert np.array_equal(start[:, :, 0].T, clo.T)
+    sources = np.maximum(start[:, :, 1] - start[:, :, 0], (start[:, :, 2:] - start[:, :, :-2]).max(axis=2))
+    anyclo = (clo > 0).any(axis=1)
+    prev = np.concatenate([[False], anyclo[:-1]])            # k_xfwd's vnz: some column was clamped in the period before
+    units, column_units, longest = np.zeros((P, S), dtype=np.int64), 0, 0
+    for t in range(P):
+        for m in range(S):
+            r0, nrows = m * XRW, min(XRW, n_a - m * XRW)
+            for e in range(n_e):
+                st = start[t, e]
+                n, ta = 0, 0
+                while ta < nrows:
+                    ja = st[max(r0 + ta - 1, 0)]
+                    has0 = ja == 0 and clo[t, e] <= 0 and prev[t]
+                    lanes = lambda b: (st[r0 + b] - ja) + (S if has0 and st[r0 + b] > ja else 0)       # noqa: E731
+                    tb = ta + 1                             # a unit holds one target row at least, however many lanes that takes
+                    while tb < nrows and lanes(tb + 1) <= 64:
+                        tb += 1
+                    if st[r0 + tb] > ja:
+                        n, longest = n + 1, max(longest, int(lanes(tb)))
+                    ta = tb
+                units[t, m] += n
+                column_units = max(column_units, n)
+    return dict(clo=clo, members=-(-clo // XRW), past128=clo > 128, all_clamped=(clo > 0).all(axis=1), reopened=~anyclo & prev,
+                quiet=~anyclo & ~prev & (np.arange(P) > 0), sources=sources, units=units, column_units=column_units, longest=longest)
 
 
 def adj_rows_per_block(M):
@@ -337,3 +411,94 @@ def check_edges(name, grid, pol):
     if "runs" in needs:
         assert any(k >= 5 and k % 2 == 1 for k in runs) and any(k >= 5 and k % 2 == 0 for k in runs), (name, runs)
     return sides
+
+
+# ---- 4. the forward sweeps against the oracle and the launches ---------------------------------------------------------------
+FAMILY = {"launch": "launch-per-period", "xcd": "xcd-persistent", "wide": "on-chip-wide"}
+N_ORACLE = 40                # the oracle covers the first 40 columns of a wider batch
+
+
+def expected_family(sched, entry, N):
+    """the kernel family that serves a sweep: the forced schedule's, or the default schedule's choice by entry point and width."""
+    if sched is not None:
+        return FAMILY[sched]
+    if N >= 80:
+        return FAMILY["wide"]                   # a full round of the on-chip wide sweeps
+    if entry == "dual":
+        return FAMILY["xcd" if N <= 32 else "launch"]     # one-pass Dual batches run on the persistent Dual pass
+    return FAMILY["xcd"]                        # tangent batches up to xjvp_max = 64
+
+
+def sweeps(hb, xhh, y, Ns):
+    """both entry points at every batch width: the Dual pass (hank_primal_jvp) and the Float64 sweeps followed by the tangent
+    sweeps (hank_primal, hank_jvp), each from a record of another x (no memo hit: every sweep runs). A second hank_jvp at the same
+    record returns the same bits. -> {(entry, N): (family, agg, dagg, policy (P, n_a, n_e), dpolicy (P, n_a, n_e, N), D)}."""
+    out = {}
+    for N in Ns:
+        yN = np.ascontiguousarray(y[:, :, :N])
+        hb.primal(xhh * 1.01)
+        agg, dagg = hb.primal_jvp(xhh, yN)
+        fam = hb.info()["last_tangent_family_name"]
+        out["dual", N] = (fam, agg, dagg, hb.policy_seq().transpose(2, 0, 1), hb.dpolicy_seq(N).transpose(2, 0, 1, 3), hb.dist_seq())
+        hb.primal(xhh * 1.01)
+        agg = hb.primal(xhh)
+        dagg = hb.jvp(yN)
+        fam = hb.info()["last_tangent_family_name"]
+        out["tan", N] = (fam, agg, dagg, hb.policy_seq().transpose(2, 0, 1), hb.dpolicy_seq(N).transpose(2, 0, 1, 3), hb.dist_seq())
+        assert np.array_equal(hb.jvp(yN), dagg), ("a second hank_jvp at the same record", N)
+    return out
+
+
+def oracle_dist_seq(orc, pol, D0):
+    """D_t (P, n_a, n_e), post-transition, of the oracle's forward iteration on the policy sequence pol (P, n_a, n_e)."""
+    return orc.forward_iteration(np.stack([pol, np.zeros_like(pol)], axis=-1), D0, 1, return_D=True)[1][..., 0]
+
+
+def against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
+    """each (schedule, env) of `runs`, both entry points at every N of Ns (per run: `Ns` may map a schedule to its widths), against
+    the oracle — aggregates, policy, partials (the first N_ORACLE columns) and the distribution sequence element-wise — and
+    against a launch-schedule context; the family that served each sweep, no fallback, the schedule in use.
+    shape: (a model or the raw constructor's arguments, V, D, xhh, oracle). -> [(schedule, env, stats, info)] of the runs."""
+    m, V, D, xhh, orc = shape
+    args = m if isinstance(m, tuple) else model_args(m)
+    n_hh, P = xhh.shape
+    widths = (lambda sched: Ns[sched]) if isinstance(Ns, dict) else (lambda sched: Ns)
+    Nmax = max(max(widths(sched)) for sched, _ in runs)
+    y = np.random.default_rng(seed).standard_normal((n_hh, P, Nmax))
+    oagg, odagg, opol, odpol = orc.block(xhh, y[:, :, :min(Nmax, N_ORACLE)], V, D)
+    oD = oracle_dist_seq(orc, opol, D)
+    refs, seen = {}, []
+    for sched, env in runs:
+        diet = env.get("HANK_RECORD_DIET")
+        if diet not in refs:                # the launches with the same record layout (diet on and off differ by rounding)
+            hl = raw_block(hank, args, "launch", HANK_RECORD_DIET=diet)
+            hl.set_boundary(V, D)
+            refs[diet] = sweeps(hl, xhh, y, sorted({N for s2, e2 in runs if e2.get("HANK_RECORD_DIET") == diet for N in widths(s2)}))
+            hl.close()
+        ref = refs[diet]
+        hb = raw_block(hank, args, sched, **env)
+        hb.set_boundary(V, D)
+        got = sweeps(hb, xhh, y, widths(sched))
+        st, info = hb.stats(), hb.info()
+        assert st["fallbacks"] == 0 and info["wide_mode"] == {"wide": 2, None: 1}.get(sched, 0), (sched, env, st, info)
+        # (a forced `wide` keeps the persistent sweeps for the primal where the grid fits them, the launches where it does not)
+        assert sched == "wide" or st["schedule"] == {"launch": 0, "xcd": 1, None: 2}[sched], (sched, env, st, info)
+        seen.append((sched, env, st, info))
+        assert info["record_diet"] == (0 if env.get("HANK_RECORD_DIET") == 0 else 1), (sched, env, info)
+        hb.close()
+        for (entry, N), (fam, agg, dagg, pol, dpol, Dq) in got.items():
+            what = f"{len(args[0])}x{len(args[1])} {sched} {env} {entry} N={N}"
+            assert fam == expected_family(sched, entry, N), (what, fam)
+            k = min(N, N_ORACLE)
+            close(agg, oagg, what=what + " agg"); close(dagg[:, :k], odagg[:, :k], what=what + " dagg")
+            close(pol, opol, what=what + " policy"); close(dpol[..., :k], odpol[..., :k], what=what + " dpolicy")
+            np.testing.assert_allclose(Dq.sum(axis=(0, 1)), 1.0, rtol=0, atol=1e-12)
+            close(Dq.transpose(2, 0, 1), oD, what=what + " D")
+            _, agg0, dagg0, pol0, dpol0, _ = ref[entry, N]
+            close(agg, agg0, 1e-12, what=what + " agg vs launch"); close(dagg, dagg0, 1e-12, what=what + " dagg vs launch")
+            assert np.array_equal(pol, pol0), what + " policy vs launch"
+            if fam != FAMILY["wide"]:
+                assert np.array_equal(dpol, dpol0), what + " dpolicy bits vs launch"
+            else:
+                close(dpol, dpol0, 1e-12, what=what + " dpolicy vs launch")
+    return seen

@@ -15,45 +15,14 @@ boundary, not a stationary one."""
 import numpy as np
 import pytest
 
-from cases import CASES, block as _block, close as _close, economy as _economy, raw_block, shape as _shape
+from cases import (CASES, FAMILY, against_oracle_and_launches as _against_oracle_and_launches, block as _block, close as _close,
+                   economy as _economy, expected_family as _expected_family, raw_block, shape as _shape, sweeps as _sweeps)
 
 pytestmark = pytest.mark.gpu
-
-FAMILY = {"launch": "launch-per-period", "xcd": "xcd-persistent", "wide": "on-chip-wide"}
 
 # the one-asset HANK calibration (the bond supply that clears the asset market) has no steady state at gamma = 0.5 (its Newton
 # step is singular); no other gamma takes the rcp(x^2) | rsqrt pair, so Krusell-Smith alone covers it
 MATRIX = [(fam, case) for fam in ("ks", "hank") for case in CASES if not (fam == "hank" and case == "gamma0.5")]
-
-
-def _sweeps(hb, xhh, y, Ns):
-    """both entry points at every batch width: the Dual pass (hank_primal_jvp) and the Float64 sweeps followed by the tangent
-    sweeps (hank_primal, hank_jvp), each from a record of another x (no memo hit: every sweep runs). A second hank_jvp at the same
-    record returns the same bits. -> {(entry, N): (family, agg, dagg, policy (P, n_a, n_e), dpolicy (P, n_a, n_e, N), D)}."""
-    out = {}
-    for N in Ns:
-        yN = np.ascontiguousarray(y[:, :, :N])
-        hb.primal(xhh * 1.01)
-        agg, dagg = hb.primal_jvp(xhh, yN)
-        fam = hb.info()["last_tangent_family_name"]
-        out["dual", N] = (fam, agg, dagg, hb.policy_seq().transpose(2, 0, 1), hb.dpolicy_seq(N).transpose(2, 0, 1, 3), hb.dist_seq())
-        hb.primal(xhh * 1.01)
-        agg = hb.primal(xhh)
-        dagg = hb.jvp(yN)
-        fam = hb.info()["last_tangent_family_name"]
-        out["tan", N] = (fam, agg, dagg, hb.policy_seq().transpose(2, 0, 1), hb.dpolicy_seq(N).transpose(2, 0, 1, 3), hb.dist_seq())
-        assert np.array_equal(hb.jvp(yN), dagg), ("a second hank_jvp at the same record", N)
-    return out
-
-
-def _expected_family(sched, entry, N):
-    if sched is not None:
-        return FAMILY[sched]
-    if N >= 80:
-        return FAMILY["wide"]                   # a full round of the on-chip wide sweeps
-    if entry == "dual":
-        return FAMILY["xcd" if N <= 32 else "launch"]     # one-pass Dual batches run on the persistent Dual pass
-    return FAMILY["xcd"]                        # tangent batches up to xjvp_max = 64
 
 
 NS = (1, 5, 12, 40)          # with 8 groups: D = 1, 1, 2, and two passes (32 at D = 4, then 8)
@@ -195,43 +164,6 @@ def test_nonaffine_outputs_at_gamma_1_5(hank, family, n_het):
 
 
 # ---- 3. shape edges of the persistent and wide families ----------------------------------------------------------------------
-def _against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
-    """each (schedule, env) of `runs`, both entry points at every N of Ns, against the oracle and a launch-schedule context."""
-    m, V, D, xhh, orc = shape
-    n_hh, P = xhh.shape
-    y = np.random.default_rng(seed).standard_normal((n_hh, P, max(Ns)))
-    oagg, odagg, opol, odpol = orc.block(xhh, y, V, D)
-    refs = {}
-    for sched, env in runs:
-        diet = env.get("HANK_RECORD_DIET")
-        if diet not in refs:                # the launches with the same record layout (diet on and off differ by rounding)
-            hl = _block(hank, m, "launch", HANK_RECORD_DIET=diet)
-            hl.set_boundary(V, D)
-            refs[diet] = _sweeps(hl, xhh, y, Ns)
-            hl.close()
-        ref = refs[diet]
-        hb = _block(hank, m, sched, **env)
-        hb.set_boundary(V, D)
-        got = _sweeps(hb, xhh, y, Ns)
-        st, info = hb.stats(), hb.info()
-        assert st["fallbacks"] == 0 and (st["schedule"] == 1 if sched == "xcd" else info["wide_mode"] == 2), (sched, env, st, info)
-        assert info["record_diet"] == (0 if env.get("HANK_RECORD_DIET") == 0 else 1), (sched, env, info)
-        hb.close()
-        for (entry, N), (fam, agg, dagg, pol, dpol, Dq) in got.items():
-            what = f"{m.heterogeneity['wealth'].n}x{m.heterogeneity['productivity'].n} {sched} {env} {entry} N={N}"
-            assert fam == FAMILY[sched], (what, fam)
-            _close(agg, oagg, what=what + " agg"); _close(dagg, odagg[:, :N], what=what + " dagg")
-            _close(pol, opol, what=what + " policy"); _close(dpol, odpol[..., :N], what=what + " dpolicy")
-            np.testing.assert_allclose(Dq.sum(axis=(0, 1)), 1.0, rtol=0, atol=1e-12)
-            _, agg0, dagg0, pol0, dpol0, _ = ref[entry, N]
-            _close(agg, agg0, 1e-12, what=what + " agg vs launch"); _close(dagg, dagg0, 1e-12, what=what + " dagg vs launch")
-            assert np.array_equal(pol, pol0), what + " policy vs launch"
-            if sched == "xcd":
-                assert np.array_equal(dpol, dpol0), what + " dpolicy bits vs launch"
-            else:
-                _close(dpol, dpol0, 1e-12, what=what + " dpolicy vs launch")
-
-
 @pytest.mark.parametrize("n_e", [11, 12, 16])
 def test_xcd_sweeps_across_the_1024_thread_boundary(hank, n_e):
     """64 (n_e + 1) threads: n_e = 11 is the last 768-thread grid, 12 the first 1024-thread one (dmax = 2). N = 12 is D = 2 in

@@ -252,3 +252,38 @@ def test_edge_economies_hold_their_edges_on_the_oracles_policy(oracle_mod):
         sides = {k: sides[k] or got[k] for k in sides}
     assert sides == {"clo_lt_nb": True, "clo_gt_nb": True}, sides
     assert [vc.adj_rows_per_block(M) for M in (1, 2, 3, 4, 5, 6, 8, 9, 16, 18, 32, 33)] == [64, 64, 16, 32, 8, 16, 16, 8, 8, 8, 8, 8]
+
+
+def test_forward_edge_economies_hold_their_edges_on_the_oracles_policy(oracle_mod):
+    """each economy of cases.FWD_EDGE_ECONOMIES, on the CPU oracle's policy, holds what tests/test_gpu_fwd_edges.py runs the forward
+    families through: `deep-prefix` a clamped prefix over three members or more and past row 128, a target row with more than 64
+    sources; `swing` a period with every column clamped, a clamp-free period after a clamped one, a clamp-free period after a
+    clamp-free one, a returning clamp, more than 64 sources on one target; `collapse` a whole column clamped. On all six economies
+    of the forward module every member-period needs at most XUCAP = 64 work units (a condition on the inputs: beyond it the
+    persistent sweeps hand the context to the launches). Prints what it measured (run with -s)."""
+    fe = {}
+    for name in vc.FWD_ECONOMIES:
+        ec = vc.raw_economy(name)
+        assert np.all(np.diff(ec["grid"]) > 0)
+        pol = ec["orc"].block(ec["x"], None, ec["V"], ec["D"])[2]               # (status 0, or `block` raises)
+        assert np.all(np.isfinite(pol)) and np.all(np.diff(pol, axis=1) >= 0), name
+        f = fe[name] = vc.forward_edges(ec["grid"], pol)
+        assert np.array_equal(f["clo"], vc.edge_stats(ec["grid"], pol)[0])
+        print(f"{name} ({ec['grid'].size} rows): clo per column {f['clo'].T.tolist()}, members {f['members'].max(axis=1).tolist()}, "
+              f"most sources on one target per period {f['sources'].max(axis=1).tolist()}, all clamped {f['all_clamped'].astype(int).tolist()}, "
+              f"reopened {f['reopened'].astype(int).tolist()}, quiet {f['quiet'].astype(int).tolist()}, units per member-period at most "
+              f"{f['units'].max()} ({f['column_units']} in one column), longest unit {f['longest']} lanes")
+        assert f["units"].max() <= vc.XUCAP and f["column_units"] < vc.XUCAP, (name, f["units"])
+    f = fe["deep-prefix"]
+    assert f["members"].max() >= 3 and f["past128"].any() and f["sources"].max() > 64
+    f = fe["swing"]
+    anyclo = (f["clo"] > 0).any(axis=1)
+    assert f["all_clamped"].any() and f["reopened"].any() and f["quiet"].any() and f["sources"].max() > 64
+    t_open = int(np.flatnonzero(f["reopened"])[0])
+    assert anyclo[t_open:].any(), "the clamp does not return"
+    f = fe["collapse"]
+    assert np.any(f["clo"] == vc.raw_economy("collapse")["grid"].size)
+    # the economies of the transposed sweeps never leave member 0 or wave 0, and never change which columns are clamped
+    for name in vc.EDGE_GRIDS:
+        assert fe[name]["members"].max() == 1 and not fe[name]["past128"].any() and not fe[name]["all_clamped"].any(), name
+        assert not fe[name]["reopened"].any() and not fe[name]["quiet"].any(), name
