@@ -181,8 +181,10 @@ struct TanBatch {
 // (V valid, I invalid, . untouched) — the families do NOT agree, see DESIGN.md section 2a:
 //                        PRIMAL_BACK PRIMAL_FWD TAN_BACK TAN_FWD DUAL_BACK DUAL_FWD VJP_A VJP_B
 //   run_primal                V          V         .        .        I        I       .     .
-//   x_run_primal              V          V*        I        I        I        I       .     .      (* I with skip_fwd: a Dual pass)
-//   x_run_tangent             .          .         V        V        I        I       .     .
+//   x_primal                  V          V         I        I        I        I       .     .
+//   x_jvp                     .          .         V        V        I        I       .     .
+//   x_dual_two                V          I         V        V        I        I       .     .
+//   x_dual_fused              V          I         V*       V        I        I       .     .      (* brackets nothing: k_xdual_back is PRIMAL_BACK's)
 //   w_run_tangent             .          .         V        V        I        I       .     .
 //   run_jvp                   .          .         V        V        .        .       .     .
 //   run_fused                 I          I         I        I        V        V       .     .
@@ -197,6 +199,7 @@ struct Spans {
     // ONE event ends span k and begins span next
     hipError_t end_begin(Span k, int launches, Span next, hipStream_t st) { s[next].valid = false; s[next].from = s[k].ev1; return end(k, st, launches); }
     void invalidate(std::initializer_list<Span> ks) { for (Span k : ks) s[k].valid = false; }
+    void absent(Span k, int launches) { s[k].valid = false; s[k].launches = launches; }      // the sweep rode on another span's launch: no events
     // after a synchronisation: -1 ms for an invalid span; the launch count of the last run that ended it either way
     hipError_t read(Span k, double *ms, int32_t *launches) const {
         float f = -1.f;
@@ -350,16 +353,14 @@ static int hip_status(hipError_t e) {
 // a context belongs to ONE HIP device (hank_create: the current one; hank_create_on: the one named). Every entry point
 // makes that device current for the duration of the call and restores the caller's, so one host thread can drive one
 // context per GPU of a node (GeneralStructures.jl:542-550 has no notion of a device: the shim owns the placement).
-static void x_section_release(int dev);
 struct DeviceGuard {
-    int prev = -1, dev = -1;
+    int prev = -1;
     bool switched = false, ok = true;
     explicit DeviceGuard(const hank_ctx *ctx);
-    ~DeviceGuard() { if (dev >= 0) x_section_release(dev); if (switched) (void)hipSetDevice(prev); }
+    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
 };
 DeviceGuard::DeviceGuard(const hank_ctx *ctx) {
     if (!ctx) return;
-    dev = ctx->device & 63;
     if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
     if (prev != ctx->device) { switched = hipSetDevice(ctx->device) == hipSuccess; ok = switched; }
 }
@@ -646,21 +647,50 @@ static int fetch_device_error(hank_ctx *ctx) {
 }
 
 // ================================ XCD-local persistent sweeps: host side ==========================
-// Two persistent launches must never share the chip half-resident (each would wait for workgroups the other's
-// spinning workgroups keep out): every sweep launch of this process, from any context or stream, is ordered behind
-// the previous one through one event per device.
+// Two chip-filling launches must never share the chip half-resident (each would wait for workgroups the other's spinning
+// workgroups keep out): every such launch of this process, from any context or stream, is ordered behind the previous one
+// through one event per device, and the launches of ONE call are enqueued as one block.
 static std::mutex g_xmutex;
 static hipEvent_t g_xlast[64] = {};
-// ... and the launches of ONE call are enqueued as one block: between x_serialize_begin and x_serialize_end this thread holds the
-// device's section lock, so a second host thread (another context on the same GPU: parallel.DeviceGroup) cannot wait for the event
-// of the call BEFORE and then enqueue its sweeps beside this call's. Nested sections of one thread count (the one-pass Dual pass
-// opens one around its prologue, its two halves open their own inside); a section left open by an early return is closed when the
-// entry point returns (DeviceGuard).
 static std::mutex g_xsection[64];
-static thread_local int t_xdepth[64];
-static void x_section_release(int dev) {
-    if (t_xdepth[dev] > 0) { t_xdepth[dev] = 0; g_xsection[dev].unlock(); }
-}
+// XSection is the one owner of both: "this thread is enqueueing a block of chip-filling launches on device d". Opening it takes the
+// device's section lock — a second host thread (another context on the same GPU: parallel.DeviceGroup) cannot wait for the event of
+// the call BEFORE and then enqueue its sweeps beside this call's — and makes the context's stream wait for the device's event.
+// Closing it records that event behind what was enqueued and releases the lock: the success path calls close(), so a HIP error
+// reaches the caller; the destructor closes what an early return left open, silently, so the next chip-filling launch of the process
+// is still ordered behind whatever was enqueued. There is no re-entrancy (a second section of the device inside one would wait for
+// itself): whatever launches inside a section takes the open one by reference and gets the stream from it, and only the body that
+// knows a call's extent opens one (ensure_lwg keeps taking the context: the launch family calls it too, outside any section; from
+// a step it is called on the section's context). One call = one section = one block for x_primal, x_jvp, x_dual_two, x_dual_fused, w_run_tangent
+// and x_fixed_point; a WIDE hank_primal_jvp[_dev] is hank_primal[_dev] and then hank_jvp[_dev]: two calls, two blocks.
+struct XSection {
+    hank_ctx *const ctx;
+    explicit XSection(hank_ctx *c) : ctx(c), d(c->device & 63) {
+        g_xsection[d].lock();
+        std::lock_guard<std::mutex> lk(g_xmutex);
+        err = g_xlast[d] ? hipStreamWaitEvent(ctx->stream, g_xlast[d], 0) : hipSuccess;
+    }
+    XSection(const XSection &) = delete;
+    ~XSection() { (void)close(); }
+    hipError_t opened() const { return err; }
+    hipStream_t stream() const { return ctx->stream; }
+    hipError_t close() {
+        if (!open) return hipSuccess;
+        open = false;
+        hipError_t e = hipSuccess;
+        {
+            std::lock_guard<std::mutex> lk(g_xmutex);
+            if (!g_xlast[d]) e = hipEventCreateWithFlags(&g_xlast[d], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventRecord(g_xlast[d], ctx->stream);
+        }
+        g_xsection[d].unlock();
+        return e;
+    }
+private:
+    const int d;
+    bool open = true;
+    hipError_t err = hipSuccess;
+};
 
 // the grid fits the XCD-local schedule: a 63-row slab per CU of an XCD, and the Float64 sweeps' LDS (which holds the
 // per-period inputs of the WHOLE horizon) fits a workgroup
@@ -762,12 +792,13 @@ static dim3 x_block(const XWork &X, const Consts &c) {
 // One launcher per persistent kernel: the whole chip (a workgroup per CU), the instance for X.maxt (and D, val), and the dynamic LDS
 // of THAT instance from the size function under the kernel. k_xdual_back and every D = 4 instance exist for 768 threads only.
 // (x_launch_vfi and x_launch_stat stand with their caller, x_fixed_point. The kernels are emitted into the code object in the order
-// these launchers name them: moving one moves its kernels, and a disassembly diff against the previous build is no longer empty.)
+// these launchers name them: moving one moves its kernels, and a disassembly diff against the previous build is no longer empty.
+// Each takes the open section and launches on its stream: a persistent launch outside a section cannot be written.)
 template <typename F>
 static void x_by_maxt(const XWork &X, F launch) { if (X.maxt == 768) launch(std::integral_constant<int, 768>()); else launch(std::integral_constant<int, 1024>()); }
-#define XL(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(X.grid), x_block(X, c), lds, s, a)
+#define XL(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(X.grid), x_block(X, c), lds, sec.stream(), a)
 static bool x_has_dual_back(const XWork &X) { return X.maxt == 768; }
-static void x_launch_dual_back(const XWork &X, const Consts &c, int D, hipStream_t s, const XDualBackArgs &a) {
+static void x_launch_dual_back(XSection &sec, const XWork &X, const Consts &c, int D, const XDualBackArgs &a) {
     const size_t lds = x_lds_dual_back(c, D);
     if (!x_has_dual_back(X)) return;
     if (D == 1) XL(k_xdual_back<1, 768>);
@@ -775,7 +806,7 @@ static void x_launch_dual_back(const XWork &X, const Consts &c, int D, hipStream
     else XL(k_xdual_back<4, 768>);
 }
 // k_xfwd<D, VAL>: D = 0 (the Float64 sweep alone, VAL), 1, 2, 4
-static void x_launch_fwd(const XWork &X, const Consts &c, int D, bool val, hipStream_t s, const XSweepFwdArgs &a) {
+static void x_launch_fwd(XSection &sec, const XWork &X, const Consts &c, int D, bool val, const XSweepFwdArgs &a) {
     const size_t lds = x_lds_fwd(c, D, val || D == 0);
     x_by_maxt(X, [&](auto mt) {
         constexpr int MT = decltype(mt)::value;
@@ -785,8 +816,8 @@ static void x_launch_fwd(const XWork &X, const Consts &c, int D, bool val, hipSt
         else if (D == 4) { if constexpr (MT == 768) { if (val) XL(k_xfwd<4, true, MT>); else XL(k_xfwd<4, false, MT>); } }
     });
 }
-static void x_launch_primal_back(const XWork &X, const Consts &c, hipStream_t s, const XBackArgs &a) { const size_t lds = x_lds_primal_back(c); x_by_maxt(X, [&](auto mt) { XL(k_xprimal_back<decltype(mt)::value>); }); }
-static void x_launch_tan_back(const XWork &X, const Consts &c, int D, hipStream_t s, const XTanBackArgs &a) {
+static void x_launch_primal_back(XSection &sec, const XWork &X, const Consts &c, const XBackArgs &a) { const size_t lds = x_lds_primal_back(c); x_by_maxt(X, [&](auto mt) { XL(k_xprimal_back<decltype(mt)::value>); }); }
+static void x_launch_tan_back(XSection &sec, const XWork &X, const Consts &c, int D, const XTanBackArgs &a) {
     const size_t lds = x_lds_tan_back(c, D);
     x_by_maxt(X, [&](auto mt) {
         constexpr int MT = decltype(mt)::value;
@@ -796,10 +827,11 @@ static void x_launch_tan_back(const XWork &X, const Consts &c, int D, hipStream_
     });
 }
 // the forward sweeps' geometry at the recorded lottery (once per primal)
-static void x_ensure_rng(hank_ctx *ctx) {
+static void x_ensure_rng(XSection &sec) {
+    hank_ctx *ctx = sec.ctx;
     XWork &X = ctx->xw;
     if (X.rng_valid) return;
-    hipLaunchKernelGGL(k_xunits_fwd, dim3((unsigned)ctx->c.P, (unsigned)X.Sact), dim3(256), 0, ctx->stream, ctx->c, ctx->R, X.Sact, X.srcF, X.unitsF, X.unit_overflow, X.ucap);
+    hipLaunchKernelGGL(k_xunits_fwd, dim3((unsigned)ctx->c.P, (unsigned)X.Sact), dim3(256), 0, sec.stream(), ctx->c, ctx->R, X.Sact, X.srcF, X.unitsF, X.unit_overflow, X.ucap);
     X.rng_valid = true;
 }
 
@@ -821,167 +853,156 @@ static int ensure_lwg(hank_ctx *ctx) {
     ctx->lwg_builds++;
     return HANK_OK;
 }
-static int x_serialize_begin(hank_ctx *ctx) {
-    const int d = ctx->device & 63;
-    if (t_xdepth[d]++ == 0) g_xsection[d].lock();
-    std::lock_guard<std::mutex> lk(g_xmutex);
-    if (g_xlast[d]) HIPC(ctx, hipStreamWaitEvent(ctx->stream, g_xlast[d], 0));
-    return HANK_OK;
-}
-static int x_serialize_end(hank_ctx *ctx) {
-    const int d = ctx->device & 63;
-    {
-        std::lock_guard<std::mutex> lk(g_xmutex);
-        hipEvent_t &e = g_xlast[d];
-        if (!e) HIPC(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPC(ctx, hipEventRecord(e, ctx->stream));
-    }
-    if (t_xdepth[d] > 0 && --t_xdepth[d] == 0) g_xsection[d].unlock();
-    return HANK_OK;
-}
-
 // zero the sync blocks of the launches about to be enqueued (and, under the dev knob, pre-set their status words)
-static int x_sync_reset(hank_ctx *ctx, XSync *base, int count, int where) {     // where: 1 primal sweeps, 2 tangent sweeps, 4 the steady state's fixed points
-    HIPC(ctx, hipMemsetAsync(base, 0, sizeof(XSync) * (size_t)count, ctx->stream));
-    if (ctx->xw.fault && ctx->xw.fault != 3 && (ctx->xw.fault_where & where)) hipLaunchKernelGGL(k_xpoison, dim3(1), dim3(64), 0, ctx->stream, base, count, (unsigned)ctx->xw.fault);
+static int x_sync_reset(XSection &sec, XSync *base, int count, int where) {     // where: 1 primal sweeps, 2 tangent sweeps, 4 the steady state's fixed points
+    hank_ctx *ctx = sec.ctx;
+    HIPC(ctx, hipMemsetAsync(base, 0, sizeof(XSync) * (size_t)count, sec.stream()));
+    if (ctx->xw.fault && ctx->xw.fault != 3 && (ctx->xw.fault_where & where)) hipLaunchKernelGGL(k_xpoison, dim3(1), dim3(64), 0, sec.stream(), base, count, (unsigned)ctx->xw.fault);
     return HANK_OK;
 }
 
-// behind a forward sweep that carried the value: both aggregates summed over the members, and the virtual rows' mass folded into D_t
-static void x_value_epilogue(hank_ctx *ctx) {
-    const XWork &X = ctx->xw;
-    const Consts &c = ctx->c;
-    const size_t P = c.P;
-    hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, X.aggpart, X.Sact, 2, ctx->d_agg_rm);
-    hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
-    hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact, X.D0own);
+// ---- the steps of the persistent shapes ----------------------------------------------------------------------------------------
+// Each takes the open section (and the batch it works on) and enqueues ONE thing, whole; none is told what another has done. The
+// bodies that compose them (x_primal, x_jvp, x_dual_two, x_dual_fused: one per shape of call) hold the section and the bookkeeping.
+// Sync blocks: 0, 1 the Float64 sweeps (backward, forward); 2 + 2p, 3 + 2p the backward and forward sweep of tangent pass p (a
+// forward sweep that carries the value too is still pass 0's): x_status reads them in this order.
+static void x_zero_err(XSection &sec) { hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, sec.stream(), sec.ctx->d_err, 4); }
+static void x_rho(XSection &sec) {
+    hank_ctx *ctx = sec.ctx;
+    hipLaunchKernelGGL(k_xrho, dim3((unsigned)((ctx->c.P + 255) / 256)), dim3(256), 0, sec.stream(), ctx->d_xhh, ctx->c.n_hh, ctx->c.P, ctx->xw.rho);
 }
-
-// the Float64 recurrences at the context's current x (d_xhh) and boundary: two persistent launches on ONE XCD's
-// workgroups (the policy sequence, the distribution path and the linearisation record the tangent sweeps read)
-// skip_fwd: the distribution sweep travels with the tangents' forward sweep instead (k_xfwd<D, true>, x_run_tangent(.., val))
-// dual: the backward sweep carries the partials of this ONE-pass batch too (k_xdual_back; implies skip_fwd — the caller follows
-// with x_run_tangent(.., val, skip_back))
-static int x_run_primal(hank_ctx *ctx, bool skip_fwd = false, XTan *dual = nullptr, bool pro_done = false) {      // pro_done: k_xdual_prologue has run (x_dual)
-    XWork &X = ctx->xw;
-    const Consts &c = ctx->c;
-    const size_t P = c.P;
-    hipStream_t s = ctx->stream;
-    int rc = x_serialize_begin(ctx);
-    if (rc) return rc;
-    if (!pro_done) {
-        rc = x_sync_reset(ctx, X.sync, 2, 1);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);
-        hipLaunchKernelGGL(k_xrho, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, ctx->d_xhh, c.n_hh, (int)P, X.rho);
-        if (dual) hipLaunchKernelGGL(k_tan_in, dim3((unsigned)((P * dual->N + 255) / 256)), dim3(256), 0, s, dual->dxhh, c.n_hh, (int)P, dual->N, dual->dxr, dual->dxw, dual->dxt);
+static void x_tan_in(XSection &sec, XTan *w) {
+    const Consts &c = sec.ctx->c;
+    hipLaunchKernelGGL(k_tan_in, dim3((unsigned)(((size_t)c.P * w->N + 255) / 256)), dim3(256), 0, sec.stream(), w->dxhh, c.n_hh, c.P, w->N, w->dxr, w->dxw, w->dxt);
+}
+// in front of the tangent sweeps at a recorded primal: their sync blocks, the inputs, and once per recorded primal which members
+// each member's gathers read, period by period
+static int x_tan_front(XSection &sec, XTan *w) {
+    hank_ctx *ctx = sec.ctx; XWork &X = ctx->xw;
+    const int rc = x_sync_reset(sec, X.sync + 2, 2 * (int)w->passes.size(), 2); if (rc) return rc;
+    x_tan_in(sec, w);
+    x_rho(sec);     // (the primal may have been recorded by the launches)
+    if (!X.src_valid) {
+        hipLaunchKernelGGL(k_xsrc_back, dim3((unsigned)ctx->c.P, X.Sact), dim3(256), 0, sec.stream(), ctx->c, ctx->R, X.Sact, X.srcB);
+        X.src_valid = true;
     }
+    return HANK_OK;
+}
+// span PRIMAL_BACK: the Float64 backward sweep at the context's x (d_xhh) and boundary, on ONE XCD's workgroups; with a one-pass
+// batch `dual` it carries the batch's partials too (k_xdual_back)
+static int x_back(XSection &sec, XTan *dual = nullptr) {
+    hank_ctx *ctx = sec.ctx; XWork &X = ctx->xw;
+    const Consts &c = ctx->c;
     XBackArgs ab{};
     ab.c = c; ab.ss_value = ctx->d_ss_value; ab.xhh = ctx->d_xhh; ab.rho = X.rho; ab.sy = X.sync; ab.st_s = X.st_s;
     ab.err = ctx->d_err; ab.R = ctx->R;
-    HIPC(ctx, ctx->spans.begin(PRIMAL_BACK, s));
+    HIPC(ctx, ctx->spans.begin(PRIMAL_BACK, sec.stream()));
     if (dual) {
         const XPass &ps = dual->passes[0];
         XDualBackArgs db{};
         db.p = ab; db.dxr = dual->dxr; db.dxw = dual->dxw; db.dxt = dual->dxt; db.Ntot = dual->N; db.n0 = ps.n0; db.N = ps.N;
         db.st_ds = X.st_ds; db.dpol = dual->dpol + ps.dpol_off; db.groups = ps.groups;
-        x_launch_dual_back(X, c, ps.D, s, db);
-    } else x_launch_primal_back(X, c, s, ab);
-    HIPC(ctx, ctx->spans.end(PRIMAL_BACK, s, 1));
-    // (the Dual pass's forward half reads the lottery through its work units: the per-target segment records are built when somebody asks)
-    hipLaunchKernelGGL(k_lottery, dim3((unsigned)(P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, (int)P * c.n_e, ctx->d_err, dual ? 0 : 1, 1);
-    record_rewritten(ctx, !dual, !skip_fwd && HANK_XPRIMAL_LWG_IN_SWEEP);     // (skip_fwd: the Dual pass's forward half follows, and it writes no per-source records)
-    x_ensure_rng(ctx);
-    HIPC(ctx, ctx->spans.begin(PRIMAL_FWD, s));
-    if (!skip_fwd) {
-        XSweepFwdArgs fa{};
-        fa.c = c; fa.R = ctx->R; fa.sy = X.sync + 1; fa.st = X.st_D; fa.D0 = ctx->d_ss_D; fa.groups = 1; fa.Dvirt = X.Dvirt; fa.aggpart = X.aggpart;
-        fa.src = X.srcF; fa.units = X.unitsF; fa.overflow = X.unit_overflow; fa.all_members = X.neigh ? 0 : 1;
-        x_launch_fwd(X, c, 0, true, s, fa);
-    }
-    HIPC(ctx, ctx->spans.end(PRIMAL_FWD, s, 1));
-    if (!skip_fwd) x_value_epilogue(ctx);
-    HIPC(ctx, hipGetLastError());
-    rc = x_serialize_end(ctx);
-    if (rc) return rc;
-    ctx->stats[SWEEP_LAUNCHES] += skip_fwd ? 1 : 2;
-    X.last_passes = 1;
-    ctx->spans.invalidate({TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD});
-    if (skip_fwd) ctx->spans.invalidate({PRIMAL_FWD});      // (its two events bracket nothing)
+        x_launch_dual_back(sec, X, c, ps.D, db);
+    } else x_launch_primal_back(sec, X, c, ab);
+    HIPC(ctx, ctx->spans.end(PRIMAL_BACK, sec.stream(), 1));
     return HANK_OK;
 }
-
-// the N partials of `w` at the recorded primal: two persistent launches per pass of up to 8*dmax directions, every XCD a group
-// val: the first pass's forward sweep carries the value too (the Float64 distribution sweep of a Dual pass) and writes the record
-// skip_back: the backward sweep of this (one-pass) batch has run with the Float64 sweep (k_xdual_back, x_run_primal(.., dual))
-struct XOut { double *agg = nullptr, *dagg = nullptr; bool pro_done = false, done = false; };      // x_dual's merged launches: the caller's output buffers, and what has been done
-static int x_run_tangent(hank_ctx *ctx, XTan *w, bool val = false, bool skip_back = false, XOut *xo = nullptr) {
-    XWork &X = ctx->xw;
+// the Young lottery of the policies just written; seg: with the per-target segment records (the Dual pass whose forward sweep reads
+// the lottery through its work units leaves them to be built when somebody asks: ensure_seg)
+static void x_lottery(XSection &sec, bool seg) {
+    hank_ctx *ctx = sec.ctx;
     const Consts &c = ctx->c;
-    const size_t P = c.P;
-    hipStream_t s = ctx->stream;
-    int rc = x_serialize_begin(ctx);
-    if (rc) return rc;
-    const int np = (int)w->passes.size(), N = w->N;
-    // sync blocks 0, 1 belong to the primal sweeps (their status is checked with this call's when both ran unchecked)
-    if (!(xo && xo->pro_done)) {
-        rc = x_sync_reset(ctx, X.sync + 2, 2 * np, 2);
-        if (rc) return rc;
-    }
-    if (!skip_back) hipLaunchKernelGGL(k_tan_in, dim3((unsigned)((P * N + 255) / 256)), dim3(256), 0, s, w->dxhh, c.n_hh, (int)P, N, w->dxr, w->dxw, w->dxt);
-    if (!skip_back) hipLaunchKernelGGL(k_xrho, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, ctx->d_xhh, c.n_hh, (int)P, X.rho);     // (the primal may have been recorded by the launches)
-    if (!X.src_valid && !skip_back) {      // once per recorded primal: which members each member's gathers read, period by period
-        hipLaunchKernelGGL(k_xsrc_back, dim3((unsigned)P, X.Sact), dim3(256), 0, s, c, ctx->R, X.Sact, X.srcB);
-        X.src_valid = true;
-    }
-    x_ensure_rng(ctx);
-    const bool neigh = X.neigh;
+    hipLaunchKernelGGL(k_lottery, dim3((unsigned)(c.P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), sec.stream(), c, ctx->R, c.P * c.n_e, ctx->d_err, seg ? 1 : 0, 1);
+}
+// span TAN_BACK: the backward sweep of every pass of the batch, every XCD a group
+static int x_tan_back(XSection &sec, XTan *w) {
+    hank_ctx *ctx = sec.ctx; XWork &X = ctx->xw;
+    const int np = (int)w->passes.size();
     XTanBackArgs ab{};
-    ab.c = c; ab.R = ctx->R; ab.rho = X.rho; ab.xhh = ctx->d_xhh; ab.dxr = w->dxr; ab.dxw = w->dxw; ab.dxt = w->dxt; ab.Ntot = N; ab.st_ds = X.st_ds;
-    ab.src = neigh ? X.srcB.get() : nullptr;
+    ab.c = ctx->c; ab.R = ctx->R; ab.rho = X.rho; ab.xhh = ctx->d_xhh; ab.dxr = w->dxr; ab.dxw = w->dxw; ab.dxt = w->dxt; ab.Ntot = w->N; ab.st_ds = X.st_ds;
+    ab.src = X.neigh ? X.srcB.get() : nullptr;
     ab.stall = X.fault == 3 ? 1 : 0;
-    XSweepFwdArgs fa{};
-    fa.c = c; fa.R = ctx->R; fa.st = X.st_dD; fa.daggpart = w->daggpart; fa.src = X.srcF; fa.units = X.unitsF; fa.overflow = X.unit_overflow; fa.all_members = neigh ? 0 : 1;
-    HIPC(ctx, ctx->spans.begin(TAN_BACK, s));
-    for (int p = 0; p < np && !skip_back; p++) {
-        const XPass &ps = w->passes[p];
-        ab.n0 = ps.n0; ab.N = ps.N; ab.groups = ps.groups; ab.sy = X.sync + 2 + 2 * p; ab.dpol = w->dpol + ps.dpol_off;
-        x_launch_tan_back(X, c, ps.D, s, ab);
-    }
-    HIPC(ctx, ctx->spans.end(TAN_BACK, s, np));
-    HIPC(ctx, ctx->spans.begin(TAN_FWD, s));
-    const int nb = X.Sact;                  // (one row of partials per member: the sync wave sums a member's columns)
+    HIPC(ctx, ctx->spans.begin(TAN_BACK, sec.stream()));
     for (int p = 0; p < np; p++) {
         const XPass &ps = w->passes[p];
-        fa.sy = X.sync + 2 + 2 * p + 1; fa.groups = ps.groups; fa.dpol = w->dpol + ps.dpol_off;
-        const bool v = val && p == 0;
-        if (v) { fa.D0 = ctx->d_ss_D; fa.Dvirt = X.Dvirt; fa.aggpart = X.aggpart; }
-        else { rc = ensure_lwg(ctx); if (rc) return rc; }      // (behind k_xfix_D where the first pass carried the value)
-        x_launch_fwd(X, c, ps.D, v, s, fa);
-        const int W = XG * ps.D;
-        if (v && np == 1 && xo) {               // the one-pass Dual pass: everything behind the sweep in ONE launch (k_xdual_epilogue)
-            HIPC(ctx, ctx->spans.end(TAN_FWD, s, np));
-            const int per = 2 * W + 2 + c.n_e;
-            hipLaunchKernelGGL(k_xdual_epilogue, dim3((unsigned)((P * per + 255) / 256)), dim3(256), 0, s, c, X.aggpart, w->daggpart, X.Sact, W, ps.n0, ps.N, N,
-                               ctx->d_agg_rm, ctx->d_agg, w->dagg_pass, w->dagg_cm, ctx->R.Dseq, X.Dvirt, X.D0own, xo->agg, xo->dagg);
-            xo->done = true;
-            break;
-        }
-        if (v) x_value_epilogue(ctx);
-        if (p == np - 1) HIPC(ctx, ctx->spans.end(TAN_FWD, s, np));
-        hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * W + 63) / 64), dim3(256), 0, s, w->daggpart, nb, 2 * W, w->dagg_pass);
-        hipLaunchKernelGGL(k_xout, dim3((unsigned)((P * ps.N + 255) / 256)), dim3(256), 0, s, w->dagg_pass, (int)P, 2 * W, 0, ps.n0, ps.N, w->dagg_cm);
-        hipLaunchKernelGGL(k_xout, dim3((unsigned)((P * ps.N + 255) / 256)), dim3(256), 0, s, w->dagg_pass, (int)P, 2 * W, W, ps.n0, ps.N, w->dagg_cm + P * (size_t)N);
+        ab.n0 = ps.n0; ab.N = ps.N; ab.groups = ps.groups; ab.sy = X.sync + 2 + 2 * p; ab.dpol = w->dpol + ps.dpol_off;
+        x_launch_tan_back(sec, X, ctx->c, ps.D, ab);
     }
-    HIPC(ctx, hipGetLastError());
-    rc = x_serialize_end(ctx);
-    if (rc) return rc;
-    ctx->stats[SWEEP_LAUNCHES] += skip_back ? np : 2 * np;
-    X.last_passes = 1 + np;
-    ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
-    batch_ran(ctx, 1, w, N, w->dagg_cm, w->dpol, &w->passes);
+    HIPC(ctx, ctx->spans.end(TAN_BACK, sec.stream(), np));
     return HANK_OK;
+}
+// behind a forward sweep that carried the value: both aggregates summed over the members, and the virtual rows' mass folded into D_t
+static void x_value_epilogue(XSection &sec) {
+    hank_ctx *ctx = sec.ctx; const XWork &X = ctx->xw;
+    const Consts &c = ctx->c;
+    const size_t P = c.P;
+    hipStream_t s = sec.stream();
+    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, X.aggpart, X.Sact, 2, ctx->d_agg_rm);
+    hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
+    hipLaunchKernelGGL(k_xfix_D, dim3((unsigned)((P * c.n_e + 255) / 256)), dim3(256), 0, s, c, ctx->R.Dseq, X.Dvirt, X.Sact, X.D0own);
+}
+// the forward sweeps' arguments; val: the sweep carries the value, from D_0 on (the record's D_t, the virtual rows' mass, the aggregates' parts)
+static XSweepFwdArgs x_fwd_args(const hank_ctx *ctx, bool val) {
+    const XWork &X = ctx->xw;
+    XSweepFwdArgs fa{};
+    fa.c = ctx->c; fa.R = ctx->R; fa.src = X.srcF; fa.units = X.unitsF; fa.overflow = X.unit_overflow; fa.all_members = X.neigh ? 0 : 1;
+    if (val) { fa.D0 = ctx->d_ss_D; fa.Dvirt = X.Dvirt; fa.aggpart = X.aggpart; }
+    return fa;
+}
+// span PRIMAL_FWD: the Float64 distribution sweep alone (k_xfwd<0, true>), and its epilogue
+static int x_fwd_value(XSection &sec) {
+    hank_ctx *ctx = sec.ctx; XWork &X = ctx->xw;
+    XSweepFwdArgs fa = x_fwd_args(ctx, true);
+    fa.sy = X.sync + 1; fa.st = X.st_D; fa.groups = 1;
+    HIPC(ctx, ctx->spans.begin(PRIMAL_FWD, sec.stream()));
+    x_launch_fwd(sec, X, ctx->c, 0, true, fa);
+    HIPC(ctx, ctx->spans.end(PRIMAL_FWD, sec.stream(), 1));
+    x_value_epilogue(sec);
+    return HANK_OK;
+}
+// the forward sweep of pass p of the batch (k_xfwd<D, val>); val: it is the Float64 distribution sweep of a Dual pass too. Without,
+// it runs at the recorded primal and reads the per-source records, built here when a persistent Dual pass left them to be made
+static int x_tan_fwd(XSection &sec, XTan *w, int p, bool val) {
+    hank_ctx *ctx = sec.ctx; XWork &X = ctx->xw;
+    const XPass &ps = w->passes[p];
+    if (!val) { const int rc = ensure_lwg(ctx); if (rc) return rc; }
+    XSweepFwdArgs fa = x_fwd_args(ctx, val);
+    fa.sy = X.sync + 2 + 2 * p + 1; fa.st = X.st_dD; fa.daggpart = w->daggpart; fa.groups = ps.groups; fa.dpol = w->dpol + ps.dpol_off;
+    x_launch_fwd(sec, X, ctx->c, ps.D, val, fa);
+    return HANK_OK;
+}
+// behind the forward sweep of pass p: its partials of both aggregates, summed over the members (one row of partials per member:
+// the sync wave sums a member's columns) and written to their columns of dagg_cm
+static void x_tan_reduce(XSection &sec, XTan *w, int p) {
+    hank_ctx *ctx = sec.ctx;
+    const size_t P = ctx->c.P;
+    const XPass &ps = w->passes[p];
+    const int W = XG * ps.D;
+    hipStream_t s = sec.stream();
+    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * W + 63) / 64), dim3(256), 0, s, w->daggpart, ctx->xw.Sact, 2 * W, w->dagg_pass);
+    hipLaunchKernelGGL(k_xout, dim3((unsigned)((P * ps.N + 255) / 256)), dim3(256), 0, s, w->dagg_pass, (int)P, 2 * W, 0, ps.n0, ps.N, w->dagg_cm);
+    hipLaunchKernelGGL(k_xout, dim3((unsigned)((P * ps.N + 255) / 256)), dim3(256), 0, s, w->dagg_pass, (int)P, 2 * W, W, ps.n0, ps.N, w->dagg_cm + P * (size_t)w->N);
+}
+// passes `first`.. of the batch at the recorded primal, each with its reduction; TAN_FWD (begun by the body) ends behind the last sweep
+static int x_tan_fwd_from(XSection &sec, XTan *w, int first) {
+    hank_ctx *ctx = sec.ctx;
+    const int np = (int)w->passes.size();
+    for (int p = first; p < np; p++) {
+        const int rc = x_tan_fwd(sec, w, p, false); if (rc) return rc;
+        if (p == np - 1) HIPC(ctx, ctx->spans.end(TAN_FWD, sec.stream(), np));
+        x_tan_reduce(sec, w, p);
+    }
+    return HANK_OK;
+}
+// behind the value-carrying forward sweep of a ONE-pass batch: the value epilogue, the reduction and the copies to the caller's
+// buffers (null: not asked for) in one launch
+static void x_dual_epilogue(XSection &sec, XTan *w, double *d_agg_out, double *d_dagg_out) {
+    hank_ctx *ctx = sec.ctx; const XWork &X = ctx->xw;
+    const Consts &c = ctx->c;
+    const XPass &ps = w->passes[0];
+    const int W = XG * ps.D, per = 2 * W + 2 + c.n_e;
+    hipLaunchKernelGGL(k_xdual_epilogue, dim3((unsigned)(((size_t)c.P * per + 255) / 256)), dim3(256), 0, sec.stream(), c, X.aggpart, w->daggpart, X.Sact, W, ps.n0, ps.N, w->N,
+                       ctx->d_agg_rm, ctx->d_agg, w->dagg_pass, w->dagg_cm, ctx->R.Dseq, X.Dvirt, X.D0own, d_agg_out, d_dagg_out);
 }
 
 // after a synchronisation: did every sweep of the last call form its groups and meet all its barriers?
@@ -1044,7 +1065,8 @@ static bool use_wide(const hank_ctx *ctx, int N) {
 }
 
 template <int NE, int R, int MAXT, int KB, int KF>
-static int w_launch_geom(hank_ctx *ctx, bool fwd, int N, const WideArgs &a) {
+static int w_launch_geom(XSection &sec, bool fwd, int N, const WideArgs &a) {
+    hank_ctx *ctx = sec.ctx;
     const Consts &c = ctx->c;
     WMat<NE> M;
     for (int k = 0; k < NE; k++)
@@ -1054,21 +1076,22 @@ static int w_launch_geom(hank_ctx *ctx, bool fwd, int N, const WideArgs &a) {
     if (fwd) {
         const size_t lds = wide_lds_fwd(c, KF);
         HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wide_fwd<NE, R, MAXT, KF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_wide_fwd<NE, R, MAXT, KF>), grd, blk, lds, ctx->stream, a, M);
+        hipLaunchKernelGGL((k_wide_fwd<NE, R, MAXT, KF>), grd, blk, lds, sec.stream(), a, M);
     } else {
         const size_t lds = wide_lds_back(c, KB);
         if (c.diet) {
             HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wide_back<NE, R, MAXT, true, KB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_wide_back<NE, R, MAXT, true, KB>), grd, blk, lds, ctx->stream, a, M);
+            hipLaunchKernelGGL((k_wide_back<NE, R, MAXT, true, KB>), grd, blk, lds, sec.stream(), a, M);
         } else {
             HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wide_back<NE, R, MAXT, false, KB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_wide_back<NE, R, MAXT, false, KB>), grd, blk, lds, ctx->stream, a, M);
+            hipLaunchKernelGGL((k_wide_back<NE, R, MAXT, false, KB>), grd, blk, lds, sec.stream(), a, M);
         }
     }
     return HANK_OK;
 }
-static int w_launch(hank_ctx *ctx, bool fwd, int N, const WideArgs &a) {
-#define X(NEV) if (ctx->c.n_e == NEV) return ctx->wide_r == 2 ? w_launch_geom<NEV, 2, 1024, 16, 7>(ctx, fwd, N, a) : w_launch_geom<NEV, 4, 512, 16, 16>(ctx, fwd, N, a);
+static int w_launch(XSection &sec, bool fwd, int N, const WideArgs &a) {
+    hank_ctx *ctx = sec.ctx;
+#define X(NEV) if (ctx->c.n_e == NEV) return ctx->wide_r == 2 ? w_launch_geom<NEV, 2, 1024, 16, 7>(sec, fwd, N, a) : w_launch_geom<NEV, 4, 512, 16, 16>(sec, fwd, N, a);
     HANK_WIDE_NE_LIST(X)
 #undef X
     return fail(ctx, HANK_ERR_BAD_ARG, "on-chip wide sweeps: n_e=%d is not instantiated", ctx->c.n_e);
@@ -1090,9 +1113,9 @@ static int w_ensure_tan(hank_ctx *ctx, int N, bool staging, WTan **out) {
 // the N partials at the recorded primal (either schedule may have recorded it): two launches, one workgroup per direction
 static int w_run_tangent(hank_ctx *ctx, WTan *w, const double *d_dxhh) {
     const Consts &c = ctx->c;
-    hipStream_t s = ctx->stream;
-    int rc = x_serialize_begin(ctx);        // (a persistent sweep of another context must not find the chip half full of these workgroups)
-    if (rc) return rc;
+    XSection sec(ctx);                      // (a persistent sweep of another context must not find the chip half full of these workgroups)
+    HIPC(ctx, sec.opened());
+    hipStream_t s = sec.stream();
     if (!ctx->d_ibw) HIPC(ctx, ctx->d_ibw.alloc((size_t)c.P * c.G + 4));      // (before the kernel arguments are filled in)
     WideArgs a{};
     a.c = c; a.R = ctx->R; a.xhh = ctx->d_xhh; a.dxhh = d_dxhh; a.Ntot = w->N; a.n0 = 0; a.dpol = w->dpol; a.dagg = w->dagg_cm;
@@ -1108,19 +1131,18 @@ static int w_run_tangent(hank_ctx *ctx, WTan *w, const double *d_dxhh) {
         ctx->wprep_valid = true;
     }
     HIPC(ctx, ctx->spans.begin(TAN_BACK, s));
-    rc = w_launch(ctx, false, w->N, a);
+    int rc = w_launch(sec, false, w->N, a);
     if (rc) return rc;
     HIPC(ctx, ctx->spans.end(TAN_BACK, s, 1));
     HIPC(ctx, join_side(ctx));              // the forward sweep reads D_t and the {w, ig D} record of the primal's forward sweep
     rc = ensure_lwg(ctx);
     if (rc) return rc;
     HIPC(ctx, ctx->spans.begin(TAN_FWD, s));
-    rc = w_launch(ctx, true, w->N, a);
+    rc = w_launch(sec, true, w->N, a);
     if (rc) return rc;
     HIPC(ctx, ctx->spans.end(TAN_FWD, s, 1));
     HIPC(ctx, hipGetLastError());
-    rc = x_serialize_end(ctx);
-    if (rc) return rc;
+    HIPC(ctx, sec.close());
     ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
     batch_ran(ctx, 2, w, w->N, w->dagg_cm, w->dpol);
     ctx->stats[SWEEP_LAUNCHES] += 2;
@@ -1400,53 +1422,145 @@ static int run_primal(hank_ctx *ctx, double *d_agg_out) {
 }
 
 // ---- xcd schedule: entry-point bodies --------------------------------------------------------------
+// One body per shape of call. Each opens the call's ONE section, enqueues its steps top to bottom, closes the section and does
+// its bookkeeping: what the record now holds, which spans are valid, the launch count, and the sync blocks x_status will read.
+// P (hank_primal[_dev]): the Float64 recurrences at x — the policy sequence, the distribution path and the linearisation record
 static int x_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double *d_agg_out) {
-    int rc = x_setup(ctx);
-    if (rc) return rc;
+    int rc = x_setup(ctx); if (rc) return rc;
     HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * ctx->c.P, kind, ctx->stream));
-    rc = x_run_primal(ctx);
-    if (rc) return rc;
+    XSection sec(ctx);
+    HIPC(ctx, sec.opened());
+    rc = x_sync_reset(sec, ctx->xw.sync, 2, 1); if (rc) return rc;
+    x_zero_err(sec);
+    x_rho(sec);
+    rc = x_back(sec); if (rc) return rc;
+    x_lottery(sec, true);
+    record_rewritten(ctx, true, HANK_XPRIMAL_LWG_IN_SWEEP);
+    x_ensure_rng(sec);
+    rc = x_fwd_value(sec); if (rc) return rc;
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, sec.close());
+    ctx->stats[SWEEP_LAUNCHES] += 2;
+    ctx->xw.last_passes = 1;
+    ctx->spans.invalidate({TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD});
     HIPC(ctx, copy_agg(ctx, d_agg_out, hipMemcpyDeviceToDevice, ctx->stream));
     return HANK_OK;
 }
-// value and N partials; xhh == nullptr keeps the recorded primal (hank_jvp): the partials are linear recurrences at
-// that record, so a y-iteration pays the Float64 sweeps once (NewtonRaphson.jl:91) and each JVP (:95) only the tangent sweeps
-static bool x_dual_back_fits(const hank_ctx *ctx, int D);
-static int x_dual(hank_ctx *ctx, const double *xhh, const double *dxhh, hipMemcpyKind kind, int N, double *d_agg_out, double *d_dagg_out) {
-    int rc = x_setup(ctx);
-    if (rc) return rc;
+// T (hank_jvp[_dev]): the N partials at the recorded primal — linear recurrences at that record, so a y-iteration pays the Float64
+// sweeps once (NewtonRaphson.jl:91) and each JVP (:95) only these: two persistent launches per pass of up to 8*dmax directions
+static int x_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, double *d_dagg_out) {
+    int rc = x_setup(ctx); if (rc) return rc;
     XTan *w = nullptr;
-    rc = x_ensure_tan(ctx, N, &w);
+    rc = x_ensure_tan(ctx, N, &w); if (rc) return rc;
+    const int np = (int)w->passes.size();
+    HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * ctx->c.P * N, kind, ctx->stream));
+    XSection sec(ctx);
+    HIPC(ctx, sec.opened());
+    rc = x_tan_front(sec, w); if (rc) return rc;
+    x_ensure_rng(sec);
+    rc = x_tan_back(sec, w); if (rc) return rc;
+    HIPC(ctx, ctx->spans.begin(TAN_FWD, sec.stream()));
+    rc = x_tan_fwd_from(sec, w, 0); if (rc) return rc;
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, sec.close());
+    ctx->stats[SWEEP_LAUNCHES] += 2 * np;
+    ctx->xw.last_passes = 1 + np;
+    ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
+    batch_ran(ctx, 1, w, N, w->dagg_cm, w->dpol, &w->passes);
+    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
+    return HANK_OK;
+}
+// what a Dual pass leaves behind whichever sweeps carried it: the Float64 forward sweep rode on pass 0's (PRIMAL_FWD has no events
+// of its own and keeps a sweep's count of one launch), and x_status reads the primal's sync blocks and every pass's
+static void x_dual_ran(hank_ctx *ctx, XTan *w, int launches) {
+    ctx->stats[SWEEP_LAUNCHES] += launches;
+    ctx->xw.last_passes = 1 + (int)w->passes.size();
+    ctx->spans.absent(PRIMAL_FWD, 1);
+    ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
+    batch_ran(ctx, 1, w, w->N, w->dagg_cm, w->dpol, &w->passes);
+}
+// D2 (hank_primal_jvp[_dev] of several passes, or whose backward sweeps do not fuse): P's backward half, T's backward sweeps at the
+// record it wrote, and the Float64 distribution sweep on the forward sweep of pass 0 (k_xfwd<D, true>): 1 + 2 np persistent launches
+static int x_dual_two(hank_ctx *ctx, XTan *w, const double *xhh, const double *dxhh, hipMemcpyKind kind, double *d_agg_out, double *d_dagg_out) {
+    const size_t nP = (size_t)ctx->c.n_hh * ctx->c.P;
+    const int np = (int)w->passes.size();
+    XSection sec(ctx);
+    HIPC(ctx, sec.opened());
+    HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * nP * w->N, kind, sec.stream()));
+    HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * nP, kind, sec.stream()));
+    int rc = x_sync_reset(sec, ctx->xw.sync, 2, 1); if (rc) return rc;
+    x_zero_err(sec);
+    x_rho(sec);
+    rc = x_back(sec); if (rc) return rc;
+    x_lottery(sec, true);
+    record_rewritten(ctx, true, false);       // (no forward sweep of a Dual pass writes the per-source records)
+    x_ensure_rng(sec);
+    rc = x_tan_front(sec, w);
+    if (!rc) rc = x_tan_back(sec, w);
     if (rc) return rc;
-    const size_t P = ctx->c.P;
-    // a Dual pass of one pass (N <= 8 groups x 4): value and partials together in BOTH sweeps (k_xdual_back, k_xfwd<D, true>)
-    const bool fused_back = xhh && w->passes.size() == 1 && x_dual_back_fits(ctx, w->passes[0].D);
-    XOut xo;
-    xo.agg = d_agg_out; xo.dagg = d_dagg_out;
-    XWork &X = ctx->xw;
-    if (fused_back && kind == hipMemcpyDeviceToDevice && !X.fault) {
-        // the one-pass Dual pass on device-resident inputs (what bench.py times): ONE launch in front of the sweeps instead of seven
-        // launches and copies (k_xdual_prologue); a fault-injection run (HANK_XFAULT) keeps the separate launches
-        rc = x_serialize_begin(ctx);        // (the sync blocks about to be zeroed may belong to a sweep still in flight on another stream)
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_xdual_prologue, dim3(64), dim3(256), 0, ctx->stream, xhh, ctx->d_xhh, dxhh, w->dxhh, ctx->c.n_hh, (int)P, N, X.rho, w->dxr, w->dxw, w->dxt,
-                           reinterpret_cast<xv4u *>(X.sync.get()), sizeof(XSync) * 4 / sizeof(xv4u), ctx->d_err);
-        xo.pro_done = true;
+    HIPC(ctx, ctx->spans.begin(TAN_FWD, sec.stream()));
+    rc = x_tan_fwd(sec, w, 0, true); if (rc) return rc;
+    if (np == 1) {
+        HIPC(ctx, ctx->spans.end(TAN_FWD, sec.stream(), 1));
+        x_dual_epilogue(sec, w, d_agg_out, d_dagg_out);
     } else {
-        HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
-        if (xhh) HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * P, kind, ctx->stream));
+        x_value_epilogue(sec);
+        x_tan_reduce(sec, w, 0);
+        rc = x_tan_fwd_from(sec, w, 1); if (rc) return rc;
     }
-    if (xhh) {
-        rc = x_run_primal(ctx, true, fused_back ? w : nullptr, xo.pro_done);        // the distribution sweep rides on the tangents' forward sweep (value + partials)
-        if (rc) return rc;
-    }
-    rc = x_run_tangent(ctx, w, xhh != nullptr, fused_back, &xo);
-    if (rc) return rc;
-    if (!xo.done) {
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, sec.close());
+    x_dual_ran(ctx, w, 1 + 2 * np);
+    if (np > 1) {       // (k_xdual_epilogue has written the caller's buffers)
         HIPC(ctx, copy_agg(ctx, d_agg_out, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
+        HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, w->N, hipMemcpyDeviceToDevice));
     }
     return HANK_OK;
+}
+// D1 (the one-pass hank_primal_jvp[_dev], N <= 8 groups x 4: what bench.py times): value and partials together in BOTH sweeps
+// (k_xdual_back, k_xfwd<D, true>), two persistent launches. prologue: the inputs are device-resident and no fault is injected, so ONE
+// launch in front of the sweeps (k_xdual_prologue) stands for the seven launches, copies and memsets of the separate front
+static int x_dual_fused(hank_ctx *ctx, XTan *w, const double *xhh, const double *dxhh, hipMemcpyKind kind, bool prologue, double *d_agg_out, double *d_dagg_out) {
+    XWork &X = ctx->xw;
+    const size_t nP = (size_t)ctx->c.n_hh * ctx->c.P;
+    XSection sec(ctx);        // (the sync blocks about to be zeroed may belong to a sweep still in flight on another stream)
+    HIPC(ctx, sec.opened());
+    if (prologue) {
+        hipLaunchKernelGGL(k_xdual_prologue, dim3(64), dim3(256), 0, sec.stream(), xhh, ctx->d_xhh, dxhh, w->dxhh, ctx->c.n_hh, ctx->c.P, w->N, X.rho, w->dxr, w->dxw, w->dxt,
+                           reinterpret_cast<xv4u *>(X.sync.get()), sizeof(XSync) * 4 / sizeof(xv4u), ctx->d_err);
+    } else {
+        HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * nP * w->N, kind, sec.stream()));
+        HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * nP, kind, sec.stream()));
+        int rc = x_sync_reset(sec, X.sync, 2, 1);
+        if (!rc) rc = x_sync_reset(sec, X.sync + 2, 2, 2);
+        if (rc) return rc;
+        x_zero_err(sec);
+        x_rho(sec);
+        x_tan_in(sec, w);
+    }
+    int rc = x_back(sec, w); if (rc) return rc;
+    x_lottery(sec, false);
+    record_rewritten(ctx, false, false);
+    x_ensure_rng(sec);
+    HIPC(ctx, ctx->spans.begin(TAN_BACK, sec.stream()));      // (brackets nothing: k_xdual_back is PRIMAL_BACK's. The readers of
+    HIPC(ctx, ctx->spans.end(TAN_BACK, sec.stream(), 1));      // hank_last_timings count on a valid slot of about 0 ms)
+    HIPC(ctx, ctx->spans.begin(TAN_FWD, sec.stream()));
+    rc = x_tan_fwd(sec, w, 0, true); if (rc) return rc;
+    HIPC(ctx, ctx->spans.end(TAN_FWD, sec.stream(), 1));
+    x_dual_epilogue(sec, w, d_agg_out, d_dagg_out);
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, sec.close());
+    x_dual_ran(ctx, w, 2);
+    return HANK_OK;
+}
+// hank_primal_jvp[_dev] on the persistent sweeps: which shape, decided once
+static bool x_dual_back_fits(const hank_ctx *ctx, int D);
+static int x_dual(hank_ctx *ctx, const double *xhh, const double *dxhh, hipMemcpyKind kind, int N, double *d_agg_out, double *d_dagg_out) {
+    int rc = x_setup(ctx); if (rc) return rc;
+    XTan *w = nullptr;
+    rc = x_ensure_tan(ctx, N, &w); if (rc) return rc;
+    if (w->passes.size() != 1 || !x_dual_back_fits(ctx, w->passes[0].D)) return x_dual_two(ctx, w, xhh, dxhh, kind, d_agg_out, d_dagg_out);
+    return x_dual_fused(ctx, w, xhh, dxhh, kind, kind == hipMemcpyDeviceToDevice && !ctx->xw.fault, d_agg_out, d_dagg_out);      // (a fault-injection run, HANK_XFAULT, keeps the separate launches)
 }
 static bool use_x_primal(const hank_ctx *ctx) { return ctx->schedule >= 1; }
 // the persistent tangent sweeps' LDS grows with the horizon too (the group's dr/dw/dtr of every period): a long horizon goes
@@ -1585,7 +1699,7 @@ static int run_jvp(hank_ctx *ctx, TanWork &w) {
 // this width at the recorded primal; batch_ran has named the family and its buffers when this returns HANK_OK
 static int enqueue_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, double *d_dagg_out) {
     if (use_wide(ctx, N)) return w_jvp(ctx, dxhh, kind, N, d_dagg_out);
-    if (use_x_jvp(ctx, N)) return x_dual(ctx, nullptr, dxhh, kind, N, nullptr, d_dagg_out);
+    if (use_x_jvp(ctx, N)) return x_jvp(ctx, dxhh, kind, N, d_dagg_out);
     TanWork *w = nullptr;
     int rc = ensure_tanwork(ctx, N, &w);
     if (rc) return rc;
@@ -2434,8 +2548,8 @@ static int stat_device_error(hank_ctx *ctx) {
     return HANK_OK;
 }
 
-static void x_launch_vfi(const XWork &X, const Consts &c, hipStream_t s, const XVfiArgs &a) { const size_t lds = x_lds_vfi(c); x_by_maxt(X, [&](auto mt) { XL(k_xvfi<decltype(mt)::value>); }); }
-static void x_launch_stat(const XWork &X, const Consts &c, hipStream_t s, const XStatArgs &a) { const size_t lds = x_lds_stat(c); x_by_maxt(X, [&](auto mt) { XL(k_xstat<decltype(mt)::value>); }); }
+static void x_launch_vfi(XSection &sec, const XWork &X, const Consts &c, const XVfiArgs &a) { const size_t lds = x_lds_vfi(c); x_by_maxt(X, [&](auto mt) { XL(k_xvfi<decltype(mt)::value>); }); }
+static void x_launch_stat(XSection &sec, const XWork &X, const Consts &c, const XStatArgs &a) { const size_t lds = x_lds_stat(c); x_by_maxt(X, [&](auto mt) { XL(k_xstat<decltype(mt)::value>); }); }
 #undef XL
 // A steady-state fixed point as ONE persistent launch on the group of XCD 0 (`launch` enqueues it on sync block 0), through to the
 // fallback decision. HANK_OK with *ran: the group formed and xs holds the kernel's {steps, converged} (d_state); HANK_OK without: it
@@ -2445,13 +2559,14 @@ static int x_fixed_point(hank_ctx *ctx, const char *what, int *d_state, int xs[2
     hipStream_t s = ctx->stream;
     int rc = x_setup(ctx);
     XWork &X = ctx->xw;
-    if (!rc) rc = x_serialize_begin(ctx);
-    if (!rc) rc = x_sync_reset(ctx, X.sync, 1, 4);
     if (rc) return rc;
-    launch(X);
+    XSection sec(ctx);
+    HIPC(ctx, sec.opened());
+    rc = x_sync_reset(sec, X.sync, 1, 4);
+    if (rc) return rc;
+    launch(sec, X);
     HIPC(ctx, hipGetLastError());
-    rc = x_serialize_end(ctx);
-    if (rc) return rc;
+    HIPC(ctx, sec.close());
     XSync hsy;
     HIPC(ctx, hipMemcpyAsync(xs, d_state, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipMemcpyAsync(&hsy, X.sync, sizeof(XSync), hipMemcpyDeviceToHost, s));
@@ -2509,11 +2624,11 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
         // the whole iteration as ONE persistent launch on the group of XCD 0 (k_xvfi): the vote on convergence rides on the group barrier
         int xs[2] = {0, 0};      // {steps, converged}
         bool ran = false;
-        int rc = x_fixed_point(ctx, "value iteration", state, xs, &ran, [&](const XWork &X) {
+        int rc = x_fixed_point(ctx, "value iteration", state, xs, &ran, [&](XSection &sec, const XWork &X) {
             XVfiArgs va{};
             va.c = c; va.V0 = V[0]; va.r = r; va.w = w; va.tr = tr; va.tol = tol; va.max_iter = max_iter; va.sy = X.sync; va.st_s = X.st_s;
             va.err = ctx->d_err; va.Vout = V[1]; va.pol = pol; va.iters = state; va.supnorm = norm;
-            x_launch_vfi(X, c, s, va);
+            x_launch_vfi(sec, X, c, va);
         });
         if (rc) return rc;
         if (ran) {
@@ -2578,11 +2693,11 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         // the whole power method as ONE persistent launch on the group of XCD 0 (k_xstat)
         int xs[2] = {0, 0};
         bool ran = false;
-        int rc = x_fixed_point(ctx, "power method", state, xs, &ran, [&](const XWork &X) {
+        int rc = x_fixed_point(ctx, "power method", state, xs, &ran, [&](XSection &sec, const XWork &X) {
             XStatArgs sa{};
             sa.c = c; sa.R = R; sa.D0 = D[0]; sa.tol = tol; sa.max_iter = max_iter; sa.check_every = check_every; sa.sy = X.sync;
             sa.st_D = X.st_D; sa.Dout = D[1]; sa.iters = state;
-            x_launch_stat(X, c, s, sa);
+            x_launch_stat(sec, X, c, sa);
         });
         if (rc) return rc;
         if (ran) {

@@ -68,6 +68,58 @@ def test_create_on_a_named_device_and_device_group(hank):
     g.close(); hb1.close(); hb0.close()
 
 
+def test_two_host_threads_drive_two_contexts_on_one_gpu_through_the_persistent_sweeps(hank):
+    """two contexts on the same GPU, each driven by its own host thread on the forced persistent schedule: the chip-filling
+    launches of ONE call are enqueued as one block (the device's section), and every block is ordered behind the one before.
+    A sweep that found the chip shared would fail loudly (a forced schedule has no fallback); a section that lost its lock or
+    its event would deadlock or give other bits. Per round and context: a three-pass Dual pass (32 + 32 + 6 directions: 1 + 2*3
+    persistent launches), a fused one-pass Dual pass (2) and a three-pass batch at the recorded primal (2*3)."""
+    import threading
+    m, ss, _ = ks_setup(37, 3, 9)
+    P, rounds = 8, 20
+    x, _ = ks_paths(m, ss, "x1", 0.05)
+    rng = np.random.default_rng(11)
+    y70, y5 = rng.standard_normal((2, P, 70)), rng.standard_normal((2, P, 5))
+
+    def triple(hb):
+        a70, d70 = hb.primal_jvp(x[2:4], y70)
+        a5, d5 = hb.primal_jvp(1.01 * x[2:4], y5)
+        return [a70, d70, a5, d5, hb.jvp(y70)]
+
+    hbs = [block(hank, m, "xcd", HANK_PRIMAL_MEMO=0) for _ in range(2)]
+    try:
+        for hb in hbs:
+            hb.set_boundary(ss.value, ss.D)
+        expected = [triple(hb) for hb in hbs]
+        before = [hb.stats()["sweep_launches"] for hb in hbs]
+        got, errors = [[], []], []
+
+        def drive(k):
+            try:
+                for _ in range(rounds):
+                    got[k].append(triple(hbs[k]))
+            except BaseException as e:      # (reported by the main thread)
+                errors.append((k, e))
+
+        threads = [threading.Thread(target=drive, args=(k,)) for k in range(2)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert not errors, errors
+        for k, hb in enumerate(hbs):
+            assert len(got[k]) == rounds
+            for res in got[k]:
+                for r, e in zip(res, expected[k]):
+                    np.testing.assert_array_equal(r, e)
+            st = hb.stats()
+            assert st["fallbacks"] == 0
+            assert st["sweep_launches"] - before[k] == rounds * (7 + 2 + 6)
+    finally:
+        for hb in hbs:
+            hb.close()
+
+
 def test_a_failed_workspace_allocation_is_not_cached(hank):
     """a tangent batch too wide for the card's memory (dpol alone: P*G*N*8 bytes) is refused with NOMEM, and again on a retry
     with the same N — the half-built workspace must not stay in the per-width cache (a second call used to find it, return OK
