@@ -129,7 +129,9 @@ int hank_jvp_dev(hank_ctx *ctx, const double *d_dxhh, int32_t N, double *d_dagg_
 /* hank_check: sync + fetch the device error word of the last primal. A persistent sweep that could not run (HANK_ERR_SWEEP:
  * its groups did not form, a wait ran into its deadline) is reported here for the asynchronous entries — which cannot re-run
  * a call — ONCE: a context whose schedule was not forced (HANK_SCHEDULE) continues on the per-period launches, so the caller's
- * next call succeeds (hank_stats out[4] counts it). */
+ * next call succeeds (hank_stats out[4] counts it). A model error reported here (knots, domain, a non-monotone policy) is an
+ * error on the recorded primal: it leaves no tangent batch current, so hank_get_dpolicy_seq and the other readers answer
+ * HANK_ERR_NOT_READY until the next primal, exactly as after the host-pointer entries. */
 int hank_check(hank_ctx *ctx);
 
 /* hank_primal_jvp == JVP(fullFunction, x, y) exactly as the reference evaluates it: the Dual pass

@@ -123,7 +123,7 @@ struct XWork {
                                               // group is short of members") and leaves at once — exercises the fallback paths
     bool src_valid = false;
     std::list<XTan> tans;           // most recently used first
-    int last_passes = 0;            // sync blocks the last call used (their status words are checked)
+    int last_blocks = 0;            // sync blocks the last call used, from block 0 (x_status checks their status words)
 };
 
 // ---- on-chip wide sweeps (hank_wide.h): tangent buffers per batch width ----
@@ -395,6 +395,9 @@ static int end_capture(hank_ctx *ctx, GraphExec *out) {
     return HANK_OK;
 }
 
+// the error word starts a run of kernels clean, in stream order (the sweeps, the granular steps, the steady state's fixed points)
+static void zero_err(hank_ctx *ctx, hipStream_t s) { hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4); }
+
 static int build_primal_graphs(hank_ctx *ctx) {
     const Consts &c = ctx->c;
     const int P = c.P;
@@ -403,7 +406,7 @@ static int build_primal_graphs(hank_ctx *ctx) {
     const size_t lds = primal_lds(c);
     // backward: X of the last period from the terminal value, then P fused Y;X steps, then lottery
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);
+    zero_err(ctx, s);
     hipLaunchKernelGGL(k_egm_X, grd, blk, lds, s, c, ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
                        ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, P - 1, (const int *)nullptr);
     for (int t = P - 1; t >= 0; t--)
@@ -496,7 +499,7 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     const dim3 pblk(RBP * c.n_e), pgrd(ctx->nbp);
     const size_t lds = primal_lds(c);
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);
+    zero_err(ctx, s);
     hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
     hipLaunchKernelGGL(k_egm_X, pgrd, pblk, lds, s, c, ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
                        ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, (int)P - 1, (const int *)nullptr);
@@ -610,40 +613,107 @@ static int ensure_graphs(hank_ctx *ctx, TanWork &w, int which) {
     return w.VF == 2 ? capture_tangent_graphs<double, double2>(ctx, w, which) : capture_tangent_graphs<double, double>(ctx, w, which);
 }
 
-static int x_status(hank_ctx *ctx);
-static int fetch_device_error(hank_ctx *ctx) {
-    int e[4] = {0, 0, 0, 0};
+// ---- the device's verdict on work already enqueued, and what the context does about it ------------------
+// Three sources — the error word d_err, the persistent sweeps' status (x_status), the fallback decision — and one consequence: the
+// caller says WHOSE work the verdict speaks about. THE_RECORD: the sweeps that (re)write the record (hank_primal*, hank_jvp,
+// hank_check, fake_news, and what an earlier asynchronous sweep left pending when a call-scoped entry starts): an error goes through
+// record_gone, so the batch, the cotangent batch and everything derived from the record go with it, as for a new boundary.
+// THIS_CALL: the call's own kernels on its own buffers (the granular steps, hank_vfi, hank_stationary_dist): an error leaves the
+// record and the batch exactly as they were.
+enum Whose { THE_RECORD, THIS_CALL };
+enum ErrIn { IN_SWEEP, IN_VFI, IN_POWER_METHOD };      // which kernels raised the word: a sweep over the periods, steps of the value iteration, the power method
+static int x_status(hank_ctx *ctx, const char *what, const XSync *fetched = nullptr);
+// the ONE host read of the error word: drain, copy {code, period, state, index}, clear it when set (reported once: the next call starts clean)
+static int take_error_word(hank_ctx *ctx, int e[4]) {
     HIPC(ctx, join_side(ctx));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    HIPC(ctx, hipMemcpy(e, ctx->d_err, sizeof(e), hipMemcpyDeviceToHost));
-    if (ctx->schedule >= 1) {
-        // a persistent sweep that did not run (its groups did not form, a wait timed out) leaves the record unwritten: what
-        // the kernels behind it then found in it (a "non-monotone policy", say) is not an error of the model — report the sweep
-        const int xs = x_status(ctx);
-        if (xs) {
-            if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, sizeof(e), ctx->stream));
-            return xs;
-        }
+    HIPC(ctx, hipMemcpy(e, ctx->d_err, 4 * sizeof(int), hipMemcpyDeviceToHost));
+    if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, 4 * sizeof(int), ctx->stream));
+    return HANK_OK;
+}
+// the word as a status code and message (step: the caller's count of the fixed-point step that raised it)
+static int word_verdict(hank_ctx *ctx, Whose whose, const int e[4], ErrIn in, int step = 0) {
+    int rc = HANK_OK;
+    if (in == IN_VFI) {
+        if (e[0] == ERR_KNOTS)
+            rc = fail(ctx, HANK_ERR_KNOTS, "knot-vectors must be unique and sorted in increasing order (steady-state value iteration, step %d, "
+                      "productivity state %d, wealth index %d)", step, e[2] + 1, e[3] + 1);
+        else if (e[0] == ERR_DOMAIN)
+            rc = fail(ctx, HANK_ERR_DOMAIN, "DomainError: negative base under a non-integer power (steady-state value iteration, step %d)", step);
+    } else if (in == IN_POWER_METHOD) {
+        if (e[0] == ERR_NONMONO) rc = fail(ctx, HANK_ERR_NONMONOTONE, "savings policy is not monotone in wealth (productivity state %d, wealth index %d)", e[2] + 1, e[3] + 1);
+    } else if (e[0] == ERR_KNOTS)
+        rc = fail(ctx, HANK_ERR_KNOTS,
+                  "knot-vectors must be unique and sorted in increasing order (EGM implied state, "
+                  "period %d, productivity state %d, wealth index %d)", e[1] + 1, e[2] + 1, e[3] + 1);
+    else if (e[0] == ERR_DOMAIN)
+        rc = fail(ctx, HANK_ERR_DOMAIN,
+                  "DomainError: negative base under a non-integer power (period %d, productivity "
+                  "state %d, wealth index %d)", e[1] + 1, e[2] + 1, e[3] + 1);
+    else if (e[0] == ERR_NONMONO)
+        rc = fail(ctx, HANK_ERR_NONMONOTONE,
+                  "savings policy is not monotone in wealth (period %d, productivity state %d, "
+                  "wealth index %d)", e[1] + 1, e[2] + 1, e[3] + 1);
+    else if (e[0] != 0)
+        rc = fail(ctx, HANK_ERR_BAD_ARG, "unknown device error %d (%d,%d,%d) d_err=%p", e[0], e[1], e[2], e[3], (void *)ctx->d_err.get());
+    if (rc && whose == THE_RECORD) record_gone(ctx);
+    return rc;
+}
+// the verdict on sweeps: a persistent sweep that did not run (its groups did not form, a wait timed out) leaves the record
+// unwritten: what the kernels behind it then found in it (a "non-monotone policy", say) is not an error of the model — the sweep's
+// status outranks the word
+static int device_verdict(hank_ctx *ctx, Whose whose) {
+    int e[4] = {0, 0, 0, 0};
+    int rc = take_error_word(ctx, e);
+    if (rc) return rc;
+    if (ctx->schedule >= 1 && (rc = x_status(ctx, nullptr)) != HANK_OK) {
+        if (whose == THE_RECORD) record_gone(ctx);
+        return rc;
     }
-    if (e[0] == 0) return HANK_OK;
-    ctx->primal_done = false;
-    HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, sizeof(e), ctx->stream));      // reported once: the next call starts clean
-    switch (e[0]) {
-    case ERR_KNOTS:
-        return fail(ctx, HANK_ERR_KNOTS,
-                    "knot-vectors must be unique and sorted in increasing order (EGM implied state, "
-                    "period %d, productivity state %d, wealth index %d)", e[1] + 1, e[2] + 1, e[3] + 1);
-    case ERR_DOMAIN:
-        return fail(ctx, HANK_ERR_DOMAIN,
-                    "DomainError: negative base under a non-integer power (period %d, productivity "
-                    "state %d, wealth index %d)", e[1] + 1, e[2] + 1, e[3] + 1);
-    case ERR_NONMONO:
-        return fail(ctx, HANK_ERR_NONMONOTONE,
-                    "savings policy is not monotone in wealth (period %d, productivity state %d, "
-                    "wealth index %d)", e[1] + 1, e[2] + 1, e[3] + 1);
-    default:
-        return fail(ctx, HANK_ERR_BAD_ARG, "unknown device error %d (%d,%d,%d) d_err=%p", e[0], e[1], e[2], e[3], (void *)ctx->d_err.get());
+    return word_verdict(ctx, whose, e, IN_SWEEP);
+}
+
+// a sweep could not form its groups (or timed out): this context continues on the per-period launches
+static int to_launch_schedule(hank_ctx *ctx) {
+    record_gone(ctx);
+    if (!ctx->g_pback) {                    // (a context that has only run persistent sweeps has never captured them)
+        const int rc = build_primal_graphs(ctx);
+        if (rc != HANK_OK) return rc;       // the schedule is left as it was: the next call reports the sweep's failure again, not a null graph
     }
+    ctx->schedule = 0;
+    ctx->stats[FALLBACKS]++;
+    return HANK_OK;
+}
+static bool x_fallback_allowed(const hank_ctx *ctx) { return !ctx->forced_xcd; }      // a schedule forced at hank_create fails loudly instead
+// the ONE fallback decision on a verdict: anything but a sweep that could not run, or a forced schedule, is reported as it is.
+// Otherwise the context moves to the launches (*moved: the work can be run again, they serve it now) and the return value is still
+// the sweep's status with the sweep's message, kept here across the move — unless the launches' graphs cannot be built either: then
+// THAT is what the caller has to see (the message names it), and the context stays unusable until a later call builds them
+static int fallback_decision(hank_ctx *ctx, int verdict, bool *moved) {
+    *moved = false;
+    if (verdict != HANK_ERR_SWEEP || !x_fallback_allowed(ctx)) return verdict;
+    char keep[sizeof(ctx->errmsg)];
+    memcpy(keep, ctx->errmsg, sizeof(keep));
+    const int rc = to_launch_schedule(ctx);
+    if (rc != HANK_OK) return rc;
+    memcpy(ctx->errmsg, keep, sizeof(keep));
+    *moved = true;
+    return verdict;
+}
+// after a host-pointer entry has enqueued its work: drain it and take the verdict on the record. *rerun: the context has moved to
+// the launches, the caller runs its work again. (The device-pointer entries never re-run work: hank_check reports and moves the context.)
+static int settle(hank_ctx *ctx, bool *rerun) {
+    const int rc = fallback_decision(ctx, device_verdict(ctx, THE_RECORD), rerun);
+    return *rerun ? HANK_OK : rc;
+}
+// a host-pointer entry: enqueue, settle, and when the context has moved to the launches enqueue again and take their verdict
+template <typename Enqueue>
+static int run_settled(hank_ctx *ctx, Enqueue enqueue) {
+    bool rerun = false;
+    int rc = enqueue();
+    if (!rc) rc = settle(ctx, &rerun);
+    if (rerun) rc = enqueue();
+    return rerun && !rc ? device_verdict(ctx, THE_RECORD) : rc;
 }
 
 // ================================ XCD-local persistent sweeps: host side ==========================
@@ -866,7 +936,6 @@ static int x_sync_reset(XSection &sec, XSync *base, int count, int where) {     
 // bodies that compose them (x_primal, x_jvp, x_dual_two, x_dual_fused: one per shape of call) hold the section and the bookkeeping.
 // Sync blocks: 0, 1 the Float64 sweeps (backward, forward); 2 + 2p, 3 + 2p the backward and forward sweep of tangent pass p (a
 // forward sweep that carries the value too is still pass 0's): x_status reads them in this order.
-static void x_zero_err(XSection &sec) { hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, sec.stream(), sec.ctx->d_err, 4); }
 static void x_rho(XSection &sec) {
     hank_ctx *ctx = sec.ctx;
     hipLaunchKernelGGL(k_xrho, dim3((unsigned)((ctx->c.P + 255) / 256)), dim3(256), 0, sec.stream(), ctx->d_xhh, ctx->c.n_hh, ctx->c.P, ctx->xw.rho);
@@ -1005,22 +1074,28 @@ static void x_dual_epilogue(XSection &sec, XTan *w, double *d_agg_out, double *d
                        ctx->d_agg_rm, ctx->d_agg, w->dagg_pass, w->dagg_cm, ctx->R.Dseq, X.Dvirt, X.D0own, d_agg_out, d_dagg_out);
 }
 
-// after a synchronisation: did every sweep of the last call form its groups and meet all its barriers?
-static int x_status(hank_ctx *ctx) {
+// after a synchronisation: did every persistent launch of the last call form its groups and meet all its barriers? The ONE judge of
+// the sync blocks. For the sweeps (what == nullptr) it reads them itself, behind the work units' overflow flag (the forward sweeps');
+// for a steady-state fixed point, `what` is its name (its wording) and `fetched` its one block, which x_fixed_point copied in front
+// of the synchronisation. What the answer does to the record is the caller's business (device_verdict)
+static int x_status(hank_ctx *ctx, const char *what, const XSync *fetched) {
     XWork &X = ctx->xw;
-    if (!X.ready || X.last_passes == 0) return HANK_OK;
-    int uo = 0;
-    HIPC(ctx, hipMemcpy(&uo, X.unit_overflow, sizeof(int), hipMemcpyDeviceToHost));
-    if (uo) {
-        HIPC(ctx, hipMemsetAsync(X.unit_overflow, 0, sizeof(int), ctx->stream));
-        record_gone(ctx);
-        return fail(ctx, HANK_ERR_SWEEP, "persistent forward sweep: a member's walk over its sources needs more than %d work units (a savings policy this flat is served by the per-period launches)", XUCAP);
+    std::vector<XSync> own;
+    if (!fetched) {
+        if (!X.ready || X.last_blocks == 0) return HANK_OK;
+        int uo = 0;
+        HIPC(ctx, hipMemcpy(&uo, X.unit_overflow, sizeof(int), hipMemcpyDeviceToHost));
+        if (uo) {
+            HIPC(ctx, hipMemsetAsync(X.unit_overflow, 0, sizeof(int), ctx->stream));
+            return fail(ctx, HANK_ERR_SWEEP, "persistent forward sweep: a member's walk over its sources needs more than %d work units (a savings policy this flat is served by the per-period launches)", XUCAP);
+        }
+        own.resize((size_t)X.last_blocks);
+        HIPC(ctx, hipMemcpy(own.data(), X.sync, sizeof(XSync) * own.size(), hipMemcpyDeviceToHost));
     }
-    std::vector<XSync> h(2 * (size_t)X.last_passes);
-    HIPC(ctx, hipMemcpy(h.data(), X.sync, sizeof(XSync) * h.size(), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < h.size(); k++)
+    const XSync *h = fetched ? fetched : own.data();
+    for (size_t k = 0; k < (fetched ? 1 : own.size()); k++)
         if (h[k].status[0] != 0) {
-            record_gone(ctx);
+            if (what) return fail(ctx, HANK_ERR_SWEEP, "persistent %s: %s on XCD %u", what, h[k].status[0] == XERR_PLACEMENT ? "the group is short of members" : "a wait timed out", h[k].status[1]);
             char waited[64] = "";
             if (h[k].status[0] == XERR_TIMEOUT) snprintf(waited, sizeof(waited), " after %.1f ms", h[k].status[2] / 1000.0);
             return fail(ctx, HANK_ERR_SWEEP, "persistent %s sweep %zu (0 = primal, then one per tangent pass): %s%s on XCD %u (workgroups per XCD: %u %u %u %u %u %u %u %u)",
@@ -1431,7 +1506,7 @@ static int x_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double
     XSection sec(ctx);
     HIPC(ctx, sec.opened());
     rc = x_sync_reset(sec, ctx->xw.sync, 2, 1); if (rc) return rc;
-    x_zero_err(sec);
+    zero_err(ctx, sec.stream());
     x_rho(sec);
     rc = x_back(sec); if (rc) return rc;
     x_lottery(sec, true);
@@ -1441,7 +1516,7 @@ static int x_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double
     HIPC(ctx, hipGetLastError());
     HIPC(ctx, sec.close());
     ctx->stats[SWEEP_LAUNCHES] += 2;
-    ctx->xw.last_passes = 1;
+    ctx->xw.last_blocks = 2;
     ctx->spans.invalidate({TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD});
     HIPC(ctx, copy_agg(ctx, d_agg_out, hipMemcpyDeviceToDevice, ctx->stream));
     return HANK_OK;
@@ -1464,7 +1539,7 @@ static int x_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, d
     HIPC(ctx, hipGetLastError());
     HIPC(ctx, sec.close());
     ctx->stats[SWEEP_LAUNCHES] += 2 * np;
-    ctx->xw.last_passes = 1 + np;
+    ctx->xw.last_blocks = 2 + 2 * np;
     ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
     batch_ran(ctx, 1, w, N, w->dagg_cm, w->dpol, &w->passes);
     HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
@@ -1474,7 +1549,7 @@ static int x_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, d
 // of its own and keeps a sweep's count of one launch), and x_status reads the primal's sync blocks and every pass's
 static void x_dual_ran(hank_ctx *ctx, XTan *w, int launches) {
     ctx->stats[SWEEP_LAUNCHES] += launches;
-    ctx->xw.last_passes = 1 + (int)w->passes.size();
+    ctx->xw.last_blocks = 2 + 2 * (int)w->passes.size();
     ctx->spans.absent(PRIMAL_FWD, 1);
     ctx->spans.invalidate({DUAL_BACK, DUAL_FWD});
     batch_ran(ctx, 1, w, w->N, w->dagg_cm, w->dpol, &w->passes);
@@ -1489,7 +1564,7 @@ static int x_dual_two(hank_ctx *ctx, XTan *w, const double *xhh, const double *d
     HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * nP * w->N, kind, sec.stream()));
     HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * nP, kind, sec.stream()));
     int rc = x_sync_reset(sec, ctx->xw.sync, 2, 1); if (rc) return rc;
-    x_zero_err(sec);
+    zero_err(ctx, sec.stream());
     x_rho(sec);
     rc = x_back(sec); if (rc) return rc;
     x_lottery(sec, true);
@@ -1534,7 +1609,7 @@ static int x_dual_fused(hank_ctx *ctx, XTan *w, const double *xhh, const double 
         int rc = x_sync_reset(sec, X.sync, 2, 1);
         if (!rc) rc = x_sync_reset(sec, X.sync + 2, 2, 2);
         if (rc) return rc;
-        x_zero_err(sec);
+        zero_err(ctx, sec.stream());
         x_rho(sec);
         x_tan_in(sec, w);
     }
@@ -1585,49 +1660,11 @@ static bool use_x_fused(const hank_ctx *ctx, int N) {
     return N <= XG * ctx->xw.dmax && x_dual_back_fits(ctx, ctx->xw.dmax);
 }
 
-// a sweep could not form its groups (or timed out): this context continues on the per-period launches
-static int to_launch_schedule(hank_ctx *ctx) {
-    record_gone(ctx);
-    if (!ctx->g_pback) {                    // (a context that has only run persistent sweeps has never captured them)
-        const int rc = build_primal_graphs(ctx);
-        if (rc != HANK_OK) return rc;       // the schedule is left as it was: the next call reports the sweep's failure again, not a null graph
-    }
-    ctx->schedule = 0;
-    ctx->stats[FALLBACKS]++;
-    return HANK_OK;
-}
-static bool x_fallback_allowed(const hank_ctx *ctx) { return !ctx->forced_xcd; }      // a schedule forced at hank_create fails loudly instead
-
-// after a host-pointer entry has enqueued its work: drain it and take the device's verdict. A persistent sweep that could not
-// run moves the context to the per-period launches (unless its schedule was forced) and sets *rerun: the caller runs its work
-// again, which the launches now serve. (The device-pointer entries never re-run work: hank_check reports and moves the context.)
-static int settle(hank_ctx *ctx, bool *rerun) {
-    *rerun = false;
-    int rc = fetch_device_error(ctx);
-    if (rc == HANK_ERR_SWEEP && x_fallback_allowed(ctx)) {
-        rc = to_launch_schedule(ctx);
-        *rerun = rc == HANK_OK;
-    }
-    return rc;
-}
-
 static int check_rates(hank_ctx *ctx, const double *xhh) {      // the host-pointer entries see x before the device does
     for (int t = 0; t < ctx->c.P; t++)
         if (!(1.0 + xhh[ctx->c.n_hh * t] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive (period %zu)", (size_t)t + 1);
     return HANK_OK;
 }
-}  // extern "C" (a template)
-// a host-pointer entry: enqueue, settle, and when the context has moved to the launches enqueue again and take their verdict
-template <typename Enqueue>
-static int run_settled(hank_ctx *ctx, Enqueue enqueue) {
-    bool rerun = false;
-    int rc = enqueue();
-    if (!rc) rc = settle(ctx, &rerun);
-    if (rerun) rc = enqueue();
-    return rerun && !rc ? fetch_device_error(ctx) : rc;
-}
-extern "C" {
-
 // hank_primal[_dev]: x from the caller (kind: where it lives) and the Float64 sweeps of the context's schedule
 static int enqueue_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double *d_agg_out) {
     if (use_x_primal(ctx)) return x_primal(ctx, xhh, kind, d_agg_out);
@@ -1647,18 +1684,10 @@ int hank_primal_dev(hank_ctx *ctx, const double *d_xhh, double *d_agg_out) {
 int hank_check(hank_ctx *ctx) {
     ENTER(ctx);
     if (!ctx) return HANK_ERR_BAD_ARG;
-    const int rc = fetch_device_error(ctx);
-    // the asynchronous entries cannot re-run a call: the error is reported (once), and a context whose schedule was not forced
-    // continues on the per-period launches, so the caller's next call succeeds
-    if (rc == HANK_ERR_SWEEP && ctx->schedule >= 1 && x_fallback_allowed(ctx)) {
-        char keep[sizeof(ctx->errmsg)];
-        memcpy(keep, ctx->errmsg, sizeof(keep));
-        const int rc2 = to_launch_schedule(ctx);
-        if (rc2 != HANK_OK) return rc2;     // the launches' graphs could not be built either: THAT is what the caller has to see (the
-                                            // message names it); the context stays unusable until a later call succeeds in building them
-        memcpy(ctx->errmsg, keep, sizeof(keep));
-    }
-    return rc;
+    // the asynchronous entries cannot re-run a call: the error is reported (once, and a model error leaves no tangent batch current),
+    // and a context whose schedule was not forced continues on the per-period launches, so the caller's next call succeeds
+    bool moved = false;
+    return fallback_decision(ctx, device_verdict(ctx, THE_RECORD), &moved);
 }
 
 int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
@@ -1724,18 +1753,16 @@ int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp");
     int rc = enqueue_jvp(ctx, dxhh, hipMemcpyHostToDevice, N, nullptr);
     if (rc) return rc;
-    // the launches' tangent sweeps raise no device error; the on-chip wide sweeps do, but have no cross-workgroup waits:
-    // nothing to fall back from
-    if (ctx->batch.family == 2) rc = fetch_device_error(ctx);
+    // the launches' tangent sweeps raise no device error: nothing to ask (and no synchronisation beyond the copy-out's); the
+    // on-chip wide sweeps do, but have no cross-workgroup waits: nothing to fall back from
+    if (ctx->batch.family == 2) rc = device_verdict(ctx, THE_RECORD);
     else if (ctx->batch.family == 1) {
         bool rerun = false;
         rc = settle(ctx, &rerun);
-        if (rerun) {
-            rc = run_primal(ctx, nullptr);       // re-record the primal at the current x with the launches
-            if (rc) return rc;
-            rc = fetch_device_error(ctx);
-            if (rc) return rc;
-            rc = enqueue_jvp(ctx, dxhh, hipMemcpyHostToDevice, N, nullptr);
+        if (rerun) {                             // this entry's extra step: re-record the primal at the current x with the launches
+            rc = run_primal(ctx, nullptr);
+            if (!rc) rc = device_verdict(ctx, THE_RECORD);
+            if (!rc) rc = enqueue_jvp(ctx, dxhh, hipMemcpyHostToDevice, N, nullptr);
         }
     }
     if (rc) return rc;
@@ -1819,9 +1846,8 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
         return rc ? rc : hank_jvp(ctx, dxhh, N, dagg_out);
     }
     note_primal_x(ctx, nullptr);
-    bool enqueued = false;
-    rc = run_settled(ctx, [&] { const int e = enqueue_primal_jvp(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr); enqueued = e == HANK_OK; return e; });
-    if (rc) { if (enqueued) batch_none(ctx); return rc; }      // (the device's verdict: the partials of a primal that failed are nobody's)
+    rc = run_settled(ctx, [&] { return enqueue_primal_jvp(ctx, xhh, dxhh, hipMemcpyHostToDevice, N, nullptr, nullptr); });
+    if (rc) return rc;      // (a verdict against the record has left no batch current: the partials of a primal that failed are nobody's)
     HIPC(ctx, copy_agg(ctx, agg_out, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(ctx, copy_dagg(ctx, dagg_out, ctx->batch.dagg_cm, N, hipMemcpyDeviceToHost));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
@@ -1925,7 +1951,7 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
     HIPC(ctx, hipMemcpyAsync(hD.data(), ctx->fn.Dv, sizeof(double) * hD.size(), hipMemcpyDeviceToHost, s));
     if (n_het) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
-    rc = fetch_device_error(ctx);
+    rc = device_verdict(ctx, THE_RECORD);
     if (rc) return rc;
     // column n' = t*N + k of the device arrays is lag j = P-1-t of input k; the same-period effect d_{o,k} lands at lag 0
     for (int o = 0; o < nh; o++)
@@ -2321,7 +2347,7 @@ static int granular_backward(hank_ctx *ctx, const double *value_next, const doub
     if (!ctx || !value_next || !xhh_t || !value_out || !policy_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     if (N > 0 && (!dvalue_next || !dxhh_t || !dvalue_out || !dpolicy_out)) return fail(ctx, HANK_ERR_BAD_ARG, "null tangent pointer");
     ENTER(ctx);
-    { const bool pd = ctx->primal_done; const int pend = fetch_device_error(ctx); if (pend) return pend; ctx->primal_done = pd; }   // an error a preceding async sweep left is reported, not overwritten
+    { const int pend = device_verdict(ctx, THE_RECORD); if (pend) return pend; }      // an error a preceding async sweep left is reported, not overwritten: it is the record's
     const Consts &c = ctx->c;
     const size_t G = c.G;
     hipStream_t s = ctx->stream;
@@ -2334,14 +2360,12 @@ static int granular_backward(hank_ctx *ctx, const double *value_next, const doub
     if (!(1.0 + xhh_t[0] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive");
     HIPC(ctx, hipMemcpyAsync(Vin, value_next, sizeof(double) * G, hipMemcpyHostToDevice, s));
     HIPC(ctx, hipMemcpyAsync(xt, xhh_t, sizeof(double) * c.n_hh, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);
+    zero_err(ctx, s);
     const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
     hipLaunchKernelGGL(k_egm_X, grd, blk, primal_lds(c), s, c, Vin, xt, sK, kc, ctx->d_err, 0, (const int *)nullptr);
     hipLaunchKernelGGL(k_egm_Y, grd, blk, 0, s, c, sK, xhh_t[0], xhh_t[1], c.n_hh > 2 ? xhh_t[2] : 0.0, pol, ib, A, B, u, v, Vout, ctx->d_err, 0, (const int *)nullptr);
     HIPC(ctx, hipGetLastError());
-    const bool was_done = ctx->primal_done;
-    int rc = fetch_device_error(ctx);
-    ctx->primal_done = was_done;
+    const int rc = device_verdict(ctx, THIS_CALL);      // the step's own error: the record and the batch stay as they were
     if (rc) return rc;
     HIPC(ctx, hipMemcpyAsync(value_out, Vout, sizeof(double) * G, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipMemcpyAsync(policy_out, pol, sizeof(double) * G, hipMemcpyDeviceToHost, s));
@@ -2521,41 +2545,15 @@ int hank_backward_step_dual(hank_ctx *ctx, const double *value_next, const doubl
 }
 }  // extern "C"
 
-// the device's error word after a synchronisation, cleared when set (reported once: the next call starts clean)
-static int take_device_error(hank_ctx *ctx, int e[4]) {
-    HIPC(ctx, hipMemcpy(e, ctx->d_err, 4 * sizeof(int), hipMemcpyDeviceToHost));
-    if (e[0] != 0) HIPC(ctx, hipMemsetAsync(ctx->d_err, 0, 4 * sizeof(int), ctx->stream));
-    return HANK_OK;
-}
-
-// the device's verdict on steps of the value iteration / of the power method (step: the caller's count of the step that raised it)
-static int vfi_device_error(hank_ctx *ctx, int step) {
-    int e[4];
-    const int rc = take_device_error(ctx, e);
-    if (rc) return rc;
-    if (e[0] == ERR_KNOTS)
-        return fail(ctx, HANK_ERR_KNOTS, "knot-vectors must be unique and sorted in increasing order (steady-state value iteration, step %d, "
-                    "productivity state %d, wealth index %d)", step, e[2] + 1, e[3] + 1);
-    if (e[0] == ERR_DOMAIN)
-        return fail(ctx, HANK_ERR_DOMAIN, "DomainError: negative base under a non-integer power (steady-state value iteration, step %d)", step);
-    return HANK_OK;
-}
-static int stat_device_error(hank_ctx *ctx) {
-    int e[4];
-    const int rc = take_device_error(ctx, e);
-    if (rc) return rc;
-    if (e[0] == ERR_NONMONO) return fail(ctx, HANK_ERR_NONMONOTONE, "savings policy is not monotone in wealth (productivity state %d, wealth index %d)", e[2] + 1, e[3] + 1);
-    return HANK_OK;
-}
-
 static void x_launch_vfi(XSection &sec, const XWork &X, const Consts &c, const XVfiArgs &a) { const size_t lds = x_lds_vfi(c); x_by_maxt(X, [&](auto mt) { XL(k_xvfi<decltype(mt)::value>); }); }
 static void x_launch_stat(XSection &sec, const XWork &X, const Consts &c, const XStatArgs &a) { const size_t lds = x_lds_stat(c); x_by_maxt(X, [&](auto mt) { XL(k_xstat<decltype(mt)::value>); }); }
 #undef XL
-// A steady-state fixed point as ONE persistent launch on the group of XCD 0 (`launch` enqueues it on sync block 0), through to the
-// fallback decision. HANK_OK with *ran: the group formed and xs holds the kernel's {steps, converged} (d_state); HANK_OK without: it
-// did not (or a wait timed out), the context has moved to the launches and d_state is zeroed for them. A forced schedule fails loudly.
+// A steady-state fixed point (in: IN_VFI | IN_POWER_METHOD) as ONE persistent launch on the group of XCD 0 (`launch` enqueues it on sync
+// block 0), through to the verdict on this call's work. HANK_OK with *ran: the group formed, xs holds the kernel's {steps, converged}
+// (d_state) and the error word was clean; HANK_OK without: it did not (or a wait timed out), the context has moved to the launches,
+// d_state is zeroed for them and the word, taken here, held nothing. A forced schedule fails loudly.
 template <typename Launch>
-static int x_fixed_point(hank_ctx *ctx, const char *what, int *d_state, int xs[2], bool *ran, Launch launch) {
+static int x_fixed_point(hank_ctx *ctx, ErrIn in, int *d_state, int xs[2], bool *ran, Launch launch) {
     hipStream_t s = ctx->stream;
     int rc = x_setup(ctx);
     XWork &X = ctx->xw;
@@ -2570,16 +2568,20 @@ static int x_fixed_point(hank_ctx *ctx, const char *what, int *d_state, int xs[2
     XSync hsy;
     HIPC(ctx, hipMemcpyAsync(xs, d_state, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipMemcpyAsync(&hsy, X.sync, sizeof(XSync), hipMemcpyDeviceToHost, s));
-    HIPC(ctx, hipStreamSynchronize(s));
-    X.last_passes = 0;       // (this sync block has been checked here)
-    *ran = hsy.status[0] == 0;
-    if (*ran) return HANK_OK;
-    if (!x_fallback_allowed(ctx))
-        return fail(ctx, HANK_ERR_SWEEP, "persistent %s: %s on XCD %u", what, hsy.status[0] == XERR_PLACEMENT ? "the group is short of members" : "a wait timed out", hsy.status[1]);
-    rc = to_launch_schedule(ctx);
+    int e[4] = {0, 0, 0, 0};
+    rc = take_error_word(ctx, e);
     if (rc) return rc;
-    HIPC(ctx, hipMemsetAsync(d_state, 0, 2 * sizeof(int), s));
-    return HANK_OK;
+    rc = x_status(ctx, in == IN_VFI ? "value iteration" : "power method", &hsy);
+    X.last_blocks = 0;       // (this sync block has been judged here: a later call does not report it again)
+    *ran = rc == HANK_OK;
+    if (!*ran) {
+        bool moved = false;
+        rc = fallback_decision(ctx, rc, &moved);
+        if (!moved) return rc;
+        HIPC(ctx, hipMemsetAsync(d_state, 0, 2 * sizeof(int), s));
+    }
+    // ran or not: the word also speaks for the kernels in FRONT of the launch (the power method's lottery), which the launches do not run again
+    return word_verdict(ctx, THIS_CALL, e, in, xs[0]);
 }
 
 // ---- steady state: the inner fixed point of get_xVals on the device (SteadyState.jl:132-141) ------------------
@@ -2588,7 +2590,7 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
     if (!ctx || !xhh_t || !value_io || !policy_out || max_iter < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument");
     if (!(1.0 + xhh_t[0] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive");
     ENTER(ctx);
-    { const bool pd = ctx->primal_done; const int pend = fetch_device_error(ctx); if (pend) return pend; ctx->primal_done = pd; }
+    { const int pend = device_verdict(ctx, THE_RECORD); if (pend) return pend; }      // (what an earlier async sweep left pending)
     const Consts &c = ctx->c;
     const size_t G = c.G;
     hipStream_t s = ctx->stream;
@@ -2603,7 +2605,7 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
     HIPC(ctx, hipMemcpyAsync(V[0], value_io, sizeof(double) * G, hipMemcpyHostToDevice, s));
     HIPC(ctx, hipMemcpyAsync(xt, xhh_t, sizeof(double) * c.n_hh, hipMemcpyHostToDevice, s));
     HIPC(ctx, hipMemsetAsync(state, 0, 2 * sizeof(int), s));
-    hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);
+    zero_err(ctx, s);
     const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
     const double r = xhh_t[0], w = xhh_t[1], tr = c.n_hh > 2 ? xhh_t[2] : 0.0;
     int hstate[2] = {0, 0};
@@ -2624,18 +2626,14 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
         // the whole iteration as ONE persistent launch on the group of XCD 0 (k_xvfi): the vote on convergence rides on the group barrier
         int xs[2] = {0, 0};      // {steps, converged}
         bool ran = false;
-        int rc = x_fixed_point(ctx, "value iteration", state, xs, &ran, [&](XSection &sec, const XWork &X) {
+        const int rc = x_fixed_point(ctx, IN_VFI, state, xs, &ran, [&](XSection &sec, const XWork &X) {
             XVfiArgs va{};
             va.c = c; va.V0 = V[0]; va.r = r; va.w = w; va.tr = tr; va.tol = tol; va.max_iter = max_iter; va.sy = X.sync; va.st_s = X.st_s;
             va.err = ctx->d_err; va.Vout = V[1]; va.pol = pol; va.iters = state; va.supnorm = norm;
             x_launch_vfi(sec, X, c, va);
         });
         if (rc) return rc;
-        if (ran) {
-            rc = vfi_device_error(ctx, xs[0]);
-            return rc ? rc : finish(V[1], xs[0]);
-        }
-        hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);      // the context continues on the launches
+        if (ran) return finish(V[1], xs[0]);
     }
     int done = 0;                      // steps enqueued
     const int chunk = 64;              // the stop flag travels to the host once per chunk; converged steps freeze the state
@@ -2650,8 +2648,9 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
         done += n;
         HIPC(ctx, hipGetLastError());
         HIPC(ctx, hipMemcpyAsync(hstate, state, sizeof(hstate), hipMemcpyDeviceToHost, s));
-        HIPC(ctx, hipStreamSynchronize(s));
-        { const int erc = vfi_device_error(ctx, hstate[1] + 1); if (erc) return erc; }
+        int e[4], erc = take_error_word(ctx, e);      // (the chunk's synchronisation)
+        if (!erc) erc = word_verdict(ctx, THIS_CALL, e, IN_VFI, hstate[1] + 1);
+        if (erc) return erc;
     }
     return finish(V[hstate[1] & 1], hstate[1]);     // step k reads V[(k-1)&1] and writes V[k&1]
 }
@@ -2665,7 +2664,7 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
                                     int32_t *iters_out) {
     if (!ctx || !policy || !D_io || max_iter < 1 || check_every < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument");
     ENTER(ctx);
-    { const bool pd = ctx->primal_done; const int pend = fetch_device_error(ctx); if (pend) return pend; ctx->primal_done = pd; }
+    { const int pend = device_verdict(ctx, THE_RECORD); if (pend) return pend; }      // (what an earlier async sweep left pending)
     const Consts &c = ctx->c;
     const size_t G = c.G;
     hipStream_t s = ctx->stream;
@@ -2683,7 +2682,7 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
     HIPC(ctx, hipMemcpyAsync(D[0], D_io, sizeof(double) * G, hipMemcpyHostToDevice, s));
     HIPC(ctx, hipMemcpyAsync(Dchk, D_io, sizeof(double) * G, hipMemcpyHostToDevice, s));
     HIPC(ctx, hipMemsetAsync(state, 0, 2 * sizeof(int), s));
-    hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4);
+    zero_err(ctx, s);
     hipLaunchKernelGGL(k_lottery, dim3((unsigned)c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, R, c.n_e, ctx->d_err, 1, 0);
     HIPC(ctx, hipGetLastError());
     const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
@@ -2693,7 +2692,7 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         // the whole power method as ONE persistent launch on the group of XCD 0 (k_xstat)
         int xs[2] = {0, 0};
         bool ran = false;
-        int rc = x_fixed_point(ctx, "power method", state, xs, &ran, [&](XSection &sec, const XWork &X) {
+        const int rc = x_fixed_point(ctx, IN_POWER_METHOD, state, xs, &ran, [&](XSection &sec, const XWork &X) {
             XStatArgs sa{};
             sa.c = c; sa.R = R; sa.D0 = D[0]; sa.tol = tol; sa.max_iter = max_iter; sa.check_every = check_every; sa.sy = X.sync;
             sa.st_D = X.st_D; sa.Dout = D[1]; sa.iters = state;
@@ -2701,8 +2700,6 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         });
         if (rc) return rc;
         if (ran) {
-            rc = stat_device_error(ctx);
-            if (rc) return rc;
             HIPC(ctx, hipMemcpyAsync(D_io, D[1], sizeof(double) * G, hipMemcpyDeviceToHost, s));
             HIPC(ctx, hipStreamSynchronize(s));
             if (iters_out) *iters_out = xs[0];
@@ -2723,7 +2720,9 @@ extern "C" int hank_stationary_dist(hank_ctx *ctx, const double *policy, double 
         HIPC(ctx, hipMemcpyAsync(hstate, state, sizeof(hstate), hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));
     }
-    { const int erc = stat_device_error(ctx); if (erc) return erc; }
+    int e[4], erc = take_error_word(ctx, e);
+    if (!erc) erc = word_verdict(ctx, THIS_CALL, e, IN_POWER_METHOD);
+    if (erc) return erc;
     // once converged the iteration kernels stop touching the buffers: Dchk holds the last checked iterate
     HIPC(ctx, hipMemcpyAsync(D_io, Dchk, sizeof(double) * G, hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
@@ -2736,6 +2735,7 @@ static int granular_forward(hank_ctx *ctx, const double *policy, const double *d
                             const double *dD_prev, int N, double *D_out, double *dD_out, double *agg_out, double *dagg_out) {
     if (!ctx || !policy || !D_prev || !D_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     if (N > 0 && (!dpolicy || !dD_prev || !dD_out)) return fail(ctx, HANK_ERR_BAD_ARG, "null tangent pointer");
+    ENTER(ctx);
     const Consts &c = ctx->c;
     const size_t G = c.G, W = 1 + (size_t)N;
     hipStream_t s = ctx->stream;
