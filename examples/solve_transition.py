@@ -80,6 +80,48 @@ def gradient(n_a=500, n_e=4, T=300, shock=0.01, chunk=256):
             "max_abs_difference_over_max": float(np.max(np.abs(g_rev - g_fwd)) / np.max(np.abs(g_fwd)))}
 
 
+def boundary_gradient(n_a=500, n_e=4, T=300, shock=0.01, seed=0):
+    """The gradient of the merit function ½‖F(x)‖² with respect to the BOUNDARY (V_T, D_0) — the terminal marginal value
+    `ss_end.value` (BackwardIteration.jl:85) and the initial distribution `ss_initial.D` (ForwardIteration.jl:293) — at the Newton
+    starting point, from ONE hank_vjp_boundary: F reaches the boundary through the household aggregates alone, so the cotangent
+    of the aggregates is the residual layer's `∂R/∂agg`ᵀ F. Printed next to its inner product with two random boundary
+    directions (dV, dD) taken forward through hank_jvp_boundary: ⟨∇_V, dV⟩ + ⟨∇_D, dD⟩ = ⟨F, ∂R/∂agg · J_b (dV, dD)⟩."""
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    from conftest import ks_setup
+    m, ss, _ = ks_setup(n_a, n_e, T)
+    P = T - 1
+    Z = 1.0 + shock * 0.8 ** np.arange(1, P + 1)
+    x0 = np.tile(np.array([ss.vars[k] for k in ("Y", "KS", "r", "w")]), P)
+    lin = h.LinearizedFunction(x0, {"Z": Z}, m, ss, ss)
+    if lin._n_out > 2:
+        raise NotImplementedError("boundary derivatives cover the policy variable and consumption only")
+    lin._linearise_residuals()
+    hb, n_out = lin.hb, lin._n_out
+    ab = np.asarray(lin._Ragg.T @ lin.Fx).reshape(len(lin.het), P)              # rows: het variable, period
+    agg_bar = np.zeros((P, n_out, 1))
+    for j, o in enumerate(lin._out_idx):
+        agg_bar[:, o, 0] += ab[j]
+    t0 = time.perf_counter()
+    _, g_V, g_D = hb.vjp_boundary(agg_bar, n_out)
+    t_rev = time.perf_counter() - t0
+    rng = np.random.default_rng(seed)
+    dV = rng.standard_normal((hb.n_a, hb.n_e, 2)) * np.abs(np.asarray(ss.value))[:, :, None]
+    dD = rng.standard_normal((hb.n_a, hb.n_e, 2)) / hb.G
+    t0 = time.perf_counter()
+    dagg = hb.jvp_boundary(None, dV, dD)                                        # (P, 2)
+    daggs = dagg[:, None, :] if n_out == 1 else hb.het_outputs(n_out, np.zeros((hb.n_hh, P, 2)))[1]
+    t_fwd = time.perf_counter() - t0
+    dF = lin._Ragg @ np.concatenate([daggs[:, o, :] for o in lin._out_idx], axis=0)
+    fwd = lin.Fx @ dF
+    rev = np.einsum("ae,aen->n", g_V[:, :, 0], dV) + np.einsum("ae,aen->n", g_D[:, :, 0], dD)
+    return {"grid": f"{n_a}x{n_e}", "T": T, "merit": 0.5 * float(lin.Fx @ lin.Fx), "boundary_unknowns": 2 * hb.G,
+            "gradient_norm_value_end": float(np.linalg.norm(g_V)), "gradient_norm_D_init": float(np.linalg.norm(g_D)),
+            "reverse_s": round(t_rev, 5), "reverse_vjps": 1, "forward_s": round(t_fwd, 5),
+            "directional_derivatives_reverse": [float(v) for v in rev], "directional_derivatives_forward": [float(v) for v in fwd],
+            "max_abs_difference_over_max": float(np.max(np.abs(rev - fwd)) / np.max(np.abs(fwd)))}
+
+
 def solve_permanent(n_a=200, n_e=3, T=150, Z_end=1.03, eps=1e-9, verbose=False):
     """The two-steady-state scenario of the reference YAML (`ending:` block, KrusellSmith.yaml:109-116): TFP moves
     to Z_end for good in period 1. The path starts from the initial steady state (KS_0, D_0 = ss_initial), the terminal
@@ -119,6 +161,7 @@ if __name__ == "__main__":
     ap.add_argument("--inner", default="fixed_point", choices=["fixed_point", "krylov"], help="y-iteration: the reference's damped fixed point or GMRES on J(x) preconditioned by the steady-state Jacobian")
     ap.add_argument("--jacobian", default="toeplitz", choices=["toeplitz", "columns"])
     ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one hank_vjp against n_hh·P JVP columns")
+    ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one hank_vjp_boundary, checked against two hank_jvp_boundary directions")
     a = ap.parse_args()
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -128,7 +171,9 @@ if __name__ == "__main__":
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", torch.cuda.current_device()))
-    if a.gradient:
+    if a.boundary_gradient:
+        out = boundary_gradient(a.n_a, a.n_e, a.T, a.shock)
+    elif a.gradient:
         out = gradient(a.n_a, a.n_e, a.T, a.shock)
     elif a.permanent is not None:
         out = solve_permanent(a.n_a, a.n_e, a.T, a.permanent, verbose=a.verbose)[0]

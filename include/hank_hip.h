@@ -300,6 +300,37 @@ int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int3
  * a new boundary makes it HANK_ERR_NOT_READY until the next hank_vjp (never the cotangents of an older primal). */
 int hank_get_policy_cotangent_seq(hank_ctx *ctx, int32_t M, double *out);
 
+/* ---- tangents and cotangents on the boundary ------------------------------------------------------
+ * The household block is a map (x, V_P, D_0) -> aggregates; the entries above differentiate it in x alone and hold the boundary
+ * of hank_set_boundary constant. These two carry the terminal marginal value `ss_end.value` (BackwardIteration.jl:85) and the
+ * initial distribution `ss_initial.D` (ForwardIteration.jl:293) as well: what a gradient with respect to a parameter that moves
+ * the ending steady state, a sensitivity to the initial wealth distribution, or the seam between two time segments of a long
+ * horizon needs in place of 2 G finite-difference primal sweeps. Outputs 0 and 1 (the policy variable, consumption) only.
+ *
+ * hank_jvp_boundary == the partials of ForwardIteration(BackwardIteration(x, ...)) under Duals seeded in xVals AND in
+ * ss_end.value (BackwardIteration.jl:85) AND in ss_initial.D (ForwardIteration.jl:293), N directions at once:
+ *   dxhh (n_hh, P, N) as in hank_jvp; dvalue_end, dD_init (G, N) column-major, pt = e n_a + a (the convention of
+ *   hank_get_dpolicy_seq); any of the three may be NULL, meaning zeros; all three NULL is HANK_ERR_BAD_ARG.
+ *   dagg_out (P, N) as in hank_jvp.
+ * It always runs on the per-period launches, whatever HANK_SCHEDULE says and whichever kernel family wrote the record, and does
+ * not change the context's schedule; hank_last_timings reports it in the tangent slots. It needs a valid record
+ * (HANK_ERR_NOT_READY otherwise) and makes its batch the current one: hank_get_dpolicy_seq and hank_get_grid_aggregates serve it
+ * as any other, hank_get_het_outputs with n_het <= 2 — consumption then includes the seed's productivity marginal,
+ * w_t sum_e z_e m_t[e] + tr_t sum_e m_t[e] with m_{-1}[e] = sum_a dD_0[a, e], m_t = m_{t-1} Pi. With n_het > 2 and tangents it
+ * answers HANK_ERR_NOT_READY at such a batch (Value and UCE under boundary seeds are not implemented); a later hank_jvp makes
+ * them servable again. With zero seeds the results are hank_jvp's under HANK_SCHEDULE=launch bit for bit. */
+int hank_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_end, const double *dD_init, int32_t N, double *dagg_out);
+int hank_jvp_boundary_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dvalue_end, const double *d_dD_init, int32_t N, double *d_dagg_out);
+/* hank_vjp_boundary == hank_vjp (n_het = 1 or 2, its arguments and its refusals) with the two cotangents its sweeps hold and
+ * drop — the reverse rules of ForwardIteration.jl:339-420 and :131-192 carried through to ss_initial.D (ForwardIteration.jl:293),
+ * and the transpose of the backward loop carried through to ss_end.value (BackwardIteration.jl:85):
+ *   value_end_bar, D_init_bar (G, M) column-major like dvalue_end / dD_init; either may be NULL (not wanted).
+ *   xhh_bar equals hank_vjp's bit for bit. The exact transpose of hank_jvp_boundary with hank_get_het_outputs(n_het <= 2).
+ * Everything else as hank_vjp: the record it needs, what it leaves alone (the tangent batch stays current),
+ * hank_get_policy_cotangent_seq, hank_last_vjp_timings (the exports are timed with Sweep B), the _dev form. */
+int hank_vjp_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar);
+int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------------------
  * Device time, in milliseconds, of the sweeps of the most recent hank_primal[_dev]/hank_jvp[_dev],
  * from HIP events recorded on the context's stream around each sweep:

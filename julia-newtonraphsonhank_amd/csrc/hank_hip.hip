@@ -9,6 +9,7 @@
 #include "hank_wide.h"
 #include "hank_hetx.h"
 #include "hank_adjoint.h"
+#include "hank_boundary.h"
 #include "../../include/hank_hip.h"
 
 #include <cstdarg>
@@ -86,6 +87,10 @@ struct TanWork {
     int nbx = 0, nbxf = 0;
     GraphExec g_back, g_fwd;
     GraphExec g_fback, g_ffwd;   // dual-sweep graphs (primal + tangents in one chain)
+    // hank_jvp_boundary (hank_boundary.h), allocated and captured on its first use at this width: the caller's seeds (G, N)
+    // column-major, m_{-1} [N][n_e], {zm, om} [2][P][N], and the tangent-only sweeps with the two seeds in them
+    DevBuf<double> bnd_dV, bnd_dD, bnd_m0, bnd_zm;
+    GraphExec g_bback, g_bfwd;
     int VB = 1, VF = 1, RGB = 1, RGF = 1;   // lane widths and row groups the graphs are captured with
     unsigned nbf = 0;
 };
@@ -149,6 +154,7 @@ struct CotWork {
     DevBuf<double> xbar;            // (n_hh, P, M) column-major
     GraphExec g_A, g_B;
     GraphExec g_AX[2];              // Sweep A with NX = 1, 2 extra outputs (hank_vjp_het), captured on first use; Sweep B is g_B
+    DevBuf<double> bnd_vbar, bnd_dbar;          // (G, M) column-major the boundary's cotangents (hank_vjp_boundary), allocated on its first use at this width
 };
 // The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
 struct CotBatch {
@@ -173,6 +179,8 @@ struct TanBatch {
     const void *ws = nullptr;       // view: the cache entry that holds it (its eviction makes nothing current)
     const double *dagg_cm = nullptr, *dpol = nullptr;     // views: the family's (P, 2 N) tangents of the aggregates and its policy partials
     const std::vector<XPass> *passes = nullptr;           // persistent family: how dpol is laid out
+    bool boundary = false;          // the batch carries boundary seeds (hank_jvp_boundary): its dD_0 is not zero, so only outputs 0 and 1 are served
+    const double *bnd_zm = nullptr; // view: {zm, om} [2][P][N] of its dD_0 seed (k_bnd_mpath), or nullptr without one
 };
 
 // The timed sweeps of hank_last_timings (the first six, in its slot order) and hank_last_vjp_timings (the last two). A span is a
@@ -259,6 +267,7 @@ struct hank_ctx {
     CotBatch cot;                  // the current cotangent batch (hank_get_policy_cotangent_seq)
     DevBuf<int> d_adj_sb;          // [P][n_e][n_a + 1] Sweep B's bracket segment starts (k_adj_seg), valid for the recorded primal or not
     bool adj_seg_valid = false;
+    DevBuf<double> d_bnd_q;        // [2][P][n_e]: Pi^{t+1} z and Pi^{t+1} 1 (hank_jvp_boundary: ensure_bnd_q), the model's; allocated once (the graphs hold its address)
     HxRecord hx;                   // the extra outputs' share of the record (ensure_hx_record), valid for the recorded primal or not
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
     long long stats[N_STATS] = {};   // see Stat and hank_stats
@@ -287,6 +296,12 @@ static void cot_none(hank_ctx *ctx) { ctx->cot = CotBatch(); }
 static void cot_ran(hank_ctx *ctx, const void *ws, int M, const double *pbar) { ctx->cot = CotBatch{true, M, ws, pbar}; }
 static void batch_ran(hank_ctx *ctx, int family, const void *ws, int N, const double *dagg_cm, const double *dpol, const std::vector<XPass> *passes = nullptr) {
     ctx->batch = TanBatch{family, true, N, ws, dagg_cm, dpol, passes};
+}
+// the same for a batch of hank_jvp_boundary (always the launch family): zm as TanBatch::bnd_zm
+static void batch_ran_boundary(hank_ctx *ctx, const void *ws, int N, const double *dagg_cm, const double *dpol, const double *zm) {
+    batch_ran(ctx, 0, ws, N, dagg_cm, dpol);
+    ctx->batch.boundary = true;
+    ctx->batch.bnd_zm = zm;
 }
 // every reader's question: is a batch of N directions current?
 static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
@@ -446,7 +461,8 @@ static int build_primal_graphs(hank_ctx *ctx) {
     } while (0)
 
 // captures ONE pair of tangent graphs, on first use: which = 0 the tangent-only sweeps (hank_jvp), 1 the dual-sweep
-// launches (hank_primal_jvp)
+// launches (hank_primal_jvp), 2 the tangent-only sweeps with the boundary's seeds (hank_jvp_boundary, hank_boundary.h: the same
+// launches of the same kernels, the seed kernels between them)
 template <typename VT, typename VF>
 static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     const int RGB = w.RGB, RGF = w.RGF;
@@ -466,22 +482,33 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     VF *dpolf = reinterpret_cast<VF *>(w.dpol.get()), *aggpart = reinterpret_cast<VF *>(w.aggpart.get());
     const unsigned nbt = (w.nbx + RGB - 1) / RGB;
     int rc = HANK_OK, cur = 0;
-    if (which == 0) {
+    const bool bnd = which == 2;
+    const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e);      // the layout kernels
+    if (which != 1) {
     // backward tangent sweep
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
     LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, (int)P - 1, 1,
                        ds[1], ds[0], dpol);
+    if (bnd) {      // dV_P (BackwardIteration.jl:85) into the knots' tangent of period P-1; ds[1] is free until the next launch writes it
+        hipLaunchKernelGGL(k_bnd_in, tgrd, tblk, 0, s, w.bnd_dV.get(), c.n_a, c.n_e, c.n_a, N, w.ds[1].get());
+        hipLaunchKernelGGL(k_bnd_seed_back, dim3((unsigned)(((size_t)c.n_a * N + 255) / 256)), dim3(256), 0, s, c, ctx->R.kc + (P - 1) * c.G, w.ds[1].get(), (size_t)N, w.ds[0].get());
+    }
     cur = 0;
     for (int t = (int)P - 1; t >= 0; t--) {
         LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, t, 0,
                            ds[cur], ds[cur ^ 1], dpol);
         cur ^= 1;
     }
-    rc = end_capture(ctx, &w.g_back);
+    rc = end_capture(ctx, bnd ? &w.g_bback : &w.g_back);
     if (rc) return rc;
     // forward tangent sweep
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    if (bnd) {      // dD_0 (ForwardIteration.jl:293) into the real rows of the state, zero virtual rows; its productivity marginal along the path
+        hipLaunchKernelGGL(k_bnd_in, tgrd, tblk, 0, s, w.bnd_dD.get(), c.n_a, c.n_e, c.n_a + KV, N, w.dD[0].get());
+        hipLaunchKernelGGL(k_bnd_marginal, dim3((unsigned)c.n_e, (unsigned)N), dim3(256), 0, s, w.bnd_dD.get(), c.n_a, c.n_e, w.bnd_m0.get());
+        hipLaunchKernelGGL(k_bnd_mpath, dim3((unsigned)((PN + 255) / 256)), dim3(256), 0, s, (int)P, c.n_e, N, w.bnd_m0.get(), ctx->d_bnd_q.get(), w.bnd_zm.get());
+    } else
     hipLaunchKernelGGL(k_zero_f64, dim3(512), dim3(256), 0, s, w.dD[0], GV * N);  // dD_0 = 0 (ForwardIteration.jl:293)
     cur = 0;
     for (int t = 0; t < (int)P; t++) {
@@ -490,7 +517,7 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     }
     hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)nbf, 2 * N, w.dagg);
     hipLaunchKernelGGL(k_tan_out, dim3((2 * PN + 255) / 256), dim3(256), 0, s, w.dagg, (int)P, 2 * N, w.dagg_cm);
-    return end_capture(ctx, &w.g_fwd);
+    return end_capture(ctx, bnd ? &w.g_bfwd : &w.g_fwd);
     }
 
     // ---- dual-sweep graphs: the primal recurrence and the tangent recurrence advance in the SAME
@@ -608,7 +635,7 @@ static int ensure_tanwork(hank_ctx *ctx, int N, TanWork **out) {
 
 // the graph pair of one schedule, captured the first time that schedule runs at this batch width
 static int ensure_graphs(hank_ctx *ctx, TanWork &w, int which) {
-    if (which == 0 ? w.g_back.get() != nullptr : w.g_fback.get() != nullptr) return HANK_OK;
+    if ((which == 0 ? w.g_back : which == 1 ? w.g_fback : w.g_bback).get() != nullptr) return HANK_OK;
     if (w.VB == 2) return w.VF == 2 ? capture_tangent_graphs<double2, double2>(ctx, w, which) : capture_tangent_graphs<double2, double>(ctx, w, which);
     return w.VF == 2 ? capture_tangent_graphs<double, double2>(ctx, w, which) : capture_tangent_graphs<double, double>(ctx, w, which);
 }
@@ -1708,19 +1735,21 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
     return HANK_OK;
 }
 
-static int run_jvp(hank_ctx *ctx, TanWork &w) {
-    int grc = ensure_graphs(ctx, w, 0);
+// bnd: the graphs with the boundary's seeds (hank_jvp_boundary: w.bnd_dV and w.bnd_dD hold them); zm: whether a dD_0 seed is among them
+static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd = false, bool zm = false) {
+    int grc = ensure_graphs(ctx, w, bnd ? 2 : 0);
     if (grc) return grc;
     HIPC(ctx, ctx->spans.begin(TAN_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(w.g_back, ctx->stream));
-    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, ctx->c.P + 2));
+    HIPC(ctx, hipGraphLaunch(bnd ? w.g_bback : w.g_back, ctx->stream));
+    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, ctx->c.P + (bnd ? 4 : 2)));
     HIPC(ctx, join_side(ctx));      // the tangent forward sweep needs D_t
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
     HIPC(ctx, ctx->spans.begin(TAN_FWD, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(w.g_fwd, ctx->stream));
-    HIPC(ctx, ctx->spans.end(TAN_FWD, ctx->stream, ctx->c.P + 3));
-    batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
+    HIPC(ctx, hipGraphLaunch(bnd ? w.g_bfwd : w.g_fwd, ctx->stream));
+    HIPC(ctx, ctx->spans.end(TAN_FWD, ctx->stream, ctx->c.P + (bnd ? 5 : 3)));
+    if (bnd) batch_ran_boundary(ctx, &w, w.N, w.dagg_cm, w.dpol, zm ? w.bnd_zm.get() : nullptr);
+    else batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
     return HANK_OK;
 }
 
@@ -1766,6 +1795,79 @@ int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
         }
     }
     if (rc) return rc;
+    HIPC(ctx, copy_dagg(ctx, dagg_out, ctx->batch.dagg_cm, N, hipMemcpyDeviceToHost));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
+// hank_jvp_boundary[_dev]: the launch family's tangent sweeps with the boundary's seeds, whatever the context's schedule and
+// whichever family wrote the record (any primal serves any tangent sweep: run_jvp's ensure_seg / ensure_lwg). A null input is a
+// zero seed. The schedule is left as it is.
+// Pi^{t+1} z and Pi^{t+1} 1, t = 0 .. P-1, once per context (k_bnd_mpath dots the seed's productivity marginal with them)
+static int ensure_bnd_q(hank_ctx *ctx) {
+    if (ctx->d_bnd_q) return HANK_OK;
+    const int ne = ctx->c.n_e, P = ctx->c.P;
+    std::vector<double> Q(2 * (size_t)P * ne), q(ctx->h_z), o(ne, 1.0), q2(ne), o2(ne);
+    for (int t = 0; t < P; t++) {
+        for (int e = 0; e < ne; e++) {
+            double a = 0.0, b = 0.0;
+            for (int e2 = 0; e2 < ne; e2++) { a += ctx->h_Pi[e + (size_t)ne * e2] * q[e2]; b += ctx->h_Pi[e + (size_t)ne * e2] * o[e2]; }
+            q2[e] = a; o2[e] = b;
+        }
+        q.swap(q2); o.swap(o2);
+        for (int e = 0; e < ne; e++) { Q[(size_t)t * ne + e] = q[e]; Q[((size_t)P + t) * ne + e] = o[e]; }
+    }
+    DevBuf<double> buf;
+    HIPC(ctx, buf.alloc(Q.size()));
+    HIPC(ctx, hipMemcpy(buf, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice));
+    ctx->d_bnd_q = std::move(buf);
+    return HANK_OK;
+}
+static int enqueue_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_end, const double *dD_init, hipMemcpyKind kind, int N, double *d_dagg_out) {
+    TanWork *w = nullptr;
+    int rc = ensure_tanwork(ctx, N, &w);
+    if (rc) return rc;
+    const size_t P = ctx->c.P, GN = (size_t)ctx->c.G * N;
+    rc = ensure_bnd_q(ctx);
+    if (rc) return rc;
+    if (!w->bnd_zm) {
+        HIPC(ctx, w->bnd_dV.alloc(GN));
+        HIPC(ctx, w->bnd_dD.alloc(GN));
+        HIPC(ctx, w->bnd_m0.alloc((size_t)N * ctx->c.n_e));
+        HIPC(ctx, w->bnd_zm.alloc(2 * P * N));      // (last: a failed allocation is tried again by the next call)
+    }
+    const struct { double *dst; const double *src; size_t count; } in[3] = {{w->dxhh, dxhh, ctx->c.n_hh * P * N}, {w->bnd_dV, dvalue_end, GN}, {w->bnd_dD, dD_init, GN}};
+    for (const auto &a : in) {
+        if (a.src) HIPC(ctx, hipMemcpyAsync(a.dst, a.src, sizeof(double) * a.count, kind, ctx->stream));
+        else HIPC(ctx, hipMemsetAsync(a.dst, 0, sizeof(double) * a.count, ctx->stream));
+    }
+    rc = run_jvp(ctx, *w, true, dD_init != nullptr);
+    if (rc) return rc;
+    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
+    return HANK_OK;
+}
+static int jvp_boundary_args(hank_ctx *ctx, const void *dxhh, const void *dvalue_end, const void *dD_init, int N, const void *out, bool need_out) {
+    if (!ctx || (!dxhh && !dvalue_end && !dD_init) || (need_out && !out) || N < 1)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_boundary: bad argument (N=%d; at least one of dxhh, dvalue_end, dD_init must be given)", N);
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_boundary");
+    return HANK_OK;
+}
+
+int hank_jvp_boundary_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dvalue_end, const double *d_dD_init, int32_t N, double *d_dagg_out) {
+    ENTER(ctx);
+    const int rc = jvp_boundary_args(ctx, d_dxhh, d_dvalue_end, d_dD_init, N, d_dagg_out, false);
+    if (rc) return rc;
+    return enqueue_jvp_boundary(ctx, d_dxhh, d_dvalue_end, d_dD_init, hipMemcpyDeviceToDevice, N, d_dagg_out);
+}
+
+int hank_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_end, const double *dD_init, int32_t N, double *dagg_out) {
+    ENTER(ctx);
+    int rc = jvp_boundary_args(ctx, dxhh, dvalue_end, dD_init, N, dagg_out, true);
+    if (rc) return rc;
+    rc = enqueue_jvp_boundary(ctx, dxhh, dvalue_end, dD_init, hipMemcpyHostToDevice, N, nullptr);
+    if (rc) return rc;
+    // (the launches' tangent sweeps raise no device error: nothing to ask, as in hank_jvp)
     HIPC(ctx, copy_dagg(ctx, dagg_out, ctx->batch.dagg_cm, N, hipMemcpyDeviceToHost));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     ctx->errmsg[0] = 0;
@@ -2224,7 +2326,10 @@ static int ensure_hx_record(hank_ctx *ctx) {
 // hank_vjp[_dev], hank_vjp_het[_dev]: M cotangent columns from the caller (kind: where they live) through the transposed sweeps
 // at the recorded primal, whichever family recorded it. Touches neither the record nor the tangent batch nor the primal memo.
 // n_het > 2: Sweep A's graph with NX = n_het - 2 extra outputs, and their direct terms after Sweep B.
-static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out) {
+// d_vend_bar, d_D0_bar (hank_vjp_boundary; device pointers, (G, M) column-major, either may be null): the cotangents of the terminal
+// value and of the initial distribution, exported from the sweeps' states (hank_boundary.h) — everything else is the same work.
+static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out,
+                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
     const int NX = n_het > 2 ? n_het - 2 : 0;
@@ -2257,8 +2362,17 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     HIPC(ctx, ctx->spans.begin(VJP_A, s));
     HIPC(ctx, hipGraphLaunch(NX > 0 ? w->g_AX[NX - 1] : w->g_A, s));
     HIPC(ctx, ctx->spans.end_begin(VJP_A, (int)P, VJP_B, s));
+    const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((M + BND_T - 1) / BND_T), (unsigned)c.n_e);      // the layout kernel
+    // Sweep A's state after its last launch (t = 0) is the cotangent of D_0; Sweep B's first launches overwrite it
+    if (d_D0_bar) hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_D0_bar);
     HIPC(ctx, hipGraphLaunch(w->g_B, s));
-    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1));
+    if (d_vend_bar) {      // Sweep B's last launch (t = P-1) read mu_{P-1} from st[(P-1) & 1] and wrote no state: mu_P goes where it would have
+        hipLaunchKernelGGL(k_bnd_vend, dim3((unsigned)(((size_t)c.n_a * M + 255) / 256)), dim3(256), 0, s, c, ctx->R, (int)P - 1, P == 1 ? 1 : 0, ctx->d_adj_sb.get(),
+                           w->st[(P - 1) & 1].get(), w->pbar.get(), (size_t)M, w->st[P & 1].get());
+        hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_vend_bar);
+    }
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1 + (d_D0_bar ? 1 : 0) + (d_vend_bar ? 2 : 0)));
     if (NX > 0) {
         hipLaunchKernelGGL(k_adj_hx_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, NX, hx_count(ctx), w->ybx.get(),
                            ctx->hx.S.get(), w->xbar.get());
@@ -2301,7 +2415,38 @@ static int vjp(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, co
     return HANK_OK;
 }
 
+// hank_vjp_boundary[_dev]: hank_vjp's path (and its rule for n_het) plus the boundary's cotangents; either may be null (not wanted).
+// The host form stages them in the workspace of this width.
+static int vjp_boundary(hank_ctx *ctx, int n_het, const double *agg_bar, int M, double *xhh_bar, double *value_end_bar, double *D_init_bar, bool dev) {
+    ENTER(ctx);
+    int rc = vjp_args(ctx, n_het, agg_bar, M, xhh_bar);
+    if (rc) return rc;
+    CotWork *w = nullptr;
+    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, value_end_bar, D_init_bar);
+    rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
+    if (rc) return rc;
+    const size_t GM = (size_t)ctx->c.G * M;
+    if (!w->bnd_dbar) {
+        HIPC(ctx, w->bnd_vbar.alloc(GM));
+        HIPC(ctx, w->bnd_dbar.alloc(GM));
+    }
+    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, value_end_bar ? w->bnd_vbar.get() : nullptr, D_init_bar ? w->bnd_dbar.get() : nullptr);
+    if (rc) return rc;
+    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
+    if (value_end_bar) HIPC(ctx, hipMemcpyAsync(value_end_bar, w->bnd_vbar, sizeof(double) * GM, hipMemcpyDeviceToHost, ctx->stream));
+    if (D_init_bar) HIPC(ctx, hipMemcpyAsync(D_init_bar, w->bnd_dbar, sizeof(double) * GM, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
 extern "C" {
+int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar) {
+    return vjp_boundary(ctx, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);
+}
+int hank_vjp_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar) {
+    return vjp_boundary(ctx, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false);
+}
 int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) { return vjp(ctx, vjp_het_args, n_het, d_agg_bar, M, d_xhh_bar, true); }
 int hank_vjp_het(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) { return vjp(ctx, vjp_het_args, n_het, agg_bar, M, xhh_bar, false); }
 int hank_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) { return vjp(ctx, vjp_args, n_het, d_agg_bar, M, d_xhh_bar, true); }
@@ -2400,7 +2545,7 @@ static int granular_backward(hank_ctx *ctx, const double *value_next, const doub
 // of the endogenous dimension (the savings a', KD / A). Output 1 is consumption, the budget residual c = (1+r_t) a + w_t z_e + tr_t
 // - a' (KrusellSmith.jl:80): its aggregate is affine in what the sweeps already reduce,
 //     C_t  = (1+r_t) AD_t + w_t ZD_t + tr_t MD_t - KD_t,      AD_t = sum a D_t (the grid-weighted aggregate), ZD_t = sum z_e D_t, MD_t = sum D_t
-//     dC_t = dr_t AD_t + dw_t ZD_t + dtr_t MD_t + (1+r_t) dAD_t - dKD_t      (ZD_t, MD_t carry no partials: see hank_set_boundary)
+//     dC_t = dr_t AD_t + dw_t ZD_t + dtr_t MD_t + (1+r_t) dAD_t - dKD_t      (ZD_t, MD_t carry no partials: see hank_set_boundary; under a dD_0 seed of hank_jvp_boundary they do, and k_bnd_cons adds them behind this kernel)
 // agg (P, 2) and dagg (P, 2 N) as the sweeps leave them -> out_agg (P, n_het), out_dagg (P, n_het, N) column-major. hxS: the
 // record's sums [t][SX][HX_NS] (SX: the outputs the record holds); hxT: the call's in-period sums [n][t][NX].
 __global__ void k_het_outputs(int P, int n_hh, int n_het, int SX, int N, const double *__restrict__ xhh, const double *__restrict__ dxhh,
@@ -2484,6 +2629,9 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
     if (tan) {
         rc = batch_current(ctx, N, &b);
         if (rc) return rc;
+        if (b->boundary && n_het > 2)
+            return fail(ctx, HANK_ERR_NOT_READY, "hank_get_het_outputs: the current tangent batch carries boundary seeds (hank_jvp_boundary), under which only outputs 0 and 1 "
+                        "have tangents (Value and UCE assume dD_0 = 0): n_het = %d is served again after hank_jvp", n_het);
     }
     HIPC(ctx, join_side(ctx));
     Scratch sc;
@@ -2507,6 +2655,9 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
     }
     hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * (Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, hx_count(ctx), Nk, ctx->d_xhh,
                        d_dx, ctx->d_agg, b ? b->dagg_cm : nullptr, ctx->d_zd, ctx->hx.S.get(), hxT, d_a, tan ? d_da : nullptr);
+    // under a dD_0 seed the productivity marginal of dD_t does not vanish: consumption gains w_t zm_t + tr_t om_t (hank_boundary.h)
+    if (tan && n_het == 2 && b->bnd_zm)
+        hipLaunchKernelGGL(k_bnd_cons, dim3((unsigned)((P * N + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, N, ctx->d_xhh, b->bnd_zm, d_da);
     HIPC(ctx, hipGetLastError());
     if (!dev) {
         if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, d_a, sizeof(double) * P * n_het, hipMemcpyDeviceToHost, ctx->stream));

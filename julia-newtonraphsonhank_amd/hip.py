@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "hank_get_grid_aggregates", "hank_get_grid_aggregates_dev", "hank_backward_step",
     "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
     "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings", "hank_vjp_het", "hank_vjp_het_dev",
+    "hank_jvp_boundary", "hank_jvp_boundary_dev", "hank_vjp_boundary", "hank_vjp_boundary_dev",
 )
 
 
@@ -122,6 +123,10 @@ def load_library() -> C.CDLL:
     lib.hank_vjp_het_dev.argtypes = [vp, i32, vp, i32, vp]
     lib.hank_get_policy_cotangent_seq.argtypes = [vp, i32, dp]
     lib.hank_last_vjp_timings.argtypes = [vp, dp, C.POINTER(i32)]
+    lib.hank_jvp_boundary.argtypes = [vp, dp, dp, dp, i32, dp]
+    lib.hank_jvp_boundary_dev.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.hank_vjp_boundary.argtypes = [vp, i32, dp, i32, dp, dp, dp]
+    lib.hank_vjp_boundary_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
@@ -323,6 +328,68 @@ class HouseholdBlock:
     def vjp_het_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int):
         """device-pointer form (asynchronous on the context's stream)."""
         self._chk(self._lib.hank_vjp_het_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr)))
+
+    # -- tangents and cotangents on the boundary ---------------------------------------------
+    def _boundary_seed(self, seed, N):
+        """a boundary seed (n_a, n_e), (n_a, n_e, N) or (G, N) -> (G, N) column-major, pt = e n_a + a; None stays None"""
+        if seed is None:
+            return None
+        s = np.asarray(seed, dtype=np.float64)
+        if s.shape == (self.n_a, self.n_e):
+            s = s[:, :, None]
+        if s.ndim == 3 and s.shape[:2] == (self.n_a, self.n_e):
+            s = s.reshape((self.G, s.shape[2]), order="F")
+        return _f(s, (self.G, N))
+
+    def jvp_boundary(self, dxhh=None, dvalue_end=None, dD_init=None) -> np.ndarray:
+        """the tangent sweeps with seeds on the boundary as well (hank_jvp_boundary): dxhh (n_hh, P, N) as in `jvp`, dvalue_end
+        and dD_init (n_a, n_e, N) — tangents of `ss_end.value` (BackwardIteration.jl:85) and `ss_initial.D`
+        (ForwardIteration.jl:293); None means zeros, at least one must be given. -> dagg (P, N). Always the launch family. The
+        batch is current afterwards: `dpolicy_seq`, `grid_aggregates`, `het_outputs(2, dxhh)` serve it (pass zeros for a dxhh of
+        None)."""
+        given = [np.asarray(v) for v in (dxhh, dvalue_end, dD_init) if v is not None]
+        if not given:
+            raise ValueError("at least one of dxhh, dvalue_end, dD_init must be given")
+        N = given[0].shape[-1] if given[0].ndim == 3 else 1
+        dx = None
+        if dxhh is not None:
+            dx = np.asarray(dxhh, dtype=np.float64)
+            dx = _f(dx[:, :, None] if dx.ndim == 2 else dx, (self.n_hh, self.P, N))
+        dv, dd = self._boundary_seed(dvalue_end, N), self._boundary_seed(dD_init, N)
+        out = np.empty((self.P, N), order="F")
+        self.calls["jvp"] += 1
+        self._chk(self._lib.hank_jvp_boundary(self._ctx, None if dx is None else _p(dx), None if dv is None else _p(dv),
+                                              None if dd is None else _p(dd), N, _p(out)))
+        return out
+
+    def jvp_boundary_dev(self, d_dxhh_ptr: int, d_dvalue_end_ptr: int, d_dD_init_ptr: int, N: int, d_dagg_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
+        self._chk(self._lib.hank_jvp_boundary_dev(self._ctx, C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dvalue_end_ptr or None),
+                                                  C.c_void_p(d_dD_init_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+
+    def vjp_boundary(self, agg_bar, n_het: int = 1):
+        """`vjp` with the boundary's cotangents (hank_vjp_boundary): -> (xhh_bar (n_hh, P, M), value_end_bar (n_a, n_e, M),
+        D_init_bar (n_a, n_e, M)) — the cotangents of the household inputs, of `ss_end.value` and of `ss_initial.D`; the exact
+        transpose of `jvp_boundary` followed by `het_outputs(n_het)`. agg_bar as in `vjp`; xhh_bar equals `vjp`'s bit for bit."""
+        yb = np.asarray(agg_bar, dtype=np.float64)
+        if yb.ndim == 1:
+            yb = yb[:, None]
+        if yb.ndim == 2:
+            if int(n_het) != 1:
+                raise ValueError("agg_bar must be (P, n_het, M) when n_het > 1")
+            yb = yb[:, None, :]
+        M = yb.shape[2]
+        yb = _f(yb, (self.P, int(n_het), M) if int(n_het) in (1, 2) else None)      # (the library refuses any other n_het)
+        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
+        vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F")
+        db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F")
+        self._chk(self._lib.hank_vjp_boundary(self._ctx, int(n_het), _p(yb), M, _p(out), _p(vb), _p(db)))
+        return out, vb, db
+
+    def vjp_boundary_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_value_end_bar_ptr: int = 0, d_D_init_bar_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); a boundary pointer of 0 is not wanted."""
+        self._chk(self._lib.hank_vjp_boundary_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr),
+                                                  C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
 
     def policy_cotangent_seq(self, M: int) -> np.ndarray:
         """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp / vjp_het (hank_get_policy_cotangent_seq)."""

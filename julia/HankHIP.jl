@@ -312,6 +312,42 @@ function hank_vjp_het!(xhh_bar::Array{Float64,3}, ctx::HankCtx, agg_bar::Array{F
     return xhh_bar
 end
 
+# ---- tangents and cotangents on the boundary (hank_jvp_boundary, hank_vjp_boundary) -----------------------------------------------
+# dagg = the partials of the household block at the recorded primal for N directions seeded in the household inputs AND in
+# `ss_end.value` (BackwardIteration.jl:85) AND in `ss_initial.D` (ForwardIteration.jl:293): dxhh (n_hh, P, N), dvalue_end and
+# dD_init (n_a, n_e, N); `nothing` is a zero seed, at least one must be given. dagg is (P, N). Always the per-period launches.
+# Afterwards hank_get_dpolicy_seq, hank_get_grid_aggregates and hank_get_het_outputs (n_het <= 2) serve this batch.
+function hank_jvp_boundary!(dagg::Matrix{Float64}, ctx::HankCtx; dxhh::Union{Nothing,Array{Float64,3}} = nothing,
+                            dvalue_end::Union{Nothing,Array{Float64,3}} = nothing, dD_init::Union{Nothing,Array{Float64,3}} = nothing)
+    P, N = size(dagg)
+    @assert P == ctx.P && !(dxhh === nothing && dvalue_end === nothing && dD_init === nothing)
+    @assert dxhh === nothing || size(dxhh) == (length(ctx.hh_rows), P, N)
+    @assert all(s -> s === nothing || size(s) == (ctx.n_a, ctx.n_e, N), (dvalue_end, dD_init))
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve dxhh dvalue_end dD_init begin
+        _check(ctx.ptr, ccall((:hank_jvp_boundary, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}),
+                              ctx.ptr, ptr(dxhh), ptr(dvalue_end), ptr(dD_init), Int32(N), dagg))
+    end
+    return dagg
+end
+
+# hank_vjp! with the cotangents of the boundary: value_end_bar and D_init_bar (n_a, n_e, M) receive the cotangents of
+# `ss_end.value` and `ss_initial.D` (the reverse rules of ForwardIteration.jl:131-192, :339-420 carried through to
+# ForwardIteration.jl:293, and the transpose of the backward loop through to BackwardIteration.jl:85); `nothing`: not wanted.
+# n_het = size(agg_bar, 2) is 1 or 2; xhh_bar equals hank_vjp!'s bit for bit. Returns (xhh_bar, value_end_bar, D_init_bar).
+function hank_vjp_boundary!(xhh_bar::Array{Float64,3}, value_end_bar::Union{Nothing,Array{Float64,3}}, D_init_bar::Union{Nothing,Array{Float64,3}},
+                            ctx::HankCtx, agg_bar::Array{Float64,3})
+    P, n_het, M = size(agg_bar)
+    @assert P == ctx.P && size(xhh_bar) == (length(ctx.hh_rows), P, M)
+    @assert all(s -> s === nothing || size(s) == (ctx.n_a, ctx.n_e, M), (value_end_bar, D_init_bar))
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve value_end_bar D_init_bar begin
+        _check(ctx.ptr, ccall((:hank_vjp_boundary, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                              ctx.ptr, Int32(n_het), agg_bar, Int32(M), xhh_bar, ptr(value_end_bar), ptr(D_init_bar)))
+    end
+    return xhh_bar, value_end_bar, D_init_bar
+end
+
 # the cotangent of the policy sequence of the last hank_vjp! / hank_vjp_het!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
 # (ForwardIteration.jl:412-416) for the policy variable when n_het = 1
 function hank_policy_cotangent_seq(ctx::HankCtx, M::Integer)
