@@ -239,70 +239,33 @@ struct YOut {
 // period, so a probe there plus a short gallop replaces the 11 dependent loads of a cold bisection.
 // `sc` is anything indexable that returns the knot s_t[i, e] (a plain pointer; the XCD-local sweep passes a
 // loader that reads the L2-resident state with L1-bypassing loads) — the arithmetic is the same for both.
-template <typename KNOTS>
-__device__ inline YOut egm_Y(const Consts &c, const KNOTS sc, int a, int e, double r, double w, double tr,
-                             int *err, int t, int guess) {
+//
+// The half is SPLIT AT THE BRACKET. In front of "the bracket is i with knots si, sj" there are two ways to get there:
+//   * the search (probe, gallops, bisection) below, which every loader can serve;
+//   * a loader that already holds the knots of the usual cases in registers names the bracket itself, in straight-line code
+//     (YFrontOf<KNOTS>::value, `sc.front()`: XKnots, hank_xsweep.h), and leaves to the search only the lanes it could not
+//     resolve — behind a wave-uniform branch, so a wave whose brackets moved by a knot at most never enters it.
+// Behind the bracket there is ONE tail for both: the interpolation or a flat outcome, then egm_Y_finish. A bracket is unique,
+// so the way it was found does not change a bit of the result. With a plain pointer the `FRONT` conditions are compile-time
+// constants and the function is the search followed by the tail, as it always was.
+enum { Y_INSIDE = 0, Y_BELOW = 1, Y_ABOVE = 2 };      // where the point lies among the knots (flat extrapolation outside)
+struct YFront {
+    int where, i;         // Y_*; the bracket of a point inside the knots (meaningless in a `slow` lane)
+    double si, sj;        // the bracket's knots
+    bool slow;            // an interior point whose bracket is none of the candidates: the search decides
+    bool bad;             // Interpolations' check_gridded fails at this row
+};
+template <typename KNOTS> struct YFrontOf { static constexpr bool value = false; };
+// a loader that brings the column's productivity z_e in a register (`sc.column_z()`), whether or not it has a front
+template <typename KNOTS> struct YColumnZOf { static constexpr bool value = false; };
+constexpr int Y_WAIT_VMCNT0 = 0x0F70;     // s_waitcnt immediate on gfx9: vmcnt(0), expcnt and lgkmcnt left at their maxima (7, 15)
+
+// the tail's second piece: the borrowing constraint on the interpolated (or flat) policy, consumption, marginal value.
+// ZREG: the column's productivity z_e comes in a register (`ze`: YColumnZOf<KNOTS>, see XKnots) instead of from c.z[e]
+template <bool ZREG>
+__device__ __forceinline__ YOut egm_Y_finish(const Consts &c, int a, int e, double r, double w, double tr, int *err, int t,
+                                             double x, double g, double A, double B, int i, double ze) {
     YOut o;
-    const int n = c.n_a;
-    const double x = c.a[a];
-    const double sa = sc[a];
-    // Interpolations' check_gridded: knots must be sorted and unique (values)
-    if (a > 0 ? !(sa > sc[a - 1]) : !(sa == sa)) set_err(err, ERR_KNOTS, t, e, a);
-    const double s0 = sc[0], sN = sc[n - 1];
-    double g, A = 0.0, B = 0.0;
-    int i;
-    if (x < s0) {
-        g = c.a[0];
-        i = 0;
-    } else if (x > sN) {
-        g = c.a[n - 1];
-        i = n - 2;
-    } else {
-        int lo = -1, hi = n;  // sc[lo] <= x < sc[hi]
-        bool have = false;    // vlo/vhi hold sc[lo], sc[hi] (bracket found by the first probe)
-        double vlo = 0.0, vhi = 0.0;
-        if (guess >= 0) {
-            // probe the guessed bracket AND its two neighbours in one round trip (four independent loads): a bracket
-            // that moved by one knot — the common miss — needs no second trip
-            const int p = guess < n - 1 ? guess : n - 2;
-            const int pm = p > 0 ? p - 1 : 0, pp = p + 2 < n ? p + 2 : n - 1;
-            const double sm = sc[pm], sp = sc[p], sp1 = sc[p + 1], sp2 = sc[pp];
-            if (sp <= x && x < sp1) {
-                lo = p; hi = p + 1; have = true; vlo = sp; vhi = sp1;   // the usual case
-            } else if (p + 2 < n && sp1 <= x && x < sp2) {
-                lo = p + 1; hi = p + 2; have = true; vlo = sp1; vhi = sp2;
-            } else if (p > 0 && sm <= x && x < sp) {
-                lo = p - 1; hi = p; have = true; vlo = sm; vhi = sp;
-            } else if (sp1 <= x) {          // gallop up
-                lo = p + 1;
-                for (int step = 1;; step <<= 1) {
-                    const int q = lo + step;
-                    if (q >= n) break;
-                    if (sc[q] <= x) lo = q; else { hi = q; break; }
-                }
-            } else {                         // gallop down
-                hi = p;
-                for (int step = 1;; step <<= 1) {
-                    const int q = hi - step;
-                    if (q < 0) break;
-                    if (sc[q] <= x) { lo = q; break; } else hi = q;
-                }
-            }
-        }
-        while (hi - lo > 1) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (sc[mid] <= x) lo = mid; else hi = mid;
-        }
-        i = lo < 0 ? 0 : (lo > n - 2 ? n - 2 : lo);
-        const double si = have ? vlo : sc[i], sj = have ? vhi : sc[i + 1];
-        const double h = sj - si, rh = fast_rcp(h);      // (one reciprocal serves both quotients)
-        const double f = (x - si) * rh;
-        const double ai = c.a[i], aj = c.a[i + 1];
-        g = (1.0 - f) * ai + f * aj;
-        const double sl = (aj - ai) * rh;
-        A = -sl * (1.0 - f);
-        B = -sl * f;
-    }
     // max(g, borrow_cons), DiffRules rule: partial passes unless (bc > g) | signbit(bc) < signbit(g)
     const double bc = c.bc;
     if ((bc > g) || ((int)signbit(bc) < (int)signbit(g))) {
@@ -311,7 +274,7 @@ __device__ inline YOut egm_Y(const Consts &c, const KNOTS sc, int a, int e, doub
     }
     g = (g > bc) ? g : ((bc > g) ? bc : (signbit(g) ? bc : g));
     const double opr = 1.0 + r;
-    const double cg = (opr * x + (w * c.z[e] + tr)) - g;
+    const double cg = (opr * x + (w * (ZREG ? ze : c.z[e]) + tr)) - g;
     if (pow_domain_error(cg, -c.gamma)) set_err(err, ERR_DOMAIN, t, e, a);
     const double u = pow_crra(cg, -c.gamma);
     o.g = g;
@@ -322,6 +285,96 @@ __device__ inline YOut egm_Y(const Consts &c, const KNOTS sc, int a, int e, doub
     o.v = c.diet ? diet_v(c, u, opr) : opr * ((-c.gamma) * (u / cg));
     o.V = opr * u;
     return o;
+}
+
+template <typename KNOTS>
+__device__ inline YOut egm_Y(const Consts &c, const KNOTS sc, int a, int e, double r, double w, double tr,
+                             int *err, int t, int guess) {
+    constexpr bool FRONT = YFrontOf<KNOTS>::value;
+    const int n = c.n_a;
+    const double x = c.a[a];
+    double s0, sN, si, sj;
+    int where, i;
+    bool slow, slow_wave;                   // (this lane / some lane of this wave) goes through the search
+    if constexpr (FRONT) {
+        const YFront f = sc.front(x, guess);
+        where = f.where; i = f.i; si = f.si; sj = f.sj;
+        slow = f.slow;
+        slow_wave = __any(f.slow || f.bad) != 0;
+        if (slow_wave) {
+            if (f.bad) set_err(err, ERR_KNOTS, t, e, a);
+        }
+    } else {
+        const double sa = sc[a];
+        // Interpolations' check_gridded: knots must be sorted and unique (values)
+        if (a > 0 ? !(sa > sc[a - 1]) : !(sa == sa)) set_err(err, ERR_KNOTS, t, e, a);
+        s0 = sc[0]; sN = sc[n - 1];
+    }
+    double g, A = 0.0, B = 0.0;
+    if (FRONT ? where == Y_BELOW : x < s0) {
+        g = c.a[0];
+        i = 0;
+    } else if (FRONT ? where == Y_ABOVE : x > sN) {
+        g = c.a[n - 1];
+        i = n - 2;
+    } else {
+        if (FRONT ? slow_wave : true) {
+            if (FRONT ? slow : true) {
+                int lo = -1, hi = n;  // sc[lo] <= x < sc[hi]
+                bool have = false;    // vlo/vhi hold sc[lo], sc[hi] (bracket found by the first probe)
+                double vlo = 0.0, vhi = 0.0;
+                if (guess >= 0) {
+                    // probe the guessed bracket AND its two neighbours in one round trip (four independent loads): a bracket
+                    // that moved by one knot — the common miss — needs no second trip
+                    const int p = guess < n - 1 ? guess : n - 2;
+                    const int pm = p > 0 ? p - 1 : 0, pp = p + 2 < n ? p + 2 : n - 1;
+                    const double sm = sc[pm], sp = sc[p], sp1 = sc[p + 1], sp2 = sc[pp];
+                    if (sp <= x && x < sp1) {
+                        lo = p; hi = p + 1; have = true; vlo = sp; vhi = sp1;   // the usual case
+                    } else if (p + 2 < n && sp1 <= x && x < sp2) {
+                        lo = p + 1; hi = p + 2; have = true; vlo = sp1; vhi = sp2;
+                    } else if (p > 0 && sm <= x && x < sp) {
+                        lo = p - 1; hi = p; have = true; vlo = sm; vhi = sp;
+                    } else if (sp1 <= x) {          // gallop up
+                        lo = p + 1;
+                        for (int step = 1;; step <<= 1) {
+                            const int q = lo + step;
+                            if (q >= n) break;
+                            if (sc[q] <= x) lo = q; else { hi = q; break; }
+                        }
+                    } else {                         // gallop down
+                        hi = p;
+                        for (int step = 1;; step <<= 1) {
+                            const int q = hi - step;
+                            if (q < 0) break;
+                            if (sc[q] <= x) { lo = q; break; } else hi = q;
+                        }
+                    }
+                }
+                while (hi - lo > 1) {
+                    const int mid = lo + ((hi - lo) >> 1);
+                    if (sc[mid] <= x) lo = mid; else hi = mid;
+                }
+                i = lo < 0 ? 0 : (lo > n - 2 ? n - 2 : lo);
+                si = have ? vlo : sc[i];
+                sj = have ? vhi : sc[i + 1];
+                // Without this explicit wait the compiler puts an s_waitcnt vmcnt(0) at the join BEHIND the search, where the waves
+                // that skipped it arrive too and then wait for their partials' rows, which nothing in the tail needs (checked in the ISA
+                // of k_xdual_back: with it, the vmcnt(0) sits inside this arm and the skipping waves keep their counted waits).
+                if constexpr (FRONT) __builtin_amdgcn_s_waitcnt(Y_WAIT_VMCNT0);
+            }
+        }
+        // ---- the tail: the bracket is i with knots si <= x < sj
+        const double h = sj - si, rh = fast_rcp(h);      // (one reciprocal serves both quotients)
+        const double f = (x - si) * rh;
+        const double ai = c.a[i], aj = c.a[i + 1];
+        g = (1.0 - f) * ai + f * aj;
+        const double sl = (aj - ai) * rh;
+        A = -sl * (1.0 - f);
+        B = -sl * f;
+    }
+    if constexpr (YColumnZOf<KNOTS>::value) return egm_Y_finish<true>(c, a, e, r, w, tr, err, t, x, g, A, B, i, sc.column_z());
+    else return egm_Y_finish<false>(c, a, e, r, w, tr, err, t, x, g, A, B, i, 0.0);
 }
 
 // block = RBP rows x n_e columns; thread (row, e) with row fastest. dynamic LDS:

@@ -36,6 +36,12 @@
 #ifndef HANK_XFWD_PRECOMBINE
 #define HANK_XFWD_PRECOMBINE 1     // k_xfwd: neighbouring lanes' parts for one tile row in one LDS add (dev knob: 0 = one add per part)
 #endif
+#ifndef HANK_XBACK_FRONT
+#define HANK_XBACK_FRONT 1         // persistent backward sweeps: the bracket of the usual cases by selects on the preloaded knots (dev knob: 0 = always the search)
+#endif
+#ifndef HANK_XBACK_ZREG
+#define HANK_XBACK_ZREG 1          // persistent backward sweeps: egm_Y's z_e from the register the kernel holds (dev knob: 0 = a global load per period)
+#endif
 #include "hank_kernels.h"
 #include <type_traits>
 
@@ -285,8 +291,9 @@ struct XKnots {
     const double *p;
     int a, n, i0, i1, i2, i3;
     double sa, sam1, s0, sN, w0, w1, w2, w3;
-    __device__ __forceinline__ void preload(const double *col, int a_, int n_, int guess) {
-        p = col; a = a_; n = n_;
+    double ze;                  // the column's productivity z_e, from the register the kernel keeps it in for the whole sweep
+    __device__ __forceinline__ void preload(const double *col, int a_, int n_, int guess, double ze_) {
+        p = col; a = a_; n = n_; ze = ze_;
         sa = xld(col + a);
         sam1 = xld(col + (a > 0 ? a - 1 : 0));
         s0 = xld(col);
@@ -299,6 +306,29 @@ struct XKnots {
             w0 = xld(col + i0); w1 = xld(col + i1); w2 = xld(col + i2); w3 = xld(col + i3);
         }
     }
+    // The straight-line front of egm_Y (hank_kernels.h), on the preloaded registers alone — no operator[], no branch: the
+    // sortedness check, the two flat outcomes (they take precedence over the probe), the guessed bracket p (clipped to n - 2
+    // by preload) and its neighbours p + 1 (if p + 2 < n) and p - 1 (if p > 0) as predicates, tried in egm_Y's order, and
+    // the chosen bracket by selects. Without a guess (i1 = -1, the first period) and when no candidate holds the lane is
+    // `slow`: the search finds its bracket, with on-demand loads.
+    __device__ __forceinline__ YFront front(double x, int guess) const {
+        YFront f;
+        f.bad = a > 0 ? !(sa > sam1) : !(sa == sa);
+        const bool below = x < s0, above = !below & (x > sN);
+        const int p = i1;
+        const bool c0 = (w1 <= x) & (x < w2);
+        const bool cp = !c0 & (p + 2 < n) & (w2 <= x) & (x < w3);
+        const bool cm = !c0 & !cp & (p > 0) & (w0 <= x) & (x < w1);
+        f.slow = !below & !above & ((guess < 0) | !(c0 | cp | cm));
+        f.where = below ? Y_BELOW : (above ? Y_ABOVE : Y_INSIDE);
+        f.i = c0 ? p : (cp ? p + 1 : p - 1);
+        f.si = c0 ? w1 : (cp ? w2 : w0);
+        f.sj = c0 ? w2 : (cp ? w3 : w1);
+        return f;
+    }
+    // z_e for egm_Y's tail (YColumnZOf, independent of the front). Read as c.z[e] it is a global load in every period — the
+    // compiler cannot keep it across the sweep's stores — with an s_waitcnt vmcnt(0) in front of the consumption that needs it.
+    __device__ __forceinline__ double column_z() const { return ze; }
     __device__ __forceinline__ double operator[](int i) const {
         if (i == a) return sa;
         if (i == a - 1) return sam1;
@@ -311,6 +341,9 @@ struct XKnots {
         return xld(p + i);
     }
 };
+
+template <> struct YFrontOf<XKnots> { static constexpr bool value = HANK_XBACK_FRONT != 0; };
+template <> struct YColumnZOf<XKnots> { static constexpr bool value = HANK_XBACK_ZREG != 0; };
 
 __device__ __forceinline__ double xwave_sum(double v) {            // butterfly: every lane ends with the same sum, fixed order
 #pragma unroll
@@ -452,7 +485,7 @@ __global__ void __launch_bounds__(MAXT) k_xprimal_back(XBackArgs A) {
             double V = 0.0;
             if (own) {
                 XKnots kn;
-                kn.preload(sS + (size_t)cur * hs + (size_t)e * na, a, na, guess);
+                kn.preload(sS + (size_t)cur * hs + (size_t)e * na, a, na, guess, ze);
                 const YOut o = egm_Y(cl, kn, a, e, xsh[4 * t], xsh[4 * t + 1], xsh[4 * t + 2], A.err, t, guess);
                 guess = o.ib;
                 V = o.V;
@@ -553,7 +586,7 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
             const int cur = (i - 1) & 1;
             if (own) {
                 XKnots kn;
-                kn.preload(sS + (size_t)cur * hs + (size_t)e * na, a, na, guess);
+                kn.preload(sS + (size_t)cur * hs + (size_t)e * na, a, na, guess, ze);
                 const YOut o = egm_Y(cl, kn, a, e, A.r, A.w, A.tr, A.err, 0, guess);
                 guess = o.ib;
                 V = o.V; pol = o.g;
@@ -1075,7 +1108,7 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
             for (int k = 0; k < NSL; k++) tv[k] = 0.0;
             if (own) {
                 XKnots kn;
-                kn.preload(sS + (size_t)cur * hs + gx + (size_t)e * na, a, na, guess);
+                kn.preload(sS + (size_t)cur * hs + gx + (size_t)e * na, a, na, guess, ze);
                 // the partials' rows at the bracket of the period before, in the same batch of loads as the knots: the bracket
                 // rarely moves by more than a knot per period, and behind the search every gather is a round trip of its own
                 const size_t rb = (size_t)cur * hs + gx + (size_t)e * na;
