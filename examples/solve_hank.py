@@ -94,6 +94,64 @@ def gradient(n_a=1000, n_e=7, T=500, shock=0.0025, rho=0.6, spec="one_asset_hank
             "max_abs_difference_over_max": float(np.max(np.abs(g_rev - g_fwd)) / np.max(np.abs(g_fwd)))}
 
 
+def _start(n_a, n_e, T, shock, rho, spec):
+    """the linearisation at the Newton starting point (the steady state repeated, where F ≠ 0 under the shock)"""
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    m, ss = build(n_a, n_e, T, spec)
+    P = T - 1
+    keys = h.vars_of_type(m, "endogenous")
+    x0 = np.tile(np.array([ss.vars[k] for k in keys]), P)
+    return h.LinearizedFunction(x0, {"ei": shock * rho ** np.arange(P)}, m, ss, ss), ss
+
+
+def boundary_gradient(n_a=1000, n_e=7, T=500, shock=0.0025, rho=0.6, spec="one_asset_hank_wages.yaml", seed=0):
+    """The gradient of the merit function ½‖F(x)‖² with respect to the BOUNDARY (V_T, D_0) — the terminal marginal value
+    `ss_end.value` (BackwardIteration.jl:85) and the initial distribution `ss_initial.D` (ForwardIteration.jl:293) — at the Newton
+    starting point, from ONE `LinearizedFunction.vjp_boundary` (hank_vjp_het_boundary on the sticky-wage model, whose wage
+    Phillips curve reads UCE). Printed next to its inner product with two random boundary directions (dV, dD) taken forward
+    through `LinearizedFunction.jvp_boundary` (hank_jvp_het): ⟨∇_V, dV⟩ + ⟨∇_D, dD⟩ = ⟨F, ∂F/∂(V_T, D_0) · (dV, dD)⟩."""
+    lin, ss = _start(n_a, n_e, T, shock, rho, spec)
+    hb = lin.hb
+    rng = np.random.default_rng(seed)
+    dV = rng.standard_normal((hb.n_a, hb.n_e, 2)) * np.abs(np.asarray(ss.value))[:, :, None]
+    dD = rng.standard_normal((hb.n_a, hb.n_e, 2)) / hb.G
+    lin.vjp_boundary(lin.Fx); lin.jvp_boundary(dV, dD)                  # warm-up: workspaces, graphs, the residual layer's linearisation
+    t0 = time.perf_counter()
+    g_V, g_D = lin.vjp_boundary(lin.Fx)
+    t_rev = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    fwd = lin.Fx @ lin.jvp_boundary(dV, dD)
+    t_fwd = time.perf_counter() - t0
+    rev = np.einsum("ae,aen->n", g_V, dV) + np.einsum("ae,aen->n", g_D, dD)
+    return {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "device_outputs": lin._n_out,
+            "merit": 0.5 * float(lin.Fx @ lin.Fx), "boundary_unknowns": 2 * hb.G,
+            "gradient_norm_value_end": float(np.linalg.norm(g_V)), "gradient_norm_D_init": float(np.linalg.norm(g_D)),
+            "reverse_s": round(t_rev, 5), "reverse_vjps": 1, "forward_s": round(t_fwd, 5),
+            "directional_derivatives_reverse": [float(v) for v in rev], "directional_derivatives_forward": [float(v) for v in fwd],
+            "max_abs_difference_over_max": float(np.max(np.abs(rev - fwd)) / np.max(np.abs(fwd)))}
+
+
+def het_in_sweep(n_a=1000, n_e=7, T=500, shock=0.0025, rho=0.6, spec="one_asset_hank_wages.yaml", reps=21, seed=0):
+    """What one inner Newton step pays for J(x)·y on a model that reads Value or UCE, both ways side by side: hank_jvp followed
+    by hank_get_het_outputs (the default) against ONE hank_jvp_het (`LinearizedFunction.het_in_sweep`). `reps` products of one
+    direction each — the ≈ 21 of a y-iteration — timed on the host, and the two answers' agreement."""
+    lin, _ = _start(n_a, n_e, T, shock, rho, spec)
+    y = np.random.default_rng(seed).standard_normal(lin.x.size) * 1e-3
+    out = {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "device_outputs": lin._n_out, "products": reps}
+    res = {}
+    for flag in (False, True, False, True):
+        lin.het_in_sweep = flag
+        res[flag] = lin.jvp(y)                                            # warm-up of this path (and the answer that is compared)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            lin.jvp(y)
+        out.setdefault("in_sweep_ms_per_product" if flag else "two_calls_ms_per_product", []).append(round(1e3 * (time.perf_counter() - t0) / reps, 4))
+    lin.het_in_sweep = False
+    out["max_abs_difference_over_max"] = float(np.max(np.abs(res[True] - res[False])) / np.max(np.abs(res[False])))
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-a", type=int, default=1000)
@@ -106,7 +164,15 @@ if __name__ == "__main__":
     ap.add_argument("--spec", default="one_asset_hank.yaml", choices=["one_asset_hank.yaml", "one_asset_hank_goods.yaml",
                                                                  "one_asset_hank_wages.yaml"])
     ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one transposed product against n_hh·P JVP columns")
+    ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one transposed boundary product, checked against two forward boundary directions")
+    ap.add_argument("--het-in-sweep", action="store_true", help="J(x)·y of a model that reads Value / UCE: hank_jvp + hank_get_het_outputs against one hank_jvp_het, timed side by side")
     a = ap.parse_args()
+    if a.boundary_gradient:
+        print(json.dumps(boundary_gradient(a.n_a, a.n_e, a.T, a.shock, spec=a.spec)))
+        sys.exit(0)
+    if a.het_in_sweep:
+        print(json.dumps(het_in_sweep(a.n_a, a.n_e, a.T, a.shock, spec=a.spec)))
+        sys.exit(0)
     if a.gradient:
         print(json.dumps(gradient(a.n_a, a.n_e, a.T, a.shock, spec=a.spec)))
         sys.exit(0)

@@ -331,6 +331,33 @@ int hank_jvp_boundary_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_d
 int hank_vjp_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar);
 int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar);
 
+/* ---- every output's tangent in one pair of sweeps, boundary seeds included -------------------------
+ * hank_jvp_het == hank_jvp_boundary followed by hank_get_het_outputs, for EVERY declared output and from one pair of sweeps: the
+ * partials of all keys of the plugin's NamedTuple (KrusellSmith.jl:80; dotted with the same D_t, ForwardIteration.jl:303-307)
+ * under Duals seeded in xVals, ss_end.value (BackwardIteration.jl:85) and ss_initial.D (ForwardIteration.jl:293).
+ *   dxhh, dvalue_end, dD_init as in hank_jvp_boundary: any may be NULL (zeros), all three NULL is HANK_ERR_BAD_ARG.
+ *   dagg_out (P, n_het, N) column-major, as hank_get_het_outputs' dagg_out.
+ *   n_het follows hank_vjp_het's rule: above the family's count HANK_ERR_BAD_ARG, above the declared count HANK_ERR_NOT_READY.
+ * For outputs 2 and 3 (Value, UCE) the forward launches carry n_het - 2 extra reductions, sum f_o,t dD_t - sum f_c,o,t D_t da'_t,
+ * over the dD_t the sweep itself holds: no second recurrence, and a dD_0 seed is simply there. n_het <= 2 launches the graphs of
+ * hank_jvp / hank_jvp_boundary: the same bits as those under HANK_SCHEDULE=launch. With n_het > 2, outputs 0 and 1, the policy
+ * partials and the grid aggregates are those of the n_het = 2 call bit for bit.
+ * It always runs on the per-period launches and leaves the context's schedule alone; a record written by any family serves it.
+ * Launches (hank_last_timings, tangent slots): backward P + 2, forward P + 3; with a seed pointer P + 4 and P + 5; one more
+ * forward launch when n_het > 2. Its batch becomes the current one, named as hank_jvp (both seed pointers NULL) or as
+ * hank_jvp_boundary (a seed pointer given) names it: hank_get_dpolicy_seq, hank_get_grid_aggregates and hank_get_het_outputs
+ * behave as after those calls (hank_get_het_outputs keeps refusing n_het > 2 at a batch with seeds).
+ * The _dev form takes device pointers and stays asynchronous on the context's stream. */
+int hank_jvp_het(hank_ctx *ctx, int32_t n_het, const double *dxhh, const double *dvalue_end, const double *dD_init, int32_t N, double *dagg_out);
+int hank_jvp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const double *d_dvalue_end, const double *d_dD_init, int32_t N, double *d_dagg_out);
+/* hank_vjp_het_boundary == hank_vjp_boundary with hank_vjp_het's rule for n_het: cotangents on every declared output (Value and
+ * UCE enter the reverse of the distribution sweep, ForwardIteration.jl:339-420, as in hank_vjp_het) carried through to
+ * ss_end.value (BackwardIteration.jl:85) and ss_initial.D (ForwardIteration.jl:293). The exact transpose of hank_jvp_het.
+ *   xhh_bar equals hank_vjp_het's bit for bit; value_end_bar, D_init_bar (G, M) column-major, either may be NULL (not wanted,
+ *   left unwritten). Everything else as hank_vjp_boundary. */
+int hank_vjp_het_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar);
+int hank_vjp_het_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------------------
  * Device time, in milliseconds, of the sweeps of the most recent hank_primal[_dev]/hank_jvp[_dev],
  * from HIP events recorded on the context's stream around each sweep:

@@ -39,6 +39,8 @@ class LinearizedFunction:
     NewtonRaphson.jl:91-105). Tangent batches (n, N) go through ONE hank_jvp."""
 
     exact_residual_layer = False        # True: J(x)·y through the compiled equations under a Dual at every call (tests compare the two)
+    het_in_sweep = False                # True: a model that reads Value / UCE (device outputs >= 2) takes every output's tangent from ONE
+                                        # hank_jvp_het instead of hank_jvp + hank_get_het_outputs; the two differ by the rounding of sums
 
     def __init__(self, x, exog_paths, mod: SequenceModel, ss_initial, ss_ending):
         self.x = np.asarray(x, dtype=np.float64)
@@ -142,8 +144,13 @@ class LinearizedFunction:
                 padded = np.zeros(sub.shape[:2] + (-(-len(nz) // pad_to) * pad_to,))
                 padded[:, :, :len(nz)] = sub
                 sub = padded
-            dagg[:, nz] = self.hb.jvp(sub)[:, :len(nz)]
-            if self._n_out > 1:
+            in_sweep = self.het_in_sweep and self._n_out > 2
+            if in_sweep:
+                ensure_het_outputs(self.hb, self._n_out)
+                daggs[:, :, nz] = self.hb.jvp_het(sub, n_het=self._n_out)[:, :, :len(nz)]
+            else:
+                dagg[:, nz] = self.hb.jvp(sub)[:, :len(nz)]
+            if self._n_out > 1 and not in_sweep:
                 if self._n_out > 2:
                     ensure_het_outputs(self.hb, self._n_out)
                 daggs[:, :, nz] = self.hb.het_outputs(self._n_out, sub)[1][:, :, :len(nz)]
@@ -203,6 +210,55 @@ class LinearizedFunction:
                 if name in endog_keys:          # exogenous inputs carry no cotangent back to x; x is (n_endog, P) column-major
                     out[np.ix_(endog_keys.index(name) + cs.n_endog * np.arange(P), nz)] += xb[k]
         return out[:, 0].copy() if single else out
+
+    def _own_record(self):
+        if getattr(self.hb, "_generation", None) != self._generation:
+            self._record_primal()               # (the same generation check as jvp: the context holds another x's record)
+        if self._n_out > 2:
+            ensure_het_outputs(self.hb, self._n_out)
+
+    def jvp_boundary(self, dV=None, dD=None):
+        """∂F/∂(V_P, D_0)·(dV, dD) at this x: the residuals' tangent under seeds on the terminal marginal value `ss_ending.value`
+        (BackwardIteration.jl:85) and on the initial distribution `ss_initial.D` (ForwardIteration.jl:293), x held fixed. dV, dD:
+        (n_a, n_e) or (n_a, n_e, N), either may be None (zeros). `_Ragg` composed with ONE boundary product of the block:
+        hank_jvp_het when the heterogeneous variables reach Value or UCE, hank_jvp_boundary (+ hank_get_het_outputs) otherwise."""
+        given = [np.asarray(v) for v in (dV, dD) if v is not None]
+        if not given:
+            raise ValueError("at least one of dV, dD must be given")
+        single = given[0].ndim == 2
+        if self._Rx is None:
+            self._linearise_residuals()
+        self._own_record()
+        hb = self.hb
+        N = 1 if single else given[0].shape[2]
+        if self._n_out > 2:
+            daggs = hb.jvp_het(None, dV, dD, n_het=self._n_out)
+        else:
+            d0 = hb.jvp_boundary(None, dV, dD)
+            daggs = d0[:, None, :] if self._n_out == 1 else hb.het_outputs(2, np.zeros((hb.n_hh, hb.P, N)))[1]
+        out = self._Ragg @ np.concatenate([daggs[:, j, :] for j in self._out_idx], axis=0)
+        return out[:, 0].copy() if single else out
+
+    def vjp_boundary(self, ȳ):
+        """the transpose of `jvp_boundary`: ȳ (n,) or (n, M) -> (value_end_bar, D_init_bar), each (n_a, n_e) or (n_a, n_e, M) —
+        the gradient of ȳ·F with respect to the ending steady state's marginal value and the initial distribution, from ONE pair
+        of transposed sweeps (hank_vjp_het_boundary when Value or UCE are read, hank_vjp_boundary otherwise)."""
+        ȳ = np.asarray(ȳ, dtype=np.float64)
+        single = ȳ.ndim == 1
+        Yb = ȳ[:, None] if single else ȳ
+        if self._Rx is None:
+            self._linearise_residuals()
+        P, M = self.mod.compspec.T - 1, Yb.shape[1]
+        ab = np.asarray(self._Ragg.T @ Yb).reshape(len(self.het), P, M)
+        agg_bar = np.zeros((P, self._n_out, M))
+        for j, o in enumerate(self._out_idx):
+            agg_bar[:, o, :] += ab[j]
+        self._own_record()
+        if self._n_out > 2:
+            _, vb, db = self.hb.vjp_het_boundary(agg_bar, self._n_out)
+        else:
+            _, vb, db = self.hb.vjp_boundary(agg_bar, self._n_out)
+        return (vb[:, :, 0].copy(), db[:, :, 0].copy()) if single else (vb, db)
 
     def as_linear_operator(self):
         """J(x) as a scipy.sparse.linalg.LinearOperator with both products: matvec / matmat = `jvp`, rmatvec / rmatmat = `vjp`

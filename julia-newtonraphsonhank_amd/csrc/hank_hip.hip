@@ -91,6 +91,11 @@ struct TanWork {
     // column-major, m_{-1} [N][n_e], {zm, om} [2][P][N], and the tangent-only sweeps with the two seeds in them
     DevBuf<double> bnd_dV, bnd_dD, bnd_m0, bnd_zm;
     GraphExec g_bback, g_bfwd;
+    // hank_jvp_het with n_het > 2, allocated and captured on its first use at this width: the extra slots'
+    // partials [P][nbf][NX][N] and sums T [N][P][NX] (sized for the family's count), the (P, n_het, N) result, and the forward
+    // graphs with NX = 1, 2 extra reductions, without and with the boundary's seeds
+    DevBuf<double> hx_parts, hx_T, het_out;
+    GraphExec g_fwdx[2], g_bfwdx[2];
     int VB = 1, VF = 1, RGB = 1, RGF = 1;   // lane widths and row groups the graphs are captured with
     unsigned nbf = 0;
 };
@@ -638,6 +643,51 @@ static int ensure_graphs(hank_ctx *ctx, TanWork &w, int which) {
     if ((which == 0 ? w.g_back : which == 1 ? w.g_fback : w.g_bback).get() != nullptr) return HANK_OK;
     if (w.VB == 2) return w.VF == 2 ? capture_tangent_graphs<double2, double2>(ctx, w, which) : capture_tangent_graphs<double2, double>(ctx, w, which);
     return w.VF == 2 ? capture_tangent_graphs<double, double2>(ctx, w, which) : capture_tangent_graphs<double, double>(ctx, w, which);
+}
+
+// hank_jvp_het's forward graph with NX extra reductions: the forward half of capture_tangent_graphs (which = 0, or 2 with bnd) with
+// k_tan_fwd_hx in k_tan_fwd's place and k_reduce_hx behind the reductions. Instantiated for the geometries the defaults launch:
+// the gather form with one row group and the source-stationary form with two; a dev knob that asks for another is refused.
+template <typename VF, int NX>
+static int capture_fwd_hx_graph(hank_ctx *ctx, TanWork &w, bool bnd) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P;
+    const int N = w.N, PN = (int)(P * N);
+    const size_t GV = (size_t)(c.n_a + KV) * c.n_e;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(64 * c.n_e);
+    const unsigned nbf = w.nbf, nyf = (w.gf.N + w.gf.NC - 1) / w.gf.NC;
+    VF *dD[2] = {reinterpret_cast<VF *>(w.dD[0].get()), reinterpret_cast<VF *>(w.dD[1].get())};
+    VF *dpolf = reinterpret_cast<VF *>(w.dpol.get()), *aggpart = reinterpret_cast<VF *>(w.aggpart.get());
+    const TanHx<VF, NX> hx{ctx->hx.f.get(), ctx->hx.fc.get(), reinterpret_cast<VF *>(w.hx_parts.get())};
+    const bool ss = w.gf.ss != 0;
+    if (!((w.RGF == 1 && !ss) || (w.RGF == 2 && ss)))
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_het: the forward kernel with extra outputs exists for the default geometries only (got %d row groups, %s form)",
+                    w.RGF, ss ? "source-stationary" : "gather");
+    const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e);
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    if (bnd) {
+        hipLaunchKernelGGL(k_bnd_in, tgrd, tblk, 0, s, w.bnd_dD.get(), c.n_a, c.n_e, c.n_a + KV, N, w.dD[0].get());
+        hipLaunchKernelGGL(k_bnd_marginal, dim3((unsigned)c.n_e, (unsigned)N), dim3(256), 0, s, w.bnd_dD.get(), c.n_a, c.n_e, w.bnd_m0.get());
+        hipLaunchKernelGGL(k_bnd_mpath, dim3((unsigned)((PN + 255) / 256)), dim3(256), 0, s, (int)P, c.n_e, N, w.bnd_m0.get(), ctx->d_bnd_q.get(), w.bnd_zm.get());
+    } else
+        hipLaunchKernelGGL(k_zero_f64, dim3(512), dim3(256), 0, s, w.dD[0], GV * N);
+    int cur = 0;
+    for (int t = 0; t < (int)P; t++) {
+        if (ss) hipLaunchKernelGGL((k_tan_fwd_hx<2, VF, true, NX>), dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart, hx);
+        else hipLaunchKernelGGL((k_tan_fwd_hx<1, VF, false, NX>), dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart, hx);
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)nbf, 2 * N, w.dagg);
+    hipLaunchKernelGGL(k_tan_out, dim3((2 * PN + 255) / 256), dim3(256), 0, s, w.dagg, (int)P, 2 * N, w.dagg_cm);
+    hipLaunchKernelGGL(k_reduce_hx, dim3((unsigned)P, (NX * N + 63) / 64), dim3(256), 0, s, w.hx_parts.get(), (int)nbf, NX, N, (int)P, w.hx_T.get());
+    return end_capture(ctx, &(bnd ? w.g_bfwdx : w.g_fwdx)[NX - 1]);
+}
+// (the record's f, f_c and the workspace's hx_parts, hx_T are allocated before this: the graph holds their addresses)
+static int ensure_fwd_hx_graph(hank_ctx *ctx, TanWork &w, bool bnd, int NX) {
+    if ((bnd ? w.g_bfwdx : w.g_fwdx)[NX - 1].get() != nullptr) return HANK_OK;
+    if (NX == 1) return w.VF == 2 ? capture_fwd_hx_graph<double2, 1>(ctx, w, bnd) : capture_fwd_hx_graph<double, 1>(ctx, w, bnd);
+    return w.VF == 2 ? capture_fwd_hx_graph<double2, 2>(ctx, w, bnd) : capture_fwd_hx_graph<double, 2>(ctx, w, bnd);
 }
 
 // ---- the device's verdict on work already enqueued, and what the context does about it ------------------
@@ -1736,8 +1786,10 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
 }
 
 // bnd: the graphs with the boundary's seeds (hank_jvp_boundary: w.bnd_dV and w.bnd_dD hold them); zm: whether a dD_0 seed is among them
-static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd = false, bool zm = false) {
+// NX > 0 (hank_jvp_het): the forward graph with that many extra reductions, one launch more (k_reduce_hx)
+static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd = false, bool zm = false, int NX = 0) {
     int grc = ensure_graphs(ctx, w, bnd ? 2 : 0);
+    if (!grc && NX > 0) grc = ensure_fwd_hx_graph(ctx, w, bnd, NX);
     if (grc) return grc;
     HIPC(ctx, ctx->spans.begin(TAN_BACK, ctx->stream));
     HIPC(ctx, hipGraphLaunch(bnd ? w.g_bback : w.g_back, ctx->stream));
@@ -1746,8 +1798,8 @@ static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd = false, bool zm = false)
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
     HIPC(ctx, ctx->spans.begin(TAN_FWD, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(bnd ? w.g_bfwd : w.g_fwd, ctx->stream));
-    HIPC(ctx, ctx->spans.end(TAN_FWD, ctx->stream, ctx->c.P + (bnd ? 5 : 3)));
+    HIPC(ctx, hipGraphLaunch(NX > 0 ? (bnd ? w.g_bfwdx : w.g_fwdx)[NX - 1] : bnd ? w.g_bfwd : w.g_fwd, ctx->stream));
+    HIPC(ctx, ctx->spans.end(TAN_FWD, ctx->stream, ctx->c.P + (bnd ? 5 : 3) + (NX > 0 ? 1 : 0)));
     if (bnd) batch_ran_boundary(ctx, &w, w.N, w.dagg_cm, w.dpol, zm ? w.bnd_zm.get() : nullptr);
     else batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
     return HANK_OK;
@@ -1820,8 +1872,24 @@ static int ensure_bnd_q(hank_ctx *ctx) {
     }
     DevBuf<double> buf;
     HIPC(ctx, buf.alloc(Q.size()));
-    HIPC(ctx, hipMemcpy(buf, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice));
+    // on the context's stream, not the legacy one: a copy there would join every blocking stream of the process, and another
+    // context of this GPU (parallel.DeviceGroup) may be capturing a graph on its own
+    HIPC(ctx, hipMemcpyAsync(buf, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (Q is this call's)
     ctx->d_bnd_q = std::move(buf);
+    return HANK_OK;
+}
+// the seeds' buffers of a workspace and the model's Q, before the first capture with seeds at this width
+static int ensure_bnd_bufs(hank_ctx *ctx, TanWork &w) {
+    const size_t P = ctx->c.P, GN = (size_t)ctx->c.G * w.N;
+    const int rc = ensure_bnd_q(ctx);
+    if (rc) return rc;
+    if (!w.bnd_zm) {
+        HIPC(ctx, w.bnd_dV.alloc(GN));
+        HIPC(ctx, w.bnd_dD.alloc(GN));
+        HIPC(ctx, w.bnd_m0.alloc((size_t)w.N * ctx->c.n_e));
+        HIPC(ctx, w.bnd_zm.alloc(2 * P * w.N));      // (last: a failed allocation is tried again by the next call)
+    }
     return HANK_OK;
 }
 static int enqueue_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_end, const double *dD_init, hipMemcpyKind kind, int N, double *d_dagg_out) {
@@ -1829,14 +1897,8 @@ static int enqueue_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double 
     int rc = ensure_tanwork(ctx, N, &w);
     if (rc) return rc;
     const size_t P = ctx->c.P, GN = (size_t)ctx->c.G * N;
-    rc = ensure_bnd_q(ctx);
+    rc = ensure_bnd_bufs(ctx, *w);
     if (rc) return rc;
-    if (!w->bnd_zm) {
-        HIPC(ctx, w->bnd_dV.alloc(GN));
-        HIPC(ctx, w->bnd_dD.alloc(GN));
-        HIPC(ctx, w->bnd_m0.alloc((size_t)N * ctx->c.n_e));
-        HIPC(ctx, w->bnd_zm.alloc(2 * P * N));      // (last: a failed allocation is tried again by the next call)
-    }
     const struct { double *dst; const double *src; size_t count; } in[3] = {{w->dxhh, dxhh, ctx->c.n_hh * P * N}, {w->bnd_dV, dvalue_end, GN}, {w->bnd_dD, dD_init, GN}};
     for (const auto &a : in) {
         if (a.src) HIPC(ctx, hipMemcpyAsync(a.dst, a.src, sizeof(double) * a.count, kind, ctx->stream));
@@ -2417,9 +2479,12 @@ static int vjp(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, co
 
 // hank_vjp_boundary[_dev]: hank_vjp's path (and its rule for n_het) plus the boundary's cotangents; either may be null (not wanted).
 // The host form stages them in the workspace of this width.
-static int vjp_boundary(hank_ctx *ctx, int n_het, const double *agg_bar, int M, double *xhh_bar, double *value_end_bar, double *D_init_bar, bool dev) {
+// hank_vjp_het_boundary[_dev]: the same with hank_vjp_het's rule (args, as in vjp), so Value and UCE carry cotangents to the boundary:
+// enqueue_vjp runs Sweep A with NX > 0 and exports the same two states.
+static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, const void *), int n_het, const double *agg_bar, int M, double *xhh_bar,
+                        double *value_end_bar, double *D_init_bar, bool dev) {
     ENTER(ctx);
-    int rc = vjp_args(ctx, n_het, agg_bar, M, xhh_bar);
+    int rc = args(ctx, n_het, agg_bar, M, xhh_bar);
     if (rc) return rc;
     CotWork *w = nullptr;
     if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, value_end_bar, D_init_bar);
@@ -2442,10 +2507,17 @@ static int vjp_boundary(hank_ctx *ctx, int n_het, const double *agg_bar, int M, 
 
 extern "C" {
 int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar) {
-    return vjp_boundary(ctx, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);
+    return vjp_boundary(ctx, vjp_args, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);
+}
+// (KrusellSmith.jl:80: Value and UCE are keys of the plugin's NamedTuple; BackwardIteration.jl:85, ForwardIteration.jl:293: the boundary)
+int hank_vjp_het_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar) {
+    return vjp_boundary(ctx, vjp_het_args, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);
+}
+int hank_vjp_het_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar) {
+    return vjp_boundary(ctx, vjp_het_args, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false);
 }
 int hank_vjp_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar) {
-    return vjp_boundary(ctx, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false);
+    return vjp_boundary(ctx, vjp_args, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false);
 }
 int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) { return vjp(ctx, vjp_het_args, n_het, d_agg_bar, M, d_xhh_bar, true); }
 int hank_vjp_het(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) { return vjp(ctx, vjp_het_args, n_het, agg_bar, M, xhh_bar, false); }
@@ -2680,6 +2752,88 @@ int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het) {
     if (rc) return rc;
     if (n_het != ctx->n_het) ctx->memo_valid = false;      // the next hank_primal_jvp records its primal afresh
     ctx->n_het = n_het;
+    return HANK_OK;
+}
+}
+
+// ---- hank_jvp_het[_dev]: every declared output's tangent from ONE pair of sweeps, boundary seeds included ----
+// The launch family's tangent sweeps, whatever the context's schedule and whichever family wrote the record (run_jvp's ensure_seg /
+// ensure_lwg), as hank_jvp_boundary runs them. For n_het > 2 the forward launches carry NX = n_het - 2 extra reductions
+// (k_tan_fwd_hx): the in-period sums T_o,t = sum f_o,t dD_t - sum f_c,o,t D_t da'_t of Value and UCE (KrusellSmith.jl:80;
+// ForwardIteration.jl:303-307 dots every key with the same D_t) from the dD_t the sweep itself carries — so a dD_0 seed
+// (ForwardIteration.jl:293) needs nothing more, and a dV_P seed (BackwardIteration.jl:85) is already in dpol. k_het_outputs then
+// assembles (P, n_het, N) as hank_get_het_outputs does, with k_bnd_cons behind it under a dD_0 seed.
+// Launches: TAN_BACK P + 2 (P + 4 with seeds), TAN_FWD P + 3 (P + 5 with seeds), one more for n_het > 2; k_het_outputs (and
+// k_bnd_cons) behind the spans. n_het <= 2 launches hank_jvp's / hank_jvp_boundary's own graphs.
+// The batch is named as those two entries name theirs under the launch schedule, so the readers behave as they do after them.
+static int enqueue_jvp_het(hank_ctx *ctx, int n_het, const double *dxhh, const double *dvalue_end, const double *dD_init, hipMemcpyKind kind, int N,
+                           double *d_dagg_out, TanWork **out) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P, GN = (size_t)c.G * N, nh = c.n_hh;
+    const int NX = n_het > 2 ? n_het - 2 : 0, SX = hx_count(ctx);
+    const bool bnd = dvalue_end || dD_init;
+    TanWork *w = nullptr;
+    int rc = ensure_tanwork(ctx, N, &w);
+    if (rc) return rc;
+    if (bnd && (rc = ensure_bnd_bufs(ctx, *w)) != HANK_OK) return rc;
+    if (!w->het_out) HIPC(ctx, w->het_out.alloc(P * het_max(ctx) * N));
+    if (NX > 0) {
+        HIPC(ctx, join_side(ctx));      // the record's sums read D_t
+        rc = ensure_hx_record(ctx);      // (before the capture: the graph holds the record's addresses)
+        if (rc) return rc;
+        if (!w->hx_T) {
+            HIPC(ctx, w->hx_parts.alloc(P * (size_t)w->nbf * SX * N));
+            HIPC(ctx, w->hx_T.alloc((size_t)N * P * SX));      // (last: a failed allocation is tried again by the next call)
+        }
+    }
+    if (dxhh) HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * nh * P * N, kind, ctx->stream));
+    else HIPC(ctx, hipMemsetAsync(w->dxhh, 0, sizeof(double) * nh * P * N, ctx->stream));
+    if (bnd) {
+        const struct { double *dst; const double *src; } in[2] = {{w->bnd_dV, dvalue_end}, {w->bnd_dD, dD_init}};
+        for (const auto &a : in) {
+            if (a.src) HIPC(ctx, hipMemcpyAsync(a.dst, a.src, sizeof(double) * GN, kind, ctx->stream));
+            else HIPC(ctx, hipMemsetAsync(a.dst, 0, sizeof(double) * GN, ctx->stream));
+        }
+    }
+    rc = run_jvp(ctx, *w, bnd, dD_init != nullptr, NX);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * ((size_t)N + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, n_het, SX, N, ctx->d_xhh,
+                       w->dxhh.get(), ctx->d_agg, w->dagg_cm.get(), ctx->d_zd, ctx->hx.S.get(), w->hx_T.get(), (double *)nullptr, w->het_out.get());
+    if (dD_init && n_het >= 2)
+        hipLaunchKernelGGL(k_bnd_cons, dim3((unsigned)((P * N + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, n_het, N, ctx->d_xhh, w->bnd_zm.get(), w->het_out.get());
+    HIPC(ctx, hipGetLastError());
+    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->het_out, sizeof(double) * P * n_het * N, hipMemcpyDeviceToDevice, ctx->stream));
+    *out = w;
+    return HANK_OK;
+}
+// the rules: the arguments, then the count (hank_vjp_het's rule), then the record
+static int jvp_het_args(hank_ctx *ctx, int n_het, const void *dxhh, const void *dvalue_end, const void *dD_init, int N, const void *out, bool need_out) {
+    if (!ctx || (!dxhh && !dvalue_end && !dD_init) || (need_out && !out) || N < 1)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_het: bad argument (N=%d; at least one of dxhh, dvalue_end, dD_init must be given)", N);
+    const int rc = het_count_ok(ctx, "hank_jvp_het", n_het, true);
+    if (rc) return rc;
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_het");
+    return HANK_OK;
+}
+extern "C" {
+int hank_jvp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const double *d_dvalue_end, const double *d_dD_init, int32_t N, double *d_dagg_out) {
+    ENTER(ctx);
+    const int rc = jvp_het_args(ctx, n_het, d_dxhh, d_dvalue_end, d_dD_init, N, d_dagg_out, false);
+    if (rc) return rc;
+    TanWork *w = nullptr;
+    return enqueue_jvp_het(ctx, n_het, d_dxhh, d_dvalue_end, d_dD_init, hipMemcpyDeviceToDevice, N, d_dagg_out, &w);
+}
+int hank_jvp_het(hank_ctx *ctx, int32_t n_het, const double *dxhh, const double *dvalue_end, const double *dD_init, int32_t N, double *dagg_out) {
+    ENTER(ctx);
+    int rc = jvp_het_args(ctx, n_het, dxhh, dvalue_end, dD_init, N, dagg_out, true);
+    if (rc) return rc;
+    TanWork *w = nullptr;
+    rc = enqueue_jvp_het(ctx, n_het, dxhh, dvalue_end, dD_init, hipMemcpyHostToDevice, N, nullptr, &w);
+    if (rc) return rc;
+    // (the launches' tangent sweeps raise no device error: nothing to ask, as in hank_jvp)
+    HIPC(ctx, hipMemcpyAsync(dagg_out, w->het_out, sizeof(double) * ctx->c.P * n_het * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
     return HANK_OK;
 }
 }

@@ -857,9 +857,19 @@ k_fused_back(Consts c, Record R, const double *__restrict__ xhh, int *err, int t
 //     0's tangent is (real row 0) + sum_p (virtual row p). Everything downstream is linear, so the
 //     parts are never combined: a virtual row is a source with row 0's lottery (no own policy
 //     tangent), and its aggregate term uses pol[0, e].
-template <int RG, typename VT, bool SS>
+// NX extra reductions (hx: nothing for NX = 0, today's kernel): the in-period sums of the outputs that are not affine in the policy
+// (hank_hetx.h), T_o,t = sum f_o,t dD_t - sum f_c,o,t D_t da'_t — the reduction made for the policy variable with other per-point
+// weights: f_o,t at the target rows next to pol, f_c,o,t at the source rows next to D_t. hx.parts: [t][block][NX][N], the blocks
+// summed in order by k_reduce_hx. The block reduction of the extra slots reuses the `sh` tiles (free after the mixing) behind one
+// more barrier, so sh has max(RG, NX) tiles there.
+template <typename VT, int NX>
+struct TanHx { const double *f, *fc; VT *parts; };      // f, f_c [jx][P][G] (k_hx_record)
+template <typename VT>
+struct TanHx<VT, 0> {};
+template <int RG, typename VT, bool SS, int NX = 0>
 __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanGeom &g, int t, const VT *__restrict__ dDin, VT *__restrict__ dDout,
-          const VT *__restrict__ dpol, VT *__restrict__ aggpart, int bidx_phys, int bidy, int nbx_total, VT (*sh)[16 * 64], double *Pish, VT *red, VT *red2) {
+          const VT *__restrict__ dpol, VT *__restrict__ aggpart, int bidx_phys, int bidy, int nbx_total, VT (*sh)[16 * 64], double *Pish, VT *red, VT *red2,
+          TanHx<VT, NX> hx = TanHx<VT, NX>()) {
     const int nbr_f = (g.nbx + RG - 1) / RG;            // regular blocks; the mass-point blocks behind them keep their place
     const int bidx = (g.N * (int)(sizeof(VT) / 8) <= HANK_XCDMAP_FWD_MAXN && bidx_phys < nbr_f) ? xcd_contiguous(bidx_phys, nbr_f) : bidx_phys;
     const int nthr = 64 * c.n_e;
@@ -883,6 +893,13 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
     double cp[RG];
     VT pagg;              // sum of dpol_j * D_t[j] over the sources this thread owns
     vzero(pagg);
+    [[maybe_unused]] VT paggx[NX > 0 ? NX : 1];        // minus the same sources' f_c,o,t[j] * D_t[j] * dpol_j, per extra output
+    [[maybe_unused]] double cfx[RG][NX > 0 ? NX : 1];  // f_o,t at the thread's target rows (a virtual row carries row 0's, as it carries pol of row 0)
+    [[maybe_unused]] const size_t PG = (size_t)c.P * c.G;
+    if constexpr (NX > 0) {
+#pragma unroll
+        for (int o = 0; o < NX; o++) vzero(paggx[o]);
+    }
     bool in_lds = false;   // the gathered tile already sits in sh (source-stationary path)
     if (SS && !virt_block) {
         // SOURCE-STATIONARY form: the block owns the RG*RB target rows [r0, r0+rows); column e's wave walks the
@@ -897,6 +914,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
             valid[q] = (r[q] < na) && nok;
             vzero(acc[q]);
             cp[q] = valid[q] ? R.pol[cb + r[q]] : 0.0;
+            if constexpr (NX > 0) {
+#pragma unroll
+                for (int o = 0; o < NX; o++) cfx[q][o] = valid[q] ? hx.f[o * PG + cb + r[q]] : 0.0;
+            }
             sh[q][e * 64 + lane] = acc[q];
         }
         const int *st = R.start + ((size_t)t * c.n_e + e) * (na + 1);
@@ -908,6 +929,7 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
             double2 wg[2];
             double dn[2];
             VT dd[2], dp[2];
+            [[maybe_unused]] double fx[2][NX > 0 ? NX : 1];
             bool ok[2];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
@@ -920,6 +942,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                     dn[u] = Dnew[j];
                     dd[u] = dDc[(size_t)j * N];
                     dp[u] = dpc[(size_t)j * N];
+                    if constexpr (NX > 0) {
+#pragma unroll
+                        for (int o = 0; o < NX; o++) fx[u][o] = hx.fc[o * PG + cb + j];
+                    }
                     if (j == 0)   // (then clo == 0) row 0 not clamped: its virtual rows follow row 0's interior lottery
                         for (int k = 0; k < KV; k++) dd[u] = vadd(dd[u], dDc[(size_t)(na + k) * N]);
                 }
@@ -934,6 +960,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                     if (th >= 0 && th < rows) {   // the source's FIRST-segment target: its aggregate term is taken here, once
                         lds_add(&sh[th >> lgRB][e * 64 + ((th & (RB - 1)) << g.lgNC) + nl], vadd(vmul(wg[u].x, dd[u]), gt));
                         pagg = vadd(pagg, vmul(dn[u], dp[u]));
+                        if constexpr (NX > 0) {
+#pragma unroll
+                            for (int o = 0; o < NX; o++) paggx[o] = vsub(paggx[o], vmul(fx[u][o] * dn[u], dp[u]));
+                        }
                     }
                 }
             }
@@ -950,6 +980,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                 const int4 sg = R.seg[cb + r[q]];
                 s0[q] = sg.x; s1[q] = sg.y; s2[q] = sg.z;
                 cp[q] = R.pol[cb + r[q]];
+            }
+            if constexpr (NX > 0) {
+#pragma unroll
+                for (int o = 0; o < NX; o++) cfx[q][o] = valid[q] ? hx.f[o * PG + cb + r[q]] : 0.0;
             }
         }
 #pragma unroll
@@ -969,6 +1003,7 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                     VT pd[FS], pp[FS];
                     double pn[FS];
                     double2 pw[FS];
+                    [[maybe_unused]] double pfx[FS][NX > 0 ? NX : 1];
 #pragma unroll
                     for (int k = 0; k < FS; k++) {
                         const int j = s0[q] + k;
@@ -977,7 +1012,13 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                             pp[k] = dpc[(size_t)j * N];
                             pw[k] = R.lwg[cb + j];
                             pd[k] = dDc[(size_t)j * N];
-                            if (j < s1[q]) pn[k] = Dnew[j];
+                            if (j < s1[q]) {
+                                pn[k] = Dnew[j];
+                                if constexpr (NX > 0) {
+#pragma unroll
+                                    for (int o = 0; o < NX; o++) pfx[k][o] = hx.fc[o * PG + cb + j];
+                                }
+                            }
                         }
                     }
 #pragma unroll
@@ -986,6 +1027,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                         if (j < s1[q]) {
                             s = vadd(s, vadd(vmul(pw[k].x, pd[k]), vmul(pw[k].y, pp[k])));
                             pagg = vadd(pagg, vmul(pn[k], pp[k]));
+                            if constexpr (NX > 0) {
+#pragma unroll
+                                for (int o = 0; o < NX; o++) paggx[o] = vsub(paggx[o], vmul(pfx[k][o] * pn[k], pp[k]));
+                            }
                         } else if (j < s2[q]) {
                             s = vadd(s, vsub(vmul(1.0 - pw[k].x, pd[k]), vmul(pw[k].y, pp[k])));
                         }
@@ -996,6 +1041,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                         if (j < s1[q]) {
                             s = vadd(s, vadd(vmul(wg.x, dDc[(size_t)j * N]), vmul(wg.y, dpj)));
                             pagg = vadd(pagg, vmul(Dnew[j], dpj));
+                            if constexpr (NX > 0) {
+#pragma unroll
+                                for (int o = 0; o < NX; o++) paggx[o] = vsub(paggx[o], vmul(hx.fc[o * PG + cb + j] * Dnew[j], dpj));
+                            }
                         } else {
                             s = vadd(s, vsub(vmul(1.0 - wg.x, dDc[(size_t)j * N]), vmul(wg.y, dpj)));
                         }
@@ -1009,6 +1058,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
                         const double2 wg = R.lwg[cb + j];
                         s = vadd(s, vadd(vmul(wg.x, dDc[(size_t)j * N]), vmul(wg.y, dpj)));
                         pagg = vadd(pagg, vmul(Dnew[j], dpj));
+                        if constexpr (NX > 0) {
+#pragma unroll
+                            for (int o = 0; o < NX; o++) paggx[o] = vsub(paggx[o], vmul(hx.fc[o * PG + cb + j] * Dnew[j], dpj));
+                        }
                     }
                     for (int j = s1[q]; j < s2[q]; j++) {
                         const double2 wg = R.lwg[cb + j];
@@ -1031,6 +1084,12 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
 #pragma unroll
         for (int q = 0; q < RG; q++) { r[q] = na + p; valid[q] = (q == 0) && nok && (rl == 0); vzero(acc[q]); cp[q] = 0.0; }
         cp[0] = R.pol[cb];       // a virtual row carries row 0's policy and no policy tangent of its own
+        if constexpr (NX > 0) {
+#pragma unroll
+            for (int q = 0; q < RG; q++)
+#pragma unroll
+                for (int o = 0; o < NX; o++) cfx[q][o] = q == 0 ? hx.f[o * PG + cb] : 0.0;
+        }
         VT s;
         vzero(s);
         if (nok && clo > 0) {
@@ -1039,10 +1098,23 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
             for (int i = lo + rl; i < hi; i += RB) {
                 s = vadd(s, dDc[(size_t)(i < clo ? i : na + (i - clo)) * N]);
                 if (i < clo) pagg = vadd(pagg, vmul(Dnew[i], dpc[(size_t)i * N]));   // clamped sources: policy partial is 0 except on a knot tie
+                if constexpr (NX > 0) {
+                    if (i < clo) {
+#pragma unroll
+                        for (int o = 0; o < NX; o++) paggx[o] = vsub(paggx[o], vmul(hx.fc[o * PG + cb + i] * Dnew[i], dpc[(size_t)i * N]));
+                    }
+                }
             }
         }
         for (int off = 32; off >= g.NC; off >>= 1) { s = vadd(s, vshfl_xor(s, off)); pagg = vadd(pagg, vshfl_xor(pagg, off)); }
         if (rl != 0) vzero(pagg);
+        if constexpr (NX > 0) {
+#pragma unroll
+            for (int o = 0; o < NX; o++) {
+                for (int off = 32; off >= g.NC; off >>= 1) paggx[o] = vadd(paggx[o], vshfl_xor(paggx[o], off));
+                if (rl != 0) vzero(paggx[o]);
+            }
+        }
         acc[0] = s;
     }
     for (int k = threadIdx.x; k < c.n_e * c.n_e; k += nthr) Pish[k] = c.Pi[k];
@@ -1053,6 +1125,11 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
     lds_barrier();
     VT part, part2;       // the policy-weighted aggregate's partial and the wealth-grid-weighted one's (see dist_step_body)
     vzero(part); vzero(part2);
+    [[maybe_unused]] VT partx[NX > 0 ? NX : 1];
+    if constexpr (NX > 0) {
+#pragma unroll
+        for (int o = 0; o < NX; o++) vzero(partx[o]);
+    }
 #pragma unroll
     for (int q = 0; q < RG; q++) {
         if (valid[q]) {
@@ -1061,6 +1138,10 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
             st_mode<HANK_ST_STATE>(&dDout[((size_t)e * nav + r[q]) * N + n], dDn);
             part = vadd(part, vmul(cp[q], dDn));
             part2 = vadd(part2, vmul(c.a[r[q] < na ? r[q] : 0], dDn));       // (a virtual row is a part of row 0)
+            if constexpr (NX > 0) {
+#pragma unroll
+                for (int o = 0; o < NX; o++) partx[o] = vadd(partx[o], vmul(cfx[q][o], dDn));
+            }
         }
     }
     part = vadd(part, pagg);
@@ -1069,6 +1150,21 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
     red[e * 64 + lane] = part;
     red2[e * 64 + lane] = part2;
     lds_barrier();
+    if constexpr (NX > 0) {
+        // every wave has left the mixing (it wrote `red` behind it): the sh tiles are free, one per extra slot
+#pragma unroll
+        for (int o = 0; o < NX; o++) sh[o][e * 64 + lane] = vadd(partx[o], paggx[o]);
+        lds_barrier();
+        if (e == 0) {
+#pragma unroll
+            for (int o = 0; o < NX; o++) {
+                VT s = sh[o][lane];
+                for (int k = 1; k < c.n_e; k++) s = vadd(s, sh[o][k * 64 + lane]);
+                for (int off = 32; off >= g.NC; off >>= 1) s = vadd(s, vshfl_xor(s, off));
+                if (rl == 0 && nok) hx.parts[(((size_t)t * nbx_total + bidx) * NX + o) * N + n] = s;      // [t][block][NX][N]
+            }
+        }
+    }
     if (e == 0) {
         VT s = red[lane], s2 = red2[lane];
         for (int k = 1; k < c.n_e; k++) { s = vadd(s, red[k * 64 + lane]); s2 = vadd(s2, red2[k * 64 + lane]); }
@@ -1088,6 +1184,36 @@ k_tan_fwd(Consts c, Record R, TanGeom g, int t, const VT *__restrict__ dDin, VT 
     __shared__ VT red[16 * 64], red2[16 * 64];
     __shared__ double Pish[256];
     tan_fwd_body<RG, VT, SS>(c, R, g, t, dDin, dDout, dpol, aggpart, blockIdx.x, blockIdx.y, gridDim.x, sh, Pish, red, red2);
+}
+
+// the forward tangent launch with NX = 1, 2 extra reductions (hank_jvp_het): k_tan_fwd keeps its name and its arguments, so the
+// NX = 0 launch is the kernel it was
+template <int RG, typename VT, bool SS, int NX>
+__global__ void __launch_bounds__(1024)
+k_tan_fwd_hx(Consts c, Record R, TanGeom g, int t, const VT *__restrict__ dDin, VT *__restrict__ dDout,
+             const VT *__restrict__ dpol, VT *__restrict__ aggpart, TanHx<VT, NX> hx) {
+    __shared__ VT sh[RG > NX ? RG : NX][16 * 64];
+    __shared__ VT red[16 * 64], red2[16 * 64];
+    __shared__ double Pish[256];
+    tan_fwd_body<RG, VT, SS, NX>(c, R, g, t, dDin, dDout, dpol, aggpart, blockIdx.x, blockIdx.y, gridDim.x, sh, Pish, red, red2, hx);
+}
+// T[n][t][jx] = sum_b parts[((t nb + b) NX + jx) N + n] (the layout k_het_outputs reads as hxT); one block per (t, 64-wide chunk
+// of the NX N columns), in the manner of k_reduce_parts: four groups of lanes stride over the blocks in order, then the groups combine
+__global__ void k_reduce_hx(const double *__restrict__ parts, int nb, int NX, int N, int P, double *__restrict__ T) {
+    __shared__ double red[256];
+    const int t = blockIdx.x, nl = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int col = blockIdx.y * 64 + nl, W = NX * N;
+    double s = 0.0;
+    if (col < W) {
+        const double *p = parts + (size_t)t * nb * W + col;
+        for (int b = g; b < nb; b += 4) s += p[(size_t)b * W];
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (g == 0 && col < W) {
+        const int jx = col / N, n = col - jx * N;
+        T[((size_t)n * P + t) * NX + jx] = (red[nl] + red[64 + nl]) + (red[128 + nl] + red[192 + nl]);
+    }
 }
 
 // the dual-sweep forward launch: blocks [0, nbp) of grid row 0 run the PRIMAL distribution step of

@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
     "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings", "hank_vjp_het", "hank_vjp_het_dev",
     "hank_jvp_boundary", "hank_jvp_boundary_dev", "hank_vjp_boundary", "hank_vjp_boundary_dev",
+    "hank_jvp_het", "hank_jvp_het_dev", "hank_vjp_het_boundary", "hank_vjp_het_boundary_dev",
 )
 
 
@@ -127,6 +128,10 @@ def load_library() -> C.CDLL:
     lib.hank_jvp_boundary_dev.argtypes = [vp, vp, vp, vp, i32, vp]
     lib.hank_vjp_boundary.argtypes = [vp, i32, dp, i32, dp, dp, dp]
     lib.hank_vjp_boundary_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    lib.hank_jvp_het.argtypes = [vp, i32, dp, dp, dp, i32, dp]
+    lib.hank_jvp_het_dev.argtypes = [vp, i32, vp, vp, vp, i32, vp]
+    lib.hank_vjp_het_boundary.argtypes = [vp, i32, dp, i32, dp, dp, dp]
+    lib.hank_vjp_het_boundary_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
@@ -390,6 +395,53 @@ class HouseholdBlock:
         """device-pointer form (asynchronous on the context's stream); a boundary pointer of 0 is not wanted."""
         self._chk(self._lib.hank_vjp_boundary_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr),
                                                   C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
+
+    # -- every output's tangent in one pair of sweeps; its transpose on the boundary ----------
+    def jvp_het(self, dxhh=None, dvalue_end=None, dD_init=None, n_het: int = 2) -> np.ndarray:
+        """every declared output's tangent from one pair of sweeps (hank_jvp_het): inputs as in `jvp_boundary` (None means zeros,
+        at least one must be given), n_het up to the count declared with `set_het_outputs`. -> dagg (P, n_het, N), the shape of
+        `het_outputs`' dagg. Value and UCE ride in the forward sweep, so boundary seeds reach them too. Always the launch
+        family; n_het <= 2 gives the bits of `jvp` / `jvp_boundary` under the launch schedule."""
+        given = [np.asarray(v) for v in (dxhh, dvalue_end, dD_init) if v is not None]
+        if not given:
+            raise ValueError("at least one of dxhh, dvalue_end, dD_init must be given")
+        N = given[0].shape[-1] if given[0].ndim == 3 else 1
+        dx = None
+        if dxhh is not None:
+            dx = np.asarray(dxhh, dtype=np.float64)
+            dx = _f(dx[:, :, None] if dx.ndim == 2 else dx, (self.n_hh, self.P, N))
+        dv, dd = self._boundary_seed(dvalue_end, N), self._boundary_seed(dD_init, N)
+        out = np.empty((self.P, max(int(n_het), 1), N), order="F")
+        self.calls["jvp"] += 1
+        self._chk(self._lib.hank_jvp_het(self._ctx, int(n_het), None if dx is None else _p(dx), None if dv is None else _p(dv),
+                                         None if dd is None else _p(dd), N, _p(out)))
+        return out
+
+    def jvp_het_dev(self, n_het: int, d_dxhh_ptr: int, d_dvalue_end_ptr: int, d_dD_init_ptr: int, N: int, d_dagg_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
+        self._chk(self._lib.hank_jvp_het_dev(self._ctx, int(n_het), C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dvalue_end_ptr or None),
+                                             C.c_void_p(d_dD_init_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+
+    def vjp_het_boundary(self, agg_bar, n_het: int, value_end: bool = True, D_init: bool = True):
+        """`vjp_het` with the boundary's cotangents (hank_vjp_het_boundary): agg_bar (P, n_het, M) -> (xhh_bar (n_hh, P, M),
+        value_end_bar (n_a, n_e, M), D_init_bar (n_a, n_e, M)); the exact transpose of `jvp_het`. A boundary cotangent that is
+        not wanted (value_end / D_init False) is not computed and comes back as None. xhh_bar equals `vjp_het`'s bit for bit."""
+        yb = np.asarray(agg_bar, dtype=np.float64)
+        if yb.ndim != 3:
+            raise ValueError("agg_bar must be (P, n_het, M)")
+        M = yb.shape[2]
+        yb = _f(yb, (self.P, int(n_het), M) if 1 <= int(n_het) <= 4 else None)      # (the library refuses any other n_het)
+        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
+        vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if value_end else None
+        db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if D_init else None
+        self._chk(self._lib.hank_vjp_het_boundary(self._ctx, int(n_het), _p(yb), M, _p(out), None if vb is None else _p(vb),
+                                                  None if db is None else _p(db)))
+        return out, vb, db
+
+    def vjp_het_boundary_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_value_end_bar_ptr: int = 0, d_D_init_bar_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); a boundary pointer of 0 is not wanted."""
+        self._chk(self._lib.hank_vjp_het_boundary_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr),
+                                                      C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
 
     def policy_cotangent_seq(self, M: int) -> np.ndarray:
         """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp / vjp_het (hank_get_policy_cotangent_seq)."""

@@ -137,6 +137,31 @@ class DeviceGroup:
         parts = self._each(lambda b, lo, hi: b.vjp_het(yb[:, :, lo:hi], n_het) if hi > lo else np.empty((b0.n_hh, b0.P, 0)), bounds)
         return np.concatenate(parts, axis=2)
 
+    def jvp_het(self, dxhh=None, dvalue_end=None, dD_init=None, n_het: int = 2):
+        """every declared output's tangent with boundary seeds (HouseholdBlock.jvp_het): dxhh (n_hh, P, N), dvalue_end and dD_init
+        (n_a, n_e, N), None = zeros -> (P, n_het, N); the direction columns of all three shard like `jvp`'s."""
+        import numpy as np
+        ins = [None if v is None else np.asarray(v, dtype=np.float64) for v in (dxhh, dvalue_end, dD_init)]
+        given = [v for v in ins if v is not None]
+        if not given:
+            raise ValueError("at least one of dxhh, dvalue_end, dD_init must be given")
+        N, W = given[0].shape[2], len(self.blocks)
+        bounds = [shard_bounds(N, W, g) for g in range(W)]
+        b0 = self.blocks[0]
+        cut = lambda lo, hi: [None if v is None else v[:, :, lo:hi] for v in ins]
+        parts = self._each(lambda b, lo, hi: b.jvp_het(*cut(lo, hi), n_het=n_het) if hi > lo else np.empty((b0.P, n_het, 0)), bounds)
+        return np.concatenate(parts, axis=2)
+
+    def vjp_het_boundary(self, agg_bar, n_het: int):
+        """`vjp_het` with the boundary's cotangents (HouseholdBlock.vjp_het_boundary), sharded the same way:
+        -> (xhh_bar (n_hh, P, M), value_end_bar (n_a, n_e, M), D_init_bar (n_a, n_e, M))."""
+        import numpy as np
+        yb = np.asarray(agg_bar, dtype=np.float64)
+        M, W = yb.shape[2], len(self.blocks)
+        bounds = [shard_bounds(M, W, g) for g in range(W)]
+        parts = [p for p in self._each(lambda b, lo, hi: b.vjp_het_boundary(yb[:, :, lo:hi], n_het) if hi > lo else None, bounds) if p is not None]
+        return tuple(np.concatenate([p[k] for p in parts], axis=2) for k in range(3))
+
     def jvp_dev(self, d_y_blocks, N_k):
         """the same partition with everything on the devices: GPU g's tangent columns are already in its memory (`d_y_blocks[g]`: a
         torch tensor of (n_hh, P, N_k[g]) column-major values on that device), every context runs its sweeps asynchronously, and

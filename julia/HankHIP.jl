@@ -348,6 +348,39 @@ function hank_vjp_boundary!(xhh_bar::Array{Float64,3}, value_end_bar::Union{Noth
     return xhh_bar, value_end_bar, D_init_bar
 end
 
+# ---- every output's tangent in one pair of sweeps (hank_jvp_het) and its transpose on the boundary (hank_vjp_het_boundary) -------
+# dagg (P, n_het, N), the shape of hank_get_het_outputs' tangents: n_het = size(dagg, 2) up to length(ctx.outputs) and at most what
+# hank_set_het_outputs declared. Seeds as in hank_jvp_boundary!. Value and UCE (ctx.outputs[3], [4]) ride in the forward sweep, so
+# the boundary's seeds reach them; n_het <= 2 gives the bits of hank_jvp / hank_jvp_boundary! on the per-period launches.
+function hank_jvp_het!(dagg::Array{Float64,3}, ctx::HankCtx; dxhh::Union{Nothing,Array{Float64,3}} = nothing,
+                       dvalue_end::Union{Nothing,Array{Float64,3}} = nothing, dD_init::Union{Nothing,Array{Float64,3}} = nothing)
+    P, n_het, N = size(dagg)
+    @assert P == ctx.P && !(dxhh === nothing && dvalue_end === nothing && dD_init === nothing)
+    @assert dxhh === nothing || size(dxhh) == (length(ctx.hh_rows), P, N)
+    @assert all(s -> s === nothing || size(s) == (ctx.n_a, ctx.n_e, N), (dvalue_end, dD_init))
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve dxhh dvalue_end dD_init begin
+        _check(ctx.ptr, ccall((:hank_jvp_het, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}),
+                              ctx.ptr, Int32(n_het), ptr(dxhh), ptr(dvalue_end), ptr(dD_init), Int32(N), dagg))
+    end
+    return dagg
+end
+
+# hank_vjp_boundary! with cotangents on every heterogeneous output (hank_vjp_het!'s rule for n_het = size(agg_bar, 2)): the exact
+# transpose of hank_jvp_het!. xhh_bar equals hank_vjp_het!'s bit for bit. Returns (xhh_bar, value_end_bar, D_init_bar).
+function hank_vjp_het_boundary!(xhh_bar::Array{Float64,3}, value_end_bar::Union{Nothing,Array{Float64,3}}, D_init_bar::Union{Nothing,Array{Float64,3}},
+                                ctx::HankCtx, agg_bar::Array{Float64,3})
+    P, n_het, M = size(agg_bar)
+    @assert P == ctx.P && size(xhh_bar) == (length(ctx.hh_rows), P, M)
+    @assert all(s -> s === nothing || size(s) == (ctx.n_a, ctx.n_e, M), (value_end_bar, D_init_bar))
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve value_end_bar D_init_bar begin
+        _check(ctx.ptr, ccall((:hank_vjp_het_boundary, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                              ctx.ptr, Int32(n_het), agg_bar, Int32(M), xhh_bar, ptr(value_end_bar), ptr(D_init_bar)))
+    end
+    return xhh_bar, value_end_bar, D_init_bar
+end
+
 # the cotangent of the policy sequence of the last hank_vjp! / hank_vjp_het!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
 # (ForwardIteration.jl:412-416) for the policy variable when n_het = 1
 function hank_policy_cotangent_seq(ctx::HankCtx, M::Integer)
