@@ -122,6 +122,59 @@ def boundary_gradient(n_a=500, n_e=4, T=300, shock=0.01, seed=0):
             "max_abs_difference_over_max": float(np.max(np.abs(rev - fwd)) / np.max(np.abs(fwd)))}
 
 
+def ss_gradient(n_a=200, n_e=3, T=150, Z_end=1.03, seed=0):
+    """The chain from the transition path's merit function back to what moves the ENDING steady state, in the two-steady-state
+    scenario: the gradient of ½‖F(x)‖² at the Newton starting point with respect to the ending steady state's household prices
+    (r, w), through the terminal marginal value V_T = V_ss(r, w) (BackwardIteration.jl:85; SteadyState.jl:132-141). Reverse mode:
+    ONE hank_vjp_het_boundary (value_end_bar), one primal at the ending steady path, ONE hank_ss_vjp(value_bar = value_end_bar).
+    Printed beside a central difference in one random direction of (r, w): V_T re-solved by the device VFI at both ends, the
+    merit function re-evaluated with it (everything else of the boundary held fixed)."""
+    import dataclasses
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    from hank_amd.BackwardIteration import ensure_het_outputs
+    ov = {"T": T, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": n_e}},
+          "steady_states": {"ending": {"fixed": {"Z": Z_end}, "guesses": {"r": 0.04, "w": 1.0, "Y": 1.5, "KS": 3.5}}}}
+    m = h.build_model_from_yaml(str(ROOT / "examples" / "krusell_smith.yaml"), overrides=ov)
+    ss_i, ss_e = h.get_SteadyStates(m, vfi_tol=1e-13)
+    P = T - 1
+    Z = np.full(P, float(Z_end))
+    x0 = np.tile(np.array([ss_e.vars[k] for k in ("Y", "KS", "r", "w")]), P)
+    names = m.value_fn.household_inputs
+    xe = np.array([ss_e.vars[k] for k in names])
+
+    def merit(ss_end):
+        lin = h.LinearizedFunction(x0, {"Z": Z}, m, ss_i, ss_end)
+        return 0.5 * float(lin.Fx @ lin.Fx), lin
+
+    f0, lin = merit(ss_e)
+    lin._linearise_residuals()
+    hb, n_out = lin.hb, lin._n_out
+    ab = np.asarray(lin._Ragg.T @ lin.Fx).reshape(len(lin.het), P)
+    agg_bar = np.zeros((P, n_out, 1))
+    for j, o in enumerate(lin._out_idx):
+        agg_bar[:, o, 0] += ab[j]
+    ensure_het_outputs(hb, n_out)
+    t0 = time.perf_counter()
+    _, g_V, _ = hb.vjp_het_boundary(agg_bar, n_out, value_end=True, D_init=False)      # d merit / d V_T
+    hb.set_boundary(ss_e.value, ss_e.D)                                                   # the ending steady state's own record
+    hb.primal(np.tile(xe[:, None], (1, P)))
+    g_x, iters = hb.ss_vjp(value_bar=g_V, n_het=n_out)                                     # ... carried back to (r, w)
+    t_rev = time.perf_counter() - t0
+    d = np.random.default_rng(seed).standard_normal(len(names))
+    d /= np.linalg.norm(d)
+    hstep, f = 1e-6, []
+    for sgn in (1.0, -1.0):
+        v, _, _, _ = hb.vfi(ss_e.value, xe + sgn * hstep * d, 1e-13, 20_000)
+        f.append(merit(dataclasses.replace(ss_e, value=v))[0])
+    fd = (f[0] - f[1]) / (2 * hstep)
+    rev = float(g_x[:, 0] @ d)
+    return {"grid": f"{n_a}x{n_e}", "T": T, "shock": f"Z: 1 -> {Z_end} for good", "merit": f0, "household_prices": list(names),
+            "gradient_wrt_ending_prices_through_V_T": [float(v) for v in g_x[:, 0]], "ss_vjp_steps_nu_lambda": list(iters),
+            "reverse_s": round(t_rev, 5), "direction": [float(v) for v in d], "directional_derivative_reverse": rev,
+            "directional_derivative_central_difference": fd, "relative_difference": abs(rev - fd) / max(abs(fd), 1e-300)}
+
+
 def solve_permanent(n_a=200, n_e=3, T=150, Z_end=1.03, eps=1e-9, verbose=False):
     """The two-steady-state scenario of the reference YAML (`ending:` block, KrusellSmith.yaml:109-116): TFP moves
     to Z_end for good in period 1. The path starts from the initial steady state (KS_0, D_0 = ss_initial), the terminal
@@ -162,6 +215,7 @@ if __name__ == "__main__":
     ap.add_argument("--jacobian", default="toeplitz", choices=["toeplitz", "columns"])
     ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one hank_vjp against n_hh·P JVP columns")
     ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one hank_vjp_boundary, checked against two hank_jvp_boundary directions")
+    ap.add_argument("--ss-gradient", action="store_true", help="with --permanent: the gradient of ½‖F(x)‖² with respect to the ending steady state's household prices through V_T (hank_vjp_het_boundary, then hank_ss_vjp), beside a central difference in one random direction")
     a = ap.parse_args()
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -175,6 +229,8 @@ if __name__ == "__main__":
         out = boundary_gradient(a.n_a, a.n_e, a.T, a.shock)
     elif a.gradient:
         out = gradient(a.n_a, a.n_e, a.T, a.shock)
+    elif a.ss_gradient:
+        out = ss_gradient(a.n_a, a.n_e, a.T, a.permanent if a.permanent is not None else 1.03)
     elif a.permanent is not None:
         out = solve_permanent(a.n_a, a.n_e, a.T, a.permanent, verbose=a.verbose)[0]
     else:

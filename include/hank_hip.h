@@ -358,6 +358,54 @@ int hank_jvp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const d
 int hank_vjp_het_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar);
 int hank_vjp_het_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar);
 
+/* ---- derivatives through the steady state ------------------------------------------------------------
+ * Two of the block's three inputs are steady-state objects: V_T is the fixed point of the EGM step at the steady-state prices
+ * (the inner loop of get_xVals, SteadyState.jl:132-141) and D_0 the stationary distribution of the lottery that step induces
+ * (invariant_dist). The reference's price Newton differentiates both: find_ss calls ForwardDiff.jacobian(F, p)
+ * (SteadyState.jl:195) through a VFI carried on Duals (SteadyState.jl:132-141) and through invariant_dist's implicit-function
+ * tangent (ForwardIteration.jl:446-530: (I - Lambda) dD = dLambda D, 1'dD = 0). These two entries serve that surface, forward
+ * and transposed, from four fixed-point loops around ONE period of the launch family's sweep kernels (csrc/hank_ssdiff.h).
+ *
+ * Precondition (hank_fake_news's): the recorded primal is hank_primal (host-pointer form) at a constant path with the steady
+ * state as both boundaries; anything else — no primal, a path that varies over time, a device-pointer primal, a new boundary, a
+ * record whose first and last policy differ by more than 1e-6 of its scale — is HANK_ERR_NOT_READY. A record written by any
+ * kernel family serves. WHICH PERIOD IS READ: the distribution side and both transposed loops read period 0 of the record
+ * (D_ss = the boundary's initial distribution D_0, the lottery of the first policy, D_1 as the post-transition weights of the
+ * aggregates); the value loop reads the interpolation brackets of period 1 and the knots and prices of period 0 (one period of
+ * the backward tangent sweep spans two records). At a stationary record every period holds the same steady state.
+ *
+ * hank_ss_jvp == the partials ForwardDiff carries through the VFI (SteadyState.jl:132-141) and through invariant_dist
+ * (ForwardIteration.jl:446-530) inside find_ss's Jacobian (SteadyState.jl:195), N directions at once:
+ *   dxhh (n_hh, N) column-major: directions in the household prices.
+ *   1. dV <- B_V dV + B_x dx from dV = 0, until max|dV_new - dV| <= tol max|dV_new| in every column;
+ *   2. da' = P_V dV + P_x dx, the policy output of the converged step;
+ *   3. dD <- Lambda dD + (dLambda/da' da') D from dD = 0, same stopping rule, centred (dD -= D_ss 1'dD) at every check;
+ *   4. dagg_out (n_het, N): dY_o = sum f_o dD - sum f_c,o D da' + d_o . dx for the outputs of hank_get_het_outputs.
+ *   dvalue_out, dpolicy_out, dD_out (G, N) column-major, pt = e n_a + a: each may be NULL (not wanted).
+ * hank_ss_vjp == the transpose of that map (reverse mode through the steady state: what carries hank_vjp_het_boundary's
+ * value_end_bar / D_init_bar back to the prices that determine V_ss and D_ss; the reference differentiates find_ss forward only,
+ * SteadyState.jl:195, :132-141, ForwardIteration.jl:446-530), M columns at once:
+ *   agg_bar (n_het, M), value_bar (G, M) on V_ss, D_bar (G, M) on D_ss: each may be NULL (zero); all three NULL is
+ *   HANK_ERR_BAD_ARG. xhh_bar (n_hh, M) column-major. <agg_bar, dagg> + <value_bar, dV> + <D_bar, dD> = <xhh_bar, dx>.
+ * n_het follows hank_vjp_het's rule (above the family's count HANK_ERR_BAD_ARG, above the declared count HANK_ERR_NOT_READY).
+ * Not converging is not an error (as in hank_vfi): HANK_OK with iters_out[k] == max_iter and the last increment ratio in
+ * resid_out[k]; k = 0 the value (nu) loop, k = 1 the distribution (lambda) loop. The loops are device-resident: the stop word
+ * comes back once per chunk of 64 steps. Both calls leave alone the record's sweeps, the current tangent batch, the current
+ * cotangent batch, the primal memo and the schedule; their workspaces live for the call. Like the other readers of a record they
+ * may first complete it with what its writer left to be built on demand — the per-target segment records and the per-source
+ * {w, ig D} records (hank_info out[7] counts that build), Sweep B's bracket segments, the extra outputs' f, f_c and sums — none of
+ * which changes what any other entry computes. No atomics: the same record and inputs give the same bits. The _dev forms take
+ * device pointers on the context's stream and synchronise with the host for the precondition's look at the recorded policy, for
+ * the stop words, and once at the end (the workspaces go with the call). */
+int hank_ss_jvp(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double tol, int32_t max_iter, double *dvalue_out, double *dpolicy_out,
+                double *dD_out, double *dagg_out, int32_t iters_out[2], double resid_out[2]);
+int hank_ss_jvp_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, int32_t N, double tol, int32_t max_iter, double *d_dvalue_out, double *d_dpolicy_out,
+                    double *d_dD_out, double *d_dagg_out, int32_t iters_out[2], double resid_out[2]);
+int hank_ss_vjp(hank_ctx *ctx, int32_t n_het, const double *agg_bar, const double *value_bar, const double *D_bar, int32_t M, double tol, int32_t max_iter,
+                double *xhh_bar, int32_t iters_out[2], double resid_out[2]);
+int hank_ss_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, const double *d_value_bar, const double *d_D_bar, int32_t M, double tol,
+                    int32_t max_iter, double *d_xhh_bar, int32_t iters_out[2], double resid_out[2]);
+
 /* ---- measurement hooks (bench.py) ---------------------------------------------------------------
  * Device time, in milliseconds, of the sweeps of the most recent hank_primal[_dev]/hank_jvp[_dev],
  * from HIP events recorded on the context's stream around each sweep:
@@ -369,6 +417,12 @@ int hank_last_timings(hank_ctx *ctx, double out_ms[6], int32_t launches[6]);
  * ForwardIteration.jl:339-420), out[1] Sweep B (the reverse of the EGM sweep, with the reduction of xhh_bar); -1 before the
  * first hank_vjp. Valid after hank_sync. */
 int hank_last_vjp_timings(hank_ctx *ctx, double out_ms[2], int32_t launches[2]);
+
+/* Time, in milliseconds, of the two loops of the most recent hank_ss_jvp[_dev] / hank_ss_vjp[_dev], from HIP events recorded on
+ * the context's stream before a loop's first step and behind the synchronisation that fetched its last stop word (the host's
+ * round trip per chunk of steps is inside): out[0] the value (nu) loop, out[1] the distribution
+ * (lambda) loop, in the order of iters_out; -1 before the first call. */
+int hank_last_ss_timings(hank_ctx *ctx, double out_ms[2]);
 
 /* Counters of this context (tests and scripts): out[0] sweep kernels launched by the persistent schedule, out[1] tangent
  * workspaces allocated (a change of batch width N re-uses a cached workspace: a small most-recently-used cache, 3 deep),

@@ -76,6 +76,7 @@ class SSAssembler:
         # the reference stops the VFI at compspec.ε; a tighter default makes ss.value a clean fixed point
         self.vfi_tol = vfi_tol if vfi_tol is not None else min(model.compspec.ε, 1e-11)
         self._value_warm = None
+        self._last_xvals, self._last_p = None, None
 
     def get_xVals(self, p_vec) -> Tuple[np.ndarray, np.ndarray, dict]:
         """full length-n_v aggregate vector for price iterate p_vec + converged marginal value
@@ -125,7 +126,9 @@ class SSAssembler:
         self._D_warm = D
         for k in vars_of_type(model, "heterogeneous"):
             xv[k] = float(res[k].reshape(-1, order="F") @ D)
-        return np.array([xv[k] for k in self.all_keys]), res["Value"], res
+        out = np.array([xv[k] for k in self.all_keys]), res["Value"], res
+        self._last_xvals, self._last_p = out, np.array(p_vec, dtype=np.float64, copy=True)      # (implicit_price_jacobian reads them)
+        return out
 
     def __call__(self, p_vec) -> np.ndarray:
         cs = self.model.compspec
@@ -135,13 +138,68 @@ class SSAssembler:
         return np.tile(xVals[:, None], (1, T_pad))
 
 
+def implicit_price_jacobian(asm: SSAssembler, p_vec) -> np.ndarray:
+    """dF/dp at the price iterate whose steady state `asm` has just solved (its last get_xVals), without another fixed point:
+    what ForwardDiff.jacobian(F, p) (SteadyState.jl:195) carries through the VFI (:132-141) and invariant_dist
+    (ForwardIteration.jl:446-530). One hank_primal at the constant path with the iterate's (V, D) as both boundaries, one
+    hank_ss_jvp over the free household inputs (d aggregates / d prices through V and D), composed with the residual layer's own
+    partials — central differences of `Residuals` alone, which is closed-form host code."""
+    from .BackwardIteration import ensure_het_outputs, het_output_count, household_block
+    model = asm.model
+    vf = model.value_fn
+    het_keys = vars_of_type(model, "heterogeneous")
+    outs = tuple(vf.outputs)
+    missing = [k for k in het_keys if k not in outs]
+    if missing:
+        raise ValueError(f"price_jacobian='implicit': the device block does not serve the heterogeneous variables {missing}")
+    xVals, value, _ = asm._last_xvals
+    xv = dict(zip(asm.all_keys, xVals))
+    hb = household_block(model)
+    n_out = het_output_count(model, het_keys)
+    ensure_het_outputs(hb, n_out)
+    hb.set_boundary(value, asm._D_warm)
+    hb.primal(np.tile(np.array([xv[k] for k in vf.household_inputs])[:, None], (1, hb.P)))
+    dx = np.zeros((hb.n_hh, asm.n_free))
+    for k, name in enumerate(vf.household_inputs):
+        if name in asm.free_keys:
+            dx[k, asm.free_keys.index(name)] = 1.0
+    dagg = hb.ss_jvp(dx, n_het=n_out)[0]                              # (n_out, n_free)
+    n_v = len(asm.all_keys)
+    dX = np.zeros((n_v, asm.n_free))                                  # d xVals / d p
+    for i, k in enumerate(asm.all_keys):
+        if k in asm.free_keys:
+            dX[i, asm.free_keys.index(k)] = 1.0
+        elif k in het_keys:
+            dX[i] = dagg[outs.index(k)]
+    cs = model.compspec
+    T_pad = 1 + cs.max_lag + cs.max_lead
+    X = np.tile(np.asarray(xVals, dtype=np.float64)[:, None], (1, T_pad))
+    R = []
+    for i in range(n_v):
+        h = 1e-6 * max(1.0, abs(xVals[i]))
+        Xp, Xm = X.copy(), X.copy()
+        Xp[i] += h
+        Xm[i] -= h
+        R.append((Residuals(Xp, model) - Residuals(Xm, model)) / (2 * h))
+    return np.stack(R, axis=1) @ dX
+
+
 @host_algebra
-def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vfi_tol=None, vfi: str = "auto") -> SteadyState:
-    """Newton–Raphson on the free endogenous variables with step halving (SteadyState.jl:184-233)."""
+def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vfi_tol=None, vfi: str = "auto",
+            price_jacobian: str = "fd") -> SteadyState:
+    """Newton–Raphson on the free endogenous variables with step halving (SteadyState.jl:184-233). price_jacobian: "fd" — forward
+    differences, one more steady state per free price — or "implicit" — the derivatives through the steady state from the device
+    (`implicit_price_jacobian`: no further fixed point; needs the device VFI, no fallback)."""
     from .NewtonRaphson import warm_linear_solver
     from .GeneralStructures import vars_of_type
+    if price_jacobian not in ("fd", "implicit"):
+        raise ValueError(f"price_jacobian must be 'fd' or 'implicit' (got {price_jacobian!r})")
     warm_linear_solver(len(vars_of_type(model, "endogenous")) * (model.compspec.T - 1))      # (library start-up behind this solve)
     asm = SSAssembler(model, ss_spec, vfi_tol, vfi)
+    if price_jacobian == "implicit" and not asm.vfi_on_device:
+        raise ValueError("price_jacobian='implicit' needs the device (hank_ss_jvp at the record of hank_primal) and the device VFI: "
+                         "there is no host form of it" + (" (vfi='host' was asked for)" if vfi == "host" else ""))
+    asm.newton_iterations = 0
 
     def F(p):
         return Residuals(asm(p), model)
@@ -163,11 +221,16 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
                 print(f"  [{label}] Iteration {it}: residual norm = {np.linalg.norm(z)}")
             asm._value_warm = getattr(asm, "_last_value", None)   # warm-start the inner VFI
             J = np.empty((len(z), asm.n_free))
-            for j in range(asm.n_free):
-                h = 1e-6 * max(1.0, abs(p[j]))
-                q = p.copy()
-                q[j] += h
-                J[:, j] = (F(q) - z) / h
+            if price_jacobian == "implicit":
+                if asm._last_p is None or not np.array_equal(asm._last_p, p):      # (a halved step's last evaluation was refused)
+                    F(p)
+                J = implicit_price_jacobian(asm, p)
+            else:
+                for j in range(asm.n_free):
+                    h = 1e-6 * max(1.0, abs(p[j]))
+                    q = p.copy()
+                    q[j] += h
+                    J[:, j] = (F(q) - z) / h
             step = np.linalg.solve(J, z)
             η, z_norm = 1.0, np.linalg.norm(z)
             p_new = p - η * step
@@ -180,6 +243,7 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
                 z_new = safe_eval(p_new)
             p, z = p_new, z_new
             it += 1
+            asm.newton_iterations = it
     if it == max_iter:
         import warnings
         warnings.warn(f"find_ss [{label}]: did not converge in {max_iter} iterations (residual norm: {np.linalg.norm(z)})")
@@ -208,12 +272,16 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
         D, _ = household_block(model).stationary_dist(policies[asm.endog_dim.policy_var], getattr(asm, "_D_warm", None))
     else:
         D = invariant_dist(Λss.T, D0=getattr(asm, "_D_warm", None))
-    return SteadyState(vars_, policies, Λss, D, ss_value)
+    ss = SteadyState(vars_, policies, Λss, D, ss_value)
+    # how the solve went (scripts and tests compare the two price Jacobians): the assembler's counters at the end
+    ss.solve_info = {"price_jacobian": price_jacobian, "vfi_steps": asm.vfi_steps, "newton_iterations": asm.newton_iterations,
+                     "residual_norm": float(np.linalg.norm(z))}
+    return ss
 
 
-def get_SteadyStates(model: SequenceModel, verbose: bool = False, vfi_tol=None, vfi: str = "auto"):
-    """both steady states (SteadyState.jl:245-259); one solve when the specs are the same object."""
-    ss_initial = find_ss(model, model.ss_initial, "initial", verbose, vfi_tol, vfi)
+def get_SteadyStates(model: SequenceModel, verbose: bool = False, vfi_tol=None, vfi: str = "auto", price_jacobian: str = "fd"):
+    """both steady states (SteadyState.jl:245-259); one solve when the specs are the same object. price_jacobian: see find_ss."""
+    ss_initial = find_ss(model, model.ss_initial, "initial", verbose, vfi_tol, vfi, price_jacobian)
     if model.ss_initial is model.ss_ending:
         return ss_initial, ss_initial
-    return ss_initial, find_ss(model, model.ss_ending, "ending", verbose, vfi_tol, vfi)
+    return ss_initial, find_ss(model, model.ss_ending, "ending", verbose, vfi_tol, vfi, price_jacobian)

@@ -28,6 +28,8 @@
 //       pbar_t[j,e] -= sum_o ybx_o,t f_c,o,t[j,e] D_t[j,e]         (next to (yb0 - yb1) D_t)
 // and the household inputs' cotangents directly (k_adj_hx_out, after Sweep B): xbar_r += ybx_o,t (Sa + Sr), xbar_w += ybx_o,t Sz,
 // xbar_tr += ybx_o,t S1. Sweep B is the same: pbar carries everything it reads.
+// NOTE: k_ss_lam and k_ss_nu (hank_ssdiff.h) restate the steps of k_adj_dist and k_adj_egm at one fixed period with their own
+// prologue and epilogue: a change to the arithmetic of either kernel here has to be made there as well.
 #pragma once
 #include "hank_hetx.h"
 #include "hank_kernels.h"

@@ -10,6 +10,7 @@
 #include "hank_hetx.h"
 #include "hank_adjoint.h"
 #include "hank_boundary.h"
+#include "hank_ssdiff_launch.h"
 #include "../../include/hank_hip.h"
 
 #include <cstdarg>
@@ -288,6 +289,8 @@ struct hank_ctx {
     bool stationary = false;                          // the recorded primal is the constant steady-state path with the steady state as both boundaries (hank_fake_news)
     std::vector<double> h_ss_value, h_ss_D;           // the boundary as the host handed it in (stationarity check)
     hipEvent_t ev_stream = nullptr;
+    hipEvent_t ss_ev[2][2] = {};                      // begin / end of the two loops of the last hank_ss_jvp / hank_ss_vjp (hank_last_ss_timings), created on first use
+    bool ss_timed[2] = {false, false};
     char errmsg[512] = {0};
 };
 
@@ -1471,6 +1474,7 @@ int hank_destroy(hank_ctx *ctx) {
     if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->ev_stream) (void)hipEventDestroy(ctx->ev_stream);
+    for (auto &pair : ctx->ss_ev) for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_side) (void)hipEventDestroy(ctx->ev_side);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
@@ -2045,6 +2049,30 @@ static int ensure_fn(hank_ctx *ctx, int n_het) {
     return HANK_OK;
 }
 
+// "Is the record stationary?" — the one check of every entry that reads the record as the steady state's linear operators
+// (hank_fake_news[_het], hank_ss_jvp, hank_ss_vjp): the recorded primal is hank_primal (host-pointer form) at a constant path, and
+// the policy of its first period equals the policy of its last (a constant path that is not the steady state of the boundary
+// drifts; 1e-6 of the policy's scale is far above a converged value iteration's 1e-11). Synchronises the stream.
+static int stationary_record(hank_ctx *ctx, const char *name) {
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before %s", name);
+    if (!ctx->stationary)
+        return fail(ctx, HANK_ERR_NOT_READY, "%s needs the recorded primal to be hank_primal at a CONSTANT path (the steady state; SteadyStateJacobian.jl:53-57): "
+                    "the last primal was recorded at a path that varies over time, or through a device-pointer entry", name);
+    const int P = ctx->c.P, G = ctx->c.G;
+    hipStream_t s = ctx->stream;
+    std::vector<double> p0((size_t)G), p1((size_t)G);
+    HIPC(ctx, join_side(ctx));
+    HIPC(ctx, hipMemcpyAsync(p0.data(), ctx->R.pol, sizeof(double) * G, hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipMemcpyAsync(p1.data(), ctx->R.pol + (size_t)(P - 1) * G, sizeof(double) * G, hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));
+    double scale = 0.0, diff = 0.0;
+    for (int k = 0; k < G; k++) { scale = std::max(scale, fabs(p1[k])); diff = std::max(diff, fabs(p0[k] - p1[k])); }
+    if (!(diff <= 1e-6 * std::max(scale, 1e-300)))
+        return fail(ctx, HANK_ERR_NOT_READY, "%s: the recorded primal is not stationary (policy of period 1 and of period %d differ by %.3g): "
+                    "it needs hank_primal at the steady state with the steady state as both boundaries", name, P, diff);
+    return HANK_OK;
+}
+
 // The household block's sequence-space Jacobian at a stationary primal from its Toeplitz structure (hank_jacobian.h):
 // F (P, P, n_hh[, n_het]) and Dv (P, n_hh[, n_het]), column-major. Requires hank_primal at the constant steady-state path
 // with the steady state as both boundaries (what getSteadyStateJacobian builds, SteadyStateJacobian.jl:53-57).
@@ -2052,26 +2080,10 @@ static int ensure_fn(hank_ctx *ctx, int n_het) {
 // (outputs 0 .. n_het-1 of hank_get_het_outputs; output 0 is the same arithmetic as n_het == 0, bit for bit).
 static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
     const char *name = n_het ? "hank_fake_news_het" : "hank_fake_news";
-    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before %s", name);
-    if (!ctx->stationary)
-        return fail(ctx, HANK_ERR_NOT_READY, "%s needs the recorded primal to be hank_primal at a CONSTANT path (the steady state; SteadyStateJacobian.jl:53-57): "
-                    "the last primal was recorded at a path that varies over time, or through a device-pointer entry", name);
+    { const int nrc = stationary_record(ctx, name); if (nrc) return nrc; }
     const Consts &c = ctx->c;
     const int P = c.P, G = c.G, N = c.n_hh, NP = P * N, S = 16, nh = n_het ? n_het : 1;
     hipStream_t s = ctx->stream;
-    {   // ... and to be stationary: the policy of the first period equals the policy of the last (a constant path that is not the
-        // steady state of the boundary drifts; 1e-6 of the policy's scale is far above a converged value iteration's 1e-11)
-        std::vector<double> p0((size_t)G), p1((size_t)G);
-        HIPC(ctx, join_side(ctx));
-        HIPC(ctx, hipMemcpyAsync(p0.data(), ctx->R.pol, sizeof(double) * G, hipMemcpyDeviceToHost, s));
-        HIPC(ctx, hipMemcpyAsync(p1.data(), ctx->R.pol + (size_t)(P - 1) * G, sizeof(double) * G, hipMemcpyDeviceToHost, s));
-        HIPC(ctx, hipStreamSynchronize(s));
-        double scale = 0.0, diff = 0.0;
-        for (int k = 0; k < G; k++) { scale = std::max(scale, fabs(p1[k])); diff = std::max(diff, fabs(p0[k] - p1[k])); }
-        if (!(diff <= 1e-6 * std::max(scale, 1e-300)))
-            return fail(ctx, HANK_ERR_NOT_READY, "%s: the recorded primal is not stationary (policy of period 1 and of period %d differ by %.3g): "
-                        "it needs hank_primal at the steady state with the steady state as both boundaries", name, P, diff);
-    }
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
     // 1. n_hh backward tangent sweeps (one batch) seeded at the last period: every lag of the policy response
@@ -3082,4 +3094,250 @@ int hank_forward_step_dual(hank_ctx *ctx, const double *policy, const double *dp
     return granular_forward(ctx, policy, dpolicy, D_prev, dD_prev, N, D_out, dD_out, agg_out, dagg_out);
 }
 
+}  // extern "C"
+
+// ---- derivatives through the steady state (hank_ssdiff.h) ------------------------------------------------
+// The loop driver of all four fixed points, in the manner of hank_vfi's launch branch: a chunk of steps is enqueued (each step =
+// the step kernel + the one-block check kernel), the stop word comes back once per chunk, and the steps enqueued behind a set stop
+// word leave at once, so the state is the converged step's. step(k): the k-th step, 0-based (it reads buffer k & 1 of a ping-pong
+// state and writes (k + 1) & 1: the final state sits in buffer iters & 1). Not converging is not an error: iters == max_iter.
+template <typename Step>
+static int ss_loop(hank_ctx *ctx, SsCtl *d_ctl, int max_iter, Step step, SsCtl *out, int which) {
+    hipStream_t s = ctx->stream;
+    SsCtl h{};
+    ctx->ss_timed[which] = false;
+    for (hipEvent_t &e : ctx->ss_ev[which]) if (!e) HIPC(ctx, hipEventCreate(&e));
+    HIPC(ctx, hipEventRecord(ctx->ss_ev[which][0], s));      // (no host synchronisation for the timing: events on the stream)
+    HIPC(ctx, hipMemsetAsync(d_ctl, 0, sizeof(SsCtl), s));
+    int done = 0;
+    const int chunk = 64;
+    while (!h.stop && done < max_iter) {
+        const int n = std::min(chunk, max_iter - done);
+        for (int k = 0; k < n; k++) step(done + k);
+        done += n;
+        HIPC(ctx, hipGetLastError());
+        HIPC(ctx, hipMemcpyAsync(&h, d_ctl, sizeof(SsCtl), hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipStreamSynchronize(s));
+    }
+    HIPC(ctx, hipEventRecord(ctx->ss_ev[which][1], s));
+    ctx->ss_timed[which] = true;
+    *out = h;
+    return HANK_OK;
+}
+
+// what both entries ask of their arguments and of the context, in hank_fake_news's order: the count of outputs (hank_vjp_het's
+// rule), then the stationary record
+static int ss_ready(hank_ctx *ctx, const char *name, int n_het, bool rest_ok) {
+    int rc = het_count_ok(ctx, name, n_het, true, rest_ok);
+    if (rc) return rc;
+    {   // the launchers' unit names the argument structs through a namespace of its own (hank_ssdiff_launch.h): same layout, or nothing runs
+        size_t theirs[5];
+        hankss_layout(theirs);
+        const size_t ours[5] = {sizeof(Consts), sizeof(Record), sizeof(TanGeom), sizeof(AdjGeom), sizeof(SsCtl)};
+        if (memcmp(ours, theirs, sizeof(ours)) != 0) return fail(ctx, HANK_ERR_LAUNCH, "%s: hank_ssdiff.hip was built with other argument structs than hank_hip.hip", name);
+    }
+    rc = stationary_record(ctx, name);
+    if (rc) return rc;
+    if (ctx->c.P < 2) return fail(ctx, HANK_ERR_BAD_ARG, "%s needs a record of at least two periods (T >= 3)", name);
+    return HANK_OK;
+}
+
+static int ss_jvp(hank_ctx *ctx, int n_het, const double *dxhh, int N, double tol, int max_iter, double *dvalue_out, double *dpolicy_out, double *dD_out,
+                  double *dagg_out, int32_t *iters_out, double *resid_out, bool dev) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    int rc = ss_ready(ctx, "hank_ss_jvp", n_het, dxhh && dagg_out && iters_out && resid_out && N >= 1 && max_iter >= 1 && tol >= 0.0);
+    if (rc) return rc;
+    const Consts &c = ctx->c;
+    const size_t G = c.G, GV = (size_t)(c.n_a + KV) * c.n_e, NN = (size_t)N;
+    const int NX = n_het > 2 ? n_het - 2 : 0, V = (N % 2 == 0) ? 2 : 1;
+    hipStream_t s = ctx->stream;
+    TanGeom g{};
+    {
+        const int NV = N / V;
+        int NC = 1, lg = 0;
+        while (NC < NV && NC < 64) { NC <<= 1; lg++; }
+        g.N = NV; g.NC = NC; g.lgNC = lg; g.nbx = (c.n_a + 64 / NC - 1) / (64 / NC); g.ss = 0;
+    }
+    TanGeom gf = g;
+    gf.ss = g.NC >= 16 ? 1 : 0;
+    const int RGB = 2, RGF = gf.ss ? 2 : 1;
+    const unsigned nbt = (g.nbx + RGB - 1) / RGB, nbf = (gf.nbx + RGF - 1) / RGF + KV, ny = (g.N + g.NC - 1) / g.NC;
+    { const int src = ensure_seg(ctx); if (src) return src; }
+    { const int src = ensure_lwg(ctx); if (src) return src; }
+    HIPC(ctx, join_side(ctx));
+    if (NX > 0) { rc = ensure_hx_record(ctx); if (rc) return rc; }
+    Scratch sc;
+    double *dx, *dxr, *dxw, *dxt, *ds[2], *dV, *dpol, *dD[2], *aggpart, *hxparts, *partsB, *partsF, *sig, *out, *expV = nullptr, *expP = nullptr, *expD = nullptr;
+    SsCtl *ctl;
+    HIPC(ctx, sc.alloc(&dx, (size_t)c.n_hh * NN)); HIPC(ctx, sc.alloc(&dxr, 2 * NN)); HIPC(ctx, sc.alloc(&dxw, 2 * NN)); HIPC(ctx, sc.alloc(&dxt, 2 * NN));
+    HIPC(ctx, sc.alloc(&ds[0], G * NN)); HIPC(ctx, sc.alloc(&ds[1], G * NN)); HIPC(ctx, sc.alloc(&dV, G * NN)); HIPC(ctx, sc.alloc(&dpol, 2 * G * NN));
+    HIPC(ctx, sc.alloc(&dD[0], GV * NN)); HIPC(ctx, sc.alloc(&dD[1], GV * NN)); HIPC(ctx, sc.alloc(&aggpart, 2 * (size_t)nbf * NN));
+    HIPC(ctx, sc.alloc(&hxparts, (size_t)nbf * (NX ? NX : 1) * NN)); HIPC(ctx, sc.alloc(&partsB, 2 * (size_t)nbt * NN));
+    HIPC(ctx, sc.alloc(&partsF, 3 * (size_t)nbf * NN)); HIPC(ctx, sc.alloc(&sig, NN)); HIPC(ctx, sc.alloc(&out, (size_t)n_het * NN));
+    HIPC(ctx, sc.alloc(&ctl, 2));
+    if (!dev && dvalue_out) HIPC(ctx, sc.alloc(&expV, G * NN));
+    if (!dev && dpolicy_out) HIPC(ctx, sc.alloc(&expP, G * NN));
+    if (!dev && dD_out) HIPC(ctx, sc.alloc(&expD, G * NN));
+    HIPC(ctx, hipMemcpyAsync(dx, dxhh, sizeof(double) * c.n_hh * NN, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemsetAsync(ds[0], 0, sizeof(double) * G * NN, s));
+    HIPC(ctx, hipMemsetAsync(dV, 0, sizeof(double) * G * NN, s));
+    HIPC(ctx, hipMemsetAsync(dD[0], 0, sizeof(double) * GV * NN, s));
+    hankss_launch_in(s, dx, c.n_hh, N, dxr, dxw, dxt);
+    SsCtl hv{}, hd{};
+    // 1. dV <- B_V dV + B_x dx; the converged step leaves dV and da' (row 1 of dpol)
+    rc = ss_loop(ctx, &ctl[0], max_iter, [&](int k) {
+        hankss_launch_back(s, V, c, ctx->R, ctx->d_xhh.get(), dxr, dxw, dxt, g, nbt, ny, ds[k & 1], ds[(k + 1) & 1], dpol, dV, partsB, &ctl[0]);
+        hankss_launch_check(s, partsB, (int)nbt, 2, N, tol, &ctl[0], nullptr);
+    }, &hv, 0);
+    if (rc) return rc;
+    // 2. dD <- Lambda dD + (dLambda da') D with that da'; the last step's reductions are dY's
+    const double *dap = dpol + G * NN;
+    rc = ss_loop(ctx, &ctl[1], max_iter, [&](int k) {
+        hankss_launch_fwd(s, V, NX, c, ctx->R, gf, nbf, ny, dD[k & 1], dD[(k + 1) & 1], dap, aggpart, ctx->hx.f.get(), ctx->hx.fc.get(), hxparts, partsF, &ctl[1]);
+        hankss_launch_check_dist(s, c, ctx->R.Dseq, partsF, (int)nbf, N, tol, dD[(k + 1) & 1], dD[k & 1], sig, &ctl[1]);
+    }, &hd, 1);
+    if (rc) return rc;
+    const double *dDfin = dD[hd.iters & 1];
+    hankss_launch_jvp_out(s, c.P, c.n_hh, n_het, N, (int)nbf, ctx->d_xhh.get(), dx, ctx->d_agg.get(), ctx->d_zd.get(), ctx->hx.S.get(), aggpart, hxparts, out);
+    const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e);
+    const hipMemcpyKind back = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPC(ctx, hipMemcpyAsync(dagg_out, out, sizeof(double) * n_het * NN, back, s));
+    // the exports (G, N) column-major; the host form stages each in a buffer of its own
+    if (dvalue_out) {
+        hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, dV, c.n_a, c.n_e, N, dev ? dvalue_out : expV);
+        if (!dev) HIPC(ctx, hipMemcpyAsync(dvalue_out, expV, sizeof(double) * G * NN, hipMemcpyDeviceToHost, s));
+    }
+    if (dpolicy_out) {
+        hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, dap, c.n_a, c.n_e, N, dev ? dpolicy_out : expP);
+        if (!dev) HIPC(ctx, hipMemcpyAsync(dpolicy_out, expP, sizeof(double) * G * NN, hipMemcpyDeviceToHost, s));
+    }
+    if (dD_out) {
+        hankss_launch_dist_out(s, dDfin, c.n_a, c.n_e, N, dev ? dD_out : expD);
+        if (!dev) HIPC(ctx, hipMemcpyAsync(dD_out, expD, sizeof(double) * G * NN, hipMemcpyDeviceToHost, s));
+    }
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, hipStreamSynchronize(s));      // (the call's buffers go with it)
+    iters_out[0] = hv.iters; iters_out[1] = hd.iters;
+    resid_out[0] = hv.resid; resid_out[1] = hd.resid;
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
+static int ss_vjp_loops(hank_ctx *ctx, int V, const AdjGeom &g, int NX, double tol, int max_iter, double *e[2], double *lam, double *pbar, double *nu[2], const double *vbar,
+                        const double *yb, double *partS, double *partM, double *parts, double *cen, SsCtl *ctl, SsCtl *hn, SsCtl *hl) {
+    const Consts &c = ctx->c;
+    hipStream_t s = ctx->stream;
+    const int M = g.MV * V;
+    const size_t ldsA = adj_lds_dist(c, g, V), ldsB = adj_lds_egm(c, g, V), PG = (size_t)c.P * c.G;
+    // 1. lam = sum_u (Lambda')^u g, re-centred every step (dev knob HANK_SS_RECENTRE=0: centred once, at the start — the series of the
+    // plain formula, which stalls where D_ss is stationary only to the caller's accuracy: scripts/dev_ss_diff.py shows it)
+    const char *rce = getenv("HANK_SS_RECENTRE");
+    const bool recentre = !(rce && atoi(rce) == 0);
+    int rc = ss_loop(ctx, &ctl[1], max_iter, [&](int k) {
+        hankss_launch_lam(s, V, false, ldsA, c, ctx->R, g, e[k & 1], e[(k + 1) & 1], lam, parts, &ctl[1], cen, nullptr, 0, nullptr, PG, nullptr);
+        hankss_launch_check(s, parts, g.nb, 3, M, tol, &ctl[1], recentre ? cen : nullptr);
+    }, hl, 1);
+    if (rc) return rc;
+    // 2. pbar from lam (Sweep A's pbar line at one period)
+    hankss_launch_lam(s, V, true, ldsA, c, ctx->R, g, lam, nullptr, nullptr, nullptr, nullptr, nullptr, yb, NX, ctx->hx.fc.get(), PG, pbar);
+    // 3. nu <- B_V' nu + (P_V' pbar + Vbar)
+    return ss_loop(ctx, &ctl[0], max_iter, [&](int k) {
+        hankss_launch_nu(s, V, ldsB, c, ctx->R, g, ctx->d_adj_sb.get(), nu[k & 1], nu[(k + 1) & 1], pbar, vbar, partS, partM, parts, &ctl[0]);
+        hankss_launch_check(s, parts, g.nb, 2, M, tol, &ctl[0], nullptr);
+    }, hn, 0);
+}
+
+static int ss_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, const double *value_bar, const double *D_bar, int M, double tol, int max_iter, double *xhh_bar,
+                  int32_t *iters_out, double *resid_out, bool dev) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    if (!agg_bar && !value_bar && !D_bar) return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_vjp: agg_bar, value_bar and D_bar are all NULL: nothing to pull back");
+    int rc = ss_ready(ctx, "hank_ss_vjp", n_het, xhh_bar && iters_out && resid_out && M >= 1 && max_iter >= 1 && tol >= 0.0);
+    if (rc) return rc;
+    const Consts &c = ctx->c;
+    const size_t G = c.G, MM = (size_t)M;
+    const int NX = n_het > 2 ? n_het - 2 : 0, V = (M % 2 == 0) ? 2 : 1;
+    hipStream_t s = ctx->stream;
+    AdjGeom g{};
+    g.MV = M / V; g.NC = 1; g.lgNC = 0;
+    while (g.NC < g.MV && g.NC < 16) { g.NC <<= 1; g.lgNC++; }
+    g.R = std::max(64 / g.NC, 8);
+    g.nb = (c.n_a + g.R - 1) / g.R;
+    if (adj_lds_dist(c, g, V) > ctx->lds_max || adj_lds_egm(c, g, V) > ctx->lds_max)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_vjp: n_e=%d needs more LDS per workgroup than the device has", c.n_e);
+    if (!ctx->d_adj_sb) HIPC(ctx, ctx->d_adj_sb.alloc((size_t)c.P * c.n_e * ((size_t)c.n_a + 1)));
+    HIPC(ctx, join_side(ctx));
+    rc = ensure_adj_seg(ctx);
+    if (rc) return rc;
+    if (NX > 0) { rc = ensure_hx_record(ctx); if (rc) return rc; }
+    Scratch sc;
+    double *ybar = nullptr, *stage = nullptr, *yb, *e[2], *lam, *pbar, *nu[2], *vbar = nullptr, *partS, *partM, *parts, *xbar, *cen;
+    SsCtl *ctl;
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIPC(ctx, sc.alloc(&yb, 4 * MM)); HIPC(ctx, sc.alloc(&e[0], G * MM)); HIPC(ctx, sc.alloc(&e[1], G * MM)); HIPC(ctx, sc.alloc(&lam, G * MM));
+    HIPC(ctx, sc.alloc(&pbar, G * MM)); HIPC(ctx, sc.alloc(&nu[0], G * MM)); HIPC(ctx, sc.alloc(&nu[1], G * MM));
+    HIPC(ctx, sc.alloc(&partS, 3 * (size_t)g.nb * MM)); HIPC(ctx, sc.alloc(&partM, 3 * (size_t)g.nb * MM)); HIPC(ctx, sc.alloc(&parts, 3 * (size_t)g.nb * MM)); HIPC(ctx, sc.alloc(&cen, MM));
+    HIPC(ctx, sc.alloc(&xbar, (size_t)c.n_hh * MM)); HIPC(ctx, sc.alloc(&ctl, 2));
+    if (agg_bar) {
+        HIPC(ctx, sc.alloc(&ybar, (size_t)n_het * MM));
+        HIPC(ctx, hipMemcpyAsync(ybar, agg_bar, sizeof(double) * n_het * MM, in, s));
+    }
+    hankss_launch_y_in(s, ybar, n_het, M, yb);
+    const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((M + BND_T - 1) / BND_T), (unsigned)c.n_e);
+    if (value_bar || D_bar) HIPC(ctx, sc.alloc(&stage, G * MM));
+    if (value_bar) {
+        HIPC(ctx, sc.alloc(&vbar, G * MM));
+        HIPC(ctx, hipMemcpyAsync(stage, value_bar, sizeof(double) * G * MM, in, s));
+        hipLaunchKernelGGL(k_bnd_in, tgrd, tblk, 0, s, (const double *)stage, c.n_a, c.n_e, c.n_a, M, vbar);
+    }
+    if (D_bar) HIPC(ctx, hipMemcpyAsync(stage, D_bar, sizeof(double) * G * MM, in, s));      // (behind k_bnd_in on the stream)
+    hankss_launch_cot_in(s, c, ctx->R, ctx->d_xhh.get(), NX, yb, D_bar ? stage : nullptr, ctx->hx.f.get(), (size_t)c.P * G, M, e[0], lam);
+    HIPC(ctx, hipMemsetAsync(nu[0], 0, sizeof(double) * G * MM, s));
+    HIPC(ctx, hipMemsetAsync(cen, 0, sizeof(double) * MM, s));      // (k_ss_cot_in has centred e_0)
+    SsCtl hn{}, hl{};
+    rc = ss_vjp_loops(ctx, V, g, NX, tol, max_iter, e, lam, pbar, nu, vbar, yb, partS, partM, parts, cen, ctl, &hn, &hl);
+    if (rc) return rc;
+    hankss_launch_xbar(s, c.P, c.n_hh, M, g.nb, NX, ctx->d_xhh.get(), partS, partM, yb, ctx->d_agg.get(), ctx->d_zd.get(), ctx->hx.S.get(), xbar);
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, hipMemcpyAsync(xhh_bar, xbar, sizeof(double) * c.n_hh * MM, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));
+    iters_out[0] = hn.iters; iters_out[1] = hl.iters;
+    resid_out[0] = hn.resid; resid_out[1] = hl.resid;
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
+extern "C" {
+// (SteadyState.jl:195 differentiates the steady state's residual through the VFI of :132-141 and through invariant_dist's
+// implicit-function tangent, ForwardIteration.jl:446-530)
+int hank_ss_jvp(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double tol, int32_t max_iter, double *dvalue_out, double *dpolicy_out, double *dD_out,
+                double *dagg_out, int32_t *iters_out, double *resid_out) {
+    return ss_jvp(ctx, n_het, dxhh, N, tol, max_iter, dvalue_out, dpolicy_out, dD_out, dagg_out, iters_out, resid_out, false);
+}
+int hank_ss_jvp_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, int32_t N, double tol, int32_t max_iter, double *d_dvalue_out, double *d_dpolicy_out,
+                    double *d_dD_out, double *d_dagg_out, int32_t *iters_out, double *resid_out) {
+    return ss_jvp(ctx, n_het, d_dxhh, N, tol, max_iter, d_dvalue_out, d_dpolicy_out, d_dD_out, d_dagg_out, iters_out, resid_out, true);
+}
+int hank_ss_vjp(hank_ctx *ctx, int32_t n_het, const double *agg_bar, const double *value_bar, const double *D_bar, int32_t M, double tol, int32_t max_iter,
+                double *xhh_bar, int32_t *iters_out, double *resid_out) {
+    return ss_vjp(ctx, n_het, agg_bar, value_bar, D_bar, M, tol, max_iter, xhh_bar, iters_out, resid_out, false);
+}
+int hank_ss_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, const double *d_value_bar, const double *d_D_bar, int32_t M, double tol, int32_t max_iter,
+                    double *d_xhh_bar, int32_t *iters_out, double *resid_out) {
+    return ss_vjp(ctx, n_het, d_agg_bar, d_value_bar, d_D_bar, M, tol, max_iter, d_xhh_bar, iters_out, resid_out, true);
+}
+int hank_last_ss_timings(hank_ctx *ctx, double *out_ms) {
+    if (!ctx || !out_ms) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    for (int k = 0; k < 2; k++) {
+        float f = -1.f;
+        if (ctx->ss_timed[k]) {
+            HIPC(ctx, hipEventSynchronize(ctx->ss_ev[k][1]));
+            HIPC(ctx, hipEventElapsedTime(&f, ctx->ss_ev[k][0], ctx->ss_ev[k][1]));
+        }
+        out_ms[k] = f;
+    }
+    return HANK_OK;
+}
 }  // extern "C"

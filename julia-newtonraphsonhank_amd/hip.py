@@ -32,6 +32,7 @@ ABI_SYMBOLS = (
     "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings", "hank_vjp_het", "hank_vjp_het_dev",
     "hank_jvp_boundary", "hank_jvp_boundary_dev", "hank_vjp_boundary", "hank_vjp_boundary_dev",
     "hank_jvp_het", "hank_jvp_het_dev", "hank_vjp_het_boundary", "hank_vjp_het_boundary_dev",
+    "hank_ss_jvp", "hank_ss_jvp_dev", "hank_ss_vjp", "hank_ss_vjp_dev", "hank_last_ss_timings",
 )
 
 
@@ -53,6 +54,10 @@ class DomainError(HankHIPError):
 
 class NoDeviceError(HankHIPError):
     """No usable gfx950 device / HIP runtime failure."""
+
+
+class SteadyStateLoopError(RuntimeError):
+    """A fixed-point loop of hank_ss_jvp / hank_ss_vjp ran into max_iter (the library reports that as HANK_OK, like hank_vfi)."""
 
 
 _ERR_CLASSES = {HANK_ERR_KNOTS: KnotsNotSortedError, HANK_ERR_DOMAIN: DomainError,
@@ -132,6 +137,11 @@ def load_library() -> C.CDLL:
     lib.hank_jvp_het_dev.argtypes = [vp, i32, vp, vp, vp, i32, vp]
     lib.hank_vjp_het_boundary.argtypes = [vp, i32, dp, i32, dp, dp, dp]
     lib.hank_vjp_het_boundary_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    lib.hank_ss_jvp.argtypes = [vp, i32, dp, i32, C.c_double, i32, dp, dp, dp, dp, C.POINTER(i32), dp]
+    lib.hank_ss_jvp_dev.argtypes = [vp, i32, vp, i32, C.c_double, i32, vp, vp, vp, vp, C.POINTER(i32), dp]
+    lib.hank_ss_vjp.argtypes = [vp, i32, dp, dp, dp, i32, C.c_double, i32, dp, C.POINTER(i32), dp]
+    lib.hank_ss_vjp_dev.argtypes = [vp, i32, vp, vp, vp, i32, C.c_double, i32, vp, C.POINTER(i32), dp]
+    lib.hank_last_ss_timings.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
@@ -443,6 +453,59 @@ class HouseholdBlock:
         self._chk(self._lib.hank_vjp_het_boundary_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr),
                                                       C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
 
+    # -- derivatives through the steady state -------------------------------------------------
+    def _ss_done(self, who, names, it, res, tol, max_iter, check):
+        self.last_ss = {"iters": (int(it[0]), int(it[1])), "resid": (float(res[0]), float(res[1]))}
+        if check:
+            for k in range(2):
+                if it[k] >= max_iter and not res[k] <= tol:
+                    raise SteadyStateLoopError(f"{who}: the {names[k]} loop took max_iter = {max_iter} steps and its last increment ratio "
+                                               f"{res[k]:.3g} is above tol = {tol:.3g}")
+
+    def ss_jvp(self, dxhh, n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
+        """derivatives of the steady state's household objects in the household prices (hank_ss_jvp; what
+        ForwardDiff.jacobian carries through the VFI and invariant_dist at SteadyState.jl:195). Needs `primal` at the constant
+        steady-state path with the steady state as both boundaries (the precondition of `fake_news`). dxhh (n_hh,) or (n_hh, N).
+        -> (dagg (n_het, N), dV (n_a, n_e, N), dpol (n_a, n_e, N), dD (n_a, n_e, N), iters (value loop, distribution loop)).
+        Raises SteadyStateLoopError when a loop ran into max_iter (check=False: returns what it has; `last_ss` holds the
+        increment ratios)."""
+        dx = np.asarray(dxhh, dtype=np.float64)
+        if dx.ndim == 1:
+            dx = dx[:, None]
+        N = dx.shape[1]
+        dx = _f(dx, (self.n_hh, N))
+        dagg = np.empty((max(int(n_het), 1), N), order="F")
+        dV, dpol, dD = (np.empty((self.n_a, self.n_e, N), order="F") for _ in range(3))
+        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
+        self._chk(self._lib.hank_ss_jvp(self._ctx, int(n_het), _p(dx), N, float(tol), int(max_iter), _p(dV), _p(dpol), _p(dD), _p(dagg), it, res))
+        self._ss_done("ss_jvp", ("value", "distribution"), it, res, tol, max_iter, check)
+        return dagg, dV, dpol, dD, (int(it[0]), int(it[1]))
+
+    def ss_vjp(self, agg_bar=None, value_bar=None, D_bar=None, n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
+        """the transpose of `ss_jvp` (hank_ss_vjp): cotangents agg_bar (n_het,) or (n_het, M) of the steady state's aggregates,
+        value_bar and D_bar (n_a, n_e[, M]) or (G, M) of V_ss and D_ss — e.g. `vjp_het_boundary`'s value_end_bar — any of them
+        None (not given), at least one given. -> (xhh_bar (n_hh, M), iters (nu loop, lambda loop))."""
+        if agg_bar is None and value_bar is None and D_bar is None:
+            raise ValueError("at least one of agg_bar, value_bar, D_bar must be given")
+        yb = None
+        M = None
+        if agg_bar is not None:
+            yb = np.asarray(agg_bar, dtype=np.float64)
+            yb = yb[:, None] if yb.ndim == 1 else yb
+            M = yb.shape[1]
+        else:
+            b = np.asarray(value_bar if value_bar is not None else D_bar)
+            M = 1 if b.shape == (self.n_a, self.n_e) else b.shape[-1]
+        if yb is not None:
+            yb = _f(yb, (int(n_het), M) if 1 <= int(n_het) <= 4 else None)
+        vb, db = self._boundary_seed(value_bar, M), self._boundary_seed(D_bar, M)
+        out = np.empty((self.n_hh, M), order="F")
+        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
+        self._chk(self._lib.hank_ss_vjp(self._ctx, int(n_het), None if yb is None else _p(yb), None if vb is None else _p(vb),
+                                        None if db is None else _p(db), M, float(tol), int(max_iter), _p(out), it, res))
+        self._ss_done("ss_vjp", ("nu", "lambda"), it, res, tol, max_iter, check)
+        return out, (int(it[0]), int(it[1]))
+
     def policy_cotangent_seq(self, M: int) -> np.ndarray:
         """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp / vjp_het (hank_get_policy_cotangent_seq)."""
         out = np.empty((self.n_a, self.n_e, self.P, max(int(M), 1)), order="F")
@@ -454,6 +517,12 @@ class HouseholdBlock:
         ln = (C.c_int32 * 2)()
         self._chk(self._lib.hank_last_vjp_timings(self._ctx, ms, ln))
         return {k: {"ms": ms[i], "launches": ln[i]} for i, k in enumerate(("sweep_a", "sweep_b"))}
+
+    def last_ss_timings(self):
+        """time (ms, HIP events on the stream) of the two loops of the last ss_jvp / ss_vjp, in the order of their `iters` (hank_last_ss_timings)"""
+        ms = (C.c_double * 2)()
+        self._chk(self._lib.hank_last_ss_timings(self._ctx, ms))
+        return (ms[0], ms[1])
 
     def last_timings(self):
         ms = (C.c_double * 6)()

@@ -381,6 +381,49 @@ function hank_vjp_het_boundary!(xhh_bar::Array{Float64,3}, value_end_bar::Union{
     return xhh_bar, value_end_bar, D_init_bar
 end
 
+# ---- derivatives through the steady state (hank_ss_jvp, hank_ss_vjp) ----------------------------------------------------------------
+# What ForwardDiff.jacobian(F, p) carries through the VFI and invariant_dist inside find_ss (SteadyState.jl:195, :132-141;
+# ForwardIteration.jl:446-530), from the record of hank_primal at the constant steady-state path with the steady state as both
+# boundaries (hank_fake_news's precondition). dxhh (n_hh, N): directions in the household prices; dagg (n_het, N); dvalue, dpolicy,
+# dD (n_a, n_e, N) or nothing (not wanted). Returns (dagg, iters, resid): steps and last increment ratio of the value and the
+# distribution loop; a loop that ran into max_iter is an error here (the library reports it as HANK_OK, like hank_vfi).
+function hank_ss_jvp!(dagg::Matrix{Float64}, ctx::HankCtx, dxhh::Matrix{Float64}; dvalue::Union{Nothing,Array{Float64,3}} = nothing,
+                      dpolicy::Union{Nothing,Array{Float64,3}} = nothing, dD::Union{Nothing,Array{Float64,3}} = nothing,
+                      tol::Float64 = 1e-13, max_iter::Integer = 50_000)
+    n_het, N = size(dagg)
+    @assert size(dxhh) == (length(ctx.hh_rows), N)
+    @assert all(s -> s === nothing || size(s) == (ctx.n_a, ctx.n_e, N), (dvalue, dpolicy, dD))
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    iters, resid = zeros(Int32, 2), zeros(Float64, 2)
+    GC.@preserve dvalue dpolicy dD begin
+        _check(ctx.ptr, ccall((:hank_ss_jvp, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                                                            Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                              ctx.ptr, Int32(n_het), dxhh, Int32(N), tol, Int32(max_iter), ptr(dvalue), ptr(dpolicy), ptr(dD), dagg, iters, resid))
+    end
+    all(k -> iters[k] < max_iter || resid[k] <= tol, 1:2) || error("hank_ss_jvp: a loop took max_iter = $max_iter steps (increment ratios $resid)")
+    return dagg, iters, resid
+end
+
+# The transpose: cotangents agg_bar (n_het, M) of the steady state's aggregates, value_bar and D_bar (n_a, n_e, M) of V_ss and D_ss
+# (e.g. hank_vjp_het_boundary!'s value_end_bar), `nothing` where one is zero, not all three -> xhh_bar (n_hh, M).
+function hank_ss_vjp!(xhh_bar::Matrix{Float64}, ctx::HankCtx; agg_bar::Union{Nothing,Matrix{Float64}} = nothing,
+                      value_bar::Union{Nothing,Array{Float64,3}} = nothing, D_bar::Union{Nothing,Array{Float64,3}} = nothing,
+                      n_het::Integer = agg_bar === nothing ? 1 : size(agg_bar, 1), tol::Float64 = 1e-13, max_iter::Integer = 50_000)
+    M = size(xhh_bar, 2)
+    @assert size(xhh_bar, 1) == length(ctx.hh_rows) && !(agg_bar === nothing && value_bar === nothing && D_bar === nothing)
+    @assert agg_bar === nothing || size(agg_bar) == (n_het, M)
+    @assert all(s -> s === nothing || size(s) == (ctx.n_a, ctx.n_e, M), (value_bar, D_bar))
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    iters, resid = zeros(Int32, 2), zeros(Float64, 2)
+    GC.@preserve agg_bar value_bar D_bar begin
+        _check(ctx.ptr, ccall((:hank_ss_vjp, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64},
+                                                            Ptr{Int32}, Ptr{Float64}),
+                              ctx.ptr, Int32(n_het), ptr(agg_bar), ptr(value_bar), ptr(D_bar), Int32(M), tol, Int32(max_iter), xhh_bar, iters, resid))
+    end
+    all(k -> iters[k] < max_iter || resid[k] <= tol, 1:2) || error("hank_ss_vjp: a loop took max_iter = $max_iter steps (increment ratios $resid)")
+    return xhh_bar, iters, resid
+end
+
 # the cotangent of the policy sequence of the last hank_vjp! / hank_vjp_het!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
 # (ForwardIteration.jl:412-416) for the policy variable when n_het = 1
 function hank_policy_cotangent_seq(ctx::HankCtx, M::Integer)
