@@ -86,19 +86,21 @@ struct TanWork {
     DevBuf<double> dagg;      // [P][N]
     DevBuf<double> dagg_cm;   // (P,N) column-major
     int nbx = 0, nbxf = 0;
-    GraphExec g_back, g_fwd;
     GraphExec g_fback, g_ffwd;   // dual-sweep graphs (primal + tangents in one chain)
-    // hank_jvp_boundary (hank_boundary.h), allocated and captured on its first use at this width: the caller's seeds (G, N)
-    // column-major, m_{-1} [N][n_e], {zm, om} [2][P][N], and the tangent-only sweeps with the two seeds in them
+    // hank_jvp_boundary (hank_boundary.h), allocated on its first use at this width: the caller's seeds (G, N) column-major,
+    // m_{-1} [N][n_e], {zm, om} [2][P][N]
     DevBuf<double> bnd_dV, bnd_dD, bnd_m0, bnd_zm;
-    GraphExec g_bback, g_bfwd;
-    // hank_jvp_het with n_het > 2, allocated and captured on its first use at this width: the extra slots'
-    // partials [P][nbf][NX][N] and sums T [N][P][NX] (sized for the family's count), the (P, n_het, N) result, and the forward
-    // graphs with NX = 1, 2 extra reductions, without and with the boundary's seeds
+    // hank_jvp_het, allocated on its first use at this width: the (P, n_het, N) result and, for n_het > 2,
+    // the extra slots' partials [P][nbf][NX][N] and sums T [N][P][NX] (sized for the family's count)
     DevBuf<double> hx_parts, hx_T, het_out;
-    GraphExec g_fwdx[2], g_bfwdx[2];
     int VB = 1, VF = 1, RGB = 1, RGF = 1;   // lane widths and row groups the graphs are captured with
     unsigned nbf = 0;
+    // The tangent-only graphs, each captured on its first use at this width, named HERE and nowhere else: bnd — with the boundary's
+    // seed kernels in them (hank_boundary.h); NX — the forward sweep with that many extra reductions (hank_jvp_het, n_het = 2 + NX)
+    GraphExec &tan_back(bool bnd) { return g_tback[bnd]; }
+    GraphExec &tan_fwd(bool bnd, int NX) { return g_tfwd[bnd][NX]; }
+private:
+    GraphExec g_tback[2], g_tfwd[2][3];
 };
 
 // ---- XCD-local persistent sweeps (hank_xsweep.h): per-context workspace and per-batch-width tangent buffers ----
@@ -468,69 +470,105 @@ static int build_primal_graphs(hank_ctx *ctx) {
         }                                                                                       \
     } while (0)
 
-// captures ONE pair of tangent graphs, on first use: which = 0 the tangent-only sweeps (hank_jvp), 1 the dual-sweep
-// launches (hank_primal_jvp), 2 the tangent-only sweeps with the boundary's seeds (hank_jvp_boundary, hank_boundary.h: the same
-// launches of the same kernels, the seed kernels between them)
-template <typename VT, typename VF>
-static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
-    const int RGB = w.RGB, RGF = w.RGF;
-    const unsigned nbf = w.nbf;
+// The launch family's graphs of one batch width, ONE capture per sweep, each on its first use (ensure_tan_graphs,
+// ensure_dual_graphs). VT / VF: the lane type of the backward / forward kernels (double: one direction per lane; double2: two).
+// the pair every forward tangent graph ends with: the partials' sums, then (P, 2 N) column-major
+static void launch_tan_reduce(hank_ctx *ctx, TanWork &w, hipStream_t s) {
+    const int P = ctx->c.P, N = w.N;
+    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)w.nbf, 2 * N, w.dagg);
+    hipLaunchKernelGGL(k_tan_out, dim3((2 * P * N + 255) / 256), dim3(256), 0, s, w.dagg, P, 2 * N, w.dagg_cm);
+}
+// the grid of the boundary's layout kernels (k_bnd_in)
+static dim3 bnd_grid(const Consts &c, int N) { return dim3((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e); }
+
+// the backward tangent sweep; bnd: with the dV_P seed (hank_boundary.h: the same launches of the same kernel, the seed kernels between them)
+template <typename VT>
+static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
-    const int N = w.N;
-    const size_t GV = (size_t)(c.n_a + KV) * c.n_e;
+    const int N = w.N, PN = (int)(P * N), RGB = w.RGB;
     hipStream_t s = ctx->own_stream;
     const dim3 blk(64 * c.n_e);
-    const unsigned ny = (w.g.N + w.g.NC - 1) / w.g.NC, nyf = (w.gf.N + w.gf.NC - 1) / w.gf.NC;
-    const int PN = (int)(P * N);
+    const unsigned ny = (w.g.N + w.g.NC - 1) / w.g.NC, nbt = (w.nbx + RGB - 1) / RGB;
+    const VT *dxr = reinterpret_cast<const VT *>(w.dxr.get()), *dxw = reinterpret_cast<const VT *>(w.dxw.get()), *dxt = reinterpret_cast<const VT *>(w.dxt.get());
+    VT *ds[2] = {reinterpret_cast<VT *>(w.ds[0].get()), reinterpret_cast<VT *>(w.ds[1].get())};
+    VT *dpol = reinterpret_cast<VT *>(w.dpol.get());
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
+    LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, (int)P - 1, 1,
+                       ds[1], ds[0], dpol);
+    if (bnd) {      // dV_P (BackwardIteration.jl:85) into the knots' tangent of period P-1; ds[1] is free until the next launch writes it
+        hipLaunchKernelGGL(k_bnd_in, bnd_grid(c, N), dim3(BND_T, 8), 0, s, w.bnd_dV.get(), c.n_a, c.n_e, c.n_a, N, w.ds[1].get());
+        hipLaunchKernelGGL(k_bnd_seed_back, dim3((unsigned)(((size_t)c.n_a * N + 255) / 256)), dim3(256), 0, s, c, ctx->R.kc + (P - 1) * c.G, w.ds[1].get(), (size_t)N, w.ds[0].get());
+    }
+    int cur = 0;
+    for (int t = (int)P - 1; t >= 0; t--) {
+        LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, t, 0,
+                           ds[cur], ds[cur ^ 1], dpol);
+        cur ^= 1;
+    }
+    return end_capture(ctx, &w.tan_back(bnd));
+}
+
+// the forward tangent sweep; bnd: with the dD_0 seed; NX > 0 (hank_jvp_het): k_tan_fwd_hx in k_tan_fwd's place and k_reduce_hx behind
+// the reductions — instantiated for the geometries the defaults launch, the gather form with one row group and the source-stationary
+// form with two; a dev knob that asks for another is refused.
+// (the seeds' buffers and, for NX > 0, the record's f, f_c and the workspace's hx_parts, hx_T are allocated before this: the graph
+// holds their addresses)
+template <typename VF, int NX>
+static int capture_tan_fwd(hank_ctx *ctx, TanWork &w, bool bnd) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P, GV = (size_t)(c.n_a + KV) * c.n_e;
+    const int N = w.N, PN = (int)(P * N);
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(64 * c.n_e);
+    const unsigned nbf = w.nbf, nyf = (w.gf.N + w.gf.NC - 1) / w.gf.NC;
+    VF *dD[2] = {reinterpret_cast<VF *>(w.dD[0].get()), reinterpret_cast<VF *>(w.dD[1].get())};
+    VF *dpolf = reinterpret_cast<VF *>(w.dpol.get()), *aggpart = reinterpret_cast<VF *>(w.aggpart.get());
+    const bool ss = w.gf.ss != 0;
+    if (NX > 0 && !((w.RGF == 1 && !ss) || (w.RGF == 2 && ss)))
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_het: the forward kernel with extra outputs exists for the default geometries only (got %d row groups, %s form)",
+                    w.RGF, ss ? "source-stationary" : "gather");
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    if (bnd) {      // dD_0 (ForwardIteration.jl:293) into the real rows of the state, zero virtual rows; its productivity marginal along the path
+        hipLaunchKernelGGL(k_bnd_in, bnd_grid(c, N), dim3(BND_T, 8), 0, s, w.bnd_dD.get(), c.n_a, c.n_e, c.n_a + KV, N, w.dD[0].get());
+        hipLaunchKernelGGL(k_bnd_marginal, dim3((unsigned)c.n_e, (unsigned)N), dim3(256), 0, s, w.bnd_dD.get(), c.n_a, c.n_e, w.bnd_m0.get());
+        hipLaunchKernelGGL(k_bnd_mpath, dim3((unsigned)((PN + 255) / 256)), dim3(256), 0, s, (int)P, c.n_e, N, w.bnd_m0.get(), ctx->d_bnd_q.get(), w.bnd_zm.get());
+    } else
+        hipLaunchKernelGGL(k_zero_f64, dim3(512), dim3(256), 0, s, w.dD[0], GV * N);  // dD_0 = 0 (ForwardIteration.jl:293)
+    int cur = 0;
+    for (int t = 0; t < (int)P; t++) {
+        if constexpr (NX == 0) {
+            LAUNCH_RG_SS(w.RGF, ss, k_tan_fwd, VF, dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart);
+        } else {
+            const TanHx<VF, NX> hx{ctx->hx.f.get(), ctx->hx.fc.get(), reinterpret_cast<VF *>(w.hx_parts.get())};
+            if (ss) hipLaunchKernelGGL((k_tan_fwd_hx<2, VF, true, NX>), dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart, hx);
+            else hipLaunchKernelGGL((k_tan_fwd_hx<1, VF, false, NX>), dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart, hx);
+        }
+        cur ^= 1;
+    }
+    launch_tan_reduce(ctx, w, s);
+    if (NX > 0) hipLaunchKernelGGL(k_reduce_hx, dim3((unsigned)P, (NX * N + 63) / 64), dim3(256), 0, s, w.hx_parts.get(), (int)nbf, NX, N, (int)P, w.hx_T.get());
+    return end_capture(ctx, &w.tan_fwd(bnd, NX));
+}
+
+// The dual-sweep graphs (hank_primal_jvp): the primal recurrence and the tangent recurrence advance in the SAME chain of launches,
+// the tangent one period behind (it reads the record the previous launch wrote): T launches per direction instead of 2(T-1).
+template <typename VT, typename VF>
+static int capture_dual_graphs(hank_ctx *ctx, TanWork &w) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P, GV = (size_t)(c.n_a + KV) * c.n_e;
+    const int N = w.N, PN = (int)(P * N), RGB = w.RGB, RGF = w.RGF;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(64 * c.n_e);
+    const unsigned nbf = w.nbf, ny = (w.g.N + w.g.NC - 1) / w.g.NC, nyf = (w.gf.N + w.gf.NC - 1) / w.gf.NC;
     const VT *dxr = reinterpret_cast<const VT *>(w.dxr.get()), *dxw = reinterpret_cast<const VT *>(w.dxw.get()), *dxt = reinterpret_cast<const VT *>(w.dxt.get());
     VT *ds[2] = {reinterpret_cast<VT *>(w.ds[0].get()), reinterpret_cast<VT *>(w.ds[1].get())};
     VF *dD[2] = {reinterpret_cast<VF *>(w.dD[0].get()), reinterpret_cast<VF *>(w.dD[1].get())};
     VT *dpol = reinterpret_cast<VT *>(w.dpol.get());
     VF *dpolf = reinterpret_cast<VF *>(w.dpol.get()), *aggpart = reinterpret_cast<VF *>(w.aggpart.get());
     const unsigned nbt = (w.nbx + RGB - 1) / RGB;
-    int rc = HANK_OK, cur = 0;
-    const bool bnd = which == 2;
-    const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e);      // the layout kernels
-    if (which != 1) {
-    // backward tangent sweep
-    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
-    LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, (int)P - 1, 1,
-                       ds[1], ds[0], dpol);
-    if (bnd) {      // dV_P (BackwardIteration.jl:85) into the knots' tangent of period P-1; ds[1] is free until the next launch writes it
-        hipLaunchKernelGGL(k_bnd_in, tgrd, tblk, 0, s, w.bnd_dV.get(), c.n_a, c.n_e, c.n_a, N, w.ds[1].get());
-        hipLaunchKernelGGL(k_bnd_seed_back, dim3((unsigned)(((size_t)c.n_a * N + 255) / 256)), dim3(256), 0, s, c, ctx->R.kc + (P - 1) * c.G, w.ds[1].get(), (size_t)N, w.ds[0].get());
-    }
-    cur = 0;
-    for (int t = (int)P - 1; t >= 0; t--) {
-        LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, t, 0,
-                           ds[cur], ds[cur ^ 1], dpol);
-        cur ^= 1;
-    }
-    rc = end_capture(ctx, bnd ? &w.g_bback : &w.g_back);
-    if (rc) return rc;
-    // forward tangent sweep
-    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    if (bnd) {      // dD_0 (ForwardIteration.jl:293) into the real rows of the state, zero virtual rows; its productivity marginal along the path
-        hipLaunchKernelGGL(k_bnd_in, tgrd, tblk, 0, s, w.bnd_dD.get(), c.n_a, c.n_e, c.n_a + KV, N, w.dD[0].get());
-        hipLaunchKernelGGL(k_bnd_marginal, dim3((unsigned)c.n_e, (unsigned)N), dim3(256), 0, s, w.bnd_dD.get(), c.n_a, c.n_e, w.bnd_m0.get());
-        hipLaunchKernelGGL(k_bnd_mpath, dim3((unsigned)((PN + 255) / 256)), dim3(256), 0, s, (int)P, c.n_e, N, w.bnd_m0.get(), ctx->d_bnd_q.get(), w.bnd_zm.get());
-    } else
-    hipLaunchKernelGGL(k_zero_f64, dim3(512), dim3(256), 0, s, w.dD[0], GV * N);  // dD_0 = 0 (ForwardIteration.jl:293)
-    cur = 0;
-    for (int t = 0; t < (int)P; t++) {
-        LAUNCH_RG_SS(RGF, w.gf.ss, k_tan_fwd, VF, dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart);
-        cur ^= 1;
-    }
-    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)nbf, 2 * N, w.dagg);
-    hipLaunchKernelGGL(k_tan_out, dim3((2 * PN + 255) / 256), dim3(256), 0, s, w.dagg, (int)P, 2 * N, w.dagg_cm);
-    return end_capture(ctx, bnd ? &w.g_bfwd : &w.g_fwd);
-    }
-
-    // ---- dual-sweep graphs: the primal recurrence and the tangent recurrence advance in the SAME
-    // chain of launches, the tangent one period behind (it reads the record the previous launch wrote):
-    // T launches per direction instead of 2(T-1).
+    int cur = 0;
     const dim3 pblk(RBP * c.n_e), pgrd(ctx->nbp);
     const size_t lds = primal_lds(c);
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -538,7 +576,6 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
     hipLaunchKernelGGL(k_egm_X, pgrd, pblk, lds, s, c, ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
                        ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, (int)P - 1, (const int *)nullptr);
-    cur = 0;
     for (int k = 0; k <= (int)P; k++) {
         const int tp = k < (int)P ? (int)P - 1 - k : -1;
         if (k == 0) {
@@ -551,7 +588,7 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
         }
     }
     hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, (int)P * c.n_e, ctx->d_err, 1, 1);
-    rc = end_capture(ctx, &w.g_fback);
+    const int rc = end_capture(ctx, &w.g_fback);
     if (rc) return rc;
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     hipLaunchKernelGGL(k_zero_f64, dim3(512), dim3(256), 0, s, w.dD[0], GV * N);
@@ -564,8 +601,7 @@ static int capture_tangent_graphs(hank_ctx *ctx, TanWork &w, int which) {
     }
     hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, 1), dim3(256), 0, s, ctx->d_aggpart, ctx->nbp, 2, ctx->d_agg_rm);
     hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, ctx->d_agg_rm, (int)P, 2, ctx->d_agg);
-    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)nbf, 2 * N, w.dagg);
-    hipLaunchKernelGGL(k_tan_out, dim3((2 * PN + 255) / 256), dim3(256), 0, s, w.dagg, (int)P, 2 * N, w.dagg_cm);
+    launch_tan_reduce(ctx, w, s);
     return end_capture(ctx, &w.g_ffwd);
 }
 
@@ -641,56 +677,26 @@ static int ensure_tanwork(hank_ctx *ctx, int N, TanWork **out) {
     return tan_cache_get(ctx, ctx->tws, N, [ctx](TanWork &w) { return build_tanwork(ctx, w); }, out);
 }
 
-// the graph pair of one schedule, captured the first time that schedule runs at this batch width
-static int ensure_graphs(hank_ctx *ctx, TanWork &w, int which) {
-    if ((which == 0 ? w.g_back : which == 1 ? w.g_fback : w.g_bback).get() != nullptr) return HANK_OK;
-    if (w.VB == 2) return w.VF == 2 ? capture_tangent_graphs<double2, double2>(ctx, w, which) : capture_tangent_graphs<double2, double>(ctx, w, which);
-    return w.VF == 2 ? capture_tangent_graphs<double, double2>(ctx, w, which) : capture_tangent_graphs<double, double>(ctx, w, which);
+// The tangent-only graphs one entry launches, captured the first time it runs at this batch width: the backward sweep and the plain
+// forward sweep as a pair (whatever NX asks: graphs_captured counts them so, and fake_news takes the backward one from the pair), then
+// the forward sweep with NX extra reductions. Every buffer the graphs name is allocated before this (enqueue_tan_launch).
+static int ensure_tan_graphs(hank_ctx *ctx, TanWork &w, bool bnd, int NX) {
+    auto fwd = [&](int nx) {
+        if (w.tan_fwd(bnd, nx)) return (int)HANK_OK;
+        if (nx == 0) return w.VF == 2 ? capture_tan_fwd<double2, 0>(ctx, w, bnd) : capture_tan_fwd<double, 0>(ctx, w, bnd);
+        if (nx == 1) return w.VF == 2 ? capture_tan_fwd<double2, 1>(ctx, w, bnd) : capture_tan_fwd<double, 1>(ctx, w, bnd);
+        return w.VF == 2 ? capture_tan_fwd<double2, 2>(ctx, w, bnd) : capture_tan_fwd<double, 2>(ctx, w, bnd);
+    };
+    int rc = HANK_OK;
+    if (!w.tan_back(bnd)) rc = w.VB == 2 ? capture_tan_back<double2>(ctx, w, bnd) : capture_tan_back<double>(ctx, w, bnd);
+    if (!rc) rc = fwd(0);
+    if (!rc && NX > 0) rc = fwd(NX);
+    return rc;
 }
-
-// hank_jvp_het's forward graph with NX extra reductions: the forward half of capture_tangent_graphs (which = 0, or 2 with bnd) with
-// k_tan_fwd_hx in k_tan_fwd's place and k_reduce_hx behind the reductions. Instantiated for the geometries the defaults launch:
-// the gather form with one row group and the source-stationary form with two; a dev knob that asks for another is refused.
-template <typename VF, int NX>
-static int capture_fwd_hx_graph(hank_ctx *ctx, TanWork &w, bool bnd) {
-    const Consts &c = ctx->c;
-    const size_t P = c.P;
-    const int N = w.N, PN = (int)(P * N);
-    const size_t GV = (size_t)(c.n_a + KV) * c.n_e;
-    hipStream_t s = ctx->own_stream;
-    const dim3 blk(64 * c.n_e);
-    const unsigned nbf = w.nbf, nyf = (w.gf.N + w.gf.NC - 1) / w.gf.NC;
-    VF *dD[2] = {reinterpret_cast<VF *>(w.dD[0].get()), reinterpret_cast<VF *>(w.dD[1].get())};
-    VF *dpolf = reinterpret_cast<VF *>(w.dpol.get()), *aggpart = reinterpret_cast<VF *>(w.aggpart.get());
-    const TanHx<VF, NX> hx{ctx->hx.f.get(), ctx->hx.fc.get(), reinterpret_cast<VF *>(w.hx_parts.get())};
-    const bool ss = w.gf.ss != 0;
-    if (!((w.RGF == 1 && !ss) || (w.RGF == 2 && ss)))
-        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_het: the forward kernel with extra outputs exists for the default geometries only (got %d row groups, %s form)",
-                    w.RGF, ss ? "source-stationary" : "gather");
-    const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e);
-    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    if (bnd) {
-        hipLaunchKernelGGL(k_bnd_in, tgrd, tblk, 0, s, w.bnd_dD.get(), c.n_a, c.n_e, c.n_a + KV, N, w.dD[0].get());
-        hipLaunchKernelGGL(k_bnd_marginal, dim3((unsigned)c.n_e, (unsigned)N), dim3(256), 0, s, w.bnd_dD.get(), c.n_a, c.n_e, w.bnd_m0.get());
-        hipLaunchKernelGGL(k_bnd_mpath, dim3((unsigned)((PN + 255) / 256)), dim3(256), 0, s, (int)P, c.n_e, N, w.bnd_m0.get(), ctx->d_bnd_q.get(), w.bnd_zm.get());
-    } else
-        hipLaunchKernelGGL(k_zero_f64, dim3(512), dim3(256), 0, s, w.dD[0], GV * N);
-    int cur = 0;
-    for (int t = 0; t < (int)P; t++) {
-        if (ss) hipLaunchKernelGGL((k_tan_fwd_hx<2, VF, true, NX>), dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart, hx);
-        else hipLaunchKernelGGL((k_tan_fwd_hx<1, VF, false, NX>), dim3(nbf, nyf), blk, 0, s, c, ctx->R, w.gf, t, dD[cur], dD[cur ^ 1], dpolf, aggpart, hx);
-        cur ^= 1;
-    }
-    hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (2 * N + 63) / 64), dim3(256), 0, s, w.aggpart, (int)nbf, 2 * N, w.dagg);
-    hipLaunchKernelGGL(k_tan_out, dim3((2 * PN + 255) / 256), dim3(256), 0, s, w.dagg, (int)P, 2 * N, w.dagg_cm);
-    hipLaunchKernelGGL(k_reduce_hx, dim3((unsigned)P, (NX * N + 63) / 64), dim3(256), 0, s, w.hx_parts.get(), (int)nbf, NX, N, (int)P, w.hx_T.get());
-    return end_capture(ctx, &(bnd ? w.g_bfwdx : w.g_fwdx)[NX - 1]);
-}
-// (the record's f, f_c and the workspace's hx_parts, hx_T are allocated before this: the graph holds their addresses)
-static int ensure_fwd_hx_graph(hank_ctx *ctx, TanWork &w, bool bnd, int NX) {
-    if ((bnd ? w.g_bfwdx : w.g_fwdx)[NX - 1].get() != nullptr) return HANK_OK;
-    if (NX == 1) return w.VF == 2 ? capture_fwd_hx_graph<double2, 1>(ctx, w, bnd) : capture_fwd_hx_graph<double, 1>(ctx, w, bnd);
-    return w.VF == 2 ? capture_fwd_hx_graph<double2, 2>(ctx, w, bnd) : capture_fwd_hx_graph<double, 2>(ctx, w, bnd);
+static int ensure_dual_graphs(hank_ctx *ctx, TanWork &w) {
+    if (w.g_fback) return HANK_OK;
+    if (w.VB == 2) return w.VF == 2 ? capture_dual_graphs<double2, double2>(ctx, w) : capture_dual_graphs<double2, double>(ctx, w);
+    return w.VF == 2 ? capture_dual_graphs<double, double2>(ctx, w) : capture_dual_graphs<double, double>(ctx, w);
 }
 
 // ---- the device's verdict on work already enqueued, and what the context does about it ------------------
@@ -1791,21 +1797,87 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
 
 // bnd: the graphs with the boundary's seeds (hank_jvp_boundary: w.bnd_dV and w.bnd_dD hold them); zm: whether a dD_0 seed is among them
 // NX > 0 (hank_jvp_het): the forward graph with that many extra reductions, one launch more (k_reduce_hx)
-static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd = false, bool zm = false, int NX = 0) {
-    int grc = ensure_graphs(ctx, w, bnd ? 2 : 0);
-    if (!grc && NX > 0) grc = ensure_fwd_hx_graph(ctx, w, bnd, NX);
+static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd, bool zm, int NX) {
+    const int grc = ensure_tan_graphs(ctx, w, bnd, NX);
     if (grc) return grc;
     HIPC(ctx, ctx->spans.begin(TAN_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(bnd ? w.g_bback : w.g_back, ctx->stream));
+    HIPC(ctx, hipGraphLaunch(w.tan_back(bnd), ctx->stream));
     HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, ctx->c.P + (bnd ? 4 : 2)));
     HIPC(ctx, join_side(ctx));      // the tangent forward sweep needs D_t
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
     HIPC(ctx, ctx->spans.begin(TAN_FWD, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(NX > 0 ? (bnd ? w.g_bfwdx : w.g_fwdx)[NX - 1] : bnd ? w.g_bfwd : w.g_fwd, ctx->stream));
+    HIPC(ctx, hipGraphLaunch(w.tan_fwd(bnd, NX), ctx->stream));
     HIPC(ctx, ctx->spans.end(TAN_FWD, ctx->stream, ctx->c.P + (bnd ? 5 : 3) + (NX > 0 ? 1 : 0)));
     if (bnd) batch_ran_boundary(ctx, &w, w.N, w.dagg_cm, w.dpol, zm ? w.bnd_zm.get() : nullptr);
     else batch_ran(ctx, 0, &w, w.N, w.dagg_cm, w.dpol);
+    return HANK_OK;
+}
+
+// One request to the launch family's tangent sweeps, whatever the context's schedule and whichever family wrote the record (any primal
+// serves any tangent sweep: run_jvp's ensure_seg / ensure_lwg). hank_jvp, hank_jvp_boundary and hank_jvp_het are this with options.
+struct TanReq {
+    int n_het;                                     // 0: the raw aggregates (P, 2 N); >= 1: hank_jvp_het's (P, n_het, N), the entry's rule has checked the count
+    const double *dxhh, *dvalue_end, *dD_init;     // the directions and the boundary's seeds, (.., N) column-major; null: zero
+    hipMemcpyKind kind;                            // where they live
+    bool seeded;                                   // run the graphs with the seed kernels: hank_jvp_boundary always (null seeds too),
+                                                   // hank_jvp_het when a seed is given, hank_jvp never — NOT derived from the pointers
+};
+static int ensure_bnd_bufs(hank_ctx *ctx, TanWork &w);
+static int ensure_hx_record(hank_ctx *ctx);
+
+// the one enqueue of a request: the workspace of this width, every buffer a graph names (before any capture: the graph holds their
+// addresses), the inputs, the sweeps. batch_ran has named the batch when this returns HANK_OK; the copy-out is the entry's.
+static int enqueue_tan_launch(hank_ctx *ctx, const TanReq &q, int N, TanWork **out) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P, GN = (size_t)c.G * N;
+    const int NX = q.n_het > 2 ? q.n_het - 2 : 0, SX = hx_count(ctx);
+    TanWork *w = nullptr;
+    int rc = ensure_tanwork(ctx, N, &w);
+    if (rc) return rc;
+    if (q.seeded && (rc = ensure_bnd_bufs(ctx, *w)) != HANK_OK) return rc;
+    if (q.n_het > 0 && !w->het_out) HIPC(ctx, w->het_out.alloc(P * het_max(ctx) * N));
+    if (NX > 0) {
+        HIPC(ctx, join_side(ctx));      // the record's sums read D_t
+        rc = ensure_hx_record(ctx);
+        if (rc) return rc;
+        if (!w->hx_T) {
+            HIPC(ctx, w->hx_parts.alloc(P * (size_t)w->nbf * SX * N));
+            HIPC(ctx, w->hx_T.alloc((size_t)N * P * SX));      // (last: a failed allocation is tried again by the next call)
+        }
+    }
+    const struct { double *dst; const double *src; size_t count; } in[3] = {{w->dxhh, q.dxhh, c.n_hh * P * N}, {w->bnd_dV, q.dvalue_end, GN}, {w->bnd_dD, q.dD_init, GN}};
+    for (int k = 0; k < (q.seeded ? 3 : 1); k++) {
+        if (in[k].src) HIPC(ctx, hipMemcpyAsync(in[k].dst, in[k].src, sizeof(double) * in[k].count, q.kind, ctx->stream));
+        else HIPC(ctx, hipMemsetAsync(in[k].dst, 0, sizeof(double) * in[k].count, ctx->stream));
+    }
+    rc = run_jvp(ctx, *w, q.seeded, q.dD_init != nullptr, NX);
+    if (rc) return rc;
+    *out = w;
+    return HANK_OK;
+}
+// a request for the raw aggregates and its device copy-out (hank_jvp's launch-family branch, hank_jvp_boundary)
+static int enqueue_tan_raw(hank_ctx *ctx, const TanReq &q, int N, double *d_dagg_out) {
+    TanWork *w = nullptr;
+    const int rc = enqueue_tan_launch(ctx, q, N, &w);
+    if (rc) return rc;
+    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
+    return HANK_OK;
+}
+// the host forms' tail: the result to the caller, the stream drained, the call a success
+static int tan_host_tail(hank_ctx *ctx, double *out, const double *d_src, size_t count) {
+    HIPC(ctx, hipMemcpyAsync(out, d_src, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+// the rule of the entries that take seeds: the arguments, then (het) the count (hank_vjp_het's rule), then the record
+static int tan_seed_args(hank_ctx *ctx, const char *who, bool het, const TanReq &q, int N, const void *out, bool need_out) {
+    if (!ctx || (!q.dxhh && !q.dvalue_end && !q.dD_init) || (need_out && !out) || N < 1)
+        return fail(ctx, HANK_ERR_BAD_ARG, "%s: bad argument (N=%d; at least one of dxhh, dvalue_end, dD_init must be given)", who, N);
+    const int rc = het ? het_count_ok(ctx, who, q.n_het, true) : HANK_OK;
+    if (rc) return rc;
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before %s", who);
     return HANK_OK;
 }
 
@@ -1814,15 +1886,7 @@ static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd = false, bool zm = false,
 static int enqueue_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, double *d_dagg_out) {
     if (use_wide(ctx, N)) return w_jvp(ctx, dxhh, kind, N, d_dagg_out);
     if (use_x_jvp(ctx, N)) return x_jvp(ctx, dxhh, kind, N, d_dagg_out);
-    TanWork *w = nullptr;
-    int rc = ensure_tanwork(ctx, N, &w);
-    if (rc) return rc;
-    const size_t P = ctx->c.P;
-    HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * ctx->c.n_hh * P * N, kind, ctx->stream));
-    rc = run_jvp(ctx, *w);
-    if (rc) return rc;
-    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
-    return HANK_OK;
+    return enqueue_tan_raw(ctx, TanReq{0, dxhh, nullptr, nullptr, kind, false}, N, d_dagg_out);
 }
 
 int hank_jvp_dev(hank_ctx *ctx, const double *d_dxhh, int32_t N, double *d_dagg_out) {
@@ -1851,15 +1915,11 @@ int hank_jvp(hank_ctx *ctx, const double *dxhh, int32_t N, double *dagg_out) {
         }
     }
     if (rc) return rc;
-    HIPC(ctx, copy_dagg(ctx, dagg_out, ctx->batch.dagg_cm, N, hipMemcpyDeviceToHost));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
+    return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
 }
 
-// hank_jvp_boundary[_dev]: the launch family's tangent sweeps with the boundary's seeds, whatever the context's schedule and
-// whichever family wrote the record (any primal serves any tangent sweep: run_jvp's ensure_seg / ensure_lwg). A null input is a
-// zero seed. The schedule is left as it is.
+// hank_jvp_boundary[_dev]: the request with the boundary's seeds, always on the seeded graphs. A null input is a zero seed. The
+// schedule is left as it is.
 // Pi^{t+1} z and Pi^{t+1} 1, t = 0 .. P-1, once per context (k_bnd_mpath dots the seed's productivity marginal with them)
 static int ensure_bnd_q(hank_ctx *ctx) {
     if (ctx->d_bnd_q) return HANK_OK;
@@ -1896,52 +1956,25 @@ static int ensure_bnd_bufs(hank_ctx *ctx, TanWork &w) {
     }
     return HANK_OK;
 }
-static int enqueue_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_end, const double *dD_init, hipMemcpyKind kind, int N, double *d_dagg_out) {
-    TanWork *w = nullptr;
-    int rc = ensure_tanwork(ctx, N, &w);
-    if (rc) return rc;
-    const size_t P = ctx->c.P, GN = (size_t)ctx->c.G * N;
-    rc = ensure_bnd_bufs(ctx, *w);
-    if (rc) return rc;
-    const struct { double *dst; const double *src; size_t count; } in[3] = {{w->dxhh, dxhh, ctx->c.n_hh * P * N}, {w->bnd_dV, dvalue_end, GN}, {w->bnd_dD, dD_init, GN}};
-    for (const auto &a : in) {
-        if (a.src) HIPC(ctx, hipMemcpyAsync(a.dst, a.src, sizeof(double) * a.count, kind, ctx->stream));
-        else HIPC(ctx, hipMemsetAsync(a.dst, 0, sizeof(double) * a.count, ctx->stream));
-    }
-    rc = run_jvp(ctx, *w, true, dD_init != nullptr);
-    if (rc) return rc;
-    HIPC(ctx, copy_dagg(ctx, d_dagg_out, w->dagg_cm, N, hipMemcpyDeviceToDevice));
-    return HANK_OK;
-}
-static int jvp_boundary_args(hank_ctx *ctx, const void *dxhh, const void *dvalue_end, const void *dD_init, int N, const void *out, bool need_out) {
-    if (!ctx || (!dxhh && !dvalue_end && !dD_init) || (need_out && !out) || N < 1)
-        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_boundary: bad argument (N=%d; at least one of dxhh, dvalue_end, dD_init must be given)", N);
-    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_boundary");
-    return HANK_OK;
-}
-
 int hank_jvp_boundary_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dvalue_end, const double *d_dD_init, int32_t N, double *d_dagg_out) {
     ENTER(ctx);
-    const int rc = jvp_boundary_args(ctx, d_dxhh, d_dvalue_end, d_dD_init, N, d_dagg_out, false);
-    if (rc) return rc;
-    return enqueue_jvp_boundary(ctx, d_dxhh, d_dvalue_end, d_dD_init, hipMemcpyDeviceToDevice, N, d_dagg_out);
+    const TanReq q{0, d_dxhh, d_dvalue_end, d_dD_init, hipMemcpyDeviceToDevice, true};
+    const int rc = tan_seed_args(ctx, "hank_jvp_boundary", false, q, N, d_dagg_out, false);
+    return rc ? rc : enqueue_tan_raw(ctx, q, N, d_dagg_out);
 }
 
 int hank_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_end, const double *dD_init, int32_t N, double *dagg_out) {
     ENTER(ctx);
-    int rc = jvp_boundary_args(ctx, dxhh, dvalue_end, dD_init, N, dagg_out, true);
-    if (rc) return rc;
-    rc = enqueue_jvp_boundary(ctx, dxhh, dvalue_end, dD_init, hipMemcpyHostToDevice, N, nullptr);
+    const TanReq q{0, dxhh, dvalue_end, dD_init, hipMemcpyHostToDevice, true};
+    int rc = tan_seed_args(ctx, "hank_jvp_boundary", false, q, N, dagg_out, true);
+    if (!rc) rc = enqueue_tan_raw(ctx, q, N, nullptr);
     if (rc) return rc;
     // (the launches' tangent sweeps raise no device error: nothing to ask, as in hank_jvp)
-    HIPC(ctx, copy_dagg(ctx, dagg_out, ctx->batch.dagg_cm, N, hipMemcpyDeviceToHost));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
+    return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
 }
 
 static int run_fused(hank_ctx *ctx, TanWork &w) {
-    int grc = ensure_graphs(ctx, w, 1);
+    const int grc = ensure_dual_graphs(ctx, w);
     if (grc) return grc;
     HIPC(ctx, join_side(ctx));
     HIPC(ctx, ctx->spans.begin(DUAL_BACK, ctx->stream));
@@ -2091,13 +2124,13 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
     int rc = ensure_tanwork(ctx, N, &wp);
     if (rc) return rc;
     TanWork &w = *wp;
-    rc = ensure_graphs(ctx, w, 0);
+    rc = ensure_tan_graphs(ctx, w, false, 0);
     if (rc) return rc;
     rc = ensure_fn(ctx, nh);
     if (rc) return rc;
     HIPC(ctx, join_side(ctx));      // D_1 and the {w, ig D} records come from the primal's forward sweep
     hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
-    HIPC(ctx, hipGraphLaunch(w.g_back, s));
+    HIPC(ctx, hipGraphLaunch(w.tan_back(false), s));
     batch_none(ctx);      // (w.dpol no longer belongs to a caller's batch)
     // 2. the lottery impulse of every lag and input at once
     hipLaunchKernelGGL(k_fn_transpose, dim3((unsigned)((G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256), 0, s, w.dpol, P, G, N, ctx->fn.dpT);
@@ -2475,24 +2508,9 @@ static int vjp_het_args(hank_ctx *ctx, int n_het, const void *in, int M, const v
     return HANK_OK;
 }
 
-// the four entries' one body: args is the entry's rule; the _dev form leaves the copy to enqueue_vjp and stays asynchronous
-static int vjp(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, const void *), int n_het, const double *agg_bar, int M, double *xhh_bar, bool dev) {
-    ENTER(ctx);
-    int rc = args(ctx, n_het, agg_bar, M, xhh_bar);
-    if (rc) return rc;
-    CotWork *w = nullptr;
-    rc = enqueue_vjp(ctx, n_het, agg_bar, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, M, dev ? xhh_bar : nullptr, &w);
-    if (rc || dev) return rc;
-    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
-}
-
-// hank_vjp_boundary[_dev]: hank_vjp's path (and its rule for n_het) plus the boundary's cotangents; either may be null (not wanted).
-// The host form stages them in the workspace of this width.
-// hank_vjp_het_boundary[_dev]: the same with hank_vjp_het's rule (args, as in vjp), so Value and UCE carry cotangents to the boundary:
-// enqueue_vjp runs Sweep A with NX > 0 and exports the same two states.
+// The eight entries' one body: args is the entry's rule (hank_vjp's, or hank_vjp_het's under which Value and UCE carry cotangents
+// too); the _dev form leaves the copies to enqueue_vjp and stays asynchronous. value_end_bar, D_init_bar (the _boundary entries):
+// the boundary's cotangents, either may be null (not wanted); the host form stages the wanted ones in the workspace of this width.
 static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, const void *), int n_het, const double *agg_bar, int M, double *xhh_bar,
                         double *value_end_bar, double *D_init_bar, bool dev) {
     ENTER(ctx);
@@ -2500,12 +2518,14 @@ static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *
     if (rc) return rc;
     CotWork *w = nullptr;
     if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, value_end_bar, D_init_bar);
-    rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
-    if (rc) return rc;
     const size_t GM = (size_t)ctx->c.G * M;
-    if (!w->bnd_dbar) {
-        HIPC(ctx, w->bnd_vbar.alloc(GM));
-        HIPC(ctx, w->bnd_dbar.alloc(GM));
+    if (value_end_bar || D_init_bar) {
+        rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
+        if (rc) return rc;
+        if (!w->bnd_dbar) {
+            HIPC(ctx, w->bnd_vbar.alloc(GM));
+            HIPC(ctx, w->bnd_dbar.alloc(GM));
+        }
     }
     rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, value_end_bar ? w->bnd_vbar.get() : nullptr, D_init_bar ? w->bnd_dbar.get() : nullptr);
     if (rc) return rc;
@@ -2515,6 +2535,9 @@ static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     ctx->errmsg[0] = 0;
     return HANK_OK;
+}
+static int vjp(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, const void *), int n_het, const double *agg_bar, int M, double *xhh_bar, bool dev) {
+    return vjp_boundary(ctx, args, n_het, agg_bar, M, xhh_bar, nullptr, nullptr, dev);
 }
 
 extern "C" {
@@ -2700,6 +2723,20 @@ static int hx_outputs(hank_ctx *ctx, int NX, const TanBatch *b, double **T_out) 
     return HANK_OK;
 }
 
+// (P, n_het) levels into d_a and (P, n_het, Nk) tangents into d_da (either may be null) from the aggregates, a batch's dagg_cm and the
+// extra outputs' sums hxT: the one place that launches k_het_outputs, and k_bnd_cons behind it
+static int assemble_het_outputs(hank_ctx *ctx, int n_het, int Nk, const double *d_dx, const double *dagg_cm, const double *hxT, const double *bnd_zm, double *d_a, double *d_da) {
+    const size_t P = ctx->c.P;
+    const int nh = ctx->c.n_hh;
+    hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * ((size_t)Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, nh, n_het, hx_count(ctx), Nk, ctx->d_xhh,
+                       d_dx, ctx->d_agg, dagg_cm, ctx->d_zd, ctx->hx.S.get(), hxT, d_a, d_da);
+    // under a dD_0 seed the productivity marginal of dD_t does not vanish: consumption gains w_t zm_t + tr_t om_t (hank_boundary.h)
+    if (d_da && n_het >= 2 && bnd_zm)
+        hipLaunchKernelGGL(k_bnd_cons, dim3((unsigned)((P * Nk + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, nh, n_het, Nk, ctx->d_xhh, bnd_zm, d_da);
+    HIPC(ctx, hipGetLastError());
+    return HANK_OK;
+}
+
 static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double *agg_out, double *dagg_out, bool dev) {
     if (!ctx) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
@@ -2737,12 +2774,9 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
         rc = hx_outputs(ctx, n_het - 2, b, &hxT);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * (Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, hx_count(ctx), Nk, ctx->d_xhh,
-                       d_dx, ctx->d_agg, b ? b->dagg_cm : nullptr, ctx->d_zd, ctx->hx.S.get(), hxT, d_a, tan ? d_da : nullptr);
-    // under a dD_0 seed the productivity marginal of dD_t does not vanish: consumption gains w_t zm_t + tr_t om_t (hank_boundary.h)
-    if (tan && n_het == 2 && b->bnd_zm)
-        hipLaunchKernelGGL(k_bnd_cons, dim3((unsigned)((P * N + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, (int)n_het, N, ctx->d_xhh, b->bnd_zm, d_da);
-    HIPC(ctx, hipGetLastError());
+    // (a batch with boundary seeds is served for n_het <= 2 only, above)
+    rc = assemble_het_outputs(ctx, n_het, Nk, d_dx, b ? b->dagg_cm : nullptr, hxT, b ? b->bnd_zm : nullptr, d_a, tan ? d_da : nullptr);
+    if (rc) return rc;
     if (!dev) {
         if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, d_a, sizeof(double) * P * n_het, hipMemcpyDeviceToHost, ctx->stream));
         if (tan) HIPC(ctx, hipMemcpyAsync(dagg_out, d_da, sizeof(double) * P * n_het * N, hipMemcpyDeviceToHost, ctx->stream));
@@ -2769,84 +2803,41 @@ int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het) {
 }
 
 // ---- hank_jvp_het[_dev]: every declared output's tangent from ONE pair of sweeps, boundary seeds included ----
-// The launch family's tangent sweeps, whatever the context's schedule and whichever family wrote the record (run_jvp's ensure_seg /
-// ensure_lwg), as hank_jvp_boundary runs them. For n_het > 2 the forward launches carry NX = n_het - 2 extra reductions
+// The request with a count (enqueue_tan_launch), seeded when a seed is given. For n_het > 2 the forward launches carry NX = n_het - 2 extra reductions
 // (k_tan_fwd_hx): the in-period sums T_o,t = sum f_o,t dD_t - sum f_c,o,t D_t da'_t of Value and UCE (KrusellSmith.jl:80;
 // ForwardIteration.jl:303-307 dots every key with the same D_t) from the dD_t the sweep itself carries — so a dD_0 seed
 // (ForwardIteration.jl:293) needs nothing more, and a dV_P seed (BackwardIteration.jl:85) is already in dpol. k_het_outputs then
-// assembles (P, n_het, N) as hank_get_het_outputs does, with k_bnd_cons behind it under a dD_0 seed.
+// assembles (P, n_het, N) as hank_get_het_outputs does (assemble_het_outputs).
 // Launches: TAN_BACK P + 2 (P + 4 with seeds), TAN_FWD P + 3 (P + 5 with seeds), one more for n_het > 2; k_het_outputs (and
 // k_bnd_cons) behind the spans. n_het <= 2 launches hank_jvp's / hank_jvp_boundary's own graphs.
 // The batch is named as those two entries name theirs under the launch schedule, so the readers behave as they do after them.
-static int enqueue_jvp_het(hank_ctx *ctx, int n_het, const double *dxhh, const double *dvalue_end, const double *dD_init, hipMemcpyKind kind, int N,
-                           double *d_dagg_out, TanWork **out) {
-    const Consts &c = ctx->c;
-    const size_t P = c.P, GN = (size_t)c.G * N, nh = c.n_hh;
-    const int NX = n_het > 2 ? n_het - 2 : 0, SX = hx_count(ctx);
-    const bool bnd = dvalue_end || dD_init;
+static int enqueue_jvp_het(hank_ctx *ctx, const TanReq &q, int N, double *d_dagg_out, TanWork **out) {
     TanWork *w = nullptr;
-    int rc = ensure_tanwork(ctx, N, &w);
+    int rc = enqueue_tan_launch(ctx, q, N, &w);
     if (rc) return rc;
-    if (bnd && (rc = ensure_bnd_bufs(ctx, *w)) != HANK_OK) return rc;
-    if (!w->het_out) HIPC(ctx, w->het_out.alloc(P * het_max(ctx) * N));
-    if (NX > 0) {
-        HIPC(ctx, join_side(ctx));      // the record's sums read D_t
-        rc = ensure_hx_record(ctx);      // (before the capture: the graph holds the record's addresses)
-        if (rc) return rc;
-        if (!w->hx_T) {
-            HIPC(ctx, w->hx_parts.alloc(P * (size_t)w->nbf * SX * N));
-            HIPC(ctx, w->hx_T.alloc((size_t)N * P * SX));      // (last: a failed allocation is tried again by the next call)
-        }
-    }
-    if (dxhh) HIPC(ctx, hipMemcpyAsync(w->dxhh, dxhh, sizeof(double) * nh * P * N, kind, ctx->stream));
-    else HIPC(ctx, hipMemsetAsync(w->dxhh, 0, sizeof(double) * nh * P * N, ctx->stream));
-    if (bnd) {
-        const struct { double *dst; const double *src; } in[2] = {{w->bnd_dV, dvalue_end}, {w->bnd_dD, dD_init}};
-        for (const auto &a : in) {
-            if (a.src) HIPC(ctx, hipMemcpyAsync(a.dst, a.src, sizeof(double) * GN, kind, ctx->stream));
-            else HIPC(ctx, hipMemsetAsync(a.dst, 0, sizeof(double) * GN, ctx->stream));
-        }
-    }
-    rc = run_jvp(ctx, *w, bnd, dD_init != nullptr, NX);
+    rc = assemble_het_outputs(ctx, q.n_het, N, w->dxhh.get(), w->dagg_cm.get(), w->hx_T.get(), q.dD_init ? w->bnd_zm.get() : nullptr, nullptr, w->het_out.get());
     if (rc) return rc;
-    hipLaunchKernelGGL(k_het_outputs, dim3((unsigned)((P * ((size_t)N + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, n_het, SX, N, ctx->d_xhh,
-                       w->dxhh.get(), ctx->d_agg, w->dagg_cm.get(), ctx->d_zd, ctx->hx.S.get(), w->hx_T.get(), (double *)nullptr, w->het_out.get());
-    if (dD_init && n_het >= 2)
-        hipLaunchKernelGGL(k_bnd_cons, dim3((unsigned)((P * N + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, n_het, N, ctx->d_xhh, w->bnd_zm.get(), w->het_out.get());
-    HIPC(ctx, hipGetLastError());
-    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->het_out, sizeof(double) * P * n_het * N, hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_dagg_out) HIPC(ctx, hipMemcpyAsync(d_dagg_out, w->het_out, sizeof(double) * ctx->c.P * q.n_het * N, hipMemcpyDeviceToDevice, ctx->stream));
     *out = w;
-    return HANK_OK;
-}
-// the rules: the arguments, then the count (hank_vjp_het's rule), then the record
-static int jvp_het_args(hank_ctx *ctx, int n_het, const void *dxhh, const void *dvalue_end, const void *dD_init, int N, const void *out, bool need_out) {
-    if (!ctx || (!dxhh && !dvalue_end && !dD_init) || (need_out && !out) || N < 1)
-        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_het: bad argument (N=%d; at least one of dxhh, dvalue_end, dD_init must be given)", N);
-    const int rc = het_count_ok(ctx, "hank_jvp_het", n_het, true);
-    if (rc) return rc;
-    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_het");
     return HANK_OK;
 }
 extern "C" {
 int hank_jvp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const double *d_dvalue_end, const double *d_dD_init, int32_t N, double *d_dagg_out) {
     ENTER(ctx);
-    const int rc = jvp_het_args(ctx, n_het, d_dxhh, d_dvalue_end, d_dD_init, N, d_dagg_out, false);
-    if (rc) return rc;
+    const TanReq q{n_het, d_dxhh, d_dvalue_end, d_dD_init, hipMemcpyDeviceToDevice, d_dvalue_end || d_dD_init};
+    const int rc = tan_seed_args(ctx, "hank_jvp_het", true, q, N, d_dagg_out, false);
     TanWork *w = nullptr;
-    return enqueue_jvp_het(ctx, n_het, d_dxhh, d_dvalue_end, d_dD_init, hipMemcpyDeviceToDevice, N, d_dagg_out, &w);
+    return rc ? rc : enqueue_jvp_het(ctx, q, N, d_dagg_out, &w);
 }
 int hank_jvp_het(hank_ctx *ctx, int32_t n_het, const double *dxhh, const double *dvalue_end, const double *dD_init, int32_t N, double *dagg_out) {
     ENTER(ctx);
-    int rc = jvp_het_args(ctx, n_het, dxhh, dvalue_end, dD_init, N, dagg_out, true);
-    if (rc) return rc;
+    const TanReq q{n_het, dxhh, dvalue_end, dD_init, hipMemcpyHostToDevice, dvalue_end || dD_init};
+    int rc = tan_seed_args(ctx, "hank_jvp_het", true, q, N, dagg_out, true);
     TanWork *w = nullptr;
-    rc = enqueue_jvp_het(ctx, n_het, dxhh, dvalue_end, dD_init, hipMemcpyHostToDevice, N, nullptr, &w);
+    if (!rc) rc = enqueue_jvp_het(ctx, q, N, nullptr, &w);
     if (rc) return rc;
     // (the launches' tangent sweeps raise no device error: nothing to ask, as in hank_jvp)
-    HIPC(ctx, hipMemcpyAsync(dagg_out, w->het_out, sizeof(double) * ctx->c.P * n_het * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
+    return tan_host_tail(ctx, dagg_out, w->het_out, (size_t)ctx->c.P * n_het * N);
 }
 }
 

@@ -183,6 +183,11 @@ def _p(arr: np.ndarray):
     return arr.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _opt(arr):
+    """an optional array's pointer: None (a null pointer) stays None"""
+    return None if arr is None else _p(arr)
+
+
 class HouseholdBlock:
     """One hank_ctx: the device-resident household block of a SequenceModel.
 
@@ -306,11 +311,12 @@ class HouseholdBlock:
         self._chk(self._lib.hank_jvp_dev(self._ctx, C.c_void_p(d_dxhh_ptr), int(N), C.c_void_p(d_dagg_ptr)))
 
     # -- the transposed block ---------------------------------------------------------------
-    def vjp(self, agg_bar, n_het: int = 1) -> np.ndarray:
-        """J(x)' agg_bar at the recorded primal (hank_vjp; the reverse rules of ForwardIteration.jl:339-420 and of the
-        backward loop). agg_bar: (P,) or (P, M) for n_het = 1, (P, n_het, M) in general — cotangents of the aggregates of
-        the policy variable and (n_het = 2) of consumption. -> xhh_bar (n_hh, P, M)."""
+    def _cotangents(self, agg_bar, n_het, het):
+        """the cotangents of `vjp` (het False: (P,), (P, M) for n_het = 1, or (P, n_het, M)) or of `vjp_het` (het True:
+        (P, n_het, M) only) -> (M, yb (P, n_het, M) column-major)"""
         yb = np.asarray(agg_bar, dtype=np.float64)
+        if het and yb.ndim != 3:
+            raise ValueError("agg_bar must be (P, n_het, M)")
         if yb.ndim == 1:
             yb = yb[:, None]
         if yb.ndim == 2:
@@ -318,7 +324,14 @@ class HouseholdBlock:
                 raise ValueError("agg_bar must be (P, n_het, M) when n_het > 1")
             yb = yb[:, None, :]
         M = yb.shape[2]
-        yb = _f(yb, (self.P, int(n_het), M) if int(n_het) in (1, 2) else None)      # (the library refuses any other n_het)
+        served = 1 <= int(n_het) <= (4 if het else 2)
+        return M, _f(yb, (self.P, int(n_het), M) if served else None)      # (the library refuses any other n_het)
+
+    def vjp(self, agg_bar, n_het: int = 1) -> np.ndarray:
+        """J(x)' agg_bar at the recorded primal (hank_vjp; the reverse rules of ForwardIteration.jl:339-420 and of the
+        backward loop). agg_bar: (P,) or (P, M) for n_het = 1, (P, n_het, M) in general — cotangents of the aggregates of
+        the policy variable and (n_het = 2) of consumption. -> xhh_bar (n_hh, P, M)."""
+        M, yb = self._cotangents(agg_bar, n_het, het=False)
         out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
         self._chk(self._lib.hank_vjp(self._ctx, int(n_het), _p(yb), M, _p(out)))
         return out
@@ -331,11 +344,7 @@ class HouseholdBlock:
         """`vjp` with cotangents on every heterogeneous output (hank_vjp_het): agg_bar (P, n_het, M), n_het up to the count
         declared with `set_het_outputs` — outputs 2, 3 are Value and UCE, which are not affine in the policy.
         -> xhh_bar (n_hh, P, M). n_het <= 2 runs `vjp`'s path: the same bits."""
-        yb = np.asarray(agg_bar, dtype=np.float64)
-        if yb.ndim != 3:
-            raise ValueError("agg_bar must be (P, n_het, M)")
-        M = yb.shape[2]
-        yb = _f(yb, (self.P, int(n_het), M) if 1 <= int(n_het) <= 4 else None)      # (the library refuses any other n_het)
+        M, yb = self._cotangents(agg_bar, n_het, het=True)
         out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
         self._chk(self._lib.hank_vjp_het(self._ctx, int(n_het), _p(yb), M, _p(out)))
         return out
@@ -356,12 +365,8 @@ class HouseholdBlock:
             s = s.reshape((self.G, s.shape[2]), order="F")
         return _f(s, (self.G, N))
 
-    def jvp_boundary(self, dxhh=None, dvalue_end=None, dD_init=None) -> np.ndarray:
-        """the tangent sweeps with seeds on the boundary as well (hank_jvp_boundary): dxhh (n_hh, P, N) as in `jvp`, dvalue_end
-        and dD_init (n_a, n_e, N) — tangents of `ss_end.value` (BackwardIteration.jl:85) and `ss_initial.D`
-        (ForwardIteration.jl:293); None means zeros, at least one must be given. -> dagg (P, N). Always the launch family. The
-        batch is current afterwards: `dpolicy_seq`, `grid_aggregates`, `het_outputs(2, dxhh)` serve it (pass zeros for a dxhh of
-        None)."""
+    def _directions(self, dxhh, dvalue_end, dD_init):
+        """the inputs of `jvp_boundary` / `jvp_het` -> (N, dx (n_hh, P, N), dv (G, N), dd (G, N)), column-major; None stays None"""
         given = [np.asarray(v) for v in (dxhh, dvalue_end, dD_init) if v is not None]
         if not given:
             raise ValueError("at least one of dxhh, dvalue_end, dD_init must be given")
@@ -370,11 +375,18 @@ class HouseholdBlock:
         if dxhh is not None:
             dx = np.asarray(dxhh, dtype=np.float64)
             dx = _f(dx[:, :, None] if dx.ndim == 2 else dx, (self.n_hh, self.P, N))
-        dv, dd = self._boundary_seed(dvalue_end, N), self._boundary_seed(dD_init, N)
+        return N, dx, self._boundary_seed(dvalue_end, N), self._boundary_seed(dD_init, N)
+
+    def jvp_boundary(self, dxhh=None, dvalue_end=None, dD_init=None) -> np.ndarray:
+        """the tangent sweeps with seeds on the boundary as well (hank_jvp_boundary): dxhh (n_hh, P, N) as in `jvp`, dvalue_end
+        and dD_init (n_a, n_e, N) — tangents of `ss_end.value` (BackwardIteration.jl:85) and `ss_initial.D`
+        (ForwardIteration.jl:293); None means zeros, at least one must be given. -> dagg (P, N). Always the launch family. The
+        batch is current afterwards: `dpolicy_seq`, `grid_aggregates`, `het_outputs(2, dxhh)` serve it (pass zeros for a dxhh of
+        None)."""
+        N, dx, dv, dd = self._directions(dxhh, dvalue_end, dD_init)
         out = np.empty((self.P, N), order="F")
         self.calls["jvp"] += 1
-        self._chk(self._lib.hank_jvp_boundary(self._ctx, None if dx is None else _p(dx), None if dv is None else _p(dv),
-                                              None if dd is None else _p(dd), N, _p(out)))
+        self._chk(self._lib.hank_jvp_boundary(self._ctx, _opt(dx), _opt(dv), _opt(dd), N, _p(out)))
         return out
 
     def jvp_boundary_dev(self, d_dxhh_ptr: int, d_dvalue_end_ptr: int, d_dD_init_ptr: int, N: int, d_dagg_ptr: int = 0):
@@ -386,15 +398,7 @@ class HouseholdBlock:
         """`vjp` with the boundary's cotangents (hank_vjp_boundary): -> (xhh_bar (n_hh, P, M), value_end_bar (n_a, n_e, M),
         D_init_bar (n_a, n_e, M)) — the cotangents of the household inputs, of `ss_end.value` and of `ss_initial.D`; the exact
         transpose of `jvp_boundary` followed by `het_outputs(n_het)`. agg_bar as in `vjp`; xhh_bar equals `vjp`'s bit for bit."""
-        yb = np.asarray(agg_bar, dtype=np.float64)
-        if yb.ndim == 1:
-            yb = yb[:, None]
-        if yb.ndim == 2:
-            if int(n_het) != 1:
-                raise ValueError("agg_bar must be (P, n_het, M) when n_het > 1")
-            yb = yb[:, None, :]
-        M = yb.shape[2]
-        yb = _f(yb, (self.P, int(n_het), M) if int(n_het) in (1, 2) else None)      # (the library refuses any other n_het)
+        M, yb = self._cotangents(agg_bar, n_het, het=False)
         out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
         vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F")
         db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F")
@@ -412,19 +416,10 @@ class HouseholdBlock:
         at least one must be given), n_het up to the count declared with `set_het_outputs`. -> dagg (P, n_het, N), the shape of
         `het_outputs`' dagg. Value and UCE ride in the forward sweep, so boundary seeds reach them too. Always the launch
         family; n_het <= 2 gives the bits of `jvp` / `jvp_boundary` under the launch schedule."""
-        given = [np.asarray(v) for v in (dxhh, dvalue_end, dD_init) if v is not None]
-        if not given:
-            raise ValueError("at least one of dxhh, dvalue_end, dD_init must be given")
-        N = given[0].shape[-1] if given[0].ndim == 3 else 1
-        dx = None
-        if dxhh is not None:
-            dx = np.asarray(dxhh, dtype=np.float64)
-            dx = _f(dx[:, :, None] if dx.ndim == 2 else dx, (self.n_hh, self.P, N))
-        dv, dd = self._boundary_seed(dvalue_end, N), self._boundary_seed(dD_init, N)
+        N, dx, dv, dd = self._directions(dxhh, dvalue_end, dD_init)
         out = np.empty((self.P, max(int(n_het), 1), N), order="F")
         self.calls["jvp"] += 1
-        self._chk(self._lib.hank_jvp_het(self._ctx, int(n_het), None if dx is None else _p(dx), None if dv is None else _p(dv),
-                                         None if dd is None else _p(dd), N, _p(out)))
+        self._chk(self._lib.hank_jvp_het(self._ctx, int(n_het), _opt(dx), _opt(dv), _opt(dd), N, _p(out)))
         return out
 
     def jvp_het_dev(self, n_het: int, d_dxhh_ptr: int, d_dvalue_end_ptr: int, d_dD_init_ptr: int, N: int, d_dagg_ptr: int = 0):
@@ -436,16 +431,11 @@ class HouseholdBlock:
         """`vjp_het` with the boundary's cotangents (hank_vjp_het_boundary): agg_bar (P, n_het, M) -> (xhh_bar (n_hh, P, M),
         value_end_bar (n_a, n_e, M), D_init_bar (n_a, n_e, M)); the exact transpose of `jvp_het`. A boundary cotangent that is
         not wanted (value_end / D_init False) is not computed and comes back as None. xhh_bar equals `vjp_het`'s bit for bit."""
-        yb = np.asarray(agg_bar, dtype=np.float64)
-        if yb.ndim != 3:
-            raise ValueError("agg_bar must be (P, n_het, M)")
-        M = yb.shape[2]
-        yb = _f(yb, (self.P, int(n_het), M) if 1 <= int(n_het) <= 4 else None)      # (the library refuses any other n_het)
+        M, yb = self._cotangents(agg_bar, n_het, het=True)
         out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
         vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if value_end else None
         db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if D_init else None
-        self._chk(self._lib.hank_vjp_het_boundary(self._ctx, int(n_het), _p(yb), M, _p(out), None if vb is None else _p(vb),
-                                                  None if db is None else _p(db)))
+        self._chk(self._lib.hank_vjp_het_boundary(self._ctx, int(n_het), _p(yb), M, _p(out), _opt(vb), _opt(db)))
         return out, vb, db
 
     def vjp_het_boundary_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_value_end_bar_ptr: int = 0, d_D_init_bar_ptr: int = 0):
@@ -501,8 +491,7 @@ class HouseholdBlock:
         vb, db = self._boundary_seed(value_bar, M), self._boundary_seed(D_bar, M)
         out = np.empty((self.n_hh, M), order="F")
         it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
-        self._chk(self._lib.hank_ss_vjp(self._ctx, int(n_het), None if yb is None else _p(yb), None if vb is None else _p(vb),
-                                        None if db is None else _p(db), M, float(tol), int(max_iter), _p(out), it, res))
+        self._chk(self._lib.hank_ss_vjp(self._ctx, int(n_het), _opt(yb), _opt(vb), _opt(db), M, float(tol), int(max_iter), _p(out), it, res))
         self._ss_done("ss_vjp", ("nu", "lambda"), it, res, tol, max_iter, check)
         return out, (int(it[0]), int(it[1]))
 

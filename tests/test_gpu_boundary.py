@@ -1,7 +1,7 @@
 """hank_jvp_boundary / hank_vjp_boundary: tangents and cotangents on the boundary of the household block — the terminal marginal
 value V_P (`ss_end.value`, BackwardIteration.jl:85) and the initial distribution D_0 (`ss_initial.D`, ForwardIteration.jl:293) — on
 the MI355X (csrc/hank_boundary.h). The reference is always the CPU oracle's loop with duals on the boundary
-(tests/boundary_cases.py, itself pinned by tests/test_boundary_host.py) or numpy; a device product is compared with another
+(tests/sweep_refs.py, itself pinned by tests/test_boundary_host.py) or numpy; a device product is compared with another
 device product only for bits. (1) the JVP against the oracle loop: dagg, dpolicy_seq, both halves of grid_aggregates,
 het_outputs(2); (2) the VJP: the full transposed boundary Jacobian at 40x2, inner products everywhere else, xhh_bar's bits;
 (3) bits; (4) the context's state rules and the host layers. Tolerance: the suite's rel 1e-10 + abs 1e-12 (cases.close)."""
@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 import pytest
 
-import boundary_cases as bc
+import sweep_refs as bc
 import cases
 from cases import close as _close
 
@@ -57,18 +57,18 @@ def _seeds(name, N, seed=0):
 def _check_jvp(hb, name, y, dV, dD, what):
     """one hank_jvp_boundary and every reader of its batch against the oracle loop"""
     _, V, D, x, orc = _case(name)
-    ref = bc.oracle_boundary(orc, x, V, D, y=y, dV=dV, dD=dD)
-    N = ref["dagg"].shape[1]
+    ref = bc.oracle_sweeps(orc, x, V, D, y=y, dV=dV, dD=dD)
+    N = ref["dagg"].shape[2]
     dagg = hb.jvp_boundary(y, dV, dD)
     assert dagg.shape == (hb.P, N)
     assert hb.info()["last_tangent_family_name"] == "launch-per-period"
-    _close(dagg, ref["dagg"], what=what + " dagg")
+    _close(dagg, ref["dagg"][:, 0], what=what + " dagg")
     _close(hb.dpolicy_seq(N).transpose(2, 0, 1, 3), ref["dpol"], what=what + " dpolicy")
     agg2, dagg2 = hb.grid_aggregates(N)
     _close(agg2, ref["agg2"], what=what + " grid aggregate"); _close(dagg2, ref["dagg2"], what=what + " grid aggregate's partials")
     aggs, daggs = hb.het_outputs(2, np.zeros(x.shape + (N,)) if y is None else y)
-    _close(aggs[:, 0], ref["agg"], what=what + " agg"); _close(aggs[:, 1], ref["cons"], what=what + " consumption")
-    _close(daggs[:, 0, :], ref["dagg"], what=what + " het output 0"); _close(daggs[:, 1, :], ref["dcons"], what=what + " het output 1")
+    _close(aggs[:, 0], ref["agg"][:, 0], what=what + " agg"); _close(aggs[:, 1], ref["cons"], what=what + " consumption")
+    _close(daggs[:, 0, :], ref["dagg"][:, 0], what=what + " het output 0"); _close(daggs[:, 1, :], ref["dcons"], what=what + " het output 1")
     return ref
 
 
@@ -86,7 +86,7 @@ def test_jvp_boundary_matches_the_oracle_loop_krusell_smith_130x3(hank, oracle_m
         y, dV, dD = _seeds(name, N)
         for mode, (wy, wv, wd) in MODES.items():
             ref = _check_jvp(hb, name, y if wy else None, dV if wv else None, dD if wd else None, f"{name} N={N} {mode}")
-            assert np.abs(ref["dagg"]).max() > 1e-6 and np.abs(ref["dcons"]).max() > 1e-6, mode
+            assert np.abs(ref["dagg"][:, 0]).max() > 1e-6 and np.abs(ref["dcons"]).max() > 1e-6, mode
     finally:
         hb.close()
 
@@ -136,8 +136,8 @@ def test_vjp_boundary_is_the_oracles_full_boundary_jacobian_transposed_40x2(hank
     G, P = n_a * n_e, x.shape[1]
     U = np.eye(G).reshape((n_a, n_e, G), order="F")
     Z = np.zeros_like(U)
-    ref = bc.oracle_boundary(orc, x, V, D, dV=np.concatenate([U, Z], axis=2), dD=np.concatenate([Z, U], axis=2))
-    J = np.stack([ref["dagg"], ref["dcons"]])                   # (output, t, seed)
+    ref = bc.oracle_sweeps(orc, x, V, D, dV=np.concatenate([U, Z], axis=2), dD=np.concatenate([Z, U], axis=2))
+    J = np.stack([ref["dagg"][:, 0], ref["dcons"]])                   # (output, t, seed)
     assert np.abs(J[:, :, :G]).max() > 1e-6 and np.abs(J[:, :, G:]).max() > 1e-3
     yb = np.zeros((P, 2, 2 * P))
     for o in range(2):
@@ -174,8 +174,8 @@ def _boundary_columns(name):
         _, V, D, x, orc = _case(name)
         _, dV, dD = _seeds(name, 3, seed=2)
         dV[:, :, 1] = 0.0; dD[:, :, 0] = 0.0
-        ref = bc.oracle_boundary(orc, x, V, D, dV=dV, dD=dD)
-        _JB[name] = (dV, dD, np.stack([ref["dagg"], ref["dcons"]]))
+        ref = bc.oracle_sweeps(orc, x, V, D, dV=dV, dD=dD)
+        _JB[name] = (dV, dD, np.stack([ref["dagg"][:, 0], ref["dcons"]]))
         assert np.all(np.abs(_JB[name][2]).max(axis=1) > 1e-6), name
     return _JB[name]
 

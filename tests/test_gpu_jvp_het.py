@@ -2,7 +2,7 @@
 inputs, on the terminal marginal value V_P (`ss_end.value`, BackwardIteration.jl:85) and on the initial distribution D_0
 (`ss_initial.D`, ForwardIteration.jl:293) — Value and UCE ride in the forward launches (k_tan_fwd_hx) — and
 the transpose with the boundary's cotangents. The reference is always the CPU oracle's loop with duals on the boundary
-(tests/het_boundary_cases.py, pinned by tests/test_jvp_het_host.py) or numpy; a device product is compared with another device
+(tests/sweep_refs.py, pinned by tests/test_jvp_het_host.py) or numpy; a device product is compared with another device
 product only for bits. (1) against the oracle loop; (2) edges; (3) records; (4) bits; (5) the transposed entry; (6) state rules;
 (7) host layers. Tolerance: the suite's rel 1e-10 + abs 1e-12 (cases.close)."""
 import ctypes
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import cases
-import het_boundary_cases as hbc
+import sweep_refs as hbc
 from cases import close as _close
 
 pytestmark = pytest.mark.gpu
@@ -71,7 +71,7 @@ def _ref(name, N, mode, seed=0):
         args, V, D, x, orc, n_het = _case(name)
         y, dV, dD = _seeds(name, N, seed)
         wy, wv, wd = MODES[mode]
-        _REF[key] = hbc.oracle_het_boundary(orc, x, V, D, args[4], n_het, y=y if wy else None, dV=dV if wv else None, dD=dD if wd else None)
+        _REF[key] = hbc.oracle_sweeps(orc, x, V, D, args[4], n_het, y=y if wy else None, dV=dV if wv else None, dD=dD if wd else None)
     return _REF[key]
 
 
@@ -181,6 +181,39 @@ def test_jvp_het_bits(hank, oracle_mod, N):
         hb.close()
 
 
+@pytest.mark.parametrize("N", [2, 18])
+def test_order_of_first_use_does_not_matter(hank, oracle_mod, N):
+    """every variant of the launch family's tangent entries at one width, first used in one order on one context and in the reverse
+    order on another: the same bits from every call and the same policy partials behind it, and the same count of captured graphs
+    — the two pairs (without and with seeds) and the two forward graphs with extra reductions that were asked for. A graph slot
+    picked wrongly, or a graph captured before a buffer it names was allocated, shows here. N = 2: two directions per lane, the
+    gather form, one row group; N = 18: the source-stationary form, two row groups (the geometries k_tan_fwd_hx exists for)."""
+    y, dV, dD = _seeds("hank", N)
+    calls = [lambda hb: hb.jvp(y), lambda hb: hb.jvp_boundary(y, dV, dD), lambda hb: hb.jvp_boundary(y), lambda hb: hb.jvp_het(y, n_het=2),
+             lambda hb: hb.jvp_het(y, dV, dD, n_het=2), lambda hb: hb.jvp_het(y, n_het=3), lambda hb: hb.jvp_het(y, dV, dD, n_het=4)]
+
+    def run(order):
+        hb, V, D, x, orc, n_het = _ctx(hank, "hank", "launch")
+        try:
+            assert n_het == 4
+            hb.primal(x)
+            before = hb.stats()["graphs_captured"]
+            got = {}
+            for k in order:
+                got[k] = (calls[k](hb), hb.dpolicy_seq(N))
+                assert hb.info()["last_tangent_family_name"] == "launch-per-period"
+            return got, hb.stats()["graphs_captured"] - before
+        finally:
+            hb.close()
+    a, captured_a = run(range(len(calls)))
+    b, captured_b = run(reversed(range(len(calls))))
+    for k in range(len(calls)):
+        assert np.array_equal(a[k][0], b[k][0]), f"call {k}"
+        assert np.array_equal(a[k][1], b[k][1]), f"dpolicy_seq after call {k}"
+    assert np.abs(a[6][0][:, 2:, :]).max() > 0
+    assert captured_a == captured_b == 6
+
+
 def test_the_device_pointer_forms_agree_and_the_tangent_batch_survives_vjp_het_boundary(hank, oracle_mod):
     import torch
     hb, V, D, x, orc, n_het = _ctx(hank, "ks13")
@@ -233,7 +266,7 @@ def test_vjp_het_boundary_is_the_oracles_full_boundary_jacobian_transposed_40x2(
     G, P = n_a * n_e, x.shape[1]
     U = np.eye(G).reshape((n_a, n_e, G), order="F")
     Z = np.zeros_like(U)
-    ref = hbc.oracle_het_boundary(orc, x, V, D, args[4], 3, dV=np.concatenate([U, Z], axis=2), dD=np.concatenate([Z, U], axis=2))
+    ref = hbc.oracle_sweeps(orc, x, V, D, args[4], 3, dV=np.concatenate([U, Z], axis=2), dD=np.concatenate([Z, U], axis=2))
     J = ref["dagg"].transpose(1, 0, 2)                          # (output, t, seed)
     assert np.abs(J[2, :, :G]).max() > 1e-6 and np.abs(J[2, :, G:]).max() > 1e-3
     yb = np.zeros((P, 3, 3 * P))
