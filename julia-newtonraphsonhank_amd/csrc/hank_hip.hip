@@ -1043,6 +1043,25 @@ static int x_tan_front(XSection &sec, XTan *w) {
     }
     return HANK_OK;
 }
+// HANK_XADDR_BUF: the Dual-pass sweeps reach the record and dpol through buffer descriptors with 32-bit offsets, and the work units
+// (on their pointer) with a 32-bit index (hank_xsweep.h: XRecOff, hank_xaddr.h: x_addr_fits). The
+// record's offsets, and whether every stream of the widest Dual pass of this context fits (asked where the schedule is chosen:
+// a context that does not fit keeps the per-period launches, as one whose LDS does not fit does)
+static XRecOff x_rec_off(const hank_ctx *ctx) {
+    const Record &R = ctx->R;
+    const char *b = ctx->rec_slab;
+    auto off = [&](const void *p) { return (unsigned)((const char *)p - b); };
+    XRecOff o{};
+    o.rec = b; o.bytes = (unsigned)ctx->rec_bytes;
+    o.pol = off(R.pol); o.ib = off(R.ib); o.A = off(R.A); o.B = off(R.B); o.u = off(R.u); o.v = off(R.v); o.s = off(R.s); o.kc = off(R.kc);
+    o.lo = off(R.lo); o.lw = off(R.lw); o.ig = off(R.ig); o.Dseq = off(R.Dseq);
+    return o;
+}
+static bool x_dual_addr_fits(const hank_ctx *ctx) {
+    if (!HANK_XADDR_BUF) return true;
+    const Consts &c = ctx->c;
+    return x_addr_fits(ctx->rec_bytes, (unsigned long long)c.P, XG, (unsigned long long)c.G, XD_MAX, (unsigned long long)((c.n_a + XRW - 1) / XRW), XUCAP);
+}
 // span PRIMAL_BACK: the Float64 backward sweep at the context's x (d_xhh) and boundary, on ONE XCD's workgroups; with a one-pass
 // batch `dual` it carries the batch's partials too (k_xdual_back)
 static int x_back(XSection &sec, XTan *dual = nullptr) {
@@ -1057,6 +1076,7 @@ static int x_back(XSection &sec, XTan *dual = nullptr) {
         XDualBackArgs db{};
         db.p = ab; db.dxr = dual->dxr; db.dxw = dual->dxw; db.dxt = dual->dxt; db.Ntot = dual->N; db.n0 = ps.n0; db.N = ps.N;
         db.st_ds = X.st_ds; db.dpol = dual->dpol + ps.dpol_off; db.groups = ps.groups;
+        db.ro = x_rec_off(ctx); db.dpol_bytes = (unsigned)((size_t)c.P * ps.groups * c.G * ps.D * sizeof(double));
         x_launch_dual_back(sec, X, c, ps.D, db);
     } else x_launch_primal_back(sec, X, c, ab);
     HIPC(ctx, ctx->spans.end(PRIMAL_BACK, sec.stream(), 1));
@@ -1123,6 +1143,7 @@ static int x_tan_fwd(XSection &sec, XTan *w, int p, bool val) {
     if (!val) { const int rc = ensure_lwg(ctx); if (rc) return rc; }
     XSweepFwdArgs fa = x_fwd_args(ctx, val);
     fa.sy = X.sync + 2 + 2 * p + 1; fa.st = X.st_dD; fa.daggpart = w->daggpart; fa.groups = ps.groups; fa.dpol = w->dpol + ps.dpol_off;
+    fa.ro = x_rec_off(ctx); fa.dpol_bytes = (unsigned)((size_t)ctx->c.P * ps.groups * ctx->c.G * ps.D * sizeof(double));
     x_launch_fwd(sec, X, ctx->c, ps.D, val, fa);
     return HANK_OK;
 }
@@ -1742,7 +1763,7 @@ static bool x_dual_back_fits(const hank_ctx *ctx, int D) {
     return ctx->xdual_back && x_has_dual_back(X) && 64 * (ctx->c.n_e + 1) <= X.maxt && x_lds_dual_back(ctx->c, D) <= (size_t)X.lds_max;
 }
 static bool use_x_fused(const hank_ctx *ctx, int N) {
-    if (ctx->schedule < 1 || !x_tan_fits(ctx, N)) return false;
+    if (ctx->schedule < 1 || !x_tan_fits(ctx, N) || !x_dual_addr_fits(ctx)) return false;
     if (ctx->schedule == 1) return true;
     return N <= XG * ctx->xw.dmax && x_dual_back_fits(ctx, ctx->xw.dmax);
 }

@@ -158,6 +158,66 @@ __device__ __forceinline__ void st_mode_i(int *p, int x) {
     else *p = x;
 }
 
+// buffer accesses: ONE scalar descriptor for the whole record, a 32-bit lane offset (the row pair: shared by every array), a scalar
+// offset (array, period and column)
+typedef unsigned int wv2u __attribute__((ext_vector_type(2)));
+typedef unsigned int wv4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wide_rsrc(const void *p) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0x7fffffff, 0x00020000);
+}
+__device__ __forceinline__ double wide_ld64(__amdgpu_buffer_rsrc_t rs, int vo, int so) {
+    const wv2u q = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, 0);
+    return __hiloint2double((int)q.y, (int)q.x);
+}
+__device__ __forceinline__ wv2u wide_ld2i(__amdgpu_buffer_rsrc_t rs, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, 0); }
+template <int AUX>
+__device__ __forceinline__ void wide_ld2d(__amdgpu_buffer_rsrc_t rs, int vo, int so, double &a, double &b) {    // two adjacent doubles: one 16-byte load
+    const wv4u q = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, AUX);
+    a = __hiloint2double((int)q.y, (int)q.x); b = __hiloint2double((int)q.w, (int)q.z);
+}
+__device__ __forceinline__ wv4u wide_ld128(__amdgpu_buffer_rsrc_t rs, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0); }
+__device__ __forceinline__ void wide_st2d_nt(double a, double b, __amdgpu_buffer_rsrc_t rs, int vo, int so) {
+    wv4u q;
+    q.x = (unsigned)__double2loint(a); q.y = (unsigned)__double2hiint(a); q.z = (unsigned)__double2loint(b); q.w = (unsigned)__double2hiint(b);
+    __builtin_amdgcn_raw_buffer_store_b128(q, rs, vo, so, 2);
+}
+__device__ __forceinline__ void wide_st64_nt(double v, __amdgpu_buffer_rsrc_t rs, int vo, int so) {
+    wv2u q;
+    q.x = (unsigned)__double2loint(v); q.y = (unsigned)__double2hiint(v);
+    __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, so, 2);
+}
+
+// the same with the cache mode as a parameter, for the persistent sweeps (hank_xsweep.h, HANK_XADDR_BUF). AUX: 0 plain, 2 nontemporal,
+// 16 sc1 (bypasses the CU's L1: served by the XCD's L2). The descriptor's size is the allocation's, but that is NO safety net: the
+// hardware's range check sees the lane offset and the immediate only, and the sweeps put array, period and column into the scalar
+// offset, which it does not see. A wrong scalar offset reads and writes wherever it points; what keeps the offsets right is
+// x_addr_fits (hank_xaddr.h) and the tests against the launches.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void *p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
+}
+template <int AUX>
+__device__ __forceinline__ double buf_ld64(__amdgpu_buffer_rsrc_t rs, int vo, int so) {
+    const wv2u q = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, AUX);
+    return __hiloint2double((int)q.y, (int)q.x);
+}
+template <int AUX>
+__device__ __forceinline__ int buf_ld32(__amdgpu_buffer_rsrc_t rs, int vo, int so) { return (int)__builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, AUX); }
+template <int AUX>
+__device__ __forceinline__ void buf_st64(double v, __amdgpu_buffer_rsrc_t rs, int vo, int so) {
+    wv2u q;
+    q.x = (unsigned)__double2loint(v); q.y = (unsigned)__double2hiint(v);
+    __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, so, AUX);
+}
+template <int AUX>
+__device__ __forceinline__ void buf_st32(int v, __amdgpu_buffer_rsrc_t rs, int vo, int so) { __builtin_amdgcn_raw_buffer_store_b32((unsigned)v, rs, vo, so, AUX); }
+template <int AUX>
+__device__ __forceinline__ void buf_st2d(double a, double b, __amdgpu_buffer_rsrc_t rs, int vo, int so) {
+    wv4u q;
+    q.x = (unsigned)__double2loint(a); q.y = (unsigned)__double2hiint(a); q.z = (unsigned)__double2loint(b); q.w = (unsigned)__double2hiint(b);
+    __builtin_amdgcn_raw_buffer_store_b128(q, rs, vo, so, AUX);
+}
+constexpr int BUF_AUX_REC = HANK_ST_REC == 1 ? 16 : (HANK_ST_REC == 2 ? 2 : 0);      // the record stores' mode as a buffer access
+
 // acc += sum_{k=k0}^{n-1} P[k*ps] * V[k*vs], added in index order. The n_e-long mixing sums sit on every launch's
 // critical path; as a plain loop each LDS read waits for the one before (n_e round trips of ~100 clocks: the launch
 // floor is 4.1 us at n_e = 4 and 6.2 us at n_e = 11). Reads are issued four columns at a time, the order of the

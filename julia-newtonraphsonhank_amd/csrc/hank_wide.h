@@ -104,34 +104,7 @@ __device__ __forceinline__ void wide_mix(double (&x)[R][KR], double *lst, const 
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// buffer accesses: ONE scalar descriptor for the whole record, a 32-bit lane offset (the row pair: shared by every array), a scalar
-// offset (array, period and column)
-typedef unsigned int wv2u __attribute__((ext_vector_type(2)));
-typedef unsigned int wv4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wide_rsrc(const void *p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ double wide_ld64(__amdgpu_buffer_rsrc_t rs, int vo, int so) {
-    const wv2u q = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, 0);
-    return __hiloint2double((int)q.y, (int)q.x);
-}
-__device__ __forceinline__ wv2u wide_ld2i(__amdgpu_buffer_rsrc_t rs, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, 0); }
-template <int AUX>
-__device__ __forceinline__ void wide_ld2d(__amdgpu_buffer_rsrc_t rs, int vo, int so, double &a, double &b) {    // two adjacent doubles: one 16-byte load
-    const wv4u q = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, AUX);
-    a = __hiloint2double((int)q.y, (int)q.x); b = __hiloint2double((int)q.w, (int)q.z);
-}
-__device__ __forceinline__ wv4u wide_ld128(__amdgpu_buffer_rsrc_t rs, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0); }
-__device__ __forceinline__ void wide_st2d_nt(double a, double b, __amdgpu_buffer_rsrc_t rs, int vo, int so) {
-    wv4u q;
-    q.x = (unsigned)__double2loint(a); q.y = (unsigned)__double2hiint(a); q.z = (unsigned)__double2loint(b); q.w = (unsigned)__double2hiint(b);
-    __builtin_amdgcn_raw_buffer_store_b128(q, rs, vo, so, 2);
-}
-__device__ __forceinline__ void wide_st64_nt(double v, __amdgpu_buffer_rsrc_t rs, int vo, int so) {
-    wv2u q;
-    q.x = (unsigned)__double2loint(v); q.y = (unsigned)__double2hiint(v);
-    __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, so, 2);
-}
+// (the buffer accesses — wide_rsrc, wide_ld*, wide_st* — live in hank_kernels.h: the persistent sweeps of hank_xsweep.h share them)
 
 // dev build only (make stamp): s_memtime of wave 0 / lane 0 of workgroup 0 at fixed points of periods [100, 104)
 // dev timing builds (wrong numbers): HANK_WIDE_TIMING_L2 confines the record to two periods (every line an L2 hit: what the HBM

@@ -42,7 +42,11 @@
 #ifndef HANK_XBACK_ZREG
 #define HANK_XBACK_ZREG 1          // persistent backward sweeps: egm_Y's z_e from the register the kernel holds (dev knob: 0 = a global load per period)
 #endif
+#ifndef HANK_XADDR_BUF
+#define HANK_XADDR_BUF 1           // Dual-pass persistent sweeps: every stream through a few buffer descriptors, 32-bit offsets (dev knob: 0 = a 64-bit pointer per array)
+#endif
 #include "hank_kernels.h"
+#include "hank_xaddr.h"
 #include <type_traits>
 
 namespace hank {
@@ -108,6 +112,33 @@ struct XRows {
     __device__ __forceinline__ double load_one(size_t row, int k) const {            // slot k of a row (sc1, 8 bytes)
         return D == 1 ? xld(base + row) : xld(base + ((size_t)(k / 2) * plane + row) * 2 + (k & 1));
     }
+    // HANK_XADDR_BUF: the row index in two parts — the lane's (rv, 32-bit, often loop-invariant) and the wave's (rs_, scalar: ping-pong
+    // half, group, column) — straight into the instruction's vector and scalar offsets. init_buf: a descriptor for D = 1 too
+    static constexpr int RB = D == 1 ? 8 : 16;       // bytes of a row in one plane
+    __device__ __forceinline__ void init_buf(double *p, int rows_total) {
+        base = p; plane = (size_t)rows_total;
+        rs = __builtin_amdgcn_make_buffer_rsrc(p, 0, rows_total * 8 * D, 0x00020000);
+    }
+    __device__ __forceinline__ void load_vs(int rv, int rs_, double *v) const {     // sc1
+        if (D == 1) {
+            v[0] = buf_ld64<16>(rs, rv * RB, rs_ * RB);
+        } else {
+#pragma unroll
+            for (int k = 0; k < D / 2; k++) {
+                const xv4u q = __builtin_amdgcn_raw_buffer_load_b128(rs, rv * RB, (k * (int)plane + rs_) * RB, 16);
+                v[2 * k] = __hiloint2double((int)q.y, (int)q.x);
+                v[2 * k + 1] = __hiloint2double((int)q.w, (int)q.z);
+            }
+        }
+    }
+    __device__ __forceinline__ void store_vs(int rv, int rs_, const double *v) const {      // plain
+        if (D == 1) {
+            buf_st64<0>(v[0], rs, rv * RB, rs_ * RB);
+        } else {
+#pragma unroll
+            for (int k = 0; k < D / 2; k++) buf_st2d<0>(v[2 * k], v[2 * k + 1], rs, rv * RB, (k * (int)plane + rs_) * RB);
+        }
+    }
     __device__ __forceinline__ void store(size_t row, const double *v) const {      // plain stores: the line stays in the XCD's L2
         if (D == 1) {
             base[row] = v[0];
@@ -133,6 +164,24 @@ __device__ __forceinline__ void xstore_row(double *p, const double *v) {
     }
 }
 template <int D>
+__device__ __forceinline__ void xstore_row_buf(__amdgpu_buffer_rsrc_t rs, int vo, int so, const double *v) {     // the same, HANK_XADDR_BUF
+    if (D == 1) {
+        buf_st64<2>(v[0], rs, vo, so);
+    } else {
+#pragma unroll
+        for (int k = 0; k < D / 2; k++) buf_st2d<2>(v[2 * k], v[2 * k + 1], rs, vo + 16 * k, so);
+    }
+}
+template <int D>
+__device__ __forceinline__ void xload_row_buf(__amdgpu_buffer_rsrc_t rs, int vo, int so, double *v) {           // plain loads
+    if (D == 1) {
+        v[0] = buf_ld64<0>(rs, vo, so);
+    } else {
+#pragma unroll
+        for (int k = 0; k < D / 2; k++) wide_ld2d<0>(rs, vo + 16 * k, so, v[2 * k], v[2 * k + 1]);
+    }
+}
+template <int D>
 __device__ __forceinline__ void xload_row_plain(const double *p, double *v) {  // read-only inputs (written by an earlier launch)
     if (D == 1) {
         v[0] = *p;
@@ -141,6 +190,11 @@ __device__ __forceinline__ void xload_row_plain(const double *p, double *v) {  /
         for (int k = 0; k < D / 2; k++) { const double2 q = reinterpret_cast<const double2 *>(p)[k]; v[2 * k] = q.x; v[2 * k + 1] = q.y; }
     }
 }
+
+// HANK_XADDR_BUF: a sweep-long wave-uniform integer whose TESTS are made anew where they are used (one s_cmp / s_bitcmp on one
+// scalar register). Left to itself the compiler hoists every test `k < ne`, `flags & bit` out of the period loop as a 64-bit lane
+// mask of its own: more of them than there are scalar registers, so each costs two v_readlane per period.
+__device__ __forceinline__ int xopaque(int v) { asm volatile("" : "+s"(v)); return v; }
 
 struct XGroup { int x, c, S, ok; };
 
@@ -287,11 +341,20 @@ __device__ __forceinline__ void xpublish(XSync *sy, int x, int c, unsigned episo
 // four knots around the guessed bracket — is fetched in ONE batch of independent loads up front: behind the branches
 // of the bracket search each of them would be a round trip of its own. Anything else (a gallop after a far move) is
 // loaded on demand.
-struct XKnots {
+// BUF (HANK_XADDR_BUF, k_xdual_back): the column is reached through a buffer descriptor over the whole knot state — a 32-bit lane
+// offset (the knot's index) and a scalar offset (ping-pong half, group, column) instead of a 64-bit address per load.
+template <bool BUF>
+struct XKnotsT {
     const double *p;
+    __amdgpu_buffer_rsrc_t rs;
+    int so;                     // BUF: the column's byte offset in the state
     int a, n, i0, i1, i2, i3;
     double sa, sam1, s0, sN, w0, w1, w2, w3;
     double ze;                  // the column's productivity z_e, from the register the kernel keeps it in for the whole sweep
+    __device__ __forceinline__ double ld(int i) const {
+        if constexpr (BUF) return buf_ld64<16>(rs, i * 8, so);
+        else return xld(p + i);
+    }
     __device__ __forceinline__ void preload(const double *col, int a_, int n_, int guess, double ze_) {
         p = col; a = a_; n = n_; ze = ze_;
         sa = xld(col + a);
@@ -304,6 +367,20 @@ struct XKnots {
             const int q = guess < n - 1 ? guess : n - 2;
             i0 = q > 0 ? q - 1 : 0; i1 = q; i2 = q + 1; i3 = q + 2 < n ? q + 2 : n - 1;
             w0 = xld(col + i0); w1 = xld(col + i1); w2 = xld(col + i2); w3 = xld(col + i3);
+        }
+    }
+    __device__ __forceinline__ void preload(__amdgpu_buffer_rsrc_t rs_, int so_, int a_, int n_, int guess, double ze_) {     // the same batch, BUF
+        rs = rs_; so = so_; a = a_; n = n_; ze = ze_;
+        sa = ld(a);
+        sam1 = ld(a > 0 ? a - 1 : 0);
+        s0 = ld(0);
+        sN = ld(n - 1);
+        i0 = i1 = i2 = i3 = -1;
+        w0 = w1 = w2 = w3 = 0.0;
+        if (guess >= 0) {
+            const int q = guess < n - 1 ? guess : n - 2;
+            i0 = q > 0 ? q - 1 : 0; i1 = q; i2 = q + 1; i3 = q + 2 < n ? q + 2 : n - 1;
+            w0 = ld(i0); w1 = ld(i1); w2 = ld(i2); w3 = ld(i3);
         }
     }
     // The straight-line front of egm_Y (hank_kernels.h), on the preloaded registers alone — no operator[], no branch: the
@@ -338,12 +415,13 @@ struct XKnots {
         if (i == i3) return w3;
         if (i == 0) return s0;
         if (i == n - 1) return sN;
-        return xld(p + i);
+        return ld(i);
     }
 };
+using XKnots = XKnotsT<false>;
 
-template <> struct YFrontOf<XKnots> { static constexpr bool value = HANK_XBACK_FRONT != 0; };
-template <> struct YColumnZOf<XKnots> { static constexpr bool value = HANK_XBACK_ZREG != 0; };
+template <bool BUF> struct YFrontOf<XKnotsT<BUF>> { static constexpr bool value = HANK_XBACK_FRONT != 0; };
+template <bool BUF> struct YColumnZOf<XKnotsT<BUF>> { static constexpr bool value = HANK_XBACK_ZREG != 0; };
 
 __device__ __forceinline__ double xwave_sum(double v) {            // butterfly: every lane ends with the same sum, fixed order
 #pragma unroll
@@ -407,12 +485,15 @@ __device__ __forceinline__ void xtile_mix(const double *tl, const double *P, int
 
 // the same with the column of Pi held in registers (16 unrolled steps, the ones beyond n_e predicated off): no LDS read for
 // the coefficient, and every tile read of the pass can be in flight at once
-template <int SL, int NS, bool FMA = false>
+// BRK (HANK_XADDR_BUF; the caller passes xopaque(ne)): the pass ends at the first k >= ne — one scalar compare per step on one
+// register, where the sixteen hoisted predicates `k < ne` are sixteen spilled lane masks (two v_readlane each, every period)
+template <int SL, int NS, bool FMA = false, bool BRK = false>
 __device__ __forceinline__ void xtile_mix_reg(const double *tl, const double (&pr)[16], int ne, double *out) {
     const int ks = 64 * SL;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-        if (k < ne) {
+        if (BRK && k > 0 && k >= ne) break;
+        if (BRK || k < ne) {
             double v[SL];
             if (SL == 1) v[0] = tl[(size_t)k * ks];
             else {
@@ -428,6 +509,15 @@ __device__ __forceinline__ void xtile_mix_reg(const double *tl, const double (&p
 // ================================ the Float64 sweeps ==========================================
 // One group (the XCD with id 0) runs them; the workgroups that landed elsewhere leave at once. They write the policy
 // sequence, the distribution path and the linearisation record the tangent sweeps — of either implementation — read.
+// HANK_XADDR_BUF: where the record's arrays start in its ONE allocation (bytes): an access is descriptor + 32-bit lane offset +
+// scalar offset (array + period) instead of a 64-bit base per array — more bases than a wave has scalar registers
+struct XRecOff {
+    const char *rec;
+    unsigned bytes;
+    unsigned pol, ib, A, B, u, v, s, kc, lo, lw, ig, Dseq;
+};
+// (x_addr_fits, the host's question whether 32-bit offsets reach every stream of a launch, is plain C++ of its own: hank_xaddr.h)
+
 struct XBackArgs {
     Consts c;
     const double *ss_value;     // [G] terminal marginal value (BackwardIteration.jl:85)
@@ -1024,11 +1114,14 @@ struct XDualBackArgs {
     double *st_ds;              // [2][XG][G][D]
     double *dpol;               // [P][groups][G][D]
     int groups;
+    XRecOff ro;                 // HANK_XADDR_BUF: the record's allocation and its arrays' offsets in it ...
+    unsigned dpol_bytes;        // ... and this launch's dpol in bytes (x_addr_fits has checked that 32-bit offsets reach everything)
 };
 
 template <int D, int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     constexpr int NSL = D + 1, SL = XSlots<NSL>::SL, IV = D;
+    constexpr bool XB = HANK_XADDR_BUF != 0;            // streams through buffer descriptors (see XRecOff)
     extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_dual_back (under this kernel) is the host's sum of the same pieces
     const XBackArgs &A = B.p;
     const Consts &c = A.c;
@@ -1082,7 +1175,13 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     const size_t hs = (size_t)XG * G, gx = (size_t)x * G;
     double *const sS = A.st_s;
     XRows<D> rows;
-    rows.init(B.st_ds, 2 * hs);
+    if constexpr (XB) rows.init_buf(B.st_ds, 2 * XG * G); else rows.init(B.st_ds, 2 * hs);
+    // XB: four descriptors (record, dpol, knots, partials) instead of a dozen 64-bit bases; this lane's row as ONE loop-invariant
+    // element index (every array's lane offset is that times the element size); the writer flags as one mask in one scalar register
+    __amdgpu_buffer_rsrc_t rrec, rdp, rkn;
+    if constexpr (XB) { rrec = buf_rsrc(B.ro.rec, B.ro.bytes); rdp = buf_rsrc(B.dpol, B.dpol_bytes); rkn = buf_rsrc(sS, (unsigned)(2 * hs * 8)); }
+    const int ipt = (int)pt, igx = x * G, ihs = XG * G;
+    const int rcm0 = __builtin_amdgcn_readfirstlane((rc0 ? 1 : 0) | (rc1 ? 2 : 0) | (rc2 ? 4 : 0) | (rc3 ? 8 : 0) | (rc4 ? 16 : 0) | (rc5 ? 32 : 0) | (rc6 ? 64 : 0) | (rc7 ? 128 : 0));
     double *const myt = tile + ((size_t)e * 64 + lane) * SL;
     if (!syncw) {
         double z[NSL];
@@ -1107,15 +1206,17 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
 #pragma unroll
             for (int k = 0; k < NSL; k++) tv[k] = 0.0;
             if (own) {
-                XKnots kn;
-                kn.preload(sS + (size_t)cur * hs + gx + (size_t)e * na, a, na, guess, ze);
+                XKnotsT<XB> kn;
+                const int icb = cur * ihs + igx + e * na;          // this column in the state half being read (elements; wave-uniform); `rb` below is the pointer path's
+                if constexpr (XB) kn.preload(rkn, icb * 8, a, na, guess, ze);
+                else kn.preload(sS + (size_t)cur * hs + gx + (size_t)e * na, a, na, guess, ze);
                 // the partials' rows at the bracket of the period before, in the same batch of loads as the knots: the bracket
                 // rarely moves by more than a knot per period, and behind the search every gather is a round trip of its own
                 const size_t rb = (size_t)cur * hs + gx + (size_t)e * na;
                 const int q = guess < 0 ? 0 : (guess < na - 1 ? guess : na - 2);
                 double w0[D], w1[D];
-                rows.load(rb + q, w0);
-                rows.load(rb + q + 1, w1);
+                if constexpr (XB) { rows.load_vs(q, icb, w0); rows.load_vs(q + 1, icb, w1); }
+                else { rows.load(rb + q, w0); rows.load(rb + q + 1, w1); }
                 const YOut o = egm_Y(cl, kn, a, e, xsh[4 * t], xsh[4 * t + 1], xsh[4 * t + 2], A.err, t, guess);
                 guess = o.ib;
                 tv[IV] = o.V;
@@ -1131,14 +1232,14 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                     } else if (o.ib == q + 1) {
 #pragma unroll
                         for (int k = 0; k < D; k++) d0[k] = w1[k];
-                        rows.load(rb + o.ib + 1, d1);
+                        if constexpr (XB) rows.load_vs(o.ib + 1, icb, d1); else rows.load(rb + o.ib + 1, d1);
                     } else if (o.ib == q - 1) {
 #pragma unroll
                         for (int k = 0; k < D; k++) d1[k] = w0[k];
-                        rows.load(rb + o.ib, d0);
+                        if constexpr (XB) rows.load_vs(o.ib, icb, d0); else rows.load(rb + o.ib, d0);
                     } else {
-                        rows.load(rb + o.ib, d0);
-                        rows.load(rb + o.ib + 1, d1);
+                        if constexpr (XB) { rows.load_vs(o.ib, icb, d0); rows.load_vs(o.ib + 1, icb, d1); }
+                        else { rows.load(rb + o.ib, d0); rows.load(rb + o.ib + 1, d1); }
                     }
                 }
 #pragma unroll
@@ -1147,14 +1248,25 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                     dg[k] = o.A * d0[k] + o.B * d1[k];
                     tv[k] = o.u * dr + o.v * ((xa * dr + (ze * dw + dtr)) - dg[k]);
                 }
-                xstore_row<D>(B.dpol + (((size_t)t * B.groups + x) * G + pt) * D, dg);
-                const size_t ro = (size_t)t * G + pt;
-                if (rc0) A.R.pol[ro] = o.g;
-                if (rc1) A.R.ib[ro] = o.ib;
-                if (rc2) A.R.A[ro] = o.A;
-                if (rc3) A.R.B[ro] = o.B;
-                if (rc4) A.R.u[ro] = o.u;
-                if (rc5) A.R.v[ro] = o.v;
+                if constexpr (XB) {
+                    xstore_row_buf<D>(rdp, ipt * (8 * D), (int)((unsigned)((t * B.groups + x) * G) * (unsigned)(8 * D)), dg);
+                    const int tg = t * G, rcm = xopaque(rcm0);
+                    if (rcm & 1) buf_st64<BUF_AUX_REC>(o.g, rrec, ipt * 8, (int)(B.ro.pol + (unsigned)tg * 8u));
+                    if (rcm & 2) buf_st32<BUF_AUX_REC>(o.ib, rrec, ipt * 4, (int)(B.ro.ib + (unsigned)tg * 4u));
+                    if (rcm & 4) buf_st64<BUF_AUX_REC>(o.A, rrec, ipt * 8, (int)(B.ro.A + (unsigned)tg * 8u));
+                    if (rcm & 8) buf_st64<BUF_AUX_REC>(o.B, rrec, ipt * 8, (int)(B.ro.B + (unsigned)tg * 8u));
+                    if (rcm & 16) buf_st64<BUF_AUX_REC>(o.u, rrec, ipt * 8, (int)(B.ro.u + (unsigned)tg * 8u));
+                    if (rcm & 32) buf_st64<BUF_AUX_REC>(o.v, rrec, ipt * 8, (int)(B.ro.v + (unsigned)tg * 8u));
+                } else {
+                    xstore_row<D>(B.dpol + (((size_t)t * B.groups + x) * G + pt) * D, dg);
+                    const size_t ro = (size_t)t * G + pt;
+                    if (rc0) A.R.pol[ro] = o.g;
+                    if (rc1) A.R.ib[ro] = o.ib;
+                    if (rc2) A.R.A[ro] = o.A;
+                    if (rc3) A.R.B[ro] = o.B;
+                    if (rc4) A.R.u[ro] = o.u;
+                    if (rc5) A.R.v[ro] = o.v;
+                }
             }
             if (!syncw) xtile_store_n<SL, NSL>(myt, tv);
             XSTAMP(0, son, i, 2);
@@ -1166,7 +1278,7 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
             const int tx = P - 1 - i;
             if (own) {
                 double mx[NSL];
-                xtile_mix_reg<SL, NSL>(tile + (size_t)lane * SL, pr, ne, mx);
+                xtile_mix_reg<SL, NSL, false, XB>(tile + (size_t)lane * SL, pr, XB ? xopaque(ne) : ne, mx);
                 const double bE = mx[IV] * c.beta;
                 const double ex = -1.0 / c.gamma;
                 if (pow_domain_error(bE, ex)) set_err(A.err, ERR_DOMAIN, tx, e, a);
@@ -1180,10 +1292,18 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                     const double dr1 = dxsh[(tx * 3 + 0) * D + k], dw1 = dxsh[(tx * 3 + 1) * D + k], dt1 = dxsh[(tx * 3 + 2) * D + k];
                     ds[k] = kc * mx[k] - rho * ((ze * dw1 + dt1) + s1 * dr1);
                 }
-                sS[(size_t)(i & 1) * hs + gx + pt] = s1;
-                rows.store((size_t)(i & 1) * hs + gx + pt, ds);
-                if (rc6) A.R.s[(size_t)tx * G + pt] = s1;
-                if (rc7) A.R.kc[(size_t)tx * G + pt] = kc;
+                if constexpr (XB) {
+                    const int ihb = (i & 1) * ihs + igx, rcm = xopaque(rcm0);
+                    buf_st64<0>(s1, rkn, ipt * 8, ihb * 8);
+                    rows.store_vs(ipt, ihb, ds);
+                    if (rcm & 64) buf_st64<BUF_AUX_REC>(s1, rrec, ipt * 8, (int)(B.ro.s + (unsigned)(tx * G) * 8u));
+                    if (rcm & 128) buf_st64<BUF_AUX_REC>(kc, rrec, ipt * 8, (int)(B.ro.kc + (unsigned)(tx * G) * 8u));
+                } else {
+                    sS[(size_t)(i & 1) * hs + gx + pt] = s1;
+                    rows.store((size_t)(i & 1) * hs + gx + pt, ds);
+                    if (rc6) A.R.s[(size_t)tx * G + pt] = s1;
+                    if (rc7) A.R.kc[(size_t)tx * G + pt] = kc;
+                }
             }
             episode++;
             XSTAMP(0, son, i, 4);
@@ -1237,6 +1357,9 @@ struct XSweepFwdArgs {
     const int *overflow;        // k_xunits_fwd's flag: a member's walk did not fit XUCAP units — nothing is computed from a truncated list
     const int2 *units;          // [P][members][XUCAP] {e | ja << 4 | cnt << 16, ta | tb << 8 | nv << 16}
     int all_members;            // dev knob: every period waits for every member
+    XRecOff ro;                 // HANK_XADDR_BUF (VAL, D > 0): the record's allocation and its arrays' offsets in it ...
+    unsigned dpol_bytes;        // ... and this launch's dpol in bytes (x_addr_fits has checked that 32-bit offsets reach everything). The work units
+                                // keep their POINTER and take a 32-bit scalar index: a unit's address is wave-uniform, a third buffer resource only added spills
 };
 
 template <int D, bool VAL, int MAXT>
@@ -1247,6 +1370,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     constexpr int IV = D;                               // the value's slot
     constexpr int DD = D > 0 ? D : 1;
     constexpr bool PIREG = NSL < 4;                     // the mixing's coefficients in registers
+    constexpr bool XB = HANK_XADDR_BUF != 0 && VAL && D > 0;      // the Dual pass: streams through buffer descriptors (see XRecOff)
     extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_fwd (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const Record &R = A.R;
@@ -1304,7 +1428,17 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #pragma unroll
     for (int k = 0; k < 16; k++) pr[k] = (PIREG && k < ne) ? c.Pi[ne * e + k] : 0.0;
     XRows<SP> rows;
-    rows.init(A.st, 2 * hs);
+    // (XB: sizes and offsets in 32-bit integers from scalar sources. The 64-bit product GM above is computed by the vector unit, and a
+    // descriptor or a scalar offset derived from it sits in vector registers: every state access then runs inside a loop that reads
+    // the descriptor back lane by lane)
+    const int iGM = ne * Sact * 64;
+    if constexpr (XB) rows.init_buf(A.st, 2 * XG * iGM); else rows.init(A.st, 2 * hs);
+    // XB: three descriptors (record, dpol, state) instead of a 64-bit base per array; the work units keep their pointer (see unit_ld). A lane's offset is an element index
+    // times the element size — this row's (ipt, loop-invariant) or a unit's source row (once per unit) — and the array, the period
+    // and the column go into the instruction's scalar offset
+    __amdgpu_buffer_rsrc_t rrec, rdp;
+    if constexpr (XB) { rrec = buf_rsrc(A.ro.rec, A.ro.bytes); rdp = buf_rsrc(A.dpol, A.dpol_bytes); }
+    const int ipt = e * na + (own ? r : 0), igx = x * iGM, ihs = XG * iGM, islot = (e * Sact + cW) * 64;
     double *const myt = tile + ((size_t)e * 64 + lane) * SL;
     double mxp[NSL];                                    // this lane's row of the previous period (the state it stored)
 #pragma unroll
@@ -1314,7 +1448,8 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         double sv[SP];
 #pragma unroll
         for (int k = 0; k < SP; k++) sv[k] = k < NSL ? mxp[k] : 0.0;
-        if (live) rows.store(slot, sv);                 // D_0; it carries no partials
+        if constexpr (XB) { if (live) rows.store_vs(lane, igx + islot, sv); }
+        else if (live) rows.store(slot, sv);                 // D_0; it carries no partials
     }
     // this lane's own-row record of the period about to be processed (what the aggregate and the record need). At a recorded
     // primal the term dpol_t D_t of the aggregate is taken where the policy partials are loaded anyway — at the SOURCE rows —
@@ -1333,6 +1468,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #endif
     auto prefetch = [&](int t_) {
         const int t = XTPER(2, t_);
+        if constexpr (XB) {
+            polr = buf_ld64<0>(rrec, ipt * 8, (int)(A.ro.pol + (unsigned)(t * G) * 8u));
+            xload_row_buf<DD>(rdp, ipt * (8 * D), (int)((unsigned)((t * A.groups + x) * G) * (unsigned)(8 * D)), dpr);
+            return;
+        }
         const size_t ro = (size_t)t * G + (size_t)e * na + (own ? r : 0);       // (a virtual row carries row 0's policy and partials)
         polr = R.pol[ro];
         if constexpr (D > 0) xload_row_plain<DD>(A.dpol + ((size_t)t * A.groups + x) * (size_t)G * D + ((size_t)e * na + (own ? r : 0)) * D, dpr);
@@ -1345,9 +1485,13 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     int qlo[2];
     double qw[2], qg[2], qdn[2], qdp[2][DD], dd[2][SP];
     bool qon[2], qvl[2];
-    const int2 *const ubase = A.units + (size_t)cW * XUCAP;
+    const int2 *const ubase = A.units + (size_t)cW * XUCAP;       // (the pointer path; XB: unit_ld)
+    auto unit_ld = [&](int tu, int u) -> int2 {         // XB: a descriptor's address is wave-uniform — a scalar base and a 32-bit scalar index, no lane arithmetic
+        return A.units[(unsigned)((tu * Sact + cW) * XUCAP + u)];
+    };
     auto unit_desc = [&](int t, int u) -> int2 {        // unit u of this member in period t (u wave-uniform): broadcast load -> scalar registers
-        const int2 q = ubase[(size_t)XTPER(3, t) * Sact * XUCAP + u];
+        int2 q;
+        if constexpr (XB) q = unit_ld(XTPER(3, t), u); else q = ubase[(size_t)XTPER(3, t) * Sact * XUCAP + u];
         return make_int2(__builtin_amdgcn_readfirstlane(q.x), __builtin_amdgcn_readfirstlane(q.y));
     };
     // (branch-free: every lane loads — a lane beyond the unit's sources the unit's last row, an empty unit row 0 of column 0 — and
@@ -1361,19 +1505,32 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         const bool real = i < cnt;
         qvl[u] = !real && i < cnt + nv;                 // a member's virtual row riding on source row 0's record
         qon[u] = real || qvl[u];
-        const size_t cb = (size_t)t * G + (size_t)ue * na;
+        const size_t cb = (size_t)t * G + (size_t)ue * na;      // (the pointer path's column base; XB: icb. It stays in front of j: swapped, every k_xfwd gets another register allocation)
         const int j = real ? ja + i : (qvl[u] ? 0 : min(ja + max(cnt - 1, 0), na - 1));
+        if constexpr (XB) {
+            const int icb = t * G + ue * na;            // the unit's column in period t (elements; wave-uniform)
+            qlo[u] = buf_ld32<0>(rrec, j * 4, (int)(A.ro.lo + (unsigned)icb * 4u));
+            qw[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.lw + (unsigned)icb * 8u));
+            qg[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.ig + (unsigned)icb * 8u));
+            xload_row_buf<DD>(rdp, j * (8 * D), (int)((unsigned)((tp * A.groups + x) * G + ue * na) * (unsigned)(8 * D)), qdp[u]);
+            return;
+        }
         qlo[u] = R.lo[cb + j];
         if constexpr (VAL) { qw[u] = R.lw[cb + j]; if constexpr (D > 0) qg[u] = R.ig[cb + j]; }       // (ig only weights the policy partials)
         else { const double2 wg = R.lwg[cb + j]; qw[u] = wg.x; qg[u] = wg.y; if constexpr (D > 0) qdn[u] = R.Dseq[cb + G + j]; }
         if constexpr (D > 0) xload_row_plain<DD>(A.dpol + (((size_t)tp * A.groups + x) * G + (size_t)ue * na + j) * D, qdp[u]);
     };
-    auto load_state = [&](auto U, size_t hb, int2 d, int i0) {
+    auto load_state = [&](auto U, size_t hb, int hc, int2 d, int i0) {       // hc: the state half being read (hb = hc * hs)
         constexpr int u = decltype(U)::value;
         const int ue = d.x & 15, ja = (d.x >> 4) & 0xfff, cnt = (d.x >> 16) & 0xfff;
 #pragma unroll
         for (int k = 0; k < SP; k++) dd[u][k] = 0.0;
         const int i = i0 + lane, j = ja + i;
+        if constexpr (XB) {
+            const int rowi = qvl[u] ? (i - cnt) * 64 + 63 : (j / XRW) * 64 + j % XRW;       // within the unit's column
+            if (qon[u]) rows.load_vs(rowi, hc * ihs + igx + ue * Sact * 64, dd[u]);
+            return;
+        }
         const size_t row = qvl[u] ? ((size_t)ue * Sact + (i - cnt)) * 64 + 63 : ((size_t)ue * Sact + j / XRW) * 64 + j % XRW;
         if (qon[u]) rows.load(hb + gx + row, dd[u]);
     };
@@ -1387,8 +1544,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         int nu = (srcsh[tu] >> 18) & 0xff;              // (tu == tc but in the timing build: the count belongs to the descriptors)
         nu = t < P ? nu : 0;
         udv[0] = wv < nu; udv[1] = wv + ne < nu;
-        udn[0] = ubase[(size_t)tu * Sact * XUCAP + (udv[0] ? wv : 0)];
-        udn[1] = ubase[(size_t)tu * Sact * XUCAP + (udv[1] ? wv + ne : 0)];
+        if constexpr (XB) { udn[0] = unit_ld(tu, udv[0] ? wv : 0); udn[1] = unit_ld(tu, udv[1] ? wv + ne : 0); }
+        else {
+            udn[0] = ubase[(size_t)tu * Sact * XUCAP + (udv[0] ? wv : 0)];
+            udn[1] = ubase[(size_t)tu * Sact * XUCAP + (udv[1] ? wv + ne : 0)];
+        }
     };
     auto take_units = [&]() {
         ud[0] = udv[0] ? make_int2(__builtin_amdgcn_readfirstlane(udn[0].x), __builtin_amdgcn_readfirstlane(udn[0].y)) : make_int2(0, 0);
@@ -1480,8 +1640,8 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             if constexpr (RECL) {
                 if (need0 && lane < Sact) v0 = rows.load_one(hb + gx + ((size_t)e * Sact + lane) * 64 + 63, IV);
             }
-            load_state(I0, hb, ud[0], 0);
-            load_state(I1, hb, ud[1], 0);
+            load_state(I0, hb, cur, ud[0], 0);
+            load_state(I1, hb, cur, ud[1], 0);
             // Young lottery of a source (ForwardIteration.jl:59-73): (1-w) to row lo, w to row lo+1; the weight's partial is
             // dpol / gap (zero where clamped), times D_{t-1} of the row. Only the parts that land in the unit's own target run
             // [ta, tb) are added (the other part of a seam source belongs to the neighbouring unit).
@@ -1576,7 +1736,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
                 const int tot = ((d.x >> 16) & 0xfff) + ((d.y >> 16) & 0xff);
                 for (int i0 = u2 < 2 * ne ? 64 : 0; i0 < tot; i0 += 64) {
                     load_rec(I0, t, d, i0);
-                    load_state(I0, hb, d, i0);
+                    load_state(I0, hb, cur, d, i0);
                     process(I0, d);
                 }
             }
@@ -1612,7 +1772,8 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
                 double sv[SP];
 #pragma unroll
                 for (int k = 0; k < SP; k++) sv[k] = k < NSL ? mx[k] : 0.0;
-                rows.store((size_t)nxt * hs + slot, sv);
+                if constexpr (XB) rows.store_vs(lane, nxt * ihs + igx + islot, sv);
+                else rows.store((size_t)nxt * hs + slot, sv);
             }
             double at[NAP];
 #pragma unroll
@@ -1628,8 +1789,10 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             }
             if constexpr (VAL) {
                 if (recD) {
-                    if (own) R.Dseq[(size_t)(t + 1) * G + pt] = mx[IV];
-                    else if (virt) A.Dvirt[((size_t)t * ne + e) * 64 + cW] = mx[IV];
+                    if (own) {
+                        if constexpr (XB) buf_st64<BUF_AUX_REC>(mx[IV], rrec, ipt * 8, (int)(A.ro.Dseq + (unsigned)((t + 1) * G) * 8u));
+                        else R.Dseq[(size_t)(t + 1) * G + pt] = mx[IV];
+                    } else if (virt) A.Dvirt[((size_t)t * ne + e) * 64 + cW] = mx[IV];
                     // aggregate on the POST-transition distribution (ForwardIteration.jl:301-307); a virtual row carries row 0's policy
                     at[IV] = live ? polr * mx[IV] : 0.0;
                     at[NSL + IV] = live ? xar * mx[IV] : 0.0;
