@@ -443,6 +443,16 @@ int hank_stats(hank_ctx *ctx, int64_t out[8]);
  * at its record builds them, once per record). */
 int hank_info(hank_ctx *ctx, int64_t out[8]);
 
+/* Which instances of the Dual pass's two persistent sweeps were enqueued last (tests and scripts). beta, gamma, the grids and Pi
+ * are constructor arguments and fixed for a context's life (the reference closes over them in the same way: KrusellSmith.jl:59-80
+ * reads them from the model's parameters in every period), so the backward sweep has instances compiled for the number of
+ * productivity states and for gamma = 2 with the record diet on; they return the generic instance's bits. out[0], out[1]: NE (0 =
+ * read at run time, else 4, 7 or 11) and CRRA (0 = generic powers, 1 = gamma = 2) of the last k_xdual_back; out[2], out[3]: the
+ * same for the last k_xfwd<D, true> (always 0, 0: the forward sweep has no such instance); -1 before the first Dual pass.
+ * HANK_XSPEC (read at hank_create): unset = the CRRA half alone (the NE half measured no gain of its own: DESIGN.md section 4),
+ * 1 = both halves, ne | crra = one of them, 0 = the generic instances. */
+int hank_sweep_instance(hank_ctx *ctx, int32_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

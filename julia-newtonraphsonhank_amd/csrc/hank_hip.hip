@@ -5,6 +5,7 @@
 // and the 2(T-1) dependent launches are replayed from hipGraphs (no host launch cost).
 #include "hank_kernels.h"
 #include "hank_xsweep.h"
+#include "hank_xspec.h"
 #include "hank_jacobian.h"
 #include "hank_wide.h"
 #include "hank_hetx.h"
@@ -137,6 +138,8 @@ struct XWork {
     bool src_valid = false;
     std::list<XTan> tans;           // most recently used first
     int last_blocks = 0;            // sync blocks the last call used, from block 0 (x_status checks their status words)
+    int xspec = XSPEC_CRRA;                   // dev knob HANK_XSPEC (read once, at hank_create): which halves of hank_xspec.h's choice are on
+    int inst[4] = {-1, -1, -1, -1};           // {NE, CRRA} of the last k_xdual_back and of the last k_xfwd<D, true> enqueued (hank_sweep_instance; -1: none yet)
 };
 
 // ---- on-chip wide sweeps (hank_wide.h): tangent buffers per batch width ----
@@ -954,16 +957,36 @@ template <typename F>
 static void x_by_maxt(const XWork &X, F launch) { if (X.maxt == 768) launch(std::integral_constant<int, 768>()); else launch(std::integral_constant<int, 1024>()); }
 #define XL(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(X.grid), x_block(X, c), lds, sec.stream(), a)
 static bool x_has_dual_back(const XWork &X) { return X.maxt == 768; }
-static void x_launch_dual_back(XSection &sec, const XWork &X, const Consts &c, int D, const XDualBackArgs &a) {
+// (the instances compiled for the model's constants, hank_xspec.h, are named behind the generic three: see above)
+static void x_launch_dual_back(XSection &sec, XWork &X, const Consts &c, int D, const XDualBackArgs &a) {      // (X.inst: which instance went out)
     const size_t lds = x_lds_dual_back(c, D);
     if (!x_has_dual_back(X)) return;
-    if (D == 1) XL(k_xdual_back<1, 768>);
-    else if (D == 2) XL(k_xdual_back<2, 768>);
-    else XL(k_xdual_back<4, 768>);
+    const XSpec sp = x_spec(X.xspec, c.n_e, c.gamma, c.diet);
+    X.inst[0] = sp.ne; X.inst[1] = sp.crra;
+    if (!sp.ne && !sp.crra) {
+        if (D == 1) XL(k_xdual_back<1, 768>);
+        else if (D == 2) XL(k_xdual_back<2, 768>);
+        else XL(k_xdual_back<4, 768>);
+        return;
+    }
+    auto by_d = [&](auto ne, auto crra) {
+        constexpr int NE = decltype(ne)::value, CRRA = decltype(crra)::value;
+        if (D == 1) XL(k_xdual_back<1, 768, NE, CRRA>);
+        else if (D == 2) XL(k_xdual_back<2, 768, NE, CRRA>);
+        else XL(k_xdual_back<4, 768, NE, CRRA>);
+    };
+    auto by_crra = [&](auto ne) {
+        if (sp.crra) by_d(ne, std::integral_constant<int, 1>()); else if constexpr (decltype(ne)::value != 0) by_d(ne, std::integral_constant<int, 0>());
+    };
+    if (sp.ne == 4) by_crra(std::integral_constant<int, 4>());
+    else if (sp.ne == 7) by_crra(std::integral_constant<int, 7>());
+    else if (sp.ne == 11) by_crra(std::integral_constant<int, 11>());
+    else by_crra(std::integral_constant<int, 0>());
 }
 // k_xfwd<D, VAL>: D = 0 (the Float64 sweep alone, VAL), 1, 2, 4
-static void x_launch_fwd(XSection &sec, const XWork &X, const Consts &c, int D, bool val, const XSweepFwdArgs &a) {
+static void x_launch_fwd(XSection &sec, XWork &X, const Consts &c, int D, bool val, const XSweepFwdArgs &a) {
     const size_t lds = x_lds_fwd(c, D, val || D == 0);
+    if (val && D > 0) { X.inst[2] = 0; X.inst[3] = 0; }      // (k_xfwd has no instance of hank_xspec.h's: DESIGN.md section 4)
     x_by_maxt(X, [&](auto mt) {
         constexpr int MT = decltype(mt)::value;
         if (D == 0) XL(k_xfwd<0, true, MT>);
@@ -1058,7 +1081,7 @@ static XRecOff x_rec_off(const hank_ctx *ctx) {
     return o;
 }
 static bool x_dual_addr_fits(const hank_ctx *ctx) {
-    if (!HANK_XADDR_BUF) return true;
+    if (!HANK_XADDR_BUF_BACK && !HANK_XADDR_BUF_FWD) return true;
     const Consts &c = ctx->c;
     return x_addr_fits(ctx->rec_bytes, (unsigned long long)c.P, XG, (unsigned long long)c.G, XD_MAX, (unsigned long long)((c.n_a + XRW - 1) / XRW), XUCAP);
 }
@@ -1487,6 +1510,7 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     if (const char *xm = getenv("HANK_XJVP_MAX")) ctx->xjvp_max = atoi(xm);
     if (const char *pm = getenv("HANK_PRIMAL_MEMO")) ctx->memo_on = atoi(pm) != 0;
     if (const char *xd = getenv("HANK_XDUAL_BACK")) ctx->xdual_back = atoi(xd) != 0;
+    ctx->xw.xspec = x_spec_mode(getenv("HANK_XSPEC"));
     int rc = HANK_OK;
     if (ctx->schedule == 0) rc = build_primal_graphs(ctx);
     else rc = x_setup(ctx);
@@ -2230,6 +2254,12 @@ int hank_debug_stamps(hank_ctx *ctx, unsigned long long *out) {
 int hank_stats(hank_ctx *ctx, int64_t out[8]) {
     if (!ctx || !out) return HANK_ERR_BAD_ARG;
     for (int k = 0; k < N_STATS; k++) out[k] = k == SCHEDULE ? ctx->schedule : ctx->stats[k];
+    return HANK_OK;
+}
+
+int hank_sweep_instance(hank_ctx *ctx, int32_t out[4]) {
+    if (!ctx || !out) return HANK_ERR_BAD_ARG;
+    for (int k = 0; k < 4; k++) out[k] = ctx->xw.inst[k];
     return HANK_OK;
 }
 

@@ -46,7 +46,15 @@ __device__ inline void set_err(int *err, int code, int t, int e, int j) {
     }
 }
 
-__device__ inline bool pow_domain_error(double v, double y) { return (v < 0.0) && (y != floor(y)); }
+// CRRA (here and in pow_crra, diet_kc, diet_v, egm_Y, egm_Y_finish): 0 = gamma and the record diet are what the context holds,
+// decided where they are used; 1 = an instance compiled for gamma = 2 with the record diet on (hank_xspec.h chooses it): the
+// caller passes the exponents as the literals -0.5 and -2, and each of these functions IS the arm the generic one takes there —
+// the same expressions in the same order, so the same bits.
+template <int CRRA = 0>
+__device__ inline bool pow_domain_error(double v, double y) {
+    if constexpr (CRRA == 1) return (v < 0.0) && (y == -0.5);       // (-2 is an integer: no error; -0.5 is none)
+    else return (v < 0.0) && (y != floor(y));
+}
 
 // Reciprocal and reciprocal square root of the primal EGM step: the hardware estimate (v_rcp_f64 / v_rsq_f64) and two Newton
 // steps, without the div_scale / div_fmas / div_fixup wrapper of an IEEE division (~18 instructions) or the scaling of an IEEE
@@ -92,7 +100,9 @@ __device__ __forceinline__ double fast_sqrt(double x) {     // x rsqrt(x), one c
 // x^y with the exponents CRRA utility produces most often taken through a reciprocal / reciprocal square root
 // (gamma = 2: y = -1/2 and y = -2; gamma = 1: y = -1) — a generic fp64 pow is a few
 // hundred VALU instructions on the primal sweep's critical path. Same value as pow() to an ulp or two.
+template <int CRRA = 0>
 __device__ inline double pow_crra(double x, double y) {
+    if constexpr (CRRA == 1) return y == -0.5 ? fast_rsqrt(x) : fast_rcp(x * x);
     if (y == -0.5) return fast_rsqrt(x);
     if (y == -2.0) return fast_rcp(x * x);
     if (y == -1.0) return fast_rcp(x);
@@ -257,13 +267,15 @@ __device__ __forceinline__ T mix_sum(T acc, const T *V, int vs, const double *P,
 // lane-sparse coefficient loads are off their critical path: rebuilding cost them 1-3 %) read the record, the persistent
 // tangent sweeps (8 groups re-read the record) rebuild: the same bits either way. Against the textbook expressions the values
 // move by rounding (cm is rebuilt through a cancellation: 1e-13).
+template <int CRRA = 0>
 __device__ __forceinline__ double diet_kc(const Consts &c, double s, double rho, double opr, double wz_tr, double xa) {
     const double cm = (s * opr + wz_tr) - xa;
-    const double k = rho * (c.beta * (-1.0 / c.gamma));
-    return c.gamma == 2.0 ? k * (cm * cm * cm) : k * (cm * cm);
+    const double k = rho * (c.beta * (CRRA == 1 ? -0.5 : -1.0 / c.gamma));
+    return (CRRA == 1 || c.gamma == 2.0) ? k * (cm * cm * cm) : k * (cm * cm);
 }
+template <int CRRA = 0>
 __device__ __forceinline__ double diet_v(const Consts &c, double u, double opr) {
-    return c.gamma == 2.0 ? opr * (-2.0 * (u * fast_sqrt(u))) : opr * (-(u * u));
+    return (CRRA == 1 || c.gamma == 2.0) ? opr * (-2.0 * (u * fast_sqrt(u))) : opr * (-(u * u));
 }
 
 // household inputs of period t: xhh[n_hh*t + k]; the lump-sum transfer is 0 for families without one
@@ -322,7 +334,7 @@ constexpr int Y_WAIT_VMCNT0 = 0x0F70;     // s_waitcnt immediate on gfx9: vmcnt(
 
 // the tail's second piece: the borrowing constraint on the interpolated (or flat) policy, consumption, marginal value.
 // ZREG: the column's productivity z_e comes in a register (`ze`: YColumnZOf<KNOTS>, see XKnots) instead of from c.z[e]
-template <bool ZREG>
+template <bool ZREG, int CRRA = 0>
 __device__ __forceinline__ YOut egm_Y_finish(const Consts &c, int a, int e, double r, double w, double tr, int *err, int t,
                                              double x, double g, double A, double B, int i, double ze) {
     YOut o;
@@ -335,19 +347,20 @@ __device__ __forceinline__ YOut egm_Y_finish(const Consts &c, int a, int e, doub
     g = (g > bc) ? g : ((bc > g) ? bc : (signbit(g) ? bc : g));
     const double opr = 1.0 + r;
     const double cg = (opr * x + (w * (ZREG ? ze : c.z[e]) + tr)) - g;
-    if (pow_domain_error(cg, -c.gamma)) set_err(err, ERR_DOMAIN, t, e, a);
-    const double u = pow_crra(cg, -c.gamma);
+    const double mg = CRRA == 1 ? -2.0 : -c.gamma;
+    if (pow_domain_error<CRRA>(cg, mg)) set_err(err, ERR_DOMAIN, t, e, a);
+    const double u = pow_crra<CRRA>(cg, mg);
     o.g = g;
     o.A = A;
     o.B = B;
     o.ib = i;
     o.u = u;
-    o.v = c.diet ? diet_v(c, u, opr) : opr * ((-c.gamma) * (u / cg));
+    o.v = (CRRA == 1 || c.diet) ? diet_v<CRRA>(c, u, opr) : opr * ((-c.gamma) * (u / cg));
     o.V = opr * u;
     return o;
 }
 
-template <typename KNOTS>
+template <int CRRA = 0, typename KNOTS>
 __device__ inline YOut egm_Y(const Consts &c, const KNOTS sc, int a, int e, double r, double w, double tr,
                              int *err, int t, int guess) {
     constexpr bool FRONT = YFrontOf<KNOTS>::value;
@@ -433,8 +446,8 @@ __device__ inline YOut egm_Y(const Consts &c, const KNOTS sc, int a, int e, doub
         A = -sl * (1.0 - f);
         B = -sl * f;
     }
-    if constexpr (YColumnZOf<KNOTS>::value) return egm_Y_finish<true>(c, a, e, r, w, tr, err, t, x, g, A, B, i, sc.column_z());
-    else return egm_Y_finish<false>(c, a, e, r, w, tr, err, t, x, g, A, B, i, 0.0);
+    if constexpr (YColumnZOf<KNOTS>::value) return egm_Y_finish<true, CRRA>(c, a, e, r, w, tr, err, t, x, g, A, B, i, sc.column_z());
+    else return egm_Y_finish<false, CRRA>(c, a, e, r, w, tr, err, t, x, g, A, B, i, 0.0);
 }
 
 // block = RBP rows x n_e columns; thread (row, e) with row fastest. dynamic LDS:

@@ -45,6 +45,12 @@
 #ifndef HANK_XADDR_BUF
 #define HANK_XADDR_BUF 1           // Dual-pass persistent sweeps: every stream through a few buffer descriptors, 32-bit offsets (dev knob: 0 = a 64-bit pointer per array)
 #endif
+#ifndef HANK_XADDR_BUF_BACK
+#define HANK_XADDR_BUF_BACK HANK_XADDR_BUF      // ... k_xdual_back's alone (dev knob: each sweep's descriptor path can be A/B-ed by itself)
+#endif
+#ifndef HANK_XADDR_BUF_FWD
+#define HANK_XADDR_BUF_FWD HANK_XADDR_BUF       // ... k_xfwd<D, true>'s alone
+#endif
 #include "hank_kernels.h"
 #include "hank_xaddr.h"
 #include <type_traits>
@@ -487,11 +493,13 @@ __device__ __forceinline__ void xtile_mix(const double *tl, const double *P, int
 // the coefficient, and every tile read of the pass can be in flight at once
 // BRK (HANK_XADDR_BUF; the caller passes xopaque(ne)): the pass ends at the first k >= ne — one scalar compare per step on one
 // register, where the sixteen hoisted predicates `k < ne` are sixteen spilled lane masks (two v_readlane each, every period)
-template <int SL, int NS, bool FMA = false, bool BRK = false>
-__device__ __forceinline__ void xtile_mix_reg(const double *tl, const double (&pr)[16], int ne, double *out) {
+// NK: the coefficients held (16; a kernel instance compiled for its n_e holds exactly n_e and passes ne = NK as a literal with
+// BRK off: NK straight-line steps, no predicate and no compare)
+template <int SL, int NS, bool FMA = false, bool BRK = false, int NK = 16>
+__device__ __forceinline__ void xtile_mix_reg(const double *tl, const double (&pr)[NK], int ne, double *out) {
     const int ks = 64 * SL;
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
+    for (int k = 0; k < NK; k++) {
         if (BRK && k > 0 && k >= ne) break;
         if (BRK || k < ne) {
             double v[SL];
@@ -1118,14 +1126,18 @@ struct XDualBackArgs {
     unsigned dpol_bytes;        // ... and this launch's dpol in bytes (x_addr_fits has checked that 32-bit offsets reach everything)
 };
 
-template <int D, int MAXT>
+// NE, CRRA: instances compiled for the model's constants (hank_xspec.h: x_spec chooses, x_launch_dual_back dispatches). NE > 0 is
+// the number of productivity states as a literal — the mixing is NE straight-line steps on NE coefficients; CRRA = 1 is gamma = 2
+// with the record diet on — the powers are a reciprocal square root and a reciprocal of a square with no test of the exponent
+// (hank_kernels.h). Both take the arms the generic instance (0, 0) takes at those constants: the same bits.
+template <int D, int MAXT, int NE = 0, int CRRA = 0>
 __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     constexpr int NSL = D + 1, SL = XSlots<NSL>::SL, IV = D;
-    constexpr bool XB = HANK_XADDR_BUF != 0;            // streams through buffer descriptors (see XRecOff)
+    constexpr bool XB = HANK_XADDR_BUF_BACK != 0;            // streams through buffer descriptors (see XRecOff)
     extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_dual_back (under this kernel) is the host's sum of the same pieces
     const XBackArgs &A = B.p;
     const Consts &c = A.c;
-    const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
+    const int ne = NE > 0 ? NE : c.n_e, na = c.n_a, P = c.P, G = c.G;
     double *tile = xl;                                  // [ne][64][SL]: slots 0..D-1 the partials of V, slot D the value
     double *ash = tile + (size_t)SL * ne * 64;          // [na]
     double *xsh = ash + ((na + 1) & ~1);                // [P][4]: r_t, w_t, tr_t, rho_t
@@ -1191,9 +1203,10 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
         xtile_store_n<SL, NSL>(myt, z);
     }
     __syncthreads();
-    double pr[16];                                      // Pi[e, k]: this wave's coefficients of the mixing, in registers (1.94 -> 1.87 ms at
+    constexpr int NK = NE > 0 ? NE : 16;
+    double pr[NK];                                      // Pi[e, k]: this wave's coefficients of the mixing, in registers (1.94 -> 1.87 ms at
 #pragma unroll                                          // N=32 against LDS reads; the kernel sits at 168 VGPRs = 3 waves per SIMD)
-    for (int k = 0; k < 16; k++) pr[k] = k < ne ? c.Pi[e + ne * k] : 0.0;
+    for (int k = 0; k < NK; k++) pr[k] = k < ne ? c.Pi[e + ne * k] : 0.0;
     int guess = -1;
     unsigned episode = 0;
     XSTAMP1(0, son, 10);
@@ -1217,7 +1230,7 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                 double w0[D], w1[D];
                 if constexpr (XB) { rows.load_vs(q, icb, w0); rows.load_vs(q + 1, icb, w1); }
                 else { rows.load(rb + q, w0); rows.load(rb + q + 1, w1); }
-                const YOut o = egm_Y(cl, kn, a, e, xsh[4 * t], xsh[4 * t + 1], xsh[4 * t + 2], A.err, t, guess);
+                const YOut o = egm_Y<CRRA>(cl, kn, a, e, xsh[4 * t], xsh[4 * t + 1], xsh[4 * t + 2], A.err, t, guess);
                 guess = o.ib;
                 tv[IV] = o.V;
                 XSTAMP(0, son, i, 1);
@@ -1278,14 +1291,19 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
             const int tx = P - 1 - i;
             if (own) {
                 double mx[NSL];
-                xtile_mix_reg<SL, NSL, false, XB>(tile + (size_t)lane * SL, pr, XB ? xopaque(ne) : ne, mx);
+                // (next to the generic powers' arms, 11 columns of D = 4 partials as straight-line code spill 37 VGPRs: that one instance
+                // keeps the step-by-step form on its 11 coefficients)
+                constexpr bool STEPS = XB && CRRA == 0 && NE * ((NSL + 1) / 2) > 24;
+                if constexpr (NE > 0 && STEPS) xtile_mix_reg<SL, NSL, false, true, NK>(tile + (size_t)lane * SL, pr, xopaque(NE), mx);
+                else if constexpr (NE > 0) xtile_mix_reg<SL, NSL, false, false, NK>(tile + (size_t)lane * SL, pr, NE, mx);
+                else xtile_mix_reg<SL, NSL, false, XB>(tile + (size_t)lane * SL, pr, XB ? xopaque(ne) : ne, mx);
                 const double bE = mx[IV] * c.beta;
-                const double ex = -1.0 / c.gamma;
-                if (pow_domain_error(bE, ex)) set_err(A.err, ERR_DOMAIN, tx, e, a);
-                const double cm = pow_crra(bE, ex);
+                const double ex = CRRA == 1 ? -0.5 : -1.0 / c.gamma;
+                if (pow_domain_error<CRRA>(bE, ex)) set_err(A.err, ERR_DOMAIN, tx, e, a);
+                const double cm = pow_crra<CRRA>(bE, ex);
                 const double rho = xsh[4 * tx + 3];
                 const double s1 = rho * ((cm - (xsh[4 * tx + 1] * ze + xsh[4 * tx + 2])) + xa);
-                const double kc = c.diet ? diet_kc(c, s1, rho, 1.0 + xsh[4 * tx], xsh[4 * tx + 1] * ze + xsh[4 * tx + 2], xa) : rho * (c.beta * ex * (cm / bE));
+                const double kc = (CRRA == 1 || c.diet) ? diet_kc<CRRA>(c, s1, rho, 1.0 + xsh[4 * tx], xsh[4 * tx + 1] * ze + xsh[4 * tx + 2], xa) : rho * (c.beta * ex * (cm / bE));
                 double ds[D];
 #pragma unroll
                 for (int k = 0; k < D; k++) {
@@ -1370,7 +1388,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     constexpr int IV = D;                               // the value's slot
     constexpr int DD = D > 0 ? D : 1;
     constexpr bool PIREG = NSL < 4;                     // the mixing's coefficients in registers
-    constexpr bool XB = HANK_XADDR_BUF != 0 && VAL && D > 0;      // the Dual pass: streams through buffer descriptors (see XRecOff)
+    constexpr bool XB = HANK_XADDR_BUF_FWD != 0 && VAL && D > 0;      // the Dual pass: streams through buffer descriptors (see XRecOff)
     extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_fwd (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const Record &R = A.R;

@@ -28,7 +28,7 @@ ABI_SYMBOLS = (
     "hank_primal_jvp", "hank_primal_jvp_dev",
     "hank_get_policy_seq", "hank_get_dpolicy_seq", "hank_get_dist_seq", "hank_get_het_outputs", "hank_get_het_outputs_dev", "hank_set_het_outputs",
     "hank_get_grid_aggregates", "hank_get_grid_aggregates_dev", "hank_backward_step",
-    "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
+    "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_sweep_instance", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
     "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings", "hank_vjp_het", "hank_vjp_het_dev",
     "hank_jvp_boundary", "hank_jvp_boundary_dev", "hank_vjp_boundary", "hank_vjp_boundary_dev",
     "hank_jvp_het", "hank_jvp_het_dev", "hank_vjp_het_boundary", "hank_vjp_het_boundary_dev",
@@ -118,6 +118,7 @@ def load_library() -> C.CDLL:
     lib.hank_last_timings.argtypes = [vp, dp, C.POINTER(i32)]
     lib.hank_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.hank_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.hank_sweep_instance.argtypes = [vp, C.POINTER(i32)]
     lib.hank_vfi.argtypes = [vp, dp, C.c_double, i32, dp, dp, C.POINTER(i32), dp]
     lib.hank_stationary_dist.argtypes = [vp, dp, dp, C.c_double, i32, i32, C.POINTER(i32)]
     lib.hank_fake_news.argtypes = [vp, dp, dp]
@@ -536,6 +537,13 @@ class HouseholdBlock:
         d = {k: int(out[i]) for i, k in enumerate(names)}
         d["last_tangent_family_name"] = ("launch-per-period", "xcd-persistent", "on-chip-wide")[d["last_tangent_family"]]
         return d
+
+    def sweep_instance(self):
+        """which instances of the Dual pass's persistent sweeps were enqueued last (include/hank_hip.h: hank_sweep_instance):
+        {"back": (NE, CRRA), "fwd": (NE, CRRA)}; -1 before the first Dual pass."""
+        out = (C.c_int32 * 4)()
+        self._chk(self._lib.hank_sweep_instance(self._ctx, out))
+        return {"back": (int(out[0]), int(out[1])), "fwd": (int(out[2]), int(out[3]))}
 
     def policy_seq(self) -> np.ndarray:
         """(n_a, n_e, P): policy matrix of every period (BackwardIteration's return value)."""
