@@ -28,18 +28,15 @@
 //       pbar_t[j,e] -= sum_o ybx_o,t f_c,o,t[j,e] D_t[j,e]         (next to (yb0 - yb1) D_t)
 // and the household inputs' cotangents directly (k_adj_hx_out, after Sweep B): xbar_r += ybx_o,t (Sa + Sr), xbar_w += ybx_o,t Sz,
 // xbar_tr += ybx_o,t S1. Sweep B is the same: pbar carries everything it reads.
-// NOTE: k_ss_lam and k_ss_nu (hank_ssdiff.h) restate the steps of k_adj_dist and k_adj_egm at one fixed period with their own
-// prologue and epilogue: a change to the arithmetic of either kernel here has to be made there as well.
+// NOTE: k_ss_lam and k_ss_nu (hank_ssdiff.h) restate the tile mix, the bracket gather and the six block sums of k_adj_dist and k_adj_egm: a
+// shared inline function for any one of them changes these kernels' instructions (profiles/ssdiff_unit.txt), so a change here is made there too.
 #pragma once
 #include "hank_hetx.h"
 #include "hank_kernels.h"
 
 namespace hank {
 
-// MV = M / (columns per lane); NC lanes of a wave span the columns (a power of two <= 16), RB = 64 / NC rows per wave
-// instruction; a block owns R rows (R + 2 <= ADJ_KS * RB) x all n_e columns; nb = ceil(n_a / R) row blocks
-struct AdjGeom { int MV, NC, lgNC, R, nb; };
-constexpr int ADJ_KS = 3;      // row slots a lane may own in a block's tile
+// (AdjGeom: hank_geom.h; ADJ_KS, adj_rows_sum, AdjHx: hank_device.h)
 
 // agg_bar (P, n_het, M) column-major -> yb0[P][M], yb1[P][M] (zeros when consumption carries no cotangent)
 __global__ void k_adj_in(const double *__restrict__ agg_bar, int P, int n_het, int M, double *__restrict__ yb0, double *__restrict__ yb1) {
@@ -90,13 +87,6 @@ __global__ void __launch_bounds__(256) k_adj_seg(Consts c, Record R, int ncols, 
     for (int r = threadIdx.x; r <= n; r += blockDim.x) out[r] = shb[r];
 }
 
-// sum over the lanes of a wave that share the column pair nl (the rows rl of the wave), fixed order
-template <typename VT>
-__device__ __forceinline__ VT adj_rows_sum(VT v, int NC) {
-    for (int off = 32; off >= NC; off >>= 1) v = vadd(v, vshfl_xor(v, off));
-    return v;
-}
-
 // ---- Sweep A, one period -------------------------------------------------------------------------------------------------
 // A block owns the TARGET rows [r0, r1) of the lottery, all columns: it loads lam rows r0 .. r1 (one halo row) and row 0 once,
 // adds the period's output cotangents, mixes them with Pi through the LDS tile (U), and then serves, per column, the SOURCES
@@ -105,10 +95,6 @@ __device__ __forceinline__ VT adj_rows_sum(VT v, int NC) {
 // shared out evenly over the row blocks). Every source row is written by exactly one block.
 // NX extra outputs (hx: nothing for NX = 0): a lane also reads f_o at its target rows, f_c,o at its source rows and ybx_o,t.
 // dynamic LDS: VT tile[n_e][R + 2][NC] (slot R + 1 = row 0), double Pish[n_e * n_e]
-template <typename VT, int NX>
-struct AdjHx { const double *f, *fc; const VT *ybx; };      // f, f_c [jx][P][G] and their stride P G (k_hx_record); ybx [P][NX][MV]
-template <typename VT>
-struct AdjHx<VT, 0> {};
 template <typename VT, int NX>
 __global__ void __launch_bounds__(1024)
 k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t, int first, const VT *__restrict__ yb0,

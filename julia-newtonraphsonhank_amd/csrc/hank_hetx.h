@@ -16,7 +16,6 @@
 
 namespace hank {
 
-constexpr int HX_NS = 5;    // per period and extra output: Y, Sa, Sz, S1, Sr
 constexpr int HX_ROWS = 256;
 
 // f and its partials at one grid point for output j (2: Value, 3: UCE)

@@ -194,21 +194,23 @@ struct TanBatch {
     const double *bnd_zm = nullptr; // view: {zm, om} [2][P][N] of its dD_0 seed (k_bnd_mpath), or nullptr without one
 };
 
-// The timed sweeps of hank_last_timings (the first six, in its slot order) and hank_last_vjp_timings (the last two). A span is a
+// The timed sweeps of hank_last_timings (the first six, in its slot order), hank_last_vjp_timings (the next two) and
+// hank_last_ss_timings (the last two). A span is a
 // begin event, an end event, a valid flag and the launch count of the run that ended it; the run functions reach them through these
 // operations only. Recording a span's begin makes it invalid until its end is recorded. What each run function leaves behind
 // (V valid, I invalid, . untouched) — the families do NOT agree, see DESIGN.md section 2a:
-//                        PRIMAL_BACK PRIMAL_FWD TAN_BACK TAN_FWD DUAL_BACK DUAL_FWD VJP_A VJP_B
-//   run_primal                V          V         .        .        I        I       .     .
-//   x_primal                  V          V         I        I        I        I       .     .
-//   x_jvp                     .          .         V        V        I        I       .     .
-//   x_dual_two                V          I         V        V        I        I       .     .
-//   x_dual_fused              V          I         V*       V        I        I       .     .      (* brackets nothing: k_xdual_back is PRIMAL_BACK's)
-//   w_run_tangent             .          .         V        V        I        I       .     .
-//   run_jvp                   .          .         V        V        .        .       .     .
-//   run_fused                 I          I         I        I        V        V       .     .
-//   enqueue_vjp               .          .         .        .        .        .       V     V
-enum Span { PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD, VJP_A, VJP_B, N_SPANS };
+//                        PRIMAL_BACK PRIMAL_FWD TAN_BACK TAN_FWD DUAL_BACK DUAL_FWD VJP_A VJP_B SS_VALUE SS_DIST
+//   run_primal                V          V         .        .        I        I       .     .      .       .
+//   x_primal                  V          V         I        I        I        I       .     .      .       .
+//   x_jvp                     .          .         V        V        I        I       .     .      .       .
+//   x_dual_two                V          I         V        V        I        I       .     .      .       .
+//   x_dual_fused              V          I         V*       V        I        I       .     .      .       .      (* brackets nothing: k_xdual_back is PRIMAL_BACK's)
+//   w_run_tangent             .          .         V        V        I        I       .     .      .       .
+//   run_jvp                   .          .         V        V        .        .       .     .      .       .
+//   run_fused                 I          I         I        I        V        V       .     .      .       .
+//   enqueue_vjp               .          .         .        .        .        .       V     V      .       .
+//   ss_loop                   .          .         .        .        .        .       .     .      V       V      (the loop it was called for; I until that loop's end)
+enum Span { PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD, VJP_A, VJP_B, SS_VALUE, SS_DIST, N_SPANS };
 struct Spans {
     struct One { hipEvent_t ev0 = nullptr, ev1 = nullptr, from = nullptr; bool valid = false; int launches = 0; } s[N_SPANS];      // from: the event the span began with (ev0, or the end of the span before it)
     hipError_t create() { hipError_t e = hipSuccess; for (One &o : s) { if (e == hipSuccess) e = hipEventCreate(&o.ev0); if (e == hipSuccess) e = hipEventCreate(&o.ev1); } return e; }
@@ -253,7 +255,7 @@ struct hank_ctx {
     hipEvent_t ev_fork = nullptr, ev_side = nullptr;
     bool side_pending = false;
     GraphExec g_pback, g_pfwd;
-    Spans spans;                   // the timed sweeps (hank_last_timings, hank_last_vjp_timings)
+    Spans spans;                   // the timed sweeps (hank_last_timings, hank_last_vjp_timings, hank_last_ss_timings)
     std::list<TanWork> tws;        // per batch width, most recently used first (a small cache: Jacobian assembly and Newton alternate widths)
     // 0 = one launch per period for everything; 1 = XCD-local persistent sweeps for everything; 2 = auto (default where
     // the persistent sweeps are supported): each entry point takes the faster of the two for its shape — see sched_*
@@ -294,8 +296,6 @@ struct hank_ctx {
     bool stationary = false;                          // the recorded primal is the constant steady-state path with the steady state as both boundaries (hank_fake_news)
     std::vector<double> h_ss_value, h_ss_D;           // the boundary as the host handed it in (stationarity check)
     hipEvent_t ev_stream = nullptr;
-    hipEvent_t ss_ev[2][2] = {};                      // begin / end of the two loops of the last hank_ss_jvp / hank_ss_vjp (hank_last_ss_timings), created on first use
-    bool ss_timed[2] = {false, false};
     char errmsg[512] = {0};
 };
 
@@ -643,15 +643,7 @@ static int build_tanwork(hank_ctx *ctx, TanWork &w) {
     // an even batch can run two directions per lane (16-byte accesses): the [..][N] layout is the same, so
     // each sweep picks its own lane width
     const int VB = tan_lane_width(N, 0), VF = tan_lane_width(N, 1);
-    auto geom = [&](int V, TanGeom &g) {
-        const int NV = N / V;
-        int NC = 1, lg = 0;
-        while (NC < NV && NC < 64) { NC <<= 1; lg++; }
-        const int RB = 64 / NC;
-        g.N = NV; g.NC = NC; g.lgNC = lg; g.nbx = (c.n_a + RB - 1) / RB;
-        g.ss = 0;
-    };
-    geom(VB, w.g); geom(VF, w.gf);
+    w.g = tan_geom(c.n_a, N, VB); w.gf = tan_geom(c.n_a, N, VF);
     w.nbx = w.g.nbx; w.nbxf = w.gf.nbx;
     const size_t GV = (size_t)(c.n_a + KV) * c.n_e;   // dD state carries KV virtual rows per column
     // forward kernel form: source-stationary from 16-lane groups on (N >= 18: forward sweep 3.42 -> 3.05 ms at N=32 with 2 row
@@ -1525,7 +1517,6 @@ int hank_destroy(hank_ctx *ctx) {
     if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->ev_stream) (void)hipEventDestroy(ctx->ev_stream);
-    for (auto &pair : ctx->ss_ev) for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_side) (void)hipEventDestroy(ctx->ev_side);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
@@ -2373,20 +2364,13 @@ int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out) {
 }  // extern "C"
 
 // ================================ transposed sweeps: hank_vjp (hank_adjoint.h) ==========================
-// Lane geometry per batch width M: two adjacent cotangent columns per lane for an even M (16-byte state / pbar accesses); at
-// most 16 lanes span the columns (wider batches take more blocks in y), so a wave instruction moves RB = 64 / NC >= 4 rows;
-// a block owns R = max(RB, 8) rows: its LDS tile (n_e x (R + 2) x NC lanes) stays below 48 KiB up to n_e = 16.
+// Lane geometry per batch width M: adj_geom (hank_geom.h).
 static int build_cotwork(hank_ctx *ctx, CotWork &w) {
     const Consts &c = ctx->c;
     const size_t P = c.P, G = c.G, M = (size_t)w.N;
-    w.V = (w.N % 2 == 0) ? 2 : 1;
-    AdjGeom &g = w.g;
-    g.MV = w.N / w.V;
-    g.NC = 1; g.lgNC = 0;
-    while (g.NC < g.MV && g.NC < 16) { g.NC <<= 1; g.lgNC++; }
-    const int RB = 64 / g.NC;
-    g.R = std::max(RB, 8);
-    g.nb = (c.n_a + g.R - 1) / g.R;
+    w.V = adj_lane_width(w.N);
+    w.g = adj_geom(c.n_a, w.N);
+    const AdjGeom &g = w.g;
     HIPC(ctx, w.ybar.alloc(het_max(ctx) * P * M));
     HIPC(ctx, w.yb0.alloc(P * M));
     HIPC(ctx, w.yb1.alloc(P * M));
@@ -3143,13 +3127,12 @@ int hank_forward_step_dual(hank_ctx *ctx, const double *policy, const double *dp
 // the step kernel + the one-block check kernel), the stop word comes back once per chunk, and the steps enqueued behind a set stop
 // word leave at once, so the state is the converged step's. step(k): the k-th step, 0-based (it reads buffer k & 1 of a ping-pong
 // state and writes (k + 1) & 1: the final state sits in buffer iters & 1). Not converging is not an error: iters == max_iter.
+// span: SS_VALUE or SS_DIST, the loop's time for hank_last_ss_timings.
 template <typename Step>
-static int ss_loop(hank_ctx *ctx, SsCtl *d_ctl, int max_iter, Step step, SsCtl *out, int which) {
+static int ss_loop(hank_ctx *ctx, SsCtl *d_ctl, int max_iter, Step step, SsCtl *out, Span span) {
     hipStream_t s = ctx->stream;
     SsCtl h{};
-    ctx->ss_timed[which] = false;
-    for (hipEvent_t &e : ctx->ss_ev[which]) if (!e) HIPC(ctx, hipEventCreate(&e));
-    HIPC(ctx, hipEventRecord(ctx->ss_ev[which][0], s));      // (no host synchronisation for the timing: events on the stream)
+    HIPC(ctx, ctx->spans.begin(span, s));      // (no host synchronisation for the timing: events on the stream)
     HIPC(ctx, hipMemsetAsync(d_ctl, 0, sizeof(SsCtl), s));
     int done = 0;
     const int chunk = 64;
@@ -3161,8 +3144,7 @@ static int ss_loop(hank_ctx *ctx, SsCtl *d_ctl, int max_iter, Step step, SsCtl *
         HIPC(ctx, hipMemcpyAsync(&h, d_ctl, sizeof(SsCtl), hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));
     }
-    HIPC(ctx, hipEventRecord(ctx->ss_ev[which][1], s));
-    ctx->ss_timed[which] = true;
+    HIPC(ctx, ctx->spans.end(span, s, 2 * done));
     *out = h;
     return HANK_OK;
 }
@@ -3172,12 +3154,6 @@ static int ss_loop(hank_ctx *ctx, SsCtl *d_ctl, int max_iter, Step step, SsCtl *
 static int ss_ready(hank_ctx *ctx, const char *name, int n_het, bool rest_ok) {
     int rc = het_count_ok(ctx, name, n_het, true, rest_ok);
     if (rc) return rc;
-    {   // the launchers' unit names the argument structs through a namespace of its own (hank_ssdiff_launch.h): same layout, or nothing runs
-        size_t theirs[5];
-        hankss_layout(theirs);
-        const size_t ours[5] = {sizeof(Consts), sizeof(Record), sizeof(TanGeom), sizeof(AdjGeom), sizeof(SsCtl)};
-        if (memcmp(ours, theirs, sizeof(ours)) != 0) return fail(ctx, HANK_ERR_LAUNCH, "%s: hank_ssdiff.hip was built with other argument structs than hank_hip.hip", name);
-    }
     rc = stationary_record(ctx, name);
     if (rc) return rc;
     if (ctx->c.P < 2) return fail(ctx, HANK_ERR_BAD_ARG, "%s needs a record of at least two periods (T >= 3)", name);
@@ -3194,13 +3170,7 @@ static int ss_jvp(hank_ctx *ctx, int n_het, const double *dxhh, int N, double to
     const size_t G = c.G, GV = (size_t)(c.n_a + KV) * c.n_e, NN = (size_t)N;
     const int NX = n_het > 2 ? n_het - 2 : 0, V = (N % 2 == 0) ? 2 : 1;
     hipStream_t s = ctx->stream;
-    TanGeom g{};
-    {
-        const int NV = N / V;
-        int NC = 1, lg = 0;
-        while (NC < NV && NC < 64) { NC <<= 1; lg++; }
-        g.N = NV; g.NC = NC; g.lgNC = lg; g.nbx = (c.n_a + 64 / NC - 1) / (64 / NC); g.ss = 0;
-    }
+    const TanGeom g = tan_geom(c.n_a, N, V);
     TanGeom gf = g;
     gf.ss = g.NC >= 16 ? 1 : 0;
     const int RGB = 2, RGF = gf.ss ? 2 : 1;
@@ -3231,14 +3201,14 @@ static int ss_jvp(hank_ctx *ctx, int n_het, const double *dxhh, int N, double to
     rc = ss_loop(ctx, &ctl[0], max_iter, [&](int k) {
         hankss_launch_back(s, V, c, ctx->R, ctx->d_xhh.get(), dxr, dxw, dxt, g, nbt, ny, ds[k & 1], ds[(k + 1) & 1], dpol, dV, partsB, &ctl[0]);
         hankss_launch_check(s, partsB, (int)nbt, 2, N, tol, &ctl[0], nullptr);
-    }, &hv, 0);
+    }, &hv, SS_VALUE);
     if (rc) return rc;
     // 2. dD <- Lambda dD + (dLambda da') D with that da'; the last step's reductions are dY's
     const double *dap = dpol + G * NN;
     rc = ss_loop(ctx, &ctl[1], max_iter, [&](int k) {
         hankss_launch_fwd(s, V, NX, c, ctx->R, gf, nbf, ny, dD[k & 1], dD[(k + 1) & 1], dap, aggpart, ctx->hx.f.get(), ctx->hx.fc.get(), hxparts, partsF, &ctl[1]);
         hankss_launch_check_dist(s, c, ctx->R.Dseq, partsF, (int)nbf, N, tol, dD[(k + 1) & 1], dD[k & 1], sig, &ctl[1]);
-    }, &hd, 1);
+    }, &hd, SS_DIST);
     if (rc) return rc;
     const double *dDfin = dD[hd.iters & 1];
     hankss_launch_jvp_out(s, c.P, c.n_hh, n_het, N, (int)nbf, ctx->d_xhh.get(), dx, ctx->d_agg.get(), ctx->d_zd.get(), ctx->hx.S.get(), aggpart, hxparts, out);
@@ -3279,7 +3249,7 @@ static int ss_vjp_loops(hank_ctx *ctx, int V, const AdjGeom &g, int NX, double t
     int rc = ss_loop(ctx, &ctl[1], max_iter, [&](int k) {
         hankss_launch_lam(s, V, false, ldsA, c, ctx->R, g, e[k & 1], e[(k + 1) & 1], lam, parts, &ctl[1], cen, nullptr, 0, nullptr, PG, nullptr);
         hankss_launch_check(s, parts, g.nb, 3, M, tol, &ctl[1], recentre ? cen : nullptr);
-    }, hl, 1);
+    }, hl, SS_DIST);
     if (rc) return rc;
     // 2. pbar from lam (Sweep A's pbar line at one period)
     hankss_launch_lam(s, V, true, ldsA, c, ctx->R, g, lam, nullptr, nullptr, nullptr, nullptr, nullptr, yb, NX, ctx->hx.fc.get(), PG, pbar);
@@ -3287,7 +3257,7 @@ static int ss_vjp_loops(hank_ctx *ctx, int V, const AdjGeom &g, int NX, double t
     return ss_loop(ctx, &ctl[0], max_iter, [&](int k) {
         hankss_launch_nu(s, V, ldsB, c, ctx->R, g, ctx->d_adj_sb.get(), nu[k & 1], nu[(k + 1) & 1], pbar, vbar, partS, partM, parts, &ctl[0]);
         hankss_launch_check(s, parts, g.nb, 2, M, tol, &ctl[0], nullptr);
-    }, hn, 0);
+    }, hn, SS_VALUE);
 }
 
 static int ss_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, const double *value_bar, const double *D_bar, int M, double tol, int max_iter, double *xhh_bar,
@@ -3299,13 +3269,9 @@ static int ss_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, const double 
     if (rc) return rc;
     const Consts &c = ctx->c;
     const size_t G = c.G, MM = (size_t)M;
-    const int NX = n_het > 2 ? n_het - 2 : 0, V = (M % 2 == 0) ? 2 : 1;
+    const int NX = n_het > 2 ? n_het - 2 : 0, V = adj_lane_width(M);
     hipStream_t s = ctx->stream;
-    AdjGeom g{};
-    g.MV = M / V; g.NC = 1; g.lgNC = 0;
-    while (g.NC < g.MV && g.NC < 16) { g.NC <<= 1; g.lgNC++; }
-    g.R = std::max(64 / g.NC, 8);
-    g.nb = (c.n_a + g.R - 1) / g.R;
+    const AdjGeom g = adj_geom(c.n_a, M);
     if (adj_lds_dist(c, g, V) > ctx->lds_max || adj_lds_egm(c, g, V) > ctx->lds_max)
         return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_vjp: n_e=%d needs more LDS per workgroup than the device has", c.n_e);
     if (!ctx->d_adj_sb) HIPC(ctx, ctx->d_adj_sb.alloc((size_t)c.P * c.n_e * ((size_t)c.n_a + 1)));
@@ -3372,14 +3338,8 @@ int hank_ss_vjp_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, const
 int hank_last_ss_timings(hank_ctx *ctx, double *out_ms) {
     if (!ctx || !out_ms) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
-    for (int k = 0; k < 2; k++) {
-        float f = -1.f;
-        if (ctx->ss_timed[k]) {
-            HIPC(ctx, hipEventSynchronize(ctx->ss_ev[k][1]));
-            HIPC(ctx, hipEventElapsedTime(&f, ctx->ss_ev[k][0], ctx->ss_ev[k][1]));
-        }
-        out_ms[k] = f;
-    }
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 2; k++) HIPC(ctx, ctx->spans.read((Span)(SS_VALUE + k), &out_ms[k], nullptr));
     return HANK_OK;
 }
 }  // extern "C"

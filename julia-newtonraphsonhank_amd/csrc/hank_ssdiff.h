@@ -24,12 +24,10 @@
 //
 // These kernels are compiled in a translation unit of their own (hank_ssdiff.hip): they instantiate the sweep kernels' device bodies
 // a second time, and inside one translation unit that changes how the compiler treats the bodies in the sweep kernels themselves
-// (their register counts moved). hank_hip.hip sees the launchers of hank_ssdiff_launch.h only.
+// (their register counts moved). Everything the two units share — structs, helpers, the bodies — is hank_device.h's, one definition
+// in namespace hank; hank_hip.hip sees the launchers of hank_ssdiff_launch.h only.
 #pragma once
-#include "hank_adjoint.h"
-#include "hank_boundary.h"
-#include "hank_hetx.h"
-#include "hank_kernels.h"
+#include "hank_device.h"
 #include "hank_ssdiff_launch.h"
 
 namespace hank {

@@ -1,16 +1,12 @@
 // hank_ssdiff.hip — the device code of hank_ss_jvp / hank_ss_vjp (hank_ssdiff.h) and its host launchers (hank_ssdiff_launch.h), in a
-// translation unit of their own: the sweep kernels of hank_hip.hip are compiled exactly as before.
-#define hank hank_ssd      // this unit's copy of the shared kernel headers lives in a namespace of its own (see hank_ssdiff_launch.h)
+// translation unit of their own: the sweep kernels of hank_hip.hip are compiled exactly as before. It includes hank_device.h, not the
+// headers that define kernels, so its code object holds the k_ss_* kernels and nothing else.
 #include "hank_ssdiff.h"
 
 namespace hank {
 
 template <typename VT> static const VT *cv(const double *p) { return reinterpret_cast<const VT *>(p); }
 template <typename VT> static VT *mv(double *p) { return reinterpret_cast<VT *>(p); }
-
-void hankss_layout(size_t out[5]) {
-    out[0] = sizeof(Consts); out[1] = sizeof(Record); out[2] = sizeof(TanGeom); out[3] = sizeof(AdjGeom); out[4] = sizeof(SsCtl);
-}
 
 void hankss_launch_in(hipStream_t s, const double *dxhh, int n_hh, int N, double *dxr, double *dxw, double *dxt) {
     hipLaunchKernelGGL(k_ss_in, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, s, dxhh, n_hh, N, dxr, dxw, dxt);

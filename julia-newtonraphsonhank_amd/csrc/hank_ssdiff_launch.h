@@ -1,21 +1,11 @@
 // hank_ssdiff_launch.h — what hank_hip.hip sees of the steady-state derivative kernels (hank_ssdiff.h, compiled in hank_ssdiff.hip):
-// the loops' control word and one host launcher per kernel. V: columns per lane (2: double2 lanes, an even width; else 1).
-// The launchers have C linkage: hank_ssdiff.hip compiles the shared kernel headers a second time, under a namespace of its own
-// (their kernels would otherwise be defined twice in the library), so the two sides name the same structs through different
-// namespaces and only an unmangled name joins them. Every kernel and device global of those shared headers is therefore emitted a
-// second time into the library (unused copies, about 180 KiB).
+// one host launcher per kernel, ordinary functions of namespace hank on the argument structs of hank_device.h (the loops' control
+// word SsCtl among them). V: columns per lane (2: double2 lanes, an even width; else 1).
 #pragma once
-#include "hank_adjoint.h"
-#include "hank_kernels.h"
+#include "hank_device.h"
 
 namespace hank {
 
-struct SsCtl { int stop, iters; double resid; };      // a loop's stop word, the steps it took, the last increment ratio
-
-extern "C" {
-// sizeof of (Consts, Record, TanGeom, AdjGeom, SsCtl) as hank_ssdiff.hip sees them: the drivers compare them with their own before the
-// first launch (the structs are plain data, the same header text on both sides; this catches a build that mixed two versions)
-void hankss_layout(size_t out[5]);
 void hankss_launch_in(hipStream_t s, const double *dxhh, int n_hh, int N, double *dxr, double *dxw, double *dxt);
 void hankss_launch_back(hipStream_t s, int V, const Consts &c, const Record &R, const double *xhh, const double *dxr, const double *dxw, const double *dxt, const TanGeom &g,
                     unsigned nbt, unsigned ny, const double *dsIn, double *dsOut, double *dpol, double *dV, double *parts, const SsCtl *ctl);
@@ -39,6 +29,5 @@ void hankss_launch_nu(hipStream_t s, int V, size_t lds, const Consts &c, const R
                   const double *pbar, const double *vbar, double *partS, double *partM, double *parts, const SsCtl *ctl);
 void hankss_launch_xbar(hipStream_t s, int P, int n_hh, int M, int nb, int NX, const double *xhh, const double *partS, const double *partM, const double *yb,
                     const double *agg, const double *zd, const double *hxS, double *xhh_bar);
-}  // extern "C"
 
 }  // namespace hank

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Static instruction counts of a persistent kernel's period loop in cross-compiled gfx950 assembly.
 
+    for u in hank_hip hank_ssdiff; do      # the library's two translation units
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -S --cuda-device-only \
-          -Rpass-analysis=kernel-resource-usage -o hank_hip.s csrc/hank_hip.hip 2> resources.txt
-    scripts/dev_isa_counts.py hank_hip.s [resources.txt] [kernel-name-substring ...]
+          -Rpass-analysis=kernel-resource-usage -o $u.s csrc/$u.hip 2>> resources.txt; done
+    scripts/dev_isa_counts.py hank_hip.s[,hank_ssdiff.s] [resources.txt] [kernel-name-substring ...]
 
 The period loop is taken to be the longest backward branch of the kernel (label .. the branch that jumps back to it;
 jumps to the kernel's exit block, which the compiler may place first, are not loops).
@@ -100,7 +101,7 @@ def main():
     asm = args.pop(0)
     res = resources(args.pop(0)) if args and not args[0].startswith("k_") else {}
     want = args or DEFAULT
-    lines = open(asm).read().split("\n")
+    lines = [ln for f in asm.split(",") for ln in open(f).read().split("\n")]      # (both units: their functions have distinct names)
     fns = functions(lines)
     for w in want:
         for name, (a, b) in fns.items():

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
-"""dev: which kernels of the gfx950 code object a run launches (profiles/kernel_coverage.txt).
+"""dev: which kernels of the two gfx950 code objects a run launches (profiles/kernel_coverage.txt).
 
     python scripts/dev_kernel_coverage.py --list
-        the kernel symbols of csrc/hank_hip.hip, demangled (hipcc -S --cuda-device-only, as tests/test_isa_hazards.py; no GPU)
+        the kernel symbols of csrc/hank_hip.hip and csrc/hank_ssdiff.hip, demangled (hipcc -S --cuda-device-only, as
+        tests/test_isa_hazards.py; no GPU)
     python scripts/dev_kernel_coverage.py --stats DIR_OR_CSV [...] [--out FILE]
         every kernel with its launch count, summed over the kernel-stats CSVs of a `rocprofv3 --kernel-trace --stats
         --output-format csv` run (all *kernel_stats.csv below a directory: one per traced process). A kernel at zero launches is
@@ -18,6 +19,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "julia-newtonraphsonhank_amd" / "csrc"
+UNITS = ("hank_hip.hip", "hank_ssdiff.hip")      # the library's translation units (csrc/Makefile)
 
 # why a kernel no test launches is not launched (regex on the demangled name -> one line). The per-period tangent kernels are
 # instantiated for row groups 1, 2, 4 and both lane widths; ensure_tanwork (csrc/hank_hip.hip) picks among them by batch width.
@@ -28,17 +30,20 @@ REASONS = {
     r"k_(tan|fused)_back<1,": "1 backward row group: never the default; dev knob HANK_RG_B=1 only",
     r"k_(tan|fused)_back<4,": "4 backward row groups: the per-period launches at >= 128 lanes of directions (N >= 256 even, >= 128 odd); "
                              "the default sends such batches to the wide sweeps and no test forces the launches there",
+    r"k_ss_fwd<2, HIP_vector_type<double, 2u>, true,": "source-stationary form with two directions per lane: an even width of 18 or more; tests/test_gpu_ss_diff.py runs the widths 1, 3, 4, 33",
 }
 
 
 def kernel_symbols():
-    """[(mangled, demangled)] of every kernel descriptor in the gfx950 assembly, in the order the compiler emits them."""
+    """[(mangled, demangled)] of every kernel descriptor in the gfx950 assembly of both units, in the order the compiler emits them."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    syms = []
     with tempfile.TemporaryDirectory() as d:
-        out = Path(d) / "hank.s"
-        subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-                        "-o", str(out), str(CSRC / "hank_hip.hip")], check=True, capture_output=True, timeout=900)
-        syms = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", out.read_text(), re.M)
+        for unit in UNITS:
+            out = Path(d) / "hank.s"
+            subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
+                            "-o", str(out), str(CSRC / unit)], check=True, capture_output=True, timeout=900)
+            syms += re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", out.read_text(), re.M)
     dem = subprocess.run(["c++filt"], input="\n".join(syms) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
     assert len(dem) == len(syms)
     return list(zip(syms, dem))
@@ -85,7 +90,7 @@ def main():
             zero += 1
             why = next((r for pat, r in REASONS.items() if re.search(pat, d)), "(no reason recorded)")
             lines.append(f"{0:>9}  {d}\n{'':>11}not launched: {why}")
-    head = [f"# {len(kernels)} kernels in the gfx950 code object of csrc/hank_hip.hip, {len(kernels) - zero} launched, {zero} not",
+    head = [f"# {len(kernels)} kernels in the gfx950 code objects of csrc/hank_hip.hip and csrc/hank_ssdiff.hip, {len(kernels) - zero} launched, {zero} not",
             f"# launch counts summed over {len(files)} kernel-stats CSV(s) of one rocprofv3 --kernel-trace --stats run"]
     if counts:
         head.append(f"# {len(counts)} traced kernel name(s) outside the code object (torch, rocBLAS/hipBLASLt, ...) are not listed")

@@ -382,7 +382,7 @@ def forward_edges(grid, pol):
 
 
 def adj_rows_per_block(M):
-    """R of hank_vjp's lane geometry at batch width M (build_cotwork, csrc/hank_hip.hip): two columns per lane for an even M, at
+    """R of hank_vjp's lane geometry at batch width M (adj_geom, csrc/hank_geom.h; tests/test_geom_host.py holds the two together): two columns per lane for an even M, at
     most 16 lanes across the columns, RB = 64 / NC rows per wave instruction, R = max(RB, 8)."""
     MV = M // 2 if M % 2 == 0 else M
     NC = 1

@@ -1,0 +1,83 @@
+"""The lane geometry of the tangent kernels and of the transposed ones at a batch width has ONE definition, hank_geom.h (tan_geom,
+adj_geom), which build_tanwork, build_cotwork, ss_jvp and ss_vjp (hank_hip.hip) all call. Plain integers in a header without device
+code: compiled alone by the host compiler here, no GPU and no library, and compared with a Python mirror written from
+build_tanwork's loop and with cases.adj_rows_per_block (what the GPU tests size their economies by)."""
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+import cases
+
+CSRC = Path(__file__).resolve().parent.parent / "julia-newtonraphsonhank_amd" / "csrc"
+N_A = (30, 50, 63, 64, 65)
+MAIN = """#include "hank_geom.h"
+#include <cstdio>
+#include <cstdlib>
+int main(int argc, char **argv) {      // questions on the command line: t n_a N V | a n_a M; one line of integers per answer
+    for (int i = 1; i < argc;) {
+        if (argv[i][0] == 't' && i + 3 < argc) {
+            const hank::TanGeom g = hank::tan_geom(atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3]));
+            printf("%d %d %d %d %d\\n", g.N, g.NC, g.lgNC, g.nbx, g.ss);
+            i += 4;
+        } else if (argv[i][0] == 'a' && i + 2 < argc) {
+            const hank::AdjGeom g = hank::adj_geom(atoi(argv[i + 1]), atoi(argv[i + 2]));
+            printf("%d %d %d %d %d %d\\n", g.MV, g.NC, g.lgNC, g.R, g.nb, hank::adj_lane_width(atoi(argv[i + 2])));
+            i += 3;
+        } else {
+            return 2;
+        }
+    }
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def ask(tmp_path_factory):
+    """hank_geom.h compiled ALONE by the host compiler (it is plain C++: no HIP, no library) into a program that answers."""
+    cxx = next((c for c in (shutil.which("c++"), shutil.which("g++"), shutil.which("clang++"), "/opt/rocm/lib/llvm/bin/clang++") if c and Path(c).exists()), None)
+    assert cxx, "no host C++ compiler"
+    d = tmp_path_factory.mktemp("geom")
+    (d / "main.cpp").write_text(MAIN)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(CSRC), "-o", str(d / "geom"), str(d / "main.cpp")], check=True, capture_output=True, timeout=120)
+
+    def run(questions):
+        """[(kind, ints...)] -> one list of ints per question"""
+        args = [str(v) for q in questions for v in q]
+        out = subprocess.run([str(d / "geom")] + args, check=True, capture_output=True, text=True, timeout=30).stdout.splitlines()
+        assert len(out) == len(questions)
+        return [[int(v) for v in l.split()] for l in out]
+    return run
+
+
+def tan_mirror(n_a, N, V):
+    """build_tanwork's loop: N / V lanes of directions, NC of them (a power of two <= 64) across a wave, 64 / NC rows per instruction"""
+    NV = N // V
+    NC, lg = 1, 0
+    while NC < NV and NC < 64:
+        NC, lg = NC * 2, lg + 1
+    RB = 64 // NC
+    return [NV, NC, lg, (n_a + RB - 1) // RB, 0]
+
+
+def test_tan_geom_matches_the_mirror_at_every_width(ask):
+    qs = [("t", n_a, N, V) for n_a in N_A for V in (1, 2) for N in range(1, 71) if N % V == 0]
+    assert len(qs) == len(N_A) * (70 + 35)
+    for q, got in zip(qs, ask(qs)):
+        assert got == tan_mirror(*q[1:]), q
+        NV, NC, lg, nbx, _ = got
+        assert NC == 1 << lg and (NC >= NV or NC == 64) and (NC == 1 or NC // 2 < NV)
+        assert (nbx - 1) * (64 // NC) < q[1] <= nbx * (64 // NC)          # the row blocks cover n_a, none is empty
+
+
+def test_adj_geom_rows_per_block_are_the_tests(ask):
+    qs = [("a", n_a, M) for n_a in N_A for M in range(1, 71)]
+    for q, (MV, NC, lg, R, nb, V) in zip(qs, ask(qs)):
+        _, n_a, M = q
+        assert R == cases.adj_rows_per_block(M), q
+        assert V == (2 if M % 2 == 0 else 1) and MV * V == M
+        assert NC == 1 << lg and NC <= 16 and (NC >= MV or NC == 16) and (NC == 1 or NC // 2 < MV)
+        assert R == max(64 // NC, 8) and R + 2 <= 3 * (64 // NC)          # (ADJ_KS = 3 row slots per lane hold the tile)
+        assert nb == (n_a + R - 1) // R

@@ -170,6 +170,24 @@ def test_state_rules(hank, oracle_mod):
         hb.close()
 
 
+def test_last_ss_timings_follow_the_loops(hank, oracle_mod):
+    """(-1, -1) on a fresh context after `primal`; both loops' times after ss_jvp and after ss_vjp; a call rejected at its
+    arguments leaves the last values standing"""
+    hb, c = _ctx(hank, "ks50x2")
+    try:
+        assert hb.last_ss_timings() == (-1.0, -1.0)
+        hb.ss_jvp(np.ones((hb.n_hh, 1)), tol=S.TOL, max_iter=S.MAX_ITER)
+        tj = hb.last_ss_timings()
+        assert tj[0] > 0 and tj[1] > 0, tj
+        hb.ss_vjp(np.ones((2, 1)), tol=S.TOL, max_iter=S.MAX_ITER)
+        tv = hb.last_ss_timings()
+        assert tv[0] > 0 and tv[1] > 0, tv
+        assert _raw_jvp(hank, hb, 2, N=0)[0] == hank.hip.HANK_ERR_BAD_ARG
+        assert hb.last_ss_timings() == tv
+    finally:
+        hb.close()
+
+
 def test_calls_leave_the_context_alone(hank, oracle_mod):
     """the current tangent batch, the current cotangent batch, the memo and sweep counters, the family of the last tangent sweep:
     all as before; hank_fake_news returns the same bits before and after"""
