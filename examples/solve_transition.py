@@ -21,8 +21,8 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 
-def solve(n_a=500, n_e=4, T=300, shock=0.01, eps=1e-9, verbose=False, cold=False, inner="fixed_point", jacobian="toeplitz"):
-    """cold=True: the steady state is solved here from the YAML guesses (value iteration and stationary distribution on
+def solve(n_a=500, n_e=4, T=300, shock=0.01, eps=1e-9, verbose=False, cold=False, inner="fixed_point", jacobian="toeplitz", step="full"):
+    """step="backtrack": Newton with the backtracking step rule (the trial steps of an iteration in ONE hank_primal_batch). cold=True: the steady state is solved here from the YAML guesses (value iteration and stationary distribution on
     the device where one is present) instead of coming from the test fixtures' cache."""
     import hank_amd as h
     import hank_amd.parallel  # noqa: F401  (pulls in torch before the clocks start)
@@ -44,14 +44,67 @@ def solve(n_a=500, n_e=4, T=300, shock=0.01, eps=1e-9, verbose=False, cold=False
     h.y_Iteration.total_jvps = 0
     h.y_Iteration.setup_s = 0.0
     t0 = time.perf_counter()
-    x = h.NewtonRaphsonHANK(x0, J, {"Z": Z}, m, ss, ss, ε=eps, verbose=verbose, inner=inner)
+    x = h.NewtonRaphsonHANK(x0, J, {"Z": Z}, m, ss, ss, ε=eps, verbose=verbose, inner=inner, step=step)
     t_newton = time.perf_counter() - t0
     lin = h.LinearizedFunction(x, {"Z": Z}, m, ss, ss)
     return {"grid": f"{n_a}x{n_e}", "T": T, "shock": f"Z_t = 1 + {shock}*0.8^t", "steady_state_s": round(t_ss, 3),
             "ss_jacobian_s": round(t_jac, 3), "newton_s": round(t_newton, 3), "preconditioner_setup_s": round(h.y_Iteration.setup_s, 3),
             "newton_iterations": h.NewtonRaphsonHANK.iterations, "jvps": h.y_Iteration.total_jvps, "residual_norm": float(np.linalg.norm(lin.Fx)),
             "wall_to_converged_path_s": round(t_jac + t_newton, 3), "steady_state": "cold start" if cold else "cached",
-            "inner": inner, "jacobian": jacobian}, x
+            "inner": inner, "jacobian": jacobian, **({"step": step, "step_sizes": list(h.NewtonRaphsonHANK.step_sizes)} if step != "full" else {})}, x
+
+
+def scale_family(n_a=500, n_e=4, T=300, shock=0.01, scales=(0.5, 1.0, 2.0, -1.0), eps=1e-9, max_rounds=100):
+    """The nonlinear responses to the shock at several multiples, solved in LOCKSTEP: scenario k has the path Z_t = 1 + scales[k]·
+    shock·0.8^t and its own iterate x_k, and every round evaluates F(x_k) of all scenarios from ONE
+    hank_primal_batch, then steps each unconverged one by the chord rule x_k ← x_k − J̅⁻¹F(x_k) (J̅ the steady-state Jacobian,
+    factored once: a round costs one batch, no tangent sweep; the rule converges linearly where ‖I − J̅⁻¹J(x)‖ < 1, the regime of
+    these shocks). A converged scenario (‖step‖ ≤ eps) keeps its x. The first round from the steady state IS the first-order
+    solution x_ss − J̅⁻¹F(x_ss; Z_k): each peak response is printed beside it."""
+    import hank_amd as h
+    from conftest import ks_setup
+    from hank_amd.Aggregation import Residuals
+    from hank_amd.BackwardIteration import ensure_het_outputs, household_block, household_inputs
+    from hank_amd.GeneralStructures import assemble_full_xMat, vars_of_type
+    from hank_amd.NewtonRaphson import _lu_solver, release_linear_solver
+    m, ss, _ = ks_setup(n_a, n_e, T)
+    P, K = T - 1, len(scales)
+    names = ("Y", "KS", "r", "w")
+    Zs = [{"Z": 1.0 + sc * shock * 0.8 ** np.arange(1, P + 1)} for sc in scales]
+    x_ss = np.tile(np.array([ss.vars[k] for k in names]), P)
+    solve_J = _lu_solver(h.getSteadyStateJacobian(ss, m))
+    hb = household_block(m)
+    hb.set_boundary(ss.value, ss.D)
+    het = vars_of_type(m, "heterogeneous")
+    out_idx = [tuple(m.value_fn.outputs).index(k) for k in het]
+    n_out = 1 + max(out_idx)
+    if n_out > 2:
+        ensure_het_outputs(hb, n_out)
+    xs = np.tile(x_ss[:, None], (1, K))
+    done, first, rounds = np.zeros(K, dtype=bool), None, 0
+    t0 = time.perf_counter()
+    try:
+        while not done.all() and rounds < max_rounds:
+            xhh = np.stack([household_inputs(xs[:, k], Zs[k], m)[0] for k in range(K)], axis=2)
+            aggs, _ = hb.primal_batch(xhh, n_het=n_out)                 # ONE batch per round (a failing scenario raises)
+            for k in np.flatnonzero(~done):
+                agg = {name: aggs[:, o, k] for name, o in zip(het, out_idx)}
+                y = solve_J(Residuals(assemble_full_xMat(xs[:, k], agg, Zs[k], m, ss, ss), m))
+                xs[:, k] -= y
+                done[k] = np.linalg.norm(y) <= eps
+            first = xs.copy() if first is None else first
+            rounds += 1
+    finally:
+        release_linear_solver()
+    wall = time.perf_counter() - t0
+
+    def peaks(x):
+        d = x.reshape(len(names), P, order="F") - np.array([ss.vars[k] for k in names])[:, None]
+        return {k: float(d[j, np.argmax(np.abs(d[j]))]) for j, k in enumerate(names)}
+
+    return {"grid": f"{n_a}x{n_e}", "T": T, "shock": f"Z_t = 1 + s*{shock}*0.8^t", "scales": list(scales), "rounds": rounds, "primal_batches": rounds,
+            "converged": done.tolist(), "lockstep_s": round(wall, 3),
+            "peak_response": {str(sc): {"nonlinear": peaks(xs[:, k]), "first_order": peaks(first[:, k])} for k, sc in enumerate(scales)}}
 
 
 def gradient(n_a=500, n_e=4, T=300, shock=0.01, chunk=256):
@@ -213,6 +266,8 @@ if __name__ == "__main__":
     ap.add_argument("--cold", action="store_true", help="solve the steady state from the YAML guesses (no fixture)")
     ap.add_argument("--inner", default="fixed_point", choices=["fixed_point", "krylov"], help="y-iteration: the reference's damped fixed point or GMRES on J(x) preconditioned by the steady-state Jacobian")
     ap.add_argument("--jacobian", default="toeplitz", choices=["toeplitz", "columns"])
+    ap.add_argument("--step", default="full", choices=["full", "backtrack"], help="Newton's step rule: the reference's full step, or backtracking on ½‖F‖² with the trial steps x − 2^-j y in one hank_primal_batch")
+    ap.add_argument("--scale", default=None, metavar="S1,S2,...", help="the nonlinear responses to the shock at these multiples (e.g. 0.5,1,2,-1), solved in lockstep from ONE hank_primal_batch per round; each peak response beside the first-order one from J̅")
     ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one hank_vjp against n_hh·P JVP columns")
     ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one hank_vjp_boundary, checked against two hank_jvp_boundary directions")
     ap.add_argument("--ss-gradient", action="store_true", help="with --permanent: the gradient of ½‖F(x)‖² with respect to the ending steady state's household prices through V_T (hank_vjp_het_boundary, then hank_ss_vjp), beside a central difference in one random direction")
@@ -225,7 +280,9 @@ if __name__ == "__main__":
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", torch.cuda.current_device()))
-    if a.boundary_gradient:
+    if a.scale:
+        out = scale_family(a.n_a, a.n_e, a.T, a.shock, tuple(float(v) for v in a.scale.split(",")))
+    elif a.boundary_gradient:
         out = boundary_gradient(a.n_a, a.n_e, a.T, a.shock)
     elif a.gradient:
         out = gradient(a.n_a, a.n_e, a.T, a.shock)
@@ -234,7 +291,7 @@ if __name__ == "__main__":
     elif a.permanent is not None:
         out = solve_permanent(a.n_a, a.n_e, a.T, a.permanent, verbose=a.verbose)[0]
     else:
-        out, x = solve(a.n_a, a.n_e, a.T, a.shock, verbose=a.verbose, cold=a.cold, inner=a.inner, jacobian=a.jacobian)
+        out, x = solve(a.n_a, a.n_e, a.T, a.shock, verbose=a.verbose, cold=a.cold, inner=a.inner, jacobian=a.jacobian, step=a.step)
     out["n_gpus"] = world
     if rank == 0:
         print(json.dumps(out))

@@ -424,6 +424,28 @@ int hank_last_vjp_timings(hank_ctx *ctx, double out_ms[2], int32_t launches[2]);
  * (lambda) loop, in the order of iters_out; -1 before the first call. */
 int hank_last_ss_timings(hank_ctx *ctx, double out_ms[2]);
 
+/* ---- the household block at K input paths: one chain of launches --------------------------------------------------------------
+ * hank_primal_batch  ==  the household block inside fullFunction (NewtonRaphson.jl:77-83) at K points x_1 .. x_K at once — what a
+ *   step rule for Newton needs (the reference's alphaUpdate is a stub, NewtonRaphson.jl:117-120, and the outer loop :27-46 takes the full
+ *   step unconditionally), and what nonlinear responses to a family of shocks and central differences need. Scenario k is the primal
+ *   sweep at x_k: K independent paths share the launches of one (gridDim.y = scenario).
+ *   xhh (n_hh, P, K) -> agg_out (P, n_het, K): outputs 0 .. n_het-1 of hank_get_het_outputs (n_het up to the count declared with
+ *   hank_set_het_outputs: more is HANK_ERR_NOT_READY); policy_out (G, P, K) or NULL: every scenario's policy sequence.
+ *   Needs a boundary (else HANK_ERR_NOT_READY); 1 <= K <= 64 (else HANK_ERR_BAD_ARG); the host-pointer form refuses a scenario
+ *   with 1 + r <= 0 (HANK_ERR_DOMAIN) before anything runs. Output 0 and the policies hold the bits the per-period launches give
+ *   for that path alone (HANK_SCHEDULE=launch), whatever K is and wherever the scenario sits in the batch.
+ *   The call leaves the context's recorded primal, its tangent and cotangent batches, the memo and the counters of hank_stats
+ *   exactly as they were: it works on K records of its own, grown to the widest K asked for and freed by hank_destroy.
+ *   Verdict, per scenario: status_out[k] (K codes, or NULL) is scenario k's status (HANK_OK, HANK_ERR_KNOTS, HANK_ERR_DOMAIN,
+ *   HANK_ERR_NONMONOTONE). The call returns HANK_OK when every scenario is; otherwise the code of the lowest failing k, and the
+ *   message names k (from 0, as status_out counts), the period and the point. The outputs of the healthy scenarios are valid
+ *   either way. The device-pointer form is asynchronous: its verdict arrives at the next hank_check, once, and touches neither
+ *   the record nor the batches.
+ * hank_last_batch_timings: HIP-event times (ms) of the last batch's backward and forward chains; -1 for none. */
+int hank_primal_batch(hank_ctx *ctx, int32_t n_het, const double *xhh, int32_t K, double *agg_out, double *policy_out, int32_t *status_out);
+int hank_primal_batch_dev(hank_ctx *ctx, int32_t n_het, const double *d_xhh, int32_t K, double *d_agg_out, double *d_policy_out);
+int hank_last_batch_timings(hank_ctx *ctx, double out_ms[2]);
+
 /* Counters of this context (tests and scripts): out[0] sweep kernels launched by the persistent schedule, out[1] tangent
  * workspaces allocated (a change of batch width N re-uses a cached workspace: a small most-recently-used cache, 3 deep),
  * out[2] hipGraphs captured (per-period schedule), out[3] schedule in use (1 = XCD-local persistent sweeps, 0 = one

@@ -371,6 +371,7 @@ def y_Iteration(J̅, x, y0, exog_paths, mod: SequenceModel, ss_initial, ss_endin
     inner="krylov" (opt-in, not in the reference): GMRES on J(x) with J̅⁻¹ as right preconditioner — the same fixed point
     (the exact Newton step) in a handful of JVPs instead of the ≈ 21 that α = 0.5 needs to contract 1e-9 by halves."""
     lin = LinearizedFunction(x, exog_paths, mod, ss_initial, ss_ending)
+    y_Iteration.last_Fx = lin.Fx            # F(x) of this linearisation: the step rule's ‖F(x)‖ (NewtonRaphsonHANK, step="backtrack")
     y = np.asarray(y0, dtype=np.float64)
     n = len(y)
     y_old, M, R = np.ones(n), np.ones(n), np.ones(n)
@@ -427,21 +428,106 @@ def y_Iteration(J̅, x, y0, exog_paths, mod: SequenceModel, ss_initial, ss_endin
     return y
 
 
+class StepRuleError(RuntimeError):
+    """no trial step of the backtracking rule lowers ‖F‖ (every trial failed on the device, or y is no descent direction)."""
+
+
+def backtrack(norms2, f0_2, c1: float = 1e-4) -> int:
+    """the step rule of NewtonRaphsonHANK(step="backtrack") as a pure function: norms2[j] = ‖F(x − 2^-j y)‖² of the trials
+    j = 0, 1, …, f0_2 = ‖F(x)‖². -> the first j with norms2[j] ≤ (1 − 2 c1 2^-j) f0_2 — Armijo's condition on ½‖F‖² along a Newton
+    direction y (J y = F: the directional derivative of ½‖F‖² at α = 0 is −‖F‖²). When no trial passes: the trial of the smallest
+    norm, if that is below ‖F(x)‖; otherwise StepRuleError. Entries that are not finite (a scenario the device refused) are
+    skipped."""
+    n2 = np.asarray(norms2, dtype=np.float64).reshape(-1)
+    ok = np.isfinite(n2)
+    for j in range(n2.size):
+        if ok[j] and n2[j] <= (1.0 - 2.0 * c1 * 2.0 ** -j) * f0_2:
+            return j
+    if ok.any():
+        j = int(np.argmin(np.where(ok, n2, np.inf)))
+        if n2[j] < f0_2:
+            return j
+    raise StepRuleError(f"backtrack: none of the {n2.size} trial steps lowers ‖F‖² = {f0_2:.6e} (trials: {n2.tolist()})")
+
+
+def residuals_batch(xs, exog_paths, mod: SequenceModel, ss_initial, ss_ending):
+    """fullFunction (NewtonRaphson.jl:77-83) at K points at once: xs (n, K) -> (n_res, K). The household block of every column
+    runs in ONE hank_primal_batch (K paths through one chain of launches, at the model's count of device outputs); the padded
+    matrix and the residuals are assembled per column on the host. The context's recorded primal stays as it was, so a
+    linearisation at another x keeps serving its JVPs. A column the device refuses (its status is not HANK_OK), or whose 1 + r is
+    not positive somewhere, comes back as a column of inf."""
+    xs = np.asarray(xs, dtype=np.float64)
+    if xs.ndim == 1:
+        xs = xs[:, None]
+    K = xs.shape[1]
+    hb = household_block(mod)
+    het = vars_of_type(mod, "heterogeneous")
+    outs = tuple(mod.value_fn.outputs)
+    out_idx = [outs.index(k) for k in het]
+    n_out = 1 + max(out_idx)
+    xhh = np.stack([household_inputs(xs[:, k], exog_paths, mod)[0] for k in range(K)], axis=2)        # (n_hh, P, K)
+    before = hb._boundary
+    hb.set_boundary(ss_ending.value, ss_initial.D)
+    if before is None or not (np.array_equal(before[0], hb._boundary[0]) and np.array_equal(before[1], hb._boundary[1])):
+        hb._generation = getattr(hb, "_generation", 0) + 1      # a new boundary: the record is gone, whoever held it re-records
+        hb._last = None
+    if n_out > 2:
+        ensure_het_outputs(hb, n_out)
+    ok = np.ones(K, dtype=bool)
+    if mod.value_fn.household_inputs[0] == "r":
+        ok = np.all(1.0 + xhh[0] > 0.0, axis=0)
+    out = np.full((len(mod.equations) * (mod.compspec.T - 1), K), np.inf)
+    cols = np.flatnonzero(ok)
+    for c0 in range(0, len(cols), 64):                   # (the library takes up to 64 scenarios per call)
+        chunk = cols[c0:c0 + 64]
+        aggs, status = hb.primal_batch(xhh[:, :, chunk], n_het=n_out, check=False)
+        for j, k in enumerate(chunk):
+            if status[j] != 0:
+                continue
+            agg = {name: aggs[:, o, j] for name, o in zip(het, out_idx)}
+            out[:, k] = Residuals(assemble_full_xMat(xs[:, k], agg, exog_paths, mod, ss_initial, ss_ending), mod)
+    return out
+
+
 @host_algebra
 def NewtonRaphsonHANK(x_0, J̅, exog_paths, mod: SequenceModel, ss_initial, ss_ending, *, ε: float = 1e-9,
-                      verbose: bool = False, linear_solver: str = "auto", inner: str = "fixed_point", α: float | None = None):
+                      verbose: bool = False, linear_solver: str = "auto", inner: str = "fixed_point", α: float | None = None,
+                      step: str = "full", n_trial: int = 6, c1: float = 1e-4):
     """outer Newton loop (NewtonRaphson.jl:27-46): x ← x − y until ‖y‖ ≤ ε or 100 iterations. `inner` / `α`: see y_Iteration
-    (defaults = the reference's damped fixed point)."""
+    (defaults = the reference's damped fixed point).
+
+    step="full" (default, the reference): the full Newton step, unconditionally. step="backtrack" (not in the reference, whose
+    alphaUpdate is a stub, NewtonRaphson.jl:117-120): after each y_Iteration the trials x − 2^-j y, j = 0 .. n_trial-1, are
+    evaluated in ONE `residuals_batch` and `backtrack` picks the step; ‖F(x)‖ is the linearisation's own (`y_Iteration.last_Fx`),
+    not one more primal. A direction already below ε (the loop's last) is taken whole, without trials: at that size the trials differ
+    by the inner loop's own tolerance and say nothing. `NewtonRaphsonHANK.step_sizes` lists the accepted α, `.residual_norms` ‖F‖ at every iterate."""
+    if step not in ("full", "backtrack"):
+        raise ValueError(f"unknown step rule {step!r} (full | backtrack)")
     x = np.asarray(x_0, dtype=np.float64)
     y = x.copy()
     i = 1
+    NewtonRaphsonHANK.step_sizes, NewtonRaphsonHANK.residual_norms = [], []
     try:
         while ε < np.linalg.norm(y) and i < 100:
             y = y_Iteration(J̅, x, y, exog_paths, mod, ss_initial, ss_ending, verbose=verbose, linear_solver=linear_solver, inner=inner, α=α)
-            x = x - y
+            if step == "full":
+                x = x - y
+            elif not ε < np.linalg.norm(y):         # a step below the tolerance ends the loop: taken whole, as the reference takes it
+                x = x - y
+                NewtonRaphsonHANK.step_sizes.append(1.0)
+                NewtonRaphsonHANK.residual_norms[len(NewtonRaphsonHANK.step_sizes) - 1:] = [float(np.linalg.norm(y_Iteration.last_Fx))]
+            else:
+                f0_2 = float(np.sum(np.asarray(y_Iteration.last_Fx, dtype=np.float64) ** 2))
+                alphas = 2.0 ** -np.arange(int(n_trial), dtype=np.float64)
+                xs = x[:, None] - y[:, None] * alphas[None, :]
+                n2 = np.sum(residuals_batch(xs, exog_paths, mod, ss_initial, ss_ending) ** 2, axis=0)
+                j = backtrack(n2, f0_2, c1)
+                x = np.ascontiguousarray(xs[:, j])
+                NewtonRaphsonHANK.step_sizes.append(float(alphas[j]))
+                NewtonRaphsonHANK.residual_norms[len(NewtonRaphsonHANK.step_sizes) - 1:] = [float(np.sqrt(f0_2)), float(np.sqrt(n2[j]))]
             i += 1
             if verbose:
-                print(f"Iteration: {i}, norm(y): {np.linalg.norm(y)}")
+                print(f"Iteration: {i}, norm(y): {np.linalg.norm(y)}" + (f", α: {NewtonRaphsonHANK.step_sizes[-1]}" if step != "full" else ""))
     finally:
         release_linear_solver()         # (the factorisations of J̅ live for one solve, not for the life of the process)
     NewtonRaphsonHANK.iterations = i - 1

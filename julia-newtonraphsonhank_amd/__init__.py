@@ -17,7 +17,7 @@ from .Aggregation import Residuals
 from .BackwardIteration import BackwardIteration, household_block
 from .ForwardIteration import ForwardIteration, make_endogenous_transition, transition_step
 from .SteadyState import SSAssembler, SteadyState, find_ss, get_SteadyStates
-from .NewtonRaphson import LinearizedFunction, NewtonRaphsonHANK, make_fullFunction, y_Iteration
+from .NewtonRaphson import LinearizedFunction, NewtonRaphsonHANK, StepRuleError, backtrack, make_fullFunction, residuals_batch, y_Iteration
 from .SteadyStateJacobian import getSteadyStateJacobian
 from .hip import HouseholdBlock, HankHIPError, KnotsNotSortedError, DomainError, NoDeviceError
 

@@ -9,6 +9,7 @@
 #include "hank_jacobian.h"
 #include "hank_wide.h"
 #include "hank_hetx.h"
+#include "hank_scen.h"
 #include "hank_adjoint.h"
 #include "hank_boundary.h"
 #include "hank_ssdiff_launch.h"
@@ -181,6 +182,24 @@ struct CotBatch {
 // again: the NX > 0 Sweep A graphs hold the addresses.
 struct HxRecord { DevBuf<double> f, fc, S; bool valid = false; };
 
+// hank_primal_batch's workspace (hank_scen.h): K scenario records carved alike from ONE slab (R0 is scenario
+// 0's, `stride` bytes to the next), the scenarios' inputs, partial sums, error words and outputs, and the two graphs of the last
+// (K, n_het) that ran. Grown to the widest K asked for (build_scenwork into a local, moved in when complete: a failed allocation
+// leaves the context's workspace as it was); freed with the context.
+struct ScenWork {
+    int K = 0;                         // scenarios the buffers hold
+    int gK = 0, g_nhet = 0;            // what the graphs were captured for (gK = 0: none)
+    Record R0{};                       // views into slab (seg, lwg: null — no reader of either runs on a scenario)
+    size_t stride = 0;
+    DevBuf<char> slab;
+    DevBuf<double> xhh;                // (n_hh, P, K)
+    DevBuf<double> aggpart, agg_rm;    // [k][t][block][2], [k][t][2]
+    DevBuf<double> hxpart, hx_rm;      // [k][t][block][NX], [k][t][NX]
+    DevBuf<double> out;                // (P, n_het, K)
+    DevBuf<int> err;                   // [K][4]
+    GraphExec g_back, g_fwd;
+};
+
 // The current tangent batch: at most ONE is current, and it belongs to the recorded primal. Written by batch_ran ("family F has
 // just run a batch on workspace W") and batch_none ("nothing is current") only; the readers ask batch_current.
 struct TanBatch {
@@ -195,7 +214,7 @@ struct TanBatch {
 };
 
 // The timed sweeps of hank_last_timings (the first six, in its slot order), hank_last_vjp_timings (the next two) and
-// hank_last_ss_timings (the last two). A span is a
+// hank_last_ss_timings (the next two) and hank_last_batch_timings (the last two). A span is a
 // begin event, an end event, a valid flag and the launch count of the run that ended it; the run functions reach them through these
 // operations only. Recording a span's begin makes it invalid until its end is recorded. What each run function leaves behind
 // (V valid, I invalid, . untouched) — the families do NOT agree, see DESIGN.md section 2a:
@@ -210,7 +229,8 @@ struct TanBatch {
 //   run_fused                 I          I         I        I        V        V       .     .      .       .
 //   enqueue_vjp               .          .         .        .        .        .       V     V      .       .
 //   ss_loop                   .          .         .        .        .        .       .     .      V       V      (the loop it was called for; I until that loop's end)
-enum Span { PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD, VJP_A, VJP_B, SS_VALUE, SS_DIST, N_SPANS };
+//   primal_batch              .          .         .        .        .        .       .     .      .       .      (its own two, SCEN_BACK and SCEN_FWD: V)
+enum Span { PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD, VJP_A, VJP_B, SS_VALUE, SS_DIST, SCEN_BACK, SCEN_FWD, N_SPANS };
 struct Spans {
     struct One { hipEvent_t ev0 = nullptr, ev1 = nullptr, from = nullptr; bool valid = false; int launches = 0; } s[N_SPANS];      // from: the event the span began with (ev0, or the end of the span before it)
     hipError_t create() { hipError_t e = hipSuccess; for (One &o : s) { if (e == hipSuccess) e = hipEventCreate(&o.ev0); if (e == hipSuccess) e = hipEventCreate(&o.ev1); } return e; }
@@ -282,6 +302,8 @@ struct hank_ctx {
     bool adj_seg_valid = false;
     DevBuf<double> d_bnd_q;        // [2][P][n_e]: Pi^{t+1} z and Pi^{t+1} 1 (hank_jvp_boundary: ensure_bnd_q), the model's; allocated once (the graphs hold its address)
     HxRecord hx;                   // the extra outputs' share of the record (ensure_hx_record), valid for the recorded primal or not
+    ScenWork scen;                 // hank_primal_batch's workspace
+    int scen_pending = 0;          // scenarios of a hank_primal_batch_dev whose verdict hank_check has not taken yet
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
     long long stats[N_STATS] = {};   // see Stat and hank_stats
     // primal memo of the host-pointer hank_primal_jvp (NewtonRaphson.jl:91-95 calls JVP(fullFunction, x, y) ~21 times at one x):
@@ -704,6 +726,7 @@ static int ensure_dual_graphs(hank_ctx *ctx, TanWork &w) {
 enum Whose { THE_RECORD, THIS_CALL };
 enum ErrIn { IN_SWEEP, IN_VFI, IN_POWER_METHOD };      // which kernels raised the word: a sweep over the periods, steps of the value iteration, the power method
 static int x_status(hank_ctx *ctx, const char *what, const XSync *fetched = nullptr);
+static int scen_pending_verdict(hank_ctx *ctx);
 // the ONE host read of the error word: drain, copy {code, period, state, index}, clear it when set (reported once: the next call starts clean)
 static int take_error_word(hank_ctx *ctx, int e[4]) {
     HIPC(ctx, join_side(ctx));
@@ -1810,7 +1833,8 @@ int hank_check(hank_ctx *ctx) {
     // the asynchronous entries cannot re-run a call: the error is reported (once, and a model error leaves no tangent batch current),
     // and a context whose schedule was not forced continues on the per-period launches, so the caller's next call succeeds
     bool moved = false;
-    return fallback_decision(ctx, device_verdict(ctx, THE_RECORD), &moved);
+    const int rc = fallback_decision(ctx, device_verdict(ctx, THE_RECORD), &moved);
+    return rc ? rc : scen_pending_verdict(ctx);      // (then what a hank_primal_batch_dev left: its own words, THIS_CALL)
 }
 
 int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
@@ -3121,6 +3145,162 @@ int hank_forward_step_dual(hank_ctx *ctx, const double *policy, const double *dp
 }
 
 }  // extern "C"
+
+// ---- hank_primal_batch[_dev]: K input paths through one chain of launches (hank_scen.h) --------------------
+// Scenario k is the launch family's hank_primal at x_k on a record of its own: the same bodies in the same order, so its policy and
+// output 0 hold that entry's bits. The entry works on ScenWork only: the context's record, primal_done, both current batches, the
+// memo, `stationary`, the schedule and the sweep counters stay as they were (hank_ss_jvp's rule). It reads what hank_set_boundary
+// left (the terminal value, D_0, zd) and the model's grids.
+constexpr int SCEN_KMAX = 64;
+
+static int build_scenwork(hank_ctx *ctx, int K, ScenWork &w) {
+    const Consts &c = ctx->c;
+    const size_t P = c.P, G = c.G, d8 = P * G * sizeof(double), KK = (size_t)K;
+    size_t off = 0;
+    const size_t o_s = carve(off, d8), o_kc = carve(off, d8), o_A = carve(off, d8), o_B = carve(off, d8), o_u = carve(off, d8), o_v = carve(off, d8),
+                 o_pol = carve(off, d8), o_lw = carve(off, d8), o_ig = carve(off, d8), o_D = carve(off, (P + 1) * G * sizeof(double)),
+                 o_ib = carve(off, P * G * sizeof(int)), o_lo = carve(off, P * G * sizeof(int)),
+                 o_st = carve(off, P * (size_t)c.n_e * (c.n_a + 1) * sizeof(int)), o_clo = carve(off, P * (size_t)c.n_e * sizeof(int));
+    w.stride = off;      // (a multiple of 256: every scenario's arrays are aligned as scenario 0's)
+    HIPC(ctx, w.slab.alloc(off * KK));
+    char *b = w.slab;
+    Record &R = w.R0;
+    R = Record{};
+    R.s = (double *)(b + o_s); R.kc = (double *)(b + o_kc); R.A = (double *)(b + o_A); R.B = (double *)(b + o_B);
+    R.u = (double *)(b + o_u); R.v = (double *)(b + o_v); R.pol = (double *)(b + o_pol); R.lw = (double *)(b + o_lw);
+    R.ig = (double *)(b + o_ig); R.Dseq = (double *)(b + o_D); R.ib = (int *)(b + o_ib); R.lo = (int *)(b + o_lo);
+    R.start = (int *)(b + o_st); R.clo = (int *)(b + o_clo);
+    const size_t nbp = ctx->nbp, NXM = (size_t)hx_count(ctx);
+    HIPC(ctx, w.xhh.alloc((size_t)c.n_hh * P * KK));
+    HIPC(ctx, w.aggpart.alloc(2 * P * nbp * KK));
+    HIPC(ctx, w.agg_rm.alloc(2 * P * KK));
+    HIPC(ctx, w.hxpart.alloc(NXM * P * nbp * KK));
+    HIPC(ctx, w.hx_rm.alloc(NXM * P * KK));
+    HIPC(ctx, w.out.alloc((size_t)het_max(ctx) * P * KK));
+    HIPC(ctx, w.err.alloc(4 * KK));
+    w.K = K;
+    return HANK_OK;
+}
+
+// the two graphs of (K, n_het): ONE linear chain each on the context's own stream, backward then forward; no side stream
+static int capture_scen_graphs(hank_ctx *ctx, ScenWork &w, int K, int n_het) {
+    const Consts &c = ctx->c;
+    const int P = c.P, NX = n_het > 2 ? n_het - 2 : 0;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(RBP * c.n_e), grd(ctx->nbp, K);
+    const size_t lds = primal_lds(c);
+    const ScenArgs a{w.R0, w.stride, w.xhh.get(), w.err.get()};
+    if (w.g_back || w.g_fwd) HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (a batch of the _dev form may still be running the graphs released here)
+    w.g_back.reset(); w.g_fwd.reset(); w.gK = 0;
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    hipLaunchKernelGGL(k_zero_i32, dim3((4 * K + 63) / 64), dim3(64), 0, s, w.err.get(), 4 * K);
+    hipLaunchKernelGGL(k_scen_egm_X, grd, blk, lds, s, c, (const double *)ctx->d_ss_value.get(), a, P - 1);
+    for (int t = P - 1; t >= 0; t--) hipLaunchKernelGGL(k_scen_egm_step, grd, blk, lds, s, c, a, t);
+    hipLaunchKernelGGL(k_scen_lottery, dim3(P * c.n_e, K), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, a, P * c.n_e);
+    int rc = end_capture(ctx, &w.g_back);
+    if (rc) return rc;
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    for (int t = 0; t < P; t++)
+        hipLaunchKernelGGL(k_scen_dist_step, grd, blk, lds, s, c, a, (const double *)ctx->d_ss_D, t, w.aggpart.get(), NX, w.hxpart.get());
+    hipLaunchKernelGGL(k_reduce_parts, dim3(K * P, 1), dim3(256), 0, s, w.aggpart.get(), ctx->nbp, 2, w.agg_rm.get());
+    if (NX > 0) hipLaunchKernelGGL(k_reduce_parts, dim3(K * P, 1), dim3(256), 0, s, w.hxpart.get(), ctx->nbp, NX, w.hx_rm.get());
+    hipLaunchKernelGGL(k_scen_outputs, dim3((K * P + 255) / 256), dim3(256), 0, s, P, c.n_hh, n_het, K, (const double *)w.xhh.get(), (const double *)w.agg_rm.get(),
+                       (const double *)ctx->d_zd.get(), (const double *)w.hx_rm.get(), w.out.get());
+    rc = end_capture(ctx, &w.g_fwd);
+    if (rc) { w.g_back.reset(); return rc; }
+    w.gK = K; w.g_nhet = n_het;
+    return HANK_OK;
+}
+
+static int ensure_scen(hank_ctx *ctx, int K, int n_het) {
+    if (ctx->scen.K < K) {
+        if (ctx->scen.K > 0) HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (a batch enqueued by the _dev form may still run on the old buffers)
+        ScenWork w;
+        const int rc = build_scenwork(ctx, K, w);
+        if (rc) return rc;      // (w goes, the context keeps what it had)
+        ctx->scen = std::move(w);
+    }
+    if (ctx->scen.gK != K || ctx->scen.g_nhet != n_het) return capture_scen_graphs(ctx, ctx->scen, K, n_het);
+    return HANK_OK;
+}
+
+// the K error words as status codes: status_out[k] (when given) for every scenario; the return value and the message are the
+// lowest failing scenario's (k counts from 0, as status_out does; period, state and index from 1, as in every message)
+static int scen_verdicts(hank_ctx *ctx, const int *words, int K, int32_t *status_out) {
+    int first = HANK_OK, kfirst = -1;
+    char keep[sizeof(ctx->errmsg)];
+    for (int k = 0; k < K; k++) {
+        const int rc = word_verdict(ctx, THIS_CALL, words + 4 * k, IN_SWEEP);
+        if (status_out) status_out[k] = rc;
+        if (rc && kfirst < 0) { first = rc; kfirst = k; memcpy(keep, ctx->errmsg, sizeof(keep)); }
+    }
+    if (kfirst < 0) { ctx->errmsg[0] = 0; return HANK_OK; }
+    keep[sizeof(keep) - 1] = 0;
+    return fail(ctx, first, "hank_primal_batch: scenario %d of %d: %.400s", kfirst, K, keep);
+}
+static int scen_pending_verdict(hank_ctx *ctx) {
+    const int K = ctx->scen_pending;
+    if (K <= 0) return HANK_OK;
+    ctx->scen_pending = 0;
+    std::vector<int> e(4 * (size_t)K);
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    HIPC(ctx, hipMemcpy(e.data(), ctx->scen.err, e.size() * sizeof(int), hipMemcpyDeviceToHost));
+    return scen_verdicts(ctx, e.data(), K, nullptr);      // (the next batch's graph clears the words)
+}
+
+static int primal_batch(hank_ctx *ctx, int n_het, const double *xhh, int K, double *agg_out, double *policy_out, int32_t *status_out, bool dev) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    if (!xhh || !agg_out) return fail(ctx, HANK_ERR_BAD_ARG, "hank_primal_batch: null pointer");
+    if (K < 1 || K > SCEN_KMAX) return fail(ctx, HANK_ERR_BAD_ARG, "hank_primal_batch: K must be 1..%d, got %d", SCEN_KMAX, K);
+    int rc = het_count_ok(ctx, "hank_primal_batch", n_het, true);
+    if (rc) return rc;
+    if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
+    const Consts &c = ctx->c;
+    const size_t P = c.P, G = c.G, nx = (size_t)c.n_hh * P, KK = (size_t)K;
+    if (!dev)
+        for (size_t k = 0; k < KK; k++)
+            for (size_t t = 0; t < P; t++)
+                if (!(1.0 + xhh[nx * k + c.n_hh * t] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "hank_primal_batch: 1 + r must be positive (scenario %zu, period %zu)", k, t + 1);
+    rc = ensure_scen(ctx, K, n_het);
+    if (rc) return rc;
+    ScenWork &w = ctx->scen;
+    hipStream_t s = ctx->stream;
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, back = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    ctx->scen_pending = 0;      // (the backward graph clears the words: an unread verdict of an earlier _dev batch goes with them)
+    HIPC(ctx, hipMemcpyAsync(w.xhh, xhh, sizeof(double) * nx * KK, in, s));
+    HIPC(ctx, ctx->spans.begin(SCEN_BACK, s));
+    HIPC(ctx, hipGraphLaunch(w.g_back, s));
+    HIPC(ctx, ctx->spans.end_begin(SCEN_BACK, c.P + 3, SCEN_FWD, s));
+    HIPC(ctx, hipGraphLaunch(w.g_fwd, s));
+    HIPC(ctx, ctx->spans.end(SCEN_FWD, s, c.P + (n_het > 2 ? 3 : 2)));
+    HIPC(ctx, hipMemcpyAsync(agg_out, w.out, sizeof(double) * P * n_het * KK, back, s));
+    if (policy_out) HIPC(ctx, hipMemcpy2DAsync(policy_out, sizeof(double) * P * G, w.R0.pol, w.stride, sizeof(double) * P * G, KK, back, s));
+    if (dev) {
+        ctx->scen_pending = K;      // the verdict arrives at hank_check
+        return HANK_OK;
+    }
+    std::vector<int> e(4 * KK);
+    HIPC(ctx, hipMemcpyAsync(e.data(), w.err, e.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));      // the call's one synchronisation
+    return scen_verdicts(ctx, e.data(), K, status_out);
+}
+
+extern "C" {
+int hank_primal_batch(hank_ctx *ctx, int32_t n_het, const double *xhh, int32_t K, double *agg_out, double *policy_out, int32_t *status_out) {
+    return primal_batch(ctx, n_het, xhh, K, agg_out, policy_out, status_out, false);
+}
+int hank_primal_batch_dev(hank_ctx *ctx, int32_t n_het, const double *d_xhh, int32_t K, double *d_agg_out, double *d_policy_out) {
+    return primal_batch(ctx, n_het, d_xhh, K, d_agg_out, d_policy_out, nullptr, true);
+}
+int hank_last_batch_timings(hank_ctx *ctx, double out_ms[2]) {
+    if (!ctx || !out_ms) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 2; k++) HIPC(ctx, ctx->spans.read((Span)(SCEN_BACK + k), &out_ms[k], nullptr));
+    return HANK_OK;
+}
+}
 
 // ---- derivatives through the steady state (hank_ssdiff.h) ------------------------------------------------
 // The loop driver of all four fixed points, in the manner of hank_vfi's launch branch: a chunk of steps is enqueued (each step =

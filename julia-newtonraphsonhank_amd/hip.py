@@ -33,6 +33,7 @@ ABI_SYMBOLS = (
     "hank_jvp_boundary", "hank_jvp_boundary_dev", "hank_vjp_boundary", "hank_vjp_boundary_dev",
     "hank_jvp_het", "hank_jvp_het_dev", "hank_vjp_het_boundary", "hank_vjp_het_boundary_dev",
     "hank_ss_jvp", "hank_ss_jvp_dev", "hank_ss_vjp", "hank_ss_vjp_dev", "hank_last_ss_timings",
+    "hank_primal_batch", "hank_primal_batch_dev", "hank_last_batch_timings",
 )
 
 
@@ -143,6 +144,9 @@ def load_library() -> C.CDLL:
     lib.hank_ss_vjp.argtypes = [vp, i32, dp, dp, dp, i32, C.c_double, i32, dp, C.POINTER(i32), dp]
     lib.hank_ss_vjp_dev.argtypes = [vp, i32, vp, vp, vp, i32, C.c_double, i32, vp, C.POINTER(i32), dp]
     lib.hank_last_ss_timings.argtypes = [vp, dp]
+    lib.hank_primal_batch.argtypes = [vp, i32, dp, i32, dp, dp, C.POINTER(i32)]
+    lib.hank_primal_batch_dev.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.hank_last_batch_timings.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
@@ -300,6 +304,39 @@ class HouseholdBlock:
         self.calls["primal_jvp"] += 1
         self._chk(self._lib.hank_primal_jvp(self._ctx, _p(x), _p(dx), N, _p(agg), _p(dagg)))
         return agg, dagg
+
+    # -- K input paths through one chain of launches ------------------------------------------
+    def primal_batch(self, xhh, n_het: int = 1, policy: bool = False, check: bool = True):
+        """the household block at K input paths at once (hank_primal_batch): xhh (n_hh, P, K) — or (n_hh, P) for one path —
+        -> (aggs (P, n_het, K), status (K,) int32[, policies (n_a, n_e, P, K) with policy=True]). Scenario k is `primal` at
+        xhh[:, :, k] on the per-period launches, bit for bit in output 0 and in the policies; n_het up to the count declared
+        with `set_het_outputs`. The context's recorded primal, its batches and its memo stay as they were. status[k] is scenario
+        k's status code; the healthy scenarios' outputs are valid whatever the others did. check=True raises the first failing
+        scenario's exception (the arrays of the call are then at `last_batch`)."""
+        x = np.asarray(xhh, dtype=np.float64)
+        if x.ndim == 2:
+            x = x[:, :, None]
+        K = x.shape[2] if x.ndim == 3 else 0
+        x = _f(x, (self.n_hh, self.P, K))
+        nh = max(int(n_het), 1)
+        aggs = np.empty((self.P, nh, max(K, 1)), order="F")
+        status = np.zeros(max(K, 1), dtype=np.int32)
+        pol = np.empty((self.n_a, self.n_e, self.P, max(K, 1)), order="F") if policy else None
+        rc = self._lib.hank_primal_batch(self._ctx, int(n_het), _p(x), K, _p(aggs), _opt(pol), status.ctypes.data_as(C.POINTER(C.c_int32)))
+        self.last_batch = (aggs, status, pol)
+        if rc != HANK_OK and (check or not (1 <= K <= 64) or not np.any(status)):      # (a refusal of the call itself always raises)
+            self._chk(rc)
+        return (aggs, status, pol) if policy else (aggs, status)
+
+    def primal_batch_dev(self, n_het: int, d_xhh_ptr: int, K: int, d_agg_ptr: int, d_policy_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream; the verdict arrives at `check`)."""
+        self._chk(self._lib.hank_primal_batch_dev(self._ctx, int(n_het), C.c_void_p(d_xhh_ptr), int(K), C.c_void_p(d_agg_ptr), C.c_void_p(d_policy_ptr or None)))
+
+    def last_batch_timings(self):
+        """time (ms, HIP events on the stream) of the last batch's backward and forward chains (hank_last_batch_timings)"""
+        ms = (C.c_double * 2)()
+        self._chk(self._lib.hank_last_batch_timings(self._ctx, ms))
+        return (ms[0], ms[1])
 
     def primal_jvp_dev(self, d_xhh_ptr: int, d_dxhh_ptr: int, N: int, d_agg_ptr: int = 0, d_dagg_ptr: int = 0):
         self._chk(self._lib.hank_primal_jvp_dev(self._ctx, C.c_void_p(d_xhh_ptr), C.c_void_p(d_dxhh_ptr), int(N),

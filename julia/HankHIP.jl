@@ -424,6 +424,23 @@ function hank_ss_vjp!(xhh_bar::Matrix{Float64}, ctx::HankCtx; agg_bar::Union{Not
     return xhh_bar, iters, resid
 end
 
+# ---- the household block at K input paths (hank_primal_batch) -----------------------------------------------------------------------
+# fullFunction's household block (NewtonRaphson.jl:77-83) at K points through one chain of launches — what a step rule in place of
+# the alphaUpdate stub (:117-120) evaluates. xhh (n_hh, P, K) -> aggs (P, n_het, K); policies (n_a, n_e, P, K) or nothing (not
+# wanted). Returns (aggs, status): status[k] is scenario k's code (0 = ok); check = true turns the first failing scenario into an
+# error, check = false returns the healthy scenarios' outputs with the codes. The context's recorded primal stays as it was.
+function hank_primal_batch!(aggs::Array{Float64,3}, ctx::HankCtx, xhh::Array{Float64,3}; policies::Union{Nothing,Array{Float64,4}} = nothing,
+                            check::Bool = true)
+    P, n_het, K = size(aggs)
+    @assert size(xhh) == (length(ctx.hh_rows), P, K) && P == ctx.P
+    @assert policies === nothing || size(policies) == (ctx.n_a, ctx.n_e, P, K)
+    status = zeros(Int32, K)
+    rc = GC.@preserve policies ccall((:hank_primal_batch, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                                     ctx.ptr, Int32(n_het), xhh, Int32(K), aggs, policies === nothing ? Ptr{Float64}(C_NULL) : pointer(policies), status)
+    (check || !any(!=(0), status)) && _check(ctx.ptr, rc)       # (a refusal of the call itself — no scenario's verdict — is always an error)
+    return aggs, status
+end
+
 # the cotangent of the policy sequence of the last hank_vjp! / hank_vjp_het!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
 # (ForwardIteration.jl:412-416) for the policy variable when n_het = 1
 function hank_policy_cotangent_seq(ctx::HankCtx, M::Integer)
