@@ -449,8 +449,10 @@ k_ss_lam(Consts c, Record R, AdjGeom g, const VT *__restrict__ eIn, VT *__restri
 
 // One step nu <- B_V' nu + (P_V' pbar + Vbar): the arithmetic of k_adj_egm at period 0 (neither first nor last) with the caller's
 // cotangent of V_ss added to every new nu — nu is the TOTAL cotangent of dV, so gbar = pbar - v nu and the inputs' sums read it whole.
-// partS, partM [block][3][MV]: sum sbar (s, z_e, 1) and sum nu_new (u + v a, v z_e, v) of the step; at the converged state their
-// reduction is xbar = P_x' pbar + B_x' nu (Sweep B's, taken once). parts [block][2][MV]: max |nu_new - nu|, max |nu_new|.
+// partS, partM [block][3][MV]: sum sbar (s, z_e, 1) and sum nu (u + v a, v z_e, v) of the step, BOTH at the step's input nu: their
+// reduction is xbar = P_x' (pbar - v nu) + M' nu = P_x' pbar + B_x' nu (Sweep B's, taken once). The two nu terms nearly cancel (the
+// policy is an optimum), so a partM at nu_new next to a partS at nu leaves P_x' v (nu_new - nu) uncancelled: as large as the whole
+// remaining tail of the loop, it doubled xbar's distance from the limit. parts [block][2][MV]: max |nu_new - nu|, max |nu_new|.
 // dynamic LDS: VT tile[n_e][R][NC], double Pish[n_e * n_e], VT red[n_e][6][NC]
 template <typename VT>
 __global__ void __launch_bounds__(1024)
@@ -510,13 +512,14 @@ k_ss_nu(Consts c, Record R, AdjGeom g, const int *__restrict__ sb, const VT *__r
             for (int e1 = 0; e1 < ne; e1++) mn = vadd(mn, vmul(Pish[e1 + ne * e], tile[((size_t)e1 * NS + slot) * g.NC + nl]));
             const size_t idx = (colb + i) * MV + m;
             if (vbar) mn = vadd(mn, vbar[idx]);
-            inc = ss_max(inc, ss_abs(vsub(mn, nuIn[idx])));
+            const VT old = nuIn[idx];
+            inc = ss_max(inc, ss_abs(vsub(mn, old)));
             sc = ss_max(sc, ss_abs(mn));
             nuOut[idx] = mn;
             const double u1 = R.u[colb + i], v1 = R.v[colb + i];
-            sum[3] = vadd(sum[3], vmul(u1 + v1 * c.a[i], mn));
-            sum[4] = vadd(sum[4], vmul(v1 * ze, mn));
-            sum[5] = vadd(sum[5], vmul(v1, mn));
+            sum[3] = vadd(sum[3], vmul(u1 + v1 * c.a[i], old));      // (the nu sbar has read: see above)
+            sum[4] = vadd(sum[4], vmul(v1 * ze, old));
+            sum[5] = vadd(sum[5], vmul(v1, old));
         }
     }
 #pragma unroll

@@ -533,6 +533,27 @@ class HouseholdBlock:
         self._ss_done("ss_vjp", ("nu", "lambda"), it, res, tol, max_iter, check)
         return out, (int(it[0]), int(it[1]))
 
+    def ss_jvp_dev(self, d_dxhh_ptr: int, N: int, d_dagg_ptr: int, d_dvalue_ptr: int = 0, d_dpolicy_ptr: int = 0, d_dD_ptr: int = 0,
+                   n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
+        """device-pointer form of `ss_jvp` (hank_ss_jvp_dev): d_dxhh (n_hh, N) in; d_dagg (n_het, N) and the exports (G, N) out,
+        all column-major, written straight to the caller's buffers; an export pointer of 0 is not wanted. The loops read their
+        stop word on the host, so the call returns with the stream drained. -> iters; `last_ss` as after `ss_jvp`."""
+        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
+        self._chk(self._lib.hank_ss_jvp_dev(self._ctx, int(n_het), C.c_void_p(d_dxhh_ptr), int(N), float(tol), int(max_iter), C.c_void_p(d_dvalue_ptr or None),
+                                            C.c_void_p(d_dpolicy_ptr or None), C.c_void_p(d_dD_ptr or None), C.c_void_p(d_dagg_ptr), it, res))
+        self._ss_done("ss_jvp_dev", ("value", "distribution"), it, res, tol, max_iter, check)
+        return (int(it[0]), int(it[1]))
+
+    def ss_vjp_dev(self, d_agg_bar_ptr: int, d_value_bar_ptr: int, d_D_bar_ptr: int, M: int, d_xhh_bar_ptr: int,
+                   n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
+        """device-pointer form of `ss_vjp` (hank_ss_vjp_dev): d_agg_bar (n_het, M), d_value_bar and d_D_bar (G, M) in, a pointer
+        of 0 is a cotangent not given (at least one must be); d_xhh_bar (n_hh, M) out. -> iters; `last_ss` as after `ss_vjp`."""
+        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
+        self._chk(self._lib.hank_ss_vjp_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr or None), C.c_void_p(d_value_bar_ptr or None),
+                                            C.c_void_p(d_D_bar_ptr or None), int(M), float(tol), int(max_iter), C.c_void_p(d_xhh_bar_ptr), it, res))
+        self._ss_done("ss_vjp_dev", ("nu", "lambda"), it, res, tol, max_iter, check)
+        return (int(it[0]), int(it[1]))
+
     def policy_cotangent_seq(self, M: int) -> np.ndarray:
         """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp / vjp_het (hank_get_policy_cotangent_seq)."""
         out = np.empty((self.n_a, self.n_e, self.P, max(int(M), 1)), order="F")

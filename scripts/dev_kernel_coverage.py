@@ -7,7 +7,8 @@
     python scripts/dev_kernel_coverage.py --stats DIR_OR_CSV [...] [--out FILE]
         every kernel with its launch count, summed over the kernel-stats CSVs of a `rocprofv3 --kernel-trace --stats
         --output-format csv` run (all *kernel_stats.csv below a directory: one per traced process). A kernel at zero launches is
-        printed with its reason from REASONS when it has one, `(no reason recorded)` otherwise."""
+        printed with its reason from REASONS when it has one, `(no reason recorded)` otherwise. --only REGEX keeps the kernels whose
+        demangled name matches (a run of one test module: profiles/ss_diff_kernel_coverage.txt, --only k_ss_)."""
 import argparse
 import csv
 import re
@@ -30,7 +31,6 @@ REASONS = {
     r"k_(tan|fused)_back<1,": "1 backward row group: never the default; dev knob HANK_RG_B=1 only",
     r"k_(tan|fused)_back<4,": "4 backward row groups: the per-period launches at >= 128 lanes of directions (N >= 256 even, >= 128 odd); "
                              "the default sends such batches to the wide sweeps and no test forces the launches there",
-    r"k_ss_fwd<2, HIP_vector_type<double, 2u>, true,": "source-stationary form with two directions per lane: an even width of 18 or more; tests/test_gpu_ss_diff.py runs the widths 1, 3, 4, 33",
 }
 
 
@@ -73,8 +73,11 @@ def main():
     ap.add_argument("--list", action="store_true", help="print the kernel symbols and stop (no GPU needed)")
     ap.add_argument("--stats", nargs="*", default=[], help="kernel-stats CSVs, or directories searched for them")
     ap.add_argument("--out", help="write the report here as well")
+    ap.add_argument("--only", help="list only the kernels whose demangled name matches this regex")
     a = ap.parse_args()
     kernels = kernel_symbols()
+    if a.only:
+        kernels = [k for k in kernels if re.search(a.only, k[1])]
     if a.list or not a.stats:
         for _, d in kernels:
             print(d)
@@ -90,9 +93,9 @@ def main():
             zero += 1
             why = next((r for pat, r in REASONS.items() if re.search(pat, d)), "(no reason recorded)")
             lines.append(f"{0:>9}  {d}\n{'':>11}not launched: {why}")
-    head = [f"# {len(kernels)} kernels in the gfx950 code objects of csrc/hank_hip.hip and csrc/hank_ssdiff.hip, {len(kernels) - zero} launched, {zero} not",
+    head = [f"# {len(kernels)} kernels{f' matching {a.only}' if a.only else ''} in the gfx950 code objects of csrc/hank_hip.hip and csrc/hank_ssdiff.hip, {len(kernels) - zero} launched, {zero} not",
             f"# launch counts summed over {len(files)} kernel-stats CSV(s) of one rocprofv3 --kernel-trace --stats run"]
-    if counts:
+    if counts and not a.only:
         head.append(f"# {len(counts)} traced kernel name(s) outside the code object (torch, rocBLAS/hipBLASLt, ...) are not listed")
     text = "\n".join(head + lines) + "\n"
     print(text, end="")

@@ -81,3 +81,43 @@ def test_adj_geom_rows_per_block_are_the_tests(ask):
         assert NC == 1 << lg and NC <= 16 and (NC >= MV or NC == 16) and (NC == 1 or NC // 2 < MV)
         assert R == max(64 // NC, 8) and R + 2 <= 3 * (64 // NC)          # (ADJ_KS = 3 row slots per lane hold the tile)
         assert nb == (n_a + R - 1) // R
+
+
+# what tests/test_gpu_ss_diff.py says its widths reach in hank_ss_jvp / hank_ss_vjp (rows per wave instruction RB = 64 / NC):
+# JVP N -> (columns per lane V, NC, RB, blocks in y); the forward step is the source-stationary form where NC >= 16 (ss_jvp)
+SS_JVP_TABLE = {2: (2, 1, 64, 1), 7: (1, 8, 8, 1), 16: (2, 8, 8, 1), 9: (1, 16, 4, 1), 18: (2, 16, 4, 1), 32: (2, 16, 4, 1), 34: (2, 32, 2, 1),
+                65: (1, 64, 1, 2), 130: (2, 64, 1, 2)}
+# VJP M -> (V, NC, RB, rows per block R, blocks in y)
+SS_VJP_TABLE = {2: (2, 1, 64, 64, 1), 3: (1, 4, 16, 16, 1), 7: (1, 8, 8, 8, 1), 16: (2, 8, 8, 8, 1), 32: (2, 16, 4, 8, 1), 34: (2, 16, 4, 8, 2)}
+SS_SOURCE_STATIONARY = {2: False, 7: False, 16: False, 9: True, 18: True, 32: True, 34: True, 65: True, 130: True}
+SS_XCDMAP_FWD_MAXN = 32          # HANK_XCDMAP_FWD_MAXN: the forward step remaps its blocks while N * (columns per lane) stays below
+
+
+def test_ss_diff_widths_reach_the_geometries_they_name(ask):
+    """if the geometry rule moves, the GPU tests cannot silently stop reaching what they claim: every width of the two tables at
+    the row counts of their economies (190, 30, 40)"""
+    import re
+    for n_a in (190, 30, 40):
+        for N, (V, NC, RB, ny) in SS_JVP_TABLE.items():
+            assert V == (2 if N % 2 == 0 else 1)                      # ss_jvp's choice of lanes
+            (NV, gNC, lg, nbx, _), = ask([("t", n_a, N, V)])
+            assert (gNC, 64 // gNC, (NV + gNC - 1) // gNC) == (NC, RB, ny), (n_a, N)
+            assert nbx == (n_a + RB - 1) // RB and NV * V == N
+            assert (gNC >= 16) == SS_SOURCE_STATIONARY[N], N         # gf.ss of ss_jvp
+        for M, (V, NC, RB, R, ny) in SS_VJP_TABLE.items():
+            (MV, gNC, lg, gR, nb, gV), = ask([("a", n_a, M)])
+            assert (gV, gNC, 64 // gNC, gR, (MV + gNC - 1) // gNC) == (V, NC, RB, R, ny), (n_a, M)
+            assert nb == (n_a + R - 1) // R
+    # the widths' notes: lanes in use, the block map, the slot trips
+    assert SS_JVP_TABLE[7][1] - 7 == 1 and 16 // 2 == SS_JVP_TABLE[16][1] and 18 // 2 == 9 < SS_JVP_TABLE[18][1] and 32 // 2 == SS_JVP_TABLE[32][1]
+    src = (CSRC / "hank_device.h").read_text() + (CSRC / "hank_hip.hip").read_text()
+    assert int(re.search(r"#define\s+HANK_XCDMAP_FWD_MAXN\s+(\d+)", src).group(1)) == SS_XCDMAP_FWD_MAXN
+    assert re.search(r"gf\.ss = g\.NC >= 16 \? 1 : 0;", src), "ss_jvp no longer takes the source-stationary form at NC >= 16"
+    on = {N: N <= SS_XCDMAP_FWD_MAXN for N in SS_JVP_TABLE}          # g.N * sizeof(VT) / 8 = N
+    assert [N for N in SS_JVP_TABLE if on[N] and SS_SOURCE_STATIONARY[N]] == [9, 18, 32] and not on[34]
+    # regular blocks of the block-mapped source-stationary step (RB = 4, two row groups per block) on the three economies: a
+    # multiple of the 8 XCDs (`clamp`: 24) and two counts below 8 (4, 5); the gather form at RB = 16 (N = 3, 4) gives `clamp` 12
+    assert [(((n_a + 3) // 4) + 1) // 2 for n_a in (190, 30, 40)] == [24, 4, 5] and (190 + 15) // 16 == 12
+    R, RB = SS_VJP_TABLE[7][3], SS_VJP_TABLE[7][2]
+    assert R + 2 == 10 and -(-(R + 2) // RB) == 2                     # M = 7: NS = 10 slots, two trips of RB = 8
+    assert 65 - SS_JVP_TABLE[65][1] == 1 and 130 // 2 - SS_JVP_TABLE[130][1] == 1 and 34 // 2 - SS_VJP_TABLE[34][1] == 1   # one live lane in the second block

@@ -102,6 +102,33 @@ def test_plain_iterations_reach_the_dense_solve(name):
     assert errV <= S.bound(r["rhoV"]) and errD <= S.bound(r["rhoD"])
 
 
+@pytest.mark.parametrize("name", S.NAMES)
+def test_numpy_loops_reach_the_dense_solves(name):
+    """the loops the GPU tests count steps against (S.jvp_loops, S.vjp_loops: the device's four stopping rules on the dense
+    operators) at the tolerance of those tests, 1e-9: the JVP's land on the dense solves and the VJP's on the transposed dense
+    Jacobian inside S.bound(rho, 1e-9), none runs into the cap. The transposed loops see every cotangent at once and each alone."""
+    c = S.case(name)
+    r, tol = c["ref"], 1e-9
+    G, n_hh, n_het = c["orc"].G, len(c["x"]), c["n_het"]
+    rng = np.random.default_rng(9)
+    dx = rng.standard_normal((n_hh, 3))
+    dV, dD, (kv, kd) = S.jvp_loops(c, dx, tol)
+    refV, refD = r["JV"] @ dx, r["JD"] @ dx
+    errV, errD = np.max(np.abs(dV - refV)) / np.max(np.abs(refV)), np.max(np.abs(dD - refD)) / np.max(np.abs(refD))
+    rho = max(r["rhoV"], r["rhoD"])
+    print(f"{name}: value loop {kv} steps, {errV:.2e} (bound {S.bound(r['rhoV'], tol):.2e}); distribution loop {kd} steps, {errD:.2e} (bound {S.bound(rho, tol):.2e})")
+    assert kv < S.MAX_ITER and kd < S.MAX_ITER
+    assert errV <= S.bound(r["rhoV"], tol) and errD <= S.bound(rho, tol)
+    yb, Vb, Db = rng.standard_normal((n_het, 3)), rng.standard_normal((G, 3)), rng.standard_normal((G, 3))
+    for what, (y, v, d) in {"all": (yb, Vb, Db), "agg": (yb, None, None), "value": (None, Vb, None), "D": (None, None, Db)}.items():
+        xbar, (kn, kl) = S.vjp_loops(c, y, v, d, tol)
+        JT = (r["JY"].T @ y if y is not None else 0.0) + (r["JV"].T @ v if v is not None else 0.0) + (r["JD"].T @ d if d is not None else 0.0)
+        err = np.max(np.abs(xbar - JT)) / np.max(np.abs(JT))
+        print(f"{name} {what}: nu loop {kn} steps, lambda loop {kl} steps, xbar {err:.2e} from the transposed Jacobian (bound {S.bound(rho, tol):.2e})")
+        assert kn < S.MAX_ITER and kl < S.MAX_ITER
+        assert err <= S.bound(rho, tol)
+
+
 def test_implicit_price_jacobian_needs_the_device(hank):
     """find_ss(price_jacobian="implicit") with the host VFI raises: there is no silent fallback to finite differences"""
     from conftest import ROOT
