@@ -28,15 +28,13 @@
 //       pbar_t[j,e] -= sum_o ybx_o,t f_c,o,t[j,e] D_t[j,e]         (next to (yb0 - yb1) D_t)
 // and the household inputs' cotangents directly (k_adj_hx_out, after Sweep B): xbar_r += ybx_o,t (Sa + Sr), xbar_w += ybx_o,t Sz,
 // xbar_tr += ybx_o,t S1. Sweep B is the same: pbar carries everything it reads.
-// NOTE: k_ss_lam and k_ss_nu (hank_ssdiff.h) restate the tile mix, the bracket gather and the six block sums of k_adj_dist and k_adj_egm: a
-// shared inline function for any one of them changes these kernels' instructions (profiles/ssdiff_unit.txt), so a change here is made there too.
 #pragma once
 #include "hank_hetx.h"
 #include "hank_kernels.h"
 
 namespace hank {
 
-// (AdjGeom: hank_geom.h; ADJ_KS, adj_rows_sum, AdjHx: hank_device.h)
+// (AdjGeom: hank_geom.h; ADJ_KS, AdjLane, AdjHx, adj_dist_body, adj_egm_body, xbar_cons, xbar_hx: hank_device.h)
 
 // agg_bar (P, n_het, M) column-major -> yb0[P][M], yb1[P][M] (zeros when consumption carries no cotangent)
 __global__ void k_adj_in(const double *__restrict__ agg_bar, int P, int n_het, int M, double *__restrict__ yb0, double *__restrict__ yb1) {
@@ -87,12 +85,8 @@ __global__ void __launch_bounds__(256) k_adj_seg(Consts c, Record R, int ncols, 
     for (int r = threadIdx.x; r <= n; r += blockDim.x) out[r] = shb[r];
 }
 
-// ---- Sweep A, one period -------------------------------------------------------------------------------------------------
-// A block owns the TARGET rows [r0, r1) of the lottery, all columns: it loads lam rows r0 .. r1 (one halo row) and row 0 once,
-// adds the period's output cotangents, mixes them with Pi through the LDS tile (U), and then serves, per column, the SOURCES
-// [start[r0], start[r1]) that the recorded lottery sends to its rows — the transpose of the source-stationary forward kernel —
-// plus its share of the clamped prefix [0, clo) (sources that all read U[0] and whose policy cotangent has no lottery part:
-// shared out evenly over the row blocks). Every source row is written by exactly one block.
+// ---- Sweep A, one period: adj_dist_body (hank_device.h) --------------------------------------------------------------------------
+// A tile row is loaded with lam + yb0 pol + yb1 c (+ sum_o f_o ybx_o) of period t; source row j leaves lamOut[j] and pbar_t[j].
 // NX extra outputs (hx: nothing for NX = 0): a lane also reads f_o at its target rows, f_c,o at its source rows and ybx_o,t.
 // dynamic LDS: VT tile[n_e][R + 2][NC] (slot R + 1 = row 0), double Pish[n_e * n_e]
 template <typename VT, int NX>
@@ -100,197 +94,72 @@ __global__ void __launch_bounds__(1024)
 k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t, int first, const VT *__restrict__ yb0,
            const VT *__restrict__ yb1, const VT *__restrict__ lamIn, VT *__restrict__ lamOut, VT *__restrict__ pbar, AdjHx<VT, NX> hx) {
     extern __shared__ __attribute__((aligned(16))) double adj_sh[];
-    const int NS = g.R + 2, n = c.n_a, ne = c.n_e;
-    VT *tile = reinterpret_cast<VT *>(adj_sh);
-    double *Pish = adj_sh + (size_t)ne * NS * g.NC * (sizeof(VT) / sizeof(double));
-    const int lane = threadIdx.x & 63, e = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nl = lane & (g.NC - 1), rl = lane >> g.lgNC, RB = 64 >> g.lgNC;
-    const int m = blockIdx.y * g.NC + nl;
-    const bool mok = m < g.MV;
+    const AdjLane L = adj_lane(g);
+    const int n = c.n_a, e = L.e, m = L.m;
     const size_t MV = g.MV;
-    const int r0 = blockIdx.x * g.R, r1 = min(r0 + g.R, n);
-    for (int k = threadIdx.x; k < ne * ne; k += 64 * ne) Pish[k] = c.Pi[k];
     VT y0, y1;
     vzero(y0); vzero(y1);
-    if (mok) { y0 = yb0[(size_t)t * MV + m]; y1 = yb1[(size_t)t * MV + m]; }
+    if (L.mok) { y0 = yb0[(size_t)t * MV + m]; y1 = yb1[(size_t)t * MV + m]; }
     [[maybe_unused]] VT yx[NX > 0 ? NX : 1];
     [[maybe_unused]] const size_t PG = (size_t)c.P * c.G;
     if constexpr (NX > 0) {
 #pragma unroll
         for (int o = 0; o < NX; o++) {
             vzero(yx[o]);
-            if (mok) yx[o] = hx.ybx[((size_t)t * NX + o) * MV + m];
+            if (L.mok) yx[o] = hx.ybx[((size_t)t * NX + o) * MV + m];
         }
     }
     const double r = xhh[c.n_hh * t], w = xhh[c.n_hh * t + 1], tr = hh_tr(c, xhh, t), ze = c.z[e];
     const size_t colb = (size_t)t * c.G + (size_t)e * n;      // (t, e) column of the record
-    // 1. lam + yb0 pol + yb1 c of the block's rows, own column
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB;
-        if (slot < NS) {
-            const int row = slot == g.R + 1 ? 0 : r0 + slot;
-            VT v;
-            vzero(v);
-            if (mok && row <= r1 && row < n) {
-                const double pol = R.pol[colb + row], cons = ((1.0 + r) * c.a[row] + (w * ze + tr)) - pol;
-                if (!first) v = lamIn[((size_t)e * n + row) * MV + m];
-                v = vadd(v, vadd(vmul(pol, y0), vmul(cons, y1)));
-                if constexpr (NX > 0) {
-#pragma unroll
-                    for (int o = 0; o < NX; o++) v = vadd(v, vmul(hx.f[o * PG + colb + row], yx[o]));
-                }
-            }
-            tile[((size_t)e * NS + slot) * g.NC + nl] = v;
-        }
-    }
-    __syncthreads();
-    // 2. U[row, e] = sum_e2 Pi[e, e2] lam[row, e2], back into the tile
-    VT U[ADJ_KS];
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB;
-        vzero(U[k]);
-        if (slot < NS)
-            for (int e2 = 0; e2 < ne; e2++) U[k] = vadd(U[k], vmul(Pish[e + ne * e2], tile[((size_t)e2 * NS + slot) * g.NC + nl]));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB;
-        if (slot < NS) tile[((size_t)e * NS + slot) * g.NC + nl] = U[k];
-    }
-    __syncthreads();
-    if (!mok) return;
-    const VT *Ue = tile + (size_t)e * NS * g.NC + nl;
-    const VT yd = vsub(y0, y1);
+    VT yd;
     const double *Dprev = R.Dseq + colb, *Dnext = R.Dseq + colb + c.G;
     VT *lo_out = lamOut + ((size_t)e * n) * MV + m, *pb_out = pbar + colb * MV + m;
-    // 3. the sources of the block's target rows
-    const int *st = R.start + ((size_t)t * ne + e) * (n + 1);
-    const int j0 = min(max(st[r0], 0), n), j1 = min(max(st[r1], 0), n);
-    for (int j = j0 + rl; j < j1; j += RB) {
-        const int sl = min(max(R.lo[colb + j] - r0, 0), g.R - 1);
-        const double wj = R.lw[colb + j], gD = R.ig[colb + j] * Dprev[j], Dn = Dnext[j];
-        const VT u0 = Ue[(size_t)sl * g.NC], u1 = Ue[(size_t)(sl + 1) * g.NC];
-        st_mode<HANK_ST_STATE>(&lo_out[(size_t)j * MV], vadd(vmul(1.0 - wj, u0), vmul(wj, u1)));
-        VT ye = yd;      // the policy's direct weight in the outputs, per unit of D_t: yb0 - yb1 - sum_o f_c,o ybx_o
-        if constexpr (NX > 0) {
+    adj_dist_body<VT>(c, R, g, L, t, adj_sh,
+        [&](int row) __attribute__((always_inline)) {
+            const double pol = R.pol[colb + row], cons = ((1.0 + r) * c.a[row] + (w * ze + tr)) - pol;
+            VT v;
+            vzero(v);
+            if (!first) v = lamIn[((size_t)e * n + row) * MV + m];
+            v = vadd(v, vadd(vmul(pol, y0), vmul(cons, y1)));
+            if constexpr (NX > 0) {
 #pragma unroll
-            for (int o = 0; o < NX; o++) ye = vsub(ye, vmul(hx.fc[o * PG + colb + j], yx[o]));
-        }
-        st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], vadd(vmul(Dn, ye), vmul(gD, vsub(u1, u0))));
-    }
-    // 4. the block's share of the clamped prefix
-    const int clo = min(max(R.clo[(size_t)t * ne + e], 0), n);
-    const int c0 = (int)(((long long)clo * blockIdx.x) / gridDim.x), c1 = (int)(((long long)clo * (blockIdx.x + 1)) / gridDim.x);
-    const VT U0 = Ue[(size_t)(g.R + 1) * g.NC];
-    for (int j = c0 + rl; j < c1; j += RB) {
-        st_mode<HANK_ST_STATE>(&lo_out[(size_t)j * MV], U0);
-        VT ye = yd;
-        if constexpr (NX > 0) {
+                for (int o = 0; o < NX; o++) v = vadd(v, vmul(hx.f[o * PG + colb + row], yx[o]));
+            }
+            return v;
+        },
+        [&]() __attribute__((always_inline)) { yd = vsub(y0, y1); },
+        [&](int j, VT u0, VT u1, bool clamped) __attribute__((always_inline)) {
+            double wj = 0.0, gD = 0.0;
+            if (!clamped) { wj = R.lw[colb + j]; gD = R.ig[colb + j] * Dprev[j]; }
+            const double Dn = Dnext[j];
+            st_mode<HANK_ST_STATE>(&lo_out[(size_t)j * MV], clamped ? u0 : vadd(vmul(1.0 - wj, u0), vmul(wj, u1)));
+            VT ye = yd;      // the policy's direct weight in the outputs, per unit of D_t: yb0 - yb1 - sum_o f_c,o ybx_o
+            if constexpr (NX > 0) {
 #pragma unroll
-            for (int o = 0; o < NX; o++) ye = vsub(ye, vmul(hx.fc[o * PG + colb + j], yx[o]));
-        }
-        st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], vmul(Dnext[j], ye));
-    }
+                for (int o = 0; o < NX; o++) ye = vsub(ye, vmul(hx.fc[o * PG + colb + j], yx[o]));
+            }
+            // (a clamped source's policy cotangent has no lottery part)
+            st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], clamped ? vmul(Dn, ye) : vadd(vmul(Dn, ye), vmul(gD, vsub(u1, u0))));
+        });
 }
 
-// ---- Sweep B, one period -------------------------------------------------------------------------------------------------
-// A block owns the KNOT rows [i0, i0 + R), all columns. Knot i of column e gathers gbar = pbar_t - v_t mu over the two
-// contiguous row segments that bracket on it ([sb[i], sb[i+1]) with weight A, [sb[i-1], sb[i]) with weight B: k_adj_seg), the
-// n_e x n_e mixing of kc_t sbar goes through the LDS tile, and the block writes mu_{t+1} for its rows. A row of mu / pbar is
-// read by the (at most two) knots of its bracket. The household inputs' cotangents leave as per-block partials, summed in a
-// fixed order by k_adj_out: partS[t][block][3][M] = sum sbar (s_t, z_e, 1), partM[t+1][block][3][M] = sum mu_{t+1} (u + v a, v z_e, v).
+// ---- Sweep B, one period: adj_egm_body (hank_device.h) ---------------------------------------------------------------------------
+// gbar = pbar_t - v_t mu (mu_0 = 0: first), and the mixed rows are mu_{t+1} (dropped when last: the terminal value is fixed), which
+// the inputs' sums weigh at period t + 1. The partials are summed in a fixed order by k_adj_out:
+// partS[t][block][3][M] = sum sbar (s_t, z_e, 1), partM[t+1][block][3][M] = sum mu_{t+1} (u + v a, v z_e, v).
 // dynamic LDS: VT tile[n_e][R][NC], double Pish[n_e * n_e], VT red[n_e][6][NC]
 template <typename VT>
 __global__ void __launch_bounds__(1024)
 k_adj_egm(Consts c, Record R, AdjGeom g, int t, int first, int last, const int *__restrict__ sb, const VT *__restrict__ muIn,
           VT *__restrict__ muOut, const VT *__restrict__ pbar, VT *__restrict__ partS, VT *__restrict__ partM) {
     extern __shared__ __attribute__((aligned(16))) double adj_sh[];
-    const int n = c.n_a, ne = c.n_e;
-    const int lane = threadIdx.x & 63, e = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nl = lane & (g.NC - 1), rl = lane >> g.lgNC, RB = 64 >> g.lgNC, NS = g.R;
-    VT *tile = reinterpret_cast<VT *>(adj_sh);
-    double *Pish = adj_sh + (size_t)ne * NS * g.NC * (sizeof(VT) / sizeof(double));
-    VT *red = reinterpret_cast<VT *>(Pish + ((ne * ne + 1) & ~1));
-    const int m = blockIdx.y * g.NC + nl;
-    const bool mok = m < g.MV;
-    const size_t MV = g.MV;
-    const int i0 = blockIdx.x * g.R;
-    for (int k = threadIdx.x; k < ne * ne; k += 64 * ne) Pish[k] = c.Pi[k];
-    const size_t colb = (size_t)t * c.G + (size_t)e * n;
-    const int *sbc = sb + ((size_t)t * ne + e) * (n + 1);
-    const double ze = c.z[e];
-    VT sum[6];
-#pragma unroll
-    for (int q = 0; q < 6; q++) vzero(sum[q]);
-    // 1. sbar of the block's knots, own column; kc sbar into the tile
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB, i = i0 + slot;
-        VT sbar;
-        vzero(sbar);
-        if (mok && slot < g.R && i < n) {
-            const int b1 = min(max(sbc[i], 0), n), b0 = i > 0 ? min(max(sbc[i - 1], 0), b1) : b1, b2 = min(max(sbc[i + 1], b1), n);
-            const VT *pb = pbar + colb * MV + m, *mu = muIn + ((size_t)e * n) * MV + m;
-            for (int a = b0; a < b2; a += 2) {      // two rows per trip, their loads in flight together; summed in row order
-                const bool two = a + 1 < b2;
-                const int a1 = two ? a + 1 : a;
-                const double w0 = a < b1 ? R.B[colb + a] : R.A[colb + a], w1 = a1 < b1 ? R.B[colb + a1] : R.A[colb + a1];
-                VT g0 = pb[(size_t)a * MV], g1 = pb[(size_t)a1 * MV];
-                if (!first) {
-                    const double v0 = R.v[colb + a], v1 = R.v[colb + a1];
-                    const VT m0 = mu[(size_t)a * MV], m1 = mu[(size_t)a1 * MV];
-                    g0 = vsub(g0, vmul(v0, m0));
-                    g1 = vsub(g1, vmul(v1, m1));
-                }
-                sbar = vadd(sbar, vmul(w0, g0));
-                if (two) sbar = vadd(sbar, vmul(w1, g1));
-            }
-            sum[0] = vadd(sum[0], vmul(R.s[colb + i], sbar));
-            sum[1] = vadd(sum[1], vmul(ze, sbar));
-            sum[2] = vadd(sum[2], sbar);
-            sbar = vmul(R.kc[colb + i], sbar);
-        }
-        if (slot < g.R) tile[((size_t)e * NS + slot) * g.NC + nl] = sbar;
-    }
-    __syncthreads();
-    // 2. mu_{t+1}[i, e2] = sum_e Pi[e, e2] kc_t[e, i] sbar[e, i] for the wave's column e2 = e
-    if (!last) {
-        const size_t coln = colb + c.G;
-#pragma unroll
-        for (int k = 0; k < ADJ_KS; k++) {
-            const int slot = rl + k * RB, i = i0 + slot;
-            if (mok && slot < g.R && i < n) {
-                VT mn;
-                vzero(mn);
-                for (int e1 = 0; e1 < ne; e1++) mn = vadd(mn, vmul(Pish[e1 + ne * e], tile[((size_t)e1 * NS + slot) * g.NC + nl]));
-                st_mode<HANK_ST_STATE>(&muOut[((size_t)e * n + i) * MV + m], mn);
-                const double u1 = R.u[coln + i], v1 = R.v[coln + i];
-                sum[3] = vadd(sum[3], vmul(u1 + v1 * c.a[i], mn));
-                sum[4] = vadd(sum[4], vmul(v1 * ze, mn));
-                sum[5] = vadd(sum[5], vmul(v1, mn));
-            }
-        }
-    }
-    // 3. the block's partial sums: rows of a wave, then — sum q in wave q mod n_e — the waves, RB at a time, in a fixed order
-#pragma unroll
-    for (int q = 0; q < 6; q++) {
-        const VT v = adj_rows_sum(sum[q], g.NC);
-        if (rl == 0) red[((size_t)e * 6 + q) * g.NC + nl] = v;
-    }
-    __syncthreads();
-    for (int q = e; q < 6; q += ne) {
-        VT v;
-        vzero(v);
-        for (int e1 = rl; e1 < ne; e1 += RB) v = vadd(v, red[((size_t)e1 * 6 + q) * g.NC + nl]);
-        v = adj_rows_sum(v, g.NC);
-        if (rl == 0 && mok) {
-            if (q < 3) partS[(((size_t)t * gridDim.x + blockIdx.x) * 3 + q) * MV + m] = v;
-            else if (!last) partM[(((size_t)(t + 1) * gridDim.x + blockIdx.x) * 3 + (q - 3)) * MV + m] = v;
-        }
-    }
+    const AdjLane L = adj_lane(g);
+    const size_t MV = g.MV, per = (size_t)gridDim.x * 3 * MV;      // a period of partS / partM
+    adj_egm_body<VT>(c, R, g, L, t, t + 1, !first, !last, sb, muIn, pbar, adj_sh, partS + (size_t)t * per, partM + (size_t)(t + 1) * per,
+        [&](int i, VT mn) __attribute__((always_inline)) {
+            st_mode<HANK_ST_STATE>(&muOut[((size_t)L.e * c.n_a + i) * MV + L.m], mn);
+            return mn;
+        });
 }
 
 // xhh_bar (n_hh, P, M) column-major from the blocks' partials, in block order (the manner of k_reduce_parts: the same record
@@ -311,9 +180,9 @@ __global__ void k_adj_out(int P, int n_hh, int M, int nb, const double *__restri
     }
     const double rho = 1.0 / (1.0 + xhh[n_hh * t]), y1 = yb1[idx];
     double *out = xhh_bar + (size_t)n_hh * ((size_t)t + (size_t)P * m);
-    out[0] = (mu[0] - rho * s[0]) + y1 * agg2[t];
-    out[1] = (mu[1] - rho * s[1]) + y1 * zd[t];
-    if (n_hh > 2) out[2] = (mu[2] - rho * s[2]) + y1 * zd[P + t];
+    out[0] = xbar_cons(mu[0], rho, s[0], y1, agg2[t]);
+    out[1] = xbar_cons(mu[1], rho, s[1], y1, zd[t]);
+    if (n_hh > 2) out[2] = xbar_cons(mu[2], rho, s[2], y1, zd[P + t]);
 }
 
 // The extra outputs' direct dependence on the inputs, added to xhh_bar after k_adj_out, in output order:
@@ -324,13 +193,7 @@ __global__ void k_adj_hx_out(int P, int n_hh, int M, int NX, int SX, const doubl
     if (idx >= P * M) return;
     const int t = idx / M, m = idx - t * M;
     double *out = xhh_bar + (size_t)n_hh * ((size_t)t + (size_t)P * m);
-    for (int o = 0; o < NX; o++) {
-        const double y = ybx[((size_t)t * NX + o) * M + m];
-        const double *s = S + ((size_t)t * SX + o) * HX_NS;      // Y, Sa, Sz, S1, Sr
-        out[0] += y * (s[1] + s[4]);
-        out[1] += y * s[2];
-        if (n_hh > 2) out[2] += y * s[3];
-    }
+    for (int o = 0; o < NX; o++) xbar_hx(ybx[((size_t)t * NX + o) * M + m], S + ((size_t)t * SX + o) * HX_NS, n_hh, out);
 }
 
 }  // namespace hank

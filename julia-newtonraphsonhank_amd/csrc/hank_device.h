@@ -1,5 +1,6 @@
 // hank_device.h — what a kernel of the household block is built from: the argument structs, the constants, the lane helpers and the
-// step bodies that kernels of more than one translation unit share (hank_hip.hip's sweeps, hank_ssdiff.hip's fixed-point steps).
+// bodies that more than one kernel is a wrapper of, in either translation unit (hank_hip.hip's sweeps, hank_ssdiff.hip's fixed-point
+// steps): tan_back_body, tan_fwd_body, lottery_body, adj_dist_body, adj_egm_body and the outputs' arithmetic (out_*, xbar_*).
 // It defines no __global__ function and no __device__ variable, so any number of units may include it. hank_kernels.h,
 // hank_hetx.h, hank_adjoint.h and hank_boundary.h include it and hold the kernels.
 #pragma once
@@ -613,5 +614,280 @@ template <typename VT>
 struct AdjHx<VT, 0> {};
 
 struct SsCtl { int stop, iters; double resid; };      // a loop's stop word, the steps it took, the last increment ratio
+
+// ---- the device's error word -----------------------------------------------------------------------------------------------------
+enum { ERR_KNOTS = 3, ERR_DOMAIN = 4, ERR_NONMONO = 6 };
+
+__device__ inline void set_err(int *err, int code, int t, int e, int j) {
+    if (atomicCAS(&err[0], 0, code) == 0) {
+        err[1] = t;
+        err[2] = e;
+        err[3] = j;
+    }
+}
+
+// ---- Young lottery of one column col = (t, e) of the record R (ForwardIteration.jl:37-78): the body of k_lottery and of the
+// scenario batch's k_scen_lottery --------------------------------------------------------------------------------------------------
+// one block per column; builds lo / lw / ig and the segment offsets that turn the 2-nnz-per-column
+// scatter into a deterministic gather (the policy is monotone in wealth):
+//   clo      = number of sources clamped at the FIRST grid point (policy <= grid[1], :54-58): a
+//              prefix [0, clo) of the column, all mass to row 0 with weight one and no weight
+//              tangent — the borrowing-constraint mass point, summed separately (it is long);
+//   start[r] = max(clo, first source j with lo_j >= r): target row r receives w_j from the sources
+//              in [start[r-1], start[r]) and 1-w_j from those in [start[r], start[r+1]).
+// shlo: the block's dynamic LDS, 2 n_a + 2 ints; sh_clo: one more LDS word
+__device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, int col, int *err, int write_seg, int use_ib, int *shlo, int *sh_clo) {
+    const int t = col / c.n_e, e = col % c.n_e;
+    const size_t base = (size_t)col * c.n_a;  // == t*G + e*n_a
+    const int n = c.n_a;
+    if (threadIdx.x == 0) *sh_clo = 0;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const double p = R.pol[base + j];
+        int lo = -1, hi = n;  // grid[lo] < p <= grid[hi]  (searchsortedfirst, :52)
+        if (use_ib) {
+            // the policy is the interpolation's convex combination of grid[ib] and grid[ib + 1] (egm_Y): its lottery bracket is the
+            // interpolation's unless it sits on a grid point or was moved by the borrowing constraint — a probe of that bracket and
+            // of the one below replaces the 11 dependent loads of the bisection (which still decides whatever the probe does not)
+            const int g0 = min(max(R.ib[base + j], 0), n - 2);
+            const double a0 = c.a[g0], a1 = c.a[g0 + 1];
+            if (a0 < p && p <= a1) { lo = g0; hi = g0 + 1; }
+            else if (g0 > 0 && p <= a0 && c.a[g0 - 1] < p) { lo = g0 - 1; hi = g0; }
+        }
+        while (hi - lo > 1) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (c.a[mid] < p) lo = mid; else hi = mid;
+        }
+        int l;
+        double w, ig;
+        if (hi == 0) {            // m == 1: all mass on the first point (:54-58)
+            l = 0; w = 0.0; ig = 0.0;
+            atomicMax(sh_clo, j + 1);
+        } else if (hi >= n) {     // m > n_a: all mass on the last point (:59-63)
+            l = n - 2; w = 1.0; ig = 0.0;
+        } else {                  // interior (:64-73)
+            l = hi - 1;
+            const double gap = c.a[hi] - c.a[l];
+            w = (p - c.a[l]) / gap;
+            ig = 1.0 / gap;
+        }
+        R.lo[base + j] = l; R.lw[base + j] = w; R.ig[base + j] = ig;
+        shlo[j] = (hi == 0) ? -1 : l;   // clamped-low sources sort before every interior bracket
+    }
+    __syncthreads();
+    const int clo = *sh_clo;
+    if (threadIdx.x == 0) R.clo[col] = clo;
+    int *st = R.start + (size_t)col * (n + 1);
+    int *shst = shlo + n;          // segment offsets staged in LDS (second half of the dynamic LDS)
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const int prev = j ? shlo[j - 1] : -1, cur = shlo[j];
+        if (cur < prev) set_err(err, ERR_NONMONO, t, e, j);
+        for (int r = (prev < 0 ? 0 : prev + 1); r <= cur; r++) shst[r] = j;   // j >= clo whenever cur >= 0
+        if (j == n - 1)
+            for (int r = (cur < 0 ? 0 : cur + 1); r <= n; r++) shst[r] = n;
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r <= n; r += blockDim.x) st[r] = shst[r];
+    // per target row: its three segment bounds in one 16-byte record — what the launch family's gather reads (and k_xstat, and
+    // k_fn_impulse); a third of this kernel's bytes, and the persistent Dual pass reads none of them: written there on demand
+    // (write_seg = 0, then k_seg_build before the first reader)
+    if (write_seg)
+        for (int r = threadIdx.x; r < n; r += blockDim.x)
+            R.seg[base + r] = make_int4(r > 0 ? shst[r - 1] : shst[r], shst[r], shst[r + 1], 0);
+}
+
+// ---- the transposed steps: one body each for the sweep kernel (hank_adjoint.h) and the steady-state loop's (hank_ssdiff.h) --------
+// A thread of the transposed kernels: block = one wave per productivity column e, lanes = (column lane nl fastest, row rl), RB rows
+// per wave instruction; m: the lane's cotangent column (pair), mok: it exists.
+struct AdjLane { int e, nl, rl, RB, m; bool mok; };
+__device__ __forceinline__ AdjLane adj_lane(const AdjGeom &g) {
+    AdjLane L;
+    const int lane = threadIdx.x & 63;
+    L.e = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    L.nl = lane & (g.NC - 1); L.rl = lane >> g.lgNC; L.RB = 64 >> g.lgNC;
+    L.m = blockIdx.y * g.NC + L.nl;
+    L.mok = L.m < g.MV;
+    return L;
+}
+
+// One step of Sweep A at the record of period t. A block owns the TARGET rows [r0, r1) of the lottery, all columns: it loads the
+// rows r0 .. r1 (one halo row) and row 0 once — load(row): what a tile row holds before the mix —, mixes them with Pi through the LDS
+// tile (U), and then serves, per column, the SOURCES [start[r0], start[r1]) that the recorded lottery sends to its rows — the
+// transpose of the source-stationary forward kernel — plus its share of the clamped prefix [0, clo) (sources that all read U[0]:
+// shared out evenly over the row blocks). Every source row j meets exactly one block, once: src(j, u0, u1, clamped) with
+// u0 = U[lo_j], u1 = U[lo_j + 1] of the lane's column (both U[0] for a clamped source). begin(): once per lane with a column, behind
+// the mix — where a caller loads what only src reads, so that it does not occupy registers next to U.
+// adj_sh, dynamic LDS: VT tile[n_e][R + 2][NC] (slot R + 1 = row 0), double Pish[n_e * n_e]
+template <typename VT, typename Load, typename Begin, typename Src>
+__device__ __forceinline__ void adj_dist_body(const Consts &c, const Record &R, const AdjGeom &g, const AdjLane &L, int t, double *adj_sh, Load load,
+                                              Begin begin, Src src) {
+    const int NS = g.R + 2, n = c.n_a, ne = c.n_e;
+    VT *tile = reinterpret_cast<VT *>(adj_sh);
+    double *Pish = adj_sh + (size_t)ne * NS * g.NC * (sizeof(VT) / sizeof(double));
+    const int e = L.e, nl = L.nl, rl = L.rl, RB = L.RB;
+    const int r0 = blockIdx.x * g.R, r1 = min(r0 + g.R, n);
+    for (int k = threadIdx.x; k < ne * ne; k += 64 * ne) Pish[k] = c.Pi[k];
+    // 1. the block's rows, own column
+#pragma unroll
+    for (int k = 0; k < ADJ_KS; k++) {
+        const int slot = rl + k * RB;
+        if (slot < NS) {
+            const int row = slot == g.R + 1 ? 0 : r0 + slot;
+            VT v;
+            vzero(v);
+            if (L.mok && row <= r1 && row < n) v = load(row);
+            tile[((size_t)e * NS + slot) * g.NC + nl] = v;
+        }
+    }
+    __syncthreads();
+    // 2. U[row, e] = sum_e2 Pi[e, e2] tile[row, e2], back into the tile
+    VT U[ADJ_KS];
+#pragma unroll
+    for (int k = 0; k < ADJ_KS; k++) {
+        const int slot = rl + k * RB;
+        vzero(U[k]);
+        if (slot < NS)
+            for (int e2 = 0; e2 < ne; e2++) U[k] = vadd(U[k], vmul(Pish[e + ne * e2], tile[((size_t)e2 * NS + slot) * g.NC + nl]));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < ADJ_KS; k++) {
+        const int slot = rl + k * RB;
+        if (slot < NS) tile[((size_t)e * NS + slot) * g.NC + nl] = U[k];
+    }
+    __syncthreads();
+    if (!L.mok) return;
+    begin();
+    const VT *Ue = tile + (size_t)e * NS * g.NC + nl;
+    const size_t colb = (size_t)t * c.G + (size_t)e * n;      // (t, e) column of the record
+    // 3. the sources of the block's target rows
+    const int *st = R.start + ((size_t)t * ne + e) * (n + 1);
+    const int j0 = min(max(st[r0], 0), n), j1 = min(max(st[r1], 0), n);
+    for (int j = j0 + rl; j < j1; j += RB) {
+        const int sl = min(max(R.lo[colb + j] - r0, 0), g.R - 1);
+        src(j, Ue[(size_t)sl * g.NC], Ue[(size_t)(sl + 1) * g.NC], false);
+    }
+    // 4. the block's share of the clamped prefix
+    const int clo = min(max(R.clo[(size_t)t * ne + e], 0), n);
+    const int c0 = (int)(((long long)clo * blockIdx.x) / gridDim.x), c1 = (int)(((long long)clo * (blockIdx.x + 1)) / gridDim.x);
+    const VT U0 = Ue[(size_t)(g.R + 1) * g.NC];
+    for (int j = c0 + rl; j < c1; j += RB) src(j, U0, U0, true);
+}
+
+// One step of Sweep B at the record of period t. A block owns the KNOT rows [i0, i0 + R), all columns. Knot i of column e gathers
+// gbar = pbar - v mu (sub; pbar alone without it) over the two contiguous row segments that bracket on it ([sb[i], sb[i+1]) with
+// weight A, [sb[i-1], sb[i]) with weight B: k_adj_seg); the n_e x n_e mixing of kc sbar goes through the LDS tile; mix: every mixed
+// row mn = sum_e Pi[e, e2] kc[e, i] sbar[e, i] goes to row(i, mn), which stores the new state and returns the state the inputs'
+// sums weigh with (u + v a, v z_e, v) of period tm. The household inputs' cotangents leave as per-block partials, every sum in a
+// fixed order: partS[block][3][MV] = sum sbar (s, z_e, 1), partM[block][3][MV] (written when mix) the sums of what row returned.
+// adj_sh, dynamic LDS: VT tile[n_e][R][NC], double Pish[n_e * n_e], VT red[n_e][6][NC]
+template <typename VT, typename Row>
+__device__ __forceinline__ void adj_egm_body(const Consts &c, const Record &R, const AdjGeom &g, const AdjLane &L, int t, int tm, bool sub, bool mix,
+                                             const int *__restrict__ sb, const VT *__restrict__ muIn, const VT *__restrict__ pbar, double *adj_sh,
+                                             VT *__restrict__ partS, VT *__restrict__ partM, Row row) {
+    const int n = c.n_a, ne = c.n_e, NS = g.R;
+    const int e = L.e, nl = L.nl, rl = L.rl, RB = L.RB, m = L.m;
+    const bool mok = L.mok;
+    VT *tile = reinterpret_cast<VT *>(adj_sh);
+    double *Pish = adj_sh + (size_t)ne * NS * g.NC * (sizeof(VT) / sizeof(double));
+    VT *red = reinterpret_cast<VT *>(Pish + ((ne * ne + 1) & ~1));
+    const size_t MV = g.MV;
+    const int i0 = blockIdx.x * g.R;
+    for (int k = threadIdx.x; k < ne * ne; k += 64 * ne) Pish[k] = c.Pi[k];
+    const size_t colb = (size_t)t * c.G + (size_t)e * n;
+    const int *sbc = sb + ((size_t)t * ne + e) * (n + 1);
+    const double ze = c.z[e];
+    VT sum[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) vzero(sum[q]);
+    // 1. sbar of the block's knots, own column; kc sbar into the tile
+#pragma unroll
+    for (int k = 0; k < ADJ_KS; k++) {
+        const int slot = rl + k * RB, i = i0 + slot;
+        VT sbar;
+        vzero(sbar);
+        if (mok && slot < g.R && i < n) {
+            const int b1 = min(max(sbc[i], 0), n), b0 = i > 0 ? min(max(sbc[i - 1], 0), b1) : b1, b2 = min(max(sbc[i + 1], b1), n);
+            const VT *pb = pbar + colb * MV + m, *mu = muIn + ((size_t)e * n) * MV + m;
+            for (int a = b0; a < b2; a += 2) {      // two rows per trip, their loads in flight together; summed in row order
+                const bool two = a + 1 < b2;
+                const int a1 = two ? a + 1 : a;
+                const double w0 = a < b1 ? R.B[colb + a] : R.A[colb + a], w1 = a1 < b1 ? R.B[colb + a1] : R.A[colb + a1];
+                VT g0 = pb[(size_t)a * MV], g1 = pb[(size_t)a1 * MV];
+                if (sub) {
+                    const double v0 = R.v[colb + a], v1 = R.v[colb + a1];
+                    const VT m0 = mu[(size_t)a * MV], m1 = mu[(size_t)a1 * MV];
+                    g0 = vsub(g0, vmul(v0, m0));
+                    g1 = vsub(g1, vmul(v1, m1));
+                }
+                sbar = vadd(sbar, vmul(w0, g0));
+                if (two) sbar = vadd(sbar, vmul(w1, g1));
+            }
+            sum[0] = vadd(sum[0], vmul(R.s[colb + i], sbar));
+            sum[1] = vadd(sum[1], vmul(ze, sbar));
+            sum[2] = vadd(sum[2], sbar);
+            sbar = vmul(R.kc[colb + i], sbar);
+        }
+        if (slot < g.R) tile[((size_t)e * NS + slot) * g.NC + nl] = sbar;
+    }
+    __syncthreads();
+    // 2. the mixed rows of the wave's column e2 = e
+    if (mix) {
+        const size_t colm = (size_t)tm * c.G + (size_t)e * n;
+#pragma unroll
+        for (int k = 0; k < ADJ_KS; k++) {
+            const int slot = rl + k * RB, i = i0 + slot;
+            if (mok && slot < g.R && i < n) {
+                VT mn;
+                vzero(mn);
+                for (int e1 = 0; e1 < ne; e1++) mn = vadd(mn, vmul(Pish[e1 + ne * e], tile[((size_t)e1 * NS + slot) * g.NC + nl]));
+                const VT ms = row(i, mn);
+                const double u1 = R.u[colm + i], v1 = R.v[colm + i];
+                sum[3] = vadd(sum[3], vmul(u1 + v1 * c.a[i], ms));
+                sum[4] = vadd(sum[4], vmul(v1 * ze, ms));
+                sum[5] = vadd(sum[5], vmul(v1, ms));
+            }
+        }
+    }
+    // 3. the block's partial sums: rows of a wave, then — sum q in wave q mod n_e — the waves, RB at a time, in a fixed order
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        const VT v = adj_rows_sum(sum[q], g.NC);
+        if (rl == 0) red[((size_t)e * 6 + q) * g.NC + nl] = v;
+    }
+    __syncthreads();
+    for (int q = e; q < 6; q += ne) {
+        VT v;
+        vzero(v);
+        for (int e1 = rl; e1 < ne; e1 += RB) v = vadd(v, red[((size_t)e1 * 6 + q) * g.NC + nl]);
+        v = adj_rows_sum(v, g.NC);
+        if (rl == 0 && mok) {
+            if (q < 3) partS[((size_t)blockIdx.x * 3 + q) * MV + m] = v;
+            else if (mix) partM[((size_t)blockIdx.x * 3 + (q - 3)) * MV + m] = v;
+        }
+    }
+}
+
+// ---- the outputs' arithmetic: consumption's affine identity and the extra outputs' direct terms, forward and transposed -----------
+//     C_t  = (1+r_t) AD_t + w_t ZD_t + tr_t MD_t - KD_t,      AD_t = sum a D_t, ZD_t = sum z_e D_t, MD_t = sum D_t
+//     dC_t = dr_t AD_t + dw_t ZD_t + dtr_t MD_t + (1+r_t) dAD_t - dKD_t
+//     dY^o_t = T_o,t + dr_t (Sa + Sr) + dw_t Sz + dtr_t S1      (S: k_hx_record's Y, Sa, Sz, S1, Sr)
+__device__ __forceinline__ double out_cons(double r, double w, double tr, double AD, double ZD, double MD, double KD) {
+    return ((1.0 + r) * AD + w * ZD + tr * MD) - KD;
+}
+__device__ __forceinline__ double out_dcons(double r, double dr, double dw, double dtr, double AD, double ZD, double MD, double dAD, double dKD) {
+    return (dr * AD + dw * ZD + dtr * MD + (1.0 + r) * dAD) - dKD;
+}
+__device__ __forceinline__ double out_dhx(double T, double dr, double dw, double dtr, const double *S) {
+    return T + dr * (S[1] + S[4]) + dw * S[2] + dtr * S[3];
+}
+// transposed: input q's cotangent from Sweep B's sums and consumption's direct term (d: sum a D, sum z_e D or sum D), and an extra
+// output's direct terms added to o = (xbar_r, xbar_w, xbar_tr)
+__device__ __forceinline__ double xbar_cons(double mu, double rho, double s, double y1, double d) { return (mu - rho * s) + y1 * d; }
+__device__ __forceinline__ void xbar_hx(double y, const double *S, int n_hh, double *o) {
+    o[0] += y * (S[1] + S[4]);
+    o[1] += y * S[2];
+    if (n_hh > 2) o[2] += y * S[3];
+}
 
 }  // namespace hank

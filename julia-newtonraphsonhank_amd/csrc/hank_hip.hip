@@ -2705,44 +2705,7 @@ static int granular_backward(hank_ctx *ctx, const double *value_next, const doub
     return HANK_OK;
 }
 
-// ---- n_het heterogeneous outputs ---------------------------------------------------------------------------------------------
-// ForwardIteration aggregates EVERY heterogeneous variable with the same D_t: agg_j[t] = dot(vec(policy_j[t]), D_t)
-// (ForwardIteration.jl:303-307; BackwardIteration.jl:99-112 keeps one policy sequence per variable). Output 0 is the policy variable
-// of the endogenous dimension (the savings a', KD / A). Output 1 is consumption, the budget residual c = (1+r_t) a + w_t z_e + tr_t
-// - a' (KrusellSmith.jl:80): its aggregate is affine in what the sweeps already reduce,
-//     C_t  = (1+r_t) AD_t + w_t ZD_t + tr_t MD_t - KD_t,      AD_t = sum a D_t (the grid-weighted aggregate), ZD_t = sum z_e D_t, MD_t = sum D_t
-//     dC_t = dr_t AD_t + dw_t ZD_t + dtr_t MD_t + (1+r_t) dAD_t - dKD_t      (ZD_t, MD_t carry no partials: see hank_set_boundary; under a dD_0 seed of hank_jvp_boundary they do, and k_bnd_cons adds them behind this kernel)
-// agg (P, 2) and dagg (P, 2 N) as the sweeps leave them -> out_agg (P, n_het), out_dagg (P, n_het, N) column-major. hxS: the
-// record's sums [t][SX][HX_NS] (SX: the outputs the record holds); hxT: the call's in-period sums [n][t][NX].
-__global__ void k_het_outputs(int P, int n_hh, int n_het, int SX, int N, const double *__restrict__ xhh, const double *__restrict__ dxhh,
-                              const double *__restrict__ agg, const double *__restrict__ dagg, const double *__restrict__ zd,
-                              const double *__restrict__ hxS, const double *__restrict__ hxT,
-                              double *__restrict__ out_agg, double *__restrict__ out_dagg) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)P * (N + 1)) return;
-    const int t = (int)(idx % P), n = (int)(idx / P) - 1;
-    const int NX = n_het > 2 ? n_het - 2 : 0;      // outputs 2, 3 (Value, UCE): hank_hetx.h
-    const double r = xhh[n_hh * t], w = xhh[n_hh * t + 1], tr = n_hh > 2 ? xhh[n_hh * t + 2] : 0.0;
-    const double KD = agg[t], AD = agg[P + t], ZD = zd[t], MD = zd[P + t];
-    if (n < 0) {
-        if (!out_agg) return;
-        out_agg[t] = KD;
-        if (n_het > 1) out_agg[P + t] = ((1.0 + r) * AD + w * ZD + tr * MD) - KD;
-        for (int jx = 0; jx < NX; jx++) out_agg[(size_t)(2 + jx) * P + t] = hxS[((size_t)t * SX + jx) * HX_NS];
-        return;
-    }
-    if (!out_dagg) return;
-    const double dKD = dagg[(size_t)n * P + t], dAD = dagg[((size_t)N + n) * P + t];
-    const double *dx = dxhh + ((size_t)n * P + t) * n_hh;
-    const double dtr = n_hh > 2 ? dx[2] : 0.0;
-    out_dagg[((size_t)n * n_het) * P + t] = dKD;
-    if (n_het > 1) out_dagg[((size_t)n * n_het + 1) * P + t] = (dx[0] * AD + dx[1] * ZD + dtr * MD + (1.0 + r) * dAD) - dKD;
-    for (int jx = 0; jx < NX; jx++) {
-        const double *S = hxS + ((size_t)t * SX + jx) * HX_NS;      // Y, Sa, Sz, S1, Sr
-        out_dagg[((size_t)n * n_het + 2 + jx) * P + t] = hxT[((size_t)n * P + t) * NX + jx] + dx[0] * (S[1] + S[4]) + dx[1] * S[2] + dtr * S[3];
-    }
-}
-
+// ---- n_het heterogeneous outputs (k_het_outputs and what it assembles: hank_hetx.h) --------------------------------------------
 // outputs 2 .. n_het-1: for N > 0 the in-period sums of every direction (T) from one forward tangent recurrence over the exported
 // policy partials (hank_hetx.h) and the record's f, f_c (ensure_hx_record, which also holds the direction-independent sums). The
 // direction-dependent buffers live in the context (hx_slab: one allocation, grown when a wider batch asks, reused in stream

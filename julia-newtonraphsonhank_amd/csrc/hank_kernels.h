@@ -22,15 +22,7 @@ namespace hank {
 
 constexpr int RBP = 32;        // rows (wealth points) per block in the primal kernels
 
-enum { ERR_KNOTS = 3, ERR_DOMAIN = 4, ERR_NONMONO = 6 };
-
-__device__ inline void set_err(int *err, int code, int t, int e, int j) {
-    if (atomicCAS(&err[0], 0, code) == 0) {
-        err[1] = t;
-        err[2] = e;
-        err[3] = j;
-    }
-}
+// (ERR_KNOTS, ERR_DOMAIN, ERR_NONMONO, set_err: hank_device.h)
 
 // CRRA (here and in pow_crra, diet_kc, diet_v, egm_Y, egm_Y_finish): 0 = gamma and the record diet are what the context holds,
 // decided where they are used; 1 = an instance compiled for gamma = 2 with the record diet on (hank_xspec.h chooses it): the
@@ -411,76 +403,14 @@ __global__ void k_egm_step(Consts c, Record R, const double *xhh, int t, int *er
     egm_step_body(c, R, xhh, t, err, blockIdx.x, sh);
 }
 
-// ---- Young lottery for every (period, column) at once (ForwardIteration.jl:37-78) ------------
-// one block per column; builds lo / lw / ig and the segment offsets that turn the 2-nnz-per-column
-// scatter into a deterministic gather (the policy is monotone in wealth):
-//   clo      = number of sources clamped at the FIRST grid point (policy <= grid[1], :54-58): a
-//              prefix [0, clo) of the column, all mass to row 0 with weight one and no weight
-//              tangent — the borrowing-constraint mass point, summed separately (it is long);
-//   start[r] = max(clo, first source j with lo_j >= r): target row r receives w_j from the sources
-//              in [start[r-1], start[r]) and 1-w_j from those in [start[r], start[r+1]).
+// ---- Young lottery for every (period, column) at once: lottery_body (hank_device.h), one block per column -------------------
+// dynamic LDS: 2 n_a + 2 ints
 __global__ void k_lottery(Consts c, Record R, int ncols, int *err, int write_seg, int use_ib) {
     extern __shared__ int shlo[];
     __shared__ int sh_clo;
     const int col = blockIdx.x;
     if (col >= ncols) return;
-    const int t = col / c.n_e, e = col % c.n_e;
-    const size_t base = (size_t)col * c.n_a;  // == t*G + e*n_a
-    const int n = c.n_a;
-    if (threadIdx.x == 0) sh_clo = 0;
-    __syncthreads();
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const double p = R.pol[base + j];
-        int lo = -1, hi = n;  // grid[lo] < p <= grid[hi]  (searchsortedfirst, :52)
-        if (use_ib) {
-            // the policy is the interpolation's convex combination of grid[ib] and grid[ib + 1] (egm_Y): its lottery bracket is the
-            // interpolation's unless it sits on a grid point or was moved by the borrowing constraint — a probe of that bracket and
-            // of the one below replaces the 11 dependent loads of the bisection (which still decides whatever the probe does not)
-            const int g0 = min(max(R.ib[base + j], 0), n - 2);
-            const double a0 = c.a[g0], a1 = c.a[g0 + 1];
-            if (a0 < p && p <= a1) { lo = g0; hi = g0 + 1; }
-            else if (g0 > 0 && p <= a0 && c.a[g0 - 1] < p) { lo = g0 - 1; hi = g0; }
-        }
-        while (hi - lo > 1) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (c.a[mid] < p) lo = mid; else hi = mid;
-        }
-        int l;
-        double w, ig;
-        if (hi == 0) {            // m == 1: all mass on the first point (:54-58)
-            l = 0; w = 0.0; ig = 0.0;
-            atomicMax(&sh_clo, j + 1);
-        } else if (hi >= n) {     // m > n_a: all mass on the last point (:59-63)
-            l = n - 2; w = 1.0; ig = 0.0;
-        } else {                  // interior (:64-73)
-            l = hi - 1;
-            const double gap = c.a[hi] - c.a[l];
-            w = (p - c.a[l]) / gap;
-            ig = 1.0 / gap;
-        }
-        R.lo[base + j] = l; R.lw[base + j] = w; R.ig[base + j] = ig;
-        shlo[j] = (hi == 0) ? -1 : l;   // clamped-low sources sort before every interior bracket
-    }
-    __syncthreads();
-    const int clo = sh_clo;
-    if (threadIdx.x == 0) R.clo[col] = clo;
-    int *st = R.start + (size_t)col * (n + 1);
-    int *shst = shlo + n;          // segment offsets staged in LDS (second half of the dynamic LDS)
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const int prev = j ? shlo[j - 1] : -1, cur = shlo[j];
-        if (cur < prev) set_err(err, ERR_NONMONO, t, e, j);
-        for (int r = (prev < 0 ? 0 : prev + 1); r <= cur; r++) shst[r] = j;   // j >= clo whenever cur >= 0
-        if (j == n - 1)
-            for (int r = (cur < 0 ? 0 : cur + 1); r <= n; r++) shst[r] = n;
-    }
-    __syncthreads();
-    for (int r = threadIdx.x; r <= n; r += blockDim.x) st[r] = shst[r];
-    // per target row: its three segment bounds in one 16-byte record — what the launch family's gather reads (and k_xstat, and
-    // k_fn_impulse); a third of this kernel's bytes, and the persistent Dual pass reads none of them: written there on demand
-    // (write_seg = 0, then k_seg_build before the first reader)
-    if (write_seg)
-        for (int r = threadIdx.x; r < n; r += blockDim.x)
-            R.seg[base + r] = make_int4(r > 0 ? shst[r - 1] : shst[r], shst[r], shst[r + 1], 0);
+    lottery_body(c, R, col, err, write_seg, use_ib, shlo, &sh_clo);
 }
 // the same records from the segment offsets k_lottery left (one block per column)
 __global__ void k_seg_build(Consts c, Record R, int ncols) {

@@ -1,6 +1,6 @@
 // hank_scen.h — the scenario batch of hank_primal_batch: K independent input paths x_k through ONE chain of launches, with
 // gridDim.y = K. Scenario k is the launch family's hank_primal at x_k: the kernels here call the same bodies (egm_X, egm_step_body,
-// dist_step_body — the only places the household problem is written; the lottery is restated, see k_scen_lottery) on scenario k's
+// lottery_body, dist_step_body — the only places the household problem is written) on scenario k's
 // record, scenario k's inputs and scenario k's error word, so its policy and its aggregate hold the bits of k_egm_X / k_egm_step /
 // k_lottery / k_dist_step.
 //
@@ -56,63 +56,13 @@ __global__ void k_scen_egm_step(Consts c, ScenArgs a, int t) {
     egm_step_body(c, scen_record(a.R0, a.stride * k), scen_xhh(c, a, k), t, a.err + 4 * k, blockIdx.x, sh);
 }
 
-// grid (P n_e, K), block 256, LDS 2 n_a + 2 ints: k_lottery with write_seg = 0 and use_ib = 1. RESTATED, not shared: factoring a
-// lottery_body out of k_lottery changed that kernel's instructions (profiles/primal_batch_isa_diff.txt), and the existing kernels
-// stay as they are — k_ss_lam is the precedent. The arithmetic below is k_lottery's, line for line (ForwardIteration.jl:37-78): the
-// same probe of the interpolation's bracket, the same bisection, the same weights, the same segment offsets.
+// grid (P n_e, K), block 256, LDS 2 n_a + 2 ints: k_lottery's body with write_seg = 0 and use_ib = 1
 __global__ void k_scen_lottery(Consts c, ScenArgs a, int ncols) {
     extern __shared__ int shlo[];
     __shared__ int sh_clo;
     const int col = blockIdx.x, k = blockIdx.y;
     if (col >= ncols) return;
-    const Record R = scen_record(a.R0, a.stride * k);
-    int *err = a.err + 4 * k;
-    const int t = col / c.n_e, e = col % c.n_e;
-    const size_t base = (size_t)col * c.n_a;
-    const int n = c.n_a;
-    if (threadIdx.x == 0) sh_clo = 0;
-    __syncthreads();
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const double p = R.pol[base + j];
-        int lo = -1, hi = n;  // grid[lo] < p <= grid[hi]
-        const int g0 = min(max(R.ib[base + j], 0), n - 2);
-        const double a0 = c.a[g0], a1 = c.a[g0 + 1];
-        if (a0 < p && p <= a1) { lo = g0; hi = g0 + 1; }
-        else if (g0 > 0 && p <= a0 && c.a[g0 - 1] < p) { lo = g0 - 1; hi = g0; }
-        while (hi - lo > 1) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (c.a[mid] < p) lo = mid; else hi = mid;
-        }
-        int l;
-        double w, ig;
-        if (hi == 0) {
-            l = 0; w = 0.0; ig = 0.0;
-            atomicMax(&sh_clo, j + 1);
-        } else if (hi >= n) {
-            l = n - 2; w = 1.0; ig = 0.0;
-        } else {
-            l = hi - 1;
-            const double gap = c.a[hi] - c.a[l];
-            w = (p - c.a[l]) / gap;
-            ig = 1.0 / gap;
-        }
-        R.lo[base + j] = l; R.lw[base + j] = w; R.ig[base + j] = ig;
-        shlo[j] = (hi == 0) ? -1 : l;
-    }
-    __syncthreads();
-    const int clo = sh_clo;
-    if (threadIdx.x == 0) R.clo[col] = clo;
-    int *st = R.start + (size_t)col * (n + 1);
-    int *shst = shlo + n;
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const int prev = j ? shlo[j - 1] : -1, cur = shlo[j];
-        if (cur < prev) set_err(err, ERR_NONMONO, t, e, j);
-        for (int r = (prev < 0 ? 0 : prev + 1); r <= cur; r++) shst[r] = j;
-        if (j == n - 1)
-            for (int r = (cur < 0 ? 0 : cur + 1); r <= n; r++) shst[r] = n;
-    }
-    __syncthreads();
-    for (int r = threadIdx.x; r <= n; r += blockDim.x) st[r] = shst[r];
+    lottery_body(c, scen_record(a.R0, a.stride * k), col, a.err + 4 * k, 0, 1, shlo, &sh_clo);
 }
 
 // grid (nbp, K), block RBP n_e, LDS primal_lds: k_dist_step of period t with aggpart [k][t][block][2]. D0: the initial distribution
@@ -148,7 +98,7 @@ __global__ void k_scen_dist_step(Consts c, ScenArgs a, const double *D0, int t, 
     }
 }
 
-// outputs 0 .. n_het-1 of every scenario, (P, n_het, K) column-major, with the arithmetic of the value half of k_het_outputs:
+// outputs 0 .. n_het-1 of every scenario, (P, n_het, K) column-major, the value half of k_het_outputs (out_cons):
 // agg [k][t][2] and hx [k][t][NX] as k_reduce_parts leaves them over K P rows; zd does not depend on the scenario
 __global__ void k_scen_outputs(int P, int n_hh, int n_het, int K, const double *__restrict__ xhh, const double *__restrict__ agg,
                                const double *__restrict__ zd, const double *__restrict__ hx, double *__restrict__ out) {
@@ -161,7 +111,7 @@ __global__ void k_scen_outputs(int P, int n_hh, int n_het, int K, const double *
     const double KD = agg[(size_t)idx * 2], AD = agg[(size_t)idx * 2 + 1], ZD = zd[t], MD = zd[P + t];
     double *o = out + (size_t)k * n_het * P + t;
     o[0] = KD;
-    if (n_het > 1) o[P] = ((1.0 + r) * AD + w * ZD + tr * MD) - KD;
+    if (n_het > 1) o[P] = out_cons(r, w, tr, AD, ZD, MD, KD);
     for (int jx = 0; jx < NX; jx++) o[(size_t)(2 + jx) * P] = hx[(size_t)idx * NX + jx];
 }
 

@@ -9,8 +9,8 @@
 //
 //   JVP   dV  <- B_V dV + B_x dx                  k_ss_back: tan_back_body (k_tan_back's body), Y half of period 1, X half of period 0
 //         dD  <- Lambda dD + (dLambda da') D      k_ss_fwd:  tan_fwd_body (k_tan_fwd / k_tan_fwd_hx's body) at period 0
-//   VJP   e   <- Lambda' (e - (D'e) 1), lam += e  k_ss_lam:  the step of k_adj_dist at period 0, no output cotangent inside
-//         nu  <- B_V' nu + (P_V' pbar + Vbar)     k_ss_nu:   the step of k_adj_egm at period 0, with a constant source
+//   VJP   e   <- Lambda' (e - (D'e) 1), lam += e  k_ss_lam:  adj_dist_body (k_adj_dist's body) at period 0, no output cotangent inside
+//         nu  <- B_V' nu + (P_V' pbar + Vbar)     k_ss_nu:   adj_egm_body (k_adj_egm's body) at period 0, with a constant source
 //
 // The constant sources of the two JVP loops are the step bodies' own (the input tangents and the policy tangent are fed again every
 // step). What the loops add lives in each step's epilogue, not in a second pass over the state: the per-column increment norm and
@@ -245,12 +245,11 @@ __global__ void k_ss_jvp_out(int P, int n_hh, int n_het, int N, int nbf, const d
     const double *dx = dxhh + (size_t)n_hh * n;
     const double dtr = n_hh > 2 ? dx[2] : 0.0;
     out[(size_t)n_het * n] = dKD;
-    if (n_het > 1) out[(size_t)n_het * n + 1] = (dx[0] * AD + dx[1] * ZD + dtr * MD + (1.0 + r) * dAD) - dKD;
+    if (n_het > 1) out[(size_t)n_het * n + 1] = out_dcons(r, dx[0], dx[1], dtr, AD, ZD, MD, dAD, dKD);
     for (int jx = 0; jx < NX; jx++) {
         double T = 0.0;
         for (int b = 0; b < nbf; b++) T += hxparts[((size_t)b * NX + jx) * N + n];
-        const double *S = hxS + (size_t)jx * HX_NS;      // period 0: Y, Sa, Sz, S1, Sr
-        out[(size_t)n_het * n + 2 + jx] = T + dx[0] * (S[1] + S[4]) + dx[1] * S[2] + dtr * S[3];
+        out[(size_t)n_het * n + 2 + jx] = out_dhx(T, dx[0], dx[1], dtr, hxS + (size_t)jx * HX_NS);      // (the sums of period 0)
     }
 }
 
@@ -330,9 +329,9 @@ __device__ __forceinline__ void ss_adj_norms(VT inc, VT sc, VT sum, const AdjGeo
     }
 }
 
-// One step e <- Lambda' e with lam += e (PB = false), or the policy cotangent from the converged lam (PB = true): the arithmetic of
-// k_adj_dist at period 0 — a block owns the target rows [r0, r1), mixes them with Pi through the LDS tile (U) and serves the sources
-// the recorded lottery sends to them plus its share of the clamped prefix; every source row is written by exactly one block.
+// One step e <- Lambda' e with lam += e (PB = false), or the policy cotangent from the converged lam (PB = true):
+// adj_dist_body at period 0 with eIn in the tile — a block owns the target rows [r0, r1) and serves the sources the recorded lottery
+// sends to them plus its share of the clamped prefix; every source row is written by exactly one block.
 //   PB = false: eOut[j] = (1-w_j) U[lo_j] + w_j U[lo_j+1] - cen (U[0] - cen for a clamped source); lam[j] += eOut[j];
 //               cen [MV]: D_ss'eIn of the last check — Lambda'(e - c 1) = Lambda'e - c 1, so the centring of the input is taken on
 //               the output: a D_ss that is stationary only to the accuracy of the caller's steady state leaves a constant in e that
@@ -348,106 +347,46 @@ k_ss_lam(Consts c, Record R, AdjGeom g, const VT *__restrict__ eIn, VT *__restri
          const SsCtl *__restrict__ ctl, const VT *__restrict__ cen, const VT *__restrict__ yb, int NX, const double *__restrict__ hxfc, size_t PG, VT *__restrict__ pbar) {
     extern __shared__ __attribute__((aligned(16))) double adj_sh[];
     if (!PB && ctl->stop) return;
-    const int NS = g.R + 2, n = c.n_a, ne = c.n_e;
-    VT *tile = reinterpret_cast<VT *>(adj_sh);
-    double *Pish = adj_sh + (size_t)ne * NS * g.NC * (sizeof(VT) / sizeof(double));
-    const int lane = threadIdx.x & 63, e = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nl = lane & (g.NC - 1), rl = lane >> g.lgNC, RB = 64 >> g.lgNC;
-    const int m = blockIdx.y * g.NC + nl;
-    const bool mok = m < g.MV;
-    const size_t MV = g.MV;
-    const int r0 = blockIdx.x * g.R, r1 = min(r0 + g.R, n);
-    for (int k = threadIdx.x; k < ne * ne; k += 64 * ne) Pish[k] = c.Pi[k];
-    const size_t colb = (size_t)e * n;      // (period 0, column e) of the record
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB;
-        if (slot < NS) {
-            const int row = slot == g.R + 1 ? 0 : r0 + slot;
-            VT v;
-            vzero(v);
-            if (mok && row <= r1 && row < n) v = eIn[((size_t)e * n + row) * MV + m];
-            tile[((size_t)e * NS + slot) * g.NC + nl] = v;
-        }
-    }
-    __syncthreads();
-    VT U[ADJ_KS];
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB;
-        vzero(U[k]);
-        if (slot < NS)
-            for (int e2 = 0; e2 < ne; e2++) U[k] = vadd(U[k], vmul(Pish[e + ne * e2], tile[((size_t)e2 * NS + slot) * g.NC + nl]));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB;
-        if (slot < NS) tile[((size_t)e * NS + slot) * g.NC + nl] = U[k];
-    }
-    __syncthreads();
-    VT inc, sc, dsum;
-    vzero(inc); vzero(sc); vzero(dsum);
-    if (mok) {
-        VT cm;
-        vzero(cm);
-        if (!PB) cm = cen[m];
-        const VT *Ue = tile + (size_t)e * NS * g.NC + nl;
-        const double *Dprev = R.Dseq + colb, *Dnext = R.Dseq + colb + c.G;
+    const AdjLane L = adj_lane(g);
+    const int n = c.n_a, m = L.m;
+    const size_t MV = g.MV, colb = (size_t)L.e * n;      // (period 0, column e) of the record
+    const double *Dprev = R.Dseq + colb, *Dnext = R.Dseq + colb + c.G;
+    const auto load = [&](int row) __attribute__((always_inline)) { return eIn[(colb + row) * MV + m]; };
+    if constexpr (PB) {
         VT yd, yx[2];
-        vzero(yd); vzero(yx[0]); vzero(yx[1]);
-        if (PB) {
+        const auto begin = [&]() __attribute__((always_inline)) {
+            vzero(yx[0]); vzero(yx[1]);
             yd = vsub(yb[m], yb[MV + m]);
 #pragma unroll
             for (int o = 0; o < 2; o++)
                 if (o < NX) yx[o] = yb[(size_t)(2 + o) * MV + m];
-        }
-        const int *st = R.start + (size_t)e * (n + 1);
-        const int j0 = min(max(st[r0], 0), n), j1 = min(max(st[r1], 0), n);
-        for (int j = j0 + rl; j < j1; j += RB) {
-            const int sl = min(max(R.lo[colb + j] - r0, 0), g.R - 1);
-            const VT u0 = Ue[(size_t)sl * g.NC], u1 = Ue[(size_t)(sl + 1) * g.NC];
-            const size_t idx = (colb + j) * MV + m;
-            if (PB) {
-                const double gD = R.ig[colb + j] * Dprev[j], Dn = Dnext[j];
-                VT ye = yd;
+        };
+        adj_dist_body<VT>(c, R, g, L, 0, adj_sh, load, begin, [&](int j, VT u0, VT u1, bool clamped) __attribute__((always_inline)) {
+            VT ye = yd;
 #pragma unroll
-                for (int o = 0; o < 2; o++)
-                    if (o < NX) ye = vsub(ye, vmul(hxfc[o * PG + colb + j], yx[o]));
-                pbar[idx] = vadd(vmul(Dn, ye), vmul(gD, vsub(u1, u0)));
-            } else {
-                const double wj = R.lw[colb + j];
-                const VT v = vsub(vadd(vmul(1.0 - wj, u0), vmul(wj, u1)), cm);
-                const VT l = vadd(lam[idx], v);
-                eOut[idx] = v;
-                lam[idx] = l;
-                inc = ss_max(inc, ss_abs(v)); sc = ss_max(sc, ss_abs(l)); dsum = vadd(dsum, vmul(Dprev[j], v));
-            }
-        }
-        const int clo = min(max(R.clo[e], 0), n);
-        const int c0 = (int)(((long long)clo * blockIdx.x) / gridDim.x), c1 = (int)(((long long)clo * (blockIdx.x + 1)) / gridDim.x);
-        const VT U0 = Ue[(size_t)(g.R + 1) * g.NC];
-        for (int j = c0 + rl; j < c1; j += RB) {
+            for (int o = 0; o < 2; o++)
+                if (o < NX) ye = vsub(ye, vmul(hxfc[o * PG + colb + j], yx[o]));
+            pbar[(colb + j) * MV + m] = clamped ? vmul(Dnext[j], ye) : vadd(vmul(Dnext[j], ye), vmul(R.ig[colb + j] * Dprev[j], vsub(u1, u0)));
+        });
+    } else {
+        VT inc, sc, dsum, cm;
+        vzero(inc); vzero(sc); vzero(dsum);
+        const auto begin = [&]() __attribute__((always_inline)) { cm = cen[m]; };
+        adj_dist_body<VT>(c, R, g, L, 0, adj_sh, load, begin, [&](int j, VT u0, VT u1, bool clamped) __attribute__((always_inline)) {
             const size_t idx = (colb + j) * MV + m;
-            if (PB) {
-                VT ye = yd;
-#pragma unroll
-                for (int o = 0; o < 2; o++)
-                    if (o < NX) ye = vsub(ye, vmul(hxfc[o * PG + colb + j], yx[o]));
-                pbar[idx] = vmul(Dnext[j], ye);
-            } else {
-                const VT v = vsub(U0, cm);
-                const VT l = vadd(lam[idx], v);
-                eOut[idx] = v;
-                lam[idx] = l;
-                inc = ss_max(inc, ss_abs(v)); sc = ss_max(sc, ss_abs(l)); dsum = vadd(dsum, vmul(Dprev[j], v));
-            }
-        }
+            double wj = 0.0;
+            if (!clamped) wj = R.lw[colb + j];
+            const VT v = vsub(clamped ? u0 : vadd(vmul(1.0 - wj, u0), vmul(wj, u1)), cm);
+            const VT l = vadd(lam[idx], v);
+            eOut[idx] = v;
+            lam[idx] = l;
+            inc = ss_max(inc, ss_abs(v)); sc = ss_max(sc, ss_abs(l)); dsum = vadd(dsum, vmul(Dprev[j], v));
+        });
+        ss_adj_norms<VT, 3>(inc, sc, dsum, g, c.n_e, L.e, L.nl, L.rl, m, parts);
     }
-    if (!PB) ss_adj_norms<VT, 3>(inc, sc, dsum, g, ne, e, nl, rl, m, parts);
 }
 
-// One step nu <- B_V' nu + (P_V' pbar + Vbar): the arithmetic of k_adj_egm at period 0 (neither first nor last) with the caller's
+// One step nu <- B_V' nu + (P_V' pbar + Vbar): adj_egm_body at period 0 (neither first nor last) with the caller's
 // cotangent of V_ss added to every new nu — nu is the TOTAL cotangent of dV, so gbar = pbar - v nu and the inputs' sums read it whole.
 // partS, partM [block][3][MV]: sum sbar (s, z_e, 1) and sum nu (u + v a, v z_e, v) of the step, BOTH at the step's input nu: their
 // reduction is xbar = P_x' (pbar - v nu) + M' nu = P_x' pbar + B_x' nu (Sweep B's, taken once). The two nu terms nearly cancel (the
@@ -460,85 +399,20 @@ k_ss_nu(Consts c, Record R, AdjGeom g, const int *__restrict__ sb, const VT *__r
         const VT *__restrict__ vbar, VT *__restrict__ partS, VT *__restrict__ partM, VT *__restrict__ parts, const SsCtl *__restrict__ ctl) {
     extern __shared__ __attribute__((aligned(16))) double adj_sh[];
     if (ctl->stop) return;
-    const int n = c.n_a, ne = c.n_e;
-    const int lane = threadIdx.x & 63, e = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nl = lane & (g.NC - 1), rl = lane >> g.lgNC, RB = 64 >> g.lgNC, NS = g.R;
-    VT *tile = reinterpret_cast<VT *>(adj_sh);
-    double *Pish = adj_sh + (size_t)ne * NS * g.NC * (sizeof(VT) / sizeof(double));
-    VT *red = reinterpret_cast<VT *>(Pish + ((ne * ne + 1) & ~1));
-    const int m = blockIdx.y * g.NC + nl;
-    const bool mok = m < g.MV;
-    const size_t MV = g.MV;
-    const int i0 = blockIdx.x * g.R;
-    for (int k = threadIdx.x; k < ne * ne; k += 64 * ne) Pish[k] = c.Pi[k];
-    const size_t colb = (size_t)e * n;
-    const int *sbc = sb + (size_t)e * (n + 1);
-    const double ze = c.z[e];
-    VT sum[6], inc, sc;
-#pragma unroll
-    for (int q = 0; q < 6; q++) vzero(sum[q]);
+    const AdjLane L = adj_lane(g);
+    const size_t MV = g.MV, colb = (size_t)L.e * c.n_a;
+    VT inc, sc;
     vzero(inc); vzero(sc);
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB, i = i0 + slot;
-        VT sbar;
-        vzero(sbar);
-        if (mok && slot < g.R && i < n) {
-            const int b1 = min(max(sbc[i], 0), n), b0 = i > 0 ? min(max(sbc[i - 1], 0), b1) : b1, b2 = min(max(sbc[i + 1], b1), n);
-            const VT *pb = pbar + colb * MV + m, *mu = nuIn + colb * MV + m;
-            for (int a = b0; a < b2; a += 2) {
-                const bool two = a + 1 < b2;
-                const int a1 = two ? a + 1 : a;
-                const double w0 = a < b1 ? R.B[colb + a] : R.A[colb + a], w1 = a1 < b1 ? R.B[colb + a1] : R.A[colb + a1];
-                const double v0 = R.v[colb + a], v1 = R.v[colb + a1];
-                const VT g0 = vsub(pb[(size_t)a * MV], vmul(v0, mu[(size_t)a * MV])), g1 = vsub(pb[(size_t)a1 * MV], vmul(v1, mu[(size_t)a1 * MV]));
-                sbar = vadd(sbar, vmul(w0, g0));
-                if (two) sbar = vadd(sbar, vmul(w1, g1));
-            }
-            sum[0] = vadd(sum[0], vmul(R.s[colb + i], sbar));
-            sum[1] = vadd(sum[1], vmul(ze, sbar));
-            sum[2] = vadd(sum[2], sbar);
-            sbar = vmul(R.kc[colb + i], sbar);
-        }
-        if (slot < g.R) tile[((size_t)e * NS + slot) * g.NC + nl] = sbar;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < ADJ_KS; k++) {
-        const int slot = rl + k * RB, i = i0 + slot;
-        if (mok && slot < g.R && i < n) {
-            VT mn;
-            vzero(mn);
-            for (int e1 = 0; e1 < ne; e1++) mn = vadd(mn, vmul(Pish[e1 + ne * e], tile[((size_t)e1 * NS + slot) * g.NC + nl]));
-            const size_t idx = (colb + i) * MV + m;
-            if (vbar) mn = vadd(mn, vbar[idx]);
-            const VT old = nuIn[idx];
-            inc = ss_max(inc, ss_abs(vsub(mn, old)));
-            sc = ss_max(sc, ss_abs(mn));
-            nuOut[idx] = mn;
-            const double u1 = R.u[colb + i], v1 = R.v[colb + i];
-            sum[3] = vadd(sum[3], vmul(u1 + v1 * c.a[i], old));      // (the nu sbar has read: see above)
-            sum[4] = vadd(sum[4], vmul(v1 * ze, old));
-            sum[5] = vadd(sum[5], vmul(v1, old));
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 6; q++) {
-        const VT v = adj_rows_sum(sum[q], g.NC);
-        if (rl == 0) red[((size_t)e * 6 + q) * g.NC + nl] = v;
-    }
-    __syncthreads();
-    for (int q = e; q < 6; q += ne) {
-        VT v;
-        vzero(v);
-        for (int e1 = rl; e1 < ne; e1 += RB) v = vadd(v, red[((size_t)e1 * 6 + q) * g.NC + nl]);
-        v = adj_rows_sum(v, g.NC);
-        if (rl == 0 && mok) {
-            if (q < 3) partS[(((size_t)blockIdx.x) * 3 + q) * MV + m] = v;
-            else partM[(((size_t)blockIdx.x) * 3 + (q - 3)) * MV + m] = v;
-        }
-    }
-    ss_adj_norms<VT, 2>(inc, sc, inc, g, ne, e, nl, rl, m, parts);
+    adj_egm_body<VT>(c, R, g, L, 0, 0, true, true, sb, nuIn, pbar, adj_sh, partS, partM, [&](int i, VT mn) __attribute__((always_inline)) {
+        const size_t idx = (colb + i) * MV + L.m;
+        if (vbar) mn = vadd(mn, vbar[idx]);
+        const VT old = nuIn[idx];
+        inc = ss_max(inc, ss_abs(vsub(mn, old)));
+        sc = ss_max(sc, ss_abs(mn));
+        nuOut[idx] = mn;
+        return old;      // (the sums weigh the nu sbar has read: see above)
+    });
+    ss_adj_norms<VT, 2>(inc, sc, inc, g, c.n_e, L.e, L.nl, L.rl, L.m, parts);
 }
 
 // xhh_bar (n_hh, M) column-major: the blocks' partials in block order (k_adj_out at one period), then the outputs' direct terms
@@ -552,12 +426,8 @@ __global__ void k_ss_xbar(int P, int n_hh, int M, int nb, int NX, const double *
     for (int b = 0; b < nb; b++)
         for (int q = 0; q < 3; q++) { s[q] += partS[((size_t)b * 3 + q) * M + m]; mu[q] += partM[((size_t)b * 3 + q) * M + m]; }
     const double rho = 1.0 / (1.0 + xhh[0]), y1 = yb[M + m];
-    double o[3] = {(mu[0] - rho * s[0]) + y1 * agg[P], (mu[1] - rho * s[1]) + y1 * zd[0], (mu[2] - rho * s[2]) + y1 * zd[P]};
-    for (int jx = 0; jx < NX; jx++) {
-        const double y = yb[(size_t)(2 + jx) * M + m];
-        const double *S = hxS + (size_t)jx * HX_NS;
-        o[0] += y * (S[1] + S[4]); o[1] += y * S[2]; o[2] += y * S[3];
-    }
+    double o[3] = {xbar_cons(mu[0], rho, s[0], y1, agg[P]), xbar_cons(mu[1], rho, s[1], y1, zd[0]), xbar_cons(mu[2], rho, s[2], y1, zd[P])};
+    for (int jx = 0; jx < NX; jx++) xbar_hx(yb[(size_t)(2 + jx) * M + m], hxS + (size_t)jx * HX_NS, n_hh, o);
     double *out = xhh_bar + (size_t)n_hh * m;
     out[0] = o[0]; out[1] = o[1];
     if (n_hh > 2) out[2] = o[2];
