@@ -12,7 +12,8 @@ The economies: Krusell-Smith 50x2 and 30x3 and the one-asset HANK with sticky wa
 (V, D) is a fixed point far below the tests' bounds — see `case`), and `clamp`: a Krusell-Smith household on a grid that is dense
 at the bottom, at prices where the borrowing constraint clamps more source rows of the low-income column than one row block of
 hank_vjp's widest geometry owns. Five more (NEW_NAMES):
-Krusell-Smith 40x16 and 40x5, and Krusell-Smith 40x3 at gamma = 1, 0.5 and 3, each at its own host steady state.
+Krusell-Smith 40x16 and 40x5, and Krusell-Smith 40x3 at gamma = 1, 0.5 and 3, each at its own host steady state. `case` also
+builds Krusell-Smith 64x4 (G = 256) for the fake-news module (tests/fake_news_refs.py), which is in none of the NAMES.
 
 The module ends with the four fixed-point loops as plain numpy iterations on these operators under the device's stopping rules
 (`jvp_loops`, `vjp_loops`): the step counts the GPU tests compare the device's `iters` with."""
@@ -155,7 +156,8 @@ _CASES = {}
 OLD_NAMES = ("ks50x2", "ks30x3", "hank30x3", "clamp")
 NEW_NAMES = ("ks40x16", "ks40x5", "gamma1", "gamma0.5", "gamma3")
 NAMES = OLD_NAMES + NEW_NAMES
-_KS_SHAPE = {"ks50x2": (50, 2, 100), "ks30x3": (30, 3, 40), "ks40x16": (40, 16, 40), "ks40x5": (40, 5, 40)}
+_KS_SHAPE = {"ks50x2": (50, 2, 100), "ks30x3": (30, 3, 40), "ks40x16": (40, 16, 40), "ks40x5": (40, 5, 40),
+             "ks64x4": (64, 4, 40)}      # G = 256, for tests/test_gpu_fake_news_dense.py alone: not in NAMES
 _GAMMA = {"gamma1": 1.0, "gamma0.5": 0.5, "gamma3": 3.0}
 _GAMMA_ECON = {}
 

@@ -121,3 +121,36 @@ def test_ss_diff_widths_reach_the_geometries_they_name(ask):
     R, RB = SS_VJP_TABLE[7][3], SS_VJP_TABLE[7][2]
     assert R + 2 == 10 and -(-(R + 2) // RB) == 2                     # M = 7: NS = 10 slots, two trips of RB = 8
     assert 65 - SS_JVP_TABLE[65][1] == 1 and 130 // 2 - SS_JVP_TABLE[130][1] == 1 and 34 // 2 - SS_VJP_TABLE[34][1] == 1   # one live lane in the second block
+
+
+def test_fake_news_shapes_reach_what_they_name():
+    """tests/test_gpu_fake_news_dense.py's shapes against fake_news()'s launch arithmetic restated in fake_news_refs.geometry, and
+    that restatement against the source: if a tile, the K split or a block size moves, the GPU module cannot silently stop reaching
+    the edges its table names"""
+    import re
+    import fake_news_refs as R
+    for name, P in R.SHAPES:
+        R.check_shape(name, P)
+    # the claims of the table that are sentences rather than entries
+    g = R.geometry(90, 2, 3, 7)
+    assert g["slices"][5] == 10 and g["kchunk"] == 16 and not any(g["slices"][6:])          # slice 5: 10 of 16 k
+    g = R.geometry(380, 2, 3, 12)
+    assert g["slices"][11] == 16 + 12 and g["slices"][11] < g["kchunk"]                      # one full 16-chunk plus 12
+    g = R.geometry(640, 2, 3, 12)
+    assert g["slices"].count(48) == 13 and g["slices"][13] == 16 and g["slices"].count(0) == 2
+    g = R.geometry(256, 2, 3, 16)
+    assert set(g["slices"]) == {R.GEMM_KSTEP} and g["expect"] == (1, R.BLOCK)
+    assert R.geometry(100, 2, 3, 32)["gemm_n"][1] == R.GEMM_TILE and R.geometry(100, 2, 3, 32)["transpose_t"][1] == R.TRANSPOSE_TILE
+    assert R.geometry(90, 3, 4, 100)["gemm_m"] == (7, 400 - 6 * 64)
+    n_e = {n: e for n, (_, e, _, _) in R.ECONOMIES.items()}
+    assert n_e["ks40x16"] == 16 and n_e["ks40x5"] == 5 and max(n_e.values()) == 16           # k_fn_impulse keeps double mid[16]
+    # ... and the source
+    host, jac = (CSRC / "hank_hip.hip").read_text(), (CSRC / "hank_jacobian.h").read_text()
+    body = host[host.index("static int fake_news("):host.index("int hank_fake_news(")]
+    assert re.search(r"NP = P \* N, S = 16,", body) and R.FN_SLICES == 16
+    assert "const int kchunk = ((G + S - 1) / S + 15) / 16 * 16, MP = nh * P;" in body
+    assert "(G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256)" in body and "tile[32][33]" in jac
+    assert body.count("(NP + 63) / 64)") == 2 and "(MP + 63) / 64)" in body and "(nh + 63) / 64)" in body
+    assert "As[16][68], Bs[16][64]" in jac and "k0 += 16" in jac
+    assert "dim3((unsigned)c.n_a, (unsigned)((NP + 255) / 256)), dim3(256)" in body and "blockIdx.y * 256 + threadIdx.x" in jac
+    assert body.count("(G + 255) / 256)") == 2 and "double mid[16];" in jac
