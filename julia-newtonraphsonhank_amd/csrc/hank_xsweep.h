@@ -51,6 +51,18 @@
 #ifndef HANK_XADDR_BUF_FWD
 #define HANK_XADDR_BUF_FWD HANK_XADDR_BUF       // ... k_xfwd<D, true>'s alone
 #endif
+#ifndef HANK_XMIX_PEEL
+#define HANK_XMIX_PEEL 1           // xtile_mix: the first column by itself, the loop over the others holds the multiply-adds only (dev knob: 0 = the first-term select in every trip)
+#endif
+#ifndef HANK_XMIX_UNROLL
+#define HANK_XMIX_UNROLL 5         // ... columns per trip of that loop: n_e = 11 is two whole trips of five, no single-column trip left over (dev knob)
+#endif
+#ifndef HANK_XMIX_BATCH
+#define HANK_XMIX_BATCH 1          // ... a trip issues all its tile reads, then its multiply-adds (dev knob: 0 = `#pragma unroll`, the reads where the compiler's scheduler puts them)
+#endif
+#ifndef HANK_XFWD_ROWIDX
+#define HANK_XFWD_ROWIDX 1         // k_xfwd<D, true>, D > 0, on buffer descriptors: a unit's state-row index set with its record, the state loads unconditional (dev knob: 0 = computed behind the source poll, loads under `qon`)
+#endif
 #include "hank_kernels.h"
 #include "hank_xaddr.h"
 #include <type_traits>
@@ -475,18 +487,59 @@ __device__ __forceinline__ void xtile_store_n(double *t, const double *v) {    /
 template <int SL, int NS, bool FMA = false>
 __device__ __forceinline__ void xtile_mix(const double *tl, const double *P, int ps, int ne, double *out) {
     const int ks = 64 * SL;
-#pragma unroll 4
-    for (int k = 0; k < ne; k++) {
-        double v[SL];
+    auto rd = [&](int k, double *v) {                   // column k's slots of this lane
         if (SL == 1) v[0] = tl[(size_t)k * ks];
         else {
 #pragma unroll
             for (int q = 0; q < (NS + 1) / 2; q++) { const double2 d = reinterpret_cast<const double2 *>(tl + (size_t)k * ks)[q]; v[2 * q] = d.x; v[2 * q + 1] = d.y; }
         }
+    };
+    auto acc = [&](double p, const double *v) {
+#pragma unroll
+        for (int q = 0; q < NS; q++) out[q] = FMA ? __builtin_fma(p, v[q], out[q]) : out[q] + p * v[q];
+    };
+#if HANK_XMIX_PEEL
+    // the first column by itself: with `k == 0 ? p * v : fma(p, v, out)` in the loop the compiler keeps the test in every trip — a
+    // product and two selects per slot and column next to the multiply-add. The operands and their order are the same.
+    {
+        double v[SL];
+        rd(0, v);
+        const double p = P[0];
+#pragma unroll
+        for (int q = 0; q < NS; q++) out[q] = p * v[q];
+    }
+    int k = 1;
+#if HANK_XMIX_BATCH
+    // U columns per trip: every read of the trip is in flight before its first multiply-add (left to itself the scheduler does that
+    // at `unroll 4`; at 5 it reuses the registers and waits for the LDS three times a trip), then single columns
+    constexpr int U = HANK_XMIX_UNROLL;
+    for (; k + U <= ne; k += U) {
+        double v[U][SL], p[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) { rd(k + u, v[u]); p[u] = P[(k + u) * ps]; }
+        __builtin_amdgcn_sched_barrier(0);              // (nothing moves across: the reads stay in front)
+#pragma unroll
+        for (int u = 0; u < U; u++) acc(p[u], v[u]);
+    }
+#pragma unroll 1
+#else
+#pragma unroll HANK_XMIX_UNROLL
+#endif
+    for (; k < ne; k++) {
+        double v[SL];
+        rd(k, v);
+        acc(P[k * ps], v);
+    }
+#else
+#pragma unroll 4
+    for (int k = 0; k < ne; k++) {
+        double v[SL];
+        rd(k, v);
         const double p = P[k * ps];
 #pragma unroll
         for (int q = 0; q < NS; q++) out[q] = k == 0 ? p * v[q] : (FMA ? __builtin_fma(p, v[q], out[q]) : out[q] + p * v[q]);
     }
+#endif
 }
 
 // the same with the column of Pi held in registers (16 unrolled steps, the ones beyond n_e predicated off): no LDS read for
@@ -1503,6 +1556,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     int qlo[2];
     double qw[2], qg[2], qdn[2], qdp[2][DD], dd[2][SP];
     bool qon[2], qvl[2];
+    // ROWIDX (HANK_XFWD_ROWIDX, the descriptor path): a unit's state row within its column, set by load_rec — a period before the
+    // state is read, in the mixing phase's shadow — so that nothing but scalar setup stands between the barrier behind the source
+    // poll and the state loads. A lane that is off reads row 0 of the unit's column (in range; process_* gate on qon / doL / doH)
+    constexpr bool ROWIDX = XB && HANK_XFWD_ROWIDX != 0;
+    int qrow[2] = {0, 0};
     const int2 *const ubase = A.units + (size_t)cW * XUCAP;       // (the pointer path; XB: unit_ld)
     auto unit_ld = [&](int tu, int u) -> int2 {         // XB: a descriptor's address is wave-uniform — a scalar base and a 32-bit scalar index, no lane arithmetic
         return A.units[(unsigned)((tu * Sact + cW) * XUCAP + u)];
@@ -1527,6 +1585,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         const int j = real ? ja + i : (qvl[u] ? 0 : min(ja + max(cnt - 1, 0), na - 1));
         if constexpr (XB) {
             const int icb = t * G + ue * na;            // the unit's column in period t (elements; wave-uniform)
+            if constexpr (ROWIDX) qrow[u] = qvl[u] ? (i - cnt) * 64 + 63 : (real ? (j / XRW) * 64 + j % XRW : 0);
             qlo[u] = buf_ld32<0>(rrec, j * 4, (int)(A.ro.lo + (unsigned)icb * 4u));
             qw[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.lw + (unsigned)icb * 8u));
             qg[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.ig + (unsigned)icb * 8u));
@@ -1544,6 +1603,10 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #pragma unroll
         for (int k = 0; k < SP; k++) dd[u][k] = 0.0;
         const int i = i0 + lane, j = ja + i;
+        if constexpr (ROWIDX) {
+            rows.load_vs(qrow[u], hc * ihs + igx + ue * Sact * 64, dd[u]);        // unconditional: the compiler counts the loads in flight
+            return;
+        }
         if constexpr (XB) {
             const int rowi = qvl[u] ? (i - cnt) * 64 + 63 : (j / XRW) * 64 + j % XRW;       // within the unit's column
             if (qon[u]) rows.load_vs(rowi, hc * ihs + igx + ue * Sact * 64, dd[u]);
