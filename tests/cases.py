@@ -2,7 +2,8 @@
 (tests/test_vjp_host.py, tests/test_cases_host.py) share. Nothing here needs a GPU except `raw_block` / `block`, which create a
 device context, and section 4, which runs sweeps on one.
 
-0. the owners: `close` (the suite's only tolerance function), `raw_block` / `block` (a context under HANK_* variables, every
+0. the owners: `close` (the suite's tolerance function: a relative figure on the array's largest entry) and `within` (the entry-wise
+   one: every entry inside a running error bound of tests/ld_refs.py), `raw_block` / `block` (a context under HANK_* variables, every
    variable restored), `model_args` / `oracle_of` (a model's constructor arguments), `hank_economy` / `hank_x` (the one-asset HANK
    economy and its input path). The oracle's references are methods of oracle.oracle.Oracle: block, block_het, het_outputs, vfi;
 1. the references of hank_vjp[_het]: the CPU oracle's Jacobian from unit tangents (`oracle_jacobian`, `oracle_jacobian_het` /
@@ -17,7 +18,9 @@ device context, and section 4, which runs sweeps on one.
    several 63-row members and past row 128, every column or a whole column clamped, a clamp that vanishes after a clamped period
    and returns, more than 64 sources on one target row — measured by `forward_edges`, which restates k_xunits_fwd's cut;
 4. the forward sweeps' comparison (`sweeps`, `against_oracle_and_launches`, `expected_family`): both entry points at every
-   batch width against the oracle and a launch-schedule context, for a model or for raw constructor arguments."""
+   batch width against the oracle and a launch-schedule context, for a model or for raw constructor arguments;
+5. the entry-wise tests' exact inputs and their long double references (`entry_backward`, `entry_refs`, `entry_forward`,
+   `entry_forward_ref`, `push_distribution`), shared by tests/test_ld_refs_host.py and tests/test_gpu_entrywise.py."""
 import os
 
 import numpy as np
@@ -33,6 +36,30 @@ def close(a, b, rel=1e-10, ab=1e-12, what=""):
     err, scale = np.max(np.abs(a - b)), np.abs(b).max()
     print(f"{what}: max err {err:.3e} vs scale {scale:.3e} (bound {ab + rel * scale:.3e})")
     assert err <= ab + rel * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
+
+
+def within(a, ref, bound, what, skip=None):
+    """the entry-wise owner: |a - ref| <= bound at EVERY entry (ref and bound of tests/ld_refs.py: an extended-precision value and
+    the running error bound of the float64 kernel). `skip` (a's shape, or its leading axes): the entries whose bracket is ambiguous,
+    at most 1 % of the array. Prints max |a - ref| / bound, the share skipped and the worst entry before it asserts; a NaN anywhere
+    and a shape mismatch fail it. -> the largest ratio."""
+    a, ref, bound = np.atleast_1d(a), np.atleast_1d(ref), np.atleast_1d(np.asarray(bound, dtype=np.float64))
+    assert a.shape == ref.shape == bound.shape and a.size, (what, a.shape, ref.shape, bound.shape)
+    assert not (np.isnan(a).any() or np.isnan(ref).any() or np.isnan(bound).any()), f"{what}: NaN"
+    assert np.all(bound >= 0), what
+    skip = np.zeros(a.shape, dtype=bool) if skip is None else np.asarray(skip, dtype=bool)
+    assert skip.shape == a.shape[:skip.ndim], (what, skip.shape, a.shape)
+    skip = np.broadcast_to(skip.reshape(skip.shape + (1,) * (a.ndim - skip.ndim)), a.shape)
+    share = float(skip.mean())
+    err = np.abs(a - ref).astype(np.float64)                 # (the difference in the reference's precision)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(skip | (err == 0), 0.0, err / bound)      # (an error under a zero bound: inf)
+    k = tuple(int(q) for q in np.unravel_index(np.argmax(ratio), a.shape))
+    print(f"{what}: max err/bound {ratio.max():.3f} at {k} (a {float(a[k]):.17g}, ref {float(ref[k]):.17g}, bound {float(bound[k]):.3e}), "
+          f"skipped {100 * share:.2f} %")
+    assert share <= 0.01, f"{what}: {100 * share:.2f} % of the entries have an ambiguous bracket"
+    assert np.all((err <= bound) | skip), f"{what}: max err/bound {ratio.max():.3f} at {k}"
+    return float(ratio.max())
 
 
 def raw_block(hank, args, schedule, **env):
@@ -502,3 +529,123 @@ def against_oracle_and_launches(hank, shape, runs, Ns, seed=29):
             else:
                 close(dpol, dpol0, 1e-12, what=what + " dpolicy vs launch")
     return seen
+
+
+# ---- 5. the entry-wise tests' inputs (tests/test_ld_refs_host.py, tests/test_gpu_entrywise.py) -------------------------------
+# one EGM step and one distribution step at exact inputs, for tests/ld_refs.py's restatement and its running error bound
+ENTRY_GRIDS = ((33, 2), (130, 3))            # the primal blocks take 32 rows: 33 is two blocks, the second holding one row
+ENTRY_WIDE = (40, 11)                        # once, at gamma = 2
+ENTRY_BASE = (0.03, 1.0)
+ENTRY_PRICES = ((1.3 * 0.03, 0.97 * 1.0), (-0.5, 0.1), (1.0, 3.0))      # the last two push the grid off both ends of the knots
+ENTRY_TR = 0.07                              # the one-asset HANK family's transfer
+ENTRY_BC = 0.04                              # ... and its borrowing limit: above the first grid point and on none
+ENTRY_N = 3
+# the six CASES and the record diet's gamma = 2 arm — what a context takes by default at gamma = 2: diet_kc's k cm^3 and diet_v's
+# u sqrt(u), the library's only use of fast_sqrt
+ENTRY_CASES = {**CASES, "gamma2": (2.0, None, 1)}
+ENTRY_BACKWARD = [(f, name, n_a, n_e) for f in ("ks", "hank") for name in ENTRY_CASES for n_a, n_e in ENTRY_GRIDS] + \
+                 [(f, name, *ENTRY_WIDE) for f in ("ks", "hank") for name in ("gamma2", "gamma2-nodiet")]
+_ENTRY = {}
+
+
+def entry_Pi(n_e):
+    """a dense row-stochastic transition matrix that is NOT symmetric (a transposed use of Pi must show): 0.8 on the diagonal, the
+    rest spread by weights that differ by row and by column"""
+    k = np.arange(n_e)
+    M = 1.0 + k[None, :] + 0.5 * k[:, None] * (k[None, :] % 2)
+    return 0.8 * np.eye(n_e) + 0.2 * M / M.sum(axis=1, keepdims=True)
+
+
+def entry_backward(family, gamma, n_a, n_e):
+    """one EGM step's exact inputs -> dict(args: HouseholdBlock's, a, z, Pi, beta, gamma, bc, V, dV (n_a, n_e, 3), steps: [(x, dx)] at
+    ENTRY_PRICES). family "ks": inputs (r, w), the borrowing limit on the first grid point; "hank": (r, w, tr) with the transfer
+    ENTRY_TR and the limit ENTRY_BC off the grid, so that the `max` rule binds on interpolated policies too. V_next: three float64
+    EGM iterates (ld_refs.egm_step) of a power-law start at ENTRY_BASE — sorted knots, a decreasing value."""
+    key = ("back", family, gamma, n_a, n_e)
+    if key not in _ENTRY:
+        import ld_refs
+        a = 50.0 * np.linspace(0.0, 1.0, n_a) ** 2
+        z = np.linspace(0.5, 1.5, n_e)
+        Pi = entry_Pi(n_e)
+        beta, n_hh = 0.95, (2 if family == "ks" else 3)
+        bc = a[0] if family == "ks" else ENTRY_BC
+        tr = () if family == "ks" else (ENTRY_TR,)
+        V = np.outer((2.0 + a) ** -gamma, np.linspace(1.2, 0.8, n_e))
+        none = np.zeros((n_a, n_e, 0))
+        for _ in range(3):
+            V = ld_refs.egm_step(np.float64, a, z, Pi, beta, gamma, bc, V, none, ENTRY_BASE + tr, np.zeros((n_hh, 0)), 0)["V"].v
+        assert np.all(np.diff(V, axis=0) < 0)
+        rng = np.random.default_rng(n_a * 100 + n_e)
+        dV = rng.standard_normal(V.shape + (ENTRY_N,))
+        steps = [(np.array(p + tr), rng.standard_normal((n_hh, ENTRY_N))) for p in ENTRY_PRICES]
+        _ENTRY[key] = dict(args=(a, z, Pi, beta, gamma, bc, 5, 0 if family == "ks" else 1), a=a, z=z, Pi=Pi, beta=beta, gamma=gamma, bc=bc,
+                           V=np.ascontiguousarray(V), dV=dV, steps=steps)
+    return _ENTRY[key]
+
+
+def entry_refs(c, diet):
+    """ld_refs.egm_step in long double at every step of the case c (of `entry_backward`), once per case and diet"""
+    key = ("ref", id(c), diet)
+    if key not in _ENTRY:
+        import ld_refs
+        _ENTRY[key] = [ld_refs.egm_step(np.longdouble, c["a"], c["z"], c["Pi"], c["beta"], c["gamma"], c["bc"], c["V"], c["dV"], x, dx, diet)
+                       for x, dx in c["steps"]]
+    return _ENTRY[key]
+
+
+ENTRY_FORWARD = ("golden", "golden-own", "33x2", "257x4")
+
+
+def entry_forward(name):
+    """one distribution step's exact inputs -> dict(args, a, Pi, policy, dpolicy, D, dD): the committed golden's policy (clamps,
+    exact grid hits, non-monotone), or a random non-monotone policy with clamps at both ends and exact grid hits at 33x2 and at
+    257x4 (where the 256-thread blocks cross); D_prev log-uniform over 1e-30 .. 1e-2, normalised, dD_prev of its size entry by entry
+    ("golden-own": the golden's own D_prev and dD_prev instead)."""
+    key = ("fwd", name)
+    if key not in _ENTRY:
+        rng = np.random.default_rng(len(name))
+        if name.startswith("golden"):
+            g, k = np.load(ROOT / "tests" / "golden" / "forward_step_edge_30x3_N3.npz"), np.load(ROOT / "tests" / "golden" / "ks_30x3_T25_N3.npz")
+            a, z, Pi = k["a_grid"], k["z_grid"], k["Pi"]
+            args = (a, z, Pi, float(k["beta"]), float(k["gamma"]), float(k["borrow_cons"]), 5)
+            pol, dpol = g["policy"], g["dpolicy"]
+        else:
+            n_a, n_e = (int(q) for q in name.split("x"))
+            a = 50.0 * np.linspace(0.0, 1.0, n_a) ** 2
+            z, Pi = np.linspace(0.5, 1.5, n_e), entry_Pi(n_e)
+            args = (a, z, Pi, 0.95, 2.0, 0.0, 5)
+            pol = rng.uniform(-5.0, 55.0, (n_a, n_e))
+            hit = rng.random((n_a, n_e)) < 0.1
+            pol[hit] = a[rng.integers(0, n_a, hit.sum())]
+            dpol = rng.standard_normal((n_a, n_e, ENTRY_N))
+        D = 10.0 ** rng.uniform(-30.0, -2.0, pol.shape)
+        D /= D.sum()
+        dD = D[..., None] * rng.standard_normal(pol.shape + (dpol.shape[2],))
+        if name == "golden-own":
+            D, dD = g["D_prev"], g["dD_prev"]
+        _ENTRY[key] = dict(args=args, a=np.asarray(a), Pi=np.asarray(Pi), policy=np.ascontiguousarray(pol), dpolicy=np.ascontiguousarray(dpol),
+                           D=D, dD=dD)
+    return _ENTRY[key]
+
+
+def entry_forward_ref(name):
+    """ld_refs.forward_step in long double on `entry_forward(name)`, once"""
+    key = ("fwdref", name)
+    if key not in _ENTRY:
+        import ld_refs
+        c = entry_forward(name)
+        _ENTRY[key] = ld_refs.forward_step(np.longdouble, c["a"], c["Pi"], c["policy"], c["dpolicy"], c["D"], c["dD"])
+    return _ENTRY[key]
+
+
+def push_distribution(grid, Pi, pol, D0):
+    """D_0 pushed in long double through the policy sequence pol (n_a, n_e, P), the context's own exported bits: exact inputs, a
+    bound that compounds from period to period. -> [ld_refs.forward_step's dict per period]"""
+    import ld_refs
+    n_a, n_e, P = pol.shape
+    none = np.zeros((n_a, n_e, 0))
+    D, out = np.asarray(D0, dtype=np.float64).reshape((n_a, n_e), order="F"), []
+    for t in range(P):
+        out.append(ld_refs.forward_step(np.longdouble, grid, Pi, pol[:, :, t], none, D, none))
+        D = out[-1]["D"]
+    return out
