@@ -228,6 +228,46 @@ def ss_gradient(n_a=200, n_e=3, T=150, Z_end=1.03, seed=0):
             "directional_derivative_central_difference": fd, "relative_difference": abs(rev - fd) / max(abs(fd), 1e-300)}
 
 
+def ss_curve(var, lo, hi, K, n_a=500, n_e=4, T=300):
+    """The steady state's household side along a line in the free prices — `var` from lo to hi in K points, the other free prices at
+    the YAML's guesses — from ONE hank_ss_batch (`SSAssembler.batch`): per point the heterogeneous aggregates (the asset-supply
+    curve A(r) for var = r: what brackets a market-clearing rate when the guesses are poor), the residual norm and the value
+    steps. No price Newton runs."""
+    import hank_amd as h
+    from hank_amd.Aggregation import Residuals
+    from hank_amd.GeneralStructures import vars_of_type
+    from hank_amd.SteadyState import SSAssembler
+    ov = {"T": T, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": n_e}}}
+    m = h.build_model_from_yaml(str(ROOT / "examples" / "krusell_smith.yaml"), overrides=ov)
+    asm = SSAssembler(m, m.ss_initial, None, "device")
+    if var not in asm.free_keys:
+        raise SystemExit(f"--ss-curve: {var} is not a free price of the steady state (free: {', '.join(asm.free_keys)})")
+    if not 1 <= K <= 64:
+        raise SystemExit("--ss-curve: K must be 1..64 (one batch)")
+    p = np.tile(np.array([m.ss_initial.guesses.get(k, 1.0) for k in asm.free_keys], dtype=np.float64)[:, None], (1, K))
+    line = np.linspace(lo, hi, K)
+    p[asm.free_keys.index(var)] = line
+    t0 = time.perf_counter()
+    xVals, _, _, status = asm.batch(p)
+    wall = time.perf_counter() - t0
+    hb = h.household_block(m)
+    iters, ms = asm.last_batch_iters, hb.last_ss_batch_timings()
+    cs = m.compspec
+    T_pad = 1 + cs.max_lag + cs.max_lead
+    het = vars_of_type(m, "heterogeneous")
+    points = []
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for k in range(K):
+            ok = status[k] == 0
+            z = Residuals(np.tile(xVals[:, k][:, None], (1, T_pad)), m) if ok else None
+            points.append({var: float(line[k]), "status": int(status[k]),
+                           **({name: float(xVals[asm.all_keys.index(name), k]) for name in het} if ok else {}),
+                           "residual_norm": float(np.linalg.norm(z)) if ok else None,
+                           "value_steps": int(iters[k, 0]), "distribution_iterations": int(iters[k, 1])})
+    return {"grid": f"{n_a}x{n_e}", "line": {"var": var, "lo": lo, "hi": hi, "K": K}, "batches": 1, "wall_s": round(wall, 4),
+            "value_loops_ms": round(ms[0], 3), "distribution_loops_ms": round(ms[1], 3), "points": points}
+
+
 def solve_permanent(n_a=200, n_e=3, T=150, Z_end=1.03, eps=1e-9, verbose=False):
     """The two-steady-state scenario of the reference YAML (`ending:` block, KrusellSmith.yaml:109-116): TFP moves
     to Z_end for good in period 1. The path starts from the initial steady state (KS_0, D_0 = ss_initial), the terminal
@@ -270,6 +310,7 @@ if __name__ == "__main__":
     ap.add_argument("--scale", default=None, metavar="S1,S2,...", help="the nonlinear responses to the shock at these multiples (e.g. 0.5,1,2,-1), solved in lockstep from ONE hank_primal_batch per round; each peak response beside the first-order one from J̅")
     ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one hank_vjp against n_hh·P JVP columns")
     ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one hank_vjp_boundary, checked against two hank_jvp_boundary directions")
+    ap.add_argument("--ss-curve", nargs=4, default=None, metavar=("VAR", "LO", "HI", "K"), help="the steady state's household side along a line in the free prices (VAR from LO to HI in K points, the others at the YAML's guesses) from ONE hank_ss_batch: the heterogeneous aggregates, the residual norm and the value steps per point")
     ap.add_argument("--ss-gradient", action="store_true", help="with --permanent: the gradient of ½‖F(x)‖² with respect to the ending steady state's household prices through V_T (hank_vjp_het_boundary, then hank_ss_vjp), beside a central difference in one random direction")
     a = ap.parse_args()
     import os
@@ -280,7 +321,9 @@ if __name__ == "__main__":
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", torch.cuda.current_device()))
-    if a.scale:
+    if a.ss_curve:
+        out = ss_curve(a.ss_curve[0], float(a.ss_curve[1]), float(a.ss_curve[2]), int(a.ss_curve[3]), a.n_a, a.n_e, a.T)
+    elif a.scale:
         out = scale_family(a.n_a, a.n_e, a.T, a.shock, tuple(float(v) for v in a.scale.split(",")))
     elif a.boundary_gradient:
         out = boundary_gradient(a.n_a, a.n_e, a.T, a.shock)

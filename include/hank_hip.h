@@ -446,11 +446,44 @@ int hank_primal_batch(hank_ctx *ctx, int32_t n_het, const double *xhh, int32_t K
 int hank_primal_batch_dev(hank_ctx *ctx, int32_t n_het, const double *d_xhh, int32_t K, double *d_agg_out, double *d_policy_out);
 int hank_last_batch_timings(hank_ctx *ctx, double out_ms[2]);
 
+/* ---- the steady state's household side at K price vectors: one chain of launches ----------------------------------------------
+ * hank_ss_batch  ==  the inner fixed point of get_xVals (SteadyState.jl:132-141) followed by invariant_dist's fixed point
+ *   (ForwardIteration.jl:436-442, as the power method of hank_stationary_dist) and the aggregation of the heterogeneous keys, at K
+ *   constant household price vectors at once — the forward-difference columns and the step-halving trials of the price Newton
+ *   (SteadyState.jl:195), the two sides of a central difference, an asset-supply curve. Scenario k is hank_vfi at xhh[:, k] on the
+ *   per-step launches, then hank_stationary_dist on its policy: K independent fixed points share the launches of one
+ *   (gridDim.y = scenario), each with its own stop words; a scenario that has converged freezes while the others go on.
+ *   xhh (n_hh, K) column-major. value_io (G, K): in = scenario k's starting value, out = its converged value; policy_out (G, K) =
+ *   the policy of the step that produced it. D_io (G, K) or NULL (value iteration only; agg_out must then be NULL, else
+ *   HANK_ERR_BAD_ARG): in = scenario k's start (positive, as the caller normalised it), out = the iterate at which its rule first
+ *   held — exactly iters_out[2k+1] applications of Lambda(policy_k) to the start, NOT normalised. agg_out (n_het, K) or NULL:
+ *   Y_o = sum f_o D_k / sum D_k, f_o the outputs of hank_get_het_outputs (n_het above the family's count is HANK_ERR_BAD_ARG, above
+ *   the count declared with hank_set_het_outputs HANK_ERR_NOT_READY), by a block reduction in a fixed order: the same inputs give
+ *   the same bits. iters_out [K][2]: value steps, distribution iterations applied (a multiple of check_every, or dist_max_iter);
+ *   supnorm_out [K]: the last max|value_new - value|. Running into a cap is not an error (hank_vfi's rule): the scenario goes on
+ *   with what it has and iters_out tells.
+ *   The value, policy, step count and sup-norm of scenario k hold the bits of hank_vfi under HANK_SCHEDULE=launch, and D_io those of
+ *   hank_stationary_dist there with max_iter = iters_out[2k+1], whatever K is and wherever the scenario sits in the batch.
+ *   1 <= K <= 64, caps and check_every >= 1 (else HANK_ERR_BAD_ARG); a scenario with 1 + r <= 0 is HANK_ERR_DOMAIN before anything
+ *   runs. Verdict, per scenario, as in hank_primal_batch: status_out[k] (K codes, or NULL) is HANK_OK, HANK_ERR_KNOTS,
+ *   HANK_ERR_DOMAIN or HANK_ERR_NONMONOTONE; a failing scenario stops at its next check and skips the later stages (its outputs
+ *   are unspecified); the call returns the code of the lowest failing k and the message names k (from 0), K and the step. The
+ *   healthy scenarios' outputs are valid either way.
+ *   The call needs no boundary, always runs on the launches, and leaves the recorded primal, both current batches, the memo, the
+ *   schedule and the counters of hank_stats as they were, except out[5], which grows by the sum of the value steps. Its
+ *   workspaces live for the call. There is no _dev form: the loops need the host once per chunk of steps.
+ * hank_last_ss_batch_timings: HIP-event times (ms) of the last batch's value loops and distribution loops, the host's round trip
+ *   per chunk inside; -1 before the first call (out[1]: and after a call without D_io). */
+int hank_ss_batch(hank_ctx *ctx, int32_t n_het, const double *xhh, int32_t K, double vfi_tol, int32_t vfi_max_iter, double dist_tol,
+                  int32_t dist_max_iter, int32_t check_every, double *value_io, double *policy_out, double *D_io, double *agg_out,
+                  int32_t *iters_out, double *supnorm_out, int32_t *status_out);
+int hank_last_ss_batch_timings(hank_ctx *ctx, double out_ms[2]);
+
 /* Counters of this context (tests and scripts): out[0] sweep kernels launched by the persistent schedule, out[1] tangent
  * workspaces allocated (a change of batch width N re-uses a cached workspace: a small most-recently-used cache, 3 deep),
  * out[2] hipGraphs captured (per-period schedule), out[3] schedule in use (1 = XCD-local persistent sweeps, 0 = one
  * launch per period), out[4] times this context fell back from 1 to 0, out[5] device-resident value-function iterations
- * run by hank_vfi, out[6] primal sweeps the memo of hank_primal_jvp skipped, out[7] primal sweeps run (hank_primal[_dev],
+ * run by hank_vfi and hank_ss_batch (summed over its scenarios), out[6] primal sweeps the memo of hank_primal_jvp skipped, out[7] primal sweeps run (hank_primal[_dev],
  * hank_primal_jvp[_dev]). */
 int hank_stats(hank_ctx *ctx, int64_t out[8]);
 

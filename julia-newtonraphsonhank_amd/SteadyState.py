@@ -137,6 +137,57 @@ class SSAssembler:
         self._last_value = value
         return np.tile(xVals[:, None], (1, T_pad))
 
+    def batch(self, p_mat):
+        """`get_xVals` for K price vectors through one hank_ss_batch per 64 of them: p_mat (n_free, K) -> (xVals (n_v, K), values
+        (n_a, n_e, K), policies (n_a, n_e, K), status (K,) int32). The value loops, the lotteries, the power methods and the
+        aggregation of every heterogeneous key (output `vf.outputs.index(key)` of the device) run on the device for all K at once,
+        warm-started from `_value_warm` / `_D_warm` when present. A column the device refuses, or whose 1 + r is not positive,
+        has a non-zero status and unspecified values. The assembler's own warm state and `_last_xvals` stay as they were (the
+        normalised distributions of the call are at `last_batch_D`, (G, K), its step counts at `last_batch_iters`, (K, 2)). Device
+        VFI only."""
+        if not self.vfi_on_device:
+            raise ValueError("SSAssembler.batch needs the device VFI (hank_ss_batch): there is no host form of it")
+        from .BackwardIteration import ensure_het_outputs, het_output_count, household_block
+        from .hip import HANK_ERR_DOMAIN
+        model = self.model
+        vf = model.value_fn
+        P = np.asarray(p_mat, dtype=np.float64)
+        if P.ndim == 1:
+            P = P[:, None]
+        K = P.shape[1]
+        het_keys = vars_of_type(model, "heterogeneous")
+        outs = tuple(vf.outputs)
+        missing = [k for k in het_keys if k not in outs]
+        if missing:
+            raise ValueError(f"SSAssembler.batch: the device block does not serve the heterogeneous variables {missing}")
+        hb = household_block(model)
+        n_out = het_output_count(model, het_keys)
+        ensure_het_outputs(hb, n_out)
+        xv = {k: np.zeros(K) for k in self.all_keys}
+        for i, k in enumerate(self.free_keys):
+            xv[k] = P[i].copy()
+        for k, v in self.ss_spec.fixed.items():
+            xv[k] = np.full(K, float(v))
+        xhh = np.stack([xv[k] for k in vf.household_inputs], axis=0)                  # (n_hh, K)
+        ok = 1.0 + xhh[0] > 0.0 if vf.household_inputs[0] == "r" else np.ones(K, dtype=bool)
+        n_a, n_e = self.endog_dim.n, self.n_exog
+        values, policies = np.ones((n_a, n_e, K), order="F"), np.zeros((n_a, n_e, K), order="F")
+        D = np.zeros((n_a * n_e, K), order="F")
+        aggs = np.zeros((n_out, K))
+        status = np.where(ok, 0, HANK_ERR_DOMAIN).astype(np.int32)
+        iters_all = np.zeros((K, 2), dtype=np.int32)
+        cols = np.flatnonzero(ok)
+        for c0 in range(0, len(cols), 64):                   # (the library takes up to 64 scenarios per call)
+            cc = cols[c0:c0 + 64]
+            a, v, pol, d, iters, st = hb.ss_batch(xhh[:, cc], self.vfi_tol, n_het=n_out, value0=self._value_warm,
+                                                  D0=getattr(self, "_D_warm", None), check=False)
+            aggs[:, cc], values[:, :, cc], policies[:, :, cc], D[:, cc], status[cc], iters_all[cc] = a, v, pol, d, st, iters
+            self.vfi_steps += int(iters[:, 0].sum())
+        for k in het_keys:
+            xv[k] = aggs[outs.index(k)]
+        self.last_batch_D, self.last_batch_iters = D, iters_all
+        return np.stack([xv[k] for k in self.all_keys], axis=0), values, policies, status
+
 
 def implicit_price_jacobian(asm: SSAssembler, p_vec) -> np.ndarray:
     """dF/dp at the price iterate whose steady state `asm` has just solved (its last get_xVals), without another fixed point:
@@ -184,12 +235,49 @@ def implicit_price_jacobian(asm: SSAssembler, p_vec) -> np.ndarray:
     return np.stack(R, axis=1) @ dX
 
 
+def _residuals_batch(asm: SSAssembler, p_mat):
+    """(residuals (n_res, K), values (n_a, n_e, K), D (G, K)) of `asm.batch(p_mat)`; a failed scenario's column is inf"""
+    xVals, values, _, status = asm.batch(p_mat)
+    cs = asm.model.compspec
+    T_pad = 1 + cs.max_lag + cs.max_lead
+    out = None
+    for k in range(xVals.shape[1]):
+        if status[k] != 0:
+            continue
+        z = np.asarray(Residuals(np.tile(xVals[:, k][:, None], (1, T_pad)), asm.model), dtype=np.float64)
+        if out is None:
+            out = np.full((len(z), xVals.shape[1]), np.inf)
+        out[:, k] = z
+    if out is None:
+        out = np.full((asm.n_free, xVals.shape[1]), np.inf)
+    return out, values, asm.last_batch_D
+
+
+def residuals_batch(asm: SSAssembler, p_mat) -> np.ndarray:
+    """F(p) = Residuals(asm(p)) at K price vectors at once: p_mat (n_free, K) -> (n_res, K), the household side of every column in
+    one hank_ss_batch (`SSAssembler.batch`), the residual layer per column on the host. A column the device refuses, or whose
+    1 + r is not positive, comes back as a column of inf, as `NewtonRaphson.residuals_batch` does."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        return _residuals_batch(asm, p_mat)[0]
+
+
+def first_acceptable(norms, z_norm):
+    """the step-halving rule of find_ss on a batch of trials: the first j whose residual norm is finite and <= z_norm (the trial the
+    sequential loop would have stopped at), or None when no trial is acceptable. inf and nan entries are skipped."""
+    for j, nj in enumerate(norms):
+        if np.isfinite(nj) and nj <= z_norm:
+            return j
+    return None
+
+
 @host_algebra
 def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vfi_tol=None, vfi: str = "auto",
-            price_jacobian: str = "fd") -> SteadyState:
+            price_jacobian: str = "fd", batch: bool = False) -> SteadyState:
     """Newton–Raphson on the free endogenous variables with step halving (SteadyState.jl:184-233). price_jacobian: "fd" — forward
     differences, one more steady state per free price — or "implicit" — the derivatives through the steady state from the device
-    (`implicit_price_jacobian`: no further fixed point; needs the device VFI, no fallback)."""
+    (`implicit_price_jacobian`: no further fixed point; needs the device VFI, no fallback). batch=True (device VFI only): the
+    forward-difference columns of an iterate run as ONE hank_ss_batch, and so do its trials p - 2^-j step, j = 0..5, of which the
+    first acceptable one is taken — the sequential rule's choice; when none is, the halving goes on one trial at a time."""
     from .NewtonRaphson import warm_linear_solver
     from .GeneralStructures import vars_of_type
     if price_jacobian not in ("fd", "implicit"):
@@ -199,7 +287,11 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
     if price_jacobian == "implicit" and not asm.vfi_on_device:
         raise ValueError("price_jacobian='implicit' needs the device (hank_ss_jvp at the record of hank_primal) and the device VFI: "
                          "there is no host form of it" + (" (vfi='host' was asked for)" if vfi == "host" else ""))
+    if batch and not asm.vfi_on_device:
+        raise ValueError("batch=True needs the device VFI (hank_ss_batch runs the value loops of all trials on the device): "
+                         "there is no host form of it" + (" (vfi='host' was asked for)" if vfi == "host" else ""))
     asm.newton_iterations = 0
+    batches = 0
 
     def F(p):
         return Residuals(asm(p), model)
@@ -225,6 +317,13 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
                 if asm._last_p is None or not np.array_equal(asm._last_p, p):      # (a halved step's last evaluation was refused)
                     F(p)
                 J = implicit_price_jacobian(asm, p)
+            elif batch:
+                h = 1e-6 * np.maximum(1.0, np.abs(p))
+                Zq = _residuals_batch(asm, p[:, None] + np.diag(h))[0]
+                batches += 1
+                if not np.all(np.isfinite(Zq)):
+                    raise ValueError(f"find_ss [{label}]: a forward-difference column of the batch has no finite residual")
+                J = (Zq - z[:, None]) / h[None, :]
             else:
                 for j in range(asm.n_free):
                     h = 1e-6 * max(1.0, abs(p[j]))
@@ -233,8 +332,20 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
                     J[:, j] = (F(q) - z) / h
             step = np.linalg.solve(J, z)
             η, z_norm = 1.0, np.linalg.norm(z)
-            p_new = p - η * step
-            z_new = safe_eval(p_new)
+            if batch:
+                etas = 0.5 ** np.arange(6)
+                P_try = p[:, None] - step[:, None] * etas[None, :]
+                Zt, Vt, Dt = _residuals_batch(asm, P_try)
+                batches += 1
+                j = first_acceptable([np.linalg.norm(Zt[:, q]) for q in range(6)], z_norm)
+                if j is None:                       # the sequential halving goes on from j = 6
+                    η, p_new, z_new = etas[5], P_try[:, 5], np.full(len(z), np.inf)
+                else:                               # the accepted trial's fixed point warm-starts the next iterate's
+                    η, p_new, z_new = etas[j], P_try[:, j], Zt[:, j]
+                    asm._last_value, asm._D_warm = Vt[:, :, j], Dt[:, j]
+            else:
+                p_new = p - η * step
+                z_new = safe_eval(p_new)
             while (not np.isfinite(np.linalg.norm(z_new))) or np.linalg.norm(z_new) > z_norm:
                 η /= 2
                 if not η > 1e-8:
@@ -275,13 +386,13 @@ def find_ss(model: SequenceModel, ss_spec, label: str, verbose: bool = False, vf
     ss = SteadyState(vars_, policies, Λss, D, ss_value)
     # how the solve went (scripts and tests compare the two price Jacobians): the assembler's counters at the end
     ss.solve_info = {"price_jacobian": price_jacobian, "vfi_steps": asm.vfi_steps, "newton_iterations": asm.newton_iterations,
-                     "residual_norm": float(np.linalg.norm(z))}
+                     "residual_norm": float(np.linalg.norm(z)), "batches": batches}
     return ss
 
 
-def get_SteadyStates(model: SequenceModel, verbose: bool = False, vfi_tol=None, vfi: str = "auto", price_jacobian: str = "fd"):
-    """both steady states (SteadyState.jl:245-259); one solve when the specs are the same object. price_jacobian: see find_ss."""
-    ss_initial = find_ss(model, model.ss_initial, "initial", verbose, vfi_tol, vfi, price_jacobian)
+def get_SteadyStates(model: SequenceModel, verbose: bool = False, vfi_tol=None, vfi: str = "auto", price_jacobian: str = "fd", batch: bool = False):
+    """both steady states (SteadyState.jl:245-259); one solve when the specs are the same object. price_jacobian, batch: see find_ss."""
+    ss_initial = find_ss(model, model.ss_initial, "initial", verbose, vfi_tol, vfi, price_jacobian, batch)
     if model.ss_initial is model.ss_ending:
         return ss_initial, ss_initial
-    return ss_initial, find_ss(model, model.ss_ending, "ending", verbose, vfi_tol, vfi, price_jacobian)
+    return ss_initial, find_ss(model, model.ss_ending, "ending", verbose, vfi_tol, vfi, price_jacobian, batch)

@@ -10,6 +10,7 @@
 #include "hank_wide.h"
 #include "hank_hetx.h"
 #include "hank_scen.h"
+#include "hank_ssbatch.h"
 #include "hank_adjoint.h"
 #include "hank_boundary.h"
 #include "hank_ssdiff_launch.h"
@@ -214,7 +215,7 @@ struct TanBatch {
 };
 
 // The timed sweeps of hank_last_timings (the first six, in its slot order), hank_last_vjp_timings (the next two) and
-// hank_last_ss_timings (the next two) and hank_last_batch_timings (the last two). A span is a
+// hank_last_ss_timings (the next two), hank_last_batch_timings (the next two) and hank_last_ss_batch_timings (the last two). A span is a
 // begin event, an end event, a valid flag and the launch count of the run that ended it; the run functions reach them through these
 // operations only. Recording a span's begin makes it invalid until its end is recorded. What each run function leaves behind
 // (V valid, I invalid, . untouched) — the families do NOT agree, see DESIGN.md section 2a:
@@ -230,7 +231,8 @@ struct TanBatch {
 //   enqueue_vjp               .          .         .        .        .        .       V     V      .       .
 //   ss_loop                   .          .         .        .        .        .       .     .      V       V      (the loop it was called for; I until that loop's end)
 //   primal_batch              .          .         .        .        .        .       .     .      .       .      (its own two, SCEN_BACK and SCEN_FWD: V)
-enum Span { PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD, VJP_A, VJP_B, SS_VALUE, SS_DIST, SCEN_BACK, SCEN_FWD, N_SPANS };
+//   ss_batch                  .          .         .        .        .        .       .     .      .       .      (its own two, SSB_VALUE and SSB_DIST: V; SSB_DIST I without a distribution)
+enum Span { PRIMAL_BACK, PRIMAL_FWD, TAN_BACK, TAN_FWD, DUAL_BACK, DUAL_FWD, VJP_A, VJP_B, SS_VALUE, SS_DIST, SCEN_BACK, SCEN_FWD, SSB_VALUE, SSB_DIST, N_SPANS };
 struct Spans {
     struct One { hipEvent_t ev0 = nullptr, ev1 = nullptr, from = nullptr; bool valid = false; int launches = 0; } s[N_SPANS];      // from: the event the span began with (ev0, or the end of the span before it)
     hipError_t create() { hipError_t e = hipSuccess; for (One &o : s) { if (e == hipSuccess) e = hipEventCreate(&o.ev0); if (e == hipSuccess) e = hipEventCreate(&o.ev1); } return e; }
@@ -3264,6 +3266,156 @@ int hank_last_batch_timings(hank_ctx *ctx, double out_ms[2]) {
     return HANK_OK;
 }
 }
+
+// ---- hank_ss_batch: the steady state's household side at K price vectors (hank_ssbatch.h) -----------------
+// Scenario k is hank_vfi's launch branch at x_k, then hank_stationary_dist's, on a workspace of its own that lives for the call
+// (Scratch): the context's record, primal_done, both current batches, the memo, `stationary`, the schedule and the sweep counters
+// stay as they were; the context's error word is not touched (every scenario has its own). It needs no boundary.
+//
+// One loop of either kind: `enqueue` issues a chunk of launches for all K and returns the count of steps issued so far; the K stop
+// words come back once per chunk; the loop ends when every scenario has stopped or `cap` steps are out.
+template <typename Enqueue>
+static int ssb_loop(hank_ctx *ctx, const SsbCtl *d_ctl, int K, int cap, std::vector<SsbCtl> &h, Span span, Enqueue enqueue) {
+    hipStream_t s = ctx->stream;
+    HIPC(ctx, ctx->spans.begin(span, s));
+    int done = 0, launches = 0;
+    bool all = false;
+    while (!all && done < cap) {
+        done = enqueue(done, &launches);
+        HIPC(ctx, hipGetLastError());
+        HIPC(ctx, hipMemcpyAsync(h.data(), d_ctl, sizeof(SsbCtl) * K, hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipStreamSynchronize(s));
+        all = true;
+        for (int k = 0; k < K; k++) all = all && h[k].stop != 0;
+    }
+    HIPC(ctx, ctx->spans.end(span, s, launches));
+    return HANK_OK;
+}
+
+extern "C" {
+int hank_ss_batch(hank_ctx *ctx, int32_t n_het, const double *xhh, int32_t K, double vfi_tol, int32_t vfi_max_iter, double dist_tol, int32_t dist_max_iter,
+                  int32_t check_every, double *value_io, double *policy_out, double *D_io, double *agg_out, int32_t *iters_out, double *supnorm_out,
+                  int32_t *status_out) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    if (!xhh || !value_io || !policy_out || !iters_out || !supnorm_out) return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_batch: null pointer");
+    if (agg_out && !D_io) return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_batch: agg_out needs D_io (the aggregates are sums over the distribution)");
+    if (K < 1 || K > SCEN_KMAX) return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_batch: K must be 1..%d, got %d", SCEN_KMAX, K);
+    if (vfi_max_iter < 1 || dist_max_iter < 1 || check_every < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_batch: vfi_max_iter, dist_max_iter and check_every must be >= 1");
+    if (agg_out) { const int hrc = het_count_ok(ctx, "hank_ss_batch", n_het, true); if (hrc) return hrc; }
+    const Consts &c = ctx->c;
+    for (int k = 0; k < K; k++)
+        if (!(1.0 + xhh[(size_t)c.n_hh * k] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "hank_ss_batch: 1 + r must be positive (scenario %d of %d)", k, K);
+    const size_t G = c.G, g8 = G * sizeof(double), g4 = G * sizeof(int), KK = (size_t)K, nbp = ctx->nbp;
+    hipStream_t s = ctx->stream;
+    // every scenario's arrays, carved alike: the value double buffer, the EGM step's one-period record, the lottery's, the distribution's
+    size_t off = 0;
+    const size_t o_V0 = carve(off, g8), o_V1 = carve(off, g8), o_s = carve(off, g8), o_kc = carve(off, g8), o_A = carve(off, g8), o_B = carve(off, g8),
+                 o_u = carve(off, g8), o_v = carve(off, g8), o_pol = carve(off, g8), o_ib = carve(off, g4);
+    size_t o_lw = 0, o_ig = 0, o_lo = 0, o_st = 0, o_clo = 0, o_D0 = 0, o_D1 = 0, o_Dc = 0, o_ap = 0;
+    if (D_io) {
+        o_lw = carve(off, g8); o_ig = carve(off, g8); o_lo = carve(off, g4); o_st = carve(off, (size_t)c.n_e * (c.n_a + 1) * sizeof(int));
+        o_clo = carve(off, c.n_e * sizeof(int)); o_D0 = carve(off, g8); o_D1 = carve(off, g8); o_Dc = carve(off, g8); o_ap = carve(off, 2 * nbp * sizeof(double));
+    }
+    Scratch sc;
+    char *b;
+    double *xd, *expo, *outd = nullptr;
+    int *err;
+    SsbCtl *ctl;
+    HIPC(ctx, sc.alloc(&b, off * KK)); HIPC(ctx, sc.alloc(&xd, (size_t)c.n_hh * KK)); HIPC(ctx, sc.alloc(&err, 4 * KK)); HIPC(ctx, sc.alloc(&ctl, 2 * KK));
+    HIPC(ctx, sc.alloc(&expo, (D_io ? 3 : 2) * G * KK));
+    if (agg_out) HIPC(ctx, sc.alloc(&outd, (size_t)n_het * KK));
+    SsbArgs a{};
+    a.V[0] = (double *)(b + o_V0); a.V[1] = (double *)(b + o_V1); a.sK = (double *)(b + o_s); a.kc = (double *)(b + o_kc); a.A = (double *)(b + o_A);
+    a.B = (double *)(b + o_B); a.u = (double *)(b + o_u); a.v = (double *)(b + o_v); a.ib = (int *)(b + o_ib); a.R0.pol = (double *)(b + o_pol);
+    if (D_io) {
+        a.R0.lw = (double *)(b + o_lw); a.R0.ig = (double *)(b + o_ig); a.R0.lo = (int *)(b + o_lo); a.R0.start = (int *)(b + o_st); a.R0.clo = (int *)(b + o_clo);
+        a.D[0] = (double *)(b + o_D0); a.D[1] = (double *)(b + o_D1); a.Dchk = (double *)(b + o_Dc); a.aggp = (double *)(b + o_ap);
+    }
+    a.stride = off; a.xhh = xd; a.err = err; a.vctl = ctl; a.dctl = ctl + KK;
+    HIPC(ctx, join_side(ctx));
+    HIPC(ctx, hipMemcpyAsync(xd, xhh, sizeof(double) * c.n_hh * KK, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemcpy2DAsync(a.V[0], off, value_io, g8, g8, KK, hipMemcpyHostToDevice, s));
+    HIPC(ctx, hipMemsetAsync(err, 0, sizeof(int) * 4 * KK, s));
+    HIPC(ctx, hipMemsetAsync(ctl, 0, sizeof(SsbCtl) * 2 * KK, s));
+    const dim3 blk(RBP * c.n_e), grd((unsigned)nbp, (unsigned)K);
+    const size_t lds = primal_lds(c);
+    std::vector<SsbCtl> hv(KK), hd(KK);
+    // 1. the value loops: three launches per step for all K, the stop words once per chunk of 64 steps
+    int rc = ssb_loop(ctx, a.vctl, K, vfi_max_iter, hv, SSB_VALUE, [&](int done, int *launches) {
+        const int n = std::min(64, (int)vfi_max_iter - done);
+        for (int j = 0; j < n; j++) {
+            const int cur = (done + j) & 1;
+            hipLaunchKernelGGL(k_ssb_egm_X, grd, blk, lds, s, c, a, cur);
+            hipLaunchKernelGGL(k_ssb_egm_Y, grd, blk, 0, s, c, a, cur);
+            hipLaunchKernelGGL(k_ssb_vfi_check, dim3((unsigned)K), dim3(1024), 0, s, a, (int)G, cur, vfi_tol);
+        }
+        *launches += 3 * n;
+        return done + n;
+    });
+    if (rc) return rc;
+    if (D_io) {
+        // 2. every scenario's lottery in one launch, then the power methods: a chunk = 16 checks, check_every iterations before each
+        HIPC(ctx, hipMemcpy2DAsync(a.D[0], off, D_io, g8, g8, KK, hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpy2DAsync(a.Dchk, off, D_io, g8, g8, KK, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_ssb_lottery, dim3((unsigned)c.n_e, (unsigned)K), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, a);
+        hipLaunchKernelGGL(k_ssb_dist_init, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, s, a, (int)K);
+        rc = ssb_loop(ctx, a.dctl, K, dist_max_iter, hd, SSB_DIST, [&](int done, int *launches) {
+            for (int q = 0; q < 16 && done < dist_max_iter; q++) {
+                const int n = std::min((int)check_every, (int)dist_max_iter - done);
+                for (int j = 0; j < n; j++, done++) hipLaunchKernelGGL(k_ssb_dist_iter, grd, blk, lds, s, c, a, done & 1);
+                hipLaunchKernelGGL(k_ssb_dist_check, dim3((unsigned)K), dim3(1024), 0, s, a, (int)G, done & 1, n, dist_tol);
+                *launches += n + 1;
+            }
+            return done;
+        });
+        if (rc) return rc;
+        // 3. the outputs
+        if (agg_out) {
+            HIPC(ctx, hipMemsetAsync(outd, 0, sizeof(double) * n_het * KK, s));
+            hipLaunchKernelGGL(k_ssb_outputs, dim3((unsigned)n_het, (unsigned)K), dim3(1024), 0, s, c, a, (int)n_het, outd);
+            HIPC(ctx, hipMemcpyAsync(agg_out, outd, sizeof(double) * n_het * KK, hipMemcpyDeviceToHost, s));
+        }
+    } else {
+        ctx->spans.invalidate({SSB_DIST});
+    }
+    double *Vexp = expo, *Pexp = expo + G * KK, *Dexp = D_io ? expo + 2 * G * KK : nullptr;
+    hipLaunchKernelGGL(k_ssb_export, dim3((unsigned)((G + 255) / 256), (unsigned)K), dim3(256), 0, s, a, (int)G, Vexp, Pexp, Dexp);
+    HIPC(ctx, hipGetLastError());
+    HIPC(ctx, hipMemcpyAsync(value_io, Vexp, g8 * KK, hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipMemcpyAsync(policy_out, Pexp, g8 * KK, hipMemcpyDeviceToHost, s));
+    if (D_io) HIPC(ctx, hipMemcpyAsync(D_io, Dexp, g8 * KK, hipMemcpyDeviceToHost, s));
+    std::vector<int> e(4 * KK);
+    HIPC(ctx, hipMemcpyAsync(e.data(), err, e.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(ctx, hipStreamSynchronize(s));      // (the call's buffers go with it)
+    // the verdict, per scenario: the value loop's word names the step that raised it; the lottery's is the power method's
+    int first = HANK_OK, kfirst = -1;
+    long long steps = 0;
+    char keep[sizeof(ctx->errmsg)];
+    for (int k = 0; k < K; k++) {
+        iters_out[2 * k] = hv[k].n;
+        iters_out[2 * k + 1] = D_io ? hd[k].n : 0;
+        supnorm_out[k] = hv[k].norm;
+        steps += hv[k].n;
+        int vrc = word_verdict(ctx, THIS_CALL, &e[4 * k], IN_VFI, hv[k].n);
+        if (!vrc) vrc = word_verdict(ctx, THIS_CALL, &e[4 * k], IN_POWER_METHOD);
+        if (!vrc && e[4 * k]) vrc = word_verdict(ctx, THIS_CALL, &e[4 * k], IN_SWEEP);
+        if (status_out) status_out[k] = vrc;
+        if (vrc && kfirst < 0) { first = vrc; kfirst = k; memcpy(keep, ctx->errmsg, sizeof(keep)); }
+    }
+    ctx->stats[VFI_ITERATIONS] += steps;
+    if (kfirst < 0) { ctx->errmsg[0] = 0; return HANK_OK; }
+    keep[sizeof(keep) - 1] = 0;
+    return fail(ctx, first, "hank_ss_batch: scenario %d of %d: %.400s", kfirst, K, keep);
+}
+int hank_last_ss_batch_timings(hank_ctx *ctx, double out_ms[2]) {
+    if (!ctx || !out_ms) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 2; k++) HIPC(ctx, ctx->spans.read((Span)(SSB_VALUE + k), &out_ms[k], nullptr));
+    return HANK_OK;
+}
+}  // extern "C"
 
 // ---- derivatives through the steady state (hank_ssdiff.h) ------------------------------------------------
 // The loop driver of all four fixed points, in the manner of hank_vfi's launch branch: a chunk of steps is enqueued (each step =

@@ -485,11 +485,9 @@ __global__ void k_dist_iter(Consts c, Record R, const double *Din, double *Dout,
     dist_step_body(c, R, 0, aggpart, blockIdx.x, gridDim.x, sh, Din, Dout);
 }
 
-// one convergence check of the steady state's inner fixed point (SteadyState.jl:136-139: max|value_new - value| < tol,
-// after EVERY step): one block; state = {stop, steps done}. A NaN norm never stops the loop, as in the reference.
-__global__ void k_vfi_check(const double *Vnew, const double *Vold, int G, double tol, int *state, double *norm_out) {
-    __shared__ double red[16];
-    if (state[0]) return;
+// supnorm_block: max|Vnew - Vold| over G points by one block of up to 1024 threads, valid in thread 0 (NaN when any difference is);
+// the body of k_vfi_check and of the scenario batch's checks (hank_ssbatch.h). red: 16 doubles of LDS.
+__device__ __forceinline__ double supnorm_block(const double *Vnew, const double *Vold, int G, double *red) {
     double m = 0.0;
     bool bad = false;
     for (int i = threadIdx.x; i < G; i += blockDim.x) {
@@ -502,8 +500,17 @@ __global__ void k_vfi_check(const double *Vnew, const double *Vold, int G, doubl
     for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(m, off, 64); m = (o > m || !(o == o)) ? o : m; }
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0)
         for (int k = 1; k < (int)(blockDim.x >> 6); k++) m = (red[k] > m || !(red[k] == red[k])) ? red[k] : m;
+    return m;
+}
+// one convergence check of the steady state's inner fixed point (SteadyState.jl:136-139: max|value_new - value| < tol,
+// after EVERY step): one block; state = {stop, steps done}. A NaN norm never stops the loop, as in the reference.
+__global__ void k_vfi_check(const double *Vnew, const double *Vold, int G, double tol, int *state, double *norm_out) {
+    __shared__ double red[16];
+    if (state[0]) return;
+    const double m = supnorm_block(Vnew, Vold, G, red);
+    if (threadIdx.x == 0) {
         state[1] += 1;
         *norm_out = m;
         if (m < tol) state[0] = 1;

@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "hank_jvp_het", "hank_jvp_het_dev", "hank_vjp_het_boundary", "hank_vjp_het_boundary_dev",
     "hank_ss_jvp", "hank_ss_jvp_dev", "hank_ss_vjp", "hank_ss_vjp_dev", "hank_last_ss_timings",
     "hank_primal_batch", "hank_primal_batch_dev", "hank_last_batch_timings",
+    "hank_ss_batch", "hank_last_ss_batch_timings",
 )
 
 
@@ -147,6 +148,8 @@ def load_library() -> C.CDLL:
     lib.hank_primal_batch.argtypes = [vp, i32, dp, i32, dp, dp, C.POINTER(i32)]
     lib.hank_primal_batch_dev.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.hank_last_batch_timings.argtypes = [vp, dp]
+    lib.hank_ss_batch.argtypes = [vp, i32, dp, i32, C.c_double, i32, C.c_double, i32, i32, dp, dp, dp, dp, C.POINTER(i32), dp, C.POINTER(i32)]
+    lib.hank_last_ss_batch_timings.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
@@ -336,6 +339,63 @@ class HouseholdBlock:
         """time (ms, HIP events on the stream) of the last batch's backward and forward chains (hank_last_batch_timings)"""
         ms = (C.c_double * 2)()
         self._chk(self._lib.hank_last_batch_timings(self._ctx, ms))
+        return (ms[0], ms[1])
+
+    # -- the steady state's household side at K price vectors ---------------------------------
+    def _per_scenario(self, arr, K, fill):
+        """a start of `ss_batch`: None (`fill` everywhere), (n_a, n_e) or (G,) shared, (n_a, n_e, K) or (G, K) -> (G, K) column-major"""
+        if arr is None:
+            return np.full((self.G, K), fill, order="F")
+        s = np.asarray(arr, dtype=np.float64)
+        if s.shape in ((self.n_a, self.n_e), (self.G,)):
+            return np.asfortranarray(np.repeat(s.reshape((self.G, 1), order="F"), K, axis=1))
+        if s.ndim == 3 and s.shape[:2] == (self.n_a, self.n_e):
+            s = s.reshape((self.G, s.shape[2]), order="F")
+        return _f(np.array(s, copy=True), (self.G, K))
+
+    def ss_batch(self, xhh, vfi_tol: float, n_het: int = 1, value0=None, D0=None, vfi_max_iter: int = 10_000, dist_tol: float = 1e-15,
+                 dist_max_iter: int = 500_000, check_every: int = 25, dist: bool = True, check: bool = True):
+        """the steady state's household side at K constant price vectors at once (hank_ss_batch): xhh (n_hh, K) — or (n_hh,) for
+        one scenario — -> (aggs (n_het, K), value (n_a, n_e, K), policy (n_a, n_e, K), D (G, K) with every column summing to one,
+        iters (K, 2) = value steps and distribution iterations, status (K,) int32). Scenario k is `vfi` at xhh[:, k] on the per-step
+        launches followed by `stationary_dist` on its policy, bit for bit. value0: None (ones), (n_a, n_e) shared or (n_a, n_e, K);
+        D0 likewise (normalised to sum to one; None = uniform). dist=False: value iteration only (aggs and D are None). The
+        context's record, batches and memo stay as they were. check=True raises the first failing scenario's exception; the raw
+        arrays of the call (D as the library left it, the sup-norms) are at `last_ss_batch` either way."""
+        x = np.asarray(xhh, dtype=np.float64)
+        if x.ndim == 1:
+            x = x[:, None]
+        K = x.shape[1] if x.ndim == 2 else 0
+        x = _f(x, (self.n_hh, K))
+        Kb, nh = max(K, 1), max(int(n_het), 1)
+        v = self._per_scenario(value0, Kb, 1.0)
+        pol = np.empty((self.G, Kb), order="F")
+        d = aggs = None
+        if dist:
+            d = self._per_scenario(D0, Kb, 1.0 / self.G)
+            if D0 is not None:
+                d /= d.sum(axis=0, keepdims=True)
+            aggs = np.empty((nh, Kb), order="F")
+        iters = np.zeros((Kb, 2), dtype=np.int32)
+        nrm = np.zeros(Kb)
+        status = np.zeros(Kb, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        rc = self._lib.hank_ss_batch(self._ctx, int(n_het), _p(x), K, float(vfi_tol), int(vfi_max_iter), float(dist_tol), int(dist_max_iter),
+                                     int(check_every), _p(v), _p(pol), _opt(d), _opt(aggs), iters.ctypes.data_as(ip), _p(nrm), status.ctypes.data_as(ip))
+        self.last_ss_batch = {"aggs": aggs, "value": v, "policy": pol, "D": d, "iters": iters, "supnorm": nrm, "status": status}
+        if rc != HANK_OK and (check or not np.any(status)):      # (a refusal of the call itself always raises)
+            self._chk(rc)
+        Dn = None
+        if dist:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                Dn = d / d.sum(axis=0, keepdims=True)
+        shape = (self.n_a, self.n_e, Kb)
+        return aggs, v.reshape(shape, order="F"), pol.reshape(shape, order="F"), Dn, iters, status
+
+    def last_ss_batch_timings(self):
+        """time (ms, HIP events on the stream) of the last `ss_batch`'s value loops and distribution loops (hank_last_ss_batch_timings)"""
+        ms = (C.c_double * 2)()
+        self._chk(self._lib.hank_last_ss_batch_timings(self._ctx, ms))
         return (ms[0], ms[1])
 
     def primal_jvp_dev(self, d_xhh_ptr: int, d_dxhh_ptr: int, N: int, d_agg_ptr: int = 0, d_dagg_ptr: int = 0):

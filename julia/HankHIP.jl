@@ -441,6 +441,32 @@ function hank_primal_batch!(aggs::Array{Float64,3}, ctx::HankCtx, xhh::Array{Flo
     return aggs, status
 end
 
+# ---- the steady state's household side at K price vectors (hank_ss_batch) -----------------------------------------------------------
+# get_xVals' inner fixed point (SteadyState.jl:132-141), invariant_dist's (ForwardIteration.jl:436-442, by the power method) and
+# the aggregation of the heterogeneous keys at K constant price vectors through one chain of launches — the columns of
+# ForwardDiff.jacobian's finite-difference stand-in and the trials of a step rule for find_ss (:184-233). xhh (n_hh, K); value
+# (n_a, n_e, K): in the starting values (ones in the reference), out the converged ones; D (G, K) or nothing: in the starts (positive,
+# normalised), out the iterates at which the rule first held, NOT normalised; with D, aggs (n_het, K) is filled. Returns
+# (aggs, value, policy, D, iters (2, K): value steps and distribution iterations, status). check as in hank_primal_batch!.
+function hank_ss_batch!(value::Array{Float64,3}, ctx::HankCtx, xhh::Matrix{Float64}, vfi_tol::Float64; n_het::Integer = 1,
+                        D::Union{Nothing,Matrix{Float64}} = nothing, vfi_max_iter::Integer = 10_000, dist_tol::Float64 = 1e-15,
+                        dist_max_iter::Integer = 500_000, check_every::Integer = 25, check::Bool = true)
+    K = size(xhh, 2)
+    @assert size(xhh, 1) == length(ctx.hh_rows) && size(value) == (ctx.n_a, ctx.n_e, K)
+    @assert D === nothing || size(D) == (ctx.n_a * ctx.n_e, K)
+    policy = Array{Float64}(undef, ctx.n_a, ctx.n_e, K)
+    aggs = D === nothing ? nothing : Array{Float64}(undef, n_het, K)
+    iters, supnorm, status = zeros(Int32, 2, K), zeros(Float64, K), zeros(Int32, K)
+    np(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    rc = GC.@preserve D aggs ccall((:hank_ss_batch, LIBHANK), Cint,
+                                   (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Float64, Int32, Float64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                                    Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+                                   ctx.ptr, Int32(n_het), xhh, Int32(K), vfi_tol, Int32(vfi_max_iter), dist_tol, Int32(dist_max_iter), Int32(check_every),
+                                   value, policy, np(D), np(aggs), iters, supnorm, status)
+    (check || !any(!=(0), status)) && _check(ctx.ptr, rc)
+    return aggs, value, policy, D, iters, status
+end
+
 # the cotangent of the policy sequence of the last hank_vjp! / hank_vjp_het!, (n_a, n_e, P, M): the reference's Δpolicy_seqs
 # (ForwardIteration.jl:412-416) for the policy variable when n_het = 1
 function hank_policy_cotangent_seq(ctx::HankCtx, M::Integer)
