@@ -132,14 +132,14 @@ k_adj_dist(Consts c, Record R, const double *__restrict__ xhh, AdjGeom g, int t,
             double wj = 0.0, gD = 0.0;
             if (!clamped) { wj = R.lw[colb + j]; gD = R.ig[colb + j] * Dprev[j]; }
             const double Dn = Dnext[j];
-            st_mode<HANK_ST_STATE>(&lo_out[(size_t)j * MV], clamped ? u0 : vadd(vmul(1.0 - wj, u0), vmul(wj, u1)));
+            st_wt(&lo_out[(size_t)j * MV], clamped ? u0 : vadd(vmul(1.0 - wj, u0), vmul(wj, u1)));
             VT ye = yd;      // the policy's direct weight in the outputs, per unit of D_t: yb0 - yb1 - sum_o f_c,o ybx_o
             if constexpr (NX > 0) {
 #pragma unroll
                 for (int o = 0; o < NX; o++) ye = vsub(ye, vmul(hx.fc[o * PG + colb + j], yx[o]));
             }
             // (a clamped source's policy cotangent has no lottery part)
-            st_mode<HANK_ST_DPOL>(&pb_out[(size_t)j * MV], clamped ? vmul(Dn, ye) : vadd(vmul(Dn, ye), vmul(gD, vsub(u1, u0))));
+            st_wt(&pb_out[(size_t)j * MV], clamped ? vmul(Dn, ye) : vadd(vmul(Dn, ye), vmul(gD, vsub(u1, u0))));
         });
 }
 
@@ -157,7 +157,7 @@ k_adj_egm(Consts c, Record R, AdjGeom g, int t, int first, int last, const int *
     const size_t MV = g.MV, per = (size_t)gridDim.x * 3 * MV;      // a period of partS / partM
     adj_egm_body<VT>(c, R, g, L, t, t + 1, !first, !last, sb, muIn, pbar, adj_sh, partS + (size_t)t * per, partM + (size_t)(t + 1) * per,
         [&](int i, VT mn) __attribute__((always_inline)) {
-            st_mode<HANK_ST_STATE>(&muOut[((size_t)L.e * c.n_a + i) * MV + L.m], mn);
+            st_wt(&muOut[((size_t)L.e * c.n_a + i) * MV + L.m], mn);
             return mn;
         });
 }

@@ -48,34 +48,12 @@ __device__ inline double block_sum(double x, double *red, int nthreads) {
 
 // Workgroup barrier for LDS hand-offs: waits for this wave's LDS operations only. __syncthreads() carries a fence that
 // also drains vmcnt — every write-through (sc1) store issued before it would have to reach memory before the barrier
-// opens, although nothing behind these barriers reads global memory another thread of the block wrote (dev knob
-// HANK_RAW_BARRIER=0 restores __syncthreads()).
-#ifndef HANK_RAW_BARRIER
-#define HANK_RAW_BARRIER 1
-#endif
-__device__ __forceinline__ void lds_barrier() {
-#if HANK_RAW_BARRIER
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-    __syncthreads();
-#endif
-}
+// opens, although nothing behind these barriers reads global memory another thread of the block wrote.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// dev knob: how the big streaming stores leave the CU (0 plain, 1 sc1 write-through, 2 nontemporal)
-#ifndef HANK_ST_DPOL
-#define HANK_ST_DPOL 1
-#endif
-#ifndef HANK_ST_STATE
-#define HANK_ST_STATE 1
-#endif
-#ifndef HANK_ST_REC
-#define HANK_ST_REC 0
-#endif
-template <int MODE>
-__device__ __forceinline__ void st_mode(double *p, double x) {
-    if (MODE == 1) __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if (MODE == 2) __builtin_nontemporal_store(x, p);
-    else *p = x;
+// how the big streaming stores (policy partials, tangent state) leave the CU: sc1 write-through. The record's stores are plain.
+__device__ __forceinline__ void st_wt(double *p, double x) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // acc += sum_{k=k0}^{n-1} P[k*ps] * V[k*vs], added in index order. The n_e-long mixing sums sit on every launch's
@@ -129,19 +107,12 @@ __device__ __forceinline__ void vzero(double &v) { v = 0.0; }
 __device__ __forceinline__ void vzero(double2 &v) { v.x = 0.0; v.y = 0.0; }
 __device__ __forceinline__ double vshfl_xor(double v, int m) { return __shfl_xor(v, m, 64); }
 __device__ __forceinline__ double2 vshfl_xor(double2 v, int m) { return make_double2(__shfl_xor(v.x, m, 64), __shfl_xor(v.y, m, 64)); }
-template <int MODE>
-__device__ __forceinline__ void st_mode(double2 *p, double2 v) {
-    if (MODE == 1) {
-        // one 16-byte write-through store (there is no 16-byte atomic store to spell it with); the trailing
-        // s_nop keeps the compiler's next instruction off the data registers until the store has read them
-        typedef double d2_t __attribute__((ext_vector_type(2)));
-        d2_t d = {v.x, v.y};
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(d) : "memory");
-    } else if (MODE == 2) {
-        __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y);
-    } else {
-        *p = v;
-    }
+__device__ __forceinline__ void st_wt(double2 *p, double2 v) {
+    // one 16-byte write-through store (there is no 16-byte atomic store to spell it with); the trailing
+    // s_nop keeps the compiler's next instruction off the data registers until the store has read them
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    d2_t d = {v.x, v.y};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(d) : "memory");
 }
 __device__ __forceinline__ void lds_add(double *p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_add(double2 *p, double2 v) { lds_add(&p->x, v.x); lds_add(&p->y, v.y); }
@@ -250,7 +221,7 @@ __device__ inline void tan_back_body(const Consts &c, const Record &R, const dou
         vzero(dV);
         if (valid[q] && !first) {
             const VT dg = vadd(vmul(cA[q], d0[q]), vmul(cB[q], d1[q]));
-            st_mode<HANK_ST_DPOL>(&dpol[((size_t)t * c.G + (size_t)e * c.n_a + a[q]) * N + n], dg);
+            st_wt(&dpol[((size_t)t * c.G + (size_t)e * c.n_a + a[q]) * N + n], dg);
             dV = vadd(vmul(cu[q], dr), vmul(cv[q], vsub(vadd(vmul(xa[q], dr), vadd(vmul(ze, dw), dtr)), dg)));
         }
         dVsh[q][e * 64 + lane] = dV;
@@ -261,7 +232,7 @@ __device__ inline void tan_back_body(const Consts &c, const Record &R, const dou
     for (int q = 0; q < RG; q++) {
         if (valid[q]) {
             const VT dE = mix_sum(vmul(Pish[e], dVsh[q][lane]), &dVsh[q][lane], 64, Pish + e, c.n_e, 1, c.n_e);
-            st_mode<HANK_ST_STATE>(&dsOut[((size_t)e * c.n_a + a[q]) * N + n],
+            st_wt(&dsOut[((size_t)e * c.n_a + a[q]) * N + n],
                                    vsub(vmul(ck[q], dE), vmul(rho1, vadd(vadd(vmul(ze, dw1), dtr1), vmul(cs[q], dr1)))));
         }
     }
@@ -555,7 +526,7 @@ __device__ inline void tan_fwd_body(const Consts &c, const Record &R, const TanG
         if (valid[q]) {
             // dD_t[r,e] = sum_k dD_mid[r,k] * Pi[k,e]
             const VT dDn = mix_sum(vmul(Pish[c.n_e * e], sh[q][lane]), &sh[q][lane], 64, Pish + c.n_e * e, 1, 1, c.n_e);
-            st_mode<HANK_ST_STATE>(&dDout[((size_t)e * nav + r[q]) * N + n], dDn);
+            st_wt(&dDout[((size_t)e * nav + r[q]) * N + n], dDn);
             part = vadd(part, vmul(cp[q], dDn));
             part2 = vadd(part2, vmul(c.a[r[q] < na ? r[q] : 0], dDn));       // (a virtual row is a part of row 0)
             if constexpr (NX > 0) {

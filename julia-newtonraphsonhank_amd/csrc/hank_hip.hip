@@ -1083,7 +1083,7 @@ static int x_tan_front(XSection &sec, XTan *w) {
     }
     return HANK_OK;
 }
-// HANK_XADDR_BUF: the Dual-pass sweeps reach the record and dpol through buffer descriptors with 32-bit offsets, and the work units
+// The Dual-pass sweeps reach the record and dpol through buffer descriptors with 32-bit offsets, and the work units
 // (on their pointer) with a 32-bit index (hank_xsweep.h: XRecOff, hank_xaddr.h: x_addr_fits). The
 // record's offsets, and whether every stream of the widest Dual pass of this context fits (asked where the schedule is chosen:
 // a context that does not fit keeps the per-period launches, as one whose LDS does not fit does)
@@ -1098,7 +1098,6 @@ static XRecOff x_rec_off(const hank_ctx *ctx) {
     return o;
 }
 static bool x_dual_addr_fits(const hank_ctx *ctx) {
-    if (!HANK_XADDR_BUF_BACK && !HANK_XADDR_BUF_FWD) return true;
     const Consts &c = ctx->c;
     return x_addr_fits(ctx->rec_bytes, (unsigned long long)c.P, XG, (unsigned long long)c.G, XD_MAX, (unsigned long long)((c.n_a + XRW - 1) / XRW), XUCAP);
 }
@@ -1658,7 +1657,7 @@ static int x_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double
     x_rho(sec);
     rc = x_back(sec); if (rc) return rc;
     x_lottery(sec, true);
-    record_rewritten(ctx, true, HANK_XPRIMAL_LWG_IN_SWEEP);
+    record_rewritten(ctx, true, true);
     x_ensure_rng(sec);
     rc = x_fwd_value(sec); if (rc) return rc;
     HIPC(ctx, hipGetLastError());

@@ -43,36 +43,21 @@ __device__ inline bool pow_domain_error(double v, double y) {
 // on the critical path of a SIMD's three waves (the staircase at the tile barrier). EVERY primal
 // kernel takes its quotients and roots from here (egm_X / egm_Y / diet_v are shared), so k_egm_step, k_xprimal_back, k_xdual_back
 // and k_xvfi still agree with each other bit for bit.
-#ifndef HANK_IEEE_DIV
-#define HANK_IEEE_DIV 0     // dev knob: 1 = the IEEE forms (A/B, profiles/r05c_fast_div.log)
-#endif
 __device__ __forceinline__ double fast_rcp(double x) {
-#if HANK_IEEE_DIV
-    return 1.0 / x;
-#else
     double r = __builtin_amdgcn_rcp(x);
     r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
     r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
     return r;
-#endif
 }
 __device__ __forceinline__ double fast_rsqrt(double x) {
-#if HANK_IEEE_DIV
-    return 1.0 / sqrt(x);
-#else
     double y = __builtin_amdgcn_rsq(x);
     y = __builtin_fma(y * 0.5, __builtin_fma(-(x * y), y, 1.0), y);
     y = __builtin_fma(y * 0.5, __builtin_fma(-(x * y), y, 1.0), y);
     return y;
-#endif
 }
 __device__ __forceinline__ double fast_sqrt(double x) {     // x rsqrt(x), one correction of the product
-#if HANK_IEEE_DIV
-    return sqrt(x);
-#else
     const double y = fast_rsqrt(x), g = x * y;
     return __builtin_fma(y * 0.5, __builtin_fma(-g, g, x), g);
-#endif
 }
 
 // x^y with the exponents CRRA utility produces most often taken through a reciprocal / reciprocal square root
@@ -85,13 +70,6 @@ __device__ inline double pow_crra(double x, double y) {
     if (y == -2.0) return fast_rcp(x * x);
     if (y == -1.0) return fast_rcp(x);
     return pow(x, y);
-}
-
-template <int MODE>
-__device__ __forceinline__ void st_mode_i(int *p, int x) {
-    if (MODE == 1) __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if (MODE == 2) __builtin_nontemporal_store(x, p);
-    else *p = x;
 }
 
 // buffer accesses: ONE scalar descriptor for the whole record, a 32-bit lane offset (the row pair: shared by every array), a scalar
@@ -123,7 +101,7 @@ __device__ __forceinline__ void wide_st64_nt(double v, __amdgpu_buffer_rsrc_t rs
     __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, so, 2);
 }
 
-// the same with the cache mode as a parameter, for the persistent sweeps (hank_xsweep.h, HANK_XADDR_BUF). AUX: 0 plain, 2 nontemporal,
+// the same with the cache mode as a parameter, for the persistent sweeps' descriptor path (hank_xsweep.h). AUX: 0 plain, 2 nontemporal,
 // 16 sc1 (bypasses the CU's L1: served by the XCD's L2). The descriptor's size is the allocation's, but that is NO safety net: the
 // hardware's range check sees the lane offset and the immediate only, and the sweeps put array, period and column into the scalar
 // offset, which it does not see. A wrong scalar offset reads and writes wherever it points; what keeps the offsets right is
@@ -152,7 +130,6 @@ __device__ __forceinline__ void buf_st2d(double a, double b, __amdgpu_buffer_rsr
     q.x = (unsigned)__double2loint(a); q.y = (unsigned)__double2hiint(a); q.z = (unsigned)__double2loint(b); q.w = (unsigned)__double2hiint(b);
     __builtin_amdgcn_raw_buffer_store_b128(q, rs, vo, so, AUX);
 }
-constexpr int BUF_AUX_REC = HANK_ST_REC == 1 ? 16 : (HANK_ST_REC == 2 ? 2 : 0);      // the record stores' mode as a buffer access
 
 // RECORD DIET. Two of the seven coefficients a backward tangent step reads per point are functions of their neighbours in the
 // record: s = rho ((cm - (w z_e + tr)) + a) gives back cm, and kc = rho beta (-1/gamma) cm^(1 + gamma); u = cg^(-gamma) gives back
@@ -187,10 +164,10 @@ __device__ inline void egm_X(const Consts &c, const double *Vsh, const double *P
     const double cm = pow_crra(bE, ex);
     const double rho = 1.0 / (1.0 + r);
     const double s1 = rho * ((cm - (w * c.z[e] + tr)) + c.a[a]);
-    st_mode<HANK_ST_REC>(s_out, s1);
+    *s_out = s1;
     // d cmat/dE = beta*ex*(bE)^(ex-1)  (Dual^Real, ForwardDiff dual.jl:563-572); under the record diet the recorded value IS the
     // one the persistent tangent sweeps rebuild from s (diet_kc): whoever reads it and whoever rebuilds it hold the same bits
-    st_mode<HANK_ST_REC>(kc_out, c.diet ? diet_kc(c, s1, rho, 1.0 + r, w * c.z[e] + tr, c.a[a]) : rho * (c.beta * ex * (cm / bE)));
+    *kc_out = c.diet ? diet_kc(c, s1, rho, 1.0 + r, w * c.z[e] + tr, c.a[a]) : rho * (c.beta * ex * (cm / bE));
 }
 
 // Y half (KrusellSmith.jl:66-80): interpolate the policy on the exogenous grid point a from the
@@ -387,8 +364,8 @@ __device__ inline void egm_step_body(const Consts &c, const Record &R, const dou
         const int guess = (t + 1 < c.P) ? R.ib[base + c.G + (size_t)e * c.n_a + a] : -1;
         const YOut o = egm_Y(c, R.s + base + (size_t)e * c.n_a, a, e, r, w, tr, err, t, guess);
         const size_t off = base + (size_t)e * c.n_a + a;
-        st_mode<HANK_ST_REC>(&R.pol[off], o.g); st_mode_i<HANK_ST_REC>(&R.ib[off], o.ib); st_mode<HANK_ST_REC>(&R.A[off], o.A);
-        st_mode<HANK_ST_REC>(&R.B[off], o.B); st_mode<HANK_ST_REC>(&R.u[off], o.u); st_mode<HANK_ST_REC>(&R.v[off], o.v);
+        R.pol[off] = o.g; R.ib[off] = o.ib; R.A[off] = o.A;
+        R.B[off] = o.B; R.u[off] = o.u; R.v[off] = o.v;
         Vsh[e * RBP + row] = o.V;
     }
     lds_barrier();
@@ -466,7 +443,7 @@ __device__ inline void dist_step_body(const Consts &c, const Record &R, int t, d
         const int e2 = e;  // D_new[r,e2] = sum_e D_mid[r,e] * Pi[e,e2]
         double Dn = 0.0;
         Dn = mix_sum(Dn, Dsh + row, RBP, Pish + c.n_e * e2, 1, 0, c.n_e);
-        st_mode<HANK_ST_REC>(Dout ? &Dout[(size_t)e2 * n + r] : &R.Dseq[(size_t)(t + 1) * c.G + (size_t)e2 * n + r], Dn);
+        (Dout ? Dout[(size_t)e2 * n + r] : R.Dseq[(size_t)(t + 1) * c.G + (size_t)e2 * n + r]) = Dn;
         part = R.pol[base + (size_t)e2 * n + r] * Dn;
         part2 = c.a[r] * Dn;
     }

@@ -37,7 +37,7 @@ __device__ __forceinline__ double ss_abs(double v) { return fabs(v); }
 __device__ __forceinline__ double2 ss_abs(double2 v) { return make_double2(fabs(v.x), fabs(v.y)); }
 __device__ __forceinline__ double ss_max(double a, double b) { return fmax(a, b); }
 __device__ __forceinline__ double2 ss_max(double2 a, double2 b) { return make_double2(fmax(a.x, b.x), fmax(a.y, b.y)); }
-// the value this thread has just stored with st_mode (a write-through store): read where that store went
+// the value this thread has just stored with st_wt (a write-through store): read where that store went
 __device__ __forceinline__ double ss_ld(const double *p) {
     return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }

@@ -107,13 +107,6 @@ __device__ __forceinline__ void wide_mix(double (&x)[R][KR], double *lst, const 
 // (the buffer accesses — wide_rsrc, wide_ld*, wide_st* — live in hank_kernels.h: the persistent sweeps of hank_xsweep.h share them)
 
 // dev build only (make stamp): s_memtime of wave 0 / lane 0 of workgroup 0 at fixed points of periods [100, 104)
-// dev timing builds (wrong numbers): HANK_WIDE_TIMING_L2 confines the record to two periods (every line an L2 hit: what the HBM
-// latency of the record stream costs)
-#ifdef HANK_WIDE_TIMING_L2
-#define WIDE_TPER(t) ((t) & 1)
-#else
-#define WIDE_TPER(t) (t)
-#endif
 #ifdef HANK_XSTAMP
 __device__ unsigned long long g_wstamps[2][4][64];
 #define WSTAMP(sw, per, i)                                                                                          \
@@ -258,18 +251,16 @@ __global__ void __launch_bounds__(MAXT) k_wide_back(WideArgs A, WMat<NE> M) {
     const int tch_v4 = tch_line < tch_n4 ? tch_line : (int)0x80000000;
     unsigned tch_j8 = 0, tch_j4 = 0;
     __syncthreads();
-    { const int so = WIDE_TPER(P - 1) * G; load_X(so); load_Y1(so); load_Y2(so); }
+    { const int so = (P - 1) * G; load_X(so); load_Y1(so); load_Y2(so); }
     int pb = 0;
     for (int t = P - 1; t >= 0; t--) {
         WSTAMP(0, t, 0);
-#ifndef HANK_WIDE_NO_TOUCH
         asm volatile("" :: "v"(tch_j8), "v"(tch_j4));       // (last period's two: long landed)
         {
-            const int tb = WIDE_TPER(t > 0 ? t - 1 : 0) * G;
+            const int tb = (t > 0 ? t - 1 : 0) * G;
             tch_j8 = __builtin_amdgcn_raw_buffer_load_b32(rs, tch_v8, tb * 8, 0);
             tch_j4 = __builtin_amdgcn_raw_buffer_load_b32(rs_w, tch_v4, tb * 4, 0);
         }
-#endif
         // (uniform over the workgroup: scalar registers)
         const double rho = wide_uniform(uni[8 * t]), opr = wide_uniform(uni[8 * t + 1]), w = wide_uniform(uni[8 * t + 2]), tr = wide_uniform(uni[8 * t + 3]);
         const double dr = wide_uniform(uni[8 * t + 4]), dw = wide_uniform(uni[8 * t + 5]), dtr = wide_uniform(uni[8 * t + 6]);
@@ -282,7 +273,7 @@ __global__ void __launch_bounds__(MAXT) k_wide_back(WideArgs A, WMat<NE> M) {
 #pragma unroll
         for (int e = 0; e < NE; e++) {
             const int last = e + 1 == NE;
-            const int son = WIDE_TPER(last ? (t > 0 ? t - 1 : 0) : t) * G + (last ? 0 : e + 1) * na + zt;      // the next column (of the next period behind the last)
+            const int son = (last ? (t > 0 ? t - 1 : 0) : t) * G + (last ? 0 : e + 1) * na + zt;      // the next column (of the next period behind the last)
             const double ze = M.z[e], wz = w * ze + tr, zd = ze * dw + dtr;
             double2 *const col = buf + pb * CS;
             double ds[R];
@@ -386,7 +377,7 @@ __global__ void __launch_bounds__(MAXT) k_wide_fwd(WideArgs A, WMat<NE> M) {
 #pragma unroll
     for (int j = 0; j < R / 2; j++) so4[j] = (rw.ok[2 * j] ? max(rw.row[2 * j] - 1, 0) : 0) * 4;
     auto load_src = [&](int t, int e, int zt) {
-        const int pt = e * na + zt, so = WIDE_TPER(t) * G + pt;
+        const int pt = e * na + zt, so = t * G + pt;
         const __amdgpu_buffer_rsrc_t rs_dp = wide_rsrc(A.dpol + ((size_t)t * A.Ntot + n) * (size_t)G);
 #pragma unroll
         for (int j = 0; j < R / 2; j++) {
@@ -398,7 +389,7 @@ __global__ void __launch_bounds__(MAXT) k_wide_fwd(WideArgs A, WMat<NE> M) {
         }
     };
     auto load_seg = [&](int t, int e, int zt) {
-        const int so = ((WIDE_TPER(t) * NE + e) * (na + 1) + zt) * 4;
+        const int so = ((t * NE + e) * (na + 1) + zt) * 4;
 #pragma unroll
         for (int j = 0; j < R / 2; j++) {
             const wv4u v = wide_ld128(rs, so4[j], A.o_start + so);

@@ -1,5 +1,5 @@
 // hank_xaddr.h — plain C++ on integers, no device code: the one predicate the host asks before it lets the Dual-pass persistent sweeps
-// (hank_xsweep.h, HANK_XADDR_BUF) address their streams with 32-bit offsets. A CPU test compiles this header alone
+// (hank_xsweep.h) address their streams with 32-bit offsets. A CPU test compiles this header alone
 // (tests/test_xaddr_host.py).
 #pragma once
 

@@ -33,36 +33,6 @@
 // What was measured on the way (a dual kernel carrying value and partials together, a run-ahead wave, atomic-counter
 // barriers, ...) is in DESIGN.md section 4.
 #pragma once
-#ifndef HANK_XFWD_PRECOMBINE
-#define HANK_XFWD_PRECOMBINE 1     // k_xfwd: neighbouring lanes' parts for one tile row in one LDS add (dev knob: 0 = one add per part)
-#endif
-#ifndef HANK_XBACK_FRONT
-#define HANK_XBACK_FRONT 1         // persistent backward sweeps: the bracket of the usual cases by selects on the preloaded knots (dev knob: 0 = always the search)
-#endif
-#ifndef HANK_XBACK_ZREG
-#define HANK_XBACK_ZREG 1          // persistent backward sweeps: egm_Y's z_e from the register the kernel holds (dev knob: 0 = a global load per period)
-#endif
-#ifndef HANK_XADDR_BUF
-#define HANK_XADDR_BUF 1           // Dual-pass persistent sweeps: every stream through a few buffer descriptors, 32-bit offsets (dev knob: 0 = a 64-bit pointer per array)
-#endif
-#ifndef HANK_XADDR_BUF_BACK
-#define HANK_XADDR_BUF_BACK HANK_XADDR_BUF      // ... k_xdual_back's alone (dev knob: each sweep's descriptor path can be A/B-ed by itself)
-#endif
-#ifndef HANK_XADDR_BUF_FWD
-#define HANK_XADDR_BUF_FWD HANK_XADDR_BUF       // ... k_xfwd<D, true>'s alone
-#endif
-#ifndef HANK_XMIX_PEEL
-#define HANK_XMIX_PEEL 1           // xtile_mix: the first column by itself, the loop over the others holds the multiply-adds only (dev knob: 0 = the first-term select in every trip)
-#endif
-#ifndef HANK_XMIX_UNROLL
-#define HANK_XMIX_UNROLL 5         // ... columns per trip of that loop: n_e = 11 is two whole trips of five, no single-column trip left over (dev knob)
-#endif
-#ifndef HANK_XMIX_BATCH
-#define HANK_XMIX_BATCH 1          // ... a trip issues all its tile reads, then its multiply-adds (dev knob: 0 = `#pragma unroll`, the reads where the compiler's scheduler puts them)
-#endif
-#ifndef HANK_XFWD_ROWIDX
-#define HANK_XFWD_ROWIDX 1         // k_xfwd<D, true>, D > 0, on buffer descriptors: a unit's state-row index set with its record, the state loads unconditional (dev knob: 0 = computed behind the source poll, loads under `qon`)
-#endif
 #include "hank_kernels.h"
 #include "hank_xaddr.h"
 #include <type_traits>
@@ -130,7 +100,7 @@ struct XRows {
     __device__ __forceinline__ double load_one(size_t row, int k) const {            // slot k of a row (sc1, 8 bytes)
         return D == 1 ? xld(base + row) : xld(base + ((size_t)(k / 2) * plane + row) * 2 + (k & 1));
     }
-    // HANK_XADDR_BUF: the row index in two parts — the lane's (rv, 32-bit, often loop-invariant) and the wave's (rs_, scalar: ping-pong
+    // the descriptor path (k_xdual_back, k_xfwd<D, true>): the row index in two parts — the lane's (rv, 32-bit, often loop-invariant) and the wave's (rs_, scalar: ping-pong
     // half, group, column) — straight into the instruction's vector and scalar offsets. init_buf: a descriptor for D = 1 too
     static constexpr int RB = D == 1 ? 8 : 16;       // bytes of a row in one plane
     __device__ __forceinline__ void init_buf(double *p, int rows_total) {
@@ -182,7 +152,7 @@ __device__ __forceinline__ void xstore_row(double *p, const double *v) {
     }
 }
 template <int D>
-__device__ __forceinline__ void xstore_row_buf(__amdgpu_buffer_rsrc_t rs, int vo, int so, const double *v) {     // the same, HANK_XADDR_BUF
+__device__ __forceinline__ void xstore_row_buf(__amdgpu_buffer_rsrc_t rs, int vo, int so, const double *v) {     // the same through a buffer descriptor
     if (D == 1) {
         buf_st64<2>(v[0], rs, vo, so);
     } else {
@@ -209,7 +179,7 @@ __device__ __forceinline__ void xload_row_plain(const double *p, double *v) {  /
     }
 }
 
-// HANK_XADDR_BUF: a sweep-long wave-uniform integer whose TESTS are made anew where they are used (one s_cmp / s_bitcmp on one
+// The descriptor path's sweep-long wave-uniform integers: one whose TESTS are made anew where they are used (one s_cmp / s_bitcmp on one
 // scalar register). Left to itself the compiler hoists every test `k < ne`, `flags & bit` out of the period loop as a 64-bit lane
 // mask of its own: more of them than there are scalar registers, so each costs two v_readlane per period.
 __device__ __forceinline__ int xopaque(int v) { asm volatile("" : "+s"(v)); return v; }
@@ -359,7 +329,7 @@ __device__ __forceinline__ void xpublish(XSync *sy, int x, int c, unsigned episo
 // four knots around the guessed bracket — is fetched in ONE batch of independent loads up front: behind the branches
 // of the bracket search each of them would be a round trip of its own. Anything else (a gallop after a far move) is
 // loaded on demand.
-// BUF (HANK_XADDR_BUF, k_xdual_back): the column is reached through a buffer descriptor over the whole knot state — a 32-bit lane
+// BUF (k_xdual_back): the column is reached through a buffer descriptor over the whole knot state — a 32-bit lane
 // offset (the knot's index) and a scalar offset (ping-pong half, group, column) instead of a 64-bit address per load.
 template <bool BUF>
 struct XKnotsT {
@@ -438,8 +408,8 @@ struct XKnotsT {
 };
 using XKnots = XKnotsT<false>;
 
-template <bool BUF> struct YFrontOf<XKnotsT<BUF>> { static constexpr bool value = HANK_XBACK_FRONT != 0; };
-template <bool BUF> struct YColumnZOf<XKnotsT<BUF>> { static constexpr bool value = HANK_XBACK_ZREG != 0; };
+template <bool BUF> struct YFrontOf<XKnotsT<BUF>> { static constexpr bool value = true; };
+template <bool BUF> struct YColumnZOf<XKnotsT<BUF>> { static constexpr bool value = true; };
 
 __device__ __forceinline__ double xwave_sum(double v) {            // butterfly: every lane ends with the same sum, fixed order
 #pragma unroll
@@ -498,7 +468,6 @@ __device__ __forceinline__ void xtile_mix(const double *tl, const double *P, int
 #pragma unroll
         for (int q = 0; q < NS; q++) out[q] = FMA ? __builtin_fma(p, v[q], out[q]) : out[q] + p * v[q];
     };
-#if HANK_XMIX_PEEL
     // the first column by itself: with `k == 0 ? p * v : fma(p, v, out)` in the loop the compiler keeps the test in every trip — a
     // product and two selects per slot and column next to the multiply-add. The operands and their order are the same.
     {
@@ -509,10 +478,9 @@ __device__ __forceinline__ void xtile_mix(const double *tl, const double *P, int
         for (int q = 0; q < NS; q++) out[q] = p * v[q];
     }
     int k = 1;
-#if HANK_XMIX_BATCH
     // U columns per trip: every read of the trip is in flight before its first multiply-add (left to itself the scheduler does that
     // at `unroll 4`; at 5 it reuses the registers and waits for the LDS three times a trip), then single columns
-    constexpr int U = HANK_XMIX_UNROLL;
+    constexpr int U = 5;                                // (n_e = 11 is two whole trips, no single-column trip left over)
     for (; k + U <= ne; k += U) {
         double v[U][SL], p[U];
 #pragma unroll
@@ -522,29 +490,16 @@ __device__ __forceinline__ void xtile_mix(const double *tl, const double *P, int
         for (int u = 0; u < U; u++) acc(p[u], v[u]);
     }
 #pragma unroll 1
-#else
-#pragma unroll HANK_XMIX_UNROLL
-#endif
     for (; k < ne; k++) {
         double v[SL];
         rd(k, v);
         acc(P[k * ps], v);
     }
-#else
-#pragma unroll 4
-    for (int k = 0; k < ne; k++) {
-        double v[SL];
-        rd(k, v);
-        const double p = P[k * ps];
-#pragma unroll
-        for (int q = 0; q < NS; q++) out[q] = k == 0 ? p * v[q] : (FMA ? __builtin_fma(p, v[q], out[q]) : out[q] + p * v[q]);
-    }
-#endif
 }
 
 // the same with the column of Pi held in registers (16 unrolled steps, the ones beyond n_e predicated off): no LDS read for
 // the coefficient, and every tile read of the pass can be in flight at once
-// BRK (HANK_XADDR_BUF; the caller passes xopaque(ne)): the pass ends at the first k >= ne — one scalar compare per step on one
+// BRK (the descriptor path; the caller passes xopaque(ne)): the pass ends at the first k >= ne — one scalar compare per step on one
 // register, where the sixteen hoisted predicates `k < ne` are sixteen spilled lane masks (two v_readlane each, every period)
 // NK: the coefficients held (16; a kernel instance compiled for its n_e holds exactly n_e and passes ne = NK as a literal with
 // BRK off: NK straight-line steps, no predicate and no compare)
@@ -570,7 +525,7 @@ __device__ __forceinline__ void xtile_mix_reg(const double *tl, const double (&p
 // ================================ the Float64 sweeps ==========================================
 // One group (the XCD with id 0) runs them; the workgroups that landed elsewhere leave at once. They write the policy
 // sequence, the distribution path and the linearisation record the tangent sweeps — of either implementation — read.
-// HANK_XADDR_BUF: where the record's arrays start in its ONE allocation (bytes): an access is descriptor + 32-bit lane offset +
+// The descriptor path: where the record's arrays start in its ONE allocation (bytes): an access is descriptor + 32-bit lane offset +
 // scalar offset (array + period) instead of a 64-bit base per array — more bases than a wave has scalar registers
 struct XRecOff {
     const char *rec;
@@ -1175,7 +1130,7 @@ struct XDualBackArgs {
     double *st_ds;              // [2][XG][G][D]
     double *dpol;               // [P][groups][G][D]
     int groups;
-    XRecOff ro;                 // HANK_XADDR_BUF: the record's allocation and its arrays' offsets in it ...
+    XRecOff ro;                 // the record's allocation and its arrays' offsets in it ...
     unsigned dpol_bytes;        // ... and this launch's dpol in bytes (x_addr_fits has checked that 32-bit offsets reach everything)
 };
 
@@ -1186,7 +1141,6 @@ struct XDualBackArgs {
 template <int D, int MAXT, int NE = 0, int CRRA = 0>
 __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     constexpr int NSL = D + 1, SL = XSlots<NSL>::SL, IV = D;
-    constexpr bool XB = HANK_XADDR_BUF_BACK != 0;            // streams through buffer descriptors (see XRecOff)
     extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_dual_back (under this kernel) is the host's sum of the same pieces
     const XBackArgs &A = B.p;
     const Consts &c = A.c;
@@ -1237,14 +1191,14 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     Consts cl = c;
     cl.a = ash;
     const double ze = c.z[e], xa = c.a[own ? a : 0];
-    const size_t hs = (size_t)XG * G, gx = (size_t)x * G;
+    const size_t hs = (size_t)XG * G;
     double *const sS = A.st_s;
     XRows<D> rows;
-    if constexpr (XB) rows.init_buf(B.st_ds, 2 * XG * G); else rows.init(B.st_ds, 2 * hs);
-    // XB: four descriptors (record, dpol, knots, partials) instead of a dozen 64-bit bases; this lane's row as ONE loop-invariant
+    rows.init_buf(B.st_ds, 2 * XG * G);
+    // Every stream goes through a buffer descriptor (see XRecOff): four descriptors (record, dpol, knots, partials) instead of a
+    // dozen 64-bit bases; this lane's row as ONE loop-invariant
     // element index (every array's lane offset is that times the element size); the writer flags as one mask in one scalar register
-    __amdgpu_buffer_rsrc_t rrec, rdp, rkn;
-    if constexpr (XB) { rrec = buf_rsrc(B.ro.rec, B.ro.bytes); rdp = buf_rsrc(B.dpol, B.dpol_bytes); rkn = buf_rsrc(sS, (unsigned)(2 * hs * 8)); }
+    const __amdgpu_buffer_rsrc_t rrec = buf_rsrc(B.ro.rec, B.ro.bytes), rdp = buf_rsrc(B.dpol, B.dpol_bytes), rkn = buf_rsrc(sS, (unsigned)(2 * hs * 8));
     const int ipt = (int)pt, igx = x * G, ihs = XG * G;
     const int rcm0 = __builtin_amdgcn_readfirstlane((rc0 ? 1 : 0) | (rc1 ? 2 : 0) | (rc2 ? 4 : 0) | (rc3 ? 8 : 0) | (rc4 ? 16 : 0) | (rc5 ? 32 : 0) | (rc6 ? 64 : 0) | (rc7 ? 128 : 0));
     double *const myt = tile + ((size_t)e * 64 + lane) * SL;
@@ -1272,17 +1226,14 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
 #pragma unroll
             for (int k = 0; k < NSL; k++) tv[k] = 0.0;
             if (own) {
-                XKnotsT<XB> kn;
-                const int icb = cur * ihs + igx + e * na;          // this column in the state half being read (elements; wave-uniform); `rb` below is the pointer path's
-                if constexpr (XB) kn.preload(rkn, icb * 8, a, na, guess, ze);
-                else kn.preload(sS + (size_t)cur * hs + gx + (size_t)e * na, a, na, guess, ze);
+                XKnotsT<true> kn;
+                const int icb = cur * ihs + igx + e * na;          // this column in the state half being read (elements; wave-uniform)
+                kn.preload(rkn, icb * 8, a, na, guess, ze);
                 // the partials' rows at the bracket of the period before, in the same batch of loads as the knots: the bracket
                 // rarely moves by more than a knot per period, and behind the search every gather is a round trip of its own
-                const size_t rb = (size_t)cur * hs + gx + (size_t)e * na;
                 const int q = guess < 0 ? 0 : (guess < na - 1 ? guess : na - 2);
                 double w0[D], w1[D];
-                if constexpr (XB) { rows.load_vs(q, icb, w0); rows.load_vs(q + 1, icb, w1); }
-                else { rows.load(rb + q, w0); rows.load(rb + q + 1, w1); }
+                rows.load_vs(q, icb, w0); rows.load_vs(q + 1, icb, w1);
                 const YOut o = egm_Y<CRRA>(cl, kn, a, e, xsh[4 * t], xsh[4 * t + 1], xsh[4 * t + 2], A.err, t, guess);
                 guess = o.ib;
                 tv[IV] = o.V;
@@ -1298,14 +1249,13 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                     } else if (o.ib == q + 1) {
 #pragma unroll
                         for (int k = 0; k < D; k++) d0[k] = w1[k];
-                        if constexpr (XB) rows.load_vs(o.ib + 1, icb, d1); else rows.load(rb + o.ib + 1, d1);
+                        rows.load_vs(o.ib + 1, icb, d1);
                     } else if (o.ib == q - 1) {
 #pragma unroll
                         for (int k = 0; k < D; k++) d1[k] = w0[k];
-                        if constexpr (XB) rows.load_vs(o.ib, icb, d0); else rows.load(rb + o.ib, d0);
+                        rows.load_vs(o.ib, icb, d0);
                     } else {
-                        if constexpr (XB) { rows.load_vs(o.ib, icb, d0); rows.load_vs(o.ib + 1, icb, d1); }
-                        else { rows.load(rb + o.ib, d0); rows.load(rb + o.ib + 1, d1); }
+                        rows.load_vs(o.ib, icb, d0); rows.load_vs(o.ib + 1, icb, d1);
                     }
                 }
 #pragma unroll
@@ -1314,25 +1264,14 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                     dg[k] = o.A * d0[k] + o.B * d1[k];
                     tv[k] = o.u * dr + o.v * ((xa * dr + (ze * dw + dtr)) - dg[k]);
                 }
-                if constexpr (XB) {
-                    xstore_row_buf<D>(rdp, ipt * (8 * D), (int)((unsigned)((t * B.groups + x) * G) * (unsigned)(8 * D)), dg);
-                    const int tg = t * G, rcm = xopaque(rcm0);
-                    if (rcm & 1) buf_st64<BUF_AUX_REC>(o.g, rrec, ipt * 8, (int)(B.ro.pol + (unsigned)tg * 8u));
-                    if (rcm & 2) buf_st32<BUF_AUX_REC>(o.ib, rrec, ipt * 4, (int)(B.ro.ib + (unsigned)tg * 4u));
-                    if (rcm & 4) buf_st64<BUF_AUX_REC>(o.A, rrec, ipt * 8, (int)(B.ro.A + (unsigned)tg * 8u));
-                    if (rcm & 8) buf_st64<BUF_AUX_REC>(o.B, rrec, ipt * 8, (int)(B.ro.B + (unsigned)tg * 8u));
-                    if (rcm & 16) buf_st64<BUF_AUX_REC>(o.u, rrec, ipt * 8, (int)(B.ro.u + (unsigned)tg * 8u));
-                    if (rcm & 32) buf_st64<BUF_AUX_REC>(o.v, rrec, ipt * 8, (int)(B.ro.v + (unsigned)tg * 8u));
-                } else {
-                    xstore_row<D>(B.dpol + (((size_t)t * B.groups + x) * G + pt) * D, dg);
-                    const size_t ro = (size_t)t * G + pt;
-                    if (rc0) A.R.pol[ro] = o.g;
-                    if (rc1) A.R.ib[ro] = o.ib;
-                    if (rc2) A.R.A[ro] = o.A;
-                    if (rc3) A.R.B[ro] = o.B;
-                    if (rc4) A.R.u[ro] = o.u;
-                    if (rc5) A.R.v[ro] = o.v;
-                }
+                xstore_row_buf<D>(rdp, ipt * (8 * D), (int)((unsigned)((t * B.groups + x) * G) * (unsigned)(8 * D)), dg);
+                const int tg = t * G, rcm = xopaque(rcm0);
+                if (rcm & 1) buf_st64<0>(o.g, rrec, ipt * 8, (int)(B.ro.pol + (unsigned)tg * 8u));
+                if (rcm & 2) buf_st32<0>(o.ib, rrec, ipt * 4, (int)(B.ro.ib + (unsigned)tg * 4u));
+                if (rcm & 4) buf_st64<0>(o.A, rrec, ipt * 8, (int)(B.ro.A + (unsigned)tg * 8u));
+                if (rcm & 8) buf_st64<0>(o.B, rrec, ipt * 8, (int)(B.ro.B + (unsigned)tg * 8u));
+                if (rcm & 16) buf_st64<0>(o.u, rrec, ipt * 8, (int)(B.ro.u + (unsigned)tg * 8u));
+                if (rcm & 32) buf_st64<0>(o.v, rrec, ipt * 8, (int)(B.ro.v + (unsigned)tg * 8u));
             }
             if (!syncw) xtile_store_n<SL, NSL>(myt, tv);
             XSTAMP(0, son, i, 2);
@@ -1346,10 +1285,10 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                 double mx[NSL];
                 // (next to the generic powers' arms, 11 columns of D = 4 partials as straight-line code spill 37 VGPRs: that one instance
                 // keeps the step-by-step form on its 11 coefficients)
-                constexpr bool STEPS = XB && CRRA == 0 && NE * ((NSL + 1) / 2) > 24;
+                constexpr bool STEPS = CRRA == 0 && NE * ((NSL + 1) / 2) > 24;
                 if constexpr (NE > 0 && STEPS) xtile_mix_reg<SL, NSL, false, true, NK>(tile + (size_t)lane * SL, pr, xopaque(NE), mx);
                 else if constexpr (NE > 0) xtile_mix_reg<SL, NSL, false, false, NK>(tile + (size_t)lane * SL, pr, NE, mx);
-                else xtile_mix_reg<SL, NSL, false, XB>(tile + (size_t)lane * SL, pr, XB ? xopaque(ne) : ne, mx);
+                else xtile_mix_reg<SL, NSL, false, true>(tile + (size_t)lane * SL, pr, xopaque(ne), mx);
                 const double bE = mx[IV] * c.beta;
                 const double ex = CRRA == 1 ? -0.5 : -1.0 / c.gamma;
                 if (pow_domain_error<CRRA>(bE, ex)) set_err(A.err, ERR_DOMAIN, tx, e, a);
@@ -1363,18 +1302,11 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                     const double dr1 = dxsh[(tx * 3 + 0) * D + k], dw1 = dxsh[(tx * 3 + 1) * D + k], dt1 = dxsh[(tx * 3 + 2) * D + k];
                     ds[k] = kc * mx[k] - rho * ((ze * dw1 + dt1) + s1 * dr1);
                 }
-                if constexpr (XB) {
-                    const int ihb = (i & 1) * ihs + igx, rcm = xopaque(rcm0);
-                    buf_st64<0>(s1, rkn, ipt * 8, ihb * 8);
-                    rows.store_vs(ipt, ihb, ds);
-                    if (rcm & 64) buf_st64<BUF_AUX_REC>(s1, rrec, ipt * 8, (int)(B.ro.s + (unsigned)(tx * G) * 8u));
-                    if (rcm & 128) buf_st64<BUF_AUX_REC>(kc, rrec, ipt * 8, (int)(B.ro.kc + (unsigned)(tx * G) * 8u));
-                } else {
-                    sS[(size_t)(i & 1) * hs + gx + pt] = s1;
-                    rows.store((size_t)(i & 1) * hs + gx + pt, ds);
-                    if (rc6) A.R.s[(size_t)tx * G + pt] = s1;
-                    if (rc7) A.R.kc[(size_t)tx * G + pt] = kc;
-                }
+                const int ihb = (i & 1) * ihs + igx, rcm = xopaque(rcm0);
+                buf_st64<0>(s1, rkn, ipt * 8, ihb * 8);
+                rows.store_vs(ipt, ihb, ds);
+                if (rcm & 64) buf_st64<0>(s1, rrec, ipt * 8, (int)(B.ro.s + (unsigned)(tx * G) * 8u));
+                if (rcm & 128) buf_st64<0>(kc, rrec, ipt * 8, (int)(B.ro.kc + (unsigned)(tx * G) * 8u));
             }
             episode++;
             XSTAMP(0, son, i, 4);
@@ -1409,9 +1341,6 @@ static inline size_t x_lds_dual_back(const Consts &c, int D) { return sizeof(dou
 // The mass kept on the members' virtual rows travels as extra lanes of the unit that walks source row 0 of an open column
 // (same lottery record, the members' virtual rows as state rows): no special sums. The mass point itself needs no load at
 // all: a member's clamped rows and its virtual row are its own rows of the previous period — its own registers.
-#ifndef HANK_XPRIMAL_LWG_IN_SWEEP
-#define HANK_XPRIMAL_LWG_IN_SWEEP 1     // dev knob, 0: the Float64 sweep (k_xfwd<0, true>) leaves the per-source record to k_xlwg_build too
-#endif
 constexpr int XUCAP = 64;       // work units per member and period (k_xunits_fwd reports an overflow; the host then uses the launches)
 struct XSweepFwdArgs {
     Consts c;
@@ -1428,7 +1357,7 @@ struct XSweepFwdArgs {
     const int *overflow;        // k_xunits_fwd's flag: a member's walk did not fit XUCAP units — nothing is computed from a truncated list
     const int2 *units;          // [P][members][XUCAP] {e | ja << 4 | cnt << 16, ta | tb << 8 | nv << 16}
     int all_members;            // dev knob: every period waits for every member
-    XRecOff ro;                 // HANK_XADDR_BUF (VAL, D > 0): the record's allocation and its arrays' offsets in it ...
+    XRecOff ro;                 // VAL, D > 0: the record's allocation and its arrays' offsets in it ...
     unsigned dpol_bytes;        // ... and this launch's dpol in bytes (x_addr_fits has checked that 32-bit offsets reach everything). The work units
                                 // keep their POINTER and take a 32-bit scalar index: a unit's address is wave-uniform, a third buffer resource only added spills
 };
@@ -1441,7 +1370,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     constexpr int IV = D;                               // the value's slot
     constexpr int DD = D > 0 ? D : 1;
     constexpr bool PIREG = NSL < 4;                     // the mixing's coefficients in registers
-    constexpr bool XB = HANK_XADDR_BUF_FWD != 0 && VAL && D > 0;      // the Dual pass: streams through buffer descriptors (see XRecOff)
+    constexpr bool XB = VAL && D > 0;                   // the Dual pass: streams through buffer descriptors (see XRecOff)
     extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_fwd (under this kernel) is the host's sum of the same pieces
     const Consts &c = A.c;
     const Record &R = A.R;
@@ -1471,7 +1400,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     // one group) also writes the per-source record {w, ig D_{t-1}} — whose row 0 needs every member's virtual row, i.e. member 0
     // waits for everybody; the Dual pass (D >= 1) leaves that record to k_xlwg_build: its two own-row loads were dead in seven
     // groups of eight, and the all-member wait of its row 0 sat in the period's latency chain
-    constexpr bool RECL = VAL && D == 0 && HANK_XPRIMAL_LWG_IN_SWEEP;
+    constexpr bool RECL = VAL && D == 0;
     const bool recD = VAL && x == 0, recL = RECL && x == 1 % A.groups;       // (one group: group 0)
     for (int k = threadIdx.x; k < ne * ne; k += blockDim.x) Pish[k] = c.Pi[k];
     for (int k = threadIdx.x; k < P * ne; k += blockDim.x) closh[k] = R.clo[k];
@@ -1529,16 +1458,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     double polr = 0.0, Dr = 0.0, lwr = 0.0, igr = 0.0, dpr[DD];
 #pragma unroll
     for (int k = 0; k < DD; k++) dpr[k] = 0.0;
-    // dev timing build (wrong numbers): -DHANK_X_TIMING_L2=<mask> confines what a period READS of an input stream to two periods —
-    // every such load an L2 / Infinity-Cache hit: what the HBM latency of that stream costs the sweep. Bits: 1 the units' lottery
-    // record, 2 the units' policy partials, 4 the own-row batch, 8 the unit descriptors (7 = every record and partial load)
-#ifdef HANK_X_TIMING_L2
-#define XTPER(bit, t) ((((HANK_X_TIMING_L2) >> (bit)) & 1) ? ((t) & 1) : (t))
-#else
-#define XTPER(bit, t) (t)
-#endif
-    auto prefetch = [&](int t_) {
-        const int t = XTPER(2, t_);
+    auto prefetch = [&](int t) {
         if constexpr (XB) {
             polr = buf_ld64<0>(rrec, ipt * 8, (int)(A.ro.pol + (unsigned)(t * G) * 8u));
             xload_row_buf<DD>(rdp, ipt * (8 * D), (int)((unsigned)((t * A.groups + x) * G) * (unsigned)(8 * D)), dpr);
@@ -1556,10 +1476,9 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     int qlo[2];
     double qw[2], qg[2], qdn[2], qdp[2][DD], dd[2][SP];
     bool qon[2], qvl[2];
-    // ROWIDX (HANK_XFWD_ROWIDX, the descriptor path): a unit's state row within its column, set by load_rec — a period before the
+    // qrow (the descriptor path): a unit's state row within its column, set by load_rec — a period before the
     // state is read, in the mixing phase's shadow — so that nothing but scalar setup stands between the barrier behind the source
     // poll and the state loads. A lane that is off reads row 0 of the unit's column (in range; process_* gate on qon / doL / doH)
-    constexpr bool ROWIDX = XB && HANK_XFWD_ROWIDX != 0;
     int qrow[2] = {0, 0};
     const int2 *const ubase = A.units + (size_t)cW * XUCAP;       // (the pointer path; XB: unit_ld)
     auto unit_ld = [&](int tu, int u) -> int2 {         // XB: a descriptor's address is wave-uniform — a scalar base and a 32-bit scalar index, no lane arithmetic
@@ -1567,15 +1486,13 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     };
     auto unit_desc = [&](int t, int u) -> int2 {        // unit u of this member in period t (u wave-uniform): broadcast load -> scalar registers
         int2 q;
-        if constexpr (XB) q = unit_ld(XTPER(3, t), u); else q = ubase[(size_t)XTPER(3, t) * Sact * XUCAP + u];
+        if constexpr (XB) q = unit_ld(t, u); else q = ubase[(size_t)t * Sact * XUCAP + u];
         return make_int2(__builtin_amdgcn_readfirstlane(q.x), __builtin_amdgcn_readfirstlane(q.y));
     };
     // (branch-free: every lane loads — a lane beyond the unit's sources the unit's last row, an empty unit row 0 of column 0 — and
     // qon / qvl say what counts)
-    auto load_rec = [&](auto U, int t_, int2 d, int i0) {
+    auto load_rec = [&](auto U, int t, int2 d, int i0) {
         constexpr int u = decltype(U)::value;
-        const int t = XTPER(0, t_), tp = XTPER(1, t_);
-        (void)tp;
         const int ue = d.x & 15, ja = (d.x >> 4) & 0xfff, cnt = (d.x >> 16) & 0xfff, nv = (d.y >> 16) & 0xff;
         const int i = i0 + lane;
         const bool real = i < cnt;
@@ -1585,17 +1502,17 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         const int j = real ? ja + i : (qvl[u] ? 0 : min(ja + max(cnt - 1, 0), na - 1));
         if constexpr (XB) {
             const int icb = t * G + ue * na;            // the unit's column in period t (elements; wave-uniform)
-            if constexpr (ROWIDX) qrow[u] = qvl[u] ? (i - cnt) * 64 + 63 : (real ? (j / XRW) * 64 + j % XRW : 0);
+            qrow[u] = qvl[u] ? (i - cnt) * 64 + 63 : (real ? (j / XRW) * 64 + j % XRW : 0);
             qlo[u] = buf_ld32<0>(rrec, j * 4, (int)(A.ro.lo + (unsigned)icb * 4u));
             qw[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.lw + (unsigned)icb * 8u));
             qg[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.ig + (unsigned)icb * 8u));
-            xload_row_buf<DD>(rdp, j * (8 * D), (int)((unsigned)((tp * A.groups + x) * G + ue * na) * (unsigned)(8 * D)), qdp[u]);
+            xload_row_buf<DD>(rdp, j * (8 * D), (int)((unsigned)((t * A.groups + x) * G + ue * na) * (unsigned)(8 * D)), qdp[u]);
             return;
         }
         qlo[u] = R.lo[cb + j];
-        if constexpr (VAL) { qw[u] = R.lw[cb + j]; if constexpr (D > 0) qg[u] = R.ig[cb + j]; }       // (ig only weights the policy partials)
+        if constexpr (VAL) qw[u] = R.lw[cb + j];        // (D = 0: ig only weights the policy partials)
         else { const double2 wg = R.lwg[cb + j]; qw[u] = wg.x; qg[u] = wg.y; if constexpr (D > 0) qdn[u] = R.Dseq[cb + G + j]; }
-        if constexpr (D > 0) xload_row_plain<DD>(A.dpol + (((size_t)tp * A.groups + x) * G + (size_t)ue * na + j) * D, qdp[u]);
+        if constexpr (D > 0) xload_row_plain<DD>(A.dpol + (((size_t)t * A.groups + x) * G + (size_t)ue * na + j) * D, qdp[u]);
     };
     auto load_state = [&](auto U, size_t hb, int hc, int2 d, int i0) {       // hc: the state half being read (hb = hc * hs)
         constexpr int u = decltype(U)::value;
@@ -1603,13 +1520,8 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #pragma unroll
         for (int k = 0; k < SP; k++) dd[u][k] = 0.0;
         const int i = i0 + lane, j = ja + i;
-        if constexpr (ROWIDX) {
-            rows.load_vs(qrow[u], hc * ihs + igx + ue * Sact * 64, dd[u]);        // unconditional: the compiler counts the loads in flight
-            return;
-        }
         if constexpr (XB) {
-            const int rowi = qvl[u] ? (i - cnt) * 64 + 63 : (j / XRW) * 64 + j % XRW;       // within the unit's column
-            if (qon[u]) rows.load_vs(rowi, hc * ihs + igx + ue * Sact * 64, dd[u]);
+            rows.load_vs(qrow[u], hc * ihs + igx + ue * Sact * 64, dd[u]);        // unconditional: the compiler counts the loads in flight
             return;
         }
         const size_t row = qvl[u] ? ((size_t)ue * Sact + (i - cnt)) * 64 + 63 : ((size_t)ue * Sact + j / XRW) * 64 + j % XRW;
@@ -1621,14 +1533,14 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     bool udv[2] = {false, false};                       // ... and whether this wave has such a unit at all
     udn[0] = udn[1] = make_int2(0, 0);
     auto request_units = [&](int t) {                   // this wave's two units of period t (branch-free: an index that exists is loaded anyway)
-        const int tc = min(t, P - 1), tu = XTPER(3, tc);
-        int nu = (srcsh[tu] >> 18) & 0xff;              // (tu == tc but in the timing build: the count belongs to the descriptors)
+        const int tc = min(t, P - 1);
+        int nu = (srcsh[tc] >> 18) & 0xff;
         nu = t < P ? nu : 0;
         udv[0] = wv < nu; udv[1] = wv + ne < nu;
-        if constexpr (XB) { udn[0] = unit_ld(tu, udv[0] ? wv : 0); udn[1] = unit_ld(tu, udv[1] ? wv + ne : 0); }
+        if constexpr (XB) { udn[0] = unit_ld(tc, udv[0] ? wv : 0); udn[1] = unit_ld(tc, udv[1] ? wv + ne : 0); }
         else {
-            udn[0] = ubase[(size_t)tu * Sact * XUCAP + (udv[0] ? wv : 0)];
-            udn[1] = ubase[(size_t)tu * Sact * XUCAP + (udv[1] ? wv + ne : 0)];
+            udn[0] = ubase[(size_t)tc * Sact * XUCAP + (udv[0] ? wv : 0)];
+            udn[1] = ubase[(size_t)tc * Sact * XUCAP + (udv[1] ? wv + ne : 0)];
         }
     };
     auto take_units = [&]() {
@@ -1726,9 +1638,6 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             // Young lottery of a source (ForwardIteration.jl:59-73): (1-w) to row lo, w to row lo+1; the weight's partial is
             // dpol / gap (zero where clamped), times D_{t-1} of the row. Only the parts that land in the unit's own target run
             // [ta, tb) are added (the other part of a seam source belongs to the neighbouring unit).
-#ifdef HANK_DEV_NOATOMIC      // timing experiment only (wrong numbers): what the same-address serialisation of the LDS adds costs
-#define lds_add(p, v) (*(p) = (v))
-#endif
             // PRE-COMBINE (round 5). The sources of a unit are consecutive lanes and their brackets rise with them: where the policy moves
             // one grid row per source row — most of the grid — the upper part of lane i-1 and the lower part of lane i land on the SAME
             // tile row. Lane i then adds both in one ds_add_f64 (the neighbour's part arrives by a wave_shr:1 DPP move) and lane i-1
@@ -1799,19 +1708,12 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             };
             // (narrow kernels — one or two slots per tile row — keep one add per part: at D = 1 the exchange costs more than the
             // one atomic it saves, single-tangent JVP 1.98 -> 2.06 ms)
-            constexpr bool PRECOMB = HANK_XFWD_PRECOMBINE && (D + (VAL ? 1 : 0)) >= 3;
+            constexpr bool PRECOMB = NSL >= 3;
             auto process = [&](auto U, int2 d) { if constexpr (PRECOMB) process_pc(U, d); else process_1(U, d); };
             process(I0, ud[0]);
             process(I1, ud[1]);
-#ifdef HANK_DEV_NOATOMIC
-#undef lds_add
-#endif
             // (rare) a unit wider than a wave — more than 64 sources on ONE target row — and units beyond the member's 2 n_e slots
-#ifdef HANK_X_TIMING_L2
-            const int nu = (srcsh[XTPER(3, t)] >> 18) & 0xff;      // (the count belongs to the descriptors)
-#else
             const int nu = (sw >> 18) & 0xff;
-#endif
             for (int u2 = wv; u2 < nu; u2 += ne) {
                 const int2 d = u2 < 2 * ne ? ud[u2 >= ne ? 1 : 0] : unit_desc(t, u2);
                 const int tot = ((d.x >> 16) & 0xfff) + ((d.y >> 16) & 0xff);
@@ -1871,7 +1773,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             if constexpr (VAL) {
                 if (recD) {
                     if (own) {
-                        if constexpr (XB) buf_st64<BUF_AUX_REC>(mx[IV], rrec, ipt * 8, (int)(A.ro.Dseq + (unsigned)((t + 1) * G) * 8u));
+                        if constexpr (XB) buf_st64<0>(mx[IV], rrec, ipt * 8, (int)(A.ro.Dseq + (unsigned)((t + 1) * G) * 8u));
                         else R.Dseq[(size_t)(t + 1) * G + pt] = mx[IV];
                     } else if (virt) A.Dvirt[((size_t)t * ne + e) * 64 + cW] = mx[IV];
                     // aggregate on the POST-transition distribution (ForwardIteration.jl:301-307); a virtual row carries row 0's policy

@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """dev: which kernels of the two gfx950 code objects differ between two source trees (profiles/ssdiff_unit_isa_diff.txt; no GPU).
 
-    python scripts/dev_isa_diff.py OLD_TREE NEW_TREE [--keep DIR]
+    python scripts/dev_isa_diff.py OLD_TREE NEW_TREE [--keep DIR] [--flag=-DNAME ...]
 
-Each unit (csrc/hank_hip.hip, csrc/hank_ssdiff.hip) of each tree is compiled with the Makefile's flags plus -S --cuda-device-only.
+Each unit (csrc/hank_hip.hip, csrc/hank_ssdiff.hip) of each tree is compiled with the Makefile's flags (and every --flag, e.g. --flag=-DHANK_XSTAMP for
+the instrumented build) plus -S --cuda-device-only.
 The assembly is split at the kernel labels; comments and assembler directives are dropped; the function number in local labels
 (.LBB<n>_) and the namespace of a unit that renames it (_ZN8hank_ssd -> _ZN4hank) are normalised. What remains of a kernel is its
 instructions and labels: the names whose text differs are printed with their resource lines (registers, scratch — a spill shows
@@ -68,8 +69,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("old")
     ap.add_argument("new")
+    ap.add_argument("--flag", action="append", default=[], help="one more compiler flag for both trees (repeatable)")
     ap.add_argument("--keep", help="leave the four assembly files in this directory, and reuse those already there")
     a = ap.parse_args()
+    FLAGS.extend(a.flag)
     d = Path(a.keep) if a.keep else Path(tempfile.mkdtemp())
     d.mkdir(parents=True, exist_ok=True)
     jobs = [(tree, u, d / f"{tag}_{u}.s") for tag, tree in (("old", a.old), ("new", a.new)) for u in UNITS]

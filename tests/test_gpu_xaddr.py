@@ -1,5 +1,5 @@
 """The Dual-pass persistent sweeps (k_xdual_back, k_xfwd<D, true>) address the record, dpol and the state through buffer
-descriptors with 32-bit offsets (HANK_XADDR_BUF, hank_xsweep.h). Addressing can go wrong where a member is short, where a group
+descriptors with 32-bit offsets (XRecOff, hank_xsweep.h). Addressing can go wrong where a member is short, where a group
 writes several record arrays or none, where a column's offset and a row's offset meet, and in the rows of the mass point — so
 every case runs hank_primal_jvp under HANK_SCHEDULE=xcd and under HANK_SCHEDULE=launch on the same inputs:
   * policies and their partials (the dpol export) bit-identical between the two;

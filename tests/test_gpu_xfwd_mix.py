@@ -1,8 +1,8 @@
 """The forward Dual-pass sweep's mixing loop and state-row index (k_xfwd<4, ...> in hank_xsweep.h) at every shape they take.
 
-xtile_mix takes its first column by itself, the others in trips of HANK_XMIX_UNROLL = 5 columns and what is left one column at
-a time (HANK_XMIX_PEEL); k_xfwd<D, true> sets a unit's state-row index `(j / 63) * 64 + j % 63` with the unit's record and loads
-the state rows unconditionally (HANK_XFWD_ROWIDX). So the cases are
+xtile_mix takes its first column by itself (the peeled first term), the others in trips of U = 5 columns and what is left one
+column at a time; k_xfwd<D, true> sets a unit's state-row index `(j / 63) * 64 + j % 63` with the unit's record (`qrow`, set by
+load_rec) and loads the state rows unconditionally. So the cases are
 
   n_e = 1       the first term only, neither loop entered
   n_e = 2       one single-column trip

@@ -1,5 +1,5 @@
 """The Dual-pass persistent sweeps reach the record and a launch's dpol through buffer descriptors with 32-bit offsets, and the work
-units (which keep their pointer) with a 32-bit index (HANK_XADDR_BUF, hank_xsweep.h). x_addr_fits (hank_xaddr.h) is the ONE
+units (which keep their pointer) with a 32-bit index (XRecOff and unit_ld, hank_xsweep.h). x_addr_fits (hank_xaddr.h) is the ONE
 predicate the host asks where it chooses the schedule: every stream's bytes, plus room for the largest lane offset (XADDR_MARGIN =
 2^24, which must hold a whole period of a group's dpol: G D 8 bytes), stay below 2^32. Plain integers in a header without device
 code: compiled alone by the host compiler here, no GPU and no library."""
