@@ -79,10 +79,6 @@ typedef unsigned int wv4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wide_rsrc(const void *p) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0x7fffffff, 0x00020000);
 }
-__device__ __forceinline__ double wide_ld64(__amdgpu_buffer_rsrc_t rs, int vo, int so) {
-    const wv2u q = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, 0);
-    return __hiloint2double((int)q.y, (int)q.x);
-}
 __device__ __forceinline__ wv2u wide_ld2i(__amdgpu_buffer_rsrc_t rs, int vo, int so) { return __builtin_amdgcn_raw_buffer_load_b64(rs, vo, so, 0); }
 template <int AUX>
 __device__ __forceinline__ void wide_ld2d(__amdgpu_buffer_rsrc_t rs, int vo, int so, double &a, double &b) {    // two adjacent doubles: one 16-byte load
@@ -154,20 +150,30 @@ __device__ __forceinline__ double diet_v(const Consts &c, double u, double opr) 
 // ---- EGM step, split in the two halves that fuse across the period boundary ------------------
 // X half (KrusellSmith.jl:59-62): from V_{t+1} (all e2 of this row, in LDS) to the endogenous
 // knot s_t[a,e] and kc = d s / d E  (= rho * d c / d E).
+// The half at ONE point, from the mixed expectation E = sum_k Pi[e, k] V_{t+1}[a, k]: every primal kernel — the launches through
+// egm_X below, the persistent sweeps (k_xprimal_back, k_xvfi, k_xdual_back: hank_xsweep.h) behind their own mixing — takes s and kc
+// from here, so they agree bit for bit. rho = 1/(1+r), opr = 1 + r, wz_tr = w z_e + tr, xa = the grid point a.
+struct XPoint { double s1, kc; };
+template <int CRRA = 0>
+__device__ __forceinline__ XPoint egm_X_point(const Consts &c, double E, const double *x4, double ze, double xa, int *err, int t, int e, int a) {
+    const double bE = E * c.beta;
+    const double ex = CRRA == 1 ? -0.5 : -1.0 / c.gamma;
+    if (pow_domain_error<CRRA>(bE, ex)) set_err(err, ERR_DOMAIN, t, e, a);
+    const double cm = pow_crra<CRRA>(bE, ex);
+    const double rho = x4[3];
+    const double s1 = rho * ((cm - (x4[1] * ze + x4[2])) + xa);
+    // d cmat/dE = beta*ex*(bE)^(ex-1)  (Dual^Real, ForwardDiff dual.jl:563-572); under the record diet the recorded value IS the
+    // one the persistent tangent sweeps rebuild from s (diet_kc): whoever reads it and whoever rebuilds it hold the same bits
+    const double kc = (CRRA == 1 || c.diet) ? diet_kc<CRRA>(c, s1, rho, 1.0 + x4[0], x4[1] * ze + x4[2], xa) : rho * (c.beta * ex * (cm / bE));
+    return {s1, kc};
+}
 __device__ inline void egm_X(const Consts &c, const double *Vsh, const double *Pish, int row, int a,
                              int e, double r, double w, double tr, double *s_out, double *kc_out, int *err,
                              int t) {
     const double E = mix_sum(Vsh[row] * Pish[e], Vsh + row, RBP, Pish + e, c.n_e, 1, c.n_e);
-    const double bE = E * c.beta;
-    const double ex = -1.0 / c.gamma;
-    if (pow_domain_error(bE, ex)) set_err(err, ERR_DOMAIN, t, e, a);
-    const double cm = pow_crra(bE, ex);
-    const double rho = 1.0 / (1.0 + r);
-    const double s1 = rho * ((cm - (w * c.z[e] + tr)) + c.a[a]);
-    *s_out = s1;
-    // d cmat/dE = beta*ex*(bE)^(ex-1)  (Dual^Real, ForwardDiff dual.jl:563-572); under the record diet the recorded value IS the
-    // one the persistent tangent sweeps rebuild from s (diet_kc): whoever reads it and whoever rebuilds it hold the same bits
-    *kc_out = c.diet ? diet_kc(c, s1, rho, 1.0 + r, w * c.z[e] + tr, c.a[a]) : rho * (c.beta * ex * (cm / bE));
+    const double x4[4] = {r, w, tr, 1.0 / (1.0 + r)};
+    const XPoint p = egm_X_point(c, E, x4, c.z[e], c.a[a], err, t, e, a);
+    *s_out = p.s1; *kc_out = p.kc;
 }
 
 // Y half (KrusellSmith.jl:66-80): interpolate the policy on the exogenous grid point a from the

@@ -1,10 +1,14 @@
 // hank_xsweep.h — the XCD-local persistent sweeps: ONE launch per sweep instead of one per period.
 //
 // The same recurrences as hank_kernels.h (BackwardIteration.jl:90-113, ForwardIteration.jl:297-308 and their partials
-// under Dual{Tag,Float64,N}), behind the same entry points and on the same record, as four persistent kernels:
-//   k_xprimal_back / k_xprimal_fwd : the Float64 recurrences (they record the linearisation),
-//   k_xtan_back<D> / k_xtan_fwd<D> : the N partials as linear recurrences at that record (the whole y-iteration keeps x
-//                                    fixed, NewtonRaphson.jl:91-111; so does every pass of a wide batch).
+// under Dual{Tag,Float64,N}), behind the same entry points and on the same record, as six persistent kernels:
+//   k_xprimal_back, k_xfwd<0, true>  : the Float64 recurrences (they record the linearisation),
+//   k_xtan_back<D>, k_xfwd<D, false> : the N partials as linear recurrences at that record (the whole y-iteration keeps x
+//                                      fixed, NewtonRaphson.jl:91-111; so does every pass of a wide batch),
+//   k_xdual_back<D>, k_xfwd<D, true> : value AND partials in one chain of periods (the Dual pass, hank_primal_jvp),
+//   k_xvfi, k_xstat                  : the steady state's two fixed points, one launch each, with a convergence vote.
+// What they share is stated once: the LDS layouts (hank_xlds.h: the kernel's pointers and the host's launch size from ONE struct), admission
+// and wave roles (xmember_join, xroles), the group barrier and the vote (xbar_*, xpoll, xvote), the staging (xstage_*) and egm_X_point.
 //
 // Mapping (MI355X: 8 XCDs x 32 CUs, one 4 MiB L2 per XCD, L2s not coherent with each other):
 //   * a launch has one workgroup per CU; each workgroup reads the XCD it actually runs on (HW_REG_XCC_ID) and takes a
@@ -35,6 +39,7 @@
 #pragma once
 #include "hank_kernels.h"
 #include "hank_xaddr.h"
+#include "hank_xlds.h"
 #include <type_traits>
 
 namespace hank {
@@ -62,9 +67,11 @@ struct XSync {                    // zeroed by a memset node before EVERY launch
     unsigned status[32];          // [0]: XERR_* (sticky), [1]: the XCD that raised it, [2]: microseconds the wait that timed out had lasted
     unsigned pad[32];
 };
-constexpr size_t XCTL_BYTES = 64;      // ctl[] at the end of every persistent kernel's LDS carve: the group placement and a vote's outcome
 
 typedef unsigned int xv4u __attribute__((ext_vector_type(4)));
+
+template <class T>      // a piece of a kernel's dynamic LDS at the byte offset its layout states (hank_xlds.h)
+__device__ __forceinline__ T *xlds_at(double *xl, unsigned off) { return reinterpret_cast<T *>(reinterpret_cast<char *>(xl) + off); }
 
 __device__ __forceinline__ double xld(const double *p) {      // 8-byte sc1 load: bypasses L1, served by the XCD's L2
     return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -184,7 +191,8 @@ __device__ __forceinline__ void xload_row_plain(const double *p, double *v) {  /
 // mask of its own: more of them than there are scalar registers, so each costs two v_readlane per period.
 __device__ __forceinline__ int xopaque(int v) { asm volatile("" : "+s"(v)); return v; }
 
-struct XGroup { int x, c, S, ok; };
+struct XMember { int x, c, Sact; bool on; };       // the XCD, the member index in its group, the members that own rows; on: this workgroup is one of them
+struct XRoles { int lane, wv, e; bool syncw, sync_duty; };
 
 // dev build only (make stamp): s_memtime stamps of lane 0 / wave 0 of the first and last member of group 0, periods
 // [XSTAMP_T0, XSTAMP_T0+8): where a period's time goes. Never compiled into the product library.
@@ -204,12 +212,6 @@ __device__ unsigned long long g_xstamps[2][32][XSTAMP_NP][XSTAMP_NS];     // [sw
         if ((on) >= 0 && XSTAMP_ON(per) && threadIdx.x == 0)                 \
             g_xstamps[sw][on][XSTAMP_SLOT(per)][i] = __builtin_amdgcn_s_memrealtime();                              \
     } while (0)
-// stamp taken by lane 0 of wave `wave` (arrival of the other waves at a workgroup barrier)
-#define XSTAMPW(sw, on, per, i, wave)                                                                            \
-    do {                                                                                                         \
-        if ((on) >= 0 && XSTAMP_ON(per) && (int)threadIdx.x == 64 * (wave))  \
-            g_xstamps[sw][on][XSTAMP_SLOT(per)][i] = __builtin_amdgcn_s_memrealtime();                              \
-    } while (0)
 // every wave's arrival at one chosen point of the period (lane 0 of each wave)
 __device__ unsigned long long g_xwaves[2][32][XSTAMP_NP][16];
 #define XSTAMPV(sw, on, per)                                                                                     \
@@ -223,7 +225,6 @@ __device__ unsigned long long g_xwaves[2][32][XSTAMP_NP][16];
 #define XSTAMP1(sw, on, i) do {} while (0)
 #define XSTAMPV(sw, on, per) do {} while (0)
 #define XSTAMP(sw, on, per, i) do {} while (0)
-#define XSTAMPW(sw, on, per, i, wave) do {} while (0)
 #endif
 
 __device__ inline void xfail(XSync *sy, unsigned code, int x, unsigned waited_us = 0u) {
@@ -238,9 +239,11 @@ __global__ void k_xpoison(XSync *base, int count, unsigned code) {
     if ((int)threadIdx.x < count) { base[threadIdx.x].status[0] = code; base[threadIdx.x].status[1] = 0u; }
 }
 
-// which XCD am I on, which member of its group am I, how many members does it have (known once EVERY workgroup of the
-// launch holds a ticket: one launch-wide wait at the start of the sweep, none afterwards)
-__device__ inline XGroup xgroup_join(XSync *sy, int *ctl) {
+// Admission, the same for every persistent kernel: which XCD am I on, which member of its group am I, how many members does it
+// have (known once EVERY workgroup of the launch holds a ticket: one launch-wide wait at the start of the sweep, none afterwards).
+// A workgroup takes part (`on`) if the launch has not failed, its XCD is one of the `groups` that work (1: the Float64 sweeps, XCD 0
+// only) and it is one of the Sact members that own rows; a group of fewer reports XERR_PLACEMENT (the whole group agrees on the count).
+__device__ __forceinline__ XMember xmember_join(XSync *sy, int *ctl, int groups, int n_a) {
     if (threadIdx.x == 0) {
         int xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
@@ -262,10 +265,25 @@ __device__ inline XGroup xgroup_join(XSync *sy, int *ctl) {
         }
     }
     __syncthreads();
-    XGroup g;
-    g.x = __builtin_amdgcn_readfirstlane(ctl[0]); g.c = __builtin_amdgcn_readfirstlane(ctl[1]);
-    g.S = __builtin_amdgcn_readfirstlane(ctl[2]); g.ok = __builtin_amdgcn_readfirstlane(ctl[3]);
-    return g;
+    XMember m;
+    m.x = __builtin_amdgcn_readfirstlane(ctl[0]); m.c = __builtin_amdgcn_readfirstlane(ctl[1]);
+    const int S = __builtin_amdgcn_readfirstlane(ctl[2]), ok = __builtin_amdgcn_readfirstlane(ctl[3]);
+    m.Sact = (n_a + XRW - 1) / XRW;
+    m.on = false;
+    if (!ok || m.x >= groups) return m;
+    if (S < m.Sact) { if (threadIdx.x == 0) xfail(sy, XERR_PLACEMENT, m.x); return m; }
+    m.on = m.c < m.Sact;
+    return m;
+}
+// Wave roles of a member: wave e < n_e is column e (lane = row); a block with room for one more wave has a SYNC wave with no memory traffic
+// of its own that runs the group barrier's polls (else wave 0 does: sync_duty). The wave index is a scalar register: column bases become scalar.
+__device__ __forceinline__ XRoles xroles(int ne) {
+    XRoles r;
+    r.lane = threadIdx.x & 63; r.wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    r.syncw = r.wv >= ne;
+    r.sync_duty = blockDim.x > 64 * ne ? r.syncw : r.wv == 0;
+    r.e = r.syncw ? 0 : r.wv;
+    return r;
 }
 
 // workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations, NOT for its global loads and stores
@@ -283,30 +301,11 @@ __device__ __forceinline__ void xbar_arrive(bool drain) {
     if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     xlds_barrier();
 }
-__device__ __forceinline__ void xbar_wait(XSync *sy, int x, int c, int members, unsigned episode, bool sync_wave) {
-    if (sync_wave) {
-        const int lane = threadIdx.x & 63;
-        if (lane == 0) *reinterpret_cast<volatile unsigned *>(&sy->flag[x][c][0]) = episode;
-        const XDeadline dl;
-        for (unsigned spins = 0;; spins++) {
-            const unsigned f = lane < members ? xldu(&sy->flag[x][lane][0]) : episode;
-            if (__all((int)(f - episode) >= 0)) break;
-            if (dl.expired(spins) || ((spins & 255u) == 255u && xldu(&sy->status[0]) != 0u)) {
-                if (lane == 0) xfail(sy, XERR_TIMEOUT, x, dl.waited_us());
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    xlds_barrier();
+// the wait half's two steps, each run by ONE wave: publish this member's episode; poll the flag lines of members lo..hi until every one
+// has reached `need` (bounded: see XDeadline)
+__device__ __forceinline__ void xpublish(XSync *sy, int x, int c, unsigned episode) {
+    if ((threadIdx.x & 63) == 0) *reinterpret_cast<volatile unsigned *>(&sy->flag[x][c][0]) = episode;
 }
-
-// The tangent sweeps split the barrier further. A member's period t needs the state rows of FEW other members (the
-// brackets / lottery segments of its 63 rows: recorded by the primal, so the range of members is known in advance), and
-// it may overwrite a state half only when EVERY member is done reading it. So: (1) before a period's gathers wait only
-// for the source members' episode; (2) before the period's state stores — a whole gather-and-mix phase later — check that
-// all members have published the previous episode; (3) publish after the stores have drained, and wait for nobody.
-// Arrival skew up to the length of the first phase disappears from the critical path. xpoll: one wave, bounded.
 __device__ __forceinline__ void xpoll(XSync *sy, int x, int lo, int hi, unsigned need) {
     const int lane = threadIdx.x & 63;
     const XDeadline dl;
@@ -320,9 +319,16 @@ __device__ __forceinline__ void xpoll(XSync *sy, int x, int lo, int hi, unsigned
         __builtin_amdgcn_s_sleep(1);
     }
 }
-__device__ __forceinline__ void xpublish(XSync *sy, int x, int c, unsigned episode) {
-    if ((threadIdx.x & 63) == 0) *reinterpret_cast<volatile unsigned *>(&sy->flag[x][c][0]) = episode;
+__device__ __forceinline__ void xbar_wait(XSync *sy, int x, int c, int members, unsigned episode, bool sync_wave) {
+    if (sync_wave) { xpublish(sy, x, c, episode); xpoll(sy, x, 0, members - 1, episode); }
+    xlds_barrier();
 }
+// The tangent sweeps split the barrier further. A member's period t needs the state rows of FEW other members (the
+// brackets / lottery segments of its 63 rows: recorded by the primal, so the range of members is known in advance), and
+// it may overwrite a state half only when EVERY member is done reading it. So: (1) before a period's gathers wait only
+// for the source members' episode; (2) before the period's state stores — a whole gather-and-mix phase later — check that
+// all members have published the previous episode; (3) publish after the stores have drained, and wait for nobody.
+// Arrival skew up to the length of the first phase disappears from the critical path.
 
 // knots of one column, read from the L2-resident state. Everything egm_Y is going to look at in the usual case — the
 // row's own knot and its lower neighbour (sortedness check), the column's two end knots (flat extrapolation) and the
@@ -343,22 +349,10 @@ struct XKnotsT {
         if constexpr (BUF) return buf_ld64<16>(rs, i * 8, so);
         else return xld(p + i);
     }
-    __device__ __forceinline__ void preload(const double *col, int a_, int n_, int guess, double ze_) {
-        p = col; a = a_; n = n_; ze = ze_;
-        sa = xld(col + a);
-        sam1 = xld(col + (a > 0 ? a - 1 : 0));
-        s0 = xld(col);
-        sN = xld(col + n - 1);
-        i0 = i1 = i2 = i3 = -1;
-        w0 = w1 = w2 = w3 = 0.0;
-        if (guess >= 0) {
-            const int q = guess < n - 1 ? guess : n - 2;
-            i0 = q > 0 ? q - 1 : 0; i1 = q; i2 = q + 1; i3 = q + 2 < n ? q + 2 : n - 1;
-            w0 = xld(col + i0); w1 = xld(col + i1); w2 = xld(col + i2); w3 = xld(col + i3);
-        }
-    }
-    __device__ __forceinline__ void preload(__amdgpu_buffer_rsrc_t rs_, int so_, int a_, int n_, int guess, double ze_) {     // the same batch, BUF
-        rs = rs_; so = so_; a = a_; n = n_; ze = ze_;
+    __device__ __forceinline__ void preload(const double *col, int a_, int n_, int guess, double ze_) { p = col; batch(a_, n_, guess, ze_); }
+    __device__ __forceinline__ void preload(__amdgpu_buffer_rsrc_t rs_, int so_, int a_, int n_, int guess, double ze_) { rs = rs_; so = so_; batch(a_, n_, guess, ze_); }      // BUF
+    __device__ __forceinline__ void batch(int a_, int n_, int guess, double ze_) {
+        a = a_; n = n_; ze = ze_;
         sa = ld(a);
         sam1 = ld(a > 0 ? a - 1 : 0);
         s0 = ld(0);
@@ -415,6 +409,48 @@ __device__ __forceinline__ double xwave_sum(double v) {            // butterfly:
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+__device__ __forceinline__ double xmax_nan(double a, double b) { return (b > a || !(b == b)) ? b : a; }      // a NaN wins and stays
+__device__ __forceinline__ double xwave_max_nan(double v) {        // butterfly: every lane ends with the wave's max
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = xmax_nan(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// The convergence vote of the two fixed points (k_xvfi, k_xstat), run by the member's sync_duty wave in place of xbar_wait: the group
+// barrier carries it. The member publishes {episode, my rows converged | error word seen << 1, my max} in ONE 16-byte store to ITS flag
+// line (converged: the max over redsh[0..ne), its waves' maxima of this trip, is below tol, in Float64 like k_vfi_check; a NaN never
+// converges, nor a trip without a comparison: !have) and reads everybody's, bounded like every wait: a timeout says stop. Every member
+// reads every line, so all leave in the same trip: ctl[4] = all have converged, ctl[5] = stop anyway; WITH_MAX: redsh[15] = the group's max.
+template <bool WITH_MAX>
+__device__ __forceinline__ void xvote(XSync *sy, int x, int c, int members, unsigned episode, double *redsh, int ne, bool have, double tol, unsigned bad, int *ctl) {
+    const int lane = threadIdx.x & 63;
+    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(&sy->flag[x][0][0], 0, 64 * 32 * 4, 0x00020000);     // the group's flag lines
+    double m = 0.0;
+    if (have) for (int k = 0; k < ne; k++) m = xmax_nan(m, redsh[k]);
+    if (lane == 0) {
+        const xv4u q = {episode, ((have && m < tol) ? 1u : 0u) | (bad << 1), WITH_MAX ? (unsigned)__double2loint(m) : 0u, WITH_MAX ? (unsigned)__double2hiint(m) : 0u};
+        *reinterpret_cast<volatile xv4u *>(&sy->flag[x][c][0]) = q;
+    }
+    xv4u f = {episode, 1u, 0u, 0u};
+    const XDeadline dl;
+    for (unsigned spins = 0;; spins++) {
+        if (lane < members) f = __builtin_amdgcn_raw_buffer_load_b128(frs, lane * 128, 0, 16);     // sc1: served by the XCD's L2
+        if (__all((int)(f.x - episode) >= 0)) break;
+        if (dl.expired(spins) || ((spins & 255u) == 255u && xldu(&sy->status[0]) != 0u)) {
+            if (lane == 0) xfail(sy, XERR_TIMEOUT, x, dl.waited_us());
+            f.y = 2u;                               // leave the loop: the host reads the status word
+            break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    const bool allc = __all((f.y & 1u) != 0u) != 0, anyb = __any((f.y & 2u) != 0u) != 0;      // (every lane votes: not inside the lane-0 branch)
+    if (lane == 0) { ctl[4] = (have && allc) ? 1 : 0; ctl[5] = anyb ? 1 : 0; }
+    if constexpr (WITH_MAX) {
+        const double fm = xwave_max_nan(__hiloint2double((int)f.w, (int)f.z));
+        if (lane == 0) redsh[15] = fm;
+    }
 }
 
 // sum over the 64 lanes with DPP moves (no LDS traffic), fixed order; the result is valid in lane 63 ONLY
@@ -522,6 +558,26 @@ __device__ __forceinline__ void xtile_mix_reg(const double *tl, const double (&p
     }
 }
 
+// Per-period inputs that are uniform over the workgroup, staged in LDS once for the whole sweep (as a per-period global load each is a
+// cold round trip on the critical path). xsh[P][4]: r_t, w_t, tr_t, rho_t = 1/(1+r_t)
+__device__ __forceinline__ void xstage_prices(double *xsh, const Consts &c, const double *xhh, const double *rho, int P) {
+    for (int k = threadIdx.x; k < P; k += blockDim.x) {
+        xsh[4 * k] = xhh[c.n_hh * k]; xsh[4 * k + 1] = xhh[c.n_hh * k + 1]; xsh[4 * k + 2] = hh_tr(c, xhh, k); xsh[4 * k + 3] = rho[k];
+    }
+}
+// dxsh[P][3][D]: dr, dw, dtr of the D directions group x owns, out of the pass's N (columns n0.. of [P][Ntot]); a direction beyond N is zero
+template <int D>
+__device__ __forceinline__ void xstage_dx(double *dxsh, const Consts &c, const double *dxr, const double *dxw, const double *dxt, int Ntot, int n0, int N, int x, int P) {
+    for (int k = threadIdx.x; k < P * D; k += blockDim.x) {
+        const int t_ = k / D, d_ = k - t_ * D;
+        const bool on = x * D + d_ < N;
+        const size_t ix = (size_t)t_ * Ntot + n0 + x * D + d_;
+        dxsh[(t_ * 3 + 0) * D + d_] = on ? dxr[ix] : 0.0;
+        dxsh[(t_ * 3 + 1) * D + d_] = on ? dxw[ix] : 0.0;
+        dxsh[(t_ * 3 + 2) * D + d_] = (on && c.n_hh > 2) ? dxt[ix] : 0.0;
+    }
+}
+
 // ================================ the Float64 sweeps ==========================================
 // One group (the XCD with id 0) runs them; the workgroups that landed elsewhere leave at once. They write the policy
 // sequence, the distribution path and the linearisation record the tangent sweeps — of either implementation — read.
@@ -547,33 +603,23 @@ struct XBackArgs {
 
 template <int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xprimal_back(XBackArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_primal_back (under this kernel) is the host's sum of the same pieces
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_primal_back (hank_xlds.h), which also sizes the launch
     const Consts &c = A.c;
     const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
-    double *Vsh = xl;                                   // [ne][64]
-    double *Pish = Vsh + (size_t)ne * 64;               // [ne*ne] (registers for it would spill the 1024-thread variant)
-    double *ash = Pish + ne * ne;                      // [na]: the wealth grid (the bracket's grid values are a dependent load)
-    double *xsh = ash + na;                             // [P][4]: r_t, w_t, tr_t, rho_t — a cold uniform load per period otherwise
-    int *ctl = reinterpret_cast<int *>(xsh + 4 * (size_t)P);
-    const XGroup g = xgroup_join(A.sy, ctl);
-    if (!g.ok) return;
-    const int x = g.x, cW = g.c;
-    if (x != 0) return;
-    const int Sact = (na + XRW - 1) / XRW;              // members that own rows
-    if (g.S < Sact) { if (threadIdx.x == 0) xfail(A.sy, XERR_PLACEMENT, x); return; }   // the whole group agrees on S
-    if (cW >= Sact) return;
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (the wave index in a scalar register: column bases become scalar)
-    const bool syncw = wv >= ne;                        // see k_xtan_back
-    const bool sync_duty = blockDim.x > 64 * ne ? syncw : wv == 0;
-    const int e = syncw ? 0 : wv;
+    const XLdsPrimalBack L = xlds_primal_back(ne, na, P);
+    double *Vsh = xlds_at<double>(xl, L.Vsh), *Pish = xlds_at<double>(xl, L.Pish), *ash = xlds_at<double>(xl, L.ash), *xsh = xlds_at<double>(xl, L.xsh);
+    int *ctl = xlds_at<int>(xl, L.ctl);
+    const XMember mb = xmember_join(A.sy, ctl, 1, na);
+    if (!mb.on) return;
+    const int x = mb.x, cW = mb.c, Sact = mb.Sact;
+    const XRoles rl = xroles(ne);
+    const int lane = rl.lane, e = rl.e; const bool syncw = rl.syncw, sync_duty = rl.sync_duty;
     const int a = cW * XRW + lane;
     const bool own = !syncw && lane < XRW && a < na;
     const size_t pt = (size_t)e * na + (own ? a : 0);
     for (int k = threadIdx.x; k < ne * ne; k += blockDim.x) Pish[k] = c.Pi[k];
     for (int k = threadIdx.x; k < na; k += blockDim.x) ash[k] = c.a[k];
-    for (int k = threadIdx.x; k < P; k += blockDim.x) {
-        xsh[4 * k] = A.xhh[c.n_hh * k]; xsh[4 * k + 1] = A.xhh[c.n_hh * k + 1]; xsh[4 * k + 2] = hh_tr(c, A.xhh, k); xsh[4 * k + 3] = A.rho[k];
-    }
+    xstage_prices(xsh, c, A.xhh, A.rho, P);
     Consts cl = c;                                      // what egm_Y sees: the same model, grid served from LDS
     cl.a = ash;
     const double ze = c.z[e], xa = c.a[own ? a : 0];
@@ -602,20 +648,14 @@ __global__ void __launch_bounds__(MAXT) k_xprimal_back(XBackArgs A) {
             xlds_barrier();
         }
         if (i < P) {
-            // ---- X half of period tx from V_{tx+1} in LDS (KrusellSmith.jl:59-62; same expressions as egm_X): the knots s_tx -> state[i & 1]
+            // ---- X half of period tx from V_{tx+1} in LDS (KrusellSmith.jl:59-62): the knots s_tx -> state[i & 1]
             const int tx = P - 1 - i;
             if (own) {
                 double E;
                 xtile_mix<1, 1>(Vsh + lane, Pish + e, ne, ne, &E);
-                const double bE = E * c.beta;
-                const double ex = -1.0 / c.gamma;
-                if (pow_domain_error(bE, ex)) set_err(A.err, ERR_DOMAIN, tx, e, a);
-                const double cm = pow_crra(bE, ex);
-                const double rho = xsh[4 * tx + 3];             // 1/(1+r_tx), once per period (k_xrho), not once per thread
-                const double s1 = rho * ((cm - (xsh[4 * tx + 1] * ze + xsh[4 * tx + 2])) + xa);
-                const double kc = c.diet ? diet_kc(c, s1, rho, 1.0 + xsh[4 * tx], xsh[4 * tx + 1] * ze + xsh[4 * tx + 2], xa) : rho * (c.beta * ex * (cm / bE));
-                sS[(size_t)(i & 1) * hs + pt] = s1;
-                A.R.s[(size_t)tx * G + pt] = s1; A.R.kc[(size_t)tx * G + pt] = kc;
+                const XPoint p = egm_X_point(c, E, xsh + 4 * tx, ze, xa, A.err, tx, e, a);      // rho = 1/(1+r_tx) once per period (k_xrho), not once per thread
+                sS[(size_t)(i & 1) * hs + pt] = p.s1;
+                A.R.s[(size_t)tx * G + pt] = p.s1; A.R.kc[(size_t)tx * G + pt] = p.kc;
             }
             episode++;
             xbar_arrive(!syncw);
@@ -623,15 +663,11 @@ __global__ void __launch_bounds__(MAXT) k_xprimal_back(XBackArgs A) {
         }
     }
 }
-// dynamic LDS of k_xprimal_back: the carve at its top (Vsh, Pish, ash, xsh, ctl) — it grows with the horizon P
-static inline size_t x_lds_primal_back(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * 64 + (size_t)c.n_e * c.n_e + c.n_a + 4 * (size_t)c.P) + XCTL_BYTES; }
+static inline size_t x_lds_primal_back(const Consts &c) { return xlds_primal_back(c.n_e, c.n_a, c.P).bytes; }
 
 // ---- the steady state's inner fixed point as ONE launch (hank_vfi; SteadyState.jl:132-141) ----------------------------
 // value <- value_fn(value, xVals).Value until max|value' - value| < tol, on the group of XCD 0 exactly like k_xprimal_back
-// (constant prices, nothing recorded). The group barrier carries the vote: every member publishes, in the same 16-byte
-// store as its episode number, whether ITS rows have converged (compared in Float64 against tol, like k_vfi_check:
-// max < tol over all rows <=> every member's max < tol; a NaN never converges), whether it has seen the device error word
-// set, and its max; every member reads every line, so all of them leave the loop in the same trip.
+// (constant prices, nothing recorded). The group barrier carries the vote (xvote: max < tol over all rows <=> every member's max < tol).
 struct XVfiArgs {
     Consts c;
     const double *V0;           // [G] start value
@@ -648,25 +684,17 @@ struct XVfiArgs {
 
 template <int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_vfi (under this kernel) is the host's sum of the same pieces
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_vfi (hank_xlds.h), which also sizes the launch
     const Consts &c = A.c;
     const int ne = c.n_e, na = c.n_a, G = c.G;
-    double *Vsh = xl;                                   // [ne][64]
-    double *Pish = Vsh + (size_t)ne * 64;               // [ne*ne]
-    double *ash = Pish + ne * ne;                       // [na]
-    double *redsh = ash + na;                           // [16] per-wave max
-    int *ctl = reinterpret_cast<int *>(redsh + 16);     // [4] group placement, [4..7] the vote's outcome
-    const XGroup g = xgroup_join(A.sy, ctl);
-    if (!g.ok) return;
-    const int x = g.x, cW = g.c;
-    if (x != 0) return;
-    const int Sact = (na + XRW - 1) / XRW;
-    if (g.S < Sact) { if (threadIdx.x == 0) xfail(A.sy, XERR_PLACEMENT, x); return; }
-    if (cW >= Sact) return;
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (the wave index in a scalar register: column bases become scalar)
-    const bool syncw = wv >= ne;
-    const bool sync_duty = blockDim.x > 64 * ne ? syncw : wv == 0;
-    const int e = syncw ? 0 : wv;
+    const XLdsVfi L = xlds_vfi(ne, na);
+    double *Vsh = xlds_at<double>(xl, L.Vsh), *Pish = xlds_at<double>(xl, L.Pish), *ash = xlds_at<double>(xl, L.ash), *redsh = xlds_at<double>(xl, L.redsh);
+    int *ctl = xlds_at<int>(xl, L.ctl);                 // [4] group placement, [4..5] the vote's outcome
+    const XMember mb = xmember_join(A.sy, ctl, 1, na);
+    if (!mb.on) return;
+    const int x = mb.x, cW = mb.c, Sact = mb.Sact;
+    const XRoles rl = xroles(ne);
+    const int lane = rl.lane, wv = rl.wv, e = rl.e; const bool syncw = rl.syncw, sync_duty = rl.sync_duty;
     const int a = cW * XRW + lane;
     const bool own = !syncw && lane < XRW && a < na;
     const size_t pt = (size_t)e * na + (own ? a : 0);
@@ -675,7 +703,7 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
     Consts cl = c;
     cl.a = ash;
     const double ze = c.z[e], xa = c.a[own ? a : 0];
-    const double rho = 1.0 / (1.0 + A.r);               // same expression as egm_X / k_xrho
+    const double x4[4] = {A.r, A.w, A.tr, 1.0 / (1.0 + A.r)};      // the prices and rho (same expression as egm_X / k_xrho)
     const size_t hs = (size_t)XG * G;
     double *const sS = A.st_s;
     double Vprev = own ? A.V0[pt] : 0.0, V = Vprev, pol = 0.0;
@@ -683,7 +711,6 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
     __syncthreads();
     int guess = -1, steps = 0, conv = 0;
     double gmax = 0.0;
-    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(&A.sy->flag[x][0][0], 0, 64 * 32 * 4, 0x00020000);     // the group's flag lines
     unsigned episode = 0;
     // sequence: X(V_0) | Y -> V_1, vote, X(V_1) | Y -> V_2, vote, X(V_2) | ...: step k is complete after the Y half of trip k
     for (int i = 0; i <= A.max_iter; i++) {
@@ -700,9 +727,7 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
                 Vprev = V;
             }
             if (!syncw) Vsh[e * 64 + lane] = V;
-            // this wave's max (a NaN wins and stays)
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { const double o2 = __shfl_xor(dmax, off, 64); dmax = (o2 > dmax || !(o2 == o2)) ? o2 : dmax; }
+            dmax = xwave_max_nan(dmax);
             if (lane == 0) redsh[wv] = syncw ? 0.0 : dmax;
             xlds_barrier();
         }
@@ -710,44 +735,11 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
         if (own) {
             double E;
             xtile_mix<1, 1>(Vsh + lane, Pish + e, ne, ne, &E);
-            const double bE = E * c.beta;
-            const double ex = -1.0 / c.gamma;
-            if (pow_domain_error(bE, ex)) set_err(A.err, ERR_DOMAIN, 0, e, a);
-            const double cm = pow_crra(bE, ex);
-            sS[(size_t)(i & 1) * hs + pt] = rho * ((cm - (A.w * ze + A.tr)) + xa);
+            sS[(size_t)(i & 1) * hs + pt] = egm_X_point(c, E, x4, ze, xa, A.err, 0, e, a).s1;      // (kc is not needed)
         }
         episode++;
         xbar_arrive(!syncw);
-        if (sync_duty) {
-            // publish {episode, my rows converged, error word seen, -} + my max in ONE 16-byte store, then read everybody's
-            double m = 0.0;
-            for (int k = 0; k < ne; k++) m = (redsh[k] > m || !(redsh[k] == redsh[k])) ? redsh[k] : m;
-            const unsigned mine = (i > 0 && m < A.tol) ? 1u : 0u;
-            const unsigned bad = xldu(reinterpret_cast<const unsigned *>(A.err)) != 0u ? 1u : 0u;
-            if (lane == 0) {
-                xv4u q;
-                q.x = episode; q.y = mine | (bad << 1); q.z = (unsigned)__double2loint(m); q.w = (unsigned)__double2hiint(m);
-                *reinterpret_cast<volatile xv4u *>(&A.sy->flag[x][cW][0]) = q;
-            }
-            xv4u f;
-            f.x = episode; f.y = 1u; f.z = 0u; f.w = 0u;
-            const XDeadline dl;
-            for (unsigned spins = 0;; spins++) {
-                if (lane < Sact) f = __builtin_amdgcn_raw_buffer_load_b128(frs, lane * 128, 0, 16);     // sc1: served by the XCD's L2
-                if (__all((int)(f.x - episode) >= 0)) break;
-                if (dl.expired(spins) || ((spins & 255u) == 255u && xldu(&A.sy->status[0]) != 0u)) {
-                    if (lane == 0) xfail(A.sy, XERR_TIMEOUT, x, dl.waited_us());
-                    f.y = 2u;                               // leave the loop: the host reads the status word
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            const bool allc = __all((f.y & 1u) != 0u) != 0, anyb = __any((f.y & 2u) != 0u) != 0;
-            double fm = __hiloint2double((int)f.w, (int)f.z);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { const double o2 = __shfl_xor(fm, off, 64); fm = (o2 > fm || !(o2 == o2)) ? o2 : fm; }
-            if (lane == 0) { ctl[4] = allc ? 1 : 0; ctl[5] = anyb ? 1 : 0; redsh[15] = fm; }
-        }
+        if (sync_duty) xvote<true>(A.sy, x, cW, Sact, episode, redsh, ne, i > 0, A.tol, xldu(reinterpret_cast<const unsigned *>(A.err)) != 0u ? 1u : 0u, ctl);
         xlds_barrier();
         if (i > 0) { steps = i; gmax = redsh[15]; }
         conv = ctl[4];
@@ -758,8 +750,7 @@ __global__ void __launch_bounds__(MAXT) k_xvfi(XVfiArgs A) {
     if (own) { A.Vout[pt] = V; A.pol[pt] = pol; }
     if (cW == 0 && threadIdx.x == 0) { A.iters[0] = steps; A.iters[1] = conv; *A.supnorm = gmax; }
 }
-// dynamic LDS of k_xvfi: the carve at its top (Vsh, Pish, ash, redsh, ctl)
-static inline size_t x_lds_vfi(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * 64 + (size_t)c.n_e * c.n_e + c.n_a + 16) + XCTL_BYTES; }
+static inline size_t x_lds_vfi(const Consts &c) { return xlds_vfi(c.n_e, c.n_a).bytes; }
 
 // ================================ tangent-only sweeps at a recorded primal ===================================
 // The dual sweeps above cost what the Float64 recurrence costs — and every group repeats it (bracket search, two
@@ -767,10 +758,6 @@ static inline size_t x_lds_vfi(const Consts &c) { return sizeof(double) * ((size
 // NewtonRaphson.jl:91-111; every pass of a wide batch) the primal sweep runs ONCE (the D = 0 instances above, which
 // also record the linearisation) and the partials run as pure linear recurrences: these two kernels. Same groups, same
 // state exchange through the XCD's L2, same barrier; per point and period a few FMAs per direction.
-// slots of the tangent tile: D, padded where a lane stride of 8*D bytes would bank-conflict the 16-byte reads (D = 4: 32 B
-// -> lanes i and i+8 collide, 31 % of the LDS cycles in profiles/r02a; 48 B is conflict-free)
-template <int D> struct XTileT { static constexpr int SL = D == 4 ? 6 : (D == 8 ? 10 : D); };
-static inline int xtile_sl(int D) { return D == 1 ? XTileT<1>::SL : (D == 2 ? XTileT<2>::SL : XTileT<4>::SL); }      // the trait at a run-time D in {1, 2, 4} (the host's size functions)
 
 // ---- the stationary distribution as ONE launch (hank_stationary_dist) ------------------------------------------------
 // D <- Lambda(policy) D on the group of XCD 0 exactly like k_xprimal_fwd with ONE period's lottery record (k_lottery on the
@@ -792,25 +779,19 @@ struct XStatArgs {
 
 template <int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xstat(XStatArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_stat (under this kernel) is the host's sum of the same pieces
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_stat (hank_xlds.h), which also sizes the launch
     const Consts &c = A.c;
     const Record &R = A.R;
     const int ne = c.n_e, na = c.n_a, G = c.G;
     const int GV = G + 64 * ne;
-    double *tile = xl;                                  // [ne][64]
-    double *redsh = tile + (size_t)ne * 64;             // [16] per-wave max
-    int *ctl = reinterpret_cast<int *>(redsh + 16);     // [4] placement, [4..5] the vote's outcome
-    const XGroup g = xgroup_join(A.sy, ctl);
-    if (!g.ok) return;
-    const int x = g.x, cW = g.c;
-    if (x != 0) return;
-    const int Sact = (na + XRW - 1) / XRW;
-    if (g.S < Sact) { if (threadIdx.x == 0) xfail(A.sy, XERR_PLACEMENT, x); return; }
-    if (cW >= Sact) return;
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (the wave index in a scalar register: column bases become scalar)
-    const bool syncw = wv >= ne;
-    const bool sync_duty = blockDim.x > 64 * ne ? syncw : wv == 0;
-    const int e = syncw ? 0 : wv;
+    const XLdsStat L = xlds_stat(ne);
+    double *tile = xlds_at<double>(xl, L.tile), *redsh = xlds_at<double>(xl, L.redsh);
+    int *ctl = xlds_at<int>(xl, L.ctl);                 // [4] placement, [4..5] the vote's outcome
+    const XMember mb = xmember_join(A.sy, ctl, 1, na);
+    if (!mb.on) return;
+    const int x = mb.x, cW = mb.c, Sact = mb.Sact;
+    const XRoles rl = xroles(ne);
+    const int lane = rl.lane, wv = rl.wv, e = rl.e; const bool syncw = rl.syncw, sync_duty = rl.sync_duty;
     const int r0 = cW * XRW, r = r0 + lane;
     const bool own = !syncw && lane < XRW && r < na;
     const bool virt = !syncw && lane == 63;
@@ -832,7 +813,6 @@ __global__ void __launch_bounds__(MAXT) k_xstat(XStatArgs A) {
     for (int k = 0; k < ne; k++) anyclo = anyclo || R.clo[k] > 0;
     const int s0 = max(sg0, 0), s2 = min(sg2, na);
     const bool need_vD = anyclo && clo == 0 && __any(own && (sg0 <= 0 && s2 > 0));
-    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(&A.sy->flag[x][0][0], 0, 64 * 32 * 4, 0x00020000);
     unsigned episode = 1;
     xbar_arrive(!syncw);
     xbar_wait(A.sy, x, cW, Sact, episode, sync_duty);
@@ -889,38 +869,14 @@ __global__ void __launch_bounds__(MAXT) k_xstat(XStatArgs A) {
                 if (own) dmax = fabs(Dn - Dchk);
                 else if (virt) dmax = fabs(Dn - Dchk) * (double)Sact;      // one of up to Sact parts of row 0 (see top)
                 Dchk = Dn;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) { const double o2 = __shfl_xor(dmax, off, 64); dmax = (o2 > dmax || !(o2 == o2)) ? o2 : dmax; }
+                dmax = xwave_max_nan(dmax);
             }
         }
         if (chk && lane == 0) redsh[wv] = syncw ? 0.0 : dmax;
         cur = nxt;
         episode++;
         xbar_arrive(!syncw);
-        if (sync_duty) {
-            double m = 0.0;
-            if (chk) for (int k = 0; k < ne; k++) m = (redsh[k] > m || !(redsh[k] == redsh[k])) ? redsh[k] : m;
-            if (lane == 0) {
-                xv4u q;
-                q.x = episode; q.y = (chk && m < A.tol) ? 1u : 0u; q.z = 0u; q.w = 0u;
-                *reinterpret_cast<volatile xv4u *>(&A.sy->flag[x][cW][0]) = q;
-            }
-            xv4u f;
-            f.x = episode; f.y = 1u; f.z = 0u; f.w = 0u;
-            const XDeadline dl;
-            for (unsigned spins = 0;; spins++) {
-                if (lane < Sact) f = __builtin_amdgcn_raw_buffer_load_b128(frs, lane * 128, 0, 16);
-                if (__all((int)(f.x - episode) >= 0)) break;
-                if (dl.expired(spins) || ((spins & 255u) == 255u && xldu(&A.sy->status[0]) != 0u)) {
-                    if (lane == 0) xfail(A.sy, XERR_TIMEOUT, x, dl.waited_us());
-                    f.y = 2u;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            const bool allc = __all((f.y & 1u) != 0u) != 0, anyb = __any((f.y & 2u) != 0u) != 0;      // (every lane votes: not inside the lane-0 branch)
-            if (lane == 0) { ctl[4] = (chk && allc) ? 1 : 0; ctl[5] = anyb ? 1 : 0; }
-        }
+        if (sync_duty) xvote<false>(A.sy, x, cW, Sact, episode, redsh, ne, chk, A.tol, 0u, ctl);
         xlds_barrier();
         conv = ctl[4];
         const int stop = conv | ctl[5];
@@ -936,8 +892,7 @@ __global__ void __launch_bounds__(MAXT) k_xstat(XStatArgs A) {
     }
     if (cW == 0 && threadIdx.x == 0) { A.iters[0] = it; A.iters[1] = conv; }
 }
-// dynamic LDS of k_xstat: the carve at its top (tile, redsh, ctl)
-static inline size_t x_lds_stat(const Consts &c) { return sizeof(double) * ((size_t)c.n_e * 64 + 16) + XCTL_BYTES; }
+static inline size_t x_lds_stat(const Consts &c) { return xlds_stat(c.n_e).bytes; }
 
 struct XTanBackArgs {
     Consts c;
@@ -957,38 +912,21 @@ struct XTanBackArgs {
 template <int D, int MAXT>
 __global__ void __launch_bounds__(MAXT) k_xtan_back(XTanBackArgs A) {
     constexpr int SL = XTileT<D>::SL;
-    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_tan_back (under this kernel) is the host's sum of the same pieces
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_tan_back (hank_xlds.h), which also sizes the launch
     const Consts &c = A.c;
     const Record &R = A.R;
     const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
-    double *tile = xl;                                  // [ne][64][SL]
-    double *rhosh = tile + (size_t)SL * ne * 64;                    // [P]
-    double *pxsh = rhosh + ((P + 1) & ~1);                       // [P][3]: 1 + r_t, w_t, tr_t (record diet)
-    double *dxsh = pxsh + 3 * (size_t)P + (P & 1);               // [P][3][D]: this group's dr, dw, dtr (a cold uniform load per period otherwise)
-    int *srcsh = reinterpret_cast<int *>(dxsh + (size_t)P * 3 * D);      // [P]: this member's source ranges
-    int *ctl = srcsh + P;
-    const XGroup g = xgroup_join(A.sy, ctl);
-    if (!g.ok) return;
-    const int x = g.x, cW = g.c;
-    if (x >= A.groups) return;
-    const int Sact = (na + XRW - 1) / XRW;
-    if (g.S < Sact) { if (threadIdx.x == 0) xfail(A.sy, XERR_PLACEMENT, x); return; }
-    if (cW >= Sact) return;
-    for (int k = threadIdx.x; k < P; k += blockDim.x) rhosh[k] = A.rho[k];
-    for (int k = threadIdx.x; k < P; k += blockDim.x) { pxsh[3 * k] = 1.0 + A.xhh[c.n_hh * k]; pxsh[3 * k + 1] = A.xhh[c.n_hh * k + 1]; pxsh[3 * k + 2] = hh_tr(c, A.xhh, k); }
+    const XLdsTanBack L = xlds_tan_back(ne, P, D);
+    double *tile = xlds_at<double>(xl, L.tile), *rhosh = xlds_at<double>(xl, L.rhosh), *pxsh = xlds_at<double>(xl, L.pxsh), *dxsh = xlds_at<double>(xl, L.dxsh);
+    int *srcsh = xlds_at<int>(xl, L.srcsh), *ctl = xlds_at<int>(xl, L.ctl);
+    const XMember mb = xmember_join(A.sy, ctl, A.groups, na);
+    if (!mb.on) return;
+    const int x = mb.x, cW = mb.c, Sact = mb.Sact;
+    for (int k = threadIdx.x; k < P; k += blockDim.x) { rhosh[k] = A.rho[k]; pxsh[3 * k] = 1.0 + A.xhh[c.n_hh * k]; pxsh[3 * k + 1] = A.xhh[c.n_hh * k + 1]; pxsh[3 * k + 2] = hh_tr(c, A.xhh, k); }
     for (int k = threadIdx.x; k < P; k += blockDim.x) srcsh[k] = A.src ? A.src[(size_t)k * Sact + cW] : ((Sact - 1) << 8);
-    for (int k = threadIdx.x; k < P * D; k += blockDim.x) {
-        const int t_ = k / D, d_ = k - t_ * D;
-        const bool on = x * D + d_ < A.N;
-        const size_t ix = (size_t)t_ * A.Ntot + A.n0 + x * D + d_;
-        dxsh[(t_ * 3 + 0) * D + d_] = on ? A.dxr[ix] : 0.0;
-        dxsh[(t_ * 3 + 1) * D + d_] = on ? A.dxw[ix] : 0.0;
-        dxsh[(t_ * 3 + 2) * D + d_] = (on && c.n_hh > 2) ? A.dxt[ix] : 0.0;
-    }
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (the wave index in a scalar register: column bases become scalar)
-    const bool syncw = wv >= ne;                        // the extra wave (when the block has one) only runs the group barrier's poll
-    const bool sync_duty = blockDim.x > 64 * ne ? syncw : wv == 0;
-    const int e = syncw ? 0 : wv;
+    xstage_dx<D>(dxsh, c, A.dxr, A.dxw, A.dxt, A.Ntot, A.n0, A.N, x, P);
+    const XRoles rl = xroles(ne);
+    const int lane = rl.lane, e = rl.e; const bool syncw = rl.syncw, sync_duty = rl.sync_duty;
     const int r0 = cW * XRW, a = r0 + lane;
     const bool own = !syncw && lane < XRW && a < na;
     const size_t pt = (size_t)e * na + (own ? a : 0);
@@ -1103,17 +1041,7 @@ __global__ void __launch_bounds__(MAXT) k_xtan_back(XTanBackArgs A) {
         }
     }
 }
-// dynamic LDS of k_xtan_back<D>: the carve at its top (tile, rhosh and pxsh padded to pairs, dxsh, srcsh, ctl) — the group's input tangents of every period
-static inline size_t x_lds_tan_back(const Consts &c, int D) { return sizeof(double) * ((size_t)xtile_sl(D) * c.n_e * 64 + c.P + 1 + 3 * (size_t)c.P + 1 + 3 * (size_t)c.P * D) + sizeof(int) * (size_t)c.P + XCTL_BYTES; }
-
-// slots of a sweep that carries NSL numbers per grid point (the D partials and, in a Dual pass, the value)
-template <int NSL> struct XSlots {
-    static constexpr int SP = NSL == 1 ? 1 : ((NSL + 1) / 2) * 2;        // slots of a state row (planes of 16-byte pairs)
-    static constexpr int SL = NSL <= 2 ? NSL : (NSL <= 6 ? 6 : 10);      // slots of a tile entry (see XTileT)
-};
-struct XSlotsRt { int SP, SL; };                                          // the traits at a run-time NSL in {1, ..., 5} (the host's size functions and buffers)
-template <int NSL> constexpr XSlotsRt xslots_of() { return {XSlots<NSL>::SP, XSlots<NSL>::SL}; }
-static inline XSlotsRt xslots(int NSL) { return NSL == 1 ? xslots_of<1>() : NSL == 2 ? xslots_of<2>() : NSL == 3 ? xslots_of<3>() : NSL == 4 ? xslots_of<4>() : xslots_of<5>(); }
+static inline size_t x_lds_tan_back(const Consts &c, int D) { return xlds_tan_back(c.n_e, c.P, D).bytes; }
 
 // ---- the backward half of a Dual pass (hank_primal_jvp) as ONE launch: value AND D partials in every group -----------
 // Every group repeats the Float64 EGM step (bit for bit the same in all of them: same expressions, same order) and carries
@@ -1141,35 +1069,27 @@ struct XDualBackArgs {
 template <int D, int MAXT, int NE = 0, int CRRA = 0>
 __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     constexpr int NSL = D + 1, SL = XSlots<NSL>::SL, IV = D;
-    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_dual_back (under this kernel) is the host's sum of the same pieces
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_dual_back (hank_xlds.h), which also sizes the launch
     const XBackArgs &A = B.p;
     const Consts &c = A.c;
     const int ne = NE > 0 ? NE : c.n_e, na = c.n_a, P = c.P, G = c.G;
-    double *tile = xl;                                  // [ne][64][SL]: slots 0..D-1 the partials of V, slot D the value
-    double *ash = tile + (size_t)SL * ne * 64;          // [na]
-    double *xsh = ash + ((na + 1) & ~1);                // [P][4]: r_t, w_t, tr_t, rho_t
-    double *dxsh = xsh + 4 * (size_t)P;                 // [P][3][D]: this group's dr, dw, dtr
-    int *ctl = reinterpret_cast<int *>(dxsh + (size_t)P * 3 * D);
+    const XLdsDualBack L = xlds_dual_back(ne, na, P, D);
+    double *tile = xlds_at<double>(xl, L.tile), *ash = xlds_at<double>(xl, L.ash), *xsh = xlds_at<double>(xl, L.xsh), *dxsh = xlds_at<double>(xl, L.dxsh);
+    int *ctl = xlds_at<int>(xl, L.ctl);
 #ifdef HANK_XSTAMP
     const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
 #endif
-    const XGroup g = xgroup_join(A.sy, ctl);
-    if (!g.ok) return;
-    const int x = g.x, cW = g.c;
-    if (x >= B.groups) return;
-    const int Sact = (na + XRW - 1) / XRW;
-    if (g.S < Sact) { if (threadIdx.x == 0) xfail(A.sy, XERR_PLACEMENT, x); return; }
-    if (cW >= Sact) return;
+    const XMember mb = xmember_join(A.sy, ctl, B.groups, na);
+    if (!mb.on) return;
+    const int x = mb.x, cW = mb.c, Sact = mb.Sact;
     const int son = (x == 0 && cW < 32) ? cW : -1;     // dev stamps (make stamp)
     (void)son;
 #ifdef HANK_XSTAMP
     if (son >= 0 && threadIdx.x == 0) g_xstamps[0][son][0][8] = t_entry;
 #endif
     XSTAMP1(0, son, 9);
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const bool syncw = wv >= ne;
-    const bool sync_duty = blockDim.x > 64 * ne ? syncw : wv == 0;
-    const int e = syncw ? 0 : wv;
+    const XRoles rl = xroles(ne);
+    const int lane = rl.lane, e = rl.e; const bool syncw = rl.syncw, sync_duty = rl.sync_duty;
     const int a = cW * XRW + lane;
     const bool own = !syncw && lane < XRW && a < na;
     // every group holds the same Float64 numbers: group x writes the record arrays j with j % groups == x (pol, ib, A, B, u, v, s, kc)
@@ -1177,17 +1097,8 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     const bool rc0 = 0 % ng == x, rc1 = 1 % ng == x, rc2 = 2 % ng == x, rc3 = 3 % ng == x, rc4 = 4 % ng == x, rc5 = 5 % ng == x, rc6 = 6 % ng == x, rc7 = 7 % ng == x;
     const size_t pt = (size_t)e * na + (own ? a : 0);
     for (int k = threadIdx.x; k < na; k += blockDim.x) ash[k] = c.a[k];
-    for (int k = threadIdx.x; k < P; k += blockDim.x) {
-        xsh[4 * k] = A.xhh[c.n_hh * k]; xsh[4 * k + 1] = A.xhh[c.n_hh * k + 1]; xsh[4 * k + 2] = hh_tr(c, A.xhh, k); xsh[4 * k + 3] = A.rho[k];
-    }
-    for (int k = threadIdx.x; k < P * D; k += blockDim.x) {
-        const int t_ = k / D, d_ = k - t_ * D;
-        const bool on = x * D + d_ < B.N;
-        const size_t ix = (size_t)t_ * B.Ntot + B.n0 + x * D + d_;
-        dxsh[(t_ * 3 + 0) * D + d_] = on ? B.dxr[ix] : 0.0;
-        dxsh[(t_ * 3 + 1) * D + d_] = on ? B.dxw[ix] : 0.0;
-        dxsh[(t_ * 3 + 2) * D + d_] = (on && c.n_hh > 2) ? B.dxt[ix] : 0.0;
-    }
+    xstage_prices(xsh, c, A.xhh, A.rho, P);
+    xstage_dx<D>(dxsh, c, B.dxr, B.dxw, B.dxt, B.Ntot, B.n0, B.N, x, P);
     Consts cl = c;
     cl.a = ash;
     const double ze = c.z[e], xa = c.a[own ? a : 0];
@@ -1289,13 +1200,8 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
                 if constexpr (NE > 0 && STEPS) xtile_mix_reg<SL, NSL, false, true, NK>(tile + (size_t)lane * SL, pr, xopaque(NE), mx);
                 else if constexpr (NE > 0) xtile_mix_reg<SL, NSL, false, false, NK>(tile + (size_t)lane * SL, pr, NE, mx);
                 else xtile_mix_reg<SL, NSL, false, true>(tile + (size_t)lane * SL, pr, xopaque(ne), mx);
-                const double bE = mx[IV] * c.beta;
-                const double ex = CRRA == 1 ? -0.5 : -1.0 / c.gamma;
-                if (pow_domain_error<CRRA>(bE, ex)) set_err(A.err, ERR_DOMAIN, tx, e, a);
-                const double cm = pow_crra<CRRA>(bE, ex);
-                const double rho = xsh[4 * tx + 3];
-                const double s1 = rho * ((cm - (xsh[4 * tx + 1] * ze + xsh[4 * tx + 2])) + xa);
-                const double kc = (CRRA == 1 || c.diet) ? diet_kc<CRRA>(c, s1, rho, 1.0 + xsh[4 * tx], xsh[4 * tx + 1] * ze + xsh[4 * tx + 2], xa) : rho * (c.beta * ex * (cm / bE));
+                const XPoint p = egm_X_point<CRRA>(c, mx[IV], xsh + 4 * tx, ze, xa, A.err, tx, e, a);
+                const double s1 = p.s1, kc = p.kc, rho = xsh[4 * tx + 3];
                 double ds[D];
 #pragma unroll
                 for (int k = 0; k < D; k++) {
@@ -1317,8 +1223,7 @@ __global__ void __launch_bounds__(MAXT) k_xdual_back(XDualBackArgs B) {
     }
     XSTAMP1(0, son, 11);
 }
-// dynamic LDS of k_xdual_back<D>: the carve at its top (tile of D + 1 live slots, ash padded to a pair, xsh, dxsh, ctl)
-static inline size_t x_lds_dual_back(const Consts &c, int D) { return sizeof(double) * ((size_t)xslots(D + 1).SL * c.n_e * 64 + c.n_a + 1 + 4 * (size_t)c.P + 3 * (size_t)c.P * D) + XCTL_BYTES; }
+static inline size_t x_lds_dual_back(const Consts &c, int D) { return xlds_dual_back(c.n_e, c.n_a, c.P, D).bytes; }
 
 // ================================ forward sweeps, source-stationary (round 4) ========================================
 // ONE kernel for the three forward recurrences (ForwardIteration.jl:297-308 and its partials):
@@ -1371,12 +1276,12 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     constexpr int DD = D > 0 ? D : 1;
     constexpr bool PIREG = NSL < 4;                     // the mixing's coefficients in registers
     constexpr bool XB = VAL && D > 0;                   // the Dual pass: streams through buffer descriptors (see XRecOff)
-    extern __shared__ __attribute__((aligned(16))) double xl[];      // carved below; x_lds_fwd (under this kernel) is the host's sum of the same pieces
+    extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_fwd (hank_xlds.h), which also sizes the launch
     const Consts &c = A.c;
     const Record &R = A.R;
     const int ne = c.n_e, na = c.n_a, P = c.P, G = c.G;
-    double *tile = xl;                                  // [ne][64][SL]
-    double *Pish = tile + (size_t)SL * ne * 64;         // [ne*ne] (read when !PIREG)
+    const XLdsFwd L = xlds_fwd(ne, P, D, VAL);
+    double *tile = xlds_at<double>(xl, L.tile), *Pish = xlds_at<double>(xl, L.Pish), *aggsh = xlds_at<double>(xl, L.aggsh);      // [ne][64][SL]; [ne*ne] (read when !PIREG); [ne][64][NAP]:
     // (round 5) the aggregate's terms of a period, per lane: the column waves leave them here and the SYNC wave — idle between its
     // polls — sums them over the columns and the lanes one period later. As eleven waves' own reductions they were 105 of the 562
     // VALU instructions a wave issues per period, three waves deep on a SIMD.
@@ -1384,18 +1289,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     // the sync wave reads it between the period's first barrier and its own all-member poll, which stands in front of the barrier
     // the column waves must pass before they write the next period's terms.
     constexpr int NAP = 2 * NSL;                        // terms per lane: NSL of the first aggregate, NSL of the second
-    double *aggsh = Pish + ((ne * ne + 1) & ~1);        // [ne][64][NAP]
-    int *closh = reinterpret_cast<int *>(aggsh + (size_t)ne * 64 * NAP);           // [P][ne]: the clamped-prefix lengths (a cold uniform load per period otherwise)
-    int *srcsh = closh + (size_t)P * ne;                // [P]
-    int *ctl = srcsh + P;
+    int *closh = xlds_at<int>(xl, L.closh), *srcsh = xlds_at<int>(xl, L.srcsh), *ctl = xlds_at<int>(xl, L.ctl);      // [P][ne] the clamped-prefix lengths, [P]
     if (*A.overflow) return;                            // (every workgroup of the launch reads the same word: written by a kernel that ran before it)
-    const XGroup g = xgroup_join(A.sy, ctl);
-    if (!g.ok) return;
-    const int x = g.x, cW = g.c;
-    if (x >= A.groups) return;
-    const int Sact = (na + XRW - 1) / XRW;
-    if (g.S < Sact) { if (threadIdx.x == 0) xfail(A.sy, XERR_PLACEMENT, x); return; }
-    if (cW >= Sact) return;
+    const XMember mb = xmember_join(A.sy, ctl, A.groups, na);
+    if (!mb.on) return;
+    const int x = mb.x, cW = mb.c, Sact = mb.Sact;
     // every group carries the same D_t: group 0 writes D_t, the virtual rows' mass and the aggregate. The Float64 sweep (D = 0,
     // one group) also writes the per-source record {w, ig D_{t-1}} — whose row 0 needs every member's virtual row, i.e. member 0
     // waits for everybody; the Dual pass (D >= 1) leaves that record to k_xlwg_build: its two own-row loads were dead in seven
@@ -1409,10 +1307,8 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         if (A.all_members || (recL && ((w >> 17) & 1))) w = (w & ~0xffff) | ((Sact - 1) << 8);
         srcsh[k] = w;
     }
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (the wave index in a scalar register: column bases become scalar)
-    const bool syncw = wv >= ne;                        // see k_xtan_back
-    const bool sync_duty = blockDim.x > 64 * ne ? syncw : wv == 0;
-    const int e = syncw ? 0 : wv;
+    const XRoles rl = xroles(ne);
+    const int lane = rl.lane, wv = rl.wv, e = rl.e; const bool syncw = rl.syncw, sync_duty = rl.sync_duty;
     const int r0 = cW * XRW, r = r0 + lane;
     const bool own = !syncw && lane < XRW && r < na;
     const bool virt = !syncw && lane == 63;             // this wave's virtual row: part of the mass point (row 0) kept by this member
@@ -1566,9 +1462,6 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         load_rec(I0, t1, ud[0], 0);
         load_rec(I1, t1, ud[1], 0);
         request_units(t + 2);
-    };
-    auto next_period_loads = [&](int t) {               // t: the period that has just been stored
-        prefetch(min(t + 1, P - 1));
     };
     xbar_arrive(!syncw);                                // the initial state has reached L2: episode 1
     if (sync_duty) xpublish(A.sy, x, cW, 1u);
@@ -1800,7 +1693,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         XSTAMP(1, son, t, 5);
         if (!syncw) {
             asm volatile("; XFWD_BATCH_BEGIN" ::: "memory");
-            next_period_loads(t);
+            prefetch(min(t + 1, P - 1));                // (t: the period that has just been stored)
             XSTAMP(1, son, t, 7);
             asm volatile("; XFWD_BATCH_END\n\ts_waitcnt vmcnt(%0)" ::"n"(XFWD_NLD) : "memory");       // this member's stores have reached L2 ...
             XSTAMP(1, son, t, 8);
@@ -1811,11 +1704,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     }
     if (sync_duty) reduce_agg(P - 1);                   // (every wave wrote its terms before the last barrier)
 }
-// dynamic LDS of k_xfwd<D, VAL>: the carve at its top (tile, Pish padded to a pair, aggsh, closh, srcsh, ctl), with the kernel's own NSL and NAP
-static inline size_t x_lds_fwd(const Consts &c, int D, bool val) {
-    const int NSL = D + (val ? 1 : 0), NAP = 2 * NSL;
-    return sizeof(double) * ((size_t)xslots(NSL).SL * c.n_e * 64 + (size_t)c.n_e * c.n_e + 1 + (size_t)c.n_e * 64 * NAP) + sizeof(int) * ((size_t)c.P * c.n_e + c.P) + XCTL_BYTES;
-}
+static inline size_t x_lds_fwd(const Consts &c, int D, bool val) { return xlds_fwd(c.n_e, c.P, D, val).bytes; }
 
 // the forward sweeps' work units from the lottery record (see k_xfwd), one block per (period, member): thread e cuts column
 // e's walk over the sources of the member's target rows into units — a run [ta, tb) of target rows (relative to the member's

@@ -15,7 +15,7 @@ EDGE_GRIDS, deep clamped prefixes and flat tops), T <= 13. dump, per economy, sa
   hank_ss_jvp: N = 1, 3, 4, 33, every count of outputs, on ks30x3 and hank30x3
   hank_primal under every forced schedule (and the default): aggregates, policies, distributions, every output, their tangents
       after hank_jvp at N = 3, and the Dual pass (hank_primal_jvp, whose lottery writes no segment records) on ks30x3, hank30x3, clamp
-  hank_stationary_dist, hank_primal_batch (K = 1, 3, every count of outputs, policies), hank_jvp_het with both boundary seeds
+  hank_stationary_dist, hank_vfi from a perturbed value (ks30x3, hank30x3), hank_primal_batch (K = 1, 3, every count of outputs, policies), hank_jvp_het with both boundary seeds
 An entry that raises leaves its message in place of its arrays."""
 import os
 import sys
@@ -151,6 +151,11 @@ def dump(inputs, path):
                     D, steps = hb.stationary_dist(hb.policy_seq()[:, :, 0], max_iter=20_000)
                     return {"D": D, "steps": steps}
                 group(f"{ec.name}/stationary_dist", stat)
+                if ec.name in ("ks30x3", "hank30x3"):
+                    def vfi():
+                        V, pol, steps, supnorm = hb.vfi(ec.V * 1.01, xp[:, 0], tol=1e-10, max_iter=5000)
+                        return {"V": V, "policy": pol, "steps": steps, "supnorm": supnorm}
+                    group(f"{ec.name}/vfi", vfi)
                 for K in (1, 3):
                     xs = np.stack([xp * (1.0 + 0.001 * k) for k in range(K)], axis=2)
                     for n_het in range(1, ec.n_het + 1):
