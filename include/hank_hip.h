@@ -158,6 +158,12 @@ int hank_primal_jvp_dev(hank_ctx *ctx, const double *d_xhh, const double *d_dxhh
  * makes the partials HANK_ERR_NOT_READY until the next hank_jvp, under every schedule. */
 int hank_get_policy_seq(hank_ctx *ctx, double *out);
 int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out);
+/* The Young lottery of the last primal, as the record holds it (tests): per period and grid point the bracket lo[P*G], the weight
+ * lw[P*G] and the inverse gap ig[P*G] (0 at either clamp), the packed records lq[P*G] of 16 bytes {double w; int32 lo; int32
+ * flags} (flags bit 0: ig is zero) that the lottery in front of a persistent Dual pass writes for its forward sweep — valid after
+ * hank_primal_jvp[_dev] on the persistent sweeps only — and the wealth grid's inverse gaps iga[n_a] (iga[l] = 1 / (a[l+1] - a[l]),
+ * the last entry 0): ig == (flags & 1 ? 0 : iga[lo]). Null: not asked for. */
+int hank_get_lottery_record(hank_ctx *ctx, int32_t *lo, double *lw, double *ig, void *lq, double *iga);
 /* More than one heterogeneous variable. BackwardIteration keeps one policy sequence per heterogeneous variable
  * (`seqs_data[j][t] = result[varname]`, BackwardIteration.jl:99-112) and ForwardIteration aggregates every one of them with the
  * SAME D_t: `agg_data[j][t] = dot(vec(policy_seqs[varname][t]), D)` (ForwardIteration.jl:303-307). Every forward kernel of the

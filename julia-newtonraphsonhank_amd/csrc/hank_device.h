@@ -8,6 +8,18 @@
 #include <stdint.h>
 #include "hank_geom.h"
 
+// dev knobs of the Dual pass's forward sweep (A-B builds; with both at 0 every kernel is the one before them):
+//   HANK_XFWD_LQ           one 16-byte load of a source's packed lottery record {w, lo, flags} instead of lo, lw and ig
+//                          (k_lottery_lq writes it, k_xfwd<D, true, MAXT, true> reads it; ig comes from a table of the grid's inverse gaps in LDS)
+//   HANK_XFWD_EARLY_BATCH  the next period's unit batch is issued in front of the period's second barrier, not behind it
+//                          (measured and lost, +0.18 ms per step: off)
+#ifndef HANK_XFWD_LQ
+#define HANK_XFWD_LQ 1
+#endif
+#ifndef HANK_XFWD_EARLY_BATCH
+#define HANK_XFWD_EARLY_BATCH 0
+#endif
+
 namespace hank {
 
 struct Consts {
@@ -607,7 +619,9 @@ __device__ inline void set_err(int *err, int code, int t, int e, int j) {
 //   start[r] = max(clo, first source j with lo_j >= r): target row r receives w_j from the sources
 //              in [start[r-1], start[r]) and 1-w_j from those in [start[r], start[r+1]).
 // shlo: the block's dynamic LDS, 2 n_a + 2 ints; sh_clo: one more LDS word
-__device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, int col, int *err, int write_seg, int use_ib, int *shlo, int *sh_clo) {
+// lq (k_lottery for the persistent Dual pass; everybody else: null): the same lo and w once more as ONE 16-byte record per source,
+// {w, lo, flags}, flags bit 0: ig is zero (either clamp) — ig is otherwise 1 / (a[lo+1] - a[lo]), a table of n_a entries (k_iga_build)
+__device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, int col, int *err, int write_seg, int use_ib, int *shlo, int *sh_clo, int4 *lq = nullptr) {
     const int t = col / c.n_e, e = col % c.n_e;
     const size_t base = (size_t)col * c.n_a;  // == t*G + e*n_a
     const int n = c.n_a;
@@ -643,6 +657,7 @@ __device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, i
             ig = 1.0 / gap;
         }
         R.lo[base + j] = l; R.lw[base + j] = w; R.ig[base + j] = ig;
+        if (lq) lq[base + j] = make_int4(__double2loint(w), __double2hiint(w), l, (hi == 0 || hi >= n) ? 1 : 0);
         shlo[j] = (hi == 0) ? -1 : l;   // clamped-low sources sort before every interior bracket
     }
     __syncthreads();

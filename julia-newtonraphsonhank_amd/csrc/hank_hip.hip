@@ -292,6 +292,8 @@ struct hank_ctx {
     size_t lds_max = 65536;
     DevBuf<char> rec_slab;         // the record's ONE allocation
     size_t rec_bytes = 0;
+    int4 *rec_lq = nullptr;        // views into it (HANK_XFWD_LQ; null without): the packed per-source records [P][G] {w, lo, flags} that k_lottery_lq writes in front
+    double *rec_iga = nullptr;     // of a persistent Dual pass, and the grid's inverse gaps [n_a] (k_iga_build, once: hank_create)
     DevBuf<int> d_ibw;             // the wide backward sweep's bracket record (k_wide_prep), valid for the recorded primal or not
     bool seg_valid = true;          // the record's per-target segment records match its lottery (k_lottery writes them except in the persistent Dual pass)
     bool lwg_valid = true;          // the record's per-source records {w, ig D} match it (every forward sweep of a primal writes them except the persistent Dual pass's)
@@ -1002,8 +1004,21 @@ static void x_launch_dual_back(XSection &sec, XWork &X, const Consts &c, int D, 
 }
 // k_xfwd<D, VAL>: D = 0 (the Float64 sweep alone, VAL), 1, 2, 4
 static void x_launch_fwd(XSection &sec, XWork &X, const Consts &c, int D, bool val, const XSweepFwdArgs &a) {
-    const size_t lds = x_lds_fwd(c, D, val || D == 0);
     if (val && D > 0) { X.inst[2] = 0; X.inst[3] = 0; }      // (k_xfwd has no instance of hank_xspec.h's: DESIGN.md section 4)
+#if HANK_XFWD_LQ
+    // the Dual pass (every caller has run k_lottery_lq in front, in this section): the packed record where the table fits beside the carve
+    if (val && D > 0 && x_lds_fwd_lq(c, D) <= (size_t)X.lds_max) {
+        const size_t lds = x_lds_fwd_lq(c, D);
+        x_by_maxt(X, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            if (D == 1) XL(k_xfwd<1, true, MT, true>);
+            else if (D == 2) XL(k_xfwd<2, true, MT, true>);
+            else if (D == 4) { if constexpr (MT == 768) XL(k_xfwd<4, true, MT, true>); }
+        });
+        return;
+    }
+#endif
+    const size_t lds = x_lds_fwd(c, D, val || D == 0);
     x_by_maxt(X, [&](auto mt) {
         constexpr int MT = decltype(mt)::value;
         if (D == 0) XL(k_xfwd<0, true, MT>);
@@ -1095,6 +1110,7 @@ static XRecOff x_rec_off(const hank_ctx *ctx) {
     o.rec = b; o.bytes = (unsigned)ctx->rec_bytes;
     o.pol = off(R.pol); o.ib = off(R.ib); o.A = off(R.A); o.B = off(R.B); o.u = off(R.u); o.v = off(R.v); o.s = off(R.s); o.kc = off(R.kc);
     o.lo = off(R.lo); o.lw = off(R.lw); o.ig = off(R.ig); o.Dseq = off(R.Dseq);
+    o.lq = ctx->rec_lq ? off(ctx->rec_lq) : 0u;
     return o;
 }
 static bool x_dual_addr_fits(const hank_ctx *ctx) {
@@ -1123,9 +1139,16 @@ static int x_back(XSection &sec, XTan *dual = nullptr) {
 }
 // the Young lottery of the policies just written; seg: with the per-target segment records (the Dual pass whose forward sweep reads
 // the lottery through its work units leaves them to be built when somebody asks: ensure_seg)
-static void x_lottery(XSection &sec, bool seg) {
+// lq: a persistent Dual pass follows — with the packed per-source records its forward sweep reads (k_lottery_lq)
+static void x_lottery(XSection &sec, bool seg, bool lq = false) {
     hank_ctx *ctx = sec.ctx;
     const Consts &c = ctx->c;
+#if HANK_XFWD_LQ
+    if (lq) {
+        hipLaunchKernelGGL(k_lottery_lq, dim3((unsigned)(c.P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), sec.stream(), c, ctx->R, c.P * c.n_e, ctx->d_err, seg ? 1 : 0, 1, ctx->rec_lq);
+        return;
+    }
+#endif
     hipLaunchKernelGGL(k_lottery, dim3((unsigned)(c.P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), sec.stream(), c, ctx->R, c.P * c.n_e, ctx->d_err, seg ? 1 : 0, 1);
 }
 // span TAN_BACK: the backward sweep of every pass of the batch, every XCD a group
@@ -1183,6 +1206,7 @@ static int x_tan_fwd(XSection &sec, XTan *w, int p, bool val) {
     XSweepFwdArgs fa = x_fwd_args(ctx, val);
     fa.sy = X.sync + 2 + 2 * p + 1; fa.st = X.st_dD; fa.daggpart = w->daggpart; fa.groups = ps.groups; fa.dpol = w->dpol + ps.dpol_off;
     fa.ro = x_rec_off(ctx); fa.dpol_bytes = (unsigned)((size_t)ctx->c.P * ps.groups * ctx->c.G * ps.D * sizeof(double));
+    fa.iga = ctx->rec_iga ? (unsigned)((const char *)ctx->rec_iga - (const char *)ctx->rec_slab) : 0u;
     x_launch_fwd(sec, X, ctx->c, ps.D, val, fa);
     return HANK_OK;
 }
@@ -1479,6 +1503,9 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
                      o_ib = carve(off, P * G * sizeof(int)), o_lo = carve(off, P * G * sizeof(int)),
                      o_st = carve(off, P * (size_t)c.n_e * (c.n_a + 1) * sizeof(int)), o_clo = carve(off, P * (size_t)c.n_e * sizeof(int)),
                      o_lwg = carve(off, P * G * sizeof(double2)), o_seg = carve(off, P * G * sizeof(int4));
+#if HANK_XFWD_LQ
+        const size_t o_lq = carve(off, P * G * sizeof(int4)), o_iga = carve(off, (size_t)c.n_a * sizeof(double));      // (behind everything else: the other arrays keep their offsets)
+#endif
         HIPC(ctx, ctx->rec_slab.alloc(off));
         ctx->rec_bytes = off;
         char *b = ctx->rec_slab;
@@ -1486,6 +1513,12 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
         R.u = (double *)(b + o_u); R.v = (double *)(b + o_v); R.pol = (double *)(b + o_pol); R.lw = (double *)(b + o_lw);
         R.ig = (double *)(b + o_ig); R.Dseq = (double *)(b + o_D); R.ib = (int *)(b + o_ib); R.lo = (int *)(b + o_lo);
         R.start = (int *)(b + o_st); R.clo = (int *)(b + o_clo); R.lwg = (double2 *)(b + o_lwg); R.seg = (int4 *)(b + o_seg);
+#if HANK_XFWD_LQ
+        ctx->rec_lq = (int4 *)(b + o_lq); ctx->rec_iga = (double *)(b + o_iga);
+        hipLaunchKernelGGL(k_iga_build, dim3((unsigned)((c.n_a + 255) / 256)), dim3(256), 0, ctx->stream, c, ctx->rec_iga);
+        HIPC(ctx, hipGetLastError());
+        HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (whichever stream a sweep runs on later, the table is there)
+#endif
     }
     HIPC(ctx, ctx->d_ss_value.alloc(G));
     ctx->d_ss_D = R.Dseq;      // view
@@ -1714,7 +1747,7 @@ static int x_dual_two(hank_ctx *ctx, XTan *w, const double *xhh, const double *d
     zero_err(ctx, sec.stream());
     x_rho(sec);
     rc = x_back(sec); if (rc) return rc;
-    x_lottery(sec, true);
+    x_lottery(sec, true, true);
     record_rewritten(ctx, true, false);       // (no forward sweep of a Dual pass writes the per-source records)
     x_ensure_rng(sec);
     rc = x_tan_front(sec, w);
@@ -1761,7 +1794,7 @@ static int x_dual_fused(hank_ctx *ctx, XTan *w, const double *xhh, const double 
         x_tan_in(sec, w);
     }
     int rc = x_back(sec, w); if (rc) return rc;
-    x_lottery(sec, false);
+    x_lottery(sec, false, true);
     record_rewritten(ctx, false, false);
     x_ensure_rng(sec);
     HIPC(ctx, ctx->spans.begin(TAN_BACK, sec.stream()));      // (brackets nothing: k_xdual_back is PRIMAL_BACK's. The readers of
@@ -2332,6 +2365,22 @@ int hank_get_policy_seq(hank_ctx *ctx, double *out) {
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
     HIPC(ctx, join_side(ctx));
     HIPC(ctx, hipMemcpyAsync(out, ctx->R.pol, sizeof(double) * (size_t)ctx->c.P * ctx->c.G, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    return HANK_OK;
+}
+
+int hank_get_lottery_record(hank_ctx *ctx, int32_t *lo, double *lw, double *ig, void *lq, double *iga) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
+    if ((lq || iga) && !ctx->rec_lq) return fail(ctx, HANK_ERR_BAD_ARG, "hank_get_lottery_record: this build keeps no packed lottery record");
+    HIPC(ctx, join_side(ctx));
+    const size_t n = (size_t)ctx->c.P * ctx->c.G;
+    if (lo) HIPC(ctx, hipMemcpyAsync(lo, ctx->R.lo, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (lw) HIPC(ctx, hipMemcpyAsync(lw, ctx->R.lw, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (ig) HIPC(ctx, hipMemcpyAsync(ig, ctx->R.ig, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (lq) HIPC(ctx, hipMemcpyAsync(lq, ctx->rec_lq, sizeof(int4) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (iga) HIPC(ctx, hipMemcpyAsync(iga, ctx->rec_iga, sizeof(double) * (size_t)ctx->c.n_a, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return HANK_OK;
 }

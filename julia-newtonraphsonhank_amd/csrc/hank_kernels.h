@@ -395,6 +395,23 @@ __global__ void k_lottery(Consts c, Record R, int ncols, int *err, int write_seg
     if (col >= ncols) return;
     lottery_body(c, R, col, err, write_seg, use_ib, shlo, &sh_clo);
 }
+#if HANK_XFWD_LQ
+// k_lottery in front of a persistent Dual pass: with the packed per-source records lq [ncols][n_a] its forward sweep reads (see
+// lottery_body). A kernel of its own: k_lottery's arguments, and with them its code, stay what every other caller has
+__global__ void k_lottery_lq(Consts c, Record R, int ncols, int *err, int write_seg, int use_ib, int4 *lq) {
+    extern __shared__ int shlo[];
+    __shared__ int sh_clo;
+    const int col = blockIdx.x;
+    if (col >= ncols) return;
+    lottery_body(c, R, col, err, write_seg, use_ib, shlo, &sh_clo, lq);
+}
+// the inverse gaps of the wealth grid, once per context: iga[l] = 1 / (a[l+1] - a[l]) — the expression lottery_body's ig is made
+// with, so that the table's entry IS the record's ig of an interior source with bracket l — and 0 behind the last bracket
+__global__ void k_iga_build(Consts c, double *iga) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l < c.n_a) iga[l] = l + 1 < c.n_a ? 1.0 / (c.a[l + 1] - c.a[l]) : 0.0;
+}
+#endif
 // the same records from the segment offsets k_lottery left (one block per column)
 __global__ void k_seg_build(Consts c, Record R, int ncols) {
     const int col = blockIdx.x, n = c.n_a;

@@ -101,4 +101,17 @@ XLDS_HD inline XLdsFwd xlds_fwd(int n_e, int P, int D, bool val) {      // with 
     return xlds_end(L, o);
 }
 
+// The Dual pass's forward sweep that reads the packed lottery record (k_xfwd<D, true, MAXT, true>): xlds_fwd's pieces where xlds_fwd puts them, then
+// the inverse-gap table in front of ctl. srcsh ends on a multiple of 4: the table starts on the next multiple of 16.
+struct XLdsFwdLq { unsigned tile, aggsh, Pish, closh, srcsh, iga, ctl; size_t bytes; };
+XLDS_HD inline XLdsFwdLq xlds_fwd_lq(int n_e, int n_a, int P, int D) {
+    const XLdsFwd F = xlds_fwd(n_e, P, D, true);
+    XLdsFwdLq L;
+    L.tile = F.tile; L.aggsh = F.aggsh; L.Pish = F.Pish; L.closh = F.closh; L.srcsh = F.srcsh;
+    XLdsCursor o = {F.ctl, F.bytes - XCTL_BYTES};
+    xlds_take(o, (16 - F.ctl % 16) % 16, 1);                 // pad
+    L.iga = xlds_take(o, n_a, 8);                            // [n_a]: 1 / (a[l+1] - a[l]), the last entry 0 (k_iga_build)
+    return xlds_end(L, o);
+}
+
 }  // namespace hank

@@ -587,7 +587,9 @@ struct XRecOff {
     const char *rec;
     unsigned bytes;
     unsigned pol, ib, A, B, u, v, s, kc, lo, lw, ig, Dseq;
-};
+    unsigned lq;                // the packed per-source records {w, lo, flags} (k_lottery_lq), 16-byte aligned. It takes the struct's tail pad:
+};                              // the arguments of every kernel that holds an XRecOff keep their places
+static_assert(sizeof(XRecOff) == 64, "XRecOff: a field more moves the arguments behind it in k_xdual_back and k_xfwd");
 // (x_addr_fits, the host's question whether 32-bit offsets reach every stream of a launch, is plain C++ of its own: hank_xaddr.h)
 
 struct XBackArgs {
@@ -1265,17 +1267,30 @@ struct XSweepFwdArgs {
     XRecOff ro;                 // VAL, D > 0: the record's allocation and its arrays' offsets in it ...
     unsigned dpol_bytes;        // ... and this launch's dpol in bytes (x_addr_fits has checked that 32-bit offsets reach everything). The work units
                                 // keep their POINTER and take a 32-bit scalar index: a unit's address is wave-uniform, a third buffer resource only added spills
+    unsigned iga;               // LQ: the grid's inverse gaps [n_a] in the record's allocation (bytes; k_iga_build). In the struct's tail pad, like XRecOff::lq
 };
 
+// LQ (VAL and D > 0 only; HANK_XFWD_LQ): a source's lo, w and "ig is zero" come as ONE 16-byte load of the packed record, ig itself
+// from the grid's inverse gaps in LDS (xlds_fwd_lq) — two vector-memory instructions per unit less on the one path the mix phase
+// queues on. Without the knob the kernel has no fourth parameter: its instances are, name and code, what they were.
+#if HANK_XFWD_LQ
+template <int D, bool VAL, int MAXT, bool LQ = false>
+#else
 template <int D, bool VAL, int MAXT>
+#endif
 __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #pragma clang fp contract(fast)                         // (round 5) fused multiply-adds in this kernel (the mixing: xtile_mix<.., true>)
+#if !HANK_XFWD_LQ
+    constexpr bool LQ = false;
+#endif
     constexpr int NSL = D + (VAL ? 1 : 0);              // live slots: the D partials, then the value
     constexpr int SP = XSlots<NSL>::SP, SL = XSlots<NSL>::SL;
     constexpr int IV = D;                               // the value's slot
     constexpr int DD = D > 0 ? D : 1;
     constexpr bool PIREG = NSL < 4;                     // the mixing's coefficients in registers
     constexpr bool XB = VAL && D > 0;                   // the Dual pass: streams through buffer descriptors (see XRecOff)
+    constexpr bool EARLYB = XB && HANK_XFWD_EARLY_BATCH != 0;       // ... and issues the unit batch in front of the second barrier
+    static_assert(!LQ || XB, "the packed record is read through the record's descriptor");
     extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_fwd (hank_xlds.h), which also sizes the launch
     const Consts &c = A.c;
     const Record &R = A.R;
@@ -1290,6 +1305,9 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     // the column waves must pass before they write the next period's terms.
     constexpr int NAP = 2 * NSL;                        // terms per lane: NSL of the first aggregate, NSL of the second
     int *closh = xlds_at<int>(xl, L.closh), *srcsh = xlds_at<int>(xl, L.srcsh), *ctl = xlds_at<int>(xl, L.ctl);      // [P][ne] the clamped-prefix lengths, [P]
+    double *igash = nullptr;                            // LQ: [na] the grid's inverse gaps, between srcsh and ctl (xlds_fwd_lq: the other pieces are xlds_fwd's)
+    if constexpr (LQ) { const XLdsFwdLq Q = xlds_fwd_lq(ne, na, P, D); igash = xlds_at<double>(xl, Q.iga); ctl = xlds_at<int>(xl, Q.ctl); }
+    (void)igash;
     if (*A.overflow) return;                            // (every workgroup of the launch reads the same word: written by a kernel that ran before it)
     const XMember mb = xmember_join(A.sy, ctl, A.groups, na);
     if (!mb.on) return;
@@ -1302,6 +1320,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     const bool recD = VAL && x == 0, recL = RECL && x == 1 % A.groups;       // (one group: group 0)
     for (int k = threadIdx.x; k < ne * ne; k += blockDim.x) Pish[k] = c.Pi[k];
     for (int k = threadIdx.x; k < P * ne; k += blockDim.x) closh[k] = R.clo[k];
+    if constexpr (LQ) { for (int k = threadIdx.x; k < na; k += blockDim.x) igash[k] = reinterpret_cast<const double *>(A.ro.rec + A.iga)[k]; }
     for (int k = threadIdx.x; k < P; k += blockDim.x) {
         int w = A.src[(size_t)k * Sact + cW];
         if (A.all_members || (recL && ((w >> 17) & 1))) w = (w & ~0xffff) | ((Sact - 1) << 8);
@@ -1376,6 +1395,8 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     // state is read, in the mixing phase's shadow — so that nothing but scalar setup stands between the barrier behind the source
     // poll and the state loads. A lane that is off reads row 0 of the unit's column (in range; process_* gate on qon / doL / doH)
     int qrow[2] = {0, 0};
+    int qfl[2] = {1, 1};                                // LQ: the packed record's flags (bit 0: ig is zero — the source is clamped at either end of the grid)
+    (void)qfl;
     const int2 *const ubase = A.units + (size_t)cW * XUCAP;       // (the pointer path; XB: unit_ld)
     auto unit_ld = [&](int tu, int u) -> int2 {         // XB: a descriptor's address is wave-uniform — a scalar base and a 32-bit scalar index, no lane arithmetic
         return A.units[(unsigned)((tu * Sact + cW) * XUCAP + u)];
@@ -1399,9 +1420,14 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         if constexpr (XB) {
             const int icb = t * G + ue * na;            // the unit's column in period t (elements; wave-uniform)
             qrow[u] = qvl[u] ? (i - cnt) * 64 + 63 : (real ? (j / XRW) * 64 + j % XRW : 0);
-            qlo[u] = buf_ld32<0>(rrec, j * 4, (int)(A.ro.lo + (unsigned)icb * 4u));
-            qw[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.lw + (unsigned)icb * 8u));
-            qg[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.ig + (unsigned)icb * 8u));
+            if constexpr (LQ) {                         // {w, lo, flags} in one instruction; qg[u]: set_g, where the wave is idle and the record has landed
+                const xv4u q = __builtin_amdgcn_raw_buffer_load_b128(rrec, j * 16, (int)(A.ro.lq + (unsigned)icb * 16u), 0);
+                qw[u] = __hiloint2double((int)q.y, (int)q.x); qlo[u] = (int)q.z; qfl[u] = (int)q.w;
+            } else {
+                qlo[u] = buf_ld32<0>(rrec, j * 4, (int)(A.ro.lo + (unsigned)icb * 4u));
+                qw[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.lw + (unsigned)icb * 8u));
+                qg[u] = buf_ld64<0>(rrec, j * 8, (int)(A.ro.ig + (unsigned)icb * 8u));
+            }
             xload_row_buf<DD>(rdp, j * (8 * D), (int)((unsigned)((t * A.groups + x) * G + ue * na) * (unsigned)(8 * D)), qdp[u]);
             return;
         }
@@ -1422,6 +1448,12 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         }
         const size_t row = qvl[u] ? ((size_t)ue * Sact + (i - cnt)) * 64 + 63 : ((size_t)ue * Sact + j / XRW) * 64 + j % XRW;
         if (qon[u]) rows.load(hb + gx + row, dd[u]);
+    };
+    // LQ: a unit's ig from the table — the record's own bits: k_iga_build's expression is lottery_body's, and a clamped source's
+    // ig is +0. The bracket is one the lottery wrote, lo <= na - 2 (the index is held in the table all the same)
+    auto set_g = [&](auto U) {
+        constexpr int u = decltype(U)::value;
+        if constexpr (LQ) { const double g = igash[min((unsigned)qlo[u], (unsigned)(na - 1))]; qg[u] = (qfl[u] & 1) ? 0.0 : g; }
     };
     const std::integral_constant<int, 0> I0;
     const std::integral_constant<int, 1> I1;
@@ -1512,6 +1544,8 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #pragma unroll
             for (int k = 0; k < SL; k++) z[k] = 0.0;
             xtile_store<SL>(myt, z);                    // (every wave is past the previous period's mixing: xbar_arrive)
+            set_g(I0);                                  // (LQ) the units' records have landed — the drain waited for them — and the wave has
+            set_g(I1);                                  // nothing to do until the source poll is through: not between the state loads and process()
         }
         if (sync_duty) xpoll(A.sy, x, sw & 255, (sw >> 8) & 255, (unsigned)(t + 1));   // this period's source members have published period t-1
         xlds_barrier();
@@ -1613,11 +1647,16 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
                 for (int i0 = u2 < 2 * ne ? 64 : 0; i0 < tot; i0 += 64) {
                     load_rec(I0, t, d, i0);
                     load_state(I0, hb, cur, d, i0);
+                    set_g(I0);                          // (behind the state loads' issue: the record, loaded first, lands first)
                     process(I0, d);
                 }
             }
             if constexpr (RECL) { if (need0) v0 = xwave_sum(v0); }
             take_units();                               // the next period's descriptors (requested a period ago; this wave's loads have all landed here)
+            // (dev knob HANK_XFWD_EARLY_BATCH, off) the unit batch HERE, where its registers are free — process() and the rare units are through —
+            // instead of behind the barrier below; still older than the own-row batch, vmcnt(XFWD_NLD) drains it. Measured: 0.18 ms per step
+            // SLOWER — the path is not idle in front of that barrier, and the period's stores then queue behind the batch
+            if constexpr (EARLYB) next_units_loads(t);
             XSTAMP(1, son, t, 2);
             // the mass point: sources clamped at the first grid point (:54-58) go to row 0 with weight one and no weight
             // partial. Each member sums ITS clamped rows into its virtual row (never combined: everything downstream is
@@ -1639,7 +1678,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         vnz = ((sw >> 16) & 1) != 0;
         const int nxt = cur ^ 1;
         if (!syncw) {
-            next_units_loads(t);                        // accepted by the memory path while the waves mix (see above)
+            if constexpr (!EARLYB) next_units_loads(t); // accepted by the memory path while the waves mix (see above)
             // exogenous transition: D_t[., e] = sum_k D_mid[., k] Pi[k, e] (ForwardIteration.jl:95-99), value and partials in one pass
             double mx[NSL];
             if (PIREG) xtile_mix_reg<SL, NSL, true>(tile + (size_t)lane * SL, pr, ne, mx);
@@ -1705,6 +1744,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     if (sync_duty) reduce_agg(P - 1);                   // (every wave wrote its terms before the last barrier)
 }
 static inline size_t x_lds_fwd(const Consts &c, int D, bool val) { return xlds_fwd(c.n_e, c.P, D, val).bytes; }
+static inline size_t x_lds_fwd_lq(const Consts &c, int D) { return xlds_fwd_lq(c.n_e, c.n_a, c.P, D).bytes; }      // k_xfwd<D, true, ., true>: where it does not fit the device, the launcher takes k_xfwd<D, true>
 
 // the forward sweeps' work units from the lottery record (see k_xfwd), one block per (period, member): thread e cuts column
 // e's walk over the sources of the member's target rows into units — a run [ta, tb) of target rows (relative to the member's

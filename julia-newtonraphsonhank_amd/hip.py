@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "hank_ss_jvp", "hank_ss_jvp_dev", "hank_ss_vjp", "hank_ss_vjp_dev", "hank_last_ss_timings",
     "hank_primal_batch", "hank_primal_batch_dev", "hank_last_batch_timings",
     "hank_ss_batch", "hank_last_ss_batch_timings",
+    "hank_get_lottery_record",
 )
 
 
@@ -108,6 +109,8 @@ def load_library() -> C.CDLL:
     lib.hank_get_policy_seq.argtypes = [vp, dp]
     lib.hank_get_dpolicy_seq.argtypes = [vp, i32, dp]
     lib.hank_get_dist_seq.argtypes = [vp, dp]
+    if hasattr(lib, "hank_get_lottery_record"):      # (an older library named by HANK_HIP_LIB for an A-B has none)
+        lib.hank_get_lottery_record.argtypes = [vp, vp, dp, dp, vp, dp]
     lib.hank_get_het_outputs.argtypes = [vp, i32, dp, i32, dp, dp]
     lib.hank_get_het_outputs_dev.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.hank_set_het_outputs.argtypes = [vp, i32]
@@ -151,6 +154,8 @@ def load_library() -> C.CDLL:
     lib.hank_ss_batch.argtypes = [vp, i32, dp, i32, C.c_double, i32, C.c_double, i32, i32, dp, dp, dp, dp, C.POINTER(i32), dp, C.POINTER(i32)]
     lib.hank_last_ss_batch_timings.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
+        if name == "hank_get_lottery_record" and not hasattr(lib, name):
+            continue
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
     _lib = lib
@@ -668,6 +673,16 @@ class HouseholdBlock:
         out = np.empty((self.n_a, self.n_e, self.P), order="F")
         self._chk(self._lib.hank_get_policy_seq(self._ctx, _p(out)))
         return out
+
+    def lottery_record(self):
+        """the Young lottery of the last primal as the record holds it (hank_get_lottery_record): lo, lw, ig of shape (n_a, n_e, P),
+        the packed records lq (structured: w, lo, flags) of the same shape and the grid's inverse gaps iga (n_a,)."""
+        shp = (self.n_a, self.n_e, self.P)
+        lo, lw, ig = np.empty(shp, np.int32, order="F"), np.empty(shp, order="F"), np.empty(shp, order="F")
+        lq = np.empty(shp, np.dtype([("w", "<f8"), ("lo", "<i4"), ("flags", "<i4")]), order="F")
+        iga = np.empty(self.n_a)
+        self._chk(self._lib.hank_get_lottery_record(self._ctx, lo.ctypes.data_as(C.c_void_p), _p(lw), _p(ig), lq.ctypes.data_as(C.c_void_p), _p(iga)))
+        return {"lo": lo, "lw": lw, "ig": ig, "lq": lq, "iga": iga}
 
     def dist_seq(self) -> np.ndarray:
         out = np.empty((self.n_a, self.n_e, self.P), order="F")
