@@ -164,6 +164,12 @@ int hank_get_dpolicy_seq(hank_ctx *ctx, int32_t N, double *out);
  * hank_primal_jvp[_dev] on the persistent sweeps only — and the wealth grid's inverse gaps iga[n_a] (iga[l] = 1 / (a[l+1] - a[l]),
  * the last entry 0): ig == (flags & 1 ? 0 : iga[lo]). Null: not asked for. */
 int hank_get_lottery_record(hank_ctx *ctx, int32_t *lo, double *lw, double *ig, void *lq, double *iga);
+/* Its counterpart for the persistent forward sweeps (tests): the work units the recorded lottery was cut into. With S =
+ * ceil(n_a / 63) members: src[P*S], per period and member (source members lo | hi << 8 | a column is clamped << 16 | member 0 records
+ * row 0's full mass << 17 | units << 18), and units[P*S*64*2], per period, member and unit the pair {e | ja << 4 | cnt << 16,
+ * ta | tb << 8 | nv << 16}; a member's slots behind its count hold nothing. HANK_ERR_NOT_READY unless a persistent sweep has run at
+ * the recorded primal. Null: not asked for. */
+int hank_get_forward_units(hank_ctx *ctx, int32_t *src, int32_t *units);
 /* More than one heterogeneous variable. BackwardIteration keeps one policy sequence per heterogeneous variable
  * (`seqs_data[j][t] = result[varname]`, BackwardIteration.jl:99-112) and ForwardIteration aggregates every one of them with the
  * SAME D_t: `agg_data[j][t] = dot(vec(policy_seqs[varname][t]), D)` (ForwardIteration.jl:303-307). Every forward kernel of the

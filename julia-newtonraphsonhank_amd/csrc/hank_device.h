@@ -621,6 +621,9 @@ __device__ inline void set_err(int *err, int code, int t, int e, int j) {
 // shlo: the block's dynamic LDS, 2 n_a + 2 ints; sh_clo: one more LDS word
 // lq (k_lottery for the persistent Dual pass; everybody else: null): the same lo and w once more as ONE 16-byte record per source,
 // {w, lo, flags}, flags bit 0: ig is zero (either clamp) — ig is otherwise 1 / (a[lo+1] - a[lo]), a table of n_a entries (k_iga_build)
+// LEAN (k_xdual_front, in front of the one-pass persistent Dual pass; everybody else: false): only what that pass reads is written —
+// lq and clo; lo, lw, ig, start and seg are left to k_lottery when a reader comes (ensure_lottery). shlo / shst are built as always.
+template <bool LEAN = false>
 __device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, int col, int *err, int write_seg, int use_ib, int *shlo, int *sh_clo, int4 *lq = nullptr) {
     const int t = col / c.n_e, e = col % c.n_e;
     const size_t base = (size_t)col * c.n_a;  // == t*G + e*n_a
@@ -656,7 +659,7 @@ __device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, i
             w = (p - c.a[l]) / gap;
             ig = 1.0 / gap;
         }
-        R.lo[base + j] = l; R.lw[base + j] = w; R.ig[base + j] = ig;
+        if constexpr (!LEAN) { R.lo[base + j] = l; R.lw[base + j] = w; R.ig[base + j] = ig; }
         if (lq) lq[base + j] = make_int4(__double2loint(w), __double2hiint(w), l, (hi == 0 || hi >= n) ? 1 : 0);
         shlo[j] = (hi == 0) ? -1 : l;   // clamped-low sources sort before every interior bracket
     }
@@ -673,6 +676,7 @@ __device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, i
             for (int r = (cur < 0 ? 0 : cur + 1); r <= n; r++) shst[r] = n;
     }
     __syncthreads();
+    if constexpr (LEAN) return;
     for (int r = threadIdx.x; r <= n; r += blockDim.x) st[r] = shst[r];
     // per target row: its three segment bounds in one 16-byte record — what the launch family's gather reads (and k_xstat, and
     // k_fn_impulse); a third of this kernel's bytes, and the persistent Dual pass reads none of them: written there on demand
@@ -680,6 +684,26 @@ __device__ __forceinline__ void lottery_body(const Consts &c, const Record &R, i
     if (write_seg)
         for (int r = threadIdx.x; r < n; r += blockDim.x)
             R.seg[base + r] = make_int4(r > 0 ? shst[r - 1] : shst[r], shst[r], shst[r + 1], 0);
+}
+
+// lottery_body's bracket search for ONE record entry, for a caller that needs only "is this source clamped at the first grid point"
+// (k_xdual_front: row 0 of the columns of the period before). The same statements as in lottery_body above, which keeps its own
+// copy: calling this one there reordered an instruction of k_lottery, and every existing kernel stays what it was.
+// -> hi with grid[hi - 1] < p <= grid[hi]; hi == 0: clamped at the first grid point, hi >= n_a: at the last
+__device__ __forceinline__ int lottery_hi(const Consts &c, const Record &R, size_t idx, double p, int use_ib) {
+    const int n = c.n_a;
+    int lo = -1, hi = n;
+    if (use_ib) {
+        const int g0 = min(max(R.ib[idx], 0), n - 2);
+        const double a0 = c.a[g0], a1 = c.a[g0 + 1];
+        if (a0 < p && p <= a1) { lo = g0; hi = g0 + 1; }
+        else if (g0 > 0 && p <= a0 && c.a[g0 - 1] < p) { lo = g0 - 1; hi = g0; }
+    }
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (c.a[mid] < p) lo = mid; else hi = mid;
+    }
+    return hi;
 }
 
 // ---- the transposed steps: one body each for the sweep kernel (hank_adjoint.h) and the steady-state loop's (hank_ssdiff.h) --------

@@ -131,6 +131,10 @@ struct XWork {
     DevBuf<int> unit_overflow;                // set by k_xunits_fwd when a member has more units than XUCAP
     int ucap = 64;                            // dev knob HANK_XUCAP (read once, at hank_create): a smaller budget, to exercise the overflow path
     bool rng_valid = false;                   // srcF / unitsF belong to the recorded lottery
+    DevBuf<int2> stageU;                      // [P][Sact][n_e][XU_ROWS] k_xdual_front's staged units per (period, member, column), read by k_xunits_pack
+    DevBuf<int4> stageM;                      // [P][Sact][n_e] their {count, source members lo, hi, has virtual lanes}
+    bool front = true;                        // knob HANK_XDUAL_FRONT=0 (read once, at hank_create): the one-pass Dual pass keeps k_lottery_lq + k_xunits_fwd in front
+    int front_poison = 0;                     // tests only, HANK_XDUAL_FRONT_POISON=1 (read once, at hank_create): the lean front fills what it leaves unwritten (k_xdual_front)
     bool neigh = true;                        // dev knob HANK_XNEIGH=0 (read once, at hank_create): every period waits for every member
     bool syncwave = true;                     // dev knob HANK_XSYNCWAVE=0 (read once, at hank_create): wave 0 polls instead of an extra wave
     int lds_max = 65536;
@@ -297,6 +301,7 @@ struct hank_ctx {
     DevBuf<int> d_ibw;             // the wide backward sweep's bracket record (k_wide_prep), valid for the recorded primal or not
     bool seg_valid = true;          // the record's per-target segment records match its lottery (k_lottery writes them except in the persistent Dual pass)
     bool lwg_valid = true;          // the record's per-source records {w, ig D} match it (every forward sweep of a primal writes them except the persistent Dual pass's)
+    bool lot_valid = true;          // the record's lo, lw, ig and start match its policies (every lottery writes them except the lean front of the one-pass persistent Dual pass: ensure_lottery)
     long long lwg_builds = 0;       // times k_xlwg_build ran (hank_info)
     bool wprep_valid = false;
     std::list<WTan> wtans;         // most recently used first
@@ -350,9 +355,10 @@ static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
 }
 // the record was rewritten (or is about to be, by work already enqueued): what was derived from the old one goes, and so does the
 // batch. seg_written: the per-target segment records were written with it (k_lottery writes them except in the persistent Dual pass);
-// lwg_written: so were the per-source records {w, ig D} (the forward sweep writes them except the persistent Dual pass's)
-static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written) {
-    ctx->primal_done = true; ctx->seg_valid = seg_written; ctx->lwg_valid = lwg_written;
+// lwg_written: so were the per-source records {w, ig D} (the forward sweep writes them except the persistent Dual pass's);
+// lot_written: so were lo, lw, ig and start (every lottery but k_xdual_front's) — seg and lwg are made from them, so neither is valid without
+static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written, bool lot_written = true) {
+    ctx->primal_done = true; ctx->seg_valid = seg_written && lot_written; ctx->lwg_valid = lwg_written && lot_written; ctx->lot_valid = lot_written;
     ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->hx.valid = false;
     batch_none(ctx);
     cot_none(ctx);
@@ -907,6 +913,10 @@ static int x_setup(hank_ctx *ctx) {
     HIPC(ctx, X.unitsF.alloc(P * X.Sact * XUCAP));
     HIPC(ctx, X.unit_overflow.alloc(1));
     HIPC(ctx, hipMemsetAsync(X.unit_overflow, 0, sizeof(int), ctx->stream));
+    if (X.front && ctx->rec_lq) {      // the staging of k_xdual_front
+        HIPC(ctx, X.stageU.alloc(P * X.Sact * c.n_e * XU_ROWS));
+        HIPC(ctx, X.stageM.alloc(P * X.Sact * c.n_e));
+    }
     if (const char *ng = getenv("HANK_XNEIGH")) X.neigh = atoi(ng) != 0;
     if (const char *uc = getenv("HANK_XUCAP")) X.ucap = std::min(XUCAP, std::max(1, atoi(uc)));
     {   // the bound on every wait inside a persistent sweep, in 100 MHz ticks (read once, here)
@@ -1002,12 +1012,21 @@ static void x_launch_dual_back(XSection &sec, XWork &X, const Consts &c, int D, 
     else if (sp.ne == 11) by_crra(std::integral_constant<int, 11>());
     else by_crra(std::integral_constant<int, 0>());
 }
+// does the Dual pass's forward sweep take the packed-record instance k_xfwd<D, true, ., true>? (x_launch_fwd's rule, asked by x_dual_fused
+// too: only that instance can run behind the lean front)
+static bool x_fwd_serves_lq(const XWork &X, const Consts &c, int D) {
+#if HANK_XFWD_LQ
+    return D > 0 && x_lds_fwd_lq(c, D) <= (size_t)X.lds_max;
+#else
+    return false;
+#endif
+}
 // k_xfwd<D, VAL>: D = 0 (the Float64 sweep alone, VAL), 1, 2, 4
 static void x_launch_fwd(XSection &sec, XWork &X, const Consts &c, int D, bool val, const XSweepFwdArgs &a) {
     if (val && D > 0) { X.inst[2] = 0; X.inst[3] = 0; }      // (k_xfwd has no instance of hank_xspec.h's: DESIGN.md section 4)
 #if HANK_XFWD_LQ
-    // the Dual pass (every caller has run k_lottery_lq in front, in this section): the packed record where the table fits beside the carve
-    if (val && D > 0 && x_lds_fwd_lq(c, D) <= (size_t)X.lds_max) {
+    // the Dual pass (every caller has written the packed record in front, in this section: k_lottery_lq or k_xdual_front): the packed record where the table fits beside the carve
+    if (val && x_fwd_serves_lq(X, c, D)) {
         const size_t lds = x_lds_fwd_lq(c, D);
         x_by_maxt(X, [&](auto mt) {
             constexpr int MT = decltype(mt)::value;
@@ -1037,17 +1056,30 @@ static void x_launch_tan_back(XSection &sec, const XWork &X, const Consts &c, in
         else if (D == 4) { if constexpr (MT == 768) XL(k_xtan_back<4, MT>); }
     });
 }
+// before a reader of R.lo, R.lw, R.ig or R.start: the lean front of the one-pass persistent Dual pass (k_xdual_front) wrote none of
+// them — k_lottery on the recorded policies makes them, the same body and the same bits as every other lottery (it rewrites clo
+// with the values it has). Every host path that lets a kernel read one of the four comes through here: DESIGN.md section 2a.
+static int ensure_lottery(hank_ctx *ctx, hipStream_t s = nullptr) {
+    if (ctx->lot_valid) return HANK_OK;
+    const Consts &c = ctx->c;
+    hipLaunchKernelGGL(k_lottery, dim3((unsigned)(c.P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s ? s : ctx->stream, c, ctx->R, c.P * c.n_e, ctx->d_err, 0, 1);
+    HIPC(ctx, hipGetLastError());
+    ctx->lot_valid = true;
+    return HANK_OK;
+}
 // the forward sweeps' geometry at the recorded lottery (once per primal)
 static void x_ensure_rng(XSection &sec) {
     hank_ctx *ctx = sec.ctx;
     XWork &X = ctx->xw;
     if (X.rng_valid) return;
+    (void)ensure_lottery(ctx, sec.stream());      // (k_xunits_fwd reads R.start)
     hipLaunchKernelGGL(k_xunits_fwd, dim3((unsigned)ctx->c.P, (unsigned)X.Sact), dim3(256), 0, sec.stream(), ctx->c, ctx->R, X.Sact, X.srcF, X.unitsF, X.unit_overflow, X.ucap);
     X.rng_valid = true;
 }
 
 static int ensure_seg(hank_ctx *ctx) {       // before a reader of R.seg (launch-family forward tangent sweeps, hank_fake_news)
     if (ctx->seg_valid) return HANK_OK;
+    { const int rc = ensure_lottery(ctx); if (rc) return rc; }
     hipLaunchKernelGGL(k_seg_build, dim3((unsigned)(ctx->c.P * ctx->c.n_e)), dim3(256), 0, ctx->stream, ctx->c, ctx->R, ctx->c.P * ctx->c.n_e);
     HIPC(ctx, hipGetLastError());
     ctx->seg_valid = true;
@@ -1057,6 +1089,7 @@ static int ensure_seg(hank_ctx *ctx) {       // before a reader of R.seg (launch
 // hank_fake_news): a persistent Dual pass leaves the record to be made from what it wrote (lw, ig, D_t, the virtual rows' mass)
 static int ensure_lwg(hank_ctx *ctx) {
     if (ctx->lwg_valid) return HANK_OK;
+    { const int rc = ensure_lottery(ctx); if (rc) return rc; }
     const XWork &X = ctx->xw;
     hipLaunchKernelGGL(k_xlwg_build, dim3((unsigned)(ctx->c.P * ctx->c.n_e)), dim3(256), 0, ctx->stream, ctx->c, ctx->R, X.Dvirt, X.D0own, X.Sact);
     HIPC(ctx, hipGetLastError());
@@ -1150,6 +1183,17 @@ static void x_lottery(XSection &sec, bool seg, bool lq = false) {
     }
 #endif
     hipLaunchKernelGGL(k_lottery, dim3((unsigned)(c.P * c.n_e)), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), sec.stream(), c, ctx->R, c.P * c.n_e, ctx->d_err, seg ? 1 : 0, 1);
+}
+// the front of the one-pass Dual pass whose forward sweep reads the packed record: the lean lottery with the cut of every column in
+// its launch (k_xdual_front), then the units packed member by member (k_xunits_pack) — what x_lottery(sec, false, true) and
+// x_ensure_rng leave behind for that sweep, without lo, lw, ig and start (the caller marks the record: ensure_lottery)
+static void x_front(XSection &sec) {
+    hank_ctx *ctx = sec.ctx; XWork &X = ctx->xw;
+    const Consts &c = ctx->c;
+    hipLaunchKernelGGL(k_xdual_front, dim3((unsigned)(c.P * c.n_e)), dim3(512), sizeof(int) * (2 * (size_t)c.n_a + 2), sec.stream(), c, ctx->R, c.P * c.n_e, ctx->d_err, ctx->rec_lq,
+                       X.Sact, X.stageU.get(), X.stageM.get(), X.front_poison);
+    hipLaunchKernelGGL(k_xunits_pack, dim3((unsigned)((c.P * X.Sact + 3) / 4)), dim3(256), 0, sec.stream(), c, ctx->R, X.Sact, X.stageU.get(), X.stageM.get(), X.srcF.get(), X.unitsF.get(),
+                       X.unit_overflow.get(), X.ucap);
 }
 // span TAN_BACK: the backward sweep of every pass of the batch, every XCD a group
 static int x_tan_back(XSection &sec, XTan *w) {
@@ -1560,6 +1604,8 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     if (const char *pm = getenv("HANK_PRIMAL_MEMO")) ctx->memo_on = atoi(pm) != 0;
     if (const char *xd = getenv("HANK_XDUAL_BACK")) ctx->xdual_back = atoi(xd) != 0;
     ctx->xw.xspec = x_spec_mode(getenv("HANK_XSPEC"));
+    if (const char *xf = getenv("HANK_XDUAL_FRONT")) ctx->xw.front = atoi(xf) != 0;
+    if (const char *xp = getenv("HANK_XDUAL_FRONT_POISON")) ctx->xw.front_poison = atoi(xp) != 0 ? 1 : 0;
     int rc = HANK_OK;
     if (ctx->schedule == 0) rc = build_primal_graphs(ctx);
     else rc = x_setup(ctx);
@@ -1794,9 +1840,16 @@ static int x_dual_fused(hank_ctx *ctx, XTan *w, const double *xhh, const double 
         x_tan_in(sec, w);
     }
     int rc = x_back(sec, w); if (rc) return rc;
-    x_lottery(sec, false, true);
-    record_rewritten(ctx, false, false);
-    x_ensure_rng(sec);
+    if (X.front && X.stageU && ctx->rec_lq && x_fwd_serves_lq(X, ctx->c, w->passes[0].D)) {
+        // the lean front: k_xfwd<D, true, ., true> reads lq, clo, the grid's inverse gaps and the work units, and nothing else of the lottery
+        x_front(sec);
+        record_rewritten(ctx, false, false, false);
+        X.rng_valid = true;
+    } else {
+        x_lottery(sec, false, true);
+        record_rewritten(ctx, false, false);
+        x_ensure_rng(sec);
+    }
     HIPC(ctx, ctx->spans.begin(TAN_BACK, sec.stream()));      // (brackets nothing: k_xdual_back is PRIMAL_BACK's. The readers of
     HIPC(ctx, ctx->spans.end(TAN_BACK, sec.stream(), 1));      // hank_last_timings count on a valid slot of about 0 ms)
     HIPC(ctx, ctx->spans.begin(TAN_FWD, sec.stream()));
@@ -2375,12 +2428,28 @@ int hank_get_lottery_record(hank_ctx *ctx, int32_t *lo, double *lw, double *ig, 
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
     if ((lq || iga) && !ctx->rec_lq) return fail(ctx, HANK_ERR_BAD_ARG, "hank_get_lottery_record: this build keeps no packed lottery record");
     HIPC(ctx, join_side(ctx));
+    if (lo || lw || ig) { const int rc = ensure_lottery(ctx); if (rc) return rc; }
     const size_t n = (size_t)ctx->c.P * ctx->c.G;
     if (lo) HIPC(ctx, hipMemcpyAsync(lo, ctx->R.lo, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
     if (lw) HIPC(ctx, hipMemcpyAsync(lw, ctx->R.lw, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     if (ig) HIPC(ctx, hipMemcpyAsync(ig, ctx->R.ig, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     if (lq) HIPC(ctx, hipMemcpyAsync(lq, ctx->rec_lq, sizeof(int4) * n, hipMemcpyDeviceToHost, ctx->stream));
     if (iga) HIPC(ctx, hipMemcpyAsync(iga, ctx->rec_iga, sizeof(double) * (size_t)ctx->c.n_a, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    return HANK_OK;
+}
+
+// the forward sweeps' work units of the recorded lottery as the persistent sweeps read them (tests): src [P][Sact], units
+// [P][Sact][XUCAP][2]; the slots of a member behind its count (src >> 18) hold nothing
+int hank_get_forward_units(hank_ctx *ctx, int32_t *src, int32_t *units) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    const XWork &X = ctx->xw;
+    if (!ctx->primal_done || !X.ready || !X.rng_valid) return fail(ctx, HANK_ERR_NOT_READY, "hank_get_forward_units: no persistent sweep has cut the recorded lottery into work units");
+    HIPC(ctx, join_side(ctx));
+    const size_t n = (size_t)ctx->c.P * X.Sact;
+    if (src) HIPC(ctx, hipMemcpyAsync(src, X.srcF, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (units) HIPC(ctx, hipMemcpyAsync(units, X.unitsF, sizeof(int2) * n * XUCAP, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     return HANK_OK;
 }
@@ -2515,6 +2584,7 @@ static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
 static int ensure_adj_seg(hank_ctx *ctx) {
     const Consts &c = ctx->c;
     if (ctx->adj_seg_valid) return HANK_OK;
+    { const int rc = ensure_lottery(ctx); if (rc) return rc; }
     hipLaunchKernelGGL(k_adj_seg, dim3((unsigned)(c.P * c.n_e)), dim3(256), sizeof(int) * ((size_t)c.n_a + 1), ctx->stream, c, ctx->R, c.P * c.n_e, ctx->d_adj_sb);
     HIPC(ctx, hipGetLastError());
     ctx->adj_seg_valid = true;
@@ -2527,6 +2597,7 @@ static int ensure_hx_record(hank_ctx *ctx) {
     const Consts &c = ctx->c;
     HxRecord &h = ctx->hx;
     if (h.valid) return HANK_OK;
+    { const int rc = ensure_lottery(ctx); if (rc) return rc; }
     const size_t P = c.P, SX = hx_count(ctx);
     if (!h.S) {
         HIPC(ctx, h.f.alloc(SX * P * c.G));

@@ -40,6 +40,7 @@
 #include "hank_kernels.h"
 #include "hank_xaddr.h"
 #include "hank_xlds.h"
+#include "hank_xunits.h"
 #include <type_traits>
 
 namespace hank {
@@ -1845,6 +1846,97 @@ __global__ void k_xunits_fwd(Consts c, Record R, int Sact, int *src, int2 *units
         if (sany0) { ml = 0; mh = Sact - 1; }           // the units with virtual lanes read every member's virtual row
         const int allv = (m == 0 && vnz && anyopen) ? 1 : 0;
         src[(size_t)t * Sact + m] = ml | (mh << 8) | (anyclo << 16) | (allv << 17) | (tot << 18);
+    }
+}
+
+// ---- the front of the one-pass persistent Dual pass (between k_xdual_back and k_xfwd<D, true, ., true>): two launches that stand for
+// k_lottery_lq and k_xunits_fwd and write only what that pass reads --------------------------------------------------------------
+// k_xdual_front, one block per column (t, e) like k_lottery. Lottery: lottery_body's lean arm — lq and clo; lo, lw, ig, start and
+// seg stay unwritten (the host marks the record: ensure_lottery runs k_lottery before the first reader). Cut: with the column's
+// start table still in LDS (shst), a thread per member cuts the column's walk into that member's units (xu_cut,
+// hank_xunits.h: the end of each unit by bisection, then the chain is followed) and stages them per
+// (t, member, column): su [P][Sact][n_e][XU_ROWS] the units, sm [P][Sact][n_e] {count, source members lo, hi, a unit has virtual lanes}.
+// A column has at most XU_ROWS units of a member, so the staging never truncates: what overflows is a member's TOTAL, in k_xunits_pack.
+// vnz — the virtual rows hold mass in period t: some column of t - 1 is clamped — is the one thing a column needs from other columns:
+// row 0 of every column of pol[t - 1] under lottery_body's own test (a clamped prefix, where the policy is monotone, starts at row 0;
+// where it is not, the error word is set and the call fails).
+// poison (tests only: HANK_XDUAL_FRONT_POISON): the arrays left unwritten are filled with values no reader can take for a lottery —
+// lw, ig NaN; lo, start 0 (in range) — so that a reader that skipped ensure_lottery fails a parity test instead of reading the last record.
+// dynamic LDS: 2 n_a + 2 ints (lottery_body's)
+static_assert(XU_ROWS == XRW && XU_LANES == 64, "hank_xunits.h cuts for this sweep geometry");
+__global__ void __launch_bounds__(512) k_xdual_front(Consts c, Record R, int ncols, int *err, int4 *lq, int Sact, int2 *su, int4 *sm, int poison) {
+    extern __shared__ int shlo[];
+    __shared__ int sh_clo, sh_vnz;
+    const int col = blockIdx.x;
+    if (col >= ncols) return;
+    const int ne = c.n_e, n = c.n_a;
+    const int t = col / ne, e = col - t * ne;
+    bool v = false;
+    if (t > 0 && (int)threadIdx.x < ne) {
+        const size_t i0 = (size_t)(t - 1) * c.G + (size_t)threadIdx.x * n;
+        v = lottery_hi(c, R, i0, R.pol[i0], 1) == 0;
+    }
+    if (threadIdx.x == 0) sh_vnz = 0;
+    lottery_body<true>(c, R, col, err, 0, 1, shlo, &sh_clo, lq);      // (its barriers order sh_vnz's reset, and shst is complete behind it)
+    if (v) atomicOr(&sh_vnz, 1);
+    if (poison) {
+        const size_t base = (size_t)col * n;
+        const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int j = threadIdx.x; j < n; j += blockDim.x) { R.lo[base + j] = 0; R.lw[base + j] = qnan; R.ig[base + j] = qnan; }
+        for (int r = threadIdx.x; r <= n; r += blockDim.x) R.start[(size_t)col * (n + 1) + r] = 0;
+    }
+    __syncthreads();
+    const int *shst = shlo + n;
+    const int clo = sh_clo;
+    const bool vnz = sh_vnz != 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    auto S = [&](int r) { return min(max(shst[min(max(r, 0), n)], 0), n); };
+    // a thread per member, the members dealt round the block's waves (Sact / waves lanes of each: the walks of a wave's lanes run in
+    // lockstep and take as long as the longest, so few share a wave): the serial form of the cut, every read from LDS
+    for (int m = wave + nwaves * lane; m < Sact; m += nwaves * 64) {
+        const int r0 = m * XRW, nrows = min(XRW, n - r0);
+        const size_t slot = ((size_t)t * Sact + m) * ne + e;
+        int2 *out = su + slot * XU_ROWS;
+        const XuCut q = xu_cut(S, [&](int ta) { return xu_next(S, clo, vnz, Sact, r0, nrows, ta); }, [&](int k, int x, int y) { out[k] = make_int2(x, y); },
+                               clo, vnz, r0, nrows, Sact, e, m, XU_ROWS);
+        sm[slot] = make_int4(q.n, q.mlo, q.mhi, q.anyv);
+    }
+}
+// k_xunits_pack, one wave per (period, member): the prefix over the columns' staged counts, the units copied to units[t][m][k]
+// numbered column by column, the src word — bit for bit k_xunits_fwd's — and the overflow flag. A launch of its own behind
+// k_xdual_front: a "last block of the period finishes" counter inside that launch would be a hand-off between XCDs within one launch.
+__global__ void __launch_bounds__(256) k_xunits_pack(Consts c, Record R, int Sact, const int2 *su, const int4 *sm, int *src, int2 *units, int *overflow, int ucap) {
+    const int lane = threadIdx.x & 63, w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (w >= c.P * Sact) return;                         // (wave-uniform)
+    const int ne = c.n_e, t = w / Sact, m = w - t * Sact;
+    int4 q = make_int4(0, m, m, 0);
+    int clo = 0, clop = 0;
+    if (lane < ne) {
+        q = sm[(size_t)w * ne + lane];
+        clo = R.clo[(size_t)t * ne + lane];
+        clop = t > 0 ? R.clo[(size_t)(t - 1) * ne + lane] : 0;
+    }
+    const int cnt = min(max(q.x, 0), XU_ROWS);
+    int inc = cnt;
+    for (int off = 1; off < 64; off <<= 1) { const int up = __shfl_up(inc, off, 64); if (lane >= off) inc += up; }
+    const int excl = inc - cnt;
+    int tot = __shfl(inc, 63, 64);
+    int mycol = -1, myoff = 0;
+    for (int e = 0; e < ne; e++) {
+        const int oe = __shfl(excl, e, 64), ce = __shfl(cnt, e, 64);
+        if (lane >= oe && lane < oe + ce) { mycol = e; myoff = lane - oe; }
+    }
+    if (mycol >= 0 && lane < XUCAP) units[(size_t)w * XUCAP + lane] = su[((size_t)w * ne + mycol) * XU_ROWS + myoff];
+    int ml = min(q.y, m), mh = max(q.z, m);
+    for (int off = 32; off > 0; off >>= 1) { ml = min(ml, __shfl_xor(ml, off, 64)); mh = max(mh, __shfl_xor(mh, off, 64)); }
+    const bool sany0 = __ballot(lane < ne && q.w != 0) != 0, anyclo = __ballot(lane < ne && clo > 0) != 0;
+    const bool anyopen = __ballot(lane < ne && clo <= 0) != 0, vnz = __ballot(clop > 0) != 0;
+    if (lane == 0) {
+        if (tot > ucap) { atomicExch(overflow, 1); tot = min(tot, XUCAP); }      // (ucap = XUCAP but for the dev knob HANK_XUCAP)
+        ml = min(max(ml, 0), Sact - 1); mh = min(max(mh, 0), Sact - 1);
+        if (sany0) { ml = 0; mh = Sact - 1; }           // the units with virtual lanes read every member's virtual row
+        const int allv = (m == 0 && vnz && anyopen) ? 1 : 0;
+        src[w] = ml | (mh << 8) | ((anyclo ? 1 : 0) << 16) | (allv << 17) | (tot << 18);
     }
 }
 

@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "hank_ss_jvp", "hank_ss_jvp_dev", "hank_ss_vjp", "hank_ss_vjp_dev", "hank_last_ss_timings",
     "hank_primal_batch", "hank_primal_batch_dev", "hank_last_batch_timings",
     "hank_ss_batch", "hank_last_ss_batch_timings",
-    "hank_get_lottery_record",
+    "hank_get_lottery_record", "hank_get_forward_units",
 )
 
 
@@ -111,6 +111,8 @@ def load_library() -> C.CDLL:
     lib.hank_get_dist_seq.argtypes = [vp, dp]
     if hasattr(lib, "hank_get_lottery_record"):      # (an older library named by HANK_HIP_LIB for an A-B has none)
         lib.hank_get_lottery_record.argtypes = [vp, vp, dp, dp, vp, dp]
+    if hasattr(lib, "hank_get_forward_units"):       # (likewise)
+        lib.hank_get_forward_units.argtypes = [vp, vp, vp]
     lib.hank_get_het_outputs.argtypes = [vp, i32, dp, i32, dp, dp]
     lib.hank_get_het_outputs_dev.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.hank_set_het_outputs.argtypes = [vp, i32]
@@ -154,7 +156,7 @@ def load_library() -> C.CDLL:
     lib.hank_ss_batch.argtypes = [vp, i32, dp, i32, C.c_double, i32, C.c_double, i32, i32, dp, dp, dp, dp, C.POINTER(i32), dp, C.POINTER(i32)]
     lib.hank_last_ss_batch_timings.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
-        if name == "hank_get_lottery_record" and not hasattr(lib, name):
+        if name in ("hank_get_lottery_record", "hank_get_forward_units") and not hasattr(lib, name):
             continue
         if name != "hank_last_error":
             getattr(lib, name).restype = C.c_int
@@ -683,6 +685,14 @@ class HouseholdBlock:
         iga = np.empty(self.n_a)
         self._chk(self._lib.hank_get_lottery_record(self._ctx, lo.ctypes.data_as(C.c_void_p), _p(lw), _p(ig), lq.ctypes.data_as(C.c_void_p), _p(iga)))
         return {"lo": lo, "lw": lw, "ig": ig, "lq": lq, "iga": iga}
+
+    def forward_units(self):
+        """the persistent forward sweeps' work units of the recorded lottery (hank_get_forward_units): src (P, S) and units
+        (P, S, 64, 2) as the library lays them out, S = ceil(n_a / 63) members; src >> 18 is a member's unit count."""
+        S = (self.n_a + 62) // 63
+        src, units = np.empty((self.P, S), np.int32), np.empty((self.P, S, 64, 2), np.int32)
+        self._chk(self._lib.hank_get_forward_units(self._ctx, src.ctypes.data_as(C.c_void_p), units.ctypes.data_as(C.c_void_p)))
+        return src, units
 
     def dist_seq(self) -> np.ndarray:
         out = np.empty((self.n_a, self.n_e, self.P), order="F")
