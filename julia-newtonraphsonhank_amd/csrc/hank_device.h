@@ -19,8 +19,26 @@
 #ifndef HANK_XFWD_EARLY_BATCH
 #define HANK_XFWD_EARLY_BATCH 0
 #endif
+// dev knobs of the forward sweeps' source walk (the cost of ds_add_f64 by its lanes' addresses: scripts/ubench/lds_add_bench.hip,
+// DESIGN.md section 4; with both at 0 every kernel is the one before them):
+//   HANK_XFWD_TILE_SOA     k_xfwd<D, true, MAXT, true>'s tile is slot-major, [column][slot][lane] (hank_xlds.h): adds into consecutive
+//                          target rows hit consecutive banks. Same sums in the same order: the outputs' bits do not move
+//                          (measured and kept, -0.075 ms per step: on)
+//   HANK_XFWD_FLAT_TR      a flat work unit (more than XFLAT_NUM / XFLAT_DEN sources per target row) deals its sources four apart
+//                          inside each 16-lane group, in EVERY k_xfwd (same-address lanes of a group are added one after the other)
+//                          (measured and lost, +0.03 ms per step alone and beside the slot-major tile: off)
+#ifndef HANK_XFWD_TILE_SOA
+#define HANK_XFWD_TILE_SOA 1
+#endif
+#ifndef HANK_XFWD_FLAT_TR
+#define HANK_XFWD_FLAT_TR 0
+#endif
 
 namespace hank {
+
+// a work unit is FLAT at more than 3/2 sources per target row: from there on some 16-lane group holds a run of two sources on one row,
+// 20 cycles per ds_add_f64 in the slot-major tile against 16 for sources dealt four apart (32 and 44 against 16 and 11 at three and four)
+constexpr int XFLAT_NUM = 3, XFLAT_DEN = 2;
 
 struct Consts {
     int n_a, n_e, G, P;

@@ -135,6 +135,8 @@ struct XWork {
     DevBuf<int4> stageM;                      // [P][Sact][n_e] their {count, source members lo, hi, has virtual lanes}
     bool front = true;                        // knob HANK_XDUAL_FRONT=0 (read once, at hank_create): the one-pass Dual pass keeps k_lottery_lq + k_xunits_fwd in front
     int front_poison = 0;                     // tests only, HANK_XDUAL_FRONT_POISON=1 (read once, at hank_create): the lean front fills what it leaves unwritten (k_xdual_front)
+    bool packed = true;                       // dev knob HANK_XFWD_PACKED=0 (read once, at hank_create): the Dual pass's forward sweep reads the three-array record (k_xfwd<D, true>, the
+                                              // [lane][SL] tile) — what tests/test_gpu_xfwd_walk.py holds the packed-record instance's slot-major tile against, byte for byte
     bool neigh = true;                        // dev knob HANK_XNEIGH=0 (read once, at hank_create): every period waits for every member
     bool syncwave = true;                     // dev knob HANK_XSYNCWAVE=0 (read once, at hank_create): wave 0 polls instead of an extra wave
     int lds_max = 65536;
@@ -918,6 +920,7 @@ static int x_setup(hank_ctx *ctx) {
         HIPC(ctx, X.stageM.alloc(P * X.Sact * c.n_e));
     }
     if (const char *ng = getenv("HANK_XNEIGH")) X.neigh = atoi(ng) != 0;
+    if (const char *pk = getenv("HANK_XFWD_PACKED")) X.packed = atoi(pk) != 0;
     if (const char *uc = getenv("HANK_XUCAP")) X.ucap = std::min(XUCAP, std::max(1, atoi(uc)));
     {   // the bound on every wait inside a persistent sweep, in 100 MHz ticks (read once, here)
         double ms = 20.0;
@@ -1016,7 +1019,7 @@ static void x_launch_dual_back(XSection &sec, XWork &X, const Consts &c, int D, 
 // too: only that instance can run behind the lean front)
 static bool x_fwd_serves_lq(const XWork &X, const Consts &c, int D) {
 #if HANK_XFWD_LQ
-    return D > 0 && x_lds_fwd_lq(c, D) <= (size_t)X.lds_max;
+    return X.packed && D > 0 && x_lds_fwd_lq(c, D) <= (size_t)X.lds_max;
 #else
     return false;
 #endif

@@ -114,4 +114,13 @@ XLDS_HD inline XLdsFwdLq xlds_fwd_lq(int n_e, int n_a, int P, int D) {
     return xlds_end(L, o);
 }
 
+// ... and its tile SLOT-MAJOR (HANK_XFWD_TILE_SOA): [column][slot][lane] in doubles, the NSL = D + 1 live slots only — no pad slot,
+// NSL / SL of the piece's bytes (5/6 at D = 4), the piece and everything behind it where xlds_fwd puts them. Consecutive target rows
+// of one slot are consecutive doubles: the source walk's 8-byte adds and the mixing's 8-byte reads meet no bank twice in 16 lanes.
+constexpr int XTILE_SOA_SLOT = 64;                                         // doubles from a slot to the next of the same column and lane
+XLDS_HD inline unsigned xtile_soa_at(int NSL, int col, int slot, int lane) {      // an entry's offset in the tile piece (bytes)
+    return (unsigned)(((col * NSL + slot) * XTILE_SOA_SLOT + lane) * 8);
+}
+XLDS_HD inline size_t xtile_soa_bytes(int n_e, int NSL) { return (size_t)n_e * NSL * XTILE_SOA_SLOT * 8; }      // <= the tile piece: NSL <= xslots(NSL).SL
+
 }  // namespace hank

@@ -559,6 +559,73 @@ __device__ __forceinline__ void xtile_mix_reg(const double *tl, const double (&p
     }
 }
 
+// ---- the SLOT-MAJOR tile of k_xfwd<D, true, MAXT, true> (HANK_XFWD_TILE_SOA; hank_xlds.h: xtile_soa): [column k][slot][lane] in
+// doubles. The source walk's ds_add_f64 into consecutive target rows then hit consecutive banks (8.4 cycles per wave-instruction
+// against 16 at the 48-byte row stride of [lane][SL = 6]: scripts/ubench/lds_add_bench.hip), and a lane's slot is read by one
+// conflict-free ds_read_b64. The functions beside xtile_store, xtile_store_n, xtile_mix and xtile_mix_reg, which every other kernel
+// keeps; t and tl point at this lane's entry of column 0's (the store: of the lane's own column's) slot 0.
+// (a volatile read in the LDS address space: ONE ds_read_b64 each — paired into ds_read2st64_b64 the reads take four times the LDS
+// cycles, and volatile through a generic pointer is a flat load, which the counted vector-memory batch must not see)
+typedef const volatile __attribute__((address_space(3))) double xlds_cvdouble;
+__device__ __forceinline__ double xtile_soa_ld(const double *p) { return *(xlds_cvdouble *)p; }
+template <int NS>
+__device__ __forceinline__ void xtile_soa_store(double *t, const double *v) {      // v holds NS values
+#pragma unroll
+    for (int q = 0; q < NS; q++) t[q * XTILE_SOA_SLOT] = v[q];
+}
+// xtile_mix's sums, operand by operand: k ascending, the first column by itself, U columns' reads in front of their multiply-adds
+template <int NS, bool FMA = false>
+__device__ __forceinline__ void xtile_soa_mix(const double *tl, const double *P, int ps, int ne, double *out) {
+    constexpr int ks = XTILE_SOA_SLOT * NS;
+    auto rd = [&](int k, double *v) {
+#pragma unroll
+        for (int q = 0; q < NS; q++) v[q] = xtile_soa_ld(tl + (size_t)k * ks + q * XTILE_SOA_SLOT);
+    };
+    auto acc = [&](double p, const double *v) {
+#pragma unroll
+        for (int q = 0; q < NS; q++) out[q] = FMA ? __builtin_fma(p, v[q], out[q]) : out[q] + p * v[q];
+    };
+    {
+        double v[NS];
+        rd(0, v);
+        const double p = P[0];
+#pragma unroll
+        for (int q = 0; q < NS; q++) out[q] = p * v[q];
+    }
+    int k = 1;
+    constexpr int U = 5;
+    for (; k + U <= ne; k += U) {
+        double v[U][NS], p[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) { rd(k + u, v[u]); p[u] = P[(k + u) * ps]; }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; u++) acc(p[u], v[u]);
+    }
+#pragma unroll 1
+    for (; k < ne; k++) {
+        double v[NS];
+        rd(k, v);
+        acc(P[k * ps], v);
+    }
+}
+// xtile_mix_reg's sums, operand by operand
+template <int NS, bool FMA = false, bool BRK = false, int NK = 16>
+__device__ __forceinline__ void xtile_soa_mix_reg(const double *tl, const double (&pr)[NK], int ne, double *out) {
+    constexpr int ks = XTILE_SOA_SLOT * NS;
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        if (BRK && k > 0 && k >= ne) break;
+        if (BRK || k < ne) {
+            double v[NS];
+#pragma unroll
+            for (int q = 0; q < NS; q++) v[q] = tl[(size_t)k * ks + q * XTILE_SOA_SLOT];
+#pragma unroll
+            for (int q = 0; q < NS; q++) out[q] = k == 0 ? pr[k] * v[q] : (FMA ? __builtin_fma(pr[k], v[q], out[q]) : out[q] + pr[k] * v[q]);
+        }
+    }
+}
+
 // Per-period inputs that are uniform over the workgroup, staged in LDS once for the whole sweep (as a per-period global load each is a
 // cold round trip on the critical path). xsh[P][4]: r_t, w_t, tr_t, rho_t = 1/(1+r_t)
 __device__ __forceinline__ void xstage_prices(double *xsh, const Consts &c, const double *xhh, const double *rho, int P) {
@@ -1292,6 +1359,21 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     constexpr bool XB = VAL && D > 0;                   // the Dual pass: streams through buffer descriptors (see XRecOff)
     constexpr bool EARLYB = XB && HANK_XFWD_EARLY_BATCH != 0;       // ... and issues the unit batch in front of the second barrier
     static_assert(!LQ || XB, "the packed record is read through the record's descriptor");
+    // SOA (HANK_XFWD_TILE_SOA): this instance's tile is slot-major, [column][slot][lane] (xtile_soa_at, hank_xlds.h); every other
+    // instance keeps [column][lane][SL]. The strides, in doubles, of a target row, a slot and a column of the tile:
+    // (without the knob the text is the parent's, token by token: the register allocation of several instances follows it)
+#if HANK_XFWD_TILE_SOA
+    constexpr bool SOA = LQ;
+    constexpr int TCS = SOA ? XTILE_SOA_SLOT * NSL : 64 * SL;
+    static_assert(NSL <= SL, "the slot-major tile lies inside the tile piece");
+#define XT_COL(c) (SOA ? tile + (size_t)(c) * (XTILE_SOA_SLOT * NSL) : tile + (size_t)(c) * 64 * SL)
+#define XT_ROW(p, r) (SOA ? (p) + (size_t)(r) : (p) + (size_t)(r) * SL)
+#define XT_SLOT(p, k) (SOA ? (p) + (k) * XTILE_SOA_SLOT : (p) + (k))
+#else
+#define XT_COL(c) (tile + (size_t)(c) * 64 * SL)
+#define XT_ROW(p, r) ((p) + (size_t)(r) * SL)
+#define XT_SLOT(p, k) ((p) + (k))
+#endif
     extern __shared__ __attribute__((aligned(16))) double xl[];      // laid out by xlds_fwd (hank_xlds.h), which also sizes the launch
     const Consts &c = A.c;
     const Record &R = A.R;
@@ -1355,7 +1437,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     __amdgpu_buffer_rsrc_t rrec, rdp;
     if constexpr (XB) { rrec = buf_rsrc(A.ro.rec, A.ro.bytes); rdp = buf_rsrc(A.dpol, A.dpol_bytes); }
     const int ipt = e * na + (own ? r : 0), igx = x * iGM, ihs = XG * iGM, islot = (e * Sact + cW) * 64;
+#if HANK_XFWD_TILE_SOA
+    double *const myt = SOA ? tile + (size_t)e * TCS + lane : tile + ((size_t)e * 64 + lane) * SL;      // this lane's entry of its column (SOA: its slot 0)
+#else
     double *const myt = tile + ((size_t)e * 64 + lane) * SL;
+#endif
     double mxp[NSL];                                    // this lane's row of the previous period (the state it stored)
 #pragma unroll
     for (int k = 0; k < NSL; k++) mxp[k] = 0.0;
@@ -1409,10 +1495,27 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     };
     // (branch-free: every lane loads — a lane beyond the unit's sources the unit's last row, an empty unit row 0 of column 0 — and
     // qon / qvl say what counts)
+    // FLAT_TR (HANK_XFWD_FLAT_TR): a FLAT unit — more than XFLAT_NUM / XFLAT_DEN sources per row of its target run [ta, tb), asked of the
+    // descriptor in scalar code — deals a trip's 64 sources four apart inside each 16-lane group: lane g * 16 + j walks source 4 j + g.
+    // ds_add_f64 is served in 16-lane groups and lanes of a group on ONE address are added one after the other (12 cycles per wave-
+    // instruction and extra lane: scripts/ubench/lds_add_bench.hip); consecutive sources of a flat unit share their target rows, sources
+    // four apart mostly do not. Every kernel that walks the units takes the same map (this lambda): the lanes' order at a tile entry is
+    // the order of its terms, and the value's bits are the same whichever k_xfwd carries it.
+#if HANK_XFWD_FLAT_TR
+    const int ltr = (lane & 15) * 4 + (lane >> 4);
+    auto unit_flat = [&](int2 d) -> bool {              // (wave-uniform; an empty unit is not flat)
+        const int cnt = (d.x >> 16) & 0xfff, ta = d.y & 0xff, tb = (d.y >> 8) & 0xff;
+        return XFLAT_DEN * cnt > XFLAT_NUM * (tb - ta);
+    };
+    auto unit_lane = [&](int2 d) -> int { return unit_flat(d) ? ltr : lane; };      // this lane's source within a trip of unit d
+#define XUNIT_LANE(d) unit_lane(d)
+#else
+#define XUNIT_LANE(d) lane
+#endif
     auto load_rec = [&](auto U, int t, int2 d, int i0) {
         constexpr int u = decltype(U)::value;
         const int ue = d.x & 15, ja = (d.x >> 4) & 0xfff, cnt = (d.x >> 16) & 0xfff, nv = (d.y >> 16) & 0xff;
-        const int i = i0 + lane;
+        const int i = i0 + XUNIT_LANE(d);
         const bool real = i < cnt;
         qvl[u] = !real && i < cnt + nv;                 // a member's virtual row riding on source row 0's record
         qon[u] = real || qvl[u];
@@ -1442,7 +1545,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
         const int ue = d.x & 15, ja = (d.x >> 4) & 0xfff, cnt = (d.x >> 16) & 0xfff;
 #pragma unroll
         for (int k = 0; k < SP; k++) dd[u][k] = 0.0;
-        const int i = i0 + lane, j = ja + i;
+        const int i = i0 + XUNIT_LANE(d), j = ja + i;    // (load_rec's source)
         if constexpr (XB) {
             rows.load_vs(qrow[u], hc * ihs + igx + ue * Sact * 64, dd[u]);        // unconditional: the compiler counts the loads in flight
             return;
@@ -1544,8 +1647,11 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             double z[SL];
 #pragma unroll
             for (int k = 0; k < SL; k++) z[k] = 0.0;
+#if HANK_XFWD_TILE_SOA
+            if constexpr (SOA) xtile_soa_store<NSL>(myt, z); else
+#endif
             xtile_store<SL>(myt, z);                    // (every wave is past the previous period's mixing: xbar_arrive)
-            set_g(I0);                                  // (LQ) the units' records have landed — the drain waited for them — and the wave has
+            set_g(I0);                                 // (LQ) the units' records have landed — the drain waited for them — and the wave has
             set_g(I1);                                  // nothing to do until the source poll is through: not between the state loads and process()
         }
         if (sync_duty) xpoll(A.sy, x, sw & 255, (sw >> 8) & 255, (unsigned)(t + 1));   // this period's source members have published period t-1
@@ -1575,7 +1681,7 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             auto process_pc = [&](auto U, int2 d) {
                 constexpr int u = decltype(U)::value;
                 const int ta = d.y & 0xff, tb = (d.y >> 8) & 0xff;
-                double *const colt = tile + (size_t)(d.x & 15) * 64 * SL;
+                double *const colt = XT_COL(d.x & 15);
                 const double w = qw[u], w1 = 1.0 - w;
                 double gD = qg[u], Dv = 0.0;
                 if constexpr (VAL) { Dv = dd[u][IV]; gD = qg[u] * Dv; }
@@ -1583,20 +1689,24 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
                 const int tl = qlo[u] - r0, th = tl + 1;
                 const bool doL = qon[u] && tl >= ta && tl < tb, doH = qon[u] && th >= ta && th < tb;
                 const int thp = __builtin_amdgcn_update_dpp(-2, doH ? th : -2, 0x138, 0xf, 0xf, false);        // lane i-1's upper target (wave_shr:1; lane 0: none)
+#if HANK_XFWD_FLAT_TR
+                const bool take = doL && thp == tl && !unit_flat(d);      // (a transposed unit's DPP neighbours are not its source neighbours)
+#else
                 const bool take = doL && thp == tl;
+#endif
                 const bool given = __builtin_amdgcn_update_dpp(0, take ? 1 : 0, 0x130, 0xf, 0xf, false) != 0;   // lane i+1 adds my upper part with its lower one (wave_shl:1)
-                double *const tpl = colt + (size_t)(doL ? tl : 0) * SL, *const tph = colt + (size_t)(doH ? th : 0) * SL;
+                double *const tpl = XT_ROW(colt, doL ? tl : 0), *const tph = XT_ROW(colt, doH ? th : 0);
 #pragma unroll
                 for (int k = 0; k < D; k++) {
                     const double hk = w * dd[u][k] + gD * qdp[u][k];
                     const double hp = xdpp<0x138, 0xf, 0xf>(hk);
                     const double lk = w1 * dd[u][k] - gD * qdp[u][k];
-                    if (doL) lds_add(tpl + k, take ? lk + hp : lk);
-                    if (doH && !given) lds_add(tph + k, hk);
+                    if (doL) lds_add(XT_SLOT(tpl, k), take ? lk + hp : lk);
+                    if (doH && !given) lds_add(XT_SLOT(tph, k), hk);
                 }
                 if constexpr (VAL) {                    // (the VALUE keeps one add per part: D_t — the record — is the same bits whichever kernel carries it)
-                    if (doL) lds_add(tpl + IV, w1 * Dv);
-                    if (doH) lds_add(tph + IV, w * Dv);
+                    if (doL) lds_add(XT_SLOT(tpl, IV), w1 * Dv);
+                    if (doH) lds_add(XT_SLOT(tph, IV), w * Dv);
                 }
                 if constexpr (!VAL) {
                     if (doL && !qvl[u]) {               // (every unclamped source has exactly one lower target: its aggregate term is taken here, once)
@@ -1609,17 +1719,17 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
                 constexpr int u = decltype(U)::value;
                 if (!qon[u]) return;
                 const int ta = d.y & 0xff, tb = (d.y >> 8) & 0xff;
-                double *const colt = tile + (size_t)(d.x & 15) * 64 * SL;
+                double *const colt = XT_COL(d.x & 15);
                 const double w = qw[u], w1 = 1.0 - w;
                 double gD = qg[u], Dv = 0.0;
                 if constexpr (VAL) { Dv = dd[u][IV]; gD = qg[u] * Dv; }
                 else { if (qvl[u]) gD = 0.0; }          // (a virtual row's mass is part of the recorded ig * D of row 0)
                 const int tl = qlo[u] - r0, th = tl + 1;
                 if (tl >= ta && tl < tb) {              // (every unclamped source has exactly one lower target: its aggregate term is taken here, once)
-                    double *tp = colt + (size_t)tl * SL;
+                    double *tp = XT_ROW(colt, tl);
 #pragma unroll
-                    for (int k = 0; k < D; k++) lds_add(tp + k, w1 * dd[u][k] - gD * qdp[u][k]);
-                    if constexpr (VAL) lds_add(tp + IV, w1 * Dv);
+                    for (int k = 0; k < D; k++) lds_add(XT_SLOT(tp, k), w1 * dd[u][k] - gD * qdp[u][k]);
+                    if constexpr (VAL) lds_add(XT_SLOT(tp, IV), w1 * Dv);
                     if constexpr (!VAL) {
                         if (!qvl[u]) {
 #pragma unroll
@@ -1628,10 +1738,10 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
                     }
                 }
                 if (th >= ta && th < tb) {
-                    double *tp = colt + (size_t)th * SL;
+                    double *tp = XT_ROW(colt, th);
 #pragma unroll
-                    for (int k = 0; k < D; k++) lds_add(tp + k, w * dd[u][k] + gD * qdp[u][k]);
-                    if constexpr (VAL) lds_add(tp + IV, w * Dv);
+                    for (int k = 0; k < D; k++) lds_add(XT_SLOT(tp, k), w * dd[u][k] + gD * qdp[u][k]);
+                    if constexpr (VAL) lds_add(XT_SLOT(tp, IV), w * Dv);
                 }
             };
             // (narrow kernels — one or two slots per tile row — keep one add per part: at D = 1 the exchange costs more than the
@@ -1669,6 +1779,9 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
 #pragma unroll
                 for (int k = 0; k < NSL; k++) cT[k] = xwave_reduce63(cT[k]);
             }
+#if HANK_XFWD_TILE_SOA
+            if constexpr (SOA) { if (virt) xtile_soa_store<NSL>(myt, cT); } else
+#endif
             if (virt) xtile_store_n<SL, NSL>(myt, cT);
         }
         XSTAMP(1, son, t, 3);
@@ -1682,6 +1795,12 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
             if constexpr (!EARLYB) next_units_loads(t); // accepted by the memory path while the waves mix (see above)
             // exogenous transition: D_t[., e] = sum_k D_mid[., k] Pi[k, e] (ForwardIteration.jl:95-99), value and partials in one pass
             double mx[NSL];
+#if HANK_XFWD_TILE_SOA
+            if constexpr (SOA) {
+                if (PIREG) xtile_soa_mix_reg<NSL, true>(tile + lane, pr, ne, mx);
+                else xtile_soa_mix<NSL, true>(tile + lane, Pish + ne * e, 1, ne, mx);
+            } else
+#endif
             if (PIREG) xtile_mix_reg<SL, NSL, true>(tile + (size_t)lane * SL, pr, ne, mx);
             else xtile_mix<SL, NSL, true>(tile + (size_t)lane * SL, Pish + ne * e, 1, ne, mx);
             if (live) {
@@ -1744,6 +1863,10 @@ __global__ void __launch_bounds__(MAXT) k_xfwd(XSweepFwdArgs A) {
     }
     if (sync_duty) reduce_agg(P - 1);                   // (every wave wrote its terms before the last barrier)
 }
+#undef XUNIT_LANE
+#undef XT_COL
+#undef XT_ROW
+#undef XT_SLOT
 static inline size_t x_lds_fwd(const Consts &c, int D, bool val) { return xlds_fwd(c.n_e, c.P, D, val).bytes; }
 static inline size_t x_lds_fwd_lq(const Consts &c, int D) { return xlds_fwd_lq(c.n_e, c.n_a, c.P, D).bytes; }      // k_xfwd<D, true, ., true>: where it does not fit the device, the launcher takes k_xfwd<D, true>
 
