@@ -384,7 +384,9 @@ int hank_vjp_het_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_
  * kernel family serves. WHICH PERIOD IS READ: the distribution side and both transposed loops read period 0 of the record
  * (D_ss = the boundary's initial distribution D_0, the lottery of the first policy, D_1 as the post-transition weights of the
  * aggregates); the value loop reads the interpolation brackets of period 1 and the knots and prices of period 0 (one period of
- * the backward tangent sweep spans two records). At a stationary record every period holds the same steady state.
+ * the backward tangent sweep spans two records). At a stationary record every period holds the same steady state. For that
+ * reason a context of ONE period (T = 2) is refused by both entries before anything is launched: HANK_ERR_BAD_ARG, "needs a
+ * record of at least two periods (T >= 3)". hank_fake_news[_het] reads period 0 alone and serves T = 2 (one lag).
  *
  * hank_ss_jvp == the partials ForwardDiff carries through the VFI (SteadyState.jl:132-141) and through invariant_dist
  * (ForwardIteration.jl:446-530) inside find_ss's Jacobian (SteadyState.jl:195), N directions at once:

@@ -22,15 +22,19 @@ ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "julia-newtonraphsonhank_amd" / "csrc"
 UNITS = ("hank_hip.hip", "hank_ssdiff.hip")      # the library's translation units (csrc/Makefile)
 
-# why a kernel no test launches is not launched (regex on the demangled name -> one line). The per-period tangent kernels are
-# instantiated for row groups 1, 2, 4 and both lane widths; ensure_tanwork (csrc/hank_hip.hip) picks among them by batch width.
+# why a kernel is at zero in a run (regex on the demangled name -> one line). The per-period tangent kernels are instantiated for row
+# groups 1, 2, 4 and both lane widths; ensure_tanwork (csrc/hank_hip.hip) picks among them by batch width. Every instance is launched
+# by tests/test_gpu_launch_lanes.py (profiles/launch_lanes_kernel_coverage.txt); a run without that module shows these at zero.
+_LANES = "; tests/test_gpu_launch_lanes.py alone launches it"
 REASONS = {
-    r"k_(tan|fused)_fwd<1, (double|HIP_vector_type<double, 2u>), true>": "source-stationary form (16-lane groups and up) with 1 row group: the default gives that form 2; dev knob HANK_RG_F=1 only",
-    r"k_(tan|fused)_fwd<2, (double|HIP_vector_type<double, 2u>), false>": "target-stationary gather with 2 row groups: the default takes that gather only below 16-lane groups, with 1; HANK_RG_F=2 / HANK_FWD_SS=0 only",
-    r"k_(tan|fused)_fwd<4,": "4 forward row groups: never the default; dev knob HANK_RG_F=4 only",
-    r"k_(tan|fused)_back<1,": "1 backward row group: never the default; dev knob HANK_RG_B=1 only",
-    r"k_(tan|fused)_back<4,": "4 backward row groups: the per-period launches at >= 128 lanes of directions (N >= 256 even, >= 128 odd); "
-                             "the default sends such batches to the wide sweeps and no test forces the launches there",
+    r"k_(tan|fused)_fwd<1, (double|HIP_vector_type<double, 2u>), true>": "source-stationary form (16-lane groups and up) with 1 row group: the default gives that form 2; dev knob HANK_RG_F=1" + _LANES,
+    r"k_(tan|fused)_fwd<2, (double|HIP_vector_type<double, 2u>), false>": "target-stationary gather with 2 row groups: the default takes that gather only below 16-lane groups, with 1; HANK_RG_F=2 / HANK_FWD_SS=0" + _LANES,
+    r"k_(tan|fused)_fwd<4,": "4 forward row groups: never the default; dev knob HANK_RG_F=4" + _LANES,
+    r"k_(tan|fused)_back<1,": "1 backward row group: never the default; dev knob HANK_RG_B=1" + _LANES,
+    r"k_(tan|fused)_back<4, double>": "4 backward row groups, one direction per lane: the per-period launches at an odd N >= 129, which the default sends to the wide "
+                                      "sweeps where those exist" + _LANES,
+    r"k_tan_back<4, HIP_vector_type<double, 2u> >": "4 backward row groups, two directions per lane: hank_jvp on the per-period launches at an even N >= 256, which the default "
+                                                    "sends to the wide sweeps where those exist" + _LANES,
 }
 
 

@@ -4,7 +4,7 @@ device context, and section 4, which runs sweeps on one.
 
 0. the owners: `close` (the suite's tolerance function: a relative figure on the array's largest entry) and `within` (the entry-wise
    one: every entry inside a running error bound of tests/ld_refs.py), `raw_block` / `block` (a context under HANK_* variables, every
-   variable restored), `model_args` / `oracle_of` (a model's constructor arguments), `hank_economy` / `hank_x` (the one-asset HANK
+   variable restored: `hank_env`), `model_args` / `oracle_of` (a model's constructor arguments), `hank_economy` / `hank_x` (the one-asset HANK
    economy and its input path). The oracle's references are methods of oracle.oracle.Oracle: block, block_het, het_outputs, vfi;
 1. the references of hank_vjp[_het]: the CPU oracle's Jacobian from unit tangents (`oracle_jacobian`, `oracle_jacobian_het` /
    `jacobian_het` for every heterogeneous output, transposed by `jt`) and the numpy
@@ -21,6 +21,7 @@ device context, and section 4, which runs sweeps on one.
    batch width against the oracle and a launch-schedule context, for a model or for raw constructor arguments;
 5. the entry-wise tests' exact inputs and their long double references (`entry_backward`, `entry_refs`, `entry_forward`,
    `entry_forward_ref`, `push_distribution`), shared by tests/test_ld_refs_host.py and tests/test_gpu_entrywise.py."""
+import contextlib
 import os
 
 import numpy as np
@@ -62,9 +63,11 @@ def within(a, ref, bound, what, skip=None):
     return float(ratio.max())
 
 
-def raw_block(hank, args, schedule, **env):
-    """hank.HouseholdBlock(*args) created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
-    env = {"HANK_SCHEDULE": schedule, **env}
+@contextlib.contextmanager
+def hank_env(**env):
+    """the given HANK_* variables set (None: unset) for the body, every one restored after it. `raw_block` creates under it; a
+    variable the library reads later than hank_create — HANK_RG_B, HANK_RG_F, HANK_FWD_SS, read when a width's workspace is built —
+    needs the first sweep of that width inside it as well."""
     old = {k: os.environ.get(k) for k in env}
     for k, v in env.items():
         if v is None:
@@ -72,13 +75,19 @@ def raw_block(hank, args, schedule, **env):
         else:
             os.environ[k] = str(v)
     try:
-        return hank.HouseholdBlock(*args)
+        yield
     finally:
         for k, v in old.items():
             if v is None:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def raw_block(hank, args, schedule, **env):
+    """hank.HouseholdBlock(*args) created under HANK_SCHEDULE=schedule (None: the default) and the given HANK_* variables."""
+    with hank_env(HANK_SCHEDULE=schedule, **env):
+        return hank.HouseholdBlock(*args)
 
 
 def raw_args(grid, z, Pi, m, T):

@@ -123,6 +123,32 @@ def test_ss_diff_widths_reach_the_geometries_they_name(ask):
     assert 65 - SS_JVP_TABLE[65][1] == 1 and 130 // 2 - SS_JVP_TABLE[130][1] == 1 and 34 // 2 - SS_VJP_TABLE[34][1] == 1   # one live lane in the second block
 
 
+LAUNCH_LANES = {129: (1, 129), 256: (2, 128), 130: (2, 65)}      # tests/test_gpu_launch_lanes.py's widths -> (directions per lane, NV)
+TAN_RG_BACK_4 = 128              # tan_rg: 4 backward row groups per wave from this many lanes of directions on
+
+
+def test_launch_lane_widths_straddle_the_row_group_threshold(ask):
+    """tests/test_gpu_launch_lanes.py's three widths give g.N = 129, 128 and 65 at its row counts, and tan_rg's threshold is still
+    128: two widths at and above it (one per lane type), one below. If the threshold moves, move LANES there (and this table) so
+    that an odd and an even width sit at or just above it and one even width below."""
+    import re
+    src = (CSRC / "hank_hip.hip").read_text()
+    m = re.search(r"static inline int tan_rg\(int NV, int forward, int ss = 0\) \{.*?\n\}", src, re.S)
+    assert m, "tan_rg has moved"
+    assert re.search(r"return \(want == 2 && N % 2 == 0\) \? 2 : 1;", src), "tan_lane_width no longer takes two directions per lane for an even N"
+    rule = re.search(r"return forward \? \(\(NV >= 32 \|\| ss\) \? 2 : 1\) : \(NV >= (\d+) \? 4 : 2\);", m.group(0))
+    assert rule and int(rule.group(1)) == TAN_RG_BACK_4, "tan_rg's rule has moved: move tests/test_gpu_launch_lanes.py's widths with it"
+    assert "tan_rg(w.g.N, 0)" in src and "tan_rg(w.gf.N, 1, w.gf.ss)" in src          # build_tanwork asks with g.N
+    for n_a in (37, 50, 40):
+        for N, (V, NV) in LAUNCH_LANES.items():
+            assert V == (2 if N % 2 == 0 else 1)
+            (gN, NC, lg, nbx, _), = ask([("t", n_a, N, V)])
+            assert gN == NV and NC == 64 and nbx == n_a, (n_a, N, gN, NC, nbx)      # one row per wave instruction
+    NVs = sorted(NV for _, NV in LAUNCH_LANES.values())
+    assert NVs[0] < TAN_RG_BACK_4 <= NVs[1] and NVs[0] >= 32                          # (the control keeps 2 forward row groups as well)
+    assert 37 % 4 != 0 and 37 % 2 != 0                                                # a ragged last block at 4 and at 2 row groups
+
+
 def test_fake_news_shapes_reach_what_they_name():
     """tests/test_gpu_fake_news_dense.py's shapes against fake_news()'s launch arithmetic restated in fake_news_refs.geometry, and
     that restatement against the source: if a tile, the K split or a block size moves, the GPU module cannot silently stop reaching

@@ -9,7 +9,8 @@ reference entry. The largest ENTRYWISE relative error per slab is printed and no
 The context is test_gpu_ss_diff._ctx's with T = P + 1: the polished (V, D) of ss_diff_cases.case as both boundaries, so that the
 record is stationary to rounding, and `primal` at the constant path. The shapes, and what each reaches in the eight kernels of
 csrc/hank_jacobian.h, are fake_news_refs.SHAPES; every case asserts its claims on fake_news_refs.geometry (tests/test_geom_host.py
-holds that arithmetic and the source together). P = 1 (T = 2) is not covered: nothing in the suite runs that horizon."""
+holds that arithmetic and the source together). P = 1 (T = 2), a single lag, is covered by tests/test_gpu_short_horizons.py
+(test_fake_news_matches_the_dense_reference), against the same reference at the same bound."""
 import numpy as np
 import pytest
 

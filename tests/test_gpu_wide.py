@@ -101,7 +101,8 @@ def test_default_schedule_sends_full_rounds_to_the_wide_sweeps(hank):
 
 def test_wide_sweeps_refuse_what_they_cannot_hold(hank):
     """a horizon whose per-period inputs do not fit LDS, or a productivity grid that is not instantiated: auto keeps the other
-    families, a forced `wide` fails at hank_create with the reason."""
+    families, a forced `wide` fails at hank_create with the reason. What the default schedule then runs at 129 and 256 directions —
+    the per-period launches with 4 backward row groups — is tests/test_gpu_launch_lanes.py's."""
     args = (np.linspace(0.0, 50.0, 40), np.linspace(0.5, 1.5, 6), np.full((6, 6), 1.0 / 6.0), 0.98, 2.0, 0.0, 12)
     hb = raw_block(hank, args, None)
     assert hb.info()["wide_supported"] == 0 and hb.info()["wide_mode"] == 0
