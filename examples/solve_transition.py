@@ -21,8 +21,8 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 
-def solve(n_a=500, n_e=4, T=300, shock=0.01, eps=1e-9, verbose=False, cold=False, inner="fixed_point", jacobian="toeplitz", step="full"):
-    """step="backtrack": Newton with the backtracking step rule (the trial steps of an iteration in ONE hank_primal_batch). cold=True: the steady state is solved here from the YAML guesses (value iteration and stationary distribution on
+def solve(n_a=500, n_e=4, T=300, shock=0.01, eps=1e-9, verbose=False, cold=False, inner="fixed_point", jacobian="toeplitz", step="full", with_model=False):
+    """with_model=True: -> (report, x, model, steady state) instead of (report, x). step="backtrack": Newton with the backtracking step rule (the trial steps of an iteration in ONE hank_primal_batch). cold=True: the steady state is solved here from the YAML guesses (value iteration and stationary distribution on
     the device where one is present) instead of coming from the test fixtures' cache."""
     import hank_amd as h
     import hank_amd.parallel  # noqa: F401  (pulls in torch before the clocks start)
@@ -47,11 +47,49 @@ def solve(n_a=500, n_e=4, T=300, shock=0.01, eps=1e-9, verbose=False, cold=False
     x = h.NewtonRaphsonHANK(x0, J, {"Z": Z}, m, ss, ss, ε=eps, verbose=verbose, inner=inner, step=step)
     t_newton = time.perf_counter() - t0
     lin = h.LinearizedFunction(x, {"Z": Z}, m, ss, ss)
-    return {"grid": f"{n_a}x{n_e}", "T": T, "shock": f"Z_t = 1 + {shock}*0.8^t", "steady_state_s": round(t_ss, 3),
+    out = {"grid": f"{n_a}x{n_e}", "T": T, "shock": f"Z_t = 1 + {shock}*0.8^t", "steady_state_s": round(t_ss, 3),
             "ss_jacobian_s": round(t_jac, 3), "newton_s": round(t_newton, 3), "preconditioner_setup_s": round(h.y_Iteration.setup_s, 3),
             "newton_iterations": h.NewtonRaphsonHANK.iterations, "jvps": h.y_Iteration.total_jvps, "residual_norm": float(np.linalg.norm(lin.Fx)),
             "wall_to_converged_path_s": round(t_jac + t_newton, 3), "steady_state": "cold start" if cold else "cached",
-            "inner": inner, "jacobian": jacobian, **({"step": step, "step_sizes": list(h.NewtonRaphsonHANK.step_sizes)} if step != "full" else {})}, x
+            "inner": inner, "jacobian": jacobian, **({"step": step, "step_sizes": list(h.NewtonRaphsonHANK.step_sizes)} if step != "full" else {})}
+    return (out, x, m, ss) if with_model else (out, x)
+
+
+def group_report(x, m, ss, Z, cuts):
+    """Who moves along the converged path x: the wealth groups cut at the steady-state CDF points `cuts` (0.5 0.9: the bottom half,
+    the next 40 %, the top decile; `hank_amd.groups.wealth_groups`, fixed by wealth level), each with its mass, savings and
+    consumption (hank_set_group_outputs / hank_get_group_outputs on a context of its own). Per group: the steady-state level, the
+    peak deviation along the path, and the largest gap between that nonlinear path and the linear response J_group · dx of the
+    household inputs' deviation (`SteadyStateJacobian.group_jacobian`: hank_fake_news_group)."""
+    from hank_amd.BackwardIteration import household_block, household_inputs
+    from hank_amd.groups import wealth_groups
+    from hank_amd.SteadyStateJacobian import group_jacobian
+    P = m.compspec.T - 1
+    edges = [0.0, *[float(c) for c in cuts], 1.0]
+    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
+    Wg = wealth_groups(ss.D, wd.grid.size, pd_.grid.size, edges)
+    K = Wg.shape[1]
+    hb = household_block(m).clone()
+    hb.set_boundary(ss.value, ss.D)
+    hb.set_group_outputs(np.concatenate([Wg, Wg, Wg], axis=1), np.repeat([hb.GROUP_MASS, hb.GROUP_POLICY, hb.GROUP_CONS], K))
+    x_ss = np.tile(np.array([ss.vars[k] for k in ("Y", "KS", "r", "w")]), P)
+    xhh_ss = np.asarray(household_inputs(x_ss, {"Z": np.ones(P)}, m)[0])
+    xhh = np.asarray(household_inputs(x, {"Z": Z}, m)[0])
+    hb.primal(xhh_ss)
+    Y_ss = hb.group_outputs()[0]
+    J = group_jacobian(hb)                                              # (3 K, P, n_hh, P)
+    hb.primal(xhh)
+    dY = hb.group_outputs()[0] - Y_ss                                   # (P, 3 K)
+    lin = np.einsum("ktis,is->tk", J, xhh - xhh_ss)
+    hb.close()
+
+    def one(k):
+        return {"steady_state": float(Y_ss[0, k]), "peak_deviation": float(dY[np.argmax(np.abs(dY[:, k])), k]),
+                "linear_peak_deviation": float(lin[np.argmax(np.abs(lin[:, k])), k]), "max_gap_to_linear": float(np.abs(dY[:, k] - lin[:, k]).max())}
+
+    return {"edges": edges, "groups": [{"cdf": [edges[g], edges[g + 1]], "mass": one(g), "savings": one(K + g), "consumption": one(2 * K + g)}
+                                       for g in range(K)],
+            "max_gap_to_linear": float(np.abs(dY - lin).max())}
 
 
 def scale_family(n_a=500, n_e=4, T=300, shock=0.01, scales=(0.5, 1.0, 2.0, -1.0), eps=1e-9, max_rounds=100):
@@ -311,6 +349,7 @@ if __name__ == "__main__":
     ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one hank_vjp against n_hh·P JVP columns")
     ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one hank_vjp_boundary, checked against two hank_jvp_boundary directions")
     ap.add_argument("--ss-curve", nargs=4, default=None, metavar=("VAR", "LO", "HI", "K"), help="the steady state's household side along a line in the free prices (VAR from LO to HI in K points, the others at the YAML's guesses) from ONE hank_ss_batch: the heterogeneous aggregates, the residual norm and the value steps per point")
+    ap.add_argument("--groups", nargs="+", type=float, default=None, metavar="CDF", help="after the converged path: the wealth groups cut at these steady-state CDF points (0.5 0.9: bottom half, next 40 %%, top decile) — each group's mass, savings and consumption deviation, and the largest gap between the nonlinear path and the linear response J_group · dx")
     ap.add_argument("--ss-gradient", action="store_true", help="with --permanent: the gradient of ½‖F(x)‖² with respect to the ending steady state's household prices through V_T (hank_vjp_het_boundary, then hank_ss_vjp), beside a central difference in one random direction")
     a = ap.parse_args()
     import os
@@ -334,7 +373,9 @@ if __name__ == "__main__":
     elif a.permanent is not None:
         out = solve_permanent(a.n_a, a.n_e, a.T, a.permanent, verbose=a.verbose)[0]
     else:
-        out, x = solve(a.n_a, a.n_e, a.T, a.shock, verbose=a.verbose, cold=a.cold, inner=a.inner, jacobian=a.jacobian, step=a.step)
+        out, x, m, ss = solve(a.n_a, a.n_e, a.T, a.shock, verbose=a.verbose, cold=a.cold, inner=a.inner, jacobian=a.jacobian, step=a.step, with_model=True)
+        if a.groups:
+            out["group_outputs"] = group_report(x, m, ss, 1.0 + a.shock * 0.8 ** np.arange(1, a.T), a.groups)
     out["n_gpus"] = world
     if rank == 0:
         print(json.dumps(out))

@@ -198,6 +198,35 @@ int hank_get_het_outputs_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh,
  * sweeps are the same for every count; a change of the count drops the primal memo of hank_primal_jvp (a host shim that
  * serves several callers on one context only ever raises it: BackwardIteration.py ensure_het_outputs).                     */
 int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het);
+
+/* ---- group outputs: who moves ----------------------------------------------------------------------
+ * ForwardIteration aggregates every heterogeneous variable with the same post-transition D_t (ForwardIteration.jl:303-307).
+ * A group output dots a WEIGHTED one with it: K groups (K <= HANK_GROUP_MAX), group k a weight vector W_k[G] indexed like D
+ * (pt = e n_a + ia, the column-major vec of the (n_a, n_e) matrix; any real values, fixed over time) and a base b_k:
+ *     Y^k_t  = sum W_k f D_t,   f = 1 (HANK_GROUP_MASS), a'_t (HANK_GROUP_POLICY), c_t = (1+r_t) a + w_t z_e + tr_t - a'_t (HANK_GROUP_CONS)
+ *     dY^k_t = sum W_k f dD_t + sigma_b sum W_k D_t da'_t + [CONS] (dr_t sum W_k D_t a + dw_t sum W_k D_t z_e + dtr_t sum W_k D_t)
+ * with sigma = 0, +1, -1. With W = 1, POLICY is output 0 of hank_get_het_outputs, CONS output 1, MASS is 1 with a zero tangent.
+ * The caller supplies data, not formulas: the bottom half of the wealth distribution, the borrowing limit, a productivity state. */
+enum {
+    HANK_GROUP_MASS = 0,
+    HANK_GROUP_POLICY = 1,
+    HANK_GROUP_CONS = 2
+};
+#define HANK_GROUP_MAX 32
+/* hank_set_group_outputs (ForwardIteration.jl:303-307): copies W (host, (G, K) column-major) and base[K] into buffers the context
+ * owns; K = 0 clears them. The record, the current tangent batch, the primal memo and the hank_set_het_outputs count stay
+ * untouched. K outside 0..HANK_GROUP_MAX, a base outside 0..2, or a null pointer with K > 0: HANK_ERR_BAD_ARG. A context made by
+ * hank_clone starts without groups. */
+int hank_set_group_outputs(hank_ctx *ctx, int32_t K, const double *W, const int32_t *base);
+/* hank_get_group_outputs (ForwardIteration.jl:303-307): the rules of hank_get_het_outputs. agg_out (P, K) column-major from the last
+ * primal; dagg_out (P, K, N) column-major from the current tangent batch of width N, whichever kernel family ran it, whose input
+ * dxhh (n_hh, P, N) is passed again. dagg_out NULL or N = 0: values only. HANK_ERR_NOT_READY before any groups are set, before a
+ * primal, when no batch of that width is current, and when the current batch carries boundary seeds (the recurrence after the
+ * sweeps assumes dD_0 = 0, as for Value and UCE). Every sum is taken in a fixed order: the same inputs give the same bits. The
+ * _dev form takes device pointers and is asynchronous on the context's stream; its direction-dependent buffers
+ * (P·G·N doubles and less) live in the context and grow to the widest request. */
+int hank_get_group_outputs(hank_ctx *ctx, const double *dxhh, int32_t N, double *agg_out, double *dagg_out);
+int hank_get_group_outputs_dev(hank_ctx *ctx, const double *d_dxhh, int32_t N, double *d_agg_out, double *d_dagg_out);
 int hank_get_grid_aggregates(hank_ctx *ctx, double *agg2_out, int32_t N, double *dagg2_out);
 int hank_get_grid_aggregates_dev(hank_ctx *ctx, double *d_agg2_out, int32_t N, double *d_dagg2_out);
 /* The distribution path D_1..D_P of the last hank_primal -> out[P*G] (ForwardIteration.jl:297-300). */
@@ -277,6 +306,15 @@ int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out);
  * Same precondition and HANK_ERR_NOT_READY cases as hank_fake_news; independent of hank_set_het_outputs, which it leaves
  * unchanged. */
 int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out);
+
+/* hank_fake_news_group: the same Toeplitz form for the K group outputs of hank_set_group_outputs (ForwardIteration.jl:303-307 dots
+ * every output with the same D_t, so the policy responses and the lottery impulses are shared once more):
+ *   E^k_0 = W_k f_ss,  F_out (P, P, n_hh, K): F[u, j, i, k] = E^k_u . iota_{j,i}
+ *   Dv_out (P, n_hh, K): Dv[j, i, k] = sigma_b sum W_k D_ss Y_{j,i} + [j == 0] d_{k,i}, d_{k,.} = sum W_k D_ss (a, z_e, 1) for
+ *          HANK_GROUP_CONS and 0 for the other bases
+ * The groups are served eight at a time, so the expectation vectors never take more than 8·P·G doubles. hank_fake_news's
+ * precondition and refusals; HANK_ERR_NOT_READY without groups. Each group's J follows from the same recursion. */
+int hank_fake_news_group(hank_ctx *ctx, double *F_out, double *Dv_out);
 
 /* ---- the transposed household block: xhh_bar = J(x)' agg_bar -------------------------------------
  * hank_vjp == the reverse rules of the same composition at the recorded primal: the pullback of ForwardIteration

@@ -41,6 +41,14 @@ def household_jacobian(F, Dv):
     return J
 
 
+def group_jacobian(block):
+    """d Y^k_t / d xhh_{i,s} at the steady state for the group outputs set on `block` (HouseholdBlock.set_group_outputs), which
+    holds the stationary primal: `block.fake_news_group()`'s F (P, P, n_hh, K) and Dv (P, n_hh, K) through the recursion of
+    `household_jacobian`, once per group. Returns J (K, P, n_hh, P): J[k, t, i, s]."""
+    F, Dv = block.fake_news_group()
+    return np.stack([household_jacobian(F[..., k], Dv[..., k]).transpose(1, 0, 2) for k in range(F.shape[3])])
+
+
 def direct_blocks(model: SequenceModel, ss):
     """d R_t / d xMat[:, t + o] at the steady state for every offset o in -max_lag..max_lead: the `blocks` of
     SteadyStateJacobian.jl:124-145, from ONE evaluation of the compiled equations on a (1 + max_lag + max_lead)-column

@@ -9,6 +9,7 @@
 #include "hank_jacobian.h"
 #include "hank_wide.h"
 #include "hank_hetx.h"
+#include "hank_groups.h"
 #include "hank_scen.h"
 #include "hank_ssbatch.h"
 #include "hank_adjoint.h"
@@ -189,6 +190,20 @@ struct CotBatch {
 // again: the NX > 0 Sweep A graphs hold the addresses.
 struct HxRecord { DevBuf<double> f, fc, S; bool valid = false; };
 
+// The caller's group outputs (hank_set_group_outputs; hank_groups.h): K weight vectors W (G, K) and their bases, owned by the context,
+// and their share of the record — the levels Y [P][K] and the CONS sums S [P][K][GRP_NS] (k_grp_record) — which belongs to the recorded
+// primal AND to this set of groups: ensure_grp_record builds it for the first reader, record_rewritten and a new set drop it. slab:
+// the direction-dependent buffers of hank_get_group_outputs, grown to the widest request.
+struct GroupSet {
+    int K = 0;
+    DevBuf<double> W, Y, S;
+    DevBuf<int> base;
+    unsigned long long codes = 0;      // the bases as k_grp_mix takes them (grp_codes)
+    bool valid = false;
+    DevBuf<char> slab;
+    size_t bytes = 0;
+};
+
 // hank_primal_batch's workspace (hank_scen.h): K scenario records carved alike from ONE slab (R0 is scenario
 // 0's, `stride` bytes to the next), the scenarios' inputs, partial sums, error words and outputs, and the two graphs of the last
 // (K, n_het) that ran. Grown to the widest K asked for (build_scenwork into a local, moved in when complete: a failed allocation
@@ -313,6 +328,7 @@ struct hank_ctx {
     bool adj_seg_valid = false;
     DevBuf<double> d_bnd_q;        // [2][P][n_e]: Pi^{t+1} z and Pi^{t+1} 1 (hank_jvp_boundary: ensure_bnd_q), the model's; allocated once (the graphs hold its address)
     HxRecord hx;                   // the extra outputs' share of the record (ensure_hx_record), valid for the recorded primal or not
+    GroupSet grp;                  // the group outputs and their share of the record (ensure_grp_record)
     ScenWork scen;                 // hank_primal_batch's workspace
     int scen_pending = 0;          // scenarios of a hank_primal_batch_dev whose verdict hank_check has not taken yet
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
@@ -361,7 +377,7 @@ static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
 // lot_written: so were lo, lw, ig and start (every lottery but k_xdual_front's) — seg and lwg are made from them, so neither is valid without
 static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written, bool lot_written = true) {
     ctx->primal_done = true; ctx->seg_valid = seg_written && lot_written; ctx->lwg_valid = lwg_written && lot_written; ctx->lot_valid = lot_written;
-    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->hx.valid = false;
+    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->hx.valid = false; ctx->grp.valid = false;
     batch_none(ctx);
     cot_none(ctx);
 }
@@ -2260,12 +2276,15 @@ static int stationary_record(hank_ctx *ctx, const char *name) {
 // F (P, P, n_hh[, n_het]) and Dv (P, n_hh[, n_het]), column-major. Requires hank_primal at the constant steady-state path
 // with the steady state as both boundaries (what getSteadyStateJacobian builds, SteadyStateJacobian.jl:53-57).
 // n_het == 0: hank_fake_news (the policy variable's aggregate: E_0 = pol_ss, Dv weights D_ss); n_het >= 1: hank_fake_news_het
-// (outputs 0 .. n_het-1 of hank_get_het_outputs; output 0 is the same arithmetic as n_het == 0, bit for bit).
-static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
-    const char *name = n_het ? "hank_fake_news_het" : "hank_fake_news";
+// (outputs 0 .. n_het-1 of hank_get_het_outputs; output 0 is the same arithmetic as n_het == 0, bit for bit); groups: hank_fake_news_group
+// (the context's K group outputs: the same policy responses and impulses, the outputs served GRP_FN_CHUNK at a time so the expectation
+// workspace never holds more — steps 3 and 4 run once per chunk, once in all for the other two entries).
+static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, double *Dv_out) {
+    const char *name = groups ? "hank_fake_news_group" : n_het ? "hank_fake_news_het" : "hank_fake_news";
     { const int nrc = stationary_record(ctx, name); if (nrc) return nrc; }
     const Consts &c = ctx->c;
-    const int P = c.P, G = c.G, N = c.n_hh, NP = P * N, S = 16, nh = n_het ? n_het : 1;
+    const int P = c.P, G = c.G, N = c.n_hh, NP = P * N, S = 16, nout = groups ? ctx->grp.K : n_het ? n_het : 1;
+    const int cap = groups ? std::min(nout, GRP_FN_CHUNK) : nout;      // outputs per pass
     hipStream_t s = ctx->stream;
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
@@ -2276,7 +2295,7 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
     TanWork &w = *wp;
     rc = ensure_tan_graphs(ctx, w, false, 0);
     if (rc) return rc;
-    rc = ensure_fn(ctx, nh);
+    rc = ensure_fn(ctx, cap);
     if (rc) return rc;
     HIPC(ctx, join_side(ctx));      // D_1 and the {w, ig D} records come from the primal's forward sweep
     hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
@@ -2285,43 +2304,52 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
     // 2. the lottery impulse of every lag and input at once
     hipLaunchKernelGGL(k_fn_transpose, dim3((unsigned)((G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256), 0, s, w.dpol, P, G, N, ctx->fn.dpT);
     hipLaunchKernelGGL(k_fn_impulse, dim3((unsigned)c.n_a, (unsigned)((NP + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.dpT, NP, ctx->fn.iota);
-    // 3. the expectation vectors E^o_u = (T')^u f_o,ss of every output (rows o*P + u of E) and the direct term's weights
     const size_t PG = (size_t)P * G;
-    const double *Wd = ctx->R.Dseq + G;
-    if (n_het) {
-        hipLaunchKernelGGL(k_fn_het_record, dim3((unsigned)nh), dim3(256), 0, s, c, ctx->R, ctx->d_xhh, PG, ctx->fn.E, ctx->fn.W, ctx->fn.dsum);
-        for (int u = 0; u + 1 < P; u++)
-            hipLaunchKernelGGL(k_fn_expect_het, dim3((unsigned)((G + 255) / 256), (unsigned)nh), dim3(256), 0, s, c, ctx->R, ctx->fn.E, PG, u);
-        Wd = ctx->fn.W;
-    } else {
-        HIPC(ctx, hipMemcpyAsync(ctx->fn.E, ctx->R.pol, sizeof(double) * G, hipMemcpyDeviceToDevice, s));
-        for (int u = 0; u + 1 < P; u++)
-            hipLaunchKernelGGL(k_fn_expect, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.E + (size_t)u * G, ctx->fn.E + (size_t)(u + 1) * G);
+    std::vector<double> hF((size_t)cap * P * NP), hD((size_t)cap * NP), hd((size_t)cap * N, 0.0);
+    for (int o0 = 0; o0 < nout; o0 += cap) {
+        const int nh = std::min(cap, nout - o0);
+        const int kchunk = ((G + S - 1) / S + 15) / 16 * 16, MP = nh * P;
+        // 3. the expectation vectors E^o_u = (T')^u f_o,ss of every output (rows o*P + u of E) and the direct term's weights
+        const double *Wd = ctx->R.Dseq + G;
+        if (groups || n_het) {
+            if (groups)
+                hipLaunchKernelGGL(k_grp_fn_record, dim3((unsigned)nh), dim3(256), 0, s, c, ctx->R, ctx->d_xhh, o0, ctx->grp.W, ctx->grp.base, PG, ctx->fn.E, ctx->fn.W, ctx->fn.dsum);
+            else
+                hipLaunchKernelGGL(k_fn_het_record, dim3((unsigned)nh), dim3(256), 0, s, c, ctx->R, ctx->d_xhh, PG, ctx->fn.E, ctx->fn.W, ctx->fn.dsum);
+            for (int u = 0; u + 1 < P; u++)
+                hipLaunchKernelGGL(k_fn_expect_het, dim3((unsigned)((G + 255) / 256), (unsigned)nh), dim3(256), 0, s, c, ctx->R, ctx->fn.E, PG, u);
+            Wd = ctx->fn.W;
+        } else {
+            HIPC(ctx, hipMemcpyAsync(ctx->fn.E, ctx->R.pol, sizeof(double) * G, hipMemcpyDeviceToDevice, s));
+            for (int u = 0; u + 1 < P; u++)
+                hipLaunchKernelGGL(k_fn_expect, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.E + (size_t)u * G, ctx->fn.E + (size_t)(u + 1) * G);
+        }
+        // 4. F = E iota, Dv = W dpT (the K split depends on G only: every output's elements are summed in the same order)
+        hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), (unsigned)((MP + 63) / 64), (unsigned)S), dim3(256), 0, s, ctx->fn.E, ctx->fn.iota, ctx->fn.Cp, MP, NP, G, kchunk);
+        hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)(((size_t)MP * NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, MP * NP, S, ctx->fn.F);
+        hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), (unsigned)((nh + 63) / 64), (unsigned)S), dim3(256), 0, s, Wd, ctx->fn.dpT, ctx->fn.Cp, nh, NP, G, kchunk);
+        hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)((nh * NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, nh * NP, S, ctx->fn.Dv);
+        HIPC(ctx, hipGetLastError());
+        HIPC(ctx, hipMemcpyAsync(hF.data(), ctx->fn.F, sizeof(double) * MP * NP, hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipMemcpyAsync(hD.data(), ctx->fn.Dv, sizeof(double) * nh * NP, hipMemcpyDeviceToHost, s));
+        if (groups || n_het) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * nh * N, hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipStreamSynchronize(s));
+        if (o0 == 0) {
+            rc = device_verdict(ctx, THE_RECORD);
+            if (rc) return rc;
+        }
+        // column n' = t*N + k of the device arrays is lag j = P-1-t of input k; the same-period effect d_{o,k} lands at lag 0
+        // (output 0 of the het outputs has none; a group's is zero unless its base is consumption)
+        for (int o = 0; o < nh; o++)
+            for (int k = 0; k < N; k++)
+                for (int t = 0; t < P; t++) {
+                    const int j = P - 1 - t;
+                    const size_t kc = (size_t)k + (size_t)N * o, ko = (size_t)k + (size_t)N * (o0 + o);
+                    const double dv = hD[(size_t)o * NP + (size_t)t * N + k];
+                    Dv_out[j + (size_t)P * ko] = ((groups || o > 0) && j == 0) ? dv + hd[kc] : dv;
+                    for (int u = 0; u < P; u++) F_out[u + (size_t)P * (j + (size_t)P * ko)] = hF[((size_t)o * P + u) * NP + (size_t)t * N + k];
+                }
     }
-    // 4. F = E iota, Dv = W dpT (the K split depends on G only: every output's elements are summed in the same order)
-    const int kchunk = ((G + S - 1) / S + 15) / 16 * 16, MP = nh * P;
-    hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), (unsigned)((MP + 63) / 64), (unsigned)S), dim3(256), 0, s, ctx->fn.E, ctx->fn.iota, ctx->fn.Cp, MP, NP, G, kchunk);
-    hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)(((size_t)MP * NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, MP * NP, S, ctx->fn.F);
-    hipLaunchKernelGGL(k_fn_gemm, dim3((unsigned)((NP + 63) / 64), (unsigned)((nh + 63) / 64), (unsigned)S), dim3(256), 0, s, Wd, ctx->fn.dpT, ctx->fn.Cp, nh, NP, G, kchunk);
-    hipLaunchKernelGGL(k_fn_reduce, dim3((unsigned)((nh * NP + 255) / 256)), dim3(256), 0, s, ctx->fn.Cp, nh * NP, S, ctx->fn.Dv);
-    HIPC(ctx, hipGetLastError());
-    std::vector<double> hF((size_t)MP * NP), hD((size_t)nh * NP), hd((size_t)nh * N, 0.0);
-    HIPC(ctx, hipMemcpyAsync(hF.data(), ctx->fn.F, sizeof(double) * hF.size(), hipMemcpyDeviceToHost, s));
-    HIPC(ctx, hipMemcpyAsync(hD.data(), ctx->fn.Dv, sizeof(double) * hD.size(), hipMemcpyDeviceToHost, s));
-    if (n_het) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, s));
-    HIPC(ctx, hipStreamSynchronize(s));
-    rc = device_verdict(ctx, THE_RECORD);
-    if (rc) return rc;
-    // column n' = t*N + k of the device arrays is lag j = P-1-t of input k; the same-period effect d_{o,k} lands at lag 0
-    for (int o = 0; o < nh; o++)
-        for (int k = 0; k < N; k++)
-            for (int t = 0; t < P; t++) {
-                const int j = P - 1 - t;
-                const size_t ko = (size_t)k + (size_t)N * o;
-                const double dv = hD[(size_t)o * NP + (size_t)t * N + k];
-                Dv_out[j + (size_t)P * ko] = (o > 0 && j == 0) ? dv + hd[ko] : dv;
-                for (int u = 0; u < P; u++) F_out[u + (size_t)P * (j + (size_t)P * ko)] = hF[((size_t)o * P + u) * NP + (size_t)t * N + k];
-            }
     ctx->errmsg[0] = 0;
     return HANK_OK;
 }
@@ -2329,7 +2357,7 @@ static int fake_news(hank_ctx *ctx, int n_het, double *F_out, double *Dv_out) {
 int hank_fake_news(hank_ctx *ctx, double *F_out, double *Dv_out) {
     ENTER(ctx);
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
-    return fake_news(ctx, 0, F_out, Dv_out);
+    return fake_news(ctx, 0, false, F_out, Dv_out);
 }
 
 // every heterogeneous output at once (hank_jacobian.h): F (P, P, n_hh, n_het), Dv (P, n_hh, n_het). Independent of the
@@ -2338,7 +2366,7 @@ int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_o
     ENTER(ctx);
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     const int rc = het_count_ok(ctx, "hank_fake_news_het", n_het, false);
-    return rc ? rc : fake_news(ctx, n_het, F_out, Dv_out);
+    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out);
 }
 
 #ifdef HANK_XSTAMP
@@ -2945,6 +2973,162 @@ int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het) {
     if (n_het != ctx->n_het) ctx->memo_valid = false;      // the next hank_primal_jvp records its primal afresh
     ctx->n_het = n_het;
     return HANK_OK;
+}
+}
+
+// ---- group outputs (hank_groups.h) ---------------------------------------------------------------------------
+// the groups' share of the record: built before the first reader at a record and a set of groups (group_outputs), after join_side
+// (the sums read D_t). It reads the policies and D_t alone, so a call for the levels needs no lottery record. The only launch of
+// k_grp_record.
+static int ensure_grp_record(hank_ctx *ctx) {
+    const Consts &c = ctx->c;
+    GroupSet &g = ctx->grp;
+    if (g.valid) return HANK_OK;
+    hipLaunchKernelGGL(k_grp_record, dim3((unsigned)c.P, (unsigned)g.K), dim3(256), 0, ctx->stream, c, ctx->R, ctx->d_xhh, g.K, g.W.get(), g.base.get(), g.Y.get(), g.S.get());
+    HIPC(ctx, hipGetLastError());
+    g.valid = true;
+    return HANK_OK;
+}
+
+static_assert(GRP_MAX == HANK_GROUP_MAX, "hank_groups.h and hank_hip.h disagree on the largest K");
+template <int KC>
+static void launch_grp_mix(hank_ctx *ctx, dim3 grid, int t, int N, const double *dpc, const double *mid, double *dD, double *parts) {
+    const GroupSet &g = ctx->grp;
+    hipLaunchKernelGGL(k_grp_mix<KC>, grid, dim3(GRP_ROWS * GRP_LANES), 0, ctx->stream, ctx->c, ctx->R, t, N, g.K, ctx->d_xhh, g.W.get(), g.codes, dpc, mid, dD, parts);
+}
+
+// the in-period sums T [n][t][k] of every direction of batch b: hx_outputs' recurrence (k_hx_mid as it is) with k_grp_mix's K
+// reductions, in the groups' own slab (grown when a wider batch asks, reused in stream order: the _dev form stays asynchronous)
+static int grp_tangent_sums(hank_ctx *ctx, const TanBatch &b, double **T_out) {
+    const Consts &c = ctx->c;
+    GroupSet &g = ctx->grp;
+    const int N = b.N, K = g.K;
+    const size_t P = c.P, G = c.G;
+    const int nbr = (c.n_a + GRP_ROWS - 1) / GRP_ROWS;
+    const size_t sz[5] = {P * G * N, G * N, G * N, (size_t)N * P * nbr * K, (size_t)N * P * K};
+    size_t need = 0, off = 0;
+    for (size_t k : sz) carve(need, sizeof(double) * k);
+    if (need > g.bytes) {
+        if (g.slab) HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (the old slab is released by alloc)
+        g.bytes = 0;
+        HIPC(ctx, g.slab.alloc(need));
+        g.bytes = need;
+    }
+    double *buf[5];      // views
+    for (int k = 0; k < 5; k++) buf[k] = reinterpret_cast<double *>(g.slab + carve(off, sizeof(double) * sz[k]));
+    double *dpc = buf[0], *mid = buf[1], *dD = buf[2], *parts = buf[3], *T = buf[4];
+    int rc = ensure_lottery(ctx);      // (k_hx_mid reads lw, ig and start)
+    if (rc) return rc;
+    rc = export_dpol_dev(ctx, b, dpc);
+    if (rc) return rc;
+    const dim3 gmid((unsigned)((G + HX_ROWS - 1) / HX_ROWS), (unsigned)N), gmix((unsigned)nbr, (unsigned)((N + GRP_LANES - 1) / GRP_LANES));
+    for (size_t t = 0; t < P; t++) {
+        hipLaunchKernelGGL(k_hx_mid, gmid, dim3(HX_ROWS), 0, ctx->stream, c, ctx->R, (int)t, dpc, dD, mid);
+        if (K <= 4) launch_grp_mix<4>(ctx, gmix, (int)t, N, dpc, mid, dD, parts);
+        else if (K <= 8) launch_grp_mix<8>(ctx, gmix, (int)t, N, dpc, mid, dD, parts);
+        else if (K <= 16) launch_grp_mix<16>(ctx, gmix, (int)t, N, dpc, mid, dD, parts);
+        else launch_grp_mix<GRP_MAX>(ctx, gmix, (int)t, N, dpc, mid, dD, parts);
+    }
+    const size_t cnt = (size_t)N * P * K;
+    hipLaunchKernelGGL(k_hx_reduce, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, parts, nbr, K, cnt, T);
+    HIPC(ctx, hipGetLastError());
+    *T_out = T;
+    return HANK_OK;
+}
+
+// hank_get_group_outputs[_dev]: hank_get_het_outputs' rules, for the context's groups
+static int group_outputs(hank_ctx *ctx, const double *dxhh, int32_t N, double *agg_out, double *dagg_out, bool dev) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    if (N < 0 || !(agg_out || dagg_out)) return fail(ctx, HANK_ERR_BAD_ARG, "hank_get_group_outputs: bad argument: N must be >= 0 and an output array given");
+    const int K = ctx->grp.K;
+    if (K == 0) return fail(ctx, HANK_ERR_NOT_READY, "hank_get_group_outputs: no groups are set: call hank_set_group_outputs first");
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
+    const size_t P = ctx->c.P, nh = ctx->c.n_hh;
+    const bool tan = dagg_out && N > 0;
+    if (tan && !dxhh) return fail(ctx, HANK_ERR_BAD_ARG, "the tangent outputs need the dxhh of the last tangent sweep");
+    const TanBatch *b = nullptr;
+    if (tan) {
+        int rc = batch_current(ctx, N, &b);
+        if (rc) return rc;
+        if (b->boundary)
+            return fail(ctx, HANK_ERR_NOT_READY, "hank_get_group_outputs: the current tangent batch carries boundary seeds (hank_jvp_boundary); the group tangents "
+                        "assume dD_0 = 0 and are served again after hank_jvp");
+    }
+    HIPC(ctx, join_side(ctx));
+    Scratch sc;
+    const double *d_dx = dxhh;
+    double *d_a = agg_out, *d_da = dagg_out;
+    if (!dev) {
+        double *tmp = nullptr;
+        if (tan) {
+            HIPC(ctx, sc.alloc(&tmp, nh * P * N));
+            HIPC(ctx, hipMemcpyAsync(tmp, dxhh, sizeof(double) * nh * P * N, hipMemcpyHostToDevice, ctx->stream));
+            d_dx = tmp;
+            HIPC(ctx, sc.alloc(&d_da, P * K * N));
+        }
+        if (agg_out) HIPC(ctx, sc.alloc(&d_a, P * K));
+    }
+    int rc = ensure_grp_record(ctx);
+    if (rc) return rc;
+    const int Nk = tan ? N : 0;
+    double *T = nullptr;
+    if (tan) {
+        rc = grp_tangent_sums(ctx, *b, &T);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_grp_outputs, dim3((unsigned)((P * K * ((size_t)Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, (int)nh, K, Nk, d_dx,
+                       ctx->grp.Y.get(), ctx->grp.S.get(), T, d_a, tan ? d_da : nullptr);
+    HIPC(ctx, hipGetLastError());
+    if (!dev) {
+        if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, d_a, sizeof(double) * P * K, hipMemcpyDeviceToHost, ctx->stream));
+        if (tan) HIPC(ctx, hipMemcpyAsync(dagg_out, d_da, sizeof(double) * P * K * N, hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return HANK_OK;
+}
+extern "C" {
+int hank_get_group_outputs(hank_ctx *ctx, const double *dxhh, int32_t N, double *agg_out, double *dagg_out) {
+    return group_outputs(ctx, dxhh, N, agg_out, dagg_out, false);
+}
+int hank_get_group_outputs_dev(hank_ctx *ctx, const double *d_dxhh, int32_t N, double *d_agg_out, double *d_dagg_out) {
+    return group_outputs(ctx, d_dxhh, N, d_agg_out, d_dagg_out, true);
+}
+// The context's copies of W (G, K) and base[K]; K = 0 clears them. The record, the current tangent batch, the primal memo and the
+// hank_set_het_outputs count stay as they are: only the groups' own share of the record (ensure_grp_record) is dropped.
+int hank_set_group_outputs(hank_ctx *ctx, int32_t K, const double *W, const int32_t *base) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    ENTER(ctx);
+    if (K < 0 || K > HANK_GROUP_MAX) return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_group_outputs: bad argument: K must be 0..%d, got %d", HANK_GROUP_MAX, K);
+    if (K > 0 && (!W || !base)) return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_group_outputs: null pointer");
+    for (int k = 0; k < K; k++)
+        if (base[k] < HANK_GROUP_MASS || base[k] > HANK_GROUP_CONS)
+            return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_group_outputs: bad argument: base[%d] = %d is none of HANK_GROUP_MASS, _POLICY, _CONS", k, base[k]);
+    GroupSet &g = ctx->grp;
+    const size_t P = ctx->c.P, G = ctx->c.G;
+    if (g.K > 0) HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (a reader of the old set may still be enqueued)
+    g.valid = false;
+    const int K_old = g.K;
+    g.K = 0;      // (until the new set is complete: a failed allocation or copy leaves no groups set)
+    if (K != K_old) {
+        g.W.reset(); g.base.reset(); g.Y.reset(); g.S.reset();
+        if (K == 0) return HANK_OK;
+        HIPC(ctx, g.W.alloc(G * K)); HIPC(ctx, g.base.alloc(K));
+        HIPC(ctx, g.Y.alloc(P * K)); HIPC(ctx, g.S.alloc(P * K * GRP_NS));
+    }
+    if (K == 0) return HANK_OK;
+    HIPC(ctx, hipMemcpy(g.W.get(), W, sizeof(double) * G * K, hipMemcpyHostToDevice));
+    HIPC(ctx, hipMemcpy(g.base.get(), base, sizeof(int32_t) * K, hipMemcpyHostToDevice));
+    g.codes = grp_codes(base, K);
+    g.K = K;
+    return HANK_OK;
+}
+// hank_fake_news_group: hank_fake_news's precondition and refusals, for the context's groups: F (P, P, n_hh, K), Dv (P, n_hh, K)
+int hank_fake_news_group(hank_ctx *ctx, double *F_out, double *Dv_out) {
+    ENTER(ctx);
+    if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
+    if (ctx->grp.K == 0) return fail(ctx, HANK_ERR_NOT_READY, "hank_fake_news_group: no groups are set: call hank_set_group_outputs first");
+    return fake_news(ctx, 0, true, F_out, Dv_out);
 }
 }
 

@@ -20,6 +20,8 @@ HANK_OK = 0
 HANK_ERR_NO_DEVICE, HANK_ERR_BAD_ARG, HANK_ERR_KNOTS, HANK_ERR_DOMAIN = 1, 2, 3, 4
 HANK_ERR_NOT_READY, HANK_ERR_NONMONOTONE, HANK_ERR_NOMEM, HANK_ERR_SWEEP, HANK_ERR_LAUNCH = 5, 6, 7, 8, 9
 HANK_VF_KRUSELL_SMITH = 0
+HANK_GROUP_MASS, HANK_GROUP_POLICY, HANK_GROUP_CONS = 0, 1, 2      # the base of a group output (hank_set_group_outputs)
+HANK_GROUP_MAX = 32
 
 # the symbols include/hank_hip.h declares (tests check that every one is exported)
 ABI_SYMBOLS = (
@@ -36,6 +38,7 @@ ABI_SYMBOLS = (
     "hank_primal_batch", "hank_primal_batch_dev", "hank_last_batch_timings",
     "hank_ss_batch", "hank_last_ss_batch_timings",
     "hank_get_lottery_record", "hank_get_forward_units",
+    "hank_set_group_outputs", "hank_get_group_outputs", "hank_get_group_outputs_dev", "hank_fake_news_group",
 )
 
 
@@ -155,6 +158,10 @@ def load_library() -> C.CDLL:
     lib.hank_last_batch_timings.argtypes = [vp, dp]
     lib.hank_ss_batch.argtypes = [vp, i32, dp, i32, C.c_double, i32, C.c_double, i32, i32, dp, dp, dp, dp, C.POINTER(i32), dp, C.POINTER(i32)]
     lib.hank_last_ss_batch_timings.argtypes = [vp, dp]
+    lib.hank_set_group_outputs.argtypes = [vp, i32, dp, C.POINTER(i32)]
+    lib.hank_get_group_outputs.argtypes = [vp, dp, i32, dp, dp]
+    lib.hank_get_group_outputs_dev.argtypes = [vp, vp, i32, vp, vp]
+    lib.hank_fake_news_group.argtypes = [vp, dp, dp]
     for name in ABI_SYMBOLS:
         if name in ("hank_get_lottery_record", "hank_get_forward_units") and not hasattr(lib, name):
             continue
@@ -210,6 +217,7 @@ class HouseholdBlock:
     borrow_cons, T; GeneralStructures.jl:216-226) and from `ss_end` / `ss_initial`.
     All matrices are (n_a, n_e); numpy arrays of that shape are accepted in any memory order.
     """
+    GROUP_MASS, GROUP_POLICY, GROUP_CONS = HANK_GROUP_MASS, HANK_GROUP_POLICY, HANK_GROUP_CONS
 
     def __init__(self, a_grid, z_grid, Pi, beta, gamma, borrow_cons, T, value_fn_id=HANK_VF_KRUSELL_SMITH, device=None):
         """device: HIP device ordinal of the context (hank_create_on); None = the calling thread's current device."""
@@ -240,6 +248,7 @@ class HouseholdBlock:
         self.n_hh = self._lib.hank_n_hh(self._ctx)
         # sweeps issued through this context, by entry point (tests assert "ONE sweep per fullFunction")
         self.calls = {"primal": 0, "jvp": 0, "primal_jvp": 0}
+        self.n_groups = 0      # group outputs set on this context (set_group_outputs)
 
     # -- plumbing ---------------------------------------------------------------------------
     def _chk(self, rc: int):
@@ -249,7 +258,8 @@ class HouseholdBlock:
     def clone(self, device=None) -> "HouseholdBlock":
         """A second, independent context of the same model and boundary (its own device memory, graphs and
         stream): independent tangent batches — Jacobian column chunks — can be in flight on both. `device`: put the
-        clone on another GPU of the node (default: this context's)."""
+        clone on another GPU of the node (default: this context's). The clone carries no group outputs: call
+        `set_group_outputs` on it."""
         beta, gamma, bc, vf = self._params
         other = HouseholdBlock(self.a_grid, self.z_grid, self.Pi, beta, gamma, bc, self.T, vf, device=self.device if device is None else device)
         if self._boundary is not None:
@@ -755,6 +765,59 @@ class HouseholdBlock:
         F = np.empty((self.P, self.P, self.n_hh, nb), order="F")
         Dv = np.empty((self.P, self.n_hh, nb), order="F")
         self._chk(self._lib.hank_fake_news_het(self._ctx, int(n_het), _p(F), _p(Dv)))
+        return F, Dv
+
+    # -- group outputs: aggregates by household group -------------------------------------------
+    def set_group_outputs(self, W, base):
+        """the groups `group_outputs` and `fake_news_group` serve (hank_set_group_outputs): W (G, K) — or (n_a, n_e, K) — holds
+        one weight vector per group, indexed like D (pt = e n_a + ia), any real values; base[k] is GROUP_MASS, GROUP_POLICY or
+        GROUP_CONS (one value serves every group). K = 0 (W=None) clears them. The record, the current tangent batch, the primal memo
+        and the `set_het_outputs` count stay as they are. `clone()` does not carry the groups."""
+        if W is None:
+            self._chk(self._lib.hank_set_group_outputs(self._ctx, 0, None, None))
+            self.n_groups = 0
+            return
+        W = np.asarray(W, dtype=np.float64)
+        if W.ndim == 3 and W.shape[:2] == (self.n_a, self.n_e):
+            W = W.reshape(self.G, W.shape[2], order="F")
+        if W.ndim == 1:
+            W = W[:, None]
+        if W.ndim != 2 or W.shape[0] != self.G:
+            raise ValueError(f"W must be ({self.G}, K) or ({self.n_a}, {self.n_e}, K), got {W.shape}")
+        W = np.asfortranarray(W)
+        K = W.shape[1]
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(base, dtype=np.int32), (K,)))
+        self._chk(self._lib.hank_set_group_outputs(self._ctx, K, _p(W), b.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.n_groups = K
+
+    def group_outputs(self, dxhh=None):
+        """the group outputs of the last sweeps (hank_get_group_outputs; ForwardIteration.jl:303-307): Y^k_t = sum W_k f D_t.
+        -> agg (P, K), and dagg (P, K, N) when `dxhh` (n_hh, P, N) — the input of the last tangent sweep — is given (else
+        None). The rules of `het_outputs`; a batch with boundary seeds is refused."""
+        K = max(self.n_groups, 1)      # (the library refuses a call without groups)
+        agg = np.empty((self.P, K), order="F")
+        if dxhh is None:
+            self._chk(self._lib.hank_get_group_outputs(self._ctx, None, 0, _p(agg), None))
+            return agg, None
+        dxhh = np.asfortranarray(dxhh, dtype=np.float64)
+        if dxhh.ndim != 3 or dxhh.shape[:2] != (self.n_hh, self.P):
+            raise ValueError(f"dxhh must be ({self.n_hh}, {self.P}, N), got {dxhh.shape}")
+        N = dxhh.shape[2]
+        dagg = np.empty((self.P, K, N), order="F")
+        self._chk(self._lib.hank_get_group_outputs(self._ctx, _p(dxhh), N, _p(agg), _p(dagg)))
+        return agg, dagg
+
+    def group_outputs_dev(self, d_dxhh: int, N: int, d_agg: int, d_dagg: int):
+        """device-pointer form (asynchronous on the context's stream)."""
+        self._chk(self._lib.hank_get_group_outputs_dev(self._ctx, d_dxhh or None, int(N), d_agg or None, d_dagg or None))
+
+    def fake_news_group(self):
+        """the Toeplitz form of `fake_news_het` for the group outputs (hank_fake_news_group): -> F (P, P, n_hh, K),
+        Dv (P, n_hh, K); `household_jacobian(F[..., k], Dv[..., k])` is d Y^k_t / d xhh_{i,s}."""
+        K = max(self.n_groups, 1)
+        F = np.empty((self.P, self.P, self.n_hh, K), order="F")
+        Dv = np.empty((self.P, self.n_hh, K), order="F")
+        self._chk(self._lib.hank_fake_news_group(self._ctx, _p(F), _p(Dv)))
         return F, Dv
 
     def vfi(self, value0, xhh_t, tol: float, max_iter: int = 10_000):

@@ -29,6 +29,7 @@ mutable struct HankCtx
     P::Int; G::Int; n_a::Int; n_e::Int
     hh_rows::Tuple        # names of the xVals rows the native family reads, in the order the library expects
     outputs::Tuple        # the heterogeneous variables the family returns, in the order of hank_get_het_outputs
+    n_groups::Int         # group outputs the context holds (hank_set_group_outputs): the readers size their arrays by it
 end
 
 # native kernel families by value-function name: id (include/hank_hip.h), the household inputs it reads, and the heterogeneous
@@ -74,7 +75,7 @@ function hank_context(model::SequenceModel; device::Union{Nothing,Integer} = not
                 ccall((:hank_create_on, LIBHANK), Cint, (Ref{HankModelC}, Int32, Ref{Ptr{Cvoid}}), m, Int32(device), ref)
         end
         _check(ref[], rc)
-        ctx = HankCtx(ref[], model.compspec.T - 1, w.n * p.n, w.n, p.n, rows, outs)
+        ctx = HankCtx(ref[], model.compspec.T - 1, w.n * p.n, w.n, p.n, rows, outs, 0)
         @assert ccall((:hank_n_hh, LIBHANK), Cint, (Ptr{Cvoid},), ref[]) == length(rows)
         finalizer(c -> ccall((:hank_destroy, LIBHANK), Cint, (Ptr{Cvoid},), c.ptr), ctx)
         ctx
@@ -286,6 +287,41 @@ function _toeplitz_recursion(F::Array{Float64,3}, Dv::Matrix{Float64})
         end
     end
     return J
+end
+
+# ---- group outputs: aggregates by household group (hank_set_group_outputs, hank_get_group_outputs, hank_fake_news_group) -------
+# W (G, K): one weight vector per group over the grid, indexed like D (vec of the (n_a, n_e) matrix), fixed over time; base[k] the
+# policy it weighs: 0 mass (f = 1), 1 the policy variable a', 2 consumption. Y^k_t = sum W_k f D_t, dotted with the same D_t as
+# every heterogeneous variable (ForwardIteration.jl:303-307). K = 0 (an empty W) clears the groups.
+const HANK_GROUP_MASS, HANK_GROUP_POLICY, HANK_GROUP_CONS = Int32(0), Int32(1), Int32(2)
+function hank_set_group_outputs(ctx::HankCtx, W::AbstractMatrix, base::AbstractVector{<:Integer})
+    size(W, 2) == length(base) && (isempty(base) || size(W, 1) == ctx.G) || error("W must be (G, K) = ($(ctx.G), $(length(base)))")
+    Wd = Matrix{Float64}(W); b = Vector{Int32}(base)
+    _check(ctx.ptr, ccall((:hank_set_group_outputs, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}),
+                          ctx.ptr, Int32(length(b)), isempty(b) ? C_NULL : Wd, isempty(b) ? C_NULL : b))
+    ctx.n_groups = length(b)      # (after the check: a refused call leaves the library's set, and this count, as they were)
+    return ctx
+end
+
+# agg (P, K) of the last primal, and with the dxhh (n_hh, P, N) of the last tangent sweep also dagg (P, K, N); the rules of
+# hank_get_het_outputs (a batch with boundary seeds is refused)
+function hank_get_group_outputs(ctx::HankCtx, dxhh::Union{Nothing,Array{Float64,3}} = nothing)
+    K = max(ctx.n_groups, 1)      # (the library refuses a call without groups; the arrays are sized by the count it holds)
+    agg = Matrix{Float64}(undef, ctx.P, K)
+    N = dxhh === nothing ? 0 : size(dxhh, 3)
+    dagg = dxhh === nothing ? nothing : Array{Float64}(undef, ctx.P, K, N)
+    _check(ctx.ptr, ccall((:hank_get_group_outputs, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                          ctx.ptr, dxhh === nothing ? C_NULL : dxhh, Int32(N), agg, dagg === nothing ? C_NULL : dagg))
+    return agg, dagg
+end
+
+# J[t, s, i] = d Y^k_t / d xhh_{i,s} per group k at the stationary primal the context holds (household_jacobian_toeplitz's
+# precondition: hank_primal at the constant steady-state path), from the same recursion
+function group_jacobian_toeplitz(ctx::HankCtx)
+    P = ctx.P; n_hh = length(ctx.hh_rows); K = max(ctx.n_groups, 1)
+    F = Array{Float64}(undef, P, P, n_hh, K); Dv = Array{Float64}(undef, P, n_hh, K)
+    _check(ctx.ptr, ccall((:hank_fake_news_group, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, F, Dv))
+    return [_toeplitz_recursion(F[:, :, :, k], Dv[:, :, k]) for k in 1:K]
 end
 
 # ---- the transposed household block (hank_vjp) -----------------------------------------------------------------------------
