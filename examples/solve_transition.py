@@ -92,6 +92,42 @@ def group_report(x, m, ss, Z, cuts):
             "max_gap_to_linear": float(np.abs(dY - lin).max())}
 
 
+def group_gradient(x, m, ss, Z, cuts):
+    """The gradient of the distributional criterion L = ½ Σ_g Σ_t (C^g_t − C^g_ss)², C^g the consumption of wealth group g
+    (`group_report`'s groups under GROUP_CONS), with respect to the n_hh·P household inputs at the converged path x: ONE
+    hank_vjp_group with the cotangents C^g_t − C^g_ss, where the forward route takes n_hh·P tangent columns. Printed beside a central
+    difference of L (`primal` + `group_outputs()`) at three coordinates."""
+    from hank_amd.BackwardIteration import household_block, household_inputs
+    from hank_amd.groups import wealth_groups
+    P = m.compspec.T - 1
+    edges = [0.0, *[float(c) for c in cuts], 1.0]
+    wd, pd_ = m.heterogeneity["wealth"], m.heterogeneity["productivity"]
+    Wg = wealth_groups(ss.D, wd.grid.size, pd_.grid.size, edges)
+    hb = household_block(m).clone()
+    hb.set_boundary(ss.value, ss.D)
+    hb.set_group_outputs(Wg, hb.GROUP_CONS)
+    x_ss = np.tile(np.array([ss.vars[k] for k in ("Y", "KS", "r", "w")]), P)
+    xhh_ss = np.asarray(household_inputs(x_ss, {"Z": np.ones(P)}, m)[0])
+    xhh = np.asarray(household_inputs(x, {"Z": Z}, m)[0])
+    hb.primal(xhh_ss)
+    C_ss = hb.group_outputs()[0]
+
+    def loss(xh):
+        hb.primal(xh)
+        return 0.5 * float(np.sum((hb.group_outputs()[0] - C_ss) ** 2))
+
+    L = loss(xhh)
+    grad = hb.vjp_group(hb.group_outputs()[0] - C_ss)[:, :, 0]          # (n_hh, P)
+    checks = []
+    for i, t in ((0, 0), (1, P // 2), (0, P - 1)):
+        h = 1e-6 * max(1.0, abs(xhh[i, t]))
+        e = np.zeros_like(xhh); e[i, t] = h
+        fd = (loss(xhh + e) - loss(xhh - e)) / (2 * h)
+        checks.append({"input": i, "period": t, "vjp_group": float(grad[i, t]), "central_difference": fd})
+    hb.close()
+    return {"edges": edges, "loss": L, "gradient_norm": float(np.linalg.norm(grad)), "checks": checks}
+
+
 def scale_family(n_a=500, n_e=4, T=300, shock=0.01, scales=(0.5, 1.0, 2.0, -1.0), eps=1e-9, max_rounds=100):
     """The nonlinear responses to the shock at several multiples, solved in LOCKSTEP: scenario k has the path Z_t = 1 + scales[k]·
     shock·0.8^t and its own iterate x_k, and every round evaluates F(x_k) of all scenarios from ONE
@@ -350,8 +386,11 @@ if __name__ == "__main__":
     ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one hank_vjp_boundary, checked against two hank_jvp_boundary directions")
     ap.add_argument("--ss-curve", nargs=4, default=None, metavar=("VAR", "LO", "HI", "K"), help="the steady state's household side along a line in the free prices (VAR from LO to HI in K points, the others at the YAML's guesses) from ONE hank_ss_batch: the heterogeneous aggregates, the residual norm and the value steps per point")
     ap.add_argument("--groups", nargs="+", type=float, default=None, metavar="CDF", help="after the converged path: the wealth groups cut at these steady-state CDF points (0.5 0.9: bottom half, next 40 %%, top decile) — each group's mass, savings and consumption deviation, and the largest gap between the nonlinear path and the linear response J_group · dx")
+    ap.add_argument("--group-gradient", action="store_true", help="with --groups: the gradient of ½ Σ (C^g_t − C^g_ss)² over the groups' consumption paths with respect to the household inputs at the converged path, from ONE hank_vjp_group, beside a central difference at three coordinates")
     ap.add_argument("--ss-gradient", action="store_true", help="with --permanent: the gradient of ½‖F(x)‖² with respect to the ending steady state's household prices through V_T (hank_vjp_het_boundary, then hank_ss_vjp), beside a central difference in one random direction")
     a = ap.parse_args()
+    if a.group_gradient and not a.groups:
+        ap.error("--group-gradient requires --groups")
     import os
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world > 1:       # under torch.distributed.run: the Jacobian assembly is shared out over the ranks (one GPU each)
@@ -376,6 +415,8 @@ if __name__ == "__main__":
         out, x, m, ss = solve(a.n_a, a.n_e, a.T, a.shock, verbose=a.verbose, cold=a.cold, inner=a.inner, jacobian=a.jacobian, step=a.step, with_model=True)
         if a.groups:
             out["group_outputs"] = group_report(x, m, ss, 1.0 + a.shock * 0.8 ** np.arange(1, a.T), a.groups)
+            if a.group_gradient:
+                out["group_gradient"] = group_gradient(x, m, ss, 1.0 + a.shock * 0.8 ** np.arange(1, a.T), a.groups)
     out["n_gpus"] = world
     if rank == 0:
         print(json.dumps(out))

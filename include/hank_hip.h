@@ -407,6 +407,26 @@ int hank_jvp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const d
  *   left unwritten). Everything else as hank_vjp_boundary. */
 int hank_vjp_het_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar);
 int hank_vjp_het_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar);
+/* hank_vjp_group == the exact transpose of hank_get_group_outputs' tangent map: cotangents on the K group outputs of
+ * hank_set_group_outputs through the transposed sweeps at the recorded primal, whichever kernel family recorded it. Group k is the
+ * weighted dot of ForwardIteration.jl:303-307, so it enters the reverse of the distribution sweep (ForwardIteration.jl:339-420, on
+ * the reverse rule of transition_step, :131-192) as an output with f = W_k f_b and f_c = -sigma_b W_k, formed inside the kernel:
+ * nothing per grid point is stored. CONS groups also reach the inputs directly: xhh_bar_{i,t} += sum_k g[t,k] S[t][k][i].
+ *   grp_bar (P, K, M) column-major, the shape of hank_get_group_outputs' dagg_out; required.
+ *   agg_bar (P, n_het, M) column-major or NULL: cotangents on outputs 0 and 1 (hank_vjp's) in the same product. With agg_bar
+ *   n_het is 1 or 2 (cotangents on Value / UCE come from hank_vjp_het and add linearly); with NULL n_het must be 0.
+ *   xhh_bar (n_hh, P, M); value_end_bar, D_init_bar (G, M) column-major, either may be NULL (not wanted, left unwritten): the
+ *   cotangents of ss_end.value (BackwardIteration.jl:85) and ss_initial.D (ForwardIteration.jl:293), as in hank_vjp_boundary.
+ * HANK_ERR_BAD_ARG: a null grp_bar or xhh_bar, M < 1, an n_het that does not fit agg_bar, more LDS than the device has.
+ * HANK_ERR_NOT_READY: no groups set, before a primal, after a new boundary, after a persistent sweep that did not run.
+ * Leaves the record, the current tangent batch, the primal memo, the declared count and the schedule alone; shares hank_vjp's
+ * workspace per width (a later hank_vjp / hank_vjp_het returns the bits it returned before). hank_get_policy_cotangent_seq serves
+ * its total policy cotangent, hank_last_vjp_timings its two sweeps. No atomics, fixed-order sums: the same record, groups and
+ * cotangents give the same bits. A new hank_set_group_outputs is honoured by the next call. The _dev form takes device pointers
+ * and is asynchronous on the context's stream; extra workspace P * HANK_GROUP_MAX * M doubles, twice, per width. */
+int hank_vjp_group(hank_ctx *ctx, int32_t n_het, const double *agg_bar, const double *grp_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar);
+int hank_vjp_group_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, const double *d_grp_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar,
+                       double *d_D_init_bar);
 
 /* ---- derivatives through the steady state ------------------------------------------------------------
  * Two of the block's three inputs are steady-state objects: V_T is the fixed point of the EGM step at the steady-state prices

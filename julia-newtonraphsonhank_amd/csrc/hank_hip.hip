@@ -174,6 +174,9 @@ struct CotWork {
     DevBuf<double> xbar;            // (n_hh, P, M) column-major
     GraphExec g_A, g_B;
     GraphExec g_AX[2];              // Sweep A with NX = 1, 2 extra outputs (hank_vjp_het), captured on first use; Sweep B is g_B
+    DevBuf<double> gin, gb;         // hank_vjp_group, allocated on its first use at this width: the caller's (P, K, M) cotangents on the group outputs
+                                    // (staging) and the same as [P][K][M] (k_adj_in_grp), both at HANK_GROUP_MAX groups
+    GraphExec g_AG;                 // Sweep A with the context's groups (k_adj_dist_grp), captured on first use and dropped with the set (GroupSet)
     DevBuf<double> bnd_vbar, bnd_dbar;          // (G, M) column-major the boundary's cotangents (hank_vjp_boundary), allocated on its first use at this width
 };
 // The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
@@ -194,6 +197,9 @@ struct HxRecord { DevBuf<double> f, fc, S; bool valid = false; };
 // and their share of the record — the levels Y [P][K] and the CONS sums S [P][K][GRP_NS] (k_grp_record) — which belongs to the recorded
 // primal AND to this set of groups: ensure_grp_record builds it for the first reader, record_rewritten and a new set drop it. slab:
 // the direction-dependent buffers of hank_get_group_outputs, grown to the widest request.
+// hank_vjp_group's Sweep A graphs (CotWork::g_AG, one per cached width) hold K, the bases and the addresses of W and of the cotangents:
+// hank_set_group_outputs drops the group graph of EVERY cached width (after its stream synchronisation), so the next hank_vjp_group
+// captures against the new set. Nothing else of a CotWork depends on the groups.
 struct GroupSet {
     int K = 0;
     DevBuf<double> W, Y, S;
@@ -1991,6 +1997,7 @@ struct TanReq {
 };
 static int ensure_bnd_bufs(hank_ctx *ctx, TanWork &w);
 static int ensure_hx_record(hank_ctx *ctx);
+static int ensure_grp_record(hank_ctx *ctx);
 
 // the one enqueue of a request: the workspace of this width, every buffer a graph names (before any capture: the graph holds their
 // addresses), the inputs, the sweeps. batch_ran has named the batch when this returns HANK_OK; the copy-out is the entry's.
@@ -2557,6 +2564,8 @@ static int build_cotwork(hank_ctx *ctx, CotWork &w) {
     return HANK_OK;
 }
 static size_t adj_lds_dist(const Consts &c, const AdjGeom &g, int V) { return sizeof(double) * ((size_t)c.n_e * (g.R + 2) * g.NC * V + (size_t)c.n_e * c.n_e); }
+// k_adj_dist_grp: k_adj_dist's tile and Pi, then the K groups' cotangents of the block's columns
+static size_t adj_lds_dist_grp(const Consts &c, const AdjGeom &g, int V, int K) { return sizeof(double) * (adj_grp_lds_off(c.n_e, g, V) + (size_t)K * g.NC * V); }
 static size_t adj_lds_egm(const Consts &c, const AdjGeom &g, int V) {
     return sizeof(double) * ((size_t)c.n_e * g.R * g.NC * V + (((size_t)c.n_e * c.n_e + 1) & ~(size_t)1) + (size_t)c.n_e * 6 * g.NC * V);
 }
@@ -2584,6 +2593,28 @@ template <typename VT, int NX>
 static int capture_cot_graph_ax(hank_ctx *ctx, CotWork &w) {
     const AdjHx<VT, NX> hx{ctx->hx.f.get(), ctx->hx.fc.get(), reinterpret_cast<const VT *>(w.ybx.get())};
     return capture_cot_graph_a<VT, NX>(ctx, w, hx, &w.g_AX[NX - 1]);
+}
+
+// Sweep A's graph of a width with the context's groups (k_adj_dist_grp): it holds K, the bases and the addresses of W and w.gb
+template <typename VT>
+static int capture_cot_graph_ag(hank_ctx *ctx, CotWork &w) {
+    const Consts &c = ctx->c;
+    const GroupSet &gs = ctx->grp;
+    const int P = c.P;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(64 * c.n_e), grd((unsigned)w.g.nb, (unsigned)((w.g.MV + w.g.NC - 1) / w.g.NC));
+    const size_t ldsA = adj_lds_dist_grp(c, w.g, w.V, gs.K);
+    VT *st[2] = {reinterpret_cast<VT *>(w.st[0].get()), reinterpret_cast<VT *>(w.st[1].get())};
+    VT *pbar = reinterpret_cast<VT *>(w.pbar.get());
+    const VT *yb0 = reinterpret_cast<const VT *>(w.yb0.get()), *yb1 = reinterpret_cast<const VT *>(w.yb1.get());
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int cur = 0;
+    for (int t = P - 1; t >= 0; t--) {
+        hipLaunchKernelGGL((k_adj_dist_grp<VT>), grd, blk, ldsA, s, c, ctx->R, ctx->d_xhh, w.g, t, t == P - 1 ? 1 : 0, yb0, yb1, st[cur], st[cur ^ 1], pbar, gs.K, gs.codes,
+                           gs.W.get(), reinterpret_cast<const VT *>(w.gb.get()));
+        cur ^= 1;
+    }
+    return end_capture(ctx, &w.g_AG);
 }
 
 // the two graphs of a width, captured the first time hank_vjp runs at it: Sweep A (NX = 0) and Sweep B (P launches,
@@ -2646,26 +2677,43 @@ static int ensure_hx_record(hank_ctx *ctx) {
 // n_het > 2: Sweep A's graph with NX = n_het - 2 extra outputs, and their direct terms after Sweep B.
 // d_vend_bar, d_D0_bar (hank_vjp_boundary; device pointers, (G, M) column-major, either may be null): the cotangents of the terminal
 // value and of the initial distribution, exported from the sweeps' states (hank_boundary.h) — everything else is the same work.
+// grp_bar (hank_vjp_group; (P, K, M) column-major, where `kind` says): cotangents on the context's group outputs — Sweep A's graph
+// with the groups, and their direct terms after Sweep B; agg_bar may then be null (n_het = 0: no cotangent on outputs 0 and 1).
 static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out,
-                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr) {
+                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr, const double *grp_bar = nullptr) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
-    const int NX = n_het > 2 ? n_het - 2 : 0;
+    const int NX = n_het > 2 ? n_het - 2 : 0, K = grp_bar ? ctx->grp.K : 0;
     CotWork *w = nullptr;
     int rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
     if (rc) return rc;
     if (adj_lds_dist(c, w->g, w->V) > ctx->lds_max || adj_lds_egm(c, w->g, w->V) > ctx->lds_max)
         return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_e=%d needs more LDS per workgroup than the device has", c.n_e);
+    if (K > 0 && adj_lds_dist_grp(c, w->g, w->V, K) > ctx->lds_max)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_group: n_e=%d with K=%d groups needs more LDS per workgroup than the device has", c.n_e, K);
+    if (K > 0 && !w->gb) {
+        HIPC(ctx, w->gin.alloc(P * GRP_MAX * M));
+        HIPC(ctx, w->gb.alloc(P * GRP_MAX * M));      // (the group graph holds its address)
+    }
     if (!w->g_A) {
         if (!ctx->d_adj_sb) HIPC(ctx, ctx->d_adj_sb.alloc(P * c.n_e * ((size_t)c.n_a + 1)));      // (the graphs hold its address)
         rc = w->V == 2 ? capture_cot_graphs<double2>(ctx, *w) : capture_cot_graphs<double>(ctx, *w);
         if (rc) return rc;
     }
     hipStream_t s = ctx->stream;
-    HIPC(ctx, hipMemcpyAsync(w->ybar, agg_bar, sizeof(double) * P * n_het * M, kind, s));
+    if (agg_bar) HIPC(ctx, hipMemcpyAsync(w->ybar, agg_bar, sizeof(double) * P * n_het * M, kind, s));
+    if (K > 0) HIPC(ctx, hipMemcpyAsync(w->gin, grp_bar, sizeof(double) * P * K * M, kind, s));
     HIPC(ctx, join_side(ctx));      // D_t, the lottery and the grid aggregates come from the primal's forward sweep
     rc = ensure_adj_seg(ctx);
     if (rc) return rc;
+    if (K > 0) {
+        rc = ensure_grp_record(ctx);      // (before the capture, as below; the CONS sums read D_t)
+        if (rc) return rc;
+        if (!w->g_AG) {
+            rc = w->V == 2 ? capture_cot_graph_ag<double2>(ctx, *w) : capture_cot_graph_ag<double>(ctx, *w);
+            if (rc) return rc;
+        }
+    }
     if (NX > 0) {
         rc = ensure_hx_record(ctx);      // (before the capture: the graph holds the record's addresses)
         if (rc) return rc;
@@ -2675,10 +2723,15 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
             if (rc) return rc;
         }
     }
-    hipLaunchKernelGGL(k_adj_in, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->yb0, w->yb1);
+    if (agg_bar) hipLaunchKernelGGL(k_adj_in, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->yb0, w->yb1);
+    else {
+        HIPC(ctx, hipMemsetAsync(w->yb0, 0, sizeof(double) * P * M, s));
+        HIPC(ctx, hipMemsetAsync(w->yb1, 0, sizeof(double) * P * M, s));
+    }
+    if (K > 0) hipLaunchKernelGGL(k_adj_in_grp, dim3((unsigned)((P * K * M + 255) / 256)), dim3(256), 0, s, w->gin.get(), (int)P, K, M, w->gb.get());
     if (NX > 0) hipLaunchKernelGGL(k_adj_in_hx, dim3((unsigned)((P * NX * M + 255) / 256)), dim3(256), 0, s, w->ybar, (int)P, n_het, M, w->ybx.get());
     HIPC(ctx, ctx->spans.begin(VJP_A, s));
-    HIPC(ctx, hipGraphLaunch(NX > 0 ? w->g_AX[NX - 1] : w->g_A, s));
+    HIPC(ctx, hipGraphLaunch(K > 0 ? w->g_AG : (NX > 0 ? w->g_AX[NX - 1] : w->g_A), s));
     HIPC(ctx, ctx->spans.end_begin(VJP_A, (int)P, VJP_B, s));
     const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((M + BND_T - 1) / BND_T), (unsigned)c.n_e);      // the layout kernel
     // Sweep A's state after its last launch (t = 0) is the cotangent of D_0; Sweep B's first launches overwrite it
@@ -2696,6 +2749,10 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
                            ctx->hx.S.get(), w->xbar.get());
         HIPC(ctx, hipGetLastError());
     }
+    if (K > 0) {
+        hipLaunchKernelGGL(k_adj_grp_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, K, w->gb.get(), ctx->grp.S.get(), w->xbar.get());
+        HIPC(ctx, hipGetLastError());
+    }
     cot_ran(ctx, w, M, w->pbar);
     if (d_xhh_bar) HIPC(ctx, hipMemcpyAsync(d_xhh_bar, w->xbar, sizeof(double) * c.n_hh * P * M, hipMemcpyDeviceToDevice, s));
     *out = w;
@@ -2707,6 +2764,19 @@ static int vjp_args(hank_ctx *ctx, int n_het, const void *in, int M, const void 
         return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_het=%d reaches Value / UCE, which are not affine in the policy: their cotangents are not implemented (n_het must be 1 or 2)", n_het);
     if (n_het < 1 || n_het > 2) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp: n_het must be 1 (the policy variable) or 2 (and consumption), got %d", n_het);
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp");
+    return HANK_OK;
+}
+
+// hank_vjp_group's rules (grp_bar itself: the entries, below): agg_bar with n_het 1 or 2, or none with n_het 0; then the groups, then
+// the record — hank_get_group_outputs' order
+static int vjp_group_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out) {
+    if (!ctx || !out || M < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_group: bad argument (M=%d)", M);
+    if (in && (n_het < 1 || n_het > 2))
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_group: with agg_bar n_het must be 1 (the policy variable) or 2 (and consumption), got %d; cotangents on Value / UCE "
+                    "come from hank_vjp_het and add linearly", n_het);
+    if (!in && n_het != 0) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_group: n_het=%d without agg_bar (n_het must be 0 then)", n_het);
+    if (ctx->grp.K == 0) return fail(ctx, HANK_ERR_NOT_READY, "hank_vjp_group: no groups are set: call hank_set_group_outputs first");
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp_group");
     return HANK_OK;
 }
 
@@ -2723,12 +2793,12 @@ static int vjp_het_args(hank_ctx *ctx, int n_het, const void *in, int M, const v
 // too); the _dev form leaves the copies to enqueue_vjp and stays asynchronous. value_end_bar, D_init_bar (the _boundary entries):
 // the boundary's cotangents, either may be null (not wanted); the host form stages the wanted ones in the workspace of this width.
 static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, const void *), int n_het, const double *agg_bar, int M, double *xhh_bar,
-                        double *value_end_bar, double *D_init_bar, bool dev) {
+                        double *value_end_bar, double *D_init_bar, bool dev, const double *grp_bar = nullptr) {
     ENTER(ctx);
     int rc = args(ctx, n_het, agg_bar, M, xhh_bar);
     if (rc) return rc;
     CotWork *w = nullptr;
-    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, value_end_bar, D_init_bar);
+    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, value_end_bar, D_init_bar, grp_bar);
     const size_t GM = (size_t)ctx->c.G * M;
     if (value_end_bar || D_init_bar) {
         rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
@@ -2738,7 +2808,8 @@ static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *
             HIPC(ctx, w->bnd_dbar.alloc(GM));
         }
     }
-    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, value_end_bar ? w->bnd_vbar.get() : nullptr, D_init_bar ? w->bnd_dbar.get() : nullptr);
+    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, value_end_bar ? w->bnd_vbar.get() : nullptr, D_init_bar ? w->bnd_dbar.get() : nullptr,
+                     grp_bar);
     if (rc) return rc;
     HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
     if (value_end_bar) HIPC(ctx, hipMemcpyAsync(value_end_bar, w->bnd_vbar, sizeof(double) * GM, hipMemcpyDeviceToHost, ctx->stream));
@@ -2764,6 +2835,18 @@ int hank_vjp_het_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, i
 }
 int hank_vjp_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar) {
     return vjp_boundary(ctx, vjp_args, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false);
+}
+// (ForwardIteration.jl:303-307: the weighted dot; :339-420 on :131-192: the reverse rules; BackwardIteration.jl:85, ForwardIteration.jl:293: the exports)
+int hank_vjp_group(hank_ctx *ctx, int32_t n_het, const double *agg_bar, const double *grp_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    if (!grp_bar) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_group: grp_bar is required");
+    return vjp_boundary(ctx, vjp_group_args, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false, grp_bar);
+}
+int hank_vjp_group_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, const double *d_grp_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar,
+                       double *d_D_init_bar) {
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    if (!d_grp_bar) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_group: grp_bar is required");
+    return vjp_boundary(ctx, vjp_group_args, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true, d_grp_bar);
 }
 int hank_vjp_het_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar) { return vjp(ctx, vjp_het_args, n_het, d_agg_bar, M, d_xhh_bar, true); }
 int hank_vjp_het(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar) { return vjp(ctx, vjp_het_args, n_het, agg_bar, M, xhh_bar, false); }
@@ -3108,6 +3191,7 @@ int hank_set_group_outputs(hank_ctx *ctx, int32_t K, const double *W, const int3
     const size_t P = ctx->c.P, G = ctx->c.G;
     if (g.K > 0) HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (a reader of the old set may still be enqueued)
     g.valid = false;
+    for (CotWork &cw : ctx->cws) cw.g_AG.reset();      // (hank_vjp_group's graphs hold the old set: see GroupSet)
     const int K_old = g.K;
     g.K = 0;      // (until the new set is complete: a failed allocation or copy leaves no groups set)
     if (K != K_old) {

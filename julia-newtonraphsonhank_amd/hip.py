@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "hank_ss_batch", "hank_last_ss_batch_timings",
     "hank_get_lottery_record", "hank_get_forward_units",
     "hank_set_group_outputs", "hank_get_group_outputs", "hank_get_group_outputs_dev", "hank_fake_news_group",
+    "hank_vjp_group", "hank_vjp_group_dev",
 )
 
 
@@ -162,6 +163,8 @@ def load_library() -> C.CDLL:
     lib.hank_get_group_outputs.argtypes = [vp, dp, i32, dp, dp]
     lib.hank_get_group_outputs_dev.argtypes = [vp, vp, i32, vp, vp]
     lib.hank_fake_news_group.argtypes = [vp, dp, dp]
+    lib.hank_vjp_group.argtypes = [vp, i32, dp, dp, i32, dp, dp, dp]
+    lib.hank_vjp_group_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         if name in ("hank_get_lottery_record", "hank_get_forward_units") and not hasattr(lib, name):
             continue
@@ -810,6 +813,41 @@ class HouseholdBlock:
     def group_outputs_dev(self, d_dxhh: int, N: int, d_agg: int, d_dagg: int):
         """device-pointer form (asynchronous on the context's stream)."""
         self._chk(self._lib.hank_get_group_outputs_dev(self._ctx, d_dxhh or None, int(N), d_agg or None, d_dagg or None))
+
+    def vjp_group(self, grp_bar, agg_bar=None, n_het: int = 0, value_end: bool = False, D_init: bool = False):
+        """the transpose of `group_outputs`' tangent map (hank_vjp_group; the reverse rules of ForwardIteration.jl:339-420 with the
+        weighted dot of :303-307): grp_bar (P, K, M) — or (P, K) for M = 1 — holds cotangents on the K group outputs, the shape of
+        `group_outputs`' dagg. agg_bar (P, n_het, M), n_het 1 or 2, adds cotangents on outputs 0 and 1 (`vjp`'s) in the same product;
+        without it n_het is 0. -> xhh_bar (n_hh, P, M); with value_end or D_init the triple (xhh_bar, value_end_bar, D_init_bar) of
+        `vjp_het_boundary`, an unwanted one None. `policy_cotangent_seq(M)` serves its policy cotangent afterwards."""
+        gb, M = None, None
+        if grp_bar is not None:
+            gb = np.asarray(grp_bar, dtype=np.float64)
+            if gb.ndim == 2:
+                gb = gb[:, :, None]
+            if gb.ndim != 3:
+                raise ValueError("grp_bar must be (P, K) or (P, K, M)")
+            M = gb.shape[2]
+            gb = _f(gb, (self.P, self.n_groups, M) if self.n_groups > 0 else None)      # (the library refuses a call without groups)
+        yb = None
+        if agg_bar is not None:
+            Ma, yb = self._cotangents(agg_bar, n_het, het=False)
+            if M is not None and Ma != M:
+                raise ValueError(f"agg_bar has {Ma} columns, grp_bar {M}")
+            M = Ma
+        M = 1 if M is None else M
+        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
+        vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if value_end else None
+        db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if D_init else None
+        self._chk(self._lib.hank_vjp_group(self._ctx, int(n_het), _opt(yb), _opt(gb), M, _p(out), _opt(vb), _opt(db)))
+        return (out, vb, db) if (value_end or D_init) else out
+
+    def vjp_group_dev(self, n_het: int, d_agg_bar_ptr: int, d_grp_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_value_end_bar_ptr: int = 0,
+                      d_D_init_bar_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); an agg_bar pointer of 0 goes with n_het = 0, a boundary pointer
+        of 0 is not wanted."""
+        self._chk(self._lib.hank_vjp_group_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr or None), C.c_void_p(d_grp_bar_ptr or None), int(M),
+                                               C.c_void_p(d_xhh_bar_ptr), C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
 
     def fake_news_group(self):
         """the Toeplitz form of `fake_news_het` for the group outputs (hank_fake_news_group): -> F (P, P, n_hh, K),

@@ -417,6 +417,26 @@ function hank_vjp_het_boundary!(xhh_bar::Array{Float64,3}, value_end_bar::Union{
     return xhh_bar, value_end_bar, D_init_bar
 end
 
+# hank_vjp_group: cotangents on the K group outputs of hank_set_group_outputs (grp_bar (P, K, M), the shape of
+# hank_get_group_outputs' tangents) through the transposed sweeps — the exact transpose of hank_get_group_outputs' tangent map
+# (ForwardIteration.jl:303-307 is the weighted dot, :339-420 the reverse rule). agg_bar (P, n_het, M), n_het 1 or 2, or nothing:
+# cotangents on outputs 0 and 1 in the same product. value_end_bar, D_init_bar (n_a, n_e, M) or nothing (not wanted).
+# Returns (xhh_bar, value_end_bar, D_init_bar).
+function hank_vjp_group!(xhh_bar::Array{Float64,3}, ctx::HankCtx, grp_bar::Array{Float64,3}; agg_bar::Union{Nothing,Array{Float64,3}} = nothing,
+                         value_end_bar::Union{Nothing,Array{Float64,3}} = nothing, D_init_bar::Union{Nothing,Array{Float64,3}} = nothing)
+    P, K, M = size(grp_bar)
+    @assert P == ctx.P && (ctx.n_groups == 0 || K == ctx.n_groups) && size(xhh_bar) == (length(ctx.hh_rows), P, M)
+    @assert agg_bar === nothing || (size(agg_bar, 1) == P && size(agg_bar, 3) == M)
+    @assert all(s -> s === nothing || size(s) == (ctx.n_a, ctx.n_e, M), (value_end_bar, D_init_bar))
+    n_het = agg_bar === nothing ? 0 : size(agg_bar, 2)
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve agg_bar value_end_bar D_init_bar begin
+        _check(ctx.ptr, ccall((:hank_vjp_group, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                              ctx.ptr, Int32(n_het), ptr(agg_bar), grp_bar, Int32(M), xhh_bar, ptr(value_end_bar), ptr(D_init_bar)))
+    end
+    return xhh_bar, value_end_bar, D_init_bar
+end
+
 # ---- derivatives through the steady state (hank_ss_jvp, hank_ss_vjp) ----------------------------------------------------------------
 # What ForwardDiff.jacobian(F, p) carries through the VFI and invariant_dist inside find_ss (SteadyState.jl:195, :132-141;
 # ForwardIteration.jl:446-530), from the record of hank_primal at the constant steady-state path with the steady state as both
