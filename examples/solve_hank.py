@@ -6,6 +6,10 @@ family HANK_VF_ONE_ASSET_HANK; --jacobian columns: batched unit-tangent JVPs) ->
 response to a monetary-policy shock.
 
     python examples/solve_hank.py [--n-a 1000 --n-e 7 --T 500 --shock 0.0025]
+    python examples/solve_hank.py --discount-shock 0.002 0.8 [--gradient]
+        a household-side shock instead: the discount factor follows beta_t = beta (1 + SIZE RHO^t) (HouseholdBlock.set_discount_path);
+        the nonlinear transition beside the linear response -J̅⁻¹ J_beta dbeta (SteadyStateJacobian.shock_jacobian); with --gradient
+        the gradient of ½‖F‖² with respect to the path from one hank_vjp_shock, beside a central difference in two of its entries
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/solve_hank.py
         one process per GPU (RCCL): the unit-tangent chunks of the Jacobian assembly are shared out over the ranks and
         all-gathered; the Newton iteration itself (one tangent per inner step) runs replicated on every rank."""
@@ -152,7 +156,78 @@ def het_in_sweep(n_a=1000, n_e=7, T=500, shock=0.0025, rho=0.6, spec="one_asset_
     return out
 
 
-if __name__ == "__main__":
+def _discount_setup(n_a, n_e, T, size, rho, spec):
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    m, ss = build(n_a, n_e, T, spec)
+    P = T - 1
+    keys = h.vars_of_type(m, "endogenous")
+    x0 = np.tile(np.array([ss.vars[k] for k in keys]), P)
+    dbeta = m.params.β * size * rho ** np.arange(P)
+    exog = {"ei": np.zeros(P)}
+    return h, m, ss, keys, x0, exog, dbeta
+
+
+def discount_shock(n_a=1000, n_e=7, T=500, size=0.002, rho=0.8, eps=1e-9, spec="one_asset_hank.yaml"):
+    """The transition under beta_t = beta (1 + size rho^t), no other shock: Newton on the nonlinear system with the path set on the
+    household block, beside the first-order response dx = -J̅⁻¹ (∂F/∂beta) dbeta with ∂F/∂beta assembled from `shock_jacobian`
+    (hank_fake_news_shock: one backward tangent sweep seeded at the last period). Prints output's and the policy variable's
+    deviations from the steady state, both ways."""
+    h, m, ss, keys, x0, exog, dbeta = _discount_setup(n_a, n_e, T, size, rho, spec)
+    from hank_amd.SteadyStateJacobian import shock_jacobian
+    P = T - 1
+    J = h.getSteadyStateJacobian(ss, m)                      # the steady-state J̅, taken before the path is set
+    lin0 = h.LinearizedFunction(x0, exog, m, ss, ss)
+    Jb = shock_jacobian(lin0.hb, lin0._n_out)                # (outputs, P, P) at the stationary record lin0 holds
+    dx_lin = -np.linalg.solve(np.asarray(J), lin0.residual_shock_jacobian(Jb) @ dbeta)
+    t0 = time.perf_counter()
+    x = h.NewtonRaphsonHANK(x0, J, exog, m, ss, ss, ε=eps, discount_path=m.params.β + dbeta)
+    t_newton = time.perf_counter() - t0
+    lin = h.LinearizedFunction(x, exog, m, ss, ss, discount_path=m.params.β + dbeta)
+    dX, dL = (x - x0).reshape(len(keys), P, order="F"), dx_lin.reshape(len(keys), P, order="F")
+    agg_dev = lin.aggs[:, 0] - lin0.aggs[:, 0]               # device output 0: the policy variable's aggregate
+    # ... and its first-order response: the household block's tangent under (dx_lin, dbeta) at the stationary record
+    from hank_amd.BackwardIteration import household_inputs
+    from hank_amd.dual import Dual
+    _, dxhh = household_inputs(Dual.seed(x0, dx_lin[:, None]), exog, m)
+    lin0._own_record()
+    agg_lin = lin0.hb.jvp_shock(np.asarray(dxhh, dtype=np.float64).reshape(lin0.hb.n_hh, P, 1), dbeta)[:, 0]
+    show = [k for k in ("Y", "y", "r") if k in keys][:2] or list(keys[:2])
+    return {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "shock": f"beta_t = beta*(1 + {size}*{rho}^t)",
+            "newton_s": round(t_newton, 3), "newton_iterations": h.NewtonRaphsonHANK.iterations, "residual_norm": float(np.linalg.norm(lin.Fx)),
+            "deviation_nonlinear": {k: [float(v) for v in dX[keys.index(k), :4]] for k in show},
+            "deviation_linear": {k: [float(v) for v in dL[keys.index(k), :4]] for k in show},
+            "policy_variable": m.value_fn.outputs[0], "policy_variable_deviation_nonlinear": [float(v) for v in agg_dev[:4]],
+            "policy_variable_deviation_linear": [float(v) for v in agg_lin[:4]],
+            "max_abs_difference_over_max": float(np.max(np.abs(dX - dL)) / np.max(np.abs(dX)))}
+
+
+def discount_gradient(n_a=1000, n_e=7, T=500, size=0.002, rho=0.8, spec="one_asset_hank.yaml", step=1e-6):
+    """The gradient of ½‖F(x0)‖² with respect to the discount-factor path at the Newton starting point (the steady state repeated,
+    where F ≠ 0 under the path): ONE `LinearizedFunction.vjp_shock` (hank_vjp_shock), beside a central difference in the first and
+    the last entry of the path."""
+    h, m, ss, keys, x0, exog, dbeta = _discount_setup(n_a, n_e, T, size, rho, spec)
+    path = m.params.β + dbeta
+    lin = h.LinearizedFunction(x0, exog, m, ss, ss, discount_path=path)
+    lin.vjp_shock(lin.Fx)                                     # warm-up: workspace, graphs, the residual layer's linearisation
+    t0 = time.perf_counter()
+    g = lin.vjp_shock(lin.Fx)
+    t_rev = time.perf_counter() - t0
+    fd = {}
+    for t in (0, T - 2):
+        f = []
+        for sgn in (1.0, -1.0):
+            p = path.copy()
+            p[t] += sgn * step
+            F = h.LinearizedFunction(x0, exog, m, ss, ss, discount_path=p).Fx
+            f.append(0.5 * float(F @ F))
+        fd[t] = (f[0] - f[1]) / (2 * step)
+    return {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "merit": 0.5 * float(lin.Fx @ lin.Fx),
+            "gradient_norm": float(np.linalg.norm(g)), "reverse_s": round(t_rev, 5), "reverse_vjps": 1,
+            "beta_bar": {str(t): float(g[t]) for t in fd}, "central_difference": {str(t): float(v) for t, v in fd.items()}}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-a", type=int, default=1000)
     ap.add_argument("--n-e", type=int, default=7)
@@ -166,7 +241,17 @@ if __name__ == "__main__":
     ap.add_argument("--gradient", action="store_true", help="the gradient of ½‖F(x)‖² at the starting point: one transposed product against n_hh·P JVP columns")
     ap.add_argument("--boundary-gradient", action="store_true", help="the gradient of ½‖F(x)‖² with respect to the boundary (V_T, D_0) at the starting point: one transposed boundary product, checked against two forward boundary directions")
     ap.add_argument("--het-in-sweep", action="store_true", help="J(x)·y of a model that reads Value / UCE: hank_jvp + hank_get_het_outputs against one hank_jvp_het, timed side by side")
-    a = ap.parse_args()
+    ap.add_argument("--discount-shock", type=float, nargs=2, metavar=("SIZE", "RHO"), default=None,
+                    help="a path of the discount factor, beta_t = beta (1 + SIZE RHO^t), instead of the monetary shock: the nonlinear transition beside the linear response; with --gradient the path's gradient of ½‖F‖²")
+    return ap.parse_args(argv)
+
+
+if __name__ == "__main__":
+    a = parse_args()
+    if a.discount_shock is not None:
+        fn = discount_gradient if a.gradient else discount_shock
+        print(json.dumps(fn(a.n_a, a.n_e, a.T, a.discount_shock[0], a.discount_shock[1], spec=a.spec)))
+        sys.exit(0)
     if a.boundary_gradient:
         print(json.dumps(boundary_gradient(a.n_a, a.n_e, a.T, a.shock, spec=a.spec)))
         sys.exit(0)

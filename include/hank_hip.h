@@ -428,6 +428,59 @@ int hank_vjp_group(hank_ctx *ctx, int32_t n_het, const double *agg_bar, const do
 int hank_vjp_group_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, const double *d_grp_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar,
                        double *d_D_init_bar);
 
+/* ---- a path of the discount factor: beta_t --------------------------------------------------------------
+ * The household's own primitives are constants of a context; the one users move most is the discount factor — the demand /
+ * preference shock of the HANK literature. beta enters the EGM step once, cm = (beta E_t[V_{t+1}])^(-1/gamma)
+ * (KrusellSmith.jl:59-62), inside the backward loop (BackwardIteration.jl:90-113). A PATH has no counterpart in the reference,
+ * which takes beta from the model's parameters (`model.params.β`) in every period.
+ * DATING: beta_t is the factor in period t's Euler equation, u'(c_t) = beta_t E_t[V_{t+1}], t = 0 .. P-1; beta_{P-1} multiplies
+ * the expectation of the terminal V_T (`ss_end.value`, BackwardIteration.jl:85).
+ *
+ * hank_set_discount_path (KrusellSmith.jl:59-62; BackwardIteration.jl:90-113; no counterpart in the reference: beta comes from
+ * the model's parameters there): beta_t [P] on the host; NULL returns the context to the constant hank_model.beta (with no path
+ * set that changes nothing). A non-finite or non-positive entry is HANK_ERR_BAD_ARG and nothing changes: the path in force and the
+ * record stay valid. Setting or clearing a path invalidates what a new boundary invalidates — the record, the current tangent
+ * batch, the policy cotangent, the primal memo (an x recorded under another path is not recognised).
+ * WHILE A PATH IS SET hank_primal[_dev], hank_primal_jvp[_dev] and hank_jvp[_dev] run on the per-period launches whatever
+ * HANK_SCHEDULE says (the persistent, wide and HANK_XSPEC kernels hold beta as a constant and are left as they are), without
+ * changing the context's schedule policy and without counting a fallback — hank_jvp_boundary's precedent; hank_last_timings and
+ * hank_info report the launch family, hank_stats out[0] does not grow. hank_vjp*, hank_jvp_boundary, hank_jvp_het,
+ * hank_get_het_outputs and hank_get_group_outputs read the record and work at it unchanged. The entries that are defined at ONE
+ * beta answer HANK_ERR_NOT_READY: hank_primal_batch[_dev], hank_ss_batch, hank_vfi, hank_ss_jvp[_dev], hank_ss_vjp[_dev] and
+ * every hank_fake_news*. The step entries hank_backward_step[_dual] keep using hank_model.beta. */
+int hank_set_discount_path(hank_ctx *ctx, const double *beta_t);
+/* hank_jvp_shock == the partials of the block under Duals seeded in xVals AND in beta_t (KrusellSmith.jl:59-62 under Duals, inside
+ * the loop of BackwardIteration.jl:90-113; a path has no counterpart in the reference, which takes beta from the model's
+ * parameters), N directions at once:
+ *   dxhh (n_hh, P, N) as in hank_jvp, or NULL (zeros); dbeta (P, N) column-major, or NULL (zeros); both NULL is HANK_ERR_BAD_ARG.
+ *   dagg_out (P, N) as in hank_jvp.
+ * d s_t / d beta_t = rho_t (-1/gamma) cm_t / beta_t at every knot, cm_t rebuilt from the recorded s_t: a rank-one seed of the knots'
+ * tangent in EVERY period, applied by a seed kernel behind each launch of the backward tangent sweep (2 P + 3 launches; the forward
+ * sweep is hank_jvp's). Works with or without a path (beta_t = hank_model.beta then). Always the per-period launches, the schedule
+ * left alone; needs a valid record (HANK_ERR_NOT_READY). Its batch becomes the current one, named as hank_jvp names it:
+ * hank_get_dpolicy_seq, hank_get_grid_aggregates, hank_get_het_outputs (every declared output) and hank_get_group_outputs serve
+ * it. beta has NO direct term in any output: the caller passes the same dxhh (or zeros) to those getters. With dbeta zero or NULL
+ * dagg_out and hank_get_dpolicy_seq equal hank_jvp's under HANK_SCHEDULE=launch bit for bit. */
+int hank_jvp_shock(hank_ctx *ctx, const double *dxhh, const double *dbeta, int32_t N, double *dagg_out);
+int hank_jvp_shock_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dbeta, int32_t N, double *d_dagg_out);
+/* hank_vjp_shock == hank_vjp_het (its n_het rule, its refusals, its workspace, what it leaves alone) plus the cotangent of the
+ * path (the transpose of KrusellSmith.jl:59-62's beta inside the loop of BackwardIteration.jl:90-113; no counterpart in the
+ * reference, which differentiates forward only and takes beta from the model's parameters):
+ *   beta_bar (P, M) column-major, required: beta_bar_t[m] = sum_{e,i} (d s_t / d beta_t)[e,i] sbar_t[e,i,m], sbar_t the knots'
+ *   cotangent of Sweep B at period t — per-block partials behind every period's launch (the row blocks hank_vjp uses at this width),
+ *   then one fixed-order sum over the blocks: no atomics, the same inputs give the same bits. P + 2 launches more in Sweep B.
+ *   xhh_bar equals hank_vjp_het's bit for bit. The exact transpose of hank_jvp_shock followed by hank_get_het_outputs. */
+int hank_vjp_shock(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *beta_bar);
+int hank_vjp_shock_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_beta_bar);
+/* hank_fake_news_shock: the Toeplitz column block of every heterogeneous output with respect to beta at the steady state
+ * (KrusellSmith.jl:59-62; BackwardIteration.jl:90-113; the recursion of SteadyStateJacobian.jl:363-371 — a beta path has no
+ * counterpart in the reference, which takes beta from the model's parameters). hank_fake_news_het's preconditions, refusals,
+ * definitions and recursion with the input fixed to beta; no path may be set. The policy responses come from ONE backward tangent
+ * sweep seeded with d beta_{P-1} = 1; the lottery impulses, expectation vectors and products are shared code.
+ *   F_out (P, P, n_het): F[u, j, o] = E^o_u . iota_j;  Dv_out (P, n_het): Dv[j, o] = sum D_ss (d f_o / d a') Y_j — the direct
+ *   term d_{o,beta} is zero for every output. J_o[t, s] = J_o[t-1, s-1] + F[t, s, o], J_o[0, s] = Dv[s, o] + F[0, s, o]. */
+int hank_fake_news_shock(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out);
+
 /* ---- derivatives through the steady state ------------------------------------------------------------
  * Two of the block's three inputs are steady-state objects: V_T is the fixed point of the EGM step at the steady-state prices
  * (the inner loop of get_xVals, SteadyState.jl:132-141) and D_0 the stationary distribution of the lottery that step induces

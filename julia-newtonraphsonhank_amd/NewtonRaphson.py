@@ -42,8 +42,12 @@ class LinearizedFunction:
     het_in_sweep = False                # True: a model that reads Value / UCE (device outputs >= 2) takes every output's tangent from ONE
                                         # hank_jvp_het instead of hank_jvp + hank_get_het_outputs; the two differ by the rounding of sums
 
-    def __init__(self, x, exog_paths, mod: SequenceModel, ss_initial, ss_ending):
+    def __init__(self, x, exog_paths, mod: SequenceModel, ss_initial, ss_ending, discount_path=None):
+        """discount_path: beta_t (P,), the discount factor of period t's Euler equation (HouseholdBlock.set_discount_path; not in the
+        reference, which reads beta from the model's parameters); None: the model's constant. The path is set on the model's
+        context before the primal is recorded, and restored with the record when another user of the context changed it."""
         self.x = np.asarray(x, dtype=np.float64)
+        self.discount_path = None if discount_path is None else np.ascontiguousarray(discount_path, dtype=np.float64)
         self.mod, self.exog_paths, self.ss_initial, self.ss_ending = mod, exog_paths, ss_initial, ss_ending
         self.hb = household_block(mod)
         xhh, _ = household_inputs(self.x, exog_paths, mod)
@@ -110,6 +114,9 @@ class LinearizedFunction:
         it currently holds (BackwardIteration and other linearisations bump it too)."""
         hb = self.hb
         hb.set_boundary(self.ss_ending.value, self.ss_initial.D)
+        cur, want = getattr(hb, "discount_path", None), self.discount_path
+        if (cur is None) != (want is None) or (want is not None and not np.array_equal(cur, want)):
+            hb.set_discount_path(want)          # (the context is shared: a linearisation without a path clears another's)
         self.agg = hb.primal(self._xhh)
         if self._n_out > 2:
             ensure_het_outputs(hb, self._n_out)
@@ -260,6 +267,46 @@ class LinearizedFunction:
             _, vb, db = self.hb.vjp_boundary(agg_bar, self._n_out)
         return (vb[:, :, 0].copy(), db[:, :, 0].copy()) if single else (vb, db)
 
+    def _shock_ready(self):
+        if self._Rx is None:
+            self._linearise_residuals()
+        self._own_record()
+
+    def jvp_shock(self, dbeta):
+        """∂F/∂beta · dbeta at this x: the residuals' tangent under a direction dbeta (P,) or (P, N) of the discount-factor path, x
+        held fixed — `_Ragg` composed with ONE hank_jvp_shock (+ hank_get_het_outputs: beta has no direct term in any output)."""
+        db = np.asarray(dbeta, dtype=np.float64)
+        single = db.ndim == 1
+        db = db[:, None] if single else db
+        self._shock_ready()
+        hb = self.hb
+        d0 = hb.jvp_shock(None, db)
+        daggs = d0[:, None, :] if self._n_out == 1 else hb.het_outputs(self._n_out, np.zeros((hb.n_hh, hb.P, db.shape[1])))[1]
+        out = self._Ragg @ np.concatenate([daggs[:, j, :] for j in self._out_idx], axis=0)
+        return out[:, 0].copy() if single else out
+
+    def vjp_shock(self, ȳ):
+        """the transpose of `jvp_shock`: ȳ (n,) or (n, M) -> beta_bar (P,) or (P, M), the gradient of ȳ·F with respect to the
+        discount-factor path, from ONE hank_vjp_shock."""
+        ȳ = np.asarray(ȳ, dtype=np.float64)
+        single = ȳ.ndim == 1
+        Yb = ȳ[:, None] if single else ȳ
+        self._shock_ready()
+        P, M = self.mod.compspec.T - 1, Yb.shape[1]
+        ab = np.asarray(self._Ragg.T @ Yb).reshape(len(self.het), P, M)
+        agg_bar = np.zeros((P, self._n_out, M))
+        for j, o in enumerate(self._out_idx):
+            agg_bar[:, o, :] += ab[j]
+        _, bb = self.hb.vjp_shock(agg_bar, self._n_out)
+        return bb[:, 0].copy() if single else bb
+
+    def residual_shock_jacobian(self, J_beta):
+        """∂F/∂beta (n, P) from the household block's J_beta (n_out, P, P) of `SteadyStateJacobian.shock_jacobian`: `_Ragg` composed
+        with the rows of the heterogeneous variables the equations read."""
+        if self._Rx is None:
+            self._linearise_residuals()
+        return np.asarray(self._Ragg @ np.concatenate([np.asarray(J_beta)[j] for j in self._out_idx], axis=0))
+
     def as_linear_operator(self):
         """J(x) as a scipy.sparse.linalg.LinearOperator with both products: matvec / matmat = `jvp`, rmatvec / rmatmat = `vjp`
         (`vjp_het` for a model whose heterogeneous variables reach Value or UCE) — LSQR / LSMR, BiCG, QMR and every other user of
@@ -363,14 +410,14 @@ def _device_inverse_solver(J, device=None):
 @host_algebra
 def y_Iteration(J̅, x, y0, exog_paths, mod: SequenceModel, ss_initial, ss_ending, *, precond=None,
                 α: float | None = None, γ: float = 1.5, ε: float = 1e-9, verbose: bool = False, max_inner: int = 10_000,
-                linear_solver: str = "auto", inner: str = "fixed_point"):
+                linear_solver: str = "auto", inner: str = "fixed_point", discount_path=None):
     """inner iteration for the search direction y with J(x)·y = F(x) (NewtonRaphson.jl:65-114).
 
     inner="fixed_point" (default, the reference): y ← y + α·J̅⁻¹(F(x) − J(x)·y). The reference accepts α (:72) and
     overrides it with 0.5 (:102): `α=None` is that; a value passed here is honoured (α = 1 is the undamped iteration).
     inner="krylov" (opt-in, not in the reference): GMRES on J(x) with J̅⁻¹ as right preconditioner — the same fixed point
     (the exact Newton step) in a handful of JVPs instead of the ≈ 21 that α = 0.5 needs to contract 1e-9 by halves."""
-    lin = LinearizedFunction(x, exog_paths, mod, ss_initial, ss_ending)
+    lin = LinearizedFunction(x, exog_paths, mod, ss_initial, ss_ending, discount_path=discount_path)
     y_Iteration.last_Fx = lin.Fx            # F(x) of this linearisation: the step rule's ‖F(x)‖ (NewtonRaphsonHANK, step="backtrack")
     y = np.asarray(y0, dtype=np.float64)
     n = len(y)
@@ -492,7 +539,7 @@ def residuals_batch(xs, exog_paths, mod: SequenceModel, ss_initial, ss_ending):
 @host_algebra
 def NewtonRaphsonHANK(x_0, J̅, exog_paths, mod: SequenceModel, ss_initial, ss_ending, *, ε: float = 1e-9,
                       verbose: bool = False, linear_solver: str = "auto", inner: str = "fixed_point", α: float | None = None,
-                      step: str = "full", n_trial: int = 6, c1: float = 1e-4):
+                      step: str = "full", n_trial: int = 6, c1: float = 1e-4, discount_path=None):
     """outer Newton loop (NewtonRaphson.jl:27-46): x ← x − y until ‖y‖ ≤ ε or 100 iterations. `inner` / `α`: see y_Iteration
     (defaults = the reference's damped fixed point).
 
@@ -500,16 +547,22 @@ def NewtonRaphsonHANK(x_0, J̅, exog_paths, mod: SequenceModel, ss_initial, ss_e
     alphaUpdate is a stub, NewtonRaphson.jl:117-120): after each y_Iteration the trials x − 2^-j y, j = 0 .. n_trial-1, are
     evaluated in ONE `residuals_batch` and `backtrack` picks the step; ‖F(x)‖ is the linearisation's own (`y_Iteration.last_Fx`),
     not one more primal. A direction already below ε (the loop's last) is taken whole, without trials: at that size the trials differ
-    by the inner loop's own tolerance and say nothing. `NewtonRaphsonHANK.step_sizes` lists the accepted α, `.residual_norms` ‖F‖ at every iterate."""
+    by the inner loop's own tolerance and say nothing. `NewtonRaphsonHANK.step_sizes` lists the accepted α, `.residual_norms` ‖F‖ at every iterate.
+
+    discount_path: beta_t (P,) (`LinearizedFunction`): the transition under a path of the discount factor. J̅ is still the
+    steady-state Jacobian: take it before the path is set, or on a clone of the context without one."""
     if step not in ("full", "backtrack"):
         raise ValueError(f"unknown step rule {step!r} (full | backtrack)")
+    if discount_path is not None and step == "backtrack":
+        raise ValueError("step='backtrack' evaluates its trials with hank_primal_batch, which is defined at one discount factor: use step='full' with a discount_path")
     x = np.asarray(x_0, dtype=np.float64)
     y = x.copy()
     i = 1
     NewtonRaphsonHANK.step_sizes, NewtonRaphsonHANK.residual_norms = [], []
     try:
         while ε < np.linalg.norm(y) and i < 100:
-            y = y_Iteration(J̅, x, y, exog_paths, mod, ss_initial, ss_ending, verbose=verbose, linear_solver=linear_solver, inner=inner, α=α)
+            y = y_Iteration(J̅, x, y, exog_paths, mod, ss_initial, ss_ending, verbose=verbose, linear_solver=linear_solver, inner=inner, α=α,
+                            discount_path=discount_path)
             if step == "full":
                 x = x - y
             elif not ε < np.linalg.norm(y):         # a step below the tolerance ends the loop: taken whole, as the reference takes it

@@ -49,6 +49,15 @@ def group_jacobian(block):
     return np.stack([household_jacobian(F[..., k], Dv[..., k]).transpose(1, 0, 2) for k in range(F.shape[3])])
 
 
+def shock_jacobian(block, n_het):
+    """d Y^o_t / d beta_s at the steady state for the first n_het heterogeneous outputs, beta_s the discount factor of period s's
+    Euler equation (HouseholdBlock.set_discount_path): `block.fake_news_shock(n_het)`'s F (P, P, n_het) and Dv (P, n_het) through
+    the recursion of `household_jacobian`, once per output. `block` holds the stationary primal and no path. Returns J_beta
+    (n_het, P, P): J[o, t, s]."""
+    F, Dv = block.fake_news_shock(n_het)
+    return np.stack([household_jacobian(F[..., o:o + 1], Dv[..., o:o + 1])[0] for o in range(F.shape[2])])
+
+
 def direct_blocks(model: SequenceModel, ss):
     """d R_t / d xMat[:, t + o] at the steady state for every offset o in -max_lag..max_lead: the `blocks` of
     SteadyStateJacobian.jl:124-145, from ONE evaluation of the compiled equations on a (1 + max_lag + max_lead)-column

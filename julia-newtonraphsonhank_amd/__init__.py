@@ -18,7 +18,7 @@ from .BackwardIteration import BackwardIteration, household_block
 from .ForwardIteration import ForwardIteration, make_endogenous_transition, transition_step
 from .SteadyState import SSAssembler, SteadyState, find_ss, get_SteadyStates
 from .NewtonRaphson import LinearizedFunction, NewtonRaphsonHANK, StepRuleError, backtrack, make_fullFunction, residuals_batch, y_Iteration
-from .SteadyStateJacobian import getSteadyStateJacobian, group_jacobian
+from .SteadyStateJacobian import getSteadyStateJacobian, group_jacobian, shock_jacobian
 from . import groups
 from .hip import HouseholdBlock, HankHIPError, KnotsNotSortedError, DomainError, NoDeviceError
 

@@ -14,6 +14,7 @@
 #include "hank_ssbatch.h"
 #include "hank_adjoint.h"
 #include "hank_boundary.h"
+#include "hank_shock.h"
 #include "hank_ssdiff_launch.h"
 #include "../../include/hank_hip.h"
 
@@ -101,6 +102,10 @@ struct TanWork {
     unsigned nbf = 0;
     // The tangent-only graphs, each captured on its first use at this width, named HERE and nowhere else: bnd — with the boundary's
     // seed kernels in them (hank_boundary.h); NX — the forward sweep with that many extra reductions (hank_jvp_het, n_het = 2 + NX)
+    // hank_jvp_shock (hank_shock.h), allocated on its first use at this width: the caller's dbeta (P, N) column-major (staging) and the
+    // same as [P][N] (k_shk_in); g_tback_shk: the backward sweep with the seed of every period between its launches
+    DevBuf<double> shk_in, shk_db;
+    GraphExec g_tback_shk;
     GraphExec &tan_back(bool bnd) { return g_tback[bnd]; }
     GraphExec &tan_fwd(bool bnd, int NX) { return g_tfwd[bnd][NX]; }
 private:
@@ -177,6 +182,8 @@ struct CotWork {
     DevBuf<double> gin, gb;         // hank_vjp_group, allocated on its first use at this width: the caller's (P, K, M) cotangents on the group outputs
                                     // (staging) and the same as [P][K][M] (k_adj_in_grp), both at HANK_GROUP_MAX groups
     GraphExec g_AG;                 // Sweep A with the context's groups (k_adj_dist_grp), captured on first use and dropped with the set (GroupSet)
+    DevBuf<double> bb_part, bb_rm, bb_cm;       // hank_vjp_shock, allocated on its first use at this width: beta_bar's partials [P][nb][M], their sums [P][M] and (P, M) column-major
+    GraphExec g_BS;                 // Sweep B with beta_bar's reduction behind every period's launch (k_shk_bbar), captured on first use
     DevBuf<double> bnd_vbar, bnd_dbar;          // (G, M) column-major the boundary's cotangents (hank_vjp_boundary), allocated on its first use at this width
 };
 // The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
@@ -304,6 +311,13 @@ struct hank_ctx {
     hipEvent_t ev_fork = nullptr, ev_side = nullptr;
     bool side_pending = false;
     GraphExec g_pback, g_pfwd;
+    // the discount-factor path (hank_set_discount_path; hank_shock.h): d_beta [P] always holds the beta_t in force — the model's beta
+    // in every period without a path (the graphs hold its address); beta_on: a path is set, so everything that (re)writes the record
+    // runs on the per-period launches through g_pback_b, the backward primal graph of k_shk_egm_X / k_shk_egm_step
+    DevBuf<double> d_beta;
+    bool beta_on = false;
+    std::vector<double> h_beta;
+    GraphExec g_pback_b;
     Spans spans;                   // the timed sweeps (hank_last_timings, hank_last_vjp_timings, hank_last_ss_timings)
     std::list<TanWork> tws;        // per batch width, most recently used first (a small cache: Jacobian assembly and Newton alternate widths)
     // 0 = one launch per period for everything; 1 = XCD-local persistent sweeps for everything; 2 = auto (default where
@@ -506,6 +520,25 @@ static int build_primal_graphs(hank_ctx *ctx) {
     hipLaunchKernelGGL(k_tan_out, dim3((2 * P + 255) / 256), dim3(256), 0, s, ctx->d_agg_rm, P, 2, ctx->d_agg);
     return end_capture(ctx, &ctx->g_pfwd);
 }
+// the backward primal graph at a discount-factor path (hank_shock.h): g_pback's launches with beta_t' from d_beta in the X half of
+// period t'; the forward graph is g_pfwd. Captured the first time a primal runs with a path set.
+static int ensure_shock_primal_graphs(hank_ctx *ctx) {
+    if (!ctx->g_pback) { const int rc = build_primal_graphs(ctx); if (rc) return rc; }
+    if (ctx->g_pback_b) return HANK_OK;
+    const Consts &c = ctx->c;
+    const int P = c.P;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
+    const size_t lds = primal_lds(c);
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    zero_err(ctx, s);
+    hipLaunchKernelGGL(k_shk_egm_X, grd, blk, lds, s, c, ctx->d_beta.get(), ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
+                       ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, P - 1);
+    for (int t = P - 1; t >= 0; t--)
+        hipLaunchKernelGGL(k_shk_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, ctx->d_beta.get(), t, ctx->d_err);
+    hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
+    return end_capture(ctx, &ctx->g_pback_b);
+}
 
 // Captures the four tangent graphs for lane type VT (double: one direction per lane; double2: two).
 // the row-group count is a template parameter of the kernels and a run-time choice here
@@ -541,8 +574,10 @@ static void launch_tan_reduce(hank_ctx *ctx, TanWork &w, hipStream_t s) {
 static dim3 bnd_grid(const Consts &c, int N) { return dim3((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e); }
 
 // the backward tangent sweep; bnd: with the dV_P seed (hank_boundary.h: the same launches of the same kernel, the seed kernels between them)
+// shock (hank_shock.h): the d beta_t seed of EVERY period behind the launch that produced that period's knots' tangent — P launches more, and
+// k_shk_in in front; w.shk_in, w.shk_db are allocated before this
 template <typename VT>
-static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd) {
+static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = false) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
     const int N = w.N, PN = (int)(P * N), RGB = w.RGB;
@@ -554,8 +589,14 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd) {
     VT *dpol = reinterpret_cast<VT *>(w.dpol.get());
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
+    if (shock) hipLaunchKernelGGL(k_shk_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.shk_in.get(), (int)P, N, w.shk_db.get());
+    const dim3 sgrd((unsigned)(((size_t)c.n_a * N + 255) / 256));
+    auto seed = [&](int t, double *ds_t) {      // ds_t: the knots' tangent of period t, as the launch before left it
+        hipLaunchKernelGGL(k_shk_seed_back, sgrd, dim3(256), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->d_beta.get(), t, w.shk_db.get() + (size_t)t * N, (size_t)N, ds_t);
+    };
     LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, (int)P - 1, 1,
                        ds[1], ds[0], dpol);
+    if (shock) seed((int)P - 1, w.ds[0].get());
     if (bnd) {      // dV_P (BackwardIteration.jl:85) into the knots' tangent of period P-1; ds[1] is free until the next launch writes it
         hipLaunchKernelGGL(k_bnd_in, bnd_grid(c, N), dim3(BND_T, 8), 0, s, w.bnd_dV.get(), c.n_a, c.n_e, c.n_a, N, w.ds[1].get());
         hipLaunchKernelGGL(k_bnd_seed_back, dim3((unsigned)(((size_t)c.n_a * N + 255) / 256)), dim3(256), 0, s, c, ctx->R.kc + (P - 1) * c.G, w.ds[1].get(), (size_t)N, w.ds[0].get());
@@ -564,9 +605,10 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd) {
     for (int t = (int)P - 1; t >= 0; t--) {
         LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, t, 0,
                            ds[cur], ds[cur ^ 1], dpol);
+        if (shock && t > 0) seed(t - 1, w.ds[cur ^ 1].get());
         cur ^= 1;
     }
-    return end_capture(ctx, &w.tan_back(bnd));
+    return end_capture(ctx, shock ? &w.g_tback_shk : &w.tan_back(bnd));
 }
 
 // the forward tangent sweep; bnd: with the dD_0 seed; NX > 0 (hank_jvp_het): k_tan_fwd_hx in k_tan_fwd's place and k_reduce_hx behind
@@ -743,6 +785,16 @@ static int ensure_tan_graphs(hank_ctx *ctx, TanWork &w, bool bnd, int NX) {
     if (!rc) rc = fwd(0);
     if (!rc && NX > 0) rc = fwd(NX);
     return rc;
+}
+// hank_jvp_shock's / hank_fake_news_shock's backward graph (the forward sweep is the plain one: it does not know where a seed came from)
+static int ensure_shock_tan_graph(hank_ctx *ctx, TanWork &w) {
+    const size_t PN = (size_t)ctx->c.P * w.N;
+    if (!w.shk_db) {
+        HIPC(ctx, w.shk_in.alloc(PN));
+        HIPC(ctx, w.shk_db.alloc(PN));      // (last: a failed allocation is tried again by the next call)
+    }
+    if (w.g_tback_shk) return HANK_OK;
+    return w.VB == 2 ? capture_tan_back<double2>(ctx, w, false, true) : capture_tan_back<double>(ctx, w, false, true);
 }
 static int ensure_dual_graphs(hank_ctx *ctx, TanWork &w) {
     if (w.g_fback) return HANK_OK;
@@ -1593,6 +1645,9 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     ctx->d_ss_D = R.Dseq;      // view
     ctx->nbp = (c.n_a + RBP - 1) / RBP;
     HIPC(ctx, ctx->d_xhh.alloc((size_t)c.n_hh * P));
+    HIPC(ctx, ctx->d_beta.alloc(P));
+    ctx->h_beta.assign(P, c.beta);      // no path: the model's beta in every period
+    HIPC(ctx, hipMemcpy(ctx->d_beta, ctx->h_beta.data(), sizeof(double) * P, hipMemcpyHostToDevice));
     HIPC(ctx, ctx->d_agg.alloc(2 * P));
     HIPC(ctx, ctx->d_agg_rm.alloc(2 * P));
     HIPC(ctx, ctx->d_zd.alloc(2 * P));
@@ -1717,6 +1772,37 @@ int hank_set_boundary(hank_ctx *ctx, const double *ss_end_value, const double *s
 
 // which x the record belongs to: the host-pointer entries know it (and whether it is a constant path), the device-pointer
 // entries do not
+// hank_set_discount_path (hank_shock.h; KrusellSmith.jl:59-62, BackwardIteration.jl:90-113): beta_t [P] on the host, or null for the
+// model's constant. What a new boundary invalidates goes: the record, both current batches, the memo.
+int hank_set_discount_path(hank_ctx *ctx, const double *beta_t) {
+    ENTER(ctx);
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    const size_t P = ctx->c.P;
+    if (!beta_t && !ctx->beta_on) { ctx->errmsg[0] = 0; return HANK_OK; }      // (no path to clear: nothing changes)
+    if (beta_t)
+        for (size_t t = 0; t < P; t++)
+            if (!(beta_t[t] > 0.0) || !(beta_t[t] <= 1.7976931348623157e308))
+                return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_discount_path: beta_t must be finite and positive (period %zu: %g); the path in force is unchanged", t + 1, beta_t[t]);
+    HIPC(ctx, join_side(ctx));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (sweeps in flight read d_beta)
+    if (beta_t) ctx->h_beta.assign(beta_t, beta_t + P);
+    else ctx->h_beta.assign(P, ctx->c.beta);
+    HIPC(ctx, hipMemcpyAsync(ctx->d_beta, ctx->h_beta.data(), sizeof(double) * P, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->beta_on = beta_t != nullptr;
+    record_gone(ctx);
+    ctx->memo_valid = false;
+    ctx->stationary = false;
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+// the entries that are defined at ONE beta (the scenario and steady-state entries, the Toeplitz Jacobians) while a path is set
+static int path_refuses(hank_ctx *ctx, const char *name) {
+    if (ctx && ctx->beta_on)
+        return fail(ctx, HANK_ERR_NOT_READY, "%s is defined at one discount factor: a path is set (hank_set_discount_path(ctx, NULL) clears it)", name);
+    return HANK_OK;
+}
+
 static void note_primal_x(hank_ctx *ctx, const double *xhh) {
     const size_t n = (size_t)ctx->c.n_hh * ctx->c.P, nh = ctx->c.n_hh;
     if (!xhh) { ctx->memo_valid = false; ctx->stationary = false; return; }
@@ -1728,9 +1814,10 @@ static void note_primal_x(hank_ctx *ctx, const double *xhh) {
 }
 
 static int run_primal(hank_ctx *ctx, double *d_agg_out) {
+    if (ctx->beta_on) { const int grc = ensure_shock_primal_graphs(ctx); if (grc) return grc; }      // (whatever the schedule: a path runs on the launches)
     HIPC(ctx, join_side(ctx));     // a previous forward sweep still reads the record this one overwrites
     HIPC(ctx, ctx->spans.begin(PRIMAL_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(ctx->g_pback, ctx->stream));
+    HIPC(ctx, hipGraphLaunch(ctx->beta_on ? ctx->g_pback_b : ctx->g_pback, ctx->stream));
     HIPC(ctx, ctx->spans.end(PRIMAL_BACK, ctx->stream, ctx->c.P + 2));
     // fork: the distribution sweep goes to the side stream; the main stream is free for the tangent
     // backward sweep and joins (join_side) before anything that needs D_t or the aggregates
@@ -1925,7 +2012,7 @@ static int check_rates(hank_ctx *ctx, const double *xhh) {      // the host-poin
 }
 // hank_primal[_dev]: x from the caller (kind: where it lives) and the Float64 sweeps of the context's schedule
 static int enqueue_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double *d_agg_out) {
-    if (use_x_primal(ctx)) return x_primal(ctx, xhh, kind, d_agg_out);
+    if (!ctx->beta_on && use_x_primal(ctx)) return x_primal(ctx, xhh, kind, d_agg_out);      // (a path: the launches, the schedule left as it is)
     HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * ctx->c.P, kind, ctx->stream));
     return run_primal(ctx, d_agg_out);
 }
@@ -1969,12 +2056,14 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
 
 // bnd: the graphs with the boundary's seeds (hank_jvp_boundary: w.bnd_dV and w.bnd_dD hold them); zm: whether a dD_0 seed is among them
 // NX > 0 (hank_jvp_het): the forward graph with that many extra reductions, one launch more (k_reduce_hx)
-static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd, bool zm, int NX) {
-    const int grc = ensure_tan_graphs(ctx, w, bnd, NX);
+// shock (hank_jvp_shock; never with bnd): the backward graph with the d beta_t seeds, 2 P + 3 launches
+static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd, bool zm, int NX, bool shock = false) {
+    int grc = ensure_tan_graphs(ctx, w, bnd, NX);
+    if (!grc && shock) grc = ensure_shock_tan_graph(ctx, w);
     if (grc) return grc;
     HIPC(ctx, ctx->spans.begin(TAN_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(w.tan_back(bnd), ctx->stream));
-    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, ctx->c.P + (bnd ? 4 : 2)));
+    HIPC(ctx, hipGraphLaunch(shock ? w.g_tback_shk : w.tan_back(bnd), ctx->stream));
+    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, shock ? 2 * ctx->c.P + 3 : ctx->c.P + (bnd ? 4 : 2)));
     HIPC(ctx, join_side(ctx));      // the tangent forward sweep needs D_t
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
@@ -1994,6 +2083,8 @@ struct TanReq {
     hipMemcpyKind kind;                            // where they live
     bool seeded;                                   // run the graphs with the seed kernels: hank_jvp_boundary always (null seeds too),
                                                    // hank_jvp_het when a seed is given, hank_jvp never — NOT derived from the pointers
+    const double *dbeta = nullptr;                 // hank_jvp_shock: the directions in beta_t, (P, N) column-major; null: zero
+    bool shock = false;                            // run the backward graph with the d beta_t seeds (hank_jvp_shock always, null dbeta too)
 };
 static int ensure_bnd_bufs(hank_ctx *ctx, TanWork &w);
 static int ensure_hx_record(hank_ctx *ctx);
@@ -2024,7 +2115,13 @@ static int enqueue_tan_launch(hank_ctx *ctx, const TanReq &q, int N, TanWork **o
         if (in[k].src) HIPC(ctx, hipMemcpyAsync(in[k].dst, in[k].src, sizeof(double) * in[k].count, q.kind, ctx->stream));
         else HIPC(ctx, hipMemsetAsync(in[k].dst, 0, sizeof(double) * in[k].count, ctx->stream));
     }
-    rc = run_jvp(ctx, *w, q.seeded, q.dD_init != nullptr, NX);
+    if (q.shock) {      // (the seeds' buffers before the capture; the graph is captured in run_jvp)
+        rc = ensure_shock_tan_graph(ctx, *w);
+        if (rc) return rc;
+        if (q.dbeta) HIPC(ctx, hipMemcpyAsync(w->shk_in, q.dbeta, sizeof(double) * P * N, q.kind, ctx->stream));
+        else HIPC(ctx, hipMemsetAsync(w->shk_in, 0, sizeof(double) * P * N, ctx->stream));
+    }
+    rc = run_jvp(ctx, *w, q.seeded, q.dD_init != nullptr, NX, q.shock);
     if (rc) return rc;
     *out = w;
     return HANK_OK;
@@ -2057,8 +2154,10 @@ static int tan_seed_args(hank_ctx *ctx, const char *who, bool het, const TanReq 
 // hank_jvp[_dev]: N directions from the caller (kind: where they live) through the tangent sweeps of the family that serves
 // this width at the recorded primal; batch_ran has named the family and its buffers when this returns HANK_OK
 static int enqueue_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, double *d_dagg_out) {
-    if (use_wide(ctx, N)) return w_jvp(ctx, dxhh, kind, N, d_dagg_out);
-    if (use_x_jvp(ctx, N)) return x_jvp(ctx, dxhh, kind, N, d_dagg_out);
+    // at a record written under a discount-factor path the persistent and the wide tangent sweeps would rebuild kc with the model's
+    // beta (diet_kc): the launches read it from the record
+    if (!ctx->beta_on && use_wide(ctx, N)) return w_jvp(ctx, dxhh, kind, N, d_dagg_out);
+    if (!ctx->beta_on && use_x_jvp(ctx, N)) return x_jvp(ctx, dxhh, kind, N, d_dagg_out);
     return enqueue_tan_raw(ctx, TanReq{0, dxhh, nullptr, nullptr, kind, false}, N, d_dagg_out);
 }
 
@@ -2146,6 +2245,29 @@ int hank_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_en
     return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
 }
 
+// hank_jvp_shock[_dev] (hank_shock.h): the request with the d beta_t seeds, always on the launches' graphs with the seed kernels; a null
+// input is a zero seed. Named as hank_jvp names its batch.
+static int shock_args(hank_ctx *ctx, const double *dxhh, const double *dbeta, int N, const void *out, bool need_out) {
+    if (!ctx || (!dxhh && !dbeta) || (need_out && !out) || N < 1)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_shock: bad argument (N=%d; at least one of dxhh, dbeta must be given)", N);
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_shock");
+    return HANK_OK;
+}
+int hank_jvp_shock_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dbeta, int32_t N, double *d_dagg_out) {
+    ENTER(ctx);
+    const TanReq q{0, d_dxhh, nullptr, nullptr, hipMemcpyDeviceToDevice, false, d_dbeta, true};
+    const int rc = shock_args(ctx, d_dxhh, d_dbeta, N, d_dagg_out, false);
+    return rc ? rc : enqueue_tan_raw(ctx, q, N, d_dagg_out);
+}
+int hank_jvp_shock(hank_ctx *ctx, const double *dxhh, const double *dbeta, int32_t N, double *dagg_out) {
+    ENTER(ctx);
+    const TanReq q{0, dxhh, nullptr, nullptr, hipMemcpyHostToDevice, false, dbeta, true};
+    int rc = shock_args(ctx, dxhh, dbeta, N, dagg_out, true);
+    if (!rc) rc = enqueue_tan_raw(ctx, q, N, nullptr);
+    if (rc) return rc;
+    return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
+}
+
 static int run_fused(hank_ctx *ctx, TanWork &w) {
     const int grc = ensure_dual_graphs(ctx, w);
     if (grc) return grc;
@@ -2184,7 +2306,7 @@ int hank_primal_jvp_dev(hank_ctx *ctx, const double *d_xhh, const double *d_dxhh
     ENTER(ctx);
     if (!ctx || !d_xhh || !d_dxhh || N < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument (N=%d)", N);
     if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
-    if (use_wide(ctx, N)) {           // a wide batch: the Float64 sweeps of the context's schedule, then the on-chip tangent sweeps
+    if (use_wide(ctx, N) || ctx->beta_on) {           // a wide batch: the Float64 sweeps of the context's schedule, then the on-chip tangent sweeps; a path: both on the launches
         const int rc = hank_primal_dev(ctx, d_xhh, d_agg_out);
         return rc ? rc : hank_jvp_dev(ctx, d_dxhh, N, d_dagg_out);
     }
@@ -2215,7 +2337,7 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
         }
         return HANK_OK;
     }
-    if (use_wide(ctx, N)) {
+    if (use_wide(ctx, N) || ctx->beta_on) {
         rc = hank_primal(ctx, xhh, agg_out);
         return rc ? rc : hank_jvp(ctx, dxhh, N, dagg_out);
     }
@@ -2286,11 +2408,14 @@ static int stationary_record(hank_ctx *ctx, const char *name) {
 // (outputs 0 .. n_het-1 of hank_get_het_outputs; output 0 is the same arithmetic as n_het == 0, bit for bit); groups: hank_fake_news_group
 // (the context's K group outputs: the same policy responses and impulses, the outputs served GRP_FN_CHUNK at a time so the expectation
 // workspace never holds more — steps 3 and 4 run once per chunk, once in all for the other two entries).
-static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, double *Dv_out) {
-    const char *name = groups ? "hank_fake_news_group" : n_het ? "hank_fake_news_het" : "hank_fake_news";
+// shock (hank_fake_news_shock; with n_het >= 1): ONE direction in place of the n_hh inputs' — the backward sweep seeded with
+// d beta_{P-1} = 1 (hank_shock.h) — and no direct term: F (P, P, n_het), Dv (P, n_het).
+static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, double *Dv_out, bool shock = false) {
+    const char *name = shock ? "hank_fake_news_shock" : groups ? "hank_fake_news_group" : n_het ? "hank_fake_news_het" : "hank_fake_news";
+    { const int prc = path_refuses(ctx, name); if (prc) return prc; }
     { const int nrc = stationary_record(ctx, name); if (nrc) return nrc; }
     const Consts &c = ctx->c;
-    const int P = c.P, G = c.G, N = c.n_hh, NP = P * N, S = 16, nout = groups ? ctx->grp.K : n_het ? n_het : 1;
+    const int P = c.P, G = c.G, N = shock ? 1 : c.n_hh, NP = P * N, S = 16, nout = groups ? ctx->grp.K : n_het ? n_het : 1;
     const int cap = groups ? std::min(nout, GRP_FN_CHUNK) : nout;      // outputs per pass
     hipStream_t s = ctx->stream;
     { const int src = ensure_seg(ctx); if (src) return src; }
@@ -2301,12 +2426,19 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
     if (rc) return rc;
     TanWork &w = *wp;
     rc = ensure_tan_graphs(ctx, w, false, 0);
+    if (!rc && shock) rc = ensure_shock_tan_graph(ctx, w);
     if (rc) return rc;
     rc = ensure_fn(ctx, cap);
     if (rc) return rc;
     HIPC(ctx, join_side(ctx));      // D_1 and the {w, ig D} records come from the primal's forward sweep
-    hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
-    HIPC(ctx, hipGraphLaunch(w.tan_back(false), s));
+    if (shock) {      // no input moves; d beta_{P-1} = 1 (the batch is one direction wide: (P, 1) column-major is [P])
+        static const double one = 1.0;
+        HIPC(ctx, hipMemsetAsync(w.dxhh, 0, sizeof(double) * c.n_hh * P, s));
+        HIPC(ctx, hipMemsetAsync(w.shk_in, 0, sizeof(double) * P, s));
+        HIPC(ctx, hipMemcpyAsync(w.shk_in.get() + (P - 1), &one, sizeof(double), hipMemcpyHostToDevice, s));
+    } else
+        hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
+    HIPC(ctx, hipGraphLaunch(shock ? w.g_tback_shk : w.tan_back(false), s));
     batch_none(ctx);      // (w.dpol no longer belongs to a caller's batch)
     // 2. the lottery impulse of every lag and input at once
     hipLaunchKernelGGL(k_fn_transpose, dim3((unsigned)((G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256), 0, s, w.dpol, P, G, N, ctx->fn.dpT);
@@ -2353,7 +2485,7 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
                     const int j = P - 1 - t;
                     const size_t kc = (size_t)k + (size_t)N * o, ko = (size_t)k + (size_t)N * (o0 + o);
                     const double dv = hD[(size_t)o * NP + (size_t)t * N + k];
-                    Dv_out[j + (size_t)P * ko] = ((groups || o > 0) && j == 0) ? dv + hd[kc] : dv;
+                    Dv_out[j + (size_t)P * ko] = (!shock && (groups || o > 0) && j == 0) ? dv + hd[kc] : dv;      // (beta has no direct term in any output)
                     for (int u = 0; u < P; u++) F_out[u + (size_t)P * (j + (size_t)P * ko)] = hF[((size_t)o * P + u) * NP + (size_t)t * N + k];
                 }
     }
@@ -2374,6 +2506,14 @@ int hank_fake_news_het(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_o
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     const int rc = het_count_ok(ctx, "hank_fake_news_het", n_het, false);
     return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out);
+}
+
+// (KrusellSmith.jl:59-62, BackwardIteration.jl:90-113; the recursion of SteadyStateJacobian.jl:363-371 with the input fixed to beta)
+int hank_fake_news_shock(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out) {
+    ENTER(ctx);
+    if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
+    const int rc = het_count_ok(ctx, "hank_fake_news_shock", n_het, false);
+    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, true);
 }
 
 #ifdef HANK_XSTAMP
@@ -2619,27 +2759,40 @@ static int capture_cot_graph_ag(hank_ctx *ctx, CotWork &w) {
 
 // the two graphs of a width, captured the first time hank_vjp runs at it: Sweep A (NX = 0) and Sweep B (P launches,
 // t = 0 .. P-1, then the fixed-order reduction of the inputs' cotangents)
+// shock (hank_vjp_shock; hank_shock.h): Sweep B with beta_bar_t's partials behind every period's launch, while that period's mu_t is in
+// the state the launch read — the same launches of k_adj_egm and k_adj_out, P + 2 more: w.g_BS
+static int shk_mc(int M) { int mc = 1; while (mc < M && mc < 64) mc <<= 1; return mc; }      // cotangent columns across k_shk_bbar's lanes
 template <typename VT>
-static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
+static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, bool shock) {
     const Consts &c = ctx->c;
-    const int P = c.P;
+    const int P = c.P, M = w.N, MC = shk_mc(M);
     hipStream_t s = ctx->own_stream;
     const dim3 blk(64 * c.n_e), grd((unsigned)w.g.nb, (unsigned)((w.g.MV + w.g.NC - 1) / w.g.NC));
     const size_t ldsB = adj_lds_egm(c, w.g, w.V);
     VT *st[2] = {reinterpret_cast<VT *>(w.st[0].get()), reinterpret_cast<VT *>(w.st[1].get())};
     VT *pbar = reinterpret_cast<VT *>(w.pbar.get());
-    int rc = capture_cot_graph_a<VT, 0>(ctx, w, AdjHx<VT, 0>{}, &w.g_A);
-    if (rc) return rc;
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     int cur = 0;
     for (int t = 0; t < P; t++) {
         hipLaunchKernelGGL((k_adj_egm<VT>), grd, blk, ldsB, s, c, ctx->R, w.g, t, t == 0 ? 1 : 0, t == P - 1 ? 1 : 0, ctx->d_adj_sb, st[cur], st[cur ^ 1], pbar,
                            reinterpret_cast<VT *>(w.partS.get()), reinterpret_cast<VT *>(w.partM.get()));
+        if (shock)
+            hipLaunchKernelGGL(k_shk_bbar, dim3((unsigned)w.g.nb, (unsigned)((M + MC - 1) / MC)), dim3(SHK_BT), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->d_beta.get(), w.g.R, MC, t,
+                               t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, w.bb_part.get() + (size_t)t * w.g.nb * M);
         cur ^= 1;
     }
     hipLaunchKernelGGL(k_adj_out, dim3((unsigned)((P * w.N + 255) / 256)), dim3(256), 0, s, P, c.n_hh, w.N, w.g.nb, ctx->d_xhh, w.partS, w.partM, w.yb1,
                        ctx->d_agg + P, ctx->d_zd, w.xbar);
-    return end_capture(ctx, &w.g_B);
+    if (shock) {
+        hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (unsigned)((M + 63) / 64)), dim3(256), 0, s, w.bb_part.get(), w.g.nb, M, w.bb_rm.get());
+        hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w.bb_rm.get(), P, M, w.bb_cm.get());
+    }
+    return end_capture(ctx, shock ? &w.g_BS : &w.g_B);
+}
+template <typename VT>
+static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
+    const int rc = capture_cot_graph_a<VT, 0>(ctx, w, AdjHx<VT, 0>{}, &w.g_A);
+    return rc ? rc : capture_cot_graph_b<VT>(ctx, w, false);
 }
 
 // Sweep B's segment starts belong to the record (like seg_valid): built before the first hank_vjp at a record, by whichever family wrote it
@@ -2679,8 +2832,9 @@ static int ensure_hx_record(hank_ctx *ctx) {
 // value and of the initial distribution, exported from the sweeps' states (hank_boundary.h) — everything else is the same work.
 // grp_bar (hank_vjp_group; (P, K, M) column-major, where `kind` says): cotangents on the context's group outputs — Sweep A's graph
 // with the groups, and their direct terms after Sweep B; agg_bar may then be null (n_het = 0: no cotangent on outputs 0 and 1).
+// d_beta_bar (hank_vjp_shock; a device pointer, (P, M) column-major): the cotangent of the discount-factor path, reduced in Sweep B.
 static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out,
-                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr, const double *grp_bar = nullptr) {
+                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr, const double *grp_bar = nullptr, double *d_beta_bar = nullptr, bool shock = false) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
     const int NX = n_het > 2 ? n_het - 2 : 0, K = grp_bar ? ctx->grp.K : 0;
@@ -2698,6 +2852,15 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     if (!w->g_A) {
         if (!ctx->d_adj_sb) HIPC(ctx, ctx->d_adj_sb.alloc(P * c.n_e * ((size_t)c.n_a + 1)));      // (the graphs hold its address)
         rc = w->V == 2 ? capture_cot_graphs<double2>(ctx, *w) : capture_cot_graphs<double>(ctx, *w);
+        if (rc) return rc;
+    }
+    if (shock && !w->g_BS) {
+        if (!w->bb_cm) {
+            HIPC(ctx, w->bb_part.alloc(P * (size_t)w->g.nb * M));
+            HIPC(ctx, w->bb_rm.alloc(P * M));
+            HIPC(ctx, w->bb_cm.alloc(P * M));      // (last: a failed allocation is tried again by the next call)
+        }
+        rc = w->V == 2 ? capture_cot_graph_b<double2>(ctx, *w, true) : capture_cot_graph_b<double>(ctx, *w, true);
         if (rc) return rc;
     }
     hipStream_t s = ctx->stream;
@@ -2736,14 +2899,15 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((M + BND_T - 1) / BND_T), (unsigned)c.n_e);      // the layout kernel
     // Sweep A's state after its last launch (t = 0) is the cotangent of D_0; Sweep B's first launches overwrite it
     if (d_D0_bar) hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_D0_bar);
-    HIPC(ctx, hipGraphLaunch(w->g_B, s));
+    HIPC(ctx, hipGraphLaunch(shock ? w->g_BS : w->g_B, s));
     if (d_vend_bar) {      // Sweep B's last launch (t = P-1) read mu_{P-1} from st[(P-1) & 1] and wrote no state: mu_P goes where it would have
         hipLaunchKernelGGL(k_bnd_vend, dim3((unsigned)(((size_t)c.n_a * M + 255) / 256)), dim3(256), 0, s, c, ctx->R, (int)P - 1, P == 1 ? 1 : 0, ctx->d_adj_sb.get(),
                            w->st[(P - 1) & 1].get(), w->pbar.get(), (size_t)M, w->st[P & 1].get());
         hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_vend_bar);
     }
     HIPC(ctx, hipGetLastError());
-    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1 + (d_D0_bar ? 1 : 0) + (d_vend_bar ? 2 : 0)));
+    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1 + (d_D0_bar ? 1 : 0) + (d_vend_bar ? 2 : 0) + (shock ? (int)P + 2 : 0)));
+    if (d_beta_bar) HIPC(ctx, hipMemcpyAsync(d_beta_bar, w->bb_cm, sizeof(double) * P * M, hipMemcpyDeviceToDevice, s));
     if (NX > 0) {
         hipLaunchKernelGGL(k_adj_hx_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, NX, hx_count(ctx), w->ybx.get(),
                            ctx->hx.S.get(), w->xbar.get());
@@ -2822,7 +2986,27 @@ static int vjp(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, co
     return vjp_boundary(ctx, args, n_het, agg_bar, M, xhh_bar, nullptr, nullptr, dev);
 }
 
+// hank_vjp_shock[_dev]: hank_vjp_het's rule and work, Sweep B from the graph with beta_bar's reduction
+static int vjp_shock(hank_ctx *ctx, int n_het, const double *agg_bar, int M, double *xhh_bar, double *beta_bar, bool dev) {
+    ENTER(ctx);
+    if (ctx && !beta_bar) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_shock: beta_bar is required");
+    int rc = vjp_het_args(ctx, n_het, agg_bar, M, xhh_bar);
+    if (rc) return rc;
+    CotWork *w = nullptr;
+    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, nullptr, nullptr, nullptr, beta_bar, true);
+    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, nullptr, nullptr, nullptr, nullptr, true);
+    if (rc) return rc;
+    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(beta_bar, w->bb_cm, sizeof(double) * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
 extern "C" {
+// (KrusellSmith.jl:59-62: where beta enters; BackwardIteration.jl:90-113: the loop the transposed sweep reverses)
+int hank_vjp_shock(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *beta_bar) { return vjp_shock(ctx, n_het, agg_bar, M, xhh_bar, beta_bar, false); }
+int hank_vjp_shock_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_beta_bar) { return vjp_shock(ctx, n_het, d_agg_bar, M, d_xhh_bar, d_beta_bar, true); }
 int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar) {
     return vjp_boundary(ctx, vjp_args, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);
 }
@@ -3312,6 +3496,7 @@ extern "C" int hank_vfi(hank_ctx *ctx, const double *xhh_t, double tol, int32_t 
     if (!ctx || !xhh_t || !value_io || !policy_out || max_iter < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument");
     if (!(1.0 + xhh_t[0] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "1 + r must be positive");
     ENTER(ctx);
+    { const int prc = path_refuses(ctx, "hank_vfi"); if (prc) return prc; }
     { const int pend = device_verdict(ctx, THE_RECORD); if (pend) return pend; }      // (what an earlier async sweep left pending)
     const Consts &c = ctx->c;
     const size_t G = c.G;
@@ -3609,6 +3794,7 @@ static int primal_batch(hank_ctx *ctx, int n_het, const double *xhh, int K, doub
     if (!xhh || !agg_out) return fail(ctx, HANK_ERR_BAD_ARG, "hank_primal_batch: null pointer");
     if (K < 1 || K > SCEN_KMAX) return fail(ctx, HANK_ERR_BAD_ARG, "hank_primal_batch: K must be 1..%d, got %d", SCEN_KMAX, K);
     int rc = het_count_ok(ctx, "hank_primal_batch", n_het, true);
+    if (!rc) rc = path_refuses(ctx, "hank_primal_batch");
     if (rc) return rc;
     if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
     const Consts &c = ctx->c;
@@ -3693,6 +3879,7 @@ int hank_ss_batch(hank_ctx *ctx, int32_t n_het, const double *xhh, int32_t K, do
     if (K < 1 || K > SCEN_KMAX) return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_batch: K must be 1..%d, got %d", SCEN_KMAX, K);
     if (vfi_max_iter < 1 || dist_max_iter < 1 || check_every < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_ss_batch: vfi_max_iter, dist_max_iter and check_every must be >= 1");
     if (agg_out) { const int hrc = het_count_ok(ctx, "hank_ss_batch", n_het, true); if (hrc) return hrc; }
+    { const int prc = path_refuses(ctx, "hank_ss_batch"); if (prc) return prc; }
     const Consts &c = ctx->c;
     for (int k = 0; k < K; k++)
         if (!(1.0 + xhh[(size_t)c.n_hh * k] > 0.0)) return fail(ctx, HANK_ERR_DOMAIN, "hank_ss_batch: 1 + r must be positive (scenario %d of %d)", k, K);
@@ -3838,6 +4025,7 @@ static int ss_loop(hank_ctx *ctx, SsCtl *d_ctl, int max_iter, Step step, SsCtl *
 // rule), then the stationary record
 static int ss_ready(hank_ctx *ctx, const char *name, int n_het, bool rest_ok) {
     int rc = het_count_ok(ctx, name, n_het, true, rest_ok);
+    if (!rc) rc = path_refuses(ctx, name);
     if (rc) return rc;
     rc = stationary_record(ctx, name);
     if (rc) return rc;

@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "hank_get_lottery_record", "hank_get_forward_units",
     "hank_set_group_outputs", "hank_get_group_outputs", "hank_get_group_outputs_dev", "hank_fake_news_group",
     "hank_vjp_group", "hank_vjp_group_dev",
+    "hank_set_discount_path", "hank_jvp_shock", "hank_jvp_shock_dev", "hank_vjp_shock", "hank_vjp_shock_dev", "hank_fake_news_shock",
 )
 
 
@@ -165,6 +166,12 @@ def load_library() -> C.CDLL:
     lib.hank_fake_news_group.argtypes = [vp, dp, dp]
     lib.hank_vjp_group.argtypes = [vp, i32, dp, dp, i32, dp, dp, dp]
     lib.hank_vjp_group_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
+    lib.hank_set_discount_path.argtypes = [vp, dp]
+    lib.hank_jvp_shock.argtypes = [vp, dp, dp, i32, dp]
+    lib.hank_jvp_shock_dev.argtypes = [vp, vp, vp, i32, vp]
+    lib.hank_vjp_shock.argtypes = [vp, i32, dp, i32, dp, dp]
+    lib.hank_vjp_shock_dev.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.hank_fake_news_shock.argtypes = [vp, i32, dp, dp]
     for name in ABI_SYMBOLS:
         if name in ("hank_get_lottery_record", "hank_get_forward_units") and not hasattr(lib, name):
             continue
@@ -234,6 +241,7 @@ class HouseholdBlock:
         self.T, self.P, self.G = int(T), int(T) - 1, self.n_a * self.n_e
         self._params = (float(beta), float(gamma), float(borrow_cons), value_fn_id)
         self._boundary = None
+        self.discount_path = None      # the beta_t path in force (set_discount_path), or None: the model's constant beta
         m = hank_model(self.n_a, self.n_e, self.T, value_fn_id, _p(self.a_grid), _p(self.z_grid),
                        _p(self.Pi), float(beta), float(gamma), float(borrow_cons))
         if device is None:
@@ -267,6 +275,8 @@ class HouseholdBlock:
         other = HouseholdBlock(self.a_grid, self.z_grid, self.Pi, beta, gamma, bc, self.T, vf, device=self.device if device is None else device)
         if self._boundary is not None:
             other.set_boundary(*self._boundary)
+        if self.discount_path is not None:
+            other.set_discount_path(self.discount_path)
         return other
 
     def close(self):
@@ -295,6 +305,75 @@ class HouseholdBlock:
         d = _f(np.asarray(ss_init_D, dtype=np.float64).reshape((self.n_a, self.n_e), order="F"))
         self._chk(self._lib.hank_set_boundary(self._ctx, _p(v), _p(d)))
         self._boundary = (v, d)
+
+    # -- the discount-factor path -------------------------------------------------------------
+    def set_discount_path(self, beta_t):
+        """a path beta_t (P,) of the discount factor (hank_set_discount_path): beta_t is the factor in period t's Euler equation,
+        u'(c_t) = beta_t E_t[V_{t+1}], so beta_{P-1} multiplies the expectation of the terminal value. None returns to the
+        model's constant. Like a new boundary it drops the record: the next tangent sweep needs a primal first. While a path is
+        set every sweep runs on the per-period launches; the scenario, steady-state and `fake_news*` entries are refused."""
+        if beta_t is None:
+            self._chk(self._lib.hank_set_discount_path(self._ctx, None))
+            self.discount_path = None
+            return
+        b = np.ascontiguousarray(beta_t, dtype=np.float64)
+        if b.shape != (self.P,):
+            raise ValueError(f"beta_t must be ({self.P},), got {b.shape}")
+        self._chk(self._lib.hank_set_discount_path(self._ctx, _p(b)))
+        self.discount_path = b.copy()
+
+    def jvp_shock(self, dxhh=None, dbeta=None) -> np.ndarray:
+        """the tangent sweeps with seeds in the discount-factor path as well (hank_jvp_shock): dxhh (n_hh, P, N) as in `jvp`,
+        dbeta (P,) or (P, N); None means zeros, at least one must be given. -> dagg (P, N). Works with or without a path set;
+        always the launch family. The batch is current afterwards as `jvp`'s is: `dpolicy_seq`, `grid_aggregates`,
+        `het_outputs(n_het, dxhh)` and `group_outputs(dxhh)` serve it — beta has no direct term in any output, so pass the same
+        dxhh (zeros for None)."""
+        if dxhh is None and dbeta is None:
+            raise ValueError("at least one of dxhh, dbeta must be given")
+        dx = db = None
+        if dxhh is not None:
+            dx = np.asarray(dxhh, dtype=np.float64)
+            dx = dx[:, :, None] if dx.ndim == 2 else dx
+            N = dx.shape[2]
+        if dbeta is not None:
+            db = np.asarray(dbeta, dtype=np.float64)
+            db = db[:, None] if db.ndim == 1 else db
+            N = db.shape[1] if dx is None else N
+            db = _f(db, (self.P, N))
+        if dx is not None:
+            dx = _f(dx, (self.n_hh, self.P, N))
+        out = np.empty((self.P, N), order="F")
+        self.calls["jvp"] += 1
+        self._chk(self._lib.hank_jvp_shock(self._ctx, _opt(dx), _opt(db), N, _p(out)))
+        return out
+
+    def jvp_shock_dev(self, d_dxhh_ptr: int, d_dbeta_ptr: int, N: int, d_dagg_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
+        self._chk(self._lib.hank_jvp_shock_dev(self._ctx, C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dbeta_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+
+    def vjp_shock(self, agg_bar, n_het: int):
+        """`vjp_het` with the cotangent of the discount-factor path (hank_vjp_shock): agg_bar (P, n_het, M) -> (xhh_bar
+        (n_hh, P, M), beta_bar (P, M)); the exact transpose of `jvp_shock` followed by `het_outputs(n_het)`. xhh_bar equals
+        `vjp_het`'s bit for bit; beta_bar is a fixed-order reduction (the same inputs give the same bits)."""
+        M, yb = self._cotangents(agg_bar, n_het, het=True)
+        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
+        bb = np.empty((self.P, max(M, 1)), order="F")
+        self._chk(self._lib.hank_vjp_shock(self._ctx, int(n_het), _p(yb), M, _p(out), _p(bb)))
+        return out, bb
+
+    def vjp_shock_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_beta_bar_ptr: int):
+        """device-pointer form (asynchronous on the context's stream)."""
+        self._chk(self._lib.hank_vjp_shock_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr), C.c_void_p(d_beta_bar_ptr)))
+
+    def fake_news_shock(self, n_het: int):
+        """the Toeplitz form of every output's Jacobian with respect to the discount-factor path at the steady state
+        (hank_fake_news_shock): -> (F (P, P, n_het), Dv (P, n_het)), the definitions of `fake_news_het` with the input fixed to
+        beta. `SteadyStateJacobian.shock_jacobian` does the recursion. Same precondition as `fake_news`; no path may be set."""
+        nh = max(int(n_het), 1)
+        F = np.empty((self.P, self.P, nh), order="F")
+        Dv = np.empty((self.P, nh), order="F")
+        self._chk(self._lib.hank_fake_news_shock(self._ctx, int(n_het), _p(F), _p(Dv)))
+        return F, Dv
 
     def primal(self, xhh) -> np.ndarray:
         x = _f(xhh, (self.n_hh, self.P))

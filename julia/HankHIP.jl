@@ -551,3 +551,49 @@ function ForwardIteration_pullback(seqs::DevicePolicySeqs, model::SequenceModel,
     end
     return agg, pullback
 end
+
+# ---- a path of the discount factor (hank_set_discount_path, hank_jvp_shock, hank_vjp_shock, hank_fake_news_shock) ----------------
+# beta_t is the factor in period t's Euler equation, u'(c_t) = beta_t E_t[V_{t+1}] (KrusellSmith.jl:59-62 inside the loop of
+# BackwardIteration.jl:90-113), t = 1 .. P; beta_P multiplies the expectation of the terminal value. The reference has no path: it
+# reads beta from model.params. `nothing` returns the context to that constant. Like a new boundary, a new path drops the record.
+function hank_set_discount_path(ctx::HankCtx, beta_t::Union{Nothing,AbstractVector{<:Real}})
+    if beta_t === nothing
+        _check(ctx.ptr, ccall((:hank_set_discount_path, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}), ctx.ptr, C_NULL))
+    else
+        length(beta_t) == ctx.P || error("beta_t must have P = $(ctx.P) entries")
+        b = Vector{Float64}(beta_t)
+        _check(ctx.ptr, ccall((:hank_set_discount_path, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}), ctx.ptr, b))
+    end
+    return ctx
+end
+
+# dagg (P, N) under directions dxhh (n_hh, P, N) in the household inputs and dbeta (P, N) in the path, either `nothing` (zeros), at
+# the recorded primal; the batch is current afterwards as hank_jvp's is (beta has no direct term in any output: pass the same dxhh,
+# or zeros, to hank_get_het_outputs / hank_get_group_outputs)
+function hank_jvp_shock(ctx::HankCtx, dxhh::Union{Nothing,Array{Float64,3}}, dbeta::Union{Nothing,Matrix{Float64}})
+    (dxhh === nothing && dbeta === nothing) && error("at least one of dxhh, dbeta must be given")
+    N = dxhh === nothing ? size(dbeta, 2) : size(dxhh, 3)
+    dagg = Matrix{Float64}(undef, ctx.P, N)
+    _check(ctx.ptr, ccall((:hank_jvp_shock, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}),
+                          ctx.ptr, dxhh === nothing ? C_NULL : dxhh, dbeta === nothing ? C_NULL : dbeta, Int32(N), dagg))
+    return dagg
+end
+
+# hank_vjp_het! with the cotangent of the path: agg_bar (P, n_het, M) -> (xhh_bar (n_hh, P, M), beta_bar (P, M)); the exact
+# transpose of hank_jvp_shock followed by hank_get_het_outputs
+function hank_vjp_shock!(xhh_bar::Array{Float64,3}, beta_bar::Matrix{Float64}, ctx::HankCtx, agg_bar::Array{Float64,3})
+    P, n_het, M = size(agg_bar)
+    @assert P == ctx.P && size(xhh_bar) == (length(ctx.hh_rows), P, M) && size(beta_bar) == (P, M)
+    _check(ctx.ptr, ccall((:hank_vjp_shock, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                          ctx.ptr, Int32(n_het), agg_bar, Int32(M), xhh_bar, beta_bar))
+    return xhh_bar, beta_bar
+end
+
+# J[t, s, o] = d Y^o_t / d beta_s for the first n_het outputs at the stationary primal the context holds (household_jacobian_toeplitz's
+# precondition, and no path set), from the recursion of SteadyStateJacobian.jl:363-371 with the input fixed to beta
+function shock_jacobian_toeplitz(ctx::HankCtx, n_het::Integer)
+    P = ctx.P
+    F = Array{Float64}(undef, P, P, n_het); Dv = Matrix{Float64}(undef, P, n_het)
+    _check(ctx.ptr, ccall((:hank_fake_news_shock, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), ctx.ptr, Int32(n_het), F, Dv))
+    return _toeplitz_recursion(F, Dv)
+end

@@ -1,0 +1,78 @@
+"""CPU tests of the discount-factor path's references and host layers (no GPU):
+1. tests/shock_refs.oracle_shock_sweeps — the oracle loop with beta = beta_t and the value's partials augmented by V dbeta_t / beta_t —
+   against a central difference of ITS OWN level in the entries beta_0 and beta_{P-1} (step 1e-6, agreement 1e-6 relative): the
+   construction the GPU tests compare with is pinned without a device;
+2. SteadyStateJacobian.shock_jacobian's recursion on a stand-in block;
+3. examples/solve_hank.py's arguments."""
+import numpy as np
+import pytest
+
+import shock_refs as R
+from cases import close
+
+STEP = 1e-6
+
+
+@pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 4), ("hank", "gamma1.5", 33, 2, 4), ("ks", "gamma1", 33, 2, 2),
+                                                  ("hank", "gamma3", 130, 3, 12)])
+def test_the_reference_s_beta_tangent_is_the_derivative_of_its_own_level(oracle_mod, family, name, n_a, n_e, T):
+    c = R.shock_case(family, name, n_a, n_e, T)
+    P, nh = T - 1, c["n_het"]
+    entries = sorted({0, P - 1})
+    dbeta = np.zeros((P, len(entries)))
+    for k, t in enumerate(entries):
+        dbeta[t, k] = 1.0
+    ref = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], nh, dbeta=dbeta)
+    assert c["orc"].m.beta == c["beta"]                          # the oracle's own beta is restored
+    for k, t in enumerate(entries):
+        lv = []
+        for sgn in (1.0, -1.0):
+            b = c["path"].copy()
+            b[t] += sgn * STEP
+            lv.append(R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], b, c["gamma"], nh))
+        what = f"{family} {name} {n_a}x{n_e} T={T} beta_{t}"
+        fd_agg = (lv[0]["agg"] - lv[1]["agg"]) / (2 * STEP)
+        fd_pol = (lv[0]["pol"] - lv[1]["pol"]) / (2 * STEP)
+        assert np.abs(fd_agg).max() > 1e-3, what
+        for o in range(nh):
+            close(ref["dagg"][:, o, k], fd_agg[:, o], rel=1e-6, ab=0.0, what=f"{what} output {o}")
+        close(ref["dpol"][..., k], fd_pol, rel=1e-6, ab=0.0, what=f"{what} policy")
+        # beta_t moves no policy after t
+        assert not np.any(ref["dpol"][t + 1:, ..., k])
+
+
+def test_a_constant_path_is_the_oracle_s_own_block(oracle_mod):
+    c = R.shock_case("ks", "gamma2", 33, 2, 4)
+    ref = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], np.full(3, c["beta"]), c["gamma"], 3)
+    agg, _, pol, _ = c["orc"].block(c["x"], None, c["V"], c["D"])
+    close(ref["agg"][:, 0], agg, what="constant path: aggregate")
+    close(ref["pol"], pol, what="constant path: policy")
+
+
+def test_shock_jacobian_is_the_toeplitz_recursion_per_output(hank):
+    from hank_amd.SteadyStateJacobian import household_jacobian, shock_jacobian
+    rng = np.random.default_rng(4)
+    P, nh = 6, 3
+    F, Dv = rng.standard_normal((P, P, nh)), rng.standard_normal((P, nh))
+    stub = R.StubShockBlock(F, Dv)
+    J = shock_jacobian(stub, nh)
+    assert J.shape == (nh, P, P) and stub.calls == 1
+    for o in range(nh):
+        want = np.empty((P, P))
+        for t in range(P):
+            for s in range(P):
+                want[t, s] = F[t, s, o] + (want[t - 1, s - 1] if t > 0 and s > 0 else (Dv[s, o] if t == 0 else 0.0))
+        assert np.allclose(J[o], want, rtol=0, atol=1e-14)
+        assert np.array_equal(J[o], household_jacobian(F[..., o:o + 1], Dv[..., o:o + 1])[0])
+    assert shock_jacobian(stub, 2).shape == (2, P, P)
+
+
+def test_the_example_parses_the_discount_shock():
+    from examples.solve_hank import parse_args
+    a = parse_args(["--discount-shock", "0.002", "0.8"])
+    assert a.discount_shock == [0.002, 0.8] and not a.gradient
+    a = parse_args(["--discount-shock", "0.002", "0.8", "--gradient", "--n-a", "130", "--n-e", "3", "--T", "40"])
+    assert a.discount_shock == [0.002, 0.8] and a.gradient and (a.n_a, a.n_e, a.T) == (130, 3, 40)
+    assert parse_args([]).discount_shock is None
+    with pytest.raises(SystemExit):
+        parse_args(["--discount-shock", "0.002"])
