@@ -1,5 +1,5 @@
 """The references of the discount-factor path (hank_set_discount_path, hank_jvp_shock, hank_vjp_shock, hank_fake_news_shock), shared by
-tests/test_shock_host.py (CPU) and tests/test_gpu_shock.py.
+tests/test_shock_host.py (CPU), tests/test_gpu_shock.py and tests/test_gpu_shock_geometry.py.
 
 1. `oracle_shock_sweeps`: the loop of `sweep_refs.oracle_sweeps` with two changes per period, t descending — the oracle's model
    gets beta = beta_t before `Oracle.value_function`, and the function is handed a copy of the incoming dual value whose partials
@@ -9,7 +9,10 @@ tests/test_shock_host.py (CPU) and tests/test_gpu_shock.py.
 2. `shock_case`: the economies — the exact inputs of cases.entry_backward (both families, every gamma of cases.ENTRY_CASES, the grids
    of cases.ENTRY_GRIDS and ENTRY_WIDE) at a horizon T, with a smooth path of the household inputs and a beta path that swings 3 %.
 3. `StubShockBlock`: stands in for the device context under `SteadyStateJacobian.shock_jacobian` (the pattern of
-   sweep_refs._StubBlock)."""
+   sweep_refs._StubBlock).
+4. `oracle_shock_jacobians` (and `oracle_shock_grid_jacobians`, `shock_linear`, `shock_beta_bar`): the dense pair (Jx, Jb) from the
+   oracle's unit tangents — one reference for every width of tests/test_gpu_shock_geometry.py, whose economies `geometry_case` puts in
+   one form and whose raw grids' edges under a path `check_path_edges` asserts (tests/test_shock_host.py: on the oracle's policy)."""
 import numpy as np
 
 import cases
@@ -105,6 +108,101 @@ def oracle_shock_sweeps(orc, x, V, D, beta_t, gamma=None, n_het=2, y=None, dbeta
     res = {k: np.concatenate(v, axis=-1) for k, v in out.items()}
     res.update(agg=agg, agg2=agg2, grp=grp, pol=np.stack([p[..., 0] for p in pol]), D=Dd[..., 0])
     return res
+
+
+_JAC = {}
+
+
+def _unit_sweeps(orc, x, V, D, beta_t, gamma, n_het):
+    """`oracle_shock_sweeps` with cases.unit_tangents as y, and with dbeta = I, once per session and key (the oracle and the bits of
+    every input); every output's block of either must exceed 1e-3"""
+    x, V, D, beta_t = (np.ascontiguousarray(v, dtype=np.float64) for v in (x, V, D, beta_t))
+    key = (id(orc), x.tobytes(), V.tobytes(), D.tobytes(), beta_t.tobytes(), gamma, n_het)
+    if key not in _JAC:
+        n_hh, P = x.shape
+        sx = oracle_shock_sweeps(orc, x, V, D, beta_t, gamma, n_het, y=cases.unit_tangents(n_hh, P))
+        sb = oracle_shock_sweeps(orc, x, V, D, beta_t, gamma, n_het, dbeta=np.eye(P))
+        for o in range(n_het):
+            assert np.abs(sx["dagg"][:, o, :]).max() > 1e-3 and np.abs(sb["dagg"][:, o, :]).max() > 1e-3, (o, n_het, x.shape, V.shape)
+        _JAC[key] = (sx, sb)
+    return _JAC[key]
+
+
+def oracle_shock_jacobians(orc, x, V, D, beta_t, gamma, n_het):
+    """the dense Jacobians of every heterogeneous output at the path beta_t, from the oracle's unit tangents: -> (Jx (n_het, P, n_hh, P),
+    d output o at t / d input k at s — the layout cases.jt takes — and Jb (P, n_het, P), d output o at t / d beta_s as [t, o, s]).
+    The tangent map is linear, so the pair is the reference of every width:
+        dagg = Jx y + Jb dbeta (`shock_linear`), xhh_bar = cases.jt(Jx[:n_het], yb), beta_bar[s, m] = sum_{t,o} Jb[t, o, s] yb[t, o, m]
+    (`shock_beta_bar`). Cached per session (`_unit_sweeps`)."""
+    sx, sb = _unit_sweeps(orc, x, V, D, beta_t, gamma, n_het)
+    n_hh, P = np.asarray(x).shape
+    return np.ascontiguousarray(sx["dagg"].reshape(P, n_het, P, n_hh).transpose(1, 0, 3, 2)), sb["dagg"]
+
+
+def oracle_shock_grid_jacobians(orc, x, V, D, beta_t, gamma, n_het):
+    """the same pair for the grid-weighted aggregate of hank_get_grid_aggregates, from the same two sweeps:
+    -> (J2x (P, n_hh, P) as [t, k, s], J2b (P, P) as [t, s])"""
+    sx, sb = _unit_sweeps(orc, x, V, D, beta_t, gamma, n_het)
+    n_hh, P = np.asarray(x).shape
+    return np.ascontiguousarray(sx["dagg2"].reshape(P, P, n_hh).transpose(0, 2, 1)), sb["dagg2"]
+
+
+def shock_linear(J, y, dbeta):
+    """dagg (P, n_het, N) = Jx y + Jb dbeta of J = `oracle_shock_jacobians`' pair; y (n_hh, P, N) or None, dbeta (P, N) or None"""
+    Jx, Jb = J
+    N = next(v.shape[-1] for v in (y, dbeta) if v is not None)
+    out = np.zeros((Jb.shape[0], Jb.shape[1], N))
+    if y is not None:
+        out += np.einsum("otks,ksn->ton", Jx, y)
+    if dbeta is not None:
+        out += np.einsum("tos,sn->ton", Jb, dbeta)
+    return out
+
+
+def shock_beta_bar(Jb, yb):
+    """beta_bar (P, M): [s, m] = sum_{t,o} Jb[t, o, s] yb[t, o, m] over the outputs yb (P, n_het, M) holds"""
+    return np.einsum("tos,tom->sm", Jb[:, :yb.shape[1], :], yb)
+
+
+_GEOM = {}
+
+
+def geometry_case(kind, *key):
+    """the economies of tests/test_gpu_shock_geometry.py in one form: ("shape", n_a, n_e, T): cases.shape (n_e = 1: shape_one_column);
+    ("raw", name): cases.raw_economy. Krusell-Smith at gamma = 2 throughout: three outputs.
+    -> dict(args: HouseholdBlock's, V, D, x (2, P), orc, beta, gamma, n_het = 3, path: beta_path(beta, P), grid), cached"""
+    if (kind,) + key not in _GEOM:
+        if kind == "raw":
+            ec = cases.raw_economy(*key)
+            args, V, D, x, orc = ec["args"], ec["V"], ec["D"], ec["x"], ec["orc"]
+        else:
+            n_a, n_e, T = key
+            m, V, D, x, orc = cases.shape_one_column(n_a, T) if n_e == 1 else cases.shape(n_a, n_e, T)
+            args = m if isinstance(m, tuple) else cases.model_args(m)
+        beta, gamma = float(args[3]), float(args[4])
+        assert gamma == 2.0 and x.shape == (2, args[6] - 1)
+        _GEOM[(kind,) + key] = dict(args=args, V=V, D=D, x=x, orc=orc, beta=beta, gamma=gamma, n_het=3, path=beta_path(beta, x.shape[1]),
+                                    grid=np.asarray(args[0]))
+    return _GEOM[(kind,) + key]
+
+
+EDGE_ECONOMIES = tuple(cases.EDGE_GRIDS) + ("deep-prefix", "swing")
+
+
+def check_path_edges(name, grid, pol):
+    """a policy sequence pol (P, n_a, n_e) recorded under beta_path(beta, 9) still holds the edges of its raw-grid economy:
+    cases.check_edges for the grids of cases.EDGE_GRIDS; cases.forward_edges' figures for "deep-prefix" (a clamped prefix of 200 rows
+    or more, past row 128) and "swing" (every column clamped in period 1, none in period 2, 100 sources or more on one target row)"""
+    if name in cases.EDGE_GRIDS:
+        return cases.check_edges(name, grid, pol)
+    f = cases.forward_edges(grid, pol)
+    print(f"{name} ({grid.size} rows): clo per column {f['clo'].T.tolist()}, most sources on one target per period {f['sources'].max(axis=1).tolist()}, "
+          f"all clamped {f['all_clamped'].astype(int).tolist()}, reopened {f['reopened'].astype(int).tolist()}")
+    if name == "deep-prefix":
+        assert f["past128"].any() and f["clo"].max() >= 200, (name, f["clo"].max())
+    else:
+        assert name == "swing" and f["all_clamped"][1] and f["reopened"][2] and f["sources"].max() >= 100, (name, f["sources"].max())
+    return f
 
 
 def shock_seeds(c, N, seed, t_only=None):

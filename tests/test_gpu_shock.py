@@ -7,7 +7,8 @@ of cases.ENTRY_CASES (gamma = 1 and 2 with the record diet on, where the persist
 beta; general gammas and the diet switched off), horizons T = 2, 3, 4 and 12 (P = 1 makes beta_0 and beta_{P-1} the same entry, P = 2
 separates them), widths 1, 3 and 33, and N = 96 once at cases.ENTRY_WIDE. Tolerance: cases.close (rel 1e-10 + abs 1e-12) against the
 oracle; bits where the header promises bits; the transposed identity under the projection bound of tests/test_gpu_vjp_variants.py
-(1e-10 of the summed magnitudes); hank_fake_news_shock under cases.close, as tests/test_gpu_fake_news_dense.py."""
+(1e-10 of the summed magnitudes); hank_fake_news_shock under cases.close, as tests/test_gpu_fake_news_dense.py. Every other width, n_e,
+the raw grids with deep clamps and the oracle's own beta_bar are in tests/test_gpu_shock_geometry.py."""
 import numpy as np
 import pytest
 

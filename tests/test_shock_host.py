@@ -2,13 +2,16 @@
 1. tests/shock_refs.oracle_shock_sweeps — the oracle loop with beta = beta_t and the value's partials augmented by V dbeta_t / beta_t —
    against a central difference of ITS OWN level in the entries beta_0 and beta_{P-1} (step 1e-6, agreement 1e-6 relative): the
    construction the GPU tests compare with is pinned without a device;
-2. SteadyStateJacobian.shock_jacobian's recursion on a stand-in block;
-3. examples/solve_hank.py's arguments."""
+2. tests/shock_refs.oracle_shock_jacobians — the dense pair every width of tests/test_gpu_shock_geometry.py is compared with — against
+   the sweeps with random seeds in the inputs and in beta together, and the raw grids' edges on the oracle's policy under a path;
+3. SteadyStateJacobian.shock_jacobian's recursion on a stand-in block;
+4. examples/solve_hank.py's arguments."""
 import numpy as np
 import pytest
 
+import cases
 import shock_refs as R
-from cases import close
+from cases import close, jt
 
 STEP = 1e-6
 
@@ -47,6 +50,48 @@ def test_a_constant_path_is_the_oracle_s_own_block(oracle_mod):
     agg, _, pol, _ = c["orc"].block(c["x"], None, c["V"], c["D"])
     close(ref["agg"][:, 0], agg, what="constant path: aggregate")
     close(ref["pol"], pol, what="constant path: policy")
+
+
+LINEAR_ECONOMIES = [("shape", 65, 3, 12), ("shape", 40, 11, 10), ("shape", 40, 1, 10), ("raw", "both")]
+
+
+@pytest.mark.parametrize("econ", LINEAR_ECONOMIES, ids=lambda e: "-".join(str(q) for q in e))
+def test_the_dense_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, econ):
+    """oracle_shock_jacobians' (Jx, Jb) — and the grid aggregate's pair — against oracle_shock_sweeps with random y and dbeta together:
+    the map is linear, so the two agree to rounding (1e-13 of the largest entry; measured <= 1.2e-15)"""
+    c = R.geometry_case(*econ)
+    n_hh, P = c["x"].shape
+    ref_args = (c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], c["n_het"])
+    Jx, Jb = J = R.oracle_shock_jacobians(*ref_args)
+    assert Jx.shape == (c["n_het"], P, n_hh, P) and Jb.shape == (P, c["n_het"], P)
+    assert R.oracle_shock_jacobians(*ref_args)[1] is Jb                            # (the sweeps ran once)
+    rng = np.random.default_rng(P)
+    y, db = rng.standard_normal((n_hh, P, 5)), rng.standard_normal((P, 5))
+    ref = R.oracle_shock_sweeps(*ref_args, y=y, dbeta=db)
+    lin = R.shock_linear(J, y, db)
+    for o in range(c["n_het"]):
+        close(lin[:, o, :], ref["dagg"][:, o, :], rel=1e-13, ab=0.0, what=f"{econ} output {o}")
+    J2x, J2b = R.oracle_shock_grid_jacobians(*ref_args)
+    close(np.einsum("tks,ksn->tn", J2x, y) + J2b @ db, ref["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate")
+    # the cotangent formulas are the transposes of the same pair
+    yb = rng.standard_normal((P, c["n_het"], 4))
+    lhs = np.einsum("tom,ton->mn", yb, lin)
+    rhs = np.einsum("ksm,ksn->mn", jt(Jx, yb), y) + R.shock_beta_bar(Jb, yb).T @ db
+    scale = np.einsum("tom,ton->mn", np.abs(yb), R.shock_linear((np.abs(Jx), np.abs(Jb)), np.abs(y), np.abs(db)))
+    assert np.all(np.abs(lhs - rhs) <= 1e-13 * scale), np.max(np.abs(lhs - rhs) / scale)
+
+
+@pytest.mark.parametrize("name", R.EDGE_ECONOMIES)
+def test_the_raw_grids_keep_their_edges_under_a_path(oracle_mod, name):
+    """conditions on the inputs of tests/test_gpu_shock_geometry.py section D: under beta_path(beta, 9) the oracle's policy holds
+    a deep clamped prefix, sources capped at the top and long runs of rows in one bracket (measured: clo up to 61 / 3 / 73, top up to
+    1 / 43 / 19, runs up to 52 / 2 / 60 for dense-bottom / short-top / both; deep-prefix: 265 clamped rows; swing: 123 sources on one
+    target row)"""
+    c = R.geometry_case("raw", name)
+    assert c["path"].shape == (cases.EDGE_P,)
+    pol = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], c["n_het"])["pol"]
+    assert np.all(np.isfinite(pol))
+    R.check_path_edges(name, c["grid"], pol)
 
 
 def test_shock_jacobian_is_the_toeplitz_recursion_per_output(hank):
