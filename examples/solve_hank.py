@@ -10,6 +10,13 @@ response to a monetary-policy shock.
         a household-side shock instead: the discount factor follows beta_t = beta (1 + SIZE RHO^t) (HouseholdBlock.set_discount_path);
         the nonlinear transition beside the linear response -J̅⁻¹ J_beta dbeta (SteadyStateJacobian.shock_jacobian); with --gradient
         the gradient of ½‖F‖² with respect to the path from one hank_vjp_shock, beside a central difference in two of its entries
+    python examples/solve_hank.py --redistribute 0.01 0.8 2 [--groups] [--gradient]
+        who is hit: a budget-neutral transfer SIZE RHO^t to each productivity state <= E; every other state pays one common amount,
+        set so that the transfers sum to zero under the column masses (hank_amd.incidence.redistribution;
+        HouseholdBlock.set_income_path); the nonlinear transition beside the linear response -J̅⁻¹ J_y y
+        (SteadyStateJacobian.income_jacobian); with --groups each productivity state's savings response (group outputs on the
+        policy base), nonlinear beside linear; with --gradient the gradient of ½‖F‖² with respect to the path
+        from one hank_vjp_income, beside a central difference in two of its entries
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/solve_hank.py
         one process per GPU (RCCL): the unit-tangent chunks of the Jacobian assembly are shared out over the ranks and
         all-gathered; the Newton iteration itself (one tangent per inner step) runs replicated on every rank."""
@@ -227,6 +234,86 @@ def discount_gradient(n_a=1000, n_e=7, T=500, size=0.002, rho=0.8, spec="one_ass
             "beta_bar": {str(t): float(g[t]) for t in fd}, "central_difference": {str(t): float(v) for t, v in fd.items()}}
 
 
+def _redistribute_setup(n_a, n_e, T, size, rho, upto, spec):
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    from hank_amd import incidence
+    m, ss = build(n_a, n_e, T, spec)
+    P = T - 1
+    keys = h.vars_of_type(m, "endogenous")
+    x0 = np.tile(np.array([ss.vars[k] for k in keys]), P)
+    mass = np.asarray(ss.D, dtype=np.float64).reshape((n_a, n_e), order="F").sum(axis=0)      # the productivity marginal: stationary, so m_t = m
+    y = incidence.redistribution(np.tile(mass[:, None], (1, P)), list(range(int(upto) + 1)), size, rho)
+    return h, m, ss, keys, x0, {"ei": np.zeros(P)}, y
+
+
+def redistribute(n_a=1000, n_e=7, T=500, size=0.01, rho=0.8, upto=2, eps=1e-9, spec="one_asset_hank.yaml", groups=False):
+    """The transition under a budget-neutral transfer to the productivity states <= upto, no other shock: Newton on the nonlinear
+    system with the income path set on the household block, beside the first-order response dx = -J̅⁻¹ (∂F/∂y) y with ∂F/∂y
+    assembled from `income_jacobian` (hank_fake_news_income: n_e backward tangent directions seeded at the last period). With
+    `groups` the savings response of every productivity state (group outputs on the policy base), nonlinear beside linear."""
+    h, m, ss, keys, x0, exog, y = _redistribute_setup(n_a, n_e, T, size, rho, upto, spec)
+    from hank_amd.SteadyStateJacobian import income_jacobian
+    from hank_amd import groups as G
+    P = T - 1
+    J = h.getSteadyStateJacobian(ss, m)                      # the steady-state J̅, taken before the path is set
+    lin0 = h.LinearizedFunction(x0, exog, m, ss, ss)
+    hb = lin0.hb
+    Jy = income_jacobian(hb, lin0._n_out)                    # (outputs, P, n_e, P) at the stationary record lin0 holds
+    yv = y.reshape(-1, order="F")
+    dx_lin = -np.linalg.solve(np.asarray(J), lin0.residual_income_jacobian(Jy) @ yv)
+    if groups:
+        hb.set_group_outputs(G.productivity_groups(n_a, n_e), np.full(n_e, hb.GROUP_POLICY, dtype=np.int32))
+        grp0, _ = hb.group_outputs()
+    t0 = time.perf_counter()
+    x = h.NewtonRaphsonHANK(x0, J, exog, m, ss, ss, ε=eps, income_path=y)
+    t_newton = time.perf_counter() - t0
+    lin = h.LinearizedFunction(x, exog, m, ss, ss, income_path=y)
+    dX, dL = (x - x0).reshape(len(keys), P, order="F"), dx_lin.reshape(len(keys), P, order="F")
+    show = [k for k in ("Y", "y", "r") if k in keys][:2] or list(keys[:2])
+    out = {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T,
+           "shock": f"y_t[e] = {size}*{rho}^t for e <= {upto}, zero-sum under the column masses", "paid_by_the_others": float(y[-1, 0]),
+           "newton_s": round(t_newton, 3), "newton_iterations": h.NewtonRaphsonHANK.iterations, "residual_norm": float(np.linalg.norm(lin.Fx)),
+           "deviation_nonlinear": {k: [float(v) for v in dX[keys.index(k), :4]] for k in show},
+           "deviation_linear": {k: [float(v) for v in dL[keys.index(k), :4]] for k in show},
+           "max_abs_difference_over_max": float(np.max(np.abs(dX - dL)) / np.max(np.abs(dX)))}
+    if groups:
+        grp, _ = hb.group_outputs()                          # the record is lin's: the converged path under the income path
+        from hank_amd.BackwardIteration import household_inputs
+        from hank_amd.dual import Dual
+        _, dxhh = household_inputs(Dual.seed(x0, dx_lin[:, None]), exog, m)
+        dxhh = np.asarray(dxhh, dtype=np.float64).reshape(hb.n_hh, P, 1)
+        lin0._record_primal()                                # back to the stationary record, without a path
+        hb.jvp_income(dxhh, y[:, :, None])
+        _, dgrp = hb.group_outputs(dxhh)
+        out["savings_by_state_nonlinear"] = {str(e): [float(v) for v in (grp - grp0)[:4, e]] for e in range(n_e)}
+        out["savings_by_state_linear"] = {str(e): [float(v) for v in dgrp[:4, e, 0]] for e in range(n_e)}
+    return out
+
+
+def redistribute_gradient(n_a=1000, n_e=7, T=500, size=0.01, rho=0.8, upto=2, spec="one_asset_hank.yaml", step=1e-6):
+    """The gradient of ½‖F(x0)‖² with respect to the income path at the Newton starting point (the steady state repeated, where
+    F ≠ 0 under the path): ONE `LinearizedFunction.vjp_income` (hank_vjp_income), beside a central difference in two entries."""
+    h, m, ss, keys, x0, exog, y = _redistribute_setup(n_a, n_e, T, size, rho, upto, spec)
+    lin = h.LinearizedFunction(x0, exog, m, ss, ss, income_path=y)
+    lin.vjp_income(lin.Fx)                                    # warm-up: workspace, graphs, the residual layer's linearisation
+    t0 = time.perf_counter()
+    g = lin.vjp_income(lin.Fx)
+    t_rev = time.perf_counter() - t0
+    fd = {}
+    for e, t in ((0, 0), (n_e - 1, T - 2)):
+        f = []
+        for sgn in (1.0, -1.0):
+            p = y.copy()
+            p[e, t] += sgn * step
+            F = h.LinearizedFunction(x0, exog, m, ss, ss, income_path=p).Fx
+            f.append(0.5 * float(F @ F))
+        fd[(e, t)] = (f[0] - f[1]) / (2 * step)
+    return {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "merit": 0.5 * float(lin.Fx @ lin.Fx),
+            "gradient_norm": float(np.linalg.norm(g)), "reverse_s": round(t_rev, 5), "reverse_vjps": 1,
+            "y_bar": {f"{e},{t}": float(g[e, t]) for e, t in fd}, "central_difference": {f"{e},{t}": float(v) for (e, t), v in fd.items()}}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-a", type=int, default=1000)
@@ -243,6 +330,9 @@ def parse_args(argv=None):
     ap.add_argument("--het-in-sweep", action="store_true", help="J(x)·y of a model that reads Value / UCE: hank_jvp + hank_get_het_outputs against one hank_jvp_het, timed side by side")
     ap.add_argument("--discount-shock", type=float, nargs=2, metavar=("SIZE", "RHO"), default=None,
                     help="a path of the discount factor, beta_t = beta (1 + SIZE RHO^t), instead of the monetary shock: the nonlinear transition beside the linear response; with --gradient the path's gradient of ½‖F‖²")
+    ap.add_argument("--redistribute", type=float, nargs=3, metavar=("SIZE", "RHO", "E"), default=None,
+                    help="a budget-neutral transfer SIZE RHO^t to the productivity states <= E (an income path by state) instead of the monetary shock: the nonlinear transition beside the linear response; with --gradient the path's gradient of ½‖F‖²")
+    ap.add_argument("--groups", action="store_true", help="with --redistribute: the savings response of every productivity state (group outputs on the policy base)")
     return ap.parse_args(argv)
 
 
@@ -251,6 +341,13 @@ if __name__ == "__main__":
     if a.discount_shock is not None:
         fn = discount_gradient if a.gradient else discount_shock
         print(json.dumps(fn(a.n_a, a.n_e, a.T, a.discount_shock[0], a.discount_shock[1], spec=a.spec)))
+        sys.exit(0)
+    if a.redistribute is not None:
+        size, rho, upto = a.redistribute[0], a.redistribute[1], int(a.redistribute[2])
+        if a.gradient:
+            print(json.dumps(redistribute_gradient(a.n_a, a.n_e, a.T, size, rho, upto, spec=a.spec)))
+        else:
+            print(json.dumps(redistribute(a.n_a, a.n_e, a.T, size, rho, upto, spec=a.spec, groups=a.groups)))
         sys.exit(0)
     if a.boundary_gradient:
         print(json.dumps(boundary_gradient(a.n_a, a.n_e, a.T, a.shock, spec=a.spec)))

@@ -481,6 +481,67 @@ int hank_vjp_shock_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, in
  *   term d_{o,beta} is zero for every output. J_o[t, s] = J_o[t-1, s-1] + F[t, s, o], J_o[0, s] = Dv[s, o] + F[0, s, o]. */
 int hank_fake_news_shock(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out);
 
+/* ---- a path of income by productivity state: y_t[e] -------------------------------------------------------
+ * Every income term of the budget is common to the productivity states; y_t[e] is an additive one that is not:
+ *     c + a' = (1 + r_t) a + w_t z_e + tr_t + y_t[e],    t = 0 .. P-1, e = 0 .. n_e-1
+ * (KrusellSmith.jl:59-62 and :66-80 inside the loop of BackwardIteration.jl:90-113; no counterpart in the reference, whose income
+ * process is a constant of the model). Targeted transfers, redistribution between states, unequal incidence of earnings and a path
+ * of the productivities z_t[e] (y_t[e] = w_t (z_t[e] - z_e)) are all this primitive. y_t[e] enters wherever tr_t enters, per column:
+ * the X half of period t (the knots s_t) and the Y half of period t (consumption, the marginal value), and consumption's aggregate
+ * directly, C_t += sum_e y_t[e] m_t[e] with m_t[e] = sum_a D_t[e,a] the column masses of the post-transition distribution.
+ *
+ * hank_set_income_path: y (n_e, P) column-major on the host, y[e + n_e t]; NULL clears it (with no path set that changes nothing).
+ * A non-finite entry is HANK_ERR_BAD_ARG and nothing changes. Setting or clearing a path invalidates what a new boundary
+ * invalidates — the record, the current tangent batch, the policy cotangent, the primal memo. A path of zeros gives the bits of no
+ * path. The income path and the discount-factor path exclude each other: each setter answers HANK_ERR_NOT_READY while the other's
+ * path is set.
+ * WHILE A PATH IS SET hank_primal[_dev], hank_primal_jvp[_dev] and hank_jvp[_dev] run on the per-period launches whatever
+ * HANK_SCHEDULE says, as under a discount-factor path: the schedule policy is left alone, no fallback is counted, hank_info and
+ * hank_last_timings report the launch family. hank_vjp (n_het <= 2), hank_get_policy_seq, hank_get_dist_seq,
+ * hank_get_grid_aggregates and the group outputs on the mass and policy bases read the record and stay correct;
+ * hank_get_het_outputs[_dev] with n_het <= 2 adds the direct term to consumption's level. The entries that rebuild consumption from
+ * the inputs or are defined at one income process answer HANK_ERR_NOT_READY: hank_get_het_outputs with n_het > 2,
+ * hank_get_group_outputs with a HANK_GROUP_CONS group, hank_jvp_het, hank_vjp_het*, hank_vjp_group, hank_jvp_boundary,
+ * hank_vjp_boundary, hank_primal_batch, hank_ss_batch, hank_vfi, hank_ss_jvp, hank_ss_vjp and every hank_fake_news*. The step entries
+ * hank_backward_step[_dual] ignore the path. */
+int hank_set_income_path(hank_ctx *ctx, const double *y);
+/* hank_jvp_income == the partials of the block under Duals seeded in xVals AND in y_t[e] (KrusellSmith.jl:59-62, :66-80 under
+ * Duals, inside the loop of BackwardIteration.jl:90-113; no counterpart in the reference), N directions at once:
+ *   dxhh (n_hh, P, N) as in hank_jvp, or NULL (zeros); dy (n_e, P, N) column-major, or NULL (zeros); both NULL is HANK_ERR_BAD_ARG.
+ *   dagg_out (P, N) as in hank_jvp.
+ * The seed, behind each launch of the backward tangent sweep: ds_t[e,i,n] += kc_t[e,i] sum_e2 Pi[e,e2] v_{t+1}[e2,i] dy_{t+1}[e2,n]
+ * - rho_t dy_t[e,n] (2 P + 3 launches; the forward sweep is hank_jvp's). Works with or without a path; always the per-period
+ * launches; needs a valid record (HANK_ERR_NOT_READY). Its batch becomes the current one, named as hank_jvp names it:
+ * hank_get_dpolicy_seq, hank_get_grid_aggregates, hank_get_group_outputs and hank_get_het_outputs[_income] serve it. A batch seeded
+ * with a dy carries it: hank_get_het_outputs (n_het <= 2) adds consumption's direct term from the batch's own dy, and the readers that
+ * rebuild c from the inputs — hank_get_het_outputs with n_het > 2, hank_get_group_outputs with a HANK_GROUP_CONS group — answer
+ * HANK_ERR_NOT_READY for its tangents until hank_jvp runs again. With dy zero or NULL dagg_out and hank_get_dpolicy_seq equal
+ * hank_jvp's under HANK_SCHEDULE=launch bit for bit; with dy NULL the batch is hank_jvp's in every respect. */
+int hank_jvp_income(hank_ctx *ctx, const double *dxhh, const double *dy, int32_t N, double *dagg_out);
+int hank_jvp_income_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dy, int32_t N, double *d_dagg_out);
+/* hank_get_het_outputs_income == hank_get_het_outputs for n_het <= 2 (KrusellSmith.jl:80: consumption is the budget residual;
+ * ForwardIteration.jl:303-307: the weighted dot) with the direct term of the income directions: dy (n_e, P, N) column-major as
+ * hank_jvp_income took it, or NULL (the dy the current batch carries, if any): consumption's tangent gains sum_e dy_t[e,n] m_t[e].
+ * Output 0 has no direct term. */
+int hank_get_het_outputs_income(hank_ctx *ctx, int32_t n_het, const double *dxhh, const double *dy, int32_t N, double *agg_out, double *dagg_out);
+int hank_get_het_outputs_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const double *d_dy, int32_t N, double *d_agg_out, double *d_dagg_out);
+/* hank_vjp_income == hank_vjp (n_het 1 or 2, its refusals, its workspace, what it leaves alone) plus the cotangent of the path
+ * (the transpose of KrusellSmith.jl:59-62, :66-80 inside the loop of BackwardIteration.jl:90-113; no counterpart in the reference,
+ * which differentiates forward only):
+ *   y_bar (n_e, P, M) column-major, required: y_bar_t[e,m] = sum_i (v_t[e,i] mu_t[e,i,m] - rho_t sbar_t[e,i,m]) + m_t[e] Cbar_t[m],
+ *   sbar_t the knots' cotangent and mu_t the value's cotangent of Sweep B at period t, Cbar_t consumption's cotangent — per-block
+ *   partials beside every period's launch, then one fixed-order sum over the blocks: no atomics, the same inputs give the same
+ *   bits. P + 2 launches more in Sweep B. xhh_bar equals hank_vjp's bit for bit. The exact transpose of hank_jvp_income followed by
+ *   hank_get_het_outputs_income. */
+int hank_vjp_income(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *y_bar);
+int hank_vjp_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_y_bar);
+/* hank_fake_news_income: the Toeplitz column blocks of outputs 0 .. n_het-1 (n_het <= 2) with respect to y[e] at the steady state
+ * (KrusellSmith.jl:59-62, :66-80; BackwardIteration.jl:90-113; the recursion of SteadyStateJacobian.jl:363-371 — no counterpart in
+ * the reference). hank_fake_news_het's preconditions and recursion with the input fixed to y[e]; no path may be set. The policy
+ * responses come from n_e backward tangent directions seeded with d y_{P-1}[e] = 1; the rest is shared code.
+ *   F_out (P, P, n_e, n_het), Dv_out (P, n_e, n_het); consumption's Dv carries the direct term m_ss[e] at lag 0, output 0 none. */
+int hank_fake_news_income(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out);
+
 /* ---- derivatives through the steady state ------------------------------------------------------------
  * Two of the block's three inputs are steady-state objects: V_T is the fixed point of the EGM step at the steady-state prices
  * (the inner loop of get_xVals, SteadyState.jl:132-141) and D_0 the stationary distribution of the lottery that step induces

@@ -58,6 +58,15 @@ def shock_jacobian(block, n_het):
     return np.stack([household_jacobian(F[..., o:o + 1], Dv[..., o:o + 1])[0] for o in range(F.shape[2])])
 
 
+def income_jacobian(block, n_het):
+    """d Y^o_t / d y_s[e] at the steady state for the first n_het (1 or 2) heterogeneous outputs, y_s[e] the additive income of
+    productivity state e in period s (HouseholdBlock.set_income_path): `block.fake_news_income(n_het)`'s F (P, P, n_e, n_het) and Dv
+    (P, n_e, n_het) through the recursion of `household_jacobian`, once per output. `block` holds the stationary primal and no path.
+    Returns J_y (n_het, P, n_e, P): J[o, t, e, s]."""
+    F, Dv = block.fake_news_income(n_het)
+    return np.stack([household_jacobian(F[..., o], Dv[..., o]).transpose(1, 0, 2) for o in range(F.shape[3])])
+
+
 def direct_blocks(model: SequenceModel, ss):
     """d R_t / d xMat[:, t + o] at the steady state for every offset o in -max_lag..max_lead: the `blocks` of
     SteadyStateJacobian.jl:124-145, from ONE evaluation of the compiled equations on a (1 + max_lag + max_lead)-column

@@ -15,6 +15,7 @@
 #include "hank_adjoint.h"
 #include "hank_boundary.h"
 #include "hank_shock.h"
+#include "hank_income.h"
 #include "hank_ssdiff_launch.h"
 #include "../../include/hank_hip.h"
 
@@ -106,6 +107,10 @@ struct TanWork {
     // same as [P][N] (k_shk_in); g_tback_shk: the backward sweep with the seed of every period between its launches
     DevBuf<double> shk_in, shk_db;
     GraphExec g_tback_shk;
+    // hank_jvp_income (hank_income.h), allocated on its first use at this width: the caller's dy (n_e, P, N) column-major (staging) and the
+    // same as [P][n_e][N] (k_inc_in); g_tback_inc: the backward sweep with the income seed of every period between its launches
+    DevBuf<double> inc_in, inc_dy;
+    GraphExec g_tback_inc;
     GraphExec &tan_back(bool bnd) { return g_tback[bnd]; }
     GraphExec &tan_fwd(bool bnd, int NX) { return g_tfwd[bnd][NX]; }
 private:
@@ -184,6 +189,8 @@ struct CotWork {
     GraphExec g_AG;                 // Sweep A with the context's groups (k_adj_dist_grp), captured on first use and dropped with the set (GroupSet)
     DevBuf<double> bb_part, bb_rm, bb_cm;       // hank_vjp_shock, allocated on its first use at this width: beta_bar's partials [P][nb][M], their sums [P][M] and (P, M) column-major
     GraphExec g_BS;                 // Sweep B with beta_bar's reduction behind every period's launch (k_shk_bbar), captured on first use
+    DevBuf<double> yb_part, yb_rm, yb_cm;       // hank_vjp_income, allocated on its first use at this width: y_bar's partials [P][nb][n_e][M], their sums [P][n_e][M] and (n_e, P, M) column-major
+    GraphExec g_BI;                 // Sweep B with y_bar's reduction behind every period's launch (k_inc_ybar), captured on first use
     DevBuf<double> bnd_vbar, bnd_dbar;          // (G, M) column-major the boundary's cotangents (hank_vjp_boundary), allocated on its first use at this width
 };
 // The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
@@ -246,6 +253,8 @@ struct TanBatch {
     const std::vector<XPass> *passes = nullptr;           // persistent family: how dpol is laid out
     bool boundary = false;          // the batch carries boundary seeds (hank_jvp_boundary): its dD_0 is not zero, so only outputs 0 and 1 are served
     const double *bnd_zm = nullptr; // view: {zm, om} [2][P][N] of its dD_0 seed (k_bnd_mpath), or nullptr without one
+    const double *inc_dy = nullptr; // view: the dy (n_e, P, N) column-major of a batch hank_jvp_income seeded with one, or nullptr: consumption's tangent has
+                                    // a direct term in it, so the readers that rebuild c from the inputs refuse such a batch and hank_get_het_outputs adds the term
 };
 
 // The timed sweeps of hank_last_timings (the first six, in its slot order), hank_last_vjp_timings (the next two) and
@@ -318,6 +327,14 @@ struct hank_ctx {
     bool beta_on = false;
     std::vector<double> h_beta;
     GraphExec g_pback_b;
+    // the income path (hank_set_income_path; hank_income.h): d_y [P][n_e] always holds the y_t[e] in force — zeros without a path (the
+    // graphs hold its address); inc_on: a path is set, so everything that (re)writes the record runs on the per-period launches through
+    // g_pback_y, the backward primal graph of k_inc_egm_X / k_inc_egm_step. d_inc_m [P][n_e]: the column masses of the recorded
+    // distributions (k_inc_mass), valid for the recorded primal or not (ensure_inc_mass). The two paths exclude each other.
+    DevBuf<double> d_y, d_inc_m;
+    bool inc_on = false, inc_m_valid = false;
+    std::vector<double> h_y;
+    GraphExec g_pback_y;
     Spans spans;                   // the timed sweeps (hank_last_timings, hank_last_vjp_timings, hank_last_ss_timings)
     std::list<TanWork> tws;        // per batch width, most recently used first (a small cache: Jacobian assembly and Newton alternate widths)
     // 0 = one launch per period for everything; 1 = XCD-local persistent sweeps for everything; 2 = auto (default where
@@ -385,6 +402,8 @@ static void batch_ran_boundary(hank_ctx *ctx, const void *ws, int N, const doubl
     ctx->batch.boundary = true;
     ctx->batch.bnd_zm = zm;
 }
+// the same for a batch of hank_jvp_income with income directions: dy as TanBatch::inc_dy, marking the batch batch_ran has just named
+static void batch_ran_income(hank_ctx *ctx, const double *dy) { ctx->batch.inc_dy = dy; }
 // every reader's question: is a batch of N directions current?
 static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
     if (!ctx->batch.current || ctx->batch.N != N) return fail(ctx, HANK_ERR_NOT_READY, "no tangent sweep with N=%d is current", N);
@@ -397,7 +416,7 @@ static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
 // lot_written: so were lo, lw, ig and start (every lottery but k_xdual_front's) — seg and lwg are made from them, so neither is valid without
 static void record_rewritten(hank_ctx *ctx, bool seg_written, bool lwg_written, bool lot_written = true) {
     ctx->primal_done = true; ctx->seg_valid = seg_written && lot_written; ctx->lwg_valid = lwg_written && lot_written; ctx->lot_valid = lot_written;
-    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->hx.valid = false; ctx->grp.valid = false;
+    ctx->wprep_valid = false; ctx->xw.src_valid = false; ctx->xw.rng_valid = false; ctx->adj_seg_valid = false; ctx->hx.valid = false; ctx->grp.valid = false; ctx->inc_m_valid = false;
     batch_none(ctx);
     cot_none(ctx);
 }
@@ -539,6 +558,24 @@ static int ensure_shock_primal_graphs(hank_ctx *ctx) {
     hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
     return end_capture(ctx, &ctx->g_pback_b);
 }
+// the same at an income path (hank_income.h): y_t[e] from d_y in both halves. Captured the first time a primal runs with a path set.
+static int ensure_income_primal_graphs(hank_ctx *ctx) {
+    if (!ctx->g_pback) { const int rc = build_primal_graphs(ctx); if (rc) return rc; }
+    if (ctx->g_pback_y) return HANK_OK;
+    const Consts &c = ctx->c;
+    const int P = c.P;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
+    const size_t lds = primal_lds(c);
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    zero_err(ctx, s);
+    hipLaunchKernelGGL(k_inc_egm_X, grd, blk, lds, s, c, ctx->d_y.get(), ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
+                       ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, P - 1);
+    for (int t = P - 1; t >= 0; t--)
+        hipLaunchKernelGGL(k_inc_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, ctx->d_y.get(), t, ctx->d_err);
+    hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
+    return end_capture(ctx, &ctx->g_pback_y);
+}
 
 // Captures the four tangent graphs for lane type VT (double: one direction per lane; double2: two).
 // the row-group count is a template parameter of the kernels and a run-time choice here
@@ -576,8 +613,14 @@ static dim3 bnd_grid(const Consts &c, int N) { return dim3((unsigned)((c.n_a + B
 // the backward tangent sweep; bnd: with the dV_P seed (hank_boundary.h: the same launches of the same kernel, the seed kernels between them)
 // shock (hank_shock.h): the d beta_t seed of EVERY period behind the launch that produced that period's knots' tangent — P launches more, and
 // k_shk_in in front; w.shk_in, w.shk_db are allocated before this
+// income (hank_income.h; never with shock or bnd): the d y_t[e] seed of every period in the same places, k_inc_in in front; w.inc_in, w.inc_dy are
+// allocated before this
+static size_t inc_seed_lds(const Consts &c, int N) {      // k_inc_seed_back's staging, or 0 where it does not fit (it reads global memory then)
+    const size_t b = sizeof(double) * ((size_t)c.n_e * c.n_e + 2 * (size_t)c.n_e * N);
+    return b <= 48 * 1024 ? b : 0;
+}
 template <typename VT>
-static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = false) {
+static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = false, bool income = false) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
     const int N = w.N, PN = (int)(P * N), RGB = w.RGB;
@@ -590,10 +633,17 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = fa
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
     if (shock) hipLaunchKernelGGL(k_shk_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.shk_in.get(), (int)P, N, w.shk_db.get());
+    if (income) hipLaunchKernelGGL(k_inc_in, dim3((unsigned)(((size_t)PN * c.n_e + 255) / 256)), dim3(256), 0, s, w.inc_in.get(), c.n_e, (int)P, N, w.inc_dy.get());
     const dim3 sgrd((unsigned)(((size_t)c.n_a * N + 255) / 256));
+    const size_t ilds = inc_seed_lds(c, N), eN = (size_t)c.n_e * N;
     auto seed = [&](int t, double *ds_t) {      // ds_t: the knots' tangent of period t, as the launch before left it
-        hipLaunchKernelGGL(k_shk_seed_back, sgrd, dim3(256), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->d_beta.get(), t, w.shk_db.get() + (size_t)t * N, (size_t)N, ds_t);
+        if (income)
+            hipLaunchKernelGGL(k_inc_seed_back, sgrd, dim3(256), ilds, s, c, ctx->R, ctx->d_xhh.get(), t, w.inc_dy.get() + (size_t)t * eN,
+                               t + 1 < (int)P ? w.inc_dy.get() + (size_t)(t + 1) * eN : (const double *)nullptr, (size_t)N, ilds ? 1 : 0, ds_t);
+        else
+            hipLaunchKernelGGL(k_shk_seed_back, sgrd, dim3(256), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->d_beta.get(), t, w.shk_db.get() + (size_t)t * N, (size_t)N, ds_t);
     };
+    shock = shock || income;      // (the seeds sit in the same places)
     LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, (int)P - 1, 1,
                        ds[1], ds[0], dpol);
     if (shock) seed((int)P - 1, w.ds[0].get());
@@ -608,7 +658,7 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = fa
         if (shock && t > 0) seed(t - 1, w.ds[cur ^ 1].get());
         cur ^= 1;
     }
-    return end_capture(ctx, shock ? &w.g_tback_shk : &w.tan_back(bnd));
+    return end_capture(ctx, income ? &w.g_tback_inc : shock ? &w.g_tback_shk : &w.tan_back(bnd));
 }
 
 // the forward tangent sweep; bnd: with the dD_0 seed; NX > 0 (hank_jvp_het): k_tan_fwd_hx in k_tan_fwd's place and k_reduce_hx behind
@@ -795,6 +845,16 @@ static int ensure_shock_tan_graph(hank_ctx *ctx, TanWork &w) {
     }
     if (w.g_tback_shk) return HANK_OK;
     return w.VB == 2 ? capture_tan_back<double2>(ctx, w, false, true) : capture_tan_back<double>(ctx, w, false, true);
+}
+// hank_jvp_income's / hank_fake_news_income's backward graph
+static int ensure_income_tan_graph(hank_ctx *ctx, TanWork &w) {
+    const size_t cnt = (size_t)ctx->c.P * ctx->c.n_e * w.N;
+    if (!w.inc_dy) {
+        HIPC(ctx, w.inc_in.alloc(cnt));
+        HIPC(ctx, w.inc_dy.alloc(cnt));      // (last: a failed allocation is tried again by the next call)
+    }
+    if (w.g_tback_inc) return HANK_OK;
+    return w.VB == 2 ? capture_tan_back<double2>(ctx, w, false, false, true) : capture_tan_back<double>(ctx, w, false, false, true);
 }
 static int ensure_dual_graphs(hank_ctx *ctx, TanWork &w) {
     if (w.g_fback) return HANK_OK;
@@ -1648,6 +1708,10 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     HIPC(ctx, ctx->d_beta.alloc(P));
     ctx->h_beta.assign(P, c.beta);      // no path: the model's beta in every period
     HIPC(ctx, hipMemcpy(ctx->d_beta, ctx->h_beta.data(), sizeof(double) * P, hipMemcpyHostToDevice));
+    HIPC(ctx, ctx->d_y.alloc((size_t)P * c.n_e));
+    HIPC(ctx, ctx->d_inc_m.alloc((size_t)P * c.n_e));
+    ctx->h_y.assign((size_t)P * c.n_e, 0.0);      // no path: zeros
+    HIPC(ctx, hipMemset(ctx->d_y, 0, sizeof(double) * P * c.n_e));
     HIPC(ctx, ctx->d_agg.alloc(2 * P));
     HIPC(ctx, ctx->d_agg_rm.alloc(2 * P));
     HIPC(ctx, ctx->d_zd.alloc(2 * P));
@@ -1779,6 +1843,7 @@ int hank_set_discount_path(hank_ctx *ctx, const double *beta_t) {
     if (!ctx) return HANK_ERR_BAD_ARG;
     const size_t P = ctx->c.P;
     if (!beta_t && !ctx->beta_on) { ctx->errmsg[0] = 0; return HANK_OK; }      // (no path to clear: nothing changes)
+    if (ctx->inc_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_discount_path: an income path is set and the two exclude each other (hank_set_income_path(ctx, NULL) clears it)");
     if (beta_t)
         for (size_t t = 0; t < P; t++)
             if (!(beta_t[t] > 0.0) || !(beta_t[t] <= 1.7976931348623157e308))
@@ -1796,10 +1861,51 @@ int hank_set_discount_path(hank_ctx *ctx, const double *beta_t) {
     ctx->errmsg[0] = 0;
     return HANK_OK;
 }
-// the entries that are defined at ONE beta (the scenario and steady-state entries, the Toeplitz Jacobians) while a path is set
+// hank_set_income_path (hank_income.h; KrusellSmith.jl:59-62, :66-80 inside the loop of BackwardIteration.jl:90-113): y (n_e, P) column-major
+// on the host, or null for no path. What a new boundary invalidates goes: the record, both current batches, the memo.
+int hank_set_income_path(hank_ctx *ctx, const double *y) {
+    ENTER(ctx);
+    if (!ctx) return HANK_ERR_BAD_ARG;
+    const size_t cnt = (size_t)ctx->c.P * ctx->c.n_e;
+    if (!y && !ctx->inc_on) { ctx->errmsg[0] = 0; return HANK_OK; }      // (no path to clear: nothing changes)
+    if (y && ctx->beta_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_income_path: a discount-factor path is set and the two exclude each other (hank_set_discount_path(ctx, NULL) clears it)");
+    if (y)
+        for (size_t k = 0; k < cnt; k++)
+            if (!(y[k] >= -1.7976931348623157e308 && y[k] <= 1.7976931348623157e308))
+                return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_income_path: y must be finite (state %zu, period %zu: %g); the path in force is unchanged", k % ctx->c.n_e + 1, k / ctx->c.n_e + 1, y[k]);
+    HIPC(ctx, join_side(ctx));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (sweeps in flight read d_y)
+    if (y) ctx->h_y.assign(y, y + cnt);
+    else ctx->h_y.assign(cnt, 0.0);
+    HIPC(ctx, hipMemcpyAsync(ctx->d_y, ctx->h_y.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->inc_on = y != nullptr;
+    record_gone(ctx);
+    ctx->memo_valid = false;
+    ctx->stationary = false;
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+// the entries that rebuild consumption from the inputs (w z_e + tr) or carry seeds the income entries do not, while an income path is set
+static int income_refuses(hank_ctx *ctx, const char *name) {
+    if (ctx && ctx->inc_on)
+        return fail(ctx, HANK_ERR_NOT_READY, "%s is not served at an income path: a path is set (hank_set_income_path(ctx, NULL) clears it)", name);
+    return HANK_OK;
+}
+// the entries that are defined at ONE beta and ONE income process (the scenario and steady-state entries, the Toeplitz Jacobians) while a path is set
 static int path_refuses(hank_ctx *ctx, const char *name) {
     if (ctx && ctx->beta_on)
         return fail(ctx, HANK_ERR_NOT_READY, "%s is defined at one discount factor: a path is set (hank_set_discount_path(ctx, NULL) clears it)", name);
+    return income_refuses(ctx, name);
+}
+// a path of either kind: the sweeps run on the per-period launches
+static bool path_on(const hank_ctx *ctx) { return ctx->beta_on || ctx->inc_on; }
+// the column masses of the recorded distributions, for the first reader at this record (the main stream has joined the forward sweep)
+static int ensure_inc_mass(hank_ctx *ctx) {
+    if (ctx->inc_m_valid) return HANK_OK;
+    hipLaunchKernelGGL(k_inc_mass, dim3((unsigned)ctx->c.n_e, (unsigned)ctx->c.P), dim3(256), 0, ctx->stream, ctx->c, ctx->R, ctx->d_inc_m.get());
+    HIPC(ctx, hipGetLastError());
+    ctx->inc_m_valid = true;
     return HANK_OK;
 }
 
@@ -1815,9 +1921,10 @@ static void note_primal_x(hank_ctx *ctx, const double *xhh) {
 
 static int run_primal(hank_ctx *ctx, double *d_agg_out) {
     if (ctx->beta_on) { const int grc = ensure_shock_primal_graphs(ctx); if (grc) return grc; }      // (whatever the schedule: a path runs on the launches)
+    if (ctx->inc_on) { const int grc = ensure_income_primal_graphs(ctx); if (grc) return grc; }
     HIPC(ctx, join_side(ctx));     // a previous forward sweep still reads the record this one overwrites
     HIPC(ctx, ctx->spans.begin(PRIMAL_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(ctx->beta_on ? ctx->g_pback_b : ctx->g_pback, ctx->stream));
+    HIPC(ctx, hipGraphLaunch(ctx->beta_on ? ctx->g_pback_b : ctx->inc_on ? ctx->g_pback_y : ctx->g_pback, ctx->stream));
     HIPC(ctx, ctx->spans.end(PRIMAL_BACK, ctx->stream, ctx->c.P + 2));
     // fork: the distribution sweep goes to the side stream; the main stream is free for the tangent
     // backward sweep and joins (join_side) before anything that needs D_t or the aggregates
@@ -2012,7 +2119,7 @@ static int check_rates(hank_ctx *ctx, const double *xhh) {      // the host-poin
 }
 // hank_primal[_dev]: x from the caller (kind: where it lives) and the Float64 sweeps of the context's schedule
 static int enqueue_primal(hank_ctx *ctx, const double *xhh, hipMemcpyKind kind, double *d_agg_out) {
-    if (!ctx->beta_on && use_x_primal(ctx)) return x_primal(ctx, xhh, kind, d_agg_out);      // (a path: the launches, the schedule left as it is)
+    if (!path_on(ctx) && use_x_primal(ctx)) return x_primal(ctx, xhh, kind, d_agg_out);      // (a path: the launches, the schedule left as it is)
     HIPC(ctx, hipMemcpyAsync(ctx->d_xhh, xhh, sizeof(double) * ctx->c.n_hh * ctx->c.P, kind, ctx->stream));
     return run_primal(ctx, d_agg_out);
 }
@@ -2057,13 +2164,15 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
 // bnd: the graphs with the boundary's seeds (hank_jvp_boundary: w.bnd_dV and w.bnd_dD hold them); zm: whether a dD_0 seed is among them
 // NX > 0 (hank_jvp_het): the forward graph with that many extra reductions, one launch more (k_reduce_hx)
 // shock (hank_jvp_shock; never with bnd): the backward graph with the d beta_t seeds, 2 P + 3 launches
-static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd, bool zm, int NX, bool shock = false) {
+// income (hank_jvp_income; never with bnd or shock): the backward graph with the d y_t[e] seeds, the same count
+static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd, bool zm, int NX, bool shock = false, bool income = false) {
     int grc = ensure_tan_graphs(ctx, w, bnd, NX);
     if (!grc && shock) grc = ensure_shock_tan_graph(ctx, w);
+    if (!grc && income) grc = ensure_income_tan_graph(ctx, w);
     if (grc) return grc;
     HIPC(ctx, ctx->spans.begin(TAN_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(shock ? w.g_tback_shk : w.tan_back(bnd), ctx->stream));
-    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, shock ? 2 * ctx->c.P + 3 : ctx->c.P + (bnd ? 4 : 2)));
+    HIPC(ctx, hipGraphLaunch(income ? w.g_tback_inc : shock ? w.g_tback_shk : w.tan_back(bnd), ctx->stream));
+    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, (shock || income) ? 2 * ctx->c.P + 3 : ctx->c.P + (bnd ? 4 : 2)));
     HIPC(ctx, join_side(ctx));      // the tangent forward sweep needs D_t
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
@@ -2085,6 +2194,8 @@ struct TanReq {
                                                    // hank_jvp_het when a seed is given, hank_jvp never — NOT derived from the pointers
     const double *dbeta = nullptr;                 // hank_jvp_shock: the directions in beta_t, (P, N) column-major; null: zero
     bool shock = false;                            // run the backward graph with the d beta_t seeds (hank_jvp_shock always, null dbeta too)
+    const double *dy = nullptr;                    // hank_jvp_income: the directions in y_t[e], (n_e, P, N) column-major; null: zero
+    bool income = false;                           // run the backward graph with the d y_t[e] seeds (hank_jvp_income always, null dy too)
 };
 static int ensure_bnd_bufs(hank_ctx *ctx, TanWork &w);
 static int ensure_hx_record(hank_ctx *ctx);
@@ -2121,8 +2232,15 @@ static int enqueue_tan_launch(hank_ctx *ctx, const TanReq &q, int N, TanWork **o
         if (q.dbeta) HIPC(ctx, hipMemcpyAsync(w->shk_in, q.dbeta, sizeof(double) * P * N, q.kind, ctx->stream));
         else HIPC(ctx, hipMemsetAsync(w->shk_in, 0, sizeof(double) * P * N, ctx->stream));
     }
-    rc = run_jvp(ctx, *w, q.seeded, q.dD_init != nullptr, NX, q.shock);
+    if (q.income) {
+        rc = ensure_income_tan_graph(ctx, *w);
+        if (rc) return rc;
+        if (q.dy) HIPC(ctx, hipMemcpyAsync(w->inc_in, q.dy, sizeof(double) * P * c.n_e * N, q.kind, ctx->stream));
+        else HIPC(ctx, hipMemsetAsync(w->inc_in, 0, sizeof(double) * P * c.n_e * N, ctx->stream));
+    }
+    rc = run_jvp(ctx, *w, q.seeded, q.dD_init != nullptr, NX, q.shock, q.income);
     if (rc) return rc;
+    if (q.income && q.dy) batch_ran_income(ctx, w->inc_in);      // (a null dy is hank_jvp's batch)
     *out = w;
     return HANK_OK;
 }
@@ -2145,7 +2263,8 @@ static int tan_host_tail(hank_ctx *ctx, double *out, const double *d_src, size_t
 static int tan_seed_args(hank_ctx *ctx, const char *who, bool het, const TanReq &q, int N, const void *out, bool need_out) {
     if (!ctx || (!q.dxhh && !q.dvalue_end && !q.dD_init) || (need_out && !out) || N < 1)
         return fail(ctx, HANK_ERR_BAD_ARG, "%s: bad argument (N=%d; at least one of dxhh, dvalue_end, dD_init must be given)", who, N);
-    const int rc = het ? het_count_ok(ctx, who, q.n_het, true) : HANK_OK;
+    int rc = het ? het_count_ok(ctx, who, q.n_het, true) : HANK_OK;
+    if (!rc) rc = income_refuses(ctx, who);
     if (rc) return rc;
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before %s", who);
     return HANK_OK;
@@ -2156,8 +2275,8 @@ static int tan_seed_args(hank_ctx *ctx, const char *who, bool het, const TanReq 
 static int enqueue_jvp(hank_ctx *ctx, const double *dxhh, hipMemcpyKind kind, int N, double *d_dagg_out) {
     // at a record written under a discount-factor path the persistent and the wide tangent sweeps would rebuild kc with the model's
     // beta (diet_kc): the launches read it from the record
-    if (!ctx->beta_on && use_wide(ctx, N)) return w_jvp(ctx, dxhh, kind, N, d_dagg_out);
-    if (!ctx->beta_on && use_x_jvp(ctx, N)) return x_jvp(ctx, dxhh, kind, N, d_dagg_out);
+    if (!path_on(ctx) && use_wide(ctx, N)) return w_jvp(ctx, dxhh, kind, N, d_dagg_out);
+    if (!path_on(ctx) && use_x_jvp(ctx, N)) return x_jvp(ctx, dxhh, kind, N, d_dagg_out);
     return enqueue_tan_raw(ctx, TanReq{0, dxhh, nullptr, nullptr, kind, false}, N, d_dagg_out);
 }
 
@@ -2268,6 +2387,34 @@ int hank_jvp_shock(hank_ctx *ctx, const double *dxhh, const double *dbeta, int32
     return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
 }
 
+// hank_jvp_income[_dev] (hank_income.h): the request with the d y_t[e] seeds, always on the launches' graphs with the seed kernels; a
+// null input is a zero seed. Named as hank_jvp names its batch.
+static int income_args(hank_ctx *ctx, const double *dxhh, const double *dy, int N, const void *out, bool need_out) {
+    if (!ctx || (!dxhh && !dy) || (need_out && !out) || N < 1)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_income: bad argument (N=%d; at least one of dxhh, dy must be given)", N);
+    if (ctx->beta_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_jvp_income: a discount-factor path is set and the two exclude each other");
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_income");
+    return HANK_OK;
+}
+static TanReq income_req(const double *dxhh, const double *dy, hipMemcpyKind kind) {
+    TanReq q{0, dxhh, nullptr, nullptr, kind, false};
+    q.dy = dy;
+    q.income = true;
+    return q;
+}
+int hank_jvp_income_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dy, int32_t N, double *d_dagg_out) {
+    ENTER(ctx);
+    const int rc = income_args(ctx, d_dxhh, d_dy, N, d_dagg_out, false);
+    return rc ? rc : enqueue_tan_raw(ctx, income_req(d_dxhh, d_dy, hipMemcpyDeviceToDevice), N, d_dagg_out);
+}
+int hank_jvp_income(hank_ctx *ctx, const double *dxhh, const double *dy, int32_t N, double *dagg_out) {
+    ENTER(ctx);
+    int rc = income_args(ctx, dxhh, dy, N, dagg_out, true);
+    if (!rc) rc = enqueue_tan_raw(ctx, income_req(dxhh, dy, hipMemcpyHostToDevice), N, nullptr);
+    if (rc) return rc;
+    return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
+}
+
 static int run_fused(hank_ctx *ctx, TanWork &w) {
     const int grc = ensure_dual_graphs(ctx, w);
     if (grc) return grc;
@@ -2306,7 +2453,7 @@ int hank_primal_jvp_dev(hank_ctx *ctx, const double *d_xhh, const double *d_dxhh
     ENTER(ctx);
     if (!ctx || !d_xhh || !d_dxhh || N < 1) return fail(ctx, HANK_ERR_BAD_ARG, "bad argument (N=%d)", N);
     if (!ctx->boundary_set) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_boundary must be called first");
-    if (use_wide(ctx, N) || ctx->beta_on) {           // a wide batch: the Float64 sweeps of the context's schedule, then the on-chip tangent sweeps; a path: both on the launches
+    if (use_wide(ctx, N) || path_on(ctx)) {           // a wide batch: the Float64 sweeps of the context's schedule, then the on-chip tangent sweeps; a path: both on the launches
         const int rc = hank_primal_dev(ctx, d_xhh, d_agg_out);
         return rc ? rc : hank_jvp_dev(ctx, d_dxhh, N, d_dagg_out);
     }
@@ -2337,7 +2484,7 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
         }
         return HANK_OK;
     }
-    if (use_wide(ctx, N) || ctx->beta_on) {
+    if (use_wide(ctx, N) || path_on(ctx)) {
         rc = hank_primal(ctx, xhh, agg_out);
         return rc ? rc : hank_jvp(ctx, dxhh, N, dagg_out);
     }
@@ -2355,16 +2502,20 @@ int hank_primal_jvp(hank_ctx *ctx, const double *xhh, const double *dxhh, int32_
 
 // the fake-news workspace for n_het outputs: allocated at the first call, grown (all of it, after the stream drains) when a
 // call asks for more outputs than it holds
-static int ensure_fn(hank_ctx *ctx, int n_het) {
-    if (ctx->fn.n_het >= n_het) return HANK_OK;
-    const size_t P = ctx->c.P, G = ctx->c.G, NP = P * ctx->c.n_hh, S = 16, nh = n_het;
+// Nw: the directions of the backward batch — the n_hh inputs, or the n_e income states of hank_fake_news_income; the workspace holds the
+// widest and the most outputs asked for so far
+static int ensure_fn(hank_ctx *ctx, int n_het, int Nw) {
+    if (ctx->fn.n_het >= n_het && ctx->fn.N >= std::max(Nw, ctx->c.n_hh)) return HANK_OK;
+    n_het = std::max(n_het, ctx->fn.n_het);
+    Nw = std::max(std::max(Nw, ctx->fn.N), ctx->c.n_hh);      // (never below n_hh: k_fn_het_record and k_grp_fn_record write dsum [nh][n_hh] whatever the batch)
+    const size_t P = ctx->c.P, G = ctx->c.G, NP = P * Nw, S = 16, nh = n_het;
     if (ctx->fn.dpT) HIPC(ctx, hipStreamSynchronize(ctx->stream));
     ctx->fn = {};
     auto alloc = [&]() -> int {
         HIPC(ctx, ctx->fn.dpT.alloc(G * NP)); HIPC(ctx, ctx->fn.iota.alloc(G * NP));
         HIPC(ctx, ctx->fn.E.alloc(nh * P * G)); HIPC(ctx, ctx->fn.Cp.alloc(S * nh * P * NP));
         HIPC(ctx, ctx->fn.F.alloc(nh * P * NP)); HIPC(ctx, ctx->fn.Dv.alloc(nh * NP));
-        HIPC(ctx, ctx->fn.W.alloc(nh * G)); HIPC(ctx, ctx->fn.dsum.alloc(nh * ctx->c.n_hh));
+        HIPC(ctx, ctx->fn.W.alloc(nh * G)); HIPC(ctx, ctx->fn.dsum.alloc(nh * Nw));
         return HANK_OK;
     };
     const int rc = alloc();
@@ -2374,6 +2525,7 @@ static int ensure_fn(hank_ctx *ctx, int n_het) {
         return rc;
     }
     ctx->fn.n_het = n_het;
+    ctx->fn.N = Nw;
     return HANK_OK;
 }
 
@@ -2410,12 +2562,14 @@ static int stationary_record(hank_ctx *ctx, const char *name) {
 // workspace never holds more — steps 3 and 4 run once per chunk, once in all for the other two entries).
 // shock (hank_fake_news_shock; with n_het >= 1): ONE direction in place of the n_hh inputs' — the backward sweep seeded with
 // d beta_{P-1} = 1 (hank_shock.h) — and no direct term: F (P, P, n_het), Dv (P, n_het).
-static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, double *Dv_out, bool shock = false) {
-    const char *name = shock ? "hank_fake_news_shock" : groups ? "hank_fake_news_group" : n_het ? "hank_fake_news_het" : "hank_fake_news";
+// income (hank_fake_news_income; with n_het = 1, 2): n_e directions in place of the inputs' — the backward sweep seeded with
+// d y_{P-1}[e] = 1 in direction e (hank_income.h) — and the direct term m_ss[e] of consumption at lag 0: F (P, P, n_e, n_het), Dv (P, n_e, n_het).
+static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, double *Dv_out, bool shock = false, bool income = false) {
+    const char *name = income ? "hank_fake_news_income" : shock ? "hank_fake_news_shock" : groups ? "hank_fake_news_group" : n_het ? "hank_fake_news_het" : "hank_fake_news";
     { const int prc = path_refuses(ctx, name); if (prc) return prc; }
     { const int nrc = stationary_record(ctx, name); if (nrc) return nrc; }
     const Consts &c = ctx->c;
-    const int P = c.P, G = c.G, N = shock ? 1 : c.n_hh, NP = P * N, S = 16, nout = groups ? ctx->grp.K : n_het ? n_het : 1;
+    const int P = c.P, G = c.G, N = income ? c.n_e : shock ? 1 : c.n_hh, NP = P * N, S = 16, nout = groups ? ctx->grp.K : n_het ? n_het : 1;
     const int cap = groups ? std::min(nout, GRP_FN_CHUNK) : nout;      // outputs per pass
     hipStream_t s = ctx->stream;
     { const int src = ensure_seg(ctx); if (src) return src; }
@@ -2427,18 +2581,30 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
     TanWork &w = *wp;
     rc = ensure_tan_graphs(ctx, w, false, 0);
     if (!rc && shock) rc = ensure_shock_tan_graph(ctx, w);
+    if (!rc && income) rc = ensure_income_tan_graph(ctx, w);
     if (rc) return rc;
-    rc = ensure_fn(ctx, cap);
+    rc = ensure_fn(ctx, cap, N);
     if (rc) return rc;
     HIPC(ctx, join_side(ctx));      // D_1 and the {w, ig D} records come from the primal's forward sweep
-    if (shock) {      // no input moves; d beta_{P-1} = 1 (the batch is one direction wide: (P, 1) column-major is [P])
+    std::vector<double> hm;         // income: the steady state's column masses, the direct term of consumption
+    if (income) {      // no input moves; d y_{P-1}[e] = 1 in direction e, (n_e, P, n_e) column-major
+        std::vector<double> seed((size_t)N * P * N, 0.0);
+        for (int e = 0; e < N; e++) seed[(size_t)e + (size_t)N * ((size_t)(P - 1) + (size_t)P * e)] = 1.0;
+        hm.resize(N);
+        rc = ensure_inc_mass(ctx);
+        if (rc) return rc;
+        HIPC(ctx, hipMemsetAsync(w.dxhh, 0, sizeof(double) * c.n_hh * P * N, s));
+        HIPC(ctx, hipMemcpyAsync(w.inc_in, seed.data(), sizeof(double) * seed.size(), hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync(hm.data(), ctx->d_inc_m, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+        HIPC(ctx, hipStreamSynchronize(s));      // (seed is this block's)
+    } else if (shock) {      // no input moves; d beta_{P-1} = 1 (the batch is one direction wide: (P, 1) column-major is [P])
         static const double one = 1.0;
         HIPC(ctx, hipMemsetAsync(w.dxhh, 0, sizeof(double) * c.n_hh * P, s));
         HIPC(ctx, hipMemsetAsync(w.shk_in, 0, sizeof(double) * P, s));
         HIPC(ctx, hipMemcpyAsync(w.shk_in.get() + (P - 1), &one, sizeof(double), hipMemcpyHostToDevice, s));
     } else
         hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
-    HIPC(ctx, hipGraphLaunch(shock ? w.g_tback_shk : w.tan_back(false), s));
+    HIPC(ctx, hipGraphLaunch(income ? w.g_tback_inc : shock ? w.g_tback_shk : w.tan_back(false), s));
     batch_none(ctx);      // (w.dpol no longer belongs to a caller's batch)
     // 2. the lottery impulse of every lag and input at once
     hipLaunchKernelGGL(k_fn_transpose, dim3((unsigned)((G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256), 0, s, w.dpol, P, G, N, ctx->fn.dpT);
@@ -2471,7 +2637,7 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
         HIPC(ctx, hipGetLastError());
         HIPC(ctx, hipMemcpyAsync(hF.data(), ctx->fn.F, sizeof(double) * MP * NP, hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipMemcpyAsync(hD.data(), ctx->fn.Dv, sizeof(double) * nh * NP, hipMemcpyDeviceToHost, s));
-        if (groups || n_het) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * nh * N, hipMemcpyDeviceToHost, s));
+        if ((groups || n_het) && !shock && !income) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * nh * N, hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));
         if (o0 == 0) {
             rc = device_verdict(ctx, THE_RECORD);
@@ -2485,7 +2651,8 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
                     const int j = P - 1 - t;
                     const size_t kc = (size_t)k + (size_t)N * o, ko = (size_t)k + (size_t)N * (o0 + o);
                     const double dv = hD[(size_t)o * NP + (size_t)t * N + k];
-                    Dv_out[j + (size_t)P * ko] = (!shock && (groups || o > 0) && j == 0) ? dv + hd[kc] : dv;      // (beta has no direct term in any output)
+                    // (beta has no direct term in any output; y_t[e]'s is m_ss[e], in consumption)
+                    Dv_out[j + (size_t)P * ko] = (income && o == 1 && j == 0) ? dv + hm[k] : (!shock && !income && (groups || o > 0) && j == 0) ? dv + hd[kc] : dv;
                     for (int u = 0; u < P; u++) F_out[u + (size_t)P * (j + (size_t)P * ko)] = hF[((size_t)o * P + u) * NP + (size_t)t * N + k];
                 }
     }
@@ -2514,6 +2681,14 @@ int hank_fake_news_shock(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     const int rc = het_count_ok(ctx, "hank_fake_news_shock", n_het, false);
     return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, true);
+}
+
+// (KrusellSmith.jl:59-62, :66-80, BackwardIteration.jl:90-113; the recursion of SteadyStateJacobian.jl:363-371 with the input fixed to y[e])
+int hank_fake_news_income(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out) {
+    ENTER(ctx);
+    if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
+    const int rc = het_count_ok(ctx, "hank_fake_news_income", n_het, false, n_het <= 2);
+    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, false, true);
 }
 
 #ifdef HANK_XSTAMP
@@ -2762,10 +2937,12 @@ static int capture_cot_graph_ag(hank_ctx *ctx, CotWork &w) {
 // shock (hank_vjp_shock; hank_shock.h): Sweep B with beta_bar_t's partials behind every period's launch, while that period's mu_t is in
 // the state the launch read — the same launches of k_adj_egm and k_adj_out, P + 2 more: w.g_BS
 static int shk_mc(int M) { int mc = 1; while (mc < M && mc < 64) mc <<= 1; return mc; }      // cotangent columns across k_shk_bbar's lanes
+// income (hank_vjp_income; hank_income.h; never with shock): y_bar_t's partials in the same place (k_inc_ybar), then their reduction and
+// k_inc_ybar_out — P + 2 more: w.g_BI. The column masses (ensure_inc_mass) are current before the graph is launched.
 template <typename VT>
-static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, bool shock) {
+static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, bool shock, bool income = false) {
     const Consts &c = ctx->c;
-    const int P = c.P, M = w.N, MC = shk_mc(M);
+    const int P = c.P, M = w.N, MC = shk_mc(M), IMC = std::min(MC, INC_MC);
     hipStream_t s = ctx->own_stream;
     const dim3 blk(64 * c.n_e), grd((unsigned)w.g.nb, (unsigned)((w.g.MV + w.g.NC - 1) / w.g.NC));
     const size_t ldsB = adj_lds_egm(c, w.g, w.V);
@@ -2779,15 +2956,24 @@ static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, bool shock) {
         if (shock)
             hipLaunchKernelGGL(k_shk_bbar, dim3((unsigned)w.g.nb, (unsigned)((M + MC - 1) / MC)), dim3(SHK_BT), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->d_beta.get(), w.g.R, MC, t,
                                t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, w.bb_part.get() + (size_t)t * w.g.nb * M);
+        if (income)
+            hipLaunchKernelGGL(k_inc_ybar, dim3((unsigned)w.g.nb, (unsigned)((M + IMC - 1) / IMC)), dim3(INC_BT), inc_ybar_lds(c, w.g.R, IMC), s, c, ctx->R, ctx->d_xhh.get(),
+                               w.g.R, IMC, t, t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, w.yb_part.get() + (size_t)t * w.g.nb * c.n_e * M);
         cur ^= 1;
     }
     hipLaunchKernelGGL(k_adj_out, dim3((unsigned)((P * w.N + 255) / 256)), dim3(256), 0, s, P, c.n_hh, w.N, w.g.nb, ctx->d_xhh, w.partS, w.partM, w.yb1,
                        ctx->d_agg + P, ctx->d_zd, w.xbar);
+    if (income) {
+        const int W = c.n_e * M;
+        hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (unsigned)((W + 63) / 64)), dim3(256), 0, s, w.yb_part.get(), w.g.nb, W, w.yb_rm.get());
+        hipLaunchKernelGGL(k_inc_ybar_out, dim3((unsigned)(((size_t)P * c.n_e * M + 255) / 256)), dim3(256), 0, s, P, c.n_e, M, w.yb_rm.get(),
+                           ctx->d_inc_m.get(), w.yb1.get(), w.yb_cm.get());
+    }
     if (shock) {
         hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (unsigned)((M + 63) / 64)), dim3(256), 0, s, w.bb_part.get(), w.g.nb, M, w.bb_rm.get());
         hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w.bb_rm.get(), P, M, w.bb_cm.get());
     }
-    return end_capture(ctx, shock ? &w.g_BS : &w.g_B);
+    return end_capture(ctx, income ? &w.g_BI : shock ? &w.g_BS : &w.g_B);
 }
 template <typename VT>
 static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
@@ -2833,8 +3019,10 @@ static int ensure_hx_record(hank_ctx *ctx) {
 // grp_bar (hank_vjp_group; (P, K, M) column-major, where `kind` says): cotangents on the context's group outputs — Sweep A's graph
 // with the groups, and their direct terms after Sweep B; agg_bar may then be null (n_het = 0: no cotangent on outputs 0 and 1).
 // d_beta_bar (hank_vjp_shock; a device pointer, (P, M) column-major): the cotangent of the discount-factor path, reduced in Sweep B.
+// income (hank_vjp_income; never with shock): d_beta_bar is then y_bar, (n_e, P, M) column-major, the cotangent of the income path.
 static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out,
-                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr, const double *grp_bar = nullptr, double *d_beta_bar = nullptr, bool shock = false) {
+                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr, const double *grp_bar = nullptr, double *d_beta_bar = nullptr, bool shock = false,
+                       bool income = false) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
     const int NX = n_het > 2 ? n_het - 2 : 0, K = grp_bar ? ctx->grp.K : 0;
@@ -2863,11 +3051,23 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
         rc = w->V == 2 ? capture_cot_graph_b<double2>(ctx, *w, true) : capture_cot_graph_b<double>(ctx, *w, true);
         if (rc) return rc;
     }
+    if (income && inc_ybar_lds(c, w->g.R, std::min(shk_mc(M), INC_MC)) > ctx->lds_max)
+        return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_income: n_e=%d needs more LDS per workgroup than the device has", c.n_e);
+    if (income && !w->g_BI) {
+        if (!w->yb_cm) {
+            HIPC(ctx, w->yb_part.alloc(P * (size_t)w->g.nb * c.n_e * M));
+            HIPC(ctx, w->yb_rm.alloc(P * c.n_e * M));
+            HIPC(ctx, w->yb_cm.alloc(P * c.n_e * M));      // (last: a failed allocation is tried again by the next call)
+        }
+        rc = w->V == 2 ? capture_cot_graph_b<double2>(ctx, *w, false, true) : capture_cot_graph_b<double>(ctx, *w, false, true);
+        if (rc) return rc;
+    }
     hipStream_t s = ctx->stream;
     if (agg_bar) HIPC(ctx, hipMemcpyAsync(w->ybar, agg_bar, sizeof(double) * P * n_het * M, kind, s));
     if (K > 0) HIPC(ctx, hipMemcpyAsync(w->gin, grp_bar, sizeof(double) * P * K * M, kind, s));
     HIPC(ctx, join_side(ctx));      // D_t, the lottery and the grid aggregates come from the primal's forward sweep
     rc = ensure_adj_seg(ctx);
+    if (!rc && income) rc = ensure_inc_mass(ctx);
     if (rc) return rc;
     if (K > 0) {
         rc = ensure_grp_record(ctx);      // (before the capture, as below; the CONS sums read D_t)
@@ -2899,15 +3099,16 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((M + BND_T - 1) / BND_T), (unsigned)c.n_e);      // the layout kernel
     // Sweep A's state after its last launch (t = 0) is the cotangent of D_0; Sweep B's first launches overwrite it
     if (d_D0_bar) hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_D0_bar);
-    HIPC(ctx, hipGraphLaunch(shock ? w->g_BS : w->g_B, s));
+    HIPC(ctx, hipGraphLaunch(income ? w->g_BI : shock ? w->g_BS : w->g_B, s));
     if (d_vend_bar) {      // Sweep B's last launch (t = P-1) read mu_{P-1} from st[(P-1) & 1] and wrote no state: mu_P goes where it would have
         hipLaunchKernelGGL(k_bnd_vend, dim3((unsigned)(((size_t)c.n_a * M + 255) / 256)), dim3(256), 0, s, c, ctx->R, (int)P - 1, P == 1 ? 1 : 0, ctx->d_adj_sb.get(),
                            w->st[(P - 1) & 1].get(), w->pbar.get(), (size_t)M, w->st[P & 1].get());
         hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_vend_bar);
     }
     HIPC(ctx, hipGetLastError());
-    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1 + (d_D0_bar ? 1 : 0) + (d_vend_bar ? 2 : 0) + (shock ? (int)P + 2 : 0)));
-    if (d_beta_bar) HIPC(ctx, hipMemcpyAsync(d_beta_bar, w->bb_cm, sizeof(double) * P * M, hipMemcpyDeviceToDevice, s));
+    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1 + (d_D0_bar ? 1 : 0) + (d_vend_bar ? 2 : 0) + ((shock || income) ? (int)P + 2 : 0)));
+    if (d_beta_bar && income) HIPC(ctx, hipMemcpyAsync(d_beta_bar, w->yb_cm, sizeof(double) * P * c.n_e * M, hipMemcpyDeviceToDevice, s));
+    else if (d_beta_bar) HIPC(ctx, hipMemcpyAsync(d_beta_bar, w->bb_cm, sizeof(double) * P * M, hipMemcpyDeviceToDevice, s));
     if (NX > 0) {
         hipLaunchKernelGGL(k_adj_hx_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, NX, hx_count(ctx), w->ybx.get(),
                            ctx->hx.S.get(), w->xbar.get());
@@ -2940,6 +3141,7 @@ static int vjp_group_args(hank_ctx *ctx, int n_het, const void *in, int M, const
                     "come from hank_vjp_het and add linearly", n_het);
     if (!in && n_het != 0) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_group: n_het=%d without agg_bar (n_het must be 0 then)", n_het);
     if (ctx->grp.K == 0) return fail(ctx, HANK_ERR_NOT_READY, "hank_vjp_group: no groups are set: call hank_set_group_outputs first");
+    { const int irc = income_refuses(ctx, "hank_vjp_group"); if (irc) return irc; }
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp_group");
     return HANK_OK;
 }
@@ -2947,7 +3149,8 @@ static int vjp_group_args(hank_ctx *ctx, int n_het, const void *in, int M, const
 // hank_vjp_het's rules: the family's count, then the declared count (the rule of hank_get_het_outputs), then the record
 static int vjp_het_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out) {
     if (!ctx || !in || !out || M < 1) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_het: bad argument (M=%d)", M);
-    const int rc = het_count_ok(ctx, "hank_vjp_het", n_het, true);
+    int rc = het_count_ok(ctx, "hank_vjp_het", n_het, true);
+    if (!rc) rc = income_refuses(ctx, "hank_vjp_het");
     if (rc) return rc;
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_vjp_het");
     return HANK_OK;
@@ -3003,11 +3206,33 @@ static int vjp_shock(hank_ctx *ctx, int n_het, const double *agg_bar, int M, dou
     return HANK_OK;
 }
 
+// hank_vjp_income[_dev]: hank_vjp's rule and work (n_het 1 or 2), Sweep B from the graph with y_bar's reduction
+static int vjp_income(hank_ctx *ctx, int n_het, const double *agg_bar, int M, double *xhh_bar, double *y_bar, bool dev) {
+    ENTER(ctx);
+    if (ctx && !y_bar) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_income: y_bar is required");
+    int rc = vjp_args(ctx, n_het, agg_bar, M, xhh_bar);
+    if (rc) return rc;
+    if (ctx->beta_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_vjp_income: a discount-factor path is set and the two exclude each other");
+    CotWork *w = nullptr;
+    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, nullptr, nullptr, nullptr, y_bar, false, true);
+    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, nullptr, nullptr, nullptr, nullptr, false, true);
+    if (rc) return rc;
+    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(y_bar, w->yb_cm, sizeof(double) * ctx->c.P * ctx->c.n_e * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->errmsg[0] = 0;
+    return HANK_OK;
+}
+
 extern "C" {
+// (KrusellSmith.jl:59-62, :66-80: where y enters; BackwardIteration.jl:90-113: the loop the transposed sweep reverses)
+int hank_vjp_income(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *y_bar) { return vjp_income(ctx, n_het, agg_bar, M, xhh_bar, y_bar, false); }
+int hank_vjp_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_y_bar) { return vjp_income(ctx, n_het, d_agg_bar, M, d_xhh_bar, d_y_bar, true); }
 // (KrusellSmith.jl:59-62: where beta enters; BackwardIteration.jl:90-113: the loop the transposed sweep reverses)
 int hank_vjp_shock(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *beta_bar) { return vjp_shock(ctx, n_het, agg_bar, M, xhh_bar, beta_bar, false); }
 int hank_vjp_shock_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_beta_bar) { return vjp_shock(ctx, n_het, d_agg_bar, M, d_xhh_bar, d_beta_bar, true); }
 int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar) {
+    { const int irc = income_refuses(ctx, "hank_vjp_boundary"); if (irc) return irc; }
     return vjp_boundary(ctx, vjp_args, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);
 }
 // (KrusellSmith.jl:80: Value and UCE are keys of the plugin's NamedTuple; BackwardIteration.jl:85, ForwardIteration.jl:293: the boundary)
@@ -3018,6 +3243,7 @@ int hank_vjp_het_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, i
     return vjp_boundary(ctx, vjp_het_args, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false);
 }
 int hank_vjp_boundary(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *value_end_bar, double *D_init_bar) {
+    { const int irc = income_refuses(ctx, "hank_vjp_boundary"); if (irc) return irc; }
     return vjp_boundary(ctx, vjp_args, n_het, agg_bar, M, xhh_bar, value_end_bar, D_init_bar, false);
 }
 // (ForwardIteration.jl:303-307: the weighted dot; :339-420 on :131-192: the reverse rules; BackwardIteration.jl:85, ForwardIteration.jl:293: the exports)
@@ -3178,10 +3404,15 @@ static int assemble_het_outputs(hank_ctx *ctx, int n_het, int Nk, const double *
     return HANK_OK;
 }
 
-static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double *agg_out, double *dagg_out, bool dev) {
+// income (hank_get_het_outputs_income; n_het <= 2): dy (n_e, P, N) column-major, the income directions of the batch hank_jvp_income made, or
+// null — consumption's tangent gains sum_e dy_t[e,n] m_t[e]. Its level gains sum_e y_t[e] m_t[e] whenever a path is set, in either entry.
+static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double *agg_out, double *dagg_out, bool dev, const double *dy = nullptr,
+                       bool income = false) {
     if (!ctx) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
-    int rc = het_count_ok(ctx, "hank_get_het_outputs", n_het, true, N >= 0 && (agg_out || dagg_out));      // (N >= 0, an output array)
+    const char *who = income ? "hank_get_het_outputs_income" : "hank_get_het_outputs";
+    int rc = het_count_ok(ctx, who, n_het, true, N >= 0 && (agg_out || dagg_out) && !(income && n_het > 2));      // (N >= 0, an output array)
+    if (!rc && n_het > 2) rc = income_refuses(ctx, who);      // (Value and UCE rebuild c from the inputs)
     if (rc) return rc;
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
     const size_t P = ctx->c.P, nh = ctx->c.n_hh;
@@ -3191,6 +3422,9 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
     if (tan) {
         rc = batch_current(ctx, N, &b);
         if (rc) return rc;
+        if (b->inc_dy && n_het > 2)
+            return fail(ctx, HANK_ERR_NOT_READY, "%s: the current tangent batch carries income directions (hank_jvp_income), under which only outputs 0 and 1 "
+                        "have tangents (Value and UCE rebuild c from the inputs): n_het = %d is served again after hank_jvp", who, n_het);
         if (b->boundary && n_het > 2)
             return fail(ctx, HANK_ERR_NOT_READY, "hank_get_het_outputs: the current tangent batch carries boundary seeds (hank_jvp_boundary), under which only outputs 0 and 1 "
                         "have tangents (Value and UCE assume dD_0 = 0): n_het = %d is served again after hank_jvp", n_het);
@@ -3206,9 +3440,15 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
             HIPC(ctx, hipMemcpyAsync(tmp, dxhh, sizeof(double) * nh * P * N, hipMemcpyHostToDevice, ctx->stream));
             d_dx = tmp;
             HIPC(ctx, sc.alloc(&d_da, P * n_het * N));
+            if (dy) {
+                HIPC(ctx, sc.alloc(&tmp, P * ctx->c.n_e * N));
+                HIPC(ctx, hipMemcpyAsync(tmp, dy, sizeof(double) * P * ctx->c.n_e * N, hipMemcpyHostToDevice, ctx->stream));
+                dy = tmp;
+            }
         }
         if (agg_out) HIPC(ctx, sc.alloc(&d_a, P * n_het));
     }
+    if (tan && !dy) dy = b->inc_dy;      // no dy from the caller: the batch's own (a device pointer; null for a batch without income directions)
     const int Nk = tan ? N : 0;
     double *hxT = nullptr;
     if (n_het > 2) {
@@ -3218,6 +3458,13 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
     // (a batch with boundary seeds is served for n_het <= 2 only, above)
     rc = assemble_het_outputs(ctx, n_het, Nk, d_dx, b ? b->dagg_cm : nullptr, hxT, b ? b->bnd_zm : nullptr, d_a, tan ? d_da : nullptr);
     if (rc) return rc;
+    if (n_het == 2 && (ctx->inc_on || (tan && dy))) {      // the direct term of y_t[e] in consumption (hank_income.h)
+        rc = ensure_inc_mass(ctx);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_inc_cons, dim3((unsigned)((P * ((size_t)Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, ctx->c.n_e, Nk,
+                           ctx->inc_on ? ctx->d_y.get() : (const double *)nullptr, tan ? dy : (const double *)nullptr, ctx->d_inc_m.get(), d_a, tan ? d_da : nullptr);
+        HIPC(ctx, hipGetLastError());
+    }
     if (!dev) {
         if (agg_out) HIPC(ctx, hipMemcpyAsync(agg_out, d_a, sizeof(double) * P * n_het, hipMemcpyDeviceToHost, ctx->stream));
         if (tan) HIPC(ctx, hipMemcpyAsync(dagg_out, d_da, sizeof(double) * P * n_het * N, hipMemcpyDeviceToHost, ctx->stream));
@@ -3231,6 +3478,13 @@ int hank_get_het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32
 }
 int hank_get_het_outputs_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, int32_t N, double *d_agg_out, double *d_dagg_out) {
     return het_outputs(ctx, n_het, d_dxhh, N, d_agg_out, d_dagg_out, true);
+}
+// (KrusellSmith.jl:80: consumption is the budget residual, which gains y_t[e]; ForwardIteration.jl:303-307: the weighted dot)
+int hank_get_het_outputs_income(hank_ctx *ctx, int32_t n_het, const double *dxhh, const double *dy, int32_t N, double *agg_out, double *dagg_out) {
+    return het_outputs(ctx, n_het, dxhh, N, agg_out, dagg_out, false, dy, true);
+}
+int hank_get_het_outputs_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const double *d_dy, int32_t N, double *d_agg_out, double *d_dagg_out) {
+    return het_outputs(ctx, n_het, d_dxhh, N, d_agg_out, d_dagg_out, true, d_dy, true);
 }
 int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het) {
     if (!ctx) return HANK_ERR_BAD_ARG;
@@ -3310,6 +3564,9 @@ static int group_outputs(hank_ctx *ctx, const double *dxhh, int32_t N, double *a
     if (N < 0 || !(agg_out || dagg_out)) return fail(ctx, HANK_ERR_BAD_ARG, "hank_get_group_outputs: bad argument: N must be >= 0 and an output array given");
     const int K = ctx->grp.K;
     if (K == 0) return fail(ctx, HANK_ERR_NOT_READY, "hank_get_group_outputs: no groups are set: call hank_set_group_outputs first");
+    if (ctx->inc_on)      // (a consumption group rebuilds c from the inputs)
+        for (int k = 0; k < K; k++)
+            if (((ctx->grp.codes >> (2 * k)) & 3) == HANK_GROUP_CONS) return income_refuses(ctx, "hank_get_group_outputs with a HANK_GROUP_CONS group");
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
     const size_t P = ctx->c.P, nh = ctx->c.n_hh;
     const bool tan = dagg_out && N > 0;
@@ -3318,6 +3575,11 @@ static int group_outputs(hank_ctx *ctx, const double *dxhh, int32_t N, double *a
     if (tan) {
         int rc = batch_current(ctx, N, &b);
         if (rc) return rc;
+        if (b->inc_dy)
+            for (int k = 0; k < K; k++)
+                if (((ctx->grp.codes >> (2 * k)) & 3) == HANK_GROUP_CONS)
+                    return fail(ctx, HANK_ERR_NOT_READY, "hank_get_group_outputs: the current tangent batch carries income directions (hank_jvp_income) and a HANK_GROUP_CONS "
+                                "group rebuilds c from the inputs: its tangent is served again after hank_jvp");
         if (b->boundary)
             return fail(ctx, HANK_ERR_NOT_READY, "hank_get_group_outputs: the current tangent batch carries boundary seeds (hank_jvp_boundary); the group tangents "
                         "assume dD_0 = 0 and are served again after hank_jvp");

@@ -41,6 +41,8 @@ ABI_SYMBOLS = (
     "hank_set_group_outputs", "hank_get_group_outputs", "hank_get_group_outputs_dev", "hank_fake_news_group",
     "hank_vjp_group", "hank_vjp_group_dev",
     "hank_set_discount_path", "hank_jvp_shock", "hank_jvp_shock_dev", "hank_vjp_shock", "hank_vjp_shock_dev", "hank_fake_news_shock",
+    "hank_set_income_path", "hank_jvp_income", "hank_jvp_income_dev", "hank_vjp_income", "hank_vjp_income_dev", "hank_fake_news_income",
+    "hank_get_het_outputs_income", "hank_get_het_outputs_income_dev",
 )
 
 
@@ -172,6 +174,14 @@ def load_library() -> C.CDLL:
     lib.hank_vjp_shock.argtypes = [vp, i32, dp, i32, dp, dp]
     lib.hank_vjp_shock_dev.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.hank_fake_news_shock.argtypes = [vp, i32, dp, dp]
+    lib.hank_set_income_path.argtypes = [vp, dp]
+    lib.hank_jvp_income.argtypes = [vp, dp, dp, i32, dp]
+    lib.hank_jvp_income_dev.argtypes = [vp, vp, vp, i32, vp]
+    lib.hank_vjp_income.argtypes = [vp, i32, dp, i32, dp, dp]
+    lib.hank_vjp_income_dev.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.hank_fake_news_income.argtypes = [vp, i32, dp, dp]
+    lib.hank_get_het_outputs_income.argtypes = [vp, i32, dp, dp, i32, dp, dp]
+    lib.hank_get_het_outputs_income_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     for name in ABI_SYMBOLS:
         if name in ("hank_get_lottery_record", "hank_get_forward_units") and not hasattr(lib, name):
             continue
@@ -242,6 +252,7 @@ class HouseholdBlock:
         self._params = (float(beta), float(gamma), float(borrow_cons), value_fn_id)
         self._boundary = None
         self.discount_path = None      # the beta_t path in force (set_discount_path), or None: the model's constant beta
+        self.income_path = None        # the y_t[e] path in force (set_income_path), or None
         m = hank_model(self.n_a, self.n_e, self.T, value_fn_id, _p(self.a_grid), _p(self.z_grid),
                        _p(self.Pi), float(beta), float(gamma), float(borrow_cons))
         if device is None:
@@ -277,6 +288,8 @@ class HouseholdBlock:
             other.set_boundary(*self._boundary)
         if self.discount_path is not None:
             other.set_discount_path(self.discount_path)
+        if self.income_path is not None:
+            other.set_income_path(self.income_path)
         return other
 
     def close(self):
@@ -373,6 +386,79 @@ class HouseholdBlock:
         F = np.empty((self.P, self.P, nh), order="F")
         Dv = np.empty((self.P, nh), order="F")
         self._chk(self._lib.hank_fake_news_shock(self._ctx, int(n_het), _p(F), _p(Dv)))
+        return F, Dv
+
+    # -- the income path by productivity state ------------------------------------------------
+    def set_income_path(self, y):
+        """a path y (n_e, P) of additive income by productivity state (hank_set_income_path): the budget of period t is
+        c + a' = (1 + r_t) a + w_t z_e + tr_t + y_t[e]. None clears it. Like a new boundary it drops the record: the next tangent
+        sweep needs a primal first. While a path is set every sweep runs on the per-period launches and the entries that rebuild
+        consumption from the inputs or are defined at one income process are refused; it excludes a discount-factor path."""
+        if y is None:
+            self._chk(self._lib.hank_set_income_path(self._ctx, None))
+            self.income_path = None
+            return
+        yy = _f(y, (self.n_e, self.P))
+        self._chk(self._lib.hank_set_income_path(self._ctx, _p(yy)))
+        self.income_path = yy.copy(order="F")
+
+    def _income_dirs(self, dxhh, dy):
+        """the directions of `jvp_income`: dxhh (n_hh, P[, N]) or None, dy (n_e, P[, N]) or None -> (N, dx, dy) column-major"""
+        if dxhh is None and dy is None:
+            raise ValueError("at least one of dxhh, dy must be given")
+        dx = d = None
+        if dxhh is not None:
+            dx = np.asarray(dxhh, dtype=np.float64)
+            dx = dx[:, :, None] if dx.ndim == 2 else dx
+            N = dx.shape[2]
+        if dy is not None:
+            d = np.asarray(dy, dtype=np.float64)
+            d = d[:, :, None] if d.ndim == 2 else d
+            N = d.shape[2] if dx is None else N
+            d = _f(d, (self.n_e, self.P, N))
+        if dx is not None:
+            dx = _f(dx, (self.n_hh, self.P, N))
+        return N, dx, d
+
+    def jvp_income(self, dxhh=None, dy=None) -> np.ndarray:
+        """the tangent sweeps with seeds in the income path as well (hank_jvp_income): dxhh (n_hh, P, N) as in `jvp`, dy (n_e, P)
+        or (n_e, P, N); None means zeros, at least one must be given. -> dagg (P, N). Works with or without a path set; always the
+        launch family. The batch is current afterwards as `jvp`'s is: `dpolicy_seq`, `grid_aggregates`, `group_outputs` (mass and
+        policy bases) and `het_outputs(n_het, dxhh)` serve it — y has a direct term in consumption, which `het_outputs` adds from
+        the dy the batch carries (or from a `dy=` of the caller's); Value, UCE and consumption groups have no tangent at such a batch."""
+        N, dx, d = self._income_dirs(dxhh, dy)
+        out = np.empty((self.P, N), order="F")
+        self.calls["jvp"] += 1
+        self._chk(self._lib.hank_jvp_income(self._ctx, _opt(dx), _opt(d), N, _p(out)))
+        return out
+
+    def jvp_income_dev(self, d_dxhh_ptr: int, d_dy_ptr: int, N: int, d_dagg_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
+        self._chk(self._lib.hank_jvp_income_dev(self._ctx, C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dy_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+
+    def vjp_income(self, agg_bar, n_het: int = 1):
+        """`vjp` with the cotangent of the income path (hank_vjp_income): agg_bar as in `vjp` -> (xhh_bar (n_hh, P, M), y_bar
+        (n_e, P, M)); the exact transpose of `jvp_income` followed by `het_outputs(n_het, dxhh, dy=dy)`. xhh_bar equals `vjp`'s bit
+        for bit; y_bar is a fixed-order reduction (the same inputs give the same bits)."""
+        M, yb = self._cotangents(agg_bar, n_het, het=False)
+        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
+        ybar = np.empty((self.n_e, self.P, max(M, 1)), order="F")
+        self._chk(self._lib.hank_vjp_income(self._ctx, int(n_het), _p(yb), M, _p(out), _p(ybar)))
+        return out, ybar
+
+    def vjp_income_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_y_bar_ptr: int):
+        """device-pointer form (asynchronous on the context's stream)."""
+        self._chk(self._lib.hank_vjp_income_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr), C.c_void_p(d_y_bar_ptr)))
+
+    def fake_news_income(self, n_het: int):
+        """the Toeplitz form of the Jacobian of outputs 0 .. n_het-1 (n_het <= 2) with respect to the income path at the steady
+        state (hank_fake_news_income): -> (F (P, P, n_e, n_het), Dv (P, n_e, n_het)), the definitions of `fake_news_het` with the
+        input fixed to y[e]. `SteadyStateJacobian.income_jacobian` does the recursion. Same precondition as `fake_news`; no path
+        may be set."""
+        nh = max(int(n_het), 1)
+        F = np.empty((self.P, self.P, self.n_e, nh), order="F")
+        Dv = np.empty((self.P, self.n_e, nh), order="F")
+        self._chk(self._lib.hank_fake_news_income(self._ctx, int(n_het), _p(F), _p(Dv)))
         return F, Dv
 
     def primal(self, xhh) -> np.ndarray:
@@ -797,12 +883,21 @@ class HouseholdBlock:
         self._chk(self._lib.hank_get_dpolicy_seq(self._ctx, int(N), _p(out)))
         return out
 
-    def het_outputs(self, n_het: int = 2, dxhh=None):
+    def het_outputs(self, n_het: int = 2, dxhh=None, dy=None):
         """every heterogeneous variable's aggregate of the last sweeps (hank_get_het_outputs; ForwardIteration.jl:303-307):
         output 0 the policy variable (KD / A), output 1 consumption, output 2 Value, output 3 UCE (one-asset HANK), up to the
         count declared with `set_het_outputs`. -> agg (P, n_het), and dagg (P, n_het, N) when `dxhh`
-        (n_hh, P, N) — the input of the last tangent sweep — is given (else None)."""
+        (n_hh, P, N) — the input of the last tangent sweep — is given (else None). dy (n_e, P, N): income directions
+        (hank_get_het_outputs_income, n_het <= 2) for consumption's direct term, in place of the ones a batch of `jvp_income`
+        carries and adds by itself; dxhh may then be None (zeros)."""
         agg = np.empty((self.P, n_het), order="F")
+        if dy is not None:
+            N, dx, d = self._income_dirs(dxhh, dy)
+            if dx is None:
+                dx = np.zeros((self.n_hh, self.P, N), order="F")
+            dagg = np.empty((self.P, n_het, N), order="F")
+            self._chk(self._lib.hank_get_het_outputs_income(self._ctx, int(n_het), _p(dx), _p(d), N, _p(agg), _p(dagg)))
+            return agg, dagg
         if dxhh is None:
             self._chk(self._lib.hank_get_het_outputs(self._ctx, int(n_het), None, 0, _p(agg), None))
             return agg, None
@@ -819,8 +914,11 @@ class HouseholdBlock:
         self._chk(self._lib.hank_set_het_outputs(self._ctx, int(n_het)))
         self._n_het_declared = int(n_het)
 
-    def het_outputs_dev(self, n_het: int, d_dxhh: int, N: int, d_agg: int, d_dagg: int):
-        """device-pointer form (asynchronous on the context's stream)."""
+    def het_outputs_dev(self, n_het: int, d_dxhh: int, N: int, d_agg: int, d_dagg: int, d_dy: int = 0):
+        """device-pointer form (asynchronous on the context's stream); d_dy: the income directions (hank_get_het_outputs_income_dev)."""
+        if d_dy:
+            self._chk(self._lib.hank_get_het_outputs_income_dev(self._ctx, int(n_het), d_dxhh or None, d_dy, int(N), d_agg or None, d_dagg or None))
+            return
         self._chk(self._lib.hank_get_het_outputs_dev(self._ctx, int(n_het), d_dxhh or None, int(N), d_agg or None, d_dagg or None))
 
     def grid_aggregates(self, N: int = 0):

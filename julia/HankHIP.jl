@@ -597,3 +597,69 @@ function shock_jacobian_toeplitz(ctx::HankCtx, n_het::Integer)
     _check(ctx.ptr, ccall((:hank_fake_news_shock, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), ctx.ptr, Int32(n_het), F, Dv))
     return _toeplitz_recursion(F, Dv)
 end
+
+# ---- a path of income by productivity state (hank_set_income_path, hank_jvp_income, hank_vjp_income, hank_fake_news_income) -------
+# y[e, t] is the additive income of productivity state e in period t's budget, c + a' = (1 + r_t) a + w_t z_e + tr_t + y_t[e]
+# (KrusellSmith.jl:59-62 and :66-80 inside the loop of BackwardIteration.jl:90-113). The reference has no such path: its income
+# process is a constant of the model. `nothing` clears it. Like a new boundary, a new path drops the record; it excludes a
+# discount-factor path.
+function hank_set_income_path(ctx::HankCtx, y::Union{Nothing,AbstractMatrix{<:Real}})
+    if y === nothing
+        _check(ctx.ptr, ccall((:hank_set_income_path, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}), ctx.ptr, C_NULL))
+    else
+        size(y) == (ctx.n_e, ctx.P) || error("y must be (n_e, P) = ($(ctx.n_e), $(ctx.P)), got $(size(y))")
+        yy = Matrix{Float64}(y)
+        _check(ctx.ptr, ccall((:hank_set_income_path, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}), ctx.ptr, yy))
+    end
+    return ctx
+end
+
+# dagg (P, N) under directions dxhh (n_hh, P, N) in the household inputs and dy (n_e, P, N) in the path, either `nothing` (zeros),
+# at the recorded primal; the batch is current afterwards as hank_jvp's is. y has a direct term in consumption: pass the same dy to
+# hank_het_outputs_income.
+function hank_jvp_income(ctx::HankCtx, dxhh::Union{Nothing,Array{Float64,3}}, dy::Union{Nothing,Array{Float64,3}})
+    (dxhh === nothing && dy === nothing) && error("at least one of dxhh, dy must be given")
+    N = dxhh === nothing ? size(dy, 3) : size(dxhh, 3)
+    dxhh === nothing || size(dxhh) == (length(ctx.hh_rows), ctx.P, N) || error("dxhh must be (n_hh, P, N)")
+    dy === nothing || size(dy) == (ctx.n_e, ctx.P, N) || error("dy must be (n_e, P, N) = ($(ctx.n_e), $(ctx.P), $N), got $(size(dy))")
+    dagg = Matrix{Float64}(undef, ctx.P, N)
+    _check(ctx.ptr, ccall((:hank_jvp_income, LIBHANK), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}),
+                          ctx.ptr, dxhh === nothing ? C_NULL : dxhh, dy === nothing ? C_NULL : dy, Int32(N), dagg))
+    return dagg
+end
+
+# (agg (P, n_het), dagg (P, n_het, N)) for n_het <= 2 with the direct term of the income directions in consumption's tangent
+# (dy `nothing`: the ones the current batch carries, if any)
+function hank_het_outputs_income(ctx::HankCtx, n_het::Integer, dxhh::Array{Float64,3}, dy::Union{Nothing,Array{Float64,3}})
+    N = size(dxhh, 3)
+    size(dxhh) == (length(ctx.hh_rows), ctx.P, N) || error("dxhh must be (n_hh, P, N)")
+    dy === nothing || size(dy) == (ctx.n_e, ctx.P, N) || error("dy must be (n_e, P, N) = ($(ctx.n_e), $(ctx.P), $N), got $(size(dy))")
+    agg = Matrix{Float64}(undef, ctx.P, n_het); dagg = Array{Float64}(undef, ctx.P, n_het, N)
+    _check(ctx.ptr, ccall((:hank_get_het_outputs_income, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                          ctx.ptr, Int32(n_het), dxhh, dy === nothing ? C_NULL : dy, Int32(N), agg, dagg))
+    return agg, dagg
+end
+
+# hank_vjp! with the cotangent of the path: agg_bar (P, n_het, M), n_het 1 or 2 -> (xhh_bar (n_hh, P, M), y_bar (n_e, P, M)); the
+# exact transpose of hank_jvp_income followed by hank_het_outputs_income
+function hank_vjp_income!(xhh_bar::Array{Float64,3}, y_bar::Array{Float64,3}, ctx::HankCtx, agg_bar::Array{Float64,3})
+    P, n_het, M = size(agg_bar)
+    @assert P == ctx.P && size(xhh_bar) == (length(ctx.hh_rows), P, M) && size(y_bar) == (ctx.n_e, P, M)
+    _check(ctx.ptr, ccall((:hank_vjp_income, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                          ctx.ptr, Int32(n_het), agg_bar, Int32(M), xhh_bar, y_bar))
+    return xhh_bar, y_bar
+end
+
+# J[t, s, e, o] = d Y^o_t / d y_s[e] for the first n_het (1 or 2) outputs at the stationary primal the context holds
+# (household_jacobian_toeplitz's precondition, and no path set), from the recursion of SteadyStateJacobian.jl:363-371 with the input
+# fixed to y[e]
+function income_jacobian_toeplitz(ctx::HankCtx, n_het::Integer)
+    P, n_e = ctx.P, ctx.n_e
+    F = Array{Float64}(undef, P, P, n_e, n_het); Dv = Array{Float64}(undef, P, n_e, n_het)
+    _check(ctx.ptr, ccall((:hank_fake_news_income, LIBHANK), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), ctx.ptr, Int32(n_het), F, Dv))
+    J = Array{Float64}(undef, P, P, n_e, n_het)
+    for o in 1:n_het
+        J[:, :, :, o] = _toeplitz_recursion(F[:, :, :, o], Dv[:, :, o])
+    end
+    return J
+end

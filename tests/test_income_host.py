@@ -1,0 +1,163 @@
+"""CPU tests of the income path's references and host layers (no GPU):
+1. tests/income_refs.oracle_income_sweeps — the oracle's EGM step run once per productivity state with the dual transfer
+   (tr_t + y_t[e], dtr_t + dy_t[e]), the columns assembled — against a central difference of ITS OWN level in entries of y_0 and
+   y_{P-1} (the step and the agreement of tests/test_shock_host.py: 1e-6, 1e-6 relative);
+2. a path of zeros reproduces sweep_refs.oracle_sweeps exactly;
+3. the dense pair (Jx, Jy) against the sweeps with random seeds in the inputs and in y together, and its transpose;
+4. hank_amd.incidence: the zero-sum property, the z-path's tangent against a difference, the incidence rule's normalisation;
+5. SteadyStateJacobian.income_jacobian's recursion on a stand-in block;
+6. examples/solve_hank.py's arguments."""
+import numpy as np
+import pytest
+
+import income_refs as R
+import sweep_refs
+from cases import close, jt
+from test_shock_host import STEP
+
+
+@pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 4), ("hank", "gamma1.5", 33, 2, 4), ("ks", "gamma1", 33, 2, 2),
+                                                  ("hank", "gamma3", 130, 3, 12)])
+def test_the_reference_s_income_tangent_is_the_derivative_of_its_own_level(oracle_mod, family, name, n_a, n_e, T):
+    c = R.income_case(family, name, n_a, n_e, T)
+    P = T - 1
+    entries = sorted({(0, 0), (n_e - 1, P - 1), (n_e - 1, 0)})          # (state, period)
+    dy = np.zeros((n_e, P, len(entries)))
+    for k, (e, t) in enumerate(entries):
+        dy[e, t, k] = 1.0
+    args = (c["orc"], c["x"], c["V"], c["D"])
+    ref = R.oracle_income_sweeps(*args, c["y"], dy=dy)
+    for k, (e, t) in enumerate(entries):
+        lv = []
+        for sgn in (1.0, -1.0):
+            y = c["y"].copy()
+            y[e, t] += sgn * STEP
+            lv.append(R.oracle_income_sweeps(*args, y))
+        what = f"{family} {name} {n_a}x{n_e} T={T} y_{t}[{e}]"
+        fd_agg = (lv[0]["agg"] - lv[1]["agg"]) / (2 * STEP)
+        fd_pol = (lv[0]["pol"] - lv[1]["pol"]) / (2 * STEP)
+        assert np.abs(fd_agg).max() > 1e-3, what
+        for o in range(2):
+            close(ref["dagg"][:, o, k], fd_agg[:, o], rel=1e-6, ab=0.0, what=f"{what} output {o}")
+        close(ref["dpol"][..., k], fd_pol, rel=1e-6, ab=0.0, what=f"{what} policy")
+        assert not np.any(ref["dpol"][t + 1:, ..., k])                   # y_t moves no policy after t
+        assert np.any(ref["dpol"][t, :, e, k])
+
+
+@pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 4), ("hank", "gamma2", 130, 3, 12)])
+def test_a_path_of_zeros_is_the_oracle_s_own_loop(oracle_mod, family, name, n_a, n_e, T):
+    c = R.income_case(family, name, n_a, n_e, T)
+    dx, _ = R.income_seeds(c, 3, 1)
+    ref = R.oracle_income_sweeps(c["orc"], c["x"], c["V"], c["D"], np.zeros_like(c["y"]), dx=dx)
+    own = sweep_refs.oracle_sweeps(c["orc"], c["x"], c["V"], c["D"], c["gamma"], 2, y=dx)
+    for k in ("agg", "dagg", "agg2", "dagg2", "pol", "dpol"):
+        assert np.array_equal(ref[k], own[k]), (family, name, k, np.abs(ref[k] - own[k]).max())
+    moved = R.oracle_income_sweeps(c["orc"], c["x"], c["V"], c["D"], c["y"])
+    assert np.abs(moved["pol"] - own["pol"]).max() > 1e-3                # (the path moves the policy)
+    close(moved["mass"].sum(axis=1), np.ones(T - 1), what="the column masses sum to one")
+
+
+@pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 12), ("hank", "gamma1", 130, 3, 4)])
+def test_the_dense_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, family, name, n_a, n_e, T):
+    """(Jx, Jy) against oracle_income_sweeps with random dx and dy together: the map is linear, so the two agree to rounding (1e-13
+    of the largest entry)"""
+    c = R.income_case(family, name, n_a, n_e, T)
+    n_hh, P = c["x"].shape
+    args = (c["orc"], c["x"], c["V"], c["D"], c["y"])
+    Jx, Jy = J = R.oracle_income_jacobians(*args)
+    assert Jx.shape == (2, P, n_hh, P) and Jy.shape == (P, 2, n_e, P)
+    assert R._unit_sweeps(*args)[1] is R._unit_sweeps(*args)[1]                    # (the sweeps ran once)
+    rng = np.random.default_rng(P)
+    dx, dy = rng.standard_normal((n_hh, P, 5)), rng.standard_normal((n_e, P, 5))
+    ref = R.oracle_income_sweeps(*args, dx=dx, dy=dy)
+    lin = R.income_linear(J, dx, dy)
+    for o in range(2):
+        close(lin[:, o, :], ref["dagg"][:, o, :], rel=1e-13, ab=0.0, what=f"{family} {name} output {o}")
+    # the budget, aggregated: dC_t + dA'_t - (1 + r_t) d(sum a D_t) = the direct term, the column mass m_t[e] at s = t and nothing else
+    sy = R._unit_sweeps(*args)[1]
+    J2y = sy["dagg2"].reshape(P, P, n_e).transpose(0, 2, 1)                        # [t, e, s]
+    direct = Jy[:, 0] + Jy[:, 1] - (1.0 + c["x"][0])[:, None, None] * J2y
+    want = np.zeros((P, n_e, P))
+    want[np.arange(P), :, np.arange(P)] = sy["mass"]
+    close(direct, want, rel=1e-12, ab=0.0, what=f"{family} {name} direct term")
+    yb = rng.standard_normal((P, 2, 4))
+    lhs = np.einsum("tom,ton->mn", yb, lin)
+    rhs = np.einsum("ksm,ksn->mn", jt(Jx, yb), dx) + np.einsum("esm,esn->mn", R.income_y_bar(Jy, yb), dy)
+    scale = np.einsum("tom,ton->mn", np.abs(yb), R.income_linear((np.abs(Jx), np.abs(Jy)), np.abs(dx), np.abs(dy)))
+    assert np.all(np.abs(lhs - rhs) <= 1e-13 * scale), np.max(np.abs(lhs - rhs) / scale)
+
+
+def test_redistribution_is_zero_sum_and_a_transfer_reaches_its_states_alone(hank):
+    from hank_amd import incidence as I
+    rng = np.random.default_rng(3)
+    n_e, P = 5, 7
+    m = rng.uniform(0.1, 1.0, (n_e, P))
+    m /= m.sum(axis=0, keepdims=True)
+    y = I.redistribution(m, [0, 1], 0.02, 0.8)
+    assert y.shape == (n_e, P)
+    assert np.abs((m * y).sum(axis=0)).max() <= 1e-17
+    assert np.array_equal(y[0], 0.02 * 0.8 ** np.arange(P)) and np.array_equal(y[0], y[1]) and np.all(y[2:] < 0)
+    assert np.array_equal(y[2], y[3]) and np.array_equal(y[3], y[4])
+    tr = I.targeted_transfer(n_e, P, [0, 3], 0.01, 0.5)
+    assert np.array_equal(tr[0], 0.01 * 0.5 ** np.arange(P)) and np.array_equal(tr[3], tr[0]) and not np.any(tr[[1, 2, 4]])
+    for bad in ([], list(range(n_e))):
+        with pytest.raises(ValueError):
+            I.redistribution(m, bad, 0.02, 0.8)
+    with pytest.raises(ValueError):
+        I.redistribution(m[:, 0], [0], 0.02, 0.8)
+
+
+def test_the_z_path_s_tangent_is_the_derivative_of_its_income_and_the_incidence_keeps_the_mean(hank):
+    from hank_amd import incidence as I
+    rng = np.random.default_rng(5)
+    n_e, P, N = 4, 6, 3
+    z = np.linspace(0.4, 1.8, n_e)
+    pi = rng.uniform(0.1, 1.0, n_e); pi /= pi.sum()
+    z = z / (pi @ z)
+    Y = 1.0 + 0.03 * np.cos(np.arange(P))
+    z_t = I.incidence(z, pi, Y, 0.7)
+    assert z_t.shape == (n_e, P)
+    close(pi @ z_t, np.ones(P), rel=1e-15, ab=0.0, what="the incidence rule keeps the mean at one")
+    assert np.array_equal(I.incidence(z, pi, np.ones(P), 0.7), np.tile(z[:, None], (1, P)) * ((pi @ z) / (pi @ np.tile(z[:, None], (1, P))))[None, :])
+    hi = Y > 1.0
+    assert np.all(z_t[-1, hi] > z[-1]) and np.all(z_t[0, hi] < z[0])       # zeta > 0: a boom spreads earnings
+    w = 1.0 + 0.1 * rng.standard_normal(P)
+    y = I.z_path_to_income(z, z_t, w)
+    close(y, w[None, :] * (z_t - z[:, None]), rel=1e-16, ab=0.0, what="y = w (z_t - z)")
+    dz, dw = rng.standard_normal((n_e, P, N)), rng.standard_normal((P, N))
+    dy = I.z_path_to_income_tangent(z, z_t, w, dz, dw)
+    h = 1e-6
+    for n in range(N):
+        fd = (I.z_path_to_income(z, z_t + h * dz[..., n], w + h * dw[:, n]) - I.z_path_to_income(z, z_t - h * dz[..., n], w - h * dw[:, n])) / (2 * h)
+        close(dy[..., n], fd, rel=1e-9, ab=0.0, what=f"direction {n}")       # (y is bilinear: the central difference is exact to rounding)
+    close(I.z_path_to_income_tangent(z, z_t, w, dz, None) + I.z_path_to_income_tangent(z, z_t, w, None, dw), dy, rel=1e-15, ab=0.0, what="the parts add")
+
+
+def test_income_jacobian_is_the_toeplitz_recursion_per_output_and_state(hank):
+    from hank_amd.SteadyStateJacobian import household_jacobian, income_jacobian
+    rng = np.random.default_rng(4)
+    P, n_e, nh = 6, 3, 2
+    F, Dv = rng.standard_normal((P, P, n_e, nh)), rng.standard_normal((P, n_e, nh))
+    stub = R.StubIncomeBlock(F, Dv)
+    J = income_jacobian(stub, nh)
+    assert J.shape == (nh, P, n_e, P) and stub.calls == 1
+    for o in range(nh):
+        for e in range(n_e):
+            want = np.empty((P, P))
+            for t in range(P):
+                for s in range(P):
+                    want[t, s] = F[t, s, e, o] + (want[t - 1, s - 1] if t > 0 and s > 0 else (Dv[s, e, o] if t == 0 else 0.0))
+            assert np.allclose(J[o, :, e, :], want, rtol=0, atol=1e-14)
+        assert np.array_equal(J[o], household_jacobian(F[..., o], Dv[..., o]).transpose(1, 0, 2))
+    assert income_jacobian(stub, 1).shape == (1, P, n_e, P)
+
+
+def test_the_example_parses_the_redistribution():
+    from examples.solve_hank import parse_args
+    a = parse_args(["--redistribute", "0.01", "0.8", "2"])
+    assert a.redistribute == [0.01, 0.8, 2.0] and not a.gradient and not a.groups
+    a = parse_args(["--redistribute", "0.01", "0.8", "2", "--groups", "--gradient", "--n-a", "130", "--n-e", "3", "--T", "40"])
+    assert a.redistribute == [0.01, 0.8, 2.0] and a.gradient and a.groups and (a.n_a, a.n_e, a.T) == (130, 3, 40)
+    assert parse_args([]).redistribute is None
+    with pytest.raises(SystemExit):
+        parse_args(["--redistribute", "0.01", "0.8"])
