@@ -80,6 +80,39 @@ static inline int tan_lane_width(int N, int forward) {
     return (want == 2 && N % 2 == 0) ? 2 : 1;
 }
 
+// Which exogenous path the household block runs under: the discount factors beta_t (hank_shock.h) or income by
+// productivity state y_t[e] (hank_income.h). What differs between the kinds on the host is stated HERE, once; everything below indexes
+// by kind. The context owns the path in force (hank_ctx::path, set_path); the kinds exclude each other.
+enum PathKind { PATH_NONE, PATH_DISCOUNT, PATH_INCOME };
+constexpr int N_PATH_KINDS = 3;
+struct hank_ctx;
+typedef int (*VjpRule)(hank_ctx *, int, const void *, int, const void *);
+static int vjp_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out);
+static int vjp_het_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out);
+struct PathTraits {
+    const char *a_path;                     // the kind, as the messages name a path of it
+    const char *set, *jvp, *vjp, *fn;       // its entries, as the messages name them (set: also the clearing hint, `set(ctx, NULL) clears it`)
+    const char *dir, *bar;                  // its directions and its cotangent among their arguments
+    const char *refusal;                    // what an entry that is not served at a path of this kind says of itself (refuses_at)
+    PathKind excluded_by;                   // the kind under which its jvp / vjp entries refuse (path_entry_excluded); PATH_NONE: neither
+    VjpRule vjp_rule;                       // the argument rule of its vjp entry
+};
+static const PathTraits PATHS[N_PATH_KINDS] = {
+    {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, PATH_NONE, nullptr},
+    {"a discount-factor path", "hank_set_discount_path", "hank_jvp_shock", "hank_vjp_shock", "hank_fake_news_shock", "dbeta", "beta_bar",
+     "is defined at one discount factor", PATH_NONE, vjp_het_args},
+    {"an income path", "hank_set_income_path", "hank_jvp_income", "hank_vjp_income", "hank_fake_news_income", "dy", "y_bar",
+     "is not served at an income path", PATH_DISCOUNT, vjp_args},
+};
+// values per period (beta_t: 1; y_t[e]: n_e), and the value of every period without a path (the model's beta; zero)
+static int path_width(const Consts &c, PathKind k) { return k == PATH_INCOME ? c.n_e : 1; }
+static double path_neutral(const Consts &c, PathKind k) { return k == PATH_DISCOUNT ? c.beta : 0.0; }
+
+// a kind's share of a tangent workspace, allocated on its first use at this width (ensure_path_tan_graph): the caller's directions as they
+// come — dbeta (P, N), dy (n_e, P, N), column-major (staging) — the same as [P][N] / [P][n_e][N] (k_shk_in, k_inc_in), and the backward
+// sweep with the seed of every period between its launches
+struct PathSeed { DevBuf<double> in, dir; GraphExec g_tback; };
+
 struct TanWork {
     int N = 0;
     TanGeom g{}, gf{};   // lane geometry of the backward / forward tangent kernels
@@ -103,14 +136,9 @@ struct TanWork {
     unsigned nbf = 0;
     // The tangent-only graphs, each captured on its first use at this width, named HERE and nowhere else: bnd — with the boundary's
     // seed kernels in them (hank_boundary.h); NX — the forward sweep with that many extra reductions (hank_jvp_het, n_het = 2 + NX)
-    // hank_jvp_shock (hank_shock.h), allocated on its first use at this width: the caller's dbeta (P, N) column-major (staging) and the
-    // same as [P][N] (k_shk_in); g_tback_shk: the backward sweep with the seed of every period between its launches
-    DevBuf<double> shk_in, shk_db;
-    GraphExec g_tback_shk;
-    // hank_jvp_income (hank_income.h), allocated on its first use at this width: the caller's dy (n_e, P, N) column-major (staging) and the
-    // same as [P][n_e][N] (k_inc_in); g_tback_inc: the backward sweep with the income seed of every period between its launches
-    DevBuf<double> inc_in, inc_dy;
-    GraphExec g_tback_inc;
+    // The path kinds' seeds and backward graphs (hank_jvp_shock, hank_jvp_income, the two Toeplitz entries), by kind: each kind has its
+    // OWN buffers and graph, so the kinds alternate at one width without touching each other's ([PATH_NONE] stays empty: tan_back)
+    PathSeed seed[N_PATH_KINDS];
     GraphExec &tan_back(bool bnd) { return g_tback[bnd]; }
     GraphExec &tan_fwd(bool bnd, int NX) { return g_tfwd[bnd][NX]; }
 private:
@@ -171,6 +199,11 @@ struct WTan {
 
 // ---- transposed sweeps (hank_adjoint.h): hank_vjp's workspace per batch width M (its own: no TanWork's dpol is reused, so the
 // current tangent batch stays current and its readers keep serving it) ----
+// a kind's share of it: g_B is Sweep B — for a path kind with the path cotangent's partials behind every period's launch (k_shk_bbar,
+// k_inc_ybar) and their reduction at the end, captured on its first use at this width with the buffers: the partials [P][nb][width][M],
+// their sums [P][width][M] and the caller's layout (width, P, M) column-major (width: 1 for beta_bar, n_e for y_bar).
+// [PATH_NONE]: hank_vjp's plain Sweep B, captured with Sweep A, and no buffers.
+struct PathCot { DevBuf<double> part, rm, cm; GraphExec g_B; };
 struct CotWork {
     int N = 0;                      // the batch width M (the cache's key)
     int V = 1;                      // cotangent columns per lane
@@ -182,15 +215,12 @@ struct CotWork {
     DevBuf<double> pbar;            // [P][G][M] the policy cotangent sequence: written once by Sweep A, read once by Sweep B
     DevBuf<double> partS, partM;                // [P][nb][3][M] per-block partial sums of the inputs' cotangents
     DevBuf<double> xbar;            // (n_hh, P, M) column-major
-    GraphExec g_A, g_B;
-    GraphExec g_AX[2];              // Sweep A with NX = 1, 2 extra outputs (hank_vjp_het), captured on first use; Sweep B is g_B
+    GraphExec g_A;
+    PathCot path[N_PATH_KINDS];     // Sweep B by path kind, each kind with its own buffers: the kinds alternate at one width
+    GraphExec g_AX[2];              // Sweep A with NX = 1, 2 extra outputs (hank_vjp_het), captured on first use; Sweep B is the same
     DevBuf<double> gin, gb;         // hank_vjp_group, allocated on its first use at this width: the caller's (P, K, M) cotangents on the group outputs
                                     // (staging) and the same as [P][K][M] (k_adj_in_grp), both at HANK_GROUP_MAX groups
     GraphExec g_AG;                 // Sweep A with the context's groups (k_adj_dist_grp), captured on first use and dropped with the set (GroupSet)
-    DevBuf<double> bb_part, bb_rm, bb_cm;       // hank_vjp_shock, allocated on its first use at this width: beta_bar's partials [P][nb][M], their sums [P][M] and (P, M) column-major
-    GraphExec g_BS;                 // Sweep B with beta_bar's reduction behind every period's launch (k_shk_bbar), captured on first use
-    DevBuf<double> yb_part, yb_rm, yb_cm;       // hank_vjp_income, allocated on its first use at this width: y_bar's partials [P][nb][n_e][M], their sums [P][n_e][M] and (n_e, P, M) column-major
-    GraphExec g_BI;                 // Sweep B with y_bar's reduction behind every period's launch (k_inc_ybar), captured on first use
     DevBuf<double> bnd_vbar, bnd_dbar;          // (G, M) column-major the boundary's cotangents (hank_vjp_boundary), allocated on its first use at this width
 };
 // The current cotangent batch, with the same single owner as the tangent batch: cot_ran / cot_none write, the reader asks cot_current.
@@ -319,22 +349,19 @@ struct hank_ctx {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_side = nullptr;
     bool side_pending = false;
-    GraphExec g_pback, g_pfwd;
-    // the discount-factor path (hank_set_discount_path; hank_shock.h): d_beta [P] always holds the beta_t in force — the model's beta
-    // in every period without a path (the graphs hold its address); beta_on: a path is set, so everything that (re)writes the record
-    // runs on the per-period launches through g_pback_b, the backward primal graph of k_shk_egm_X / k_shk_egm_step
-    DevBuf<double> d_beta;
-    bool beta_on = false;
-    std::vector<double> h_beta;
-    GraphExec g_pback_b;
-    // the income path (hank_set_income_path; hank_income.h): d_y [P][n_e] always holds the y_t[e] in force — zeros without a path (the
-    // graphs hold its address); inc_on: a path is set, so everything that (re)writes the record runs on the per-period launches through
-    // g_pback_y, the backward primal graph of k_inc_egm_X / k_inc_egm_step. d_inc_m [P][n_e]: the column masses of the recorded
-    // distributions (k_inc_mass), valid for the recorded primal or not (ensure_inc_mass). The two paths exclude each other.
-    DevBuf<double> d_y, d_inc_m;
-    bool inc_on = false, inc_m_valid = false;
-    std::vector<double> h_y;
-    GraphExec g_pback_y;
+    GraphExec g_pfwd;              // the primal forward sweep (every kind's: it does not know a path)
+    // The exogenous paths, one ExoPath per kind: d — beta_t [P] / y_t[e] [P][n_e] — ALWAYS holds the values in
+    // force, the kind's neutral value in every period while no path of it is set (the graphs hold its address); h is its host copy;
+    // g_pback is the backward primal graph that reads it (capture_primal_back, captured at the first primal under a path of the kind).
+    // exo[PATH_NONE] has no values: its g_pback is the model's own backward graph. `path` says which kind is in force — at most one:
+    // set_path alone writes it, and it and the refusals next to it alone ask. A path in force keeps everything that (re)writes the
+    // record on the per-period launches.
+    // The income kind's alone: d_inc_m [P][n_e], the column masses of the recorded distributions (k_inc_mass) — the direct term of
+    // y_t[e] in consumption — valid for the recorded primal or not (inc_m_valid, ensure_inc_mass; record_rewritten drops it).
+    struct ExoPath { DevBuf<double> d; std::vector<double> h; GraphExec g_pback; } exo[N_PATH_KINDS];
+    PathKind path = PATH_NONE;
+    DevBuf<double> d_inc_m;
+    bool inc_m_valid = false;
     Spans spans;                   // the timed sweeps (hank_last_timings, hank_last_vjp_timings, hank_last_ss_timings)
     std::list<TanWork> tws;        // per batch width, most recently used first (a small cache: Jacobian assembly and Newton alternate widths)
     // 0 = one launch per period for everything; 1 = XCD-local persistent sweeps for everything; 2 = auto (default where
@@ -402,7 +429,8 @@ static void batch_ran_boundary(hank_ctx *ctx, const void *ws, int N, const doubl
     ctx->batch.boundary = true;
     ctx->batch.bnd_zm = zm;
 }
-// the same for a batch of hank_jvp_income with income directions: dy as TanBatch::inc_dy, marking the batch batch_ran has just named
+// the same for a batch of hank_jvp_income with income directions: dy as TanBatch::inc_dy, marking the batch batch_ran has just named.
+// The income kind alone marks its batches: y_t[e] has a direct term in consumption, beta_t has none in any output
 static void batch_ran_income(hank_ctx *ctx, const double *dy) { ctx->batch.inc_dy = dy; }
 // every reader's question: is a batch of N directions current?
 static int batch_current(hank_ctx *ctx, int N, const TanBatch **out) {
@@ -515,66 +543,52 @@ static int end_capture(hank_ctx *ctx, GraphExec *out) {
 // the error word starts a run of kernels clean, in stream order (the sweeps, the granular steps, the steady state's fixed points)
 static void zero_err(hank_ctx *ctx, hipStream_t s) { hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, ctx->d_err, 4); }
 
+// The backward primal graph of one path kind, the chain written ONCE: the error word cleared, X of the last period from the terminal
+// value, then P fused Y;X steps, then the lottery. Only the two EGM launches differ by kind: PATH_NONE the model's own; PATH_DISCOUNT
+// (hank_shock.h) beta_t' from the kind's values in the X half of period t'; PATH_INCOME (hank_income.h) y_t[e] in both halves.
+static int capture_primal_back(hank_ctx *ctx, PathKind kind) {
+    const Consts &c = ctx->c;
+    const int P = c.P;
+    hipStream_t s = ctx->own_stream;
+    const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
+    const size_t lds = primal_lds(c);
+    const double *v = ctx->exo[kind].d.get(), *x_last = ctx->d_xhh + c.n_hh * (P - 1);
+    double *s_last = ctx->R.s + (size_t)(P - 1) * c.G, *kc_last = ctx->R.kc + (size_t)(P - 1) * c.G;
+    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    zero_err(ctx, s);
+    switch (kind) {
+    case PATH_NONE: hipLaunchKernelGGL(k_egm_X, grd, blk, lds, s, c, ctx->d_ss_value, x_last, s_last, kc_last, ctx->d_err, P - 1, (const int *)nullptr); break;
+    case PATH_DISCOUNT: hipLaunchKernelGGL(k_shk_egm_X, grd, blk, lds, s, c, v, ctx->d_ss_value, x_last, s_last, kc_last, ctx->d_err, P - 1); break;
+    case PATH_INCOME: hipLaunchKernelGGL(k_inc_egm_X, grd, blk, lds, s, c, v, ctx->d_ss_value, x_last, s_last, kc_last, ctx->d_err, P - 1); break;
+    }
+    for (int t = P - 1; t >= 0; t--)
+        switch (kind) {
+        case PATH_NONE: hipLaunchKernelGGL(k_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, t, ctx->d_err); break;
+        case PATH_DISCOUNT: hipLaunchKernelGGL(k_shk_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, v, t, ctx->d_err); break;
+        case PATH_INCOME: hipLaunchKernelGGL(k_inc_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, v, t, ctx->d_err); break;
+        }
+    hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
+    return end_capture(ctx, &ctx->exo[kind].g_pback);
+}
+// the model's own pair: backward without a path, and the forward graph every kind shares
 static int build_primal_graphs(hank_ctx *ctx) {
     const Consts &c = ctx->c;
     const int P = c.P;
     hipStream_t s = ctx->own_stream;
     const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
-    const size_t lds = primal_lds(c);
-    // backward: X of the last period from the terminal value, then P fused Y;X steps, then lottery
-    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    zero_err(ctx, s);
-    hipLaunchKernelGGL(k_egm_X, grd, blk, lds, s, c, ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
-                       ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, P - 1, (const int *)nullptr);
-    for (int t = P - 1; t >= 0; t--)
-        hipLaunchKernelGGL(k_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, t, ctx->d_err);
-    hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
-    int rc = end_capture(ctx, &ctx->g_pback);
+    const int rc = capture_primal_back(ctx, PATH_NONE);
     if (rc) return rc;
-    // forward
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     for (int t = 0; t < P; t++)
-        hipLaunchKernelGGL(k_dist_step, grd, blk, lds, s, c, ctx->R, t, ctx->d_aggpart);
+        hipLaunchKernelGGL(k_dist_step, grd, blk, primal_lds(c), s, c, ctx->R, t, ctx->d_aggpart);
     hipLaunchKernelGGL(k_reduce_parts, dim3(P, 1), dim3(256), 0, s, ctx->d_aggpart, ctx->nbp, 2, ctx->d_agg_rm);
     hipLaunchKernelGGL(k_tan_out, dim3((2 * P + 255) / 256), dim3(256), 0, s, ctx->d_agg_rm, P, 2, ctx->d_agg);
     return end_capture(ctx, &ctx->g_pfwd);
 }
-// the backward primal graph at a discount-factor path (hank_shock.h): g_pback's launches with beta_t' from d_beta in the X half of
-// period t'; the forward graph is g_pfwd. Captured the first time a primal runs with a path set.
-static int ensure_shock_primal_graphs(hank_ctx *ctx) {
-    if (!ctx->g_pback) { const int rc = build_primal_graphs(ctx); if (rc) return rc; }
-    if (ctx->g_pback_b) return HANK_OK;
-    const Consts &c = ctx->c;
-    const int P = c.P;
-    hipStream_t s = ctx->own_stream;
-    const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
-    const size_t lds = primal_lds(c);
-    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    zero_err(ctx, s);
-    hipLaunchKernelGGL(k_shk_egm_X, grd, blk, lds, s, c, ctx->d_beta.get(), ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
-                       ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, P - 1);
-    for (int t = P - 1; t >= 0; t--)
-        hipLaunchKernelGGL(k_shk_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, ctx->d_beta.get(), t, ctx->d_err);
-    hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
-    return end_capture(ctx, &ctx->g_pback_b);
-}
-// the same at an income path (hank_income.h): y_t[e] from d_y in both halves. Captured the first time a primal runs with a path set.
-static int ensure_income_primal_graphs(hank_ctx *ctx) {
-    if (!ctx->g_pback) { const int rc = build_primal_graphs(ctx); if (rc) return rc; }
-    if (ctx->g_pback_y) return HANK_OK;
-    const Consts &c = ctx->c;
-    const int P = c.P;
-    hipStream_t s = ctx->own_stream;
-    const dim3 blk(RBP * c.n_e), grd(ctx->nbp);
-    const size_t lds = primal_lds(c);
-    HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    zero_err(ctx, s);
-    hipLaunchKernelGGL(k_inc_egm_X, grd, blk, lds, s, c, ctx->d_y.get(), ctx->d_ss_value, ctx->d_xhh + c.n_hh * (P - 1),
-                       ctx->R.s + (size_t)(P - 1) * c.G, ctx->R.kc + (size_t)(P - 1) * c.G, ctx->d_err, P - 1);
-    for (int t = P - 1; t >= 0; t--)
-        hipLaunchKernelGGL(k_inc_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, ctx->d_y.get(), t, ctx->d_err);
-    hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
-    return end_capture(ctx, &ctx->g_pback_y);
+// the graphs a primal on the launches needs under `kind`: a path kind's backward graph is captured the first time a primal runs under it
+static int ensure_primal_graphs(hank_ctx *ctx, PathKind kind) {
+    if (!ctx->exo[PATH_NONE].g_pback) { const int rc = build_primal_graphs(ctx); if (rc) return rc; }
+    return ctx->exo[kind].g_pback ? (int)HANK_OK : capture_primal_back(ctx, kind);
 }
 
 // Captures the four tangent graphs for lane type VT (double: one direction per lane; double2: two).
@@ -611,16 +625,14 @@ static void launch_tan_reduce(hank_ctx *ctx, TanWork &w, hipStream_t s) {
 static dim3 bnd_grid(const Consts &c, int N) { return dim3((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((N + BND_T - 1) / BND_T), (unsigned)c.n_e); }
 
 // the backward tangent sweep; bnd: with the dV_P seed (hank_boundary.h: the same launches of the same kernel, the seed kernels between them)
-// shock (hank_shock.h): the d beta_t seed of EVERY period behind the launch that produced that period's knots' tangent — P launches more, and
-// k_shk_in in front; w.shk_in, w.shk_db are allocated before this
-// income (hank_income.h; never with shock or bnd): the d y_t[e] seed of every period in the same places, k_inc_in in front; w.inc_in, w.inc_dy are
-// allocated before this
+// kind (never with bnd): a path kind's seed of EVERY period — d beta_t (hank_shock.h), d y_t[e] (hank_income.h) — behind the launch that produced
+// that period's knots' tangent — P launches more, and the kind's layout kernel in front; w.seed[kind]'s buffers are allocated before this
 static size_t inc_seed_lds(const Consts &c, int N) {      // k_inc_seed_back's staging, or 0 where it does not fit (it reads global memory then)
     const size_t b = sizeof(double) * ((size_t)c.n_e * c.n_e + 2 * (size_t)c.n_e * N);
     return b <= 48 * 1024 ? b : 0;
 }
 template <typename VT>
-static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = false, bool income = false) {
+static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, PathKind kind = PATH_NONE) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
     const int N = w.N, PN = (int)(P * N), RGB = w.RGB;
@@ -632,21 +644,22 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = fa
     VT *dpol = reinterpret_cast<VT *>(w.dpol.get());
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
-    if (shock) hipLaunchKernelGGL(k_shk_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.shk_in.get(), (int)P, N, w.shk_db.get());
-    if (income) hipLaunchKernelGGL(k_inc_in, dim3((unsigned)(((size_t)PN * c.n_e + 255) / 256)), dim3(256), 0, s, w.inc_in.get(), c.n_e, (int)P, N, w.inc_dy.get());
+    PathSeed &ps = w.seed[kind];
+    const bool seeded = kind != PATH_NONE;
+    if (kind == PATH_DISCOUNT) hipLaunchKernelGGL(k_shk_in, dim3((PN + 255) / 256), dim3(256), 0, s, ps.in.get(), (int)P, N, ps.dir.get());
+    if (kind == PATH_INCOME) hipLaunchKernelGGL(k_inc_in, dim3((unsigned)(((size_t)PN * c.n_e + 255) / 256)), dim3(256), 0, s, ps.in.get(), c.n_e, (int)P, N, ps.dir.get());
     const dim3 sgrd((unsigned)(((size_t)c.n_a * N + 255) / 256));
     const size_t ilds = inc_seed_lds(c, N), eN = (size_t)c.n_e * N;
     auto seed = [&](int t, double *ds_t) {      // ds_t: the knots' tangent of period t, as the launch before left it
-        if (income)
-            hipLaunchKernelGGL(k_inc_seed_back, sgrd, dim3(256), ilds, s, c, ctx->R, ctx->d_xhh.get(), t, w.inc_dy.get() + (size_t)t * eN,
-                               t + 1 < (int)P ? w.inc_dy.get() + (size_t)(t + 1) * eN : (const double *)nullptr, (size_t)N, ilds ? 1 : 0, ds_t);
+        if (kind == PATH_INCOME)
+            hipLaunchKernelGGL(k_inc_seed_back, sgrd, dim3(256), ilds, s, c, ctx->R, ctx->d_xhh.get(), t, ps.dir.get() + (size_t)t * eN,
+                               t + 1 < (int)P ? ps.dir.get() + (size_t)(t + 1) * eN : (const double *)nullptr, (size_t)N, ilds ? 1 : 0, ds_t);
         else
-            hipLaunchKernelGGL(k_shk_seed_back, sgrd, dim3(256), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->d_beta.get(), t, w.shk_db.get() + (size_t)t * N, (size_t)N, ds_t);
+            hipLaunchKernelGGL(k_shk_seed_back, sgrd, dim3(256), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->exo[PATH_DISCOUNT].d.get(), t, ps.dir.get() + (size_t)t * N, (size_t)N, ds_t);
     };
-    shock = shock || income;      // (the seeds sit in the same places)
     LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, (int)P - 1, 1,
                        ds[1], ds[0], dpol);
-    if (shock) seed((int)P - 1, w.ds[0].get());
+    if (seeded) seed((int)P - 1, w.ds[0].get());
     if (bnd) {      // dV_P (BackwardIteration.jl:85) into the knots' tangent of period P-1; ds[1] is free until the next launch writes it
         hipLaunchKernelGGL(k_bnd_in, bnd_grid(c, N), dim3(BND_T, 8), 0, s, w.bnd_dV.get(), c.n_a, c.n_e, c.n_a, N, w.ds[1].get());
         hipLaunchKernelGGL(k_bnd_seed_back, dim3((unsigned)(((size_t)c.n_a * N + 255) / 256)), dim3(256), 0, s, c, ctx->R.kc + (P - 1) * c.G, w.ds[1].get(), (size_t)N, w.ds[0].get());
@@ -655,10 +668,10 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, bool shock = fa
     for (int t = (int)P - 1; t >= 0; t--) {
         LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, t, 0,
                            ds[cur], ds[cur ^ 1], dpol);
-        if (shock && t > 0) seed(t - 1, w.ds[cur ^ 1].get());
+        if (seeded && t > 0) seed(t - 1, w.ds[cur ^ 1].get());
         cur ^= 1;
     }
-    return end_capture(ctx, income ? &w.g_tback_inc : shock ? &w.g_tback_shk : &w.tan_back(bnd));
+    return end_capture(ctx, seeded ? &ps.g_tback : &w.tan_back(bnd));
 }
 
 // the forward tangent sweep; bnd: with the dD_0 seed; NX > 0 (hank_jvp_het): k_tan_fwd_hx in k_tan_fwd's place and k_reduce_hx behind
@@ -836,25 +849,17 @@ static int ensure_tan_graphs(hank_ctx *ctx, TanWork &w, bool bnd, int NX) {
     if (!rc && NX > 0) rc = fwd(NX);
     return rc;
 }
-// hank_jvp_shock's / hank_fake_news_shock's backward graph (the forward sweep is the plain one: it does not know where a seed came from)
-static int ensure_shock_tan_graph(hank_ctx *ctx, TanWork &w) {
-    const size_t PN = (size_t)ctx->c.P * w.N;
-    if (!w.shk_db) {
-        HIPC(ctx, w.shk_in.alloc(PN));
-        HIPC(ctx, w.shk_db.alloc(PN));      // (last: a failed allocation is tried again by the next call)
+// a path kind's backward graph — its jvp entry's and its Toeplitz entry's (the forward sweep is the plain one: it does not know where a
+// seed came from) — and, before the capture, the kind's buffers at this width
+static int ensure_path_tan_graph(hank_ctx *ctx, TanWork &w, PathKind kind) {
+    PathSeed &ps = w.seed[kind];
+    const size_t cnt = (size_t)ctx->c.P * path_width(ctx->c, kind) * w.N;
+    if (!ps.dir) {
+        HIPC(ctx, ps.in.alloc(cnt));
+        HIPC(ctx, ps.dir.alloc(cnt));      // (last: a failed allocation is tried again by the next call)
     }
-    if (w.g_tback_shk) return HANK_OK;
-    return w.VB == 2 ? capture_tan_back<double2>(ctx, w, false, true) : capture_tan_back<double>(ctx, w, false, true);
-}
-// hank_jvp_income's / hank_fake_news_income's backward graph
-static int ensure_income_tan_graph(hank_ctx *ctx, TanWork &w) {
-    const size_t cnt = (size_t)ctx->c.P * ctx->c.n_e * w.N;
-    if (!w.inc_dy) {
-        HIPC(ctx, w.inc_in.alloc(cnt));
-        HIPC(ctx, w.inc_dy.alloc(cnt));      // (last: a failed allocation is tried again by the next call)
-    }
-    if (w.g_tback_inc) return HANK_OK;
-    return w.VB == 2 ? capture_tan_back<double2>(ctx, w, false, false, true) : capture_tan_back<double>(ctx, w, false, false, true);
+    if (ps.g_tback) return HANK_OK;
+    return w.VB == 2 ? capture_tan_back<double2>(ctx, w, false, kind) : capture_tan_back<double>(ctx, w, false, kind);
 }
 static int ensure_dual_graphs(hank_ctx *ctx, TanWork &w) {
     if (w.g_fback) return HANK_OK;
@@ -926,7 +931,7 @@ static int device_verdict(hank_ctx *ctx, Whose whose) {
 // a sweep could not form its groups (or timed out): this context continues on the per-period launches
 static int to_launch_schedule(hank_ctx *ctx) {
     record_gone(ctx);
-    if (!ctx->g_pback) {                    // (a context that has only run persistent sweeps has never captured them)
+    if (!ctx->exo[PATH_NONE].g_pback) {     // (a context that has only run persistent sweeps has never captured them)
         const int rc = build_primal_graphs(ctx);
         if (rc != HANK_OK) return rc;       // the schedule is left as it was: the next call reports the sweep's failure again, not a null graph
     }
@@ -1705,13 +1710,13 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     ctx->d_ss_D = R.Dseq;      // view
     ctx->nbp = (c.n_a + RBP - 1) / RBP;
     HIPC(ctx, ctx->d_xhh.alloc((size_t)c.n_hh * P));
-    HIPC(ctx, ctx->d_beta.alloc(P));
-    ctx->h_beta.assign(P, c.beta);      // no path: the model's beta in every period
-    HIPC(ctx, hipMemcpy(ctx->d_beta, ctx->h_beta.data(), sizeof(double) * P, hipMemcpyHostToDevice));
-    HIPC(ctx, ctx->d_y.alloc((size_t)P * c.n_e));
+    for (PathKind k : {PATH_DISCOUNT, PATH_INCOME}) {      // no path: the kind's neutral value in every period
+        hank_ctx::ExoPath &e = ctx->exo[k];
+        e.h.assign((size_t)P * path_width(c, k), path_neutral(c, k));
+        HIPC(ctx, e.d.alloc(e.h.size()));
+        HIPC(ctx, hipMemcpy(e.d, e.h.data(), sizeof(double) * e.h.size(), hipMemcpyHostToDevice));
+    }
     HIPC(ctx, ctx->d_inc_m.alloc((size_t)P * c.n_e));
-    ctx->h_y.assign((size_t)P * c.n_e, 0.0);      // no path: zeros
-    HIPC(ctx, hipMemset(ctx->d_y, 0, sizeof(double) * P * c.n_e));
     HIPC(ctx, ctx->d_agg.alloc(2 * P));
     HIPC(ctx, ctx->d_agg_rm.alloc(2 * P));
     HIPC(ctx, ctx->d_zd.alloc(2 * P));
@@ -1834,72 +1839,69 @@ int hank_set_boundary(hank_ctx *ctx, const double *ss_end_value, const double *s
     return HANK_OK;
 }
 
-// which x the record belongs to: the host-pointer entries know it (and whether it is a constant path), the device-pointer
-// entries do not
-// hank_set_discount_path (hank_shock.h; KrusellSmith.jl:59-62, BackwardIteration.jl:90-113): beta_t [P] on the host, or null for the
-// model's constant. What a new boundary invalidates goes: the record, both current batches, the memo.
-int hank_set_discount_path(hank_ctx *ctx, const double *beta_t) {
+// ---- the path in force: its one writer and the refusals that ask about it ------------------------------------
+// No other code tests which path is set; what else names a kind selects that kind's graph, buffer or kernel argument.
+// a kind's validity rule for the caller's values, with its message
+static int path_values_ok(hank_ctx *ctx, PathKind kind, const double *v) {
+    const size_t ne = ctx->c.n_e, cnt = (size_t)ctx->c.P * path_width(ctx->c, kind);
+    for (size_t k = 0; k < cnt; k++) {
+        if (kind == PATH_DISCOUNT && (!(v[k] > 0.0) || !(v[k] <= 1.7976931348623157e308)))
+            return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_discount_path: beta_t must be finite and positive (period %zu: %g); the path in force is unchanged", k + 1, v[k]);
+        if (kind == PATH_INCOME && !(v[k] >= -1.7976931348623157e308 && v[k] <= 1.7976931348623157e308))
+            return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_income_path: y must be finite (state %zu, period %zu: %g); the path in force is unchanged", k % ne + 1, k / ne + 1, v[k]);
+    }
+    return HANK_OK;
+}
+// hank_set_discount_path (hank_shock.h; KrusellSmith.jl:59-62, BackwardIteration.jl:90-113): beta_t [P]; hank_set_income_path
+// (hank_income.h; KrusellSmith.jl:59-62, :66-80 inside the same loop): y (n_e, P) column-major — on the host, or null for no path of the
+// kind (its neutral value in every period). THE rule that the kinds exclude each other. What a new boundary invalidates goes: the
+// record, both current batches, the memo.
+static int set_path(hank_ctx *ctx, PathKind kind, const double *values) {
     ENTER(ctx);
     if (!ctx) return HANK_ERR_BAD_ARG;
-    const size_t P = ctx->c.P;
-    if (!beta_t && !ctx->beta_on) { ctx->errmsg[0] = 0; return HANK_OK; }      // (no path to clear: nothing changes)
-    if (ctx->inc_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_discount_path: an income path is set and the two exclude each other (hank_set_income_path(ctx, NULL) clears it)");
-    if (beta_t)
-        for (size_t t = 0; t < P; t++)
-            if (!(beta_t[t] > 0.0) || !(beta_t[t] <= 1.7976931348623157e308))
-                return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_discount_path: beta_t must be finite and positive (period %zu: %g); the path in force is unchanged", t + 1, beta_t[t]);
+    hank_ctx::ExoPath &e = ctx->exo[kind];
+    if (!values && ctx->path != kind) { ctx->errmsg[0] = 0; return HANK_OK; }      // (no path to clear: nothing changes)
+    if (ctx->path != PATH_NONE && ctx->path != kind)
+        return fail(ctx, HANK_ERR_NOT_READY, "%s: %s is set and the two exclude each other (%s(ctx, NULL) clears it)", PATHS[kind].set, PATHS[ctx->path].a_path, PATHS[ctx->path].set);
+    if (values) { const int vrc = path_values_ok(ctx, kind, values); if (vrc) return vrc; }
     HIPC(ctx, join_side(ctx));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (sweeps in flight read d_beta)
-    if (beta_t) ctx->h_beta.assign(beta_t, beta_t + P);
-    else ctx->h_beta.assign(P, ctx->c.beta);
-    HIPC(ctx, hipMemcpyAsync(ctx->d_beta, ctx->h_beta.data(), sizeof(double) * P, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (sweeps in flight read the values)
+    if (values) e.h.assign(values, values + e.h.size());
+    else e.h.assign(e.h.size(), path_neutral(ctx->c, kind));
+    HIPC(ctx, hipMemcpyAsync(e.d, e.h.data(), sizeof(double) * e.h.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->beta_on = beta_t != nullptr;
+    ctx->path = values ? kind : PATH_NONE;
     record_gone(ctx);
     ctx->memo_valid = false;
     ctx->stationary = false;
     ctx->errmsg[0] = 0;
     return HANK_OK;
 }
-// hank_set_income_path (hank_income.h; KrusellSmith.jl:59-62, :66-80 inside the loop of BackwardIteration.jl:90-113): y (n_e, P) column-major
-// on the host, or null for no path. What a new boundary invalidates goes: the record, both current batches, the memo.
-int hank_set_income_path(hank_ctx *ctx, const double *y) {
-    ENTER(ctx);
-    if (!ctx) return HANK_ERR_BAD_ARG;
-    const size_t cnt = (size_t)ctx->c.P * ctx->c.n_e;
-    if (!y && !ctx->inc_on) { ctx->errmsg[0] = 0; return HANK_OK; }      // (no path to clear: nothing changes)
-    if (y && ctx->beta_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_set_income_path: a discount-factor path is set and the two exclude each other (hank_set_discount_path(ctx, NULL) clears it)");
-    if (y)
-        for (size_t k = 0; k < cnt; k++)
-            if (!(y[k] >= -1.7976931348623157e308 && y[k] <= 1.7976931348623157e308))
-                return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_income_path: y must be finite (state %zu, period %zu: %g); the path in force is unchanged", k % ctx->c.n_e + 1, k / ctx->c.n_e + 1, y[k]);
-    HIPC(ctx, join_side(ctx));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));      // (sweeps in flight read d_y)
-    if (y) ctx->h_y.assign(y, y + cnt);
-    else ctx->h_y.assign(cnt, 0.0);
-    HIPC(ctx, hipMemcpyAsync(ctx->d_y, ctx->h_y.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->inc_on = y != nullptr;
-    record_gone(ctx);
-    ctx->memo_valid = false;
-    ctx->stationary = false;
-    ctx->errmsg[0] = 0;
+int hank_set_discount_path(hank_ctx *ctx, const double *beta_t) { return set_path(ctx, PATH_DISCOUNT, beta_t); }
+int hank_set_income_path(hank_ctx *ctx, const double *y) { return set_path(ctx, PATH_INCOME, y); }
+// a path of either kind: the sweeps run on the per-period launches
+static bool path_on(const hank_ctx *ctx) { return ctx->path != PATH_NONE; }
+// the income values in force as k_inc_cons takes them: null without an income path
+static const double *income_in_force(const hank_ctx *ctx) { return ctx->path == PATH_INCOME ? ctx->exo[PATH_INCOME].d.get() : nullptr; }
+// an entry that is not served while a path of `kind` is set
+static int refuses_at(hank_ctx *ctx, PathKind kind, const char *name) {
+    if (ctx && ctx->path == kind)
+        return fail(ctx, HANK_ERR_NOT_READY, "%s %s: a path is set (%s(ctx, NULL) clears it)", name, PATHS[kind].refusal, PATHS[kind].set);
     return HANK_OK;
 }
 // the entries that rebuild consumption from the inputs (w z_e + tr) or carry seeds the income entries do not, while an income path is set
-static int income_refuses(hank_ctx *ctx, const char *name) {
-    if (ctx && ctx->inc_on)
-        return fail(ctx, HANK_ERR_NOT_READY, "%s is not served at an income path: a path is set (hank_set_income_path(ctx, NULL) clears it)", name);
-    return HANK_OK;
-}
+static int income_refuses(hank_ctx *ctx, const char *name) { return refuses_at(ctx, PATH_INCOME, name); }
 // the entries that are defined at ONE beta and ONE income process (the scenario and steady-state entries, the Toeplitz Jacobians) while a path is set
 static int path_refuses(hank_ctx *ctx, const char *name) {
-    if (ctx && ctx->beta_on)
-        return fail(ctx, HANK_ERR_NOT_READY, "%s is defined at one discount factor: a path is set (hank_set_discount_path(ctx, NULL) clears it)", name);
-    return income_refuses(ctx, name);
+    const int rc = refuses_at(ctx, PATH_DISCOUNT, name);
+    return rc ? rc : refuses_at(ctx, PATH_INCOME, name);
 }
-// a path of either kind: the sweeps run on the per-period launches
-static bool path_on(const hank_ctx *ctx) { return ctx->beta_on || ctx->inc_on; }
+// a kind's own jvp / vjp entry (`who`) while the kind that excludes it is set: hank_jvp_income and hank_vjp_income under a discount-factor path
+static int path_entry_excluded(hank_ctx *ctx, PathKind kind, const char *who) {
+    const PathKind other = PATHS[kind].excluded_by;
+    if (other != PATH_NONE && ctx->path == other) return fail(ctx, HANK_ERR_NOT_READY, "%s: %s is set and the two exclude each other", who, PATHS[other].a_path);
+    return HANK_OK;
+}
 // the column masses of the recorded distributions, for the first reader at this record (the main stream has joined the forward sweep)
 static int ensure_inc_mass(hank_ctx *ctx) {
     if (ctx->inc_m_valid) return HANK_OK;
@@ -1909,6 +1911,8 @@ static int ensure_inc_mass(hank_ctx *ctx) {
     return HANK_OK;
 }
 
+// which x the record belongs to: the host-pointer entries know it (and whether it is a constant path), the device-pointer
+// entries do not
 static void note_primal_x(hank_ctx *ctx, const double *xhh) {
     const size_t n = (size_t)ctx->c.n_hh * ctx->c.P, nh = ctx->c.n_hh;
     if (!xhh) { ctx->memo_valid = false; ctx->stationary = false; return; }
@@ -1920,11 +1924,10 @@ static void note_primal_x(hank_ctx *ctx, const double *xhh) {
 }
 
 static int run_primal(hank_ctx *ctx, double *d_agg_out) {
-    if (ctx->beta_on) { const int grc = ensure_shock_primal_graphs(ctx); if (grc) return grc; }      // (whatever the schedule: a path runs on the launches)
-    if (ctx->inc_on) { const int grc = ensure_income_primal_graphs(ctx); if (grc) return grc; }
+    { const int grc = ensure_primal_graphs(ctx, ctx->path); if (grc) return grc; }      // (whatever the schedule: a path runs on the launches)
     HIPC(ctx, join_side(ctx));     // a previous forward sweep still reads the record this one overwrites
     HIPC(ctx, ctx->spans.begin(PRIMAL_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(ctx->beta_on ? ctx->g_pback_b : ctx->inc_on ? ctx->g_pback_y : ctx->g_pback, ctx->stream));
+    HIPC(ctx, hipGraphLaunch(ctx->exo[ctx->path].g_pback, ctx->stream));
     HIPC(ctx, ctx->spans.end(PRIMAL_BACK, ctx->stream, ctx->c.P + 2));
     // fork: the distribution sweep goes to the side stream; the main stream is free for the tangent
     // backward sweep and joins (join_side) before anything that needs D_t or the aggregates
@@ -2163,16 +2166,15 @@ int hank_primal(hank_ctx *ctx, const double *xhh, double *agg_out) {
 
 // bnd: the graphs with the boundary's seeds (hank_jvp_boundary: w.bnd_dV and w.bnd_dD hold them); zm: whether a dD_0 seed is among them
 // NX > 0 (hank_jvp_het): the forward graph with that many extra reductions, one launch more (k_reduce_hx)
-// shock (hank_jvp_shock; never with bnd): the backward graph with the d beta_t seeds, 2 P + 3 launches
-// income (hank_jvp_income; never with bnd or shock): the backward graph with the d y_t[e] seeds, the same count
-static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd, bool zm, int NX, bool shock = false, bool income = false) {
+// kind (hank_jvp_shock, hank_jvp_income; never with bnd): the kind's backward graph with its seeds, 2 P + 3 launches
+static int run_jvp(hank_ctx *ctx, TanWork &w, bool bnd, bool zm, int NX, PathKind kind = PATH_NONE) {
+    const bool seeded = kind != PATH_NONE;
     int grc = ensure_tan_graphs(ctx, w, bnd, NX);
-    if (!grc && shock) grc = ensure_shock_tan_graph(ctx, w);
-    if (!grc && income) grc = ensure_income_tan_graph(ctx, w);
+    if (!grc && seeded) grc = ensure_path_tan_graph(ctx, w, kind);
     if (grc) return grc;
     HIPC(ctx, ctx->spans.begin(TAN_BACK, ctx->stream));
-    HIPC(ctx, hipGraphLaunch(income ? w.g_tback_inc : shock ? w.g_tback_shk : w.tan_back(bnd), ctx->stream));
-    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, (shock || income) ? 2 * ctx->c.P + 3 : ctx->c.P + (bnd ? 4 : 2)));
+    HIPC(ctx, hipGraphLaunch(seeded ? w.seed[kind].g_tback : w.tan_back(bnd), ctx->stream));
+    HIPC(ctx, ctx->spans.end(TAN_BACK, ctx->stream, seeded ? 2 * ctx->c.P + 3 : ctx->c.P + (bnd ? 4 : 2)));
     HIPC(ctx, join_side(ctx));      // the tangent forward sweep needs D_t
     { const int src = ensure_seg(ctx); if (src) return src; }
     { const int src = ensure_lwg(ctx); if (src) return src; }
@@ -2192,10 +2194,8 @@ struct TanReq {
     hipMemcpyKind kind;                            // where they live
     bool seeded;                                   // run the graphs with the seed kernels: hank_jvp_boundary always (null seeds too),
                                                    // hank_jvp_het when a seed is given, hank_jvp never — NOT derived from the pointers
-    const double *dbeta = nullptr;                 // hank_jvp_shock: the directions in beta_t, (P, N) column-major; null: zero
-    bool shock = false;                            // run the backward graph with the d beta_t seeds (hank_jvp_shock always, null dbeta too)
-    const double *dy = nullptr;                    // hank_jvp_income: the directions in y_t[e], (n_e, P, N) column-major; null: zero
-    bool income = false;                           // run the backward graph with the d y_t[e] seeds (hank_jvp_income always, null dy too)
+    PathKind path = PATH_NONE;                     // run the backward graph with this kind's seeds (hank_jvp_shock, hank_jvp_income always, null directions too)
+    const double *dpath = nullptr;                 // the directions in the kind's values — dbeta (P, N), dy (n_e, P, N), column-major; null: zero
 };
 static int ensure_bnd_bufs(hank_ctx *ctx, TanWork &w);
 static int ensure_hx_record(hank_ctx *ctx);
@@ -2226,21 +2226,16 @@ static int enqueue_tan_launch(hank_ctx *ctx, const TanReq &q, int N, TanWork **o
         if (in[k].src) HIPC(ctx, hipMemcpyAsync(in[k].dst, in[k].src, sizeof(double) * in[k].count, q.kind, ctx->stream));
         else HIPC(ctx, hipMemsetAsync(in[k].dst, 0, sizeof(double) * in[k].count, ctx->stream));
     }
-    if (q.shock) {      // (the seeds' buffers before the capture; the graph is captured in run_jvp)
-        rc = ensure_shock_tan_graph(ctx, *w);
+    if (q.path != PATH_NONE) {      // the path directions staged or zeroed (their buffers, and the kind's graph, before that)
+        rc = ensure_path_tan_graph(ctx, *w, q.path);
         if (rc) return rc;
-        if (q.dbeta) HIPC(ctx, hipMemcpyAsync(w->shk_in, q.dbeta, sizeof(double) * P * N, q.kind, ctx->stream));
-        else HIPC(ctx, hipMemsetAsync(w->shk_in, 0, sizeof(double) * P * N, ctx->stream));
+        const size_t bytes = sizeof(double) * P * path_width(c, q.path) * N;
+        if (q.dpath) HIPC(ctx, hipMemcpyAsync(w->seed[q.path].in, q.dpath, bytes, q.kind, ctx->stream));
+        else HIPC(ctx, hipMemsetAsync(w->seed[q.path].in, 0, bytes, ctx->stream));
     }
-    if (q.income) {
-        rc = ensure_income_tan_graph(ctx, *w);
-        if (rc) return rc;
-        if (q.dy) HIPC(ctx, hipMemcpyAsync(w->inc_in, q.dy, sizeof(double) * P * c.n_e * N, q.kind, ctx->stream));
-        else HIPC(ctx, hipMemsetAsync(w->inc_in, 0, sizeof(double) * P * c.n_e * N, ctx->stream));
-    }
-    rc = run_jvp(ctx, *w, q.seeded, q.dD_init != nullptr, NX, q.shock, q.income);
+    rc = run_jvp(ctx, *w, q.seeded, q.dD_init != nullptr, NX, q.path);
     if (rc) return rc;
-    if (q.income && q.dy) batch_ran_income(ctx, w->inc_in);      // (a null dy is hank_jvp's batch)
+    if (q.path == PATH_INCOME && q.dpath) batch_ran_income(ctx, w->seed[PATH_INCOME].in);      // (a null dy is hank_jvp's batch; beta_t has no direct term to mark)
     *out = w;
     return HANK_OK;
 }
@@ -2364,56 +2359,28 @@ int hank_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_en
     return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
 }
 
-// hank_jvp_shock[_dev] (hank_shock.h): the request with the d beta_t seeds, always on the launches' graphs with the seed kernels; a null
-// input is a zero seed. Named as hank_jvp names its batch.
-static int shock_args(hank_ctx *ctx, const double *dxhh, const double *dbeta, int N, const void *out, bool need_out) {
-    if (!ctx || (!dxhh && !dbeta) || (need_out && !out) || N < 1)
-        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_shock: bad argument (N=%d; at least one of dxhh, dbeta must be given)", N);
-    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_shock");
-    return HANK_OK;
-}
-int hank_jvp_shock_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dbeta, int32_t N, double *d_dagg_out) {
+// hank_jvp_shock[_dev] (hank_shock.h), hank_jvp_income[_dev] (hank_income.h): the request with the kind's seeds — d beta_t, d y_t[e] —
+// always on the launches' graphs with the seed kernels; a null input is a zero seed. Named as hank_jvp names its batch. The four
+// entries' one body; the rule differs by kind in its messages and in path_entry_excluded alone.
+static int jvp_path(hank_ctx *ctx, PathKind kind, const double *dxhh, const double *dpath, int N, double *out, bool dev) {
     ENTER(ctx);
-    const TanReq q{0, d_dxhh, nullptr, nullptr, hipMemcpyDeviceToDevice, false, d_dbeta, true};
-    const int rc = shock_args(ctx, d_dxhh, d_dbeta, N, d_dagg_out, false);
-    return rc ? rc : enqueue_tan_raw(ctx, q, N, d_dagg_out);
-}
-int hank_jvp_shock(hank_ctx *ctx, const double *dxhh, const double *dbeta, int32_t N, double *dagg_out) {
-    ENTER(ctx);
-    const TanReq q{0, dxhh, nullptr, nullptr, hipMemcpyHostToDevice, false, dbeta, true};
-    int rc = shock_args(ctx, dxhh, dbeta, N, dagg_out, true);
-    if (!rc) rc = enqueue_tan_raw(ctx, q, N, nullptr);
+    const PathTraits &pt = PATHS[kind];
+    if (!ctx || (!dxhh && !dpath) || (!dev && !out) || N < 1)
+        return fail(ctx, HANK_ERR_BAD_ARG, "%s: bad argument (N=%d; at least one of dxhh, %s must be given)", pt.jvp, N, pt.dir);
+    int rc = path_entry_excluded(ctx, kind, pt.jvp);
     if (rc) return rc;
-    return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
+    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before %s", pt.jvp);
+    TanReq q{0, dxhh, nullptr, nullptr, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, false};
+    q.path = kind;
+    q.dpath = dpath;
+    rc = enqueue_tan_raw(ctx, q, N, dev ? out : nullptr);
+    if (rc || dev) return rc;
+    return tan_host_tail(ctx, out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
 }
-
-// hank_jvp_income[_dev] (hank_income.h): the request with the d y_t[e] seeds, always on the launches' graphs with the seed kernels; a
-// null input is a zero seed. Named as hank_jvp names its batch.
-static int income_args(hank_ctx *ctx, const double *dxhh, const double *dy, int N, const void *out, bool need_out) {
-    if (!ctx || (!dxhh && !dy) || (need_out && !out) || N < 1)
-        return fail(ctx, HANK_ERR_BAD_ARG, "hank_jvp_income: bad argument (N=%d; at least one of dxhh, dy must be given)", N);
-    if (ctx->beta_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_jvp_income: a discount-factor path is set and the two exclude each other");
-    if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "hank_primal must be called before hank_jvp_income");
-    return HANK_OK;
-}
-static TanReq income_req(const double *dxhh, const double *dy, hipMemcpyKind kind) {
-    TanReq q{0, dxhh, nullptr, nullptr, kind, false};
-    q.dy = dy;
-    q.income = true;
-    return q;
-}
-int hank_jvp_income_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dy, int32_t N, double *d_dagg_out) {
-    ENTER(ctx);
-    const int rc = income_args(ctx, d_dxhh, d_dy, N, d_dagg_out, false);
-    return rc ? rc : enqueue_tan_raw(ctx, income_req(d_dxhh, d_dy, hipMemcpyDeviceToDevice), N, d_dagg_out);
-}
-int hank_jvp_income(hank_ctx *ctx, const double *dxhh, const double *dy, int32_t N, double *dagg_out) {
-    ENTER(ctx);
-    int rc = income_args(ctx, dxhh, dy, N, dagg_out, true);
-    if (!rc) rc = enqueue_tan_raw(ctx, income_req(dxhh, dy, hipMemcpyHostToDevice), N, nullptr);
-    if (rc) return rc;
-    return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
-}
+int hank_jvp_shock_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dbeta, int32_t N, double *d_dagg_out) { return jvp_path(ctx, PATH_DISCOUNT, d_dxhh, d_dbeta, N, d_dagg_out, true); }
+int hank_jvp_shock(hank_ctx *ctx, const double *dxhh, const double *dbeta, int32_t N, double *dagg_out) { return jvp_path(ctx, PATH_DISCOUNT, dxhh, dbeta, N, dagg_out, false); }
+int hank_jvp_income_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dy, int32_t N, double *d_dagg_out) { return jvp_path(ctx, PATH_INCOME, d_dxhh, d_dy, N, d_dagg_out, true); }
+int hank_jvp_income(hank_ctx *ctx, const double *dxhh, const double *dy, int32_t N, double *dagg_out) { return jvp_path(ctx, PATH_INCOME, dxhh, dy, N, dagg_out, false); }
 
 static int run_fused(hank_ctx *ctx, TanWork &w) {
     const int grc = ensure_dual_graphs(ctx, w);
@@ -2560,16 +2527,21 @@ static int stationary_record(hank_ctx *ctx, const char *name) {
 // (outputs 0 .. n_het-1 of hank_get_het_outputs; output 0 is the same arithmetic as n_het == 0, bit for bit); groups: hank_fake_news_group
 // (the context's K group outputs: the same policy responses and impulses, the outputs served GRP_FN_CHUNK at a time so the expectation
 // workspace never holds more — steps 3 and 4 run once per chunk, once in all for the other two entries).
-// shock (hank_fake_news_shock; with n_het >= 1): ONE direction in place of the n_hh inputs' — the backward sweep seeded with
-// d beta_{P-1} = 1 (hank_shock.h) — and no direct term: F (P, P, n_het), Dv (P, n_het).
-// income (hank_fake_news_income; with n_het = 1, 2): n_e directions in place of the inputs' — the backward sweep seeded with
-// d y_{P-1}[e] = 1 in direction e (hank_income.h) — and the direct term m_ss[e] of consumption at lag 0: F (P, P, n_e, n_het), Dv (P, n_e, n_het).
-static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, double *Dv_out, bool shock = false, bool income = false) {
-    const char *name = income ? "hank_fake_news_income" : shock ? "hank_fake_news_shock" : groups ? "hank_fake_news_group" : n_het ? "hank_fake_news_het" : "hank_fake_news";
+// kind: the derivative with respect to a path kind's values, its directions in place of the n_hh inputs' —
+// PATH_DISCOUNT (hank_fake_news_shock; with n_het >= 1): ONE direction, the backward sweep seeded with d beta_{P-1} = 1 (hank_shock.h),
+// and no direct term: F (P, P, n_het), Dv (P, n_het);
+// PATH_INCOME (hank_fake_news_income; with n_het = 1, 2): n_e directions, the backward sweep seeded with d y_{P-1}[e] = 1 in direction e
+// (hank_income.h), and the direct term m_ss[e] of consumption at lag 0: F (P, P, n_e, n_het), Dv (P, n_e, n_het).
+static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, double *Dv_out, PathKind kind = PATH_NONE) {
+    const bool inputs = kind == PATH_NONE;      // the directions are the n_hh inputs'
+    const char *name = !inputs ? PATHS[kind].fn : groups ? "hank_fake_news_group" : n_het ? "hank_fake_news_het" : "hank_fake_news";
     { const int prc = path_refuses(ctx, name); if (prc) return prc; }
     { const int nrc = stationary_record(ctx, name); if (nrc) return nrc; }
     const Consts &c = ctx->c;
-    const int P = c.P, G = c.G, N = income ? c.n_e : shock ? 1 : c.n_hh, NP = P * N, S = 16, nout = groups ? ctx->grp.K : n_het ? n_het : 1;
+    // the input, described once: the batch width N; the direct term of its direction k in output o at lag 0 — dsum of the record kernels
+    // (hd) for the inputs, the column mass m_ss[k] (hm) in consumption for y[k], none for beta; below, its seed and its backward graph
+    const int P = c.P, G = c.G, N = inputs ? c.n_hh : path_width(c, kind), NP = P * N, S = 16, nout = groups ? ctx->grp.K : n_het ? n_het : 1;
+    const bool direct_hd = inputs && (groups || n_het), direct_hm = kind == PATH_INCOME;
     const int cap = groups ? std::min(nout, GRP_FN_CHUNK) : nout;      // outputs per pass
     hipStream_t s = ctx->stream;
     { const int src = ensure_seg(ctx); if (src) return src; }
@@ -2580,37 +2552,45 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
     if (rc) return rc;
     TanWork &w = *wp;
     rc = ensure_tan_graphs(ctx, w, false, 0);
-    if (!rc && shock) rc = ensure_shock_tan_graph(ctx, w);
-    if (!rc && income) rc = ensure_income_tan_graph(ctx, w);
+    if (!rc && !inputs) rc = ensure_path_tan_graph(ctx, w, kind);
     if (rc) return rc;
+    const GraphExec &back = inputs ? w.tan_back(false) : w.seed[kind].g_tback;
     rc = ensure_fn(ctx, cap, N);
     if (rc) return rc;
     HIPC(ctx, join_side(ctx));      // D_1 and the {w, ig D} records come from the primal's forward sweep
-    std::vector<double> hm;         // income: the steady state's column masses, the direct term of consumption
-    if (income) {      // no input moves; d y_{P-1}[e] = 1 in direction e, (n_e, P, n_e) column-major
+    std::vector<double> hm(direct_hm ? N : 0);         // income: the steady state's column masses, the direct term of consumption
+    switch (kind) {
+    case PATH_INCOME: {      // no input moves; d y_{P-1}[e] = 1 in direction e, (n_e, P, n_e) column-major
         std::vector<double> seed((size_t)N * P * N, 0.0);
         for (int e = 0; e < N; e++) seed[(size_t)e + (size_t)N * ((size_t)(P - 1) + (size_t)P * e)] = 1.0;
-        hm.resize(N);
         rc = ensure_inc_mass(ctx);
         if (rc) return rc;
         HIPC(ctx, hipMemsetAsync(w.dxhh, 0, sizeof(double) * c.n_hh * P * N, s));
-        HIPC(ctx, hipMemcpyAsync(w.inc_in, seed.data(), sizeof(double) * seed.size(), hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync(w.seed[kind].in, seed.data(), sizeof(double) * seed.size(), hipMemcpyHostToDevice, s));
         HIPC(ctx, hipMemcpyAsync(hm.data(), ctx->d_inc_m, sizeof(double) * N, hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));      // (seed is this block's)
-    } else if (shock) {      // no input moves; d beta_{P-1} = 1 (the batch is one direction wide: (P, 1) column-major is [P])
+        break;
+    }
+    case PATH_DISCOUNT: {      // no input moves; d beta_{P-1} = 1 (the batch is one direction wide: (P, 1) column-major is [P])
         static const double one = 1.0;
         HIPC(ctx, hipMemsetAsync(w.dxhh, 0, sizeof(double) * c.n_hh * P, s));
-        HIPC(ctx, hipMemsetAsync(w.shk_in, 0, sizeof(double) * P, s));
-        HIPC(ctx, hipMemcpyAsync(w.shk_in.get() + (P - 1), &one, sizeof(double), hipMemcpyHostToDevice, s));
-    } else
-        hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P);
-    HIPC(ctx, hipGraphLaunch(income ? w.g_tback_inc : shock ? w.g_tback_shk : w.tan_back(false), s));
+        HIPC(ctx, hipMemsetAsync(w.seed[kind].in, 0, sizeof(double) * P, s));
+        HIPC(ctx, hipMemcpyAsync(w.seed[kind].in.get() + (P - 1), &one, sizeof(double), hipMemcpyHostToDevice, s));
+        break;
+    }
+    case PATH_NONE: hipLaunchKernelGGL(k_fn_seed, dim3((unsigned)((N * P * N + 255) / 256)), dim3(256), 0, s, w.dxhh, N, P); break;
+    }
+    HIPC(ctx, hipGraphLaunch(back, s));
     batch_none(ctx);      // (w.dpol no longer belongs to a caller's batch)
     // 2. the lottery impulse of every lag and input at once
     hipLaunchKernelGGL(k_fn_transpose, dim3((unsigned)((G + 31) / 32), (unsigned)((P + 31) / 32), (unsigned)N), dim3(256), 0, s, w.dpol, P, G, N, ctx->fn.dpT);
     hipLaunchKernelGGL(k_fn_impulse, dim3((unsigned)c.n_a, (unsigned)((NP + 255) / 256)), dim3(256), 0, s, c, ctx->R, ctx->fn.dpT, NP, ctx->fn.iota);
     const size_t PG = (size_t)P * G;
     std::vector<double> hF((size_t)cap * P * NP), hD((size_t)cap * NP), hd((size_t)cap * N, 0.0);
+    auto direct = [&](int o, int k) -> const double * {      // the direct term of direction k in output o of a pass, or none
+        if (direct_hm) return o == 1 ? &hm[k] : nullptr;      // (y_t[e]'s is m_ss[e], in consumption; beta has none in any output)
+        return direct_hd && (groups || o > 0) ? &hd[(size_t)k + (size_t)N * o] : nullptr;
+    };
     for (int o0 = 0; o0 < nout; o0 += cap) {
         const int nh = std::min(cap, nout - o0);
         const int kchunk = ((G + S - 1) / S + 15) / 16 * 16, MP = nh * P;
@@ -2637,7 +2617,7 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
         HIPC(ctx, hipGetLastError());
         HIPC(ctx, hipMemcpyAsync(hF.data(), ctx->fn.F, sizeof(double) * MP * NP, hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipMemcpyAsync(hD.data(), ctx->fn.Dv, sizeof(double) * nh * NP, hipMemcpyDeviceToHost, s));
-        if ((groups || n_het) && !shock && !income) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * nh * N, hipMemcpyDeviceToHost, s));
+        if (direct_hd) HIPC(ctx, hipMemcpyAsync(hd.data(), ctx->fn.dsum, sizeof(double) * nh * N, hipMemcpyDeviceToHost, s));
         HIPC(ctx, hipStreamSynchronize(s));
         if (o0 == 0) {
             rc = device_verdict(ctx, THE_RECORD);
@@ -2646,15 +2626,16 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
         // column n' = t*N + k of the device arrays is lag j = P-1-t of input k; the same-period effect d_{o,k} lands at lag 0
         // (output 0 of the het outputs has none; a group's is zero unless its base is consumption)
         for (int o = 0; o < nh; o++)
-            for (int k = 0; k < N; k++)
+            for (int k = 0; k < N; k++) {
+                const double *dk = direct(o, k);
                 for (int t = 0; t < P; t++) {
                     const int j = P - 1 - t;
-                    const size_t kc = (size_t)k + (size_t)N * o, ko = (size_t)k + (size_t)N * (o0 + o);
+                    const size_t ko = (size_t)k + (size_t)N * (o0 + o);
                     const double dv = hD[(size_t)o * NP + (size_t)t * N + k];
-                    // (beta has no direct term in any output; y_t[e]'s is m_ss[e], in consumption)
-                    Dv_out[j + (size_t)P * ko] = (income && o == 1 && j == 0) ? dv + hm[k] : (!shock && !income && (groups || o > 0) && j == 0) ? dv + hd[kc] : dv;
+                    Dv_out[j + (size_t)P * ko] = dk && j == 0 ? dv + *dk : dv;
                     for (int u = 0; u < P; u++) F_out[u + (size_t)P * (j + (size_t)P * ko)] = hF[((size_t)o * P + u) * NP + (size_t)t * N + k];
                 }
+            }
     }
     ctx->errmsg[0] = 0;
     return HANK_OK;
@@ -2680,7 +2661,7 @@ int hank_fake_news_shock(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv
     ENTER(ctx);
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     const int rc = het_count_ok(ctx, "hank_fake_news_shock", n_het, false);
-    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, true);
+    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, PATH_DISCOUNT);
 }
 
 // (KrusellSmith.jl:59-62, :66-80, BackwardIteration.jl:90-113; the recursion of SteadyStateJacobian.jl:363-371 with the input fixed to y[e])
@@ -2688,7 +2669,7 @@ int hank_fake_news_income(hank_ctx *ctx, int32_t n_het, double *F_out, double *D
     ENTER(ctx);
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     const int rc = het_count_ok(ctx, "hank_fake_news_income", n_het, false, n_het <= 2);
-    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, false, true);
+    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, PATH_INCOME);
 }
 
 #ifdef HANK_XSTAMP
@@ -2934,13 +2915,13 @@ static int capture_cot_graph_ag(hank_ctx *ctx, CotWork &w) {
 
 // the two graphs of a width, captured the first time hank_vjp runs at it: Sweep A (NX = 0) and Sweep B (P launches,
 // t = 0 .. P-1, then the fixed-order reduction of the inputs' cotangents)
-// shock (hank_vjp_shock; hank_shock.h): Sweep B with beta_bar_t's partials behind every period's launch, while that period's mu_t is in
-// the state the launch read — the same launches of k_adj_egm and k_adj_out, P + 2 more: w.g_BS
+// kind: Sweep B with a path kind's cotangent — beta_bar_t (hank_vjp_shock; hank_shock.h: k_shk_bbar), y_bar_t (hank_vjp_income; hank_income.h:
+// k_inc_ybar) — as partials behind every period's launch, while that period's mu_t is in the state the launch read, then their reduction
+// and the caller's layout — the same launches of k_adj_egm and k_adj_out, P + 2 more, into w.path[kind].g_B. For y_bar the column masses
+// (ensure_inc_mass) are current before the graph is launched.
 static int shk_mc(int M) { int mc = 1; while (mc < M && mc < 64) mc <<= 1; return mc; }      // cotangent columns across k_shk_bbar's lanes
-// income (hank_vjp_income; hank_income.h; never with shock): y_bar_t's partials in the same place (k_inc_ybar), then their reduction and
-// k_inc_ybar_out — P + 2 more: w.g_BI. The column masses (ensure_inc_mass) are current before the graph is launched.
 template <typename VT>
-static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, bool shock, bool income = false) {
+static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, PathKind kind) {
     const Consts &c = ctx->c;
     const int P = c.P, M = w.N, MC = shk_mc(M), IMC = std::min(MC, INC_MC);
     hipStream_t s = ctx->own_stream;
@@ -2948,37 +2929,36 @@ static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, bool shock, bool incom
     const size_t ldsB = adj_lds_egm(c, w.g, w.V);
     VT *st[2] = {reinterpret_cast<VT *>(w.st[0].get()), reinterpret_cast<VT *>(w.st[1].get())};
     VT *pbar = reinterpret_cast<VT *>(w.pbar.get());
+    PathCot &pc = w.path[kind];
     HIPC(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     int cur = 0;
     for (int t = 0; t < P; t++) {
         hipLaunchKernelGGL((k_adj_egm<VT>), grd, blk, ldsB, s, c, ctx->R, w.g, t, t == 0 ? 1 : 0, t == P - 1 ? 1 : 0, ctx->d_adj_sb, st[cur], st[cur ^ 1], pbar,
                            reinterpret_cast<VT *>(w.partS.get()), reinterpret_cast<VT *>(w.partM.get()));
-        if (shock)
-            hipLaunchKernelGGL(k_shk_bbar, dim3((unsigned)w.g.nb, (unsigned)((M + MC - 1) / MC)), dim3(SHK_BT), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->d_beta.get(), w.g.R, MC, t,
-                               t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, w.bb_part.get() + (size_t)t * w.g.nb * M);
-        if (income)
+        if (kind == PATH_DISCOUNT)
+            hipLaunchKernelGGL(k_shk_bbar, dim3((unsigned)w.g.nb, (unsigned)((M + MC - 1) / MC)), dim3(SHK_BT), 0, s, c, ctx->R, ctx->d_xhh.get(), ctx->exo[PATH_DISCOUNT].d.get(), w.g.R, MC, t,
+                               t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, pc.part.get() + (size_t)t * w.g.nb * M);
+        if (kind == PATH_INCOME)
             hipLaunchKernelGGL(k_inc_ybar, dim3((unsigned)w.g.nb, (unsigned)((M + IMC - 1) / IMC)), dim3(INC_BT), inc_ybar_lds(c, w.g.R, IMC), s, c, ctx->R, ctx->d_xhh.get(),
-                               w.g.R, IMC, t, t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, w.yb_part.get() + (size_t)t * w.g.nb * c.n_e * M);
+                               w.g.R, IMC, t, t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, pc.part.get() + (size_t)t * w.g.nb * c.n_e * M);
         cur ^= 1;
     }
     hipLaunchKernelGGL(k_adj_out, dim3((unsigned)((P * w.N + 255) / 256)), dim3(256), 0, s, P, c.n_hh, w.N, w.g.nb, ctx->d_xhh, w.partS, w.partM, w.yb1,
                        ctx->d_agg + P, ctx->d_zd, w.xbar);
-    if (income) {
-        const int W = c.n_e * M;
-        hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (unsigned)((W + 63) / 64)), dim3(256), 0, s, w.yb_part.get(), w.g.nb, W, w.yb_rm.get());
-        hipLaunchKernelGGL(k_inc_ybar_out, dim3((unsigned)(((size_t)P * c.n_e * M + 255) / 256)), dim3(256), 0, s, P, c.n_e, M, w.yb_rm.get(),
-                           ctx->d_inc_m.get(), w.yb1.get(), w.yb_cm.get());
-    }
-    if (shock) {
-        hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (unsigned)((M + 63) / 64)), dim3(256), 0, s, w.bb_part.get(), w.g.nb, M, w.bb_rm.get());
-        hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, w.bb_rm.get(), P, M, w.bb_cm.get());
-    }
-    return end_capture(ctx, income ? &w.g_BI : shock ? &w.g_BS : &w.g_B);
+    const int W = path_width(c, kind) * M;
+    if (kind != PATH_NONE)
+        hipLaunchKernelGGL(k_reduce_parts, dim3((unsigned)P, (unsigned)((W + 63) / 64)), dim3(256), 0, s, pc.part.get(), w.g.nb, W, pc.rm.get());
+    if (kind == PATH_INCOME)
+        hipLaunchKernelGGL(k_inc_ybar_out, dim3((unsigned)(((size_t)P * c.n_e * M + 255) / 256)), dim3(256), 0, s, P, c.n_e, M, pc.rm.get(),
+                           ctx->d_inc_m.get(), w.yb1.get(), pc.cm.get());
+    if (kind == PATH_DISCOUNT)
+        hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, pc.rm.get(), P, M, pc.cm.get());
+    return end_capture(ctx, &pc.g_B);
 }
 template <typename VT>
 static int capture_cot_graphs(hank_ctx *ctx, CotWork &w) {
     const int rc = capture_cot_graph_a<VT, 0>(ctx, w, AdjHx<VT, 0>{}, &w.g_A);
-    return rc ? rc : capture_cot_graph_b<VT>(ctx, w, false);
+    return rc ? rc : capture_cot_graph_b<VT>(ctx, w, PATH_NONE);
 }
 
 // Sweep B's segment starts belong to the record (like seg_valid): built before the first hank_vjp at a record, by whichever family wrote it
@@ -3014,17 +2994,29 @@ static int ensure_hx_record(hank_ctx *ctx) {
 // hank_vjp[_dev], hank_vjp_het[_dev]: M cotangent columns from the caller (kind: where they live) through the transposed sweeps
 // at the recorded primal, whichever family recorded it. Touches neither the record nor the tangent batch nor the primal memo.
 // n_het > 2: Sweep A's graph with NX = n_het - 2 extra outputs, and their direct terms after Sweep B.
-// d_vend_bar, d_D0_bar (hank_vjp_boundary; device pointers, (G, M) column-major, either may be null): the cotangents of the terminal
-// value and of the initial distribution, exported from the sweeps' states (hank_boundary.h) — everything else is the same work.
-// grp_bar (hank_vjp_group; (P, K, M) column-major, where `kind` says): cotangents on the context's group outputs — Sweep A's graph
-// with the groups, and their direct terms after Sweep B; agg_bar may then be null (n_het = 0: no cotangent on outputs 0 and 1).
-// d_beta_bar (hank_vjp_shock; a device pointer, (P, M) column-major): the cotangent of the discount-factor path, reduced in Sweep B.
-// income (hank_vjp_income; never with shock): d_beta_bar is then y_bar, (n_e, P, M) column-major, the cotangent of the income path.
-static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcpyKind kind, int M, double *d_xhh_bar, CotWork **out,
-                       double *d_vend_bar = nullptr, double *d_D0_bar = nullptr, const double *grp_bar = nullptr, double *d_beta_bar = nullptr, bool shock = false,
-                       bool income = false) {
+// One request to them, as TanReq is one to the tangent sweeps: an entry names the options it sets.
+struct CotReq {
+    int n_het;                        // the outputs agg_bar covers (the entry's rule has checked the count)
+    const double *agg_bar;            // (P, n_het, M) column-major, where `kind` says; null (hank_vjp_group with n_het = 0): no cotangent on outputs 0 and 1
+    hipMemcpyKind kind;
+    int M;
+    double *d_xhh_bar;                // a device pointer for the inputs' cotangents, or null: the entry copies them from the workspace
+    // hank_vjp_boundary (device pointers, (G, M) column-major, either may be null): the cotangents of the terminal value and of the initial
+    // distribution, exported from the sweeps' states (hank_boundary.h) — everything else is the same work
+    double *d_vend_bar = nullptr, *d_D0_bar = nullptr;
+    // hank_vjp_group ((P, K, M) column-major, where `kind` says): cotangents on the context's group outputs — Sweep A's graph with the
+    // groups, and their direct terms after Sweep B
+    const double *grp_bar = nullptr;
+    PathKind path = PATH_NONE;        // hank_vjp_shock, hank_vjp_income: Sweep B from the kind's graph, which reduces the path's cotangent
+    double *d_path_bar = nullptr;     // a device pointer for it — beta_bar (P, M), y_bar (n_e, P, M), column-major — or null: the entry copies it from the workspace
+};
+static int enqueue_vjp(hank_ctx *ctx, const CotReq &q, CotWork **out) {
     const Consts &c = ctx->c;
     const size_t P = c.P;
+    const int n_het = q.n_het, M = q.M;
+    const double *agg_bar = q.agg_bar, *grp_bar = q.grp_bar;
+    double *d_vend_bar = q.d_vend_bar, *d_D0_bar = q.d_D0_bar;
+    const hipMemcpyKind kind = q.kind;
     const int NX = n_het > 2 ? n_het - 2 : 0, K = grp_bar ? ctx->grp.K : 0;
     CotWork *w = nullptr;
     int rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
@@ -3042,24 +3034,17 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
         rc = w->V == 2 ? capture_cot_graphs<double2>(ctx, *w) : capture_cot_graphs<double>(ctx, *w);
         if (rc) return rc;
     }
-    if (shock && !w->g_BS) {
-        if (!w->bb_cm) {
-            HIPC(ctx, w->bb_part.alloc(P * (size_t)w->g.nb * M));
-            HIPC(ctx, w->bb_rm.alloc(P * M));
-            HIPC(ctx, w->bb_cm.alloc(P * M));      // (last: a failed allocation is tried again by the next call)
-        }
-        rc = w->V == 2 ? capture_cot_graph_b<double2>(ctx, *w, true) : capture_cot_graph_b<double>(ctx, *w, true);
-        if (rc) return rc;
-    }
-    if (income && inc_ybar_lds(c, w->g.R, std::min(shk_mc(M), INC_MC)) > ctx->lds_max)
+    if (q.path == PATH_INCOME && inc_ybar_lds(c, w->g.R, std::min(shk_mc(M), INC_MC)) > ctx->lds_max)
         return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_income: n_e=%d needs more LDS per workgroup than the device has", c.n_e);
-    if (income && !w->g_BI) {
-        if (!w->yb_cm) {
-            HIPC(ctx, w->yb_part.alloc(P * (size_t)w->g.nb * c.n_e * M));
-            HIPC(ctx, w->yb_rm.alloc(P * c.n_e * M));
-            HIPC(ctx, w->yb_cm.alloc(P * c.n_e * M));      // (last: a failed allocation is tried again by the next call)
+    PathCot &pc = w->path[q.path];      // ([PATH_NONE]: the plain Sweep B, captured above)
+    const size_t PWM = P * path_width(c, q.path) * M;
+    if (!pc.g_B) {
+        if (!pc.cm) {
+            HIPC(ctx, pc.part.alloc(PWM * w->g.nb));
+            HIPC(ctx, pc.rm.alloc(PWM));
+            HIPC(ctx, pc.cm.alloc(PWM));      // (last: a failed allocation is tried again by the next call)
         }
-        rc = w->V == 2 ? capture_cot_graph_b<double2>(ctx, *w, false, true) : capture_cot_graph_b<double>(ctx, *w, false, true);
+        rc = w->V == 2 ? capture_cot_graph_b<double2>(ctx, *w, q.path) : capture_cot_graph_b<double>(ctx, *w, q.path);
         if (rc) return rc;
     }
     hipStream_t s = ctx->stream;
@@ -3067,7 +3052,7 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     if (K > 0) HIPC(ctx, hipMemcpyAsync(w->gin, grp_bar, sizeof(double) * P * K * M, kind, s));
     HIPC(ctx, join_side(ctx));      // D_t, the lottery and the grid aggregates come from the primal's forward sweep
     rc = ensure_adj_seg(ctx);
-    if (!rc && income) rc = ensure_inc_mass(ctx);
+    if (!rc && q.path == PATH_INCOME) rc = ensure_inc_mass(ctx);
     if (rc) return rc;
     if (K > 0) {
         rc = ensure_grp_record(ctx);      // (before the capture, as below; the CONS sums read D_t)
@@ -3099,16 +3084,15 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
     const dim3 tblk(BND_T, 8), tgrd((unsigned)((c.n_a + BND_T - 1) / BND_T), (unsigned)((M + BND_T - 1) / BND_T), (unsigned)c.n_e);      // the layout kernel
     // Sweep A's state after its last launch (t = 0) is the cotangent of D_0; Sweep B's first launches overwrite it
     if (d_D0_bar) hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_D0_bar);
-    HIPC(ctx, hipGraphLaunch(income ? w->g_BI : shock ? w->g_BS : w->g_B, s));
+    HIPC(ctx, hipGraphLaunch(pc.g_B, s));
     if (d_vend_bar) {      // Sweep B's last launch (t = P-1) read mu_{P-1} from st[(P-1) & 1] and wrote no state: mu_P goes where it would have
         hipLaunchKernelGGL(k_bnd_vend, dim3((unsigned)(((size_t)c.n_a * M + 255) / 256)), dim3(256), 0, s, c, ctx->R, (int)P - 1, P == 1 ? 1 : 0, ctx->d_adj_sb.get(),
                            w->st[(P - 1) & 1].get(), w->pbar.get(), (size_t)M, w->st[P & 1].get());
         hipLaunchKernelGGL(k_bnd_out, tgrd, tblk, 0, s, w->st[P & 1].get(), c.n_a, c.n_e, M, d_vend_bar);
     }
     HIPC(ctx, hipGetLastError());
-    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1 + (d_D0_bar ? 1 : 0) + (d_vend_bar ? 2 : 0) + ((shock || income) ? (int)P + 2 : 0)));
-    if (d_beta_bar && income) HIPC(ctx, hipMemcpyAsync(d_beta_bar, w->yb_cm, sizeof(double) * P * c.n_e * M, hipMemcpyDeviceToDevice, s));
-    else if (d_beta_bar) HIPC(ctx, hipMemcpyAsync(d_beta_bar, w->bb_cm, sizeof(double) * P * M, hipMemcpyDeviceToDevice, s));
+    HIPC(ctx, ctx->spans.end(VJP_B, s, (int)P + 1 + (d_D0_bar ? 1 : 0) + (d_vend_bar ? 2 : 0) + (q.path != PATH_NONE ? (int)P + 2 : 0)));
+    if (q.d_path_bar) HIPC(ctx, hipMemcpyAsync(q.d_path_bar, pc.cm, sizeof(double) * PWM, hipMemcpyDeviceToDevice, s));
     if (NX > 0) {
         hipLaunchKernelGGL(k_adj_hx_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, (int)P, c.n_hh, M, NX, hx_count(ctx), w->ybx.get(),
                            ctx->hx.S.get(), w->xbar.get());
@@ -3119,7 +3103,7 @@ static int enqueue_vjp(hank_ctx *ctx, int n_het, const double *agg_bar, hipMemcp
         HIPC(ctx, hipGetLastError());
     }
     cot_ran(ctx, w, M, w->pbar);
-    if (d_xhh_bar) HIPC(ctx, hipMemcpyAsync(d_xhh_bar, w->xbar, sizeof(double) * c.n_hh * P * M, hipMemcpyDeviceToDevice, s));
+    if (q.d_xhh_bar) HIPC(ctx, hipMemcpyAsync(q.d_xhh_bar, w->xbar, sizeof(double) * c.n_hh * P * M, hipMemcpyDeviceToDevice, s));
     *out = w;
     return HANK_OK;
 }
@@ -3165,7 +3149,13 @@ static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *
     int rc = args(ctx, n_het, agg_bar, M, xhh_bar);
     if (rc) return rc;
     CotWork *w = nullptr;
-    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, value_end_bar, D_init_bar, grp_bar);
+    CotReq q{n_het, agg_bar, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, M, dev ? xhh_bar : nullptr};
+    q.grp_bar = grp_bar;
+    if (dev) {
+        q.d_vend_bar = value_end_bar;
+        q.d_D0_bar = D_init_bar;
+        return enqueue_vjp(ctx, q, &w);
+    }
     const size_t GM = (size_t)ctx->c.G * M;
     if (value_end_bar || D_init_bar) {
         rc = tan_cache_get(ctx, ctx->cws, M, [ctx](CotWork &cw) { return build_cotwork(ctx, cw); }, &w);
@@ -3175,8 +3165,9 @@ static int vjp_boundary(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *
             HIPC(ctx, w->bnd_dbar.alloc(GM));
         }
     }
-    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, value_end_bar ? w->bnd_vbar.get() : nullptr, D_init_bar ? w->bnd_dbar.get() : nullptr,
-                     grp_bar);
+    if (value_end_bar) q.d_vend_bar = w->bnd_vbar.get();
+    if (D_init_bar) q.d_D0_bar = w->bnd_dbar.get();
+    rc = enqueue_vjp(ctx, q, &w);
     if (rc) return rc;
     HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
     if (value_end_bar) HIPC(ctx, hipMemcpyAsync(value_end_bar, w->bnd_vbar, sizeof(double) * GM, hipMemcpyDeviceToHost, ctx->stream));
@@ -3189,36 +3180,23 @@ static int vjp(hank_ctx *ctx, int (*args)(hank_ctx *, int, const void *, int, co
     return vjp_boundary(ctx, args, n_het, agg_bar, M, xhh_bar, nullptr, nullptr, dev);
 }
 
-// hank_vjp_shock[_dev]: hank_vjp_het's rule and work, Sweep B from the graph with beta_bar's reduction
-static int vjp_shock(hank_ctx *ctx, int n_het, const double *agg_bar, int M, double *xhh_bar, double *beta_bar, bool dev) {
+// hank_vjp_shock[_dev], hank_vjp_income[_dev]: the kind's rule (PathTraits::vjp_rule — hank_vjp_het's for beta_bar; hank_vjp's, n_het 1 or 2,
+// for y_bar — then path_entry_excluded), the same work, Sweep B from the kind's graph with the path cotangent's reduction
+static int vjp_path(hank_ctx *ctx, PathKind kind, int n_het, const double *agg_bar, int M, double *xhh_bar, double *path_bar, bool dev) {
     ENTER(ctx);
-    if (ctx && !beta_bar) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_shock: beta_bar is required");
-    int rc = vjp_het_args(ctx, n_het, agg_bar, M, xhh_bar);
+    const PathTraits &pt = PATHS[kind];
+    if (ctx && !path_bar) return fail(ctx, HANK_ERR_BAD_ARG, "%s: %s is required", pt.vjp, pt.bar);
+    int rc = pt.vjp_rule(ctx, n_het, agg_bar, M, xhh_bar);
+    if (!rc) rc = path_entry_excluded(ctx, kind, pt.vjp);
     if (rc) return rc;
     CotWork *w = nullptr;
-    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, nullptr, nullptr, nullptr, beta_bar, true);
-    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, nullptr, nullptr, nullptr, nullptr, true);
-    if (rc) return rc;
+    CotReq q{n_het, agg_bar, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, M, dev ? xhh_bar : nullptr};
+    q.path = kind;
+    if (dev) q.d_path_bar = path_bar;
+    rc = enqueue_vjp(ctx, q, &w);
+    if (rc || dev) return rc;
     HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipMemcpyAsync(beta_bar, w->bb_cm, sizeof(double) * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->errmsg[0] = 0;
-    return HANK_OK;
-}
-
-// hank_vjp_income[_dev]: hank_vjp's rule and work (n_het 1 or 2), Sweep B from the graph with y_bar's reduction
-static int vjp_income(hank_ctx *ctx, int n_het, const double *agg_bar, int M, double *xhh_bar, double *y_bar, bool dev) {
-    ENTER(ctx);
-    if (ctx && !y_bar) return fail(ctx, HANK_ERR_BAD_ARG, "hank_vjp_income: y_bar is required");
-    int rc = vjp_args(ctx, n_het, agg_bar, M, xhh_bar);
-    if (rc) return rc;
-    if (ctx->beta_on) return fail(ctx, HANK_ERR_NOT_READY, "hank_vjp_income: a discount-factor path is set and the two exclude each other");
-    CotWork *w = nullptr;
-    if (dev) return enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyDeviceToDevice, M, xhh_bar, &w, nullptr, nullptr, nullptr, y_bar, false, true);
-    rc = enqueue_vjp(ctx, n_het, agg_bar, hipMemcpyHostToDevice, M, nullptr, &w, nullptr, nullptr, nullptr, nullptr, false, true);
-    if (rc) return rc;
-    HIPC(ctx, hipMemcpyAsync(xhh_bar, w->xbar, sizeof(double) * ctx->c.n_hh * ctx->c.P * M, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipMemcpyAsync(y_bar, w->yb_cm, sizeof(double) * ctx->c.P * ctx->c.n_e * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(path_bar, w->path[kind].cm, sizeof(double) * ctx->c.P * path_width(ctx->c, kind) * M, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     ctx->errmsg[0] = 0;
     return HANK_OK;
@@ -3226,11 +3204,11 @@ static int vjp_income(hank_ctx *ctx, int n_het, const double *agg_bar, int M, do
 
 extern "C" {
 // (KrusellSmith.jl:59-62, :66-80: where y enters; BackwardIteration.jl:90-113: the loop the transposed sweep reverses)
-int hank_vjp_income(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *y_bar) { return vjp_income(ctx, n_het, agg_bar, M, xhh_bar, y_bar, false); }
-int hank_vjp_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_y_bar) { return vjp_income(ctx, n_het, d_agg_bar, M, d_xhh_bar, d_y_bar, true); }
+int hank_vjp_income(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *y_bar) { return vjp_path(ctx, PATH_INCOME, n_het, agg_bar, M, xhh_bar, y_bar, false); }
+int hank_vjp_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_y_bar) { return vjp_path(ctx, PATH_INCOME, n_het, d_agg_bar, M, d_xhh_bar, d_y_bar, true); }
 // (KrusellSmith.jl:59-62: where beta enters; BackwardIteration.jl:90-113: the loop the transposed sweep reverses)
-int hank_vjp_shock(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *beta_bar) { return vjp_shock(ctx, n_het, agg_bar, M, xhh_bar, beta_bar, false); }
-int hank_vjp_shock_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_beta_bar) { return vjp_shock(ctx, n_het, d_agg_bar, M, d_xhh_bar, d_beta_bar, true); }
+int hank_vjp_shock(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *beta_bar) { return vjp_path(ctx, PATH_DISCOUNT, n_het, agg_bar, M, xhh_bar, beta_bar, false); }
+int hank_vjp_shock_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_beta_bar) { return vjp_path(ctx, PATH_DISCOUNT, n_het, d_agg_bar, M, d_xhh_bar, d_beta_bar, true); }
 int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar) {
     { const int irc = income_refuses(ctx, "hank_vjp_boundary"); if (irc) return irc; }
     return vjp_boundary(ctx, vjp_args, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);
@@ -3407,11 +3385,11 @@ static int assemble_het_outputs(hank_ctx *ctx, int n_het, int Nk, const double *
 // income (hank_get_het_outputs_income; n_het <= 2): dy (n_e, P, N) column-major, the income directions of the batch hank_jvp_income made, or
 // null — consumption's tangent gains sum_e dy_t[e,n] m_t[e]. Its level gains sum_e y_t[e] m_t[e] whenever a path is set, in either entry.
 static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t N, double *agg_out, double *dagg_out, bool dev, const double *dy = nullptr,
-                       bool income = false) {
+                       PathKind entry = PATH_NONE) {
     if (!ctx) return HANK_ERR_BAD_ARG;
     ENTER(ctx);
-    const char *who = income ? "hank_get_het_outputs_income" : "hank_get_het_outputs";
-    int rc = het_count_ok(ctx, who, n_het, true, N >= 0 && (agg_out || dagg_out) && !(income && n_het > 2));      // (N >= 0, an output array)
+    const char *who = entry == PATH_INCOME ? "hank_get_het_outputs_income" : "hank_get_het_outputs";
+    int rc = het_count_ok(ctx, who, n_het, true, N >= 0 && (agg_out || dagg_out) && !(entry == PATH_INCOME && n_het > 2));      // (N >= 0, an output array)
     if (!rc && n_het > 2) rc = income_refuses(ctx, who);      // (Value and UCE rebuild c from the inputs)
     if (rc) return rc;
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
@@ -3458,11 +3436,12 @@ static int het_outputs(hank_ctx *ctx, int32_t n_het, const double *dxhh, int32_t
     // (a batch with boundary seeds is served for n_het <= 2 only, above)
     rc = assemble_het_outputs(ctx, n_het, Nk, d_dx, b ? b->dagg_cm : nullptr, hxT, b ? b->bnd_zm : nullptr, d_a, tan ? d_da : nullptr);
     if (rc) return rc;
-    if (n_het == 2 && (ctx->inc_on || (tan && dy))) {      // the direct term of y_t[e] in consumption (hank_income.h)
+    const double *d_y = income_in_force(ctx);
+    if (n_het == 2 && (d_y || (tan && dy))) {      // the direct term of y_t[e] in consumption (hank_income.h)
         rc = ensure_inc_mass(ctx);
         if (rc) return rc;
         hipLaunchKernelGGL(k_inc_cons, dim3((unsigned)((P * ((size_t)Nk + 1) + 255) / 256)), dim3(256), 0, ctx->stream, (int)P, ctx->c.n_e, Nk,
-                           ctx->inc_on ? ctx->d_y.get() : (const double *)nullptr, tan ? dy : (const double *)nullptr, ctx->d_inc_m.get(), d_a, tan ? d_da : nullptr);
+                           d_y, tan ? dy : (const double *)nullptr, ctx->d_inc_m.get(), d_a, tan ? d_da : nullptr);
         HIPC(ctx, hipGetLastError());
     }
     if (!dev) {
@@ -3481,10 +3460,10 @@ int hank_get_het_outputs_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh,
 }
 // (KrusellSmith.jl:80: consumption is the budget residual, which gains y_t[e]; ForwardIteration.jl:303-307: the weighted dot)
 int hank_get_het_outputs_income(hank_ctx *ctx, int32_t n_het, const double *dxhh, const double *dy, int32_t N, double *agg_out, double *dagg_out) {
-    return het_outputs(ctx, n_het, dxhh, N, agg_out, dagg_out, false, dy, true);
+    return het_outputs(ctx, n_het, dxhh, N, agg_out, dagg_out, false, dy, PATH_INCOME);
 }
 int hank_get_het_outputs_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_dxhh, const double *d_dy, int32_t N, double *d_agg_out, double *d_dagg_out) {
-    return het_outputs(ctx, n_het, d_dxhh, N, d_agg_out, d_dagg_out, true, d_dy, true);
+    return het_outputs(ctx, n_het, d_dxhh, N, d_agg_out, d_dagg_out, true, d_dy, PATH_INCOME);
 }
 int hank_set_het_outputs(hank_ctx *ctx, int32_t n_het) {
     if (!ctx) return HANK_ERR_BAD_ARG;
@@ -3564,9 +3543,11 @@ static int group_outputs(hank_ctx *ctx, const double *dxhh, int32_t N, double *a
     if (N < 0 || !(agg_out || dagg_out)) return fail(ctx, HANK_ERR_BAD_ARG, "hank_get_group_outputs: bad argument: N must be >= 0 and an output array given");
     const int K = ctx->grp.K;
     if (K == 0) return fail(ctx, HANK_ERR_NOT_READY, "hank_get_group_outputs: no groups are set: call hank_set_group_outputs first");
-    if (ctx->inc_on)      // (a consumption group rebuilds c from the inputs)
-        for (int k = 0; k < K; k++)
-            if (((ctx->grp.codes >> (2 * k)) & 3) == HANK_GROUP_CONS) return income_refuses(ctx, "hank_get_group_outputs with a HANK_GROUP_CONS group");
+    for (int k = 0; k < K; k++)      // (a consumption group rebuilds c from the inputs)
+        if (((ctx->grp.codes >> (2 * k)) & 3) == HANK_GROUP_CONS) {
+            const int irc = income_refuses(ctx, "hank_get_group_outputs with a HANK_GROUP_CONS group");
+            if (irc) return irc;
+        }
     if (!ctx->primal_done) return fail(ctx, HANK_ERR_NOT_READY, "no primal sweep has been run");
     const size_t P = ctx->c.P, nh = ctx->c.n_hh;
     const bool tan = dagg_out && N > 0;
