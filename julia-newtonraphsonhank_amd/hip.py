@@ -2,10 +2,17 @@
 
 There is no CPU fallback on this path: if the shared library is missing or no MI355X is usable the
 constructors raise — the product never silently computes the household block anywhere else.
+
+Every fact of the boundary has one owner here. `ABI` is the C ABI, one row per symbol (tests/test_abi.py holds it against the header
+by arity and parameter class); `load_library` applies it in one loop. The module functions under "argument shapes" own one shape
+each: a path or a batch of paths (`_batch`), a group of optional seeds (`_seeds`), output buffers and their clamp (`_out`, `_n1`),
+device pointers (`_dev`), a status (`_raise_status`); `HouseholdBlock` adds the ones that need its dimensions. `_PATHS` says what
+differs between the two exogenous paths. A new entry point is one row of `ABI` and one thin method.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from pathlib import Path
 
 import numpy as np
@@ -22,28 +29,6 @@ HANK_ERR_NOT_READY, HANK_ERR_NONMONOTONE, HANK_ERR_NOMEM, HANK_ERR_SWEEP, HANK_E
 HANK_VF_KRUSELL_SMITH = 0
 HANK_GROUP_MASS, HANK_GROUP_POLICY, HANK_GROUP_CONS = 0, 1, 2      # the base of a group output (hank_set_group_outputs)
 HANK_GROUP_MAX = 32
-
-# the symbols include/hank_hip.h declares (tests check that every one is exported)
-ABI_SYMBOLS = (
-    "hank_create", "hank_create_on", "hank_gather_columns", "hank_destroy", "hank_last_error", "hank_n_hh", "hank_set_stream", "hank_sync",
-    "hank_set_boundary", "hank_primal", "hank_jvp", "hank_primal_dev", "hank_jvp_dev", "hank_check",
-    "hank_primal_jvp", "hank_primal_jvp_dev",
-    "hank_get_policy_seq", "hank_get_dpolicy_seq", "hank_get_dist_seq", "hank_get_het_outputs", "hank_get_het_outputs_dev", "hank_set_het_outputs",
-    "hank_get_grid_aggregates", "hank_get_grid_aggregates_dev", "hank_backward_step",
-    "hank_backward_step_dual", "hank_forward_step", "hank_forward_step_dual", "hank_last_timings", "hank_stats", "hank_info", "hank_sweep_instance", "hank_vfi", "hank_stationary_dist", "hank_fake_news", "hank_fake_news_het", "hank_device_available",
-    "hank_vjp", "hank_vjp_dev", "hank_get_policy_cotangent_seq", "hank_last_vjp_timings", "hank_vjp_het", "hank_vjp_het_dev",
-    "hank_jvp_boundary", "hank_jvp_boundary_dev", "hank_vjp_boundary", "hank_vjp_boundary_dev",
-    "hank_jvp_het", "hank_jvp_het_dev", "hank_vjp_het_boundary", "hank_vjp_het_boundary_dev",
-    "hank_ss_jvp", "hank_ss_jvp_dev", "hank_ss_vjp", "hank_ss_vjp_dev", "hank_last_ss_timings",
-    "hank_primal_batch", "hank_primal_batch_dev", "hank_last_batch_timings",
-    "hank_ss_batch", "hank_last_ss_batch_timings",
-    "hank_get_lottery_record", "hank_get_forward_units",
-    "hank_set_group_outputs", "hank_get_group_outputs", "hank_get_group_outputs_dev", "hank_fake_news_group",
-    "hank_vjp_group", "hank_vjp_group_dev",
-    "hank_set_discount_path", "hank_jvp_shock", "hank_jvp_shock_dev", "hank_vjp_shock", "hank_vjp_shock_dev", "hank_fake_news_shock",
-    "hank_set_income_path", "hank_jvp_income", "hank_jvp_income_dev", "hank_vjp_income", "hank_vjp_income_dev", "hank_fake_news_income",
-    "hank_get_het_outputs_income", "hank_get_het_outputs_income_dev",
-)
 
 
 class HankHIPError(RuntimeError):
@@ -81,6 +66,62 @@ class hank_model(C.Structure):
                 ("beta", C.c_double), ("gamma", C.c_double), ("borrow_cons", C.c_double)]
 
 
+# -- the C ABI -------------------------------------------------------------------------------------------------------------------
+# One row per symbol of include/hank_hip.h: its parameters in order, one letter each. Every function returns a status (c_int)
+# except those in ABI_RESTYPE.
+_ARG = {"v": C.c_void_p,                    # a context, a stream, a device pointer, host memory that is not doubles
+        "d": C.POINTER(C.c_double),         # doubles on the host (double x[n] included)
+        "i": C.c_int32, "f": C.c_double,
+        "I": C.POINTER(C.c_int32), "L": C.POINTER(C.c_int64),
+        "m": C.POINTER(hank_model), "V": C.POINTER(C.c_void_p)}
+ABI = {name: tuple(_ARG[a] for a in row.split()) for name, row in {
+    # lifetime, stream, verdict
+    "hank_create": "m V", "hank_create_on": "m i V", "hank_destroy": "v", "hank_gather_columns": "V i V I v", "hank_last_error": "v",
+    "hank_n_hh": "v", "hank_device_available": "", "hank_set_stream": "v v", "hank_sync": "v", "hank_check": "v",
+    # boundary and the fused sweeps
+    "hank_set_boundary": "v d d", "hank_primal": "v d d", "hank_primal_dev": "v v v", "hank_jvp": "v d i d", "hank_jvp_dev": "v v i v",
+    "hank_primal_jvp": "v d d i d d", "hank_primal_jvp_dev": "v v v i v v",
+    # what the last sweeps left
+    "hank_get_policy_seq": "v d", "hank_get_dpolicy_seq": "v i d", "hank_get_dist_seq": "v d",
+    "hank_get_lottery_record": "v v d d v d", "hank_get_forward_units": "v v v",
+    "hank_set_het_outputs": "v i", "hank_get_het_outputs": "v i d i d d", "hank_get_het_outputs_dev": "v i v i v v",
+    "hank_get_het_outputs_income": "v i d d i d d", "hank_get_het_outputs_income_dev": "v i v v i v v",
+    "hank_get_grid_aggregates": "v d i d", "hank_get_grid_aggregates_dev": "v v i v",
+    "hank_last_timings": "v d I", "hank_stats": "v L", "hank_info": "v L", "hank_sweep_instance": "v I",
+    # granular steps, steady state, Toeplitz forms
+    "hank_backward_step": "v d d d d", "hank_backward_step_dual": "v d d d d i d d d d",
+    "hank_forward_step": "v d d d d", "hank_forward_step_dual": "v d d d d i d d d d",
+    "hank_vfi": "v d f i d d I d", "hank_stationary_dist": "v d d f i i I",
+    "hank_fake_news": "v d d", "hank_fake_news_het": "v i d d", "hank_fake_news_group": "v d d",
+    # the transposed block
+    "hank_vjp": "v i d i d", "hank_vjp_dev": "v i v i v", "hank_vjp_het": "v i d i d", "hank_vjp_het_dev": "v i v i v",
+    "hank_get_policy_cotangent_seq": "v i d", "hank_last_vjp_timings": "v d I",
+    # the boundary, every output in one pair of sweeps
+    "hank_jvp_boundary": "v d d d i d", "hank_jvp_boundary_dev": "v v v v i v",
+    "hank_vjp_boundary": "v i d i d d d", "hank_vjp_boundary_dev": "v i v i v v v",
+    "hank_jvp_het": "v i d d d i d", "hank_jvp_het_dev": "v i v v v i v",
+    "hank_vjp_het_boundary": "v i d i d d d", "hank_vjp_het_boundary_dev": "v i v i v v v",
+    # through the steady state
+    "hank_ss_jvp": "v i d i f i d d d d I d", "hank_ss_jvp_dev": "v i v i f i v v v v I d",
+    "hank_ss_vjp": "v i d d d i f i d I d", "hank_ss_vjp_dev": "v i v v v i f i v I d", "hank_last_ss_timings": "v d",
+    # scenarios
+    "hank_primal_batch": "v i d i d d I", "hank_primal_batch_dev": "v i v i v v", "hank_last_batch_timings": "v d",
+    "hank_ss_batch": "v i d i f i f i i d d d d I d I", "hank_last_ss_batch_timings": "v d",
+    # group outputs
+    "hank_set_group_outputs": "v i d I", "hank_get_group_outputs": "v d i d d", "hank_get_group_outputs_dev": "v v i v v",
+    "hank_vjp_group": "v i d d i d d d", "hank_vjp_group_dev": "v i v v i v v v",
+    # the exogenous paths (_PATHS)
+    "hank_set_discount_path": "v d", "hank_jvp_shock": "v d d i d", "hank_jvp_shock_dev": "v v v i v",
+    "hank_vjp_shock": "v i d i d d", "hank_vjp_shock_dev": "v i v i v v", "hank_fake_news_shock": "v i d d",
+    "hank_set_income_path": "v d", "hank_jvp_income": "v d d i d", "hank_jvp_income_dev": "v v v i v",
+    "hank_vjp_income": "v i d i d d", "hank_vjp_income_dev": "v i v i v v", "hank_fake_news_income": "v i d d",
+}.items()}
+ABI_RESTYPE = {"hank_last_error": C.c_char_p}
+ABI_OPTIONAL = frozenset({"hank_get_lottery_record", "hank_get_forward_units"})      # (an older library named by HANK_HIP_LIB for an A-B has none)
+# the symbols include/hank_hip.h declares (tests check that every one is exported)
+ABI_SYMBOLS = tuple(ABI)
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -95,98 +136,11 @@ def load_library() -> C.CDLL:
             f"{_LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     lib = C.CDLL(str(_LIB_PATH))
-    dp, vp, i32 = C.POINTER(C.c_double), C.c_void_p, C.c_int32
-    lib.hank_create.argtypes = [C.POINTER(hank_model), C.POINTER(vp)]
-    lib.hank_create_on.argtypes = [C.POINTER(hank_model), i32, C.POINTER(vp)]
-    lib.hank_destroy.argtypes = [vp]
-    lib.hank_gather_columns.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i32), vp]
-    lib.hank_last_error.argtypes = [vp]
-    lib.hank_last_error.restype = C.c_char_p
-    lib.hank_n_hh.argtypes = [vp]
-    lib.hank_set_stream.argtypes = [vp, vp]
-    lib.hank_sync.argtypes = [vp]
-    lib.hank_set_boundary.argtypes = [vp, dp, dp]
-    lib.hank_primal.argtypes = [vp, dp, dp]
-    lib.hank_jvp.argtypes = [vp, dp, i32, dp]
-    lib.hank_primal_dev.argtypes = [vp, vp, vp]
-    lib.hank_jvp_dev.argtypes = [vp, vp, i32, vp]
-    lib.hank_check.argtypes = [vp]
-    lib.hank_primal_jvp.argtypes = [vp, dp, dp, i32, dp, dp]
-    lib.hank_primal_jvp_dev.argtypes = [vp, vp, vp, i32, vp, vp]
-    lib.hank_get_policy_seq.argtypes = [vp, dp]
-    lib.hank_get_dpolicy_seq.argtypes = [vp, i32, dp]
-    lib.hank_get_dist_seq.argtypes = [vp, dp]
-    if hasattr(lib, "hank_get_lottery_record"):      # (an older library named by HANK_HIP_LIB for an A-B has none)
-        lib.hank_get_lottery_record.argtypes = [vp, vp, dp, dp, vp, dp]
-    if hasattr(lib, "hank_get_forward_units"):       # (likewise)
-        lib.hank_get_forward_units.argtypes = [vp, vp, vp]
-    lib.hank_get_het_outputs.argtypes = [vp, i32, dp, i32, dp, dp]
-    lib.hank_get_het_outputs_dev.argtypes = [vp, i32, vp, i32, vp, vp]
-    lib.hank_set_het_outputs.argtypes = [vp, i32]
-    lib.hank_get_grid_aggregates.argtypes = [vp, dp, i32, dp]
-    lib.hank_get_grid_aggregates_dev.argtypes = [vp, vp, i32, vp]
-    lib.hank_backward_step.argtypes = [vp, dp, dp, dp, dp]
-    lib.hank_backward_step_dual.argtypes = [vp, dp, dp, dp, dp, i32, dp, dp, dp, dp]
-    lib.hank_forward_step.argtypes = [vp, dp, dp, dp, dp]
-    lib.hank_forward_step_dual.argtypes = [vp, dp, dp, dp, dp, i32, dp, dp, dp, dp]
-    lib.hank_last_timings.argtypes = [vp, dp, C.POINTER(i32)]
-    lib.hank_stats.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.hank_info.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.hank_sweep_instance.argtypes = [vp, C.POINTER(i32)]
-    lib.hank_vfi.argtypes = [vp, dp, C.c_double, i32, dp, dp, C.POINTER(i32), dp]
-    lib.hank_stationary_dist.argtypes = [vp, dp, dp, C.c_double, i32, i32, C.POINTER(i32)]
-    lib.hank_fake_news.argtypes = [vp, dp, dp]
-    lib.hank_fake_news_het.argtypes = [vp, i32, dp, dp]
-    lib.hank_device_available.argtypes = []
-    lib.hank_vjp.argtypes = [vp, i32, dp, i32, dp]
-    lib.hank_vjp_dev.argtypes = [vp, i32, vp, i32, vp]
-    lib.hank_vjp_het.argtypes = [vp, i32, dp, i32, dp]
-    lib.hank_vjp_het_dev.argtypes = [vp, i32, vp, i32, vp]
-    lib.hank_get_policy_cotangent_seq.argtypes = [vp, i32, dp]
-    lib.hank_last_vjp_timings.argtypes = [vp, dp, C.POINTER(i32)]
-    lib.hank_jvp_boundary.argtypes = [vp, dp, dp, dp, i32, dp]
-    lib.hank_jvp_boundary_dev.argtypes = [vp, vp, vp, vp, i32, vp]
-    lib.hank_vjp_boundary.argtypes = [vp, i32, dp, i32, dp, dp, dp]
-    lib.hank_vjp_boundary_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
-    lib.hank_jvp_het.argtypes = [vp, i32, dp, dp, dp, i32, dp]
-    lib.hank_jvp_het_dev.argtypes = [vp, i32, vp, vp, vp, i32, vp]
-    lib.hank_vjp_het_boundary.argtypes = [vp, i32, dp, i32, dp, dp, dp]
-    lib.hank_vjp_het_boundary_dev.argtypes = [vp, i32, vp, i32, vp, vp, vp]
-    lib.hank_ss_jvp.argtypes = [vp, i32, dp, i32, C.c_double, i32, dp, dp, dp, dp, C.POINTER(i32), dp]
-    lib.hank_ss_jvp_dev.argtypes = [vp, i32, vp, i32, C.c_double, i32, vp, vp, vp, vp, C.POINTER(i32), dp]
-    lib.hank_ss_vjp.argtypes = [vp, i32, dp, dp, dp, i32, C.c_double, i32, dp, C.POINTER(i32), dp]
-    lib.hank_ss_vjp_dev.argtypes = [vp, i32, vp, vp, vp, i32, C.c_double, i32, vp, C.POINTER(i32), dp]
-    lib.hank_last_ss_timings.argtypes = [vp, dp]
-    lib.hank_primal_batch.argtypes = [vp, i32, dp, i32, dp, dp, C.POINTER(i32)]
-    lib.hank_primal_batch_dev.argtypes = [vp, i32, vp, i32, vp, vp]
-    lib.hank_last_batch_timings.argtypes = [vp, dp]
-    lib.hank_ss_batch.argtypes = [vp, i32, dp, i32, C.c_double, i32, C.c_double, i32, i32, dp, dp, dp, dp, C.POINTER(i32), dp, C.POINTER(i32)]
-    lib.hank_last_ss_batch_timings.argtypes = [vp, dp]
-    lib.hank_set_group_outputs.argtypes = [vp, i32, dp, C.POINTER(i32)]
-    lib.hank_get_group_outputs.argtypes = [vp, dp, i32, dp, dp]
-    lib.hank_get_group_outputs_dev.argtypes = [vp, vp, i32, vp, vp]
-    lib.hank_fake_news_group.argtypes = [vp, dp, dp]
-    lib.hank_vjp_group.argtypes = [vp, i32, dp, dp, i32, dp, dp, dp]
-    lib.hank_vjp_group_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
-    lib.hank_set_discount_path.argtypes = [vp, dp]
-    lib.hank_jvp_shock.argtypes = [vp, dp, dp, i32, dp]
-    lib.hank_jvp_shock_dev.argtypes = [vp, vp, vp, i32, vp]
-    lib.hank_vjp_shock.argtypes = [vp, i32, dp, i32, dp, dp]
-    lib.hank_vjp_shock_dev.argtypes = [vp, i32, vp, i32, vp, vp]
-    lib.hank_fake_news_shock.argtypes = [vp, i32, dp, dp]
-    lib.hank_set_income_path.argtypes = [vp, dp]
-    lib.hank_jvp_income.argtypes = [vp, dp, dp, i32, dp]
-    lib.hank_jvp_income_dev.argtypes = [vp, vp, vp, i32, vp]
-    lib.hank_vjp_income.argtypes = [vp, i32, dp, i32, dp, dp]
-    lib.hank_vjp_income_dev.argtypes = [vp, i32, vp, i32, vp, vp]
-    lib.hank_fake_news_income.argtypes = [vp, i32, dp, dp]
-    lib.hank_get_het_outputs_income.argtypes = [vp, i32, dp, dp, i32, dp, dp]
-    lib.hank_get_het_outputs_income_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp]
-    for name in ABI_SYMBOLS:
-        if name in ("hank_get_lottery_record", "hank_get_forward_units") and not hasattr(lib, name):
+    for name, argtypes in ABI.items():
+        if name in ABI_OPTIONAL and not hasattr(lib, name):
             continue
-        if name != "hank_last_error":
-            getattr(lib, name).restype = C.c_int
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = list(argtypes), ABI_RESTYPE.get(name, C.c_int)
     _lib = lib
     return lib
 
@@ -199,18 +153,11 @@ def device_available() -> bool:
         return False
 
 
-def gather_columns(blocks, d_block_ptrs, N_k, d_out_ptr: int):
-    """hank_gather_columns: the (P, N_k) column blocks the contexts `blocks` hold in their own GPUs' memory (device pointers
-    `d_block_ptrs`, as written by jvp_dev / primal_jvp_dev) assembled as one (P, sum N_k) matrix at `d_out_ptr` on blocks[0]'s device
-    — over xGMI where the devices differ. Asynchronous: blocks[0].sync() before reading."""
-    lib = load_library()
-    n = len(blocks)
-    ctxs = (C.c_void_p * n)(*[b._ctx for b in blocks])
-    ptrs = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in d_block_ptrs])
-    nk = (C.c_int32 * n)(*[int(v) for v in N_k])
-    rc = lib.hank_gather_columns(ctxs, n, ptrs, nk, C.c_void_p(int(d_out_ptr)))
+# -- argument shapes: one owner each -----------------------------------------------------------------------------------------------
+def _raise_status(lib, ctx, rc: int, msg=None):
+    """a status that is not HANK_OK becomes the exception of its class, with `msg` or the context's hank_last_error"""
     if rc != HANK_OK:
-        raise _ERR_CLASSES.get(rc, HankHIPError)(rc, lib.hank_last_error(blocks[0]._ctx).decode())
+        raise _ERR_CLASSES.get(rc, HankHIPError)(rc, lib.hank_last_error(ctx).decode() if msg is None else msg)
 
 
 def _f(x, shape=None) -> np.ndarray:
@@ -228,6 +175,90 @@ def _p(arr: np.ndarray):
 def _opt(arr):
     """an optional array's pointer: None (a null pointer) stays None"""
     return None if arr is None else _p(arr)
+
+
+def _ip(arr: np.ndarray):
+    return arr.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _dev(ptr):
+    """a device pointer (or a stream handle) as the library takes it: 0 or None is NULL"""
+    return C.c_void_p(ptr or None)
+
+
+def _n1(n) -> int:
+    """a count of columns or outputs as a buffer's extent: at least 1, so that a count of 0 reaches the library's own refusal"""
+    return max(int(n), 1)
+
+
+def _out(*dims) -> np.ndarray:
+    """a column-major output buffer"""
+    return np.empty(dims, order="F")
+
+
+def _cols(x, rank: int) -> np.ndarray:
+    """x as float64 with its trailing batch axis: an array of `rank` axes is one column"""
+    a = np.asarray(x, dtype=np.float64)
+    return a[..., None] if a.ndim == rank else a
+
+
+def _batch(x, dims, N=None, strict=False):
+    """a path or a batch of paths: x of shape `dims` or (*dims, N) -> ((*dims, N) column-major, N). A given N is checked, not
+    taken from x; strict: any other rank is a batch of no columns (primal_batch, ss_batch)."""
+    a = _cols(x, len(dims))
+    if N is None:
+        N = 0 if strict and a.ndim != len(dims) + 1 else a.shape[len(dims)]
+    return _f(a, (*dims, N)), N
+
+
+def _seeds(named, N=None, last_first=False):
+    """a group of optional seeds, `named` = ((name, seed, dims), ...): at least one is given; N is the caller's or the first given
+    seed's; every given seed -> (*dims, N) column-major (`_batch`), or what `dims(seed, N)` makes of it where dims is a function;
+    None stays None. last_first: the seeds are checked from the last to the first. -> (N, [seeds])"""
+    given = [(seed, dims) for _, seed, dims in named if seed is not None]
+    if not given:
+        raise ValueError(f"at least one of {', '.join(name for name, _, _ in named)} must be given")
+    if N is None:
+        seed, dims = given[0]
+        N = _cols(seed, len(dims)).shape[len(dims)]
+    out = [None] * len(named)
+    for i in reversed(range(len(named))) if last_first else range(len(named)):
+        _, seed, dims = named[i]
+        if seed is not None:
+            out[i] = dims(seed, N) if callable(dims) else _batch(seed, dims, N)[0]
+    return N, out
+
+
+def _grid_batch(x, n_a: int, n_e: int) -> np.ndarray:
+    """a batch on the grid, (n_a, n_e) or (n_a, n_e, N) -> (G, N) with pt = e n_a + a; any other shape ((G, N) among them) as it is"""
+    s = np.asarray(x, dtype=np.float64)
+    if s.shape == (n_a, n_e):
+        s = _cols(s, 2)
+    if s.ndim == 3 and s.shape[:2] == (n_a, n_e):
+        s = s.reshape((n_a * n_e, s.shape[2]), order="F")
+    return s
+
+
+# What differs between the two exogenous paths: the attribute that holds the path in force, the name of its seed, the axes in
+# front of the period axis (the path is (*axes, P), a seed (*axes, P, N), the Toeplitz form (P, P, *axes, n_het)), the C symbols
+# (the device-pointer forms add _dev), and whether its transposed entry takes cotangents by `vjp_het`'s rule or by `vjp`'s.
+_Path = namedtuple("_Path", "attr seed axes set jvp vjp fake_news het")
+_PATHS = {
+    "discount": _Path("discount_path", "dbeta", lambda hb: (), "hank_set_discount_path", "hank_jvp_shock", "hank_vjp_shock", "hank_fake_news_shock", True),
+    "income": _Path("income_path", "dy", lambda hb: (hb.n_e,), "hank_set_income_path", "hank_jvp_income", "hank_vjp_income", "hank_fake_news_income", False),
+}
+
+
+def gather_columns(blocks, d_block_ptrs, N_k, d_out_ptr: int):
+    """hank_gather_columns: the (P, N_k) column blocks the contexts `blocks` hold in their own GPUs' memory (device pointers
+    `d_block_ptrs`, as written by jvp_dev / primal_jvp_dev) assembled as one (P, sum N_k) matrix at `d_out_ptr` on blocks[0]'s device
+    — over xGMI where the devices differ. Asynchronous: blocks[0].sync() before reading."""
+    lib = load_library()
+    n = len(blocks)
+    ctxs = (C.c_void_p * n)(*[b._ctx for b in blocks])
+    ptrs = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in d_block_ptrs])
+    nk = (C.c_int32 * n)(*[int(v) for v in N_k])
+    _raise_status(lib, blocks[0]._ctx, lib.hank_gather_columns(ctxs, n, ptrs, nk, C.c_void_p(int(d_out_ptr))))
 
 
 class HouseholdBlock:
@@ -266,7 +297,7 @@ class HouseholdBlock:
             if self._ctx:
                 self._lib.hank_destroy(self._ctx)
                 self._ctx = C.c_void_p()
-            raise _ERR_CLASSES.get(rc, HankHIPError)(rc, msg or "no HIP device available (gfx950 required)")
+            _raise_status(self._lib, None, rc, msg or "no HIP device available (gfx950 required)")
         self.n_hh = self._lib.hank_n_hh(self._ctx)
         # sweeps issued through this context, by entry point (tests assert "ONE sweep per fullFunction")
         self.calls = {"primal": 0, "jvp": 0, "primal_jvp": 0}
@@ -274,8 +305,43 @@ class HouseholdBlock:
 
     # -- plumbing ---------------------------------------------------------------------------
     def _chk(self, rc: int):
-        if rc != HANK_OK:
-            raise _ERR_CLASSES.get(rc, HankHIPError)(rc, self._lib.hank_last_error(self._ctx).decode())
+        _raise_status(self._lib, self._ctx, rc)
+
+    def _call(self, symbol: str, *args):
+        """one entry of the library on this context; its status through `_chk`"""
+        self._chk(getattr(self._lib, symbol)(self._ctx, *args))
+
+    def _read(self, symbol: str, *bufs):
+        """a getter that fills small ctypes arrays -> their contents, a list each"""
+        self._call(symbol, *bufs)
+        return [list(b) for b in bufs]
+
+    def _ms_pair(self, symbol: str):
+        """the two times (ms, HIP events on the stream) a timing getter reports"""
+        ms, = self._read(symbol, (C.c_double * 2)())
+        return (ms[0], ms[1])
+
+    def _ms_launches(self, symbol: str, names):
+        ms, ln = self._read(symbol, (C.c_double * len(names))(), (C.c_int32 * len(names))())
+        return {k: {"ms": ms[i], "launches": ln[i]} for i, k in enumerate(names)}
+
+    def _counters(self, symbol: str, names):
+        out, = self._read(symbol, (C.c_int64 * 8)())
+        return {k: int(out[i]) for i, k in enumerate(names)}
+
+    def _cot_outputs(self, M, value_end=False, D_init=False):
+        """the outputs of a transposed sweep of M columns: (xhh_bar (n_hh, P, M), value_end_bar, D_init_bar (n_a, n_e, M)), a boundary
+        cotangent that is not wanted None"""
+        M = _n1(M)
+        return (_out(self.n_hh, self.P, M), _out(self.n_a, self.n_e, M) if value_end else None,
+                _out(self.n_a, self.n_e, M) if D_init else None)
+
+    def _sweep_input(self, dxhh):
+        """`dxhh` (n_hh, P, N), the input of the last tangent sweep, passed again to a reader of that batch -> (column-major, N)"""
+        dxhh = np.asfortranarray(dxhh, dtype=np.float64)
+        if dxhh.ndim != 3 or dxhh.shape[:2] != (self.n_hh, self.P):      # (a 2-D dxhh is not promoted here, as it never was)
+            raise ValueError(f"dxhh must be ({self.n_hh}, {self.P}, N), got {dxhh.shape}")
+        return dxhh, dxhh.shape[2]
 
     def clone(self, device=None) -> "HouseholdBlock":
         """A second, independent context of the same model and boundary (its own device memory, graphs and
@@ -286,10 +352,9 @@ class HouseholdBlock:
         other = HouseholdBlock(self.a_grid, self.z_grid, self.Pi, beta, gamma, bc, self.T, vf, device=self.device if device is None else device)
         if self._boundary is not None:
             other.set_boundary(*self._boundary)
-        if self.discount_path is not None:
-            other.set_discount_path(self.discount_path)
-        if self.income_path is not None:
-            other.set_income_path(self.income_path)
+        for kind, path in _PATHS.items():
+            if getattr(self, path.attr) is not None:
+                other._set_path(kind, getattr(self, path.attr))
         return other
 
     def close(self):
@@ -304,36 +369,107 @@ class HouseholdBlock:
             pass
 
     def set_stream(self, hip_stream_handle: int | None):
-        self._chk(self._lib.hank_set_stream(self._ctx, C.c_void_p(hip_stream_handle or 0)))
+        self._call("hank_set_stream", _dev(hip_stream_handle))
 
     def sync(self):
-        self._chk(self._lib.hank_sync(self._ctx))
+        self._call("hank_sync")
 
     def check(self):
-        self._chk(self._lib.hank_check(self._ctx))
+        self._call("hank_check")
 
     # -- boundary + fused sweeps ------------------------------------------------------------
     def set_boundary(self, ss_end_value, ss_init_D):
         v = _f(ss_end_value, (self.n_a, self.n_e))
         d = _f(np.asarray(ss_init_D, dtype=np.float64).reshape((self.n_a, self.n_e), order="F"))
-        self._chk(self._lib.hank_set_boundary(self._ctx, _p(v), _p(d)))
+        self._call("hank_set_boundary", _p(v), _p(d))
         self._boundary = (v, d)
 
-    # -- the discount-factor path -------------------------------------------------------------
+    def primal(self, xhh) -> np.ndarray:
+        x = _f(xhh, (self.n_hh, self.P))
+        agg = np.empty(self.P)
+        self.calls["primal"] += 1
+        self._call("hank_primal", _p(x), _p(agg))
+        return agg
+
+    def jvp(self, dxhh) -> np.ndarray:
+        dx, N = _batch(dxhh, (self.n_hh, self.P))
+        out = _out(self.P, N)
+        self.calls["jvp"] += 1
+        self._call("hank_jvp", _p(dx), N, _p(out))
+        return out
+
+    def primal_jvp(self, xhh, dxhh):
+        """value and N partials in one dual-sweep pass (what JVP(fullFunction, x, y) does in the reference)."""
+        x = _f(xhh, (self.n_hh, self.P))
+        dx, N = _batch(dxhh, (self.n_hh, self.P))
+        agg = np.empty(self.P)
+        dagg = _out(self.P, N)
+        self.calls["primal_jvp"] += 1
+        self._call("hank_primal_jvp", _p(x), _p(dx), N, _p(agg), _p(dagg))
+        return agg, dagg
+
+    def primal_jvp_dev(self, d_xhh_ptr: int, d_dxhh_ptr: int, N: int, d_agg_ptr: int = 0, d_dagg_ptr: int = 0):
+        self._call("hank_primal_jvp_dev", _dev(d_xhh_ptr), _dev(d_dxhh_ptr), int(N), _dev(d_agg_ptr), _dev(d_dagg_ptr))
+
+    def primal_dev(self, d_xhh_ptr: int, d_agg_ptr: int = 0):
+        self._call("hank_primal_dev", _dev(d_xhh_ptr), _dev(d_agg_ptr))
+
+    def jvp_dev(self, d_dxhh_ptr: int, N: int, d_dagg_ptr: int = 0):
+        self._call("hank_jvp_dev", _dev(d_dxhh_ptr), int(N), _dev(d_dagg_ptr))
+
+    # -- the exogenous paths: one body each, the kinds in _PATHS -------------------------------
+    def _set_path(self, kind, path):
+        k = _PATHS[kind]
+        if path is not None:
+            path = _f(path, (*k.axes(self), self.P))
+        self._call(k.set, _opt(path))
+        setattr(self, k.attr, None if path is None else path.copy(order="F"))
+
+    def _path_dirs(self, kind, dxhh, seed):
+        """the directions of a path's tangent entry: dxhh (n_hh, P[, N]) or None, seed (*axes, P[, N]) or None -> (N, dx, seed) column-major"""
+        k = _PATHS[kind]
+        N, (dx, seed) = _seeds((("dxhh", dxhh, (self.n_hh, self.P)), (k.seed, seed, (*k.axes(self), self.P))),
+                               last_first=True)      # (a bad path seed has always been reported before a bad dxhh)
+        return N, dx, seed
+
+    def _jvp_path(self, kind, dxhh, seed):
+        N, dx, seed = self._path_dirs(kind, dxhh, seed)
+        out = _out(self.P, N)
+        self.calls["jvp"] += 1
+        self._call(_PATHS[kind].jvp, _opt(dx), _opt(seed), N, _p(out))
+        return out
+
+    def _jvp_path_dev(self, kind, d_dxhh_ptr, d_seed_ptr, N, d_dagg_ptr):
+        self._call(_PATHS[kind].jvp + "_dev", _dev(d_dxhh_ptr), _dev(d_seed_ptr), int(N), _dev(d_dagg_ptr))
+
+    def _vjp_path(self, kind, agg_bar, n_het):
+        k = _PATHS[kind]
+        M, yb = self._cotangents(agg_bar, n_het, het=k.het)
+        out = self._cot_outputs(M)[0]
+        bar = _out(*k.axes(self), self.P, _n1(M))
+        self._call(k.vjp, int(n_het), _p(yb), M, _p(out), _p(bar))
+        return out, bar
+
+    def _vjp_path_dev(self, kind, n_het, d_agg_bar_ptr, M, d_xhh_bar_ptr, d_bar_ptr):
+        self._call(_PATHS[kind].vjp + "_dev", int(n_het), _dev(d_agg_bar_ptr), int(M), _dev(d_xhh_bar_ptr), _dev(d_bar_ptr))
+
+    def _fake_news_path(self, kind, n_het):
+        k = _PATHS[kind]
+        F = _out(self.P, self.P, *k.axes(self), _n1(n_het))
+        Dv = _out(self.P, *k.axes(self), _n1(n_het))
+        self._call(k.fake_news, int(n_het), _p(F), _p(Dv))
+        return F, Dv
+
     def set_discount_path(self, beta_t):
         """a path beta_t (P,) of the discount factor (hank_set_discount_path): beta_t is the factor in period t's Euler equation,
         u'(c_t) = beta_t E_t[V_{t+1}], so beta_{P-1} multiplies the expectation of the terminal value. None returns to the
         model's constant. Like a new boundary it drops the record: the next tangent sweep needs a primal first. While a path is
         set every sweep runs on the per-period launches; the scenario, steady-state and `fake_news*` entries are refused."""
-        if beta_t is None:
-            self._chk(self._lib.hank_set_discount_path(self._ctx, None))
-            self.discount_path = None
-            return
-        b = np.ascontiguousarray(beta_t, dtype=np.float64)
-        if b.shape != (self.P,):
-            raise ValueError(f"beta_t must be ({self.P},), got {b.shape}")
-        self._chk(self._lib.hank_set_discount_path(self._ctx, _p(b)))
-        self.discount_path = b.copy()
+        if beta_t is not None:
+            beta_t = np.ascontiguousarray(beta_t, dtype=np.float64)
+            if beta_t.shape != (self.P,):
+                raise ValueError(f"beta_t must be ({self.P},), got {beta_t.shape}")
+        self._set_path("discount", beta_t)
 
     def jvp_shock(self, dxhh=None, dbeta=None) -> np.ndarray:
         """the tangent sweeps with seeds in the discount-factor path as well (hank_jvp_shock): dxhh (n_hh, P, N) as in `jvp`,
@@ -341,84 +477,34 @@ class HouseholdBlock:
         always the launch family. The batch is current afterwards as `jvp`'s is: `dpolicy_seq`, `grid_aggregates`,
         `het_outputs(n_het, dxhh)` and `group_outputs(dxhh)` serve it — beta has no direct term in any output, so pass the same
         dxhh (zeros for None)."""
-        if dxhh is None and dbeta is None:
-            raise ValueError("at least one of dxhh, dbeta must be given")
-        dx = db = None
-        if dxhh is not None:
-            dx = np.asarray(dxhh, dtype=np.float64)
-            dx = dx[:, :, None] if dx.ndim == 2 else dx
-            N = dx.shape[2]
-        if dbeta is not None:
-            db = np.asarray(dbeta, dtype=np.float64)
-            db = db[:, None] if db.ndim == 1 else db
-            N = db.shape[1] if dx is None else N
-            db = _f(db, (self.P, N))
-        if dx is not None:
-            dx = _f(dx, (self.n_hh, self.P, N))
-        out = np.empty((self.P, N), order="F")
-        self.calls["jvp"] += 1
-        self._chk(self._lib.hank_jvp_shock(self._ctx, _opt(dx), _opt(db), N, _p(out)))
-        return out
+        return self._jvp_path("discount", dxhh, dbeta)
 
     def jvp_shock_dev(self, d_dxhh_ptr: int, d_dbeta_ptr: int, N: int, d_dagg_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
-        self._chk(self._lib.hank_jvp_shock_dev(self._ctx, C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dbeta_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+        self._jvp_path_dev("discount", d_dxhh_ptr, d_dbeta_ptr, N, d_dagg_ptr)
 
     def vjp_shock(self, agg_bar, n_het: int):
         """`vjp_het` with the cotangent of the discount-factor path (hank_vjp_shock): agg_bar (P, n_het, M) -> (xhh_bar
         (n_hh, P, M), beta_bar (P, M)); the exact transpose of `jvp_shock` followed by `het_outputs(n_het)`. xhh_bar equals
         `vjp_het`'s bit for bit; beta_bar is a fixed-order reduction (the same inputs give the same bits)."""
-        M, yb = self._cotangents(agg_bar, n_het, het=True)
-        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
-        bb = np.empty((self.P, max(M, 1)), order="F")
-        self._chk(self._lib.hank_vjp_shock(self._ctx, int(n_het), _p(yb), M, _p(out), _p(bb)))
-        return out, bb
+        return self._vjp_path("discount", agg_bar, n_het)
 
     def vjp_shock_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_beta_bar_ptr: int):
         """device-pointer form (asynchronous on the context's stream)."""
-        self._chk(self._lib.hank_vjp_shock_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr), C.c_void_p(d_beta_bar_ptr)))
+        self._vjp_path_dev("discount", n_het, d_agg_bar_ptr, M, d_xhh_bar_ptr, d_beta_bar_ptr)
 
     def fake_news_shock(self, n_het: int):
         """the Toeplitz form of every output's Jacobian with respect to the discount-factor path at the steady state
         (hank_fake_news_shock): -> (F (P, P, n_het), Dv (P, n_het)), the definitions of `fake_news_het` with the input fixed to
         beta. `SteadyStateJacobian.shock_jacobian` does the recursion. Same precondition as `fake_news`; no path may be set."""
-        nh = max(int(n_het), 1)
-        F = np.empty((self.P, self.P, nh), order="F")
-        Dv = np.empty((self.P, nh), order="F")
-        self._chk(self._lib.hank_fake_news_shock(self._ctx, int(n_het), _p(F), _p(Dv)))
-        return F, Dv
+        return self._fake_news_path("discount", n_het)
 
-    # -- the income path by productivity state ------------------------------------------------
     def set_income_path(self, y):
         """a path y (n_e, P) of additive income by productivity state (hank_set_income_path): the budget of period t is
         c + a' = (1 + r_t) a + w_t z_e + tr_t + y_t[e]. None clears it. Like a new boundary it drops the record: the next tangent
         sweep needs a primal first. While a path is set every sweep runs on the per-period launches and the entries that rebuild
         consumption from the inputs or are defined at one income process are refused; it excludes a discount-factor path."""
-        if y is None:
-            self._chk(self._lib.hank_set_income_path(self._ctx, None))
-            self.income_path = None
-            return
-        yy = _f(y, (self.n_e, self.P))
-        self._chk(self._lib.hank_set_income_path(self._ctx, _p(yy)))
-        self.income_path = yy.copy(order="F")
-
-    def _income_dirs(self, dxhh, dy):
-        """the directions of `jvp_income`: dxhh (n_hh, P[, N]) or None, dy (n_e, P[, N]) or None -> (N, dx, dy) column-major"""
-        if dxhh is None and dy is None:
-            raise ValueError("at least one of dxhh, dy must be given")
-        dx = d = None
-        if dxhh is not None:
-            dx = np.asarray(dxhh, dtype=np.float64)
-            dx = dx[:, :, None] if dx.ndim == 2 else dx
-            N = dx.shape[2]
-        if dy is not None:
-            d = np.asarray(dy, dtype=np.float64)
-            d = d[:, :, None] if d.ndim == 2 else d
-            N = d.shape[2] if dx is None else N
-            d = _f(d, (self.n_e, self.P, N))
-        if dx is not None:
-            dx = _f(dx, (self.n_hh, self.P, N))
-        return N, dx, d
+        self._set_path("income", y)
 
     def jvp_income(self, dxhh=None, dy=None) -> np.ndarray:
         """the tangent sweeps with seeds in the income path as well (hank_jvp_income): dxhh (n_hh, P, N) as in `jvp`, dy (n_e, P)
@@ -426,72 +512,28 @@ class HouseholdBlock:
         launch family. The batch is current afterwards as `jvp`'s is: `dpolicy_seq`, `grid_aggregates`, `group_outputs` (mass and
         policy bases) and `het_outputs(n_het, dxhh)` serve it — y has a direct term in consumption, which `het_outputs` adds from
         the dy the batch carries (or from a `dy=` of the caller's); Value, UCE and consumption groups have no tangent at such a batch."""
-        N, dx, d = self._income_dirs(dxhh, dy)
-        out = np.empty((self.P, N), order="F")
-        self.calls["jvp"] += 1
-        self._chk(self._lib.hank_jvp_income(self._ctx, _opt(dx), _opt(d), N, _p(out)))
-        return out
+        return self._jvp_path("income", dxhh, dy)
 
     def jvp_income_dev(self, d_dxhh_ptr: int, d_dy_ptr: int, N: int, d_dagg_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
-        self._chk(self._lib.hank_jvp_income_dev(self._ctx, C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dy_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+        self._jvp_path_dev("income", d_dxhh_ptr, d_dy_ptr, N, d_dagg_ptr)
 
     def vjp_income(self, agg_bar, n_het: int = 1):
         """`vjp` with the cotangent of the income path (hank_vjp_income): agg_bar as in `vjp` -> (xhh_bar (n_hh, P, M), y_bar
         (n_e, P, M)); the exact transpose of `jvp_income` followed by `het_outputs(n_het, dxhh, dy=dy)`. xhh_bar equals `vjp`'s bit
         for bit; y_bar is a fixed-order reduction (the same inputs give the same bits)."""
-        M, yb = self._cotangents(agg_bar, n_het, het=False)
-        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
-        ybar = np.empty((self.n_e, self.P, max(M, 1)), order="F")
-        self._chk(self._lib.hank_vjp_income(self._ctx, int(n_het), _p(yb), M, _p(out), _p(ybar)))
-        return out, ybar
+        return self._vjp_path("income", agg_bar, n_het)
 
     def vjp_income_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_y_bar_ptr: int):
         """device-pointer form (asynchronous on the context's stream)."""
-        self._chk(self._lib.hank_vjp_income_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr), C.c_void_p(d_y_bar_ptr)))
+        self._vjp_path_dev("income", n_het, d_agg_bar_ptr, M, d_xhh_bar_ptr, d_y_bar_ptr)
 
     def fake_news_income(self, n_het: int):
         """the Toeplitz form of the Jacobian of outputs 0 .. n_het-1 (n_het <= 2) with respect to the income path at the steady
         state (hank_fake_news_income): -> (F (P, P, n_e, n_het), Dv (P, n_e, n_het)), the definitions of `fake_news_het` with the
         input fixed to y[e]. `SteadyStateJacobian.income_jacobian` does the recursion. Same precondition as `fake_news`; no path
         may be set."""
-        nh = max(int(n_het), 1)
-        F = np.empty((self.P, self.P, self.n_e, nh), order="F")
-        Dv = np.empty((self.P, self.n_e, nh), order="F")
-        self._chk(self._lib.hank_fake_news_income(self._ctx, int(n_het), _p(F), _p(Dv)))
-        return F, Dv
-
-    def primal(self, xhh) -> np.ndarray:
-        x = _f(xhh, (self.n_hh, self.P))
-        agg = np.empty(self.P)
-        self.calls["primal"] += 1
-        self._chk(self._lib.hank_primal(self._ctx, _p(x), _p(agg)))
-        return agg
-
-    def jvp(self, dxhh) -> np.ndarray:
-        dx = np.asarray(dxhh, dtype=np.float64)
-        if dx.ndim == 2:
-            dx = dx[:, :, None]
-        N = dx.shape[2]
-        dx = _f(dx, (self.n_hh, self.P, N))
-        out = np.empty((self.P, N), order="F")
-        self.calls["jvp"] += 1
-        self._chk(self._lib.hank_jvp(self._ctx, _p(dx), N, _p(out)))
-        return out
-
-    def primal_jvp(self, xhh, dxhh):
-        """value and N partials in one dual-sweep pass (what JVP(fullFunction, x, y) does in the reference)."""
-        x = _f(xhh, (self.n_hh, self.P))
-        dx = np.asarray(dxhh, dtype=np.float64)
-        if dx.ndim == 2:
-            dx = dx[:, :, None]
-        N = dx.shape[2]
-        dx = _f(dx, (self.n_hh, self.P, N))
-        agg = np.empty(self.P)
-        dagg = np.empty((self.P, N), order="F")
-        self.calls["primal_jvp"] += 1
-        self._chk(self._lib.hank_primal_jvp(self._ctx, _p(x), _p(dx), N, _p(agg), _p(dagg)))
-        return agg, dagg
+        return self._fake_news_path("income", n_het)
 
     # -- K input paths through one chain of launches ------------------------------------------
     def primal_batch(self, xhh, n_het: int = 1, policy: bool = False, check: bool = True):
@@ -501,16 +543,11 @@ class HouseholdBlock:
         with `set_het_outputs`. The context's recorded primal, its batches and its memo stay as they were. status[k] is scenario
         k's status code; the healthy scenarios' outputs are valid whatever the others did. check=True raises the first failing
         scenario's exception (the arrays of the call are then at `last_batch`)."""
-        x = np.asarray(xhh, dtype=np.float64)
-        if x.ndim == 2:
-            x = x[:, :, None]
-        K = x.shape[2] if x.ndim == 3 else 0
-        x = _f(x, (self.n_hh, self.P, K))
-        nh = max(int(n_het), 1)
-        aggs = np.empty((self.P, nh, max(K, 1)), order="F")
-        status = np.zeros(max(K, 1), dtype=np.int32)
-        pol = np.empty((self.n_a, self.n_e, self.P, max(K, 1)), order="F") if policy else None
-        rc = self._lib.hank_primal_batch(self._ctx, int(n_het), _p(x), K, _p(aggs), _opt(pol), status.ctypes.data_as(C.POINTER(C.c_int32)))
+        x, K = _batch(xhh, (self.n_hh, self.P), strict=True)
+        aggs = _out(self.P, _n1(n_het), _n1(K))
+        status = np.zeros(_n1(K), dtype=np.int32)
+        pol = _out(self.n_a, self.n_e, self.P, _n1(K)) if policy else None
+        rc = self._lib.hank_primal_batch(self._ctx, int(n_het), _p(x), K, _p(aggs), _opt(pol), _ip(status))
         self.last_batch = (aggs, status, pol)
         if rc != HANK_OK and (check or not (1 <= K <= 64) or not np.any(status)):      # (a refusal of the call itself always raises)
             self._chk(rc)
@@ -518,13 +555,11 @@ class HouseholdBlock:
 
     def primal_batch_dev(self, n_het: int, d_xhh_ptr: int, K: int, d_agg_ptr: int, d_policy_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream; the verdict arrives at `check`)."""
-        self._chk(self._lib.hank_primal_batch_dev(self._ctx, int(n_het), C.c_void_p(d_xhh_ptr), int(K), C.c_void_p(d_agg_ptr), C.c_void_p(d_policy_ptr or None)))
+        self._call("hank_primal_batch_dev", int(n_het), _dev(d_xhh_ptr), int(K), _dev(d_agg_ptr), _dev(d_policy_ptr))
 
     def last_batch_timings(self):
         """time (ms, HIP events on the stream) of the last batch's backward and forward chains (hank_last_batch_timings)"""
-        ms = (C.c_double * 2)()
-        self._chk(self._lib.hank_last_batch_timings(self._ctx, ms))
-        return (ms[0], ms[1])
+        return self._ms_pair("hank_last_batch_timings")
 
     # -- the steady state's household side at K price vectors ---------------------------------
     def _per_scenario(self, arr, K, fill):
@@ -534,9 +569,7 @@ class HouseholdBlock:
         s = np.asarray(arr, dtype=np.float64)
         if s.shape in ((self.n_a, self.n_e), (self.G,)):
             return np.asfortranarray(np.repeat(s.reshape((self.G, 1), order="F"), K, axis=1))
-        if s.ndim == 3 and s.shape[:2] == (self.n_a, self.n_e):
-            s = s.reshape((self.G, s.shape[2]), order="F")
-        return _f(np.array(s, copy=True), (self.G, K))
+        return _f(np.array(_grid_batch(s, self.n_a, self.n_e), copy=True), (self.G, K))
 
     def ss_batch(self, xhh, vfi_tol: float, n_het: int = 1, value0=None, D0=None, vfi_max_iter: int = 10_000, dist_tol: float = 1e-15,
                  dist_max_iter: int = 500_000, check_every: int = 25, dist: bool = True, check: bool = True):
@@ -547,26 +580,21 @@ class HouseholdBlock:
         D0 likewise (normalised to sum to one; None = uniform). dist=False: value iteration only (aggs and D are None). The
         context's record, batches and memo stay as they were. check=True raises the first failing scenario's exception; the raw
         arrays of the call (D as the library left it, the sup-norms) are at `last_ss_batch` either way."""
-        x = np.asarray(xhh, dtype=np.float64)
-        if x.ndim == 1:
-            x = x[:, None]
-        K = x.shape[1] if x.ndim == 2 else 0
-        x = _f(x, (self.n_hh, K))
-        Kb, nh = max(K, 1), max(int(n_het), 1)
+        x, K = _batch(xhh, (self.n_hh,), strict=True)
+        Kb = _n1(K)
         v = self._per_scenario(value0, Kb, 1.0)
-        pol = np.empty((self.G, Kb), order="F")
+        pol = _out(self.G, Kb)
         d = aggs = None
         if dist:
             d = self._per_scenario(D0, Kb, 1.0 / self.G)
             if D0 is not None:
                 d /= d.sum(axis=0, keepdims=True)
-            aggs = np.empty((nh, Kb), order="F")
+            aggs = _out(_n1(n_het), Kb)
         iters = np.zeros((Kb, 2), dtype=np.int32)
         nrm = np.zeros(Kb)
         status = np.zeros(Kb, dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
         rc = self._lib.hank_ss_batch(self._ctx, int(n_het), _p(x), K, float(vfi_tol), int(vfi_max_iter), float(dist_tol), int(dist_max_iter),
-                                     int(check_every), _p(v), _p(pol), _opt(d), _opt(aggs), iters.ctypes.data_as(ip), _p(nrm), status.ctypes.data_as(ip))
+                                     int(check_every), _p(v), _p(pol), _opt(d), _opt(aggs), _ip(iters), _p(nrm), _ip(status))
         self.last_ss_batch = {"aggs": aggs, "value": v, "policy": pol, "D": d, "iters": iters, "supnorm": nrm, "status": status}
         if rc != HANK_OK and (check or not np.any(status)):      # (a refusal of the call itself always raises)
             self._chk(rc)
@@ -579,19 +607,7 @@ class HouseholdBlock:
 
     def last_ss_batch_timings(self):
         """time (ms, HIP events on the stream) of the last `ss_batch`'s value loops and distribution loops (hank_last_ss_batch_timings)"""
-        ms = (C.c_double * 2)()
-        self._chk(self._lib.hank_last_ss_batch_timings(self._ctx, ms))
-        return (ms[0], ms[1])
-
-    def primal_jvp_dev(self, d_xhh_ptr: int, d_dxhh_ptr: int, N: int, d_agg_ptr: int = 0, d_dagg_ptr: int = 0):
-        self._chk(self._lib.hank_primal_jvp_dev(self._ctx, C.c_void_p(d_xhh_ptr), C.c_void_p(d_dxhh_ptr), int(N),
-                                                C.c_void_p(d_agg_ptr), C.c_void_p(d_dagg_ptr)))
-
-    def primal_dev(self, d_xhh_ptr: int, d_agg_ptr: int = 0):
-        self._chk(self._lib.hank_primal_dev(self._ctx, C.c_void_p(d_xhh_ptr), C.c_void_p(d_agg_ptr)))
-
-    def jvp_dev(self, d_dxhh_ptr: int, N: int, d_dagg_ptr: int = 0):
-        self._chk(self._lib.hank_jvp_dev(self._ctx, C.c_void_p(d_dxhh_ptr), int(N), C.c_void_p(d_dagg_ptr)))
+        return self._ms_pair("hank_last_ss_batch_timings")
 
     # -- the transposed block ---------------------------------------------------------------
     def _cotangents(self, agg_bar, n_het, het):
@@ -600,8 +616,7 @@ class HouseholdBlock:
         yb = np.asarray(agg_bar, dtype=np.float64)
         if het and yb.ndim != 3:
             raise ValueError("agg_bar must be (P, n_het, M)")
-        if yb.ndim == 1:
-            yb = yb[:, None]
+        yb = _cols(yb, 1)
         if yb.ndim == 2:
             if int(n_het) != 1:
                 raise ValueError("agg_bar must be (P, n_het, M) when n_het > 1")
@@ -615,50 +630,39 @@ class HouseholdBlock:
         backward loop). agg_bar: (P,) or (P, M) for n_het = 1, (P, n_het, M) in general — cotangents of the aggregates of
         the policy variable and (n_het = 2) of consumption. -> xhh_bar (n_hh, P, M)."""
         M, yb = self._cotangents(agg_bar, n_het, het=False)
-        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
-        self._chk(self._lib.hank_vjp(self._ctx, int(n_het), _p(yb), M, _p(out)))
+        out = self._cot_outputs(M)[0]
+        self._call("hank_vjp", int(n_het), _p(yb), M, _p(out))
         return out
 
     def vjp_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int):
         """device-pointer form (asynchronous on the context's stream)."""
-        self._chk(self._lib.hank_vjp_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr)))
+        self._call("hank_vjp_dev", int(n_het), _dev(d_agg_bar_ptr), int(M), _dev(d_xhh_bar_ptr))
 
     def vjp_het(self, agg_bar, n_het: int) -> np.ndarray:
         """`vjp` with cotangents on every heterogeneous output (hank_vjp_het): agg_bar (P, n_het, M), n_het up to the count
         declared with `set_het_outputs` — outputs 2, 3 are Value and UCE, which are not affine in the policy.
         -> xhh_bar (n_hh, P, M). n_het <= 2 runs `vjp`'s path: the same bits."""
         M, yb = self._cotangents(agg_bar, n_het, het=True)
-        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
-        self._chk(self._lib.hank_vjp_het(self._ctx, int(n_het), _p(yb), M, _p(out)))
+        out = self._cot_outputs(M)[0]
+        self._call("hank_vjp_het", int(n_het), _p(yb), M, _p(out))
         return out
 
     def vjp_het_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int):
         """device-pointer form (asynchronous on the context's stream)."""
-        self._chk(self._lib.hank_vjp_het_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr)))
+        self._call("hank_vjp_het_dev", int(n_het), _dev(d_agg_bar_ptr), int(M), _dev(d_xhh_bar_ptr))
 
     # -- tangents and cotangents on the boundary ---------------------------------------------
     def _boundary_seed(self, seed, N):
         """a boundary seed (n_a, n_e), (n_a, n_e, N) or (G, N) -> (G, N) column-major, pt = e n_a + a; None stays None"""
-        if seed is None:
-            return None
-        s = np.asarray(seed, dtype=np.float64)
-        if s.shape == (self.n_a, self.n_e):
-            s = s[:, :, None]
-        if s.ndim == 3 and s.shape[:2] == (self.n_a, self.n_e):
-            s = s.reshape((self.G, s.shape[2]), order="F")
-        return _f(s, (self.G, N))
+        return None if seed is None else _f(_grid_batch(seed, self.n_a, self.n_e), (self.G, N))
 
     def _directions(self, dxhh, dvalue_end, dD_init):
         """the inputs of `jvp_boundary` / `jvp_het` -> (N, dx (n_hh, P, N), dv (G, N), dd (G, N)), column-major; None stays None"""
-        given = [np.asarray(v) for v in (dxhh, dvalue_end, dD_init) if v is not None]
-        if not given:
-            raise ValueError("at least one of dxhh, dvalue_end, dD_init must be given")
-        N = given[0].shape[-1] if given[0].ndim == 3 else 1
-        dx = None
-        if dxhh is not None:
-            dx = np.asarray(dxhh, dtype=np.float64)
-            dx = _f(dx[:, :, None] if dx.ndim == 2 else dx, (self.n_hh, self.P, N))
-        return N, dx, self._boundary_seed(dvalue_end, N), self._boundary_seed(dD_init, N)
+        first = next((np.asarray(v) for v in (dxhh, dvalue_end, dD_init) if v is not None), None)
+        N = None if first is None else first.shape[-1] if first.ndim == 3 else 1      # (so a lone (G, N) seed with N > 1 is refused, as it always was)
+        N, (dx, dv, dd) = _seeds((("dxhh", dxhh, (self.n_hh, self.P)), ("dvalue_end", dvalue_end, self._boundary_seed),
+                                  ("dD_init", dD_init, self._boundary_seed)), N)
+        return N, dx, dv, dd
 
     def jvp_boundary(self, dxhh=None, dvalue_end=None, dD_init=None) -> np.ndarray:
         """the tangent sweeps with seeds on the boundary as well (hank_jvp_boundary): dxhh (n_hh, P, N) as in `jvp`, dvalue_end
@@ -667,31 +671,27 @@ class HouseholdBlock:
         batch is current afterwards: `dpolicy_seq`, `grid_aggregates`, `het_outputs(2, dxhh)` serve it (pass zeros for a dxhh of
         None)."""
         N, dx, dv, dd = self._directions(dxhh, dvalue_end, dD_init)
-        out = np.empty((self.P, N), order="F")
+        out = _out(self.P, N)
         self.calls["jvp"] += 1
-        self._chk(self._lib.hank_jvp_boundary(self._ctx, _opt(dx), _opt(dv), _opt(dd), N, _p(out)))
+        self._call("hank_jvp_boundary", _opt(dx), _opt(dv), _opt(dd), N, _p(out))
         return out
 
     def jvp_boundary_dev(self, d_dxhh_ptr: int, d_dvalue_end_ptr: int, d_dD_init_ptr: int, N: int, d_dagg_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
-        self._chk(self._lib.hank_jvp_boundary_dev(self._ctx, C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dvalue_end_ptr or None),
-                                                  C.c_void_p(d_dD_init_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+        self._call("hank_jvp_boundary_dev", _dev(d_dxhh_ptr), _dev(d_dvalue_end_ptr), _dev(d_dD_init_ptr), int(N), _dev(d_dagg_ptr))
 
     def vjp_boundary(self, agg_bar, n_het: int = 1):
         """`vjp` with the boundary's cotangents (hank_vjp_boundary): -> (xhh_bar (n_hh, P, M), value_end_bar (n_a, n_e, M),
         D_init_bar (n_a, n_e, M)) — the cotangents of the household inputs, of `ss_end.value` and of `ss_initial.D`; the exact
         transpose of `jvp_boundary` followed by `het_outputs(n_het)`. agg_bar as in `vjp`; xhh_bar equals `vjp`'s bit for bit."""
         M, yb = self._cotangents(agg_bar, n_het, het=False)
-        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
-        vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F")
-        db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F")
-        self._chk(self._lib.hank_vjp_boundary(self._ctx, int(n_het), _p(yb), M, _p(out), _p(vb), _p(db)))
+        out, vb, db = self._cot_outputs(M, True, True)
+        self._call("hank_vjp_boundary", int(n_het), _p(yb), M, _p(out), _p(vb), _p(db))
         return out, vb, db
 
     def vjp_boundary_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_value_end_bar_ptr: int = 0, d_D_init_bar_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream); a boundary pointer of 0 is not wanted."""
-        self._chk(self._lib.hank_vjp_boundary_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr),
-                                                  C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
+        self._call("hank_vjp_boundary_dev", int(n_het), _dev(d_agg_bar_ptr), int(M), _dev(d_xhh_bar_ptr), _dev(d_value_end_bar_ptr), _dev(d_D_init_bar_ptr))
 
     # -- every output's tangent in one pair of sweeps; its transpose on the boundary ----------
     def jvp_het(self, dxhh=None, dvalue_end=None, dD_init=None, n_het: int = 2) -> np.ndarray:
@@ -700,31 +700,27 @@ class HouseholdBlock:
         `het_outputs`' dagg. Value and UCE ride in the forward sweep, so boundary seeds reach them too. Always the launch
         family; n_het <= 2 gives the bits of `jvp` / `jvp_boundary` under the launch schedule."""
         N, dx, dv, dd = self._directions(dxhh, dvalue_end, dD_init)
-        out = np.empty((self.P, max(int(n_het), 1), N), order="F")
+        out = _out(self.P, _n1(n_het), N)
         self.calls["jvp"] += 1
-        self._chk(self._lib.hank_jvp_het(self._ctx, int(n_het), _opt(dx), _opt(dv), _opt(dd), N, _p(out)))
+        self._call("hank_jvp_het", int(n_het), _opt(dx), _opt(dv), _opt(dd), N, _p(out))
         return out
 
     def jvp_het_dev(self, n_het: int, d_dxhh_ptr: int, d_dvalue_end_ptr: int, d_dD_init_ptr: int, N: int, d_dagg_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
-        self._chk(self._lib.hank_jvp_het_dev(self._ctx, int(n_het), C.c_void_p(d_dxhh_ptr or None), C.c_void_p(d_dvalue_end_ptr or None),
-                                             C.c_void_p(d_dD_init_ptr or None), int(N), C.c_void_p(d_dagg_ptr or None)))
+        self._call("hank_jvp_het_dev", int(n_het), _dev(d_dxhh_ptr), _dev(d_dvalue_end_ptr), _dev(d_dD_init_ptr), int(N), _dev(d_dagg_ptr))
 
     def vjp_het_boundary(self, agg_bar, n_het: int, value_end: bool = True, D_init: bool = True):
         """`vjp_het` with the boundary's cotangents (hank_vjp_het_boundary): agg_bar (P, n_het, M) -> (xhh_bar (n_hh, P, M),
         value_end_bar (n_a, n_e, M), D_init_bar (n_a, n_e, M)); the exact transpose of `jvp_het`. A boundary cotangent that is
         not wanted (value_end / D_init False) is not computed and comes back as None. xhh_bar equals `vjp_het`'s bit for bit."""
         M, yb = self._cotangents(agg_bar, n_het, het=True)
-        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
-        vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if value_end else None
-        db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if D_init else None
-        self._chk(self._lib.hank_vjp_het_boundary(self._ctx, int(n_het), _p(yb), M, _p(out), _opt(vb), _opt(db)))
+        out, vb, db = self._cot_outputs(M, value_end, D_init)
+        self._call("hank_vjp_het_boundary", int(n_het), _p(yb), M, _p(out), _opt(vb), _opt(db))
         return out, vb, db
 
     def vjp_het_boundary_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_value_end_bar_ptr: int = 0, d_D_init_bar_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream); a boundary pointer of 0 is not wanted."""
-        self._chk(self._lib.hank_vjp_het_boundary_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr), int(M), C.c_void_p(d_xhh_bar_ptr),
-                                                      C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
+        self._call("hank_vjp_het_boundary_dev", int(n_het), _dev(d_agg_bar_ptr), int(M), _dev(d_xhh_bar_ptr), _dev(d_value_end_bar_ptr), _dev(d_D_init_bar_ptr))
 
     # -- derivatives through the steady state -------------------------------------------------
     def _ss_done(self, who, names, it, res, tol, max_iter, check):
@@ -735,6 +731,13 @@ class HouseholdBlock:
                     raise SteadyStateLoopError(f"{who}: the {names[k]} loop took max_iter = {max_iter} steps and its last increment ratio "
                                                f"{res[k]:.3g} is above tol = {tol:.3g}")
 
+    def _ss_loops(self, who, names, tol, max_iter, check, symbol, *args):
+        """a steady-state entry, whose last two arguments are its loops' (iters, resid) pair: `last_ss`, the verdict of `_ss_done` -> iters"""
+        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
+        self._call(symbol, *args, it, res)
+        self._ss_done(who, names, it, res, tol, max_iter, check)
+        return (int(it[0]), int(it[1]))
+
     def ss_jvp(self, dxhh, n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
         """derivatives of the steady state's household objects in the household prices (hank_ss_jvp; what
         ForwardDiff.jacobian carries through the VFI and invariant_dist at SteadyState.jl:195). Needs `primal` at the constant
@@ -742,126 +745,97 @@ class HouseholdBlock:
         -> (dagg (n_het, N), dV (n_a, n_e, N), dpol (n_a, n_e, N), dD (n_a, n_e, N), iters (value loop, distribution loop)).
         Raises SteadyStateLoopError when a loop ran into max_iter (check=False: returns what it has; `last_ss` holds the
         increment ratios)."""
-        dx = np.asarray(dxhh, dtype=np.float64)
-        if dx.ndim == 1:
-            dx = dx[:, None]
-        N = dx.shape[1]
-        dx = _f(dx, (self.n_hh, N))
-        dagg = np.empty((max(int(n_het), 1), N), order="F")
-        dV, dpol, dD = (np.empty((self.n_a, self.n_e, N), order="F") for _ in range(3))
-        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
-        self._chk(self._lib.hank_ss_jvp(self._ctx, int(n_het), _p(dx), N, float(tol), int(max_iter), _p(dV), _p(dpol), _p(dD), _p(dagg), it, res))
-        self._ss_done("ss_jvp", ("value", "distribution"), it, res, tol, max_iter, check)
-        return dagg, dV, dpol, dD, (int(it[0]), int(it[1]))
+        dx, N = _batch(dxhh, (self.n_hh,))
+        dagg = _out(_n1(n_het), N)
+        dV, dpol, dD = (_out(self.n_a, self.n_e, N) for _ in range(3))
+        iters = self._ss_loops("ss_jvp", ("value", "distribution"), tol, max_iter, check,
+                               "hank_ss_jvp", int(n_het), _p(dx), N, float(tol), int(max_iter), _p(dV), _p(dpol), _p(dD), _p(dagg))
+        return dagg, dV, dpol, dD, iters
 
     def ss_vjp(self, agg_bar=None, value_bar=None, D_bar=None, n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
         """the transpose of `ss_jvp` (hank_ss_vjp): cotangents agg_bar (n_het,) or (n_het, M) of the steady state's aggregates,
         value_bar and D_bar (n_a, n_e[, M]) or (G, M) of V_ss and D_ss — e.g. `vjp_het_boundary`'s value_end_bar — any of them
         None (not given), at least one given. -> (xhh_bar (n_hh, M), iters (nu loop, lambda loop))."""
-        if agg_bar is None and value_bar is None and D_bar is None:
-            raise ValueError("at least one of agg_bar, value_bar, D_bar must be given")
-        yb = None
         M = None
         if agg_bar is not None:
-            yb = np.asarray(agg_bar, dtype=np.float64)
-            yb = yb[:, None] if yb.ndim == 1 else yb
-            M = yb.shape[1]
-        else:
+            M = _cols(agg_bar, 1).shape[1]
+        elif value_bar is not None or D_bar is not None:
             b = np.asarray(value_bar if value_bar is not None else D_bar)
             M = 1 if b.shape == (self.n_a, self.n_e) else b.shape[-1]
-        if yb is not None:
-            yb = _f(yb, (int(n_het), M) if 1 <= int(n_het) <= 4 else None)
-        vb, db = self._boundary_seed(value_bar, M), self._boundary_seed(D_bar, M)
-        out = np.empty((self.n_hh, M), order="F")
-        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
-        self._chk(self._lib.hank_ss_vjp(self._ctx, int(n_het), _opt(yb), _opt(vb), _opt(db), M, float(tol), int(max_iter), _p(out), it, res))
-        self._ss_done("ss_vjp", ("nu", "lambda"), it, res, tol, max_iter, check)
-        return out, (int(it[0]), int(it[1]))
+        served = 1 <= int(n_het) <= 4      # (the library refuses any other n_het)
+        M, (yb, vb, db) = _seeds((("agg_bar", agg_bar, lambda y, M: _f(_cols(y, 1), (int(n_het), M) if served else None)),
+                                  ("value_bar", value_bar, self._boundary_seed), ("D_bar", D_bar, self._boundary_seed)), M)
+        out = _out(self.n_hh, M)
+        iters = self._ss_loops("ss_vjp", ("nu", "lambda"), tol, max_iter, check,
+                               "hank_ss_vjp", int(n_het), _opt(yb), _opt(vb), _opt(db), M, float(tol), int(max_iter), _p(out))
+        return out, iters
 
     def ss_jvp_dev(self, d_dxhh_ptr: int, N: int, d_dagg_ptr: int, d_dvalue_ptr: int = 0, d_dpolicy_ptr: int = 0, d_dD_ptr: int = 0,
                    n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
         """device-pointer form of `ss_jvp` (hank_ss_jvp_dev): d_dxhh (n_hh, N) in; d_dagg (n_het, N) and the exports (G, N) out,
         all column-major, written straight to the caller's buffers; an export pointer of 0 is not wanted. The loops read their
         stop word on the host, so the call returns with the stream drained. -> iters; `last_ss` as after `ss_jvp`."""
-        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
-        self._chk(self._lib.hank_ss_jvp_dev(self._ctx, int(n_het), C.c_void_p(d_dxhh_ptr), int(N), float(tol), int(max_iter), C.c_void_p(d_dvalue_ptr or None),
-                                            C.c_void_p(d_dpolicy_ptr or None), C.c_void_p(d_dD_ptr or None), C.c_void_p(d_dagg_ptr), it, res))
-        self._ss_done("ss_jvp_dev", ("value", "distribution"), it, res, tol, max_iter, check)
-        return (int(it[0]), int(it[1]))
+        return self._ss_loops("ss_jvp_dev", ("value", "distribution"), tol, max_iter, check,
+                              "hank_ss_jvp_dev", int(n_het), _dev(d_dxhh_ptr), int(N), float(tol), int(max_iter), _dev(d_dvalue_ptr), _dev(d_dpolicy_ptr),
+                              _dev(d_dD_ptr), _dev(d_dagg_ptr))
 
     def ss_vjp_dev(self, d_agg_bar_ptr: int, d_value_bar_ptr: int, d_D_bar_ptr: int, M: int, d_xhh_bar_ptr: int,
                    n_het: int = 2, tol: float = 1e-13, max_iter: int = 50_000, check: bool = True):
         """device-pointer form of `ss_vjp` (hank_ss_vjp_dev): d_agg_bar (n_het, M), d_value_bar and d_D_bar (G, M) in, a pointer
         of 0 is a cotangent not given (at least one must be); d_xhh_bar (n_hh, M) out. -> iters; `last_ss` as after `ss_vjp`."""
-        it, res = (C.c_int32 * 2)(), (C.c_double * 2)()
-        self._chk(self._lib.hank_ss_vjp_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr or None), C.c_void_p(d_value_bar_ptr or None),
-                                            C.c_void_p(d_D_bar_ptr or None), int(M), float(tol), int(max_iter), C.c_void_p(d_xhh_bar_ptr), it, res))
-        self._ss_done("ss_vjp_dev", ("nu", "lambda"), it, res, tol, max_iter, check)
-        return (int(it[0]), int(it[1]))
+        return self._ss_loops("ss_vjp_dev", ("nu", "lambda"), tol, max_iter, check,
+                              "hank_ss_vjp_dev", int(n_het), _dev(d_agg_bar_ptr), _dev(d_value_bar_ptr), _dev(d_D_bar_ptr), int(M), float(tol), int(max_iter),
+                              _dev(d_xhh_bar_ptr))
 
     def policy_cotangent_seq(self, M: int) -> np.ndarray:
         """(n_a, n_e, P, M): cotangent of the policy sequence of the last vjp / vjp_het (hank_get_policy_cotangent_seq)."""
-        out = np.empty((self.n_a, self.n_e, self.P, max(int(M), 1)), order="F")
-        self._chk(self._lib.hank_get_policy_cotangent_seq(self._ctx, int(M), _p(out)))
+        out = _out(self.n_a, self.n_e, self.P, _n1(M))
+        self._call("hank_get_policy_cotangent_seq", int(M), _p(out))
         return out
 
+    # -- timings and counters -----------------------------------------------------------------
     def last_vjp_timings(self):
-        ms = (C.c_double * 2)()
-        ln = (C.c_int32 * 2)()
-        self._chk(self._lib.hank_last_vjp_timings(self._ctx, ms, ln))
-        return {k: {"ms": ms[i], "launches": ln[i]} for i, k in enumerate(("sweep_a", "sweep_b"))}
+        return self._ms_launches("hank_last_vjp_timings", ("sweep_a", "sweep_b"))
 
     def last_ss_timings(self):
         """time (ms, HIP events on the stream) of the two loops of the last ss_jvp / ss_vjp, in the order of their `iters` (hank_last_ss_timings)"""
-        ms = (C.c_double * 2)()
-        self._chk(self._lib.hank_last_ss_timings(self._ctx, ms))
-        return (ms[0], ms[1])
+        return self._ms_pair("hank_last_ss_timings")
 
     def last_timings(self):
-        ms = (C.c_double * 6)()
-        ln = (C.c_int32 * 6)()
-        self._chk(self._lib.hank_last_timings(self._ctx, ms, ln))
-        names = ("primal_backward", "primal_forward", "tangent_backward", "tangent_forward", "dual_backward", "dual_forward")
-        return {k: {"ms": ms[i], "launches": ln[i]} for i, k in enumerate(names)}
+        return self._ms_launches("hank_last_timings", ("primal_backward", "primal_forward", "tangent_backward", "tangent_forward", "dual_backward", "dual_forward"))
 
     def stats(self):
         """counters of the context (include/hank_hip.h: hank_stats)."""
-        out = (C.c_int64 * 8)()
-        self._chk(self._lib.hank_stats(self._ctx, out))
-        names = ("sweep_launches", "tangent_workspaces_allocated", "graphs_captured", "schedule", "fallbacks", "vfi_iterations",
-                 "primal_memo_hits", "primal_sweeps")
-        return {k: int(out[i]) for i, k in enumerate(names)}
+        return self._counters("hank_stats", ("sweep_launches", "tangent_workspaces_allocated", "graphs_captured", "schedule", "fallbacks", "vfi_iterations",
+                                             "primal_memo_hits", "primal_sweeps"))
 
     def info(self):
         """which kernel family served the last tangent sweep and how the context chooses (include/hank_hip.h: hank_info)."""
-        out = (C.c_int64 * 8)()
-        self._chk(self._lib.hank_info(self._ctx, out))
-        names = ("last_tangent_family", "wide_mode", "wide_min", "wide_supported", "xjvp_max", "record_diet", "record_bytes", "lwg_builds")
-        d = {k: int(out[i]) for i, k in enumerate(names)}
+        d = self._counters("hank_info", ("last_tangent_family", "wide_mode", "wide_min", "wide_supported", "xjvp_max", "record_diet", "record_bytes", "lwg_builds"))
         d["last_tangent_family_name"] = ("launch-per-period", "xcd-persistent", "on-chip-wide")[d["last_tangent_family"]]
         return d
 
     def sweep_instance(self):
         """which instances of the Dual pass's persistent sweeps were enqueued last (include/hank_hip.h: hank_sweep_instance):
         {"back": (NE, CRRA), "fwd": (NE, CRRA)}; -1 before the first Dual pass."""
-        out = (C.c_int32 * 4)()
-        self._chk(self._lib.hank_sweep_instance(self._ctx, out))
+        out, = self._read("hank_sweep_instance", (C.c_int32 * 4)())
         return {"back": (int(out[0]), int(out[1])), "fwd": (int(out[2]), int(out[3]))}
 
+    # -- what the last sweeps left ------------------------------------------------------------
     def policy_seq(self) -> np.ndarray:
         """(n_a, n_e, P): policy matrix of every period (BackwardIteration's return value)."""
-        out = np.empty((self.n_a, self.n_e, self.P), order="F")
-        self._chk(self._lib.hank_get_policy_seq(self._ctx, _p(out)))
+        out = _out(self.n_a, self.n_e, self.P)
+        self._call("hank_get_policy_seq", _p(out))
         return out
 
     def lottery_record(self):
         """the Young lottery of the last primal as the record holds it (hank_get_lottery_record): lo, lw, ig of shape (n_a, n_e, P),
         the packed records lq (structured: w, lo, flags) of the same shape and the grid's inverse gaps iga (n_a,)."""
         shp = (self.n_a, self.n_e, self.P)
-        lo, lw, ig = np.empty(shp, np.int32, order="F"), np.empty(shp, order="F"), np.empty(shp, order="F")
+        lo, lw, ig = np.empty(shp, np.int32, order="F"), _out(*shp), _out(*shp)
         lq = np.empty(shp, np.dtype([("w", "<f8"), ("lo", "<i4"), ("flags", "<i4")]), order="F")
         iga = np.empty(self.n_a)
-        self._chk(self._lib.hank_get_lottery_record(self._ctx, lo.ctypes.data_as(C.c_void_p), _p(lw), _p(ig), lq.ctypes.data_as(C.c_void_p), _p(iga)))
+        self._call("hank_get_lottery_record", lo.ctypes.data_as(C.c_void_p), _p(lw), _p(ig), lq.ctypes.data_as(C.c_void_p), _p(iga))
         return {"lo": lo, "lw": lw, "ig": ig, "lq": lq, "iga": iga}
 
     def forward_units(self):
@@ -869,18 +843,18 @@ class HouseholdBlock:
         (P, S, 64, 2) as the library lays them out, S = ceil(n_a / 63) members; src >> 18 is a member's unit count."""
         S = (self.n_a + 62) // 63
         src, units = np.empty((self.P, S), np.int32), np.empty((self.P, S, 64, 2), np.int32)
-        self._chk(self._lib.hank_get_forward_units(self._ctx, src.ctypes.data_as(C.c_void_p), units.ctypes.data_as(C.c_void_p)))
+        self._call("hank_get_forward_units", src.ctypes.data_as(C.c_void_p), units.ctypes.data_as(C.c_void_p))
         return src, units
 
     def dist_seq(self) -> np.ndarray:
-        out = np.empty((self.n_a, self.n_e, self.P), order="F")
-        self._chk(self._lib.hank_get_dist_seq(self._ctx, _p(out)))
+        out = _out(self.n_a, self.n_e, self.P)
+        self._call("hank_get_dist_seq", _p(out))
         return out
 
     def dpolicy_seq(self, N: int) -> np.ndarray:
         """(n_a, n_e, P, N): partials of the policy sequence of the last jvp."""
-        out = np.empty((self.n_a, self.n_e, self.P, N), order="F")
-        self._chk(self._lib.hank_get_dpolicy_seq(self._ctx, int(N), _p(out)))
+        out = _out(self.n_a, self.n_e, self.P, N)
+        self._call("hank_get_dpolicy_seq", int(N), _p(out))
         return out
 
     def het_outputs(self, n_het: int = 2, dxhh=None, dy=None):
@@ -890,61 +864,58 @@ class HouseholdBlock:
         (n_hh, P, N) — the input of the last tangent sweep — is given (else None). dy (n_e, P, N): income directions
         (hank_get_het_outputs_income, n_het <= 2) for consumption's direct term, in place of the ones a batch of `jvp_income`
         carries and adds by itself; dxhh may then be None (zeros)."""
-        agg = np.empty((self.P, n_het), order="F")
+        agg = _out(self.P, n_het)
         if dy is not None:
-            N, dx, d = self._income_dirs(dxhh, dy)
+            N, dx, d = self._path_dirs("income", dxhh, dy)
             if dx is None:
                 dx = np.zeros((self.n_hh, self.P, N), order="F")
-            dagg = np.empty((self.P, n_het, N), order="F")
-            self._chk(self._lib.hank_get_het_outputs_income(self._ctx, int(n_het), _p(dx), _p(d), N, _p(agg), _p(dagg)))
+            dagg = _out(self.P, n_het, N)
+            self._call("hank_get_het_outputs_income", int(n_het), _p(dx), _p(d), N, _p(agg), _p(dagg))
             return agg, dagg
         if dxhh is None:
-            self._chk(self._lib.hank_get_het_outputs(self._ctx, int(n_het), None, 0, _p(agg), None))
+            self._call("hank_get_het_outputs", int(n_het), None, 0, _p(agg), None)
             return agg, None
-        dxhh = np.asfortranarray(dxhh, dtype=np.float64)
-        if dxhh.ndim != 3 or dxhh.shape[:2] != (self.n_hh, self.P):
-            raise ValueError(f"dxhh must be ({self.n_hh}, {self.P}, N), got {dxhh.shape}")
-        N = dxhh.shape[2]
-        dagg = np.empty((self.P, n_het, N), order="F")
-        self._chk(self._lib.hank_get_het_outputs(self._ctx, int(n_het), _p(dxhh), N, _p(agg), _p(dagg)))
+        dxhh, N = self._sweep_input(dxhh)
+        dagg = _out(self.P, n_het, N)
+        self._call("hank_get_het_outputs", int(n_het), _p(dxhh), N, _p(agg), _p(dagg))
         return agg, dagg
 
     def set_het_outputs(self, n_het: int):
         """declare how many heterogeneous outputs het_outputs will be asked for (hank_set_het_outputs; default 2)."""
-        self._chk(self._lib.hank_set_het_outputs(self._ctx, int(n_het)))
+        self._call("hank_set_het_outputs", int(n_het))
         self._n_het_declared = int(n_het)
 
     def het_outputs_dev(self, n_het: int, d_dxhh: int, N: int, d_agg: int, d_dagg: int, d_dy: int = 0):
         """device-pointer form (asynchronous on the context's stream); d_dy: the income directions (hank_get_het_outputs_income_dev)."""
         if d_dy:
-            self._chk(self._lib.hank_get_het_outputs_income_dev(self._ctx, int(n_het), d_dxhh or None, d_dy, int(N), d_agg or None, d_dagg or None))
+            self._call("hank_get_het_outputs_income_dev", int(n_het), _dev(d_dxhh), _dev(d_dy), int(N), _dev(d_agg), _dev(d_dagg))
             return
-        self._chk(self._lib.hank_get_het_outputs_dev(self._ctx, int(n_het), d_dxhh or None, int(N), d_agg or None, d_dagg or None))
+        self._call("hank_get_het_outputs_dev", int(n_het), _dev(d_dxhh), int(N), _dev(d_agg), _dev(d_dagg))
 
     def grid_aggregates(self, N: int = 0):
         """the grid-weighted aggregate sum_pt a(pt) D_t(pt) of the last primal sweep, and (N > 0) its partials (P, N) of the
         last tangent sweep (hank_get_grid_aggregates)."""
         agg2 = np.empty(self.P)
-        dagg2 = np.empty((self.P, N), order="F") if N > 0 else None
-        self._chk(self._lib.hank_get_grid_aggregates(self._ctx, _p(agg2), int(N), _p(dagg2) if N > 0 else None))
+        dagg2 = _out(self.P, N) if N > 0 else None
+        self._call("hank_get_grid_aggregates", _p(agg2), int(N), _opt(dagg2))
         return agg2, dagg2
 
     def fake_news(self):
         """the household block's Jacobian at the steady state from its Toeplitz structure (hank_fake_news):
         -> F (P, P, n_hh), Dv (P, n_hh); `SteadyStateJacobian.household_jacobian` turns them into d agg_t / d xhh_{k,s}."""
-        F = np.empty((self.P, self.P, self.n_hh), order="F")
-        Dv = np.empty((self.P, self.n_hh), order="F")
-        self._chk(self._lib.hank_fake_news(self._ctx, _p(F), _p(Dv)))
+        F = _out(self.P, self.P, self.n_hh)
+        Dv = _out(self.P, self.n_hh)
+        self._call("hank_fake_news", _p(F), _p(Dv))
         return F, Dv
 
     def fake_news_het(self, n_het: int):
         """the same Toeplitz form for heterogeneous outputs 0 .. n_het-1 of `het_outputs` (hank_fake_news_het):
         -> F (P, P, n_hh, n_het), Dv (P, n_hh, n_het); output 0 equals `fake_news()` bit for bit, and
         `household_jacobian(F[..., o], Dv[..., o])` is d agg^o_t / d xhh_{k,s}."""
-        nb = max(int(n_het), 1)                  # (the library refuses an n_het outside 1..3 / 1..4)
-        F = np.empty((self.P, self.P, self.n_hh, nb), order="F")
-        Dv = np.empty((self.P, self.n_hh, nb), order="F")
-        self._chk(self._lib.hank_fake_news_het(self._ctx, int(n_het), _p(F), _p(Dv)))
+        nb = _n1(n_het)                  # (the library refuses an n_het outside 1..3 / 1..4)
+        F = _out(self.P, self.P, self.n_hh, nb)
+        Dv = _out(self.P, self.n_hh, nb)
+        self._call("hank_fake_news_het", int(n_het), _p(F), _p(Dv))
         return F, Dv
 
     # -- group outputs: aggregates by household group -------------------------------------------
@@ -954,42 +925,38 @@ class HouseholdBlock:
         GROUP_CONS (one value serves every group). K = 0 (W=None) clears them. The record, the current tangent batch, the primal memo
         and the `set_het_outputs` count stay as they are. `clone()` does not carry the groups."""
         if W is None:
-            self._chk(self._lib.hank_set_group_outputs(self._ctx, 0, None, None))
+            self._call("hank_set_group_outputs", 0, None, None)
             self.n_groups = 0
             return
         W = np.asarray(W, dtype=np.float64)
-        if W.ndim == 3 and W.shape[:2] == (self.n_a, self.n_e):
-            W = W.reshape(self.G, W.shape[2], order="F")
-        if W.ndim == 1:
-            W = W[:, None]
+        if W.ndim == 3:      # (a lone (n_a, n_e) matrix is not one group here, as it never was)
+            W = _grid_batch(W, self.n_a, self.n_e)
+        W = _cols(W, 1)
         if W.ndim != 2 or W.shape[0] != self.G:
             raise ValueError(f"W must be ({self.G}, K) or ({self.n_a}, {self.n_e}, K), got {W.shape}")
         W = np.asfortranarray(W)
         K = W.shape[1]
         b = np.ascontiguousarray(np.broadcast_to(np.asarray(base, dtype=np.int32), (K,)))
-        self._chk(self._lib.hank_set_group_outputs(self._ctx, K, _p(W), b.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._call("hank_set_group_outputs", K, _p(W), _ip(b))
         self.n_groups = K
 
     def group_outputs(self, dxhh=None):
         """the group outputs of the last sweeps (hank_get_group_outputs; ForwardIteration.jl:303-307): Y^k_t = sum W_k f D_t.
         -> agg (P, K), and dagg (P, K, N) when `dxhh` (n_hh, P, N) — the input of the last tangent sweep — is given (else
         None). The rules of `het_outputs`; a batch with boundary seeds is refused."""
-        K = max(self.n_groups, 1)      # (the library refuses a call without groups)
-        agg = np.empty((self.P, K), order="F")
+        K = _n1(self.n_groups)      # (the library refuses a call without groups)
+        agg = _out(self.P, K)
         if dxhh is None:
-            self._chk(self._lib.hank_get_group_outputs(self._ctx, None, 0, _p(agg), None))
+            self._call("hank_get_group_outputs", None, 0, _p(agg), None)
             return agg, None
-        dxhh = np.asfortranarray(dxhh, dtype=np.float64)
-        if dxhh.ndim != 3 or dxhh.shape[:2] != (self.n_hh, self.P):
-            raise ValueError(f"dxhh must be ({self.n_hh}, {self.P}, N), got {dxhh.shape}")
-        N = dxhh.shape[2]
-        dagg = np.empty((self.P, K, N), order="F")
-        self._chk(self._lib.hank_get_group_outputs(self._ctx, _p(dxhh), N, _p(agg), _p(dagg)))
+        dxhh, N = self._sweep_input(dxhh)
+        dagg = _out(self.P, K, N)
+        self._call("hank_get_group_outputs", _p(dxhh), N, _p(agg), _p(dagg))
         return agg, dagg
 
     def group_outputs_dev(self, d_dxhh: int, N: int, d_agg: int, d_dagg: int):
         """device-pointer form (asynchronous on the context's stream)."""
-        self._chk(self._lib.hank_get_group_outputs_dev(self._ctx, d_dxhh or None, int(N), d_agg or None, d_dagg or None))
+        self._call("hank_get_group_outputs_dev", _dev(d_dxhh), int(N), _dev(d_agg), _dev(d_dagg))
 
     def vjp_group(self, grp_bar, agg_bar=None, n_het: int = 0, value_end: bool = False, D_init: bool = False):
         """the transpose of `group_outputs`' tangent map (hank_vjp_group; the reverse rules of ForwardIteration.jl:339-420 with the
@@ -999,9 +966,7 @@ class HouseholdBlock:
         `vjp_het_boundary`, an unwanted one None. `policy_cotangent_seq(M)` serves its policy cotangent afterwards."""
         gb, M = None, None
         if grp_bar is not None:
-            gb = np.asarray(grp_bar, dtype=np.float64)
-            if gb.ndim == 2:
-                gb = gb[:, :, None]
+            gb = _cols(grp_bar, 2)
             if gb.ndim != 3:
                 raise ValueError("grp_bar must be (P, K) or (P, K, M)")
             M = gb.shape[2]
@@ -1013,26 +978,24 @@ class HouseholdBlock:
                 raise ValueError(f"agg_bar has {Ma} columns, grp_bar {M}")
             M = Ma
         M = 1 if M is None else M
-        out = np.empty((self.n_hh, self.P, max(M, 1)), order="F")
-        vb = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if value_end else None
-        db = np.empty((self.n_a, self.n_e, max(M, 1)), order="F") if D_init else None
-        self._chk(self._lib.hank_vjp_group(self._ctx, int(n_het), _opt(yb), _opt(gb), M, _p(out), _opt(vb), _opt(db)))
+        out, vb, db = self._cot_outputs(M, value_end, D_init)
+        self._call("hank_vjp_group", int(n_het), _opt(yb), _opt(gb), M, _p(out), _opt(vb), _opt(db))
         return (out, vb, db) if (value_end or D_init) else out
 
     def vjp_group_dev(self, n_het: int, d_agg_bar_ptr: int, d_grp_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_value_end_bar_ptr: int = 0,
                       d_D_init_bar_ptr: int = 0):
         """device-pointer form (asynchronous on the context's stream); an agg_bar pointer of 0 goes with n_het = 0, a boundary pointer
         of 0 is not wanted."""
-        self._chk(self._lib.hank_vjp_group_dev(self._ctx, int(n_het), C.c_void_p(d_agg_bar_ptr or None), C.c_void_p(d_grp_bar_ptr or None), int(M),
-                                               C.c_void_p(d_xhh_bar_ptr), C.c_void_p(d_value_end_bar_ptr or None), C.c_void_p(d_D_init_bar_ptr or None)))
+        self._call("hank_vjp_group_dev", int(n_het), _dev(d_agg_bar_ptr), _dev(d_grp_bar_ptr), int(M), _dev(d_xhh_bar_ptr), _dev(d_value_end_bar_ptr),
+                   _dev(d_D_init_bar_ptr))
 
     def fake_news_group(self):
         """the Toeplitz form of `fake_news_het` for the group outputs (hank_fake_news_group): -> F (P, P, n_hh, K),
         Dv (P, n_hh, K); `household_jacobian(F[..., k], Dv[..., k])` is d Y^k_t / d xhh_{i,s}."""
-        K = max(self.n_groups, 1)
-        F = np.empty((self.P, self.P, self.n_hh, K), order="F")
-        Dv = np.empty((self.P, self.n_hh, K), order="F")
-        self._chk(self._lib.hank_fake_news_group(self._ctx, _p(F), _p(Dv)))
+        K = _n1(self.n_groups)
+        F = _out(self.P, self.P, self.n_hh, K)
+        Dv = _out(self.P, self.n_hh, K)
+        self._call("hank_fake_news_group", _p(F), _p(Dv))
         return F, Dv
 
     def vfi(self, value0, xhh_t, tol: float, max_iter: int = 10_000):
@@ -1040,9 +1003,9 @@ class HouseholdBlock:
         -> (value, policy, steps, last sup-norm)."""
         v = _f(np.array(value0, dtype=np.float64, copy=True), (self.n_a, self.n_e))
         x = _f(xhh_t, (self.n_hh,))
-        pol = np.empty((self.n_a, self.n_e), order="F")
+        pol = _out(self.n_a, self.n_e)
         it, nrm = C.c_int32(), C.c_double()
-        self._chk(self._lib.hank_vfi(self._ctx, _p(x), float(tol), int(max_iter), _p(v), _p(pol), C.byref(it), C.byref(nrm)))
+        self._call("hank_vfi", _p(x), float(tol), int(max_iter), _p(v), _p(pol), C.byref(it), C.byref(nrm))
         return v, pol, it.value, nrm.value
 
     def stationary_dist(self, policy, D0=None, tol: float = 1e-15, max_iter: int = 500_000, check_every: int = 25):
@@ -1052,7 +1015,7 @@ class HouseholdBlock:
         d = np.full(self.G, 1.0 / self.G) if D0 is None else np.asarray(D0, dtype=np.float64).reshape(-1, order="F") / np.sum(D0)
         d = _f(d.reshape((self.n_a, self.n_e), order="F"))
         it = C.c_int32()
-        self._chk(self._lib.hank_stationary_dist(self._ctx, _p(p), _p(d), float(tol), int(max_iter), int(check_every), C.byref(it)))
+        self._call("hank_stationary_dist", _p(p), _p(d), float(tol), int(max_iter), int(check_every), C.byref(it))
         out = d.reshape(-1, order="F")
         return out / out.sum(), it.value
 
@@ -1060,9 +1023,8 @@ class HouseholdBlock:
     def backward_step(self, value_next, xhh_t):
         v = _f(value_next, (self.n_a, self.n_e))
         x = _f(xhh_t, (self.n_hh,))
-        vo = np.empty((self.n_a, self.n_e), order="F")
-        po = np.empty((self.n_a, self.n_e), order="F")
-        self._chk(self._lib.hank_backward_step(self._ctx, _p(v), _p(x), _p(vo), _p(po)))
+        vo, po = _out(self.n_a, self.n_e), _out(self.n_a, self.n_e)
+        self._call("hank_backward_step", _p(v), _p(x), _p(vo), _p(po))
         return vo, po
 
     def backward_step_dual(self, value_next, dvalue_next, xhh_t, dxhh_t):
@@ -1072,20 +1034,17 @@ class HouseholdBlock:
         dv = _f(dv, (self.n_a, self.n_e, N))
         x = _f(xhh_t, (self.n_hh,))
         dx = _f(dxhh_t, (self.n_hh, N))
-        vo = np.empty((self.n_a, self.n_e), order="F")
-        po = np.empty((self.n_a, self.n_e), order="F")
-        dvo = np.empty((self.n_a, self.n_e, N), order="F")
-        dpo = np.empty((self.n_a, self.n_e, N), order="F")
-        self._chk(self._lib.hank_backward_step_dual(self._ctx, _p(v), _p(dv), _p(x), _p(dx), N,
-                                                    _p(vo), _p(dvo), _p(po), _p(dpo)))
+        vo, po = _out(self.n_a, self.n_e), _out(self.n_a, self.n_e)
+        dvo, dpo = _out(self.n_a, self.n_e, N), _out(self.n_a, self.n_e, N)
+        self._call("hank_backward_step_dual", _p(v), _p(dv), _p(x), _p(dx), N, _p(vo), _p(dvo), _p(po), _p(dpo))
         return vo, dvo, po, dpo
 
     def forward_step(self, policy, D_prev):
         p = _f(policy, (self.n_a, self.n_e))
         d = _f(np.asarray(D_prev, dtype=np.float64).reshape((self.n_a, self.n_e), order="F"))
-        do = np.empty((self.n_a, self.n_e), order="F")
+        do = _out(self.n_a, self.n_e)
         agg = C.c_double()
-        self._chk(self._lib.hank_forward_step(self._ctx, _p(p), _p(d), _p(do), C.byref(agg)))
+        self._call("hank_forward_step", _p(p), _p(d), _p(do), C.byref(agg))
         return do, agg.value
 
     def forward_step_dual(self, policy, dpolicy, D_prev, dD_prev):
@@ -1095,10 +1054,8 @@ class HouseholdBlock:
         dp_ = _f(dp_, (self.n_a, self.n_e, N))
         d = _f(np.asarray(D_prev, dtype=np.float64).reshape((self.n_a, self.n_e), order="F"))
         dd = _f(np.asarray(dD_prev, dtype=np.float64).reshape((self.n_a, self.n_e, N), order="F"))
-        do = np.empty((self.n_a, self.n_e), order="F")
-        ddo = np.empty((self.n_a, self.n_e, N), order="F")
+        do, ddo = _out(self.n_a, self.n_e), _out(self.n_a, self.n_e, N)
         agg = C.c_double()
         dagg = np.empty(N)
-        self._chk(self._lib.hank_forward_step_dual(self._ctx, _p(p), _p(dp_), _p(d), _p(dd), N,
-                                                   _p(do), _p(ddo), C.byref(agg), _p(dagg)))
+        self._call("hank_forward_step_dual", _p(p), _p(dp_), _p(d), _p(dd), N, _p(do), _p(ddo), C.byref(agg), _p(dagg))
         return do, ddo, agg.value, dagg

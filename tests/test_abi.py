@@ -19,6 +19,35 @@ def test_header_and_binding_agree(hank):
     assert _declared_symbols() == sorted(hip.ABI_SYMBOLS)
 
 
+def _ctype_class(t):
+    """the class of a ctypes type as tests/abi_header.py names the header's: "ptr", "i32", "f64" (None: none of them)"""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_double))):
+        return "ptr"
+    return {ctypes.c_int32: "i32", ctypes.c_double: "f64"}.get(t)
+
+
+def test_header_and_binding_agree_on_every_signature(hank):
+    """arity, the class of every parameter (pointer — arrays included —, int32_t, double) and the return class, for every
+    symbol; a table row the header does not have, or the reverse, fails the name comparison above"""
+    from abi_header import prototypes
+    from hank_amd import hip
+    protos = prototypes()
+    assert len(protos) == len(hip.ABI) == len(hip.ABI_SYMBOLS) == 83 and sorted(protos) == sorted(hip.ABI) == _declared_symbols()
+    assert hip.ABI_OPTIONAL <= set(hip.ABI) and set(hip.ABI_RESTYPE) <= set(hip.ABI)
+    for name, proto in protos.items():
+        assert tuple(_ctype_class(t) for t in hip.ABI[name]) == proto.params, name
+        ret = hip.ABI_RESTYPE.get(name, ctypes.c_int)
+        assert {"int": ret is ctypes.c_int, "str": ret is ctypes.c_char_p}[proto.ret], name
+
+
+def test_header_and_binding_agree_on_the_model_struct(hank):
+    from abi_header import model_fields
+    from hank_amd import hip
+    classes = {ctypes.c_int32: "i32", ctypes.c_double: "f64", ctypes.POINTER(ctypes.c_double): "ptr_f64"}
+    assert [(n, classes[t]) for n, t in hip.hank_model._fields_] == model_fields()
+    assert len(model_fields()) == 10
+
+
 def test_library_exports_every_declared_symbol(hank):
     from hank_amd import hip
     lib = ctypes.CDLL(str(hip.library_path()))
