@@ -427,6 +427,15 @@ def adj_rows_per_block(M):
     return max(64 // NC, 8)
 
 
+def shk_mc(M):
+    """the cotangent columns across k_shk_bbar's lanes at batch width M (shk_mc, csrc/hank_hip.hip: the next power of two, 64 at
+    most); k_inc_ybar takes min(shk_mc(M), INC_MC = 32) of them (tests/test_income_host.py holds the two together)."""
+    mc = 1
+    while mc < M and mc < 64:
+        mc *= 2
+    return mc
+
+
 def check_edges(name, grid, pol):
     """measure and print the edges of EDGE_GRIDS[name] on the policy sequence pol (P, n_a, n_e), and assert the ones EDGE_NEEDS
     promises. -> {"clo_lt_nb": bool, "clo_gt_nb": bool}: on which side of the row-block count the deep prefixes fall."""

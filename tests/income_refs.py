@@ -1,5 +1,5 @@
 """The references of the income path by productivity state (hank_set_income_path, hank_jvp_income, hank_vjp_income,
-hank_fake_news_income), shared by tests/test_income_host.py (CPU) and tests/test_gpu_income.py.
+hank_fake_news_income), shared by tests/test_income_host.py (CPU), tests/test_gpu_income.py and tests/test_gpu_income_geometry.py.
 
 1. `oracle_income_sweeps`: the loop of `sweep_refs.oracle_sweeps` built from the unchanged oracle. A column's EGM step depends only on
    its own income and on the common V_{t+1}, so for each period t and each state e' `Oracle.value_function` runs with the dual transfer
@@ -10,7 +10,9 @@ hank_fake_news_income), shared by tests/test_income_host.py (CPU) and tests/test
    scaled to 2 % of the smallest w z_e.
 3. `oracle_income_jacobians`, `income_linear`, `income_y_bar`: the dense pair (Jx, Jy) from unit tangents, cached, and the linear and
    transposed products of it.
-4. `StubIncomeBlock`: stands in for the device context under `SteadyStateJacobian.income_jacobian` (the pattern of StubShockBlock)."""
+4. `StubIncomeBlock`: stands in for the device context under `SteadyStateJacobian.income_jacobian` (the pattern of StubShockBlock).
+5. `geometry_case`, `oracle_income_grid_jacobians`, `check_income_edges`, `rescaled_D0`, GEOM_M, GEOM_N: the economies, the grid
+   aggregate's pair and the widths of tests/test_gpu_income_geometry.py, whose conditions tests/test_income_host.py checks on the CPU."""
 import numpy as np
 
 import cases
@@ -179,6 +181,56 @@ def income_linear(J, dx, dy):
 def income_y_bar(Jy, yb):
     """y_bar (n_e, P, M): [e, s, m] = sum_{t,o} Jy[t, o, e, s] yb[t, o, m] over the outputs yb (P, n_het, M) holds"""
     return np.einsum("toes,tom->esm", Jy[:, :yb.shape[1]], yb)
+
+
+def oracle_income_grid_jacobians(orc, x, V, D, y=None):
+    """the same pair for the grid-weighted aggregate of hank_get_grid_aggregates, from the same two sweeps (the counterpart of
+    shock_refs.oracle_shock_grid_jacobians): -> (J2x (P, n_hh, P) as [t, k, s], J2y (P, n_e, P) as [t, e, s])"""
+    sx, sy = _unit_sweeps(orc, x, V, D, y)
+    n_hh, P = np.asarray(x).shape
+    return (np.ascontiguousarray(sx["dagg2"].reshape(P, P, n_hh).transpose(0, 2, 1)),
+            np.ascontiguousarray(sy["dagg2"].reshape(P, P, orc.n_e).transpose(0, 2, 1)))
+
+
+def income_grid_linear(J2, dx, dy):
+    """dagg2 (P, N) = J2x dx + J2y dy of J2 = `oracle_income_grid_jacobians`' pair; dx (n_hh, P, N) or None, dy (n_e, P, N) or None"""
+    return (0.0 if dx is None else np.einsum("tks,ksn->tn", J2[0], dx)) + (0.0 if dy is None else np.einsum("tes,esn->tn", J2[1], dy))
+
+
+# ---- 5. the economies of tests/test_gpu_income_geometry.py ------------------------------------------------------------------------------
+# the cotangent and direction widths: tests/test_gpu_shock_geometry.py's lists, and M = 5 besides — k_inc_ybar's columns across the lanes
+# stop at 32 where k_shk_bbar's go on to 64, so its (RO, MC) pairs are not that kernel's: (8, 8) is reached by M = 5 and 7 alone
+# (tests/test_income_host.py holds the widths and the launch arithmetic together)
+GEOM_M = (1, 2, 3, 4, 5, 6, 8, 16, 17, 32, 34, 64, 65, 66, 97, 130, 256)
+GEOM_N = (2, 4, 16, 34, 64, 66, 129, 130, 256)
+EDGE_ECONOMIES = shock_refs.EDGE_ECONOMIES
+D0_SCALE = (0.5, 1.0, 1.5)
+
+
+def geometry_case(kind, *key):
+    """`shock_refs.geometry_case`'s economies — ("shape", n_a, n_e, T), ("raw", name); Krusell-Smith at gamma = 2, the record diet
+    `raw_case` has — with y = income_path(orc.z, x) and n_het = 2 in place of the beta path and the three outputs, cached"""
+    k = ("geometry", kind) + key
+    if k not in _CASES:
+        c = dict(shock_refs.geometry_case(kind, *key))
+        c.update(y=income_path(c["orc"].z, c["x"]), n_het=N_HET)
+        del c["path"]
+        _CASES[k] = c
+    return _CASES[k]
+
+
+def check_income_edges(name, grid, pol):
+    """a policy sequence pol (P, n_a, n_e) recorded under `income_path` still holds the edges of its raw-grid economy: the figures
+    `shock_refs.check_path_edges` asks for under a beta path, as they are"""
+    return shock_refs.check_path_edges(name, grid, pol)
+
+
+def rescaled_D0(c, scale=D0_SCALE):
+    """a second D_0 (G,) of case c (three columns) whose column masses differ: column e scaled by scale[e], renormalised"""
+    n_a, n_e = c["V"].shape
+    assert n_e == len(scale)
+    D = np.asarray(c["D"]).reshape((n_a, n_e), order="F") * np.asarray(scale)[None, :]
+    return np.ascontiguousarray((D / D.sum()).reshape(-1, order="F"))
 
 
 def income_seeds(c, N, seed, t_only=None):

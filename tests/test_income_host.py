@@ -6,10 +6,14 @@
 3. the dense pair (Jx, Jy) against the sweeps with random seeds in the inputs and in y together, and its transpose;
 4. hank_amd.incidence: the zero-sum property, the z-path's tangent against a difference, the incidence rule's normalisation;
 5. SteadyStateJacobian.income_jacobian's recursion on a stand-in block;
-6. examples/solve_hank.py's arguments."""
+6. examples/solve_hank.py's arguments;
+7. what tests/test_gpu_income_geometry.py relies on: the raw grids' edges under the income path and exact zeros at clamped points, the
+   grid aggregate's pair (J2x, J2y), the reference at n_e = 1 and 16 against a difference of its own level, column masses that follow
+   D_0 and not x, and the cotangent widths against k_inc_ybar's launch arithmetic restated in Python."""
 import numpy as np
 import pytest
 
+import cases
 import income_refs as R
 import sweep_refs
 from cases import close, jt
@@ -85,6 +89,116 @@ def test_the_dense_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, family
     rhs = np.einsum("ksm,ksn->mn", jt(Jx, yb), dx) + np.einsum("esm,esn->mn", R.income_y_bar(Jy, yb), dy)
     scale = np.einsum("tom,ton->mn", np.abs(yb), R.income_linear((np.abs(Jx), np.abs(Jy)), np.abs(dx), np.abs(dy)))
     assert np.all(np.abs(lhs - rhs) <= 1e-13 * scale), np.max(np.abs(lhs - rhs) / scale)
+
+
+# ---- 7. the conditions of tests/test_gpu_income_geometry.py -----------------------------------------------------------------------------
+@pytest.mark.parametrize("name", R.EDGE_ECONOMIES)
+def test_the_raw_grids_keep_their_edges_under_an_income_path(oracle_mod, name):
+    """section D of the GPU module: under income_path the oracle's policy holds the deep clamped prefix, the capped sources and the
+    long runs (measured: clo up to 47 on dense-bottom, 56 on both, 205 on deep-prefix with sources past row 128; swing clamps every
+    column in period 1 and none in period 2), and a clamped (t, a, e) does not move with any y_s[e']: its partials are exact zeros"""
+    c = R.geometry_case("raw", name)
+    n_e, P = c["y"].shape
+    assert P == cases.EDGE_P and c["n_het"] == 2 and "path" not in c
+    _, sy = R._unit_sweeps(c["orc"], c["x"], c["V"], c["D"], c["y"])
+    assert np.all(np.isfinite(sy["pol"])) and sy["dpol"].shape == sy["pol"].shape + (n_e * P,)
+    R.check_income_edges(name, c["grid"], sy["pol"])
+    clamped = sy["pol"] <= c["grid"][0]
+    assert clamped.any(axis=1).any(), name
+    assert not np.any(sy["dpol"][clamped]), name
+    assert np.any(sy["dpol"][~clamped]), name
+
+
+GRID_PAIR_ECONOMIES = [("shape", 65, 3, 12), ("shape", 40, 16, 10), ("shape", 40, 1, 10), ("raw", "both")]
+
+
+@pytest.mark.parametrize("econ", GRID_PAIR_ECONOMIES, ids=lambda e: "-".join(str(q) for q in e))
+def test_the_grid_aggregate_s_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, econ):
+    """(J2x, J2y) against oracle_income_sweeps' dagg2 with random dx and dy together (1e-13 of the largest entry)"""
+    c = R.geometry_case(*econ)
+    n_hh, P = c["x"].shape
+    n_e = c["y"].shape[0]
+    args = (c["orc"], c["x"], c["V"], c["D"], c["y"])
+    J2x, J2y = J2 = R.oracle_income_grid_jacobians(*args)
+    assert J2x.shape == (P, n_hh, P) and J2y.shape == (P, n_e, P)
+    rng = np.random.default_rng(P + n_e)
+    dx, dy = rng.standard_normal((n_hh, P, 5)), rng.standard_normal((n_e, P, 5))
+    ref = R.oracle_income_sweeps(*args, dx=dx, dy=dy)
+    close(R.income_grid_linear(J2, dx, dy), ref["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate")
+    close(R.income_grid_linear(J2, None, dy), R.oracle_income_sweeps(*args, dy=dy)["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate, y alone")
+    assert np.abs(J2y).max() > 2e-2 and min(np.abs(R.oracle_income_jacobians(*args)[1][:, o]).max() for o in range(2)) > 2e-2
+
+
+@pytest.mark.parametrize("n_e", [1, 16])
+def test_the_reference_at_one_and_at_sixteen_states_is_the_derivative_of_its_own_level(oracle_mod, n_e):
+    c = R.geometry_case("shape", 40, n_e, 4)
+    P = 3
+    assert c["y"].shape == (n_e, P) and c["orc"].n_e == n_e
+    entries = sorted({(0, 0), (n_e - 1, P - 1)})                         # (state, period)
+    dy = np.zeros((n_e, P, len(entries)))
+    for k, (e, t) in enumerate(entries):
+        dy[e, t, k] = 1.0
+    args = (c["orc"], c["x"], c["V"], c["D"])
+    ref = R.oracle_income_sweeps(*args, c["y"], dy=dy)
+    for k, (e, t) in enumerate(entries):
+        lv = []
+        for sgn in (1.0, -1.0):
+            y = c["y"].copy()
+            y[e, t] += sgn * STEP
+            lv.append(R.oracle_income_sweeps(*args, y))
+        what = f"40x{n_e} T=4 y_{t}[{e}]"
+        fd_agg = (lv[0]["agg"] - lv[1]["agg"]) / (2 * STEP)
+        fd_pol = (lv[0]["pol"] - lv[1]["pol"]) / (2 * STEP)
+        assert np.abs(fd_agg).max() > 1e-3, what
+        for o in range(2):
+            close(ref["dagg"][:, o, k], fd_agg[:, o], rel=1e-6, ab=0.0, what=f"{what} output {o}")
+        close(ref["dpol"][..., k], fd_pol, rel=1e-6, ab=0.0, what=f"{what} policy")
+        assert not np.any(ref["dpol"][t + 1:, ..., k]) and np.any(ref["dpol"][t, :, e, k])
+
+
+def test_the_column_masses_follow_the_initial_distribution_and_not_the_inputs(oracle_mod):
+    """m_t[e] = sum_a D_t[e, a] is the productivity chain's alone: it does not move with x (measured: 3.9e-16) and does with a D_0
+    whose column masses differ (measured: 0.16). Section F.4 of the GPU module tells a stale m_t[e] from a fresh one by this."""
+    c = R.geometry_case("shape", 65, 3, 12)
+    args = (c["orc"], c["x"], c["V"])
+    mass = R.oracle_income_sweeps(*args, c["D"], c["y"])["mass"]
+    close(mass.sum(axis=1), np.ones(11), what="the column masses sum to one")
+    moved_x = R.oracle_income_sweeps(c["orc"], c["x"] * np.array([[1.3], [0.97]]), c["V"], c["D"], c["y"])
+    assert np.abs(moved_x["pol"] - R.oracle_income_sweeps(*args, c["D"], c["y"])["pol"]).max() > 1e-3
+    print(f"column masses under another x: max move {np.abs(moved_x['mass'] - mass).max():.3e}")
+    assert np.abs(moved_x["mass"] - mass).max() <= 1e-14
+    D2 = R.rescaled_D0(c)
+    assert D2.shape == c["D"].shape and abs(D2.sum() - 1.0) <= 1e-15
+    mass2 = R.oracle_income_sweeps(*args, D2, c["y"])["mass"]
+    print(f"column masses under the rescaled D_0: max move {np.abs(mass2 - mass).max():.3e}")
+    assert np.abs(mass2 - mass).max() > 0.1
+
+
+def test_the_cotangent_widths_reach_every_block_shape_of_k_inc_ybar():
+    """k_inc_ybar is launched with RO = AdjGeom::R of the batch width and MC = min(shk_mc(M), INC_MC) columns across the lanes: over
+    M = 1 .. 256 that is eight (RO, MC) pairs, and R.GEOM_M reaches every one. (8, 8) — M = 5 and 7 alone — is why GEOM_M holds a 5
+    that the shock suite's list does not: k_shk_bbar's MC goes on to 64, so its pairs are others. If the rule moves, move GEOM_M."""
+    import re
+    from pathlib import Path
+    csrc = Path(__file__).resolve().parent.parent / "julia-newtonraphsonhank_amd" / "csrc"
+    host, inc = (csrc / "hank_hip.hip").read_text(), (csrc / "hank_income.h").read_text()
+    assert "static int shk_mc(int M) { int mc = 1; while (mc < M && mc < 64) mc <<= 1; return mc; }" in host, "shk_mc has moved: move cases.shk_mc"
+    inc_mc = int(re.search(r"constexpr int INC_BT = 1024, INC_MC = (\d+);", inc).group(1))
+    assert inc_mc == 32 and "IMC = std::min(MC, INC_MC)" in host and "inc_ybar_lds(c, w.g.R, IMC)" in host
+    assert int(re.search(r"constexpr int INC_NE = (\d+);", inc).group(1)) == 16
+    pair = lambda M: (cases.adj_rows_per_block(M), min(cases.shk_mc(M), inc_mc))       # noqa: E731
+    every = {pair(M) for M in range(1, 257)}
+    assert every == {(64, 1), (64, 2), (16, 4), (32, 4), (8, 8), (16, 8), (8, 16), (8, 32)}, sorted(every)
+    assert {pair(M) for M in R.GEOM_M} == every, sorted(every - {pair(M) for M in R.GEOM_M})
+    assert {M for M in range(1, 257) if pair(M) == (8, 8)} == {5, 7}
+    # the tails section A names: a full and a partial last column block (blockIdx.y > 0), column 70 in blockIdx.y = 2
+    assert [(-(-M // 32), M % 32) for M in (65, 66, 97, 130, 256)] == [(3, 1), (3, 2), (4, 1), (5, 2), (8, 0)] and 70 // 32 == 2
+    # ... and the row counts: a multiple of every RO but 64's neighbours, one off it on either side, several blocks
+    assert all(64 % ro == 0 for ro, _ in every) and [129 % ro for ro in (64, 32, 16, 8)] == [1, 1, 1, 1]
+    # the seed's staging limit at the bound on n_e (section B) and at the 11 states of tests/test_gpu_income.py
+    lds = lambda n_e, N: 8 * (n_e * n_e + 2 * n_e * N)                                  # noqa: E731
+    assert "const size_t b = sizeof(double) * ((size_t)c.n_e * c.n_e + 2 * (size_t)c.n_e * N);" in host and "return b <= 48 * 1024 ? b : 0;" in host
+    assert lds(16, 184) <= 48 * 1024 < lds(16, 185) and lds(11, 273) <= 48 * 1024 < lds(11, 274)
 
 
 def test_redistribution_is_zero_sum_and_a_transfer_reaches_its_states_alone(hank):
