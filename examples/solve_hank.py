@@ -17,6 +17,12 @@ response to a monetary-policy shock.
         (SteadyStateJacobian.income_jacobian); with --groups each productivity state's savings response (group outputs on the
         policy base), nonlinear beside linear; with --gradient the gradient of ½‖F‖² with respect to the path
         from one hank_vjp_income, beside a central difference in two of its entries
+    python examples/solve_hank.py --credit-crunch 0.01 0.8 [--groups] [--gradient]
+        a credit crunch: the borrowing limit follows amin_t = amin + SIZE RHO^t (HouseholdBlock.set_borrow_path) at a steady state
+        whose limit lies INSIDE the wealth grid — with the limit on the first grid point the grid's flat extrapolation binds instead
+        and every derivative in the limit is an exact zero; the nonlinear transition beside the linear response -J̅⁻¹ J_amin damin
+        (SteadyStateJacobian.borrow_jacobian); with --groups the consumption of the constrained households and of the top half of
+        the grid; with --gradient the gradient of ½‖F‖² with respect to the path from one hank_vjp_borrow, beside a central difference
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/solve_hank.py
         one process per GPU (RCCL): the unit-tangent chunks of the Jacobian assembly are shared out over the ranks and
         all-gathered; the Newton iteration itself (one tangent per inner step) runs replicated on every rank."""
@@ -314,6 +320,103 @@ def redistribute_gradient(n_a=1000, n_e=7, T=500, size=0.01, rho=0.8, upto=2, sp
             "y_bar": {f"{e},{t}": float(g[e, t]) for e, t in fd}, "central_difference": {f"{e},{t}": float(v) for (e, t), v in fd.items()}}
 
 
+def _crunch_setup(n_a, n_e, T, size, rho, spec):
+    """the model with its borrowing limit moved INSIDE the wealth grid — the middle of the last bracket below 0.05, at least three
+    grid points under it — and the steady state solved at that limit. With the limit on the first grid point, as the specs have it,
+    the grid's flat extrapolation binds instead of the limit and every derivative in the limit is an exact zero
+    (HouseholdBlock.set_borrow_path): a wealth grid that is to show a credit crunch carries points below the limit."""
+    import hank_amd as h
+    import hank_amd.parallel  # noqa: F401
+    from hank_amd import OneAssetHANK as oa
+    ov = {"T": T, "dimensions": {"wealth": {"n": n_a}, "productivity": {"n": n_e}}}
+    m = h.build_model_from_yaml(str(ROOT / "examples" / spec), overrides=ov)
+    a = np.asarray(m.heterogeneity["wealth"].grid)
+    k = max(int(np.searchsorted(a, 0.05)), 3)
+    m.params.borrow_cons = float(0.5 * (a[k - 1] + a[k]))
+    m.params.B = oa.calibrate_bond_supply(m)
+    if hasattr(m.params, "vφ"):
+        m.params.vφ = oa.calibrate_disutility(m)
+    ss, _ = h.get_SteadyStates(m)
+    P = T - 1
+    keys = h.vars_of_type(m, "endogenous")
+    x0 = np.tile(np.array([ss.vars[k_] for k_ in keys]), P)
+    damin = size * rho ** np.arange(P)
+    return h, m, ss, keys, x0, {"ei": np.zeros(P)}, damin, a, k
+
+
+def credit_crunch(n_a=1000, n_e=7, T=500, size=0.01, rho=0.8, eps=1e-9, spec="one_asset_hank.yaml", groups=False):
+    """The transition under amin_t = amin + size rho^t, no other shock (a tightening that fades): Newton on the nonlinear system
+    with the path set on the household block, beside the first-order response dx = -J̅⁻¹ (∂F/∂amin) damin with ∂F/∂amin assembled
+    from `borrow_jacobian` (hank_fake_news_borrow: one backward tangent sweep seeded at the last period). With `groups` the
+    consumption of the households at or below the tightest limit and of the top half of the wealth grid, nonlinear beside linear."""
+    h, m, ss, keys, x0, exog, damin, a, k = _crunch_setup(n_a, n_e, T, size, rho, spec)
+    from hank_amd.SteadyStateJacobian import borrow_jacobian
+    P = T - 1
+    bc = m.params.borrow_cons
+    J = h.getSteadyStateJacobian(ss, m)                      # the steady-state J̅, taken before the path is set
+    lin0 = h.LinearizedFunction(x0, exog, m, ss, ss)
+    hb = lin0.hb
+    Ja = borrow_jacobian(hb, lin0._n_out)                    # (outputs, P, P) at the stationary record lin0 holds
+    dx_lin = -np.linalg.solve(np.asarray(J), lin0.residual_borrow_jacobian(Ja) @ damin)
+    if groups:
+        W = np.zeros((n_a, n_e, 2))
+        W[a <= bc + size, :, 0] = 1.0
+        W[n_a // 2:, :, 1] = 1.0
+        hb.set_group_outputs(W.reshape((n_a * n_e, 2), order="F"), np.full(2, hb.GROUP_CONS, dtype=np.int32))
+        lin0._record_primal()
+        grp0, _ = hb.group_outputs()
+    t0 = time.perf_counter()
+    x = h.NewtonRaphsonHANK(x0, J, exog, m, ss, ss, ε=eps, borrow_path=bc + damin)
+    t_newton = time.perf_counter() - t0
+    lin = h.LinearizedFunction(x, exog, m, ss, ss, borrow_path=bc + damin)
+    dX, dL = (x - x0).reshape(len(keys), P, order="F"), dx_lin.reshape(len(keys), P, order="F")
+    show = [k_ for k_ in ("Y", "y", "r") if k_ in keys][:2] or list(keys[:2])
+    out = {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "steady_state_limit": float(bc), "grid_points_below_it": int(k),
+           "shock": f"amin_t = amin + {size}*{rho}^t",
+           "newton_s": round(t_newton, 3), "newton_iterations": h.NewtonRaphsonHANK.iterations, "residual_norm": float(np.linalg.norm(lin.Fx)),
+           "deviation_nonlinear": {k_: [float(v) for v in dX[keys.index(k_), :4]] for k_ in show},
+           "deviation_linear": {k_: [float(v) for v in dL[keys.index(k_), :4]] for k_ in show},
+           "max_abs_difference_over_max": float(np.max(np.abs(dX - dL)) / np.max(np.abs(dX)))}
+    if groups:
+        grp, _ = hb.group_outputs()                          # the record is lin's: the converged path under the limit's path
+        from hank_amd.BackwardIteration import household_inputs
+        from hank_amd.dual import Dual
+        _, dxhh = household_inputs(Dual.seed(x0, dx_lin[:, None]), exog, m)
+        dxhh = np.asarray(dxhh, dtype=np.float64).reshape(hb.n_hh, P, 1)
+        lin0._record_primal()                                # back to the stationary record, without a path
+        hb.jvp_borrow(dxhh, damin[:, None])
+        _, dgrp = hb.group_outputs(dxhh)
+        for j, name in enumerate(("constrained", "top_half")):
+            out[f"consumption_{name}_nonlinear"] = [float(v) for v in (grp - grp0)[:4, j]]
+            out[f"consumption_{name}_linear"] = [float(v) for v in dgrp[:4, j, 0]]
+    return out
+
+
+def credit_gradient(n_a=1000, n_e=7, T=500, size=0.01, rho=0.8, spec="one_asset_hank.yaml", step=1e-6):
+    """The gradient of ½‖F(x0)‖² with respect to the borrowing-limit path at the Newton starting point (the steady state repeated,
+    where F ≠ 0 under the path): ONE `LinearizedFunction.vjp_borrow` (hank_vjp_borrow), beside a central difference in the first and
+    the last entry of the path."""
+    h, m, ss, keys, x0, exog, damin, a, k = _crunch_setup(n_a, n_e, T, size, rho, spec)
+    path = m.params.borrow_cons + damin
+    lin = h.LinearizedFunction(x0, exog, m, ss, ss, borrow_path=path)
+    lin.vjp_borrow(lin.Fx)                                    # warm-up: workspace, graphs, the residual layer's linearisation
+    t0 = time.perf_counter()
+    g = lin.vjp_borrow(lin.Fx)
+    t_rev = time.perf_counter() - t0
+    fd = {}
+    for t in (0, T - 2):
+        f = []
+        for sgn in (1.0, -1.0):
+            p = path.copy()
+            p[t] += sgn * step
+            F = h.LinearizedFunction(x0, exog, m, ss, ss, borrow_path=p).Fx
+            f.append(0.5 * float(F @ F))
+        fd[t] = (f[0] - f[1]) / (2 * step)
+    return {"model": "one-asset HANK", "spec": spec, "grid": f"{n_a}x{n_e}", "T": T, "merit": 0.5 * float(lin.Fx @ lin.Fx),
+            "gradient_norm": float(np.linalg.norm(g)), "reverse_s": round(t_rev, 5), "reverse_vjps": 1,
+            "amin_bar": {str(t): float(g[t]) for t in fd}, "central_difference": {str(t): float(v) for t, v in fd.items()}}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-a", type=int, default=1000)
@@ -332,6 +435,8 @@ def parse_args(argv=None):
                     help="a path of the discount factor, beta_t = beta (1 + SIZE RHO^t), instead of the monetary shock: the nonlinear transition beside the linear response; with --gradient the path's gradient of ½‖F‖²")
     ap.add_argument("--redistribute", type=float, nargs=3, metavar=("SIZE", "RHO", "E"), default=None,
                     help="a budget-neutral transfer SIZE RHO^t to the productivity states <= E (an income path by state) instead of the monetary shock: the nonlinear transition beside the linear response; with --gradient the path's gradient of ½‖F‖²")
+    ap.add_argument("--credit-crunch", type=float, nargs=2, metavar=("SIZE", "RHO"), default=None,
+                    help="a path of the borrowing limit, amin_t = amin + SIZE RHO^t, instead of the monetary shock, at a steady state whose limit lies inside the wealth grid (with the limit on the first grid point every derivative in it is zero): the nonlinear transition beside the linear response; with --groups the constrained households' and the top half's consumption; with --gradient the path's gradient of ½‖F‖²")
     ap.add_argument("--groups", action="store_true", help="with --redistribute: the savings response of every productivity state (group outputs on the policy base)")
     return ap.parse_args(argv)
 
@@ -341,6 +446,12 @@ if __name__ == "__main__":
     if a.discount_shock is not None:
         fn = discount_gradient if a.gradient else discount_shock
         print(json.dumps(fn(a.n_a, a.n_e, a.T, a.discount_shock[0], a.discount_shock[1], spec=a.spec)))
+        sys.exit(0)
+    if a.credit_crunch is not None:
+        if a.gradient:
+            print(json.dumps(credit_gradient(a.n_a, a.n_e, a.T, a.credit_crunch[0], a.credit_crunch[1], spec=a.spec)))
+        else:
+            print(json.dumps(credit_crunch(a.n_a, a.n_e, a.T, a.credit_crunch[0], a.credit_crunch[1], spec=a.spec, groups=a.groups)))
         sys.exit(0)
     if a.redistribute is not None:
         size, rho, upto = a.redistribute[0], a.redistribute[1], int(a.redistribute[2])

@@ -542,6 +542,9 @@ int hank_vjp_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, i
  *   F_out (P, P, n_e, n_het), Dv_out (P, n_e, n_het); consumption's Dv carries the direct term m_ss[e] at lag 0, output 0 none. */
 int hank_fake_news_income(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out);
 
+/* A path of the borrowing limit (the credit crunch) is declared in a header of its own, include/hank_hip_borrow.h, which includes
+ * this one: the entries of this header stay what every binding of it counts on. */
+
 /* ---- derivatives through the steady state ------------------------------------------------------------
  * Two of the block's three inputs are steady-state objects: V_T is the fixed point of the EGM step at the steady-state prices
  * (the inner loop of get_xVals, SteadyState.jl:132-141) and D_0 the stationary distribution of the lottery that step induces

@@ -42,17 +42,22 @@ class LinearizedFunction:
     het_in_sweep = False                # True: a model that reads Value / UCE (device outputs >= 2) takes every output's tangent from ONE
                                         # hank_jvp_het instead of hank_jvp + hank_get_het_outputs; the two differ by the rounding of sums
 
-    def __init__(self, x, exog_paths, mod: SequenceModel, ss_initial, ss_ending, discount_path=None, income_path=None):
+    def __init__(self, x, exog_paths, mod: SequenceModel, ss_initial, ss_ending, discount_path=None, income_path=None, borrow_path=None):
         """discount_path: beta_t (P,), the discount factor of period t's Euler equation (HouseholdBlock.set_discount_path; not in the
         reference, which reads beta from the model's parameters); None: the model's constant. The path is set on the model's
         context before the primal is recorded, and restored with the record when another user of the context changed it.
         income_path: y (n_e, P), additive income by productivity state (HouseholdBlock.set_income_path; not in the reference either),
-        handled in the same way; the two exclude each other, and a model that reads Value or UCE is not served at one."""
+        handled in the same way; a model that reads Value or UCE is not served at one.
+        borrow_path: amin_t (P,), the borrowing limit of period t's choice (HouseholdBlock.set_borrow_path; not in the reference, which
+        reads borrow_cons from the model's parameters), handled in the same way. The three exclude each other."""
         self.x = np.asarray(x, dtype=np.float64)
         self.discount_path = None if discount_path is None else np.ascontiguousarray(discount_path, dtype=np.float64)
         self.income_path = None if income_path is None else np.asfortranarray(income_path, dtype=np.float64)
+        self.borrow_path = None if borrow_path is None else np.ascontiguousarray(borrow_path, dtype=np.float64)
         if self.discount_path is not None and self.income_path is not None:
             raise ValueError("discount_path and income_path exclude each other")
+        if self.borrow_path is not None and (self.discount_path is not None or self.income_path is not None):
+            raise ValueError("borrow_path excludes discount_path and income_path")
         self.mod, self.exog_paths, self.ss_initial, self.ss_ending = mod, exog_paths, ss_initial, ss_ending
         self.hb = household_block(mod)
         xhh, _ = household_inputs(self.x, exog_paths, mod)
@@ -123,9 +128,9 @@ class LinearizedFunction:
         hb = self.hb
         hb.set_boundary(self.ss_ending.value, self.ss_initial.D)
         differs = lambda cur, want: (cur is None) != (want is None) or (want is not None and not np.array_equal(cur, want))
-        # (the context is shared: a linearisation without a path clears another's; the two paths exclude each other, so what has to
+        # (the context is shared: a linearisation without a path clears another's; the paths exclude each other, so what has to
         # go is cleared before what has to come is set)
-        paths = [("discount_path", self.discount_path), ("income_path", self.income_path)]
+        paths = [("discount_path", self.discount_path), ("income_path", self.income_path), ("borrow_path", self.borrow_path)]
         for name, want in sorted(paths, key=lambda q: q[1] is not None):
             if differs(getattr(hb, name, None), want):
                 getattr(hb, "set_" + name)(want)
@@ -312,6 +317,34 @@ class LinearizedFunction:
         _, bb = self.hb.vjp_shock(agg_bar, self._n_out)
         return bb[:, 0].copy() if single else bb
 
+    def jvp_borrow(self, damin):
+        """∂F/∂amin · damin at this x: the residuals' tangent under a direction damin (P,) or (P, N) of the borrowing-limit path, x
+        held fixed — `_Ragg` composed with ONE hank_jvp_borrow (+ hank_get_het_outputs: the limit has no direct term in any output)."""
+        da = np.asarray(damin, dtype=np.float64)
+        single = da.ndim == 1
+        da = da[:, None] if single else da
+        self._shock_ready()
+        hb = self.hb
+        d0 = hb.jvp_borrow(None, da)
+        daggs = d0[:, None, :] if self._n_out == 1 else hb.het_outputs(self._n_out, np.zeros((hb.n_hh, hb.P, da.shape[1])))[1]
+        out = self._Ragg @ np.concatenate([daggs[:, j, :] for j in self._out_idx], axis=0)
+        return out[:, 0].copy() if single else out
+
+    def vjp_borrow(self, ȳ):
+        """the transpose of `jvp_borrow`: ȳ (n,) or (n, M) -> amin_bar (P,) or (P, M), the gradient of ȳ·F with respect to the
+        borrowing-limit path, from ONE hank_vjp_borrow."""
+        ȳ = np.asarray(ȳ, dtype=np.float64)
+        single = ȳ.ndim == 1
+        Yb = ȳ[:, None] if single else ȳ
+        self._shock_ready()
+        P, M = self.mod.compspec.T - 1, Yb.shape[1]
+        ab = np.asarray(self._Ragg.T @ Yb).reshape(len(self.het), P, M)
+        agg_bar = np.zeros((P, self._n_out, M))
+        for j, o in enumerate(self._out_idx):
+            agg_bar[:, o, :] += ab[j]
+        _, bb = self.hb.vjp_borrow(agg_bar, self._n_out)
+        return bb[:, 0].copy() if single else bb
+
     def jvp_income(self, dy):
         """∂F/∂y · dy at this x: the residuals' tangent under a direction dy (n_e, P) or (n_e, P, N) of the income path, x held fixed
         — `_Ragg` composed with ONE hank_jvp_income and hank_get_het_outputs_income (y has a direct term in consumption)."""
@@ -357,6 +390,11 @@ class LinearizedFunction:
         if self._Rx is None:
             self._linearise_residuals()
         return np.asarray(self._Ragg @ np.concatenate([np.asarray(J_beta)[j] for j in self._out_idx], axis=0))
+
+    def residual_borrow_jacobian(self, J_amin):
+        """∂F/∂amin (n, P) from the household block's J_amin (n_out, P, P) of `SteadyStateJacobian.borrow_jacobian`: `_Ragg` composed
+        with the rows of the heterogeneous variables the equations read."""
+        return self.residual_shock_jacobian(J_amin)
 
     def as_linear_operator(self):
         """J(x) as a scipy.sparse.linalg.LinearOperator with both products: matvec / matmat = `jvp`, rmatvec / rmatmat = `vjp`
@@ -461,14 +499,14 @@ def _device_inverse_solver(J, device=None):
 @host_algebra
 def y_Iteration(J̅, x, y0, exog_paths, mod: SequenceModel, ss_initial, ss_ending, *, precond=None,
                 α: float | None = None, γ: float = 1.5, ε: float = 1e-9, verbose: bool = False, max_inner: int = 10_000,
-                linear_solver: str = "auto", inner: str = "fixed_point", discount_path=None, income_path=None):
+                linear_solver: str = "auto", inner: str = "fixed_point", discount_path=None, income_path=None, borrow_path=None):
     """inner iteration for the search direction y with J(x)·y = F(x) (NewtonRaphson.jl:65-114).
 
     inner="fixed_point" (default, the reference): y ← y + α·J̅⁻¹(F(x) − J(x)·y). The reference accepts α (:72) and
     overrides it with 0.5 (:102): `α=None` is that; a value passed here is honoured (α = 1 is the undamped iteration).
     inner="krylov" (opt-in, not in the reference): GMRES on J(x) with J̅⁻¹ as right preconditioner — the same fixed point
     (the exact Newton step) in a handful of JVPs instead of the ≈ 21 that α = 0.5 needs to contract 1e-9 by halves."""
-    lin = LinearizedFunction(x, exog_paths, mod, ss_initial, ss_ending, discount_path=discount_path, income_path=income_path)
+    lin = LinearizedFunction(x, exog_paths, mod, ss_initial, ss_ending, discount_path=discount_path, income_path=income_path, borrow_path=borrow_path)
     y_Iteration.last_Fx = lin.Fx            # F(x) of this linearisation: the step rule's ‖F(x)‖ (NewtonRaphsonHANK, step="backtrack")
     y = np.asarray(y0, dtype=np.float64)
     n = len(y)
@@ -590,7 +628,7 @@ def residuals_batch(xs, exog_paths, mod: SequenceModel, ss_initial, ss_ending):
 @host_algebra
 def NewtonRaphsonHANK(x_0, J̅, exog_paths, mod: SequenceModel, ss_initial, ss_ending, *, ε: float = 1e-9,
                       verbose: bool = False, linear_solver: str = "auto", inner: str = "fixed_point", α: float | None = None,
-                      step: str = "full", n_trial: int = 6, c1: float = 1e-4, discount_path=None, income_path=None):
+                      step: str = "full", n_trial: int = 6, c1: float = 1e-4, discount_path=None, income_path=None, borrow_path=None):
     """outer Newton loop (NewtonRaphson.jl:27-46): x ← x − y until ‖y‖ ≤ ε or 100 iterations. `inner` / `α`: see y_Iteration
     (defaults = the reference's damped fixed point).
 
@@ -602,11 +640,14 @@ def NewtonRaphsonHANK(x_0, J̅, exog_paths, mod: SequenceModel, ss_initial, ss_e
 
     discount_path: beta_t (P,) (`LinearizedFunction`): the transition under a path of the discount factor. J̅ is still the
     steady-state Jacobian: take it before the path is set, or on a clone of the context without one.
-    income_path: y (n_e, P) (`LinearizedFunction`): the transition under a path of income by productivity state, under the same rules."""
+    income_path: y (n_e, P) (`LinearizedFunction`): the transition under a path of income by productivity state, under the same rules.
+    borrow_path: amin_t (P,) (`LinearizedFunction`): the transition under a path of the borrowing limit, under the same rules."""
     if step not in ("full", "backtrack"):
         raise ValueError(f"unknown step rule {step!r} (full | backtrack)")
     if income_path is not None and step == "backtrack":
         raise ValueError("step='backtrack' evaluates its trials with hank_primal_batch, which is defined at one income process: use step='full' with an income_path")
+    if borrow_path is not None and step == "backtrack":
+        raise ValueError("step='backtrack' evaluates its trials with hank_primal_batch, which is defined at one borrowing limit: use step='full' with a borrow_path")
     if discount_path is not None and step == "backtrack":
         raise ValueError("step='backtrack' evaluates its trials with hank_primal_batch, which is defined at one discount factor: use step='full' with a discount_path")
     x = np.asarray(x_0, dtype=np.float64)
@@ -616,7 +657,7 @@ def NewtonRaphsonHANK(x_0, J̅, exog_paths, mod: SequenceModel, ss_initial, ss_e
     try:
         while ε < np.linalg.norm(y) and i < 100:
             y = y_Iteration(J̅, x, y, exog_paths, mod, ss_initial, ss_ending, verbose=verbose, linear_solver=linear_solver, inner=inner, α=α,
-                            discount_path=discount_path, income_path=income_path)
+                            discount_path=discount_path, income_path=income_path, borrow_path=borrow_path)
             if step == "full":
                 x = x - y
             elif not ε < np.linalg.norm(y):         # a step below the tolerance ends the loop: taken whole, as the reference takes it

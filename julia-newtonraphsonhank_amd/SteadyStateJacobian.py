@@ -58,6 +58,15 @@ def shock_jacobian(block, n_het):
     return np.stack([household_jacobian(F[..., o:o + 1], Dv[..., o:o + 1])[0] for o in range(F.shape[2])])
 
 
+def borrow_jacobian(block, n_het):
+    """d Y^o_t / d amin_s at the steady state for the first n_het heterogeneous outputs, amin_s the borrowing limit of period s's
+    choice (HouseholdBlock.set_borrow_path): `block.fake_news_borrow(n_het)`'s F (P, P, n_het) and Dv (P, n_het) through the
+    recursion of `household_jacobian`, once per output. `block` holds the stationary primal and no path; its grid carries points
+    below the limit, or the result is zero (the kink convention of `set_borrow_path`). Returns J_amin (n_het, P, P): J[o, t, s]."""
+    F, Dv = block.fake_news_borrow(n_het)
+    return np.stack([household_jacobian(F[..., o:o + 1], Dv[..., o:o + 1])[0] for o in range(F.shape[2])])
+
+
 def income_jacobian(block, n_het):
     """d Y^o_t / d y_s[e] at the steady state for the first n_het (1 or 2) heterogeneous outputs, y_s[e] the additive income of
     productivity state e in period s (HouseholdBlock.set_income_path): `block.fake_news_income(n_het)`'s F (P, P, n_e, n_het) and Dv

@@ -18,7 +18,7 @@ from .BackwardIteration import BackwardIteration, household_block
 from .ForwardIteration import ForwardIteration, make_endogenous_transition, transition_step
 from .SteadyState import SSAssembler, SteadyState, find_ss, get_SteadyStates
 from .NewtonRaphson import LinearizedFunction, NewtonRaphsonHANK, StepRuleError, backtrack, make_fullFunction, residuals_batch, y_Iteration
-from .SteadyStateJacobian import getSteadyStateJacobian, group_jacobian, income_jacobian, shock_jacobian
+from .SteadyStateJacobian import borrow_jacobian, getSteadyStateJacobian, group_jacobian, income_jacobian, shock_jacobian
 from . import groups
 from . import incidence
 from .hip import HouseholdBlock, HankHIPError, KnotsNotSortedError, DomainError, NoDeviceError

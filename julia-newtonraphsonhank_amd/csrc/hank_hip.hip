@@ -16,8 +16,10 @@
 #include "hank_boundary.h"
 #include "hank_shock.h"
 #include "hank_income.h"
+#include "hank_borrow.h"
 #include "hank_ssdiff_launch.h"
 #include "../../include/hank_hip.h"
+#include "../../include/hank_hip_borrow.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -80,11 +82,11 @@ static inline int tan_lane_width(int N, int forward) {
     return (want == 2 && N % 2 == 0) ? 2 : 1;
 }
 
-// Which exogenous path the household block runs under: the discount factors beta_t (hank_shock.h) or income by
-// productivity state y_t[e] (hank_income.h). What differs between the kinds on the host is stated HERE, once; everything below indexes
+// Which exogenous path the household block runs under: the discount factors beta_t (hank_shock.h), income by
+// productivity state y_t[e] (hank_income.h) or the borrowing limit amin_t (hank_borrow.h). What differs between the kinds on the host is stated HERE, once; everything below indexes
 // by kind. The context owns the path in force (hank_ctx::path, set_path); the kinds exclude each other.
-enum PathKind { PATH_NONE, PATH_DISCOUNT, PATH_INCOME };
-constexpr int N_PATH_KINDS = 3;
+enum PathKind { PATH_NONE, PATH_DISCOUNT, PATH_INCOME, PATH_BORROW };
+constexpr int N_PATH_KINDS = 4;
 struct hank_ctx;
 typedef int (*VjpRule)(hank_ctx *, int, const void *, int, const void *);
 static int vjp_args(hank_ctx *ctx, int n_het, const void *in, int M, const void *out);
@@ -94,22 +96,24 @@ struct PathTraits {
     const char *set, *jvp, *vjp, *fn;       // its entries, as the messages name them (set: also the clearing hint, `set(ctx, NULL) clears it`)
     const char *dir, *bar;                  // its directions and its cotangent among their arguments
     const char *refusal;                    // what an entry that is not served at a path of this kind says of itself (refuses_at)
-    PathKind excluded_by;                   // the kind under which its jvp / vjp entries refuse (path_entry_excluded); PATH_NONE: neither
+    unsigned excluded_under;                // the kinds (one bit each, 1u << kind) under whose path its jvp / vjp entries refuse (path_entry_excluded)
     VjpRule vjp_rule;                       // the argument rule of its vjp entry
 };
 static const PathTraits PATHS[N_PATH_KINDS] = {
-    {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, PATH_NONE, nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr},
     {"a discount-factor path", "hank_set_discount_path", "hank_jvp_shock", "hank_vjp_shock", "hank_fake_news_shock", "dbeta", "beta_bar",
-     "is defined at one discount factor", PATH_NONE, vjp_het_args},
+     "is defined at one discount factor", 1u << PATH_BORROW, vjp_het_args},
     {"an income path", "hank_set_income_path", "hank_jvp_income", "hank_vjp_income", "hank_fake_news_income", "dy", "y_bar",
-     "is not served at an income path", PATH_DISCOUNT, vjp_args},
+     "is not served at an income path", (1u << PATH_DISCOUNT) | (1u << PATH_BORROW), vjp_args},
+    {"a borrowing-limit path", "hank_set_borrow_path", "hank_jvp_borrow", "hank_vjp_borrow", "hank_fake_news_borrow", "damin", "amin_bar",
+     "is defined at one borrowing limit", (1u << PATH_DISCOUNT) | (1u << PATH_INCOME), vjp_het_args},
 };
-// values per period (beta_t: 1; y_t[e]: n_e), and the value of every period without a path (the model's beta; zero)
+// values per period (beta_t, amin_t: 1; y_t[e]: n_e), and the value of every period without a path (the model's beta; zero; the model's limit)
 static int path_width(const Consts &c, PathKind k) { return k == PATH_INCOME ? c.n_e : 1; }
-static double path_neutral(const Consts &c, PathKind k) { return k == PATH_DISCOUNT ? c.beta : 0.0; }
+static double path_neutral(const Consts &c, PathKind k) { return k == PATH_DISCOUNT ? c.beta : k == PATH_BORROW ? c.bc : 0.0; }
 
 // a kind's share of a tangent workspace, allocated on its first use at this width (ensure_path_tan_graph): the caller's directions as they
-// come — dbeta (P, N), dy (n_e, P, N), column-major (staging) — the same as [P][N] / [P][n_e][N] (k_shk_in, k_inc_in), and the backward
+// come — dbeta (P, N), dy (n_e, P, N), damin (P, N), column-major (staging) — the same as [P][N] / [P][n_e][N] (k_shk_in, k_inc_in), and the backward
 // sweep with the seed of every period between its launches
 struct PathSeed { DevBuf<double> in, dir; GraphExec g_tback; };
 
@@ -200,7 +204,7 @@ struct WTan {
 // ---- transposed sweeps (hank_adjoint.h): hank_vjp's workspace per batch width M (its own: no TanWork's dpol is reused, so the
 // current tangent batch stays current and its readers keep serving it) ----
 // a kind's share of it: g_B is Sweep B — for a path kind with the path cotangent's partials behind every period's launch (k_shk_bbar,
-// k_inc_ybar) and their reduction at the end, captured on its first use at this width with the buffers: the partials [P][nb][width][M],
+// k_inc_ybar, k_brw_abar) and their reduction at the end, captured on its first use at this width with the buffers: the partials [P][nb][width][M],
 // their sums [P][width][M] and the caller's layout (width, P, M) column-major (width: 1 for beta_bar, n_e for y_bar).
 // [PATH_NONE]: hank_vjp's plain Sweep B, captured with Sweep A, and no buffers.
 struct PathCot { DevBuf<double> part, rm, cm; GraphExec g_B; };
@@ -396,6 +400,7 @@ struct hank_ctx {
     ScenWork scen;                 // hank_primal_batch's workspace
     int scen_pending = 0;          // scenarios of a hank_primal_batch_dev whose verdict hank_check has not taken yet
     std::vector<double> h_Pi, h_z;  // host copies (the wide sweeps take the mixing matrix as a kernel argument)
+    double a_top = 0.0;             // a_grid[n_a-1]: the bound on a borrowing-limit path's values (path_values_ok)
     long long stats[N_STATS] = {};   // see Stat and hank_stats
     // primal memo of the host-pointer hank_primal_jvp (NewtonRaphson.jl:91-95 calls JVP(fullFunction, x, y) ~21 times at one x):
     // the x whose linearisation is on record, as the host handed it in
@@ -545,7 +550,8 @@ static void zero_err(hank_ctx *ctx, hipStream_t s) { hipLaunchKernelGGL(k_zero_i
 
 // The backward primal graph of one path kind, the chain written ONCE: the error word cleared, X of the last period from the terminal
 // value, then P fused Y;X steps, then the lottery. Only the two EGM launches differ by kind: PATH_NONE the model's own; PATH_DISCOUNT
-// (hank_shock.h) beta_t' from the kind's values in the X half of period t'; PATH_INCOME (hank_income.h) y_t[e] in both halves.
+// (hank_shock.h) beta_t' from the kind's values in the X half of period t'; PATH_INCOME (hank_income.h) y_t[e] in both halves;
+// PATH_BORROW (hank_borrow.h) amin_t in the Y half of period t.
 static int capture_primal_back(hank_ctx *ctx, PathKind kind) {
     const Consts &c = ctx->c;
     const int P = c.P;
@@ -560,12 +566,14 @@ static int capture_primal_back(hank_ctx *ctx, PathKind kind) {
     case PATH_NONE: hipLaunchKernelGGL(k_egm_X, grd, blk, lds, s, c, ctx->d_ss_value, x_last, s_last, kc_last, ctx->d_err, P - 1, (const int *)nullptr); break;
     case PATH_DISCOUNT: hipLaunchKernelGGL(k_shk_egm_X, grd, blk, lds, s, c, v, ctx->d_ss_value, x_last, s_last, kc_last, ctx->d_err, P - 1); break;
     case PATH_INCOME: hipLaunchKernelGGL(k_inc_egm_X, grd, blk, lds, s, c, v, ctx->d_ss_value, x_last, s_last, kc_last, ctx->d_err, P - 1); break;
+    case PATH_BORROW: hipLaunchKernelGGL(k_egm_X, grd, blk, lds, s, c, ctx->d_ss_value, x_last, s_last, kc_last, ctx->d_err, P - 1, (const int *)nullptr); break;      // (no bc in the X half)
     }
     for (int t = P - 1; t >= 0; t--)
         switch (kind) {
         case PATH_NONE: hipLaunchKernelGGL(k_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, t, ctx->d_err); break;
         case PATH_DISCOUNT: hipLaunchKernelGGL(k_shk_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, v, t, ctx->d_err); break;
         case PATH_INCOME: hipLaunchKernelGGL(k_inc_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, v, t, ctx->d_err); break;
+        case PATH_BORROW: hipLaunchKernelGGL(k_brw_egm_step, grd, blk, lds, s, c, ctx->R, ctx->d_xhh, v, t, ctx->d_err); break;
         }
     hipLaunchKernelGGL(k_lottery, dim3(P * c.n_e), dim3(256), sizeof(int) * (2 * (size_t)c.n_a + 2), s, c, ctx->R, P * c.n_e, ctx->d_err, 1, 1);
     return end_capture(ctx, &ctx->exo[kind].g_pback);
@@ -626,7 +634,12 @@ static dim3 bnd_grid(const Consts &c, int N) { return dim3((unsigned)((c.n_a + B
 
 // the backward tangent sweep; bnd: with the dV_P seed (hank_boundary.h: the same launches of the same kernel, the seed kernels between them)
 // kind (never with bnd): a path kind's seed of EVERY period — d beta_t (hank_shock.h), d y_t[e] (hank_income.h) — behind the launch that produced
-// that period's knots' tangent — P launches more, and the kind's layout kernel in front; w.seed[kind]'s buffers are allocated before this
+// that period's knots' tangent — P launches more, and the kind's layout kernel in front; w.seed[kind]'s buffers are allocated before this.
+// d amin_t (hank_borrow.h) is seeded behind the launch that wrote dpol_t — the P launches of the loop — and touches dpol_t and ds_{t-1}.
+static size_t brw_seed_lds(const Consts &c, int N) {      // k_brw_seed_back's staging, or 0 where it does not fit (it reads global memory then)
+    const size_t b = sizeof(double) * ((size_t)c.n_e * c.n_e + (size_t)N);
+    return b <= 48 * 1024 ? b : 0;
+}
 static size_t inc_seed_lds(const Consts &c, int N) {      // k_inc_seed_back's staging, or 0 where it does not fit (it reads global memory then)
     const size_t b = sizeof(double) * ((size_t)c.n_e * c.n_e + 2 * (size_t)c.n_e * N);
     return b <= 48 * 1024 ? b : 0;
@@ -646,10 +659,15 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, PathKind kind =
     hipLaunchKernelGGL(k_tan_in, dim3((PN + 255) / 256), dim3(256), 0, s, w.dxhh, c.n_hh, (int)P, N, w.dxr, w.dxw, w.dxt);
     PathSeed &ps = w.seed[kind];
     const bool seeded = kind != PATH_NONE;
-    if (kind == PATH_DISCOUNT) hipLaunchKernelGGL(k_shk_in, dim3((PN + 255) / 256), dim3(256), 0, s, ps.in.get(), (int)P, N, ps.dir.get());
+    if (kind == PATH_DISCOUNT || kind == PATH_BORROW) hipLaunchKernelGGL(k_shk_in, dim3((PN + 255) / 256), dim3(256), 0, s, ps.in.get(), (int)P, N, ps.dir.get());
     if (kind == PATH_INCOME) hipLaunchKernelGGL(k_inc_in, dim3((unsigned)(((size_t)PN * c.n_e + 255) / 256)), dim3(256), 0, s, ps.in.get(), c.n_e, (int)P, N, ps.dir.get());
     const dim3 sgrd((unsigned)(((size_t)c.n_a * N + 255) / 256));
-    const size_t ilds = inc_seed_lds(c, N), eN = (size_t)c.n_e * N;
+    const size_t ilds = inc_seed_lds(c, N), eN = (size_t)c.n_e * N, blds = brw_seed_lds(c, N);
+    const bool brw = kind == PATH_BORROW;
+    auto seed_brw = [&](int t, double *ds_prev) {      // behind the launch that wrote dpol_t and ds_{t-1} (null at t = 0)
+        hipLaunchKernelGGL(k_brw_seed_back, sgrd, dim3(256), blds, s, c, ctx->R, ctx->exo[PATH_BORROW].d.get(), t, ps.dir.get() + (size_t)t * N, (size_t)N, blds ? 1 : 0,
+                           w.dpol.get() + (size_t)t * c.G * N, ds_prev);
+    };
     auto seed = [&](int t, double *ds_t) {      // ds_t: the knots' tangent of period t, as the launch before left it
         if (kind == PATH_INCOME)
             hipLaunchKernelGGL(k_inc_seed_back, sgrd, dim3(256), ilds, s, c, ctx->R, ctx->d_xhh.get(), t, ps.dir.get() + (size_t)t * eN,
@@ -659,7 +677,7 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, PathKind kind =
     };
     LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, (int)P - 1, 1,
                        ds[1], ds[0], dpol);
-    if (seeded) seed((int)P - 1, w.ds[0].get());
+    if (seeded && !brw) seed((int)P - 1, w.ds[0].get());
     if (bnd) {      // dV_P (BackwardIteration.jl:85) into the knots' tangent of period P-1; ds[1] is free until the next launch writes it
         hipLaunchKernelGGL(k_bnd_in, bnd_grid(c, N), dim3(BND_T, 8), 0, s, w.bnd_dV.get(), c.n_a, c.n_e, c.n_a, N, w.ds[1].get());
         hipLaunchKernelGGL(k_bnd_seed_back, dim3((unsigned)(((size_t)c.n_a * N + 255) / 256)), dim3(256), 0, s, c, ctx->R.kc + (P - 1) * c.G, w.ds[1].get(), (size_t)N, w.ds[0].get());
@@ -668,7 +686,8 @@ static int capture_tan_back(hank_ctx *ctx, TanWork &w, bool bnd, PathKind kind =
     for (int t = (int)P - 1; t >= 0; t--) {
         LAUNCH_RG(RGB, k_tan_back, VT, dim3(nbt, ny), blk, 0, s, c, ctx->R, ctx->d_xhh, dxr, dxw, dxt, w.g, t, 0,
                            ds[cur], ds[cur ^ 1], dpol);
-        if (seeded && t > 0) seed(t - 1, w.ds[cur ^ 1].get());
+        if (brw) seed_brw(t, t > 0 ? w.ds[cur ^ 1].get() : (double *)nullptr);
+        else if (seeded && t > 0) seed(t - 1, w.ds[cur ^ 1].get());
         cur ^= 1;
     }
     return end_capture(ctx, seeded ? &ps.g_tback : &w.tan_back(bnd));
@@ -1678,6 +1697,7 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     c.a = ctx->d_a; c.z = ctx->d_z; c.Pi = ctx->d_Pi;      // views
     ctx->h_Pi.assign(m->Pi, m->Pi + (size_t)c.n_e * c.n_e);
     ctx->h_z.assign(m->z_grid, m->z_grid + c.n_e);
+    ctx->a_top = m->a_grid[c.n_a - 1];
     ctx->lds_max = prop.sharedMemPerBlock;
     ctx->num_cus = std::max(1, prop.multiProcessorCount);
     Record &R = ctx->R;
@@ -1710,7 +1730,7 @@ int hank_create_on(const hank_model *m, int32_t device, hank_ctx **out) {
     ctx->d_ss_D = R.Dseq;      // view
     ctx->nbp = (c.n_a + RBP - 1) / RBP;
     HIPC(ctx, ctx->d_xhh.alloc((size_t)c.n_hh * P));
-    for (PathKind k : {PATH_DISCOUNT, PATH_INCOME}) {      // no path: the kind's neutral value in every period
+    for (PathKind k : {PATH_DISCOUNT, PATH_INCOME, PATH_BORROW}) {      // no path: the kind's neutral value in every period
         hank_ctx::ExoPath &e = ctx->exo[k];
         e.h.assign((size_t)P * path_width(c, k), path_neutral(c, k));
         HIPC(ctx, e.d.alloc(e.h.size()));
@@ -1849,6 +1869,9 @@ static int path_values_ok(hank_ctx *ctx, PathKind kind, const double *v) {
             return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_discount_path: beta_t must be finite and positive (period %zu: %g); the path in force is unchanged", k + 1, v[k]);
         if (kind == PATH_INCOME && !(v[k] >= -1.7976931348623157e308 && v[k] <= 1.7976931348623157e308))
             return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_income_path: y must be finite (state %zu, period %zu: %g); the path in force is unchanged", k % ne + 1, k / ne + 1, v[k]);
+        if (kind == PATH_BORROW && !(v[k] >= -1.7976931348623157e308 && v[k] <= ctx->a_top))
+            return fail(ctx, HANK_ERR_BAD_ARG, "hank_set_borrow_path: amin_t must be finite and at most a_grid[n_a-1] = %g (period %zu: %g); the path in force is unchanged", ctx->a_top,
+                        k + 1, v[k]);
     }
     return HANK_OK;
 }
@@ -1879,7 +1902,9 @@ static int set_path(hank_ctx *ctx, PathKind kind, const double *values) {
 }
 int hank_set_discount_path(hank_ctx *ctx, const double *beta_t) { return set_path(ctx, PATH_DISCOUNT, beta_t); }
 int hank_set_income_path(hank_ctx *ctx, const double *y) { return set_path(ctx, PATH_INCOME, y); }
-// a path of either kind: the sweeps run on the per-period launches
+// (hank_borrow.h; KrusellSmith.jl:52, :76 inside the same loop): amin_t [P]
+int hank_set_borrow_path(hank_ctx *ctx, const double *amin_t) { return set_path(ctx, PATH_BORROW, amin_t); }
+// a path of any kind: the sweeps run on the per-period launches
 static bool path_on(const hank_ctx *ctx) { return ctx->path != PATH_NONE; }
 // the income values in force as k_inc_cons takes them: null without an income path
 static const double *income_in_force(const hank_ctx *ctx) { return ctx->path == PATH_INCOME ? ctx->exo[PATH_INCOME].d.get() : nullptr; }
@@ -1893,13 +1918,17 @@ static int refuses_at(hank_ctx *ctx, PathKind kind, const char *name) {
 static int income_refuses(hank_ctx *ctx, const char *name) { return refuses_at(ctx, PATH_INCOME, name); }
 // the entries that are defined at ONE beta and ONE income process (the scenario and steady-state entries, the Toeplitz Jacobians) while a path is set
 static int path_refuses(hank_ctx *ctx, const char *name) {
-    const int rc = refuses_at(ctx, PATH_DISCOUNT, name);
-    return rc ? rc : refuses_at(ctx, PATH_INCOME, name);
+    for (PathKind k : {PATH_DISCOUNT, PATH_INCOME, PATH_BORROW}) {
+        const int rc = refuses_at(ctx, k, name);
+        if (rc) return rc;
+    }
+    return HANK_OK;
 }
-// a kind's own jvp / vjp entry (`who`) while the kind that excludes it is set: hank_jvp_income and hank_vjp_income under a discount-factor path
+// a kind's own jvp / vjp entry (`who`) while a kind that excludes it is set (PathTraits::excluded_under): hank_jvp_income under a discount-factor path,
+// every kind's under a borrowing-limit path and the limit's under either of theirs — one path at a time
 static int path_entry_excluded(hank_ctx *ctx, PathKind kind, const char *who) {
-    const PathKind other = PATHS[kind].excluded_by;
-    if (other != PATH_NONE && ctx->path == other) return fail(ctx, HANK_ERR_NOT_READY, "%s: %s is set and the two exclude each other", who, PATHS[other].a_path);
+    const PathKind other = ctx->path;
+    if (other != PATH_NONE && (PATHS[kind].excluded_under >> other & 1u)) return fail(ctx, HANK_ERR_NOT_READY, "%s: %s is set and the two exclude each other", who, PATHS[other].a_path);
     return HANK_OK;
 }
 // the column masses of the recorded distributions, for the first reader at this record (the main stream has joined the forward sweep)
@@ -2359,7 +2388,8 @@ int hank_jvp_boundary(hank_ctx *ctx, const double *dxhh, const double *dvalue_en
     return tan_host_tail(ctx, dagg_out, ctx->batch.dagg_cm, (size_t)ctx->c.P * N);
 }
 
-// hank_jvp_shock[_dev] (hank_shock.h), hank_jvp_income[_dev] (hank_income.h): the request with the kind's seeds — d beta_t, d y_t[e] —
+// hank_jvp_shock[_dev] (hank_shock.h), hank_jvp_income[_dev] (hank_income.h), hank_jvp_borrow[_dev] (hank_borrow.h): the request with the
+// kind's seeds — d beta_t, d y_t[e], d amin_t —
 // always on the launches' graphs with the seed kernels; a null input is a zero seed. Named as hank_jvp names its batch. The four
 // entries' one body; the rule differs by kind in its messages and in path_entry_excluded alone.
 static int jvp_path(hank_ctx *ctx, PathKind kind, const double *dxhh, const double *dpath, int N, double *out, bool dev) {
@@ -2381,6 +2411,8 @@ int hank_jvp_shock_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dbet
 int hank_jvp_shock(hank_ctx *ctx, const double *dxhh, const double *dbeta, int32_t N, double *dagg_out) { return jvp_path(ctx, PATH_DISCOUNT, dxhh, dbeta, N, dagg_out, false); }
 int hank_jvp_income_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_dy, int32_t N, double *d_dagg_out) { return jvp_path(ctx, PATH_INCOME, d_dxhh, d_dy, N, d_dagg_out, true); }
 int hank_jvp_income(hank_ctx *ctx, const double *dxhh, const double *dy, int32_t N, double *dagg_out) { return jvp_path(ctx, PATH_INCOME, dxhh, dy, N, dagg_out, false); }
+int hank_jvp_borrow_dev(hank_ctx *ctx, const double *d_dxhh, const double *d_damin, int32_t N, double *d_dagg_out) { return jvp_path(ctx, PATH_BORROW, d_dxhh, d_damin, N, d_dagg_out, true); }
+int hank_jvp_borrow(hank_ctx *ctx, const double *dxhh, const double *damin, int32_t N, double *dagg_out) { return jvp_path(ctx, PATH_BORROW, dxhh, damin, N, dagg_out, false); }
 
 static int run_fused(hank_ctx *ctx, TanWork &w) {
     const int grc = ensure_dual_graphs(ctx, w);
@@ -2571,6 +2603,7 @@ static int fake_news(hank_ctx *ctx, int n_het, bool groups, double *F_out, doubl
         HIPC(ctx, hipStreamSynchronize(s));      // (seed is this block's)
         break;
     }
+    case PATH_BORROW:          // no input moves; d amin_{P-1} = 1, staged as d beta_{P-1} = 1 is
     case PATH_DISCOUNT: {      // no input moves; d beta_{P-1} = 1 (the batch is one direction wide: (P, 1) column-major is [P])
         static const double one = 1.0;
         HIPC(ctx, hipMemsetAsync(w.dxhh, 0, sizeof(double) * c.n_hh * P, s));
@@ -2670,6 +2703,14 @@ int hank_fake_news_income(hank_ctx *ctx, int32_t n_het, double *F_out, double *D
     if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
     const int rc = het_count_ok(ctx, "hank_fake_news_income", n_het, false, n_het <= 2);
     return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, PATH_INCOME);
+}
+
+// (KrusellSmith.jl:52, :76, BackwardIteration.jl:90-113; the recursion of SteadyStateJacobian.jl:363-371 with the input fixed to the limit)
+int hank_fake_news_borrow(hank_ctx *ctx, int32_t n_het, double *F_out, double *Dv_out) {
+    ENTER(ctx);
+    if (!ctx || !F_out || !Dv_out) return fail(ctx, HANK_ERR_BAD_ARG, "null pointer");
+    const int rc = het_count_ok(ctx, "hank_fake_news_borrow", n_het, false);
+    return rc ? rc : fake_news(ctx, n_het, false, F_out, Dv_out, PATH_BORROW);
 }
 
 #ifdef HANK_XSTAMP
@@ -2941,6 +2982,9 @@ static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, PathKind kind) {
         if (kind == PATH_INCOME)
             hipLaunchKernelGGL(k_inc_ybar, dim3((unsigned)w.g.nb, (unsigned)((M + IMC - 1) / IMC)), dim3(INC_BT), inc_ybar_lds(c, w.g.R, IMC), s, c, ctx->R, ctx->d_xhh.get(),
                                w.g.R, IMC, t, t == 0 ? 1 : 0, ctx->d_adj_sb.get(), w.st[cur].get(), w.pbar.get(), M, pc.part.get() + (size_t)t * w.g.nb * c.n_e * M);
+        if (kind == PATH_BORROW)
+            hipLaunchKernelGGL(k_brw_abar, dim3((unsigned)w.g.nb, (unsigned)((M + MC - 1) / MC)), dim3(BRW_BT), 0, s, c, ctx->R, ctx->exo[PATH_BORROW].d.get(), w.g.R, MC, t,
+                               t == 0 ? 1 : 0, w.st[cur].get(), w.pbar.get(), M, pc.part.get() + (size_t)t * w.g.nb * M);
         cur ^= 1;
     }
     hipLaunchKernelGGL(k_adj_out, dim3((unsigned)((P * w.N + 255) / 256)), dim3(256), 0, s, P, c.n_hh, w.N, w.g.nb, ctx->d_xhh, w.partS, w.partM, w.yb1,
@@ -2951,7 +2995,7 @@ static int capture_cot_graph_b(hank_ctx *ctx, CotWork &w, PathKind kind) {
     if (kind == PATH_INCOME)
         hipLaunchKernelGGL(k_inc_ybar_out, dim3((unsigned)(((size_t)P * c.n_e * M + 255) / 256)), dim3(256), 0, s, P, c.n_e, M, pc.rm.get(),
                            ctx->d_inc_m.get(), w.yb1.get(), pc.cm.get());
-    if (kind == PATH_DISCOUNT)
+    if (kind == PATH_DISCOUNT || kind == PATH_BORROW)      // [P][M] -> (P, M) column-major
         hipLaunchKernelGGL(k_tan_out, dim3((unsigned)((P * M + 255) / 256)), dim3(256), 0, s, pc.rm.get(), P, M, pc.cm.get());
     return end_capture(ctx, &pc.g_B);
 }
@@ -3209,6 +3253,9 @@ int hank_vjp_income_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, i
 // (KrusellSmith.jl:59-62: where beta enters; BackwardIteration.jl:90-113: the loop the transposed sweep reverses)
 int hank_vjp_shock(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *beta_bar) { return vjp_path(ctx, PATH_DISCOUNT, n_het, agg_bar, M, xhh_bar, beta_bar, false); }
 int hank_vjp_shock_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_beta_bar) { return vjp_path(ctx, PATH_DISCOUNT, n_het, d_agg_bar, M, d_xhh_bar, d_beta_bar, true); }
+// (KrusellSmith.jl:52, :76: where the limit enters; BackwardIteration.jl:90-113: the loop the transposed sweep reverses)
+int hank_vjp_borrow(hank_ctx *ctx, int32_t n_het, const double *agg_bar, int32_t M, double *xhh_bar, double *amin_bar) { return vjp_path(ctx, PATH_BORROW, n_het, agg_bar, M, xhh_bar, amin_bar, false); }
+int hank_vjp_borrow_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_amin_bar) { return vjp_path(ctx, PATH_BORROW, n_het, d_agg_bar, M, d_xhh_bar, d_amin_bar, true); }
 int hank_vjp_boundary_dev(hank_ctx *ctx, int32_t n_het, const double *d_agg_bar, int32_t M, double *d_xhh_bar, double *d_value_end_bar, double *d_D_init_bar) {
     { const int irc = income_refuses(ctx, "hank_vjp_boundary"); if (irc) return irc; }
     return vjp_boundary(ctx, vjp_args, n_het, d_agg_bar, M, d_xhh_bar, d_value_end_bar, d_D_init_bar, true);

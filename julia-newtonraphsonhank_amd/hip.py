@@ -120,6 +120,12 @@ ABI_RESTYPE = {"hank_last_error": C.c_char_p}
 ABI_OPTIONAL = frozenset({"hank_get_lottery_record", "hank_get_forward_units"})      # (an older library named by HANK_HIP_LIB for an A-B has none)
 # the symbols include/hank_hip.h declares (tests check that every one is exported)
 ABI_SYMBOLS = tuple(ABI)
+# The rows of the extension headers, in the same letters and bound by the same loop (load_library): one table per header, so that
+# ABI stays the image of include/hank_hip.h. include/hank_hip_borrow.h: the borrowing-limit path (_PATHS["borrow"]).
+ABI_BORROW = {name: tuple(_ARG[a] for a in row.split()) for name, row in {
+    "hank_set_borrow_path": "v d", "hank_jvp_borrow": "v d d i d", "hank_jvp_borrow_dev": "v v v i v",
+    "hank_vjp_borrow": "v i d i d d", "hank_vjp_borrow_dev": "v i v i v v", "hank_fake_news_borrow": "v i d d",
+}.items()}
 
 
 def library_path() -> Path:
@@ -136,7 +142,7 @@ def load_library() -> C.CDLL:
             f"{_LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
     lib = C.CDLL(str(_LIB_PATH))
-    for name, argtypes in ABI.items():
+    for name, argtypes in {**ABI, **ABI_BORROW}.items():
         if name in ABI_OPTIONAL and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
@@ -239,13 +245,14 @@ def _grid_batch(x, n_a: int, n_e: int) -> np.ndarray:
     return s
 
 
-# What differs between the two exogenous paths: the attribute that holds the path in force, the name of its seed, the axes in
+# What differs between the exogenous paths: the attribute that holds the path in force, the name of its seed, the axes in
 # front of the period axis (the path is (*axes, P), a seed (*axes, P, N), the Toeplitz form (P, P, *axes, n_het)), the C symbols
 # (the device-pointer forms add _dev), and whether its transposed entry takes cotangents by `vjp_het`'s rule or by `vjp`'s.
 _Path = namedtuple("_Path", "attr seed axes set jvp vjp fake_news het")
 _PATHS = {
     "discount": _Path("discount_path", "dbeta", lambda hb: (), "hank_set_discount_path", "hank_jvp_shock", "hank_vjp_shock", "hank_fake_news_shock", True),
     "income": _Path("income_path", "dy", lambda hb: (hb.n_e,), "hank_set_income_path", "hank_jvp_income", "hank_vjp_income", "hank_fake_news_income", False),
+    "borrow": _Path("borrow_path", "damin", lambda hb: (), "hank_set_borrow_path", "hank_jvp_borrow", "hank_vjp_borrow", "hank_fake_news_borrow", True),
 }
 
 
@@ -284,6 +291,7 @@ class HouseholdBlock:
         self._boundary = None
         self.discount_path = None      # the beta_t path in force (set_discount_path), or None: the model's constant beta
         self.income_path = None        # the y_t[e] path in force (set_income_path), or None
+        self.borrow_path = None        # the amin_t path in force (set_borrow_path), or None: the model's constant borrow_cons
         m = hank_model(self.n_a, self.n_e, self.T, value_fn_id, _p(self.a_grid), _p(self.z_grid),
                        _p(self.Pi), float(beta), float(gamma), float(borrow_cons))
         if device is None:
@@ -534,6 +542,48 @@ class HouseholdBlock:
         input fixed to y[e]. `SteadyStateJacobian.income_jacobian` does the recursion. Same precondition as `fake_news`; no path
         may be set."""
         return self._fake_news_path("income", n_het)
+
+    def set_borrow_path(self, amin_t):
+        """a path amin_t (P,) of the borrowing limit (hank_set_borrow_path): amin_t is the limit in period t's choice,
+        a'_t = max(g_t, amin_t). None returns to the model's constant. Like a new boundary it drops the record. While a path is set
+        every sweep runs on the per-period launches; the scenario, steady-state and `fake_news*` entries are refused; it excludes
+        the other two paths. MIND THE KINK: with amin_t <= a_grid[0] the limit never binds through max — the grid's flat
+        extrapolation binds instead — and every partial in amin_t is an exact zero: a grid that is to show a response carries
+        points below the limit. With amin_t on a grid point a_grid[k], k > 0, the derivative is the left one."""
+        if amin_t is not None:
+            amin_t = np.ascontiguousarray(amin_t, dtype=np.float64)
+            if amin_t.shape != (self.P,):
+                raise ValueError(f"amin_t must be ({self.P},), got {amin_t.shape}")
+        self._set_path("borrow", amin_t)
+
+    def jvp_borrow(self, dxhh=None, damin=None) -> np.ndarray:
+        """the tangent sweeps with seeds in the borrowing-limit path as well (hank_jvp_borrow): dxhh (n_hh, P, N) as in `jvp`,
+        damin (P,) or (P, N); None means zeros, at least one must be given. -> dagg (P, N). Works with or without a path set;
+        always the launch family. The batch is current afterwards as `jvp`'s is: `dpolicy_seq`, `grid_aggregates`,
+        `het_outputs(n_het, dxhh)` and `group_outputs(dxhh)` serve it — the limit has no direct term in any output, so pass the
+        same dxhh (zeros for None)."""
+        return self._jvp_path("borrow", dxhh, damin)
+
+    def jvp_borrow_dev(self, d_dxhh_ptr: int, d_damin_ptr: int, N: int, d_dagg_ptr: int = 0):
+        """device-pointer form (asynchronous on the context's stream); a pointer of 0 is a zero seed."""
+        self._jvp_path_dev("borrow", d_dxhh_ptr, d_damin_ptr, N, d_dagg_ptr)
+
+    def vjp_borrow(self, agg_bar, n_het: int):
+        """`vjp_het` with the cotangent of the borrowing-limit path (hank_vjp_borrow): agg_bar (P, n_het, M) -> (xhh_bar
+        (n_hh, P, M), amin_bar (P, M)); the exact transpose of `jvp_borrow` followed by `het_outputs(n_het)`. xhh_bar equals
+        `vjp_het`'s bit for bit; amin_bar is a fixed-order reduction (the same inputs give the same bits)."""
+        return self._vjp_path("borrow", agg_bar, n_het)
+
+    def vjp_borrow_dev(self, n_het: int, d_agg_bar_ptr: int, M: int, d_xhh_bar_ptr: int, d_amin_bar_ptr: int):
+        """device-pointer form (asynchronous on the context's stream)."""
+        self._vjp_path_dev("borrow", n_het, d_agg_bar_ptr, M, d_xhh_bar_ptr, d_amin_bar_ptr)
+
+    def fake_news_borrow(self, n_het: int):
+        """the Toeplitz form of every output's Jacobian with respect to the borrowing-limit path at the steady state
+        (hank_fake_news_borrow): -> (F (P, P, n_het), Dv (P, n_het)), the definitions of `fake_news_het` with the input fixed to
+        the limit. `SteadyStateJacobian.borrow_jacobian` does the recursion. Same precondition as `fake_news`; no path may be
+        set. A steady state whose limit is a_grid[0] gives zeros (the kink convention of `set_borrow_path`)."""
+        return self._fake_news_path("borrow", n_het)
 
     # -- K input paths through one chain of launches ------------------------------------------
     def primal_batch(self, xhh, n_het: int = 1, policy: bool = False, check: bool = True):
