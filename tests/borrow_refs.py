@@ -1,7 +1,7 @@
 """The references of the borrowing-limit path (hank_set_borrow_path, hank_jvp_borrow, hank_vjp_borrow, hank_fake_news_borrow), shared by
 tests/test_borrow_host.py (CPU) and tests/test_gpu_borrow.py.
 
-1. `oracle_borrow_sweeps`: the loop of `shock_refs.oracle_shock_sweeps` built from the unchanged oracle with ONE `Oracle` per limit —
+1. `KIND`: the kind's row of tests/path_refs.py, whose `oracle_path_sweeps` is the loop, built from the unchanged oracle with ONE `Oracle` per limit —
    its constructor takes borrow_cons — so period t's `value_function` runs at amin_t. The tangent in amin: the same step with an oracle
    whose limit lies far below the grid gives the unconstrained dual g; the constrained set C_t is where the DiffRules rule of max holds
    against amin_t, (amin_t > g) | (signbit(amin_t) < signbit(g)); and KrusellSmith.jl:76-80 restated on duals says what amin's partial
@@ -11,19 +11,18 @@ tests/test_borrow_host.py (CPU) and tests/test_gpu_borrow.py.
 2. `borrow_case`: the economies of `shock_refs.shock_case`; their wealth grid 50 (k / (n_a - 1))^2 has several points below the limits
    chosen here (`limits`: two or three points at n_a = 33, eight to twelve at 130), so nothing is added to it. `borrow_path` cycles
    through: strictly inside a bracket; exactly on a grid point; a[0]; below a[0]; and tightens and relaxes between them.
-3. `oracle_borrow_jacobians`, `borrow_linear_policies`: the dense pair (Jx, Ja) from unit tangents, cached; `shock_refs.shock_linear` and
-   `shock_refs.shock_beta_bar` are its products (Ja has Jb's layout).
-4. `StubBorrowBlock`: stands in for the device context under `SteadyStateJacobian.borrow_jacobian`."""
+3. the dense pair (Jx, Ja) and its products are path_refs' (Ja has Jb's layout: the leading shape ())."""
 import numpy as np
 
 import cases
+import path_refs
 import shock_refs
-from oracle.oracle import SUPPORTED_N, Oracle, pad_N
+from oracle.oracle import Oracle
 
 HORIZONS = shock_refs.HORIZONS
 WIDTHS = shock_refs.WIDTHS
 FAR_BELOW = -1e300
-_CASES, _ORC, _JAC = {}, {}, {}
+_CASES, _ORC = {}, {}
 
 
 LIMIT_LO, LIMIT_HI = 0.19, 0.45
@@ -157,131 +156,36 @@ def constrained(am, g):
     return (am > g) | (np.signbit(am) < np.signbit(g))
 
 
-def oracle_borrow_sweeps(args, x, V, D, amin, gamma=None, n_het=2, dx=None, damin=None, groups=None):
-    """args: HouseholdBlock's (the oracle's first five are read); x (n_hh, P), boundary V (n_a, n_e), D (G,), amin (P,); seeds dx
-    (n_hh, P, N) and damin (P, N), None = zeros (both None: the level alone, one zero direction). -> the dict of
-    shock_refs.oracle_shock_sweeps, and C (P, n_a, n_e) the constrained sets, Dseq (P, n_a, n_e)."""
-    x, amin = np.asarray(x, dtype=np.float64), np.asarray(amin, dtype=np.float64)
-    n_hh, P = x.shape
-    assert amin.shape == (P,)
-    free = oracle_at(args, FAR_BELOW)
-    n_a, n_e, a, z = free.n_a, free.n_e, free.a, free.z
-    gamma = float(args[4]) if gamma is None else gamma
-    N = next((np.asarray(v).shape[-1] for v in (dx, damin) if v is not None), 1)
-    out = {k: [] for k in ("dagg", "dagg2", "dpol", "dgrp")}
-    K = 0 if groups is None else np.asarray(groups[0]).shape[1]
-    for c0 in range(0, N, SUPPORTED_N[-1]):
-        n = min(N, c0 + SUPPORTED_N[-1]) - c0
-        Nc = pad_N(n)
-        xd = np.zeros((n_hh, P, 1 + Nc)); xd[..., 0] = x
-        Vn = np.zeros((n_a, n_e, 1 + Nc)); Vn[..., 0] = V
-        Dd = np.zeros((n_a, n_e, 1 + Nc)); Dd[..., 0] = np.asarray(D).reshape((n_a, n_e), order="F")
-        if dx is not None:
-            xd[..., 1:1 + n] = dx[:, :, c0:c0 + n]
-        pol, val, Cs = [None] * P, [None] * P, [None] * P
-        for t in range(P - 1, -1, -1):
-            tr = xd[2, t] if n_hh > 2 else None
-            st, Vc, Kc = oracle_at(args, amin[t]).value_function(Vn, xd[0, t], xd[1, t], Nc, tr)
-            assert st == 0, (t, st)
-            st, _, Ku = free.value_function(Vn, xd[0, t], xd[1, t], Nc, tr)
-            assert st == 0, (t, st, "free")
-            C = constrained(amin[t], Ku[..., 0])
-            assert np.array_equal(Kc[..., 0], np.where(C, amin[t], Ku[..., 0])) and not np.any(Kc[C, 1:]), t
-            if damin is not None and np.any(damin[t, c0:c0 + n]):
-                da = damin[t, c0:c0 + n]
-                r, w, tr0 = xd[0, t, 0], xd[1, t, 0], (xd[2, t, 0] if n_hh > 2 else 0.0)
-                cg = (1.0 + r) * a[:, None] + w * z[None, :] + tr0 - Kc[..., 0]                   # :79
-                Kc[C, 1:1 + n] += da                                                             # :76 the partial of max is amin's
-                Vc[C, 1:1 + n] += (gamma * (1.0 + r) * cg ** (-gamma - 1.0))[C][:, None] * da   # :80 Value = (1 + r) c^-gamma, dc = -damin
-            Vn, pol[t], val[t], Cs[t] = Vc, Kc, Vc, C
-        agg, agg2 = np.zeros((P, n_het)), np.zeros(P)
-        dagg, dagg2 = np.zeros((P, n_het, n)), np.zeros((P, n))
-        grp, dgrp = np.zeros((P, K)), np.zeros((P, K, n))
-        Dseq = np.zeros((P, n_a, n_e))
-        for t in range(P):
-            Dd = free.transition_step(pol[t], Dd, Nc)
-            p0, dp, D0, dDt = pol[t][..., 0], pol[t][..., 1:1 + n], Dd[..., 0], Dd[..., 1:1 + n]
-            tr, dtr = (xd[2, t, 0], xd[2, t, 1:1 + n]) if n_hh > 2 else (0.0, np.zeros(n))
-            c0_ = (1.0 + xd[0, t, 0]) * a[:, None] + xd[1, t, 0] * z[None, :] + tr - p0
-            dc = xd[0, t, 1:1 + n] * a[:, None, None] + xd[1, t, 1:1 + n] * z[None, :, None] + dtr - dp
-            fs = [(p0, dp), (c0_, dc), (val[t][..., 0], val[t][..., 1:1 + n])]
-            if n_het > 3:
-                fs.append((z[None, :] * c0_ ** (-gamma), (z[None, :] * (-gamma) * c0_ ** (-gamma - 1.0))[..., None] * dc))
-            for o, (f0, df) in enumerate(fs[:n_het]):
-                agg[t, o] = np.sum(f0 * D0)
-                dagg[t, o] = np.einsum("aen,ae->n", df, D0) + np.einsum("ae,aen->n", f0, dDt)
-            for k in range(K):
-                Wk = np.asarray(groups[0])[:, k].reshape((n_a, n_e), order="F")
-                f0, df = ((np.ones_like(p0), np.zeros_like(dp)), fs[0], fs[1])[int(groups[1][k])]
-                grp[t, k] = np.sum(Wk * f0 * D0)
-                dgrp[t, k] = np.einsum("aen,ae->n", df, Wk * D0) + np.einsum("ae,aen->n", Wk * f0, dDt)
-            agg2[t] = np.sum(a[:, None] * D0)
-            dagg2[t] = np.einsum("a,aen->n", a, dDt)
-            Dseq[t] = D0
-        out["dagg"].append(dagg); out["dagg2"].append(dagg2); out["dgrp"].append(dgrp)
-        out["dpol"].append(np.stack([p[..., 1:1 + n] for p in pol]))
-    res = {k: np.concatenate(v, axis=-1) for k, v in out.items()}
-    res.update(agg=agg, agg2=agg2, grp=grp, pol=np.stack([p[..., 0] for p in pol]), D=Dd[..., 0], C=np.stack(Cs), Dseq=Dseq)
-    return res
+def _step(w, Vn, xd, pd, t):
+    """period t at amin_t: `value_function` of the Oracle with borrow_cons = amin_t; the same step with the oracle whose limit lies far
+    below the grid (w.orc) gives the unconstrained dual and so C_t, recorded as C; amin's partial is ADDED to the constrained oracle's
+    own duals on C_t (exact zeros there, asserted), and only where damin_t is not zero"""
+    n, gamma = w.n, w.gamma
+    a, z = w.orc.a, w.orc.z
+    amin = pd[t, 0]
+    tr = xd[2, t] if w.n_hh > 2 else None
+    st, Vc, Kc = oracle_at(w.model, amin).value_function(Vn, xd[0, t], xd[1, t], w.Nc, tr)
+    assert st == 0, (t, st)
+    st, _, Ku = w.orc.value_function(Vn, xd[0, t], xd[1, t], w.Nc, tr)
+    assert st == 0, (t, st, "free")
+    C = constrained(amin, Ku[..., 0])
+    assert np.array_equal(Kc[..., 0], np.where(C, amin, Ku[..., 0])) and not np.any(Kc[C, 1:]), t
+    if w.seeded and np.any(pd[t, 1:1 + n]):
+        da = pd[t, 1:1 + n]
+        r, wg, tr0 = xd[0, t, 0], xd[1, t, 0], (xd[2, t, 0] if w.n_hh > 2 else 0.0)
+        cg = (1.0 + r) * a[:, None] + wg * z[None, :] + tr0 - Kc[..., 0]                  # :79
+        Kc[C, 1:1 + n] += da                                                             # :76 the partial of max is amin's
+        Vc[C, 1:1 + n] += (gamma * (1.0 + r) * cg ** (-gamma - 1.0))[C][:, None] * da   # :80 Value = (1 + r) c^-gamma, dc = -damin
+    w.rec.setdefault("C", [None] * xd.shape[1])[t] = C
+    return Vc, Kc
+
+
+# the model is HouseholdBlock's args (the oracle's first five are read), gamma is always given; C (P, n_a, n_e): the constrained sets
+KIND = path_refs.register(path_refs.Kind("borrow", "borrow", "amin", "args", lambda orc: (), lambda args, P: np.full(P, float(args[5])), _step,
+                                         lambda args: oracle_at(args, FAR_BELOW), False, None, None, True))
 
 
 def case_args(c, path=True):
     """(args, x, V, D, amin) of case c: the path, or the model's constant in every period"""
     P = c["x"].shape[1]
     return (c["args"], c["x"], c["V"], c["D"], c["amin"] if path else np.full(P, c["bc"]))
-
-
-def _unit_sweeps(args, x, V, D, amin, gamma, n_het):
-    x, V, D, amin = (np.ascontiguousarray(v, dtype=np.float64) for v in (x, V, D, amin))
-    key = (np.asarray(args[0]).tobytes(), np.asarray(args[1]).tobytes(), np.asarray(args[2]).tobytes(), float(args[3]), float(args[4]),
-           x.tobytes(), V.tobytes(), D.tobytes(), amin.tobytes(), gamma, n_het)
-    if key not in _JAC:
-        n_hh, P = x.shape
-        sx = oracle_borrow_sweeps(args, x, V, D, amin, gamma, n_het, dx=cases.unit_tangents(n_hh, P))
-        sa = oracle_borrow_sweeps(args, x, V, D, amin, gamma, n_het, damin=np.eye(P))
-        _JAC[key] = (sx, sa)
-    return _JAC[key]
-
-
-def oracle_borrow_jacobians(args, x, V, D, amin, gamma, n_het):
-    """-> (Jx (n_het, P, n_hh, P), the layout cases.jt takes, and Ja (P, n_het, P), d output o at t / d amin_s as [t, o, s]): the layouts
-    of shock_refs.oracle_shock_jacobians, so shock_refs.shock_linear and shock_beta_bar are the pair's products"""
-    sx, sa = _unit_sweeps(args, x, V, D, amin, gamma, n_het)
-    n_hh, P = np.asarray(x).shape
-    return np.ascontiguousarray(sx["dagg"].reshape(P, n_het, P, n_hh).transpose(1, 0, 3, 2)), sa["dagg"]
-
-
-def borrow_linear_policies(args, x, V, D, amin, gamma, n_het, dx, damin):
-    """dpol (P, n_a, n_e, N) of the directions dx (n_hh, P, N) or None and damin (P, N) or None, from the unit sweeps (the map is linear)"""
-    sx, sa = _unit_sweeps(args, x, V, D, amin, gamma, n_het)
-    n_hh, P = np.asarray(x).shape
-    N = next(v.shape[-1] for v in (dx, damin) if v is not None)
-    out = np.zeros(sx["dpol"].shape[:3] + (N,))
-    if dx is not None:
-        out += sx["dpol"] @ np.asarray(dx).reshape((n_hh * P, N), order="F")
-    if damin is not None:
-        out += sa["dpol"] @ np.asarray(damin)
-    return out
-
-
-def borrow_seeds(c, N, seed, t_only=None):
-    """(dx (n_hh, P, N), damin (P, N)): random directions of the inputs' and of the limit's scale; t_only: damin in that period alone"""
-    rng = np.random.default_rng(seed)
-    n_hh, P = c["x"].shape
-    dx = rng.standard_normal((n_hh, P, N)) * 1e-2
-    da = rng.standard_normal((P, N)) * 1e-2
-    if t_only is not None:
-        keep = np.zeros((P, 1)); keep[t_only] = 1.0
-        da = da * keep
-    return dx, da
-
-
-class StubBorrowBlock:
-    """stands in for the device context under `borrow_jacobian`: fake_news_borrow hands out the F and Dv it was made with"""
-
-    def __init__(self, F, Dv):
-        self.F, self.Dv, self.calls = F, Dv, 0
-
-    def fake_news_borrow(self, n_het):
-        self.calls += 1
-        return self.F[..., :n_het].copy(), self.Dv[..., :n_het].copy()

@@ -6,7 +6,8 @@ compare the device with them).
    section 3d) in numpy on a random linearisation record — with extra outputs that are not affine in the policy (X, section 3a:
    dY^o_t = sum f_o,t dD_t - sum f_c,o,t D_t da'_t + dr_t (Sa + Sr) + dw_t Sz + dtr_t S1) and with seeds / cotangents on the
    boundary (dV_P, dD_0) as options;
-2. `oracle_sweeps`: the CPU oracle's household block with duals on the inputs AND on the boundary — `Oracle.value_function`
+2. `oracle_sweeps`: tests/path_refs.oracle_path_sweeps — the one loop, which the household-side paths share — at the row without a
+   path: the CPU oracle's household block with duals on the inputs AND on the boundary — `Oracle.value_function`
    backward with a dual `value_next` (the tangent of `ss_end.value`, BackwardIteration.jl:85), `Oracle.transition_step` forward with
    a dual `D_prev` (the tangent of `ss_initial.D`, ForwardIteration.jl:293), the aggregates in numpy. Value is the dual V_t that
    `Oracle.value_function` returns in that loop — the reference's own Value key (KrusellSmith.jl:80); UCE is z_e c^-gamma by the
@@ -19,8 +20,8 @@ import numpy as np
 import pytest
 
 import cases as vc
+import path_refs
 from conftest import ROOT, ks_paths, ks_setup
-from oracle.oracle import SUPPORTED_N, pad_N
 
 NXT = 2         # extra outputs of the numpy maps
 
@@ -144,51 +145,9 @@ def oracle_sweeps(orc, x, V, D, gamma=None, n_het=2, y=None, dV=None, dD=None):
     -> dict: agg (P, n_het) and dagg (P, n_het, N) of (savings, consumption, Value[, UCE]) with the post-transition D_t — the shapes
     of hank_get_het_outputs; cons (P,), dcons (P, N) their consumption columns; agg2 (P,), dagg2 (P, N) the wealth grid's
     aggregate; pol (P, n_a, n_e), dpol (P, n_a, n_e, N)."""
-    x = np.asarray(x, dtype=np.float64)
-    n_hh, P = x.shape
-    n_a, n_e, a, z = orc.n_a, orc.n_e, orc.a, orc.z
-    N = next(np.asarray(v).shape[-1] for v in (y, dV, dD) if v is not None)
-    out = {k: [] for k in ("dagg", "dagg2", "dpol")}
-    for c0 in range(0, N, SUPPORTED_N[-1]):
-        n = min(N, c0 + SUPPORTED_N[-1]) - c0
-        Nc = pad_N(n)
-        xd = np.zeros((n_hh, P, 1 + Nc)); xd[..., 0] = x
-        Vn = np.zeros((n_a, n_e, 1 + Nc)); Vn[..., 0] = V
-        Dd = np.zeros((n_a, n_e, 1 + Nc)); Dd[..., 0] = np.asarray(D).reshape((n_a, n_e), order="F")
-        if y is not None:
-            xd[..., 1:1 + n] = y[:, :, c0:c0 + n]
-        if dV is not None:
-            Vn[..., 1:1 + n] = dV[:, :, c0:c0 + n]
-        if dD is not None:
-            Dd[..., 1:1 + n] = dD[:, :, c0:c0 + n]
-        pol, val = [None] * P, [None] * P
-        for t in range(P - 1, -1, -1):
-            st, Vn, pol[t] = orc.value_function(Vn, xd[0, t], xd[1, t], Nc, xd[2, t] if n_hh > 2 else None)
-            assert st == 0, (t, st)
-            val[t] = Vn
-        agg, agg2 = np.zeros((P, n_het)), np.zeros(P)
-        dagg, dagg2 = np.zeros((P, n_het, n)), np.zeros((P, n))
-        for t in range(P):
-            Dd = orc.transition_step(pol[t], Dd, Nc)
-            p0, dp, D0, dDt = pol[t][..., 0], pol[t][..., 1:1 + n], Dd[..., 0], Dd[..., 1:1 + n]
-            tr, dtr = (xd[2, t, 0], xd[2, t, 1:1 + n]) if n_hh > 2 else (0.0, np.zeros(n))
-            # consumption: the affine map of the policy dual, c = (1 + r) a + w z_e + tr - a' (KrusellSmith.jl:79)
-            c0_ = (1.0 + xd[0, t, 0]) * a[:, None] + xd[1, t, 0] * z[None, :] + tr - p0
-            dc = xd[0, t, 1:1 + n] * a[:, None, None] + xd[1, t, 1:1 + n] * z[None, :, None] + dtr - dp
-            fs = [(p0, dp), (c0_, dc), (val[t][..., 0], val[t][..., 1:1 + n])]
-            if n_het > 3:
-                fs.append((z[None, :] * c0_ ** (-gamma), (z[None, :] * (-gamma) * c0_ ** (-gamma - 1.0))[..., None] * dc))
-            for o, (f0, df) in enumerate(fs[:n_het]):
-                agg[t, o] = np.sum(f0 * D0)
-                dagg[t, o] = np.einsum("aen,ae->n", df, D0) + np.einsum("ae,aen->n", f0, dDt)
-            agg2[t] = np.sum(a[:, None] * D0)
-            dagg2[t] = np.einsum("a,aen->n", a, dDt)
-        out["dagg"].append(dagg); out["dagg2"].append(dagg2)
-        out["dpol"].append(np.stack([p[..., 1:1 + n] for p in pol]))
-    res = {k: np.concatenate(v, axis=-1) for k, v in out.items()}
-    res.update(agg=agg, agg2=agg2, pol=np.stack([p[..., 0] for p in pol]))
+    res = path_refs.oracle_path_sweeps(path_refs.PLAIN, orc, x, V, D, None, gamma, n_het, dx=y, dV=dV, dD=dD)
     if n_het > 1:
-        res.update(cons=agg[:, 1], dcons=res["dagg"][:, 1])
+        res.update(cons=res["agg"][:, 1], dcons=res["dagg"][:, 1])
     return res
 
 

@@ -14,9 +14,13 @@ import pytest
 
 import borrow_refs as R
 import cases
+import path_checks as C
+import path_refs
 import shock_refs
-from cases import close, jt
+from cases import close
 from test_shock_host import STEP
+
+K = R.KIND
 
 ECONOMIES = [(f, name, n_a, n_e) for f in ("ks", "hank") for name in cases.ENTRY_CASES for n_a, n_e in cases.ENTRY_GRIDS]
 
@@ -51,7 +55,7 @@ def test_the_economies_hold_their_conditions(oracle_mod, family, name, n_a, n_e)
         if T == 12:
             assert {"inside", "on", "first", "below"} <= set(kinds)
             assert np.any(np.diff(amin) > 0) and np.any(np.diff(amin) < 0)        # a tightening and a relaxing step
-        s = R.oracle_borrow_sweeps(*R.case_args(c), c["gamma"], 2)                # (every oracle status is 0: asserted inside)
+        s = path_refs.oracle_path_sweeps(K, *R.case_args(c), c["gamma"], 2)                # (every oracle status is 0: asserted inside)
         here = True
         for t, k in enumerate(kinds):
             C = s["C"][t]
@@ -78,10 +82,10 @@ def test_without_a_seed_in_the_limit_the_reference_is_the_constant_limit_oracle_
     for bc in (c0["bc"], L["inside"]):
         c = R.with_limit(c0, bc)
         P = T - 1
-        dx, _ = R.borrow_seeds(c, 3, 1)
-        own = shock_refs.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], np.full(P, c["beta"]), c["gamma"], c["n_het"], y=dx)
+        dx, _ = path_refs.seeds(K, c, 3, 1)
+        own = path_refs.oracle_path_sweeps(shock_refs.KIND, c["orc"], c["x"], c["V"], c["D"], np.full(P, c["beta"]), c["gamma"], c["n_het"], dx=dx)
         for damin in (None, np.zeros((P, 3))):
-            ref = R.oracle_borrow_sweeps(*R.case_args(c, False), c["gamma"], c["n_het"], dx=dx, damin=damin)
+            ref = path_refs.oracle_path_sweeps(K, *R.case_args(c, False), c["gamma"], c["n_het"], dx=dx, dpath=damin)
             for k in ("agg", "dagg", "agg2", "dagg2", "pol", "dpol"):
                 assert np.array_equal(ref[k], own[k]), (family, name, bc, k, np.abs(ref[k] - own[k]).max())
 
@@ -98,13 +102,13 @@ def test_the_reference_s_limit_tangent_is_the_derivative_of_its_own_level(oracle
     damin = np.zeros((P, len(ts)))
     damin[ts, np.arange(len(ts))] = 1.0
     args = R.case_args(c)
-    ref = R.oracle_borrow_sweeps(*args, c["gamma"], c["n_het"], damin=damin)
+    ref = path_refs.oracle_path_sweeps(K, *args, c["gamma"], c["n_het"], dpath=damin)
     for k, t in enumerate(ts):
         lv = []
         for sgn in (1.0, -1.0):
             am = c["amin"].copy()
             am[t] += sgn * STEP
-            lv.append(R.oracle_borrow_sweeps(*args[:4], am, c["gamma"], c["n_het"]))
+            lv.append(path_refs.oracle_path_sweeps(K, *args[:4], am, c["gamma"], c["n_het"]))
         what = f"{family} {name} {n_a}x{n_e} T={T} amin_{t}"
         assert np.array_equal(lv[0]["C"], ref["C"]) and np.array_equal(lv[1]["C"], ref["C"]), what      # a condition on the inputs
         fd_agg = (lv[0]["agg"] - lv[1]["agg"]) / (2 * STEP)
@@ -120,29 +124,14 @@ def test_the_reference_s_limit_tangent_is_the_derivative_of_its_own_level(oracle
 @pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 12), ("hank", "gamma1", 130, 3, 5)])
 def test_the_dense_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, family, name, n_a, n_e, T):
     c = R.borrow_case(family, name, n_a, n_e, T)
-    n_hh, P = c["x"].shape
-    nh = c["n_het"]
-    args = R.case_args(c) + (c["gamma"], nh)
-    Jx, Ja = J = R.oracle_borrow_jacobians(*args)
-    assert Jx.shape == (nh, P, n_hh, P) and Ja.shape == (P, nh, P)
-    assert R._unit_sweeps(*args)[1] is R._unit_sweeps(*args)[1]               # (the sweeps ran once)
+    r = C.dense_pair_reproduces_sweeps(K, c, f"{family} {name}", 1e-12)
+    Ja, sa = r.J[1], path_refs.unit_sweeps(*r.args)[1]
     for s, k in enumerate(c["kinds"]):                                        # convention (i): exact zeros, every output, every period
         if k in ("first", "below"):
-            assert not np.any(Ja[:, :, s]) and not np.any(R._unit_sweeps(*args)[1]["dpol"][..., s]), (s, k)
+            assert not np.any(Ja[:, :, s]) and not np.any(sa["dpol"][..., s]), (s, k)
         else:
-            assert np.any(R._unit_sweeps(*args)[1]["dpol"][s, ..., s]), (s, k)      # (a relaxing step may find no mass on C_s: Ja's column is zero then)
-    rng = np.random.default_rng(P)
-    dx, da = rng.standard_normal((n_hh, P, 5)), rng.standard_normal((P, 5))
-    ref = R.oracle_borrow_sweeps(*args, dx=dx, damin=da)
-    lin = shock_refs.shock_linear(J, dx, da)
-    for o in range(nh):
-        close(lin[:, o, :], ref["dagg"][:, o, :], rel=1e-12, ab=0.0, what=f"{family} {name} output {o}")
-    close(R.borrow_linear_policies(*args, dx, da), ref["dpol"], rel=1e-12, ab=0.0, what=f"{family} {name} policy")
-    yb = rng.standard_normal((P, nh, 4))
-    lhs = np.einsum("tom,ton->mn", yb, lin)
-    rhs = np.einsum("ksm,ksn->mn", jt(Jx, yb), dx) + np.einsum("sm,sn->mn", shock_refs.shock_beta_bar(Ja, yb), da)
-    scale = np.einsum("tom,ton->mn", np.abs(yb), shock_refs.shock_linear((np.abs(Jx), np.abs(Ja)), np.abs(dx), np.abs(da)))
-    assert np.all(np.abs(lhs - rhs) <= 1e-13 * scale), np.max(np.abs(lhs - rhs) / scale)
+            assert np.any(sa["dpol"][s, ..., s]), (s, k)      # (a relaxing step may find no mass on C_s: Ja's column is zero then)
+    close(path_refs.linear_policies(*r.args, dx=r.dx, dp=r.dp), r.ref["dpol"], rel=1e-12, ab=0.0, what=f"{family} {name} policy")
 
 
 # ---- 3. the third kind in the binding's one table ---------------------------------------------------------------------------------------
@@ -232,21 +221,7 @@ def test_the_host_library_names_the_kind_in_its_one_table_and_nowhere_else():
 
 # ---- 4. the Toeplitz recursion ------------------------------------------------------------------------------------------------------------
 def test_borrow_jacobian_is_the_toeplitz_recursion_per_output(hank):
-    from hank_amd.SteadyStateJacobian import borrow_jacobian, household_jacobian
-    rng = np.random.default_rng(4)
-    P, nh = 6, 3
-    F, Dv = rng.standard_normal((P, P, nh)), rng.standard_normal((P, nh))
-    stub = R.StubBorrowBlock(F, Dv)
-    J = borrow_jacobian(stub, nh)
-    assert J.shape == (nh, P, P) and stub.calls == 1
-    for o in range(nh):
-        want = np.empty((P, P))
-        for t in range(P):
-            for s in range(P):
-                want[t, s] = F[t, s, o] + (want[t - 1, s - 1] if t > 0 and s > 0 else (Dv[s, o] if t == 0 else 0.0))
-        assert np.allclose(J[o], want, rtol=0, atol=1e-14)
-        assert np.array_equal(J[o], household_jacobian(F[..., o:o + 1], Dv[..., o:o + 1])[0])
-    assert borrow_jacobian(stub, 1).shape == (1, P, P)
+    C.jacobian_is_the_toeplitz_recursion(hank, K, (), 3, 1)
 
 
 # ---- 5. the Newton keyword ----------------------------------------------------------------------------------------------------------------

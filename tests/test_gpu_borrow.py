@@ -1,5 +1,5 @@
 """The borrowing-limit path on the device (hank_set_borrow_path, hank_jvp_borrow, hank_vjp_borrow, hank_fake_news_borrow) through the
-C ABI, against tests/borrow_refs.oracle_borrow_sweeps — one unchanged CPU oracle per limit, the constrained set from an oracle whose
+C ABI, against tests/path_refs.oracle_path_sweeps at tests/borrow_refs.KIND — one unchanged CPU oracle per limit, the constrained set from an oracle whose
 limit lies far below the grid, KrusellSmith.jl:76-80 restated on duals — which tests/test_borrow_host.py pins against the
 constant-limit oracle's bits and against a central difference of its own level.
 
@@ -13,37 +13,15 @@ import pytest
 import borrow_refs as R
 import cases
 import fake_news_refs as FR
+import path_checks as C
+import path_refs
 import ss_diff_cases as S
 from cases import close, jt
-from hank_amd.hip import _p
-from shock_refs import shock_beta_bar, shock_linear
+from path_checks import NOT_READY, grid_cases
 
 pytestmark = pytest.mark.gpu
 
-GRID_CASES = [(f, name, n_a, n_e) for f in ("ks", "hank") for name in cases.ENTRY_CASES for n_a, n_e in cases.ENTRY_GRIDS]
-grid_cases = pytest.mark.parametrize("family,name,n_a,n_e", GRID_CASES)
-NOT_READY, BAD_ARG = 5, 2
-
-
-def _ctx(hank, c, schedule="launch", path=True):
-    hb = cases.raw_block(hank, c["args"], schedule, **c["env"])
-    hb.set_boundary(c["V"], c["D"])
-    hb.set_het_outputs(c["n_het"])
-    assert hb.info()["record_diet"] == c["diet"]
-    if path:
-        hb.set_borrow_path(c["amin"])
-    return hb
-
-
-def _raises(code, fn, *a, **kw):
-    from hank_amd.hip import HankHIPError
-    with pytest.raises(HankHIPError) as ei:
-        fn(*a, **kw)
-    assert ei.value.code == code, (ei.value.code, code, str(ei.value))
-
-
-def _jac(c, path=True):
-    return R.case_args(c, path) + (c["gamma"], c["n_het"])
+K = R.KIND
 
 
 def _groups(c):
@@ -65,10 +43,10 @@ def test_primal_at_a_path_matches_the_oracle_under_every_schedule(hank, oracle_m
     for T in R.HORIZONS:
         c = R.borrow_case(family, name, n_a, n_e, T)
         P, nh, what = T - 1, c["n_het"], f"{family} {name} {n_a}x{n_e} T={T}"
-        ref = R.oracle_borrow_sweeps(*_jac(c))
+        ref = path_refs.oracle_path_sweeps(*C.ref_args(K, c))
         got = {}
         for sched in ("launch", "xcd", "wide"):
-            hb = _ctx(hank, c, sched)
+            hb = C.ctx(hank, K, c, sched)
             try:
                 before = hb.stats()
                 agg0 = hb.primal(c["x"])
@@ -87,7 +65,7 @@ def test_primal_at_a_path_matches_the_oracle_under_every_schedule(hank, oracle_m
         assert np.array_equal(pol.transpose(2, 0, 1) == c["amin"][:, None, None], ref["pol"] == c["amin"][:, None, None]), what
         for sched in ("xcd", "wide"):
             assert all(np.array_equal(g, l) for g, l in zip(got[sched], got["launch"])), (what, sched)
-        assert np.abs(ref["pol"] - R.oracle_borrow_sweeps(*_jac(c, False))["pol"]).max() > 1e-3, what      # (the path moves the policy)
+        assert np.abs(ref["pol"] - path_refs.oracle_path_sweeps(*C.ref_args(K, c, False))["pol"]).max() > 1e-3, what      # (the path moves the policy)
 
 
 @grid_cases
@@ -97,31 +75,16 @@ def test_a_path_at_the_model_s_limit_gives_the_bits_of_no_path(hank, oracle_mod,
     with the neutral path gives its bits"""
     for T in (2, 12):
         c = R.borrow_case(family, name, n_a, n_e, T)
-        hb = _ctx(hank, c, "launch", path=False)
-        try:
-            agg, het, pol = hb.primal(c["x"]), hb.het_outputs(c["n_het"])[0], hb.policy_seq()
-            hb.set_borrow_path(np.full(T - 1, c["bc"]))
-            _raises(NOT_READY, hb.policy_seq)
-            assert np.array_equal(hb.primal(c["x"]), agg) and np.array_equal(hb.policy_seq(), pol), (family, name, n_a, n_e, T)
-            assert np.array_equal(hb.het_outputs(c["n_het"])[0], het), (family, name, n_a, n_e, T)
-        finally:
-            hb.close()
-        hb = _ctx(hank, c, None, path=False)
-        try:
-            hb.set_borrow_path(np.full(T - 1, c["bc"]))
-            assert np.array_equal(hb.primal(c["x"]), agg) and np.array_equal(hb.policy_seq(), pol), (family, name, n_a, n_e, T, "default")
-            assert np.array_equal(hb.het_outputs(c["n_het"])[0], het), (family, name, n_a, n_e, T, "default")
-        finally:
-            hb.close()
+        C.neutral_path_gives_the_bits_of_no_path(hank, K, c, (family, name, n_a, n_e, T), het=c["n_het"], default_too=True)
 
 
 # ---- 2. hank_jvp_borrow ---------------------------------------------------------------------------------------------------------------
 def _borrow_against_oracle(hb, c, tag, dx, da, path):
-    J = R.oracle_borrow_jacobians(*_jac(c, path))
+    J = path_refs.jacobians(*C.ref_args(K, c, path))
     N = next(v.shape[-1] for v in (dx, da) if v is not None)
     nh = c["n_het"]
-    ref = shock_linear(J, dx, da)
-    dpol = R.borrow_linear_policies(*_jac(c, path), dx, da)
+    ref = path_refs.linear(J, dx, da)
+    dpol = path_refs.linear_policies(*C.ref_args(K, c, path), dx=dx, dp=da)
     close(hb.jvp_borrow(dx, da), ref[:, 0, :], what=f"{tag} dagg")
     got = hb.dpolicy_seq(N).transpose(2, 0, 1, 3)
     close(got, dpol, what=f"{tag} dpolicy")
@@ -134,23 +97,23 @@ def _borrow_against_oracle(hb, c, tag, dx, da, path):
 def _jvp_borrow_case(hank, c, tag, widths=R.WIDTHS, t_only=True, schedule=None, paths=(True, False)):
     P = c["x"].shape[1]
     for path in paths:
-        hb = _ctx(hank, c, schedule, path=path)
+        hb = C.ctx(hank, K, c, schedule, path=path)
         try:
             hb.primal(c["x"])
             tg = f"{tag} {'path' if path else 'no path'}"
             for N in widths:
-                dx, da = R.borrow_seeds(c, N, 11 + N)
+                dx, da = path_refs.seeds(K, c, N, 11 + N)
                 _borrow_against_oracle(hb, c, f"{tg} N={N} inputs and amin", dx, da, path)
                 _borrow_against_oracle(hb, c, f"{tg} N={N} amin alone", None, da, path)
                 _borrow_against_oracle(hb, c, f"{tg} N={N} inputs alone", dx, None, path)
             if t_only:
                 for t in sorted({0, P - 1}):
-                    _, da = R.borrow_seeds(c, 3, 13, t_only=t)
+                    _, da = path_refs.seeds(K, c, 3, 13, t_only=t)
                     _borrow_against_oracle(hb, c, f"{tg} N=3 amin_{t} alone", None, da, path)
             if path:      # convention (i): a seed in a period with amin_t <= a[0] moves nothing, exactly
                 for t, k in enumerate(c["kinds"]):
                     if k in ("first", "below"):
-                        _, da = R.borrow_seeds(c, 3, 17, t_only=t)
+                        _, da = path_refs.seeds(K, c, 3, 17, t_only=t)
                         dagg = hb.jvp_borrow(None, da)
                         assert not np.any(dagg) and not np.any(hb.dpolicy_seq(3)), (tg, t, k)
                         assert not np.any(hb.het_outputs(c["n_het"], np.zeros((hb.n_hh, P, 3)))[1]), (tg, t, k)
@@ -173,10 +136,10 @@ def test_jvp_borrow_at_a_record_written_by_another_family(hank, oracle_mod, sche
     limit is moved inside the grid, or the set would be empty"""
     c0 = R.borrow_case("hank", "gamma2", 130, 3, 12)
     c = R.with_limit(c0, R.limits(np.asarray(c0["args"][0]))["inside"])
-    hb = _ctx(hank, c, schedule, path=False)
+    hb = C.ctx(hank, K, c, schedule, path=False)
     try:
         hb.primal(c["x"])
-        dx, da = R.borrow_seeds(c, 33, 5)
+        dx, da = path_refs.seeds(K, c, 33, 5)
         got, _ = _borrow_against_oracle(hb, c, f"record by {schedule}", dx, da, False)
         assert np.any(got[0] != 0)
     finally:
@@ -186,21 +149,7 @@ def test_jvp_borrow_at_a_record_written_by_another_family(hank, oracle_mod, sche
 @grid_cases
 def test_jvp_borrow_without_a_seed_in_the_limit_is_hank_jvp_bit_for_bit(hank, oracle_mod, family, name, n_a, n_e):
     for T in (2, 4):
-        c = R.borrow_case(family, name, n_a, n_e, T)
-        hb = _ctx(hank, c, "launch")
-        try:
-            hb.primal(c["x"])
-            out = np.empty((T - 1, 3), order="F")
-            assert hb._lib.hank_jvp_borrow(hb._ctx, None, None, 3, _p(out)) == BAD_ARG
-            for N in R.WIDTHS:
-                dx, _ = R.borrow_seeds(c, N, 5)
-                dagg, dpol = hb.jvp(dx), hb.dpolicy_seq(N)
-                for da in (None, np.zeros((T - 1, N))):
-                    assert np.array_equal(hb.jvp_borrow(dx, da), dagg), (family, name, n_a, n_e, T, N)
-                    got = hb.dpolicy_seq(N)
-                    assert np.array_equal(got, dpol) and np.array_equal(np.signbit(got), np.signbit(dpol)), (family, name, n_a, n_e, T, N)
-        finally:
-            hb.close()
+        C.no_seed_in_the_path_is_hank_jvp_bit_for_bit(hank, K, R.borrow_case(family, name, n_a, n_e, T), (family, name, n_a, n_e, T), R.WIDTHS, signbits=True)
 
 
 # ---- 3. hank_vjp_borrow ----------------------------------------------------------------------------------------------------------------
@@ -208,11 +157,11 @@ def _vjp_borrow_case(hank, c, tag, widths=R.WIDTHS, schedule=None, paths=(True, 
     P, nh = c["x"].shape[1], c["n_het"]
     rng = np.random.default_rng(P)
     for path in paths:
-        hb = _ctx(hank, c, schedule, path=path)
+        hb = C.ctx(hank, K, c, schedule, path=path)
         try:
             hb.primal(c["x"])
-            Jx, Ja = R.oracle_borrow_jacobians(*_jac(c, path))
-            dx, da = R.borrow_seeds(c, 3, 21)
+            Jx, Ja = path_refs.jacobians(*C.ref_args(K, c, path))
+            dx, da = path_refs.seeds(K, c, 3, 21)
             hb.jvp_borrow(dx, da)
             _, Jd = hb.het_outputs(nh, dx)                                        # (P, n_het, N)
             for M in widths:
@@ -223,13 +172,9 @@ def _vjp_borrow_case(hank, c, tag, widths=R.WIDTHS, schedule=None, paths=(True, 
                     assert np.array_equal(xbar, hb.vjp_het(yb, n_het)), what
                     x2, a2 = hb.vjp_borrow(yb, n_het)
                     assert np.array_equal(x2, xbar) and np.array_equal(a2, abar), what
-                    close(abar, shock_beta_bar(Ja, yb), what=f"{what} amin_bar")
+                    close(abar, path_refs.path_bar(Ja, yb), what=f"{what} amin_bar")
                     close(xbar, jt(Jx[:n_het], yb), what=f"{what} xhh_bar")
-                    lhs = np.einsum("tom,ton->mn", yb, Jd[:, :n_het, :])
-                    rhs = np.einsum("ktm,ktn->mn", xbar, dx) + np.einsum("tm,tn->mn", abar, da)
-                    scale = np.einsum("tom,ton->mn", np.abs(yb), np.abs(Jd[:, :n_het, :]))
-                    print(f"{what}: max |lhs - rhs| / scale = {np.max(np.abs(lhs - rhs) / scale):.3e}; |amin_bar| {np.abs(abar).max():.3e}")
-                    assert np.all(np.abs(lhs - rhs) <= 1e-10 * scale), what
+                    C.transposed_identity(what, K, yb, Jd, xbar, dx, abar, da, moves=False)
                     if path:      # convention (i): exact zeros
                         assert not np.any(abar[[t for t, k in enumerate(c["kinds"]) if k in ("first", "below")]]), what
             tv = hb.last_vjp_timings()
@@ -263,9 +208,9 @@ def test_a_raw_grid_with_a_deep_constrained_prefix(hank, oracle_mod):
     interior prefix of more than 400 rows in every column — hundreds of sources on one target row of the forward sweep, many row blocks
     of the seed and of the reduction"""
     c = R.raw_case("deep-prefix")
-    ref = R.oracle_borrow_sweeps(*_jac(c))
+    ref = path_refs.oracle_path_sweeps(*C.ref_args(K, c))
     assert ref["C"][0].sum(axis=0).min() > 64 and ref["C"][0].sum(axis=0).min() > 2 * cases.adj_rows_per_block(1)
-    hb = _ctx(hank, c, None)
+    hb = C.ctx(hank, K, c, None)
     try:
         agg = hb.primal(c["x"])
         close(agg, ref["agg"][:, 0], what="raw deep-prefix aggregate")
@@ -292,7 +237,7 @@ def test_borrow_jacobian_matches_the_reference_at_a_steady_record(hank, oracle_m
         x = np.tile(c["x"][:, None], (1, P))
         hb.primal(x)
         J = borrow_jacobian(hb, nh)                                          # (n_het, P, P)
-        _, Ja = R.oracle_borrow_jacobians(args, x, c["V"], c["D"], np.full(P, c["bc"]), c["gamma"], nh)
+        _, Ja = path_refs.jacobians(K, args, x, c["V"], c["D"], np.full(P, c["bc"]), c["gamma"], nh)
         for o in range(nh):
             assert np.abs(Ja[:, o]).max() > 1e-3
             close(J[o], Ja[:, o, :], what=f"{econ} T={T} J_amin of output {o}")
@@ -306,7 +251,7 @@ def test_borrow_jacobian_matches_the_reference_at_a_steady_record(hank, oracle_m
             close(J[o], cols[:, o, :], what=f"{econ} T={T} J_amin of output {o} against the unit columns")
         hb.set_borrow_path(np.full(P, c["bc"]))
         hb.primal(x)
-        _raises(NOT_READY, hb.fake_news_borrow, nh)
+        C.raises(NOT_READY, hb.fake_news_borrow, nh)
     finally:
         hb.close()
 
@@ -317,13 +262,13 @@ def test_the_record_s_readers_work_at_a_path(hank, oracle_mod, family, name, n_a
     c = R.borrow_case(family, name, n_a, n_e, 12)
     P, nh = 11, c["n_het"]
     grp = _groups(c)
-    hb = _ctx(hank, c, None)
+    hb = C.ctx(hank, K, c, None)
     try:
         hb.set_group_outputs(*grp)
         hb.primal(c["x"])
-        dx, _ = R.borrow_seeds(c, 3, 7)
-        ref = R.oracle_borrow_sweeps(*_jac(c), dx=dx, groups=grp)
-        Jx, _ = R.oracle_borrow_jacobians(*_jac(c))
+        dx, _ = path_refs.seeds(K, c, 3, 7)
+        ref = path_refs.oracle_path_sweeps(*C.ref_args(K, c), dx=dx, groups=grp)
+        Jx, _ = path_refs.jacobians(*C.ref_args(K, c))
         what = f"{family} {name} {n_a}x{n_e}"
         close(hb.jvp_het(dx, n_het=nh), ref["dagg"], what=f"{what} hank_jvp_het")
         hb.jvp(dx)
@@ -343,7 +288,7 @@ def test_the_record_s_readers_work_at_a_path(hank, oracle_mod, family, name, n_a
         step = [hb.backward_step(c["V"], c["x"][:, 0]), hb.backward_step_dual(c["V"], np.ones(c["V"].shape + (2,)), c["x"][:, 0], np.ones((hb.n_hh, 2)))]
     finally:
         hb.close()
-    hb = _ctx(hank, c, None, path=False)                                         # the step entries keep the model's constant: no path's bits
+    hb = C.ctx(hank, K, c, None, path=False)                                         # the step entries keep the model's constant: no path's bits
     try:
         same = [hb.backward_step(c["V"], c["x"][:, 0]), hb.backward_step_dual(c["V"], np.ones(c["V"].shape + (2,)), c["x"][:, 0], np.ones((hb.n_hh, 2)))]
         for got, want in zip(step, same):
@@ -386,26 +331,26 @@ def test_entries_defined_at_one_limit_are_refused_while_a_path_is_set(hank, orac
         hb.primal(x)
         dagg = hb.jvp(dx)
         for k, f in calls.items():
-            _raises(NOT_READY, f)
+            C.raises(NOT_READY, f)
             assert np.array_equal(hb.jvp(dx), dagg), k                              # the record is still valid
         # each pair of setters, and the other kinds' entries under this path
         for f in (lambda: hb.jvp_shock(dx, None), lambda: hb.vjp_shock(yb, 2), lambda: hb.jvp_income(dx, None), lambda: hb.vjp_income(yb, 2)):
-            _raises(NOT_READY, f)
-        _raises(NOT_READY, hb.set_discount_path, np.full(P, c["args"][3]))
-        _raises(NOT_READY, hb.set_income_path, np.zeros((hb.n_e, P)))
+            C.raises(NOT_READY, f)
+        C.raises(NOT_READY, hb.set_discount_path, np.full(P, c["args"][3]))
+        C.raises(NOT_READY, hb.set_income_path, np.zeros((hb.n_e, P)))
         assert np.array_equal(hb.borrow_path, amin) and hb.discount_path is None and hb.income_path is None
         assert np.array_equal(hb.jvp(dx), dagg)
         hb.set_borrow_path(None)
-        _raises(NOT_READY, hb.jvp, dx)                                           # clearing drops the record too
+        C.raises(NOT_READY, hb.jvp, dx)                                           # clearing drops the record too
         hb.primal(x)
         for k, f in calls.items():
             f()
         for setter, path in ((hb.set_discount_path, np.full(P, c["args"][3])), (hb.set_income_path, np.zeros((hb.n_e, P)))):
             setter(path)
-            _raises(NOT_READY, hb.set_borrow_path, amin)
+            C.raises(NOT_READY, hb.set_borrow_path, amin)
             hb.primal(x)
-            _raises(NOT_READY, hb.jvp_borrow, dx, None)
-            _raises(NOT_READY, hb.vjp_borrow, yb, 2)
+            C.raises(NOT_READY, hb.jvp_borrow, dx, None)
+            C.raises(NOT_READY, hb.vjp_borrow, yb, 2)
             assert hb.borrow_path is None
             setter(None)
     finally:
@@ -414,29 +359,11 @@ def test_entries_defined_at_one_limit_are_refused_while_a_path_is_set(hank, orac
 
 def test_a_bad_path_changes_nothing_and_a_new_path_drops_the_record(hank, oracle_mod):
     c = R.borrow_case("ks", "gamma2", 33, 2, 4)
-    P = 3
-    hb = _ctx(hank, c, None)
-    try:
-        agg = hb.primal(c["x"])
-        dx, da = R.borrow_seeds(c, 3, 1)
-        dagg = hb.jvp_borrow(dx, da)
-        top = float(np.asarray(c["args"][0])[-1])
-        for bad in (np.nan, np.inf, -np.inf, np.nextafter(top, np.inf)):
-            am = c["amin"].copy()
-            am[1] = bad
-            _raises(BAD_ARG, hb.set_borrow_path, am)
-            assert np.array_equal(hb.borrow_path, c["amin"])
-            assert np.array_equal(hb.jvp_borrow(dx, da), dagg)                    # the record and the path in force are still valid
-        am = c["amin"].copy()
-        am[0] += 1e-3
-        hb.set_borrow_path(am)
-        _raises(NOT_READY, hb.jvp, dx)
-        _raises(NOT_READY, hb.jvp_borrow, dx, None)
-        _raises(NOT_READY, hb.vjp_borrow, np.ones((P, 1, 1)), 1)
-        _raises(NOT_READY, hb.dpolicy_seq, 3)
-        assert not np.array_equal(hb.primal(c["x"]), agg)
-    finally:
-        hb.close()
+    top = float(np.asarray(c["args"][0])[-1])
+    am = c["amin"].copy()
+    am[0] += 1e-3
+    C.bad_path_and_new_path(hank, K, c, bad=(np.nan, np.inf, -np.inf, np.nextafter(top, np.inf)), at=1, new=am, vjp=lambda hb: hb.vjp_borrow(np.ones((3, 1, 1)), 1),
+                            own_entry=True)
 
 
 def test_a_second_path_and_a_second_boundary_on_cached_graphs_and_the_dev_forms(hank, oracle_mod):
@@ -445,9 +372,9 @@ def test_a_second_path_and_a_second_boundary_on_cached_graphs_and_the_dev_forms(
     import torch
     c = R.borrow_case("hank", "gamma2", 33, 2, 4)
     P, nh, N = 3, c["n_het"], 3
-    hb = _ctx(hank, c, None)
+    hb = C.ctx(hank, K, c, None)
     try:
-        dx, da = R.borrow_seeds(c, N, 2)
+        dx, da = path_refs.seeds(K, c, N, 2)
         yb = np.random.default_rng(1).standard_normal((P, 2, N))
         am2 = c["amin"][::-1].copy()
         V2 = c["V"] * 1.01
@@ -455,11 +382,11 @@ def test_a_second_path_and_a_second_boundary_on_cached_graphs_and_the_dev_forms(
             hb.set_boundary(V, c["D"])
             hb.set_borrow_path(amin)
             hb.primal(c["x"])
-            J = R.oracle_borrow_jacobians(c["args"], c["x"], V, c["D"], amin, c["gamma"], nh)
+            J = path_refs.jacobians(K, c["args"], c["x"], V, c["D"], amin, c["gamma"], nh)
             dagg = hb.jvp_borrow(dx, da)
-            close(dagg, shock_linear(J, dx, da)[:, 0, :], what="hank_jvp_borrow on the cached graphs")
+            close(dagg, path_refs.linear(J, dx, da)[:, 0, :], what="hank_jvp_borrow on the cached graphs")
             xbar, abar = hb.vjp_borrow(yb, 2)
-            close(abar, shock_beta_bar(J[1], yb), what="hank_vjp_borrow on the cached graphs")
+            close(abar, path_refs.path_bar(J[1], yb), what="hank_vjp_borrow on the cached graphs")
             dev = lambda v: torch.tensor(np.asfortranarray(v).ravel(order="F"), device="cuda")      # noqa: E731
             d_dx, d_da, d_out = dev(dx), dev(da), torch.empty(P * N, dtype=torch.float64, device="cuda")
             hb.jvp_borrow_dev(d_dx.data_ptr(), d_da.data_ptr(), N, d_out.data_ptr())
@@ -476,24 +403,5 @@ def test_a_second_path_and_a_second_boundary_on_cached_graphs_and_the_dev_forms(
 
 def test_clone_carries_the_path_and_the_memo_does_not_serve_another(hank, oracle_mod):
     c = R.borrow_case("hank", "gamma2", 33, 2, 4)
-    hb = _ctx(hank, c, None, path=False)
-    try:
-        dx, _ = R.borrow_seeds(c, 3, 2)
-        paths = (c["amin"], c["amin"][::-1].copy())
-        out = []
-        for k, p in enumerate(paths):
-            hb.set_borrow_path(p)
-            agg, dagg = hb.primal_jvp(c["x"], dx)
-            ref = R.oracle_borrow_sweeps(c["args"], c["x"], c["V"], c["D"], p, c["gamma"], 2, dx=dx)
-            close(agg, ref["agg"][:, 0], what=f"path {k}: hank_primal_jvp value")
-            close(dagg, ref["dagg"][:, 0, :], what=f"path {k}: hank_primal_jvp partials")
-            out.append(agg)
-        assert not np.array_equal(out[0], out[1])
-        other = hb.clone()
-        try:
-            assert np.array_equal(other.borrow_path, paths[1])
-            assert np.array_equal(other.primal(c["x"]), out[1])
-        finally:
-            other.close()
-    finally:
-        hb.close()
+    ref = lambda k, p, dx: path_refs.oracle_path_sweeps(K, c["args"], c["x"], c["V"], c["D"], p, c["gamma"], 2, dx=dx)      # noqa: E731
+    C.memo_and_clone(hank, K, c, c["amin"][::-1].copy(), ref, hits=False)

@@ -1,5 +1,5 @@
 """The income path by productivity state on the device (hank_set_income_path, hank_jvp_income, hank_vjp_income, hank_fake_news_income,
-hank_get_het_outputs_income) through the C ABI, against tests/income_refs.oracle_income_sweeps — the CPU oracle's EGM step run once per
+hank_get_het_outputs_income) through the C ABI, against tests/path_refs.oracle_path_sweeps at tests/income_refs.KIND — the CPU oracle's EGM step run once per
 productivity state with the dual transfer (tr_t + y_t[e], dtr_t + dy_t[e]) and the columns assembled, which tests/test_income_host.py
 pins against a central difference of its own level.
 
@@ -16,44 +16,25 @@ import pytest
 import cases
 import fake_news_refs as FR
 import income_refs as R
+import path_checks as C
+import path_refs
 import ss_diff_cases as S
 from cases import close, jt
 from hank_amd.hip import _p
+from path_checks import BAD_ARG, NOT_READY, grid_cases
 
 pytestmark = pytest.mark.gpu
 
-GRID_CASES = [(f, name, n_a, n_e) for f in ("ks", "hank") for name in cases.ENTRY_CASES for n_a, n_e in cases.ENTRY_GRIDS]
-grid_cases = pytest.mark.parametrize("family,name,n_a,n_e", GRID_CASES)
-NOT_READY, BAD_ARG = 5, 2
-
-
-def _ctx(hank, c, schedule="launch", path=True):
-    hb = cases.raw_block(hank, c["args"], schedule, **c["env"])
-    hb.set_boundary(c["V"], c["D"])
-    assert hb.info()["record_diet"] == c["diet"]
-    if path:
-        hb.set_income_path(c["y"])
-    return hb
-
-
-def _raises(code, fn, *a, **kw):
-    from hank_amd.hip import HankHIPError
-    with pytest.raises(HankHIPError) as ei:
-        fn(*a, **kw)
-    assert ei.value.code == code, (ei.value.code, code, str(ei.value))
-
-
-def _args(c, path=True):
-    return (c["orc"], c["x"], c["V"], c["D"], c["y"] if path else None)
+K = R.KIND
 
 
 # ---- 1. the level -------------------------------------------------------------------------------------------------------------------
 def _level(hank, c, what, schedules=("launch", "xcd")):
-    ref = R.oracle_income_sweeps(*_args(c))
+    ref = path_refs.oracle_path_sweeps(*C.ref_args(K, c))
     P = c["x"].shape[1]
     got = {}
     for sched in schedules:
-        hb = _ctx(hank, c, sched)
+        hb = C.ctx(hank, K, c, sched)
         try:
             before = hb.stats()
             agg0 = hb.primal(c["x"])
@@ -83,30 +64,21 @@ def test_primal_at_a_path_matches_the_oracle_under_every_schedule(hank, oracle_m
         c = R.income_case(family, name, n_a, n_e, T)
         what = f"{family} {name} {n_a}x{n_e} T={T}"
         ref = _level(hank, c, what)
-        assert np.abs(ref["pol"] - R.oracle_income_sweeps(*_args(c, False))["pol"]).max() > 1e-3, what      # (the path moves the policy)
+        assert np.abs(ref["pol"] - path_refs.oracle_path_sweeps(*C.ref_args(K, c, False))["pol"]).max() > 1e-3, what      # (the path moves the policy)
 
 
 @grid_cases
 def test_a_path_of_zeros_gives_the_bits_of_no_path(hank, oracle_mod, family, name, n_a, n_e):
     for T in R.HORIZONS:
-        c = R.income_case(family, name, n_a, n_e, T)
-        hb = _ctx(hank, c, "launch", path=False)
-        try:
-            agg, het, pol = hb.primal(c["x"]), hb.het_outputs(2)[0], hb.policy_seq()
-            hb.set_income_path(np.zeros_like(c["y"]))
-            _raises(NOT_READY, hb.policy_seq)
-            assert np.array_equal(hb.primal(c["x"]), agg) and np.array_equal(hb.policy_seq(), pol), (family, name, n_a, n_e, T)
-            assert np.array_equal(hb.het_outputs(2)[0], het), (family, name, n_a, n_e, T)
-        finally:
-            hb.close()
+        C.neutral_path_gives_the_bits_of_no_path(hank, K, R.income_case(family, name, n_a, n_e, T), (family, name, n_a, n_e, T), het=2)
 
 
 # ---- 2. hank_jvp_income ---------------------------------------------------------------------------------------------------------------
 def _income_against_oracle(hb, c, tag, dx, dy, path):
-    a = _args(c, path)
+    a = C.ref_args(K, c, path)
     N = next(v.shape[-1] for v in (dx, dy) if v is not None)
-    ref = R.income_linear(R.oracle_income_jacobians(*a), dx, dy)
-    dpol = R.income_linear_policies(*a, dx, dy)
+    ref = path_refs.linear(path_refs.jacobians(*a), dx, dy)
+    dpol = path_refs.linear_policies(*a, dx=dx, dp=dy)
     close(hb.jvp_income(dx, dy), ref[:, 0, :], what=f"{tag} dagg")
     close(hb.dpolicy_seq(N).transpose(2, 0, 1, 3), dpol, what=f"{tag} dpolicy")
     _, dagg = hb.het_outputs(2, dx, dy=np.zeros((hb.n_e, hb.P, N)) if dy is None else dy)
@@ -118,23 +90,23 @@ def _income_against_oracle(hb, c, tag, dx, dy, path):
 def _jvp_income_case(hank, c, tag, widths=R.WIDTHS, t_only=True, schedule=None):
     P = c["x"].shape[1]
     for path in (True, False):
-        hb = _ctx(hank, c, schedule, path=path)
+        hb = C.ctx(hank, K, c, schedule, path=path)
         try:
             hb.primal(c["x"])
             tg = f"{tag} {'path' if path else 'no path'}"
             # the sweeps themselves once, against the linear reference every width uses
-            dx, dy = R.income_seeds(c, 3, 10)
-            own = R.oracle_income_sweeps(*_args(c, path), dx=dx, dy=dy)
-            lin = R.income_linear(R.oracle_income_jacobians(*_args(c, path)), dx, dy)
+            dx, dy = path_refs.seeds(K, c, 3, 10)
+            own = path_refs.oracle_path_sweeps(*C.ref_args(K, c, path), dx=dx, dpath=dy)
+            lin = path_refs.linear(path_refs.jacobians(*C.ref_args(K, c, path)), dx, dy)
             close(lin, own["dagg"], rel=1e-12, ab=0.0, what=f"{tg} the reference is linear")
             for N in widths:
-                dx, dy = R.income_seeds(c, N, 11 + N)
+                dx, dy = path_refs.seeds(K, c, N, 11 + N)
                 _income_against_oracle(hb, c, f"{tg} N={N} inputs and y", dx, dy, path)
                 _income_against_oracle(hb, c, f"{tg} N={N} y alone", None, dy, path)
                 _income_against_oracle(hb, c, f"{tg} N={N} inputs alone", dx, None, path)
             if t_only:
                 for t in sorted({0, P - 1}):
-                    dx, dy = R.income_seeds(c, 3, 13, t_only=t)
+                    dx, dy = path_refs.seeds(K, c, 3, 13, t_only=t)
                     _income_against_oracle(hb, c, f"{tg} N=3 y_{t} alone", None, dy, path)
             tm = hb.last_timings()
             assert tm["tangent_backward"]["launches"] == 2 * P + 3 and tm["tangent_forward"]["launches"] == P + 3, (tg, tm)
@@ -167,21 +139,7 @@ def test_jvp_income_where_the_seed_s_staging_does_not_fit(hank, oracle_mod):
 @grid_cases
 def test_jvp_income_without_an_income_seed_is_hank_jvp_bit_for_bit(hank, oracle_mod, family, name, n_a, n_e):
     for T in (2, 4):
-        c = R.income_case(family, name, n_a, n_e, T)
-        hb = _ctx(hank, c, "launch")
-        try:
-            hb.primal(c["x"])
-            out = np.empty((T - 1, 3), order="F")
-            assert hb._lib.hank_jvp_income(hb._ctx, None, None, 3, _p(out)) == BAD_ARG
-            for N in R.WIDTHS:
-                dx, _ = R.income_seeds(c, N, 5)
-                dagg, dpol = hb.jvp(dx), hb.dpolicy_seq(N)
-                het = hb.het_outputs(2, dx)[1]
-                for dy in (None, np.zeros((n_e, T - 1, N))):
-                    assert np.array_equal(hb.jvp_income(dx, dy), dagg) and np.array_equal(hb.dpolicy_seq(N), dpol), (family, name, n_a, n_e, T, N)
-                assert np.array_equal(hb.het_outputs(2, dx, dy=np.zeros((n_e, T - 1, N)))[1], het), (family, name, n_a, n_e, T, N)
-        finally:
-            hb.close()
+        C.no_seed_in_the_path_is_hank_jvp_bit_for_bit(hank, K, R.income_case(family, name, n_a, n_e, T), (family, name, n_a, n_e, T), R.WIDTHS, direct=True)
 
 
 # ---- 3. hank_vjp_income ----------------------------------------------------------------------------------------------------------------
@@ -189,11 +147,11 @@ def _vjp_income_case(hank, c, tag, widths=R.WIDTHS, schedule=None):
     P = c["x"].shape[1]
     rng = np.random.default_rng(P)
     for path in (True, False):
-        hb = _ctx(hank, c, schedule, path=path)
+        hb = C.ctx(hank, K, c, schedule, path=path)
         try:
             hb.primal(c["x"])
-            Jx, Jy = R.oracle_income_jacobians(*_args(c, path))
-            dx, dy = R.income_seeds(c, 3, 21)
+            Jx, Jy = path_refs.jacobians(*C.ref_args(K, c, path))
+            dx, dy = path_refs.seeds(K, c, 3, 21)
             hb.jvp_income(dx, dy)
             _, Jd = hb.het_outputs(2, dx, dy=dy)                                  # (P, 2, N)
             for M in widths:
@@ -204,14 +162,9 @@ def _vjp_income_case(hank, c, tag, widths=R.WIDTHS, schedule=None):
                     assert np.array_equal(xbar, hb.vjp(yb, n_het)), what
                     x2, y2 = hb.vjp_income(yb, n_het)
                     assert np.array_equal(x2, xbar) and np.array_equal(y2, ybar), what
-                    close(ybar, R.income_y_bar(Jy, yb), what=f"{what} y_bar")
+                    close(ybar, path_refs.path_bar(Jy, yb), what=f"{what} y_bar")
                     close(xbar, jt(Jx[:n_het], yb), what=f"{what} xhh_bar")
-                    lhs = np.einsum("tom,ton->mn", yb, Jd[:, :n_het, :])
-                    rhs = np.einsum("ktm,ktn->mn", xbar, dx) + np.einsum("etm,etn->mn", ybar, dy)
-                    scale = np.einsum("tom,ton->mn", np.abs(yb), np.abs(Jd[:, :n_het, :]))
-                    print(f"{what}: max |lhs - rhs| / scale = {np.max(np.abs(lhs - rhs) / scale):.3e}; |y_bar| {np.abs(ybar).max():.3e}")
-                    assert np.abs(ybar).max() > 1e-6, what
-                    assert np.all(np.abs(lhs - rhs) <= 1e-10 * scale), what
+                    C.transposed_identity(what, K, yb, Jd, xbar, dx, ybar, dy)
             tv = hb.last_vjp_timings()
             assert tv["sweep_b"]["launches"] == 2 * P + 3, tv
         finally:
@@ -241,7 +194,7 @@ def test_raw_grids_with_clamped_columns(hank, oracle_mod, econ):
         assert clamped[1].any(axis=0).all() and not clamped[2].any(), econ
     P, n_e = c["x"].shape[1], c["y"].shape[0]
     dy = np.eye(n_e * P).reshape((n_e, P, n_e * P), order="F")
-    dpol = R.income_linear_policies(*_args(c), None, dy)                        # [t, a, e, (e', s)]
+    dpol = path_refs.linear_policies(*C.ref_args(K, c), dp=dy)                        # [t, a, e, (e', s)]
     for t, a, e in zip(*np.nonzero(clamped)):
         assert not np.any(dpol[t, a, e]), (econ, t, a, e)
     _jvp_income_case(hank, c, f"raw {econ}", widths=(3, 33), t_only=False)
@@ -261,8 +214,8 @@ def test_income_jacobian_matches_the_reference_at_a_steady_record(hank, oracle_m
         x = FR.constant_path(c, P)
         hb.primal(x)
         J = income_jacobian(hb, 2)                                           # (2, P, n_e, P)
-        _, Jy = R.oracle_income_jacobians(c["orc"], x, c["V"], c["D"], None)
-        mass = R.oracle_income_sweeps(c["orc"], x, c["V"], c["D"])["mass"]
+        _, Jy = path_refs.jacobians(K, c["orc"], x, c["V"], c["D"], None)
+        mass = path_refs.oracle_path_sweeps(K, c["orc"], x, c["V"], c["D"])["mass"]
         for o in range(2):
             assert np.abs(Jy[:, o]).max() > 1e-3
             close(J[o], Jy[:, o], what=f"{econ} J_y of output {o}")
@@ -280,7 +233,7 @@ def test_income_jacobian_matches_the_reference_at_a_steady_record(hank, oracle_m
             close(J[o], cols[:, o, :].reshape(P, P, hb.n_e).transpose(0, 2, 1), what=f"{econ} J_y of output {o} against the unit columns")
         hb.set_income_path(np.zeros((hb.n_e, P)))
         hb.primal(x)
-        _raises(NOT_READY, hb.fake_news_income, 2)
+        C.raises(NOT_READY, hb.fake_news_income, 2)
     finally:
         hb.close()
 
@@ -292,7 +245,7 @@ def test_fake_news_with_fewer_states_than_inputs_on_a_fresh_context(hank, oracle
     c = R.two_state_hank()
     P = c["args"][6] - 1
     x = np.tile(c["x"][:, None], (1, P))
-    _, Jy = R.oracle_income_jacobians(c["orc"], x, c["V"], c["D"], None)
+    _, Jy = path_refs.jacobians(K, c["orc"], x, c["V"], c["D"], None)
     het = None
     for first in ("income", "shock", "het"):
         hb = cases.raw_block(hank, c["args"], None)
@@ -323,22 +276,22 @@ def test_a_batch_with_income_directions_carries_them(hank, oracle_mod):
     the inputs refuse the batch's tangents — with or without a path set — until hank_jvp makes another"""
     c = R.income_case("hank", "gamma2", 33, 2, 4)
     P, N = 3, 3
-    dx, dy = R.income_seeds(c, N, 4)
+    dx, dy = path_refs.seeds(K, c, N, 4)
     cons_group = (np.ones((33 * 2, 2)), np.array([1, 2], dtype=np.int32))
     for path in (False, True):
-        hb = _ctx(hank, c, None, path=path)
+        hb = C.ctx(hank, K, c, None, path=path)
         try:
             hb.set_het_outputs(4)
             hb.set_group_outputs(*cons_group)
             hb.primal(c["x"])
-            ref = R.income_linear(R.oracle_income_jacobians(*_args(c, path)), dx, dy)
+            ref = path_refs.linear(path_refs.jacobians(*C.ref_args(K, c, path)), dx, dy)
             hb.jvp_income(dx, dy)
             _, own = hb.het_outputs(2, dx)                                       # the batch's own dy
             _, given = hb.het_outputs(2, dx, dy=dy)
             assert np.array_equal(own, given), path
             close(own[:, 1, :], ref[:, 1, :], what=f"path={path}: consumption's tangent from the batch's own dy")
-            _raises(NOT_READY, hb.het_outputs, 3, dx)
-            _raises(NOT_READY, hb.group_outputs, dx)
+            C.raises(NOT_READY, hb.het_outputs, 3, dx)
+            C.raises(NOT_READY, hb.group_outputs, dx)
             hb.het_outputs(2)                                                    # the levels of outputs 0 and 1 are always served
             if not path:
                 hb.het_outputs(3)                                                # ... and every level and tangent where c is rebuilt rightly
@@ -347,10 +300,10 @@ def test_a_batch_with_income_directions_carries_them(hank, oracle_mod):
                 hb.het_outputs(3, dx)
                 hb.group_outputs(dx)
                 hb.jvp_income(dx, dy)
-                _raises(NOT_READY, hb.het_outputs, 3, dx)
+                C.raises(NOT_READY, hb.het_outputs, 3, dx)
                 hb.jvp(dx)
                 _, plain = hb.het_outputs(3, dx)
-                close(plain[:, 1, :], R.income_linear(R.oracle_income_jacobians(*_args(c, path)), dx, None)[:, 1, :], what="after hank_jvp: no direct term")
+                close(plain[:, 1, :], path_refs.linear(path_refs.jacobians(*C.ref_args(K, c, path)), dx, None)[:, 1, :], what="after hank_jvp: no direct term")
                 hb.group_outputs(dx)
         finally:
             hb.close()
@@ -397,91 +350,49 @@ def test_entries_that_rebuild_consumption_are_refused_while_a_path_is_set(hank, 
         hb.primal(x)
         dagg = hb.jvp(dx)
         for k, f in calls.items():
-            _raises(NOT_READY, f)
+            C.raises(NOT_READY, f)
             assert np.array_equal(hb.jvp(dx), dagg), k                              # the record is still valid
         assert np.array_equal(hb.income_path, y) and hb.discount_path is None
         grp, dgrp = hb.group_outputs(dx)                                          # the mass and policy bases read the record
         close(dgrp[:, 1, :], dagg, what="the policy base over every point is the aggregate's tangent")
         close(grp[:, 0], np.ones(P), what="the mass base over every point is one")
         hb.set_group_outputs(*cons_group)
-        _raises(NOT_READY, hb.group_outputs)
+        C.raises(NOT_READY, hb.group_outputs)
         assert np.array_equal(hb.jvp(dx), dagg)
         hb.backward_step(c["V"], c["x"])                                          # the step entries ignore the path
         hb.set_income_path(None)
-        _raises(NOT_READY, hb.jvp, dx)                                           # clearing drops the record too
+        C.raises(NOT_READY, hb.jvp, dx)                                           # clearing drops the record too
         hb.primal(x)
         hb.set_group_outputs(*mass_groups)
         del calls["set_discount_path"]
         for k, f in calls.items():
             f()
         hb.set_discount_path(np.full(P, c["args"][3]))
-        _raises(NOT_READY, hb.set_income_path, y)                                 # the two paths exclude each other
+        C.raises(NOT_READY, hb.set_income_path, y)                                 # the two paths exclude each other
         hb.primal(x)
-        _raises(NOT_READY, hb.jvp_income, dx, None)
-        _raises(NOT_READY, hb.vjp_income, yb, 2)
+        C.raises(NOT_READY, hb.jvp_income, dx, None)
+        C.raises(NOT_READY, hb.vjp_income, yb, 2)
     finally:
         hb.close()
 
 
 def test_a_bad_path_changes_nothing_and_a_new_path_drops_the_record(hank, oracle_mod):
     c = R.income_case("ks", "gamma2", 33, 2, 4)
-    P = 3
-    hb = _ctx(hank, c, None)
-    try:
-        agg = hb.primal(c["x"])
-        dx, dy = R.income_seeds(c, 3, 1)
-        dagg = hb.jvp_income(dx, dy)
-        for bad in (np.nan, np.inf, -np.inf):
-            y = c["y"].copy()
-            y[1, 1] = bad
-            _raises(BAD_ARG, hb.set_income_path, y)
-            assert np.array_equal(hb.income_path, c["y"])
-            assert np.array_equal(hb.jvp_income(dx, dy), dagg)                    # the record and the path in force are still valid
-        hb.set_income_path(c["y"] * 1.001)
-        _raises(NOT_READY, hb.jvp, dx)
-        _raises(NOT_READY, hb.jvp_income, dx, None)
-        _raises(NOT_READY, hb.vjp_income, np.ones((P, 1)))
-        _raises(NOT_READY, hb.dpolicy_seq, 3)
-        assert not np.array_equal(hb.primal(c["x"]), agg)
-    finally:
-        hb.close()
+    C.bad_path_and_new_path(hank, K, c, bad=(np.nan, np.inf, -np.inf), at=(1, 1), new=c["y"] * 1.001, vjp=lambda hb: hb.vjp_income(np.ones((3, 1))), own_entry=True)
 
 
 def test_the_primal_memo_does_not_serve_another_path_and_clone_carries_the_path(hank, oracle_mod):
     c = R.income_case("hank", "gamma2", 33, 2, 4)
-    hb = _ctx(hank, c, None, path=False)
-    try:
-        dx, _ = R.income_seeds(c, 3, 2)
-        paths = (c["y"], -c["y"])
-        out = []
-        for k, p in enumerate(paths):
-            hb.set_income_path(p)
-            agg, dagg = hb.primal_jvp(c["x"], dx)
-            ref = R.oracle_income_sweeps(c["orc"], c["x"], c["V"], c["D"], p, dx=dx)
-            close(agg, ref["agg"][:, 0], what=f"path {k}: hank_primal_jvp value")
-            close(dagg, ref["dagg"][:, 0, :], what=f"path {k}: hank_primal_jvp partials")
-            out.append(agg)
-        assert not np.array_equal(out[0], out[1])
-        hits = hb.stats()["primal_memo_hits"]
-        agg, _ = hb.primal_jvp(c["x"], dx)                                        # the same x under the same path: the memo serves it
-        assert hb.stats()["primal_memo_hits"] == hits + 1 and np.array_equal(agg, out[1])
-        other = hb.clone()
-        try:
-            assert np.array_equal(other.income_path, paths[1])
-            assert np.array_equal(other.primal(c["x"]), out[1])
-        finally:
-            other.close()
-    finally:
-        hb.close()
+    C.memo_and_clone(hank, K, c, -c["y"], lambda k, p, dx: path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], p, dx=dx), hits=True)
 
 
 def test_a_forced_persistent_schedule_runs_the_launches_at_a_path(hank, oracle_mod):
     c = R.income_case("ks", "gamma2", 130, 3, 12)
-    hb = _ctx(hank, c, "xcd")
+    hb = C.ctx(hank, K, c, "xcd")
     try:
         hb.primal(c["x"])
-        dx, dy = R.income_seeds(c, 33, 3)
-        ref = R.income_linear(R.oracle_income_jacobians(*_args(c)), dx, None)
+        dx, dy = path_refs.seeds(K, c, 33, 3)
+        ref = path_refs.linear(path_refs.jacobians(*C.ref_args(K, c)), dx, None)
         close(hb.jvp(dx), ref[:, 0, :], what="hank_jvp at a path under HANK_SCHEDULE=xcd")
         assert hb.info()["last_tangent_family_name"] == cases.FAMILY["launch"], hb.info()
         agg, dagg = hb.primal_jvp(c["x"] * 1.0, dx)

@@ -2,10 +2,10 @@
 csrc/hank_income.h) where tests/test_gpu_income.py does not take them: every block shape of k_inc_ybar, every n_e up to the bound the
 seed kernel unrolls to, every lane geometry of the direction widths, the raw grids with deep clamps and more than 256 rows, the
 device-pointer forms, and the state the entries share with hank_vjp and keep across a new path or boundary. The reference is always the
-CPU oracle's dense pair (Jx, Jy) of tests/income_refs.oracle_income_jacobians — unit tangents through the oracle's loop at the path,
+CPU oracle's dense pair (Jx, Jy) of tests/path_refs.jacobians at tests/income_refs.KIND — unit tangents through the oracle's loop at the path,
 which tests/test_income_host.py pins against the loop with random seeds — never another device run: the tangent map is linear, so
     dagg = Jx dx + Jy dy,    xhh_bar = jt(Jx[:n_het], yb),    y_bar[e, s, m] = sum_{t,o} Jy[t, o, e, s] yb[t, o, m]
-hold at every width, and the policy's partials are income_linear_policies' over the full width. Comparisons between two device runs
+hold at every width, and the policy's partials are path_refs.linear_policies' over the full width. Comparisons between two device runs
 are stated as what they are (bits against hank_vjp, one column in different batches, the transposed identity, host against device
 pointers) and come on top of the oracle check.
 
@@ -41,6 +41,8 @@ import pytest
 import cases
 import fake_news_refs as FR
 import income_refs as R
+import path_refs
+import shock_refs
 import ss_diff_cases as S
 from cases import jt
 from test_gpu_vjp_variants import _same_column
@@ -67,7 +69,7 @@ def _report(sec):
 def _refs(c, y="y", D=None):
     """(the oracle's arguments, (Jx, Jy), (J2x, J2y)) of case c at its own path, at none (None) or at a given array; D: another D_0"""
     a = (c["orc"], c["x"], c["V"], c["D"] if D is None else D, c["y"] if isinstance(y, str) else y)
-    return a, R.oracle_income_jacobians(*a), R.oracle_income_grid_jacobians(*a)
+    return a, path_refs.jacobians(R.KIND, *a), path_refs.grid_jacobians(R.KIND, *a)
 
 
 def _ctx(hank, c, schedule="launch", y="y"):
@@ -92,7 +94,7 @@ def _vjp_against_oracle(sec, hb, J, yb, what):
     xbar, ybar = hb.vjp_income(yb, n_het)
     assert xbar.shape == (Jx.shape[2], Jx.shape[1], M) and ybar.shape == (Jy.shape[2], Jy.shape[3], M), (what, xbar.shape, ybar.shape)
     _close(sec, xbar, jt(Jx[:n_het], yb), f"{what} xhh_bar")
-    _close(sec, ybar, R.income_y_bar(Jy, yb), f"{what} y_bar")
+    _close(sec, ybar, path_refs.path_bar(Jy, yb), f"{what} y_bar")
     assert np.array_equal(xbar, hb.vjp(yb, n_het)), f"{what}: xhh_bar is hank_vjp's bit for bit"
     return xbar, ybar
 
@@ -103,16 +105,16 @@ def _jvp_against_oracle(sec, hb, a, J, J2, dx, dy, what, policies=True):
     launches, no fallback. a: the oracle's arguments (`_refs`)"""
     N = next(v.shape[-1] for v in (dx, dy) if v is not None)
     P = a[1].shape[1]
-    ref = R.income_linear(J, dx, dy)
+    ref = path_refs.linear(J, dx, dy)
     dagg = hb.jvp_income(dx, dy)
     assert dagg.shape == (P, N), (what, dagg.shape)
     _close(sec, dagg, ref[:, 0, :], f"{what} dagg")
     _, dhet = hb.het_outputs(2, dx, dy=np.zeros((hb.n_e, P, N)) if dy is None else dy)
     for o in range(2):
         _close(sec, dhet[:, o, :], ref[:, o, :], f"{what} output {o}")
-    _close(sec, hb.grid_aggregates(N)[1], R.income_grid_linear(J2, dx, dy), f"{what} grid aggregate")
+    _close(sec, hb.grid_aggregates(N)[1], path_refs.grid_linear(J2, dx, dy), f"{what} grid aggregate")
     if policies:
-        _close(sec, hb.dpolicy_seq(N).transpose(2, 0, 1, 3), R.income_linear_policies(*a, dx, dy), f"{what} dpolicy")
+        _close(sec, hb.dpolicy_seq(N).transpose(2, 0, 1, 3), path_refs.linear_policies(R.KIND, *a, dx=dx, dp=dy), f"{what} dpolicy")
     assert hb.info()["last_tangent_family_name"] == LAUNCH and hb.stats()["fallbacks"] == 0, (what, hb.info(), hb.stats())
 
 
@@ -158,7 +160,7 @@ def test_vjp_income_at_every_cotangent_geometry(hank, oracle_mod, n_a):
 # ---- B. n_e -----------------------------------------------------------------------------------------------------------------------------
 def _level(hank, c, what):
     """the level at the path under both schedules (tests/test_gpu_income._level): against the oracle, `xcd` against `launch` in bits"""
-    ref = R.oracle_income_sweeps(c["orc"], c["x"], c["V"], c["D"], c["y"])
+    ref = path_refs.oracle_path_sweeps(R.KIND, c["orc"], c["x"], c["V"], c["D"], c["y"])
     P = c["x"].shape[1]
     got = {}
     for sched in ("launch", "xcd"):
@@ -283,13 +285,13 @@ def test_clamped_prefix_top_clamp_and_long_segments_under_an_income_path(hank, o
     n_e, P = c["y"].shape
     assert P == cases.EDGE_P and n_e * P == 27
     a, J, J2 = _refs(c)
-    ref = R.oracle_income_sweeps(*a)
+    ref = path_refs.oracle_path_sweeps(R.KIND, *a)
     rng = np.random.default_rng(43)
     hb = _ctx(hank, c)
     try:
         assert hb.stats()["fallbacks"] == 0 and hb.n_a == c["grid"].size
         pol = hb.policy_seq().transpose(2, 0, 1)
-        R.check_income_edges(name, c["grid"], pol)                                   # the device's policy holds the edges too
+        shock_refs.check_path_edges(name, c["grid"], pol)                                   # the device's policy holds the edges too
         _close("D", pol, ref["pol"], f"{name} policy")
         _close("D", hb.het_outputs(2)[0][:, 1], ref["agg"][:, 1], f"{name} consumption (holds sum_e y_t[e] m_t[e])")
         # a clamped point's policy does not move with any y_s[e']: exact zeros in the n_e P unit directions
@@ -299,7 +301,7 @@ def test_clamped_prefix_top_clamp_and_long_segments_under_an_income_path(hank, o
         assert clamped.any(axis=1).any(), name
         dpol = hb.dpolicy_seq(n_e * P).transpose(2, 0, 1, 3)
         assert not np.any(dpol[clamped]) and np.any(dpol[~clamped]), name
-        err = np.abs(dpol - R.income_linear_policies(*a, None, unit))                # measured, not asserted (the docstring)
+        err = np.abs(dpol - path_refs.linear_policies(R.KIND, *a, dp=unit))                # measured, not asserted (the docstring)
         k = tuple(int(q) for q in np.unravel_index(np.argmax(err), err.shape))
         m0 = min(max(int(np.searchsorted(c["grid"], pol[k[:3]])), 1), c["grid"].size - 1)
         print(f"{name}: the policy's partials point by point, max err {err.max():.3e} at (t, a, e, direction) = {k}, where the policy "
@@ -431,14 +433,14 @@ def test_vjp_income_shares_its_state_with_vjp_and_follows_a_new_path_and_a_new_b
             second[tag] = new = _vjp_against_oracle("F", hb, Jr, yM, f"{tag} second path")
             assert not np.array_equal(new[0], old[0]) and not np.array_equal(new[1], old[1]), tag
         cons = hb.het_outputs(2)[0][:, 1]
-        _close("F", cons, R.oracle_income_sweeps(*a2)["agg"][:, 1], "second path: consumption")
+        _close("F", cons, path_refs.oracle_path_sweeps(R.KIND, *a2)["agg"][:, 1], "second path: consumption")
         # 4. a second boundary on the cached widths: the column masses m_t[e] are the new record's
         D2 = R.rescaled_D0(c)
         a3, Jd, _ = _refs(c, y2, D2)
-        ref2, ref3 = R.oracle_income_sweeps(*a2), R.oracle_income_sweeps(*a3)
+        ref2, ref3 = path_refs.oracle_path_sweeps(R.KIND, *a2), path_refs.oracle_path_sweeps(R.KIND, *a3)
         assert np.abs(ref3["mass"] - ref2["mass"]).max() > 0.1
         direct = lambda m: m.T[:, :, None] * y34[None, :, 1, :]                   # noqa: E731  (n_e, P, M): m_t[e] yb1_t[m]
-        assert np.abs(direct(ref3["mass"]) - direct(ref2["mass"])).max() > 1e-2 * np.abs(R.income_y_bar(Jd[1], y34)).max()
+        assert np.abs(direct(ref3["mass"]) - direct(ref2["mass"])).max() > 1e-2 * np.abs(path_refs.path_bar(Jd[1], y34)).max()
         hb.set_boundary(c["V"], D2)
         hb.primal(c["x"])
         for yM, tag in ((y34, "M=34"), (y66, "M=66")):
@@ -493,7 +495,7 @@ def test_income_jacobian_matches_the_oracle_at_short_horizons(hank, oracle_mod, 
     c = S.case(econ)
     P = T - 1
     x = FR.constant_path(c, P)
-    _, Jy = R.oracle_income_jacobians(c["orc"], x, c["V"], c["D"], None)
+    _, Jy = path_refs.jacobians(R.KIND, c["orc"], x, c["V"], c["D"], None)
     hb = cases.raw_block(hank, c["args"][:6] + (T,) + c["args"][7:], None)
     try:
         hb.set_boundary(c["V"], c["D"])

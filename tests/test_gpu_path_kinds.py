@@ -15,6 +15,7 @@ import pytest
 
 import cases
 import income_refs as IR
+import path_refs
 import shock_refs as SR
 import ss_diff_cases as S
 from cases import close
@@ -165,8 +166,8 @@ def test_switching_kinds_on_one_context(hank, oracle_mod, econ):
 
         first, grew = primal()
         assert grew == 0, grew
-        ref_beta = SR.oracle_shock_sweeps(orc, x, V, D, c["path"], c["gamma"], 2)
-        ref_y = IR.oracle_income_sweeps(orc, x, V, D, c["y"])
+        ref_beta = path_refs.oracle_path_sweeps(SR.KIND, orc, x, V, D, c["path"], c["gamma"], 2)
+        ref_y = path_refs.oracle_path_sweeps(IR.KIND, orc, x, V, D, c["y"])
         grown = []
         for _ in range(2):      # (the second round: both kinds' graphs are there)
             hb.set_discount_path(c["path"])

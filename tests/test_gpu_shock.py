@@ -1,5 +1,5 @@
 """The discount-factor path on the device (hank_set_discount_path, hank_jvp_shock, hank_vjp_shock, hank_fake_news_shock) through the C
-ABI, against tests/shock_refs.oracle_shock_sweeps — the CPU oracle's loop with beta = beta_t per period and the value's partials
+ABI, against tests/path_refs.oracle_path_sweeps at tests/shock_refs.KIND — the CPU oracle's loop with beta = beta_t per period and the value's partials
 augmented by V dbeta_t / beta_t, which tests/test_shock_host.py pins against a central difference of its own level.
 
 Shapes: the grids of cases.ENTRY_GRIDS — (33, 2): two primal blocks, the second holding one row; (130, 3) — both families, every gamma
@@ -14,36 +14,26 @@ import pytest
 
 import cases
 import fake_news_refs as FR
+import path_checks as C
+import path_refs
 import shock_refs as R
 import ss_diff_cases as S
 from cases import close
-from hank_amd.hip import _p
+from path_checks import NOT_READY, grid_cases
 
 pytestmark = pytest.mark.gpu
 
-GRID_CASES = [(f, name, n_a, n_e) for f in ("ks", "hank") for name in cases.ENTRY_CASES for n_a, n_e in cases.ENTRY_GRIDS]
-grid_cases = pytest.mark.parametrize("family,name,n_a,n_e", GRID_CASES)
-NOT_READY, BAD_ARG = 5, 2
+K = R.KIND
 _REF = {}
 
 
-def _ctx(hank, c, schedule="launch", path=True):
-    hb = cases.raw_block(hank, c["args"], schedule, **c["env"])
-    hb.set_boundary(c["V"], c["D"])
-    hb.set_het_outputs(c["n_het"])
-    assert hb.info()["record_diet"] == c["diet"]
-    if path:
-        hb.set_discount_path(c["path"])
-    return hb
-
-
 def _ref(c, key, **kw):
-    """oracle_shock_sweeps of case c, once per session and key; path: the beta path (None: the model's constant)"""
+    """path_refs.oracle_path_sweeps of case c, once per session and key; path: the beta path (None: the model's constant)"""
     k = (id(c), key)
     if k not in _REF:
         P = c["x"].shape[1]
         path = kw.pop("path", c["path"])
-        _REF[k] = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], np.full(P, c["beta"]) if path is None else path, c["gamma"], c["n_het"], **kw)
+        _REF[k] = path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], np.full(P, c["beta"]) if path is None else path, c["gamma"], c["n_het"], **kw)
     return _REF[k]
 
 
@@ -56,13 +46,6 @@ def _groups(c):
     return W.reshape((n_a * n_e, 2), order="F"), np.array([1, 2], dtype=np.int32)
 
 
-def _raises(code, fn, *a, **kw):
-    from hank_amd.hip import HankHIPError
-    with pytest.raises(HankHIPError) as ei:
-        fn(*a, **kw)
-    assert ei.value.code == code, (ei.value.code, code, str(ei.value))
-
-
 # ---- 1. the level -------------------------------------------------------------------------------------------------------------------
 @grid_cases
 def test_primal_at_a_path_matches_the_oracle_under_every_schedule(hank, oracle_mod, family, name, n_a, n_e):
@@ -72,7 +55,7 @@ def test_primal_at_a_path_matches_the_oracle_under_every_schedule(hank, oracle_m
         what = f"{family} {name} {n_a}x{n_e} T={T}"
         got = {}
         for sched in ("launch", "xcd", "wide"):
-            hb = _ctx(hank, c, sched)
+            hb = C.ctx(hank, K, c, sched)
             try:
                 before = hb.stats()
                 agg0 = hb.primal(c["x"])
@@ -97,22 +80,14 @@ def test_primal_at_a_path_matches_the_oracle_under_every_schedule(hank, oracle_m
 @grid_cases
 def test_a_constant_path_gives_the_bits_of_no_path(hank, oracle_mod, family, name, n_a, n_e):
     for T in R.HORIZONS:
-        c = R.shock_case(family, name, n_a, n_e, T)
-        hb = _ctx(hank, c, "launch", path=False)
-        try:
-            agg, pol = hb.primal(c["x"]), hb.policy_seq()
-            hb.set_discount_path(np.full(T - 1, c["beta"]))
-            _raises(NOT_READY, hb.policy_seq)
-            assert np.array_equal(hb.primal(c["x"]), agg) and np.array_equal(hb.policy_seq(), pol), (family, name, n_a, n_e, T)
-        finally:
-            hb.close()
+        C.neutral_path_gives_the_bits_of_no_path(hank, K, R.shock_case(family, name, n_a, n_e, T), (family, name, n_a, n_e, T))
 
 
 # ---- 2. hank_jvp at a beta-path record ----------------------------------------------------------------------------------------------
 def _jvp_at_path(hank, c, sched, N, what):
-    y, _ = R.shock_seeds(c, N, 7)
-    ref = _ref(c, ("inputs", N), y=y)
-    hb = _ctx(hank, c, sched)
+    y, _ = path_refs.seeds(K, c, N, 7)
+    ref = _ref(c, ("inputs", N), dx=y)
+    hb = C.ctx(hank, K, c, sched)
     try:
         hb.primal(c["x"])
         close(hb.jvp(y), ref["dagg"][:, 0, :], what=f"{what} hank_jvp")
@@ -145,7 +120,7 @@ def test_jvp_at_the_width_of_the_wide_family(hank, oracle_mod):
 
 # ---- 3. hank_jvp_shock ----------------------------------------------------------------------------------------------------------------
 def _shock_against_oracle(hb, c, tag, N, y, db, seed_key, path):
-    ref = _ref(c, (seed_key, N, path is None), y=y, dbeta=db, groups=_groups(c), path=path)
+    ref = _ref(c, (seed_key, N, path is None), dx=y, dpath=db, groups=_groups(c), path=path)
     P, n_hh = c["x"].shape[1], c["x"].shape[0]
     yz = np.zeros((n_hh, P, N)) if y is None else y
     close(hb.jvp_shock(y, db), ref["dagg"][:, 0, :], what=f"{tag} dagg")
@@ -167,18 +142,18 @@ def test_jvp_shock_matches_the_oracle(hank, oracle_mod, family, name, n_a, n_e):
         c = R.shock_case(family, name, n_a, n_e, T)
         P = T - 1
         for path in (c["path"], None):
-            hb = _ctx(hank, c, None, path=path is not None)
+            hb = C.ctx(hank, K, c, None, path=path is not None)
             try:
                 hb.set_group_outputs(*_groups(c))
                 hb.primal(c["x"])
                 tag = f"{family} {name} {n_a}x{n_e} T={T} {'path' if path is not None else 'constant beta'}"
                 for N in (1, 33):
-                    y, db = R.shock_seeds(c, N, 11)
+                    y, db = path_refs.seeds(K, c, N, 11)
                     _shock_against_oracle(hb, c, f"{tag} N={N} inputs and beta", N, y, db, "both", path)
-                y, db = R.shock_seeds(c, 3, 12)
+                y, db = path_refs.seeds(K, c, 3, 12)
                 _shock_against_oracle(hb, c, f"{tag} N=3 beta alone", 3, None, db, "beta", path)
                 for t_only in sorted({0, P - 1}):
-                    y, db = R.shock_seeds(c, 3, 13, t_only=t_only)
+                    y, db = path_refs.seeds(K, c, 3, 13, t_only=t_only)
                     _shock_against_oracle(hb, c, f"{tag} N=3 beta_{t_only} alone", 3, y, db, ("only", t_only), path)
                 tm = hb.last_timings()
                 assert tm["tangent_backward"]["launches"] == 2 * P + 3 and tm["tangent_forward"]["launches"] == P + 3, (tag, tm)
@@ -190,19 +165,7 @@ def test_jvp_shock_matches_the_oracle(hank, oracle_mod, family, name, n_a, n_e):
 @grid_cases
 def test_jvp_shock_without_a_beta_seed_is_hank_jvp_bit_for_bit(hank, oracle_mod, family, name, n_a, n_e):
     for T in (2, 4):
-        c = R.shock_case(family, name, n_a, n_e, T)
-        hb = _ctx(hank, c, "launch")
-        try:
-            hb.primal(c["x"])
-            out = np.empty((T - 1, 3), order="F")
-            assert hb._lib.hank_jvp_shock(hb._ctx, None, None, 3, _p(out)) == BAD_ARG
-            for N in R.WIDTHS:
-                y, _ = R.shock_seeds(c, N, 5)
-                dagg, dpol = hb.jvp(y), hb.dpolicy_seq(N)
-                for db in (None, np.zeros((T - 1, N))):
-                    assert np.array_equal(hb.jvp_shock(y, db), dagg) and np.array_equal(hb.dpolicy_seq(N), dpol), (family, name, n_a, n_e, T, N)
-        finally:
-            hb.close()
+        C.no_seed_in_the_path_is_hank_jvp_bit_for_bit(hank, K, R.shock_case(family, name, n_a, n_e, T), (family, name, n_a, n_e, T), R.WIDTHS)
 
 
 # ---- 4. hank_vjp_shock ------------------------------------------------------------------------------------------------------------------
@@ -213,10 +176,10 @@ def test_vjp_shock_is_the_transpose_of_jvp_shock(hank, oracle_mod, family, name,
         P, nh, N = T - 1, c["n_het"], 3
         rng = np.random.default_rng(T)
         for with_path in (True, False):
-            hb = _ctx(hank, c, None, path=with_path)
+            hb = C.ctx(hank, K, c, None, path=with_path)
             try:
                 hb.primal(c["x"])
-                y, db = R.shock_seeds(c, N, 21)
+                y, db = path_refs.seeds(K, c, N, 21)
                 hb.jvp_shock(y, db)
                 _, Jy = hb.het_outputs(nh, y)                                  # (P, n_het, N)
                 for M in R.WIDTHS:
@@ -227,12 +190,7 @@ def test_vjp_shock_is_the_transpose_of_jvp_shock(hank, oracle_mod, family, name,
                         assert np.array_equal(xbar, hb.vjp_het(yb, n_het)), what
                         x2, b2 = hb.vjp_shock(yb, n_het)
                         assert np.array_equal(x2, xbar) and np.array_equal(b2, bbar), what
-                        lhs = np.einsum("tom,ton->mn", yb, Jy[:, :n_het, :])
-                        rhs = np.einsum("ktm,ktn->mn", xbar, y) + np.einsum("tm,tn->mn", bbar, db)
-                        scale = np.einsum("tom,ton->mn", np.abs(yb), np.abs(Jy[:, :n_het, :]))
-                        print(f"{what}: max |lhs - rhs| / scale = {np.max(np.abs(lhs - rhs) / scale):.3e}; |beta_bar| {np.abs(bbar).max():.3e}")
-                        assert np.abs(bbar).max() > 1e-6, what
-                        assert np.all(np.abs(lhs - rhs) <= 1e-10 * scale), what
+                        C.transposed_identity(what, K, yb, Jy, xbar, y, bbar, db)
                 tv = hb.last_vjp_timings()
                 assert tv["sweep_b"]["launches"] == 2 * P + 3, tv
             finally:
@@ -260,7 +218,7 @@ def test_shock_jacobian_matches_the_unit_columns(hank, oracle_mod, econ, T):
         for n in range(1, nh):
             assert np.array_equal(shock_jacobian(hb, n), J[:n])
         hb.set_discount_path(np.full(P, c["args"][3]))
-        _raises(NOT_READY, hb.fake_news_shock, nh)
+        C.raises(NOT_READY, hb.fake_news_shock, nh)
     finally:
         hb.close()
 
@@ -291,9 +249,9 @@ def test_entries_defined_at_one_beta_are_refused_while_a_path_is_set(hank, oracl
         hb.set_discount_path(np.full(P, c["args"][3] * 0.999))
         hb.primal(x)
         for k, f in calls.items():
-            _raises(NOT_READY, f)
+            C.raises(NOT_READY, f)
         hb.set_discount_path(None)
-        _raises(NOT_READY, hb.jvp, np.zeros((hb.n_hh, P, 1)))                   # clearing drops the record too
+        C.raises(NOT_READY, hb.jvp, np.zeros((hb.n_hh, P, 1)))                   # clearing drops the record too
         hb.primal(x)
         for k, f in calls.items():
             f()
@@ -303,51 +261,9 @@ def test_entries_defined_at_one_beta_are_refused_while_a_path_is_set(hank, oracl
 
 def test_a_bad_path_changes_nothing_and_a_new_path_drops_the_record(hank, oracle_mod):
     c = R.shock_case("ks", "gamma2", 33, 2, 4)
-    P = 3
-    hb = _ctx(hank, c, None)
-    try:
-        agg = hb.primal(c["x"])
-        y, _ = R.shock_seeds(c, 3, 1)
-        dagg = hb.jvp(y)
-        for bad in (0.0, -0.9, np.nan, np.inf):
-            b = c["path"].copy()
-            b[1] = bad
-            _raises(BAD_ARG, hb.set_discount_path, b)
-            assert np.array_equal(hb.discount_path, c["path"])
-            assert np.array_equal(hb.jvp(y), dagg)                               # the record and the path in force are still valid
-        hb.set_discount_path(c["path"] * 1.001)
-        _raises(NOT_READY, hb.jvp, y)
-        _raises(NOT_READY, hb.jvp_shock, y, None)
-        _raises(NOT_READY, hb.vjp, np.ones((P, 1)))
-        _raises(NOT_READY, hb.dpolicy_seq, 3)
-        assert not np.array_equal(hb.primal(c["x"]), agg)
-    finally:
-        hb.close()
+    C.bad_path_and_new_path(hank, K, c, bad=(0.0, -0.9, np.nan, np.inf), at=1, new=c["path"] * 1.001, vjp=lambda hb: hb.vjp(np.ones((3, 1))), own_entry=False)
 
 
 def test_the_primal_memo_does_not_serve_another_path_and_clone_carries_the_path(hank, oracle_mod):
     c = R.shock_case("hank", "gamma2", 33, 2, 4)
-    hb = _ctx(hank, c, None, path=False)
-    try:
-        y, _ = R.shock_seeds(c, 3, 2)
-        paths = (c["path"], c["path"][::-1].copy())
-        out = []
-        for k, p in enumerate(paths):
-            hb.set_discount_path(p)
-            agg, dagg = hb.primal_jvp(c["x"], y)
-            ref = _ref(c, ("memo", k), y=y, path=p)
-            close(agg, ref["agg"][:, 0], what=f"path {k}: hank_primal_jvp value")
-            close(dagg, ref["dagg"][:, 0, :], what=f"path {k}: hank_primal_jvp partials")
-            out.append(agg)
-        assert not np.array_equal(out[0], out[1])
-        hits = hb.stats()["primal_memo_hits"]
-        agg, _ = hb.primal_jvp(c["x"], y)                                        # the same x under the same path: the memo serves it
-        assert hb.stats()["primal_memo_hits"] == hits + 1 and np.array_equal(agg, out[1])
-        other = hb.clone()
-        try:
-            assert np.array_equal(other.discount_path, paths[1])
-            assert np.array_equal(other.primal(c["x"]), out[1])
-        finally:
-            other.close()
-    finally:
-        hb.close()
+    C.memo_and_clone(hank, K, c, c["path"][::-1].copy(), lambda k, p, y: _ref(c, ("memo", k), dx=y, path=p), hits=True)

@@ -1,7 +1,7 @@
 """The discount-path entries (hank_jvp_shock, hank_vjp_shock, hank_fake_news_shock and their _dev forms; csrc/hank_shock.h) where
 tests/test_gpu_shock.py does not take them: every lane geometry of the cotangent and direction widths, every n_e, the raw grids with
 deep clamps and long segments, the device-pointer forms and the state the entries share with hank_vjp_het. The reference is always the
-CPU oracle's dense pair (Jx, Jb) of tests/shock_refs.oracle_shock_jacobians — unit tangents through the oracle's loop at the path, which
+CPU oracle's dense pair (Jx, Jb) of tests/path_refs.jacobians at tests/shock_refs.KIND — unit tangents through the oracle's loop at the path, which
 tests/test_shock_host.py pins against the loop with random seeds — never another device run: the tangent map is linear, so
     dagg = Jx y + Jb dbeta,    xhh_bar = jt(Jx[:n_het], yb),    beta_bar[s, m] = sum_{t,o} Jb[t, o, s] yb[t, o, m]
 hold at every width. Comparisons between two device runs are stated as what they are (bits against hank_vjp_het, one column in
@@ -31,6 +31,7 @@ import pytest
 
 import cases
 import fake_news_refs as FR
+import path_refs
 import shock_refs as R
 import ss_diff_cases as S
 from cases import jt
@@ -60,7 +61,7 @@ def _refs(c, path="path"):
     P = c["x"].shape[1]
     bt = c["path"] if isinstance(path, str) else np.full(P, c["beta"]) if path is None else np.asarray(path)
     a = (c["orc"], c["x"], c["V"], c["D"], bt, c["gamma"], c["n_het"])
-    return bt, R.oracle_shock_jacobians(*a), R.oracle_shock_grid_jacobians(*a)
+    return bt, path_refs.jacobians(R.KIND, *a), path_refs.grid_jacobians(R.KIND, *a)
 
 
 def _ctx(hank, c, schedule="launch", path="path"):
@@ -86,7 +87,7 @@ def _vjp_against_oracle(sec, hb, J, yb, what):
     xbar, bbar = hb.vjp_shock(yb, n_het)
     assert xbar.shape == (Jx.shape[2], Jx.shape[1], M) and bbar.shape == (Jx.shape[1], M), (what, xbar.shape, bbar.shape)
     _close(sec, xbar, jt(Jx[:n_het], yb), f"{what} xhh_bar")
-    _close(sec, bbar, R.shock_beta_bar(Jb, yb), f"{what} beta_bar")
+    _close(sec, bbar, path_refs.path_bar(Jb, yb), f"{what} beta_bar")
     assert np.array_equal(xbar, hb.vjp_het(yb, n_het)), f"{what}: xhh_bar is hank_vjp_het's bit for bit"
     return xbar, bbar
 
@@ -95,7 +96,7 @@ def _jvp_against_oracle(sec, hb, c, J, J2, y, db, what):
     """hank_jvp_shock on y (n_hh, P, N) or None and db (P, N) or None: the aggregate, every output and the grid aggregate against
     the linear reference; served by the launches, no fallback"""
     N = next(v.shape[-1] for v in (y, db) if v is not None)
-    ref = R.shock_linear(J, y, db)
+    ref = path_refs.linear(J, y, db)
     dagg = hb.jvp_shock(y, db)
     assert dagg.shape == (c["x"].shape[1], N), (what, dagg.shape)
     _close(sec, dagg, ref[:, 0, :], f"{what} dagg")
@@ -172,7 +173,7 @@ def test_jvp_shock_at_every_direction_geometry(hank, oracle_mod, n_a):
     bt, J, J2 = _refs(c)
     y, db = _seeds(c, max(GEOM_N), n_a)
     k = cases.N_ORACLE
-    loop = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], bt, c["gamma"], c["n_het"], y=y[:, :, :k], dbeta=db[:, :k])
+    loop = path_refs.oracle_path_sweeps(R.KIND, c["orc"], c["x"], c["V"], c["D"], bt, c["gamma"], c["n_het"], dx=y[:, :, :k], dpath=db[:, :k])
     assert np.abs(loop["dpol"]).max() > 1e-3
     hb = _ctx(hank, c)
     try:
@@ -350,7 +351,7 @@ def test_shock_jacobian_matches_the_oracle(hank, oracle_mod, econ, T):
     c = S.case(econ)
     P, nh = T - 1, c["n_het"]
     x = FR.constant_path(c, P)
-    _, Jb = R.oracle_shock_jacobians(c["orc"], x, c["V"], c["D"], np.full(P, c["args"][3]), c["gamma"], nh)
+    _, Jb = path_refs.jacobians(R.KIND, c["orc"], x, c["V"], c["D"], np.full(P, c["args"][3]), c["gamma"], nh)
     hb = cases.raw_block(hank, c["args"][:6] + (T,) + c["args"][7:], None)
     try:
         hb.set_boundary(c["V"], c["D"])

@@ -1,5 +1,5 @@
 """CPU tests of the income path's references and host layers (no GPU):
-1. tests/income_refs.oracle_income_sweeps — the oracle's EGM step run once per productivity state with the dual transfer
+1. tests/path_refs.oracle_path_sweeps at tests/income_refs.KIND — the oracle's EGM step run once per productivity state with the dual transfer
    (tr_t + y_t[e], dtr_t + dy_t[e]), the columns assembled — against a central difference of ITS OWN level in entries of y_0 and
    y_{P-1} (the step and the agreement of tests/test_shock_host.py: 1e-6, 1e-6 relative);
 2. a path of zeros reproduces sweep_refs.oracle_sweeps exactly;
@@ -15,9 +15,14 @@ import pytest
 
 import cases
 import income_refs as R
+import path_checks as C
+import path_refs
+import shock_refs
 import sweep_refs
-from cases import close, jt
+from cases import close
 from test_shock_host import STEP
+
+K = R.KIND
 
 
 @pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 4), ("hank", "gamma1.5", 33, 2, 4), ("ks", "gamma1", 33, 2, 2),
@@ -30,13 +35,13 @@ def test_the_reference_s_income_tangent_is_the_derivative_of_its_own_level(oracl
     for k, (e, t) in enumerate(entries):
         dy[e, t, k] = 1.0
     args = (c["orc"], c["x"], c["V"], c["D"])
-    ref = R.oracle_income_sweeps(*args, c["y"], dy=dy)
+    ref = path_refs.oracle_path_sweeps(K, *args, c["y"], dpath=dy)
     for k, (e, t) in enumerate(entries):
         lv = []
         for sgn in (1.0, -1.0):
             y = c["y"].copy()
             y[e, t] += sgn * STEP
-            lv.append(R.oracle_income_sweeps(*args, y))
+            lv.append(path_refs.oracle_path_sweeps(K, *args, y))
         what = f"{family} {name} {n_a}x{n_e} T={T} y_{t}[{e}]"
         fd_agg = (lv[0]["agg"] - lv[1]["agg"]) / (2 * STEP)
         fd_pol = (lv[0]["pol"] - lv[1]["pol"]) / (2 * STEP)
@@ -51,44 +56,30 @@ def test_the_reference_s_income_tangent_is_the_derivative_of_its_own_level(oracl
 @pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 4), ("hank", "gamma2", 130, 3, 12)])
 def test_a_path_of_zeros_is_the_oracle_s_own_loop(oracle_mod, family, name, n_a, n_e, T):
     c = R.income_case(family, name, n_a, n_e, T)
-    dx, _ = R.income_seeds(c, 3, 1)
-    ref = R.oracle_income_sweeps(c["orc"], c["x"], c["V"], c["D"], np.zeros_like(c["y"]), dx=dx)
+    dx, _ = path_refs.seeds(K, c, 3, 1)
+    ref = path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], np.zeros_like(c["y"]), dx=dx)
     own = sweep_refs.oracle_sweeps(c["orc"], c["x"], c["V"], c["D"], c["gamma"], 2, y=dx)
     for k in ("agg", "dagg", "agg2", "dagg2", "pol", "dpol"):
         assert np.array_equal(ref[k], own[k]), (family, name, k, np.abs(ref[k] - own[k]).max())
-    moved = R.oracle_income_sweeps(c["orc"], c["x"], c["V"], c["D"], c["y"])
+    moved = path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], c["y"])
     assert np.abs(moved["pol"] - own["pol"]).max() > 1e-3                # (the path moves the policy)
     close(moved["mass"].sum(axis=1), np.ones(T - 1), what="the column masses sum to one")
 
 
 @pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 12), ("hank", "gamma1", 130, 3, 4)])
 def test_the_dense_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, family, name, n_a, n_e, T):
-    """(Jx, Jy) against oracle_income_sweeps with random dx and dy together: the map is linear, so the two agree to rounding (1e-13
+    """(Jx, Jy) against path_refs.oracle_path_sweeps with random dx and dy together: the map is linear, so the two agree to rounding (1e-13
     of the largest entry)"""
     c = R.income_case(family, name, n_a, n_e, T)
-    n_hh, P = c["x"].shape
-    args = (c["orc"], c["x"], c["V"], c["D"], c["y"])
-    Jx, Jy = J = R.oracle_income_jacobians(*args)
-    assert Jx.shape == (2, P, n_hh, P) and Jy.shape == (P, 2, n_e, P)
-    assert R._unit_sweeps(*args)[1] is R._unit_sweeps(*args)[1]                    # (the sweeps ran once)
-    rng = np.random.default_rng(P)
-    dx, dy = rng.standard_normal((n_hh, P, 5)), rng.standard_normal((n_e, P, 5))
-    ref = R.oracle_income_sweeps(*args, dx=dx, dy=dy)
-    lin = R.income_linear(J, dx, dy)
-    for o in range(2):
-        close(lin[:, o, :], ref["dagg"][:, o, :], rel=1e-13, ab=0.0, what=f"{family} {name} output {o}")
+    P = T - 1
+    r = C.dense_pair_reproduces_sweeps(K, c, f"{family} {name}", 1e-13)
     # the budget, aggregated: dC_t + dA'_t - (1 + r_t) d(sum a D_t) = the direct term, the column mass m_t[e] at s = t and nothing else
-    sy = R._unit_sweeps(*args)[1]
+    Jy, sy = r.J[1], path_refs.unit_sweeps(*r.args)[1]
     J2y = sy["dagg2"].reshape(P, P, n_e).transpose(0, 2, 1)                        # [t, e, s]
     direct = Jy[:, 0] + Jy[:, 1] - (1.0 + c["x"][0])[:, None, None] * J2y
     want = np.zeros((P, n_e, P))
     want[np.arange(P), :, np.arange(P)] = sy["mass"]
     close(direct, want, rel=1e-12, ab=0.0, what=f"{family} {name} direct term")
-    yb = rng.standard_normal((P, 2, 4))
-    lhs = np.einsum("tom,ton->mn", yb, lin)
-    rhs = np.einsum("ksm,ksn->mn", jt(Jx, yb), dx) + np.einsum("esm,esn->mn", R.income_y_bar(Jy, yb), dy)
-    scale = np.einsum("tom,ton->mn", np.abs(yb), R.income_linear((np.abs(Jx), np.abs(Jy)), np.abs(dx), np.abs(dy)))
-    assert np.all(np.abs(lhs - rhs) <= 1e-13 * scale), np.max(np.abs(lhs - rhs) / scale)
 
 
 # ---- 7. the conditions of tests/test_gpu_income_geometry.py -----------------------------------------------------------------------------
@@ -100,9 +91,9 @@ def test_the_raw_grids_keep_their_edges_under_an_income_path(oracle_mod, name):
     c = R.geometry_case("raw", name)
     n_e, P = c["y"].shape
     assert P == cases.EDGE_P and c["n_het"] == 2 and "path" not in c
-    _, sy = R._unit_sweeps(c["orc"], c["x"], c["V"], c["D"], c["y"])
+    _, sy = path_refs.unit_sweeps(K, c["orc"], c["x"], c["V"], c["D"], c["y"])
     assert np.all(np.isfinite(sy["pol"])) and sy["dpol"].shape == sy["pol"].shape + (n_e * P,)
-    R.check_income_edges(name, c["grid"], sy["pol"])
+    shock_refs.check_path_edges(name, c["grid"], sy["pol"])
     clamped = sy["pol"] <= c["grid"][0]
     assert clamped.any(axis=1).any(), name
     assert not np.any(sy["dpol"][clamped]), name
@@ -114,19 +105,19 @@ GRID_PAIR_ECONOMIES = [("shape", 65, 3, 12), ("shape", 40, 16, 10), ("shape", 40
 
 @pytest.mark.parametrize("econ", GRID_PAIR_ECONOMIES, ids=lambda e: "-".join(str(q) for q in e))
 def test_the_grid_aggregate_s_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, econ):
-    """(J2x, J2y) against oracle_income_sweeps' dagg2 with random dx and dy together (1e-13 of the largest entry)"""
+    """(J2x, J2y) against path_refs.oracle_path_sweeps' dagg2 with random dx and dy together (1e-13 of the largest entry)"""
     c = R.geometry_case(*econ)
     n_hh, P = c["x"].shape
     n_e = c["y"].shape[0]
-    args = (c["orc"], c["x"], c["V"], c["D"], c["y"])
-    J2x, J2y = J2 = R.oracle_income_grid_jacobians(*args)
+    args = (K, c["orc"], c["x"], c["V"], c["D"], c["y"])
+    J2x, J2y = J2 = path_refs.grid_jacobians(*args)
     assert J2x.shape == (P, n_hh, P) and J2y.shape == (P, n_e, P)
     rng = np.random.default_rng(P + n_e)
     dx, dy = rng.standard_normal((n_hh, P, 5)), rng.standard_normal((n_e, P, 5))
-    ref = R.oracle_income_sweeps(*args, dx=dx, dy=dy)
-    close(R.income_grid_linear(J2, dx, dy), ref["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate")
-    close(R.income_grid_linear(J2, None, dy), R.oracle_income_sweeps(*args, dy=dy)["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate, y alone")
-    assert np.abs(J2y).max() > 2e-2 and min(np.abs(R.oracle_income_jacobians(*args)[1][:, o]).max() for o in range(2)) > 2e-2
+    ref = path_refs.oracle_path_sweeps(*args, dx=dx, dpath=dy)
+    close(path_refs.grid_linear(J2, dx, dy), ref["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate")
+    close(path_refs.grid_linear(J2, None, dy), path_refs.oracle_path_sweeps(*args, dpath=dy)["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate, y alone")
+    assert np.abs(J2y).max() > 2e-2 and min(np.abs(path_refs.jacobians(*args)[1][:, o]).max() for o in range(2)) > 2e-2
 
 
 @pytest.mark.parametrize("n_e", [1, 16])
@@ -139,13 +130,13 @@ def test_the_reference_at_one_and_at_sixteen_states_is_the_derivative_of_its_own
     for k, (e, t) in enumerate(entries):
         dy[e, t, k] = 1.0
     args = (c["orc"], c["x"], c["V"], c["D"])
-    ref = R.oracle_income_sweeps(*args, c["y"], dy=dy)
+    ref = path_refs.oracle_path_sweeps(K, *args, c["y"], dpath=dy)
     for k, (e, t) in enumerate(entries):
         lv = []
         for sgn in (1.0, -1.0):
             y = c["y"].copy()
             y[e, t] += sgn * STEP
-            lv.append(R.oracle_income_sweeps(*args, y))
+            lv.append(path_refs.oracle_path_sweeps(K, *args, y))
         what = f"40x{n_e} T=4 y_{t}[{e}]"
         fd_agg = (lv[0]["agg"] - lv[1]["agg"]) / (2 * STEP)
         fd_pol = (lv[0]["pol"] - lv[1]["pol"]) / (2 * STEP)
@@ -161,15 +152,15 @@ def test_the_column_masses_follow_the_initial_distribution_and_not_the_inputs(or
     whose column masses differ (measured: 0.16). Section F.4 of the GPU module tells a stale m_t[e] from a fresh one by this."""
     c = R.geometry_case("shape", 65, 3, 12)
     args = (c["orc"], c["x"], c["V"])
-    mass = R.oracle_income_sweeps(*args, c["D"], c["y"])["mass"]
+    mass = path_refs.oracle_path_sweeps(K, *args, c["D"], c["y"])["mass"]
     close(mass.sum(axis=1), np.ones(11), what="the column masses sum to one")
-    moved_x = R.oracle_income_sweeps(c["orc"], c["x"] * np.array([[1.3], [0.97]]), c["V"], c["D"], c["y"])
-    assert np.abs(moved_x["pol"] - R.oracle_income_sweeps(*args, c["D"], c["y"])["pol"]).max() > 1e-3
+    moved_x = path_refs.oracle_path_sweeps(K, c["orc"], c["x"] * np.array([[1.3], [0.97]]), c["V"], c["D"], c["y"])
+    assert np.abs(moved_x["pol"] - path_refs.oracle_path_sweeps(K, *args, c["D"], c["y"])["pol"]).max() > 1e-3
     print(f"column masses under another x: max move {np.abs(moved_x['mass'] - mass).max():.3e}")
     assert np.abs(moved_x["mass"] - mass).max() <= 1e-14
     D2 = R.rescaled_D0(c)
     assert D2.shape == c["D"].shape and abs(D2.sum() - 1.0) <= 1e-15
-    mass2 = R.oracle_income_sweeps(*args, D2, c["y"])["mass"]
+    mass2 = path_refs.oracle_path_sweeps(K, *args, D2, c["y"])["mass"]
     print(f"column masses under the rescaled D_0: max move {np.abs(mass2 - mass).max():.3e}")
     assert np.abs(mass2 - mass).max() > 0.1
 
@@ -248,22 +239,7 @@ def test_the_z_path_s_tangent_is_the_derivative_of_its_income_and_the_incidence_
 
 
 def test_income_jacobian_is_the_toeplitz_recursion_per_output_and_state(hank):
-    from hank_amd.SteadyStateJacobian import household_jacobian, income_jacobian
-    rng = np.random.default_rng(4)
-    P, n_e, nh = 6, 3, 2
-    F, Dv = rng.standard_normal((P, P, n_e, nh)), rng.standard_normal((P, n_e, nh))
-    stub = R.StubIncomeBlock(F, Dv)
-    J = income_jacobian(stub, nh)
-    assert J.shape == (nh, P, n_e, P) and stub.calls == 1
-    for o in range(nh):
-        for e in range(n_e):
-            want = np.empty((P, P))
-            for t in range(P):
-                for s in range(P):
-                    want[t, s] = F[t, s, e, o] + (want[t - 1, s - 1] if t > 0 and s > 0 else (Dv[s, e, o] if t == 0 else 0.0))
-            assert np.allclose(J[o, :, e, :], want, rtol=0, atol=1e-14)
-        assert np.array_equal(J[o], household_jacobian(F[..., o], Dv[..., o]).transpose(1, 0, 2))
-    assert income_jacobian(stub, 1).shape == (1, P, n_e, P)
+    C.jacobian_is_the_toeplitz_recursion(hank, K, (3,), 2, 1)
 
 
 def test_the_example_parses_the_redistribution():

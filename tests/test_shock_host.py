@@ -1,8 +1,8 @@
 """CPU tests of the discount-factor path's references and host layers (no GPU):
-1. tests/shock_refs.oracle_shock_sweeps — the oracle loop with beta = beta_t and the value's partials augmented by V dbeta_t / beta_t —
+1. tests/path_refs.oracle_path_sweeps at tests/shock_refs.KIND — the oracle loop with beta = beta_t and the value's partials augmented by V dbeta_t / beta_t —
    against a central difference of ITS OWN level in the entries beta_0 and beta_{P-1} (step 1e-6, agreement 1e-6 relative): the
    construction the GPU tests compare with is pinned without a device;
-2. tests/shock_refs.oracle_shock_jacobians — the dense pair every width of tests/test_gpu_shock_geometry.py is compared with — against
+2. tests/path_refs.jacobians at tests/shock_refs.KIND — the dense pair every width of tests/test_gpu_shock_geometry.py is compared with — against
    the sweeps with random seeds in the inputs and in beta together, and the raw grids' edges on the oracle's policy under a path;
 3. SteadyStateJacobian.shock_jacobian's recursion on a stand-in block;
 4. examples/solve_hank.py's arguments."""
@@ -10,10 +10,13 @@ import numpy as np
 import pytest
 
 import cases
+import path_checks as C
+import path_refs
 import shock_refs as R
-from cases import close, jt
+from cases import close
 
 STEP = 1e-6
+K = R.KIND
 
 
 @pytest.mark.parametrize("family,name,n_a,n_e,T", [("ks", "gamma2", 33, 2, 4), ("hank", "gamma1.5", 33, 2, 4), ("ks", "gamma1", 33, 2, 2),
@@ -25,14 +28,14 @@ def test_the_reference_s_beta_tangent_is_the_derivative_of_its_own_level(oracle_
     dbeta = np.zeros((P, len(entries)))
     for k, t in enumerate(entries):
         dbeta[t, k] = 1.0
-    ref = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], nh, dbeta=dbeta)
+    ref = path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], nh, dpath=dbeta)
     assert c["orc"].m.beta == c["beta"]                          # the oracle's own beta is restored
     for k, t in enumerate(entries):
         lv = []
         for sgn in (1.0, -1.0):
             b = c["path"].copy()
             b[t] += sgn * STEP
-            lv.append(R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], b, c["gamma"], nh))
+            lv.append(path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], b, c["gamma"], nh))
         what = f"{family} {name} {n_a}x{n_e} T={T} beta_{t}"
         fd_agg = (lv[0]["agg"] - lv[1]["agg"]) / (2 * STEP)
         fd_pol = (lv[0]["pol"] - lv[1]["pol"]) / (2 * STEP)
@@ -46,7 +49,7 @@ def test_the_reference_s_beta_tangent_is_the_derivative_of_its_own_level(oracle_
 
 def test_a_constant_path_is_the_oracle_s_own_block(oracle_mod):
     c = R.shock_case("ks", "gamma2", 33, 2, 4)
-    ref = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], np.full(3, c["beta"]), c["gamma"], 3)
+    ref = path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], np.full(3, c["beta"]), c["gamma"], 3)
     agg, _, pol, _ = c["orc"].block(c["x"], None, c["V"], c["D"])
     close(ref["agg"][:, 0], agg, what="constant path: aggregate")
     close(ref["pol"], pol, what="constant path: policy")
@@ -57,28 +60,12 @@ LINEAR_ECONOMIES = [("shape", 65, 3, 12), ("shape", 40, 11, 10), ("shape", 40, 1
 
 @pytest.mark.parametrize("econ", LINEAR_ECONOMIES, ids=lambda e: "-".join(str(q) for q in e))
 def test_the_dense_pair_reproduces_the_sweeps_with_both_seeds(oracle_mod, econ):
-    """oracle_shock_jacobians' (Jx, Jb) — and the grid aggregate's pair — against oracle_shock_sweeps with random y and dbeta together:
+    """path_refs.jacobians' (Jx, Jb) — and the grid aggregate's pair — against path_refs.oracle_path_sweeps with random y and dbeta together:
     the map is linear, so the two agree to rounding (1e-13 of the largest entry; measured <= 1.2e-15)"""
     c = R.geometry_case(*econ)
-    n_hh, P = c["x"].shape
-    ref_args = (c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], c["n_het"])
-    Jx, Jb = J = R.oracle_shock_jacobians(*ref_args)
-    assert Jx.shape == (c["n_het"], P, n_hh, P) and Jb.shape == (P, c["n_het"], P)
-    assert R.oracle_shock_jacobians(*ref_args)[1] is Jb                            # (the sweeps ran once)
-    rng = np.random.default_rng(P)
-    y, db = rng.standard_normal((n_hh, P, 5)), rng.standard_normal((P, 5))
-    ref = R.oracle_shock_sweeps(*ref_args, y=y, dbeta=db)
-    lin = R.shock_linear(J, y, db)
-    for o in range(c["n_het"]):
-        close(lin[:, o, :], ref["dagg"][:, o, :], rel=1e-13, ab=0.0, what=f"{econ} output {o}")
-    J2x, J2b = R.oracle_shock_grid_jacobians(*ref_args)
-    close(np.einsum("tks,ksn->tn", J2x, y) + J2b @ db, ref["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate")
-    # the cotangent formulas are the transposes of the same pair
-    yb = rng.standard_normal((P, c["n_het"], 4))
-    lhs = np.einsum("tom,ton->mn", yb, lin)
-    rhs = np.einsum("ksm,ksn->mn", jt(Jx, yb), y) + R.shock_beta_bar(Jb, yb).T @ db
-    scale = np.einsum("tom,ton->mn", np.abs(yb), R.shock_linear((np.abs(Jx), np.abs(Jb)), np.abs(y), np.abs(db)))
-    assert np.all(np.abs(lhs - rhs) <= 1e-13 * scale), np.max(np.abs(lhs - rhs) / scale)
+    r = C.dense_pair_reproduces_sweeps(K, c, f"{econ}", 1e-13)
+    J2x, J2b = path_refs.grid_jacobians(*r.args)
+    close(np.einsum("tks,ksn->tn", J2x, r.dx) + J2b @ r.dp, r.ref["dagg2"], rel=1e-13, ab=0.0, what=f"{econ} grid aggregate")
 
 
 @pytest.mark.parametrize("name", R.EDGE_ECONOMIES)
@@ -89,27 +76,13 @@ def test_the_raw_grids_keep_their_edges_under_a_path(oracle_mod, name):
     target row)"""
     c = R.geometry_case("raw", name)
     assert c["path"].shape == (cases.EDGE_P,)
-    pol = R.oracle_shock_sweeps(c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], c["n_het"])["pol"]
+    pol = path_refs.oracle_path_sweeps(K, c["orc"], c["x"], c["V"], c["D"], c["path"], c["gamma"], c["n_het"])["pol"]
     assert np.all(np.isfinite(pol))
     R.check_path_edges(name, c["grid"], pol)
 
 
 def test_shock_jacobian_is_the_toeplitz_recursion_per_output(hank):
-    from hank_amd.SteadyStateJacobian import household_jacobian, shock_jacobian
-    rng = np.random.default_rng(4)
-    P, nh = 6, 3
-    F, Dv = rng.standard_normal((P, P, nh)), rng.standard_normal((P, nh))
-    stub = R.StubShockBlock(F, Dv)
-    J = shock_jacobian(stub, nh)
-    assert J.shape == (nh, P, P) and stub.calls == 1
-    for o in range(nh):
-        want = np.empty((P, P))
-        for t in range(P):
-            for s in range(P):
-                want[t, s] = F[t, s, o] + (want[t - 1, s - 1] if t > 0 and s > 0 else (Dv[s, o] if t == 0 else 0.0))
-        assert np.allclose(J[o], want, rtol=0, atol=1e-14)
-        assert np.array_equal(J[o], household_jacobian(F[..., o:o + 1], Dv[..., o:o + 1])[0])
-    assert shock_jacobian(stub, 2).shape == (2, P, P)
+    C.jacobian_is_the_toeplitz_recursion(hank, K, (), 3, 2)
 
 
 def test_the_example_parses_the_discount_shock():
